@@ -8,16 +8,20 @@ A "step" is one TensorVMSplit.forward over one 4096-ray batch already resident i
 For N>1 every rank renders its own 4096-ray shard of an N*4096 batch (weak scaling, no
 collective on the forward path); value = N*4096*K / max-over-ranks time.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+K is the number of timed steps of the headline forward and of the training step.  --dump-outputs DIR writes what the
+last timed forward step returned (rgb [4096,3], depth [4096], float32) as DIR/rgb.npy and DIR/depth.npy (rank r > 0 of
+an N-rank run: DIR/rgb_rank<r>.npy, ...).  The field and the rays are seeded, so two builds given the same arguments
+render the same inputs and their dumps compare output for output.
 
 Prints ONE JSON line on rank 0 (see the task contract) with
   roofline      the dominant kernel: HIP-event time on the launch stream, algorithmic bytes (or flops) per
                 launch, HBM-side traffic from rocprofv3 --pmc passes of THIS run (child processes; falls back
                 to the committed profiles/ summary and says so), plus what the counters say binds it:
                 l2_frac / mfma_frac / hbm_frac and the per-kernel table
-  cpu_baseline  the reference's TensorVMSplit itself on the host cores when /root/reference is importable
-                ("reference"), else oracle/vm_render_torch.py, its ATen op chain ("port", with the reason)
+  cpu_baseline  oracle/vm_render_torch.py, the reference's ATen op chain ("port"), on the host cores
   train_step    forward with a graph + backward + (N>1) the gradient all-reduce over RCCL + FusedAdam, on every
                 N -- the design's only collective is inside this timed region
   workloads     N=1 only: the exact-fp32 colour engine, a trained-like scene (walls + rebuilt alpha mask:
@@ -58,9 +62,6 @@ FIELD_KW = dict(density_n_comp=[8, 8, 8], appearance_n_comp=[24, 24, 24], app_di
                 alphaMask_thres=1e-4, distance_scale=25, rayMarch_weight_thres=1e-3,
                 pos_pe=0, view_pe=0, fea_pe=0, featureC=128, step_ratio=0.5,
                 fea2denseAct="softplus")
-REF = "/root/reference/localTensoRF"
-
-
 def make_rays(R, seed):
     g = torch.Generator().manual_seed(seed)
     o = 0.05 * torch.randn(R, 3, generator=g)
@@ -69,49 +70,13 @@ def make_rays(R, seed):
 
 
 # ------------------------------------------------------------------------------ baselines
-def import_reference():
-    """The reference's own TensorVMSplit (read-only import; five third-party modules it never calls on
-    this path are stubbed, as tests/golden/make_golden.py does).  None + reason where it does not exist
-    (the GPU box has no /root/reference)."""
-    if not os.path.isdir(REF):
-        return None, f"{REF} is not present on this box (it exists only in the build container)"
-    import types
-    try:
-        for name, attrs in (("kornia", {"create_meshgrid": None}), ("cv2", {"COLORMAP_JET": 2}), ("torchvision", {}),
-                            ("torchvision.transforms", {}), ("plyfile", {}), ("skimage", {}), ("skimage.measure", {})):
-            if name not in sys.modules:
-                m = types.ModuleType(name)
-                m.__dict__.update(attrs)
-                sys.modules[name] = m
-        if REF not in sys.path:
-            sys.path.insert(0, REF)
-        from models.tensoRF import TensorVMSplit as RefVM
-        return RefVM, None
-    except Exception as e:                                   # noqa: BLE001
-        return None, f"import of the reference failed: {e!r}"
-
-
-def _ref_field(RefVM, sd, device):
-    with contextlib.redirect_stdout(io.StringIO()):
-        aabb = 2 * torch.tensor([[-1.0, -1, -1], [1, 1, 1]])
-        f = RefVM(device, aabb.to(device), [GRID] * 3, **FIELD_KW)
-    f.load_state_dict({k: v.to(device) for k, v in sd.items()})
-    return f.to(device)
-
-
 def cpu_baseline(field_sd, rays_cpu, runs=3):
-    """The reference on the host cores: its own module when importable, else its ATen op chain."""
-    RefVM, why = import_reference()
+    """The reference path on the host cores: its ATen op chain (oracle/vm_render_torch.py)."""
+    from oracle import vm_render_torch as ot
     sd = {k: v.detach().cpu() for k, v in field_sd.items()}
-    if RefVM is not None:
-        f = _ref_field(RefVM, sd, "cpu")
-        fn = lambda r: f(r, white_bg=True, is_train=False, N_samples=N_SAMPLES_ARG)          # noqa: E731
-        kind, what = "reference", "localTensoRF/models/tensoRF.py TensorVMSplit.forward (the real reference module)"
-    else:
-        from oracle import vm_render_torch as ot
-        z = ot.z_schedule(N_SAMPLES_ARG)
-        fn = lambda r: ot.render_field(sd, r, z)                                             # noqa: E731
-        kind, what = "port", "oracle/vm_render_torch.py (F.grid_sample/cumprod/Linear, pinned to the reference goldens)"
+    z = ot.z_schedule(N_SAMPLES_ARG)
+    fn = lambda r: ot.render_field(sd, r, z)                                                 # noqa: E731
+    kind, what = "port", "oracle/vm_render_torch.py (F.grid_sample/cumprod/Linear, pinned to the reference goldens)"
     with torch.no_grad():
         fn(rays_cpu[:512])                                            # warm-up
         t0 = time.perf_counter()
@@ -120,24 +85,16 @@ def cpu_baseline(field_sd, rays_cpu, runs=3):
         dt = (time.perf_counter() - t0) / runs
     out = {"value": rays_cpu.shape[0] / dt, "unit": "rays/s", "cores": torch.get_num_threads(), "kind": kind,
            "sample": f"{runs} x {rays_cpu.shape[0]} rays x 512 samples on the 300^3 field, {what}, {dt * 1e3:.0f} ms/batch"}
-    if why:
-        out["why_port"] = why
     return out
 
 
 def torch_rocm_baseline(field_sd, rays, iters=5):
-    """The reference path under stock PyTorch-ROCm on this GPU: denominator of the >=10x target."""
-    RefVM, why = import_reference()
-    if RefVM is not None:
-        f = _ref_field(RefVM, {k: v.detach() for k, v in field_sd.items()}, rays.device)
-        fn = lambda: f(rays, white_bg=True, is_train=False, N_samples=N_SAMPLES_ARG)         # noqa: E731
-        kind = "reference"
-    else:
-        from oracle import vm_render_torch as ot
-        fld = {k: v.detach() for k, v in field_sd.items()}
-        z = ot.z_schedule(N_SAMPLES_ARG, device=rays.device)
-        fn = lambda: ot.render_field(fld, rays, z)                                           # noqa: E731
-        kind = "port"
+    """The reference path (its ATen op chain, oracle/vm_render_torch.py) under stock PyTorch-ROCm on this GPU:
+    denominator of the >=10x target."""
+    from oracle import vm_render_torch as ot
+    fld = {k: v.detach() for k, v in field_sd.items()}
+    z = ot.z_schedule(N_SAMPLES_ARG, device=rays.device)
+    fn = lambda: ot.render_field(fld, rays, z)                                               # noqa: E731
     with torch.no_grad():
         for _ in range(2):
             fn()
@@ -147,33 +104,22 @@ def torch_rocm_baseline(field_sd, rays, iters=5):
             fn()
         torch.cuda.synchronize()
         dt = (time.perf_counter() - t0) / iters
-    out = {"value": rays.shape[0] / dt, "unit": "rays/s", "ms_per_step": dt * 1e3, "kind": kind,
-           "what": "the reference module on cuda:0" if kind == "reference" else
-                   "oracle/vm_render_torch.py on cuda:0 (the reference's ATen op chain under PyTorch-ROCm, fp32)"}
-    if why:
-        out["why_port"] = why
+    out = {"value": rays.shape[0] / dt, "unit": "rays/s", "ms_per_step": dt * 1e3, "kind": "port",
+           "what": "oracle/vm_render_torch.py on cuda:0 (the reference's ATen op chain under PyTorch-ROCm, fp32)"}
     return out
 
 
 def torch_rocm_train_baseline(field_sd, rays, g_rgb, g_depth, iters=3):
     """One training step (forward with a graph + backward + Adam) of the reference path under stock PyTorch-ROCm on this GPU:
-    the reference module when importable, else its ATen op chain -- same batch, same loss, same optimiser groups."""
-    RefVM, why = import_reference()
-    if RefVM is not None:
-        f = _ref_field(RefVM, {k: v.detach() for k, v in field_sd.items()}, rays.device)
-        opt = torch.optim.Adam(f.get_optparam_groups(0.02, 1e-3), betas=(0.9, 0.99))
-        render = lambda: f(rays, white_bg=True, is_train=True, N_samples=N_SAMPLES_ARG)      # noqa: E731
-        kind = "reference"
-    else:
-        from oracle import vm_render_torch as ot
-        fld = {k: v.detach().clone() for k, v in field_sd.items()}
-        leaves = [k for k in fld if fld[k].dtype.is_floating_point and ("plane" in k or "line" in k or "basis" in k or "renderModule" in k)]
-        for k in leaves:
-            fld[k].requires_grad_(True)
-        opt = torch.optim.Adam([fld[k] for k in leaves], lr=0.02, betas=(0.9, 0.99))
-        z = ot.z_schedule(N_SAMPLES_ARG, device=rays.device)
-        render = lambda: ot.render_field(fld, rays, z)                                       # noqa: E731
-        kind = "port"
+    its ATen op chain -- same batch, same loss, same optimiser groups."""
+    from oracle import vm_render_torch as ot
+    fld = {k: v.detach().clone() for k, v in field_sd.items()}
+    leaves = [k for k in fld if fld[k].dtype.is_floating_point and ("plane" in k or "line" in k or "basis" in k or "renderModule" in k)]
+    for k in leaves:
+        fld[k].requires_grad_(True)
+    opt = torch.optim.Adam([fld[k] for k in leaves], lr=0.02, betas=(0.9, 0.99))
+    z = ot.z_schedule(N_SAMPLES_ARG, device=rays.device)
+    render = lambda: ot.render_field(fld, rays, z)                                           # noqa: E731
 
     def step():
         opt.zero_grad(set_to_none=True)
@@ -187,11 +133,9 @@ def torch_rocm_train_baseline(field_sd, rays, g_rgb, g_depth, iters=3):
         step()
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / iters
-    out = {"ms_per_step": dt * 1e3, "rays_per_s": rays.shape[0] / dt, "kind": kind,
-           "what": ("the reference module" if kind == "reference" else "oracle/vm_render_torch.py (the reference's ATen op chain)")
-                   + " on cuda:0: forward with a graph + autograd backward + torch.optim.Adam, fp32, 4096 rays x 512 samples"}
-    if why:
-        out["why_port"] = why
+    out = {"ms_per_step": dt * 1e3, "rays_per_s": rays.shape[0] / dt, "kind": "port",
+           "what": "oracle/vm_render_torch.py (the reference's ATen op chain) on cuda:0: forward with a graph + autograd "
+                   "backward + torch.optim.Adam, fp32, 4096 rays x 512 samples"}
     return out
 
 
@@ -312,6 +256,13 @@ def geometric_losses_workload(dev, V=16, n=256, Fr=20, W=640, H=480, iters=100):
 
 
 # ------------------------------------------------------------------------------ measurement helpers
+def dump_outputs(d, arrays, suffix=""):
+    """--dump-outputs: each tensor as d/<name><suffix>.npy, float32 (these are 64 KB in all)."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(d, f"{name}{suffix}.npy"), t.detach().float().cpu().numpy())
+
 def timed(fn, steps, warmup, sync):
     for _ in range(warmup):
         fn()
@@ -514,8 +465,11 @@ def config3_scene(dev):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)        # what the driver runs
+    ap.add_argument("--steps", type=int, default=20,        # what the driver runs
+                    help="timed steps of the headline forward and of the training step")
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed forward step returned as DIR/rgb.npy and DIR/depth.npy (float32)")
     ap.add_argument("--no-baselines", action="store_true", help="skip the CPU / torch-ROCm baselines and extra workloads")
     ap.add_argument("--backend", choices=("nccl", "gloo"), default="nccl",
                     help="process-group backend for N > 1: nccl = RCCL over xGMI (one GPU per rank); gloo = host-staged, ranks may share a GPU (launch test)")
@@ -528,6 +482,8 @@ def main():
     ap.add_argument("--grid", type=int, default=GRID, help="(internal, with --child) grid size of the profiled workload")
     ap.add_argument("--n-samples", type=int, default=N_SAMPLES_ARG, help="(internal, with --child) N_samples argument (-1 = the grid's default)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if not args.child and (args.grid != GRID or args.n_samples != N_SAMPLES_ARG):
         raise SystemExit("--grid / --n-samples are for the PMC child runs; the headline workload is BASELINE configs[1]")
     grid, ns_arg = args.grid, args.n_samples
@@ -535,8 +491,8 @@ def main():
         args.preroll_ms = min(args.preroll_ms, 150.0)
 
     if args.gpus > 1 and "RANK" not in os.environ:
-        # `python bench.py --gpus N` on its own: become the launcher the driver would have used -- one rank per GPU under
-        # torch.distributed.run, same arguments (rank 0 prints the JSON line)
+        # `python bench.py --gpus N` on its own: run the launcher the driver would have used -- one rank per GPU under
+        # torch.distributed.run, same arguments (rank 0 prints the JSON line) -- as a child process, and exit with its status
         import socket
         with socket.socket() as s_:
             s_.bind(("127.0.0.1", 0))
@@ -545,7 +501,7 @@ def main():
                "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
         sys.stdout.flush()
         os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-        os.execv(sys.executable, cmd)
+        raise SystemExit(subprocess.call(cmd))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -604,6 +560,11 @@ def main():
     def fwd():
         return field(rays, white_bg=True, is_train=False, N_samples=ns_arg)
 
+    last = {}
+
+    def fwd_kept():                                           # the timed step; keeps what it returned for --dump-outputs
+        last["out"] = fwd()
+
     with torch.no_grad():
         # clock ramp: the first second of work after an idle period runs at a lower GPU clock; render untimed
         # for --preroll-ms before the W warm-up steps so that K is measured at the sustained clock
@@ -612,9 +573,12 @@ def main():
             for _ in range(20):
                 fwd()
             torch.cuda.synchronize(dev)
-        dt = timed(fwd, args.steps, args.warmup, sync) if args.child != "train" else 1.0
+        dt = timed(fwd_kept, args.steps, args.warmup, sync) if args.child != "train" else 1.0
     if args.child == "fwd":
         return
+    if args.dump_outputs and not args.child:
+        dump_outputs(args.dump_outputs, dict(zip(("rgb", "depth"), last["out"])), f"_rank{rank}" if rank else "")
+    del last
     def max_over_ranks(vals):
         t = torch.tensor(vals, dtype=torch.float64, device=dev if args.backend == "nccl" else "cpu")
         if ddp:
@@ -642,7 +606,7 @@ def main():
         if ddp and comm[0]:
             reduced[0] = allreduce_grads(field, stats=comm_stats)
         opt.step()
-    t_steps = max(5, min(args.steps, 20))
+    t_steps = args.steps
     dtt_nocomm = None
     if ddp:                                                  # the same step without the collectives: what the exchange costs on this N
         comm[0] = False

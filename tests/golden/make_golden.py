@@ -7,6 +7,7 @@ The reference needs five third-party modules it never calls on this path
 Recorded with: see `meta` in each file (torch version, seeds).
 """
 import contextlib
+import hashlib
 import io
 import os
 import sys
@@ -798,6 +799,61 @@ def case_trajectory(TensorVMSplit, LocalTensorfs, name, seed=91):
     save(name, **arrs)
 
 
+def tensor_digest(t):
+    """[dtype, shape, sha256 of the bytes] of a tensor: bit-for-bit identity without storing the tensor (tests/util.py has
+    the same function)."""
+    a = np.ascontiguousarray(t.detach().cpu().numpy())
+    return [str(a.dtype), list(a.shape), hashlib.sha256(a.tobytes()).hexdigest()]
+
+
+def case_dropin(TensorVMSplit, LocalTensorfs, name):
+    """What tests/test_dropin_hybrid.py compares the native classes against: the reference's LocalTensorfs taken through
+    append_frame x 3 + append_rf(3) on CPU (its whole state afterwards, its kwargs, the blending-weight shape), the
+    optimiser groups / state-dict keys / kwargs of a seeded TensorVMSplit, the public members of the class and
+    get_arange(1), and the seeded state dicts of three non-default colour networks (opt.py:148-157).  The tensors are
+    seeded initialisations that the native classes must reproduce bit for bit, so each is stored as its digest."""
+    import json
+    aabb = 2 * torch.tensor([[-1.0, -1, -1], [1, 1, 1]])
+    arrs, digests, keys = {}, {}, {}
+    torch.manual_seed(7)
+    lt = quiet(LocalTensorfs, fov=85.6, n_init_frames=5, n_overlap=3, WH=(32, 24), n_iters_per_frame=600,
+               n_iters_reg=100, lr_R_init=5e-3, lr_t_init=5e-4, lr_i_init=1e-3, lr_exposure_init=1e-3, rf_lr_init=0.02,
+               rf_lr_basis=1e-3, lr_decay_target_ratio=0.1, N_voxel_list={}, update_AlphaMask_list=[],
+               camera_prior=None, device="cpu", lr_upsample_reset=True, aabb=aabb, gridSize=[12, 12, 10], **FIELD_KW)
+    for _ in range(3):
+        quiet(lt.append_frame)
+    quiet(lt.append_rf, 3)
+    sd = lt.state_dict()
+    keys["scene"] = list(sd)
+    digests.update({f"scene/{k}": tensor_digest(v) for k, v in sd.items()})
+    arrs["scene_kwargs"] = np.array(json.dumps({k: str(v) for k, v in lt.get_kwargs().items()}))
+    arrs["scene_blend_shape"] = np.array(lt.blending_weights.shape)
+    torch.manual_seed(3)
+    f = quiet(TensorVMSplit, "cpu", aabb, [12, 14, 10], **FIELD_KW)
+    groups = [(g["lr"], list(g["params"])) for g in f.get_optparam_groups(0.02, 1e-3)]   # some groups hold generators
+    arrs["groups_lr"] = np.array([lr for lr, _ in groups])
+    arrs["groups_n"] = np.array([len(ps) for _, ps in groups])
+    for i, (_, ps) in enumerate(groups):
+        for j, p in enumerate(ps):
+            digests[f"group{i}/{j}"] = tensor_digest(p)
+    keys["field"] = list(f.state_dict())
+    arrs["field_kwargs"] = np.array(json.dumps({k: str(v) for k, v in f.get_kwargs().items()}))
+    torch.manual_seed(5)
+    f = quiet(TensorVMSplit, "cpu", aabb, [8, 8, 8], **FIELD_KW)
+    keys["members"] = [n for n in dir(f) if not n.startswith("_")]
+    arrs["get_arange_1"] = f.get_arange(1).numpy()
+    for i, cfg in enumerate((dict(view_pe=2, fea_pe=2, featureC=64), dict(view_pe=6, fea_pe=0, featureC=128),
+                             dict(view_pe=0, fea_pe=6, featureC=256))):
+        torch.manual_seed(9)
+        f = quiet(TensorVMSplit, "cpu", aabb, [10, 12, 8], **dict(FIELD_KW, **cfg))
+        sd = f.state_dict()
+        keys[f"pe{i}"] = list(sd)
+        digests.update({f"pe{i}/{k}": tensor_digest(v) for k, v in sd.items()})
+    arrs["keys"] = np.array(json.dumps(keys))
+    arrs["digests"] = np.array(json.dumps(digests))
+    save(name, **arrs)
+
+
 def main():
     TensorVMSplit, AlphaGridMask, LocalTensorfs = import_reference()
     only = set(sys.argv[1:])
@@ -819,7 +875,8 @@ def main():
               "ladder": lambda: case_ladder(TensorVMSplit, "ladder_64_to_640.npz"),
               "pe": lambda: (case_pe(TensorVMSplit, "field_pe_2_3_64.npz", (20, 24, 28), 64, 96, 101, fea_pe=2, view_pe=3, featureC=64),
                              case_pe(TensorVMSplit, "field_pe_0_2_128.npz", (24, 20, 22), 48, 96, 103, fea_pe=0, view_pe=2, featureC=128),
-                             case_pe(TensorVMSplit, "field_pe_6_6_200.npz", (16, 18, 20), 32, 60, 105, fea_pe=6, view_pe=6, featureC=200))}
+                             case_pe(TensorVMSplit, "field_pe_6_6_200.npz", (16, 18, 20), 32, 60, 105, fea_pe=6, view_pe=6, featureC=200)),
+              "dropin": lambda: case_dropin(TensorVMSplit, LocalTensorfs, "dropin_reference_classes.npz")}
         for k in only:
             r2[k]()
         return
@@ -859,6 +916,8 @@ def main():
     case_pe(TensorVMSplit, "field_pe_2_3_64.npz", (20, 24, 28), 64, 96, 101, fea_pe=2, view_pe=3, featureC=64)
     case_pe(TensorVMSplit, "field_pe_0_2_128.npz", (24, 20, 22), 48, 96, 103, fea_pe=0, view_pe=2, featureC=128)
     case_pe(TensorVMSplit, "field_pe_6_6_200.npz", (16, 18, 20), 32, 60, 105, fea_pe=6, view_pe=6, featureC=200)
+    # what the drop-in tests compare the native classes against (the reference's scene lifecycle, class members, seeded state)
+    case_dropin(TensorVMSplit, LocalTensorfs, "dropin_reference_classes.npz")
 
 
 if __name__ == "__main__":

@@ -1,5 +1,6 @@
 """Shared helpers for the tests: golden loading and field construction."""
 import contextlib
+import hashlib
 import io
 import os
 
@@ -64,6 +65,13 @@ def rel_err(a, b, floor=1e-3):
     a = np.asarray(a, np.float64)
     b = np.asarray(b, np.float64)
     return float((np.abs(a - b) / np.maximum(np.abs(b), floor)).max())
+
+
+def tensor_digest(t):
+    """[dtype, shape, sha256 of the bytes] of a tensor, as tests/golden/make_golden.py::tensor_digest records it: equal
+    digests are equal tensors, bit for bit."""
+    a = np.ascontiguousarray(t.detach().cpu().numpy())
+    return [str(a.dtype), list(a.shape), hashlib.sha256(a.tobytes()).hexdigest()]
 
 
 def quiet(fn, *a, **k):
