@@ -49,7 +49,19 @@ extern "C" {
 #define LRF_FLAG_PLANE_EVENTS 128u /* lrf_render_bwd only (data parallel): the appearance scatter runs as one pass per plane and records an
                                   * event behind planes 0 and 1 (lrf_render_bwd_wait buckets 3 / 4), so that the all-reduce of a plane's
                                   * gradient overlaps the scatter of the next one.  Same gradients. */
-#define LRF_FLAG_ALL        255u /* any other bit is an error (a caller built against another ABI version) */
+#define LRF_FLAG_DETERMINISTIC 256u /* lrf_render_bwd only (the forward entry points accept and ignore it): bit-reproducible gradients.
+                                  * With the same inputs every gradient (the 19 parameter tensors and d/d rays) has the same bits from
+                                  * run to run, whatever the partition of the scatter, the order the binning leaves its entries in, the
+                                  * stream layout (two streams or one, captured) and LRF_FLAG_PLANE_EVENTS.  The plane / line gradients
+                                  * are summed in 64-bit fixed point (one scale per tensor group and plane from the batch's largest
+                                  * contribution: a quantum of about 2^-39 of it at 300^3, far below fp32's own rounding of each product)
+                                  * into an int64 image in the workspace (lrf_workspace_bytes_bwd_cfg grows by 8 bytes per gradient
+                                  * element of the planes and lines when this bit is set: 69 MB at 300^3), converted once into the
+                                  * caller's gradients; the results lie within ~1e-6 of each tensor's maximum of the default mode's.
+                                  * Cost: the clear and the conversion of the image and integer run sums in the scatter.
+                                  * Refused (non-zero return): the generic engine (a non-default network, LRF_FLAG_MLP_VALU) and appearance
+                                  * lines longer than 640 cells. */
+#define LRF_FLAG_ALL        511u /* any other bit is an error (a caller built against another ABI version) */
 
 /* Parameters of one TensorVMSplit field as the reference stores them (state-dict layout,
  * models/tensoRF.py:18-50, models/tensorBase.py:97-113).  Plane p is [1,C,H_p,W_p] with

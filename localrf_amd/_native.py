@@ -16,6 +16,8 @@ LRF_FLAG_ROWS_SAVED = 16
 LRF_FLAG_SORT_RAYS = 32
 LRF_FLAG_PE_OFF = 64
 LRF_FLAG_PLANE_EVENTS = 128
+LRF_FLAG_DETERMINISTIC = 256
+LRF_FLAG_ALL = 511
 
 _f = C.c_void_p  # device float*
 
@@ -93,6 +95,7 @@ SYMBOLS = {
     "lrf_debug_saved_row_offset": (C.c_int64, [C.c_int, C.c_uint64, C.c_int]),
     "lrf_debug_set_bwd_overlap": (None, [C.c_int]),
     "lrf_debug_set_train_fwd_engine": (None, [C.c_int]),
+    "lrf_debug_set_scatter_wgs": (None, [C.c_int]),
     "lrf_workspace_layout_bwd": (None, [C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_uint64)]),
     "lrf_cache_bytes": (C.c_size_t, [C.POINTER(C.c_int32)]),
     "lrf_pack_field": (C.c_int, [C.POINTER(LrfParams), C.c_void_p, C.c_void_p]),

@@ -1409,12 +1409,63 @@ __device__ __forceinline__ void seg_sum4(float& v0, float& v1, float& v2, float&
                : "v"(r.m1), "v"(r.m2), "v"(r.m4), "v"(r.m8));
 #undef LRF_STEP
 }
-template <int C, bool APP, int NT, int CH = LRF_CD>
-__global__ __launch_bounds__(NT) void k_scatter_fix(DField f, BinGeom bg, ScatterDst dst, const float* __restrict__ rays,
-                                                     const float* __restrict__ z, int S, const int* __restrict__ offs,
-                                                     const uint32_t* __restrict__ list, const float* __restrict__ gf,
-                                                     const uint32_t* __restrict__ rowinfo, const float* __restrict__ grd,
-                                                     const unsigned* __restrict__ vmax_bits, int bin_lo, int bin_hi) {
+// ---- deterministic mode (LRF_FLAG_DETERMINISTIC): the same kernel with every sum in 64-bit integers up to the int64 image
+// of the gradient in the workspace (DetDst), one fp32 conversion behind it (k_det_convert).  What makes it order-free:
+//  * ONE scale per tensor group (density / appearance) and plane p, from quantities no partition changes: vmax (atomicMax)
+//    and n_p, plane p's entry count (offs).  Every workgroup that touches a cell -- a tile's border cells are shared with
+//    its neighbours -- uses the same quantum.
+//  * every lane's contribution is converted to fixed point BEFORE any cross-lane sum; the run sums are integer (seg_sum4_i)
+//  * the LDS accumulators are flushed with 64-bit integer global atomics.
+// Overflow bound: a cell of plane p or of line p receives at most 4 n_p contributions (each entry of the plane adds to 4 tile
+// cells and to 2 line cells), each at most vmax < 2^vex in magnitude, so with scale 2^sh, sh = min(46, 62 - bits(4 n_p)) - vex
+// (det_shift), every partial or total sum is below 4 n_p 2^vex 2^sh <= 2^62 (+ 4 n_p / 2 of rounding: < 2^63), and every
+// single addend below 2^46 (fix64 is exact there).
+struct DetDst { unsigned long long* plane[3]; unsigned long long* line[3]; };
+__device__ __forceinline__ int det_vex(const unsigned* vmax_bits) {
+  int vex = 0;
+  (void)frexpf(__uint_as_float(*vmax_bits), &vex);      // vmax < 2^vex
+  return max(-120, min(127, vex));
+}
+__device__ __forceinline__ int det_shift(const int* __restrict__ offs, const BinGeom& bg, int p, int vex) {
+  const long long n4 = 4ll * (long long)(offs[p == 2 ? bg.total : bg.base[p + 1]] - offs[bg.base[p]]);
+  const int bits = n4 ? 64 - __builtin_clzll((unsigned long long)n4) : 0;
+  return min(46, 62 - bits) - vex;
+}
+struct SegRunI { unsigned m1, m2, m4, m8; bool tail; };            // seg_run's masks as 0 / ~0u
+__device__ __forceinline__ SegRunI seg_run_i(const SegRun& r) {
+  return SegRunI{r.m1 != 0.0f ? ~0u : 0u, r.m2 != 0.0f ? ~0u : 0u, r.m4 != 0.0f ? ~0u : 0u, r.m8 != 0.0f ? ~0u : 0u, r.tail};
+}
+// seg_sum4 on 64-bit integers: per step, both halves of the value D lanes below masked by the lane's 0 / ~0 mask (v_and_b32
+// with a DPP source), then a 64-bit add (add with carry).  The four values' steps are interleaved as in seg_sum4: no DPP read
+// follows the VALU write of its register closer than 12 instructions (s_nop 1 covers whatever the compiler placed in front).
+__device__ __forceinline__ void seg_sum4_i(unsigned long long& v0, unsigned long long& v1, unsigned long long& v2,
+                                           unsigned long long& v3, const SegRunI& r) {
+  unsigned a0 = (unsigned)v0, b0 = (unsigned)(v0 >> 32), a1 = (unsigned)v1, b1 = (unsigned)(v1 >> 32);
+  unsigned a2 = (unsigned)v2, b2 = (unsigned)(v2 >> 32), a3 = (unsigned)v3, b3 = (unsigned)(v3 >> 32);
+  unsigned t0, t1;
+#define LRF_ISTEP1(L, H, N, M) \
+  "v_and_b32_dpp %8, " L ", " M " row_shr:" N " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t" \
+  "v_and_b32_dpp %9, " H ", " M " row_shr:" N " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t" \
+  "v_add_co_u32 " L ", vcc, " L ", %8\n\t" \
+  "v_addc_co_u32 " H ", vcc, " H ", %9, vcc\n\t"
+#define LRF_ISTEP(N, M) LRF_ISTEP1("%0", "%1", N, M) LRF_ISTEP1("%2", "%3", N, M) LRF_ISTEP1("%4", "%5", N, M) LRF_ISTEP1("%6", "%7", N, M)
+  asm volatile("s_nop 1\n\t" LRF_ISTEP("1", "%10") LRF_ISTEP("2", "%11") LRF_ISTEP("4", "%12") LRF_ISTEP("8", "%13")
+               : "+v"(a0), "+v"(b0), "+v"(a1), "+v"(b1), "+v"(a2), "+v"(b2), "+v"(a3), "+v"(b3), "=&v"(t0), "=&v"(t1)
+               : "v"(r.m1), "v"(r.m2), "v"(r.m4), "v"(r.m8)
+               : "vcc");
+#undef LRF_ISTEP
+#undef LRF_ISTEP1
+  v0 = ((unsigned long long)b0 << 32) | a0; v1 = ((unsigned long long)b1 << 32) | a1;
+  v2 = ((unsigned long long)b2 << 32) | a2; v3 = ((unsigned long long)b3 << 32) | a3;
+}
+
+// The body of k_scatter_fix (DET = false) and of k_scatter_det (DET = true: ddst instead of dst, see above).
+template <int C, bool APP, int NT, int CH, bool DET>
+__device__ __forceinline__ void scatter_fix_body(const DField& f, const BinGeom& bg, const ScatterDst& dst, const DetDst& ddst, const float* __restrict__ rays,
+                                                 const float* __restrict__ z, int S, const int* __restrict__ offs,
+                                                 const uint32_t* __restrict__ list, const float* __restrict__ gf,
+                                                 const uint32_t* __restrict__ rowinfo, const float* __restrict__ grd,
+                                                 const unsigned* __restrict__ vmax_bits, int bin_lo, int bin_hi) {
   // APP (C = 24): the appearance tensors, EIGHT channels per sweep over a tile's entries (three sweeps per tile, back to back:
   // a 24-channel tile of 64-bit cells would be 209 KB; the line accumulators hold all 24 channels).  The sample's
   // d(loss)/d(feature) is then per channel (the dX row k_train_app3 left), the taps come from the dense 24-channel caches
@@ -1452,7 +1503,8 @@ __global__ __launch_bounds__(NT) void k_scatter_fix(DField f, BinGeom bg, Scatte
     const double inv = ldexp(1.0, -shL);
     for (int i = threadIdx.x; i < nl; i += NT) {
       const long long q = (long long)s_fl[i];
-      if (q != 0) atomic_add_f32(gln + i, (float)((double)q * inv));
+      if constexpr (DET) { if (q != 0) atomicAdd(ddst.line[lplane] + i, (unsigned long long)q); }
+      else if (q != 0) atomic_add_f32(gln + i, (float)((double)q * inv));
     }
     __syncthreads();
   };
@@ -1468,7 +1520,7 @@ __global__ __launch_bounds__(NT) void k_scatter_fix(DField f, BinGeom bg, Scatte
       lplane = p;
       // this workgroup's entries of plane p: at most two contributions each to a line cell
       const int pend = min(b, offs[min(bin_hi, p == 2 ? bg.total : bg.base[p + 1])]);
-      shL = fix_shift(2u * (unsigned)(pend - a), vex);
+      shL = DET ? det_shift(offs, bg, p, vex) : fix_shift(2u * (unsigned)(pend - a), vex);
       for (int i = threadIdx.x; i < ll * C; i += NT) s_fl[i] = 0ull;
     }
 #ifdef LRF_SCATTER_PROF
@@ -1478,7 +1530,7 @@ __global__ __launch_bounds__(NT) void k_scatter_fix(DField f, BinGeom bg, Scatte
     for (int i = threadIdx.x; i < CH * CELLS; i += NT) s_fx[i] = 0ull;
     __syncthreads();
     SP_TICK(0);
-    const int shT = fix_shift(4u * (unsigned)(seg_end - a), vex);
+    const int shT = DET ? shL : fix_shift(4u * (unsigned)(seg_end - a), vex);   // (DET: one scale for the plane and its line)
     const double scT = ldexp(1.0, shT), scL = ldexp(1.0, shL);
     const float* lnp = APP ? f.aline2[p] + CH * sweep : f.dline[p];      // the sweep's 8 channels of a texel: 32 bytes, 16-byte aligned
     const float* plp = APP ? f.aplane2[p] + CH * sweep : f.dplane[p];
@@ -1541,6 +1593,37 @@ __global__ __launch_bounds__(NT) void k_scatter_fix(DField f, BinGeom bg, Scatte
       unsigned long long* tc = s_fx + c00;
       unsigned long long* lc0 = s_fl + (size_t)sweep * CH * ll + l0;
       unsigned long long* lc1 = s_fl + (size_t)sweep * CH * ll + l1;
+      if constexpr (DET) {                              // fixed point per lane first, then integer run sums: no fp32 sum across lanes
+        const SegRunI it = seg_run_i(rt), il = seg_run_i(rl);
+#pragma unroll
+        for (int c = 0; c < CH; c += 2) {
+          unsigned long long t[2][4], sl[4];
+#pragma unroll
+          for (int j = 0; j < 2; ++j) {
+            const float Lv = e0v[c + j] * (1.0f - tl) + e1v[c + j] * tl;
+            const float dP = dx[c + j] * Lv;
+            t[j][0] = fix64(dP * w00, scT); t[j][1] = fix64(dP * w10, scT); t[j][2] = fix64(dP * w01, scT); t[j][3] = fix64(dP * w11, scT);
+            seg_sum4_i(t[j][0], t[j][1], t[j][2], t[j][3], it);
+            const float P = v00[c + j] * w00 + v10[c + j] * w10 + v01[c + j] * w01 + v11[c + j] * w11;
+            const float dL = dx[c + j] * P;
+            sl[2 * j] = fix64(dL * (1.0f - tl), scL); sl[2 * j + 1] = fix64(dL * tl, scL);
+          }
+          seg_sum4_i(sl[0], sl[1], sl[2], sl[3], il);
+#pragma unroll
+          for (int j = 0; j < 2; ++j) {
+            if (it.tail) {
+              atomicAdd(tc + (c + j) * CELLS, t[j][0]);
+              atomicAdd(tc + (c + j) * CELLS + cx, t[j][1]);
+              atomicAdd(tc + (c + j) * CELLS + cy, t[j][2]);
+              atomicAdd(tc + (c + j) * CELLS + cy + cx, t[j][3]);
+            }
+            if (il.tail) {
+              atomicAdd(lc0 + (c + j) * ll, sl[2 * j]);
+              atomicAdd(lc1 + (c + j) * ll, sl[2 * j + 1]);
+            }
+          }
+        }
+      } else {
 #pragma unroll
       for (int c = 0; c < CH; c += 2) {
         float t[2][4], sl[4];
@@ -1569,6 +1652,7 @@ __global__ __launch_bounds__(NT) void k_scatter_fix(DField f, BinGeom bg, Scatte
           }
         }
       }
+      }                                                 // DET
       SP_WAIT_LGKM(); SP_TICK(4);
     }
     __syncthreads();
@@ -1580,7 +1664,10 @@ __global__ __launch_bounds__(NT) void k_scatter_fix(DField f, BinGeom bg, Scatte
       if (q == 0) continue;
       const int c = i / CELLS, cell = i % CELLS;
       const int x = tx0 + cell % BCELL, y = ty0 + cell / BCELL;
-      if (x < pw && y < ph) atomic_add_f32(gpl + ((size_t)c * ph + y) * pw + x, (float)((double)q * invT));
+      if (x < pw && y < ph) {
+        if constexpr (DET) atomicAdd(ddst.plane[p] + (size_t)sweep * CH * ph * pw + ((size_t)c * ph + y) * pw + x, (unsigned long long)q);
+        else atomic_add_f32(gpl + ((size_t)c * ph + y) * pw + x, (float)((double)q * invT));
+      }
     }
     __syncthreads();
     SP_TICK(6);
@@ -1596,6 +1683,50 @@ __global__ __launch_bounds__(NT) void k_scatter_fix(DField f, BinGeom bg, Scatte
   }
 #endif
 }
+template <int C, bool APP, int NT, int CH = LRF_CD>
+__global__ __launch_bounds__(NT) void k_scatter_fix(DField f, BinGeom bg, ScatterDst dst, const float* __restrict__ rays,
+                                                     const float* __restrict__ z, int S, const int* __restrict__ offs,
+                                                     const uint32_t* __restrict__ list, const float* __restrict__ gf,
+                                                     const uint32_t* __restrict__ rowinfo, const float* __restrict__ grd,
+                                                     const unsigned* __restrict__ vmax_bits, int bin_lo, int bin_hi) {
+  const DetDst none{};
+  scatter_fix_body<C, APP, NT, CH, false>(f, bg, dst, none, rays, z, S, offs, list, gf, rowinfo, grd, vmax_bits, bin_lo, bin_hi);
+}
+template <int C, bool APP, int NT, int CH = LRF_CD>
+__global__ __launch_bounds__(NT) void k_scatter_det(DField f, BinGeom bg, DetDst dst, const float* __restrict__ rays,
+                                                     const float* __restrict__ z, int S, const int* __restrict__ offs,
+                                                     const uint32_t* __restrict__ list, const float* __restrict__ gf,
+                                                     const uint32_t* __restrict__ rowinfo, const float* __restrict__ grd,
+                                                     const unsigned* __restrict__ vmax_bits, int bin_lo, int bin_hi) {
+  const ScatterDst none{};
+  scatter_fix_body<C, APP, NT, CH, true>(f, bg, none, dst, rays, z, S, offs, list, gf, rowinfo, grd, vmax_bits, bin_lo, bin_hi);
+}
+
+// Deterministic mode, behind the scatter of planes [p_lo, p_hi) of one tensor group: g += q 2^-sh over plane p's and line p's
+// int64 image (the scale det_shift gave the scatter), four elements per thread.  Every plane / line segment holds a multiple
+// of 8 elements (C = 8 or 24 channels); the image segments are 256-byte aligned, the gradients only 4-byte.
+struct DetConv { unsigned long long* img[6]; float* g[6]; long long n[6]; };   // plane 0..2, line 0..2
+__global__ __launch_bounds__(256) void k_det_convert(DetConv dc, BinGeom bg, const int* __restrict__ offs,
+                                                     const unsigned* __restrict__ vmax_bits, int p_lo, int p_hi) {
+  const int vex = det_vex(vmax_bits);
+  for (int p = p_lo; p < p_hi; ++p) {
+    const double inv = ldexp(1.0, -det_shift(offs, bg, p, vex));
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const int s = p + 3 * k;
+      const ulonglong2* q = reinterpret_cast<const ulonglong2*>(dc.img[s]);
+      float* g = dc.g[s];
+      const long long n4 = dc.n[s] / 4;
+      for (long long i = blockIdx.x * 256ll + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
+        const ulonglong2 a = q[2 * i], b = q[2 * i + 1];
+        g[4 * i]     += (float)((double)(long long)a.x * inv);
+        g[4 * i + 1] += (float)((double)(long long)a.y * inv);
+        g[4 * i + 2] += (float)((double)(long long)b.x * inv);
+        g[4 * i + 3] += (float)((double)(long long)b.y * inv);
+      }
+    }
+  }
+}
 
 #include "lrf_train32.inl"
 
@@ -1610,9 +1741,13 @@ struct BwdWorkspace {
   int* toff32;               // [R + 1] k_shade3's own tile offsets when they do not fit in its LDS (fw.toff holds the 16-row tiles')
   uint16_t* tid2; int* hist2; int* offs2; int* cursor2; uint32_t* list2;   // bins of the appearance scatter (runs beside the density scatter)
   uint32_t nmax;
+  unsigned long long* det_img;   // LRF_FLAG_DETERMINISTIC: int64 image of the density and appearance gradients (k_scatter_det), or null
+  long long det_words;           // ... its size in 64-bit words (cleared by k_clear_bins)
+  DetDst det_d, det_a;           // ... its plane / line segments per group, [C][H][W] / [C][L] as the gradients
   size_t bytes;
 };
-static BwdWorkspace carve_bwd(void* ws, int R, int S, const int32_t grid[3], int gen_ld = 0 /* generic engine: floats per row of weight-gradient operands */) {
+static BwdWorkspace carve_bwd(void* ws, int R, int S, const int32_t grid[3], int gen_ld = 0 /* generic engine: floats per row of weight-gradient operands */,
+                              bool det = false /* LRF_FLAG_DETERMINISTIC: + the int64 gradient image, behind everything else */) {
   BwdWorkspace b;
   b.fw = carve(ws, R, S);
   char* p = reinterpret_cast<char*>(ws);
@@ -1645,6 +1780,17 @@ static BwdWorkspace carve_bwd(void* ws, int R, int S, const int32_t grid[3], int
   b.offs2 = reinterpret_cast<int*>(take(2 * (BIN_MAX + 1)));
   b.list2 = reinterpret_cast<uint32_t*>(take(3 * rows));
   b.gen = gen_ld ? take(rows * (size_t)gen_ld) : nullptr;
+  b.det_img = nullptr; b.det_words = 0; b.det_d = DetDst{}; b.det_a = DetDst{};
+  if (det) {
+    const size_t img0 = off;
+    auto take64 = [&](size_t n) { return reinterpret_cast<unsigned long long*>(take(2 * n)); };
+    for (int q = 0; q < 3; ++q) {
+      b.det_d.plane[q] = take64((size_t)LRF_CD * L.pw[q] * L.ph[q]); b.det_d.line[q] = take64((size_t)LRF_CD * L.ll[q]);
+      b.det_a.plane[q] = take64((size_t)LRF_CA * L.pw[q] * L.ph[q]); b.det_a.line[q] = take64((size_t)LRF_CA * L.ll[q]);
+    }
+    b.det_img = reinterpret_cast<unsigned long long*>(p + img0);
+    b.det_words = (long long)((off - img0) / 8);          // (a multiple of 32: every piece is rounded up to 256 bytes)
+  }
   b.bytes = off;
   return b;
 }
@@ -1658,6 +1804,7 @@ static int g_scatter_fused = 1;     // lrf_debug_set_train_fwd_engine(8 | ...): 
 static int g_scatter_fix = 3;       // bit 0: density, bit 1: appearance (where its accumulators fit in LDS) through k_scatter_fix.  lrf_debug_set_train_fwd_engine(16 | ...): both through the compare-and-swap kernels of rounds 2-5 (the tests compare the two); 256: the density alone
 static int g_wgrad_kt = 64;          // rows per step of k_wgrad_w2w3 (lrf_debug_set_train_fwd_engine(512 | ...): 128, one workgroup per CU)
 static int g_wgrad_split = 1;       // lrf_debug_set_bwd_overlap(1 + 2 * (n + 1)): n > 0 = k_wgrad_w2w3 on the caller's stream, 0 = on the side stream
+static int g_scatter_wgs = 0;       // lrf_debug_set_scatter_wgs: workgroups of the binned scatter kernels (0: one per CU)
 static hipError_t launch_shade_save(DField d, const float* rays, const float* z, int S, int R, uint32_t flags, const Workspace& w,
                                     const BwdWorkspace& b, float* rgb, hipStream_t st) {
   if (!gen_is_default(d.fea_pe, d.view_pe, d.fc) || (flags & LRF_FLAG_MLP_VALU)) {          // generic engine (lrf_generic.inl): same saved state, no mask bits
@@ -1675,6 +1822,7 @@ static hipError_t launch_shade_save(DField d, const float* rays, const float* z,
 
 }  // namespace lrf
 
+extern "C" void lrf_debug_set_scatter_wgs(int n) { lrf::g_scatter_wgs = n > 0 ? n : 0; }
 extern "C" void lrf_debug_set_train_fwd_engine(int e) { lrf::g_scatter_fused = (e & 8) ? 0 : 1; lrf::g_scatter_fix = (e & 16) ? 0 : ((e & 256) ? 1 : ((e & 1024) ? 7 : 3)); lrf::g_dgrad_dbg = (e >> 5) & 7; lrf::g_wgrad_kt = (e & 512) ? 128 : 64; }
 
 namespace lrf {
@@ -1689,7 +1837,7 @@ extern "C" size_t lrf_workspace_bytes_bwd(int32_t R, int32_t S, const int32_t gr
   return lrf::carve_bwd(nullptr, R, S, grid).bytes;
 }
 extern "C" size_t lrf_workspace_bytes_bwd_cfg(int32_t R, int32_t S, const int32_t grid[3], int32_t fea_pe, int32_t view_pe, int32_t feature_c, uint32_t flags) {
-  return lrf::carve_bwd(nullptr, R, S, grid, lrf::field_gen_ld(fea_pe, view_pe, feature_c, flags)).bytes;
+  return lrf::carve_bwd(nullptr, R, S, grid, lrf::field_gen_ld(fea_pe, view_pe, feature_c, flags), (flags & LRF_FLAG_DETERMINISTIC) != 0).bytes;
 }
 
 // Byte offsets of the pieces of the training workspace a test may want to look at (debug / parity
@@ -1740,9 +1888,14 @@ extern "C" int lrf_render_bwd(const LrfField* f, const LrfParams* p, const float
   const Layout L = make_layout(f->grid);
   const int gen_ld = field_gen_ld(f->fea_pe, f->view_pe, f->feature_c, flags);
   const bool generic = gen_ld != 0;
-  const BwdWorkspace b = carve_bwd(workspace, R, S, f->grid, gen_ld);
+  const bool det = (flags & LRF_FLAG_DETERMINISTIC) != 0;
+  if (det && generic)
+    return set_err("lrf_render_bwd: LRF_FLAG_DETERMINISTIC does not cover the generic engine (a network other than fea_pe = view_pe = 0, "
+                   "featureC = 128, or LRF_FLAG_MLP_VALU): its weight-gradient GEMM adds row chunks with fp32 atomics");
+  const BwdWorkspace b = carve_bwd(workspace, R, S, f->grid, gen_ld, det);
   const Workspace& w = b.fw;
   const int cus = device_cus();
+  const int nwg_scatter = g_scatter_wgs > 0 ? g_scatter_wgs : cus;
   d.rdir = w.rdir;                                         // per-ray unit directions: written by k_march (the saved forward's, or the one below), read by k_scatter_fix
   if (flags & LRF_FLAG_ROWS_SAVED) {                       // lrf_render_fwd_train sorted (or not) with the same flags: same workspace
     if ((flags & LRF_FLAG_SORT_RAYS) && R <= LRF_SORT_MAX_R && R >= 2) { d.perm = w.perm; rays = w.rays_s; }
@@ -1778,6 +1931,12 @@ extern "C" int lrf_render_bwd(const LrfField* f, const LrfParams* p, const float
       if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_scatter_fix<LRF_CA, true, FIX_NT>),
                                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
       if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_scatter_fix<LRF_CA, true, FIX_NT, 4>),
+                                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+      if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_scatter_det<LRF_CD, false, FIX_NT>),
+                                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+      if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_scatter_det<LRF_CA, true, FIX_NT>),
+                                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+      if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_scatter_det<LRF_CA, true, FIX_NT, 4>),
                                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
       if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_wgrad_w2w3<128>),
                                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)w23_lds(128));
@@ -1825,6 +1984,11 @@ extern "C" int lrf_render_bwd(const LrfField* f, const LrfParams* p, const float
     const long long zf4 = g->zero_floats / 4;
     const unsigned nblk_clear = (unsigned)(BIN_CLEAR_BLOCKS + (zf4 + ZERO_F4_PER_BLOCK - 1) / ZERO_F4_PER_BLOCK);
     hipLaunchKernelGGL(k_clear_bins, dim3(nblk_clear), dim3(256), 0, st, b.hist, b.hist2, reinterpret_cast<float4*>(g->zero_base), zf4);     // (in front of the fork: both branches count into these)
+    if (det) {                                             // the int64 gradient image: the same kernel once more (its bins part again)
+      const long long if4 = b.det_words / 2;
+      hipLaunchKernelGGL(k_clear_bins, dim3((unsigned)(BIN_CLEAR_BLOCKS + (if4 + ZERO_F4_PER_BLOCK - 1) / ZERO_F4_PER_BLOCK)), dim3(256), 0, st,
+                         b.hist, b.hist2, reinterpret_cast<float4*>(b.det_img), if4);
+    }
   }
   hipStream_t sb = st;
   if (ss) {
@@ -1869,8 +2033,15 @@ extern "C" int lrf_render_bwd(const LrfField* f, const LrfParams* p, const float
   const size_t lds_fa4 = lds_dp + sizeof(unsigned long long) * LRF_CA * ll_max;
   const bool fix_a4 = fix_d && (g_scatter_fix & 2) && !fix_a8 && !(g_scatter_fix & 4) && lds_fa4 <= 158 * 1024;
   const bool fix_a = fix_a8 || fix_a4;
+  // LRF_FLAG_DETERMINISTIC: always the fixed-point kernels (whatever the debug switches say); lines that leave no room for them
+  // in LDS (density: > 1439 cells, appearance: > 640 cells -- the reference ends at 640^3) are refused
+  const bool det_a8 = 2 * (lds_dp + lds_dl) <= 158 * 1024 && lds_fa <= 158 * 1024;
+  const bool det_a4 = !det_a8 && 2 * (lds_dp + lds_dl) <= 158 * 1024 && lds_fa4 <= 158 * 1024;
+  if (det && !det_a8 && !det_a4)
+    return set_err("lrf_render_bwd: LRF_FLAG_DETERMINISTIC covers lines up to 640 cells (the fixed-point line accumulators of the "
+                   "appearance scatter must fit in LDS)");
   unsigned* vmax_a = reinterpret_cast<unsigned*>(b.hist2 + 2 * BIN_MAX);
-  if (fix_a)
+  if (fix_a || det)
     hipLaunchKernelGGL((k_train_app3<8, true>), dim3(n_dgrad_wg), dim3(512), app3_lds_bytes(S, 8, bg.total), st, d,
                        d.mlpwt, rays, z, S, w.toff, R, b.tileinfo, w.cidx,
                        b.grd, b.rpart, w.pmax, b.wpart, bg, b.tid2, b.hist2, b.nmax, g_dgrad_dbg & 3, vmax_a);
@@ -1884,17 +2055,30 @@ extern "C" int lrf_render_bwd(const LrfField* f, const LrfParams* p, const float
   hipLaunchKernelGGL(k_bwd_ray, dim3((R + 3) / 4), dim3(256), (size_t)14 * S * sizeof(float) + (size_t)bg.total * sizeof(int), sb,
                      d, rays, z, R, S, flags, b.feat, w.ncomp, w.cidx, b.crgb, g_rgb, g_depth,
                      (const float*)nullptr, w.pmax, g_rays, bg, b.tid, b.hist, b.nmax, vmax_d);
-  if (fix_d) {
+  auto det_convert = [&](const DetDst& img, float* const* gp, float* const* gl, int cch, const int* offs, const unsigned* vmax, int p_lo, int p_hi, hipStream_t s) {
+    DetConv dc;
+    for (int q = 0; q < 3; ++q) {
+      dc.img[q] = img.plane[q]; dc.g[q] = gp[q]; dc.n[q] = (long long)cch * L.pw[q] * L.ph[q];
+      dc.img[3 + q] = img.line[q]; dc.g[3 + q] = gl[q]; dc.n[3 + q] = (long long)cch * L.ll[q];
+    }
+    hipLaunchKernelGGL(k_det_convert, dim3(cus * 8), dim3(256), 0, s, dc, bg, offs, vmax, p_lo, p_hi);
+  };
+  if (det) {
     hipLaunchKernelGGL(k_bin_fill, dim3(nblk), dim3(256), 0, sb, bg, b.nmax, R, S, w.toff, 0, b.tid, b.hist, b.cursor, b.offs, b.list);
-    hipLaunchKernelGGL((k_scatter_fix<LRF_CD, false, FIX_NT>), dim3(cus), dim3(FIX_NT), 2 * (lds_dp + lds_dl), sb,
+    hipLaunchKernelGGL((k_scatter_det<LRF_CD, false, FIX_NT>), dim3(nwg_scatter), dim3(FIX_NT), 2 * (lds_dp + lds_dl), sb,
+                       d, bg, b.det_d, rays, z, S, b.offs, b.list, b.feat, b.rowinfo, b.grd, vmax_d, 0, bg.total);
+    det_convert(b.det_d, g->density_plane, g->density_line, LRF_CD, b.offs, vmax_d, 0, 3, sb);
+  } else if (fix_d) {
+    hipLaunchKernelGGL(k_bin_fill, dim3(nblk), dim3(256), 0, sb, bg, b.nmax, R, S, w.toff, 0, b.tid, b.hist, b.cursor, b.offs, b.list);
+    hipLaunchKernelGGL((k_scatter_fix<LRF_CD, false, FIX_NT>), dim3(nwg_scatter), dim3(FIX_NT), 2 * (lds_dp + lds_dl), sb,
                        d, bg, dst_d, rays, z, S, b.offs, b.list, b.feat, b.rowinfo, b.grd, vmax_d, 0, bg.total);
   } else if (fuse_d) {
     hipLaunchKernelGGL(k_bin_fill, dim3(nblk), dim3(256), 0, sb, bg, b.nmax, R, S, w.toff, 0, b.tid, b.hist, b.cursor, b.offs, b.list);
-    hipLaunchKernelGGL((k_scatter_plane<LRF_CD, false, 512, true>), dim3(cus * LRF_DPLANE_MULT), dim3(512), lds_dp + lds_dl, sb,
+    hipLaunchKernelGGL((k_scatter_plane<LRF_CD, false, 512, true>), dim3(nwg_scatter * LRF_DPLANE_MULT), dim3(512), lds_dp + lds_dl, sb,
                        d, bg, dst_d, rays, z, S, b.offs, b.list, b.feat, b.rowinfo, b.grd, 0, bg.total);
   } else {
     hipLaunchKernelGGL(k_bin_fill, dim3(nblk), dim3(256), 0, sb, bg, b.nmax, R, S, w.toff, 0, b.tid, b.hist, b.cursor, b.offs, b.list);
-    hipLaunchKernelGGL((k_scatter_plane<LRF_CD, false, 512, false>), dim3(cus * LRF_DPLANE_MULT), dim3(512), lds_dp, sb,
+    hipLaunchKernelGGL((k_scatter_plane<LRF_CD, false, 512, false>), dim3(nwg_scatter * LRF_DPLANE_MULT), dim3(512), lds_dp, sb,
                        d, bg, dst_d, rays, z, S, b.offs, b.list, b.feat, b.rowinfo, b.grd, 0, bg.total);
     hipLaunchKernelGGL((k_scatter_line<LRF_CD, false, 1024>), dim3(3 * LINE_WGS), dim3(1024), lds_dl, sb,
                        d, dst_d, rays, z, R, S, w.toff, b.feat, b.rowinfo, b.grd);
@@ -1958,22 +2142,30 @@ extern "C" int lrf_render_bwd(const LrfField* f, const LrfParams* p, const float
   const int npass = (flags & LRF_FLAG_PLANE_EVENTS) ? 3 : 1;
   for (int q = 0; q < npass; ++q) {
     const int blo = npass == 1 ? 0 : bg.base[q], bhi = (npass == 1 || q == 2) ? bg.total : bg.base[q + 1];
-    if (fix_a8) {
-      hipLaunchKernelGGL((k_scatter_fix<LRF_CA, true, FIX_NT>), dim3(cus), dim3(FIX_NT), lds_fa, st,
+    if (det) {
+      if (det_a8)
+        hipLaunchKernelGGL((k_scatter_det<LRF_CA, true, FIX_NT>), dim3(nwg_scatter), dim3(FIX_NT), lds_fa, st,
+                           d, bg, b.det_a, rays, z, S, b.offs2, b.list2, b.feat, b.rowinfo, b.grd, vmax_a, blo, bhi);
+      else
+        hipLaunchKernelGGL((k_scatter_det<LRF_CA, true, FIX_NT, 4>), dim3(nwg_scatter), dim3(FIX_NT), lds_fa4, st,
+                           d, bg, b.det_a, rays, z, S, b.offs2, b.list2, b.feat, b.rowinfo, b.grd, vmax_a, blo, bhi);
+      det_convert(b.det_a, g->app_plane, g->app_line, LRF_CA, b.offs2, vmax_a, npass == 1 ? 0 : q, npass == 1 ? 3 : q + 1, st);
+    } else if (fix_a8) {
+      hipLaunchKernelGGL((k_scatter_fix<LRF_CA, true, FIX_NT>), dim3(nwg_scatter), dim3(FIX_NT), lds_fa, st,
                          d, bg, dst_a, rays, z, S, b.offs2, b.list2, b.feat, b.rowinfo, b.grd, vmax_a, blo, bhi);
     } else if (fix_a4) {
-      hipLaunchKernelGGL((k_scatter_fix<LRF_CA, true, FIX_NT, 4>), dim3(cus), dim3(FIX_NT), lds_fa4, st,
+      hipLaunchKernelGGL((k_scatter_fix<LRF_CA, true, FIX_NT, 4>), dim3(nwg_scatter), dim3(FIX_NT), lds_fa4, st,
                          d, bg, dst_a, rays, z, S, b.offs2, b.list2, b.feat, b.rowinfo, b.grd, vmax_a, blo, bhi);
     } else if (fuse_a) {
-      hipLaunchKernelGGL((k_scatter_plane<LRF_CA, true, LRF_APP_NT, true>), dim3(cus), dim3(LRF_APP_NT), lds_ap + lds_al, st,
+      hipLaunchKernelGGL((k_scatter_plane<LRF_CA, true, LRF_APP_NT, true>), dim3(nwg_scatter), dim3(LRF_APP_NT), lds_ap + lds_al, st,
                          d, bg, dst_a, rays, z, S, b.offs2, b.list2, b.feat, b.rowinfo, b.grd, blo, bhi);
     } else {
-      hipLaunchKernelGGL((k_scatter_plane<LRF_CA, true, LRF_APP_NT, false>), dim3(cus), dim3(LRF_APP_NT), lds_ap, st,
+      hipLaunchKernelGGL((k_scatter_plane<LRF_CA, true, LRF_APP_NT, false>), dim3(nwg_scatter), dim3(LRF_APP_NT), lds_ap, st,
                          d, bg, dst_a, rays, z, S, b.offs2, b.list2, b.feat, b.rowinfo, b.grd, blo, bhi);
     }
     if (npass == 3 && q < 2 && sx) LRF_HIP(hipEventRecord(sx->bucket[3 + q], st));    // app_plane[q] is final (its line only if fused: bucket 2)
   }
-  if (!fuse_a && !fix_a)
+  if (!fuse_a && !fix_a && !det)
     hipLaunchKernelGGL((k_scatter_line<LRF_CA, true, 1024>), dim3(3 * LINE_WGS), dim3(1024), lds_al, st,
                        d, dst_a, rays, z, R, S, w.toff, b.feat, b.rowinfo, b.grd);
 

@@ -269,6 +269,9 @@ class TensorVMSplit(torch.nn.Module):
         # Measured (profiles/r11b): it cuts HBM-side traffic but not time -- k_shade3 124 vs 125 us, k_march unchanged, at
         # 300^3, 500^3 and 640^3; the sort launch costs 38 us -- so it is off by default
         self.sort_rays = False
+        # bit-reproducible backward (LRF_FLAG_DETERMINISTIC): None follows torch.are_deterministic_algorithms_enabled() at the
+        # moment a backward is enqueued (a CapturedIteration reads it at capture); True / False force the mode
+        self.deterministic = None
 
     # ------------------------------------------------------------------ construction
     def _check_supported(self, shadingMode, pos_pe, view_pe, fea_pe, featureC):
@@ -505,6 +508,9 @@ class TensorVMSplit(torch.nn.Module):
             raise ValueError(f"unknown mlp_engine {self.mlp_engine!r}")
         if self.sort_rays:
             fl |= N.LRF_FLAG_SORT_RAYS
+        det = getattr(self, "deterministic", None)
+        if det if det is not None else torch.are_deterministic_algorithms_enabled():
+            fl |= N.LRF_FLAG_DETERMINISTIC
         return fl
 
     def _native_forward(self, rays, z, flags, floater, want_weights=False, out=None):
@@ -606,7 +612,11 @@ class TensorVMSplit(torch.nn.Module):
         (cg.basis, cg.w1, cg.b1, cg.w2, cg.b2, cg.w3, cg.b3) = [g.data_ptr() for g in grads[12:]]
         flat = self._grad_flat["flat"]
         cg.zero_base, cg.zero_floats = flat.data_ptr(), flat.numel()          # (offsets are multiples of 64 floats: so is the total)
+        # the deterministic mode is what the field / torch say NOW, when the backward is enqueued (not at the forward)
+        flags = (flags & ~N.LRF_FLAG_DETERMINISTIC) | (self._flags(False) & N.LRF_FLAG_DETERMINISTIC)
         nbytes = lib.lrf_workspace_bytes_bwd_cfg(R, S, cp.grid, int(self.fea_pe), int(self.view_pe), int(self.featureC), flags)
+        if saved_ws is not None and saved_ws.numel() < nbytes:
+            saved_ws = None                      # (the forward ran outside the deterministic mode: no room for its int64 image)
         if saved_ws is not None:                 # filled by lrf_render_fwd_train for exactly this call
             ws = saved_ws
             flags = flags | N.LRF_FLAG_ROWS_SAVED
