@@ -442,6 +442,31 @@ int lrf_loss_combine_bwd(const float* w, const float* g_total /* device [1] */, 
 int lrf_rows_gather(const float* src, const int64_t* idx, int32_t V, int32_t K, int32_t F, float* out, void* stream);
 int lrf_rows_gather_bwd(const float* g_out, const int64_t* idx, int32_t V, int32_t K, int32_t F, float* g_src, void* stream);
 
+/* lrf_image_metrics: test-view image quality of B frame pairs img0 / img1 [B,H,W,3] (contiguous fp32, HWC, the layout of
+ * rgb_map.reshape(H, W, 3)) -- the two metrics renderer.render(test=True) computes on the host per frame (renderer.py:162-163):
+ *   mse[b]       = mean over all H*W*3 values of (img0 - img1)^2, summed in fp64 (the reference: fp32 torch);
+ *   ssim_mean[b] = mean of the SSIM map of utils/utils.py:232-287 (rgb_ssim, the mip-NeRF SSIM);
+ *   ssim_map     = that map [B, H-fs+1, W-fs+1, 3] (NULL: not written).
+ * SSIM as the reference computes it, in fp64: the separable Gaussian (filter_size taps, filter_sigma, the even-size shift)
+ * applied as scipy.signal.convolve2d(mode="valid"), rows' axis first, to x, y, x^2, y^2, xy (squares and product
+ * rounded in fp32, as numpy forms them from fp32 arrays); variances clamped at 0, the covariance at sqrt(s00 s11);
+ * c1 = (k1 max_val)^2, c2 = (k2 max_val)^2.  NaN inputs give NaN.  Outputs are fp64 device arrays of B entries.
+ * No atomics: bit-identical from run to run and independent of B.  Refused before any launch: 1 <= filter_size <= 31 is
+ * required, and H, W >= filter_size (the reference would return the NaN of an empty mean).
+ * workspace: lrf_image_metrics_workspace_bytes(B, H, W, filter_size) bytes (0 for arguments lrf_image_metrics refuses). */
+typedef struct LrfImageMetrics {
+  const float* img0;
+  const float* img1;
+  int32_t B, H, W;
+  int32_t filter_size;   /* 1..31 (utils.py default 11) */
+  double max_val;        /* 1 for images in [0, 1] (renderer.py:163) */
+  double filter_sigma;   /* 1.5 */
+  double k1, k2;         /* 0.01, 0.03 */
+} LrfImageMetrics;
+size_t lrf_image_metrics_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t filter_size);
+int lrf_image_metrics(const LrfImageMetrics* m, double* ssim_map /* nullable */, double* ssim_mean /* [B] */, double* mse /* [B] */,
+                      void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

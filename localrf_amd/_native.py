@@ -83,6 +83,11 @@ class LrfLossTerms(C.Structure):
                 ("b", C.c_float * LRF_LOSS_TERMS_MAX), ("count", C.c_int32), ("s", _f)]
 
 
+class LrfImageMetrics(C.Structure):
+    _fields_ = [("img0", _f), ("img1", _f), ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("filter_size", C.c_int32),
+                ("max_val", C.c_double), ("filter_sigma", C.c_double), ("k1", C.c_double), ("k2", C.c_double)]
+
+
 # every symbol include/lrf.h and include/lrf_debug.h declare: (restype, argtypes)
 SYMBOLS = {
     "lrf_abi_version": (C.c_int, []),
@@ -156,6 +161,8 @@ SYMBOLS = {
     "lrf_scene_fwd": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _f, _f, C.c_int32, _f, _f, C.c_int32, C.c_int32,
                                 C.c_int32, C.POINTER(LrfSceneField), C.c_float, C.c_int32, _f, _f,
                                 _f, _f, _f, _f, C.c_void_p, _f, _f, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "lrf_image_metrics_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "lrf_image_metrics": (C.c_int, [C.POINTER(LrfImageMetrics), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "lrf_scene_blend_bwd": (C.c_int, [_f, _f, _f, _f, _f, C.c_int32, C.c_int32, C.c_int32, _f, _f, _f,
                                       C.c_void_p]),
 }

@@ -1133,6 +1133,7 @@ static hipError_t launch_shade_gen(const DField& d, const GenCfg& gc, const floa
 #include "lrf_scene.inl"
 #include "lrf_adam.inl"
 #include "lrf_losses.inl"
+#include "lrf_metrics.inl"
 #include "lrf_reg.inl"
 #include "lrf_mask.inl"
 
