@@ -467,6 +467,46 @@ size_t lrf_image_metrics_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_
 int lrf_image_metrics(const LrfImageMetrics* m, double* ssim_map /* nullable */, double* ssim_mean /* [B] */, double* mse /* [B] */,
                       void* workspace, void* stream);
 
+/* Device frame store: the train split of LocalRFDataset (dataLoader/localrf_dataset.py) as a window of `capacity` frame slots
+ * on the device, each frame in separate fp32 planes as the reference stores them (slot s of a plane starts at s * n_px rows):
+ *   rgb [capacity, n_px, 3], loss_weight [capacity, n_px], invdepth [capacity, n_px] (NULL: no depth),
+ *   fwd_flow / bwd_flow [capacity, n_px, 2] with fwd_mask / bwd_mask [capacity, n_px] (NULL pairs: no flow).
+ * slot_of: device int32 [num_images], the slot holding frame v or -1.  status: device uint32 [1], sticky error bits.  The caller
+ * rewrites slot_of and status in place with stream-ordered copies: a captured lrf_frames_gather stays valid when the window moves.
+ * Every entry point checks the window (positive sizes, the required planes, flow planes paired with their masks) before any launch. */
+#define LRF_FRAMES_ERR_NOT_RESIDENT 1u   /* a gathered view lay outside [0, num_images) or had no slot: its rows are NaN */
+typedef struct LrfFrameWindow {
+  float* rgb; float* loss_weight; float* invdepth;
+  float* fwd_flow; float* fwd_mask; float* bwd_flow; float* bwd_mask;
+  const int32_t* slot_of;
+  uint32_t* status;
+  int32_t capacity, n_px, num_images;
+} LrfFrameWindow;
+/* lrf_frames_gather: the rows sample() returns (localrf_dataset.py:303-313) for V views x n rays in one launch.  view_ids int64 [V],
+ * ray_ids int64 [V n]: row r is view view_ids[r / n], pixel ray_ids[r] mod n_px (the reference's global ids view * n_px + pix and
+ * per-view pixel ids both work).  Outputs rgbs [V n, 3], loss_weights [V n], invdepths [V n], fwd_flow / bwd_flow [V n, 2],
+ * fwd_mask / bwd_mask [V n]; a NULL output is not written.  A view that is not resident gives NaN rows and sets
+ * LRF_FRAMES_ERR_NOT_RESIDENT in *status; no trap, no host synchronisation.  Refused: V <= 0, n <= 0, V n >= 2^29, null ids,
+ * an output whose plane the window does not hold. */
+int lrf_frames_gather(const LrfFrameWindow* w, const int64_t* view_ids, const int64_t* ray_ids, int32_t V, int32_t n,
+                      float* rgbs, float* loss_weights, float* invdepths, float* fwd_flow, float* fwd_mask,
+                      float* bwd_flow, float* bwd_mask, void* stream);
+/* lrf_decode_flow: decode_flow (utils/utils.py:67-71) of an encoded flow image uint16 [H,W,3] (already at the frame's size:
+ * the resize stays the caller's) times flow_scale (localrf_dataset.py:193-194) into slot `slot`'s forward (backward = 0) or
+ * backward flow plane and mask: flow = (float(e) - 32768) / 256 * float(flow_scale) in fp32 (numpy rounds the Python float to
+ * fp32 before the multiply), mask = e[...,2] > 32768.  Refused: H W != n_px, a slot outside the window, no flow planes. */
+int lrf_decode_flow(const LrfFrameWindow* w, int32_t slot, int32_t backward, const uint16_t* encoded, int32_t H, int32_t W,
+                    double flow_scale, void* stream);
+/* lrf_frame_sharpness: the loss weight of localrf_dataset.py:229-235 from slot `slot`'s rgb plane [H,W,3] (already uploaded):
+ * grey = OpenCV's 8-bit RGB2GRAY of uint8(trunc(img * 255)) ((4899 R + 9617 G + 1868 B + 8192) >> 14, its documented constants;
+ * img * 255 rounded in fp32, values outside [0, 1] clamped), the 3x3 Laplacian of cv2.Laplacian(ksize=1, CV_32F) with
+ * BORDER_REFLECT_101, its variance over all pixels (integer sums, exact; one rounding to fp32), times motion_mask (uint8 [n_px],
+ * nonzero = 1; NULL = all ones) into the slot's loss_weight plane.  Deterministic (fixed partition, integer partials, no atomics).
+ * workspace: lrf_frame_sharpness_workspace_bytes() bytes.  Refused: H W != n_px, n_px > 2^21, a slot outside the window. */
+size_t lrf_frame_sharpness_workspace_bytes(void);
+int lrf_frame_sharpness(const LrfFrameWindow* w, int32_t slot, int32_t H, int32_t W, const uint8_t* motion_mask,
+                        void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

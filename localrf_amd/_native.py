@@ -88,6 +88,15 @@ class LrfImageMetrics(C.Structure):
                 ("max_val", C.c_double), ("filter_sigma", C.c_double), ("k1", C.c_double), ("k2", C.c_double)]
 
 
+LRF_FRAMES_ERR_NOT_RESIDENT = 1
+
+
+class LrfFrameWindow(C.Structure):
+    _fields_ = [("rgb", _f), ("loss_weight", _f), ("invdepth", _f), ("fwd_flow", _f), ("fwd_mask", _f), ("bwd_flow", _f),
+                ("bwd_mask", _f), ("slot_of", C.c_void_p), ("status", C.c_void_p),
+                ("capacity", C.c_int32), ("n_px", C.c_int32), ("num_images", C.c_int32)]
+
+
 # every symbol include/lrf.h and include/lrf_debug.h declare: (restype, argtypes)
 SYMBOLS = {
     "lrf_abi_version": (C.c_int, []),
@@ -163,6 +172,13 @@ SYMBOLS = {
                                 _f, _f, _f, _f, C.c_void_p, _f, _f, C.c_void_p, C.c_size_t, C.c_void_p]),
     "lrf_image_metrics_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "lrf_image_metrics": (C.c_int, [C.POINTER(LrfImageMetrics), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "lrf_frames_gather": (C.c_int, [C.POINTER(LrfFrameWindow), C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                    _f, _f, _f, _f, _f, _f, _f, C.c_void_p]),
+    "lrf_decode_flow": (C.c_int, [C.POINTER(LrfFrameWindow), C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
+                                  C.c_double, C.c_void_p]),
+    "lrf_frame_sharpness_workspace_bytes": (C.c_size_t, []),
+    "lrf_frame_sharpness": (C.c_int, [C.POINTER(LrfFrameWindow), C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                      C.c_void_p]),
     "lrf_scene_blend_bwd": (C.c_int, [_f, _f, _f, _f, _f, C.c_int32, C.c_int32, C.c_int32, _f, _f, _f,
                                       C.c_void_p]),
 }

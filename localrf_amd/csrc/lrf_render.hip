@@ -1134,6 +1134,7 @@ static hipError_t launch_shade_gen(const DField& d, const GenCfg& gc, const floa
 #include "lrf_adam.inl"
 #include "lrf_losses.inl"
 #include "lrf_metrics.inl"
+#include "lrf_frames.inl"
 #include "lrf_reg.inl"
 #include "lrf_mask.inl"
 

@@ -6,8 +6,8 @@
   depth_loss(...)  train.py:414-423 with compute_depth_loss (utils/utils.py:50-59): returns `depth_loss_arr.mean()`
                    after the 0.8-quantile clipping
 
-  batch_gather(...) train.py:352-358,385-420: the batch's target colours, flows, flow masks and inverse depths out of the
-                   dataset tensors in one launch
+  batch_gather(...) the batch's target colours, flows, position-only flow masks and inverse depths out of frame tensors
+                   in one launch (dataset masks and loss weights: localrf_amd.DeviceFrames)
   combine(...)     train.py:425-437: the weighted sum of the iteration's loss terms, one launch each way
 
 Both take what `LocalTensorfs.forward` returns (depth_map, directions, ij) and are differentiable with respect to
@@ -199,9 +199,10 @@ def photometric_loss(rgb_map, rgb_train, loss_weights=None, weights_mean=None):
 
 
 def batch_gather(view_ids, pix, images=None, fwd_flow=None, bwd_flow=None, invdepths=None):
-    """The batch's rows of the dataset tensors in one launch (train.py:352-358 `rgb_train`, :385-420 the flows, their masks
-    and the inverse depths; the reference indexes each tensor with the (view, pixel) ids and forms the masks with tensor
-    expressions).  view_ids int64 [V], pix int64 [V, n] (pixel ids inside the view), both on the device; dataset tensors
+    """The batch's rows of frame tensors in one launch: target colours, flows and inverse depths indexed by (view, pixel)
+    ids, as train.py:352-358 and the flow / depth terms index theirs.  The masks are "has a next / previous frame" flags
+    from the view's position only, not the reference's per-pixel flow-validity masks: for the dataset's masks and loss
+    weights use localrf_amd.DeviceFrames.gather.  view_ids int64 [V], pix int64 [V, n] (pixel ids inside the view), both on the device; dataset tensors
     [n_images, H*W, 3 | 2 | 2] and [n_images, H*W] float32 on the device, None = not wanted.  Returns a dict: "target" [V n, 3],
     "fwd_flow" / "bwd_flow" [V n, 2], "fwd_mask" / "bwd_mask" [V n] (1 where the view has a next / previous image),
     "invdepths" [V n].  Not differentiable (the dataset is data)."""

@@ -106,15 +106,40 @@ class SyntheticFrames:
         self.stats = {"mean": float(self.images.mean()), "std": float(self.images.std()),
                       "frame_to_frame": float((self.images[1:] - self.images[:-1]).abs().mean())}
         del teacher
+        self.pix = pix
+        self.store = None
+
+    def open_store(self, capacity):
+        """The frames through localrf_amd.DeviceFrames, as a dataset reader would hand them over: decoded flows with
+        flow-validity masks (0 where the teacher's flow leaves the image: what RAFT's occlusion check marks invalid) and a
+        motion mask that is not uniform (every 7th diagonal masked), so the loss weights vary across pixels."""
+        from localrf_amd import DeviceFrames
+        W, H = self.W, self.H
+        x, y = self.pix[:, 0], self.pix[:, 1]
+
+        def inside(flow):
+            q = self.pix + flow
+            return ((q[:, 0] >= 0) & (q[:, 0] <= W - 1) & (q[:, 1] >= 0) & (q[:, 1] <= H - 1)).float()
+
+        motion = ((x + 2 * y) % 7 != 0).reshape(H, W).cpu().numpy()
+        host = [{"img": self.images[i].reshape(H, W, 3).cpu().numpy(), "invdepth": self.invdepths[i].reshape(H, W).cpu().numpy(),
+                 "fwd_flow": self.fwd_flow[i].reshape(H, W, 2).cpu().numpy(), "fwd_mask": inside(self.fwd_flow[i]).reshape(H, W).cpu().numpy(),
+                 "bwd_flow": self.bwd_flow[i].reshape(H, W, 2).cpu().numpy(), "bwd_mask": inside(self.bwd_flow[i]).reshape(H, W).cpu().numpy(),
+                 "mask": motion} for i in range(self.num_images)]           # (read here once: the loop's reads stay host-only)
+        self.store = DeviceFrames(host.__getitem__, self.num_images, capacity, n_init_frames=self.active_frames_bounds[1], device=self.dev)
 
     def has_left_frames(self):
         return self.active_frames_bounds[1] < self.num_images
 
     def activate_frames(self, n=1):
         self.active_frames_bounds[1] = min(self.active_frames_bounds[1] + n, self.num_images)
+        if self.store is not None:
+            self.store.activate_frames(n)
 
     def deactivate_frames(self, first_kept):
         self.active_frames_bounds[0] = int(first_kept)
+        if self.store is not None:
+            self.store.deactivate_frames(int(first_kept))
 
     def sample(self, batch_size, n_views=16):
         lo, hi = self.active_frames_bounds
@@ -197,10 +222,15 @@ class LateLog:
         self.pending = (len(tensors), sink)
 
 
-def geometric_terms(lt, data, depth_map, directions, ij, cam2world_all, view_ids, start, vsel, psel, W, H):
+def geometric_terms(lt, data, depth_map, directions, ij, cam2world_all, view_ids, start, vsel, psel, W, H, rows=None):
     """train.py:385-423: the optical-flow and monocular-depth losses of one batch (localrf_amd.losses kernels).  view_ids:
-    host or device ids; vsel [V] / psel [V, n]: device indices of the batch's views / pixels into the dataset tensors."""
+    host or device ids; vsel [V] / psel [V, n]: device indices of the batch's views / pixels into the dataset tensors.
+    rows: the batch's rows out of the frame store (DeviceFrames.gather: the dataset's flow masks) instead."""
     from localrf_amd import losses as geo_losses
+    if rows is not None:
+        fl = geo_losses.flow_loss(depth_map, directions, ij, cam2world_all, view_ids, start, rows["fwd_flow"], rows["fwd_mask"],
+                                  rows["bwd_flow"], rows["bwd_mask"], lt.focal(W), lt.center(W, H))
+        return fl, geo_losses.depth_loss(depth_map, rows["invdepths"], int(vsel.shape[0]))
     last = data.num_images - 1
     fl = geo_losses.flow_loss(depth_map, directions, ij, cam2world_all, view_ids, start,
                               data.fwd_flow[vsel[:, None], psel], (vsel < last).float()[:, None].expand(psel.shape),
@@ -212,7 +242,7 @@ def geometric_terms(lt, data, depth_map, directions, ij, cam2world_all, view_ids
 
 def run(frames=24, W=64, H=48, n_init=5, final=300, iters_per_frame=60, batch=4096, max_iters=None, seed=0,
         dev="cuda:0", ddp=False, log=None, max_drift=0.25, n_max_frames=12, geo=True, geo_every=25, graph=False, record_all=False, live=None, lr_i_init=0,
-        fuse_l1=True):
+        fuse_l1=True, frames_store=False):
     from localrf_amd import LocalTensorfs, losses as geo_losses
     from localrf_amd.dist import allreduce_grads, shard_views
     from localrf_amd.rays import N_to_reso
@@ -221,6 +251,13 @@ def run(frames=24, W=64, H=48, n_init=5, final=300, iters_per_frame=60, batch=40
     rank = dist.get_rank() if ddp else 0
     world = dist.get_world_size() if ddp else 1
     data = SyntheticFrames(frames, W, H, n_init, dev, seed)
+    store = None
+    if frames_store:                                                  # the frames through localrf_amd.DeviceFrames (one gather launch)
+        if ddp:
+            raise ValueError("frames_store: single-rank runs only")
+        data.open_store(frames)                                       # (a slot per frame: the window is not bounded by n_max_frames)
+        store = data.store
+    geo_keys = ("fwd_flow", "fwd_mask", "bwd_flow", "bwd_mask", "invdepths")
     aabb = 2 * torch.tensor([[-1.0, -1, -1], [1, 1, 1]]).to(dev)
     # opt.py:61-70 scaled by iters_per_frame / 600
     sc = iters_per_frame / 600.0
@@ -254,9 +291,13 @@ def run(frames=24, W=64, H=48, n_init=5, final=300, iters_per_frame=60, batch=40
         psel = inp.ray_ids.reshape(V, -1)
         n = int(psel.shape[1])
         want_geo = phase["reg"] and geo
-        rows = geo_losses.batch_gather(inp.view_ids, psel, images=data.images, fwd_flow=data.fwd_flow if want_geo else None,
-                                       bwd_flow=data.bwd_flow if want_geo else None, invdepths=data.invdepths if want_geo else None)
-        loss = geo_losses.photometric_loss(rgb_map, rows["target"])
+        if store is not None:                                          # the dataset's loss weights and flow masks (train.py:369-371, 385-420)
+            rows = store.gather(inp.view_ids, inp.ray_ids, want=("rgbs", "loss_weights") + (geo_keys if want_geo else ()))
+            rows["target"] = rows["rgbs"]
+        else:
+            rows = geo_losses.batch_gather(inp.view_ids, psel, images=data.images, fwd_flow=data.fwd_flow if want_geo else None,
+                                           bwd_flow=data.bwd_flow if want_geo else None, invdepths=data.invdepths if want_geo else None)
+        loss = geo_losses.photometric_loss(rgb_map, rows["target"], rows.get("loss_weights"))
         terms, kept = [(loss, 1.0, 0.0)], {"photo": loss}
         if want_geo:
             fl = geo_losses.flow_loss(depth_map, directions, ij, inp.cam2world_all, inp.view_ids, inp.start, rows["fwd_flow"], rows["fwd_mask"],
@@ -322,7 +363,12 @@ def run(frames=24, W=64, H=48, n_init=5, final=300, iters_per_frame=60, batch=40
             # host->device copy, as train.py:352-358 does) blocks the host until the stream has drained
             vv_d = vv.pin_memory().to(dev, non_blocking=True)
             pp_d = pp.pin_memory().to(dev, non_blocking=True)
-            target = data.images[vv_d, pp_d].reshape(-1, 3)
+            rows = None
+            if store is not None:
+                rows = store.gather(vv_d[:, 0], pp_d, want=("rgbs", "loss_weights") + (geo_keys if lt.regularize and geo else ()))
+                target = rows["rgbs"]
+            else:
+                target = data.images[vv_d, pp_d].reshape(-1, 3)
             if ddp:                                                        # this rank's views of the common batch
                 per = ray_idx.shape[0] // view_ids.shape[0]
                 ray_idx, v_sh = shard_views(ray_idx, view_ids, rank, world)
@@ -330,7 +376,7 @@ def run(frames=24, W=64, H=48, n_init=5, final=300, iters_per_frame=60, batch=40
                 target = target[v0 * per:(v0 + v_sh.shape[0]) * per]
                 view_ids = v_sh
             rgb_map, depth_map, directions, ij = lt(ray_idx, view_ids.tolist(), W, H, is_train=True, test_id=False)
-            loss = geo_losses.photometric_loss(rgb_map, target)            # train.py:369-371, unit loss weights (one launch each way)
+            loss = geo_losses.photometric_loss(rgb_map, target, None if rows is None else rows["loss_weights"])   # train.py:369-371 (one launch each way)
             total = loss
             if lt.regularize and geo:                                      # train.py:357,385-423; opt.py: weights 1 and 0.1
                 reg_w = lt.lr_factor ** lt.rf_iter[-1]
@@ -340,7 +386,7 @@ def run(frames=24, W=64, H=48, n_init=5, final=300, iters_per_frame=60, batch=40
                     psel = ray_idx.reshape(view_ids.shape[0], -1).pin_memory().to(dev, non_blocking=True)
                 else:
                     vsel, psel = vv_d[:, 0], pp_d
-                fl, dl = geometric_terms(lt, data, depth_map, directions, ij, lt.get_cam2world(starting_id=start), view_ids, start, vsel, psel, W, H)
+                fl, dl = geometric_terms(lt, data, depth_map, directions, ij, lt.get_cam2world(starting_id=start), view_ids, start, vsel, psel, W, H, rows)
                 total = total + fl * 1.0 * reg_w / ((W + H) / 2) + dl * 0.1 * reg_w
                 geo_vals.append((float(fl.detach()), float(dl.detach())) if it % geo_every == 0 else None)
                 if it % geo_every == 0:                                    # the curve, phase by phase (profiles/r09*_geo_curve)
@@ -477,7 +523,8 @@ def run(frames=24, W=64, H=48, n_init=5, final=300, iters_per_frame=60, batch=40
                                                              "schedule": 1e3 * v[3] / max(1, v[5]), "rest": 1e3 * v[4] / max(1, v[5])} for r, v in host_t.items()}, "graph": (dict(gs.stats, stage_wait_s=gs.stats.get("stage_wait_s", 0.0) + (gs.inputs.wait_s if getattr(gs, "inputs", None) is not None else 0.0)) if gs is not None else None), "all_losses": all_losses,
             "param_checksum": float(sum(p.detach().double().abs().sum() for p in lt.parameters())),
             "checkpoint_roundtrip": bool(same), "checkpoint_keys_follow_reference": bool(keys_ok), "world": world,
-            "final_resolution": res, "replica_divergence": divergence}
+            "final_resolution": res, "replica_divergence": divergence,
+            "frames_store": None if store is None else {"capacity": store.capacity, "errors": store.errors(), "bounds": list(store.active_frames_bounds)}}
 
 
 def main():
@@ -491,6 +538,7 @@ def main():
     ap.add_argument("--graph", action="store_true", help="the iteration as one replayed hipGraph (localrf_amd/graph_step.py)")
     ap.add_argument("--no-fuse-l1", action="store_true", help="density_L1 as an autograd node of its own (A/B of TensorVMSplit.fuse_density_L1)")
     ap.add_argument("--no-geo", action="store_true", help="without the optical-flow / monocular-depth losses")
+    ap.add_argument("--frames-store", action="store_true", help="the frames through localrf_amd.DeviceFrames: dataset loss weights and flow masks")
     ap.add_argument("--backend", default="nccl", help="under torchrun: nccl (= RCCL, one rank per GPU) or gloo (ranks may share a GPU)")
     args = ap.parse_args()
     import __graft_entry__ as ge
@@ -516,7 +564,7 @@ def main():
     if ddp and first:
         bar()
     out = run(frames=args.frames, final=args.final, iters_per_frame=args.iters_per_frame, max_iters=args.max_iters, n_max_frames=args.n_max_frames,
-              dev=f"cuda:{local}", ddp=ddp, geo=not args.no_geo, graph=args.graph, fuse_l1=not args.no_fuse_l1, log=lambda m: print(m, file=sys.stderr, flush=True))
+              dev=f"cuda:{local}", ddp=ddp, geo=not args.no_geo, graph=args.graph, fuse_l1=not args.no_fuse_l1, frames_store=args.frames_store, log=lambda m: print(m, file=sys.stderr, flush=True))
     if not ddp or int(os.environ["RANK"]) == 0:
         print(json.dumps(out, default=lambda o: o.tolist() if hasattr(o, "tolist") else str(o)))
         if args.json:
