@@ -507,6 +507,54 @@ size_t lrf_frame_sharpness_workspace_bytes(void);
 int lrf_frame_sharpness(const LrfFrameWindow* w, int32_t slot, int32_t H, int32_t W, const uint8_t* motion_mask,
                         void* workspace, void* stream);
 
+/* lrf_select: exact order statistics of B fp32 rows; row b is x[b * row_stride .. b * row_stride + n_b) (device memory).
+ *   LRF_SELECT_QUANTILE: out[b] = np.quantile(row, q) with numpy's default method="linear", bit for bit: q rounded to fp32,
+ *     v = fp32(fp32(n - 1) * q), gamma and the two-sided lerp in fp32 as numpy 2.2 forms them (csrc/lrf_select.inl);
+ *   LRF_SELECT_MEDIAN: out[b] = torch.median(row), the element of rank floor((n - 1) / 2).
+ * A row holding a NaN gives NaN (0x7FC00000); +-inf are ordinary values; -0.0 and +0.0 compare equal and a zero result is
+ * +0.0.  Radix select over order-preserving uint32 keys, four 8-bit digit passes plus one min pass: integer atomics only, a
+ * fixed launch sequence, no host synchronisation (capturable, bit-reproducible).  n: host array of B row lengths
+ * (n_count = B <= LRF_SELECT_MAX_ROWS) or of one length shared by every row (n_count = 1, B <= 65535).  Refused before any
+ * launch: a length outside 1 <= n < 2^31, q outside [0, 1], a negative row_stride, null pointers.
+ * workspace: lrf_select_workspace_bytes(B, max_n) bytes (0 for shapes lrf_select refuses). */
+#define LRF_SELECT_QUANTILE 0
+#define LRF_SELECT_MEDIAN 1
+#define LRF_SELECT_MAX_ROWS 256
+size_t lrf_select_workspace_bytes(int32_t B, int64_t max_n);
+int lrf_select(const float* x, int64_t row_stride, const int64_t* n, int32_t n_count, int32_t B, int32_t mode, float q, float* out,
+               void* workspace, void* stream);
+
+/* Test-view geometry diagnostics of renderer.render(test=True) (renderer.py:79-124) for V views of H x W pixels.
+ * lrf_flow_comparison: per view v (absolute frame index idx[v] in [0, F)) the predicted forward / backward flow of every pixel
+ * (utils.py:15-48: neighbours clamp(idx +- 1, 0, F - 1), pts = dirs * depth, pts2px with z clipped at 1e-6, minus float(ij)),
+ * written as renderer.py stacks it into fwd_cmp / bwd_cmp [V, 3H, 2W]: column half c = component c; rows 0..H prediction,
+ * H..2H dataset flow, 2H..3H |pred - flow| * mask / W.  Rows 0..2H of each half are divided by their np.quantile(., 0.9)
+ * (lrf_select; quantiles [V, 4] = fwd c0, fwd c1, bwd c0, bwd c1), then everything is clamped to [0, 1] (NaN stays NaN).
+ * fwd_raw / bwd_raw (both or neither): the images before the division and the clamp.
+ * Inputs: cam2world [F,3,4], depth [V,HW], dirs [V,HW,3], ij int64 [V,HW,2] (col, row), flows [V,HW,2], masks [V,HW] (0 / 1),
+ * focal device [1], center device [2].  Refused before any launch: V outside 1..LRF_EVAL_MAX_VIEWS, an idx outside [0, F),
+ * H or W <= 0, 6 H W >= 2^31, null pointers.  workspace: lrf_flow_comparison_workspace_bytes(V, H, W) bytes. */
+#define LRF_EVAL_MAX_VIEWS 64
+typedef struct LrfFlowComparison {
+  const float* cam2world;
+  const float* depth; const float* dirs; const int64_t* ij;
+  const float* fwd_flow; const float* fwd_mask; const float* bwd_flow; const float* bwd_mask;
+  const float* focal; const float* center;
+  int32_t F, V, H, W;
+  int32_t idx[LRF_EVAL_MAX_VIEWS];
+} LrfFlowComparison;
+size_t lrf_flow_comparison_workspace_bytes(int32_t V, int32_t H, int32_t W);
+int lrf_flow_comparison(const LrfFlowComparison* c, float* fwd_cmp, float* bwd_cmp, float* fwd_raw /* nullable */,
+                        float* bwd_raw /* nullable */, float* quantiles, void* workspace, void* stream);
+/* lrf_depth_comparison: compute_depth_loss (utils.py:50-59) of x = 1 / clamp(depth, 1e-6) against y = invdepth (both [V, HW])
+ * into out [V, 3H, W] = vstack(0.5 x^, 0.5 y^, (x^ - y^)^2) clamped to [0, 1], with ^ = (. - median) / mean|. - median|.
+ * stats [V, 4] = (median x, median y, mad x, mad y); medians exact (torch.median), each MAD summed in fp64 in a fixed order
+ * and rounded once to fp32 (the reference's fp32 mean differs in the last bits).  Refused: V outside 1..32767, H or W <= 0,
+ * 6 H W >= 2^31, null pointers.  workspace: lrf_depth_comparison_workspace_bytes(V, H, W) bytes. */
+size_t lrf_depth_comparison_workspace_bytes(int32_t V, int32_t H, int32_t W);
+int lrf_depth_comparison(const float* depth, const float* invdepth, int32_t V, int32_t H, int32_t W, float* out, float* stats,
+                         void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,6 +7,8 @@ Public surface mirrors the reference's names:
   FusedAdam                         (torch.optim.Adam as local_tensorfs.py:88-97,146 configures it)
   losses.flow_loss / depth_loss     (train.py:385-423 with utils/utils.py:15-59)
   metrics.rgb_ssim / test_view_metrics (utils/utils.py:232-287, renderer.py:155-167: test-view SSIM and MSE)
+  diagnostics.quantile / median / flow_comparison / depth_comparison / test_view_evaluation
+                                    (renderer.py:79-124: test-view flow and depth comparison images, exact device quantiles)
   DeviceFrames                      (dataLoader/localrf_dataset.py, train split: a device-resident frame window)
 The arithmetic of TensorVMSplit.forward and of LocalTensorfs.forward (ray generation, field
 blend, exposure) runs in hand-written HIP kernels for gfx950 (csrc/), reached through the C ABI
@@ -19,6 +21,7 @@ from .optim import FusedAdam  # noqa: F401
 from . import rays  # noqa: F401
 from . import losses  # noqa: F401
 from . import metrics  # noqa: F401
+from . import diagnostics  # noqa: F401
 from .frames import DeviceFrames  # noqa: F401
 
-__all__ = ["TensorVMSplit", "AlphaGridMask", "MLPRender_Fea_late_view", "LocalTensorfs", "rays", "losses", "metrics", "NativeError", "FusedAdam", "DeviceFrames"]
+__all__ = ["TensorVMSplit", "AlphaGridMask", "MLPRender_Fea_late_view", "LocalTensorfs", "rays", "losses", "metrics", "diagnostics", "NativeError", "FusedAdam", "DeviceFrames"]

@@ -97,6 +97,18 @@ class LrfFrameWindow(C.Structure):
                 ("capacity", C.c_int32), ("n_px", C.c_int32), ("num_images", C.c_int32)]
 
 
+LRF_SELECT_QUANTILE = 0
+LRF_SELECT_MEDIAN = 1
+LRF_SELECT_MAX_ROWS = 256
+LRF_EVAL_MAX_VIEWS = 64
+
+
+class LrfFlowComparison(C.Structure):
+    _fields_ = [("cam2world", _f), ("depth", _f), ("dirs", _f), ("ij", C.c_void_p), ("fwd_flow", _f), ("fwd_mask", _f),
+                ("bwd_flow", _f), ("bwd_mask", _f), ("focal", _f), ("center", _f),
+                ("F", C.c_int32), ("V", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("idx", C.c_int32 * LRF_EVAL_MAX_VIEWS)]
+
+
 # every symbol include/lrf.h and include/lrf_debug.h declare: (restype, argtypes)
 SYMBOLS = {
     "lrf_abi_version": (C.c_int, []),
@@ -179,6 +191,13 @@ SYMBOLS = {
     "lrf_frame_sharpness_workspace_bytes": (C.c_size_t, []),
     "lrf_frame_sharpness": (C.c_int, [C.POINTER(LrfFrameWindow), C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                       C.c_void_p]),
+    "lrf_select_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int64]),
+    "lrf_select": (C.c_int, [_f, C.c_int64, C.POINTER(C.c_int64), C.c_int32, C.c_int32, C.c_int32, C.c_float, _f, C.c_void_p,
+                             C.c_void_p]),
+    "lrf_flow_comparison_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "lrf_flow_comparison": (C.c_int, [C.POINTER(LrfFlowComparison), _f, _f, _f, _f, _f, C.c_void_p, C.c_void_p]),
+    "lrf_depth_comparison_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "lrf_depth_comparison": (C.c_int, [_f, _f, C.c_int32, C.c_int32, C.c_int32, _f, _f, C.c_void_p, C.c_void_p]),
     "lrf_scene_blend_bwd": (C.c_int, [_f, _f, _f, _f, _f, C.c_int32, C.c_int32, C.c_int32, _f, _f, _f,
                                       C.c_void_p]),
 }

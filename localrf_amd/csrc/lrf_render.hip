@@ -1135,6 +1135,8 @@ static hipError_t launch_shade_gen(const DField& d, const GenCfg& gc, const floa
 #include "lrf_losses.inl"
 #include "lrf_metrics.inl"
 #include "lrf_frames.inl"
+#include "lrf_select.inl"
+#include "lrf_evalgeo.inl"
 #include "lrf_reg.inl"
 #include "lrf_mask.inl"
 
