@@ -11,6 +11,9 @@
  * all calls are asynchronous on `stream` and re-entrant per stream (the test hooks of
  * include/lrf_debug.h are process-wide switches and are NOT part of this contract).
  * Return 0 on success, non-zero on error with a message available from lrf_last_error().
+ * lrf_render_fwd, lrf_render_fwd_train, lrf_render_bwd and lrf_scene_fwd check all their
+ * arguments first: a refused call enqueues nothing on any stream.  A HIP error after the
+ * arguments are accepted (a failed launch, say) can still leave a partial sequence enqueued.
  */
 #ifndef LRF_H_
 #define LRF_H_

@@ -1817,7 +1817,8 @@ static hipError_t launch_shade_save(DField d, const float* rays, const float* z,
     return hipGetLastError();
   }
   const SaveOut3 sv{b.crgb, b.act, b.relu_bits, b.tileinfo, w.toff};
-  return launch_shade3(d, rays, z, R, S, flags, w, b.toff32, rgb, nullptr, &sv, nullptr, st);
+  launch_shade3(d, rays, z, R, S, flags, w, b.toff32, rgb, nullptr, &sv, nullptr, st);
+  return hipSuccess;
 }
 
 }  // namespace lrf
@@ -1861,6 +1862,7 @@ extern "C" int lrf_render_fwd_train(const LrfField* f, const float* rays, const 
     return set_err("lrf_render_fwd_train: the row-saving forward runs the split-bf16 engine only");
   if (flags & ~LRF_FLAG_ALL) return set_err("lrf_render_fwd_train: unknown flag bits");
   if (const char* bad = gen_check(f)) return set_err(bad);
+  LRF_HIP(lds_opt_in());
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   DField d = make_dfield(f);
   const BwdWorkspace b = carve_bwd(workspace, R, S, f->grid, field_gen_ld(f->fea_pe, f->view_pe, f->feature_c, flags));
@@ -1873,81 +1875,112 @@ extern "C" int lrf_render_fwd_train(const LrfField* f, const float* rays, const 
   return 0;
 }
 
+namespace lrf {
+enum class DensEng { Det, Fix, CasFused, CasSplit };               // density scatter: int64 image, fixed point, compare-and-swap (lines fused / apart)
+enum class AppEng { Det8, Det4, Fix8, Fix4, CasFused, CasSplit };  // appearance scatter: the same, 8 or 4 channels per sweep of the first two
+// Everything lrf_render_bwd decides before its first launch
+struct BwdPlan {
+  DField d;                  // (d.rdir: per-ray unit directions, written by k_march, read by k_scatter_fix)
+  Layout L;
+  BinGeom bg;
+  BwdWorkspace b;
+  GenCfg gc;
+  int gen_ld;                // generic engine: floats per row of weight-gradient operands, else 0
+  bool generic, det, sort;   // sort: the kernels read the rays k_sort_rays left in the workspace
+  DensEng dens; size_t dens_lds, dens_line_lds;   // dynamic LDS of the scatter kernel (CasSplit: plane kernel, then line kernel)
+  AppEng app; size_t app_lds, app_line_lds;
+  bool app3_fix;             // k_train_app3<8, true>: also max|contribution| for the fixed-point appearance scatter
+  int npass, nblk;
+};
+
+// Every refusal of lrf_render_bwd, and its engines, workspace carve and grids: host arithmetic only, no HIP call.
+static const char* plan_bwd(BwdPlan& P, const LrfField* f, const LrfParams* p, const float* rays, const float* z, int32_t R, int32_t S,
+                            uint32_t flags, const float* g_rgb, const float* g_depth, const LrfGrads* g, const float* g_rays, void* workspace) {
+  if (!f || !f->cache || !p || !rays || !z || !g_rgb || !g_depth || !g || !g_rays || !workspace) return "lrf_render_bwd: null argument";
+  if (R <= 0 || S < 2 || S > LRF_MAX_S_TRAIN)
+    return "lrf_render_bwd: need R > 0 and 2 <= S <= LRF_MAX_S_TRAIN (2048: the per-ray backward keeps 16 B per sample in LDS)";
+  if (flags & ~LRF_FLAG_ALL) return "lrf_render_bwd: unknown flag bits";
+  if (const char* bad = gen_check(f)) return bad;
+  P.gen_ld = field_gen_ld(f->fea_pe, f->view_pe, f->feature_c, flags);
+  P.generic = P.gen_ld != 0;
+  P.det = (flags & LRF_FLAG_DETERMINISTIC) != 0;
+  if (P.det && P.generic)
+    return "lrf_render_bwd: LRF_FLAG_DETERMINISTIC does not cover the generic engine (a network other than fea_pe = view_pe = 0, "
+           "featureC = 128, or LRF_FLAG_MLP_VALU): its weight-gradient GEMM adds row chunks with fp32 atomics";
+  if (g->zero_floats < 0 || (g->zero_floats & 3) || (g->zero_floats && (!g->zero_base || (reinterpret_cast<uintptr_t>(g->zero_base) & 15))))
+    return "lrf_render_bwd: LrfGrads.zero_base / zero_floats must name a 16-byte aligned range of a multiple of 4 floats (or NULL / 0)";
+  P.L = make_layout(f->grid);
+  const Layout& L = P.L;
+  P.bg = make_bins(L);
+  if (P.bg.total > BIN_MAX) return "lrf_render_bwd: grid too large for the tile binning (BIN_MAX)";
+  for (int q = 0; q < 3; ++q) if ((size_t)L.ll[q] * LRF_CA * 4 > 150 * 1024) return "lrf_render_bwd: line too long for LDS accumulation";
+
+  const size_t ll_max = (size_t)max(L.ll[0], max(L.ll[1], L.ll[2]));
+  const size_t lds_ap = sizeof(float) * BCELL * BCELL * LRF_CA, lds_al = sizeof(float) * LRF_CA * ll_max;
+  const size_t lds_dp = sizeof(float) * BCELL * BCELL * LRF_CD, lds_dl = sizeof(float) * LRF_CD * ll_max;
+  const bool fit_d = 2 * (lds_dp + lds_dl) <= 158 * 1024;   // 64-bit fixed-point accumulators: twice the bytes
+  // the appearance scatter runs on fixed point too where an 8-channel tile + 24-channel line accumulators of 64-bit cells fit
+  // in LDS (lines up to 479 cells): forward + backward 1.26 -> 1.12 ms at 64^3, 1.36 -> 1.29 at 300^3, on par with the
+  // compare-and-swap kernel at 400^3-460^3 (profiles/r17_fixed_point_scatter.md); above that the compare-and-swap kernel stays
+  const size_t lds_fa = 2 * lds_dp + sizeof(unsigned long long) * LRF_CA * ll_max;
+  // ... and with FOUR channels per sweep (six sweeps, a 34.8 KB tile) where only that leaves room for the lines: 480 .. 640 cells
+  const size_t lds_fa4 = lds_dp + sizeof(unsigned long long) * LRF_CA * ll_max;
+  const bool fit_a8 = fit_d && lds_fa <= 158 * 1024, fit_a4 = fit_d && lds_fa4 <= 158 * 1024;
+  if (P.det) {
+    // LRF_FLAG_DETERMINISTIC: always the fixed-point kernels (whatever the debug switches say); lines that leave no room for them
+    // in LDS (density: > 1439 cells, appearance: > 640 cells -- the reference ends at 640^3) are refused
+    if (!fit_a8 && !fit_a4)
+      return "lrf_render_bwd: LRF_FLAG_DETERMINISTIC covers lines up to 640 cells (the fixed-point line accumulators of the "
+             "appearance scatter must fit in LDS)";
+    P.dens = DensEng::Det;
+    P.app = fit_a8 ? AppEng::Det8 : AppEng::Det4;
+  } else {
+    const bool fix_d = g_scatter_fix && g_scatter_fused && fit_d, fix_a = fix_d && (g_scatter_fix & 2);
+    P.dens = fix_d ? DensEng::Fix : (g_scatter_fused && lds_dp + lds_dl <= 64 * 1024) ? DensEng::CasFused : DensEng::CasSplit;
+    P.app = (fix_a && fit_a8) ? AppEng::Fix8 : (fix_a && !(g_scatter_fix & 4) && fit_a4) ? AppEng::Fix4
+          : (g_scatter_fused && lds_ap + lds_al <= 158 * 1024) ? AppEng::CasFused : AppEng::CasSplit;
+  }
+  P.dens_lds = (P.dens == DensEng::Det || P.dens == DensEng::Fix) ? 2 * (lds_dp + lds_dl) : P.dens == DensEng::CasFused ? lds_dp + lds_dl : lds_dp;
+  P.dens_line_lds = lds_dl;
+  P.app_lds = (P.app == AppEng::Det8 || P.app == AppEng::Fix8) ? lds_fa : (P.app == AppEng::Det4 || P.app == AppEng::Fix4) ? lds_fa4
+            : P.app == AppEng::CasFused ? lds_ap + lds_al : lds_ap;
+  P.app_line_lds = lds_al;
+  P.app3_fix = P.app != AppEng::CasFused && P.app != AppEng::CasSplit;
+
+  P.b = carve_bwd(workspace, R, S, f->grid, P.gen_ld, P.det);
+  P.nblk = (int)((P.b.nmax + BIN_CHUNK - 1) / BIN_CHUNK);
+  // LRF_FLAG_PLANE_EVENTS (data parallel): one pass per plane, an event behind planes 0 and 1 -- a collective over plane p's
+  // gradient (8.6 MB each at 300^3) starts while the later planes are still being scattered; otherwise one pass over all bins
+  P.npass = (flags & LRF_FLAG_PLANE_EVENTS) ? 3 : 1;
+  P.sort = sorts_rays(R, flags);
+  P.d = make_dfield(f);
+  P.d.rdir = P.b.fw.rdir;
+  P.gc = gen_cfg(P.d.fea_pe, P.d.view_pe, P.d.fc, !(flags & LRF_FLAG_PE_OFF));
+  return nullptr;
+}
+}  // namespace lrf
+
+// plan_bwd, then the launches: a refused call enqueues nothing
 extern "C" int lrf_render_bwd(const LrfField* f, const LrfParams* p, const float* rays, const float* z,
                               int32_t R, int32_t S, uint32_t flags, const float* g_rgb, const float* g_depth,
                               const LrfGrads* g, float* g_rays, void* workspace, void* stream) {
   using namespace lrf;
-  if (!f || !f->cache || !p || !rays || !z || !g_rgb || !g_depth || !g || !g_rays || !workspace)
-    return set_err("lrf_render_bwd: null argument");
-  if (R <= 0 || S < 2 || S > LRF_MAX_S_TRAIN)
-    return set_err("lrf_render_bwd: need R > 0 and 2 <= S <= LRF_MAX_S_TRAIN (2048: the per-ray backward keeps 16 B per sample in LDS)");
-  if (flags & ~LRF_FLAG_ALL) return set_err("lrf_render_bwd: unknown flag bits");
-  if (const char* bad = gen_check(f)) return set_err(bad);
+  BwdPlan P;
+  if (const char* bad = plan_bwd(P, f, p, rays, z, R, S, flags, g_rgb, g_depth, g, g_rays, workspace)) return set_err(bad);
+  LRF_HIP(lds_opt_in());
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  DField d = make_dfield(f);
-  const Layout L = make_layout(f->grid);
-  const int gen_ld = field_gen_ld(f->fea_pe, f->view_pe, f->feature_c, flags);
-  const bool generic = gen_ld != 0;
-  const bool det = (flags & LRF_FLAG_DETERMINISTIC) != 0;
-  if (det && generic)
-    return set_err("lrf_render_bwd: LRF_FLAG_DETERMINISTIC does not cover the generic engine (a network other than fea_pe = view_pe = 0, "
-                   "featureC = 128, or LRF_FLAG_MLP_VALU): its weight-gradient GEMM adds row chunks with fp32 atomics");
-  const BwdWorkspace b = carve_bwd(workspace, R, S, f->grid, gen_ld, det);
+  DField d = P.d;
+  const Layout& L = P.L;
+  const BinGeom& bg = P.bg;
+  const BwdWorkspace& b = P.b;
   const Workspace& w = b.fw;
+  const GenCfg& gc = P.gc;
   const int cus = device_cus();
   const int nwg_scatter = g_scatter_wgs > 0 ? g_scatter_wgs : cus;
-  d.rdir = w.rdir;                                         // per-ray unit directions: written by k_march (the saved forward's, or the one below), read by k_scatter_fix
   if (flags & LRF_FLAG_ROWS_SAVED) {                       // lrf_render_fwd_train sorted (or not) with the same flags: same workspace
-    if ((flags & LRF_FLAG_SORT_RAYS) && R <= LRF_SORT_MAX_R && R >= 2) { d.perm = w.perm; rays = w.rays_s; }
-  } else {
+    if (P.sort) { d.perm = w.perm; rays = w.rays_s; }
+  } else {                                                 // otherwise lrf_render_fwd_train left all of this in place
     rays = sort_rays_if_asked(d, rays, R, flags, w, st);
-  }
-  {
-    static std::once_flag lds_attr_once[64];   // dynamic LDS above 64 KB has to be opted into once per device
-    static hipError_t lds_attr_err[64];
-    int dev_id = 0;
-    LRF_HIP(hipGetDevice(&dev_id));
-    std::call_once(lds_attr_once[dev_id & 63], [dev_id] {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_scatter_plane<LRF_CA, true, LRF_APP_NT, false>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_scatter_plane<LRF_CA, true, LRF_APP_NT, true>),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_scatter_plane<LRF_CD, false, 512, true>),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_scatter_line<LRF_CA, true, 1024>),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_scatter_line<LRF_CD, false, 1024>),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bwd_ray),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, 14 * LRF_MAX_S_TRAIN * 4 + BIN_MAX * 4);
-      if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_train_dgrad3<8>),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256);
-      if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_train_app3<8, false>),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-      if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_train_app3<8, true>),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-      if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_scatter_fix<LRF_CD, false, FIX_NT>),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_scatter_fix<LRF_CA, true, FIX_NT>),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_scatter_fix<LRF_CA, true, FIX_NT, 4>),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_scatter_det<LRF_CD, false, FIX_NT>),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_scatter_det<LRF_CA, true, FIX_NT>),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_scatter_det<LRF_CA, true, FIX_NT, 4>),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_wgrad_w2w3<128>),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)w23_lds(128));
-      if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_wgrad_w2w3<64>),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)w23_lds(64));
-      lds_attr_err[dev_id & 63] = e;
-    });
-    LRF_HIP(lds_attr_err[dev_id & 63]);
-  }
-  if (!(flags & LRF_FLAG_ROWS_SAVED)) {            // otherwise lrf_render_fwd_train left all of this in place
-    d.rdir = w.rdir;
     launch_march(d, rays, z, R, S, flags, 0.0f, b.depth, w.acc, nullptr, w.ncomp, w.cidx, w.cw, b.feat, st);
     LRF_HIP(launch_shade_save(d, rays, z, S, R, flags, w, b, b.rgb, st));
   }
@@ -1978,13 +2011,11 @@ extern "C" int lrf_render_bwd(const LrfField* f, const LrfParams* p, const float
     dst_d.plane[q] = g->density_plane[q]; dst_d.line[q] = g->density_line[q];
     dst_a.plane[q] = g->app_plane[q]; dst_a.line[q] = g->app_line[q];
   }
-  if (g->zero_floats < 0 || (g->zero_floats & 3) || (g->zero_floats && (!g->zero_base || (reinterpret_cast<uintptr_t>(g->zero_base) & 15))))
-    return set_err("lrf_render_bwd: LrfGrads.zero_base / zero_floats must name a 16-byte aligned range of a multiple of 4 floats (or NULL / 0)");
   {
     const long long zf4 = g->zero_floats / 4;
     const unsigned nblk_clear = (unsigned)(BIN_CLEAR_BLOCKS + (zf4 + ZERO_F4_PER_BLOCK - 1) / ZERO_F4_PER_BLOCK);
     hipLaunchKernelGGL(k_clear_bins, dim3(nblk_clear), dim3(256), 0, st, b.hist, b.hist2, reinterpret_cast<float4*>(g->zero_base), zf4);     // (in front of the fork: both branches count into these)
-    if (det) {                                             // the int64 gradient image: the same kernel once more (its bins part again)
+    if (P.det) {                                           // the int64 gradient image: the same kernel once more (its bins part again)
       const long long if4 = b.det_words / 2;
       hipLaunchKernelGGL(k_clear_bins, dim3((unsigned)(BIN_CLEAR_BLOCKS + (if4 + ZERO_F4_PER_BLOCK - 1) / ZERO_F4_PER_BLOCK)), dim3(256), 0, st,
                          b.hist, b.hist2, reinterpret_cast<float4*>(b.det_img), if4);
@@ -1996,52 +2027,23 @@ extern "C" int lrf_render_bwd(const LrfField* f, const LrfParams* p, const float
     LRF_HIP(hipStreamWaitEvent(ss->s, ss->fork, 0));
     sb = ss->s;
   }
-  const BinGeom bg = make_bins(L);
-  if (bg.total > BIN_MAX) return set_err("lrf_render_bwd: grid too large for the tile binning (BIN_MAX)");
-  const int nblk = (int)((b.nmax + BIN_CHUNK - 1) / BIN_CHUNK);
-  for (int q = 0; q < 3; ++q) if ((size_t)L.ll[q] * LRF_CA * 4 > 150 * 1024) return set_err("lrf_render_bwd: line too long for LDS accumulation");
 
   // ---- caller's stream: data gradient of the colour network, then its appearance half (dX, position gradient, dbasis)
   const int n_dgrad_wg = min(cus, WGRAD_MAXCH);            // one dW1 / dbasis partial block per workgroup (k_wgrad_reduce: fixed count)
-  const GenCfg gc = gen_cfg(d.fea_pe, d.view_pe, d.fc, !(flags & LRF_FLAG_PE_OFF));
-  if (generic) {       // lrf_generic.inl: one lane per row; worst-case grid, rows behind the batch's last tile return at once
-    LRF_HIP(gen_opt_in());
+  if (P.generic) {     // lrf_generic.inl: one lane per row; worst-case grid, rows behind the batch's last tile return at once
     const int ls = gen_tile_samples(gc, true), nt = gen_block_threads(gc);
     const size_t lds = (size_t)gen_lds(gc, ls, true).total * 4;
     const dim3 grid((unsigned)((b.nmax + ls - 1) / ls));
-    if (ls == 32) hipLaunchKernelGGL(k_gen_dgrad<32>, grid, dim3(nt), lds, st, d, gc, rays, S, w.toff, R, b.tileinfo, w.cidx, w.cw, b.crgb, g_rgb, b.act, b.grd, b.rowinfo, b.gen, gen_ld);
-    else          hipLaunchKernelGGL(k_gen_dgrad<16>, grid, dim3(nt), lds, st, d, gc, rays, S, w.toff, R, b.tileinfo, w.cidx, w.cw, b.crgb, g_rgb, b.act, b.grd, b.rowinfo, b.gen, gen_ld);
+    if (ls == 32) hipLaunchKernelGGL(k_gen_dgrad<32>, grid, dim3(nt), lds, st, d, gc, rays, S, w.toff, R, b.tileinfo, w.cidx, w.cw, b.crgb, g_rgb, b.act, b.grd, b.rowinfo, b.gen, P.gen_ld);
+    else          hipLaunchKernelGGL(k_gen_dgrad<16>, grid, dim3(nt), lds, st, d, gc, rays, S, w.toff, R, b.tileinfo, w.cidx, w.cw, b.crgb, g_rgb, b.act, b.grd, b.rowinfo, b.gen, P.gen_ld);
   } else {
     hipLaunchKernelGGL((k_train_dgrad3<8>), dim3(n_dgrad_wg), dim3(512), (size_t)W32T_ALL_U4 * 16 + 4 * 64 * 16, st, d,
                        d.mlpwt, rays, S, w.toff, R, b.tileinfo, w.cidx, w.cw, b.crgb, g_rgb,
                        b.grd, b.rowinfo, b.relu_bits, b.act, b.wpart, g_dgrad_dbg & 5);
   }
   if (ss) LRF_HIP(hipEventRecord(ss->app[0], st));         // go / dfeat rows: the weight-gradient kernel may start
-  const size_t ll_max = (size_t)max(L.ll[0], max(L.ll[1], L.ll[2]));
-  const size_t lds_ap = sizeof(float) * BCELL * BCELL * LRF_CA, lds_al = sizeof(float) * LRF_CA * ll_max;
-  const bool fuse_a = g_scatter_fused && lds_ap + lds_al <= 158 * 1024;
-  // line gradients ride on the plane pass when tile + line accumulators fit in LDS (g_scatter_fused; appearance at 640^3 does not)
-  const size_t lds_dp = sizeof(float) * BCELL * BCELL * LRF_CD, lds_dl = sizeof(float) * LRF_CD * ll_max;
-  const bool fuse_d = g_scatter_fused && lds_dp + lds_dl <= 64 * 1024;
-  const bool fix_d = g_scatter_fix && g_scatter_fused && 2 * (lds_dp + lds_dl) <= 158 * 1024;   // 64-bit fixed-point accumulators: twice the bytes
-  // the appearance scatter runs on fixed point too where an 8-channel tile + 24-channel line accumulators of 64-bit cells fit
-  // in LDS (lines up to 479 cells): forward + backward 1.26 -> 1.12 ms at 64^3, 1.36 -> 1.29 at 300^3, on par with the
-  // compare-and-swap kernel at 400^3-460^3 (profiles/r17_fixed_point_scatter.md); above that the compare-and-swap kernel stays
-  const size_t lds_fa = 2 * lds_dp + sizeof(unsigned long long) * LRF_CA * ll_max;
-  const bool fix_a8 = fix_d && (g_scatter_fix & 2) && lds_fa <= 158 * 1024;
-  // ... and with FOUR channels per sweep (six sweeps, a 34.8 KB tile) where only that leaves room for the lines: 480 .. 640 cells
-  const size_t lds_fa4 = lds_dp + sizeof(unsigned long long) * LRF_CA * ll_max;
-  const bool fix_a4 = fix_d && (g_scatter_fix & 2) && !fix_a8 && !(g_scatter_fix & 4) && lds_fa4 <= 158 * 1024;
-  const bool fix_a = fix_a8 || fix_a4;
-  // LRF_FLAG_DETERMINISTIC: always the fixed-point kernels (whatever the debug switches say); lines that leave no room for them
-  // in LDS (density: > 1439 cells, appearance: > 640 cells -- the reference ends at 640^3) are refused
-  const bool det_a8 = 2 * (lds_dp + lds_dl) <= 158 * 1024 && lds_fa <= 158 * 1024;
-  const bool det_a4 = !det_a8 && 2 * (lds_dp + lds_dl) <= 158 * 1024 && lds_fa4 <= 158 * 1024;
-  if (det && !det_a8 && !det_a4)
-    return set_err("lrf_render_bwd: LRF_FLAG_DETERMINISTIC covers lines up to 640 cells (the fixed-point line accumulators of the "
-                   "appearance scatter must fit in LDS)");
   unsigned* vmax_a = reinterpret_cast<unsigned*>(b.hist2 + 2 * BIN_MAX);
-  if (fix_a || det)
+  if (P.app3_fix)
     hipLaunchKernelGGL((k_train_app3<8, true>), dim3(n_dgrad_wg), dim3(512), app3_lds_bytes(S, 8, bg.total), st, d,
                        d.mlpwt, rays, z, S, w.toff, R, b.tileinfo, w.cidx,
                        b.grd, b.rpart, w.pmax, b.wpart, bg, b.tid2, b.hist2, b.nmax, g_dgrad_dbg & 3, vmax_a);
@@ -2063,25 +2065,27 @@ extern "C" int lrf_render_bwd(const LrfField* f, const LrfParams* p, const float
     }
     hipLaunchKernelGGL(k_det_convert, dim3(cus * 8), dim3(256), 0, s, dc, bg, offs, vmax, p_lo, p_hi);
   };
-  if (det) {
-    hipLaunchKernelGGL(k_bin_fill, dim3(nblk), dim3(256), 0, sb, bg, b.nmax, R, S, w.toff, 0, b.tid, b.hist, b.cursor, b.offs, b.list);
-    hipLaunchKernelGGL((k_scatter_det<LRF_CD, false, FIX_NT>), dim3(nwg_scatter), dim3(FIX_NT), 2 * (lds_dp + lds_dl), sb,
-                       d, bg, b.det_d, rays, z, S, b.offs, b.list, b.feat, b.rowinfo, b.grd, vmax_d, 0, bg.total);
-    det_convert(b.det_d, g->density_plane, g->density_line, LRF_CD, b.offs, vmax_d, 0, 3, sb);
-  } else if (fix_d) {
-    hipLaunchKernelGGL(k_bin_fill, dim3(nblk), dim3(256), 0, sb, bg, b.nmax, R, S, w.toff, 0, b.tid, b.hist, b.cursor, b.offs, b.list);
-    hipLaunchKernelGGL((k_scatter_fix<LRF_CD, false, FIX_NT>), dim3(nwg_scatter), dim3(FIX_NT), 2 * (lds_dp + lds_dl), sb,
-                       d, bg, dst_d, rays, z, S, b.offs, b.list, b.feat, b.rowinfo, b.grd, vmax_d, 0, bg.total);
-  } else if (fuse_d) {
-    hipLaunchKernelGGL(k_bin_fill, dim3(nblk), dim3(256), 0, sb, bg, b.nmax, R, S, w.toff, 0, b.tid, b.hist, b.cursor, b.offs, b.list);
-    hipLaunchKernelGGL((k_scatter_plane<LRF_CD, false, 512, true>), dim3(nwg_scatter * LRF_DPLANE_MULT), dim3(512), lds_dp + lds_dl, sb,
-                       d, bg, dst_d, rays, z, S, b.offs, b.list, b.feat, b.rowinfo, b.grd, 0, bg.total);
-  } else {
-    hipLaunchKernelGGL(k_bin_fill, dim3(nblk), dim3(256), 0, sb, bg, b.nmax, R, S, w.toff, 0, b.tid, b.hist, b.cursor, b.offs, b.list);
-    hipLaunchKernelGGL((k_scatter_plane<LRF_CD, false, 512, false>), dim3(nwg_scatter * LRF_DPLANE_MULT), dim3(512), lds_dp, sb,
-                       d, bg, dst_d, rays, z, S, b.offs, b.list, b.feat, b.rowinfo, b.grd, 0, bg.total);
-    hipLaunchKernelGGL((k_scatter_line<LRF_CD, false, 1024>), dim3(3 * LINE_WGS), dim3(1024), lds_dl, sb,
-                       d, dst_d, rays, z, R, S, w.toff, b.feat, b.rowinfo, b.grd);
+  hipLaunchKernelGGL(k_bin_fill, dim3(P.nblk), dim3(256), 0, sb, bg, b.nmax, R, S, w.toff, 0, b.tid, b.hist, b.cursor, b.offs, b.list);
+  switch (P.dens) {
+    case DensEng::Det:
+      hipLaunchKernelGGL((k_scatter_det<LRF_CD, false, FIX_NT>), dim3(nwg_scatter), dim3(FIX_NT), P.dens_lds, sb,
+                         d, bg, b.det_d, rays, z, S, b.offs, b.list, b.feat, b.rowinfo, b.grd, vmax_d, 0, bg.total);
+      det_convert(b.det_d, g->density_plane, g->density_line, LRF_CD, b.offs, vmax_d, 0, 3, sb);
+      break;
+    case DensEng::Fix:
+      hipLaunchKernelGGL((k_scatter_fix<LRF_CD, false, FIX_NT>), dim3(nwg_scatter), dim3(FIX_NT), P.dens_lds, sb,
+                         d, bg, dst_d, rays, z, S, b.offs, b.list, b.feat, b.rowinfo, b.grd, vmax_d, 0, bg.total);
+      break;
+    case DensEng::CasFused:
+      hipLaunchKernelGGL((k_scatter_plane<LRF_CD, false, 512, true>), dim3(nwg_scatter * LRF_DPLANE_MULT), dim3(512), P.dens_lds, sb,
+                         d, bg, dst_d, rays, z, S, b.offs, b.list, b.feat, b.rowinfo, b.grd, 0, bg.total);
+      break;
+    case DensEng::CasSplit:
+      hipLaunchKernelGGL((k_scatter_plane<LRF_CD, false, 512, false>), dim3(nwg_scatter * LRF_DPLANE_MULT), dim3(512), P.dens_lds, sb,
+                         d, bg, dst_d, rays, z, S, b.offs, b.list, b.feat, b.rowinfo, b.grd, 0, bg.total);
+      hipLaunchKernelGGL((k_scatter_line<LRF_CD, false, 1024>), dim3(3 * LINE_WGS), dim3(1024), P.dens_line_lds, sb,
+                         d, dst_d, rays, z, R, S, w.toff, b.feat, b.rowinfo, b.grd);
+      break;
   }
   if (sx) LRF_HIP(hipEventRecord(sx->bucket[0], sb));
 
@@ -2090,12 +2094,12 @@ extern "C" int lrf_render_bwd(const LrfField* f, const LrfParams* p, const float
   const int nch_max = WGRAD_MAXCH;      // (blocks behind the last chunk of the actual row count return at once)
   const bool w23_on_st = !ss || g_wgrad_split > 0;
   if (!w23_on_st) LRF_HIP(hipStreamWaitEvent(sb, ss->app[0], 0));
-  if (generic) {       // dW = A^T B over the operand rows k_gen_dgrad left (added straight into the reference-layout gradients)
+  if (P.generic) {     // dW = A^T B over the operand rows k_gen_dgrad left (added straight into the reference-layout gradients)
     const GenRowOff ro = gen_row_off(gc);
     const int nchunk = (int)((b.nmax + GEN_GEMM_CHUNK - 1) / GEN_GEMM_CHUNK);
     auto gemm = [&](int offA, int M, int offB, int N, float* dW, int ldw, float* db) {
       hipLaunchKernelGGL(k_gen_gemm, dim3(((M + 63) / 64) * ((N + 63) / 64), nchunk), dim3(256), 0, w23_on_st ? st : sb,
-                         b.gen, gen_ld, offA, M, offB, N, w.toff, R, dW, ldw, db);
+                         b.gen, P.gen_ld, offA, M, offB, N, w.toff, R, dW, ldw, db);
     };
     gemm(ro.dz1, gc.fc, ro.x1, gc.in1 + 1, g->w1, gc.in1, g->b1);
     gemm(ro.dz2, gc.fc, ro.h1, gc.fc + 1, g->w2, gc.fc, g->b2);
@@ -2117,14 +2121,14 @@ extern "C" int lrf_render_bwd(const LrfField* f, const LrfParams* p, const float
       segs.s[nseg++] = WgradSeg{off, ld, n_off, m, n, dst_ld, elems, x_slots, nch, dst};
       elems += m * n;
     };
-    if (!generic) {
+    if (!P.generic) {
       seg(WP_W2, 144, 0, 128, 128, g->w2, 128);
       seg(WP_W2, 144, 128, 128, 1, g->b2, 1);
       seg(WP_W1, 32, 0, 128, LRF_APP_DIM, g->w1, LRF_APP_DIM, 0, n_dgrad_wg);     // accumulated by k_train_dgrad3: one block per workgroup
       seg(WP_W1, 32, LRF_APP_DIM, 128, 1, g->b1, 1, 0, n_dgrad_wg);
     }
     seg(WP_BAS, 96, 0, LRF_APP_DIM, 72, g->basis, 72, 1, n_dgrad_wg);   // accumulated by k_train_app3: one block per workgroup
-    if (!generic) {
+    if (!P.generic) {
       seg(WP_W3, 144, 0, 3, LRF_FEATC + 3, g->w3, LRF_FEATC + 3);
       seg(WP_W3, 144, LRF_FEATC + 3, 3, 1, g->b3, 1);
     }
@@ -2136,37 +2140,40 @@ extern "C" int lrf_render_bwd(const LrfField* f, const LrfParams* p, const float
   if (ss) LRF_HIP(hipEventRecord(ss->join, sb));
 
   // ---- caller's stream: appearance scatter (its own bin buffers: the density scatter may still be running)
-  hipLaunchKernelGGL(k_bin_fill, dim3(nblk), dim3(256), 0, st, bg, b.nmax, R, S, w.toff, 1, b.tid2, b.hist2, b.cursor2, b.offs2, b.list2);
-  // LRF_FLAG_PLANE_EVENTS (data parallel): one pass per plane, an event behind planes 0 and 1 -- a collective over plane p's
-  // gradient (8.6 MB each at 300^3) starts while the later planes are still being scattered; otherwise one pass over all bins
-  const int npass = (flags & LRF_FLAG_PLANE_EVENTS) ? 3 : 1;
-  for (int q = 0; q < npass; ++q) {
-    const int blo = npass == 1 ? 0 : bg.base[q], bhi = (npass == 1 || q == 2) ? bg.total : bg.base[q + 1];
-    if (det) {
-      if (det_a8)
-        hipLaunchKernelGGL((k_scatter_det<LRF_CA, true, FIX_NT>), dim3(nwg_scatter), dim3(FIX_NT), lds_fa, st,
+  hipLaunchKernelGGL(k_bin_fill, dim3(P.nblk), dim3(256), 0, st, bg, b.nmax, R, S, w.toff, 1, b.tid2, b.hist2, b.cursor2, b.offs2, b.list2);
+  for (int q = 0; q < P.npass; ++q) {
+    const int blo = P.npass == 1 ? 0 : bg.base[q], bhi = (P.npass == 1 || q == 2) ? bg.total : bg.base[q + 1];
+    switch (P.app) {
+      case AppEng::Det8:
+        hipLaunchKernelGGL((k_scatter_det<LRF_CA, true, FIX_NT>), dim3(nwg_scatter), dim3(FIX_NT), P.app_lds, st,
                            d, bg, b.det_a, rays, z, S, b.offs2, b.list2, b.feat, b.rowinfo, b.grd, vmax_a, blo, bhi);
-      else
-        hipLaunchKernelGGL((k_scatter_det<LRF_CA, true, FIX_NT, 4>), dim3(nwg_scatter), dim3(FIX_NT), lds_fa4, st,
+        break;
+      case AppEng::Det4:
+        hipLaunchKernelGGL((k_scatter_det<LRF_CA, true, FIX_NT, 4>), dim3(nwg_scatter), dim3(FIX_NT), P.app_lds, st,
                            d, bg, b.det_a, rays, z, S, b.offs2, b.list2, b.feat, b.rowinfo, b.grd, vmax_a, blo, bhi);
-      det_convert(b.det_a, g->app_plane, g->app_line, LRF_CA, b.offs2, vmax_a, npass == 1 ? 0 : q, npass == 1 ? 3 : q + 1, st);
-    } else if (fix_a8) {
-      hipLaunchKernelGGL((k_scatter_fix<LRF_CA, true, FIX_NT>), dim3(nwg_scatter), dim3(FIX_NT), lds_fa, st,
-                         d, bg, dst_a, rays, z, S, b.offs2, b.list2, b.feat, b.rowinfo, b.grd, vmax_a, blo, bhi);
-    } else if (fix_a4) {
-      hipLaunchKernelGGL((k_scatter_fix<LRF_CA, true, FIX_NT, 4>), dim3(nwg_scatter), dim3(FIX_NT), lds_fa4, st,
-                         d, bg, dst_a, rays, z, S, b.offs2, b.list2, b.feat, b.rowinfo, b.grd, vmax_a, blo, bhi);
-    } else if (fuse_a) {
-      hipLaunchKernelGGL((k_scatter_plane<LRF_CA, true, LRF_APP_NT, true>), dim3(nwg_scatter), dim3(LRF_APP_NT), lds_ap + lds_al, st,
-                         d, bg, dst_a, rays, z, S, b.offs2, b.list2, b.feat, b.rowinfo, b.grd, blo, bhi);
-    } else {
-      hipLaunchKernelGGL((k_scatter_plane<LRF_CA, true, LRF_APP_NT, false>), dim3(nwg_scatter), dim3(LRF_APP_NT), lds_ap, st,
-                         d, bg, dst_a, rays, z, S, b.offs2, b.list2, b.feat, b.rowinfo, b.grd, blo, bhi);
+        break;
+      case AppEng::Fix8:
+        hipLaunchKernelGGL((k_scatter_fix<LRF_CA, true, FIX_NT>), dim3(nwg_scatter), dim3(FIX_NT), P.app_lds, st,
+                           d, bg, dst_a, rays, z, S, b.offs2, b.list2, b.feat, b.rowinfo, b.grd, vmax_a, blo, bhi);
+        break;
+      case AppEng::Fix4:
+        hipLaunchKernelGGL((k_scatter_fix<LRF_CA, true, FIX_NT, 4>), dim3(nwg_scatter), dim3(FIX_NT), P.app_lds, st,
+                           d, bg, dst_a, rays, z, S, b.offs2, b.list2, b.feat, b.rowinfo, b.grd, vmax_a, blo, bhi);
+        break;
+      case AppEng::CasFused:
+        hipLaunchKernelGGL((k_scatter_plane<LRF_CA, true, LRF_APP_NT, true>), dim3(nwg_scatter), dim3(LRF_APP_NT), P.app_lds, st,
+                           d, bg, dst_a, rays, z, S, b.offs2, b.list2, b.feat, b.rowinfo, b.grd, blo, bhi);
+        break;
+      case AppEng::CasSplit:        // (the lines: k_scatter_line behind the passes)
+        hipLaunchKernelGGL((k_scatter_plane<LRF_CA, true, LRF_APP_NT, false>), dim3(nwg_scatter), dim3(LRF_APP_NT), P.app_lds, st,
+                           d, bg, dst_a, rays, z, S, b.offs2, b.list2, b.feat, b.rowinfo, b.grd, blo, bhi);
+        break;
     }
-    if (npass == 3 && q < 2 && sx) LRF_HIP(hipEventRecord(sx->bucket[3 + q], st));    // app_plane[q] is final (its line only if fused: bucket 2)
+    if (P.det) det_convert(b.det_a, g->app_plane, g->app_line, LRF_CA, b.offs2, vmax_a, P.npass == 1 ? 0 : q, P.npass == 1 ? 3 : q + 1, st);
+    if (P.npass == 3 && q < 2 && sx) LRF_HIP(hipEventRecord(sx->bucket[3 + q], st));    // app_plane[q] is final (its line only if fused: bucket 2)
   }
-  if (!fuse_a && !fix_a && !det)
-    hipLaunchKernelGGL((k_scatter_line<LRF_CA, true, 1024>), dim3(3 * LINE_WGS), dim3(1024), lds_al, st,
+  if (P.app == AppEng::CasSplit)
+    hipLaunchKernelGGL((k_scatter_line<LRF_CA, true, 1024>), dim3(3 * LINE_WGS), dim3(1024), P.app_line_lds, st,
                        d, dst_a, rays, z, R, S, w.toff, b.feat, b.rowinfo, b.grd);
 
   // ---- join: both branches done
@@ -2174,7 +2181,7 @@ extern "C" int lrf_render_bwd(const LrfField* f, const LrfParams* p, const float
   hipLaunchKernelGGL(k_rays_add_rpart, dim3((R + 255) / 256), dim3(256), 0, st, rays, R, w.ncomp, b.rpart, w.pmax, g_rays, d.perm);
   if (sx) {
     LRF_HIP(hipEventRecord(sx->bucket[2], st));
-    if (npass == 1) { LRF_HIP(hipEventRecord(sx->bucket[3], st)); LRF_HIP(hipEventRecord(sx->bucket[4], st)); }   // no per-plane passes: the planes are final with everything else
+    if (P.npass == 1) { LRF_HIP(hipEventRecord(sx->bucket[3], st)); LRF_HIP(hipEventRecord(sx->bucket[4], st)); }   // no per-plane passes: the planes are final with everything else
     sx->bucket_set = true;
   }
   LRF_HIP(hipGetLastError());

@@ -950,22 +950,19 @@ static SideStream* side_stream() {
   }
   return &x;
 }
+// Dynamic LDS above 64 KB has to be opted into, once per device, before the first launch that asks for it: every render-path
+// entry point calls this once its arguments are accepted (defined behind lrf_backward.inl, whose kernels it names too).
+static hipError_t lds_opt_in();
+
 // LRF_FLAG_SORT_RAYS: sort the batch by direction (k_sort_rays) into the workspace; returns the rays the kernels should read
 // and sets d.perm.  Batches beyond the 16-bit index of the sort words are rendered in the caller's order.
 constexpr int LRF_SORT_MAX_R = 32768;
+static bool sorts_rays(int R, uint32_t flags) { return (flags & LRF_FLAG_SORT_RAYS) && R >= 2 && R <= LRF_SORT_MAX_R; }
 static const float* sort_rays_if_asked(DField& d, const float* rays, int R, uint32_t flags, const Workspace& w, hipStream_t st) {
   d.perm = nullptr;
-  if (!(flags & LRF_FLAG_SORT_RAYS) || R > LRF_SORT_MAX_R || R < 2) return rays;
+  if (!sorts_rays(R, flags)) return rays;
   int N = 2;
   while (N < R) N <<= 1;
-  if ((size_t)N * 4 > 64 * 1024) {
-    static std::once_flag once[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) == hipSuccess)
-      std::call_once(once[dev & 63], [] {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_sort_rays), hipFuncAttributeMaxDynamicSharedMemorySize, LRF_SORT_MAX_R * 4);
-      });
-  }
   hipLaunchKernelGGL(k_sort_rays, dim3(1), dim3(1024), (size_t)N * 4, st, rays, R, N, w.rays_s, w.perm);
   d.perm = w.perm;
   return w.rays_s;
@@ -991,21 +988,7 @@ static void launch_march(const DField& d, const float* rays, const float* z, int
   const int nw = march_lds_rays(d.ll, S);
   if (nw) {
     const size_t lds = (size_t)nw * S * sizeof(float) + lds_l;
-    if (lds > 64 * 1024) {
-      static std::once_flag attr_once[64];                  // per device; host threads may render concurrently
-      int dev = 0;
-      if (hipGetDevice(&dev) == hipSuccess)
-        std::call_once(attr_once[dev & 63], [] {
-          (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_march<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        });
-    }
     if (mf) {                                              // (the caller made sure that Rf is a multiple of 16 >= nw)
-      static std::once_flag attr_once_m[64];
-      int dev = 0;
-      if (lds > 64 * 1024 && hipGetDevice(&dev) == hipSuccess)
-        std::call_once(attr_once_m[dev & 63], [] {
-          (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_march<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        });
       hipLaunchKernelGGL((k_march<true, true>), dim3((R + nw - 1) / nw), dim3(64 * nw), lds, st,
                          *mf, rays, z, R, S, flags, floater, depth, acc, w_all, ncomp, cidx, cw, feat);
       return;
@@ -1021,26 +1004,11 @@ static void launch_march(const DField& d, const float* rays, const float* z, int
 // k_march's output -> colours: k_shade3 behind an in-kernel scan of the tile offsets when they fit in LDS beside the image,
 // behind k_scan_tiles_n otherwise (toff32: R + 1 ints).  sv == nullptr: the eval forward; else the training forward, which
 // also leaves the rows of SaveOut3 (and sv->toff16 must not be toff32).  dump: lrf_debug_set_dump's buffer (eval only).
-static hipError_t launch_shade3(DField d, const float* rays, const float* z, int R, int S, uint32_t flags, const Workspace& w,
-                                int* toff32, float* rgb, float* acc_out, const SaveOut3* sv, float* dump, hipStream_t st) {
+static void launch_shade3(DField d, const float* rays, const float* z, int R, int S, uint32_t flags, const Workspace& w,
+                         int* toff32, float* rgb, float* acc_out, const SaveOut3* sv, float* dump, hipStream_t st) {
   const size_t lds_base = (size_t)W32_ALL_U4 * sizeof(uint4) + (size_t)S * sizeof(float);
   const size_t lds_toff = (size_t)(R + 1) * sizeof(int) + (size_t)R * sizeof(unsigned short) + 16;
   const bool in_lds = lds_base + lds_toff + 64 <= 160 * 1024 - 256;
-  static std::once_flag attr3_once[64];                  // per device; the launch below must not overtake the opt-in on another host thread
-  static hipError_t attr3_err[64];
-  int dev = 0;
-  hipError_t e0 = hipGetDevice(&dev);
-  if (e0 != hipSuccess) return e0;
-  std::call_once(attr3_once[dev & 63], [dev] {
-    const int lim = 160 * 1024 - 256;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_shade3<8, true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, lim);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_shade3<8, false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, lim);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_shade3<8, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lim);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_shade3<8, true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lim);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_shade3<8, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lim);
-    attr3_err[dev & 63] = e;
-  });
-  if (attr3_err[dev & 63] != hipSuccess) return attr3_err[dev & 63];
   const dim3 grid(device_cus()), block(512);
   if (sv) {
     if (in_lds) {
@@ -1063,27 +1031,15 @@ static hipError_t launch_shade3(DField d, const float* rays, const float* z, int
     hipLaunchKernelGGL((k_shade3<8, false, false>), grid, block, lds_base, st,
                        d, rays, z, S, toff32, R, w.ncomp, w.cidx, w.cw, w.part, w.pmax, flags, w.acc, rgb, acc_out, SaveOut3{});
   }
-  return hipSuccess;
 }
 
 // Several fields, one launch (see MultiF): global tile offsets over all virtual rays (k_scan_tiles_n), then the colour kernel.
-static hipError_t launch_shade3_multi(const MultiF& mf, const float* rays, const float* z, int Rv, int S, uint32_t flags,
-                                      const Workspace& w, float* rgb, hipStream_t st) {
+static void launch_shade3_multi(const MultiF& mf, const float* rays, const float* z, int Rv, int S, uint32_t flags,
+                                const Workspace& w, float* rgb, hipStream_t st) {
   const size_t lds_base = (size_t)W32_ALL_U4 * sizeof(uint4) + (size_t)S * sizeof(float);
-  static std::once_flag attrm_once[64];
-  static hipError_t attrm_err[64];
-  int dev = 0;
-  hipError_t e0 = hipGetDevice(&dev);
-  if (e0 != hipSuccess) return e0;
-  std::call_once(attrm_once[dev & 63], [dev] {
-    attrm_err[dev & 63] = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_shade3m<8, false>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256);
-  });
-  if (attrm_err[dev & 63] != hipSuccess) return attrm_err[dev & 63];
   hipLaunchKernelGGL(k_scan_tiles_n<ITEM3>, dim3(1), dim3(1024), 0, st, w.ncomp, Rv, w.toff);
   hipLaunchKernelGGL((k_shade3m<8, false>), dim3(device_cus()), dim3(512), lds_base, st,
                      mf, rays, z, S, w.toff, Rv, w.ncomp, w.cidx, w.cw, w.part, w.pmax, flags, w.acc, rgb, (float*)nullptr, SaveOut3{});
-  return hipSuccess;
 }
 
 }  // namespace lrf
@@ -1099,27 +1055,9 @@ static const char* gen_check(const LrfField* f) {
     return "localrf: a non-default colour-network configuration needs the natural-layout weights in LrfField (basis, w1 .. b3)";
   return nullptr;
 }
-// dynamic LDS above 64 KB has to be opted into once per device
-static hipError_t gen_opt_in() {
-  static std::once_flag once[64];
-  static hipError_t err[64];
-  int dev = 0;
-  hipError_t e0 = hipGetDevice(&dev);
-  if (e0 != hipSuccess) return e0;
-  std::call_once(once[dev & 63], [dev] {
-    const void* ks[4] = {reinterpret_cast<const void*>(&k_shade_gen<32, false>), reinterpret_cast<const void*>(&k_shade_gen<32, true>),
-                         reinterpret_cast<const void*>(&k_gen_dgrad<32>), reinterpret_cast<const void*>(&k_gen_dgrad<16>)};
-    hipError_t e = hipSuccess;
-    for (int i = 0; i < 4 && e == hipSuccess; ++i) e = hipFuncSetAttribute(ks[i], hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024);
-    err[dev & 63] = e;
-  });
-  return err[dev & 63];
-}
 // the generic colour kernel behind k_march; toff32 != null: the training forward (also leaves colours, feat rows, tile records)
 static hipError_t launch_shade_gen(const DField& d, const GenCfg& gc, const float* rays, const float* z, int R, int S, const Workspace& w,
                                    const int* toff32, float* crgb, float* act, int4* tileinfo, hipStream_t st) {
-  hipError_t e = gen_opt_in();
-  if (e != hipSuccess) return e;
   constexpr int ls = 32;                                      // (the forward's LDS image is at most ~116 KB (fea_pe = view_pe = 6, feature_c = 256), under the 159 KB opt-in)
   const int nt = gen_block_threads(gc);
   const size_t lds = (size_t)gen_lds(gc, ls, false).total * 4;
@@ -1130,6 +1068,55 @@ static hipError_t launch_shade_gen(const DField& d, const GenCfg& gc, const floa
 }
 }  // namespace lrf
 #include "lrf_backward.inl"
+namespace lrf {
+static hipError_t lds_opt_in() {
+  constexpr int L160 = 160 * 1024;
+  static const struct { const void* k; int bytes; } tab[] = {
+    {reinterpret_cast<const void*>(&k_sort_rays), LRF_SORT_MAX_R * 4},
+    {reinterpret_cast<const void*>(&k_march<true>), L160},
+    {reinterpret_cast<const void*>(&k_march<true, true>), L160},
+    {reinterpret_cast<const void*>(&k_shade3<8, true, false>), L160 - 256},
+    {reinterpret_cast<const void*>(&k_shade3<8, false, false>), L160 - 256},
+    {reinterpret_cast<const void*>(&k_shade3<8, true, true>), L160 - 256},
+    {reinterpret_cast<const void*>(&k_shade3<8, true, false, true>), L160 - 256},
+    {reinterpret_cast<const void*>(&k_shade3<8, false, false, true>), L160 - 256},
+    {reinterpret_cast<const void*>(&k_shade3m<8, false>), L160 - 256},
+    {reinterpret_cast<const void*>(&k_shade_gen<32, false>), L160 - 1024},
+    {reinterpret_cast<const void*>(&k_shade_gen<32, true>), L160 - 1024},
+    {reinterpret_cast<const void*>(&k_gen_dgrad<32>), L160 - 1024},
+    {reinterpret_cast<const void*>(&k_gen_dgrad<16>), L160 - 1024},
+    {reinterpret_cast<const void*>(&k_scatter_plane<LRF_CA, true, LRF_APP_NT, false>), L160},
+    {reinterpret_cast<const void*>(&k_scatter_plane<LRF_CA, true, LRF_APP_NT, true>), L160},
+    {reinterpret_cast<const void*>(&k_scatter_plane<LRF_CD, false, 512, true>), L160},
+    {reinterpret_cast<const void*>(&k_scatter_line<LRF_CA, true, 1024>), L160},
+    {reinterpret_cast<const void*>(&k_scatter_line<LRF_CD, false, 1024>), L160},
+    {reinterpret_cast<const void*>(&k_bwd_ray), 14 * LRF_MAX_S_TRAIN * 4 + BIN_MAX * 4},
+    {reinterpret_cast<const void*>(&k_train_dgrad3<8>), L160 - 256},
+    {reinterpret_cast<const void*>(&k_train_app3<8, false>), 128 * 1024},
+    {reinterpret_cast<const void*>(&k_train_app3<8, true>), 128 * 1024},
+    {reinterpret_cast<const void*>(&k_scatter_fix<LRF_CD, false, FIX_NT>), L160},
+    {reinterpret_cast<const void*>(&k_scatter_fix<LRF_CA, true, FIX_NT>), L160},
+    {reinterpret_cast<const void*>(&k_scatter_fix<LRF_CA, true, FIX_NT, 4>), L160},
+    {reinterpret_cast<const void*>(&k_scatter_det<LRF_CD, false, FIX_NT>), L160},
+    {reinterpret_cast<const void*>(&k_scatter_det<LRF_CA, true, FIX_NT>), L160},
+    {reinterpret_cast<const void*>(&k_scatter_det<LRF_CA, true, FIX_NT, 4>), L160},
+    {reinterpret_cast<const void*>(&k_wgrad_w2w3<128>), (int)w23_lds(128)},
+    {reinterpret_cast<const void*>(&k_wgrad_w2w3<64>), (int)w23_lds(64)},
+  };
+  static std::once_flag once[64];        // per device; a launch on another host thread must not overtake the opt-in
+  static hipError_t err[64];
+  int dev = 0;
+  const hipError_t e0 = hipGetDevice(&dev);
+  if (e0 != hipSuccess) return e0;
+  std::call_once(once[dev & 63], [dev] {
+    hipError_t e = hipSuccess;
+    for (const auto& t : tab)
+      if (e == hipSuccess) e = hipFuncSetAttribute(t.k, hipFuncAttributeMaxDynamicSharedMemorySize, t.bytes);
+    err[dev & 63] = e;
+  });
+  return err[dev & 63];
+}
+}  // namespace lrf
 #include "lrf_scene.inl"
 #include "lrf_adam.inl"
 #include "lrf_losses.inl"
@@ -1214,36 +1201,46 @@ size_t lrf_workspace_bytes(int32_t R, int32_t S) {
   return nc > 1 ? std::max(whole, (size_t)nc * carve(nullptr, g_pipe_chunk, S).bytes) : whole;
 }
 
-// One batch of rays through k_march and the colour stage on `st`; ev (optional, lrf_render_fwd_profile): 4 events =
-// start, after k_march, after the colour kernel(s), end.
+// the colour network the split-bf16 kernels are built for: fea_pe = view_pe = 0, featureC = 128
+static bool default_net(const LrfField* f) { return gen_is_default(f->fea_pe, f->view_pe, f->feature_c ? f->feature_c : LRF_FEATC); }
+// Every refusal of the forward render, before anything is enqueued; null when the batch can be rendered.
+static const char* check_fwd(const LrfField* f, const float* rays, const float* z, const float* rgb, const float* depth,
+                             const void* workspace, int32_t R, int32_t S, uint32_t flags) {
+  if (!f || !f->cache || !rays || !z || !rgb || !depth || !workspace) return "lrf_render_fwd: null argument";
+  if (R <= 0 || S < 2 || S > 4096) return "lrf_render_fwd: need R > 0 and 2 <= S <= 4096";
+  if (flags & ~(LRF_FLAG_ALL & ~(LRF_FLAG_ROWS_SAVED | LRF_FLAG_PLANE_EVENTS))) return "lrf_render_fwd: unknown flag bits (caller built against another ABI version?)";
+  if (const char* bad = gen_check(f)) return bad;
+  if (!default_net(f) && (flags & LRF_FLAG_MLP_F32))
+    return "lrf_render_fwd: the exact-fp32 MFMA engine is built for fea_pe = view_pe = 0, featureC = 128 only";
+  return nullptr;
+}
+// the default engine: k_march -> k_shade3, two launches and no finalize kernel
+static bool fwd_shade3(const LrfField* f, uint32_t flags) { return default_net(f) && !(flags & (LRF_FLAG_MLP_VALU | LRF_FLAG_MLP_F32)); }
+
+// One batch of rays (accepted by check_fwd) through k_march and the colour stage on `st`; ev (optional,
+// lrf_render_fwd_profile): 4 events = start, after k_march, after the colour kernel(s), end.
 static int render_fwd_impl(const LrfField* f, const float* rays, const float* z, int32_t R, int32_t S,
                            uint32_t flags, float floater_thresh, float* rgb, float* depth,
                            float* weight_out, float* acc_out, void* workspace, hipStream_t st, hipEvent_t* ev) {
-  if (!f || !f->cache || !rays || !z || !rgb || !depth || !workspace) return set_err("lrf_render_fwd: null argument");
-  if (R <= 0 || S < 2 || S > 4096) return set_err("lrf_render_fwd: need R > 0 and 2 <= S <= 4096");
-  if (flags & ~(LRF_FLAG_ALL & ~(LRF_FLAG_ROWS_SAVED | LRF_FLAG_PLANE_EVENTS))) return set_err("lrf_render_fwd: unknown flag bits (caller built against another ABI version?)");
   DField d = make_dfield(f);
   const Workspace w = carve(workspace, R, S);
   if (ev) LRF_HIP(hipEventRecord(ev[0], st));
   rays = sort_rays_if_asked(d, rays, R, flags, w, st);
-  if (const char* bad = gen_check(f)) return set_err(bad);
-  const bool generic = !gen_is_default(d.fea_pe, d.view_pe, d.fc);
-  if (generic && (flags & LRF_FLAG_MLP_F32)) return set_err("lrf_render_fwd: the exact-fp32 MFMA engine is built for fea_pe = view_pe = 0, featureC = 128 only");
-  if (!generic && !(flags & (LRF_FLAG_MLP_VALU | LRF_FLAG_MLP_F32))) {
+  if (fwd_shade3(f, flags)) {
     // Default engine: k_march -> k_shade3 (32 samples per wave on v_mfma_f32_32x32x16_bf16, lrf_shade3.inl); the tile
     // offsets are scanned inside the colour kernel when they fit in LDS beside the image, by k_scan_tiles_n otherwise.
     d.rdir = w.rdir;
     launch_march(d, rays, z, R, S, flags, floater_thresh, depth, w.acc, weight_out, w.ncomp, w.cidx, w.cw, nullptr, st);
     if (ev) LRF_HIP(hipEventRecord(ev[1], st));
-    LRF_HIP(launch_shade3(d, rays, z, R, S, flags, w, w.toff, rgb, acc_out, nullptr, g_dump, st));
+    launch_shade3(d, rays, z, R, S, flags, w, w.toff, rgb, acc_out, nullptr, g_dump, st);
     if (ev) { LRF_HIP(hipEventRecord(ev[2], st)); LRF_HIP(hipEventRecord(ev[3], st)); }
     LRF_HIP(hipGetLastError());
-    return 2;            // (internal) done, two launches: no finalize interval
+    return 0;
   }
   // exact-fp32 / plain-loop engines: 16-sample tiles, k_march -> [k_scan_tiles ->] colour kernel -> k_finalize
   launch_march(d, rays, z, R, S, flags, floater_thresh, depth, w.acc, weight_out, w.ncomp, w.cidx, w.cw, nullptr, st);
   if (ev) LRF_HIP(hipEventRecord(ev[1], st));
-  if (generic || (flags & LRF_FLAG_MLP_VALU)) {
+  if (!default_net(f) || (flags & LRF_FLAG_MLP_VALU)) {
     const GenCfg gc = gen_cfg(d.fea_pe, d.view_pe, d.fc, !(flags & LRF_FLAG_PE_OFF));
     LRF_HIP(launch_shade_gen(d, gc, rays, z, R, S, w, nullptr, nullptr, nullptr, nullptr, st));
   } else {
@@ -1261,18 +1258,15 @@ static int render_fwd_impl(const LrfField* f, const float* rays, const float* z,
 static int render_fwd_pipelined(const LrfField* f, const float* rays, const float* z, int32_t R, int32_t S,
                                 uint32_t flags, float floater_thresh, float* rgb, float* depth,
                                 float* weight_out, float* acc_out, void* workspace, hipStream_t st) {
-  const int nc = (f && rays && rgb && depth && workspace && R > 0) ? pipe_chunks(R) : 1;
+  const int nc = pipe_chunks(R);
   SideStream* ss = nc > 1 ? side_stream() : nullptr;
-  if (!ss) {
-    const int rc = render_fwd_impl(f, rays, z, R, S, flags, floater_thresh, rgb, depth, weight_out, acc_out, workspace, st, nullptr);
-    return rc == 2 ? 0 : rc;
-  }
+  if (!ss) return render_fwd_impl(f, rays, z, R, S, flags, floater_thresh, rgb, depth, weight_out, acc_out, workspace, st, nullptr);
   std::lock_guard<std::mutex> lk(ss->mu);
   LRF_HIP(hipEventRecord(ss->fork, st));
   LRF_HIP(hipStreamWaitEvent(ss->s, ss->fork, 0));
   const size_t wb = carve(nullptr, g_pipe_chunk, S).bytes;
   int rc = 0;
-  for (int c = 0; c < nc && (rc == 0 || rc == 2); ++c) {
+  for (int c = 0; c < nc && rc == 0; ++c) {
     const int r0 = c * g_pipe_chunk, rn = std::min(g_pipe_chunk, R - r0);
     rc = render_fwd_impl(f, rays + (size_t)r0 * 6, z, rn, S, flags, floater_thresh, rgb + (size_t)r0 * 3, depth + r0,
                          weight_out ? weight_out + (size_t)r0 * S : nullptr, acc_out ? acc_out + r0 : nullptr,
@@ -1280,12 +1274,14 @@ static int render_fwd_pipelined(const LrfField* f, const float* rays, const floa
   }
   LRF_HIP(hipEventRecord(ss->join, ss->s));                  // (also after an error: the side stream is joined again)
   LRF_HIP(hipStreamWaitEvent(st, ss->join, 0));
-  return rc == 2 ? 0 : rc;
+  return rc;
 }
 
 int lrf_render_fwd(const LrfField* f, const float* rays, const float* z, int32_t R, int32_t S,
                    uint32_t flags, float floater_thresh, float* rgb, float* depth,
                    float* weight_out, float* acc_out, void* workspace, void* stream) {
+  if (const char* bad = check_fwd(f, rays, z, rgb, depth, workspace, R, S, flags)) return set_err(bad);
+  LRF_HIP(lds_opt_in());
   return render_fwd_pipelined(f, rays, z, R, S, flags, floater_thresh, rgb, depth, weight_out, acc_out, workspace,
                               reinterpret_cast<hipStream_t>(stream));
 }
@@ -1293,21 +1289,23 @@ int lrf_render_fwd(const LrfField* f, const float* rays, const float* z, int32_t
 // LocalTensorfs.forward without a tape (local_tensorfs.py:397-499) as ONE call: the rays of every active field, the
 // per-field renders chunk by chunk in the reference's order (:440-474: for each chunk, for each field), the blend.  Same
 // launches as lrf_scene_rays + n_rf x lrf_render_fwd + lrf_scene_blend, enqueued from C: the host side of a 4-field scene
-// forward drops from 0.36 ms of Python per call to one ctypes call.
+// forward drops from 0.36 ms of Python per call to one ctypes call.  Every argument is checked before the first launch.
 int lrf_scene_fwd(const int64_t* ray_ids, int32_t R, int32_t per_view, const float* cam2world, const float* world2rf,
                   int32_t n_rf, const float* focal, const float* center, int32_t W, int32_t H, int32_t fov360,
                   const LrfSceneField* fields, float floater_thresh, int32_t chunk,
                   const float* blend_w, const float* exposure,
                   float* rays, float* rgb_f, float* depth_f, float* directions, int64_t* ij,
                   float* rgbs, float* depth, void* scene_workspace, size_t scene_workspace_bytes, void* stream) {
-  if (!fields || !rays || !rgb_f || !depth_f || !rgbs || !depth) return set_err("lrf_scene_fwd: null argument");
+  if (!fields || !blend_w || !rays || !rgb_f || !depth_f || !rgbs || !depth) return set_err("lrf_scene_fwd: null argument");
   if (n_rf <= 0 || n_rf > LRF_SCENE_MAX_FIELDS) return set_err("lrf_scene_fwd: 1 <= n_rf <= LRF_SCENE_MAX_FIELDS");
   if (R < 0 || per_view <= 0 || R % per_view) return set_err("lrf_scene_fwd: R must be a multiple of per_view");
   if (chunk <= 0) chunk = R;
-  for (int k = 0; k < n_rf; ++k)
-    if (!fields[k].field || !fields[k].z || !fields[k].workspace) return set_err("lrf_scene_fwd: null field / z / workspace");
-  int rc = lrf_scene_rays(ray_ids, R, per_view, cam2world, world2rf, n_rf, focal, center, W, H, fov360, rays, directions, ij, stream);
-  if (rc) return rc;
+  for (int k = 0; k < n_rf; ++k) {
+    const LrfSceneField& sf = fields[k];
+    if (!sf.field || !sf.z || !sf.workspace) return set_err("lrf_scene_fwd: null field / z / workspace");
+    if (R > 0)                                                 // (each chunk of the field: rays, outputs and R inside these)
+      if (const char* bad = check_fwd(sf.field, rays, sf.z, rgb_f, depth_f, sf.workspace, std::min(chunk, R), sf.S, sf.flags)) return set_err(bad);
+  }
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   // Fused form: groups of up to LRF_MULTI_MAX fields in ONE march and ONE colour launch over their field-major "virtual" rays
   // (3 launches per group and chunk instead of 2 per field; one prologue, one tail).  Needs: chunks of a multiple of 16 rays
@@ -1317,7 +1315,7 @@ int lrf_scene_fwd(const int64_t* ray_ids, int32_t R, int32_t per_view, const flo
   bool fuse = scene_workspace && n_rf >= 2 && R > 0 && chunk % 16 == 0 && !g_no_scene_fuse;
   for (int k = 0; fuse && k < n_rf; ++k) {
     const LrfSceneField& a = fields[k], &b = fields[0];
-    if (!a.field->cache || gen_check(a.field) || !gen_is_default(a.field->fea_pe, a.field->view_pe, a.field->feature_c ? a.field->feature_c : LRF_FEATC)) fuse = false;
+    if (!default_net(a.field)) fuse = false;
     else if (a.flags & (LRF_FLAG_MLP_VALU | LRF_FLAG_MLP_F32 | LRF_FLAG_SORT_RAYS)) fuse = false;
     else if (a.S != b.S || a.flags != b.flags || memcmp(a.field->grid, b.field->grid, sizeof(b.field->grid))) fuse = false;
     else if (a.field->weight_thres != b.field->weight_thres || a.field->term_T != b.field->term_T) fuse = false;
@@ -1328,47 +1326,39 @@ int lrf_scene_fwd(const int64_t* ray_ids, int32_t R, int32_t per_view, const flo
     const int32_t ll[3] = {g[0], g[1], g[2]};
     if (!march_lds_rays(ll, fields[0].S)) fuse = false;
   }
-  if (fuse) {
-    const int32_t S = fields[0].S;
-    if (S < 2 || S > 4096) return set_err("lrf_scene_fwd: need 2 <= S <= 4096");
-    for (int32_t lo = 0; lo < R; lo += chunk) {                // chunk by chunk, as the field-by-field form (:440)
-      const int32_t n = R - lo < chunk ? R - lo : chunk;
-      if (n % 16) {                                            // a ragged last chunk: field by field
-        for (int k = 0; k < n_rf; ++k) {
-          const LrfSceneField& sf = fields[k];
-          rc = render_fwd_pipelined(sf.field, rays + ((size_t)k * R + lo) * 6, sf.z, n, sf.S, sf.flags, floater_thresh,
-                                    rgb_f + ((size_t)k * R + lo) * 3, depth_f + (size_t)k * R + lo, nullptr, nullptr, sf.workspace, st);
-          if (rc) return rc;
-        }
-        continue;
-      }
-      for (int k0 = 0; k0 < n_rf; k0 += LRF_MULTI_MAX) {
-        const int nf = n_rf - k0 < LRF_MULTI_MAX ? n_rf - k0 : LRF_MULTI_MAX;
-        const int Rv = nf * n;
-        if (lrf_workspace_bytes(Rv, S) > scene_workspace_bytes) return set_err("lrf_scene_fwd: scene workspace too small");
-        const Workspace w = carve(scene_workspace, Rv, S);
-        MultiF mf;
-        mf.nf = nf; mf.Rf = n; mf.Rs = R; mf.lo = lo;
-        for (int k = 0; k < nf; ++k) { mf.f[k] = make_dfield(fields[k0 + k].field); mf.f[k].rdir = w.rdir; }
-        for (int k = nf; k < LRF_MULTI_MAX; ++k) mf.f[k] = mf.f[0];
-        const float* rv = rays + (size_t)k0 * R * 6;           // field k of the group: rays [k0 + k][lo + r], outputs likewise (multi_io)
-        launch_march(mf.f[0], rv, fields[k0].z, Rv, S, fields[k0].flags, 0.0f, depth_f + (size_t)k0 * R, w.acc, nullptr,
-                     w.ncomp, w.cidx, w.cw, nullptr, st, &mf);
-        LRF_HIP(launch_shade3_multi(mf, rv, fields[k0].z, Rv, S, fields[k0].flags, w, rgb_f + (size_t)k0 * R * 3, st));
-      }
-    }
-    LRF_HIP(hipGetLastError());
-    return lrf_scene_blend(rgb_f, depth_f, blend_w, exposure, R, per_view, n_rf, rgbs, depth, nullptr, stream);
-  }
-  for (int32_t lo = 0; lo < R; lo += chunk) {
+  // the largest group is the first one of the first chunk (the workspace grows with the rays); a ragged first chunk forms none
+  const int32_t S = fields[0].S, n0 = std::min(chunk, R);
+  if (fuse && n0 % 16 == 0 && lrf_workspace_bytes(std::min(n_rf, LRF_MULTI_MAX) * n0, S) > scene_workspace_bytes)
+    return set_err("lrf_scene_fwd: scene workspace too small");
+  int rc = lrf_scene_rays(ray_ids, R, per_view, cam2world, world2rf, n_rf, focal, center, W, H, fov360, rays, directions, ij, stream);
+  if (rc) return rc;
+  LRF_HIP(lds_opt_in());
+  for (int32_t lo = 0; lo < R; lo += chunk) {                  // chunk by chunk, as the field-by-field form (:440)
     const int32_t n = R - lo < chunk ? R - lo : chunk;
-    for (int k = 0; k < n_rf; ++k) {
-      const LrfSceneField& sf = fields[k];
-      rc = render_fwd_pipelined(sf.field, rays + ((size_t)k * R + lo) * 6, sf.z, n, sf.S, sf.flags, floater_thresh,   // (chunks of 32768 rays and more: over two streams)
-                                rgb_f + ((size_t)k * R + lo) * 3, depth_f + (size_t)k * R + lo, nullptr, nullptr, sf.workspace, st);
-      if (rc) return rc;
+    if (!fuse || n % 16) {                                     // field by field (in the fused form: a ragged last chunk)
+      for (int k = 0; k < n_rf; ++k) {
+        const LrfSceneField& sf = fields[k];
+        rc = render_fwd_pipelined(sf.field, rays + ((size_t)k * R + lo) * 6, sf.z, n, sf.S, sf.flags, floater_thresh,   // (chunks of 32768 rays and more: over two streams)
+                                  rgb_f + ((size_t)k * R + lo) * 3, depth_f + (size_t)k * R + lo, nullptr, nullptr, sf.workspace, st);
+        if (rc) return rc;
+      }
+      continue;
+    }
+    for (int k0 = 0; k0 < n_rf; k0 += LRF_MULTI_MAX) {
+      const int nf = n_rf - k0 < LRF_MULTI_MAX ? n_rf - k0 : LRF_MULTI_MAX;
+      const int Rv = nf * n;
+      const Workspace w = carve(scene_workspace, Rv, S);
+      MultiF mf;
+      mf.nf = nf; mf.Rf = n; mf.Rs = R; mf.lo = lo;
+      for (int k = 0; k < nf; ++k) { mf.f[k] = make_dfield(fields[k0 + k].field); mf.f[k].rdir = w.rdir; }
+      for (int k = nf; k < LRF_MULTI_MAX; ++k) mf.f[k] = mf.f[0];
+      const float* rv = rays + (size_t)k0 * R * 6;             // field k of the group: rays [k0 + k][lo + r], outputs likewise (multi_io)
+      launch_march(mf.f[0], rv, fields[k0].z, Rv, S, fields[k0].flags, 0.0f, depth_f + (size_t)k0 * R, w.acc, nullptr,
+                   w.ncomp, w.cidx, w.cw, nullptr, st, &mf);
+      launch_shade3_multi(mf, rv, fields[k0].z, Rv, S, fields[k0].flags, w, rgb_f + (size_t)k0 * R * 3, st);
     }
   }
+  LRF_HIP(hipGetLastError());
   return lrf_scene_blend(rgb_f, depth_f, blend_w, exposure, R, per_view, n_rf, rgbs, depth, nullptr, stream);
 }
 
@@ -1376,12 +1366,12 @@ int lrf_render_fwd_profile(const LrfField* f, const float* rays, const float* z,
                            uint32_t flags, float floater_thresh, float* rgb, float* depth,
                            void* workspace, void* stream, float* ms_out, int32_t* n_shaded_out) {
   if (!ms_out) return set_err("lrf_render_fwd_profile: null ms_out");
+  if (const char* bad = check_fwd(f, rays, z, rgb, depth, workspace, R, S, flags)) return set_err(bad);
+  LRF_HIP(lds_opt_in());
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   hipEvent_t ev[4];
   for (int i = 0; i < 4; ++i) LRF_HIP(hipEventCreate(&ev[i]));
   int rc = render_fwd_impl(f, rays, z, R, S, flags, floater_thresh, rgb, depth, nullptr, nullptr, workspace, st, ev);
-  const bool two_launches = rc == 2;
-  if (two_launches) rc = 0;
   if (rc == 0) {
     hipError_t e = hipStreamSynchronize(st);
     if (e != hipSuccess) rc = set_err("hipStreamSynchronize", e);
@@ -1389,7 +1379,7 @@ int lrf_render_fwd_profile(const LrfField* f, const float* rays, const float* z,
   if (rc == 0) {
     for (int i = 0; i < 3; ++i) (void)hipEventElapsedTime(&ms_out[i], ev[i], ev[i + 1]);      // march, colour stage, finalize (0 for the default engine)
     (void)hipEventElapsedTime(&ms_out[3], ev[0], ev[3]);
-    if (two_launches) { ms_out[2] = 0.0f; (void)hipEventElapsedTime(&ms_out[3], ev[0], ev[2]); }
+    if (fwd_shade3(f, flags)) { ms_out[2] = 0.0f; (void)hipEventElapsedTime(&ms_out[3], ev[0], ev[2]); }
     ms_out[4] = ms_out[5] = 0.0f;
     if (n_shaded_out) {
       // shaded-sample count of this batch = sum of ncomp (host copy; measurement only)

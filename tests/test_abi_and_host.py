@@ -219,6 +219,43 @@ def test_c_abi_argument_validation_without_a_gpu():
     assert 0 <= pe - base - rows * ld * 4 < 4096
 
 
+@pytest.mark.skipif(torch.cuda.is_available(), reason="passes fake device pointers: must never reach a device")
+def test_render_path_refuses_before_any_hip_call():
+    """lrf_render_bwd and lrf_scene_fwd check every argument before their first HIP call: without a device, a refused call
+    gives its own message, not the error of a launch or device query that ran first."""
+    import ctypes as C
+    from localrf_amd import _native as N
+    lib = N.lib()
+    fake = C.c_void_p(0x10000)                                      # non-null, 16-byte aligned; never dereferenced here
+
+    def field(n):
+        f = N.LrfField(cache=fake, feature_c=128)
+        f.grid[:] = [n, n, n]
+        return f
+
+    def bwd(f, flags=0, **grads):
+        g = N.LrfGrads(**grads)
+        return lib.lrf_render_bwd(C.byref(f), C.byref(N.LrfParams()), fake, fake, 64, 64, flags, fake, fake,
+                                  C.byref(g), fake, fake, None)
+
+    def last():
+        return lib.lrf_last_error().decode()
+
+    assert bwd(field(64), zero_base=fake, zero_floats=3) != 0 and "zero_floats must name" in last()
+    assert bwd(field(64), zero_base=C.c_void_p(0x10004), zero_floats=4) != 0 and "zero_floats must name" in last()
+    assert bwd(field(700), N.LRF_FLAG_DETERMINISTIC) != 0 and "DETERMINISTIC covers lines up to 640 cells" in last()
+
+    fs = [field(64) for _ in range(2)]
+    sf = (N.LrfSceneField * 2)(*[N.LrfSceneField(field=C.pointer(f), z=fake, S=64, flags=0, workspace=fake) for f in fs])
+
+    def scene(blend_w, ws_bytes):
+        return lib.lrf_scene_fwd(fake, 64, 64, fake, fake, 2, fake, fake, 8, 8, 0, sf, 0.0, 64, blend_w, None,
+                                 fake, fake, fake, fake, fake, fake, fake, fake, ws_bytes, None)
+
+    assert scene(None, 1 << 40) != 0 and last() == "lrf_scene_fwd: null argument"
+    assert scene(fake, 1) != 0 and last() == "lrf_scene_fwd: scene workspace too small"
+
+
 def test_saved_row_layout_is_a_bijection_and_matches_the_test_reader(built_lib):
     """The training workspace keeps activation / gradient rows in MFMA-fragment order (csrc/lrf_common.h frag_off).
     Host side of the same functions the kernels index with: every (row, column) of a few tiles maps to a distinct
