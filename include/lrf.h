@@ -558,6 +558,25 @@ size_t lrf_depth_comparison_workspace_bytes(int32_t V, int32_t H, int32_t W);
 int lrf_depth_comparison(const float* depth, const float* invdepth, int32_t V, int32_t H, int32_t W, float* out, float* stats,
                          void* workspace, void* stream);
 
+/* lrf_encode_frames: the bytes renderer.render(test=False) writes per frame (renderer.py:130-148,172-174), for V frames of
+ * H x W pixels: rgb [V,H,W,3] and depth [V,H,W] fp32 (device, 16-byte aligned) ->
+ *   rgb8 [V,H,W,3] uint8 = clamp(rint(fp32(255 * x)), 0, 255), ties to even, NaN -> 0 (cv2.imwrite's saturate_cast);
+ *     rgb and rgb8 are both null for the depth images alone;
+ *   depth_idx [V,H,W] uint8 (nullable) = the index image visualize_depth (utils/utils.py:179-197) passes to
+ *     cv2.applyColorMap, in numpy 2.2's fp32 arithmetic: x = nan_to_num(d); uint8(fp32(255 * clip(fp32(x - mi) / D, 0, 1)));
+ *   depth8 [V,H,W,3] uint8 = lut[depth_idx], lut a device [256,3] uint8 table whose channel order is kept.
+ * fixed_range: host {mi, ma, D} (mi and D already rounded to fp32 as numpy rounds the caller's numbers), or null for the
+ * automatic range of visualize_depth(minmax=None), per frame: mi = min(x[x > 0]) (NaN when the frame has no positive value),
+ * ma = max(x) (-0.0 read as +0.0), D = fp32(fp32(ma - mi) + 1e-8f).  range_out [V,2] (nullable) receives (mi, ma) per frame.
+ * One launch with a fixed range, two with the automatic one (per-workgroup integer extrema of order-preserving keys, reduced
+ * in a fixed order: no float atomics, no host synchronisation, bit-reproducible).  Refused before any launch: V < 1,
+ * H or W <= 0, 3 V H W >= 2^31, null or misaligned pointers (outputs 4-byte aligned), the automatic range without a
+ * workspace of lrf_encode_frames_workspace_bytes(V) bytes (0 for V outside 1..2^24). */
+size_t lrf_encode_frames_workspace_bytes(int32_t V);
+int lrf_encode_frames(const float* rgb /* nullable */, const float* depth, int32_t V, int32_t H, int32_t W, const uint8_t* lut,
+                      const float* fixed_range /* nullable */, uint8_t* rgb8 /* nullable */, uint8_t* depth8, uint8_t* depth_idx /* nullable */,
+                      float* range_out /* nullable */, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

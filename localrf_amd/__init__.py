@@ -10,6 +10,8 @@ Public surface mirrors the reference's names:
   diagnostics.quantile / median / flow_comparison / depth_comparison / test_view_evaluation
                                     (renderer.py:79-124: test-view flow and depth comparison images, exact device quantiles)
   DeviceFrames                      (dataLoader/localrf_dataset.py, train split: a device-resident frame window)
+  novel_views.render_poses / iter_pose_frames / encode_frames / visualize_depth / nearest_frames
+                                    (renderer.py:43-77,130-148, test=False: novel camera poses, frames encoded on the device)
 The arithmetic of TensorVMSplit.forward and of LocalTensorfs.forward (ray generation, field
 blend, exposure) runs in hand-written HIP kernels for gfx950 (csrc/), reached through the C ABI
 of include/lrf.h.
@@ -22,6 +24,7 @@ from . import rays  # noqa: F401
 from . import losses  # noqa: F401
 from . import metrics  # noqa: F401
 from . import diagnostics  # noqa: F401
+from . import novel_views  # noqa: F401
 from .frames import DeviceFrames  # noqa: F401
 
-__all__ = ["TensorVMSplit", "AlphaGridMask", "MLPRender_Fea_late_view", "LocalTensorfs", "rays", "losses", "metrics", "diagnostics", "NativeError", "FusedAdam", "DeviceFrames"]
+__all__ = ["TensorVMSplit", "AlphaGridMask", "MLPRender_Fea_late_view", "LocalTensorfs", "rays", "losses", "metrics", "diagnostics", "novel_views", "NativeError", "FusedAdam", "DeviceFrames"]

@@ -198,6 +198,9 @@ SYMBOLS = {
     "lrf_flow_comparison": (C.c_int, [C.POINTER(LrfFlowComparison), _f, _f, _f, _f, _f, C.c_void_p, C.c_void_p]),
     "lrf_depth_comparison_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "lrf_depth_comparison": (C.c_int, [_f, _f, C.c_int32, C.c_int32, C.c_int32, _f, _f, C.c_void_p, C.c_void_p]),
+    "lrf_encode_frames_workspace_bytes": (C.c_size_t, [C.c_int32]),
+    "lrf_encode_frames": (C.c_int, [_f, _f, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_float), C.c_void_p,
+                                    C.c_void_p, C.c_void_p, _f, C.c_void_p, C.c_void_p]),
     "lrf_scene_blend_bwd": (C.c_int, [_f, _f, _f, _f, _f, C.c_int32, C.c_int32, C.c_int32, _f, _f, _f,
                                       C.c_void_p]),
 }

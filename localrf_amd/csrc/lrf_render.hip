@@ -1124,6 +1124,7 @@ static hipError_t lds_opt_in() {
 #include "lrf_frames.inl"
 #include "lrf_select.inl"
 #include "lrf_evalgeo.inl"
+#include "lrf_encode.inl"
 #include "lrf_reg.inl"
 #include "lrf_mask.inl"
 

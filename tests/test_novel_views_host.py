@@ -1,0 +1,215 @@
+"""Novel-view rendering without a GPU: the numpy restatements of the frame encoding against the reference's recorded index
+images (tests/golden/novel_views.npz) and its byte rules, the start / frame-index mapping of renderer.render(test=False)
+on a CPU copy of the golden scene, argument refusals before any device work, and the new C ABI symbols."""
+import ctypes as C
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from localrf_amd import NativeError, novel_views
+from novel_views_cases import depth_idx_frames, depth_idx_host, edge_depths, edge_rgbs, golden, rgb8_host, scene
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def test_depth_index_restatement_equals_the_reference_images():
+    g = golden()
+    for s in (0, 2):
+        depth = g[f"s{s}.depth"]
+        idx, _ = depth_idx_frames(depth, [0, 5])
+        assert np.array_equal(idx, g[f"s{s}.idx_fixed"])
+        idx, ranges = depth_idx_frames(depth, None)
+        assert np.array_equal(idx, g[f"s{s}.idx_auto"])
+        assert np.array_equal(ranges.view(np.uint32), g[f"s{s}.range_auto"].view(np.uint32))
+
+
+def _visualize_depth_numpy(depth, minmax):
+    """utils/utils.py:184-196 up to cv2.applyColorMap, line by line (numpy 2.2 promotion)."""
+    x = np.nan_to_num(depth)
+    if minmax is None:
+        mi = np.min(x[x > 0])
+        ma = np.max(x)
+    else:
+        mi, ma = minmax
+    with np.errstate(invalid="ignore", over="ignore"):
+        x = (x - mi) / (ma - mi + 1e-8)
+        x = (255 * np.clip(x, 0, 1)).astype(np.uint8)
+    return x
+
+
+def test_depth_index_edge_cases():
+    rng = np.random.default_rng(3)
+    d = edge_depths(rng, 3, 17, 23)
+    for minmax in ([0, 5], (0.5, 4.25), (-1, 7), None):
+        for f in d:
+            want = _visualize_depth_numpy(f, minmax)
+            got, _ = depth_idx_host(f, minmax)
+            assert np.array_equal(got, want), minmax
+    mi, ma = np.float32(0.3), np.float32(4.7)                   # a range visualize_depth returned: fp32 arithmetic
+    assert np.array_equal(depth_idx_host(d[0], None)[0], _visualize_depth_numpy(d[0], None))
+    D = novel_views.fixed_range((mi, ma))[2]
+    assert D == np.float32(ma - mi + 1e-8) and D.dtype == np.float32
+    assert novel_views.fixed_range([0, 5]) == (np.float32(0), np.float32(5), np.float32(5))
+    zeros = np.zeros((4, 5), np.float32)
+    with pytest.raises(ValueError):
+        _visualize_depth_numpy(zeros, None)
+    with pytest.raises(ValueError):
+        depth_idx_host(zeros, None)
+    assert not depth_idx_host(zeros, [0, 5])[0].any()
+    special = np.array([[np.nan, np.inf, -np.inf, 5.0, 2.5, 0.0]], np.float32)
+    assert depth_idx_host(special, [0, 5])[0].tolist() == [[0, 255, 0, 255, 127, 0]]
+    assert depth_idx_host(special, None)[0].tolist() == _visualize_depth_numpy(special, None).tolist()
+
+
+def test_rgb_byte_rule():
+    rng = np.random.default_rng(4)
+    x = edge_rgbs(rng, 2, 9, 11)
+    got = rgb8_host(x)
+    v = np.float32(255) * x
+    with np.errstate(invalid="ignore"):
+        want = np.clip(np.rint(v), 0, 255)
+    want[np.isnan(v)] = 0
+    assert np.array_equal(got, want.astype(np.uint8))
+    # element by element: round half to even, as saturate_cast<uchar>(float) (cvRound) does for a rendered colour
+    for a, b in zip(x.reshape(-1)[:2000], got.reshape(-1)[:2000]):
+        y = float(np.float32(255) * a)
+        assert b == (0 if y != y else min(255, max(0, round(y)))) if abs(y) < 2 ** 31 else b in (0, 255)
+    ties = (np.arange(255, dtype=np.float32) + np.float32(0.5)) / np.float32(255)
+    t = np.float32(255) * ties
+    exact = t == np.arange(255, dtype=np.float32) + np.float32(0.5)
+    assert exact.sum() > 100
+    assert np.array_equal(rgb8_host(ties)[exact] % 2, np.zeros(int(exact.sum()), np.uint8))
+
+
+def test_jet_table():
+    lut = novel_views.jet_lut()
+    assert lut.shape == (256, 3) and lut.dtype == np.uint8
+    assert lut[0].tolist() == [128, 0, 0] and lut[255].tolist() == [0, 0, 128]      # BGR: dark blue .. dark red
+    assert lut[:, 1].max() == 255 and lut[:, 0].max() == 255 and lut[:, 2].max() == 255
+
+
+def test_start_and_frame_index_mapping_on_the_host():
+    lt, g = scene("cpu")
+    poses = torch.from_numpy(g["poses"])
+    N = poses.shape[0]
+    W, H = int(g["W"]), int(g["H"])
+    tests = g["test_frames"].tolist()
+    nearest = novel_views.nearest_frames(lt, poses)
+    ref = np.array([int(torch.argmin(torch.norm(torch.stack(list(lt.t_c2w)) - p[None, :, 3], dim=-1))) for p in poses])
+    assert nearest.tolist() == ref.tolist()
+    assert nearest[N - 5].item() == 6                           # frame 7 duplicates frame 6's translation: first index
+    for s in (0, 2):
+        p, views, is_test, groups, _, _ = novel_views._plan(lt, poses, W, H, tests, None, s, None)
+        n = N - 2 * s
+        assert views == g[f"s{s}.frame_indices"].tolist() and len(views) == n
+        assert torch.equal(p, poses[s:s + n])                   # frame i: pose poses[start + i]
+        assert views == novel_views.nearest_frames(lt, poses[s:])[s:s + n].tolist()   # frame_indices[start + i]
+        assert is_test == [v in tests for v in views]
+        flat = [i for i0, i1, _ in groups for i in range(i0, i1)]
+        assert flat == list(range(n))
+        bw = lt.blending_weights.detach()
+        for i0, i1, active in groups:
+            assert all(tuple(torch.nonzero(bw[views[i]])[:, 0].tolist()) == active for i in range(i0, i1))
+        for fpc in (1, 3):
+            gs = novel_views._plan(lt, poses, W, H, tests, None, s, fpc)[3]
+            assert max(i1 - i0 for i0, i1, _ in gs) <= fpc
+            assert [i for i0, i1, _ in gs for i in range(i0, i1)] == list(range(n))
+    fi = [i % len(lt.r_c2w) for i in range(N)]
+    _, views, _, _, _, _ = novel_views._plan(lt, poses, W, H, (), fi, 3, None)
+    assert views == fi[3:3 + N - 6]
+    assert novel_views._plan(lt, poses[:3], W, H, (), None, 2, None)[1] == []     # start past the middle: no frame
+
+
+def test_refusals_before_any_device_work():
+    lt, g = scene("cpu")
+    poses = torch.from_numpy(g["poses"])
+    W, H = int(g["W"]), int(g["H"])
+    with pytest.raises(ValueError, match="frames_per_call"):
+        novel_views.render_poses(lt, poses, W, H, frames_per_call=0)
+    with pytest.raises(ValueError, match="poses"):
+        novel_views.render_poses(lt, poses[:, :2], W, H)
+    with pytest.raises(ValueError, match="poses"):
+        novel_views.render_poses(lt, poses.long(), W, H)
+    with pytest.raises(ValueError, match="W, H"):
+        novel_views.render_poses(lt, poses, 0, H)
+    with pytest.raises(ValueError, match="start"):
+        novel_views.render_poses(lt, poses, W, H, start=-1)
+    with pytest.raises(ValueError, match="cmap"):
+        novel_views.render_poses(lt, poses, W, H, cmap=np.zeros((256, 4), np.uint8))
+    with pytest.raises(ValueError, match="cmap"):
+        novel_views.render_poses(lt, poses, W, H, cmap=torch.zeros(256, 3))
+    with pytest.raises(ValueError, match="frame_indices"):
+        novel_views.render_poses(lt, poses, W, H, frame_indices=[0, 1])
+    with pytest.raises(ValueError, match="outside"):
+        novel_views.render_poses(lt, poses, W, H, frame_indices=[99] * poses.shape[0])
+    with torch.no_grad():
+        lt.blending_weights[5].zero_()                          # frame 5 without an active field
+    fi = [0, 1, 5, 2]
+    with pytest.raises(ValueError, match="frame 2: its nearest frame 5 has no active field"):
+        novel_views.render_poses(lt, poses[:4], W, H, frame_indices=fi)
+    with pytest.raises(ValueError, match="no active field"):
+        list(novel_views.iter_pose_frames(lt, poses[:4], W, H, frame_indices=fi))
+    with pytest.raises(NativeError):                            # valid arguments, CPU scene: no fallback
+        novel_views.render_poses(lt, poses[:2], W, H, frame_indices=[0, 1])
+    rgb, depth = torch.zeros(2, 4, 5, 3), torch.zeros(2, 4, 5)
+    with pytest.raises(ValueError):
+        novel_views.encode_frames(rgb, depth[:1])
+    with pytest.raises(ValueError):
+        novel_views.encode_frames(rgb[..., :2], depth)
+    with pytest.raises(ValueError):
+        novel_views.encode_frames(rgb.int(), depth)
+    with pytest.raises(ValueError, match="cmap"):
+        novel_views.encode_frames(rgb, depth, cmap=np.zeros((255, 3), np.uint8))
+    with pytest.raises(ValueError, match="minmax"):
+        novel_views.encode_frames(rgb, depth, minmax=(1, 2, 3))
+    with pytest.raises(ValueError, match="cmap"):
+        novel_views.visualize_depth(depth, cmap=np.zeros((256, 3), np.float32))
+    with pytest.raises(NativeError):
+        novel_views.encode_frames(rgb, depth)
+    with pytest.raises(NativeError):
+        novel_views.visualize_depth(depth)
+
+
+def test_encode_symbols_declared_exported_and_checked(built_lib):
+    from localrf_amd import _native as N
+    header = open(os.path.join(ROOT, "include", "lrf.h")).read()
+    for name in ("lrf_encode_frames", "lrf_encode_frames_workspace_bytes"):
+        assert name in N.SYMBOLS and f"{name}(" in header
+        getattr(built_lib, name)
+    assert built_lib.lrf_abi_version() == 7
+    assert built_lib.lrf_encode_frames_workspace_bytes(3) == 3 * 64 * 8
+    assert built_lib.lrf_encode_frames_workspace_bytes(0) == 0
+    fake = C.c_void_p(0x10000)
+    fr = (C.c_float * 3)(0.0, 5.0, 5.0)
+
+    def enc(rgb=fake, depth=fake, V=2, H=4, W=5, lut=fake, fixed=fr, rgb8=fake, depth8=fake, idx=None, rng=None, ws=None):
+        rc = built_lib.lrf_encode_frames(rgb, depth, V, H, W, lut, fixed, rgb8, depth8, idx, rng, ws, None)
+        return rc, built_lib.lrf_last_error().decode()
+    rc, msg = enc(V=0)
+    assert rc != 0 and msg == "lrf_encode_frames: need V >= 1, H, W > 0 and 3 V H W < 2^31"
+    assert "need V >= 1" in enc(V=0)[1] and "need V >= 1" in enc(H=0)[1] and "need V >= 1" in enc(V=1 << 20, H=1 << 10)[1]
+    assert enc(depth=None)[1] == "lrf_encode_frames: null argument"
+    assert enc(lut=None)[1] == "lrf_encode_frames: null argument"
+    assert enc(rgb8=None)[1] == "lrf_encode_frames: rgb and rgb8 go together"
+    assert enc(fixed=None)[1] == "lrf_encode_frames: the automatic range needs a workspace"
+    assert "16-byte aligned" in enc(rgb=C.c_void_p(0x10004))[1]
+    assert "4-byte aligned" in enc(idx=C.c_void_p(0x10002))[1]
+
+
+def test_encode_kernels_use_no_scratch():
+    """k_encode (both range modes) and k_encode_range, as __graft_entry__.build() compiles them: no scratch, no spills, and
+    the division of the index image is a full-precision one (no v_rcp_f32 without the div_fixup that follows it)."""
+    import re
+    from test_isa_checks import BUILD_FLAGS, _body, _device_asm
+    asm = _device_asm(BUILD_FLAGS)
+    names = [n for pat in (r"k_encodeILb0E", r"k_encodeILb1E", r"k_encode_range") for n, _ in _body(asm, pat)]
+    assert len(names) == 3
+    for name in names:
+        meta = asm[asm.index(".amdhsa_kernel " + name):]
+        meta = meta[:meta.index(".end_amdhsa_kernel")]
+        priv = re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", meta)
+        assert priv and int(priv[1]) == 0, (name, priv and priv[1])
+    for name, body in _body(asm, r"k_encodeILb[01]E"):
+        assert "v_div_fixup_f32" in body and "scratch_" not in body, name
