@@ -8,15 +8,17 @@ A "step" is one TensorVMSplit.forward over one 4096-ray batch already resident i
 For N>1 every rank renders its own 4096-ray shard of an N*4096 batch (weak scaling, no
 collective on the forward path); value = N*4096*K / max-over-ranks time.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
-K is the number of timed steps of the headline forward and of the training step.  --dump-outputs DIR writes what the
-last timed forward step returned (rgb [4096,3], depth [4096], float32) as DIR/rgb.npy and DIR/depth.npy (rank r > 0 of
-an N-rank run: DIR/rgb_rank<r>.npy, ...).  The field and the rays are seeded, so two builds given the same arguments
-render the same inputs and their dumps compare output for output.
+K is the number of timed steps of the headline forward (and, with --full, of the training step).  --dump-outputs DIR
+writes what the last timed forward step returned (rgb [4096,3], depth [4096], float32) as DIR/rgb.npy and DIR/depth.npy
+(rank r > 0 of an N-rank run: DIR/rgb_rank<r>.npy, ...).  The field and the rays are seeded, so two builds given the same
+arguments render the same inputs and their dumps compare output for output.
 
-Prints ONE JSON line on rank 0 (see the task contract) with
+Prints ONE JSON line on rank 0.  A plain run measures the headline alone: it builds the field, ramps the clock, runs the
+W warm-up and K timed steps, writes --dump-outputs and prints metric / value / unit / ms_per_step / dtype / config.
+--full adds everything else the benchmark measures (--no-pmc and --no-baselines trim it):
   roofline      the dominant kernel: HIP-event time on the launch stream, algorithmic bytes (or flops) per
                 launch, HBM-side traffic from rocprofv3 --pmc passes of THIS run (child processes; falls back
                 to the committed profiles/ summary and says so), plus what the counters say binds it:
@@ -466,14 +468,17 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20,        # what the driver runs
-                    help="timed steps of the headline forward and of the training step")
+                    help="timed steps of the headline forward (and, with --full, of the training step)")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write what the last timed forward step returned as DIR/rgb.npy and DIR/depth.npy (float32)")
-    ap.add_argument("--no-baselines", action="store_true", help="skip the CPU / torch-ROCm baselines and extra workloads")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: roofline (kernel profile + rocprofv3 --pmc passes), training step, extra workloads, "
+                         "CPU / torch-ROCm baselines")
+    ap.add_argument("--no-baselines", action="store_true", help="(with --full) skip the CPU / torch-ROCm baselines and extra workloads")
     ap.add_argument("--backend", choices=("nccl", "gloo"), default="nccl",
                     help="process-group backend for N > 1: nccl = RCCL over xGMI (one GPU per rank); gloo = host-staged, ranks may share a GPU (launch test)")
-    ap.add_argument("--no-pmc", action="store_true", help="do not spawn the rocprofv3 --pmc passes for roofline.traffic")
+    ap.add_argument("--no-pmc", action="store_true", help="(with --full) do not spawn the rocprofv3 --pmc passes for roofline.traffic")
     ap.add_argument("--child", nargs="?", const="fwd", default=None, choices=("fwd", "train"),
                     help="(internal) the timed loop only: what the PMC passes profile (fwd: eval forward; train: training step)")
     ap.add_argument("--preroll-ms", type=float, default=1500.0,
@@ -589,6 +594,25 @@ def main():
     ms_per_step = dt / args.steps * 1e3
     value = world * R_PER_GPU * args.steps / dt
 
+    def headline(S):
+        return {"metric": "rays/sec (4096-ray batch, 512 samples, 300^3 grid)", "value": value,
+                "unit": "rays/s", "n_gpus": world, "n_ranks_seen": (dist.get_world_size() if ddp else 1), "steps": args.steps, "warmup": args.warmup,
+                "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak",
+                "vs_baseline": None, "dtype": "f32 (colour network: split-bf16 3-term products on v_mfma_f32_32x32x16_bf16, fp32 accumulate, <= 3e-5 vs the exact-fp32 engine; gathers and compositing fp32)",
+                "data": "synthetic",
+                "config": {"workload": "configs[1]: single 300^3 TensorVMSplit, 4096 rays x 512 samples "
+                                       "per GPU, full density+appearance+MLP render, eval forward",
+                           "rays_per_gpu": R_PER_GPU, "samples_per_ray": S, "grid": GRID,
+                           "parallelism": f"ray-shard x{world}", "mlp_engine": field.mlp_engine}}
+
+    if not args.full and not args.child:                      # a plain run: the headline and nothing else
+        if rank == 0:
+            print(json.dumps(headline(field.z_schedule(False, N_SAMPLES_ARG, dev).shape[0])), flush=True)
+        if ddp:
+            barrier()
+            dist.destroy_process_group()
+        return
+
     # ---- training step, every N: forward with a graph, backward, gradient all-reduce (RCCL), FusedAdam
     sd_init = {k: v.detach().clone() for k, v in field.state_dict().items()}     # the workloads below render the untrained field again
     opt = FusedAdam(field.get_optparam_groups(0.02, 1e-3), betas=(0.9, 0.99), pack_field=field)
@@ -676,16 +700,7 @@ def main():
             else:
                 train["roofline"]["traffic"] = None
                 train["roofline"]["traffic_source"] = tr_src
-        out = {"metric": "rays/sec (4096-ray batch, 512 samples, 300^3 grid)", "value": value,
-               "unit": "rays/s", "n_gpus": world, "n_ranks_seen": (dist.get_world_size() if ddp else 1), "steps": args.steps, "warmup": args.warmup,
-               "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak",
-               "vs_baseline": None, "dtype": "f32 (colour network: split-bf16 3-term products on v_mfma_f32_32x32x16_bf16, fp32 accumulate, <= 3e-5 vs the exact-fp32 engine; gathers and compositing fp32)",
-               "data": "synthetic",
-               "config": {"workload": "configs[1]: single 300^3 TensorVMSplit, 4096 rays x 512 samples "
-                                      "per GPU, full density+appearance+MLP render, eval forward",
-                          "rays_per_gpu": R_PER_GPU, "samples_per_ray": S, "grid": GRID,
-                          "parallelism": f"ray-shard x{world}", "mlp_engine": field.mlp_engine},
-               "roofline": roofline, "train_step": train}
+        out = {**headline(S), "roofline": roofline, "train_step": train}
         if not args.no_baselines and world == 1:              # baselines and extra workloads are an N=1 report
             with torch.no_grad():
                 field.mlp_engine = "f32"

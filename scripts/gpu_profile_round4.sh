@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/$TAG
 mkdir -p $O
-(cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats -d /tmp/prof_$TAG -o bench -- python -u $R/bench.py --steps 50 --warmup 5 --no-baselines --no-pmc > $O/prof_bench.log 2>&1)
+(cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats -d /tmp/prof_$TAG -o bench -- python -u $R/bench.py --steps 50 --warmup 5 --full --no-baselines --no-pmc > $O/prof_bench.log 2>&1)
 python $R/scripts/rocpd_stats.py $(find /tmp/prof_$TAG -name "*.db" | head -1) > $O/kernel_trace_bench.md
 i=0
 for ctrs in "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_VALU_MFMA_BUSY_CYCLES" \
@@ -22,6 +22,6 @@ bash $R/scripts/serial_trace.sh $TAG > /dev/null 2>&1
 cp $R/gpurun_out/serial_$TAG.md $O/kernel_trace_train_serial.md; grep "fwd+bwd" $R/gpurun_out/serial_$TAG.log > $O/fwd_bwd_ms.txt
 bash $R/scripts/gpu_pmc_train.sh $TAG > /dev/null 2>&1
 cp $R/gpurun_out/pmc_train_$TAG.md $O/pmc_train.md
-(time timeout 600 python -u $R/bench.py) > $O/bench_default.log 2>&1
+(time timeout 600 python -u $R/bench.py --full) > $O/bench_default.log 2>&1
 grep '^{' $O/bench_default.log > $O/bench_default.json
 ls -la $O

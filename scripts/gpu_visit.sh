@@ -14,7 +14,7 @@ if [ -n "$STAGES" ]; then
 fi
 if [ -n "$BENCH" ]; then
   for i in 1 2 3; do
-    timeout 300 python -u bench.py --gpus 1 --steps 20 --warmup 5 --no-baselines --no-pmc 2>/dev/null | python -c "import sys,json; [print('K20', json.loads(l)['value'], json.loads(l)['ms_per_step'], json.loads(l)['train_step']['ms_per_step']) for l in sys.stdin if l.startswith('{')]"
+    timeout 300 python -u bench.py --gpus 1 --steps 20 --warmup 5 --full --no-baselines --no-pmc 2>/dev/null | python -c "import sys,json; [print('K20', json.loads(l)['value'], json.loads(l)['ms_per_step'], json.loads(l)['train_step']['ms_per_step']) for l in sys.stdin if l.startswith('{')]"
   done
   timeout 300 python -u bench.py --gpus 1 --steps 20 --warmup 5 --no-baselines --no-pmc --preroll-ms 1500 2>/dev/null | python -c "import sys,json; [print('K20 preroll1500', json.loads(l)['value'], json.loads(l)['ms_per_step']) for l in sys.stdin if l.startswith('{')]"
   timeout 300 python -u bench.py --gpus 1 --steps 200 --warmup 20 --no-baselines --no-pmc 2>/dev/null | python -c "import sys,json; [print('K200', json.loads(l)['value'], json.loads(l)['ms_per_step']) for l in sys.stdin if l.startswith('{')]"

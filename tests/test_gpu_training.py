@@ -810,7 +810,7 @@ def test_bench_spawns_its_own_ranks(tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "3", "--warmup", "1",
-                        "--no-baselines", "--no-pmc"], capture_output=True, text=True, timeout=420, cwd=root, env=env)
+                        "--full", "--no-baselines", "--no-pmc"], capture_output=True, text=True, timeout=420, cwd=root, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -837,7 +837,7 @@ def test_bench_under_torch_distributed_run_one_rank(tmp_path):
         port = s_.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2",
-           "--no-baselines", "--no-pmc"]
+           "--full", "--no-baselines", "--no-pmc"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=280, cwd=root,
                        env={**os.environ, "HSA_ENABLE_IPC_MODE_LEGACY": "0"})
     assert r.returncode == 0, r.stderr[-2000:]
