@@ -118,8 +118,7 @@ class SceneLifecycle(torch.nn.Module):
             # stays resident.  Its optimiser is gone: drop its gradients (35-96 MB) with it.
             for p in self.tensorfs[-1].parameters():
                 p.grad = None
-            self.tensorfs[-1]._grad_flat = None
-            self.tensorfs[-1]._grad_fresh = False
+            self.tensorfs[-1].drop_grads()
         else:
             world2rf = torch.zeros(3, device=self.device)
         self.tensorfs.append(TensorVMSplit(device=self.device, **self.tensorf_args))

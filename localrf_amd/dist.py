@@ -8,6 +8,8 @@ import os
 import torch
 import torch.distributed as dist
 
+from .grad_bucket import GradBucket
+
 
 def _forced():
     """LRF_DIST_FORCE=1: issue every collective even in a one-rank group, so that the whole exchange (side stream,
@@ -61,32 +63,36 @@ def global_mean(x, group=None):
     return pair[0] / pair[1]
 
 
+def _bucket_of(m):
+    """The GradBucket a module owns (TensorVMSplit._grads: its backward ran through lrf_render_bwd at least once), or None.
+    Read from the instance's dict: every submodule of a scene is asked, and Module.__getattr__ raises for those without."""
+    b = vars(m).get("_grads")
+    return b if isinstance(b, GradBucket) else None
+
+
 def _field_buckets(params_or_module):
-    """(field, flat parameter-gradient buffer, parameters it holds) for every TensorVMSplit whose LAST backward wrote its
-    gradients into one flat buffer (TensorVMSplit.grad_bucket).  A field that took no part in
+    """(field, its GradBucket, flat parameter-gradient buffer, parameters it holds) for every field whose LAST backward
+    wrote its gradients into one flat buffer (a fresh GradBucket).  A field that took no part in
     the last backward -- a finished field of a LocalTensorfs keeps its old .grad forever, nothing zeroes it -- is not
     fresh and is left alone: its stale buffer is neither reduced nor divided.  When autograd accumulated (some of) a fresh
-    field's gradients outside the buffer (a regulariser in the loss), they are copied back first (rebucket_grads); a field
-    for which even that fails comes back as (field, None, None) and takes the small-bucket path, every tensor of it."""
+    field's gradients outside the buffer (a regulariser in the loss), they are copied back first (GradBucket.rebucket); a
+    field for which even that fails comes back with (None, None) and takes the small-bucket path, every tensor of it."""
     if not isinstance(params_or_module, torch.nn.Module):
         return []
     out = []
     for m in params_or_module.modules():
-        gb = getattr(m, "grad_bucket", None)
-        if gb is not None and getattr(m, "_grad_fresh", False):
-            b = gb()
-            if b is None and hasattr(m, "rebucket_grads"):
-                b = m.rebucket_grads()
-            out.append((m,) + (tuple(b) if b is not None else (None, None)))
-            m._grad_fresh = False
+        bucket = _bucket_of(m)
+        if bucket is not None and bucket.fresh:
+            out.append((m, bucket) + (bucket.held() or bucket.rebucket() or (None, None)))
+            bucket.fresh = False
     return out
 
 
 _prep_streams = {}
 
 
-def _reduce_field_chunks(field, flat, group, works):
-    """All-reduce one field's flat gradient buffer piece by piece (TensorVMSplit.grad_chunks): density planes / lines
+def _reduce_field_chunks(field, bucket, flat, group, works):
+    """All-reduce one field's flat gradient buffer piece by piece (GradBucket.chunks): density planes / lines
     (8.7 MB at 300^3), colour network (0.1 MB), then the appearance planes one by one (8.6 MB each; lines with the last) --
     instead of one 34.8 MB collective behind the whole backward.  The backward finishes the density branch early (its own
     stream, lrf_render_bwd) and, when ranks exchange gradients, runs the appearance scatter as one pass per plane: on the
@@ -94,19 +100,11 @@ def _reduce_field_chunks(field, flat, group, works):
     when that piece became final (lrf_render_bwd_wait), so RCCL moves finished gradients over xGMI while the rest of the
     backward still runs and only the last plane's ~ 9 MB are exposed.  Same sums as one flat all-reduce (the pieces are
     disjoint views).  Falls back to the caller's stream when the events are not those of this backward (empty batch,
-    captured graph, gradients copied back by rebucket_grads) or the wait fails: every rank still issues the same
-    collectives in the same order."""
-    chunks = getattr(field, "grad_chunks", lambda: None)()
-    if not chunks:
-        segs = getattr(field, "grad_segments", lambda: None)()
-        chunks = [(i, a, b) for i, (a, b) in enumerate(segs)] if segs else None
-    if not chunks:
-        works.append(_all_reduce(flat, group, async_op=True))
-        return 1
-    early = (flat.is_cuda and dist.get_backend(group) != "gloo" and hasattr(field, "_wait_bwd_bucket")
-             and getattr(field, "grad_events_valid", lambda: True)())
-    n = 0
-    for which, a, b in chunks:
+    captured graph, gradients copied back by GradBucket.rebucket) or the wait fails: every rank still issues the same
+    collectives in the same order.  Returns the byte count of every piece sent."""
+    early = flat.is_cuda and dist.get_backend(group) != "gloo" and bucket.events
+    sent = []
+    for which, a, b in bucket.chunks():
         if b <= a:
             continue
         chunk = flat[a:b]
@@ -125,8 +123,8 @@ def _reduce_field_chunks(field, flat, group, works):
                 early = False
         if not issued:
             works.append(_all_reduce(chunk, group, async_op=True))
-        n += 1
-    return n
+        sent.append((b - a) * 4)
+    return sent
 
 
 def allreduce_grads(params, group=None, average=False, has_grad=None, force=None, stats=None):
@@ -159,27 +157,24 @@ def allreduce_grads(params, group=None, average=False, has_grad=None, force=None
         return 0
     world = dist.get_world_size(group)
     nbytes, covered, works, flats = 0, set(), [], []
-    n_coll, chunk_bytes = 0, []
+    chunk_bytes = []
     unbucketed = set()                                        # fresh fields whose gradients could not be brought into a bucket
     always = set()                                            # ... their tensors: reduced whatever the hint says
-    for field, flat, held in _field_buckets(module):
+    for field, bucket, flat, held in _field_buckets(module):
         if flat is None:
             unbucketed.add(id(field))
             always.update(id(p) for p in field.parameters())
             continue
-        n_coll += _reduce_field_chunks(field, flat, group, works)
+        chunk_bytes += _reduce_field_chunks(field, bucket, flat, group, works)
         flats.append(flat)
         covered.update(id(p) for p in held)
         nbytes += sum(p.numel() for p in held) * 4
-        ch = getattr(field, "grad_chunks", lambda: None)()
-        if ch:
-            chunk_bytes += [(b - a) * 4 for _, a, b in ch]
-    field_bytes = nbytes
+    field_bytes, n_coll = nbytes, len(chunk_bytes)
     if module is not None:
         # Fields whose gradients live in a flat bucket but which took no part in this backward (every rank is in the same
         # lifecycle state): not ours to touch, whatever .grad holds (None after append_rf, a stale buffer otherwise)
         for m in module.modules():
-            if getattr(m, "grad_bucket", None) is not None and hasattr(m, "_grad_flat") and id(m) not in unbucketed:
+            if _bucket_of(m) is not None and id(m) not in unbucketed:
                 for p in m.parameters():
                     covered.add(id(p))
     rest = [p for p in params if id(p) not in covered]

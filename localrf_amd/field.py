@@ -17,6 +17,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _native as N
+from .grad_bucket import GradBucket
 
 EARLY_TERM_T_FAST = 1e-9                # TensorVMSplit.early_term_T opt-in value (north_star: "early termination")
 MAT_MODE = [[0, 1], [0, 2], [1, 2]]     # tensorBase.py:274
@@ -93,7 +94,7 @@ class _RenderFn(torch.autograd.Function):
         # .grad ends up outside the flat gradient buffer (rebucket_grads)
         ctx.l1 = None
         l1 = None
-        if getattr(field, "fuse_density_L1", False):
+        if field.fuse_density_L1:
             ctx.set_materialize_grads(False)
             dens = tuple(p.detach() for p in params[:6])
             l1, l1_ws = _DensityL1Fn.run_forward(field, dens)
@@ -250,10 +251,9 @@ class TensorVMSplit(torch.nn.Module):
         self.shadingMode, self.pos_pe, self.view_pe, self.fea_pe, self.featureC = (
             shadingMode, pos_pe, view_pe, fea_pe, featureC)
         self.renderModule = MLPRender_Fea_late_view(app_dim, view_pe, fea_pe, featureC).to(device)
-        # native-side state (derived; never stored in checkpoints)
-        self._cache = None
-        self._cache_key = None
-        self._ws = None
+        self._reset_native_state()
+        # opt-in: density_L1 as a third output of the render's autograd node (_RenderFn.forward); _fused_l1 is its value
+        self.fuse_density_L1 = False
         # colour-MLP engine: "bf16x3" split-bf16 (hi + lo, 3-term) MFMA chain, 32 samples per wave, k_shade3 (default) |
         # "f32" exact fp32 MFMA chain (LRF_FLAG_MLP_F32) | "valu" the generic fp32 engine on the vector ALU (LRF_FLAG_MLP_VALU); a non-default
         # view_pe / fea_pe / featureC always runs the generic engine, whatever this says
@@ -352,6 +352,16 @@ class TensorVMSplit(torch.nn.Module):
             "featureC": self.featureC,
         }
 
+    def _reset_native_state(self):
+        """Native-side state (derived; never stored in checkpoints), as __init__ and to() leave it: every piece is rebuilt by
+        the call that needs it."""
+        self._cache = self._cache_key = None     # channel-last / fragment-ordered layout of the parameters (_ensure_cache)
+        self._cfield = self._cfield_key = None   # LrfField struct of the current cache / alpha mask (_c_field)
+        self._ws = self._ws_bwd = None           # forward workspaces per stream (_workspace); the recomputing backward's
+        self._grads = None                       # GradBucket of the last backward (_native_backward)
+        self._fused_l1 = None                    # (value, parameter versions) of the last taped forward under fuse_density_L1
+        self._z_cache = {}
+
     def to(self, device):
         """tensorBase.py:560-565."""
         self.device = torch.device(device)
@@ -359,9 +369,7 @@ class TensorVMSplit(torch.nn.Module):
         self.gridSize = self.gridSize.to(device)
         if self.alphaMask is not None:
             self.alphaMask = self.alphaMask.to(device)
-        self._cache = self._cache_key = self._ws = self._ws_bwd = None
-        self._cfield_key = None
-        self._z_cache = {}
+        self._reset_native_state()
         return super().to(device)
 
     def normalize_coord(self, xyz):
@@ -413,7 +421,7 @@ class TensorVMSplit(torch.nn.Module):
         lib = N.lib()
         ps = self._param_list()
         akey = (self.aabb.data_ptr(), self.aabb._version)
-        if akey != getattr(self, "_aabb_key", None):          # load_state_dict / .to() replaced the bbox:
+        if akey != self._aabb_key:                            # load_state_dict / .to() replaced the bbox:
             self._aabb_host = [float(v) for v in self.aabb.detach().reshape(-1).tolist()]   # kernels read it live,
             self._aabb_key = akey                             # as normalize_coord does (tensorBase.py:342-345)
         key = tuple((p.data_ptr(), p._version) for p in ps) + tuple(self._grid_host) + tuple(self._aabb_host)
@@ -451,7 +459,7 @@ class TensorVMSplit(torch.nn.Module):
                None if mask is None else mask.alpha_volume.data_ptr(),
                float(self.density_shift), float(self.distance_scale), float(self.rayMarch_weight_thres),
                float(self.early_term_T), tuple(self._aabb_host))
-        if getattr(self, "_cfield_key", None) == key:
+        if self._cfield_key == key:
             return self._cfield
         f = N.LrfField()
         f.cache = self._cache.data_ptr()
@@ -508,7 +516,7 @@ class TensorVMSplit(torch.nn.Module):
             raise ValueError(f"unknown mlp_engine {self.mlp_engine!r}")
         if self.sort_rays:
             fl |= N.LRF_FLAG_SORT_RAYS
-        det = getattr(self, "deterministic", None)
+        det = self.deterministic
         if det if det is not None else torch.are_deterministic_algorithms_enabled():
             fl |= N.LRF_FLAG_DETERMINISTIC
         return fl
@@ -567,27 +575,10 @@ class TensorVMSplit(torch.nn.Module):
         return rgb, depth, ws, self._param_versions()
 
     def _new_grad_bucket(self, keep, R, dev, plane_events=False, events=False):
-        """One zero-filled buffer, one launch: the 19 gradients (and d/d rays [R,6] behind them) are views into it, 256-byte
-        aligned.  grad_bucket() / grad_chunks(): the data-parallel all-reduce runs in place on it, without copies.
-        `events`: the bucket events of lrf_render_bwd_wait belong to the backward that fills this buffer -- not for an empty
-        batch, and not inside a stream capture (a captured event cannot be waited for from outside the graph)."""
-        sizes = [p.numel() for p in keep] + [R * 6]
-        offs = [0]
-        for n in sizes:
-            offs.append(offs[-1] + (n + 63) // 64 * 64)
-        # lrf_render_bwd clears the buffer itself (LrfGrads.zero_base, with the launch that clears its bins) -- except for an
-        # empty batch, where it is not called
-        flat = torch.empty(offs[-1], dtype=torch.float32, device=dev) if R > 0 else torch.zeros(offs[-1], dtype=torch.float32, device=dev)
-        grads = [flat[offs[i]:offs[i] + p.numel()].view(p.shape) for i, p in enumerate(keep)]
-        g_rays = flat[offs[-2]:offs[-2] + R * 6].view(R, 6)
-        # (the view tensors themselves are NOT kept: autograd adopts an incoming gradient as .grad without a copy only while
-        # nobody else holds a reference to it)
-        self._grad_flat = {"flat": flat, "params": keep, "offs": offs[:len(keep)], "n_param": offs[-2],
-                           "dens": (offs[0], offs[6]), "app": (offs[6], offs[12]), "net": (offs[12], offs[-2]),
-                           "app_planes": (offs[6], offs[7], offs[8]),
-                           "events": bool(events), "plane_events": bool(plane_events)}
-        self._grad_fresh = True                    # written by THIS backward (localrf_amd.dist reduces fresh buckets only)
-        return grads, g_rays
+        """The GradBucket of a backward over R rays: one buffer, one launch -- the gradients of `keep` (_param_list(): density
+        tensors 0..5, appearance 6..11, network 12..18) and d/d rays [R,6] behind them are views into it."""
+        self._grads = GradBucket(keep, R, dev, 6, 12, plane_events, events)
+        return self._grads
 
     def _native_backward(self, rays, z, flags, g_rgb, g_depth, saved_ws=None):
         lib = N.lib()
@@ -599,8 +590,8 @@ class TensorVMSplit(torch.nn.Module):
         cp, keep = self._c_params()
         from . import dist as _dist
         plane_events = _dist.active()              # ranks exchange gradients: per-plane passes + events in the appearance scatter
-        grads, g_rays = self._new_grad_bucket(keep, R, dev, plane_events,
-                                              events=R > 0 and not torch.cuda.is_current_stream_capturing())
+        bucket = self._new_grad_bucket(keep, R, dev, plane_events, events=R > 0 and not torch.cuda.is_current_stream_capturing())
+        grads, g_rays = bucket.views()
         if R == 0:
             return g_rays, grads
         cg = N.LrfGrads()
@@ -610,8 +601,7 @@ class TensorVMSplit(torch.nn.Module):
             cg.app_plane[i] = grads[6 + i].data_ptr()
             cg.app_line[i] = grads[9 + i].data_ptr()
         (cg.basis, cg.w1, cg.b1, cg.w2, cg.b2, cg.w3, cg.b3) = [g.data_ptr() for g in grads[12:]]
-        flat = self._grad_flat["flat"]
-        cg.zero_base, cg.zero_floats = flat.data_ptr(), flat.numel()          # (offsets are multiples of 64 floats: so is the total)
+        cg.zero_base, cg.zero_floats = bucket.flat.data_ptr(), bucket.flat.numel()      # (the whole buffer: a multiple of 64 floats)
         # the deterministic mode is what the field / torch say NOW, when the backward is enqueued (not at the forward)
         flags = (flags & ~N.LRF_FLAG_DETERMINISTIC) | (self._flags(False) & N.LRF_FLAG_DETERMINISTIC)
         nbytes = lib.lrf_workspace_bytes_bwd_cfg(R, S, cp.grid, int(self.fea_pe), int(self.view_pe), int(self.featureC), flags)
@@ -621,7 +611,7 @@ class TensorVMSplit(torch.nn.Module):
             ws = saved_ws
             flags = flags | N.LRF_FLAG_ROWS_SAVED
         else:
-            if getattr(self, "_ws_bwd", None) is None or self._ws_bwd.numel() < nbytes or self._ws_bwd.device != dev:
+            if self._ws_bwd is None or self._ws_bwd.numel() < nbytes or self._ws_bwd.device != dev:
                 self._ws_bwd = None
                 self._ws_bwd = torch.empty(nbytes, dtype=torch.uint8, device=dev)
             ws = self._ws_bwd
@@ -636,85 +626,23 @@ class TensorVMSplit(torch.nn.Module):
                                    C.byref(cg), N.ptr(g_rays), ws.data_ptr(), st), "lrf_render_bwd")
         return g_rays, grads
 
+    # The gradient buffer of the last backward (localrf_amd.grad_bucket.GradBucket, which documents each of these)
     def grad_bucket(self):
-        """(flat, params): the parameter part of the ONE flat fp32 buffer holding the gradients of all 19 parameter tensors
-        after a backward, if .grad of every parameter is still a view of it (autograd adopts the views
-        when .grad was None, i.e. after zero_grad(set_to_none=True) -- what the optimisers here do).
-        localrf_amd.dist.allreduce_grads reduces it in place: one collective, no copies.  None when the
-        gradients were accumulated elsewhere (rebucket_grads() brings them back)."""
-        gf = getattr(self, "_grad_flat", None)
-        if gf is None:
-            return None
-        flat = gf["flat"]
-        base = flat.untyped_storage().data_ptr()
-        ps = [p for p in self._param_list() if p.requires_grad]
-        for p in ps:
-            if p.grad is None or p.grad.untyped_storage().data_ptr() != base:
-                return None
-        return flat[:gf["n_param"]], ps              # the parameter part: the d/d rays tail behind it is rank-local
+        return None if self._grads is None else self._grads.held()
 
     def rebucket_grads(self):
-        """Bring the gradients back into the flat buffer of the last backward when autograd put (some of) them elsewhere: it
-        sums the contributions to a parameter BEFORE it writes .grad, so with a regulariser in the loss (density_L1 / TV,
-        local_tensorfs.py:316-330: their node runs first) .grad of the density tensors is the regulariser's tensor with the
-        render gradient added to it, not the view lrf_render_bwd wrote.  One multi-tensor copy (device to device, the size of
-        the strays) and .grad re-pointed to the views -- instead of a concatenation of the whole field and a host read-back
-        on the data-parallel path.  Returns grad_bucket()."""
-        gf = getattr(self, "_grad_flat", None)
-        if gf is None:
-            return None
-        base = gf["flat"].untyped_storage().data_ptr()
-        src, dst, who = [], [], []
-        flat = gf["flat"]
-        for p, o in zip(gf["params"], gf["offs"]):
-            v = flat[o:o + p.numel()].view(p.shape)
-            if not p.requires_grad:
-                continue
-            if p.grad is None:                       # (no gradient reached it: nothing to bring back, nothing is invented)
-                return None
-            if p.grad.untyped_storage().data_ptr() != base:
-                if p.grad.shape != v.shape or p.grad.dtype != v.dtype or p.grad.device != v.device:
-                    return None
-                src.append(p.grad)
-                dst.append(v)
-                who.append(p)
-        if src:
-            torch._foreach_copy_(dst, src)
-            for p, v in zip(who, dst):
-                p.grad = v
-            gf["events"] = False                     # the bucket events of lrf_render_bwd are behind these copies
-        return self.grad_bucket()
-
-    def grad_segments(self):
-        """[(start, end)] float offsets into grad_bucket()'s flat buffer of the three branches of lrf_render_bwd, in the order
-        lrf_render_bwd_wait numbers them: density planes + lines, colour network (basis, three layers), appearance planes +
-        lines.  (grad_chunks() is what localrf_amd.dist reduces.)"""
-        gf = getattr(self, "_grad_flat", None)
-        if gf is None:
-            return None
-        return [gf["dens"], gf["net"], gf["app"]]
+        return None if self._grads is None else self._grads.rebucket()
 
     def grad_chunks(self):
-        """[(bucket, start, end)] in the order the backward finishes them: the pieces localrf_amd.dist all-reduces one by one,
-        each behind lrf_render_bwd_wait(bucket).  Density planes + lines (bucket 0: the per-ray branch ends early), colour
-        network (1), then the appearance tensors -- as ONE piece (2), or, when the backward ran its appearance scatter per
-        plane (LRF_FLAG_PLANE_EVENTS: a process group with more than one rank exists), plane 0 (3), plane 1 (4) and plane 2
-        with the three lines (2), so that only the last ~ third of the 26 MB (300^3) is exposed behind the backward."""
-        gf = getattr(self, "_grad_flat", None)
-        if gf is None:
-            return None
-        out = [(0,) + gf["dens"], (1,) + gf["net"]]
-        a0, a1, a2 = gf["app_planes"]
-        if gf["plane_events"]:
-            out += [(3, a0, a1), (4, a1, a2), (2, a2, gf["app"][1])]
-        else:
-            out.append((2,) + gf["app"])
-        return out
+        return None if self._grads is None else self._grads.chunks()
 
     def grad_events_valid(self):
-        """True when the bucket events of lrf_render_bwd_wait belong to the backward that filled grad_bucket()."""
-        gf = getattr(self, "_grad_flat", None)
-        return bool(gf is not None and gf["events"])
+        return self._grads is not None and self._grads.events
+
+    def drop_grads(self):
+        """This field takes part in no further backward (LocalTensorfs.append_rf): give up the gradient buffer."""
+        if self._grads is not None:
+            self._grads.release()
 
     def _wait_bwd_bucket(self, which, stream):
         """Make `stream` wait until bucket `which` (grad_chunks numbering) of the last lrf_render_bwd on this device is final."""
@@ -929,7 +857,7 @@ class TensorVMSplit(torch.nn.Module):
         registers instead of materialising 8 x g^3 floats per plane (same arithmetic and the
         reference's per-plane flattening orders)."""
         self._require_gpu(self.density_plane[0])
-        fused = getattr(self, "_fused_l1", None)
+        fused = self._fused_l1
         if fused is not None:                    # fuse_density_L1: the value the last taped forward of this field computed,
             self._fused_l1 = None                # once, and only for the parameters it was computed from
             if fused[1] == self._param_versions() and torch.is_grad_enabled():

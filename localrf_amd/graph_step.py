@@ -293,7 +293,7 @@ class CapturedIteration:
             self._graphs[0].replay()
             self.stats["replay_host_s"] = self.stats.get("replay_host_s", 0.0) + time.perf_counter() - t0    # (launch + any back-pressure of the queue)
             if sync is not None:
-                field._grad_fresh = True                          # (set by the backward's Python, which a replay does not run)
+                field._grads.fresh = True                         # (set by the backward's Python, which a replay does not run)
                 sync(lt)
                 self._graphs[1].replay()
             self.stats["replays"] += 1

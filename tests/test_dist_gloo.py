@@ -174,7 +174,7 @@ def test_two_rank_training_steps_match_single_rank_with_unsampled_views(tmp_path
 
 class _BucketField(torch.nn.Module):
     """Stand-in for a TensorVMSplit after lrf_render_bwd: all gradients are views of ONE flat buffer, in three branches
-    (density | appearance | network), exposed through grad_bucket() / grad_segments() as localrf_amd.field does."""
+    (density | appearance | network), owned as localrf_amd.field owns it: a localrf_amd.grad_bucket.GradBucket in _grads."""
 
     def __init__(self, seed, fresh=True):
         super().__init__()
@@ -182,35 +182,28 @@ class _BucketField(torch.nn.Module):
         self.dens = torch.nn.Parameter(torch.randn(37, generator=g))
         self.app = torch.nn.Parameter(torch.randn(101, generator=g))
         self.net = torch.nn.Parameter(torch.randn(13, generator=g))
-        self._grad_flat, self._grad_fresh = None, False
-        if fresh:
-            self.fill(seed)
+        self._grads = None
+        self.fill(seed)
+        if not fresh:                                         # a finished field (LocalTensorfs.append_rf, TensorVMSplit.drop_grads)
+            for p in self.parameters():
+                p.grad = None
+            self._grads.release()
 
-    def fill(self, seed):
+    def fill(self, seed, bucket_cls=None):
+        from localrf_amd.grad_bucket import GradBucket
         g = torch.Generator().manual_seed(1000 + seed)
-        offs = [0, 64, 192, 256]                              # 64-float aligned views, as _native_backward lays them out
-        flat = torch.zeros(offs[-1])
-        ps = [self.dens, self.app, self.net]
-        for p, o in zip(ps, offs):
-            flat[o:o + p.numel()] = torch.randn(p.numel(), generator=g)
-            p.grad = flat[o:o + p.numel()].view_as(p)
-        self._grad_flat = (flat, ps, offs[-1], (0, 64, 192, 256))
-        self._grad_fresh = True
-
-    def grad_bucket(self):
-        if self._grad_flat is None:
-            return None
-        return self._grad_flat[0][:self._grad_flat[2]], [self.dens, self.app, self.net]
-
-    def grad_segments(self):
-        d0, a0, n0, end = self._grad_flat[3]
-        return [(d0, a0), (n0, end), (a0, n0)]
+        # one tensor per branch, no rays: 64-float aligned views at 0 / 64 / 192, 256 floats in all
+        self._grads = (bucket_cls or GradBucket)([self.dens, self.app, self.net], 0, torch.device("cpu"), first_app=1, first_net=2)
+        assert self._grads.offs == [0, 64, 192] and self._grads.flat.numel() == self._grads.n_param == 256
+        for p, v in zip(self._grads.params, self._grads.views()[0]):
+            v.copy_(torch.randn(p.numel(), generator=g))
+            p.grad = v
 
 
 class _BucketScene(torch.nn.Module):
     def __init__(self, rank):
         super().__init__()
-        self.done = _BucketField(5, fresh=False)              # finished field: .grad None, _grad_flat None (append_rf)
+        self.done = _BucketField(5, fresh=False)              # finished field: .grad None, bucket released (append_rf)
         self.live = _BucketField(7 + rank)
         g = torch.Generator().manual_seed(50 + rank)
         self.poses = torch.nn.ParameterList([torch.nn.Parameter(torch.randn(3, generator=g)) for _ in range(4)])
@@ -226,10 +219,11 @@ def _worker_buckets(rank, world, port, out):
     for mode in ("flags", "hint"):
         m = _BucketScene(rank)
         hint = None if mode == "flags" else [m.poses[0], m.poses[1], m.poses[2]]
-        nbytes = allreduce_grads(m, has_grad=hint)
-        res[mode] = {"flat": m.live._grad_flat[0].clone(), "dens": m.live.dens.grad.clone(), "app": m.live.app.grad.clone(),
+        st = {}
+        nbytes = allreduce_grads(m, has_grad=hint, stats=st)
+        res[mode] = {"flat": m.live._grads.flat.clone(), "dens": m.live.dens.grad.clone(), "app": m.live.app.grad.clone(),
                      "net": m.live.net.grad.clone(), "poses": [None if p.grad is None else p.grad.clone() for p in m.poses],
-                     "done": [p.grad for p in m.done.parameters()], "bytes": nbytes, "fresh": m.live._grad_fresh}
+                     "done": [p.grad for p in m.done.parameters()], "bytes": nbytes, "fresh": m.live._grads.fresh, "stats": st}
     if rank == 0:
         torch.save(res, out)
     dist.barrier()
@@ -246,7 +240,7 @@ def test_chunked_field_reduction_equals_the_flat_sum_and_finished_fields_are_lef
     mp.spawn(_worker_buckets, args=(2, _free_port(), out), nprocs=2, join=True)
     got = torch.load(out)
     a, b = _BucketScene(0), _BucketScene(1)
-    want_flat = a.live._grad_flat[0] + b.live._grad_flat[0]
+    want_flat = a.live._grads.flat + b.live._grads.flat
     for mode in ("flags", "hint"):
         r = got[mode]
         assert torch.equal(r["flat"], want_flat), mode
@@ -256,6 +250,8 @@ def test_chunked_field_reduction_equals_the_flat_sum_and_finished_fields_are_lef
         assert r["poses"][3] is None                          # sampled by nobody: no gradient is invented
         assert all(g is None for g in r["done"])
         assert r["bytes"] == 4 * (37 + 101 + 13 + 9) and r["fresh"] is False
+        assert r["stats"]["collectives"] == 3 + 1              # density, network, appearance; the small bucket
+        assert r["stats"]["chunks"] == [4 * 64, 4 * 64, 4 * 128]       # (the pieces are the 64-float aligned branches)
 
 
 def test_shard_views_keeps_rays_per_view_integral():
@@ -273,16 +269,18 @@ def test_shard_views_keeps_rays_per_view_integral():
 
 
 class _StrayField(_BucketField):
-    """A fresh field whose gradients autograd accumulated outside the flat buffer and that cannot bring them back (no
-    rebucket_grads): grad_bucket() is None, every tensor of it must travel in the small bucket."""
+    """A fresh field whose gradients autograd accumulated outside the flat buffer and that cannot bring them back (its
+    bucket's rebucket() fails): held() is None too, every tensor of it must travel in the small bucket."""
 
     def fill(self, seed):
-        super().fill(seed)
+        from localrf_amd.grad_bucket import GradBucket
+
+        class NoWayBack(GradBucket):
+            def rebucket(self):
+                return None
+        super().fill(seed, NoWayBack)
         for p in (self.dens, self.app, self.net):
             p.grad = p.grad.clone() + 1.0
-
-    def grad_bucket(self):
-        return None
 
 
 class _StrayScene(torch.nn.Module):
@@ -304,7 +302,7 @@ class _RealFieldScene(torch.nn.Module):
         super().__init__()
         self.field = quiet(make_field, [10, 12, 14], "cpu", seed=3)
         keep = self.field._param_list()
-        grads, _ = self.field._new_grad_bucket(keep, 5, torch.device("cpu"), plane_events=True)
+        grads, _ = self.field._new_grad_bucket(keep, 5, torch.device("cpu"), plane_events=True).views()
         g = torch.Generator().manual_seed(100 + rank)
         self.full = []
         for i, (p, v) in enumerate(zip(keep, grads)):
@@ -330,7 +328,7 @@ def _worker_strays(rank, world, port, out):
         st = {}
         nb = allreduce_grads(r, has_grad=None if mode == "flags" else [r.pose], stats=st)
         bucket = r.field.grad_bucket()
-        base = r.field._grad_flat["flat"].untyped_storage().data_ptr()
+        base = r.field._grads.flat.untyped_storage().data_ptr()
         res["real_" + mode] = {"grads": [p.grad.clone() for p in r.field._param_list()], "pose": r.pose.grad.clone(), "bytes": nb,
                                "stats": st, "bucket": bucket is not None,
                                "views": all(p.grad.untyped_storage().data_ptr() == base for p in r.field._param_list())}
@@ -421,3 +419,57 @@ def test_batch_global_loss_normalisation_is_rank_count_invariant(tmp_path):
         assert float((got["global"][n] - p.grad).abs().max()) <= 2e-5 * den, n
         worst_local = max(worst_local, float((got["local"][n] - p.grad).abs().max()) / den)
     assert worst_local > 1e-2, worst_local                   # the per-shard mean is a different loss
+
+
+def test_grad_bucket_layout_hold_and_chunks():
+    """localrf_amd.grad_bucket.GradBucket on the 19 tensors of a 20 x 24 x 28 field: every view 64 floats aligned in the
+    order of _param_list(), the [R, 6] ray gradients behind the parameter part, the whole buffer a multiple of 64 floats
+    (LrfGrads.zero_floats); held() only while every .grad is a view of the buffer, rebucket() brings a stray back bit for
+    bit and invalidates the backward's events, and invents nothing for a parameter without a gradient; the pieces follow
+    lrf_render_bwd_wait's numbering with and without per-plane events and tile the parameter part."""
+    f = quiet(make_field, [20, 24, 28], "cpu", seed=5)
+    ps = f._param_list()
+    assert len(ps) == 19
+    R = 7
+    b = f._new_grad_bucket(ps, R, torch.device("cpu"), plane_events=False, events=True)
+    assert f._grads is b and b.fresh and b.events and not b.plane_events
+    pad = lambda n: (n + 63) // 64 * 64
+    want, o = [], 0
+    for p in ps:
+        want.append(o)
+        o += pad(p.numel())
+    assert b.offs == want and b.n_param == o and b.flat.numel() == o + pad(R * 6) and b.flat.numel() % 64 == 0
+    assert b.dens == (0, want[6]) and b.app == (want[6], want[12]) and b.net == (want[12], o) and b.app_planes == tuple(want[6:9])
+    grads, g_rays = b.views()
+    base = b.flat.untyped_storage().data_ptr()
+    assert g_rays.shape == (R, 6) and g_rays.data_ptr() == base + 4 * o
+    for p, g, off in zip(ps, grads, want):
+        assert g.shape == p.shape and g.data_ptr() == base + 4 * off
+    assert _field_bucket(ps, 0).flat.eq(0).all() and _field_bucket(ps, 0).views()[1].shape == (0, 6)     # empty batch: zeros, the C call is skipped
+
+    assert b.held() is None and b.rebucket() is None and b.events          # no .grad yet: nothing is invented
+    gen = torch.Generator().manual_seed(2)
+    for p, g in zip(ps, grads):
+        g.copy_(torch.randn(g.shape, generator=gen))
+        p.grad = g
+    del grads, g
+    flat, held = f.grad_bucket()
+    assert flat.data_ptr() == base and flat.numel() == o and [id(p) for p in held] == [id(p) for p in ps]
+    stray = ps[2].grad.clone() + 1.0
+    ps[2].grad = stray
+    assert b.held() is None and b.events
+    flat, held = b.rebucket()
+    assert ps[2].grad.data_ptr() == base + 4 * want[2] and torch.equal(ps[2].grad, stray) and len(held) == 19
+    assert not b.events and not f.grad_events_valid() and b.fresh
+
+    assert b.chunks() == [(0, 0, want[6]), (1, want[12], o), (2, want[6], want[12])]
+    bp = f._new_grad_bucket(ps, R, torch.device("cpu"), plane_events=True)
+    assert bp.chunks() == [(0, 0, want[6]), (1, want[12], o), (3, want[6], want[7]), (4, want[7], want[8]), (2, want[8], want[12])]
+    assert sorted((a, e) for _, a, e in bp.chunks())[0][0] == 0 and sum(e - a for _, a, e in bp.chunks()) == o
+    f.drop_grads()
+    assert f._grads is bp and bp.flat is None and not bp.fresh and f.grad_bucket() is None and f.rebucket_grads() is None and f.grad_chunks() is None
+
+
+def _field_bucket(ps, R):
+    from localrf_amd.grad_bucket import GradBucket
+    return GradBucket(ps, R, torch.device("cpu"), 6, 12)

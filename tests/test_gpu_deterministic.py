@@ -132,7 +132,7 @@ def test_plane_events_give_the_same_bits(built_lib, monkeypatch):
     plain = _native_bwd(f, rays, zz, gr, gd, f._flags(True))
     monkeypatch.setattr(dist, "active", lambda: True)
     g_rays, grads = f._native_backward(rays, zz, f._flags(True), gr, gd)
-    assert f._grad_flat["plane_events"]
+    assert f._grads.plane_events
     st = torch.cuda.current_stream(DEV).cuda_stream
     for bucket in (3, 4, 0, 1, 2):
         N.check(N.lib().lrf_render_bwd_wait(bucket, st), "lrf_render_bwd_wait")

@@ -1284,7 +1284,7 @@ def test_gradient_buckets_become_final_in_order_and_can_be_awaited_separately(bu
     rgb, depth = f(rays, white_bg=True, is_train=False, N_samples=120)
     ((rgb * gr).sum() + (depth * gd).sum()).backward()
     flat, held = f.grad_bucket()
-    segs = f.grad_segments()
+    segs = [(a, b) for _, a, b in f.grad_chunks()]          # density, colour network, appearance: lrf_render_bwd_wait's 0, 1, 2
     assert len(segs) == 3 and sorted(segs)[0][0] == 0 and sorted(segs)[-1][1] == flat.numel()
     covered = sorted(segs)
     assert all(covered[i][1] == covered[i + 1][0] for i in range(2))          # the three buckets tile the parameter part
