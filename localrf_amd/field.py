@@ -17,6 +17,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _native as N
+from .field_layout import FieldLayout, point_at
 from .grad_bucket import GradBucket
 
 EARLY_TERM_T_FAST = 1e-9                # TensorVMSplit.early_term_T opt-in value (north_star: "early termination")
@@ -246,12 +247,12 @@ class TensorVMSplit(torch.nn.Module):
         self.matMode, self.vecMode = MAT_MODE, VEC_MODE
         self.comp_w = [1, 1, 1]
         self._check_supported(shadingMode, pos_pe, view_pe, fea_pe, featureC)
+        self._reset_native_state()
         self.update_stepSize(list(gridSize))
         self.init_svd_volume(list(gridSize), device)
         self.shadingMode, self.pos_pe, self.view_pe, self.fea_pe, self.featureC = (
             shadingMode, pos_pe, view_pe, fea_pe, featureC)
         self.renderModule = MLPRender_Fea_late_view(app_dim, view_pe, fea_pe, featureC).to(device)
-        self._reset_native_state()
         # opt-in: density_L1 as a third output of the render's autograd node (_RenderFn.forward); _fused_l1 is its value
         self.fuse_density_L1 = False
         # colour-MLP engine: "bf16x3" split-bf16 (hi + lo, 3-term) MFMA chain, 32 samples per wave, k_shade3 (default) |
@@ -303,10 +304,7 @@ class TensorVMSplit(torch.nn.Module):
         self.stepSize = torch.mean(self.units) * self.step_ratio
         self.aabbDiag = torch.sqrt(torch.sum(torch.square(self.aabbSize)))
         self.nSamples = int((self.aabbDiag / self.stepSize).item()) + 1
-        # host copies, so the render call never synchronises to read them back
-        self._grid_host = [int(g) for g in gridSize]
-        self._aabb_host = [float(v) for v in self.aabb.detach().reshape(-1).tolist()]
-        self._aabb_key = (self.aabb.data_ptr(), self.aabb._version)
+        self.layout.refresh_host(self, gridSize)
         self._z_cache = {}
 
     def init_svd_volume(self, res, device):
@@ -352,15 +350,18 @@ class TensorVMSplit(torch.nn.Module):
             "featureC": self.featureC,
         }
 
-    def _reset_native_state(self):
+    def _reset_native_state(self, grid=None):
         """Native-side state (derived; never stored in checkpoints), as __init__ and to() leave it: every piece is rebuilt by
         the call that needs it."""
-        self._cache = self._cache_key = None     # channel-last / fragment-ordered layout of the parameters (_ensure_cache)
-        self._cfield = self._cfield_key = None   # LrfField struct of the current cache / alpha mask (_c_field)
-        self._ws = self._ws_bwd = None           # forward workspaces per stream (_workspace); the recomputing backward's
+        self.layout = FieldLayout(grid)          # packed parameter cache, LrfField struct, host grid / box, workspaces
         self._grads = None                       # GradBucket of the last backward (_native_backward)
         self._fused_l1 = None                    # (value, parameter versions) of the last taped forward under fuse_density_L1
         self._z_cache = {}
+
+    @property
+    def _grid_host(self):
+        """FieldLayout.grid under the name that callers written before the layout existed read (read-only)."""
+        return self.layout.grid
 
     def to(self, device):
         """tensorBase.py:560-565."""
@@ -369,7 +370,7 @@ class TensorVMSplit(torch.nn.Module):
         self.gridSize = self.gridSize.to(device)
         if self.alphaMask is not None:
             self.alphaMask = self.alphaMask.to(device)
-        self._reset_native_state()
+        self._reset_native_state(self.layout.grid)
         return super().to(device)
 
     def normalize_coord(self, xyz):
@@ -405,101 +406,20 @@ class TensorVMSplit(torch.nn.Module):
             if p.dtype != torch.float32 or not p.is_contiguous():
                 raise N.NativeError("localrf_amd: parameters must be contiguous fp32")
         cp = N.LrfParams()
-        for i in range(3):
-            cp.density_plane[i] = ps[i].data_ptr()
-            cp.density_line[i] = ps[3 + i].data_ptr()
-            cp.app_plane[i] = ps[6 + i].data_ptr()
-            cp.app_line[i] = ps[9 + i].data_ptr()
-        (cp.basis, cp.w1, cp.b1, cp.w2, cp.b2, cp.w3, cp.b3) = [p.data_ptr() for p in ps[12:]]
-        cp.grid[:] = self._grid_host
+        point_at(cp, ps)
+        cp.grid[:] = self.layout.grid
         cp.fea_pe, cp.view_pe, cp.feature_c = int(self.fea_pe), int(self.view_pe), int(self.featureC)
         return cp, ps
 
+    # bench.py and localrf_amd.scene_ops call these three; the work is FieldLayout's
     def _ensure_cache(self):
-        """(Re)build the channel-last / fragment-ordered layout cache when any parameter
-        changed (optimizer step, upsample tensoRF.py:224-233, load_state_dict, .to())."""
-        lib = N.lib()
-        ps = self._param_list()
-        akey = (self.aabb.data_ptr(), self.aabb._version)
-        if akey != self._aabb_key:                            # load_state_dict / .to() replaced the bbox:
-            self._aabb_host = [float(v) for v in self.aabb.detach().reshape(-1).tolist()]   # kernels read it live,
-            self._aabb_key = akey                             # as normalize_coord does (tensorBase.py:342-345)
-        key = tuple((p.data_ptr(), p._version) for p in ps) + tuple(self._grid_host) + tuple(self._aabb_host)
-        if self._cache is not None and key == self._cache_key:
-            return
-        cp, keep = self._c_params()
-        nbytes = lib.lrf_cache_bytes(cp.grid)
-        dev = ps[0].device
-        if self._cache is None or self._cache.numel() * 4 != nbytes or self._cache.device != dev:
-            self._cache = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
-        st = torch.cuda.current_stream(dev).cuda_stream
-        N.check(lib.lrf_pack_field(C.byref(cp), self._cache.data_ptr(), st), "lrf_pack_field")
-        self._cache_key = key
-
-    def _fused_step_target(self):
-        """(LrfParams, parameter list, cache) for lrf_adam_step_pack -- the optimiser step that leaves the layout cache holding
-        the stepped values (localrf_amd.optim.FusedAdam(pack_field=...)) -- or None while no cache of the current grid's size
-        exists (the first forward, after an upsample / a device move): then the step runs alone and the next forward packs."""
-        if self._cache is None or self._cache_key is None:
-            return None
-        cp, ps = self._c_params()
-        if self._cache.device != ps[0].device or self._cache.numel() * 4 != N.lib().lrf_cache_bytes(cp.grid):
-            return None
-        return cp, ps, self._cache
-
-    def _mark_cache_fresh(self):
-        """The cache was just rewritten from the parameters as they are now (lrf_adam_step_pack): _ensure_cache's key."""
-        ps = self._param_list()
-        self._cache_key = tuple((p.data_ptr(), p._version) for p in ps) + tuple(self._grid_host) + tuple(self._aabb_host)
+        self.layout.ensure(self)
 
     def _c_field(self):
-        """LrfField struct for the current cache / alpha mask (rebuilt only when they change)."""
-        mask = self.alphaMask
-        key = (self._cache.data_ptr(), self._cache_key, id(mask),
-               None if mask is None else mask.alpha_volume.data_ptr(),
-               float(self.density_shift), float(self.distance_scale), float(self.rayMarch_weight_thres),
-               float(self.early_term_T), tuple(self._aabb_host))
-        if self._cfield_key == key:
-            return self._cfield
-        f = N.LrfField()
-        f.cache = self._cache.data_ptr()
-        f.aabb[:] = self._aabb_host
-        f.grid[:] = self._grid_host
-        if mask is not None:
-            vol = mask.alpha_volume.detach()
-            f.alpha_vol = vol.data_ptr()
-            f.alpha_dim[:] = [vol.shape[-1], vol.shape[-2], vol.shape[-3]]
-            mk = (mask.aabb.data_ptr(), mask.aabb._version)
-            if getattr(mask, "_aabb_host_key", None) != mk:       # read back once per mask (a rebuild makes a new mask): _c_field can
-                mask._aabb_host = [float(v) for v in mask.aabb.detach().reshape(-1).tolist()]   # then run inside a stream capture
-                mask._aabb_host_key = mk
-            f.alpha_aabb[:] = mask._aabb_host
-        else:
-            f.alpha_vol = None
-            f.alpha_dim[:] = [0, 0, 0]
-            f.alpha_aabb[:] = self._aabb_host
-        f.density_shift = float(self.density_shift)
-        f.distance_scale = float(self.distance_scale)
-        f.weight_thres = float(self.rayMarch_weight_thres)
-        f.term_T = float(self.early_term_T)
-        ps = self._param_list()[12:]
-        (f.basis, f.w1, f.b1, f.w2, f.b2, f.w3, f.b3) = [p.data_ptr() for p in ps]
-        f.fea_pe, f.view_pe, f.feature_c = int(self.fea_pe), int(self.view_pe), int(self.featureC)
-        self._cfield, self._cfield_key = f, key
-        return f
+        return self.layout.c_field(self)
 
     def _workspace(self, R, S, dev):
-        nbytes = N.lib().lrf_workspace_bytes(R, S)
-        # one workspace per stream that renders through this field: two streams may run eval forwards of the same field side by
-        # side (k_march of one batch beside k_shade3 of another: 4096-ray batches alternating over two streams 0.164 -> 0.145 ms
-        # per batch, scripts/two_stream_fwd_probe.py); the layout cache they read is shared
-        key = torch.cuda.current_stream(dev).cuda_stream
-        if not isinstance(self._ws, dict):
-            self._ws = {}
-        ws = self._ws.get(key)
-        if ws is None or ws.numel() < nbytes or ws.device != dev:
-            ws = self._ws[key] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        return ws
+        return self.layout.workspace(R, S, dev)
 
     def _flags(self, white_bg):
         fl = 0
@@ -521,14 +441,18 @@ class TensorVMSplit(torch.nn.Module):
             fl |= N.LRF_FLAG_DETERMINISTIC
         return fl
 
-    def _native_forward(self, rays, z, flags, floater, want_weights=False, out=None):
+    def _open(self, rays, z):
+        """The shared opening of the three native calls: the cache packed from the current parameters, then contiguous fp32
+        rays [R,6] and z [S] with R, S and the device."""
         self._require_gpu(rays)
-        lib = N.lib()
-        self._ensure_cache()
+        self.layout.ensure(self)
         rays = rays.detach().contiguous().float()
         z = z.detach().contiguous().float().view(-1)
-        R, S = rays.shape[0], z.shape[0]
-        dev = rays.device
+        return rays, z, rays.shape[0], z.shape[0], rays.device
+
+    def _native_forward(self, rays, z, flags, floater, want_weights=False, out=None):
+        lib = N.lib()
+        rays, z, R, S, dev = self._open(rays, z)
         if out is not None:                 # caller-owned outputs (LocalTensorfs blends them in place)
             rgb, depth = out
             if (rgb.shape != (R, 3) or depth.shape != (R,) or rgb.dtype != torch.float32
@@ -541,8 +465,8 @@ class TensorVMSplit(torch.nn.Module):
         acc = torch.empty(R, dtype=torch.float32, device=dev) if want_weights else None
         if R == 0:
             return (rgb, depth, w_out, acc) if want_weights else (rgb, depth)
-        ws = self._workspace(R, S, dev)
-        f = self._c_field()
+        ws = self.layout.workspace(R, S, dev)
+        f = self.layout.c_field(self)
         st = torch.cuda.current_stream(dev).cuda_stream
         N.check(lib.lrf_render_fwd(C.byref(f), N.ptr(rays), N.ptr(z), R, S, flags, float(floater),
                                    N.ptr(rgb), N.ptr(depth), N.ptr(w_out), N.ptr(acc),
@@ -554,21 +478,16 @@ class TensorVMSplit(torch.nn.Module):
 
     def _native_forward_train(self, rays, z, flags):
         """lrf_render_fwd_train: forward that keeps the backward's per-sample state in a workspace."""
-        self._require_gpu(rays)
         lib = N.lib()
-        self._ensure_cache()
-        rays = rays.detach().contiguous().float()
-        z = z.detach().contiguous().float().view(-1)
-        R, S = rays.shape[0], z.shape[0]
-        dev = rays.device
+        rays, z, R, S, dev = self._open(rays, z)
         rgb = torch.empty(R, 3, dtype=torch.float32, device=dev)
         depth = torch.empty(R, dtype=torch.float32, device=dev)
         if R == 0:
             return rgb, depth, None, None
-        grid = (C.c_int32 * 3)(*self._grid_host)
+        grid = (C.c_int32 * 3)(*self.layout.grid)
         ws = torch.empty(lib.lrf_workspace_bytes_bwd_cfg(R, S, grid, int(self.fea_pe), int(self.view_pe), int(self.featureC), flags),
                          dtype=torch.uint8, device=dev)
-        f = self._c_field()
+        f = self.layout.c_field(self)
         st = torch.cuda.current_stream(dev).cuda_stream
         N.check(lib.lrf_render_fwd_train(C.byref(f), N.ptr(rays), N.ptr(z), R, S, flags, N.ptr(rgb), N.ptr(depth),
                                          ws.data_ptr(), st), "lrf_render_fwd_train")
@@ -582,11 +501,7 @@ class TensorVMSplit(torch.nn.Module):
 
     def _native_backward(self, rays, z, flags, g_rgb, g_depth, saved_ws=None):
         lib = N.lib()
-        self._ensure_cache()
-        rays = rays.detach().contiguous().float()
-        z = z.detach().contiguous().float().view(-1)
-        R, S = rays.shape[0], z.shape[0]
-        dev = rays.device
+        rays, z, R, S, dev = self._open(rays, z)
         cp, keep = self._c_params()
         from . import dist as _dist
         plane_events = _dist.active()              # ranks exchange gradients: per-plane passes + events in the appearance scatter
@@ -595,12 +510,7 @@ class TensorVMSplit(torch.nn.Module):
         if R == 0:
             return g_rays, grads
         cg = N.LrfGrads()
-        for i in range(3):
-            cg.density_plane[i] = grads[i].data_ptr()
-            cg.density_line[i] = grads[3 + i].data_ptr()
-            cg.app_plane[i] = grads[6 + i].data_ptr()
-            cg.app_line[i] = grads[9 + i].data_ptr()
-        (cg.basis, cg.w1, cg.b1, cg.w2, cg.b2, cg.w3, cg.b3) = [g.data_ptr() for g in grads[12:]]
+        point_at(cg, grads)
         cg.zero_base, cg.zero_floats = bucket.flat.data_ptr(), bucket.flat.numel()      # (the whole buffer: a multiple of 64 floats)
         # the deterministic mode is what the field / torch say NOW, when the backward is enqueued (not at the forward)
         flags = (flags & ~N.LRF_FLAG_DETERMINISTIC) | (self._flags(False) & N.LRF_FLAG_DETERMINISTIC)
@@ -611,13 +521,10 @@ class TensorVMSplit(torch.nn.Module):
             ws = saved_ws
             flags = flags | N.LRF_FLAG_ROWS_SAVED
         else:
-            if self._ws_bwd is None or self._ws_bwd.numel() < nbytes or self._ws_bwd.device != dev:
-                self._ws_bwd = None
-                self._ws_bwd = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-            ws = self._ws_bwd
+            ws = self.layout.workspace_bwd(nbytes, dev)
         if plane_events:
             flags = flags | N.LRF_FLAG_PLANE_EVENTS
-        f = self._c_field()
+        f = self.layout.c_field(self)
         st = torch.cuda.current_stream(dev).cuda_stream
         g_rgb_c = g_rgb.contiguous().float()         # named: must outlive the launch below
         g_depth_c = g_depth.contiguous().float()
@@ -718,7 +625,7 @@ class TensorVMSplit(torch.nn.Module):
         pts = torch.empty(R, n, 3, device=dev)
         t = torch.empty(R, n, device=dev)
         inside = torch.empty(R, n, dtype=torch.uint8, device=dev)
-        aabb = (C.c_float * 6)(*self._aabb_host)
+        aabb = (C.c_float * 6)(*self.layout.refresh_host(self))
         st = torch.cuda.current_stream(dev).cuda_stream
         N.check(lib.lrf_sample_ray_aabb(N.ptr(rays), aabb, float(self.stepSize), float(self.near_far[0]),
                                         float(self.near_far[1]), N.ptr(jit), R, n, N.ptr(pts), N.ptr(t),
@@ -763,8 +670,7 @@ class TensorVMSplit(torch.nn.Module):
         # the kernels, the workspace size and get_kwargs() read the configuration from these attributes (ADVICE round 4:
         # stale values made the kernels index the new weights with the old shapes)
         self.shadingMode, self.pos_pe, self.view_pe, self.fea_pe, self.featureC = shadingMode, pos_pe, view_pe, fea_pe, featureC
-        self._cache_key = None
-        self._cfield_key = None
+        self.layout.invalidate()
 
     def get_arange(self, idx):
         """tensoRF.py:14-16 (unused by the reference): the lattice coordinates along axis idx, pulled 1e-6 inside the box."""

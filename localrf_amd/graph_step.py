@@ -105,7 +105,7 @@ class CapturedIteration:
     def _signature(self, start, pose_ids, tune_intrinsics):
         lt = self.scene
         f = lt.tensorfs[-1]
-        return (len(lt.tensorfs), len(lt.r_c2w), tuple(int(g) for g in f._grid_host), int(f.nSamples), id(f.alphaMask),
+        return (len(lt.tensorfs), len(lt.r_c2w), f.layout.grid, int(f.nSamples), id(f.alphaMask),
                 None if f.alphaMask is None else f.alphaMask.alpha_volume.data_ptr(), id(lt.rf_optimizer), bool(lt.is_refining),
                 int(start), tuple(pose_ids), bool(tune_intrinsics), lt.grad_sync is not None,
                 tuple(p.data_ptr() for p in f._param_list())) + tuple(self.extra_signature())
@@ -282,7 +282,7 @@ class CapturedIteration:
                 # (lrf_adam_step_pack: the cache is fresh from the eager iteration just run, and every replay leaves it fresh
                 # for the next) -- otherwise lrf_pack_field is the graph's first node
                 if not self.plan.packs(field):
-                    field._cache_key = None
+                    field.layout.invalidate()
                 if sync is None:
                     self._graphs = (self._capture(lambda: (self._forward_backward(), self._adam())),)
                 else:

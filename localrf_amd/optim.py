@@ -25,7 +25,7 @@ def _pack_target(fields):
     if len(fs) != 1:
         return None
     (field,) = fs.values()
-    tgt = field._fused_step_target()
+    tgt = field.layout.step_target(field)
     return None if tgt is None else (field, tgt)
 
 
@@ -103,11 +103,11 @@ class FusedAdam(torch.optim.Optimizer):
                     field, (cp, keep, cache) = fused
                     N.check(lib.lrf_adam_step_pack(tab, len(part), None, b1, b2, eps, C.byref(cp), cache.data_ptr(), st), "lrf_adam_step_pack")
                     increment_version([e[0] for e in part])
-                    field._mark_cache_fresh()
+                    field.layout.mark_fresh(field)
                     continue
                 N.check(lib.lrf_adam_step(tab, len(part), b1, b2, eps, st), "lrf_adam_step")
                 # the kernel rewrote the parameters behind autograd's back: bump their versions so
-                # layout caches keyed on (data_ptr, _version) (TensorVMSplit._ensure_cache) and
+                # layout caches keyed on (data_ptr, _version) (FieldLayout.current_key) and
                 # autograd's saved-tensor checks see the change
                 increment_version([e[0] for e in part])
 
@@ -149,6 +149,7 @@ class StaticAdamPlan:
                 st["step"] = 0
                 st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
                 st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+        self._packed_field = None                                 # the field whose layout cache launch() rewrites (lrf_adam_step_pack)
         self._group = {}
         for opt, _ in self.pairs:
             for grp in opt.param_groups:
@@ -230,6 +231,6 @@ class StaticAdamPlan:
         """The replayed kernels rewrote the parameters behind autograd's back (see FusedAdam._launch) -- and, when the launch was
         lrf_adam_step_pack, the field's layout cache with them."""
         increment_version([p for _, p in self.pairs])
-        f = getattr(self, "_packed_field", None)
+        f = self._packed_field
         if f is not None:
-            f._mark_cache_fresh()
+            f.layout.mark_fresh(f)

@@ -20,7 +20,7 @@ rays = torch.cat([make_rays(4096, 1 + i) for i in range((a.rays + 4095) // 4096)
 ref = None
 for ch in [int(x) for x in a.chunks.split(",")]:
     lib.lrf_debug_set_pipe_chunk(ch)
-    f._ws = None                                   # (the workspace size depends on the chunking)
+    f.layout.release_workspaces()                               # (the workspace size depends on the chunking)
     with torch.no_grad():
         for _ in range(3):
             rgb, depth = f(rays, white_bg=True, is_train=False, N_samples=a.samples)

@@ -325,7 +325,7 @@ def run(frames=24, W=64, H=48, n_init=5, final=300, iters_per_frame=60, batch=40
     mem_marks = []
     training = True
     t_mark, it_mark = time.perf_counter(), 0
-    res = int(lt.tensorfs[-1]._grid_host[0])                          # (the host copy: gridSize itself is a device tensor, as in the reference -- reading it drains the stream)
+    res = int(lt.tensorfs[-1].layout.grid[0])                          # (the host copy: gridSize itself is a device tensor, as in the reference -- reading it drains the stream)
     pace = []
     host_t = {}                                                        # res -> seconds of host time by section of the loop body (captured loop)
     while training and (max_iters is None or it < max_iters):
@@ -419,7 +419,7 @@ def run(frames=24, W=64, H=48, n_init=5, final=300, iters_per_frame=60, batch=40
                                 "rot_step_deg": float(torch.rad2deg(torch.acos(cosang))[ok].mean()) if ok.any() else 0.0}
                     geo_curve.append({**diag, "it": it, "field": len(lt.tensorfs) - 1, "rf_iter": int(lt.rf_iter[-1]), "refining": bool(lt.is_refining),
                                       "reg_w": float(reg_w), "flow": geo_vals[-1][0], "depth": geo_vals[-1][1], "photo": float(loss.detach()),
-                                      "frames": [lo, hi], "res": int(lt.tensorfs[-1]._grid_host[0]),
+                                      "frames": [lo, hi], "res": int(lt.tensorfs[-1].layout.grid[0]),
                                       "pose_err": float(rel.norm(dim=-1).mean()), "est_step": float(step_est), "true_step": 0.04})
             if lt.regularize:
                 tv, l1 = lt.get_reg_loss(None, 0.0, 0.0, L1_weight)         # train.py:425-429, opt.py:111-113
@@ -460,7 +460,7 @@ def run(frames=24, W=64, H=48, n_init=5, final=300, iters_per_frame=60, batch=40
         it += 1
         if it % 250 == 0:
             pace.append((it, time.perf_counter()))                     # (the host's pace: at most four iterations ahead of the GPU)
-        new_res = int(lt.tensorfs[-1]._grid_host[0])                   # (host copy: int(gridSize[0]) here drained the stream on EVERY iteration -- host and GPU took turns, 0.15 ms of every captured iteration)
+        new_res = int(lt.tensorfs[-1].layout.grid[0])                   # (host copy: int(gridSize[0]) here drained the stream on EVERY iteration -- host and GPU took turns, 0.15 ms of every captured iteration)
         if new_res != res or not training or (max_iters is not None and it == max_iters):
             torch.cuda.synchronize(dev)
             dt = time.perf_counter() - t_mark

@@ -102,6 +102,65 @@ def test_forward_without_gpu_raises_not_falls_back():
         f.compute_densityfeature(torch.zeros(4, 3))
 
 
+def test_field_layout_invalidation_rule():
+    """FieldLayout on the host (no launch): the cache key differs after an in-place version bump, a Parameter replaced by a
+    new object of the same shape, update_stepSize to another grid and a load_state_dict that changes aabb; invalidate()
+    makes the next ensure() due; mark_fresh() stores exactly the key ensure() compares with; a fresh field and a field after
+    to() hold no cache; nothing of the layout reaches state_dict()."""
+    from localrf_amd.field_layout import FieldLayout
+    f = quiet(make_field, [16, 12, 14], seed=1)
+    lay = f.layout
+    assert isinstance(lay, FieldLayout) and not isinstance(lay, torch.nn.Module)
+    assert lay.cache is None and lay.key is None and not lay.is_fresh(f)
+    assert lay.grid == (16, 12, 14) and lay.box == (-2.0, -2.0, -2.0, 2.0, 2.0, 2.0)
+    assert f._grid_host is lay.grid                             # the read-only name earlier callers use
+    assert not any("layout" in k for k in f.state_dict())
+
+    seen = [lay.current_key(f)]
+    assert lay.current_key(f) == seen[0]                        # forming the key changes nothing
+
+    def changed():
+        k = lay.current_key(f)
+        assert k not in seen
+        seen.append(k)
+        return k
+
+    lay.mark_fresh(f)
+    assert lay.key == seen[0] and lay.is_fresh(f)               # exactly the key ensure() would store
+    with torch.no_grad():
+        f.app_line[1].mul_(1.5)                                 # an in-place version bump
+    assert not lay.is_fresh(f)
+    changed()
+    lay.mark_fresh(f)
+    old = f.density_plane[0]
+    f.density_plane[0] = torch.nn.Parameter(old.detach().clone())   # a new object of the same shape
+    assert f.density_plane[0].shape == old.shape and not lay.is_fresh(f)
+    changed()
+    lay.mark_fresh(f)
+    quiet(f.update_stepSize, [20, 12, 14])                      # another grid
+    assert lay.grid == (20, 12, 14) and not lay.is_fresh(f)
+    assert changed()[-9:-6] == (20, 12, 14)
+    lay.mark_fresh(f)
+    sd = {k: v.clone() for k, v in f.state_dict().items()}
+    sd["aabb"] = sd["aabb"] * 1.5
+    f.load_state_dict(sd)                                       # another box, read back by the key's own refresh
+    assert not lay.is_fresh(f)
+    assert changed()[-6:] == (-3.0, -3.0, -3.0, 3.0, 3.0, 3.0) and lay.box == (-3.0, -3.0, -3.0, 3.0, 3.0, 3.0)
+
+    lay.mark_fresh(f)
+    assert lay.is_fresh(f) and lay.key == lay.current_key(f)
+    lay.invalidate()
+    assert lay.key is None and not lay.is_fresh(f)              # the next ensure() packs
+    assert lay.step_target(f) is None                           # and no fused step writes into a stale cache
+
+    lay.mark_fresh(f)
+    g = f.to("cpu")
+    assert g is f and f.layout is not lay                       # to() starts over: no cache, the grid's host copy kept
+    assert f.layout.cache is None and f.layout.key is None and not f.layout.is_fresh(f)
+    assert f.layout.grid == (20, 12, 14) and f.layout.ws == {} and f.layout.ws_bwd is None
+    assert f.layout.current_key(f) == seen[-1]
+
+
 def test_local_tensorfs_surface_and_checkpoint_roundtrip(tmp_path):
     from localrf_amd import LocalTensorfs
     g = load_golden("local_4fields")

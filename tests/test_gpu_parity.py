@@ -262,7 +262,7 @@ def test_early_termination_on_a_trained_like_scene(built_lib):
     import ctypes as C
     from localrf_amd import _native as N
     out = (C.c_uint64 * 9)()
-    N.lib().lrf_workspace_layout_bwd(512, z.numel(), (C.c_int32 * 3)(*f._grid_host), out)
+    N.lib().lrf_workspace_layout_bwd(512, z.numel(), (C.c_int32 * 3)(*f.layout.grid), out)
     skipped = {}
     for T in (1e-9, 0.0):
         f.early_term_T = T
@@ -663,13 +663,13 @@ def test_large_batches_in_chunks_over_two_streams(built_lib, sort):
     try:
         for chunk in (0, 2048):
             built_lib.lrf_debug_set_pipe_chunk(chunk)
-            f._ws = None
+            f.layout.release_workspaces()
             with torch.no_grad():
                 rgb, depth = f(rays, white_bg=True, is_train=False, N_samples=96)
             out[chunk] = (rgb.clone(), depth.clone())
     finally:
         built_lib.lrf_debug_set_pipe_chunk(16384)
-        f._ws = None
+        f.layout.release_workspaces()
     assert float(out[0][0].std()) > 0.01
     assert torch.equal(out[0][0], out[2048][0]) and torch.equal(out[0][1], out[2048][1])
 
@@ -1073,7 +1073,7 @@ def test_training_results_do_not_depend_on_what_the_workspace_held(built_lib, cf
     _g = torch.Generator().manual_seed(5)
     gr, gd = torch.randn(R, 3, generator=_g).to(DEV), torch.randn(R, generator=_g).to(DEV)
     f.z_override = f.z_schedule(False, 60, torch.device(DEV)).clone()
-    nbytes = N.lib().lrf_workspace_bytes_bwd_cfg(R, f.z_override.numel(), (C.c_int32 * 3)(*f._grid_host), int(f.fea_pe), int(f.view_pe), int(f.featureC), 0)
+    nbytes = N.lib().lrf_workspace_bytes_bwd_cfg(R, f.z_override.numel(), (C.c_int32 * 3)(*f.layout.grid), int(f.fea_pe), int(f.view_pe), int(f.featureC), 0)
 
     def run(poison):
         for p in f.parameters():

@@ -1115,13 +1115,13 @@ def test_full_frame_scene_forward_in_chunks_over_two_streams(built_lib):
         for chunk in (0, 16384):
             built_lib.lrf_debug_set_pipe_chunk(chunk)
             for f in lt.tensorfs:
-                f._ws = None
+                f.layout.release_workspaces()
             with torch.no_grad():
                 out[chunk] = [t.clone() for t in lt(ray_ids, view_ids, W, H, is_train=False, white_bg=True, chunk=65536)]
     finally:
         built_lib.lrf_debug_set_pipe_chunk(16384)
         for f in lt.tensorfs:
-            f._ws = None
+            f.layout.release_workspaces()
     assert float(out[0][0].std()) > 1e-3
     for a, b in zip(out[0], out[16384]):
         assert torch.equal(a, b)
@@ -1494,27 +1494,27 @@ def test_adam_step_fused_with_the_layout_refresh(built_lib, grid):
                 out = f(rays, N_samples=64)                     # builds / takes the cache
             for n, p in f.named_parameters():
                 p.grad = None if (n == "density_line.1" and it == 1) else grads[n].clone()
-        key_before = fb._cache_key
+        key_before = fb.layout.key
         oa.step()
         ob.step()
-        assert fb._cache_key is not None and fb._cache_key != key_before          # marked fresh for the NEW parameter versions
+        assert fb.layout.key is not None and fb.layout.key != key_before          # marked fresh for the NEW parameter versions
         for (n, p), (_, q) in zip(fa.named_parameters(), fb.named_parameters()):
             assert torch.equal(p, q), n
             if p in oa.state and "exp_avg" in oa.state[p]:
                 assert torch.equal(oa.state[p]["exp_avg"], ob.state[q]["exp_avg"]) and torch.equal(oa.state[p]["exp_avg_sq"], ob.state[q]["exp_avg_sq"]), n
         # the cache the fused step left == a fresh pack of the same parameters
         cp, keep = fb._c_params()
-        fresh = fb._cache.clone()                                # (the alignment gaps between the cache's sections are nobody's: same bytes on both sides)
+        fresh = fb.layout.cache.clone()                                # (the alignment gaps between the cache's sections are nobody's: same bytes on both sides)
         N.check(built_lib.lrf_pack_field(C.byref(cp), fresh.data_ptr(), torch.cuda.current_stream().cuda_stream), "lrf_pack_field")
         torch.cuda.synchronize()
-        assert torch.equal(fresh.view(torch.int32), fb._cache.view(torch.int32)), it
-        key = fb._cache_key
+        assert torch.equal(fresh.view(torch.int32), fb.layout.cache.view(torch.int32)), it
+        key = fb.layout.key
         with torch.no_grad():
             ra, _ = fa(rays, N_samples=64)
             rb, _ = fb(rays, N_samples=64)
-        assert fb._cache_key == key                              # the forward took the cache as the step left it
+        assert fb.layout.key == key                              # the forward took the cache as the step left it
         assert torch.equal(ra, rb)
     with torch.no_grad():
         fb.app_plane[0].mul_(1.5)
         rc, _ = fb(rays, N_samples=64)
-    assert fb._cache_key != key and not torch.equal(rb, rc)
+    assert fb.layout.key != key and not torch.equal(rb, rc)

@@ -205,7 +205,7 @@ def kernel_relu_masks(f, rays, z, ws):
     from localrf_amd import _native as N
     R, S = rays.shape[0], z.numel()
     out = (C.c_uint64 * 9)()
-    N.lib().lrf_workspace_layout_bwd(R, S, (C.c_int32 * 3)(*f._grid_host), out)
+    N.lib().lrf_workspace_layout_bwd(R, S, (C.c_int32 * 3)(*f.layout.grid), out)
     _, _, ri_off, toff_off, _, _, bits_off, perm_off, _ = [int(v) for v in out]
     toff = ws[toff_off:toff_off + 4 * (R + 1)].view(torch.int32)
     tiles = int(toff[R])
