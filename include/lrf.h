@@ -577,6 +577,33 @@ int lrf_encode_frames(const float* rgb /* nullable */, const float* depth, int32
                       const float* fixed_range /* nullable */, uint8_t* rgb8 /* nullable */, uint8_t* depth8, uint8_t* depth_idx /* nullable */,
                       float* range_out /* nullable */, void* workspace, void* stream);
 
+/* lrf_points_fuse: V rendered depth images fused into one filtered, ordered, coloured world-space point list.
+ * depth [V,H,W] fp32, rgb8 [V,H,W,3] uint8 (nullable, with rgb8_out), cam2world [V,3,4] fp32, focal device [1] / center
+ * device [2] (pinhole; as lrf_scene_rays takes them) or fov360.  Candidates are the pixels (i, j) with i % stride == 0 and
+ * j % stride == 0.  A candidate is kept when its depth d is finite, positive and inside [d_min, d_max] and, with n_neigh > 0
+ * (pinhole only), when its world point pw = R_v (pixel_dir * d) + t_v, reprojected into the frames v + neigh[k] that exist,
+ * agrees with the depth found there (|z - dn| <= rel_tol * dn at the nearest pixel, ties to even) in at least
+ * min(min_consistent, offsets in range) of them; csrc/lrf_points.inl states the arithmetic, fp32 without contraction.
+ * Kept candidates are written in (frame, row, column) order, the same list on every run: xyz [M,3], rgb8_out [M,3]
+ * (nullable), src [M,2] = (frame, pixel id j * W + i).  count (device int64 [1]) receives the true total M; rows at or beyond
+ * capacity are not written.  Three launches, no atomics, no host synchronisation.  Refused before any launch: null pointers,
+ * V, H, W or stride < 1, V H W >= 2^31, capacity < 0, d_min > d_max (or NaN), n_neigh outside [0, LRF_POINTS_MAX_NEIGH], a zero
+ * or repeated offset, rel_tol < 0 (or NaN), min_consistent < 0, a consistency test with fov360, misaligned pointers.
+ * workspace: lrf_points_workspace_bytes(V, H, W, stride) bytes (0 for shapes lrf_points_fuse refuses), 8-byte aligned. */
+#define LRF_POINTS_MAX_NEIGH 8
+typedef struct LrfPointsFuse {
+  const float* depth; const uint8_t* rgb8 /* nullable */; const float* cam2world;
+  const float* focal; const float* center;
+  int32_t V, H, W, fov360, stride;
+  float d_min, d_max;
+  int32_t n_neigh, neigh[LRF_POINTS_MAX_NEIGH];
+  float rel_tol;
+  int32_t min_consistent;
+} LrfPointsFuse;
+size_t lrf_points_workspace_bytes(int32_t V, int32_t H, int32_t W, int32_t stride);
+int lrf_points_fuse(const LrfPointsFuse* a, int64_t capacity, float* xyz, uint8_t* rgb8_out /* nullable */, int32_t* src,
+                    int64_t* count /* device [1] */, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,6 +12,8 @@ Public surface mirrors the reference's names:
   DeviceFrames                      (dataLoader/localrf_dataset.py, train split: a device-resident frame window)
   novel_views.render_poses / iter_pose_frames / encode_frames / visualize_depth / nearest_frames
                                     (renderer.py:43-77,130-148, test=False: novel camera poses, frames encoded on the device)
+  pointcloud.backproject / fuse_points / scene_point_cloud / write_ply
+                                    (rendered depth fused into a filtered, coloured world-space point cloud; no reference row)
 The arithmetic of TensorVMSplit.forward and of LocalTensorfs.forward (ray generation, field
 blend, exposure) runs in hand-written HIP kernels for gfx950 (csrc/), reached through the C ABI
 of include/lrf.h.
@@ -25,6 +27,7 @@ from . import losses  # noqa: F401
 from . import metrics  # noqa: F401
 from . import diagnostics  # noqa: F401
 from . import novel_views  # noqa: F401
+from . import pointcloud  # noqa: F401
 from .frames import DeviceFrames  # noqa: F401
 
-__all__ = ["TensorVMSplit", "AlphaGridMask", "MLPRender_Fea_late_view", "LocalTensorfs", "rays", "losses", "metrics", "diagnostics", "novel_views", "NativeError", "FusedAdam", "DeviceFrames"]
+__all__ = ["TensorVMSplit", "AlphaGridMask", "MLPRender_Fea_late_view", "LocalTensorfs", "rays", "losses", "metrics", "diagnostics", "novel_views", "pointcloud", "NativeError", "FusedAdam", "DeviceFrames"]

@@ -109,6 +109,16 @@ class LrfFlowComparison(C.Structure):
                 ("F", C.c_int32), ("V", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("idx", C.c_int32 * LRF_EVAL_MAX_VIEWS)]
 
 
+LRF_POINTS_MAX_NEIGH = 8
+
+
+class LrfPointsFuse(C.Structure):
+    _fields_ = [("depth", _f), ("rgb8", C.c_void_p), ("cam2world", _f), ("focal", _f), ("center", _f),
+                ("V", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("fov360", C.c_int32), ("stride", C.c_int32),
+                ("d_min", C.c_float), ("d_max", C.c_float), ("n_neigh", C.c_int32), ("neigh", C.c_int32 * LRF_POINTS_MAX_NEIGH),
+                ("rel_tol", C.c_float), ("min_consistent", C.c_int32)]
+
+
 # every symbol include/lrf.h and include/lrf_debug.h declare: (restype, argtypes)
 SYMBOLS = {
     "lrf_abi_version": (C.c_int, []),
@@ -201,6 +211,9 @@ SYMBOLS = {
     "lrf_encode_frames_workspace_bytes": (C.c_size_t, [C.c_int32]),
     "lrf_encode_frames": (C.c_int, [_f, _f, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_float), C.c_void_p,
                                     C.c_void_p, C.c_void_p, _f, C.c_void_p, C.c_void_p]),
+    "lrf_points_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "lrf_points_fuse": (C.c_int, [C.POINTER(LrfPointsFuse), C.c_int64, _f, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_void_p]),
     "lrf_scene_blend_bwd": (C.c_int, [_f, _f, _f, _f, _f, C.c_int32, C.c_int32, C.c_int32, _f, _f, _f,
                                       C.c_void_p]),
 }

@@ -1125,6 +1125,7 @@ static hipError_t lds_opt_in() {
 #include "lrf_select.inl"
 #include "lrf_evalgeo.inl"
 #include "lrf_encode.inl"
+#include "lrf_points.inl"
 #include "lrf_reg.inl"
 #include "lrf_mask.inl"
 

@@ -1,0 +1,286 @@
+"""Rendered depth fused into a coloured world-space point cloud on the GPU (csrc/lrf_points.inl through lrf_points_fuse).
+
+  backproject(depth, poses, W, H, ...)          every pixel with a finite positive depth -> (xyz [M,3], src [M,2])
+  fuse_points(rgb, depth, poses, focal, ...)    strided, depth-ranged, multi-view-consistent points with colours
+  scene_point_cloud(local_tensorfs, W, H, ...)  novel_views.render_poses, then fuse_points with the scene's intrinsics
+  write_ply(path, xyz, rgb8)                    binary little-endian PLY from one device -> host copy
+
+Conventions (the reference's): a rendered depth is sum w z / |d|, a multiple of the UN-normalised camera direction whose z
+is -1 for a pinhole (tensorBase.py:615, utils/ray_utils.py:14-24); the camera point is direction * depth (utils/utils.py:15-48)
+and the world point R (direction * depth) + t.  The points come out in (frame, row, column) order, the same list on every
+run.  One output convention for the whole module: a point list with its source (frame, pixel id), never a dense image with
+holes.  Every function checks its arguments on the host before its first launch.  CPU tensors raise NativeError: there is no
+torch fallback.  Cited lines are relative to the reference's localTensoRF directory.
+"""
+import ctypes as C
+import math
+
+import numpy as np
+import torch
+
+from . import _native as N
+from ._native import NativeError
+from .scene_ops import _stream
+
+_INT32 = (1 << 31) - 1
+BYTES_PER_RESIDENT_PIXEL = 7                   # scene_point_cloud keeps depth (4 B) and rgb8 (3 B) of every frame
+
+
+def _require_gpu(t, name):
+    if not t.is_cuda:
+        raise NativeError(f"localrf_amd.pointcloud: {name} lives on {t.device}; the point fusion runs only on an AMD GPU (HIP "
+                          "kernels). There is no CPU fallback.")
+
+
+def _check_depth(depth):
+    if not torch.is_tensor(depth):
+        raise TypeError("depth must be a torch tensor")
+    if not depth.is_floating_point():
+        raise ValueError(f"depth must hold floating-point values, got {depth.dtype}")
+    if depth.dim() != 3 or min(depth.shape) < 1:
+        raise ValueError(f"depth must be [V, H, W] with V, H, W > 0, got {tuple(depth.shape)}")
+    V, H, W = (int(s) for s in depth.shape)
+    if V * H * W > _INT32:
+        raise ValueError(f"depth holds {V * H * W} pixels; one call takes V H W < 2^31")
+    return V, H, W
+
+
+def _check_poses(poses, V):
+    if not torch.is_tensor(poses):
+        poses = torch.as_tensor(np.asarray(poses, dtype=np.float32))
+    if poses.dim() != 3 or poses.shape[1] not in (3, 4) or poses.shape[2] != 4:
+        raise ValueError(f"poses must be [V, 3, 4] (or [V, 4, 4]) camera-to-world matrices, got {tuple(poses.shape)}")
+    if not poses.is_floating_point():
+        raise ValueError(f"poses must hold floating-point values, got {poses.dtype}")
+    if poses.shape[0] != V:
+        raise ValueError(f"{poses.shape[0]} poses for {V} depth frames")
+    return poses[:, :3, :]
+
+
+def _check_intrinsics(focal, center, fov360):
+    """-> (focal, center) as given (tensors or numbers), shapes checked; None, None for 360."""
+    if fov360:
+        return None, None
+    if focal is None or center is None:
+        raise ValueError("a pinhole camera needs focal and center (or pass fov360=True)")
+    nf = focal.numel() if torch.is_tensor(focal) else np.size(focal)
+    nc = center.numel() if torch.is_tensor(center) else np.size(center)
+    if nf != 1 or nc != 2:
+        raise ValueError(f"focal must hold 1 value and center 2 (cx, cy), got {nf} and {nc}")
+    return focal, center
+
+
+def _check_filter(stride, depth_range, neighbours, rel_tol, min_consistent, fov360, max_points):
+    if int(stride) != stride or int(stride) < 1:
+        raise ValueError(f"stride must be an integer >= 1, got {stride!r}")
+    if len(depth_range) != 2:
+        raise ValueError(f"depth_range must be (d_min, d_max), got {depth_range!r}")
+    d_min, d_max = float(depth_range[0]), float(depth_range[1])
+    if not d_min <= d_max:
+        raise ValueError(f"depth_range needs d_min <= d_max, got {depth_range!r}")
+    neigh = [int(o) for o in neighbours]
+    if any(int(o) != o for o in neighbours):
+        raise ValueError(f"neighbours must be integer frame offsets, got {neighbours!r}")
+    if len(neigh) > N.LRF_POINTS_MAX_NEIGH:
+        raise ValueError(f"at most {N.LRF_POINTS_MAX_NEIGH} neighbours, got {len(neigh)}")
+    if 0 in neigh:
+        raise ValueError("a neighbours offset must not be 0 (a frame agrees with itself)")
+    if len(set(neigh)) != len(neigh):
+        raise ValueError(f"neighbours holds a repeated offset: {neigh}")
+    if any(abs(o) > _INT32 for o in neigh):
+        raise ValueError(f"neighbours offsets must fit int32, got {neigh}")
+    if neigh and fov360:
+        raise ValueError("the consistency test needs a pinhole camera: there is no reprojection at 360 degrees (train.py:386-387)")
+    rel_tol = float(rel_tol)
+    if not rel_tol >= 0:
+        raise ValueError(f"rel_tol must be >= 0, got {rel_tol}")
+    if int(min_consistent) != min_consistent or int(min_consistent) < 0:
+        raise ValueError(f"min_consistent must be an integer >= 0, got {min_consistent!r}")
+    if max_points is not None and (int(max_points) != max_points or int(max_points) < 0):
+        raise ValueError(f"max_points must be None or an integer >= 0, got {max_points!r}")
+    return int(stride), d_min, d_max, neigh, rel_tol, min(int(min_consistent), _INT32)
+
+
+def _dev_f32(x, n, dev):
+    t = x if torch.is_tensor(x) else torch.tensor(np.asarray(x, np.float32).reshape(n))
+    return t.detach().reshape(n).to(device=dev, dtype=torch.float32).contiguous()
+
+
+def _fuse(depth, rgb8, poses, focal, center, fov360, stride, d_min, d_max, neigh, rel_tol, min_consistent, max_points):
+    """Checked arguments, device tensors -> (xyz, rgb8 or None, src, count).  The one read-back is count."""
+    dev = depth.device
+    V, H, W = (int(s) for s in depth.shape)
+    depth = depth.detach().to(torch.float32).contiguous()
+    poses = poses.detach().to(device=dev, dtype=torch.float32).contiguous()
+    f = c = None
+    if not fov360:
+        f, c = _dev_f32(focal, 1, dev), _dev_f32(center, 2, dev)
+    lib = N.lib()
+    nbytes = lib.lrf_points_workspace_bytes(V, H, W, stride)
+    if nbytes == 0:
+        raise NativeError(f"lrf_points_fuse: refused {V} x {H} x {W} at stride {stride}")
+    n_cand = V * (-(-H // stride)) * (-(-W // stride))
+    cap = n_cand if max_points is None else min(int(max_points), n_cand)
+    rows = max(cap, 1)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    xyz = torch.empty(rows, 3, dtype=torch.float32, device=dev)
+    src = torch.empty(rows, 2, dtype=torch.int32, device=dev)
+    out8 = None if rgb8 is None else torch.empty(rows, 3, dtype=torch.uint8, device=dev)
+    count = torch.empty(1, dtype=torch.int64, device=dev)
+    a = N.LrfPointsFuse()
+    a.depth, a.rgb8, a.cam2world = depth.data_ptr(), None if rgb8 is None else rgb8.data_ptr(), poses.data_ptr()
+    a.focal, a.center = (None, None) if fov360 else (f.data_ptr(), c.data_ptr())
+    a.V, a.H, a.W, a.fov360, a.stride = V, H, W, int(bool(fov360)), stride
+    a.d_min, a.d_max = d_min, d_max
+    a.n_neigh = len(neigh)
+    for k, o in enumerate(neigh):
+        a.neigh[k] = o
+    a.rel_tol, a.min_consistent = rel_tol, min_consistent
+    with torch.cuda.device(dev):
+        N.check(lib.lrf_points_fuse(C.byref(a), cap, xyz.data_ptr(), None if out8 is None else out8.data_ptr(), src.data_ptr(),
+                                    count.data_ptr(), ws.data_ptr(), _stream(dev)), "lrf_points_fuse")
+    m = int(count.item())                                          # the ONE read-back (it also orders ws's release)
+    if m > cap:
+        raise ValueError(f"the fused cloud holds {m} points; max_points={max_points} does not fit them")
+    return xyz[:m], None if out8 is None else out8[:m], src[:m], m
+
+
+def backproject(depth, poses, W, H, focal=None, center=None, fov360=False):
+    """depth [V,H,W] (device), poses [V,3,4] camera-to-world -> (xyz [M,3] fp32, src [M,2] int32 = (frame, pixel id j W + i)):
+    the world point of every pixel with a finite positive depth, no other filter, in (frame, row, column) order.  focal (one
+    value) and center (cx, cy) may be tensors or numbers; fov360=True takes the equirectangular directions instead."""
+    V, Hd, Wd = _check_depth(depth)
+    if (int(H), int(W)) != (Hd, Wd):
+        raise ValueError(f"depth is {Hd} x {Wd} (H x W) but H, W = {H}, {W}")
+    poses = _check_poses(poses, V)
+    focal, center = _check_intrinsics(focal, center, fov360)
+    _require_gpu(depth, "depth")
+    xyz, _, src, _ = _fuse(depth, None, poses, focal, center, bool(fov360), 1, 0.0, math.inf, [], 0.0, 0, None)
+    return xyz, src
+
+
+def fuse_points(rgb, depth, poses, focal, center, *, fov360=False, stride=1, depth_range=(0.0, math.inf), neighbours=(),
+                rel_tol=0.02, min_consistent=1, max_points=None):
+    """V rendered frames -> ONE filtered, ordered, coloured point list, on the device.
+    rgb [V,H,W,3]: float (encoded as novel_views.encode_frames does: clamp(rint(255 x), 0, 255), ties to even, NaN -> 0) or
+    uint8, or None for no colours; depth [V,H,W]; poses [V,3,4] camera-to-world; focal / center as backproject takes them.
+    Candidates are the pixels (i, j) with i % stride == 0 and j % stride == 0.  A candidate is kept when its depth is finite,
+    positive and inside depth_range and, with neighbours (signed frame offsets, at most 8, pinhole only), when its world
+    point reprojected into the frames v + o that exist agrees with the depth rendered there -- |z - dn| <= rel_tol * dn at
+    the nearest pixel -- in at least min(min_consistent, offsets that stayed in range) of them.  An offset that leaves the
+    trajectory counts neither for nor against, so the end frames are judged by the neighbours they have.
+    The defaults rel_tol=0.02 and min_consistent=1 are conveniences, not measured optima: choose them for the scene.
+    Returns a dict: xyz [M,3] fp32, rgb8 [M,3] uint8 (None without rgb), src [M,2] int32 (frame, pixel id j W + i) -- device
+    tensors in (frame, row, column) order, views of buffers sized for max_points rows (None: for every candidate) -- and
+    count = M, a Python int: the one read-back.  A result that does not fit max_points raises ValueError naming the true count."""
+    V, H, W = _check_depth(depth)
+    if rgb is not None:
+        if not torch.is_tensor(rgb):
+            raise TypeError("rgb must be a torch tensor or None")
+        if not (rgb.is_floating_point() or rgb.dtype is torch.uint8):
+            raise ValueError(f"rgb must hold floating-point or uint8 values, got {rgb.dtype}")
+        if tuple(rgb.shape) != (V, H, W, 3):
+            raise ValueError(f"rgb must be {(V, H, W, 3)} to go with depth {tuple(depth.shape)}, got {tuple(rgb.shape)}")
+        if rgb.device != depth.device:
+            raise ValueError("rgb and depth must live on the same device")
+    poses = _check_poses(poses, V)
+    focal, center = _check_intrinsics(focal, center, fov360)
+    stride, d_min, d_max, neigh, rel_tol, min_consistent = _check_filter(stride, depth_range, neighbours, rel_tol, min_consistent,
+                                                                         fov360, max_points)
+    _require_gpu(depth, "depth")
+    rgb8 = None
+    if rgb is not None:
+        if rgb.dtype is torch.uint8:
+            rgb8 = rgb.contiguous()
+        else:
+            from .novel_views import _aligned, _encode, _lut
+            d32 = _aligned(depth.detach())
+            rgb8 = _encode(_aligned(rgb.detach()), d32, (0, 5), _lut(None, depth.device), False, False)[0]
+    xyz, out8, src, m = _fuse(depth, rgb8, poses, focal, center, bool(fov360), stride, d_min, d_max, neigh, rel_tol,
+                              min_consistent, max_points)
+    return {"xyz": xyz, "rgb8": out8, "src": src, "count": m}
+
+
+_FUSE_KEYS = ("stride", "depth_range", "neighbours", "rel_tol", "min_consistent", "max_points")
+_RENDER_KEYS = ("test_frames", "frame_indices", "floater_thresh", "chunk", "frames_per_call")
+
+
+def scene_point_cloud(local_tensorfs, W, H, poses=None, max_bytes=4 << 30, **options):
+    """A scene's point cloud: its frames rendered by novel_views.render_poses, then fuse_points with the scene's focal(W),
+    center(W, H) and fov.  poses=None renders the scene's own get_cam2world(), each frame through itself (frame_indices =
+    0..F-1); otherwise poses [N,3,4] as render_poses takes them.  options: fuse_points' stride, depth_range, neighbours,
+    rel_tol, min_consistent, max_points and render_poses' test_frames, frame_indices, floater_thresh, chunk, frames_per_call.
+    Every frame's depth and rgb8 stay resident, 7 bytes per pixel (the float colours are dropped once encoded); more than
+    max_bytes of them raises ValueError before anything is rendered.  A sliding window over frames is not provided."""
+    from . import novel_views
+    unknown = sorted(set(options) - set(_FUSE_KEYS) - set(_RENDER_KEYS))
+    if unknown:
+        raise TypeError(f"scene_point_cloud: unknown options {unknown}")
+    W, H = int(W), int(H)
+    if W <= 0 or H <= 0:
+        raise ValueError(f"need W, H > 0, got {W} x {H}")
+    lt = local_tensorfs
+    fov360 = lt.fov == 360
+    fuse = {k: options[k] for k in _FUSE_KEYS if k in options}
+    render = {k: options[k] for k in _RENDER_KEYS if k in options}
+    _check_filter(fuse.get("stride", 1), fuse.get("depth_range", (0.0, math.inf)), fuse.get("neighbours", ()),
+                  fuse.get("rel_tol", 0.02), fuse.get("min_consistent", 1), fov360, fuse.get("max_points"))
+    if poses is None:
+        n = len(lt.r_c2w)
+        render.setdefault("frame_indices", list(range(n)))
+    else:
+        n = int(novel_views._poses(poses).shape[0])
+    need = BYTES_PER_RESIDENT_PIXEL * n * H * W
+    if need > int(max_bytes):
+        raise ValueError(f"scene_point_cloud: {n} frames of {H} x {W} keep {need} bytes of depth and rgb8 resident; "
+                         f"max_bytes is {int(max_bytes)}")
+    if n < 1:
+        raise ValueError("scene_point_cloud: no frame to render")
+    if n * H * W > _INT32:
+        raise ValueError(f"scene_point_cloud: {n * H * W} pixels; one fusion takes V H W < 2^31")
+    dev = lt.blending_weights.device
+    if dev.type != "cuda":
+        raise NativeError(f"localrf_amd.pointcloud: the scene lives on {dev}; rendering runs only on an AMD GPU (HIP kernels). "
+                          "There is no CPU fallback.")
+    if poses is None:
+        with torch.no_grad():
+            poses = lt.get_cam2world().detach()
+    out = novel_views.render_poses(lt, poses, W, H, **render)
+    depth, rgb8 = out["depth"], out["rgb8"]
+    poses = novel_views._poses(poses)
+    del out                                                         # the float colours go back to the allocator
+    return fuse_points(rgb8, depth, poses, None if fov360 else lt.focal(W), None if fov360 else lt.center(W, H),
+                       fov360=fov360, **fuse)
+
+
+def ply_header(n, colours):
+    lines = ["ply", "format binary_little_endian 1.0", f"element vertex {int(n)}",
+             "property float x", "property float y", "property float z"]
+    if colours:
+        lines += ["property uchar red", "property uchar green", "property uchar blue"]
+    return ("\n".join(lines + ["end_header"]) + "\n").encode("ascii")
+
+
+def write_ply(path, xyz, rgb8=None):
+    """Binary little-endian PLY (x y z float, red green blue uchar when rgb8 is given) of xyz [M,3] and rgb8 [M,3] uint8:
+    tensors (one device -> host copy each) or numpy arrays.  Returns the number of vertices written."""
+    def host(t, dtype, name):
+        a = t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+        if a.ndim != 2 or a.shape[1] != 3:
+            raise ValueError(f"{name} must be [M, 3], got {a.shape}")
+        if dtype == np.uint8 and a.dtype != np.uint8:
+            raise ValueError(f"rgb8 must be uint8, got {a.dtype}")
+        return np.ascontiguousarray(a, dtype=dtype)
+    pts = host(xyz, np.float32, "xyz")
+    cols = None if rgb8 is None else host(rgb8, np.uint8, "rgb8")
+    if cols is not None and cols.shape[0] != pts.shape[0]:
+        raise ValueError(f"{pts.shape[0]} points but {cols.shape[0]} colours")
+    if cols is None:
+        rec = pts.astype("<f4")
+    else:
+        rec = np.empty(pts.shape[0], dtype=np.dtype([("p", "<f4", 3), ("c", "u1", 3)]))
+        rec["p"], rec["c"] = pts, cols
+    with open(path, "wb") as fh:
+        fh.write(ply_header(pts.shape[0], cols is not None))
+        fh.write(rec.tobytes())
+    return int(pts.shape[0])
