@@ -20,41 +20,29 @@ import torch
 
 from . import _native as N
 from ._native import NativeError
-from .metrics import _device_images, _launch as _metrics_launch, _check_shape
-from .scene_ops import _stream
+from .metrics import check_shapes, image_metrics
 
 MAX_VIEWS = N.LRF_EVAL_MAX_VIEWS          # views per lrf_flow_comparison call; more are split into several calls
 _MAX_ROWS = 65535
 
 
-def _device(t, name, dtype=torch.float32):
-    if not torch.is_tensor(t):
-        raise TypeError(f"{name} must be a torch tensor")
-    if not t.is_cuda:
-        raise NativeError(f"localrf_amd.diagnostics: {name} lives on {t.device}; the diagnostics run only on an AMD GPU "
-                          "(HIP kernels). There is no CPU fallback.")
-    if t.dtype is not dtype:
-        t = t.to(dtype)
-    return t.contiguous()
+def _dev(t, name, dtype=torch.float32):
+    N.require_gpu(t, name, "the diagnostics")
+    return N.conform(t, dtype)
 
 
 def _select(rows, lengths, mode, q):
     """rows: contiguous fp32 [B, stride] on the device; lengths: one shared length or B of them.  Returns fp32 [B]."""
-    lib = N.lib()
     B, stride = rows.shape
     dev = rows.device
     out = torch.empty(B, dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        for b0 in range(0, B, _MAX_ROWS if len(lengths) == 1 else N.LRF_SELECT_MAX_ROWS):
-            b1 = min(B, b0 + (_MAX_ROWS if len(lengths) == 1 else N.LRF_SELECT_MAX_ROWS))
-            ln = lengths if len(lengths) == 1 else lengths[b0:b1]
-            nbytes = lib.lrf_select_workspace_bytes(b1 - b0, max(ln))
-            if nbytes == 0:
-                raise NativeError(f"lrf_select: refused shape B={b1 - b0} n={max(ln)}")
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-            arr = (C.c_int64 * len(ln))(*ln)
-            N.check(lib.lrf_select(rows[b0].data_ptr(), stride, arr, len(ln), b1 - b0, mode, float(q), out[b0:b1].data_ptr(),
-                                   ws.data_ptr(), _stream(dev)), "lrf_select")
+    for b0 in range(0, B, _MAX_ROWS if len(lengths) == 1 else N.LRF_SELECT_MAX_ROWS):
+        b1 = min(B, b0 + (_MAX_ROWS if len(lengths) == 1 else N.LRF_SELECT_MAX_ROWS))
+        ln = lengths if len(lengths) == 1 else lengths[b0:b1]
+        ws = N.workspace("lrf_select", dev, b1 - b0, max(ln))
+        arr = (C.c_int64 * len(ln))(*ln)
+        N.launch("lrf_select", dev, rows[b0].data_ptr(), stride, arr, len(ln), b1 - b0, mode, float(q), out[b0:b1].data_ptr(),
+                 ws.data_ptr(), guard=True)
     return out
 
 
@@ -62,7 +50,7 @@ def _order_stat(x, mode, q):
     if isinstance(x, (list, tuple)):                        # ragged rows: 1-D device tensors of their own lengths
         if len(x) == 0:
             raise ValueError("no rows")
-        rows = [_device(t, "x").reshape(-1) for t in x]
+        rows = [_dev(t, "x").reshape(-1) for t in x]
         lengths = [int(t.numel()) for t in rows]
         if min(lengths) < 1:
             raise NativeError("lrf_select: a row is empty (n = 0)")
@@ -72,7 +60,7 @@ def _order_stat(x, mode, q):
         for i, t in enumerate(rows):
             packed[i, :lengths[i]].copy_(t)
         return _select(packed, lengths, mode, q)
-    x = _device(x, "x")
+    x = _dev(x, "x")
     if x.dim() == 0:
         x = x.reshape(1)
     n = int(x.shape[-1])
@@ -105,7 +93,7 @@ def median(x):
 
 
 def _views(t, V, shape, name, dtype=torch.float32):
-    t = _device(t, name, dtype)
+    t = _dev(t, name, dtype)
     if t.numel() != V * math.prod(shape):
         raise ValueError(f"{name} must hold {V} x {list(shape)} values, got {tuple(t.shape)}")
     return t.reshape(V, *shape)
@@ -114,7 +102,7 @@ def _views(t, V, shape, name, dtype=torch.float32):
 def _flow_batch(depth, dirs, ij, cam2world, idx, focal, center, fwd_flow, fwd_mask, bwd_flow, bwd_mask, W, H, raw):
     """Views stacked on a leading axis: depth [V,HW], dirs [V,HW,3], ij [V,HW,2], flows [V,H,W,2], masks [V,H,W]; idx: V ints."""
     V, HW = len(idx), W * H
-    c2w = _device(cam2world, "cam2world")
+    c2w = _dev(cam2world, "cam2world")
     if c2w.dim() != 3 or tuple(c2w.shape[1:]) != (3, 4):
         raise ValueError(f"cam2world must be [F,3,4], got {tuple(c2w.shape)}")
     F = int(c2w.shape[0])
@@ -126,31 +114,25 @@ def _flow_batch(depth, dirs, ij, cam2world, idx, focal, center, fwd_flow, fwd_ma
     ij = _views(ij, V, (HW, 2), "ij", torch.int64)
     ins = [_views(t, V, s, n) for t, s, n in ((fwd_flow, (HW, 2), "fwd_flow"), (fwd_mask, (HW,), "fwd_mask"),
                                               (bwd_flow, (HW, 2), "bwd_flow"), (bwd_mask, (HW,), "bwd_mask"))]
-    focal = _device(torch.as_tensor(focal, device=depth.device), "focal").reshape(-1)
-    center = _device(torch.as_tensor(center, device=depth.device), "center").reshape(-1)
+    focal = _dev(torch.as_tensor(focal, device=depth.device), "focal").reshape(-1)
+    center = _dev(torch.as_tensor(center, device=depth.device), "center").reshape(-1)
     dev = depth.device
-    lib = N.lib()
     out = torch.empty(2, V, 3 * H, 2 * W, dtype=torch.float32, device=dev)
     rawt = torch.empty_like(out) if raw else None
     quant = torch.empty(V, 4, dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        for v0 in range(0, V, MAX_VIEWS):
-            v1 = min(V, v0 + MAX_VIEWS)
-            a = N.LrfFlowComparison()
-            a.cam2world, a.depth, a.dirs, a.ij = c2w.data_ptr(), depth[v0].data_ptr(), dirs[v0].data_ptr(), ij[v0].data_ptr()
-            a.fwd_flow, a.fwd_mask, a.bwd_flow, a.bwd_mask = [t[v0].data_ptr() for t in ins]
-            a.focal, a.center = focal.data_ptr(), center.data_ptr()
-            a.F, a.V, a.H, a.W = F, v1 - v0, H, W
-            for k, i in enumerate(idx[v0:v1]):
-                a.idx[k] = i
-            nbytes = lib.lrf_flow_comparison_workspace_bytes(v1 - v0, H, W)
-            if nbytes == 0:
-                raise NativeError(f"lrf_flow_comparison: refused shape V={v1 - v0} H={H} W={W}")
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-            N.check(lib.lrf_flow_comparison(C.byref(a), out[0, v0].data_ptr(), out[1, v0].data_ptr(),
-                                            None if rawt is None else rawt[0, v0].data_ptr(),
-                                            None if rawt is None else rawt[1, v0].data_ptr(),
-                                            quant[v0].data_ptr(), ws.data_ptr(), _stream(dev)), "lrf_flow_comparison")
+    for v0 in range(0, V, MAX_VIEWS):
+        v1 = min(V, v0 + MAX_VIEWS)
+        a = N.LrfFlowComparison()
+        a.cam2world, a.depth, a.dirs, a.ij = c2w.data_ptr(), depth[v0].data_ptr(), dirs[v0].data_ptr(), ij[v0].data_ptr()
+        a.fwd_flow, a.fwd_mask, a.bwd_flow, a.bwd_mask = [t[v0].data_ptr() for t in ins]
+        a.focal, a.center = focal.data_ptr(), center.data_ptr()
+        a.F, a.V, a.H, a.W = F, v1 - v0, H, W
+        for k, i in enumerate(idx[v0:v1]):
+            a.idx[k] = i
+        ws = N.workspace("lrf_flow_comparison", dev, v1 - v0, H, W)
+        N.launch("lrf_flow_comparison", dev, C.byref(a), out[0, v0].data_ptr(), out[1, v0].data_ptr(),
+                 None if rawt is None else rawt[0, v0].data_ptr(), None if rawt is None else rawt[1, v0].data_ptr(),
+                 quant[v0].data_ptr(), ws.data_ptr(), guard=True)
     return out, rawt, quant
 
 
@@ -189,22 +171,17 @@ def depth_comparison(depth_map, invdepth, W, H, return_stats=False):
     invdepth), [3H, W] fp32 on the device.  depth_map [HW] (or [V, HW]), invdepth [H, W] (or [V, H, W]), already at W x H.
     return_stats=True also returns (median x, median y, mad x, mad y) [4] ([V, 4])."""
     W, H = _frame(W, H)
-    d = _device(depth_map, "depth_map")
+    d = _dev(depth_map, "depth_map")
     single = d.numel() == W * H
     V = 1 if single else d.numel() // (W * H)
     d = _views(d, V, (W * H,), "depth_map")
     inv = _views(invdepth, V, (W * H,), "invdepth")
     dev = d.device
-    lib = N.lib()
-    nbytes = lib.lrf_depth_comparison_workspace_bytes(V, H, W)
-    if nbytes == 0:
-        raise NativeError(f"lrf_depth_comparison: refused shape V={V} H={H} W={W}")
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws = N.workspace("lrf_depth_comparison", dev, V, H, W)
     out = torch.empty(V, 3 * H, W, dtype=torch.float32, device=dev)
     stats = torch.empty(V, 4, dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        N.check(lib.lrf_depth_comparison(d.data_ptr(), inv.data_ptr(), V, H, W, out.data_ptr(), stats.data_ptr(), ws.data_ptr(),
-                                         _stream(dev)), "lrf_depth_comparison")
+    N.launch("lrf_depth_comparison", dev, d.data_ptr(), inv.data_ptr(), V, H, W, out.data_ptr(), stats.data_ptr(), ws.data_ptr(),
+             guard=True)
     if single:
         out, stats = out[0], stats[0]
     return (out, stats) if return_stats else out
@@ -235,8 +212,8 @@ def test_view_evaluation(local_tensorfs, view_ids, W, H, gt_rgbs=None, fwd_flow=
     if gt_rgbs is not None:
         if tuple(gt_rgbs.shape) != (n, H, W, 3):
             raise ValueError(f"gt_rgbs must be [{n},{H},{W},3], got {tuple(gt_rgbs.shape)}")
-        fs = _check_shape(gt_rgbs.shape[1:], (H, W, 3), filter_size)
-        gt = _device_images(gt_rgbs, "gt_rgbs")
+        check_shapes(gt_rgbs.shape[1:], (H, W, 3), filter_size)
+        gt = _dev(gt_rgbs, "gt_rgbs")
     if do_flow:
         flow_in = [_views(t, n, s, nm) for t, s, nm in zip(flow_in, ((H * W, 2), (H * W,), (H * W, 2), (H * W,)),
                                                             ("fwd_flow", "fwd_mask", "bwd_flow", "bwd_mask"))]
@@ -259,8 +236,7 @@ def test_view_evaluation(local_tensorfs, view_ids, W, H, gt_rgbs=None, fwd_flow=
             rgb, depth, d, ij = local_tensorfs(ray_ids, [v], W, H, is_train=False, cam2world=None, test_id=True, chunk=chunk,
                                                floater_thresh=floater_thresh)
             if scores is not None:
-                rgb = _device_images(rgb.to(dev), "rendered rgb").reshape(1, H, W, 3)
-                mse, ssim, _ = _metrics_launch(gt[i:i + 1], rgb, max_val, fs, filter_sigma, k1, k2, False)
+                mse, ssim = image_metrics(rgb.to(dev).reshape(1, H, W, 3), gt[i:i + 1], max_val, filter_size, filter_sigma, k1, k2)
                 scores[0, i:i + 1].copy_(mse)
                 scores[1, i:i + 1].copy_(ssim)
             if need_geo:
@@ -279,5 +255,5 @@ def test_view_evaluation(local_tensorfs, view_ids, W, H, gt_rgbs=None, fwd_flow=
         host = scores.cpu()
         res["metrics"] = {fb: {"mse": float(host[0, i]), "ssim": float(host[1, i])} for i, fb in enumerate(fbases)}
     else:
-        torch.cuda.current_stream(dev).synchronize()
+        N.torch_stream(dev).synchronize()
     return res

@@ -20,6 +20,8 @@ from . import _native as N
 from .field_layout import FieldLayout, point_at
 from .grad_bucket import GradBucket
 
+_FEATURE = "the render path"
+
 EARLY_TERM_T_FAST = 1e-9                # TensorVMSplit.early_term_T opt-in value (north_star: "early termination")
 MAT_MODE = [[0, 1], [0, 2], [1, 2]]     # tensorBase.py:274
 VEC_MODE = [2, 1, 0]                    # tensorBase.py:275
@@ -147,10 +149,8 @@ class _DensityL1Fn(torch.autograd.Function):
         dev = tensors[0].device
         ws = torch.empty(lib.lrf_density_l1_workspace(hw, ll), dtype=torch.uint8, device=dev)
         out = torch.empty(1, dtype=torch.float32, device=dev)
-        st = torch.cuda.current_stream(dev).cuda_stream
-        N.check(lib.lrf_density_l1_fwd(pp, lp, hw, ll, float(field.density_shift),
-                                       1 if field.fea2denseAct == "relu" else 0, ws.data_ptr(), N.ptr(out), st),
-                "lrf_density_l1_fwd")
+        N.launch("lrf_density_l1_fwd", dev, pp, lp, hw, ll, float(field.density_shift),
+                 1 if field.fea2denseAct == "relu" else 0, ws.data_ptr(), N.ptr(out))
         return out[0], ws
 
     @staticmethod
@@ -160,9 +160,8 @@ class _DensityL1Fn(torch.autograd.Function):
         gp = (C.c_void_p * 3)(*[g.data_ptr() for g in grads[:3]])
         gl = (C.c_void_p * 3)(*[g.data_ptr() for g in grads[3:]])
         g = g_out.detach().reshape(1).contiguous().float()
-        st = torch.cuda.current_stream(g.device).cuda_stream
-        fn = N.lib().lrf_density_l1_bwd_acc if accumulate else N.lib().lrf_density_l1_bwd
-        N.check(fn(pp, lp, hw, ll, ws.data_ptr(), N.ptr(g), gp, gl, st), "lrf_density_l1_bwd")
+        N.launch("lrf_density_l1_bwd_acc" if accumulate else "lrf_density_l1_bwd", g.device, pp, lp, hw, ll, ws.data_ptr(), N.ptr(g),
+                 gp, gl)
 
     @staticmethod
     def forward(ctx, field, *tensors):
@@ -202,8 +201,7 @@ class _TVLossFn(torch.autograd.Function):
         dev = tensors[0].device
         ws = torch.empty(lib.lrf_tv_workspace(tab, len(tensors)), dtype=torch.uint8, device=dev)
         out = torch.empty(1, dtype=torch.float32, device=dev)
-        st = torch.cuda.current_stream(dev).cuda_stream
-        N.check(lib.lrf_tv_loss_fwd(tab, len(tensors), weight, ws.data_ptr(), N.ptr(out), st), "lrf_tv_loss_fwd")
+        N.launch("lrf_tv_loss_fwd", dev, tab, len(tensors), weight, ws.data_ptr(), N.ptr(out))
         ctx.weight = weight
         ctx.save_for_backward(*tensors)
         return out[0]
@@ -214,8 +212,7 @@ class _TVLossFn(torch.autograd.Function):
         grads = [torch.empty_like(t) for t in tensors]
         tab = _TVLossFn._table(tensors, grads)
         g = g_out.detach().reshape(1).contiguous().float()
-        st = torch.cuda.current_stream(g.device).cuda_stream
-        N.check(N.lib().lrf_tv_loss_bwd(tab, len(tensors), ctx.weight, N.ptr(g), st), "lrf_tv_loss_bwd")
+        N.launch("lrf_tv_loss_bwd", g.device, tab, len(tensors), ctx.weight, N.ptr(g))
         return (None, *grads)
 
 
@@ -394,12 +391,6 @@ class TensorVMSplit(torch.nn.Module):
             out += [lin._parameters["weight"], lin._parameters["bias"]]
         return out
 
-    def _require_gpu(self, t):
-        if not t.is_cuda:
-            raise N.NativeError(
-                "localrf_amd: the render path runs only on an AMD GPU (HIP kernels); got a "
-                f"{t.device} tensor. There is no CPU fallback.")
-
     def _c_params(self):
         ps = self._param_list()                              # only data_ptr() is taken: no detach()
         for p in ps:
@@ -444,14 +435,13 @@ class TensorVMSplit(torch.nn.Module):
     def _open(self, rays, z):
         """The shared opening of the three native calls: the cache packed from the current parameters, then contiguous fp32
         rays [R,6] and z [S] with R, S and the device."""
-        self._require_gpu(rays)
+        N.require_gpu(rays, "rays", _FEATURE)
         self.layout.ensure(self)
         rays = rays.detach().contiguous().float()
         z = z.detach().contiguous().float().view(-1)
         return rays, z, rays.shape[0], z.shape[0], rays.device
 
     def _native_forward(self, rays, z, flags, floater, want_weights=False, out=None):
-        lib = N.lib()
         rays, z, R, S, dev = self._open(rays, z)
         if out is not None:                 # caller-owned outputs (LocalTensorfs blends them in place)
             rgb, depth = out
@@ -467,10 +457,8 @@ class TensorVMSplit(torch.nn.Module):
             return (rgb, depth, w_out, acc) if want_weights else (rgb, depth)
         ws = self.layout.workspace(R, S, dev)
         f = self.layout.c_field(self)
-        st = torch.cuda.current_stream(dev).cuda_stream
-        N.check(lib.lrf_render_fwd(C.byref(f), N.ptr(rays), N.ptr(z), R, S, flags, float(floater),
-                                   N.ptr(rgb), N.ptr(depth), N.ptr(w_out), N.ptr(acc),
-                                   ws.data_ptr(), st), "lrf_render_fwd")
+        N.launch("lrf_render_fwd", dev, C.byref(f), N.ptr(rays), N.ptr(z), R, S, flags, float(floater), N.ptr(rgb),
+                 N.ptr(depth), N.ptr(w_out), N.ptr(acc), ws.data_ptr())
         return (rgb, depth, w_out, acc) if want_weights else (rgb, depth)
 
     def _param_versions(self):
@@ -488,9 +476,8 @@ class TensorVMSplit(torch.nn.Module):
         ws = torch.empty(lib.lrf_workspace_bytes_bwd_cfg(R, S, grid, int(self.fea_pe), int(self.view_pe), int(self.featureC), flags),
                          dtype=torch.uint8, device=dev)
         f = self.layout.c_field(self)
-        st = torch.cuda.current_stream(dev).cuda_stream
-        N.check(lib.lrf_render_fwd_train(C.byref(f), N.ptr(rays), N.ptr(z), R, S, flags, N.ptr(rgb), N.ptr(depth),
-                                         ws.data_ptr(), st), "lrf_render_fwd_train")
+        N.launch("lrf_render_fwd_train", dev, C.byref(f), N.ptr(rays), N.ptr(z), R, S, flags, N.ptr(rgb), N.ptr(depth),
+                 ws.data_ptr())
         return rgb, depth, ws, self._param_versions()
 
     def _new_grad_bucket(self, keep, R, dev, plane_events=False, events=False):
@@ -525,12 +512,10 @@ class TensorVMSplit(torch.nn.Module):
         if plane_events:
             flags = flags | N.LRF_FLAG_PLANE_EVENTS
         f = self.layout.c_field(self)
-        st = torch.cuda.current_stream(dev).cuda_stream
         g_rgb_c = g_rgb.contiguous().float()         # named: must outlive the launch below
         g_depth_c = g_depth.contiguous().float()
-        N.check(lib.lrf_render_bwd(C.byref(f), C.byref(cp), N.ptr(rays), N.ptr(z), R, S, flags,
-                                   N.ptr(g_rgb_c), N.ptr(g_depth_c),
-                                   C.byref(cg), N.ptr(g_rays), ws.data_ptr(), st), "lrf_render_bwd")
+        N.launch("lrf_render_bwd", dev, C.byref(f), C.byref(cp), N.ptr(rays), N.ptr(z), R, S, flags, N.ptr(g_rgb_c),
+                 N.ptr(g_depth_c), C.byref(cg), N.ptr(g_rays), ws.data_ptr())
         return g_rays, grads
 
     # The gradient buffer of the last backward (localrf_amd.grad_bucket.GradBucket, which documents each of these)
@@ -553,7 +538,7 @@ class TensorVMSplit(torch.nn.Module):
 
     def _wait_bwd_bucket(self, which, stream):
         """Make `stream` wait until bucket `which` (grad_chunks numbering) of the last lrf_render_bwd on this device is final."""
-        N.check(N.lib().lrf_render_bwd_wait(int(which), stream.cuda_stream), "lrf_render_bwd_wait")
+        N.call("lrf_render_bwd_wait", int(which), stream.cuda_stream)
 
     # ------------------------------------------------------------------ sampling
     def z_schedule(self, is_train, N_samples, device):
@@ -578,8 +563,7 @@ class TensorVMSplit(torch.nn.Module):
             elif is_train:                      # the reference's two rand_like draws, in its order
                 u1 = torch.rand(1, h, dtype=torch.float32, device=dev)
                 u2 = torch.rand(1, h, dtype=torch.float32, device=dev)
-            N.check(N.lib().lrf_z_schedule(h, N.ptr(u1) if is_train else None, N.ptr(u2) if is_train else None, N.ptr(z),
-                                           torch.cuda.current_stream(dev).cuda_stream), "lrf_z_schedule")
+            N.launch("lrf_z_schedule", dev, h, N.ptr(u1) if is_train else None, N.ptr(u2) if is_train else None, N.ptr(z))
             if not is_train:
                 self._z_cache[(h, str(device))] = z
             return z
@@ -600,21 +584,19 @@ class TensorVMSplit(torch.nn.Module):
         """tensorBase.py:419-443 with its signature and return values: (rays_pts [R,S,3] contracted sample positions,
         interpx [1,S] sample distances, ~mask_outbbox [R,S] all True).  forward() does this per sample inside k_march /
         k_shade3; the method is here for callers of the reference's API."""
-        self._require_gpu(rays_o)
+        N.require_gpu(rays_o, "rays_o", _FEATURE)
         dev = rays_o.device
         z = self.z_schedule(is_train, N_samples, dev).detach().contiguous().float().view(-1)
         ro, rd = rays_o.detach().contiguous().float(), rays_d.detach().contiguous().float()
         R, S = ro.shape[0], z.shape[0]
         pts = torch.empty(R, S, 3, dtype=torch.float32, device=dev)
-        N.check(N.lib().lrf_sample_ray_contracted(N.ptr(ro), N.ptr(rd), N.ptr(z), R, S, N.ptr(pts),
-                                                  torch.cuda.current_stream(dev).cuda_stream), "lrf_sample_ray_contracted")
+        N.launch("lrf_sample_ray_contracted", dev, N.ptr(ro), N.ptr(rd), N.ptr(z), R, S, N.ptr(pts))
         return pts, z[None], torch.ones(R, S, dtype=torch.bool, device=dev)
 
     def sample_ray(self, rays_o, rays_d, is_train=True, N_samples=-1, jitter=None):
         """AABB march (tensorBase.py:396-417), via lrf_sample_ray_aabb.  `jitter` [R] (extension)
         replaces the per-ray torch.rand draw of train mode (:408-409) so a recorded draw can be replayed."""
-        self._require_gpu(rays_o)
-        lib = N.lib()
+        N.require_gpu(rays_o, "rays_o", _FEATURE)
         n = N_samples if N_samples > 0 else self.nSamples
         rays = torch.cat([rays_o, rays_d], -1).contiguous().float()
         R, dev = rays.shape[0], rays.device
@@ -626,36 +608,30 @@ class TensorVMSplit(torch.nn.Module):
         t = torch.empty(R, n, device=dev)
         inside = torch.empty(R, n, dtype=torch.uint8, device=dev)
         aabb = (C.c_float * 6)(*self.layout.refresh_host(self))
-        st = torch.cuda.current_stream(dev).cuda_stream
-        N.check(lib.lrf_sample_ray_aabb(N.ptr(rays), aabb, float(self.stepSize), float(self.near_far[0]),
-                                        float(self.near_far[1]), N.ptr(jit), R, n, N.ptr(pts), N.ptr(t),
-                                        inside.data_ptr(), st), "lrf_sample_ray_aabb")
+        N.launch("lrf_sample_ray_aabb", dev, N.ptr(rays), aabb, float(self.stepSize), float(self.near_far[0]),
+                 float(self.near_far[1]), N.ptr(jit), R, n, N.ptr(pts), N.ptr(t), inside.data_ptr())
         return pts, t, inside.bool()
 
     # ------------------------------------------------------------------ features
     def compute_densityfeature(self, xyz_sampled):
         """tensoRF.py:112-151 on normalised coordinates [P,3] (no autograd; the training
         gradient flows through forward())."""
-        self._require_gpu(xyz_sampled)
+        N.require_gpu(xyz_sampled, "xyz_sampled", _FEATURE)
         self._ensure_cache()
         u = xyz_sampled.detach().reshape(-1, 3).contiguous().float()
         out = torch.empty(u.shape[0], device=u.device)
         f = self._c_field()
-        st = torch.cuda.current_stream(u.device).cuda_stream
-        N.check(N.lib().lrf_density_feature(C.byref(f), N.ptr(u), u.shape[0], N.ptr(out), st),
-                "lrf_density_feature")
+        N.launch("lrf_density_feature", u.device, C.byref(f), N.ptr(u), u.shape[0], N.ptr(out))
         return out
 
     def compute_appfeature(self, xyz_sampled):
         """tensoRF.py:153-196 on normalised coordinates [P,3] -> [P,27]."""
-        self._require_gpu(xyz_sampled)
+        N.require_gpu(xyz_sampled, "xyz_sampled", _FEATURE)
         self._ensure_cache()
         u = xyz_sampled.detach().reshape(-1, 3).contiguous().float()
         out = torch.empty(u.shape[0], self.app_dim, device=u.device)
         f = self._c_field()
-        st = torch.cuda.current_stream(u.device).cuda_stream
-        N.check(N.lib().lrf_app_feature(C.byref(f), N.ptr(u), u.shape[0], N.ptr(out), st),
-                "lrf_app_feature")
+        N.launch("lrf_app_feature", u.device, C.byref(f), N.ptr(u), u.shape[0], N.ptr(out))
         return out
 
     def compute_features(self, xyz_sampled):
@@ -717,7 +693,7 @@ class TensorVMSplit(torch.nn.Module):
         """tensorBase.py:567-636.  rays_chunk [R,6] -> (rgb_map [R,3], depth_map [R]).
         `refine` only matters when fea_pe > 0 (tensorBase.py:117-126): False feeds zeros in place of the feature encodings.
         `out=(rgb, depth)` (extension, no-grad calls only) renders into caller-owned tensors."""
-        self._require_gpu(rays_chunk)
+        N.require_gpu(rays_chunk, "rays_chunk", _FEATURE)
         z = self.z_schedule(is_train, N_samples, rays_chunk.device)
         use_white = bool(white_bg) or bool(is_train and torch.rand((1,)) < 0.5)   # :633
         flags = self._flags(use_white)
@@ -762,7 +738,7 @@ class TensorVMSplit(torch.nn.Module):
         """tensoRF.py:83-92 through lrf_density_l1_fwd/_bwd: the lattice values are formed in
         registers instead of materialising 8 x g^3 floats per plane (same arithmetic and the
         reference's per-plane flattening orders)."""
-        self._require_gpu(self.density_plane[0])
+        N.require_gpu(self.density_plane[0], "density_plane", _FEATURE)
         fused = self._fused_l1
         if fused is not None:                    # fuse_density_L1: the value the last taped forward of this field computed,
             self._fused_l1 = None                # once, and only for the parameters it was computed from
@@ -799,8 +775,7 @@ class TensorVMSplit(torch.nn.Module):
                 raise N.NativeError("localrf_amd: upsample_volume_grid needs the field on the GPU (no CPU fallback)")
             _, c, h, w = src.shape
             dst = torch.empty(1, c, int(h2), int(w2), dtype=torch.float32, device=src.device)
-            N.check(N.lib().lrf_upsample_bilinear(N.ptr(src), c, h, w, N.ptr(dst), int(h2), int(w2),
-                                                  torch.cuda.current_stream(src.device).cuda_stream), "lrf_upsample_bilinear")
+            N.launch("lrf_upsample_bilinear", src.device, N.ptr(src), c, h, w, N.ptr(dst), int(h2), int(w2))
             return torch.nn.Parameter(dst)
         for i in range(3):
             m0, m1 = self.matMode[i]
@@ -838,15 +813,14 @@ class TensorVMSplit(torch.nn.Module):
         gridSize = self.gridSize if gridSize is None else gridSize
         gx, gy, gz = (int(g) for g in gridSize)
         dev = self.aabb.device
-        self._require_gpu(self.aabb)
+        N.require_gpu(self.aabb, "aabb", _FEATURE)
         self._ensure_cache()
         # torch.linspace on the host, as the reference builds its lattice (:504-508), then uploaded
         lin = [torch.linspace(0, 1, g).to(dev) for g in (gx, gy, gz)]
         alpha = torch.empty(gz, gy, gx, dtype=torch.float32, device=dev)
         f = self._c_field()
-        st = torch.cuda.current_stream(dev).cuda_stream
-        N.check(N.lib().lrf_dense_alpha(C.byref(f), N.ptr(lin[0]), N.ptr(lin[1]), N.ptr(lin[2]), gx, gy, gz,
-                                        float(self.stepSize), self._flags(False), N.ptr(alpha), st), "lrf_dense_alpha")
+        N.launch("lrf_dense_alpha", dev, C.byref(f), N.ptr(lin[0]), N.ptr(lin[1]), N.ptr(lin[2]), gx, gy, gz,
+                 float(self.stepSize), self._flags(False), N.ptr(alpha))
         return alpha.permute(2, 1, 0)
 
     @torch.no_grad()
@@ -857,7 +831,5 @@ class TensorVMSplit(torch.nn.Module):
         alpha = self.getDenseAlpha((gx, gy, gz)).permute(2, 1, 0)          # back to the kernel's [Z][Y][X]
         assert alpha.is_contiguous()
         out = torch.empty_like(alpha)
-        st = torch.cuda.current_stream(alpha.device).cuda_stream
-        N.check(N.lib().lrf_alpha_pool_threshold(N.ptr(alpha), gx, gy, gz, float(self.alphaMask_thres), N.ptr(out), st),
-                "lrf_alpha_pool_threshold")
+        N.launch("lrf_alpha_pool_threshold", alpha.device, N.ptr(alpha), gx, gy, gz, float(self.alphaMask_thres), N.ptr(out))
         self.alphaMask = AlphaGridMask(self.aabb.device, self.aabb.detach(), out)

@@ -71,7 +71,7 @@ class FieldLayout:
         nbytes, dev = lib.lrf_cache_bytes(cp.grid), ps[0].device
         if not self._fits(nbytes, dev):
             self.cache = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
-        N.check(lib.lrf_pack_field(C.byref(cp), self.cache.data_ptr(), torch.cuda.current_stream(dev).cuda_stream), "lrf_pack_field")
+        N.launch("lrf_pack_field", dev, C.byref(cp), self.cache.data_ptr())
         self.key = key
 
     def step_target(self, field):
@@ -115,7 +115,7 @@ class FieldLayout:
         same field side by side (k_march of one batch beside k_shade3 of another: 4096-ray batches alternating over two
         streams 0.164 -> 0.145 ms per batch, scripts/two_stream_fwd_probe.py); the cache they read is shared."""
         nbytes = N.lib().lrf_workspace_bytes(R, S)
-        st = torch.cuda.current_stream(dev).cuda_stream
+        st = N.stream(dev)
         ws = self.ws.get(st)
         if ws is None or ws.numel() < nbytes or ws.device != dev:
             ws = self.ws[st] = torch.empty(nbytes, dtype=torch.uint8, device=dev)

@@ -29,7 +29,6 @@ import torch
 
 from . import _native as N
 from ._native import NativeError
-from .scene_ops import _stream
 
 KEYS = ("rgbs", "loss_weights", "invdepths", "fwd_flow", "fwd_mask", "bwd_flow", "bwd_mask")
 _WIDTH = {"rgbs": 3, "loss_weights": 1, "invdepths": 1, "fwd_flow": 2, "fwd_mask": 1, "bwd_flow": 2, "bwd_mask": 1}
@@ -139,8 +138,7 @@ class DeviceFrames:
             off += _align(int(np.prod(shape)) * np.dtype(dt).itemsize)
         self._stage_bytes = off
         self._upload = torch.empty(off, dtype=torch.uint8, device=dev)                     # device side of the staging block
-        lib = N.lib()
-        self._ws = torch.empty(max(int(lib.lrf_frame_sharpness_workspace_bytes()), 8), dtype=torch.uint8, device=dev)
+        self._ws = torch.empty(max(int(N.lib().lrf_frame_sharpness_workspace_bytes()), 8), dtype=torch.uint8, device=dev)
 
         self.active_frames_bounds = [0, 0]
         self.activate_frames(n_init_frames)
@@ -207,19 +205,18 @@ class DeviceFrames:
         self.rgb[slot].copy_(dev_view("img", 3))
         if self.load_depth:
             self.invdepth[slot].copy_(dev_view("invdepth", 1))
-        lib, st = N.lib(), _stream(self.device)
         H, W = self.img_wh[1], self.img_wh[0]
         if self.flow_kind == "encoded":
             for back, name in ((0, "encoded_fwd_flow"), (1, "encoded_bwd_flow")):
-                N.check(lib.lrf_decode_flow(C.byref(self._win), slot, back, up.data_ptr() + self._layout[name][0], H, W,
-                                            d["flow_scale"], st), "lrf_decode_flow")
+                N.launch("lrf_decode_flow", self.device, C.byref(self._win), slot, back, up.data_ptr() + self._layout[name][0],
+                         H, W, d["flow_scale"])
         elif self.flow_kind == "decoded":
             self.fwd_flow[slot].copy_(dev_view("fwd_flow", 2))
             self.bwd_flow[slot].copy_(dev_view("bwd_flow", 2))
             self.fwd_mask[slot].copy_(dev_view("fwd_mask", 1))
             self.bwd_mask[slot].copy_(dev_view("bwd_mask", 1))
         mask_ptr = up.data_ptr() + self._layout["mask"][0] if self.has_motion_mask else None
-        N.check(lib.lrf_frame_sharpness(C.byref(self._win), slot, H, W, mask_ptr, self._ws.data_ptr(), st), "lrf_frame_sharpness")
+        N.launch("lrf_frame_sharpness", self.device, C.byref(self._win), slot, H, W, mask_ptr, self._ws.data_ptr())
 
     def _prepare(self, i, d):
         """Reader output -> the staging dtypes (masks as float32 / uint8)."""
@@ -316,9 +313,8 @@ class DeviceFrames:
             raise ValueError(f"the store holds no {missing}")
         vi, ri = view_ids.reshape(-1).contiguous(), ray_ids.reshape(-1).contiguous()
         out = {k: torch.empty(B, _WIDTH[k], dtype=torch.float32, device=self.device) for k in want}
-        with torch.cuda.device(self.device):
-            N.check(N.lib().lrf_frames_gather(C.byref(self._win), vi.data_ptr(), ri.data_ptr(), V, B // V,
-                                              *[N.ptr(out.get(k)) for k in KEYS], _stream(self.device)), "lrf_frames_gather")
+        N.launch("lrf_frames_gather", self.device, C.byref(self._win), vi.data_ptr(), ri.data_ptr(), V, B // V,
+                 *[N.ptr(out.get(k)) for k in KEYS], guard=True)
         return out
 
     def errors(self, clear=False):

@@ -28,6 +28,7 @@ import time
 import numpy as np
 import torch
 
+from . import _native as N
 from .optim import StaticAdamPlan
 from .scene_ops import rows_gather
 
@@ -206,13 +207,13 @@ class CapturedIteration:
             self._pool = torch.cuda.graph_pool_handle()
             self._side = torch.cuda.Stream()
             self._keeper = torch.cuda.CUDAGraph()                 # a one-node graph that lives as long as this object: the allocator
-            self._side.wait_stream(torch.cuda.current_stream())  # drops a private pool with its last graph
+            self._side.wait_stream(N.torch_stream())  # drops a private pool with its last graph
             with torch.cuda.stream(self._side):
                 self._keeper.capture_begin(pool=self._pool)
                 self._keeper_buf = torch.zeros(64, device=self.inputs.blob.device)
                 self._keeper.capture_end()
         g = torch.cuda.CUDAGraph()
-        cur = torch.cuda.current_stream()
+        cur = N.torch_stream()
         side = self._side
         side.wait_stream(cur)
         with torch.cuda.stream(side):

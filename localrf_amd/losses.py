@@ -19,7 +19,8 @@ import ctypes as C
 import torch
 
 from . import _native as N
-from .scene_ops import _f32c, _stream
+
+_FEATURE = "the loss kernels"
 
 
 def _i32(t, dev):
@@ -40,8 +41,8 @@ class _FlowLossFn(torch.autograd.Function):
         dev = depth.device
         V, n = depth.shape
         a = N.LrfFlowLoss()
-        keep = [_f32c(cam2world), frame, _f32c(dirs), _f32c(depth), ij.contiguous(), _f32c(fwd_flow), _f32c(fwd_mask),
-                _f32c(bwd_flow), _f32c(bwd_mask), _f32c(focal).reshape(-1), _f32c(center).reshape(-1), fwd_off]
+        keep = [N.conform(cam2world), frame, N.conform(dirs), N.conform(depth), ij.contiguous(), N.conform(fwd_flow), N.conform(fwd_mask),
+                N.conform(bwd_flow), N.conform(bwd_mask), N.conform(focal).reshape(-1), N.conform(center).reshape(-1), fwd_off]
         if keep[0].dim() != 3 or keep[0].shape[1:] != (3, 4):
             raise ValueError("cam2world must be [F,3,4]")
         if keep[4].dtype != torch.int64:
@@ -52,7 +53,7 @@ class _FlowLossFn(torch.autograd.Function):
         a.F, a.V, a.n, a.quantile = keep[0].shape[0], V, n, float(q)
         arr = torch.empty(V, n, dtype=torch.float32, device=dev)
         vsum = torch.empty(V, dtype=torch.float32, device=dev)
-        N.check(N.lib().lrf_flow_loss_fwd(C.byref(a), N.ptr(arr), N.ptr(vsum), _stream(dev)), "lrf_flow_loss_fwd")
+        N.launch("lrf_flow_loss_fwd", dev, C.byref(a), N.ptr(arr), N.ptr(vsum))
         ctx.args, ctx.keep, ctx.arr = a, [t.detach() for t in keep], arr     # (kept alive for the raw pointers in `a`)
         ctx.focal_shape = focal.shape
         ctx.mark_non_differentiable(arr)
@@ -71,9 +72,9 @@ class _FlowLossFn(torch.autograd.Function):
         ws = torch.empty(V * 36, dtype=torch.float32, device=dev)
         # per_view: the output was the V per-view sums, every one of which enters the total with the same weight (combine):
         # the first element of the incoming gradient is that weight
-        g = _f32c(g_loss[0:1] if ctx.per_view else g_loss).reshape(1)
-        N.check(N.lib().lrf_flow_loss_bwd(C.byref(a), N.ptr(arr), N.ptr(g), 1.0 if ctx.per_view else 1.0 / float(V * n), N.ptr(g_depth), N.ptr(g_dirs),
-                                          N.ptr(g_c2w), N.ptr(g_intr), N.ptr(ws), _stream(dev)), "lrf_flow_loss_bwd")
+        g = N.conform(g_loss[0:1] if ctx.per_view else g_loss).reshape(1)
+        N.launch("lrf_flow_loss_bwd", dev, C.byref(a), N.ptr(arr), N.ptr(g), 1.0 if ctx.per_view else 1.0 / float(V * n),
+                 N.ptr(g_depth), N.ptr(g_dirs), N.ptr(g_c2w), N.ptr(g_intr), N.ptr(ws))
         if not (ctx.needs_input_grad[3] or ctx.needs_input_grad[4]):   # intrinsics without a tape (LocalTensorfs.freeze_intrinsics)
             return g_depth, g_dirs, g_c2w, None, None, None, None, None, None, None, None, None, None, None
         s = g_intr.sum(0)
@@ -88,9 +89,8 @@ def flow_loss(depth_map, directions, ij, cam2world, view_ids, starting_frame_id,
     per_view: return the V per-view sums of the clipped array instead of its mean (mean = sum / (V n): `combine` folds that
     factor into the term's weight).  frame_ids: int32 device [2, V] = (view - starting_frame_id, view == F - 1) prepared by the
     caller (the captured iteration stages it with its other inputs) -- otherwise formed here from view_ids."""
+    N.require_gpu(depth_map, "depth_map", _FEATURE)
     dev = depth_map.device
-    if dev.type != "cuda":
-        raise N.NativeError("localrf_amd.losses: tensors must be on the GPU (there is no CPU fallback)")
     view_ids = torch.as_tensor(view_ids)
     V = int(view_ids.shape[0])
     depth = depth_map.reshape(V, -1)
@@ -126,12 +126,11 @@ class _DepthLossFn(torch.autograd.Function):
     def forward(ctx, depth, gt, q, per_view=False):
         dev = depth.device
         V, n = depth.shape
-        d, g = _f32c(depth), _f32c(gt)
+        d, g = N.conform(depth), N.conform(gt)
         arr = torch.empty(V, n, dtype=torch.float32, device=dev)
         stats = torch.empty(V, 6, dtype=torch.float32, device=dev)
         vsum = torch.empty(V, dtype=torch.float32, device=dev)
-        N.check(N.lib().lrf_depth_loss_fwd(N.ptr(d), N.ptr(g), V, n, float(q), N.ptr(arr), N.ptr(stats), N.ptr(vsum), _stream(dev)),
-                "lrf_depth_loss_fwd")
+        N.launch("lrf_depth_loss_fwd", dev, N.ptr(d), N.ptr(g), V, n, float(q), N.ptr(arr), N.ptr(stats), N.ptr(vsum))
         ctx.keep = (d.detach(), g.detach(), arr, stats)
         ctx.mark_non_differentiable(arr)
         ctx.per_view = bool(per_view)
@@ -142,18 +141,16 @@ class _DepthLossFn(torch.autograd.Function):
         d, g, arr, stats = ctx.keep
         V, n = arr.shape
         g_depth = torch.empty_like(d)
-        gl = _f32c(g_loss[0:1] if ctx.per_view else g_loss).reshape(1)
-        N.check(N.lib().lrf_depth_loss_bwd(N.ptr(d), N.ptr(g), V, n, N.ptr(arr), N.ptr(stats), N.ptr(gl), 1.0 if ctx.per_view else 1.0 / float(V * n),
-                                           N.ptr(g_depth), _stream(d.device)), "lrf_depth_loss_bwd")
+        gl = N.conform(g_loss[0:1] if ctx.per_view else g_loss).reshape(1)
+        N.launch("lrf_depth_loss_bwd", d.device, N.ptr(d), N.ptr(g), V, n, N.ptr(arr), N.ptr(stats), N.ptr(gl),
+                 1.0 if ctx.per_view else 1.0 / float(V * n), N.ptr(g_depth))
         return g_depth, None, None, None
 
 
 def depth_loss(depth_map, invdepths, n_views, quantile=0.8, return_arr=False, per_view=False):
     """`depth_loss_arr.mean()` of train.py:414-421: compute_depth_loss(1 / depth_map.clamp(1e-6), invdepths) per view,
     entries above the view's 0.8-quantile zeroed.  per_view: the n_views per-view sums instead of the mean (see flow_loss)."""
-    dev = depth_map.device
-    if dev.type != "cuda":
-        raise N.NativeError("localrf_amd.losses: tensors must be on the GPU (there is no CPU fallback)")
+    N.require_gpu(depth_map, "depth_map", _FEATURE)
     depth = depth_map.reshape(int(n_views), -1)
     if depth.shape[1] > N.LRF_LOSS_MAX_PER_VIEW:
         raise ValueError(f"at most {N.LRF_LOSS_MAX_PER_VIEW} rays per view")
@@ -164,23 +161,23 @@ def depth_loss(depth_map, invdepths, n_views, quantile=0.8, return_arr=False, pe
 class _PhotoLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, rgb, target, weights, w_mean):
-        r, t = _f32c(rgb), _f32c(target)
-        w = None if weights is None else _f32c(weights).reshape(-1)
-        wm = None if w_mean is None else _f32c(w_mean).reshape(-1)
+        r, t = N.conform(rgb), N.conform(target)
+        w = None if weights is None else N.conform(weights).reshape(-1)
+        wm = None if w_mean is None else N.conform(w_mean).reshape(-1)
         dev = r.device
         out = torch.empty(2, dtype=torch.float32, device=dev)
-        N.check(N.lib().lrf_photo_loss_fwd(N.ptr(r), N.ptr(t), N.ptr(w), N.ptr(wm), r.shape[0], N.ptr(out[0:1]), N.ptr(out[1:2]), _stream(dev)),
-                "lrf_photo_loss_fwd")
+        N.launch("lrf_photo_loss_fwd", dev, N.ptr(r), N.ptr(t), N.ptr(w), N.ptr(wm), r.shape[0], N.ptr(out[0:1]),
+                 N.ptr(out[1:2]))
         ctx.keep = (r.detach(), t.detach(), w, out)
         return out[0]
 
     @staticmethod
     def backward(ctx, g_loss):
         r, t, w, out = ctx.keep
-        g = _f32c(g_loss).reshape(1)
+        g = N.conform(g_loss).reshape(1)
         g_rgb = torch.empty_like(r)
-        N.check(N.lib().lrf_photo_loss_bwd(N.ptr(r), N.ptr(t), N.ptr(w), N.ptr(out[1:2]), N.ptr(g), r.shape[0], N.ptr(g_rgb), _stream(r.device)),
-                "lrf_photo_loss_bwd")
+        N.launch("lrf_photo_loss_bwd", r.device, N.ptr(r), N.ptr(t), N.ptr(w), N.ptr(out[1:2]), N.ptr(g), r.shape[0],
+                 N.ptr(g_rgb))
         return g_rgb, None, None, None
 
 
@@ -189,8 +186,7 @@ def photometric_loss(rgb_map, rgb_train, loss_weights=None, weights_mean=None):
     (differentiable in rgb_map).  rgb_map, rgb_train [R,3]; loss_weights [R] / [R,1] or None (ones); weights_mean: a device
     scalar to divide by instead of this batch's own mean -- under ray sharding the batch-global mean
     (localrf_amd.dist.global_mean), so that an N-rank step equals the 1-rank step."""
-    if rgb_map.device.type != "cuda":
-        raise N.NativeError("localrf_amd.losses: tensors must be on the GPU (there is no CPU fallback)")
+    N.require_gpu(rgb_map, "rgb_map", _FEATURE)
     if rgb_map.dim() != 2 or rgb_map.shape[1] != 3 or rgb_train.shape != rgb_map.shape:
         raise ValueError("rgb_map and rgb_train must both be [R,3]")
     if loss_weights is not None and loss_weights.numel() != rgb_map.shape[0]:
@@ -206,9 +202,8 @@ def batch_gather(view_ids, pix, images=None, fwd_flow=None, bwd_flow=None, invde
     [n_images, H*W, 3 | 2 | 2] and [n_images, H*W] float32 on the device, None = not wanted.  Returns a dict: "target" [V n, 3],
     "fwd_flow" / "bwd_flow" [V n, 2], "fwd_mask" / "bwd_mask" [V n] (1 where the view has a next / previous image),
     "invdepths" [V n].  Not differentiable (the dataset is data)."""
+    N.require_gpu(pix, "pix", _FEATURE)
     dev = pix.device
-    if dev.type != "cuda":
-        raise N.NativeError("localrf_amd.losses: tensors must be on the GPU (there is no CPU fallback)")
     if view_ids.dtype != torch.int64 or pix.dtype != torch.int64:
         raise ValueError("view_ids and pix must be int64")
     V, n = int(pix.shape[0]), int(pix.shape[1])
@@ -238,9 +233,8 @@ def batch_gather(view_ids, pix, images=None, fwd_flow=None, bwd_flow=None, invde
         out["bwd_mask"] = torch.empty(V * n, dtype=torch.float32, device=dev)
     if invdepths is not None:
         out["invdepths"] = torch.empty(V * n, dtype=torch.float32, device=dev)
-    N.check(N.lib().lrf_batch_gather(C.byref(a), N.ptr(out.get("target")), N.ptr(out.get("fwd_flow")), N.ptr(out.get("fwd_mask")),
-                                     N.ptr(out.get("bwd_flow")), N.ptr(out.get("bwd_mask")), N.ptr(out.get("invdepths")), _stream(dev)),
-            "lrf_batch_gather")
+    N.launch("lrf_batch_gather", dev, C.byref(a), N.ptr(out.get("target")), N.ptr(out.get("fwd_flow")),
+             N.ptr(out.get("fwd_mask")), N.ptr(out.get("bwd_flow")), N.ptr(out.get("bwd_mask")), N.ptr(out.get("invdepths")))
     return out
 
 
@@ -249,14 +243,14 @@ class _CombineFn(torch.autograd.Function):
     def forward(ctx, s, coef, *xs):
         dev = xs[0].device
         t = N.LrfLossTerms()
-        keep = [_f32c(x).reshape(-1) for x in xs]
+        keep = [N.conform(x).reshape(-1) for x in xs]
         for k, (x, (a, b)) in enumerate(zip(keep, coef)):
             t.x[k], t.n[k], t.a[k], t.b[k] = x.data_ptr(), int(x.numel()), float(a), float(b)
         t.count = len(keep)
-        sk = None if s is None else _f32c(s).reshape(-1)
+        sk = None if s is None else N.conform(s).reshape(-1)
         t.s = None if sk is None else sk.data_ptr()
         out = torch.empty(1 + N.LRF_LOSS_TERMS_MAX, dtype=torch.float32, device=dev)
-        N.check(N.lib().lrf_loss_combine_fwd(C.byref(t), N.ptr(out[0:1]), N.ptr(out[1:]), _stream(dev)), "lrf_loss_combine_fwd")
+        N.launch("lrf_loss_combine_fwd", dev, C.byref(t), N.ptr(out[0:1]), N.ptr(out[1:]))
         ctx.w, ctx.shapes = out[1:], [x.shape for x in xs]
         return out[0]
 
@@ -264,8 +258,8 @@ class _CombineFn(torch.autograd.Function):
     def backward(ctx, g_total):
         n = len(ctx.shapes)
         g = torch.empty(n, dtype=torch.float32, device=ctx.w.device)
-        gt = _f32c(g_total).reshape(1)
-        N.check(N.lib().lrf_loss_combine_bwd(N.ptr(ctx.w), N.ptr(gt), n, N.ptr(g), _stream(g.device)), "lrf_loss_combine_bwd")
+        gt = N.conform(g_total).reshape(1)
+        N.launch("lrf_loss_combine_bwd", g.device, N.ptr(ctx.w), N.ptr(gt), n, N.ptr(g))
         return (None, None) + tuple(g[k].expand(sh) for k, sh in enumerate(ctx.shapes))
 
 
@@ -277,6 +271,5 @@ def combine(terms, s=None):
     Differentiable in every x_k."""
     if not 0 < len(terms) <= N.LRF_LOSS_TERMS_MAX:
         raise ValueError(f"1..{N.LRF_LOSS_TERMS_MAX} terms")
-    if terms[0][0].device.type != "cuda":
-        raise N.NativeError("localrf_amd.losses: tensors must be on the GPU (there is no CPU fallback)")
+    N.require_gpu(terms[0][0], "terms[0]", _FEATURE)
     return _CombineFn.apply(s, tuple((float(a), float(b)) for _, a, b in terms), *[x for x, _, _ in terms])

@@ -19,12 +19,12 @@ import torch
 
 from . import _native as N
 from ._native import NativeError
-from .scene_ops import _stream
 
 MAX_FILTER_SIZE = 31
 
 
-def _check_shape(shape0, shape1, filter_size):
+def check_shapes(shape0, shape1, filter_size):
+    """The filter size as an int, for two image shapes that go together; ValueError otherwise.  No launch."""
     if tuple(shape0) != tuple(shape1):
         raise ValueError(f"image shapes differ: {tuple(shape0)} vs {tuple(shape1)}")
     if len(shape0) not in (3, 4) or shape0[-1] != 3:
@@ -38,15 +38,9 @@ def _check_shape(shape0, shape1, filter_size):
     return fs
 
 
-def _device_images(t, name):
-    if not torch.is_tensor(t):
-        raise TypeError(f"{name} must be a torch tensor")
-    if not t.is_cuda:
-        raise NativeError(f"localrf_amd.metrics: {name} lives on {t.device}; the metrics run only on an AMD GPU (HIP kernels). "
-                          "There is no CPU fallback.")
-    if t.dtype is not torch.float32:
-        t = t.float()
-    return t.contiguous()
+def _images(t, name):
+    N.require_gpu(t, name, "the metrics")
+    return N.conform(t)
 
 
 def _launch(img0, img1, max_val, fs, filter_sigma, k1, k2, want_map):
@@ -59,24 +53,19 @@ def _launch(img0, img1, max_val, fs, filter_sigma, k1, k2, want_map):
     a.img0, a.img1 = img0.data_ptr(), img1.data_ptr()
     a.B, a.H, a.W, a.filter_size = B, H, W, fs
     a.max_val, a.filter_sigma, a.k1, a.k2 = float(max_val), float(filter_sigma), float(k1), float(k2)
-    lib = N.lib()
-    nbytes = lib.lrf_image_metrics_workspace_bytes(B, H, W, fs)
-    if nbytes == 0:
-        raise NativeError(f"lrf_image_metrics: refused shape B={B} H={H} W={W} filter_size={fs}")
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws = N.workspace("lrf_image_metrics", dev, B, H, W, fs)
     out = torch.empty(2, B, dtype=torch.float64, device=dev)
     smap = torch.empty(B, H - fs + 1, W - fs + 1, 3, dtype=torch.float64, device=dev) if want_map else None
-    with torch.cuda.device(dev):
-        N.check(lib.lrf_image_metrics(C.byref(a), None if smap is None else smap.data_ptr(), out[1].data_ptr(),
-                                      out[0].data_ptr(), ws.data_ptr(), _stream(dev)), "lrf_image_metrics")
+    N.launch("lrf_image_metrics", dev, C.byref(a), None if smap is None else smap.data_ptr(), out[1].data_ptr(), out[0].data_ptr(),
+             ws.data_ptr(), guard=True)
     return out[0], out[1], smap
 
 
 def image_metrics(rgb, gt, max_val=1.0, filter_size=11, filter_sigma=1.5, k1=0.01, k2=0.03):
     """Per-frame (mse [B], ssim [B]) of device images [B,H,W,3] (or [H,W,3]: B = 1) as fp64 device tensors, without a
     host sync.  ssim is rgb_ssim(gt[b], rgb[b], max_val, ...) (symmetric in its two images); mse is ((gt - rgb) ** 2).mean()."""
-    fs = _check_shape(rgb.shape, gt.shape, filter_size)
-    rgb, gt = _device_images(rgb, "rgb"), _device_images(gt, "gt")
+    fs = check_shapes(rgb.shape, gt.shape, filter_size)
+    rgb, gt = _images(rgb, "rgb"), _images(gt, "gt")
     if rgb.dim() == 3:
         rgb, gt = rgb[None], gt[None]
     mse, ssim, _ = _launch(gt, rgb, max_val, fs, filter_sigma, k1, k2, False)
@@ -92,7 +81,7 @@ def rgb_ssim(img0, img1, max_val, filter_size=11, filter_sigma=1.5, k1=0.01, k2=
         img0, img1 = np.asarray(img0), np.asarray(img1)
         if img0.ndim != 3:
             raise ValueError(f"numpy images must be [H,W,3], got {img0.shape}")
-    fs = _check_shape(img0.shape, img1.shape, filter_size)
+    fs = check_shapes(img0.shape, img1.shape, filter_size)
     if host:
         if not torch.cuda.is_available():
             raise NativeError("localrf_amd.metrics.rgb_ssim: no AMD GPU visible; there is no CPU fallback")
@@ -100,7 +89,7 @@ def rgb_ssim(img0, img1, max_val, filter_size=11, filter_sigma=1.5, k1=0.01, k2=
         img0 = torch.from_numpy(np.ascontiguousarray(img0, dtype=np.float32)).to(dev)
         img1 = torch.from_numpy(np.ascontiguousarray(img1, dtype=np.float32)).to(dev)
     else:
-        img0, img1 = _device_images(img0, "img0"), _device_images(img1, "img1")
+        img0, img1 = _images(img0, "img0"), _images(img1, "img1")
     single = img0.dim() == 3
     if single:
         img0, img1 = img0[None], img1[None]
@@ -134,8 +123,8 @@ def test_view_metrics(local_tensorfs, gt_rgbs, view_ids, W, H, fbases=None, chun
         raise ValueError(f"{len(fbases)} fbases for {n} views")
     if tuple(gt_rgbs.shape) != (n, H, W, 3):
         raise ValueError(f"gt_rgbs must be [{n},{H},{W},3], got {tuple(gt_rgbs.shape)}")
-    fs = _check_shape(gt_rgbs.shape[1:], (H, W, 3), filter_size)
-    gt = _device_images(gt_rgbs, "gt_rgbs")
+    fs = check_shapes(gt_rgbs.shape[1:], (H, W, 3), filter_size)
+    gt = _images(gt_rgbs, "gt_rgbs")
     if n == 0:
         return {}
     dev = gt.device
@@ -147,7 +136,7 @@ def test_view_metrics(local_tensorfs, gt_rgbs, view_ids, W, H, fbases=None, chun
                                  floater_thresh=floater_thresh)[0]
             if not rgb.is_cuda:                         # a view no field covers: LocalTensorfs.forward's host placeholder
                 rgb = rgb.to(dev)
-            rgb = _device_images(rgb, "rendered rgb").reshape(1, H, W, 3)
+            rgb = _images(rgb, "rendered rgb").reshape(1, H, W, 3)
             mse, ssim, _ = _launch(gt[i:i + 1], rgb, max_val, fs, filter_sigma, k1, k2, False)
             out[0, i:i + 1].copy_(mse)
             out[1, i:i + 1].copy_(ssim)

@@ -19,7 +19,7 @@ import torch
 
 from . import _native as N
 from ._native import NativeError
-from .scene_ops import _stream, scene_forward
+from .scene_ops import scene_forward
 
 _ENC_MAX_PX = ((1 << 31) - 1) // 3           # lrf_encode_frames: 3 V H W < 2^31
 
@@ -79,7 +79,7 @@ def fixed_range(minmax):
 
 def _aligned(t):
     """Contiguous fp32; copied when the data does not start on 16 bytes (the kernel reads float4)."""
-    t = t.to(torch.float32).contiguous()
+    t = N.conform(t)
     return t if t.data_ptr() % 16 == 0 else t.clone()
 
 
@@ -92,22 +92,14 @@ def _encode(rgb, depth, minmax, lut, want_idx, want_range):
     depth8 = torch.empty(V, H, W, 3, dtype=torch.uint8, device=dev)
     idx = torch.empty(V, H, W, dtype=torch.uint8, device=dev) if want_idx else None
     rng = torch.empty(V, 2, dtype=torch.float32, device=dev) if want_range else None
-    lib = N.lib()
     step = _ENC_MAX_PX // (H * W)
     step = V if step >= V else max(1, step // 4 * 4)          # split calls start on 16-byte boundaries
-    ws = None
-    if minmax is None:
-        nbytes = lib.lrf_encode_frames_workspace_bytes(min(V, step))
-        if nbytes == 0:
-            raise NativeError(f"lrf_encode_frames: refused {min(V, step)} frames")
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        for v0 in range(0, V, step):
-            v1 = min(V, v0 + step)
-            p = lambda t: None if t is None else t[v0].data_ptr()  # noqa: E731
-            N.check(lib.lrf_encode_frames(p(rgb), depth[v0].data_ptr(), v1 - v0, H, W, lut.data_ptr(), fr, p(rgb8),
-                                          depth8[v0].data_ptr(), p(idx), p(rng), None if ws is None else ws.data_ptr(),
-                                          _stream(dev)), "lrf_encode_frames")
+    ws = N.workspace("lrf_encode_frames", dev, min(V, step)) if minmax is None else None
+    for v0 in range(0, V, step):
+        v1 = min(V, v0 + step)
+        p = lambda t: None if t is None else t[v0].data_ptr()  # noqa: E731
+        N.launch("lrf_encode_frames", dev, p(rgb), depth[v0].data_ptr(), v1 - v0, H, W, lut.data_ptr(), fr, p(rgb8),
+                 depth8[v0].data_ptr(), p(idx), p(rng), None if ws is None else ws.data_ptr(), guard=True)
     return rgb8, depth8, idx, rng
 
 
@@ -122,12 +114,6 @@ def _device_frames(t, name, trailing):
     return t
 
 
-def _require_gpu(t, name):
-    if not t.is_cuda:
-        raise NativeError(f"localrf_amd.novel_views: {name} lives on {t.device}; the encoding runs only on an AMD GPU (HIP "
-                          "kernels). There is no CPU fallback.")
-
-
 def visualize_depth(depth, minmax=None, cmap=None, return_index=False):
     """utils/utils.py:179-197 on the device: depth [..., H, W] -> (uint8 [..., H, W, 3], [mi, ma]).  The bytes are what
     renderer.py:148 makes of the reference's result, (ToTensor(img) * 255).byte() permuted to HWC, i.e. the colour map's
@@ -139,7 +125,7 @@ def visualize_depth(depth, minmax=None, cmap=None, return_index=False):
     if minmax is not None:
         fixed_range(minmax)
     _check_lut(cmap)
-    _require_gpu(d, "depth")
+    N.require_gpu(d, "depth", "the encoding")
     lut = _lut(cmap, d.device)
     lead, (H, W) = d.shape[:-2], d.shape[-2:]
     frames = _aligned(d.reshape(-1, H, W))
@@ -174,7 +160,7 @@ def encode_frames(rgb, depth, minmax=(0, 5), cmap=None, return_index=False):
     if minmax is not None:
         fixed_range(minmax)
     _check_lut(cmap)
-    _require_gpu(d, "depth")
+    N.require_gpu(d, "depth", "the encoding")
     lut = _lut(cmap, d.device)
     lead, (H, W) = d.shape[:-2], d.shape[-2:]
     rgb8, depth8, idx, _ = _encode(_aligned(r.reshape(-1, H, W, 3)), _aligned(d.reshape(-1, H, W)), minmax, lut,
@@ -361,7 +347,7 @@ def _iter_frames(lt, poses, vids, is_test, groups, W, H, dev, lut, exposure, flo
     names = ("rgb8", "depth8", "depth") if with_depth else ("rgb8", "depth8")
     shapes = {"rgb8": ((vmax, H, W, 3), torch.uint8), "depth8": ((vmax, H, W, 3), torch.uint8), "depth": ((vmax, H, W), torch.float32)}
     ring = [{k: torch.empty(*shapes[k][0], dtype=shapes[k][1], pin_memory=True) for k in names} for _ in range(2)]
-    main = torch.cuda.current_stream(dev)
+    main = N.torch_stream(dev)
     side = torch.cuda.Stream(dev)
     pending = [None, None]                                      # per slot: (group, copy event, device tensors kept alive)
 

@@ -86,12 +86,10 @@ class FusedAdam(torch.optim.Optimizer):
     @staticmethod
     def _launch(entries):
         """One lrf_adam_step per (betas, eps, device) class, LRF_ADAM_MAX tensors at a time."""
-        lib = N.lib()
         classes = {}
         for e in entries:
             classes.setdefault((e[6], e[7], e[0].device), []).append(e)
         for ((b1, b2), eps, dev), es in classes.items():
-            st = torch.cuda.current_stream(dev).cuda_stream
             for lo in range(0, len(es), N.LRF_ADAM_MAX):
                 part = es[lo:lo + N.LRF_ADAM_MAX]
                 tab = (N.LrfAdamTensor * len(part))()
@@ -101,11 +99,11 @@ class FusedAdam(torch.optim.Optimizer):
                 fused = _pack_target(e[8] for e in part) if len(es) <= N.LRF_ADAM_MAX else None
                 if fused is not None:                         # the step writes the field's layout cache too
                     field, (cp, keep, cache) = fused
-                    N.check(lib.lrf_adam_step_pack(tab, len(part), None, b1, b2, eps, C.byref(cp), cache.data_ptr(), st), "lrf_adam_step_pack")
+                    N.launch("lrf_adam_step_pack", dev, tab, len(part), None, b1, b2, eps, C.byref(cp), cache.data_ptr())
                     increment_version([e[0] for e in part])
                     field.layout.mark_fresh(field)
                     continue
-                N.check(lib.lrf_adam_step(tab, len(part), b1, b2, eps, st), "lrf_adam_step")
+                N.launch("lrf_adam_step", dev, tab, len(part), b1, b2, eps)
                 # the kernel rewrote the parameters behind autograd's back: bump their versions so
                 # layout caches keyed on (data_ptr, _version) (FieldLayout.current_key) and
                 # autograd's saved-tensor checks see the change
@@ -179,7 +177,6 @@ class StaticAdamPlan:
     def launch(self, scalars_dev):
         """Enqueue (or capture) the launches.  scalars_dev: float32 [len(self), 2] on the device.  Every parameter must
         hold its gradient (.grad) at this point: the pointers are baked into the launch."""
-        lib = N.lib()
         classes = {}
         for i, (opt, p) in enumerate(self.pairs):
             grp = self._group[(id(opt), id(p))]
@@ -192,7 +189,6 @@ class StaticAdamPlan:
         if order != list(range(len(self.pairs))):
             raise ValueError("StaticAdamPlan: pairs must be grouped by (betas, eps, device)")
         for ((b1, b2), eps, dev), idx in classes.items():
-            st = torch.cuda.current_stream(dev).cuda_stream
             for lo in range(0, len(idx), N.LRF_ADAM_MAX):
                 part = idx[lo:lo + N.LRF_ADAM_MAX]
                 tab = (N.LrfAdamTensor * len(part))()
@@ -204,11 +200,11 @@ class StaticAdamPlan:
                 fused = _pack_target(self.pairs[i][0].pack_field for i in part) if len(idx) <= N.LRF_ADAM_MAX else None
                 if fused is not None:                         # the step leaves the field's layout cache holding the stepped values
                     field, (cp, keep, cache) = fused
-                    N.check(lib.lrf_adam_step_pack(tab, len(part), scalars_dev[part[0]:].data_ptr(), b1, b2, eps, C.byref(cp), cache.data_ptr(), st),
-                            "lrf_adam_step_pack")
+                    N.launch("lrf_adam_step_pack", dev, tab, len(part), scalars_dev[part[0]:].data_ptr(), b1, b2, eps,
+                             C.byref(cp), cache.data_ptr())
                     self._packed_field = field
                     continue
-                N.check(lib.lrf_adam_step_dev(tab, len(part), scalars_dev[part[0]:].data_ptr(), b1, b2, eps, st), "lrf_adam_step_dev")
+                N.launch("lrf_adam_step_dev", dev, tab, len(part), scalars_dev[part[0]:].data_ptr(), b1, b2, eps)
 
     def host_scalars(self, out, active=None):
         """Advance the step counters of the parameters stepped this iteration and write their (step_size, bc2_sqrt) rows into

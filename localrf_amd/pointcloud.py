@@ -20,16 +20,9 @@ import torch
 
 from . import _native as N
 from ._native import NativeError
-from .scene_ops import _stream
 
 _INT32 = (1 << 31) - 1
 BYTES_PER_RESIDENT_PIXEL = 7                   # scene_point_cloud keeps depth (4 B) and rgb8 (3 B) of every frame
-
-
-def _require_gpu(t, name):
-    if not t.is_cuda:
-        raise NativeError(f"localrf_amd.pointcloud: {name} lives on {t.device}; the point fusion runs only on an AMD GPU (HIP "
-                          "kernels). There is no CPU fallback.")
 
 
 def _check_depth(depth):
@@ -110,19 +103,15 @@ def _fuse(depth, rgb8, poses, focal, center, fov360, stride, d_min, d_max, neigh
     """Checked arguments, device tensors -> (xyz, rgb8 or None, src, count).  The one read-back is count."""
     dev = depth.device
     V, H, W = (int(s) for s in depth.shape)
-    depth = depth.detach().to(torch.float32).contiguous()
+    depth = N.conform(depth)
     poses = poses.detach().to(device=dev, dtype=torch.float32).contiguous()
     f = c = None
     if not fov360:
         f, c = _dev_f32(focal, 1, dev), _dev_f32(center, 2, dev)
-    lib = N.lib()
-    nbytes = lib.lrf_points_workspace_bytes(V, H, W, stride)
-    if nbytes == 0:
-        raise NativeError(f"lrf_points_fuse: refused {V} x {H} x {W} at stride {stride}")
     n_cand = V * (-(-H // stride)) * (-(-W // stride))
     cap = n_cand if max_points is None else min(int(max_points), n_cand)
     rows = max(cap, 1)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws = N.workspace("lrf_points", dev, V, H, W, stride)
     xyz = torch.empty(rows, 3, dtype=torch.float32, device=dev)
     src = torch.empty(rows, 2, dtype=torch.int32, device=dev)
     out8 = None if rgb8 is None else torch.empty(rows, 3, dtype=torch.uint8, device=dev)
@@ -136,9 +125,8 @@ def _fuse(depth, rgb8, poses, focal, center, fov360, stride, d_min, d_max, neigh
     for k, o in enumerate(neigh):
         a.neigh[k] = o
     a.rel_tol, a.min_consistent = rel_tol, min_consistent
-    with torch.cuda.device(dev):
-        N.check(lib.lrf_points_fuse(C.byref(a), cap, xyz.data_ptr(), None if out8 is None else out8.data_ptr(), src.data_ptr(),
-                                    count.data_ptr(), ws.data_ptr(), _stream(dev)), "lrf_points_fuse")
+    N.launch("lrf_points_fuse", dev, C.byref(a), cap, xyz.data_ptr(), None if out8 is None else out8.data_ptr(), src.data_ptr(),
+             count.data_ptr(), ws.data_ptr(), guard=True)
     m = int(count.item())                                          # the ONE read-back (it also orders ws's release)
     if m > cap:
         raise ValueError(f"the fused cloud holds {m} points; max_points={max_points} does not fit them")
@@ -154,7 +142,7 @@ def backproject(depth, poses, W, H, focal=None, center=None, fov360=False):
         raise ValueError(f"depth is {Hd} x {Wd} (H x W) but H, W = {H}, {W}")
     poses = _check_poses(poses, V)
     focal, center = _check_intrinsics(focal, center, fov360)
-    _require_gpu(depth, "depth")
+    N.require_gpu(depth, "depth", "the point fusion")
     xyz, _, src, _ = _fuse(depth, None, poses, focal, center, bool(fov360), 1, 0.0, math.inf, [], 0.0, 0, None)
     return xyz, src
 
@@ -187,15 +175,14 @@ def fuse_points(rgb, depth, poses, focal, center, *, fov360=False, stride=1, dep
     focal, center = _check_intrinsics(focal, center, fov360)
     stride, d_min, d_max, neigh, rel_tol, min_consistent = _check_filter(stride, depth_range, neighbours, rel_tol, min_consistent,
                                                                          fov360, max_points)
-    _require_gpu(depth, "depth")
+    N.require_gpu(depth, "depth", "the point fusion")
     rgb8 = None
     if rgb is not None:
         if rgb.dtype is torch.uint8:
             rgb8 = rgb.contiguous()
         else:
-            from .novel_views import _aligned, _encode, _lut
-            d32 = _aligned(depth.detach())
-            rgb8 = _encode(_aligned(rgb.detach()), d32, (0, 5), _lut(None, depth.device), False, False)[0]
+            from .novel_views import encode_frames
+            rgb8 = encode_frames(rgb.detach(), depth.detach())[0]
     xyz, out8, src, m = _fuse(depth, rgb8, poses, focal, center, bool(fov360), stride, d_min, d_max, neigh, rel_tol,
                               min_consistent, max_points)
     return {"xyz": xyz, "rgb8": out8, "src": src, "count": m}

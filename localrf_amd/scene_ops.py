@@ -13,17 +13,7 @@ import torch
 
 from . import _native as N
 
-
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
-def _f32c(t):
-    """Contiguous fp32 view of t for a native call (only data_ptr() is taken, so an already conforming tensor is
-    passed through as is: detach() alone costs ~4 us, 70 of them per training iteration)."""
-    if t.dtype is torch.float32 and t.is_contiguous():
-        return t
-    return t.detach().contiguous().float()
+_FEATURE = "the scene kernels"
 
 
 class _SceneRaysFn(torch.autograd.Function):
@@ -32,15 +22,14 @@ class _SceneRaysFn(torch.autograd.Function):
         dev = ray_ids.device
         R, n_rf = ray_ids.shape[0], world2rf.shape[0]
         ids = ray_ids.detach().contiguous().long()
-        c2w, w2rf = _f32c(cam2world), _f32c(world2rf)
-        fo = None if focal is None else _f32c(focal)
-        ce = None if center is None else _f32c(center)
+        c2w, w2rf = N.conform(cam2world), N.conform(world2rf)
+        fo = None if focal is None else N.conform(focal)
+        ce = None if center is None else N.conform(center)
         rays = torch.empty(n_rf, R, 6, dtype=torch.float32, device=dev)
         dirs = torch.empty(R, 3, dtype=torch.float32, device=dev)
         ij = torch.empty(R, 2, dtype=torch.int64, device=dev)
-        N.check(N.lib().lrf_scene_rays(ids.data_ptr(), R, per_view, N.ptr(c2w), N.ptr(w2rf), n_rf, N.ptr(fo),
-                                       N.ptr(ce), W, H, int(fov360), N.ptr(rays), N.ptr(dirs), ij.data_ptr(),
-                                       _stream(dev)), "lrf_scene_rays")
+        N.launch("lrf_scene_rays", dev, ids.data_ptr(), R, per_view, N.ptr(c2w), N.ptr(w2rf), n_rf, N.ptr(fo), N.ptr(ce), W,
+                 H, int(fov360), N.ptr(rays), N.ptr(dirs), ij.data_ptr())
         ctx.save_for_backward(ids, c2w, fo, ce)
         ctx.set_materialize_grads(False)                         # an unused output (directions without the flow loss) costs no zero fill
         ctx.meta = (R, per_view, n_rf, W, H, int(fov360))
@@ -56,14 +45,13 @@ class _SceneRaysFn(torch.autograd.Function):
         dev, V = ids.device, R // per_view
         if g_rays is None:
             g_rays = torch.zeros(n_rf, R, 6, dtype=torch.float32, device=dev)
-        g_rays = _f32c(g_rays)
-        g_dirs = None if g_dirs is None else _f32c(g_dirs)
+        g_rays = N.conform(g_rays)
+        g_dirs = None if g_dirs is None else N.conform(g_dirs)
         g_c2w = torch.empty(V, 3, 4, dtype=torch.float32, device=dev)
         g_intr = torch.empty(V, 3, dtype=torch.float32, device=dev)        # (every entry is written: k_scene_rays_bwd, one block per view)
         g_w2rf = torch.empty(V, n_rf, 3, dtype=torch.float32, device=dev)
-        N.check(N.lib().lrf_scene_rays_bwd(ids.data_ptr(), R, per_view, N.ptr(c2w), n_rf, N.ptr(fo), N.ptr(ce),
-                                           W, H, fov360, N.ptr(g_rays), N.ptr(g_dirs), N.ptr(g_c2w),
-                                           N.ptr(g_intr), N.ptr(g_w2rf), _stream(dev)), "lrf_scene_rays_bwd")
+        N.launch("lrf_scene_rays_bwd", dev, ids.data_ptr(), R, per_view, N.ptr(c2w), n_rf, N.ptr(fo), N.ptr(ce), W, H,
+                 fov360, N.ptr(g_rays), N.ptr(g_dirs), N.ptr(g_c2w), N.ptr(g_intr), N.ptr(g_w2rf))
         g_focal = g_center = None
         if not fov360 and (ctx.needs_input_grad[3] or ctx.needs_input_grad[4]):
             s = g_intr.sum(0)
@@ -76,14 +64,14 @@ class _SceneBlendFn(torch.autograd.Function):
     def forward(ctx, rgb_f, dep_f, blend_w, exposure, per_view):
         dev = rgb_f.device
         n_rf, R = rgb_f.shape[0], rgb_f.shape[1]
-        rgb_f, dep_f, bw = _f32c(rgb_f), _f32c(dep_f), _f32c(blend_w)
-        ex = None if exposure is None else _f32c(exposure)
+        rgb_f, dep_f, bw = N.conform(rgb_f), N.conform(dep_f), N.conform(blend_w)
+        ex = None if exposure is None else N.conform(exposure)
         need_bwd = any(ctx.needs_input_grad)
         rgbs = torch.empty(R, 3, dtype=torch.float32, device=dev)
         depth = torch.empty(R, dtype=torch.float32, device=dev)
         pre = torch.empty(R, 3, dtype=torch.float32, device=dev) if need_bwd else None
-        N.check(N.lib().lrf_scene_blend(N.ptr(rgb_f), N.ptr(dep_f), N.ptr(bw), N.ptr(ex), R, per_view, n_rf,
-                                        N.ptr(rgbs), N.ptr(depth), N.ptr(pre), _stream(dev)), "lrf_scene_blend")
+        N.launch("lrf_scene_blend", dev, N.ptr(rgb_f), N.ptr(dep_f), N.ptr(bw), N.ptr(ex), R, per_view, n_rf, N.ptr(rgbs),
+                 N.ptr(depth), N.ptr(pre))
         if need_bwd:
             ctx.save_for_backward(pre, bw, ex)
         ctx.set_materialize_grads(False)                         # (depth_map unused by the loss: no zero fill, the kernel takes a null pointer)
@@ -95,14 +83,13 @@ class _SceneBlendFn(torch.autograd.Function):
         pre, bw, ex = ctx.saved_tensors
         R, per_view, n_rf = ctx.meta
         dev, V = pre.device, R // per_view
-        g_rgbs = torch.zeros(R, 3, device=dev) if g_rgbs is None else _f32c(g_rgbs)
-        g_depth = None if g_depth is None else _f32c(g_depth)
+        g_rgbs = torch.zeros(R, 3, device=dev) if g_rgbs is None else N.conform(g_rgbs)
+        g_depth = None if g_depth is None else N.conform(g_depth)
         g_rgb_f = torch.empty(n_rf, R, 3, dtype=torch.float32, device=dev)
         g_dep_f = torch.empty(n_rf, R, dtype=torch.float32, device=dev)
         g_ex = torch.empty(V, 3, 3, dtype=torch.float32, device=dev) if ex is not None else None
-        N.check(N.lib().lrf_scene_blend_bwd(N.ptr(g_rgbs), N.ptr(g_depth), N.ptr(pre), N.ptr(bw), N.ptr(ex),
-                                            R, per_view, n_rf, N.ptr(g_rgb_f), N.ptr(g_dep_f), N.ptr(g_ex),
-                                            _stream(dev)), "lrf_scene_blend_bwd")
+        N.launch("lrf_scene_blend_bwd", dev, N.ptr(g_rgbs), N.ptr(g_depth), N.ptr(pre), N.ptr(bw), N.ptr(ex), R, per_view,
+                 n_rf, N.ptr(g_rgb_f), N.ptr(g_dep_f), N.ptr(g_ex))
         return g_rgb_f, g_dep_f, None, g_ex, None
 
 
@@ -116,12 +103,11 @@ class _PoseFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, quirk, *params):
         V = len(params) // 2
-        rs = [_f32c(p) for p in params[:V]]
-        ts = [_f32c(p) for p in params[V:]]
+        rs = [N.conform(p) for p in params[:V]]
+        ts = [N.conform(p) for p in params[V:]]
         dev = rs[0].device
         c2w = torch.empty(V, 3, 4, dtype=torch.float32, device=dev)
-        N.check(N.lib().lrf_pose_assemble(_PoseFn._ptrs(rs), _PoseFn._ptrs(ts), V, int(quirk), N.ptr(c2w),
-                                          _stream(dev)), "lrf_pose_assemble")
+        N.launch("lrf_pose_assemble", dev, _PoseFn._ptrs(rs), _PoseFn._ptrs(ts), V, int(quirk), N.ptr(c2w))
         ctx.save_for_backward(*rs)
         ctx.quirk = int(quirk)
         return c2w
@@ -132,9 +118,8 @@ class _PoseFn(torch.autograd.Function):
         V, dev = len(rs), rs[0].device
         g_r = torch.empty(V, 3, 2, dtype=torch.float32, device=dev)
         g_t = torch.empty(V, 3, dtype=torch.float32, device=dev)
-        g_c = _f32c(g_c2w)
-        N.check(N.lib().lrf_pose_assemble_bwd(_PoseFn._ptrs(rs), V, ctx.quirk, N.ptr(g_c), N.ptr(g_r), N.ptr(g_t),
-                                              _stream(dev)), "lrf_pose_assemble_bwd")
+        g_c = N.conform(g_c2w)
+        N.launch("lrf_pose_assemble_bwd", dev, _PoseFn._ptrs(rs), V, ctx.quirk, N.ptr(g_c), N.ptr(g_r), N.ptr(g_t))
         return (None,) + tuple(g_r.unbind(0)) + tuple(g_t.unbind(0))
 
 
@@ -143,7 +128,7 @@ def pose_assemble(r_list, t_list, cross_over_views=False):
     (LocalTensorfs.get_cam2world, local_tensorfs.py:292-299; sixD_to_mtx, utils/utils.py:381-388).
     cross_over_views (V == 3 only): b3 = cross(b1, b2) over the VIEW axis, which is what the
     reference's dim-less torch.cross computes for a batch of exactly three views."""
-    _require_gpu(r_list[0])
+    N.require_gpu(r_list[0], "r_list[0]", _FEATURE)
     if cross_over_views and len(r_list) != 3:
         raise ValueError("cross_over_views reproduces a reference quirk that exists for exactly 3 views")
     parts = []
@@ -153,17 +138,11 @@ def pose_assemble(r_list, t_list, cross_over_views=False):
     return parts[0] if len(parts) == 1 else torch.cat(parts, 0)
 
 
-def _require_gpu(t):
-    if not t.is_cuda:
-        raise N.NativeError("localrf_amd: the scene kernels run only on an AMD GPU (HIP); got a "
-                            f"{t.device} tensor. There is no CPU fallback.")
-
-
 def scene_rays(ray_ids, cam2world, world2rf, focal, center, per_view, W, H, fov360=False, squeeze=False):
     """-> rays [n_rf,R,6] (origin | unnormalised direction, per field), directions [R,3], ij [R,2].
     cam2world [V,3,4] (or [V,4,4]); world2rf [n_rf,3]; focal [1] / center [2] tensors (None for 360).
     squeeze (one field only): rays come back as [R,6]."""
-    _require_gpu(ray_ids)
+    N.require_gpu(ray_ids, "ray_ids", _FEATURE)
     if ray_ids.shape[0] % per_view:
         raise ValueError("number of rays must be a multiple of the number of views")
     if squeeze and world2rf.shape[0] != 1:
@@ -175,7 +154,7 @@ def scene_rays(ray_ids, cam2world, world2rf, focal, center, per_view, W, H, fov3
 
 def scene_blend(rgb_f, dep_f, blend_w, exposure, per_view):
     """-> (clamp(E_v * sum_k w[v,k] rgb_k, 0, 1) [R,3], sum_k w[v,k] depth_k [R])."""
-    _require_gpu(rgb_f)
+    N.require_gpu(rgb_f, "rgb_f", _FEATURE)
     return _SceneBlendFn.apply(rgb_f, dep_f, blend_w, exposure, int(per_view))
 
 
@@ -184,7 +163,7 @@ def scene_forward(ray_ids, cam2world, world2rf, focal, center, per_view, W, H, f
     """LocalTensorfs.forward without a tape as ONE native call (lrf_scene_fwd): rays of every active field, the per-field
     renders in the reference's chunk / field order (local_tensorfs.py:440-474), blend, exposure, clamp.
     `fields`: the active TensorVMSplit objects; world2rf [n_rf,3].  -> (rgbs [R,3], depth [R], directions [R,3], ij [R,2])."""
-    _require_gpu(ray_ids)
+    N.require_gpu(ray_ids, "ray_ids", _FEATURE)
     dev = ray_ids.device
     # the kernel reads int64 ids at unit stride (as the taped path's _SceneRaysFn coerces them): an int32 or strided
     # tensor handed over as is would be read out of bounds
@@ -192,17 +171,16 @@ def scene_forward(ray_ids, cam2world, world2rf, focal, center, per_view, W, H, f
     R, n_rf = int(ids.shape[0]), len(fields)
     if R % per_view:
         raise ValueError("number of rays must be a multiple of the number of views")
-    c2w = _f32c(cam2world[:, :3, :])
-    w2rf = _f32c(world2rf)
-    fo = None if fov360 else _f32c(focal)
-    ce = None if fov360 else _f32c(center)
-    bw = _f32c(blend_w)
-    ex = None if exposure is None else _f32c(exposure)
+    c2w = N.conform(cam2world[:, :3, :])
+    w2rf = N.conform(world2rf)
+    fo = None if fov360 else N.conform(focal)
+    ce = None if fov360 else N.conform(center)
+    bw = N.conform(blend_w)
+    ex = None if exposure is None else N.conform(exposure)
     n_chunk = R if chunk <= 0 else min(int(chunk), R)
     arr = (N.LrfSceneField * n_rf)()
     keep = []
     for k, f in enumerate(fields):
-        f._require_gpu(ray_ids)
         f._ensure_cache()
         z = f.z_schedule(False, -1, dev).detach().contiguous().float().view(-1)
         cf = f._c_field()
@@ -229,11 +207,10 @@ def scene_forward(ray_ids, cam2world, world2rf, focal, center, per_view, W, H, f
     rgbs = torch.empty(R, 3, dtype=torch.float32, device=dev)
     depth = torch.empty(R, dtype=torch.float32, device=dev)
     if R:
-        N.check(N.lib().lrf_scene_fwd(ids.data_ptr(), R, int(per_view), N.ptr(c2w), N.ptr(w2rf), n_rf, N.ptr(fo), N.ptr(ce),
-                                      int(W), int(H), int(bool(fov360)), arr, float(floater_thresh), int(n_chunk),
-                                      N.ptr(bw), N.ptr(ex), N.ptr(rays), N.ptr(rgb_f), N.ptr(dep_f), N.ptr(dirs), ij.data_ptr(),
-                                      N.ptr(rgbs), N.ptr(depth), None if sws is None else sws.data_ptr(), sws_bytes,
-                                      _stream(dev)), "lrf_scene_fwd")
+        N.launch("lrf_scene_fwd", dev, ids.data_ptr(), R, int(per_view), N.ptr(c2w), N.ptr(w2rf), n_rf, N.ptr(fo), N.ptr(ce),
+                 int(W), int(H), int(bool(fov360)), arr, float(floater_thresh), int(n_chunk), N.ptr(bw), N.ptr(ex),
+                 N.ptr(rays), N.ptr(rgb_f), N.ptr(dep_f), N.ptr(dirs), ij.data_ptr(), N.ptr(rgbs), N.ptr(depth),
+                 None if sws is None else sws.data_ptr(), sws_bytes)
     return rgbs, depth, dirs, ij
 
 
@@ -254,11 +231,11 @@ class _RowsGatherFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, src, idx):
-        s = _f32c(src)
+        s = N.conform(src)
         F, K = s.shape
         V = idx.shape[0]
         out = torch.empty(V, K, dtype=torch.float32, device=s.device)
-        N.check(N.lib().lrf_rows_gather(N.ptr(s), idx.data_ptr(), V, K, F, N.ptr(out), _stream(s.device)), "lrf_rows_gather")
+        N.launch("lrf_rows_gather", s.device, N.ptr(s), idx.data_ptr(), V, K, F, N.ptr(out))
         ctx.save_for_backward(idx)
         ctx.shape = (F, K)
         return out
@@ -267,9 +244,9 @@ class _RowsGatherFn(torch.autograd.Function):
     def backward(ctx, g_out):
         (idx,) = ctx.saved_tensors
         F, K = ctx.shape
-        g = _f32c(g_out)
+        g = N.conform(g_out)
         g_src = torch.empty(F, K, dtype=torch.float32, device=g.device)
-        N.check(N.lib().lrf_rows_gather_bwd(N.ptr(g), idx.data_ptr(), idx.shape[0], K, F, N.ptr(g_src), _stream(g.device)), "lrf_rows_gather_bwd")
+        N.launch("lrf_rows_gather_bwd", g.device, N.ptr(g), idx.data_ptr(), idx.shape[0], K, F, N.ptr(g_src))
         return g_src, None
 
 

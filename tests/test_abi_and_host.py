@@ -430,3 +430,61 @@ def test_no_runtime_fill_or_copy_in_the_library_sources():
         text = re.sub(r"//[^\n]*", "", open(os.path.join(src_dir, name)).read())
         bad += [(name, m.group(0)) for m in re.finditer(r"\bhipMem(set\w*|cpy\w*Async)\s*\(", text)]   # (a blocking debug read-back is fine)
     assert not bad, bad
+
+
+def test_native_calling_convention_has_one_owner(monkeypatch):
+    """localrf_amd._native owns how a C-ABI function is called: call() reports a failure under the symbol's own name,
+    workspace() runs the *_workspace_bytes protocol, require_gpu() / conform() are the one device check and the one
+    conversion.  A stub stands in for the library: no GPU and no built library are needed."""
+    from localrf_amd import _native as N
+
+    class Stub:
+        def __init__(self):
+            self.rc, self.nbytes, self.seen = 0, 0, []
+
+        def lrf_last_error(self):
+            return b"the stub said no"
+
+        def lrf_photo_loss_fwd(self, *args):
+            self.seen.append(args)
+            return self.rc
+
+        def lrf_select_workspace_bytes(self, *shape):
+            self.seen.append(shape)
+            return self.nbytes
+
+    stub = Stub()
+    monkeypatch.setattr(N, "_lib", stub)
+    assert N.call("lrf_photo_loss_fwd", 1, 2, 3) is None
+    assert stub.seen == [(1, 2, 3)]
+    stub.rc = 5
+    with pytest.raises(N.NativeError) as e:
+        N.call("lrf_photo_loss_fwd", 4)
+    assert "lrf_photo_loss_fwd" in str(e.value) and "the stub said no" in str(e.value)
+
+    with pytest.raises(N.NativeError, match="refused") as e:
+        N.workspace("lrf_select", "cpu", 7, 9)
+    assert "7" in str(e.value) and "9" in str(e.value)
+    assert stub.seen[-1] == (7, 9)
+    stub.nbytes = 4096 + 3
+    ws = N.workspace("lrf_select", "cpu", 7, 9)
+    assert ws.dtype is torch.uint8 and ws.numel() == 4099 and ws.dim() == 1
+
+    with pytest.raises(TypeError, match="depth must be a torch tensor"):
+        N.require_gpu([1.0, 2.0], "depth", "the point fusion")
+    with pytest.raises(TypeError, match="depth must be a torch tensor"):
+        N.require_gpu(np.zeros(3, np.float32), "depth", "the point fusion")
+    with pytest.raises(N.NativeError, match="no CPU fallback") as e:
+        N.require_gpu(torch.zeros(3), "depth", "the point fusion")
+    assert "depth lives on cpu" in str(e.value) and "the point fusion" in str(e.value)
+
+    t = torch.zeros(4, 3)
+    assert N.conform(t) is t
+    i = torch.zeros(4, dtype=torch.int64)
+    assert N.conform(i, torch.int64) is i
+    for bad in (t.t(), t.double(), t.requires_grad_()[:, :2]):
+        c = N.conform(bad)
+        assert c is not bad and c.dtype is torch.float32 and c.is_contiguous() and not c.requires_grad
+        assert torch.equal(c, bad.detach().float())
+    p = torch.nn.Parameter(torch.zeros(2, 2))
+    assert N.conform(p) is p                                     # no detach() for a conforming tensor
