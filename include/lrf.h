@@ -604,6 +604,27 @@ size_t lrf_points_workspace_bytes(int32_t V, int32_t H, int32_t W, int32_t strid
 int lrf_points_fuse(const LrfPointsFuse* a, int64_t capacity, float* xyz, uint8_t* rgb8_out /* nullable */, int32_t* src,
                     int64_t* count /* device [1] */, void* workspace, void* stream);
 
+/* Surface normals from the gradient of the density feature (csrc/lrf_normals.inl states the arithmetic, all fp32).
+ * lrf_density_gradient: u [P,3] normalised coordinates -> grad_u [P,3] = d density_feature / du, analytic from the taps
+ * the value reads (piecewise constant per cell along an axis, 0 along an axis the border clamps), and feat [P] (nullable):
+ * the bits lrf_density_feature returns.  P = 0 launches nothing.
+ * lrf_render_normals: per ray N = sum over the samples the colour pass shades (w_i > weight_thres) of w_i n_i, with
+ * n_i = -grad_x g / max(|grad_x g|, 1e-8) of g(x) = density_feature(u(contract(x))) and w the weights lrf_render_fwd leaves
+ * in weight_out (alpha mask, forced last sample and floater filter applied).  N is not normalised, |N| <= acc; a ray
+ * without a shaded sample gives exactly (0, 0, 0).  One forward render into the workspace, then one launch without atomics:
+ * the same bits on every run.  flags, floater_thresh: as lrf_render_fwd takes them.  blend_w (nullable; [ceil(R / per_view)])
+ * scales ray r's N and acc by blend_w[r / per_view]; accumulate = 1 adds to normals / acc instead of overwriting them (a
+ * scene sums its fields in field order).  normals [R,3], acc [R] (nullable).  Refused before any launch: null pointers,
+ * R <= 0, S outside [2, 4096], unknown flag bits, per_view < 1 with blend_w, accumulate outside {0, 1}, misaligned pointers
+ * (workspace: 256 bytes).  workspace: lrf_normals_workspace_bytes(R, S) bytes = the forward's workspace, the [R,S] weights
+ * and 5 R floats of per-ray outputs (0 for a refused shape). */
+int lrf_density_gradient(const LrfField* f, const float* u /* [P,3] normalised */, int64_t P, float* grad_u /* [P,3] */,
+                         float* feat /* [P] or NULL */, void* stream);
+size_t lrf_normals_workspace_bytes(int32_t R, int32_t S);
+int lrf_render_normals(const LrfField* f, const float* rays, const float* z, int32_t R, int32_t S, uint32_t flags,
+                       float floater_thresh, const float* blend_w /* nullable */, int32_t per_view, int32_t accumulate,
+                       float* normals /* [R,3] */, float* acc /* [R] or NULL */, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -223,6 +223,10 @@ SYMBOLS = {
     "lrf_points_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "lrf_points_fuse": (C.c_int, [C.POINTER(LrfPointsFuse), C.c_int64, _f, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p]),
+    "lrf_density_gradient": (C.c_int, [C.POINTER(LrfField), _f, C.c_int64, _f, _f, C.c_void_p]),
+    "lrf_normals_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "lrf_render_normals": (C.c_int, [C.POINTER(LrfField), _f, _f, C.c_int32, C.c_int32, C.c_uint32, C.c_float, _f, C.c_int32,
+                                     C.c_int32, _f, _f, C.c_void_p, C.c_void_p]),
     "lrf_scene_blend_bwd": (C.c_int, [_f, _f, _f, _f, _f, C.c_int32, C.c_int32, C.c_int32, _f, _f, _f,
                                       C.c_void_p]),
 }

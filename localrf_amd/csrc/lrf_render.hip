@@ -1449,3 +1449,5 @@ int lrf_sample_ray_contracted(const float* rays_o, const float* rays_d, const fl
 }
 
 }  // extern "C"
+
+#include "lrf_normals.inl"

@@ -624,6 +624,53 @@ class TensorVMSplit(torch.nn.Module):
         N.launch("lrf_density_feature", u.device, C.byref(f), N.ptr(u), u.shape[0], N.ptr(out))
         return out
 
+    def density_gradient(self, xyz_sampled, return_feature=False):
+        """Gradient of compute_densityfeature with respect to the normalised coordinates [P,3] -> [P,3] (lrf_density_gradient:
+        analytic from the taps the value reads, 0 along an axis whose coordinate the border clamps).  No autograd, same
+        contract as compute_densityfeature; return_feature=True also returns its values [P] (the same bits)."""
+        N.require_gpu(xyz_sampled, "xyz_sampled", _FEATURE)
+        self._ensure_cache()
+        u = xyz_sampled.detach().reshape(-1, 3).contiguous().float()
+        grad = torch.empty(u.shape[0], 3, dtype=torch.float32, device=u.device)
+        feat = torch.empty(u.shape[0], dtype=torch.float32, device=u.device) if return_feature else None
+        if u.shape[0] == 0:
+            return (grad, feat) if return_feature else grad
+        f = self._c_field()
+        N.launch("lrf_density_gradient", u.device, C.byref(f), N.ptr(u), u.shape[0], N.ptr(grad), N.ptr(feat))
+        return (grad, feat) if return_feature else grad
+
+    def _native_normals(self, rays, z, flags, floater, blend_w=None, per_view=1, out=None, accumulate=False):
+        """lrf_render_normals on checked device tensors: rays [R,6] and z [S] contiguous fp32.  out=(normals [R,3], acc [R]):
+        caller-owned tensors, overwritten or (accumulate) added to -- a scene's sum over its fields, each scaled by
+        blend_w[r // per_view]."""
+        R, S, dev = rays.shape[0], z.shape[0], rays.device
+        if out is None:
+            normals = torch.empty(R, 3, dtype=torch.float32, device=dev)
+            acc = torch.empty(R, dtype=torch.float32, device=dev)
+        else:
+            normals, acc = out
+        if R == 0:
+            return normals, acc
+        self.layout.ensure(self)
+        ws = N.workspace("lrf_normals", dev, R, S)
+        f = self.layout.c_field(self)
+        N.launch("lrf_render_normals", dev, C.byref(f), N.ptr(rays), N.ptr(z), R, S, flags, float(floater), N.ptr(blend_w),
+                 int(per_view), int(bool(accumulate)), N.ptr(normals), N.ptr(acc), ws.data_ptr())
+        return normals, acc
+
+    def render_normals(self, rays_chunk, N_samples=-1, floater_thresh=0):
+        """rays_chunk [R,6] -> (normals [R,3], acc [R]): N = sum over the samples the colour pass shades (w_i >
+        rayMarch_weight_thres) of w_i n_i, n_i = -grad g / max(|grad g|, 1e-8) of g(x) = density_feature(u(contract(x))), with
+        the weights render_weights returns.  Field-local orientation (the world's: world2rf is a translation).  N is not
+        normalised and |N| <= acc; a ray through empty space gives exactly (0, 0, 0).  No autograd."""
+        N.require_gpu(rays_chunk, "rays_chunk", _FEATURE)
+        if rays_chunk.dim() != 2 or rays_chunk.shape[1] != 6:
+            raise ValueError(f"rays_chunk must be [R, 6], got {tuple(rays_chunk.shape)}")
+        z = self.z_schedule(False, N_samples, rays_chunk.device)
+        rays = rays_chunk.detach().contiguous().float()
+        z = z.detach().contiguous().float().view(-1)
+        return self._native_normals(rays, z, self._flags(True), float(floater_thresh))
+
     def compute_appfeature(self, xyz_sampled):
         """tensoRF.py:153-196 on normalised coordinates [P,3] -> [P,27]."""
         N.require_gpu(xyz_sampled, "xyz_sampled", _FEATURE)

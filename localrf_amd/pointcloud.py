@@ -3,7 +3,7 @@
   backproject(depth, poses, W, H, ...)          every pixel with a finite positive depth -> (xyz [M,3], src [M,2])
   fuse_points(rgb, depth, poses, focal, ...)    strided, depth-ranged, multi-view-consistent points with colours
   scene_point_cloud(local_tensorfs, W, H, ...)  novel_views.render_poses, then fuse_points with the scene's intrinsics
-  write_ply(path, xyz, rgb8)                    binary little-endian PLY from one device -> host copy
+  write_ply(path, xyz, rgb8, normals)           binary little-endian PLY from one device -> host copy
 
 Conventions (the reference's): a rendered depth is sum w z / |d|, a multiple of the UN-normalised camera direction whose z
 is -1 for a pinhole (tensorBase.py:615, utils/ray_utils.py:14-24); the camera point is direction * depth (utils/utils.py:15-48)
@@ -23,6 +23,7 @@ from ._native import NativeError
 
 _INT32 = (1 << 31) - 1
 BYTES_PER_RESIDENT_PIXEL = 7                   # scene_point_cloud keeps depth (4 B) and rgb8 (3 B) of every frame
+BYTES_PER_NORMAL_PIXEL = 16                    # and with normals=True the normal map (12 B) and its acc (4 B)
 
 
 def _check_depth(depth):
@@ -192,14 +193,19 @@ _FUSE_KEYS = ("stride", "depth_range", "neighbours", "rel_tol", "min_consistent"
 _RENDER_KEYS = ("test_frames", "frame_indices", "floater_thresh", "chunk", "frames_per_call")
 
 
-def scene_point_cloud(local_tensorfs, W, H, poses=None, max_bytes=4 << 30, **options):
+def scene_point_cloud(local_tensorfs, W, H, poses=None, max_bytes=4 << 30, normals=False, orient=False, **options):
     """A scene's point cloud: its frames rendered by novel_views.render_poses, then fuse_points with the scene's focal(W),
     center(W, H) and fov.  poses=None renders the scene's own get_cam2world(), each frame through itself (frame_indices =
     0..F-1); otherwise poses [N,3,4] as render_poses takes them.  options: fuse_points' stride, depth_range, neighbours,
     rel_tol, min_consistent, max_points and render_poses' test_frames, frame_indices, floater_thresh, chunk, frames_per_call.
     Every frame's depth and rgb8 stay resident, 7 bytes per pixel (the float colours are dropped once encoded); more than
-    max_bytes of them raises ValueError before anything is rendered.  A sliding window over frames is not provided."""
+    max_bytes of them raises ValueError before anything is rendered.  A sliding window over frames is not provided.
+    normals=True adds cloud["normal"] [M,3]: the scene's normal map (normals.render_normals, same poses and render options,
+    16 more resident bytes per pixel) gathered at cloud["src"] and scaled to unit length, a zero-length row left as zero.
+    orient=True (with normals) flips a normal that faces away from its source camera, n . (x - t_cam) > 0."""
     from . import novel_views
+    if orient and not normals:
+        raise ValueError("scene_point_cloud: orient=True needs normals=True")
     unknown = sorted(set(options) - set(_FUSE_KEYS) - set(_RENDER_KEYS))
     if unknown:
         raise TypeError(f"scene_point_cloud: unknown options {unknown}")
@@ -217,10 +223,10 @@ def scene_point_cloud(local_tensorfs, W, H, poses=None, max_bytes=4 << 30, **opt
         render.setdefault("frame_indices", list(range(n)))
     else:
         n = int(novel_views._poses(poses).shape[0])
-    need = BYTES_PER_RESIDENT_PIXEL * n * H * W
+    need = (BYTES_PER_RESIDENT_PIXEL + (BYTES_PER_NORMAL_PIXEL if normals else 0)) * n * H * W
     if need > int(max_bytes):
-        raise ValueError(f"scene_point_cloud: {n} frames of {H} x {W} keep {need} bytes of depth and rgb8 resident; "
-                         f"max_bytes is {int(max_bytes)}")
+        raise ValueError(f"scene_point_cloud: {n} frames of {H} x {W} keep {need} bytes of depth and rgb8"
+                         f"{' and normals' if normals else ''} resident; max_bytes is {int(max_bytes)}")
     if n < 1:
         raise ValueError("scene_point_cloud: no frame to render")
     if n * H * W > _INT32:
@@ -234,23 +240,36 @@ def scene_point_cloud(local_tensorfs, W, H, poses=None, max_bytes=4 << 30, **opt
             poses = lt.get_cam2world().detach()
     out = novel_views.render_poses(lt, poses, W, H, **render)
     depth, rgb8 = out["depth"], out["rgb8"]
-    poses = novel_views._poses(poses)
     del out                                                         # the float colours go back to the allocator
-    return fuse_points(rgb8, depth, poses, None if fov360 else lt.focal(W), None if fov360 else lt.center(W, H),
-                       fov360=fov360, **fuse)
+    cloud = fuse_points(rgb8, depth, novel_views._poses(poses), None if fov360 else lt.focal(W),
+                        None if fov360 else lt.center(W, H), fov360=fov360, **fuse)
+    if normals:
+        from .normals import render_normals, unit_normals
+        nrm = render_normals(lt, poses, W, H, **{k: v for k, v in render.items() if k != "frames_per_call"})["normal"]
+        src = cloud["src"].long()
+        unit = unit_normals(nrm.view(n, H * W, 3)[src[:, 0], src[:, 1]])[0]
+        if orient:
+            t_cam = novel_views._poses(poses)[:, :, 3].to(device=dev, dtype=torch.float32)[src[:, 0]]
+            away = ((cloud["xyz"] - t_cam) * unit).sum(-1) > 0
+            unit = torch.where(away[:, None], -unit, unit)
+        cloud["normal"] = unit
+    return cloud
 
 
-def ply_header(n, colours):
+def ply_header(n, colours, normals=False):
     lines = ["ply", "format binary_little_endian 1.0", f"element vertex {int(n)}",
              "property float x", "property float y", "property float z"]
+    if normals:
+        lines += ["property float nx", "property float ny", "property float nz"]
     if colours:
         lines += ["property uchar red", "property uchar green", "property uchar blue"]
     return ("\n".join(lines + ["end_header"]) + "\n").encode("ascii")
 
 
-def write_ply(path, xyz, rgb8=None):
-    """Binary little-endian PLY (x y z float, red green blue uchar when rgb8 is given) of xyz [M,3] and rgb8 [M,3] uint8:
-    tensors (one device -> host copy each) or numpy arrays.  Returns the number of vertices written."""
+def write_ply(path, xyz, rgb8=None, normals=None):
+    """Binary little-endian PLY (x y z float, nx ny nz float when normals are given, red green blue uchar when rgb8 is
+    given) of xyz [M,3], normals [M,3] and rgb8 [M,3] uint8: tensors (one device -> host copy each) or numpy arrays.
+    Returns the number of vertices written."""
     def host(t, dtype, name):
         a = t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
         if a.ndim != 2 or a.shape[1] != 3:
@@ -262,12 +281,20 @@ def write_ply(path, xyz, rgb8=None):
     cols = None if rgb8 is None else host(rgb8, np.uint8, "rgb8")
     if cols is not None and cols.shape[0] != pts.shape[0]:
         raise ValueError(f"{pts.shape[0]} points but {cols.shape[0]} colours")
-    if cols is None:
+    nrm = None if normals is None else host(normals, np.float32, "normals")
+    if nrm is not None and nrm.shape[0] != pts.shape[0]:
+        raise ValueError(f"{pts.shape[0]} points but {nrm.shape[0]} normals")
+    if cols is None and nrm is None:
         rec = pts.astype("<f4")
     else:
-        rec = np.empty(pts.shape[0], dtype=np.dtype([("p", "<f4", 3), ("c", "u1", 3)]))
-        rec["p"], rec["c"] = pts, cols
+        fields = [("p", "<f4", 3)] + ([("n", "<f4", 3)] if nrm is not None else []) + ([("c", "u1", 3)] if cols is not None else [])
+        rec = np.empty(pts.shape[0], dtype=np.dtype(fields))
+        rec["p"] = pts
+        if nrm is not None:
+            rec["n"] = nrm
+        if cols is not None:
+            rec["c"] = cols
     with open(path, "wb") as fh:
-        fh.write(ply_header(pts.shape[0], cols is not None))
+        fh.write(ply_header(pts.shape[0], cols is not None, nrm is not None))
         fh.write(rec.tobytes())
     return int(pts.shape[0])

@@ -1,0 +1,219 @@
+"""Normals on the GPU against the autograd oracle of tests/normals_cases.py.
+
+Tolerance: in every case the oracle is evaluated in fp64 and in fp32; e = max |fp32 - fp64| over the samples (point
+queries) or rays (composites) that sit on no kink, and the kernel must lie within max(4 e, 1e-6) of the fp64 oracle on
+that set.  Four, because the kernel sums the 24 channel products and the tap differences in another order than ATen and is
+otherwise the same fp32 arithmetic.  The excluded set comes from the oracle alone and is capped: 0.5 % of the points, 2 % of
+the rays."""
+import numpy as np
+import pytest
+import torch
+
+from localrf_amd import normals, pointcloud
+from normals_cases import (GRID, MAX_FLAGGED_POINTS, MAX_FLAGGED_RAYS, encode_normals_host, field, field_dict, flag_u, grad_u,
+                           point_queries, ray_case, test_rays)
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+
+
+def _bound(e):
+    return max(4.0 * e, 1e-6)
+
+
+def test_point_queries_against_the_oracle():
+    f = field(DEV, 21)
+    u = point_queries(22)
+    g, feat = f.density_gradient(u.to(DEV), return_feature=True)
+    assert g.shape == (u.shape[0], 3) and g.dtype is torch.float32
+    assert torch.equal(feat, f.compute_densityfeature(u.to(DEV)))       # the same bits
+    assert torch.equal(g, f.density_gradient(u.to(DEV)))
+    g = g.cpu()
+    assert torch.isfinite(g).all()
+    outside = (u < -1) | (u > 1)
+    assert outside.any() and (g[outside] == 0).all()                    # a clamped coordinate passes no gradient
+    assert (g[u.abs() == 1] == 0).all() and (g[-14:-6] == 0).all()      # nor does one on the border itself (the corners: none)
+    g64, _ = grad_u(field_dict(f, torch.float64), u.double())
+    g32, _ = grad_u(field_dict(f, torch.float32), u)
+    flagged = flag_u(u, GRID)
+    assert flagged[-14:].all()
+    assert int(flagged.sum()) <= MAX_FLAGGED_POINTS * u.shape[0], int(flagged.sum())
+    keep = ~flagged
+    e = float((g32.double() - g64)[keep].abs().max())
+    err = float((g.double() - g64)[keep].abs().max())
+    print(f"point queries: flagged {int(flagged.sum())} of {u.shape[0]}, e = {e:.3e}, kernel {err:.3e}, bound {_bound(e):.3e}, "
+          f"max |grad| {float(g64.abs().max()):.3e}")
+    assert err <= _bound(e)
+    assert f.density_gradient(torch.zeros(0, 3, device=DEV)).shape == (0, 3)
+
+
+def _composite(f, rays, floater=0.0, N_samples=-1, label=""):
+    rays = rays.to(DEV)
+    nrm, acc = f.render_normals(rays, N_samples=N_samples, floater_thresh=floater)
+    _, _, w, acc_w, z = f.render_weights(rays, N_samples=N_samples, floater_thresh=floater)
+    assert nrm.shape == (rays.shape[0], 3) and acc.shape == (rays.shape[0],)
+    assert torch.equal(acc, acc_w)                                      # bit for bit
+    nrm2, acc2 = f.render_normals(rays, N_samples=N_samples, floater_thresh=floater)
+    assert torch.equal(nrm, nrm2) and torch.equal(acc, acc2)            # two calls, the same bits
+    assert torch.isfinite(nrm).all()
+    assert (nrm.norm(dim=-1) <= acc * (1 + 1e-5) + 1e-6).all()          # |N| <= acc
+    c = ray_case(f, rays, z, w)
+    R = rays.shape[0]
+    assert c["excluded"] <= MAX_FLAGGED_RAYS * R, (c["excluded"], R)
+    err = float((nrm.cpu().double() - c["N64"])[c["keep"]].abs().max()) if c["keep"].any() else 0.0
+    shaded = c["shaded"]
+    print(f"{label}: R {R} S {shaded.shape[1]} shaded {int(shaded.sum())} flagged samples {c['flagged_samples']} ties {c['ties']} "
+          f"excluded rays {c['excluded']}, e = {c['e']:.3e}, kernel {err:.3e}, bound {_bound(c['e']):.3e}, "
+          f"max |N| {float(c['N64'].norm(dim=-1).max()):.3e}")
+    assert int(shaded.sum()) > R                                        # more than the forced last sample
+    assert err <= _bound(c["e"])
+    return nrm, acc, c
+
+
+@pytest.mark.parametrize("case", ["softplus", "relu", "alpha_mask", "floater", "three_steps", "one_ray"])
+def test_ray_normals_against_the_oracle(case):
+    rays = test_rays(200, 31)                                           # 200: the last workgroup is partial
+    over = {"fea2denseAct": "relu"} if case in ("relu", "three_steps") else {"alphaMask_thres": 1e-3} if case == "alpha_mask" else {}
+    f = field(DEV, 11, **over)
+    if case == "three_steps":
+        # S = 140: two full 64-sample steps and a partial one.  With every sample shaded a ray would meet a cell boundary
+        # too often for the 2 % cap (about 6e-4 per sample), so the planes are scaled until relu densities end a ray within
+        # some twenty samples: later steps then hold no shaded lane at all, the case the kernel skips.
+        with torch.no_grad():
+            for p in f.density_plane:
+                p.mul_(5.0)
+        f.layout.invalidate()
+    if case == "alpha_mask":
+        f.updateAlphaMask((16, 16, 16))
+        occ = float(f.alphaMask.alpha_volume.mean())
+        assert 0.0 < occ < 1.0, occ                                     # the mask really culls
+    if case == "one_ray":
+        rays = rays[17:18]
+    _composite(f, rays, floater=0.5 if case == "floater" else 0.0, N_samples=420 if case == "three_steps" else -1, label=case)
+
+
+def test_no_rays_no_launch():
+    f = field(DEV, 11)
+    nrm, acc = f.render_normals(torch.zeros(0, 6, device=DEV))
+    assert nrm.shape == (0, 3) and acc.shape == (0,) and nrm.dtype is torch.float32
+
+
+def test_empty_space_gives_exact_zeros():
+    f = field(DEV, 11)
+    with torch.no_grad():
+        for p in list(f.density_plane) + list(f.density_line):
+            p.zero_()
+    f.layout.invalidate()
+    rays = test_rays(130, 41).to(DEV)
+    nrm, acc = f.render_normals(rays)
+    _, _, w, acc_w, _ = f.render_weights(rays)
+    assert torch.equal(acc, acc_w) and torch.isfinite(acc).all()
+    assert torch.isfinite(nrm).all() and (nrm == 0).all()               # a zero gradient: n = 0 / 1e-8, never NaN
+    # a field with structure, rays that meet nothing but their forced last sample far outside: N is that one sample's
+    f2 = field(DEV, 11)
+    far = torch.cat([torch.tensor([[50.0, 60.0, 70.0]]).repeat(4, 1), torch.tensor([[1.0, 0.5, 0.25]]).repeat(4, 1)], -1).to(DEV)
+    nrm2, acc2 = f2.render_normals(far)
+    assert torch.isfinite(nrm2).all() and torch.isfinite(acc2).all()
+
+
+def _two_field_scene():
+    """The golden scene's poses and blending weights over two fields of different grids (20x24x28 and 16^3)."""
+    from novel_views_cases import scene
+    lt, g = scene("cpu")
+    f0 = field("cpu", 51)
+    gen = torch.Generator().manual_seed(52)
+    with torch.no_grad():
+        for p in list(lt.tensorfs[1].density_plane) + list(lt.tensorfs[1].density_line):
+            p.copy_(0.3 * torch.randn(p.shape, generator=gen))
+    lt.tensorfs[0] = f0
+    lt = lt.to(DEV)
+    lt.device = torch.device(DEV)
+    for f in lt.tensorfs:
+        f.to(DEV)
+    return lt, g
+
+
+@pytest.fixture(scope="module")
+def scene_case():
+    lt, g = _two_field_scene()
+    bw = lt._blending_host()
+    both = [v for v in range(bw.shape[0]) if bw[v, 0] > 0 and bw[v, 1] > 0]
+    assert both, "the scene has no frame blended from fields 0 and 1"
+    W, H = 24, 16
+    c2w = lt.get_cam2world().detach()
+    views = [both[0], both[-1], both[0]]
+    poses = c2w[views].clone()
+    poses[2, :, 3] += 0.05                                              # a third, novel pose
+    out = normals.render_normals(lt, poses, W, H, frame_indices=views, chunk=W * H * 3)
+    return lt, poses, views, W, H, out
+
+
+def test_scene_normals_are_the_blend_of_the_fields(scene_case):
+    from localrf_amd.scene_ops import scene_rays
+    lt, poses, views, W, H, out = scene_case
+    assert out["normal"].shape == (3, H, W, 3) and out["acc"].shape == (3, H, W)
+    bw = lt.blending_weights.detach()
+    want_n = torch.zeros(3, H * W, 3, device=DEV)
+    want_a = torch.zeros(3, H * W, device=DEV)
+    ids = torch.arange(H * W, dtype=torch.int64, device=DEV)
+    overlapping = 0
+    for i, v in enumerate(views):
+        active = torch.nonzero(bw[v])[:, 0].tolist()
+        overlapping += len(active) > 1
+        with torch.no_grad():
+            rays, _, _ = scene_rays(ids, poses[i:i + 1], lt._shifts(lt.world2rf, active), lt.focal(W), lt.center(W, H), H * W, W, H)
+        for k, rf in enumerate(active):
+            n_k, a_k = lt.tensorfs[rf].render_normals(rays[k])
+            want_n[i] += bw[v, rf] * n_k
+            want_a[i] += bw[v, rf] * a_k
+    assert overlapping >= 2
+    err_n = float((out["normal"].view(3, -1, 3) - want_n).abs().max())
+    err_a = float((out["acc"].view(3, -1) - want_a).abs().max())
+    print(f"scene: max |normal - blend| {err_n:.3e}, max |acc - blend| {err_a:.3e}, max |N| {float(want_n.norm(dim=-1).max()):.3e}")
+    assert err_n <= 1e-6 and err_a <= 1e-6
+    assert float(want_n.norm(dim=-1).max()) > 1e-3
+
+
+@pytest.mark.parametrize("chunk", [7, 64])
+def test_scene_normals_do_not_depend_on_the_chunk(scene_case, chunk):
+    lt, poses, views, W, H, out = scene_case
+    again = normals.render_normals(lt, poses, W, H, frame_indices=views, chunk=chunk)
+    assert torch.equal(again["normal"], out["normal"]) and torch.equal(again["acc"], out["acc"])
+
+
+def test_encode_normals_bytes(scene_case):
+    out = scene_case[5]
+    n = out["normal"].clone()
+    n[0, 0, :3] = torch.eye(3, device=DEV)
+    n[0, 1, :3] = 0.0
+    got = normals.encode_normals(n).cpu().numpy()
+    ref = encode_normals_host(n.cpu().numpy())
+    assert got.shape == (3, 16, 24, 3) and got.dtype == np.uint8
+    assert got[0, 0, :3].tolist() == [[255, 128, 128], [128, 255, 128], [128, 128, 255]]
+    assert (got[0, 1, :3] == 128).all()
+    # torch's and numpy's fp32 norms may differ in the last bit: a byte may move by one where 255 x sits on a .5 tie
+    assert np.abs(got.astype(int) - ref.astype(int)).max() <= 1 and (got != ref).mean() < 0.01
+
+
+def test_point_cloud_normals(scene_case):
+    lt, poses, views, W, H, out = scene_case
+    kw = dict(poses=poses, frame_indices=views, stride=2, depth_range=(0.0, 1e4))
+    plain = pointcloud.scene_point_cloud(lt, W, H, **kw)
+    assert "normal" not in plain
+    cloud = pointcloud.scene_point_cloud(lt, W, H, normals=True, **kw)
+    for key in ("xyz", "rgb8", "src"):
+        assert torch.equal(cloud[key], plain[key]), key
+    assert cloud["count"] == plain["count"] and cloud["count"] > 0
+    src = cloud["src"].long()
+    at = out["normal"].view(3, H * W, 3)[src[:, 0], src[:, 1]]
+    length = at.norm(dim=-1, keepdim=True)
+    want = at / length.clamp(min=1e-8)
+    assert torch.equal(cloud["normal"], want)
+    nz = length[:, 0] > 0
+    assert nz.any() and float((cloud["normal"][nz].norm(dim=-1) - 1).abs().max()) < 1e-5
+    assert (cloud["normal"][~nz] == 0).all()
+    oriented = pointcloud.scene_point_cloud(lt, W, H, normals=True, orient=True, **kw)
+    t_cam = poses[:, :3, 3][src[:, 0]]
+    facing = ((oriented["xyz"] - t_cam) * oriented["normal"]).sum(-1)
+    assert not (facing > 0).any()
+    assert torch.equal(oriented["normal"].abs(), cloud["normal"].abs()) and torch.equal(oriented["xyz"], plain["xyz"])
