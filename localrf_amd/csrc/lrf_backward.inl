@@ -1730,16 +1730,21 @@ __global__ __launch_bounds__(256) void k_det_convert(DetConv dc, BinGeom bg, con
 
 #include "lrf_train32.inl"
 
+// One tensor group's bin buffers (the density and the appearance scatter run side by side, each on its own set)
+struct BinBufs {
+  uint16_t* tid; int* hist; int* cursor; int* offs; uint32_t* list;
+  unsigned* vmax;            // max|contribution| (k_bwd_ray / k_train_app3), behind hist and cursor in the words k_clear_bins clears
+};
 struct BwdWorkspace {
   Workspace fw;
   float* feat; float* crgb; float* act; float* grd; float* rpart; float* wpart;
   float* depth; float* rgb;
-  uint32_t* rowinfo; uint16_t* tid; int* hist; int* offs; int* cursor; uint32_t* list;
+  uint32_t* rowinfo;
+  BinBufs bins[2];           // density, appearance
   uint32_t* relu_bits;       // [tile][layer 1, 2][lane]: ReLU masks, k_shade3<SAVE> -> k_train_dgrad3, k_wgrad_w2w3
   int4* tileinfo;            // [tile] (ray, j0, count, tile in ray), k_shade3<SAVE> -> k_train_dgrad3, k_train_app3
   float* gen;                // generic engine (lrf_generic.inl): [row][gen_row_ld] operands of the weight gradients, or null
   int* toff32;               // [R + 1] k_shade3's own tile offsets when they do not fit in its LDS (fw.toff holds the 16-row tiles')
-  uint16_t* tid2; int* hist2; int* offs2; int* cursor2; uint32_t* list2;   // bins of the appearance scatter (runs beside the density scatter)
   uint32_t nmax;
   unsigned long long* det_img;   // LRF_FLAG_DETERMINISTIC: int64 image of the density and appearance gradients (k_scatter_det), or null
   long long det_words;           // ... its size in 64-bit words (cleared by k_clear_bins)
@@ -1756,6 +1761,16 @@ static BwdWorkspace carve_bwd(void* ws, int R, int S, const int32_t grid[3], int
   const size_t rows = (size_t)R * b.fw.pmax * 16;
   const size_t nch = WGRAD_MAXCH;
   auto take = [&](size_t nfloat) { float* q = reinterpret_cast<float*>(p + off); off += up256(nfloat * 4); return q; };
+  auto take_bins = [&] {
+    BinBufs B;
+    B.tid = reinterpret_cast<uint16_t*>(take((3 * rows + 1) / 2 + 2));
+    B.hist = reinterpret_cast<int*>(take(BIN_CLEAR_WORDS));       // histogram, then the fill pass's cursors, then max|contribution|: cleared by k_clear_bins
+    B.cursor = B.hist + BIN_MAX;
+    B.vmax = reinterpret_cast<unsigned*>(B.hist + 2 * BIN_MAX);
+    B.offs = reinterpret_cast<int*>(take(2 * (BIN_MAX + 1)));     // entry offsets | cost offsets (k_bin_fill)
+    B.list = reinterpret_cast<uint32_t*>(take(3 * rows));
+    return B;
+  };
   b.feat = take((size_t)R * S);
   b.crgb = take((size_t)R * S * 3);
   b.act = take(rows * ACT_LD);
@@ -1766,19 +1781,11 @@ static BwdWorkspace carve_bwd(void* ws, int R, int S, const int32_t grid[3], int
   b.rgb = take((size_t)R * 3);
   b.nmax = (uint32_t)rows;                                     // rows >= R*S
   b.rowinfo = reinterpret_cast<uint32_t*>(take(rows));
-  b.tid = reinterpret_cast<uint16_t*>(take((3 * rows + 1) / 2 + 2));
-  b.hist = reinterpret_cast<int*>(take(BIN_CLEAR_WORDS));       // histogram, then the fill pass's cursors, then max|contribution| (k_bwd_ray): cleared by k_clear_bins
-  b.cursor = b.hist + BIN_MAX;
-  b.offs = reinterpret_cast<int*>(take(2 * (BIN_MAX + 1)));     // entry offsets | cost offsets (k_bin_fill)
-  b.list = reinterpret_cast<uint32_t*>(take(3 * rows));
+  b.bins[0] = take_bins();
   b.relu_bits = reinterpret_cast<uint32_t*>(take(rows / 16 * 128));
   b.tileinfo = reinterpret_cast<int4*>(take(rows / 16 * 4));
   b.toff32 = reinterpret_cast<int*>(take((size_t)R + 1));
-  b.tid2 = reinterpret_cast<uint16_t*>(take((3 * rows + 1) / 2 + 2));
-  b.hist2 = reinterpret_cast<int*>(take(BIN_CLEAR_WORDS));      // (+ max|contribution| of the appearance scatter, k_train_app3)
-  b.cursor2 = b.hist2 + BIN_MAX;
-  b.offs2 = reinterpret_cast<int*>(take(2 * (BIN_MAX + 1)));
-  b.list2 = reinterpret_cast<uint32_t*>(take(3 * rows));
+  b.bins[1] = take_bins();
   b.gen = gen_ld ? take(rows * (size_t)gen_ld) : nullptr;
   b.det_img = nullptr; b.det_words = 0; b.det_d = DetDst{}; b.det_a = DetDst{};
   if (det) {
@@ -1833,6 +1840,18 @@ static int field_gen_ld(int fea_pe, int view_pe, int fc, uint32_t flags) {
   fc = fc ? fc : LRF_FEATC;
   return (gen_is_default(fea_pe, view_pe, fc) && !(flags & LRF_FLAG_MLP_VALU)) ? 0 : gen_row_ld(gen_cfg(fea_pe, view_pe, fc, true));
 }
+// What lrf_render_fwd_train and lrf_render_bwd refuse alike, under the caller's name: null, or why.  have_all: no pointer
+// argument is null (f->cache included); refused: flag bits this entry point has no engine for.
+static const char* check_train_call(const char* who, bool have_all, const LrfField* f, int32_t R, int32_t S, uint32_t flags, uint32_t refused = 0) {
+  static thread_local char msg[256];
+  const char* bad = !have_all ? "null argument"
+                  : (R <= 0 || S < 2 || S > LRF_MAX_S_TRAIN) ? "need R > 0 and 2 <= S <= LRF_MAX_S_TRAIN (2048: the per-ray backward keeps 16 B per sample in LDS)"
+                  : (flags & refused) ? "the row-saving forward runs the split-bf16 engine only"
+                  : (flags & ~LRF_FLAG_ALL) ? "unknown flag bits" : nullptr;
+  if (!bad) return gen_check(f);
+  snprintf(msg, sizeof(msg), "%s: %s", who, bad);
+  return msg;
+}
 }  // namespace lrf
 extern "C" size_t lrf_workspace_bytes_bwd(int32_t R, int32_t S, const int32_t grid[3]) {
   return lrf::carve_bwd(nullptr, R, S, grid).bytes;
@@ -1855,13 +1874,8 @@ extern "C" void lrf_workspace_layout_bwd(int32_t R, int32_t S, const int32_t gri
 extern "C" int lrf_render_fwd_train(const LrfField* f, const float* rays, const float* z, int32_t R, int32_t S,
                                     uint32_t flags, float* rgb, float* depth, void* workspace, void* stream) {
   using namespace lrf;
-  if (!f || !f->cache || !rays || !z || !rgb || !depth || !workspace) return set_err("lrf_render_fwd_train: null argument");
-  if (R <= 0 || S < 2 || S > LRF_MAX_S_TRAIN)
-    return set_err("lrf_render_fwd_train: need R > 0 and 2 <= S <= LRF_MAX_S_TRAIN (2048: the per-ray backward keeps 16 B per sample in LDS)");
-  if (flags & (LRF_FLAG_MLP_VALU | LRF_FLAG_MLP_F32))
-    return set_err("lrf_render_fwd_train: the row-saving forward runs the split-bf16 engine only");
-  if (flags & ~LRF_FLAG_ALL) return set_err("lrf_render_fwd_train: unknown flag bits");
-  if (const char* bad = gen_check(f)) return set_err(bad);
+  if (const char* bad = check_train_call("lrf_render_fwd_train", f && f->cache && rays && z && rgb && depth && workspace, f, R, S, flags,
+                                         LRF_FLAG_MLP_VALU | LRF_FLAG_MLP_F32)) return set_err(bad);
   LRF_HIP(lds_opt_in());
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   DField d = make_dfield(f);
@@ -1876,10 +1890,28 @@ extern "C" int lrf_render_fwd_train(const LrfField* f, const float* rays, const 
 }
 
 namespace lrf {
-enum class DensEng { Det, Fix, CasFused, CasSplit };               // density scatter: int64 image, fixed point, compare-and-swap (lines fused / apart)
-enum class AppEng { Det8, Det4, Fix8, Fix4, CasFused, CasSplit };  // appearance scatter: the same, 8 or 4 channels per sweep of the first two
-// Everything lrf_render_bwd decides before its first launch
+enum class ScatterEng { Det, Fix, CasFused, CasSplit };   // int64 image, fixed point, compare-and-swap (lines fused / apart)
+// What one tensor group (density / appearance) scatters with, into what
+struct ScatterGroup {
+  ScatterEng eng;
+  int ch;                    // Det / Fix: channels per sweep, 8 or (appearance only) 4
+  size_t lds, line_lds;      // dynamic LDS of the scatter kernel (CasSplit: the plane kernel) and of k_scatter_line
+  BinBufs bins;
+  ScatterDst dst;            // the reference-layout gradients: the scatter kernels add straight into them
+  DetDst det;                // Det: the group's part of the int64 image
+  bool fixed_point() const { return eng == ScatterEng::Det || eng == ScatterEng::Fix; }
+};
+static ScatterGroup scatter_group(ScatterEng eng, int ch, size_t lds_fix, size_t lds_plane, size_t lds_line, const BinBufs& bins,
+                                  float* const* g_plane, float* const* g_line, const DetDst& det) {
+  ScatterGroup G{eng, ch, 0, lds_line, bins, ScatterDst{}, det};
+  G.lds = G.fixed_point() ? lds_fix : eng == ScatterEng::CasFused ? lds_plane + lds_line : lds_plane;
+  for (int q = 0; q < 3; ++q) { G.dst.plane[q] = g_plane[q]; G.dst.line[q] = g_line[q]; }
+  return G;
+}
+// Everything lrf_render_bwd decides before its first launch, and the arguments its stages read
 struct BwdPlan {
+  const LrfParams* p; const float* rays; const float* z; int R, S; uint32_t flags;   // rays: what the kernels read (k_sort_rays' copy where it sorted)
+  const float* g_rgb; const float* g_depth; const LrfGrads* g; float* g_rays;
   DField d;                  // (d.rdir: per-ray unit directions, written by k_march, read by k_scatter_fix)
   Layout L;
   BinGeom bg;
@@ -1887,20 +1919,21 @@ struct BwdPlan {
   GenCfg gc;
   int gen_ld;                // generic engine: floats per row of weight-gradient operands, else 0
   bool generic, det, sort;   // sort: the kernels read the rays k_sort_rays left in the workspace
-  DensEng dens; size_t dens_lds, dens_line_lds;   // dynamic LDS of the scatter kernel (CasSplit: plane kernel, then line kernel)
-  AppEng app; size_t app_lds, app_line_lds;
-  bool app3_fix;             // k_train_app3<8, true>: also max|contribution| for the fixed-point appearance scatter
+  ScatterGroup dens, app;    // (app.fixed_point(): k_train_app3<8, true> also leaves max|contribution|)
   int npass, nblk;
+  int cus, nwg_scatter;      // nwg_scatter: workgroups of the binned scatter kernels (lrf_debug_set_scatter_wgs, else one per CU)
+  int n_dgrad_wg;            // one dW1 / dbasis partial block per workgroup (k_wgrad_reduce: fixed count)
+  int nch_max;               // k_wgrad_w2w3's grid (blocks behind the last chunk of the actual row count return at once)
 };
 
-// Every refusal of lrf_render_bwd, and its engines, workspace carve and grids: host arithmetic only, no HIP call.
+// Every refusal of lrf_render_bwd, and its engines, workspace carve and grids: host arithmetic only, no launch (device_cus
+// is a cached property lookup).
 static const char* plan_bwd(BwdPlan& P, const LrfField* f, const LrfParams* p, const float* rays, const float* z, int32_t R, int32_t S,
-                            uint32_t flags, const float* g_rgb, const float* g_depth, const LrfGrads* g, const float* g_rays, void* workspace) {
-  if (!f || !f->cache || !p || !rays || !z || !g_rgb || !g_depth || !g || !g_rays || !workspace) return "lrf_render_bwd: null argument";
-  if (R <= 0 || S < 2 || S > LRF_MAX_S_TRAIN)
-    return "lrf_render_bwd: need R > 0 and 2 <= S <= LRF_MAX_S_TRAIN (2048: the per-ray backward keeps 16 B per sample in LDS)";
-  if (flags & ~LRF_FLAG_ALL) return "lrf_render_bwd: unknown flag bits";
-  if (const char* bad = gen_check(f)) return bad;
+                            uint32_t flags, const float* g_rgb, const float* g_depth, const LrfGrads* g, float* g_rays, void* workspace) {
+  if (const char* bad = check_train_call("lrf_render_bwd", f && f->cache && p && rays && z && g_rgb && g_depth && g && g_rays && workspace, f, R, S, flags))
+    return bad;
+  P.p = p; P.rays = rays; P.z = z; P.R = R; P.S = S; P.flags = flags;
+  P.g_rgb = g_rgb; P.g_depth = g_depth; P.g = g; P.g_rays = g_rays;
   P.gen_ld = field_gen_ld(f->fea_pe, f->view_pe, f->feature_c, flags);
   P.generic = P.gen_ld != 0;
   P.det = (flags & LRF_FLAG_DETERMINISTIC) != 0;
@@ -1926,28 +1959,27 @@ static const char* plan_bwd(BwdPlan& P, const LrfField* f, const LrfParams* p, c
   // ... and with FOUR channels per sweep (six sweeps, a 34.8 KB tile) where only that leaves room for the lines: 480 .. 640 cells
   const size_t lds_fa4 = lds_dp + sizeof(unsigned long long) * LRF_CA * ll_max;
   const bool fit_a8 = fit_d && lds_fa <= 158 * 1024, fit_a4 = fit_d && lds_fa4 <= 158 * 1024;
+  ScatterEng dens, app;
+  int app_ch = 8;
   if (P.det) {
     // LRF_FLAG_DETERMINISTIC: always the fixed-point kernels (whatever the debug switches say); lines that leave no room for them
     // in LDS (density: > 1439 cells, appearance: > 640 cells -- the reference ends at 640^3) are refused
     if (!fit_a8 && !fit_a4)
       return "lrf_render_bwd: LRF_FLAG_DETERMINISTIC covers lines up to 640 cells (the fixed-point line accumulators of the "
              "appearance scatter must fit in LDS)";
-    P.dens = DensEng::Det;
-    P.app = fit_a8 ? AppEng::Det8 : AppEng::Det4;
+    dens = app = ScatterEng::Det;
+    app_ch = fit_a8 ? 8 : 4;
   } else {
     const bool fix_d = g_scatter_fix && g_scatter_fused && fit_d, fix_a = fix_d && (g_scatter_fix & 2);
-    P.dens = fix_d ? DensEng::Fix : (g_scatter_fused && lds_dp + lds_dl <= 64 * 1024) ? DensEng::CasFused : DensEng::CasSplit;
-    P.app = (fix_a && fit_a8) ? AppEng::Fix8 : (fix_a && !(g_scatter_fix & 4) && fit_a4) ? AppEng::Fix4
-          : (g_scatter_fused && lds_ap + lds_al <= 158 * 1024) ? AppEng::CasFused : AppEng::CasSplit;
+    dens = fix_d ? ScatterEng::Fix : (g_scatter_fused && lds_dp + lds_dl <= 64 * 1024) ? ScatterEng::CasFused : ScatterEng::CasSplit;
+    const bool fix_a8 = fix_a && fit_a8, fix_a4 = !fix_a8 && fix_a && !(g_scatter_fix & 4) && fit_a4;
+    app = (fix_a8 || fix_a4) ? ScatterEng::Fix : (g_scatter_fused && lds_ap + lds_al <= 158 * 1024) ? ScatterEng::CasFused : ScatterEng::CasSplit;
+    app_ch = fix_a4 ? 4 : 8;
   }
-  P.dens_lds = (P.dens == DensEng::Det || P.dens == DensEng::Fix) ? 2 * (lds_dp + lds_dl) : P.dens == DensEng::CasFused ? lds_dp + lds_dl : lds_dp;
-  P.dens_line_lds = lds_dl;
-  P.app_lds = (P.app == AppEng::Det8 || P.app == AppEng::Fix8) ? lds_fa : (P.app == AppEng::Det4 || P.app == AppEng::Fix4) ? lds_fa4
-            : P.app == AppEng::CasFused ? lds_ap + lds_al : lds_ap;
-  P.app_line_lds = lds_al;
-  P.app3_fix = P.app != AppEng::CasFused && P.app != AppEng::CasSplit;
 
   P.b = carve_bwd(workspace, R, S, f->grid, P.gen_ld, P.det);
+  P.dens = scatter_group(dens, 8, 2 * (lds_dp + lds_dl), lds_dp, lds_dl, P.b.bins[0], g->density_plane, g->density_line, P.b.det_d);
+  P.app = scatter_group(app, app_ch, app_ch == 8 ? lds_fa : lds_fa4, lds_ap, lds_al, P.b.bins[1], g->app_plane, g->app_line, P.b.det_a);
   P.nblk = (int)((P.b.nmax + BIN_CHUNK - 1) / BIN_CHUNK);
   // LRF_FLAG_PLANE_EVENTS (data parallel): one pass per plane, an event behind planes 0 and 1 -- a collective over plane p's
   // gradient (8.6 MB each at 300^3) starts while the later planes are still being scattered; otherwise one pass over all bins
@@ -1956,11 +1988,177 @@ static const char* plan_bwd(BwdPlan& P, const LrfField* f, const LrfParams* p, c
   P.d = make_dfield(f);
   P.d.rdir = P.b.fw.rdir;
   P.gc = gen_cfg(P.d.fea_pe, P.d.view_pe, P.d.fc, !(flags & LRF_FLAG_PE_OFF));
+  P.cus = device_cus();
+  P.nwg_scatter = g_scatter_wgs > 0 ? g_scatter_wgs : P.cus;
+  P.n_dgrad_wg = min(P.cus, WGRAD_MAXCH);
+  P.nch_max = WGRAD_MAXCH;
   return nullptr;
+}
+
+// What differs between the two groups' launches of k_scatter_plane (FIX_NT, of the fixed-point kernels, is one constant)
+template <bool APP> struct ScatterTraits;
+template <> struct ScatterTraits<false> { static constexpr int PLANE_NT = 512, PLANE_MULT = LRF_DPLANE_MULT; };
+template <> struct ScatterTraits<true> { static constexpr int PLANE_NT = LRF_APP_NT, PLANE_MULT = 1; };
+
+// One pass of group G's scatter over bins [bin_lo, bin_hi), which hold planes [plane_lo, plane_hi).  Det: the pass ends in
+// k_det_convert over those planes and their lines; CasSplit: the planes only (launch_scatter_lines behind the last pass).
+template <int C, bool APP>
+static void launch_scatter_pass(const BwdPlan& P, const ScatterGroup& G, int bin_lo, int bin_hi, int plane_lo, int plane_hi, hipStream_t s) {
+  using T = ScatterTraits<APP>;
+  const BwdWorkspace& b = P.b;
+  const BinBufs& B = G.bins;
+  switch (G.eng) {
+    case ScatterEng::Det: {
+      auto k = k_scatter_det<C, APP, FIX_NT>;
+      if constexpr (APP) { if (G.ch == 4) k = k_scatter_det<C, APP, FIX_NT, 4>; }
+      hipLaunchKernelGGL(k, dim3(P.nwg_scatter), dim3(FIX_NT), G.lds, s,
+                         P.d, P.bg, G.det, P.rays, P.z, P.S, B.offs, B.list, b.feat, b.rowinfo, b.grd, B.vmax, bin_lo, bin_hi);
+      DetConv dc;
+      for (int q = 0; q < 3; ++q) {
+        dc.img[q] = G.det.plane[q]; dc.g[q] = G.dst.plane[q]; dc.n[q] = (long long)C * P.L.pw[q] * P.L.ph[q];
+        dc.img[3 + q] = G.det.line[q]; dc.g[3 + q] = G.dst.line[q]; dc.n[3 + q] = (long long)C * P.L.ll[q];
+      }
+      hipLaunchKernelGGL(k_det_convert, dim3(P.cus * 8), dim3(256), 0, s, dc, P.bg, B.offs, B.vmax, plane_lo, plane_hi);
+      break;
+    }
+    case ScatterEng::Fix: {
+      auto k = k_scatter_fix<C, APP, FIX_NT>;
+      if constexpr (APP) { if (G.ch == 4) k = k_scatter_fix<C, APP, FIX_NT, 4>; }
+      hipLaunchKernelGGL(k, dim3(P.nwg_scatter), dim3(FIX_NT), G.lds, s,
+                         P.d, P.bg, G.dst, P.rays, P.z, P.S, B.offs, B.list, b.feat, b.rowinfo, b.grd, B.vmax, bin_lo, bin_hi);
+      break;
+    }
+    case ScatterEng::CasFused:
+    case ScatterEng::CasSplit: {
+      auto k = G.eng == ScatterEng::CasFused ? k_scatter_plane<C, APP, T::PLANE_NT, true> : k_scatter_plane<C, APP, T::PLANE_NT, false>;
+      hipLaunchKernelGGL(k, dim3(P.nwg_scatter * T::PLANE_MULT), dim3(T::PLANE_NT), G.lds, s,
+                         P.d, P.bg, G.dst, P.rays, P.z, P.S, B.offs, B.list, b.feat, b.rowinfo, b.grd, bin_lo, bin_hi);
+      break;
+    }
+  }
+}
+// CasSplit, behind the group's last pass: the lines (no bins: every workgroup walks its slice of the rows)
+template <int C, bool APP>
+static void launch_scatter_lines(const BwdPlan& P, const ScatterGroup& G, hipStream_t s) {
+  if (G.eng != ScatterEng::CasSplit) return;
+  hipLaunchKernelGGL((k_scatter_line<C, APP, 1024>), dim3(3 * LINE_WGS), dim3(1024), G.line_lds, s,
+                     P.d, G.dst, P.rays, P.z, P.R, P.S, P.b.fw.toff, P.b.feat, P.b.rowinfo, P.b.grd);
+}
+
+// ---- The stages of lrf_render_bwd: each enqueues on the stream it is given; which stream, and behind which event, is the driver's
+
+// The saved rows of the forward: lrf_render_fwd_train left them (LRF_FLAG_ROWS_SAVED; it sorted, or not, with the same flags:
+// same workspace), or the same launches once more.  Sets the rays (and permutation) every later stage reads.
+static int bwd_forward_rows(BwdPlan& P, hipStream_t s) {
+  const BwdWorkspace& b = P.b; const Workspace& w = b.fw;
+  if (P.flags & LRF_FLAG_ROWS_SAVED) { if (P.sort) { P.d.perm = w.perm; P.rays = w.rays_s; } return 0; }
+  P.rays = sort_rays_if_asked(P.d, P.rays, P.R, P.flags, w, s);
+  launch_march(P.d, P.rays, P.z, P.R, P.S, P.flags, 0.0f, b.depth, w.acc, nullptr, w.ncomp, w.cidx, w.cw, b.feat, s);
+  LRF_HIP(launch_shade_save(P.d, P.rays, P.z, P.S, P.R, P.flags, w, b, b.rgb, s));
+  return 0;
+}
+// Both groups' histograms, cursors and maxima, with the caller's zero range; deterministic: once more with the int64 image
+static void bwd_clear(const BwdPlan& P, hipStream_t s) {
+  auto clear = [&](void* base, long long f4) {
+    hipLaunchKernelGGL(k_clear_bins, dim3((unsigned)(BIN_CLEAR_BLOCKS + (f4 + ZERO_F4_PER_BLOCK - 1) / ZERO_F4_PER_BLOCK)), dim3(256), 0, s,
+                       P.b.bins[0].hist, P.b.bins[1].hist, reinterpret_cast<float4*>(base), f4);
+  };
+  clear(P.g->zero_base, P.g->zero_floats / 4);
+  if (P.det) clear(P.b.det_img, P.b.det_words / 2);        // (its bins part again)
+}
+// Data gradient of the colour network: go / dfeat / dz1 rows [+ dW1 partials]
+static void bwd_dgrad(const BwdPlan& P, hipStream_t s) {
+  const BwdWorkspace& b = P.b; const Workspace& w = b.fw;
+  if (P.generic) {     // lrf_generic.inl: one lane per row; worst-case grid, rows behind the batch's last tile return at once
+    const int ls = gen_tile_samples(P.gc, true), nt = gen_block_threads(P.gc);
+    const size_t lds = (size_t)gen_lds(P.gc, ls, true).total * 4;
+    const dim3 grid((unsigned)((b.nmax + ls - 1) / ls));
+    auto k = ls == 32 ? k_gen_dgrad<32> : k_gen_dgrad<16>;
+    hipLaunchKernelGGL(k, grid, dim3(nt), lds, s, P.d, P.gc, P.rays, P.S, w.toff, P.R, b.tileinfo, w.cidx, w.cw, b.crgb, P.g_rgb, b.act, b.grd, b.rowinfo, b.gen, P.gen_ld);
+  } else {
+    hipLaunchKernelGGL((k_train_dgrad3<8>), dim3(P.n_dgrad_wg), dim3(512), (size_t)W32T_ALL_U4 * 16 + 4 * 64 * 16, s, P.d,
+                       P.d.mlpwt, P.rays, P.S, w.toff, P.R, b.tileinfo, w.cidx, w.cw, b.crgb, P.g_rgb,
+                       b.grd, b.rowinfo, b.relu_bits, b.act, b.wpart, g_dgrad_dbg & 5);
+  }
+}
+// Its appearance half: dX, position gradient, dbasis partials; tags and counts the appearance bins
+static void bwd_app3(const BwdPlan& P, hipStream_t s) {
+  const BwdWorkspace& b = P.b; const Workspace& w = b.fw;
+  const BinBufs& B = P.app.bins;
+  auto k = P.app.fixed_point() ? k_train_app3<8, true> : k_train_app3<8, false>;      // true: also max|contribution|
+  hipLaunchKernelGGL(k, dim3(P.n_dgrad_wg), dim3(512), app3_lds_bytes(P.S, 8, P.bg.total), s, P.d,
+                     P.d.mlpwt, P.rays, P.z, P.S, w.toff, P.R, b.tileinfo, w.cidx,
+                     b.grd, b.rpart, w.pmax, b.wpart, P.bg, B.tid, B.hist, b.nmax, g_dgrad_dbg & 3, B.vmax);
+}
+// Fill group G's bins from its tags and counts
+static void bwd_bin_fill(const BwdPlan& P, const ScatterGroup& G, int group, hipStream_t s) {
+  const BinBufs& B = G.bins;
+  hipLaunchKernelGGL(k_bin_fill, dim3(P.nblk), dim3(256), 0, s, P.bg, P.b.nmax, P.R, P.S, P.b.fw.toff, group, B.tid, B.hist, B.cursor, B.offs, B.list);
+}
+// Per-ray backward (tags and counts the density bins), then the density scatter
+static void bwd_ray_density(const BwdPlan& P, hipStream_t s) {
+  const BwdWorkspace& b = P.b; const Workspace& w = b.fw;
+  const BinBufs& B = P.dens.bins;
+  hipLaunchKernelGGL(k_bwd_ray, dim3((P.R + 3) / 4), dim3(256), (size_t)14 * P.S * sizeof(float) + (size_t)P.bg.total * sizeof(int), s,
+                     P.d, P.rays, P.z, P.R, P.S, P.flags, b.feat, w.ncomp, w.cidx, b.crgb, P.g_rgb, P.g_depth,
+                     (const float*)nullptr, w.pmax, P.g_rays, P.bg, B.tid, B.hist, b.nmax, B.vmax);
+  bwd_bin_fill(P, P.dens, 0, s);
+  launch_scatter_pass<LRF_CD, false>(P, P.dens, 0, P.bg.total, 0, 3, s);
+  launch_scatter_lines<LRF_CD, false>(P, P.dens, s);
+}
+// dW2 / dW3 [generic: every weight gradient, added straight into the reference-layout gradients] (row reads, matrix pipe)
+static void bwd_wgrad(const BwdPlan& P, hipStream_t s) {
+  const BwdWorkspace& b = P.b; const Workspace& w = b.fw;
+  const LrfGrads* g = P.g;
+  if (P.generic) {     // dW = A^T B over the operand rows k_gen_dgrad left
+    const GenCfg& gc = P.gc;
+    const GenRowOff ro = gen_row_off(gc);
+    const int nchunk = (int)((b.nmax + GEN_GEMM_CHUNK - 1) / GEN_GEMM_CHUNK);
+    auto gemm = [&](int offA, int M, int offB, int N, float* dW, int ldw, float* db) {
+      hipLaunchKernelGGL(k_gen_gemm, dim3(((M + 63) / 64) * ((N + 63) / 64), nchunk), dim3(256), 0, s,
+                         b.gen, P.gen_ld, offA, M, offB, N, w.toff, P.R, dW, ldw, db);
+    };
+    gemm(ro.dz1, gc.fc, ro.x1, gc.in1 + 1, g->w1, gc.in1, g->b1);
+    gemm(ro.dz2, gc.fc, ro.h1, gc.fc + 1, g->w2, gc.fc, g->b2);
+    gemm(ro.go, 3, ro.h2v, gc.fc + gc.inv + 1, g->w3, gc.fc + gc.inv, g->b3);
+  } else {
+    auto k = g_wgrad_kt == 64 ? k_wgrad_w2w3<64> : k_wgrad_w2w3<128>;
+    hipLaunchKernelGGL(k, dim3(P.nch_max), dim3(512), w23_lds(g_wgrad_kt == 64 ? 64 : 128), s, P.d.mlpb, b.act + 16 * ACT_FEAT, ACT_LD, b.grd + 16 * GRD_GO, GRD_LD,
+                       b.relu_bits, P.p->w3, P.p->w2, P.p->b2, w.toff, P.R, b.wpart);
+  }
+}
+// The partial blocks of the three kernels above -> the network gradients, in a fixed order
+static void bwd_wgrad_reduce(const BwdPlan& P, hipStream_t s) {
+  const LrfGrads* g = P.g;
+  WgradSegs segs;
+  for (int q = 0; q < 7; ++q) segs.s[q] = WgradSeg{0, 1, 0, 0, 1, 1, 0x7fffffff, 0, 0, nullptr};    // unused slots: behind every element
+  int nseg = 0, elems = 0;
+  auto seg = [&](int off, int ld, int n_off, int m, int n, float* dst, int dst_ld, int x_slots = 0, int nch = 0) {
+    segs.s[nseg++] = WgradSeg{off, ld, n_off, m, n, dst_ld, elems, x_slots, nch, dst};
+    elems += m * n;
+  };
+  if (!P.generic) {
+    seg(WP_W2, 144, 0, 128, 128, g->w2, 128);
+    seg(WP_W2, 144, 128, 128, 1, g->b2, 1);
+    seg(WP_W1, 32, 0, 128, LRF_APP_DIM, g->w1, LRF_APP_DIM, 0, P.n_dgrad_wg);     // accumulated by k_train_dgrad3: one block per workgroup
+    seg(WP_W1, 32, LRF_APP_DIM, 128, 1, g->b1, 1, 0, P.n_dgrad_wg);
+  }
+  seg(WP_BAS, 96, 0, LRF_APP_DIM, 72, g->basis, 72, 1, P.n_dgrad_wg);   // accumulated by k_train_app3: one block per workgroup
+  if (!P.generic) {
+    seg(WP_W3, 144, 0, 3, LRF_FEATC + 3, g->w3, LRF_FEATC + 3);
+    seg(WP_W3, 144, LRF_FEATC + 3, 3, 1, g->b3, 1);
+  }
+  segs.total_elems = elems;
+  hipLaunchKernelGGL(k_wgrad_reduce, dim3((elems * 16 + 255) / 256), dim3(256), 0, s, P.b.wpart, P.b.fw.toff, P.R, segs);
+}
+// The appearance lookups' position gradients (k_train_app3's ray partials) -> d/d(rays)
+static void bwd_rays_add(const BwdPlan& P, hipStream_t s) {
+  const Workspace& w = P.b.fw;
+  hipLaunchKernelGGL(k_rays_add_rpart, dim3((P.R + 255) / 256), dim3(256), 0, s, P.rays, P.R, w.ncomp, P.b.rpart, w.pmax, P.g_rays, P.d.perm);
 }
 }  // namespace lrf
 
-// plan_bwd, then the launches: a refused call enqueues nothing
+// plan_bwd, then the schedule: which stage, on which stream, behind which event.  A refused call enqueues nothing.
 extern "C" int lrf_render_bwd(const LrfField* f, const LrfParams* p, const float* rays, const float* z,
                               int32_t R, int32_t S, uint32_t flags, const float* g_rgb, const float* g_depth,
                               const LrfGrads* g, float* g_rays, void* workspace, void* stream) {
@@ -1969,21 +2167,7 @@ extern "C" int lrf_render_bwd(const LrfField* f, const LrfParams* p, const float
   if (const char* bad = plan_bwd(P, f, p, rays, z, R, S, flags, g_rgb, g_depth, g, g_rays, workspace)) return set_err(bad);
   LRF_HIP(lds_opt_in());
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  DField d = P.d;
-  const Layout& L = P.L;
-  const BinGeom& bg = P.bg;
-  const BwdWorkspace& b = P.b;
-  const Workspace& w = b.fw;
-  const GenCfg& gc = P.gc;
-  const int cus = device_cus();
-  const int nwg_scatter = g_scatter_wgs > 0 ? g_scatter_wgs : cus;
-  if (flags & LRF_FLAG_ROWS_SAVED) {                       // lrf_render_fwd_train sorted (or not) with the same flags: same workspace
-    if (P.sort) { d.perm = w.perm; rays = w.rays_s; }
-  } else {                                                 // otherwise lrf_render_fwd_train left all of this in place
-    rays = sort_rays_if_asked(d, rays, R, flags, w, st);
-    launch_march(d, rays, z, R, S, flags, 0.0f, b.depth, w.acc, nullptr, w.ncomp, w.cidx, w.cw, b.feat, st);
-    LRF_HIP(launch_shade_save(d, rays, z, S, R, flags, w, b, b.rgb, st));
-  }
+  LRF_TRY(bwd_forward_rows(P, st));
   // The backward runs as two branches that share no outputs (g_bwd_overlap, default on):
   //   caller's stream: k_train_dgrad3 -> k_train_app3 [-> k_wgrad_w2w3] -> appearance bins + scatter   [-> join] -> ray partials
   //   side stream:     k_bwd_ray -> density bins + scatter [-> (go / dfeat rows there) k_wgrad_w2w3] -> (partials there) reduce
@@ -1992,198 +2176,41 @@ extern "C" int lrf_render_bwd(const LrfField* f, const LrfParams* p, const float
   // k_bwd_ray and the density scatter need nothing from the data-gradient kernel (the appearance lookups' position
   // gradients it produces are added to d/d(rays) afterwards by k_rays_add_rpart), so the texture / LDS-atomic bound
   // per-ray work runs under the row-traffic bound colour-network backward instead of behind it.
-  SideStream* sx = side_stream();                          // also holds the bucket events of lrf_render_bwd_wait
   // Under stream capture the two branches go on ONE stream: ROCm runs the branches of a graph one after the other anyway
   // (DESIGN.md s4e), and every cross-stream edge of the captured fork / join costs ~10 us of idle time in the replay (four of
-  // them per backward: profiles/r18_graph_iteration_timeline.md).
-  hipStreamCaptureStatus cap_status = hipStreamCaptureStatusNone;
-  (void)hipStreamIsCapturing(st, &cap_status);
-  const bool capturing = cap_status == hipStreamCaptureStatusActive;
-  SideStream* ss = (g_bwd_overlap && !capturing) ? sx : nullptr;
-  // the side stream and its fork / join events are per device: host threads that enqueue backward passes on the same
-  // device take turns (enqueueing is ~0.3 ms of host time; the kernels themselves still overlap on the GPU)
-  std::unique_lock<std::mutex> side_lock;
-  if (sx) side_lock = std::unique_lock<std::mutex>(sx->mu);
-  // the scatter kernels add straight into the reference-layout gradients: the density tensors are final as soon as the
-  // per-ray branch is through (bucket 0), the appearance tensors at the very end (bucket 2)
-  ScatterDst dst_d, dst_a;
-  for (int q = 0; q < 3; ++q) {
-    dst_d.plane[q] = g->density_plane[q]; dst_d.line[q] = g->density_line[q];
-    dst_a.plane[q] = g->app_plane[q]; dst_a.line[q] = g->app_line[q];
-  }
-  {
-    const long long zf4 = g->zero_floats / 4;
-    const unsigned nblk_clear = (unsigned)(BIN_CLEAR_BLOCKS + (zf4 + ZERO_F4_PER_BLOCK - 1) / ZERO_F4_PER_BLOCK);
-    hipLaunchKernelGGL(k_clear_bins, dim3(nblk_clear), dim3(256), 0, st, b.hist, b.hist2, reinterpret_cast<float4*>(g->zero_base), zf4);     // (in front of the fork: both branches count into these)
-    if (P.det) {                                           // the int64 gradient image: the same kernel once more (its bins part again)
-      const long long if4 = b.det_words / 2;
-      hipLaunchKernelGGL(k_clear_bins, dim3((unsigned)(BIN_CLEAR_BLOCKS + (if4 + ZERO_F4_PER_BLOCK - 1) / ZERO_F4_PER_BLOCK)), dim3(256), 0, st,
-                         b.hist, b.hist2, reinterpret_cast<float4*>(b.det_img), if4);
-    }
-  }
-  hipStream_t sb = st;
-  if (ss) {
-    LRF_HIP(hipEventRecord(ss->fork, st));
-    LRF_HIP(hipStreamWaitEvent(ss->s, ss->fork, 0));
-    sb = ss->s;
-  }
+  // them per backward: profiles/r18_graph_iteration_timeline.md).  TwoStreams decides; on one stream side() is the caller's
+  // stream and fork / join / signal / wait do nothing, while the bucket events of lrf_render_bwd_wait are recorded all the same.
+  TwoStreams ts(st);
+  hipStream_t sb = ts.side();
+  // dW2 / dW3: on the caller's stream behind the appearance kernel (g_wgrad_split > 0), or on the side stream behind the
+  // density scatter once the go / dfeat rows are there (g_wgrad_split == 0)
+  const bool w23_on_st = !ts.overlapping() || g_wgrad_split > 0;
 
-  // ---- caller's stream: data gradient of the colour network, then its appearance half (dX, position gradient, dbasis)
-  const int n_dgrad_wg = min(cus, WGRAD_MAXCH);            // one dW1 / dbasis partial block per workgroup (k_wgrad_reduce: fixed count)
-  if (P.generic) {     // lrf_generic.inl: one lane per row; worst-case grid, rows behind the batch's last tile return at once
-    const int ls = gen_tile_samples(gc, true), nt = gen_block_threads(gc);
-    const size_t lds = (size_t)gen_lds(gc, ls, true).total * 4;
-    const dim3 grid((unsigned)((b.nmax + ls - 1) / ls));
-    if (ls == 32) hipLaunchKernelGGL(k_gen_dgrad<32>, grid, dim3(nt), lds, st, d, gc, rays, S, w.toff, R, b.tileinfo, w.cidx, w.cw, b.crgb, g_rgb, b.act, b.grd, b.rowinfo, b.gen, P.gen_ld);
-    else          hipLaunchKernelGGL(k_gen_dgrad<16>, grid, dim3(nt), lds, st, d, gc, rays, S, w.toff, R, b.tileinfo, w.cidx, w.cw, b.crgb, g_rgb, b.act, b.grd, b.rowinfo, b.gen, P.gen_ld);
-  } else {
-    hipLaunchKernelGGL((k_train_dgrad3<8>), dim3(n_dgrad_wg), dim3(512), (size_t)W32T_ALL_U4 * 16 + 4 * 64 * 16, st, d,
-                       d.mlpwt, rays, S, w.toff, R, b.tileinfo, w.cidx, w.cw, b.crgb, g_rgb,
-                       b.grd, b.rowinfo, b.relu_bits, b.act, b.wpart, g_dgrad_dbg & 5);
+  bwd_clear(P, st);                                        // (in front of the fork: both branches count into these)
+  LRF_TRY(ts.fork());
+  bwd_dgrad(P, st);
+  LRF_TRY(ts.signal(0, st));                               // go / dfeat rows: the weight-gradient kernel may start
+  bwd_app3(P, st);
+  bwd_ray_density(P, sb);
+  LRF_TRY(ts.bucket(0, sb));                               // the density tensors are final as soon as the per-ray branch is through
+  if (!w23_on_st) LRF_TRY(ts.wait(0, sb));
+  bwd_wgrad(P, w23_on_st ? st : sb);
+  LRF_TRY(ts.signal(1, st));                               // the caller's-stream partials (dW1, dbasis[, dW2, dW3]) are complete behind this
+  LRF_TRY(ts.wait(1, sb));
+  bwd_wgrad_reduce(P, sb);
+  LRF_TRY(ts.bucket(1, sb));
+  bwd_bin_fill(P, P.app, 1, st);                           // (its own bin buffers: the density scatter may still be running)
+  for (int q = 0; q < P.npass; ++q) {                      // every bin, or (LRF_FLAG_PLANE_EVENTS) plane q's
+    if (P.npass == 1) launch_scatter_pass<LRF_CA, true>(P, P.app, 0, P.bg.total, 0, 3, st);
+    else launch_scatter_pass<LRF_CA, true>(P, P.app, P.bg.base[q], q == 2 ? P.bg.total : P.bg.base[q + 1], q, q + 1, st);
+    if (P.npass == 3 && q < 2) LRF_TRY(ts.bucket(3 + q, st));      // app_plane[q] is final (its line only if fused: bucket 2)
   }
-  if (ss) LRF_HIP(hipEventRecord(ss->app[0], st));         // go / dfeat rows: the weight-gradient kernel may start
-  unsigned* vmax_a = reinterpret_cast<unsigned*>(b.hist2 + 2 * BIN_MAX);
-  if (P.app3_fix)
-    hipLaunchKernelGGL((k_train_app3<8, true>), dim3(n_dgrad_wg), dim3(512), app3_lds_bytes(S, 8, bg.total), st, d,
-                       d.mlpwt, rays, z, S, w.toff, R, b.tileinfo, w.cidx,
-                       b.grd, b.rpart, w.pmax, b.wpart, bg, b.tid2, b.hist2, b.nmax, g_dgrad_dbg & 3, vmax_a);
-  else
-    hipLaunchKernelGGL((k_train_app3<8, false>), dim3(n_dgrad_wg), dim3(512), app3_lds_bytes(S, 8, bg.total), st, d,
-                       d.mlpwt, rays, z, S, w.toff, R, b.tileinfo, w.cidx,
-                       b.grd, b.rpart, w.pmax, b.wpart, bg, b.tid2, b.hist2, b.nmax, g_dgrad_dbg & 3, vmax_a);
-
-  // ---- side stream: per-ray backward, density scatter
-  unsigned* vmax_d = reinterpret_cast<unsigned*>(b.hist + 2 * BIN_MAX);
-  hipLaunchKernelGGL(k_bwd_ray, dim3((R + 3) / 4), dim3(256), (size_t)14 * S * sizeof(float) + (size_t)bg.total * sizeof(int), sb,
-                     d, rays, z, R, S, flags, b.feat, w.ncomp, w.cidx, b.crgb, g_rgb, g_depth,
-                     (const float*)nullptr, w.pmax, g_rays, bg, b.tid, b.hist, b.nmax, vmax_d);
-  auto det_convert = [&](const DetDst& img, float* const* gp, float* const* gl, int cch, const int* offs, const unsigned* vmax, int p_lo, int p_hi, hipStream_t s) {
-    DetConv dc;
-    for (int q = 0; q < 3; ++q) {
-      dc.img[q] = img.plane[q]; dc.g[q] = gp[q]; dc.n[q] = (long long)cch * L.pw[q] * L.ph[q];
-      dc.img[3 + q] = img.line[q]; dc.g[3 + q] = gl[q]; dc.n[3 + q] = (long long)cch * L.ll[q];
-    }
-    hipLaunchKernelGGL(k_det_convert, dim3(cus * 8), dim3(256), 0, s, dc, bg, offs, vmax, p_lo, p_hi);
-  };
-  hipLaunchKernelGGL(k_bin_fill, dim3(P.nblk), dim3(256), 0, sb, bg, b.nmax, R, S, w.toff, 0, b.tid, b.hist, b.cursor, b.offs, b.list);
-  switch (P.dens) {
-    case DensEng::Det:
-      hipLaunchKernelGGL((k_scatter_det<LRF_CD, false, FIX_NT>), dim3(nwg_scatter), dim3(FIX_NT), P.dens_lds, sb,
-                         d, bg, b.det_d, rays, z, S, b.offs, b.list, b.feat, b.rowinfo, b.grd, vmax_d, 0, bg.total);
-      det_convert(b.det_d, g->density_plane, g->density_line, LRF_CD, b.offs, vmax_d, 0, 3, sb);
-      break;
-    case DensEng::Fix:
-      hipLaunchKernelGGL((k_scatter_fix<LRF_CD, false, FIX_NT>), dim3(nwg_scatter), dim3(FIX_NT), P.dens_lds, sb,
-                         d, bg, dst_d, rays, z, S, b.offs, b.list, b.feat, b.rowinfo, b.grd, vmax_d, 0, bg.total);
-      break;
-    case DensEng::CasFused:
-      hipLaunchKernelGGL((k_scatter_plane<LRF_CD, false, 512, true>), dim3(nwg_scatter * LRF_DPLANE_MULT), dim3(512), P.dens_lds, sb,
-                         d, bg, dst_d, rays, z, S, b.offs, b.list, b.feat, b.rowinfo, b.grd, 0, bg.total);
-      break;
-    case DensEng::CasSplit:
-      hipLaunchKernelGGL((k_scatter_plane<LRF_CD, false, 512, false>), dim3(nwg_scatter * LRF_DPLANE_MULT), dim3(512), P.dens_lds, sb,
-                         d, bg, dst_d, rays, z, S, b.offs, b.list, b.feat, b.rowinfo, b.grd, 0, bg.total);
-      hipLaunchKernelGGL((k_scatter_line<LRF_CD, false, 1024>), dim3(3 * LINE_WGS), dim3(1024), P.dens_line_lds, sb,
-                         d, dst_d, rays, z, R, S, w.toff, b.feat, b.rowinfo, b.grd);
-      break;
-  }
-  if (sx) LRF_HIP(hipEventRecord(sx->bucket[0], sb));
-
-  // ---- dW2 / dW3 (row reads, matrix pipe): on the caller's stream behind the appearance kernel (g_wgrad_split > 0), or on the
-  // side stream behind the density scatter once the go / dfeat rows are there (g_wgrad_split == 0)
-  const int nch_max = WGRAD_MAXCH;      // (blocks behind the last chunk of the actual row count return at once)
-  const bool w23_on_st = !ss || g_wgrad_split > 0;
-  if (!w23_on_st) LRF_HIP(hipStreamWaitEvent(sb, ss->app[0], 0));
-  if (P.generic) {     // dW = A^T B over the operand rows k_gen_dgrad left (added straight into the reference-layout gradients)
-    const GenRowOff ro = gen_row_off(gc);
-    const int nchunk = (int)((b.nmax + GEN_GEMM_CHUNK - 1) / GEN_GEMM_CHUNK);
-    auto gemm = [&](int offA, int M, int offB, int N, float* dW, int ldw, float* db) {
-      hipLaunchKernelGGL(k_gen_gemm, dim3(((M + 63) / 64) * ((N + 63) / 64), nchunk), dim3(256), 0, w23_on_st ? st : sb,
-                         b.gen, P.gen_ld, offA, M, offB, N, w.toff, R, dW, ldw, db);
-    };
-    gemm(ro.dz1, gc.fc, ro.x1, gc.in1 + 1, g->w1, gc.in1, g->b1);
-    gemm(ro.dz2, gc.fc, ro.h1, gc.fc + 1, g->w2, gc.fc, g->b2);
-    gemm(ro.go, 3, ro.h2v, gc.fc + gc.inv + 1, g->w3, gc.fc + gc.inv, g->b3);
-  } else {
-    if (g_wgrad_kt == 64)
-      hipLaunchKernelGGL(k_wgrad_w2w3<64>, dim3(nch_max), dim3(512), w23_lds(64), w23_on_st ? st : sb, d.mlpb, b.act + 16 * ACT_FEAT, ACT_LD, b.grd + 16 * GRD_GO, GRD_LD,
-                         b.relu_bits, p->w3, p->w2, p->b2, w.toff, R, b.wpart);
-    else
-      hipLaunchKernelGGL(k_wgrad_w2w3<128>, dim3(nch_max), dim3(512), w23_lds(128), w23_on_st ? st : sb, d.mlpb, b.act + 16 * ACT_FEAT, ACT_LD, b.grd + 16 * GRD_GO, GRD_LD,
-                         b.relu_bits, p->w3, p->w2, p->b2, w.toff, R, b.wpart);
-  }
-  if (ss) LRF_HIP(hipEventRecord(ss->app[1], st));          // the caller's-stream partials (dW1, dbasis[, dW2, dW3]) are complete behind this
-  {
-    WgradSegs segs;
-    for (int q = 0; q < 7; ++q) segs.s[q] = WgradSeg{0, 1, 0, 0, 1, 1, 0x7fffffff, 0, 0, nullptr};    // unused slots: behind every element
-    int nseg = 0, elems = 0;
-    auto seg = [&](int off, int ld, int n_off, int m, int n, float* dst, int dst_ld, int x_slots = 0, int nch = 0) {
-      segs.s[nseg++] = WgradSeg{off, ld, n_off, m, n, dst_ld, elems, x_slots, nch, dst};
-      elems += m * n;
-    };
-    if (!P.generic) {
-      seg(WP_W2, 144, 0, 128, 128, g->w2, 128);
-      seg(WP_W2, 144, 128, 128, 1, g->b2, 1);
-      seg(WP_W1, 32, 0, 128, LRF_APP_DIM, g->w1, LRF_APP_DIM, 0, n_dgrad_wg);     // accumulated by k_train_dgrad3: one block per workgroup
-      seg(WP_W1, 32, LRF_APP_DIM, 128, 1, g->b1, 1, 0, n_dgrad_wg);
-    }
-    seg(WP_BAS, 96, 0, LRF_APP_DIM, 72, g->basis, 72, 1, n_dgrad_wg);   // accumulated by k_train_app3: one block per workgroup
-    if (!P.generic) {
-      seg(WP_W3, 144, 0, 3, LRF_FEATC + 3, g->w3, LRF_FEATC + 3);
-      seg(WP_W3, 144, LRF_FEATC + 3, 3, 1, g->b3, 1);
-    }
-    segs.total_elems = elems;
-    if (ss) LRF_HIP(hipStreamWaitEvent(sb, ss->app[1], 0));     // partials written on the caller's stream
-    hipLaunchKernelGGL(k_wgrad_reduce, dim3((elems * 16 + 255) / 256), dim3(256), 0, sb, b.wpart, w.toff, R, segs);
-  }
-  if (sx) LRF_HIP(hipEventRecord(sx->bucket[1], sb));
-  if (ss) LRF_HIP(hipEventRecord(ss->join, sb));
-
-  // ---- caller's stream: appearance scatter (its own bin buffers: the density scatter may still be running)
-  hipLaunchKernelGGL(k_bin_fill, dim3(P.nblk), dim3(256), 0, st, bg, b.nmax, R, S, w.toff, 1, b.tid2, b.hist2, b.cursor2, b.offs2, b.list2);
-  for (int q = 0; q < P.npass; ++q) {
-    const int blo = P.npass == 1 ? 0 : bg.base[q], bhi = (P.npass == 1 || q == 2) ? bg.total : bg.base[q + 1];
-    switch (P.app) {
-      case AppEng::Det8:
-        hipLaunchKernelGGL((k_scatter_det<LRF_CA, true, FIX_NT>), dim3(nwg_scatter), dim3(FIX_NT), P.app_lds, st,
-                           d, bg, b.det_a, rays, z, S, b.offs2, b.list2, b.feat, b.rowinfo, b.grd, vmax_a, blo, bhi);
-        break;
-      case AppEng::Det4:
-        hipLaunchKernelGGL((k_scatter_det<LRF_CA, true, FIX_NT, 4>), dim3(nwg_scatter), dim3(FIX_NT), P.app_lds, st,
-                           d, bg, b.det_a, rays, z, S, b.offs2, b.list2, b.feat, b.rowinfo, b.grd, vmax_a, blo, bhi);
-        break;
-      case AppEng::Fix8:
-        hipLaunchKernelGGL((k_scatter_fix<LRF_CA, true, FIX_NT>), dim3(nwg_scatter), dim3(FIX_NT), P.app_lds, st,
-                           d, bg, dst_a, rays, z, S, b.offs2, b.list2, b.feat, b.rowinfo, b.grd, vmax_a, blo, bhi);
-        break;
-      case AppEng::Fix4:
-        hipLaunchKernelGGL((k_scatter_fix<LRF_CA, true, FIX_NT, 4>), dim3(nwg_scatter), dim3(FIX_NT), P.app_lds, st,
-                           d, bg, dst_a, rays, z, S, b.offs2, b.list2, b.feat, b.rowinfo, b.grd, vmax_a, blo, bhi);
-        break;
-      case AppEng::CasFused:
-        hipLaunchKernelGGL((k_scatter_plane<LRF_CA, true, LRF_APP_NT, true>), dim3(nwg_scatter), dim3(LRF_APP_NT), P.app_lds, st,
-                           d, bg, dst_a, rays, z, S, b.offs2, b.list2, b.feat, b.rowinfo, b.grd, blo, bhi);
-        break;
-      case AppEng::CasSplit:        // (the lines: k_scatter_line behind the passes)
-        hipLaunchKernelGGL((k_scatter_plane<LRF_CA, true, LRF_APP_NT, false>), dim3(nwg_scatter), dim3(LRF_APP_NT), P.app_lds, st,
-                           d, bg, dst_a, rays, z, S, b.offs2, b.list2, b.feat, b.rowinfo, b.grd, blo, bhi);
-        break;
-    }
-    if (P.det) det_convert(b.det_a, g->app_plane, g->app_line, LRF_CA, b.offs2, vmax_a, P.npass == 1 ? 0 : q, P.npass == 1 ? 3 : q + 1, st);
-    if (P.npass == 3 && q < 2 && sx) LRF_HIP(hipEventRecord(sx->bucket[3 + q], st));    // app_plane[q] is final (its line only if fused: bucket 2)
-  }
-  if (P.app == AppEng::CasSplit)
-    hipLaunchKernelGGL((k_scatter_line<LRF_CA, true, 1024>), dim3(3 * LINE_WGS), dim3(1024), P.app_line_lds, st,
-                       d, dst_a, rays, z, R, S, w.toff, b.feat, b.rowinfo, b.grd);
-
-  // ---- join: both branches done
-  if (ss) LRF_HIP(hipStreamWaitEvent(st, ss->join, 0));
-  hipLaunchKernelGGL(k_rays_add_rpart, dim3((R + 255) / 256), dim3(256), 0, st, rays, R, w.ncomp, b.rpart, w.pmax, g_rays, d.perm);
-  if (sx) {
-    LRF_HIP(hipEventRecord(sx->bucket[2], st));
-    if (P.npass == 1) { LRF_HIP(hipEventRecord(sx->bucket[3], st)); LRF_HIP(hipEventRecord(sx->bucket[4], st)); }   // no per-plane passes: the planes are final with everything else
-    sx->bucket_set = true;
-  }
+  launch_scatter_lines<LRF_CA, true>(P, P.app, st);
+  LRF_TRY(ts.join());                                      // both branches done
+  bwd_rays_add(P, st);
+  LRF_TRY(ts.bucket(2, st));                               // the appearance tensors, and with them everything
+  if (P.npass == 1) { LRF_TRY(ts.bucket(3, st)); LRF_TRY(ts.bucket(4, st)); }   // no per-plane passes: the planes are final with everything else
+  ts.finish();
   LRF_HIP(hipGetLastError());
   return 0;
 }

@@ -36,6 +36,7 @@ static int set_err(const char* msg, hipError_t e = hipSuccess) {
   return 1;
 }
 #define LRF_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return set_err(#call, e_); } while (0)
+#define LRF_TRY(call) do { if (int rc_ = (call)) return rc_; } while (0)     // a callee that has already set the error
 
 // ---------------------------------------------------------------------------- pack
 // [C,H,W] -> [H,W,CS] channel-last; app=1: padded appearance layout (slot app_pc(c), zero pads)
@@ -950,6 +951,41 @@ static SideStream* side_stream() {
   }
   return &x;
 }
+// The caller's stream beside the device's side stream, for one call (lrf_render_bwd, render_fwd_pipelined).  Holds the
+// SideStream's mutex for its lifetime: the side stream and its events are per device, so host threads that enqueue on the same
+// device take turns (enqueueing a backward is ~0.3 ms of host time; the kernels themselves still overlap on the GPU).
+// On one stream -- no SideStream, or (unless `always`) lrf_debug_set_bwd_overlap(0) or a capturing caller's stream -- side() is
+// the caller's stream and fork / join / signal / wait do nothing.  The bucket events of lrf_render_bwd_wait are recorded
+// whenever the device has a SideStream, on one stream and under capture too: that is sx against ss.
+class TwoStreams {
+  hipStream_t st;
+  SideStream* sx;            // the device's, or null
+  SideStream* ss;            // sx when the call runs on two streams, else null
+  std::unique_lock<std::mutex> lock;
+ public:
+  explicit TwoStreams(hipStream_t caller, bool always = false) : st(caller), sx(side_stream()), ss(sx) {
+    if (sx) lock = std::unique_lock<std::mutex>(sx->mu);
+    if (ss && !always) {
+      hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+      (void)hipStreamIsCapturing(st, &cap);
+      if (!g_bwd_overlap || cap == hipStreamCaptureStatusActive) ss = nullptr;
+    }
+  }
+  bool overlapping() const { return ss != nullptr; }
+  hipStream_t side() const { return ss ? ss->s : st; }
+  int fork() {               // the side stream continues from here
+    if (ss) { LRF_HIP(hipEventRecord(ss->fork, st)); LRF_HIP(hipStreamWaitEvent(ss->s, ss->fork, 0)); }
+    return 0;
+  }
+  int join() {               // the caller's stream continues behind everything on the side stream
+    if (ss) { LRF_HIP(hipEventRecord(ss->join, ss->s)); LRF_HIP(hipStreamWaitEvent(st, ss->join, 0)); }
+    return 0;
+  }
+  int signal(int i, hipStream_t s) { if (ss) LRF_HIP(hipEventRecord(ss->app[i], s)); return 0; }      // hand-off i (0, 1) is ready behind s ...
+  int wait(int i, hipStream_t s) { if (ss) LRF_HIP(hipStreamWaitEvent(s, ss->app[i], 0)); return 0; } // ... and s goes on behind it
+  int bucket(int i, hipStream_t s) { if (sx) LRF_HIP(hipEventRecord(sx->bucket[i], s)); return 0; }   // lrf_render_bwd_wait(i)'s event
+  void finish() { if (sx) sx->bucket_set = true; }
+};
 // Dynamic LDS above 64 KB has to be opted into, once per device, before the first launch that asks for it: every render-path
 // entry point calls this once its arguments are accepted (defined behind lrf_backward.inl, whose kernels it names too).
 static hipError_t lds_opt_in();
@@ -1261,21 +1297,19 @@ static int render_fwd_pipelined(const LrfField* f, const float* rays, const floa
                                 uint32_t flags, float floater_thresh, float* rgb, float* depth,
                                 float* weight_out, float* acc_out, void* workspace, hipStream_t st) {
   const int nc = pipe_chunks(R);
-  SideStream* ss = nc > 1 ? side_stream() : nullptr;
-  if (!ss) return render_fwd_impl(f, rays, z, R, S, flags, floater_thresh, rgb, depth, weight_out, acc_out, workspace, st, nullptr);
-  std::lock_guard<std::mutex> lk(ss->mu);
-  LRF_HIP(hipEventRecord(ss->fork, st));
-  LRF_HIP(hipStreamWaitEvent(ss->s, ss->fork, 0));
+  if (nc <= 1) return render_fwd_impl(f, rays, z, R, S, flags, floater_thresh, rgb, depth, weight_out, acc_out, workspace, st, nullptr);
+  TwoStreams ts(st, true);
+  if (!ts.overlapping()) return render_fwd_impl(f, rays, z, R, S, flags, floater_thresh, rgb, depth, weight_out, acc_out, workspace, st, nullptr);
+  LRF_TRY(ts.fork());
   const size_t wb = carve(nullptr, g_pipe_chunk, S).bytes;
   int rc = 0;
   for (int c = 0; c < nc && rc == 0; ++c) {
     const int r0 = c * g_pipe_chunk, rn = std::min(g_pipe_chunk, R - r0);
     rc = render_fwd_impl(f, rays + (size_t)r0 * 6, z, rn, S, flags, floater_thresh, rgb + (size_t)r0 * 3, depth + r0,
                          weight_out ? weight_out + (size_t)r0 * S : nullptr, acc_out ? acc_out + r0 : nullptr,
-                         static_cast<char*>(workspace) + (size_t)c * wb, (c & 1) ? ss->s : st, nullptr);
+                         static_cast<char*>(workspace) + (size_t)c * wb, (c & 1) ? ts.side() : st, nullptr);
   }
-  LRF_HIP(hipEventRecord(ss->join, ss->s));                  // (also after an error: the side stream is joined again)
-  LRF_HIP(hipStreamWaitEvent(st, ss->join, 0));
+  LRF_TRY(ts.join());                                       // (also after an error: the side stream is joined again)
   return rc;
 }
 
