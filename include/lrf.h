@@ -625,6 +625,45 @@ int lrf_render_normals(const LrfField* f, const float* rays, const float* z, int
                        float floater_thresh, const float* blend_w /* nullable */, int32_t per_view, int32_t accumulate,
                        float* normals /* [R,3] */, float* acc /* [R] or NULL */, void* workspace, void* stream);
 
+/* A TSDF volume and a triangle mesh from it (csrc/lrf_mesh.inl states the arithmetic, fp32 without contraction).
+ * A volume is a lattice of Nx x Ny x Nz points at origin + (ix, iy, iz) * voxel, x fastest: tsdf [Nz,Ny,Nx] (starts at 1),
+ * weight [Nz,Ny,Nx] (starts at 0), rgb [Nz,Ny,Nx,3] in [0, 1] (nullable, starts at 0).
+ * lrf_tsdf_integrate: V pinhole frames (depth [V,H,W], rgb8 [V,H,W,3] uint8 -- nullable, with the volume's rgb --, cam2world
+ * [V,3,4], focal device [1], center device [2]) are folded into the volume in frame order, one lane per lattice point, the
+ * volume read and written once per call: a point is projected into frame v as lrf_points_fuse's consistency test projects;
+ * with dn the depth at the nearest pixel (finite, positive, in [d_min, d_max]), sdf = dn - z; a frame with sdf < -trunc is
+ * skipped, else s = min(1, sdf / trunc), tsdf = (tsdf weight + s) / (weight + 1), rgb likewise from rgb8 / 255, weight += 1.
+ * No atomics; frames k..V integrated on the state of frames 0..k give the bits of one call.  Refused before the launch: null or
+ * misaligned pointers, Nx, Ny or Nz < 1, Nx Ny Nz >= 2^31, voxel <= 0, trunc <= 0 (or NaN), d_min > d_max (or NaN), V, H or
+ * W < 1, V H W >= 2^31, rgb without rgb8 or the reverse.
+ * lrf_mesh_extract: marching tetrahedra (the Kuhn split, six per cell) of any scalar volume at `level`; a lattice point is
+ * inside when value < level; a cell counts when its eight corners have weight >= min_weight (> 0; every cell when weight is
+ * null).  An indexed, watertight-by-construction mesh: vertices [Nv,3] on lattice edges in (z, y, x, edge) order, rgb8_out
+ * [Nv,3] (nullable, with rgb) the interpolated colour encoded as lrf_encode_frames encodes, faces [Nf,3] int32 in (cell,
+ * tetrahedron, triangle) order, wound so that the normal points towards value > level.  counts (device int64 [2]) receives
+ * the true (Nv, Nf); rows at or beyond max_vertices / max_faces are not written, and with both 0 nothing is written (a
+ * counting call).  Three launches, no atomics, no host synchronisation, the same bytes on every run.  The indices are right
+ * while Nv and Nf stay below 2^31.  Refused before any launch: null or misaligned pointers, dims < 1, Nx Ny Nz >= 2^31,
+ * voxel <= 0, a NaN level, min_weight <= 0 with weight, capacities outside [0, 2^31), rgb without rgb8_out or the reverse.
+ * workspace: lrf_mesh_workspace_bytes(Nx, Ny, Nz) bytes (0 for a refused shape), 4-byte aligned. */
+typedef struct LrfTsdfVolume {
+  float* tsdf; float* weight; float* rgb /* nullable */;
+  int32_t Nx, Ny, Nz;
+  float origin[3], voxel, trunc;
+} LrfTsdfVolume;
+int lrf_tsdf_integrate(const LrfTsdfVolume* vol, const float* depth, const uint8_t* rgb8 /* nullable */, const float* cam2world,
+                       const float* focal, const float* center, int32_t V, int32_t H, int32_t W, float d_min, float d_max,
+                       void* stream);
+typedef struct LrfMeshExtract {
+  const float* value; const float* weight /* nullable */; const float* rgb /* nullable */;
+  int32_t Nx, Ny, Nz;
+  float origin[3], voxel, level, min_weight;
+} LrfMeshExtract;
+size_t lrf_mesh_workspace_bytes(int32_t Nx, int32_t Ny, int32_t Nz);
+int lrf_mesh_extract(const LrfMeshExtract* m, int64_t max_vertices, int64_t max_faces, float* vertices,
+                     uint8_t* rgb8_out /* nullable */, int32_t* faces, int64_t* counts /* device [2] */, void* workspace,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,6 +16,8 @@ Public surface mirrors the reference's names:
                                     (rendered depth fused into a filtered, coloured world-space point cloud; no reference row)
   normals.render_normals / encode_normals, TensorVMSplit.render_normals / density_gradient
                                     (per-ray surface normals from the density gradient: normal maps, PLY normals; no reference row)
+  mesh.TsdfVolume / extract_mesh / scene_mesh
+                                    (rendered depth fused into a TSDF volume, marching tetrahedra, PLY faces; no reference row)
 The arithmetic of TensorVMSplit.forward and of LocalTensorfs.forward (ray generation, field
 blend, exposure) runs in hand-written HIP kernels for gfx950 (csrc/), reached through the C ABI
 of include/lrf.h.
@@ -31,6 +33,7 @@ from . import diagnostics  # noqa: F401
 from . import novel_views  # noqa: F401
 from . import pointcloud  # noqa: F401
 from . import normals  # noqa: F401
+from . import mesh  # noqa: F401
 from .frames import DeviceFrames  # noqa: F401
 
-__all__ = ["TensorVMSplit", "AlphaGridMask", "MLPRender_Fea_late_view", "LocalTensorfs", "rays", "losses", "metrics", "diagnostics", "novel_views", "pointcloud", "normals", "NativeError", "FusedAdam", "DeviceFrames"]
+__all__ = ["TensorVMSplit", "AlphaGridMask", "MLPRender_Fea_late_view", "LocalTensorfs", "rays", "losses", "metrics", "diagnostics", "novel_views", "pointcloud", "normals", "mesh", "NativeError", "FusedAdam", "DeviceFrames"]

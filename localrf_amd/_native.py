@@ -128,6 +128,16 @@ class LrfPointsFuse(C.Structure):
                 ("rel_tol", C.c_float), ("min_consistent", C.c_int32)]
 
 
+class LrfTsdfVolume(C.Structure):
+    _fields_ = [("tsdf", _f), ("weight", _f), ("rgb", _f), ("Nx", C.c_int32), ("Ny", C.c_int32), ("Nz", C.c_int32),
+                ("origin", C.c_float * 3), ("voxel", C.c_float), ("trunc", C.c_float)]
+
+
+class LrfMeshExtract(C.Structure):
+    _fields_ = [("value", _f), ("weight", _f), ("rgb", _f), ("Nx", C.c_int32), ("Ny", C.c_int32), ("Nz", C.c_int32),
+                ("origin", C.c_float * 3), ("voxel", C.c_float), ("level", C.c_float), ("min_weight", C.c_float)]
+
+
 # every symbol include/lrf.h and include/lrf_debug.h declare: (restype, argtypes)
 SYMBOLS = {
     "lrf_abi_version": (C.c_int, []),
@@ -223,6 +233,11 @@ SYMBOLS = {
     "lrf_points_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "lrf_points_fuse": (C.c_int, [C.POINTER(LrfPointsFuse), C.c_int64, _f, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p]),
+    "lrf_tsdf_integrate": (C.c_int, [C.POINTER(LrfTsdfVolume), _f, C.c_void_p, _f, _f, _f, C.c_int32, C.c_int32, C.c_int32,
+                                     C.c_float, C.c_float, C.c_void_p]),
+    "lrf_mesh_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "lrf_mesh_extract": (C.c_int, [C.POINTER(LrfMeshExtract), C.c_int64, C.c_int64, _f, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p]),
     "lrf_density_gradient": (C.c_int, [C.POINTER(LrfField), _f, C.c_int64, _f, _f, C.c_void_p]),
     "lrf_normals_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "lrf_render_normals": (C.c_int, [C.POINTER(LrfField), _f, _f, C.c_int32, C.c_int32, C.c_uint32, C.c_float, _f, C.c_int32,

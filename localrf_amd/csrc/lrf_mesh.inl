@@ -1,0 +1,406 @@
+// lrf_mesh.inl -- rendered depth fused into a truncated signed-distance (TSDF) volume, and a triangle mesh extracted from a
+// scalar volume (included by lrf_render.hip after lrf_encode.inl and lrf_points.inl, whose enc_rgb_byte, pts_finite_pos,
+// reproject and k_points_scan it shares).
+//
+// A volume is a lattice of Nx x Ny x Nz points at origin + (ix, iy, iz) * voxel, x fastest in memory: tsdf [Nz,Ny,Nx] (starts
+// at 1), weight [Nz,Ny,Nx] (starts at 0), rgb [Nz,Ny,Nx,3] in [0, 1] (nullable, starts at 0).
+//
+// k_tsdf_integrate: one lane per lattice point, a wave covers 64 consecutive x of one (z, y) row, so its reprojections land on
+// neighbouring pixels.  The point's tsdf, weight and rgb are read once, kept in registers over the frame loop and written
+// once.  Per frame v in frame order, in fp32 with contraction off so that a numpy restatement matches bit for bit:
+//   0. p = origin + (float)(ix, iy, iz) * voxel, one multiply and one add per axis;
+//   1. reproject (lrf_points.inl): q = R_v^T (p - t_v), nz = -q.z; skipped behind the camera or outside the image;
+//   2. dn = depth[v,iw,iu]; skipped unless finite, positive and d_min <= dn <= d_max;
+//   3. sdf = dn - nz (both in units of the un-normalised direction whose z is -1); skipped if sdf < -trunc;
+//      s = min(1, sdf / trunc) (IEEE division);
+//   4. tsdf = (tsdf * weight + s) / (weight + 1); rgb[c] = (rgb[c] * weight + (float)rgb8[v,iw,iu,c] / 255) / (weight + 1);
+//      weight = weight + 1.
+// The frame's camera-to-world matrix is addressed by the loop counter alone, so it is read with scalar loads into scalar
+// registers.  No atomics; integrating frames k..V on the state frames 0..k left gives the bits of one call over 0..V.
+//
+// Extraction: marching tetrahedra on the Kuhn split of each cell.  Corners of a cell are numbered by their offset bits
+// (bit 0 = x, bit 1 = y, bit 2 = z).  Tetrahedron t = 0..5 is the monotone path 000 -> 111 of the t-th permutation (a, b, c)
+// of the axes in lexicographic order: corners 0, 1<<a, 1<<a | 1<<b, 7; the middle two are swapped for an odd permutation so
+// that every tetrahedron is positively oriented.  The split is translation invariant: the face diagonals of neighbouring
+// cells coincide, so the mesh has no cracks, and a tetrahedron has no ambiguous case.
+// Every mesh vertex lies on one of the seven lattice edges a lattice point P owns: edge e = 0..6 runs from P to P + d with
+// d = e + 1 read as offset bits -- (1,0,0), (0,1,0), (1,1,0), (0,0,1), (1,0,1), (0,1,1), (1,1,1).  A tetrahedron's edge between
+// corners A and B (nested bit sets) is edge (A ^ B) - 1 of the point at corner A & B.
+//   inside   value < level (strict)
+//   valid    a cell whose eight corners have weight >= min_weight (every cell when weight is null)
+//   vertex   on an owned edge whose ends straddle the level and that at least one valid cell contains (the cells at P - s
+//            for the subsets s of the axes d leaves out); position pa + t * (pb - pa), t = (level - a) / (b - a), always
+//            from the owning end a, so every cell that uses it sees the same bits; colour enc_rgb_byte(ca + t * (cb - ca))
+//   faces    per valid cell, tetrahedron by tetrahedron: one inside corner i -> (ij, ik, il) for the even permutation
+//            (i, j, k, l); three inside -> the outside corner's triangle reversed; two inside i, j -> (ik, il, jl) and
+//            (ik, jl, jk).  The normal points towards value > level.
+// Three launches, no atomics, no host synchronisation:
+//   k_mesh_count  per lattice point the 7-bit mask of its vertices, the triangles of its cell and the vertices before it in
+//                 its workgroup -> info; per workgroup the vertex and face totals
+//   k_points_scan two workgroups: exclusive vertex and face bases per workgroup, the true totals in counts[0..1]
+//   k_mesh_emit   vertices in (z, y, x, edge) order, faces in (cell, tetrahedron, triangle) order; a face's vertex index is
+//                 its owner's base + popcount(owner's mask below the edge).  Rows at or beyond capacity are not written.
+namespace lrf {
+
+constexpr int TSDF_NT = 256;
+constexpr int MESH_NT = 256;                                        // lattice points per workgroup (info keeps 11 bits of prefix)
+constexpr unsigned MESH_CELL = 0x361Bu;                             // the 8 corners of a cell in the 3x3x3 neighbourhood mask
+
+struct TsdfArgs {
+  float* tsdf; float* weight; float* rgb;
+  int Nx, Ny, Nz, nxc;                                              // nxc: 64-point chunks per row
+  long long n_items;                                                // Nz Ny nxc wave items
+  float ox, oy, oz, voxel, trunc;
+  int V, H, W;
+  float d_min, d_max;
+};
+
+__global__ __launch_bounds__(TSDF_NT) void k_tsdf_integrate(TsdfArgs a, const float* __restrict__ depth,
+                                                            const uint8_t* __restrict__ rgb8, const float* __restrict__ c2w,
+                                                            const float* __restrict__ focal, const float* __restrict__ center) {
+#pragma clang fp contract(off)
+  const long long item = (long long)blockIdx.x * (TSDF_NT / 64) + (threadIdx.x >> 6);
+  if (item >= a.n_items) return;
+  const int xc = (int)(item % a.nxc);
+  const long long row = item / a.nxc;
+  const int iy = (int)(row % a.Ny), iz = (int)(row / a.Ny);
+  const int ix = xc * 64 + (threadIdx.x & 63);
+  if (ix >= a.Nx) return;
+  const size_t p = (size_t)row * a.Nx + ix;
+  const float pw[3] = {a.ox + (float)ix * a.voxel, a.oy + (float)iy * a.voxel, a.oz + (float)iz * a.voxel};
+  const float f = focal[0], cx = center[0], cy = center[1];
+  float t = a.tsdf[p], wt = a.weight[p];
+  float c0 = 0.0f, c1 = 0.0f, c2 = 0.0f;
+  if (a.rgb) { c0 = a.rgb[3 * p]; c1 = a.rgb[3 * p + 1]; c2 = a.rgb[3 * p + 2]; }
+  for (int v = 0; v < a.V; ++v) {
+    float nz;
+    int iu, iw;
+    if (!reproject(c2w + (size_t)v * 12, pw, f, cx, cy, a.W, a.H, nz, iu, iw)) continue;
+    const size_t px = (size_t)v * a.H * a.W + (size_t)iw * a.W + iu;
+    const float dn = depth[px];
+    if (!(pts_finite_pos(dn) && dn >= a.d_min && dn <= a.d_max)) continue;
+    const float sdf = dn - nz;
+    if (sdf < -a.trunc) continue;
+    const float s = fminf(1.0f, sdf / a.trunc);
+    const float w1 = wt + 1.0f;
+    t = (t * wt + s) / w1;
+    if (a.rgb) {
+      const uint8_t* c = rgb8 + 3 * px;
+      c0 = (c0 * wt + (float)c[0] / 255.0f) / w1;
+      c1 = (c1 * wt + (float)c[1] / 255.0f) / w1;
+      c2 = (c2 * wt + (float)c[2] / 255.0f) / w1;
+    }
+    wt = w1;
+  }
+  a.tsdf[p] = t; a.weight[p] = wt;
+  if (a.rgb) { a.rgb[3 * p] = c0; a.rgb[3 * p + 1] = c1; a.rgb[3 * p + 2] = c2; }
+}
+
+// ------------------------------------------------------------------------------------------------ the case tables, in code
+constexpr int mt_popc4(int m) { return (m & 1) + ((m >> 1) & 1) + ((m >> 2) & 1) + ((m >> 3) & 1); }
+// the edge of a tetrahedron between its corners i and j: (0,1) (0,2) (0,3) (1,2) (1,3) (2,3) -> 0..5
+constexpr int mt_edge(int i, int j) { return i > j ? mt_edge(j, i) : (i == 0 ? j - 1 : i + j); }
+constexpr unsigned mt_tri(int a, int b, int c, int slot) {
+  return ((unsigned)a | (unsigned)b << 3 | (unsigned)c << 6) << (2 + 9 * slot);
+}
+// inside mask m of a positively oriented tetrahedron -> triangles | edge triples << 2 (three bits per edge, nine per triangle)
+constexpr unsigned mt_case(int m) {
+  // even permutations (i, j, k, l) of the corners that put a corner, or a pair, first: they keep the orientation
+  constexpr int one[4][4] = {{0, 1, 2, 3}, {1, 0, 3, 2}, {2, 0, 1, 3}, {3, 0, 2, 1}};
+  constexpr int two[6][4] = {{0, 1, 2, 3}, {0, 2, 3, 1}, {0, 3, 1, 2}, {1, 2, 0, 3}, {1, 3, 2, 0}, {2, 3, 0, 1}};
+  const int pc = mt_popc4(m);
+  if (pc == 1 || pc == 3) {
+    const int bit = pc == 1 ? m : (~m & 15);
+    const int i = bit == 1 ? 0 : bit == 2 ? 1 : bit == 4 ? 2 : 3;
+    const int ij = mt_edge(one[i][0], one[i][1]), ik = mt_edge(one[i][0], one[i][2]), il = mt_edge(one[i][0], one[i][3]);
+    return 1u | (pc == 1 ? mt_tri(ij, ik, il, 0) : mt_tri(ij, il, ik, 0));
+  }
+  if (pc == 2) {
+    for (int r = 0; r < 6; ++r) {
+      if (((1 << two[r][0]) | (1 << two[r][1])) != m) continue;
+      const int i = two[r][0], j = two[r][1], k = two[r][2], l = two[r][3];
+      return 2u | mt_tri(mt_edge(i, k), mt_edge(i, l), mt_edge(j, l), 0) | mt_tri(mt_edge(i, k), mt_edge(j, l), mt_edge(j, k), 1);
+    }
+  }
+  return 0u;
+}
+// corner k of tetrahedron t as offset bits
+constexpr int mt_corner(int t, int k) {
+  constexpr int perm[6][3] = {{0, 1, 2}, {0, 2, 1}, {1, 0, 2}, {1, 2, 0}, {2, 0, 1}, {2, 1, 0}};
+  constexpr int odd[6] = {0, 1, 1, 0, 0, 1};
+  const int c1 = 1 << perm[t][0], c2 = c1 | 1 << perm[t][1];
+  return k == 0 ? 0 : k == 3 ? 7 : ((k == 1) != (odd[t] != 0)) ? c1 : c2;
+}
+// the six edges of tetrahedron t, six bits each: owner corner | direction << 3
+constexpr unsigned long long mt_tet_edges(int t) {
+  constexpr int ea[6] = {0, 0, 0, 1, 1, 2}, eb[6] = {1, 2, 3, 2, 3, 3};
+  unsigned long long out = 0;
+  for (int k = 0; k < 6; ++k) {
+    const int A = mt_corner(t, ea[k]), B = mt_corner(t, eb[k]);
+    out |= (unsigned long long)((A & B) | (A ^ B) << 3) << (6 * k);
+  }
+  return out;
+}
+__constant__ unsigned MT_CASE[16] = {mt_case(0), mt_case(1), mt_case(2), mt_case(3), mt_case(4), mt_case(5), mt_case(6), mt_case(7),
+                                     mt_case(8), mt_case(9), mt_case(10), mt_case(11), mt_case(12), mt_case(13), mt_case(14),
+                                     mt_case(15)};
+
+struct MeshArgs {
+  const float* value; const float* weight; const float* rgb;        // weight, rgb nullable
+  int Nx, Ny, Nz, n;                                                // n = Nx Ny Nz < 2^31
+  float ox, oy, oz, voxel, level, min_weight;
+};
+
+// lattice offset of the corner / direction with offset bits d
+__device__ __forceinline__ long long mesh_off(const MeshArgs& a, int d) {
+  return (d & 1) + (long long)((d >> 1) & 1) * a.Nx + (long long)((d >> 2) & 1) * a.Nx * a.Ny;
+}
+
+// exclusive prefix of v over the workgroup's MESH_NT threads (every thread calls), total = the workgroup's sum
+__device__ __forceinline__ unsigned mesh_block_scan(unsigned v, unsigned* part, unsigned& total) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  unsigned s = v;
+  for (int off = 1; off < 64; off <<= 1) {
+    const unsigned t = __shfl_up(s, off, 64);
+    if (lane >= off) s += t;
+  }
+  if (lane == 63) part[wv] = s;
+  __syncthreads();
+  unsigned pre = 0;
+  total = 0;
+  for (int w = 0; w < MESH_NT / 64; ++w) {
+    const unsigned q = part[w];
+    if (w < wv) pre += q;
+    total += q;
+  }
+  __syncthreads();
+  return pre + (s - v);
+}
+
+// the inside bits of tetrahedron T's four corners, from the cell's eight
+template <int T>
+__device__ __forceinline__ unsigned mesh_tet_mask(unsigned cm) {
+  return ((cm >> mt_corner(T, 0)) & 1u) | ((cm >> mt_corner(T, 1)) & 1u) << 1 | ((cm >> mt_corner(T, 2)) & 1u) << 2 |
+         ((cm >> mt_corner(T, 3)) & 1u) << 3;
+}
+__device__ __forceinline__ unsigned mesh_tet_tris(unsigned m) {
+  const unsigned pc = __popc(m);
+  return pc == 2 ? 2u : (pc == 1 || pc == 3) ? 1u : 0u;
+}
+
+// info[p] = vertex mask | triangles of the cell << 7 | vertices before p in its workgroup << 11
+__global__ __launch_bounds__(MESH_NT) void k_mesh_count(MeshArgs a, unsigned* __restrict__ info, unsigned* __restrict__ wgv,
+                                                        unsigned* __restrict__ wgf) {
+  __shared__ unsigned part[MESH_NT / 64];
+  const long long pl = (long long)blockIdx.x * MESH_NT + threadIdx.x;
+  unsigned mask = 0, ntri = 0;
+  if (pl < a.n) {
+    const int p = (int)pl;
+    const int ix = p % a.Nx, r = p / a.Nx, iy = r % a.Ny, iz = r / a.Ny;
+    const bool ina = a.value[p] < a.level;
+    unsigned cm = ina ? 1u : 0u, present = 1u, strad = 0u;
+#pragma unroll
+    for (int d = 1; d < 8; ++d) {
+      if (ix + (d & 1) >= a.Nx || iy + ((d >> 1) & 1) >= a.Ny || iz + ((d >> 2) & 1) >= a.Nz) continue;
+      const bool inb = a.value[p + mesh_off(a, d)] < a.level;
+      present |= 1u << d;
+      cm |= (inb ? 1u : 0u) << d;
+      if (inb != ina) strad |= 1u << (d - 1);
+    }
+    if (strad) {
+      unsigned ok = 0;                                              // bit (dz+1) 9 + (dy+1) 3 + (dx+1): that neighbour can be a cell's corner
+#pragma unroll
+      for (int k = 0; k < 27; ++k) {
+        const int dx = k % 3 - 1, dy = (k / 3) % 3 - 1, dz = k / 9 - 1;
+        const int jx = ix + dx, jy = iy + dy, jz = iz + dz;
+        if (jx < 0 || jx >= a.Nx || jy < 0 || jy >= a.Ny || jz < 0 || jz >= a.Nz) continue;
+        if (!a.weight || a.weight[p + dx + (long long)dy * a.Nx + (long long)dz * a.Nx * a.Ny] >= a.min_weight) ok |= 1u << k;
+      }
+#pragma unroll
+      for (int e = 0; e < 7; ++e) {
+        const int d = e + 1, fr = ~d & 7;
+        bool any = false;
+#pragma unroll
+        for (int s = 0; s < 8; ++s) {
+          if (s & ~fr) continue;                                    // s: the axes along which the cell starts one point before P
+          const int shift = 13 - (s & 1) - 3 * ((s >> 1) & 1) - 9 * ((s >> 2) & 1);
+          any = any || ((ok >> shift) & MESH_CELL) == MESH_CELL;
+        }
+        if (((strad >> e) & 1u) && any) mask |= 1u << e;
+      }
+      if (present == 0xFFu && ((ok >> 13) & MESH_CELL) == MESH_CELL)
+        ntri = mesh_tet_tris(mesh_tet_mask<0>(cm)) + mesh_tet_tris(mesh_tet_mask<1>(cm)) + mesh_tet_tris(mesh_tet_mask<2>(cm)) +
+               mesh_tet_tris(mesh_tet_mask<3>(cm)) + mesh_tet_tris(mesh_tet_mask<4>(cm)) + mesh_tet_tris(mesh_tet_mask<5>(cm));
+    }
+  }
+  unsigned vtot, ftot;
+  const unsigned vpre = mesh_block_scan(__popc(mask), part, vtot);
+  mesh_block_scan(ntri, part, ftot);
+  if (pl < a.n) info[pl] = mask | ntri << 7 | vpre << 11;
+  if (threadIdx.x == 0) { wgv[blockIdx.x] = vtot; wgf[blockIdx.x] = ftot; }
+}
+
+// the index of the vertex on edge (code >> 3) - 1 of the point at corner (code & 7) of the cell at p
+__device__ __forceinline__ int mesh_vertex_index(const MeshArgs& a, const unsigned* __restrict__ info,
+                                                 const unsigned* __restrict__ wgv, int p, unsigned code) {
+  const long long o = p + mesh_off(a, (int)(code & 7u));
+  const unsigned oi = info[o];
+  return (int)(wgv[o / MESH_NT] + (oi >> 11) + __popc(oi & ((1u << ((code >> 3) - 1u)) - 1u)));
+}
+
+template <int T>
+__device__ __forceinline__ void mesh_tet_faces(const MeshArgs& a, const unsigned* __restrict__ info,
+                                               const unsigned* __restrict__ wgv, int p, unsigned cm, long long& row,
+                                               long long max_faces, int* __restrict__ faces) {
+  constexpr unsigned long long edges = mt_tet_edges(T);
+  const unsigned m = mesh_tet_mask<T>(cm);
+  if (m == 0u || m == 15u) return;
+  const unsigned cs = MT_CASE[m];
+  const int nt = (int)(cs & 3u);
+  for (int j = 0; j < nt; ++j, ++row) {
+    if (row >= max_faces) continue;
+    for (int k = 0; k < 3; ++k) {
+      const unsigned ek = (cs >> (2 + 9 * j + 3 * k)) & 7u;
+      faces[3 * row + k] = mesh_vertex_index(a, info, wgv, p, (unsigned)(edges >> (6 * ek)) & 63u);
+    }
+  }
+}
+
+__global__ __launch_bounds__(MESH_NT) void k_mesh_emit(MeshArgs a, const unsigned* __restrict__ info,
+                                                       const unsigned* __restrict__ wgv, const unsigned* __restrict__ wgf,
+                                                       long long max_vertices, long long max_faces, float* __restrict__ vertices,
+                                                       uint8_t* __restrict__ rgb8_out, int* __restrict__ faces) {
+#pragma clang fp contract(off)
+  __shared__ unsigned part[MESH_NT / 64];
+  const long long pl = (long long)blockIdx.x * MESH_NT + threadIdx.x;
+  const unsigned me = pl < a.n ? info[pl] : 0u;
+  const unsigned mask = me & 127u, ntri = (me >> 7) & 15u;
+  unsigned ftot;
+  const unsigned fpre = mesh_block_scan(ntri, part, ftot);
+  if (!(mask | ntri)) return;
+  const int p = (int)pl;
+  const int ix = p % a.Nx, r = p / a.Nx, iy = r % a.Ny, iz = r / a.Ny;
+  if (mask) {
+    long long row = (long long)wgv[blockIdx.x] + (me >> 11);
+    const float va = a.value[p];
+    const float pa[3] = {a.ox + (float)ix * a.voxel, a.oy + (float)iy * a.voxel, a.oz + (float)iz * a.voxel};
+#pragma unroll
+    for (int e = 0; e < 7; ++e) {
+      if (!((mask >> e) & 1u)) continue;
+      const int d = e + 1;
+      if (row < max_vertices) {
+        const size_t q = (size_t)(p + mesh_off(a, d));
+        const float vb = a.value[q];
+        const float t = (a.level - va) / (vb - va);
+        const float pb[3] = {a.ox + (float)(ix + (d & 1)) * a.voxel, a.oy + (float)(iy + ((d >> 1) & 1)) * a.voxel,
+                             a.oz + (float)(iz + ((d >> 2) & 1)) * a.voxel};
+        for (int c = 0; c < 3; ++c) vertices[3 * row + c] = pa[c] + t * (pb[c] - pa[c]);
+        if (rgb8_out) {
+          for (int c = 0; c < 3; ++c) {
+            const float ca = a.rgb[3 * (size_t)p + c], cb = a.rgb[3 * q + c];
+            rgb8_out[3 * row + c] = (uint8_t)enc_rgb_byte(ca + t * (cb - ca));
+          }
+        }
+      }
+      ++row;
+    }
+  }
+  if (ntri) {                                                       // the cell at p is valid: its eight corners exist
+    unsigned cm = 0;
+#pragma unroll
+    for (int d = 0; d < 8; ++d) cm |= (a.value[p + mesh_off(a, d)] < a.level ? 1u : 0u) << d;
+    long long row = (long long)wgf[blockIdx.x] + fpre;
+    mesh_tet_faces<0>(a, info, wgv, p, cm, row, max_faces, faces);
+    mesh_tet_faces<1>(a, info, wgv, p, cm, row, max_faces, faces);
+    mesh_tet_faces<2>(a, info, wgv, p, cm, row, max_faces, faces);
+    mesh_tet_faces<3>(a, info, wgv, p, cm, row, max_faces, faces);
+    mesh_tet_faces<4>(a, info, wgv, p, cm, row, max_faces, faces);
+    mesh_tet_faces<5>(a, info, wgv, p, cm, row, max_faces, faces);
+  }
+}
+
+// lattice points of a shape, or 0 when the entry points refuse it
+static long long mesh_points(int Nx, int Ny, int Nz) {
+  if (Nx < 1 || Ny < 1 || Nz < 1) return 0;
+  const long long n = (long long)Nx * Ny;                            // < 2^62
+  return n >= (1ll << 31) || n * Nz >= (1ll << 31) ? 0 : n * Nz;
+}
+
+}  // namespace lrf
+
+extern "C" int lrf_tsdf_integrate(const LrfTsdfVolume* vol, const float* depth, const uint8_t* rgb8, const float* cam2world,
+                                  const float* focal, const float* center, int32_t V, int32_t H, int32_t W, float d_min,
+                                  float d_max, void* stream) {
+  using namespace lrf;
+  if (!vol) return set_err("lrf_tsdf_integrate: null argument");
+  const long long n = mesh_points(vol->Nx, vol->Ny, vol->Nz);
+  if (!n) return set_err("lrf_tsdf_integrate: need Nx, Ny, Nz >= 1 and Nx Ny Nz < 2^31");
+  if (V < 1 || H < 1 || W < 1 || (long long)V * H * W >= (1ll << 31))
+    return set_err("lrf_tsdf_integrate: need V, H, W >= 1 and V H W < 2^31");
+  if (!vol->tsdf || !vol->weight || !depth || !cam2world || !focal || !center) return set_err("lrf_tsdf_integrate: null argument");
+  if (!vol->rgb != !rgb8) return set_err("lrf_tsdf_integrate: the volume's rgb and the frames' rgb8 go together");
+  if (!(vol->voxel > 0.0f)) return set_err("lrf_tsdf_integrate: voxel must be > 0");
+  if (!(vol->trunc > 0.0f)) return set_err("lrf_tsdf_integrate: trunc must be > 0");
+  if (!(d_min <= d_max)) return set_err("lrf_tsdf_integrate: need d_min <= d_max");
+  if (((uintptr_t)vol->tsdf | (uintptr_t)vol->weight | (uintptr_t)vol->rgb | (uintptr_t)depth | (uintptr_t)cam2world |
+       (uintptr_t)focal | (uintptr_t)center) & 3)
+    return set_err("lrf_tsdf_integrate: float arrays must be 4-byte aligned");
+  TsdfArgs a;
+  memset(&a, 0, sizeof(a));
+  a.tsdf = vol->tsdf; a.weight = vol->weight; a.rgb = vol->rgb;
+  a.Nx = vol->Nx; a.Ny = vol->Ny; a.Nz = vol->Nz; a.nxc = (vol->Nx + 63) / 64;
+  a.n_items = (long long)vol->Nz * vol->Ny * a.nxc;
+  a.ox = vol->origin[0]; a.oy = vol->origin[1]; a.oz = vol->origin[2]; a.voxel = vol->voxel; a.trunc = vol->trunc;
+  a.V = V; a.H = H; a.W = W; a.d_min = d_min; a.d_max = d_max;
+  const long long n_wg = (a.n_items + TSDF_NT / 64 - 1) / (TSDF_NT / 64);   // <= 2^31 / 4
+  hipLaunchKernelGGL(k_tsdf_integrate, dim3((unsigned)n_wg), dim3(TSDF_NT), 0, reinterpret_cast<hipStream_t>(stream), a, depth,
+                     rgb8, cam2world, focal, center);
+  LRF_HIP(hipGetLastError());
+  return 0;
+}
+
+extern "C" size_t lrf_mesh_workspace_bytes(int32_t Nx, int32_t Ny, int32_t Nz) {
+  using namespace lrf;
+  const long long n = mesh_points(Nx, Ny, Nz);
+  if (!n) return 0;
+  const size_t n_wg = (size_t)((n + MESH_NT - 1) / MESH_NT);
+  return ((size_t)n * sizeof(unsigned) + 2 * n_wg * sizeof(unsigned) + 255) & ~(size_t)255;
+}
+
+extern "C" int lrf_mesh_extract(const LrfMeshExtract* m, int64_t max_vertices, int64_t max_faces, float* vertices,
+                                uint8_t* rgb8_out, int32_t* faces, int64_t* counts, void* workspace, void* stream) {
+  using namespace lrf;
+  if (!m) return set_err("lrf_mesh_extract: null argument");
+  const long long n = mesh_points(m->Nx, m->Ny, m->Nz);
+  if (!n) return set_err("lrf_mesh_extract: need Nx, Ny, Nz >= 1 and Nx Ny Nz < 2^31");
+  if (!m->value || !vertices || !faces || !counts || !workspace) return set_err("lrf_mesh_extract: null argument");
+  if (!m->rgb != !rgb8_out) return set_err("lrf_mesh_extract: rgb and rgb8_out go together");
+  if (!(m->voxel > 0.0f)) return set_err("lrf_mesh_extract: voxel must be > 0");
+  if (m->level != m->level) return set_err("lrf_mesh_extract: level must not be NaN");
+  if (m->weight && !(m->min_weight > 0.0f)) return set_err("lrf_mesh_extract: min_weight must be > 0");
+  if (max_vertices < 0 || max_faces < 0 || max_vertices >= (1ll << 31) || max_faces >= (1ll << 31))
+    return set_err("lrf_mesh_extract: max_vertices and max_faces must lie in [0, 2^31)");
+  if (((uintptr_t)m->value | (uintptr_t)m->weight | (uintptr_t)m->rgb | (uintptr_t)vertices | (uintptr_t)faces | (uintptr_t)workspace) & 3)
+    return set_err("lrf_mesh_extract: float and int32 arrays and the workspace must be 4-byte aligned");
+  if ((uintptr_t)counts & 7) return set_err("lrf_mesh_extract: counts must be 8-byte aligned");
+  MeshArgs a;
+  memset(&a, 0, sizeof(a));
+  a.value = m->value; a.weight = m->weight; a.rgb = m->rgb;
+  a.Nx = m->Nx; a.Ny = m->Ny; a.Nz = m->Nz; a.n = (int)n;
+  a.ox = m->origin[0]; a.oy = m->origin[1]; a.oz = m->origin[2]; a.voxel = m->voxel;
+  a.level = m->level; a.min_weight = m->min_weight;
+  const int n_wg = (int)((n + MESH_NT - 1) / MESH_NT);
+  unsigned* info = static_cast<unsigned*>(workspace);
+  unsigned* wgv = info + n;
+  unsigned* wgf = wgv + n_wg;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(k_mesh_count, dim3(n_wg), dim3(MESH_NT), 0, st, a, info, wgv, wgf);
+  LRF_HIP(hipGetLastError());
+  hipLaunchKernelGGL(k_points_scan, dim3(2), dim3(PTS_SCAN_NT), 0, st, wgv, n_wg, reinterpret_cast<long long*>(counts));
+  LRF_HIP(hipGetLastError());
+  if (max_vertices == 0 && max_faces == 0) return 0;                 // a counting call: no row could be written
+  hipLaunchKernelGGL(k_mesh_emit, dim3(n_wg), dim3(MESH_NT), 0, st, a, info, wgv, wgf, (long long)max_vertices,
+                     (long long)max_faces, vertices, rgb8_out, faces);
+  LRF_HIP(hipGetLastError());
+  return 0;
+}

@@ -19,7 +19,8 @@
 //                   depth loads coalesce at stride 1, the neighbour gathers land on nearby lines).  The wave's ballot is the
 //                   keep word of its 64 candidates, stored by one lane; a workgroup covers PTS_WORDS_WG words and leaves
 //                   their popcount.
-//   k_points_scan   ONE workgroup turns the workgroup counts into exclusive bases in place and leaves the total in count[0].
+//   k_points_scan   ONE workgroup turns the workgroup counts into exclusive bases in place and leaves the total in count[0]
+//                   (a second workgroup would scan a second array: lrf_mesh.inl).
 //                   One small launch rather than decoupled look-back: there is one uint32 per 1024 candidates (14 400 for 64
 //                   frames of 360 x 640), the scan is a fixed sequence with no spinning on other workgroups' progress, it
 //                   is capturable and it cannot deadlock under any scheduling.
@@ -69,6 +70,26 @@ __device__ __forceinline__ bool pts_world(const PointsArgs& a, int c, float f, f
   return true;
 }
 
+// step 3's projection, shared with the TSDF integration (lrf_mesh.inl): world point pw into the camera M [3,4] (camera-to-world)
+// of an H x W pinhole image.  false behind the camera (nz = -q.z <= 0) or outside the image; else nz and the nearest pixel
+// (iu, iw), ties to even.
+__device__ __forceinline__ bool reproject(const float* __restrict__ M, const float (&pw)[3], float f, float cx, float cy, int W,
+                                          int H, float& nz, int& iu, int& iw) {
+#pragma clang fp contract(off)
+  const float dx = pw[0] - M[3], dy = pw[1] - M[7], dz = pw[2] - M[11];
+  const float qx = (M[0] * dx + M[4] * dy) + M[8] * dz;
+  const float qy = (M[1] * dx + M[5] * dy) + M[9] * dz;
+  const float qz = (M[2] * dx + M[6] * dy) + M[10] * dz;
+  nz = -qz;
+  if (!(nz > 0.0f)) return false;
+  const float u = qx / nz * f + cx - 0.5f;
+  const float w = -qy / nz * f + cy - 0.5f;
+  const float ru = rintf(u), rw = rintf(w);
+  if (!(ru >= 0.0f && ru < 2147483648.0f && rw >= 0.0f && rw < 2147483648.0f)) return false;   // NaN fails
+  iu = (int)ru; iw = (int)rw;
+  return iu < W && iw < H;
+}
+
 __device__ __forceinline__ bool pts_consistent(const PointsArgs& a, int v, const float (&pw)[3], float f, float cx, float cy) {
 #pragma clang fp contract(off)
   int in_range = 0, pass = 0;
@@ -76,19 +97,9 @@ __device__ __forceinline__ bool pts_consistent(const PointsArgs& a, int v, const
     const long long nl = (long long)v + a.neigh[k];
     if (nl < 0 || nl >= a.V) continue;                              // counts neither for nor against
     ++in_range;
-    const float* M = a.c2w + (size_t)nl * 12;
-    const float dx = pw[0] - M[3], dy = pw[1] - M[7], dz = pw[2] - M[11];
-    const float qx = (M[0] * dx + M[4] * dy) + M[8] * dz;
-    const float qy = (M[1] * dx + M[5] * dy) + M[9] * dz;
-    const float qz = (M[2] * dx + M[6] * dy) + M[10] * dz;
-    const float nz = -qz;
-    if (!(nz > 0.0f)) continue;
-    const float u = qx / nz * f + cx - 0.5f;
-    const float w = -qy / nz * f + cy - 0.5f;
-    const float ru = rintf(u), rw = rintf(w);
-    if (!(ru >= 0.0f && ru < 2147483648.0f && rw >= 0.0f && rw < 2147483648.0f)) continue;   // NaN fails
-    const int iu = (int)ru, iw = (int)rw;
-    if (iu >= a.W || iw >= a.H) continue;
+    float nz;
+    int iu, iw;
+    if (!reproject(a.c2w + (size_t)nl * 12, pw, f, cx, cy, a.W, a.H, nz, iu, iw)) continue;
     const float dn = a.depth[(size_t)nl * a.H * a.W + (size_t)iw * a.W + iu];
     if (!pts_finite_pos(dn)) continue;
     if (fabsf(nz - dn) <= a.rel_tol * dn) ++pass;
@@ -125,11 +136,13 @@ __global__ __launch_bounds__(PTS_NT) void k_points_mark(PointsArgs a, unsigned l
   }
 }
 
-// one workgroup: wg[i] <- sum of wg[0..i), count[0] <- the total
+// one workgroup per array: workgroup b turns wg[b n_wg + i] into the sum of wg[b n_wg + 0..i) (modulo 2^32) and leaves the
+// true total in count[b].  The point fusion scans one array; the mesh extraction (lrf_mesh.inl) its vertex and face counts.
 __global__ __launch_bounds__(PTS_SCAN_NT) void k_points_scan(unsigned* __restrict__ wg, int n_wg, long long* __restrict__ count) {
   __shared__ unsigned part[PTS_SCAN_NT / 64];
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  unsigned carry = 0;
+  wg += (size_t)blockIdx.x * n_wg;
+  unsigned long long carry = 0;
   for (int base = 0; base < n_wg; base += PTS_SCAN_NT) {
     const int i = base + tid;
     const unsigned c = i < n_wg ? wg[i] : 0u;
@@ -146,11 +159,11 @@ __global__ __launch_bounds__(PTS_SCAN_NT) void k_points_scan(unsigned* __restric
       if (w < wv) pre += p;
       tot += p;
     }
-    if (i < n_wg) wg[i] = carry + pre + (s - c);
+    if (i < n_wg) wg[i] = (unsigned)carry + pre + (s - c);
     carry += tot;
     __syncthreads();
   }
-  if (tid == 0) count[0] = (long long)carry;
+  if (tid == 0) count[blockIdx.x] = (long long)carry;
 }
 
 __global__ __launch_bounds__(PTS_NT) void k_points_write(PointsArgs a, const unsigned long long* __restrict__ bits,

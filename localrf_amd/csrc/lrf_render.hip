@@ -1162,6 +1162,7 @@ static hipError_t lds_opt_in() {
 #include "lrf_evalgeo.inl"
 #include "lrf_encode.inl"
 #include "lrf_points.inl"
+#include "lrf_mesh.inl"
 #include "lrf_reg.inl"
 #include "lrf_mask.inl"
 

@@ -1,0 +1,325 @@
+"""Rendered depth fused into a TSDF volume and a triangle mesh extracted from it on the GPU (csrc/lrf_mesh.inl through
+lrf_tsdf_integrate and lrf_mesh_extract).
+
+  TsdfVolume(origin, voxel, dims, trunc, device)   the three volume tensors; .integrate(frames) and .extract() -> mesh
+  extract_mesh(values, origin, voxel, level, ...)  marching tetrahedra of any [Nz,Ny,Nx] device tensor
+  scene_mesh(local_tensorfs, W, H, voxel=...)      novel_views.render_poses in batches, each integrated and dropped, then extract
+  pointcloud.write_ply(path, vertices, rgb8, faces=faces) writes the result
+
+A volume is a lattice of Nx x Ny x Nz points at origin + (ix, iy, iz) * voxel, x fastest in memory.  Depth follows the
+convention of pointcloud.py: a multiple of the un-normalised camera direction whose z is -1, so the signed distance of a
+lattice point along its pixel's ray is depth - z.  Pinhole cameras only.  A mesh is a dict: vertices [Nv,3] fp32, faces [Nf,3]
+int32 (wound so that the normal points towards larger values: free space for a TSDF), rgb8 [Nv,3] uint8 or None, counts =
+(Nv, Nf) Python ints.  The same bytes on every run.  Every function checks its arguments on the host before its first launch.
+CPU tensors raise NativeError: there is no torch fallback.
+"""
+import ctypes as C
+import math
+
+import numpy as np
+import torch
+
+from . import _native as N
+from ._native import NativeError
+from .pointcloud import _check_depth, _check_intrinsics, _check_poses, _dev_f32
+
+_INT32 = (1 << 31) - 1
+BYTES_PER_VOXEL = 8                            # tsdf and weight
+BYTES_PER_VOXEL_RGB = 12
+
+
+def _check_lattice(origin, voxel, dims):
+    o = np.asarray(origin.detach().cpu() if torch.is_tensor(origin) else origin, dtype=np.float64).reshape(-1)
+    if o.size != 3 or not np.isfinite(o).all():
+        raise ValueError(f"origin must hold 3 finite values, got {origin!r}")
+    voxel = float(voxel)
+    if not (voxel > 0 and math.isfinite(voxel)):
+        raise ValueError(f"voxel must be a finite number > 0, got {voxel}")
+    if len(dims) != 3 or any(int(d) != d or int(d) < 1 for d in dims):
+        raise ValueError(f"dims must be (Nx, Ny, Nz) integers >= 1, got {dims!r}")
+    dims = tuple(int(d) for d in dims)
+    if dims[0] * dims[1] * dims[2] > _INT32:
+        raise ValueError(f"dims {dims} hold {dims[0] * dims[1] * dims[2]} lattice points; a volume takes Nx Ny Nz < 2^31")
+    return tuple(float(v) for v in o), voxel, dims
+
+
+def _check_extract(level, min_weight, max_vertices, max_faces):
+    level, min_weight = float(level), float(min_weight)
+    if math.isnan(level):
+        raise ValueError("level must not be NaN")
+    if not min_weight > 0:
+        raise ValueError(f"min_weight must be > 0, got {min_weight}")
+    for name, cap in (("max_vertices", max_vertices), ("max_faces", max_faces)):
+        if cap is not None and (int(cap) != cap or not 0 <= int(cap) <= _INT32):
+            raise ValueError(f"{name} must be None or an integer in [0, 2^31), got {cap!r}")
+    return level, min_weight
+
+
+def _check_range(depth_range):
+    if len(depth_range) != 2:
+        raise ValueError(f"depth_range must be (d_min, d_max), got {depth_range!r}")
+    d_min, d_max = float(depth_range[0]), float(depth_range[1])
+    if not d_min <= d_max:
+        raise ValueError(f"depth_range needs d_min <= d_max, got {depth_range!r}")
+    return d_min, d_max
+
+
+def _extract(value, weight, rgb, origin, voxel, dims, level, min_weight, max_vertices, max_faces):
+    """Checked arguments, contiguous fp32 device tensors -> the mesh dict."""
+    dev = value.device
+    Nx, Ny, Nz = dims
+    ws = N.workspace("lrf_mesh", dev, Nx, Ny, Nz)
+    counts = torch.empty(2, dtype=torch.int64, device=dev)
+    a = N.LrfMeshExtract()
+    a.value, a.weight, a.rgb = value.data_ptr(), None if weight is None else weight.data_ptr(), None if rgb is None else rgb.data_ptr()
+    a.Nx, a.Ny, a.Nz = Nx, Ny, Nz
+    a.origin[0], a.origin[1], a.origin[2] = origin
+    a.voxel, a.level, a.min_weight = voxel, level, min_weight
+
+    def run(cap_v, cap_f):
+        v = torch.empty(max(cap_v, 1), 3, dtype=torch.float32, device=dev)
+        f = torch.empty(max(cap_f, 1), 3, dtype=torch.int32, device=dev)
+        c = None if rgb is None else torch.empty(max(cap_v, 1), 3, dtype=torch.uint8, device=dev)
+        N.launch("lrf_mesh_extract", dev, C.byref(a), cap_v, cap_f, v.data_ptr(), None if c is None else c.data_ptr(),
+                 f.data_ptr(), counts.data_ptr(), ws.data_ptr(), guard=True)
+        nv, nf = (int(x) for x in counts.tolist())                  # the read-back (it also orders ws's release)
+        return v, f, c, nv, nf
+
+    if max_vertices is None or max_faces is None:                   # a counting call sizes the buffers: one more read-back
+        _, _, _, nv, nf = run(0, 0)
+        cap_v = nv if max_vertices is None else int(max_vertices)
+        cap_f = nf if max_faces is None else int(max_faces)
+        if nv > _INT32 or nf > _INT32:
+            raise ValueError(f"the mesh holds {nv} vertices and {nf} faces; each count must stay below 2^31")
+    else:
+        cap_v, cap_f = int(max_vertices), int(max_faces)
+    v, f, c, nv, nf = run(cap_v, cap_f)
+    if nv > cap_v or nf > cap_f:
+        err = ValueError(f"the mesh holds {nv} vertices and {nf} faces; max_vertices={max_vertices} and max_faces={max_faces} "
+                         "do not fit them")
+        err.partial = {"vertices": v[:min(nv, cap_v)], "faces": f[:min(nf, cap_f)], "rgb8": None if c is None else c[:min(nv, cap_v)],
+                       "counts": (nv, nf)}                          # the rows inside capacity, as written
+        raise err
+    return {"vertices": v[:nv], "faces": f[:nf], "rgb8": None if c is None else c[:nv], "counts": (nv, nf)}
+
+
+def extract_mesh(values, origin, voxel, level, weight=None, rgb=None, min_weight=1.0, max_vertices=None, max_faces=None):
+    """Marching tetrahedra (the Kuhn split, six per cell: no ambiguous case, watertight by construction) of values
+    [Nz,Ny,Nx] (device) on the lattice origin + (ix, iy, iz) * voxel at `level`.  A lattice point is inside when its value is
+    < level; with weight [Nz,Ny,Nx] only cells whose eight corners have weight >= min_weight give faces; rgb [Nz,Ny,Nx,3] in
+    [0, 1] gives vertex colours, interpolated like the positions and encoded as novel_views.encode_frames encodes.
+    Vertices come in (z, y, x, edge) order and faces in (cell, tetrahedron, triangle) order.  With max_vertices and max_faces
+    given, the buffers hold that many rows and the call costs one read-back; a mesh that does not fit raises ValueError naming
+    both true counts (its .partial holds the rows inside capacity).  With either None a counting call sizes the buffers
+    first: one more read-back.  Returns the mesh dict of the module docstring."""
+    if not torch.is_tensor(values):
+        raise TypeError("values must be a torch tensor")
+    if not values.is_floating_point():
+        raise ValueError(f"values must hold floating-point values, got {values.dtype}")
+    if values.dim() != 3 or min(values.shape) < 1:
+        raise ValueError(f"values must be [Nz, Ny, Nx] with Nz, Ny, Nx > 0, got {tuple(values.shape)}")
+    Nz, Ny, Nx = (int(s) for s in values.shape)
+    origin, voxel, dims = _check_lattice(origin, voxel, (Nx, Ny, Nz))
+    for name, t, shape in (("weight", weight, (Nz, Ny, Nx)), ("rgb", rgb, (Nz, Ny, Nx, 3))):
+        if t is None:
+            continue
+        if not torch.is_tensor(t):
+            raise TypeError(f"{name} must be a torch tensor or None")
+        if not t.is_floating_point() or tuple(t.shape) != shape:
+            raise ValueError(f"{name} must be a floating-point tensor of shape {shape}, got {t.dtype} {tuple(t.shape)}")
+        if t.device != values.device:
+            raise ValueError(f"{name} and values must live on the same device")
+    level, min_weight = _check_extract(level, min_weight, max_vertices, max_faces)
+    N.require_gpu(values, "values", "the mesh extraction")
+    return _extract(N.conform(values), None if weight is None else N.conform(weight), None if rgb is None else N.conform(rgb),
+                    origin, voxel, dims, level, min_weight, max_vertices, max_faces)
+
+
+class TsdfVolume:
+    """A truncated signed-distance volume on the device: tsdf [Nz,Ny,Nx] (starts at 1), weight [Nz,Ny,Nx] (starts at 0: the
+    number of frames that saw the point) and, with colours, rgb [Nz,Ny,Nx,3] in [0, 1] (starts at 0).  dims = (Nx, Ny, Nz);
+    trunc is the truncation distance in world units."""
+
+    def __init__(self, origin, voxel, dims, trunc, device, colours=True):
+        self.origin, self.voxel, self.dims = _check_lattice(origin, voxel, dims)
+        self.trunc = float(trunc)
+        if not (self.trunc > 0 and math.isfinite(self.trunc)):
+            raise ValueError(f"trunc must be a finite number > 0, got {trunc}")
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise NativeError(f"localrf_amd.mesh: a TsdfVolume on {dev}; the integration can run only on an AMD GPU (HIP kernels). "
+                              "There is no CPU fallback.")
+        Nx, Ny, Nz = self.dims
+        self.tsdf = torch.ones(Nz, Ny, Nx, dtype=torch.float32, device=dev)
+        self.weight = torch.zeros(Nz, Ny, Nx, dtype=torch.float32, device=dev)
+        self.rgb = torch.zeros(Nz, Ny, Nx, 3, dtype=torch.float32, device=dev) if colours else None
+
+    @staticmethod
+    def nbytes(dims, colours=True):
+        return int(dims[0]) * int(dims[1]) * int(dims[2]) * (BYTES_PER_VOXEL + (BYTES_PER_VOXEL_RGB if colours else 0))
+
+    def integrate(self, depth, poses, focal, center, rgb=None, depth_range=(0.0, math.inf)):
+        """Fold V frames into the volume, in frame order: depth [V,H,W] (device), poses [V,3,4] camera-to-world, focal (one
+        value) and center (cx, cy) as pointcloud.fuse_points takes them, rgb [V,H,W,3] float (encoded as encode_frames does) or
+        uint8 -- required with colours, refused without.  Per lattice point and frame: the point is projected to its nearest
+        pixel; with dn the depth there (finite, positive, inside depth_range), sdf = dn - z; the frame is skipped when
+        sdf < -trunc (the point lies behind the surface by more than trunc), else s = min(1, sdf / trunc) enters the running
+        means tsdf = (tsdf weight + s) / (weight + 1) and rgb, and weight += 1.  One launch, the volume read and written
+        once; no read-back.  Calls add up: frames k..V on top of frames 0..k leave the bits of one call over 0..V."""
+        V, H, W = _check_depth(depth)
+        if (rgb is not None) != (self.rgb is not None):
+            raise ValueError("rgb goes with a volume that keeps colours: pass rgb to a TsdfVolume(colours=True) and only to it")
+        if rgb is not None:
+            if not torch.is_tensor(rgb):
+                raise TypeError("rgb must be a torch tensor or None")
+            if not (rgb.is_floating_point() or rgb.dtype is torch.uint8):
+                raise ValueError(f"rgb must hold floating-point or uint8 values, got {rgb.dtype}")
+            if tuple(rgb.shape) != (V, H, W, 3):
+                raise ValueError(f"rgb must be {(V, H, W, 3)} to go with depth {tuple(depth.shape)}, got {tuple(rgb.shape)}")
+            if rgb.device != depth.device:
+                raise ValueError("rgb and depth must live on the same device")
+        poses = _check_poses(poses, V)
+        focal, center = _check_intrinsics(focal, center, False)
+        d_min, d_max = _check_range(depth_range)
+        N.require_gpu(depth, "depth", "the TSDF integration")
+        dev = self.tsdf.device
+        if depth.device != dev:
+            raise ValueError(f"depth lives on {depth.device}, the volume on {dev}")
+        rgb8 = None
+        if rgb is not None:
+            if rgb.dtype is torch.uint8:
+                rgb8 = rgb.contiguous()
+            else:
+                from .novel_views import encode_frames
+                rgb8 = encode_frames(rgb.detach(), depth.detach())[0]
+        depth = N.conform(depth)
+        poses = poses.detach().to(device=dev, dtype=torch.float32).contiguous()
+        f, c = _dev_f32(focal, 1, dev), _dev_f32(center, 2, dev)
+        a = N.LrfTsdfVolume()
+        a.tsdf, a.weight, a.rgb = self.tsdf.data_ptr(), self.weight.data_ptr(), None if self.rgb is None else self.rgb.data_ptr()
+        a.Nx, a.Ny, a.Nz = self.dims
+        a.origin[0], a.origin[1], a.origin[2] = self.origin
+        a.voxel, a.trunc = self.voxel, self.trunc
+        N.launch("lrf_tsdf_integrate", dev, C.byref(a), depth.data_ptr(), None if rgb8 is None else rgb8.data_ptr(),
+                 poses.data_ptr(), f.data_ptr(), c.data_ptr(), V, H, W, d_min, d_max, guard=True)
+        return self
+
+    def extract(self, level=0.0, min_weight=1.0, max_vertices=None, max_faces=None):
+        """The mesh of the surface tsdf = level over the cells every corner of which at least min_weight frames saw:
+        extract_mesh(self.tsdf, ..., weight=self.weight, rgb=self.rgb); see there for the capacities and the read-backs."""
+        level, min_weight = _check_extract(level, min_weight, max_vertices, max_faces)
+        return _extract(self.tsdf, self.weight, self.rgb, self.origin, self.voxel, self.dims, level, min_weight, max_vertices,
+                        max_faces)
+
+
+_RENDER_KEYS = ("test_frames", "frame_indices", "floater_thresh", "chunk")
+_MESH_KEYS = ("depth_range", "level", "min_weight", "max_vertices", "max_faces", "colours", "frames_per_call")
+
+
+def _lattice_of_box(lo, hi, voxel):
+    lo, hi = np.asarray(lo, np.float64).reshape(-1), np.asarray(hi, np.float64).reshape(-1)
+    if lo.size != 3 or hi.size != 3 or not (np.isfinite(lo).all() and np.isfinite(hi).all()) or not (lo <= hi).all():
+        raise ValueError(f"bounds must be ((x0, y0, z0), (x1, y1, z1)) with finite x0 <= x1, y0 <= y1, z0 <= z1, got {(lo, hi)!r}")
+    dims = tuple(int(math.ceil((b - a) / voxel)) + 1 for a, b in zip(lo, hi))
+    return tuple(float(v) for v in lo), dims
+
+
+def scene_mesh(local_tensorfs, W, H, voxel, bounds=None, poses=None, trunc=None, max_bytes=4 << 30, **options):
+    """A scene's surface as a triangle mesh: its frames rendered by novel_views.render_poses frames_per_call (default 8) at
+    a time, each batch integrated into one TsdfVolume and dropped -- only the volume stays resident, not the frames -- then
+    TsdfVolume.extract.  poses=None renders the scene's own get_cam2world(), each frame through itself; otherwise poses
+    [N,3,4] as render_poses takes them.  voxel is the lattice spacing in world units.  bounds = ((x0, y0, z0), (x1, y1, z1))
+    is covered by ceil((x1 - x0) / voxel) + 1 points per axis from (x0, y0, z0); bounds=None renders every frame once more
+    beforehand and takes the box of pointcloud.fuse_points over the depths inside depth_range, grown by trunc on every
+    side: one more render pass and one more read-back of the box.  trunc=None means 3 * voxel: a convenience, not a measured
+    optimum -- it should exceed the depth noise of the scene.  options: depth_range, level, min_weight, max_vertices,
+    max_faces, colours (default True), frames_per_call and render_poses' test_frames, frame_indices, floater_thresh, chunk.
+    A volume above max_bytes raises ValueError before it is allocated and, with bounds given, before anything is rendered.
+    Pinhole scenes only.  Returns the mesh dict of the module docstring with "volume": the TsdfVolume."""
+    from . import novel_views, pointcloud
+    unknown = sorted(set(options) - set(_MESH_KEYS) - set(_RENDER_KEYS))
+    if unknown:
+        raise TypeError(f"scene_mesh: unknown options {unknown}")
+    W, H = int(W), int(H)
+    if W <= 0 or H <= 0:
+        raise ValueError(f"need W, H > 0, got {W} x {H}")
+    voxel = float(voxel)
+    if not (voxel > 0 and math.isfinite(voxel)):
+        raise ValueError(f"voxel must be a finite number > 0, got {voxel}")
+    trunc = 3.0 * voxel if trunc is None else float(trunc)
+    if not (trunc > 0 and math.isfinite(trunc)):
+        raise ValueError(f"trunc must be a finite number > 0, got {trunc}")
+    lt = local_tensorfs
+    if lt.fov == 360:
+        raise ValueError("scene_mesh: the integration needs a pinhole camera: there is no reprojection at 360 degrees")
+    depth_range = options.get("depth_range", (0.0, math.inf))
+    _check_range(depth_range)
+    level, min_weight = _check_extract(options.get("level", 0.0), options.get("min_weight", 1.0), options.get("max_vertices"),
+                                       options.get("max_faces"))
+    colours = bool(options.get("colours", True))
+    per_call = options.get("frames_per_call", 8)
+    if int(per_call) != per_call or int(per_call) < 1:
+        raise ValueError(f"frames_per_call must be an integer >= 1, got {per_call!r}")
+    per_call = int(per_call)
+    render = {k: options[k] for k in _RENDER_KEYS if k in options}
+    if poses is None:
+        n = len(lt.r_c2w)
+        render.setdefault("frame_indices", list(range(n)))
+    else:
+        n = int(novel_views._poses(poses).shape[0])
+    if n < 1:
+        raise ValueError("scene_mesh: no frame to render")
+    if per_call * H * W > _INT32:
+        raise ValueError(f"scene_mesh: {per_call} frames of {H} x {W} per call; one integration takes V H W < 2^31")
+
+    def volume_for(lo, dims):
+        _check_lattice(lo, voxel, dims)
+        need = TsdfVolume.nbytes(dims, colours)
+        if need > int(max_bytes):
+            raise ValueError(f"scene_mesh: a volume of {dims[0]} x {dims[1]} x {dims[2]} points takes {need} bytes; max_bytes is "
+                             f"{int(max_bytes)}")
+        return lo, dims
+
+    if bounds is not None:
+        if len(bounds) != 2:
+            raise ValueError(f"bounds must be ((x0, y0, z0), (x1, y1, z1)), got {bounds!r}")
+        lo, dims = volume_for(*_lattice_of_box(bounds[0], bounds[1], voxel))
+    dev = lt.blending_weights.device
+    if dev.type != "cuda":
+        raise NativeError(f"localrf_amd.mesh: the scene lives on {dev}; rendering runs only on an AMD GPU (HIP kernels). "
+                          "There is no CPU fallback.")
+    if poses is None:
+        with torch.no_grad():
+            poses = lt.get_cam2world().detach()
+    poses = novel_views._poses(poses)
+    fi = render.pop("frame_indices", None)
+    if fi is None:
+        fi = novel_views.nearest_frames(lt, poses)
+    fi = fi.tolist() if hasattr(fi, "tolist") else list(fi)
+    if len(fi) < n:
+        raise ValueError(f"frame_indices holds {len(fi)} entries for {n} poses")
+    focal, center = lt.focal(W), lt.center(W, H)
+
+    def batches():
+        for i0 in range(0, n, per_call):
+            i1 = min(n, i0 + per_call)
+            out = novel_views.render_poses(lt, poses[i0:i1], W, H, frame_indices=fi[i0:i1], encode=colours, **render)
+            yield poses[i0:i1], out["depth"], out.get("rgb8") if colours else None
+
+    if bounds is None:
+        box = None
+        for p, depth, _ in batches():
+            xyz = pointcloud.fuse_points(None, depth, p, focal, center, depth_range=depth_range)["xyz"]
+            if xyz.shape[0]:
+                cur = torch.stack([xyz.amin(0), -xyz.amax(0)])
+                box = cur if box is None else torch.minimum(box, cur)
+        if box is None:
+            raise ValueError("scene_mesh: no rendered depth lies inside depth_range; there is no box to cover")
+        box = box.double().cpu().numpy()                            # the box's read-back
+        lo, dims = volume_for(*_lattice_of_box(box[0] - trunc, -box[1] + trunc, voxel))
+    vol = TsdfVolume(lo, voxel, dims, trunc, dev, colours=colours)
+    for p, depth, rgb8 in batches():
+        vol.integrate(depth, p, focal, center, rgb=rgb8, depth_range=depth_range)
+    mesh = vol.extract(level, min_weight, options.get("max_vertices"), options.get("max_faces"))
+    mesh["volume"] = vol
+    return mesh

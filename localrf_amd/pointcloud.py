@@ -3,7 +3,7 @@
   backproject(depth, poses, W, H, ...)          every pixel with a finite positive depth -> (xyz [M,3], src [M,2])
   fuse_points(rgb, depth, poses, focal, ...)    strided, depth-ranged, multi-view-consistent points with colours
   scene_point_cloud(local_tensorfs, W, H, ...)  novel_views.render_poses, then fuse_points with the scene's intrinsics
-  write_ply(path, xyz, rgb8, normals)           binary little-endian PLY from one device -> host copy
+  write_ply(path, xyz, rgb8, normals, faces)    binary little-endian PLY from one device -> host copy
 
 Conventions (the reference's): a rendered depth is sum w z / |d|, a multiple of the UN-normalised camera direction whose z
 is -1 for a pinhole (tensorBase.py:615, utils/ray_utils.py:14-24); the camera point is direction * depth (utils/utils.py:15-48)
@@ -256,20 +256,23 @@ def scene_point_cloud(local_tensorfs, W, H, poses=None, max_bytes=4 << 30, norma
     return cloud
 
 
-def ply_header(n, colours, normals=False):
+def ply_header(n, colours, normals=False, faces=None):
     lines = ["ply", "format binary_little_endian 1.0", f"element vertex {int(n)}",
              "property float x", "property float y", "property float z"]
     if normals:
         lines += ["property float nx", "property float ny", "property float nz"]
     if colours:
         lines += ["property uchar red", "property uchar green", "property uchar blue"]
+    if faces is not None:
+        lines += [f"element face {int(faces)}", "property list uchar int vertex_indices"]
     return ("\n".join(lines + ["end_header"]) + "\n").encode("ascii")
 
 
-def write_ply(path, xyz, rgb8=None, normals=None):
+def write_ply(path, xyz, rgb8=None, normals=None, faces=None):
     """Binary little-endian PLY (x y z float, nx ny nz float when normals are given, red green blue uchar when rgb8 is
     given) of xyz [M,3], normals [M,3] and rgb8 [M,3] uint8: tensors (one device -> host copy each) or numpy arrays.
-    Returns the number of vertices written."""
+    faces [F,3] (integers in [0, M), e.g. mesh.extract_mesh's) adds `element face F` with `property list uchar int
+    vertex_indices`: records of one byte 3 and three little-endian int32.  Returns the number of vertices written."""
     def host(t, dtype, name):
         a = t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
         if a.ndim != 2 or a.shape[1] != 3:
@@ -284,6 +287,15 @@ def write_ply(path, xyz, rgb8=None, normals=None):
     nrm = None if normals is None else host(normals, np.float32, "normals")
     if nrm is not None and nrm.shape[0] != pts.shape[0]:
         raise ValueError(f"{pts.shape[0]} points but {nrm.shape[0]} normals")
+    tri = None
+    if faces is not None:
+        f = faces.detach().cpu().numpy() if torch.is_tensor(faces) else np.asarray(faces)
+        if f.ndim != 2 or f.shape[1] != 3 or f.dtype.kind not in "iu":
+            raise ValueError(f"faces must be [F, 3] integers, got {f.dtype} {f.shape}")
+        if f.size and (int(f.min()) < 0 or int(f.max()) >= pts.shape[0]):
+            raise ValueError(f"faces index vertices outside [0, {pts.shape[0]})")
+        tri = np.empty(f.shape[0], dtype=np.dtype([("n", "u1"), ("v", "<i4", 3)]))
+        tri["n"], tri["v"] = 3, f
     if cols is None and nrm is None:
         rec = pts.astype("<f4")
     else:
@@ -295,6 +307,8 @@ def write_ply(path, xyz, rgb8=None, normals=None):
         if cols is not None:
             rec["c"] = cols
     with open(path, "wb") as fh:
-        fh.write(ply_header(pts.shape[0], cols is not None, nrm is not None))
+        fh.write(ply_header(pts.shape[0], cols is not None, nrm is not None, None if tri is None else tri.shape[0]))
         fh.write(rec.tobytes())
+        if tri is not None:
+            fh.write(tri.tobytes())
     return int(pts.shape[0])
