@@ -664,6 +664,27 @@ int lrf_mesh_extract(const LrfMeshExtract* m, int64_t max_vertices, int64_t max_
                      uint8_t* rgb8_out /* nullable */, int32_t* faces, int64_t* counts /* device [2] */, void* workspace,
                      void* stream);
 
+/* Depth quantiles of a ray: the distance at which its accumulated weight first reaches q; q = 0.5 is the median depth, which
+ * always lies on a surface the ray met (csrc/lrf_quantile.inl states the arithmetic: fp32 without contraction, one fixed
+ * summation order per ray).  With C_i the inclusive prefix sum of the weights lrf_render_fwd leaves in weight_out and i* the
+ * smallest i with C_i >= q: t = clamp((q - C_{i*-1}) / w_{i*}, 0, 1), depth = (z_{i*} + t (z_{i*+1} - z_{i*})) / |d|.  A ray
+ * whose opacity never reaches q (or that meets a NaN weight first) gives depth exactly 0 and index -1.
+ * lrf_render_depth_quantiles: one forward render into the workspace, then one launch without atomics: the same bits on every
+ * run.  q: HOST array of K quantiles, 1 <= K <= 4, each in (0, 1], any order.  flags, floater_thresh: as lrf_render_fwd takes
+ * them.  depth [K,R]; wsum [K,R] (nullable): 1 where found, else 0; index int32 [K,R] (nullable): i* or -1; acc [R]
+ * (nullable): the forward's acc.  blend_w (nullable; [ceil(R / per_view)]) scales ray r's depth, wsum and acc by
+ * blend_w[r / per_view]; accumulate = 1 adds to depth / wsum / acc instead of overwriting them: a scene sums its fields in
+ * field order and divides depth by wsum at the end.  Refused before any launch: null pointers, R <= 0, S outside [2, 4096],
+ * K outside [1, 4], a q outside (0, 1] or NaN, unknown flag bits, per_view < 1 with blend_w, accumulate outside {0, 1},
+ * accumulate = 1 with index, blend_w without wsum, misaligned pointers (workspace: 256 bytes).  workspace:
+ * lrf_quantile_workspace_bytes(R, S) bytes = the forward's workspace, the [R,S] weights and 5 R floats of per-ray outputs (0 for
+ * a refused shape). */
+size_t lrf_quantile_workspace_bytes(int32_t R, int32_t S);
+int lrf_render_depth_quantiles(const LrfField* f, const float* rays, const float* z, int32_t R, int32_t S, uint32_t flags,
+                               float floater_thresh, const float* q /* host [K] */, int32_t K, const float* blend_w /* nullable */,
+                               int32_t per_view, int32_t accumulate, float* depth /* [K,R] */, float* wsum /* [K,R] or NULL */,
+                               int32_t* index /* [K,R] or NULL */, float* acc /* [R] or NULL */, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,6 +22,10 @@ void    lrf_debug_set_scatter_wgs(int n);         /* lrf_render_bwd: workgroups 
 /* float offset of (row, col) inside the ACT (0) / GRD (1) region of a training workspace (MFMA-fragment order,
  * csrc/lrf_common.h); buffer 2: X-block column of appearance channel col */
 int64_t lrf_debug_saved_row_offset(int buffer, uint64_t row, int col);
+/* k_depth_quantiles alone on caller-supplied weights w [R,S] (device), z [S], rays [R,6]; q: host [K], 1 <= K <= 4, each in
+ * (0, 1] -> depth [K,R], index int32 [K,R] (nullable).  The arithmetic of csrc/lrf_quantile.inl without a forward render. */
+int     lrf_depth_quantiles_from_weights(const float* w, const float* z, const float* rays, int32_t R, int32_t S, const float* q,
+                                         int32_t K, float* depth, int32_t* index, void* stream);
 
 #ifdef __cplusplus
 }

@@ -16,6 +16,8 @@ Public surface mirrors the reference's names:
                                     (rendered depth fused into a filtered, coloured world-space point cloud; no reference row)
   normals.render_normals / encode_normals, TensorVMSplit.render_normals / density_gradient
                                     (per-ray surface normals from the density gradient: normal maps, PLY normals; no reference row)
+  depth_quantiles.render_depth_quantiles / median_depth, TensorVMSplit.render_depth_quantiles
+                                    (median and quantile ray depth: the depth a fusion wants; no reference row)
   mesh.TsdfVolume / extract_mesh / scene_mesh
                                     (rendered depth fused into a TSDF volume, marching tetrahedra, PLY faces; no reference row)
 The arithmetic of TensorVMSplit.forward and of LocalTensorfs.forward (ray generation, field
@@ -33,7 +35,8 @@ from . import diagnostics  # noqa: F401
 from . import novel_views  # noqa: F401
 from . import pointcloud  # noqa: F401
 from . import normals  # noqa: F401
+from . import depth_quantiles  # noqa: F401
 from . import mesh  # noqa: F401
 from .frames import DeviceFrames  # noqa: F401
 
-__all__ = ["TensorVMSplit", "AlphaGridMask", "MLPRender_Fea_late_view", "LocalTensorfs", "rays", "losses", "metrics", "diagnostics", "novel_views", "pointcloud", "normals", "mesh", "NativeError", "FusedAdam", "DeviceFrames"]
+__all__ = ["TensorVMSplit", "AlphaGridMask", "MLPRender_Fea_late_view", "LocalTensorfs", "rays", "losses", "metrics", "diagnostics", "novel_views", "pointcloud", "normals", "depth_quantiles", "mesh", "NativeError", "FusedAdam", "DeviceFrames"]

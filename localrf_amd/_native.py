@@ -242,6 +242,12 @@ SYMBOLS = {
     "lrf_normals_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "lrf_render_normals": (C.c_int, [C.POINTER(LrfField), _f, _f, C.c_int32, C.c_int32, C.c_uint32, C.c_float, _f, C.c_int32,
                                      C.c_int32, _f, _f, C.c_void_p, C.c_void_p]),
+    "lrf_quantile_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "lrf_render_depth_quantiles": (C.c_int, [C.POINTER(LrfField), _f, _f, C.c_int32, C.c_int32, C.c_uint32, C.c_float,
+                                             C.POINTER(C.c_float), C.c_int32, _f, C.c_int32, C.c_int32, _f, _f, C.c_void_p, _f,
+                                             C.c_void_p, C.c_void_p]),
+    "lrf_depth_quantiles_from_weights": (C.c_int, [_f, _f, _f, C.c_int32, C.c_int32, C.POINTER(C.c_float), C.c_int32, _f,
+                                                   C.c_void_p, C.c_void_p]),
     "lrf_scene_blend_bwd": (C.c_int, [_f, _f, _f, _f, _f, C.c_int32, C.c_int32, C.c_int32, _f, _f, _f,
                                       C.c_void_p]),
 }

@@ -1486,3 +1486,4 @@ int lrf_sample_ray_contracted(const float* rays_o, const float* rays_d, const fl
 }  // extern "C"
 
 #include "lrf_normals.inl"
+#include "lrf_quantile.inl"

@@ -671,6 +671,47 @@ class TensorVMSplit(torch.nn.Module):
         z = z.detach().contiguous().float().view(-1)
         return self._native_normals(rays, z, self._flags(True), float(floater_thresh))
 
+    def _native_depth_quantiles(self, rays, z, flags, floater, q, blend_w=None, per_view=1, out=None, accumulate=False,
+                                want_index=False):
+        """lrf_render_depth_quantiles on checked device tensors: rays [R,6] and z [S] contiguous fp32, q a checked tuple of K
+        floats.  out=(depth [K,R], wsum [K,R], acc [R]): caller-owned contiguous tensors, overwritten or (accumulate) added
+        to -- a scene's sums over its fields, each scaled by blend_w[r // per_view].  -> (depth, wsum, acc, index or None)."""
+        R, S, K, dev = rays.shape[0], z.shape[0], len(q), rays.device
+        if out is None:
+            depth = torch.empty(K, R, dtype=torch.float32, device=dev)
+            wsum = torch.empty(K, R, dtype=torch.float32, device=dev)
+            acc = torch.empty(R, dtype=torch.float32, device=dev)
+        else:
+            depth, wsum, acc = out
+        index = torch.empty(K, R, dtype=torch.int32, device=dev) if want_index else None
+        if R == 0:
+            return depth, wsum, acc, index
+        self.layout.ensure(self)
+        ws = N.workspace("lrf_quantile", dev, R, S)
+        f = self.layout.c_field(self)
+        N.launch("lrf_render_depth_quantiles", dev, C.byref(f), N.ptr(rays), N.ptr(z), R, S, flags, float(floater),
+                 (C.c_float * K)(*q), K, N.ptr(blend_w), int(per_view), int(bool(accumulate)), N.ptr(depth), N.ptr(wsum),
+                 N.ptr(index), N.ptr(acc), ws.data_ptr())
+        return depth, wsum, acc, index
+
+    def render_depth_quantiles(self, rays_chunk, q=(0.5,), N_samples=-1, floater_thresh=0, return_index=False):
+        """rays_chunk [R,6] -> (depth [K,R], acc [R]) and, with return_index, the crossing sample index [K,R] int32: for each
+        q_k (up to 4, each in (0, 1], any order) the distance at which the accumulated weight of the ray -- the weights
+        render_weights returns -- first reaches q_k, interpolated linearly in accumulated weight inside the crossing sample's
+        interval and divided by |d| as the expected depth is.  q = 0.5 is the median depth.  A ray whose opacity never
+        reaches q_k gives depth exactly 0 and index -1.  No autograd."""
+        from .depth_quantiles import check_q
+        q = check_q(q)
+        N.require_gpu(rays_chunk, "rays_chunk", _FEATURE)
+        if rays_chunk.dim() != 2 or rays_chunk.shape[1] != 6:
+            raise ValueError(f"rays_chunk must be [R, 6], got {tuple(rays_chunk.shape)}")
+        z = self.z_schedule(False, N_samples, rays_chunk.device)
+        rays = rays_chunk.detach().contiguous().float()
+        z = z.detach().contiguous().float().view(-1)
+        depth, _, acc, index = self._native_depth_quantiles(rays, z, self._flags(True), float(floater_thresh), q,
+                                                            want_index=bool(return_index))
+        return (depth, acc, index) if return_index else (depth, acc)
+
     def compute_appfeature(self, xyz_sampled):
         """tensoRF.py:153-196 on normalised coordinates [P,3] -> [P,27]."""
         N.require_gpu(xyz_sampled, "xyz_sampled", _FEATURE)

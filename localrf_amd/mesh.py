@@ -224,7 +224,8 @@ def _lattice_of_box(lo, hi, voxel):
     return tuple(float(v) for v in lo), dims
 
 
-def scene_mesh(local_tensorfs, W, H, voxel, bounds=None, poses=None, trunc=None, max_bytes=4 << 30, **options):
+def scene_mesh(local_tensorfs, W, H, voxel, bounds=None, poses=None, trunc=None, max_bytes=4 << 30, depth="expected",
+               max_spread=None, **options):
     """A scene's surface as a triangle mesh: its frames rendered by novel_views.render_poses frames_per_call (default 8) at
     a time, each batch integrated into one TsdfVolume and dropped -- only the volume stays resident, not the frames -- then
     TsdfVolume.extract.  poses=None renders the scene's own get_cam2world(), each frame through itself; otherwise poses
@@ -235,8 +236,14 @@ def scene_mesh(local_tensorfs, W, H, voxel, bounds=None, poses=None, trunc=None,
     optimum -- it should exceed the depth noise of the scene.  options: depth_range, level, min_weight, max_vertices,
     max_faces, colours (default True), frames_per_call and render_poses' test_frames, frame_indices, floater_thresh, chunk.
     A volume above max_bytes raises ValueError before it is allocated and, with bounds given, before anything is rendered.
+    depth="median" integrates the median depth of the same frames (depth_quantiles.median_depth: one more render pass per
+    batch) instead of render_poses' expected depth, which carves a phantom sheet between two surfaces a ray sees; the colours
+    stay render_poses'.  max_spread (with "median" only) also drops the pixels whose interquartile depth range (d75 - d25)
+    exceeds max_spread times their median, or that miss one of the three quartiles.  Any other depth= raises ValueError.
     Pinhole scenes only.  Returns the mesh dict of the module docstring with "volume": the TsdfVolume."""
     from . import novel_views, pointcloud
+    from .depth_quantiles import check_fusion_depth, fusion_depth
+    max_spread = check_fusion_depth("scene_mesh", depth, max_spread)
     unknown = sorted(set(options) - set(_MESH_KEYS) - set(_RENDER_KEYS))
     if unknown:
         raise TypeError(f"scene_mesh: unknown options {unknown}")
@@ -304,12 +311,15 @@ def scene_mesh(local_tensorfs, W, H, voxel, bounds=None, poses=None, trunc=None,
         for i0 in range(0, n, per_call):
             i1 = min(n, i0 + per_call)
             out = novel_views.render_poses(lt, poses[i0:i1], W, H, frame_indices=fi[i0:i1], encode=colours, **render)
-            yield poses[i0:i1], out["depth"], out.get("rgb8") if colours else None
+            dmap = out["depth"]
+            if depth == "median":
+                dmap = fusion_depth(lt, poses[i0:i1], W, H, max_spread, frame_indices=fi[i0:i1], **render)
+            yield poses[i0:i1], dmap, out.get("rgb8") if colours else None
 
     if bounds is None:
         box = None
-        for p, depth, _ in batches():
-            xyz = pointcloud.fuse_points(None, depth, p, focal, center, depth_range=depth_range)["xyz"]
+        for p, dmap, _ in batches():
+            xyz = pointcloud.fuse_points(None, dmap, p, focal, center, depth_range=depth_range)["xyz"]
             if xyz.shape[0]:
                 cur = torch.stack([xyz.amin(0), -xyz.amax(0)])
                 box = cur if box is None else torch.minimum(box, cur)
@@ -318,8 +328,8 @@ def scene_mesh(local_tensorfs, W, H, voxel, bounds=None, poses=None, trunc=None,
         box = box.double().cpu().numpy()                            # the box's read-back
         lo, dims = volume_for(*_lattice_of_box(box[0] - trunc, -box[1] + trunc, voxel))
     vol = TsdfVolume(lo, voxel, dims, trunc, dev, colours=colours)
-    for p, depth, rgb8 in batches():
-        vol.integrate(depth, p, focal, center, rgb=rgb8, depth_range=depth_range)
+    for p, dmap, rgb8 in batches():
+        vol.integrate(dmap, p, focal, center, rgb=rgb8, depth_range=depth_range)
     mesh = vol.extract(level, min_weight, options.get("max_vertices"), options.get("max_faces"))
     mesh["volume"] = vol
     return mesh

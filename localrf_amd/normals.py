@@ -18,9 +18,11 @@ from . import novel_views
 from .scene_ops import scene_rays
 
 
-def _render_group(lt, poses, vids, i0, i1, active, W, H, floater_thresh, chunk, normal, acc):
-    """Frames i0..i1 (one active set): per chunk of rays, the active fields in the reference's field order, the first
-    overwriting normal / acc and the others adding to them."""
+def _group_spans(lt, poses, vids, i0, i1, active, W, H, chunk):
+    """The per-field calls of frames i0..i1 (one active set), shared with depth_quantiles: yields (r0, r1, calls) per span of
+    rays, calls = [(f, z, flags, rays [r1 - r0, 6], blend_w)] over the active fields in the reference's field order, blend_w
+    being the field's weights from the span's first view on (per_view = H W).  A span holds whole views when chunk covers
+    one, else part of a single view."""
     dev = lt.blending_weights.device
     V, HW = i1 - i0, W * H
     fields = [lt.tensorfs[rf] for rf in active]
@@ -38,16 +40,23 @@ def _render_group(lt, poses, vids, i0, i1, active, W, H, floater_thresh, chunk, 
         z = f.z_schedule(False, -1, dev).detach().contiguous().float().view(-1)
         flags = f._flags(True) | (N.LRF_FLAG_PE_OFF if (f.fea_pe > 0 and not lt.is_refining) else 0)
         plan.append((f, z, flags))
-    normal, acc = normal[i0:i1].view(-1, 3), acc[i0:i1].view(-1)
     if chunk >= HW:                                                 # whole views per call
         step = (chunk // HW) * HW
         spans = [(r0, min(V * HW, r0 + step)) for r0 in range(0, V * HW, step)]
     else:                                                           # a call never crosses a view: one blend weight per call
         spans = [(v * HW + r0, v * HW + min(HW, r0 + chunk)) for v in range(V) for r0 in range(0, HW, chunk)]
     for r0, r1 in spans:
-        for k, (f, z, flags) in enumerate(plan):
-            f._native_normals(rays[k, r0:r1], z, flags, floater_thresh, blend_w=bw[k, r0 // HW:], per_view=HW,
-                              out=(normal[r0:r1], acc[r0:r1]), accumulate=k > 0)
+        yield r0, r1, [(f, z, flags, rays[k, r0:r1], bw[k, r0 // HW:]) for k, (f, z, flags) in enumerate(plan)]
+
+
+def _render_group(lt, poses, vids, i0, i1, active, W, H, floater_thresh, chunk, normal, acc):
+    """Frames i0..i1 (one active set): per chunk of rays, the active fields in the reference's field order, the first
+    overwriting normal / acc and the others adding to them."""
+    normal, acc = normal[i0:i1].view(-1, 3), acc[i0:i1].view(-1)
+    for r0, r1, calls in _group_spans(lt, poses, vids, i0, i1, active, W, H, chunk):
+        for k, (f, z, flags, rays, bw) in enumerate(calls):
+            f._native_normals(rays, z, flags, floater_thresh, blend_w=bw, per_view=W * H, out=(normal[r0:r1], acc[r0:r1]),
+                              accumulate=k > 0)
 
 
 def render_normals(local_tensorfs, poses, W, H, test_frames=(), frame_indices=None, start=0, floater_thresh=0, chunk=4096):

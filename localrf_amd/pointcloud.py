@@ -193,7 +193,8 @@ _FUSE_KEYS = ("stride", "depth_range", "neighbours", "rel_tol", "min_consistent"
 _RENDER_KEYS = ("test_frames", "frame_indices", "floater_thresh", "chunk", "frames_per_call")
 
 
-def scene_point_cloud(local_tensorfs, W, H, poses=None, max_bytes=4 << 30, normals=False, orient=False, **options):
+def scene_point_cloud(local_tensorfs, W, H, poses=None, max_bytes=4 << 30, normals=False, orient=False, depth="expected",
+                      max_spread=None, **options):
     """A scene's point cloud: its frames rendered by novel_views.render_poses, then fuse_points with the scene's focal(W),
     center(W, H) and fov.  poses=None renders the scene's own get_cam2world(), each frame through itself (frame_indices =
     0..F-1); otherwise poses [N,3,4] as render_poses takes them.  options: fuse_points' stride, depth_range, neighbours,
@@ -202,8 +203,14 @@ def scene_point_cloud(local_tensorfs, W, H, poses=None, max_bytes=4 << 30, norma
     max_bytes of them raises ValueError before anything is rendered.  A sliding window over frames is not provided.
     normals=True adds cloud["normal"] [M,3]: the scene's normal map (normals.render_normals, same poses and render options,
     16 more resident bytes per pixel) gathered at cloud["src"] and scaled to unit length, a zero-length row left as zero.
-    orient=True (with normals) flips a normal that faces away from its source camera, n . (x - t_cam) > 0."""
+    orient=True (with normals) flips a normal that faces away from its source camera, n . (x - t_cam) > 0.
+    depth="median" fuses the median depth of the same frames (depth_quantiles.median_depth: one more render pass) instead of
+    render_poses' expected depth, which lies in empty space where a ray sees two surfaces; the colours stay render_poses'.
+    max_spread (with "median" only) also drops the pixels whose interquartile depth range (d75 - d25) exceeds max_spread times
+    their median, or that miss one of the three quartiles.  Any other depth= raises ValueError."""
     from . import novel_views
+    from .depth_quantiles import check_fusion_depth, fusion_depth
+    max_spread = check_fusion_depth("scene_point_cloud", depth, max_spread)
     if orient and not normals:
         raise ValueError("scene_point_cloud: orient=True needs normals=True")
     unknown = sorted(set(options) - set(_FUSE_KEYS) - set(_RENDER_KEYS))
@@ -239,9 +246,11 @@ def scene_point_cloud(local_tensorfs, W, H, poses=None, max_bytes=4 << 30, norma
         with torch.no_grad():
             poses = lt.get_cam2world().detach()
     out = novel_views.render_poses(lt, poses, W, H, **render)
-    depth, rgb8 = out["depth"], out["rgb8"]
+    dmap, rgb8 = out["depth"], out["rgb8"]
     del out                                                         # the float colours go back to the allocator
-    cloud = fuse_points(rgb8, depth, novel_views._poses(poses), None if fov360 else lt.focal(W),
+    if depth == "median":
+        dmap = fusion_depth(lt, poses, W, H, max_spread, **{k: v for k, v in render.items() if k != "frames_per_call"})
+    cloud = fuse_points(rgb8, dmap, novel_views._poses(poses), None if fov360 else lt.focal(W),
                         None if fov360 else lt.center(W, H), fov360=fov360, **fuse)
     if normals:
         from .normals import render_normals, unit_normals
