@@ -17,7 +17,7 @@ import math
 
 import torch
 
-from . import normals, novel_views
+from .pose_plan import PosePlan
 
 MAX_QUANTILES = 4
 
@@ -35,20 +35,6 @@ def check_q(q):
     return q
 
 
-def _render_group(lt, poses, vids, i0, i1, active, W, H, q, floater_thresh, chunk, depth, acc):
-    """Frames i0..i1 (one active set): per span of rays, the active fields add bw depth and bw [found] in the reference's
-    field order into the span's own [K, n] sums, which are divided and stored at the end of the span."""
-    K = len(q)
-    depth, acc = depth[:, i0:i1].view(K, -1), acc[i0:i1].view(-1)
-    for r0, r1, calls in normals._group_spans(lt, poses, vids, i0, i1, active, W, H, chunk):
-        dsum = torch.empty(K, r1 - r0, dtype=torch.float32, device=acc.device)
-        wsum = torch.empty_like(dsum)
-        for k, (f, z, flags, rays, bw) in enumerate(calls):
-            f._native_depth_quantiles(rays, z, flags, floater_thresh, q, blend_w=bw, per_view=W * H,
-                                      out=(dsum, wsum, acc[r0:r1]), accumulate=k > 0)
-        depth[:, r0:r1] = torch.where(wsum > 0, dsum / wsum, torch.zeros_like(dsum))
-
-
 def render_depth_quantiles(local_tensorfs, poses, W, H, q=(0.5,), test_frames=(), frame_indices=None, start=0, floater_thresh=0,
                            chunk=4096):
     """The quantile depth maps of every pose: frame i at its pose through the blending weights of its nearest training frame,
@@ -60,14 +46,22 @@ def render_depth_quantiles(local_tensorfs, poses, W, H, q=(0.5,), test_frames=()
     [found_k] where some field reaches q and exactly 0 elsewhere, acc = sum_k blend_w acc_k.  Raises ValueError before any
     launch for a frame whose nearest frame has no active field."""
     q = check_q(q)
-    lt, poses, views, vids, _, groups, W, H, dev, _, _ = novel_views._prepare(
-        local_tensorfs, poses, W, H, test_frames, frame_indices, start, None, chunk, None, None, False)
-    n = len(views)
-    depth = torch.empty(len(q), n, H, W, dtype=torch.float32, device=dev)
+    plan = PosePlan(local_tensorfs, poses, W, H, test_frames, frame_indices, start, None, chunk).on_device()
+    n, W, H, dev, K = plan.n, plan.W, plan.H, plan.dev, len(q)
+    depth = torch.empty(K, n, H, W, dtype=torch.float32, device=dev)
     acc = torch.empty(n, H, W, dtype=torch.float32, device=dev)
     with torch.no_grad(), torch.cuda.device(dev):
-        for i0, i1, active in groups:
-            _render_group(lt, poses, vids, i0, i1, active, W, H, q, float(floater_thresh), int(chunk), depth, acc)
+        # per span of rays, the active fields add bw depth and bw [found] in the reference's field order into the span's own
+        # [K, n] sums, which are divided and stored at the end of the span
+        for i0, i1, active in plan.calls:
+            d, a = depth[:, i0:i1].view(K, -1), acc[i0:i1].view(-1)
+            for r0, r1, calls in plan.group_spans(i0, i1, active):
+                dsum = torch.empty(K, r1 - r0, dtype=torch.float32, device=dev)
+                wsum = torch.empty_like(dsum)
+                for k, (f, z, flags, rays, bw) in enumerate(calls):
+                    f._native_depth_quantiles(rays, z, flags, float(floater_thresh), q, blend_w=bw, per_view=W * H,
+                                              out=(dsum, wsum, a[r0:r1]), accumulate=k > 0)
+                d[:, r0:r1] = torch.where(wsum > 0, dsum / wsum, torch.zeros_like(dsum))
     return {"depth": depth, "acc": acc}
 
 

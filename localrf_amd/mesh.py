@@ -21,7 +21,9 @@ import torch
 
 from . import _native as N
 from ._native import NativeError
-from .pointcloud import _check_depth, _check_intrinsics, _check_poses, _dev_f32
+from . import depth_quantiles, novel_views, pointcloud
+from .pointcloud import SceneFrames, _check_depth, _check_intrinsics, _check_poses, _dev_f32
+from .pose_plan import nearest_frames
 
 _INT32 = (1 << 31) - 1
 BYTES_PER_VOXEL = 8                            # tsdf and weight
@@ -212,7 +214,6 @@ class TsdfVolume:
                         max_faces)
 
 
-_RENDER_KEYS = ("test_frames", "frame_indices", "floater_thresh", "chunk")
 _MESH_KEYS = ("depth_range", "level", "min_weight", "max_vertices", "max_faces", "colours", "frames_per_call")
 
 
@@ -241,22 +242,15 @@ def scene_mesh(local_tensorfs, W, H, voxel, bounds=None, poses=None, trunc=None,
     stay render_poses'.  max_spread (with "median" only) also drops the pixels whose interquartile depth range (d75 - d25)
     exceeds max_spread times their median, or that miss one of the three quartiles.  Any other depth= raises ValueError.
     Pinhole scenes only.  Returns the mesh dict of the module docstring with "volume": the TsdfVolume."""
-    from . import novel_views, pointcloud
-    from .depth_quantiles import check_fusion_depth, fusion_depth
-    max_spread = check_fusion_depth("scene_mesh", depth, max_spread)
-    unknown = sorted(set(options) - set(_MESH_KEYS) - set(_RENDER_KEYS))
-    if unknown:
-        raise TypeError(f"scene_mesh: unknown options {unknown}")
-    W, H = int(W), int(H)
-    if W <= 0 or H <= 0:
-        raise ValueError(f"need W, H > 0, got {W} x {H}")
+    lt = local_tensorfs
+    frames = SceneFrames("scene_mesh", lt, W, H, poses, depth, max_spread, options, _MESH_KEYS, False)
+    W, H, n, options, render = frames.W, frames.H, frames.n, frames.own, frames.render
     voxel = float(voxel)
     if not (voxel > 0 and math.isfinite(voxel)):
         raise ValueError(f"voxel must be a finite number > 0, got {voxel}")
     trunc = 3.0 * voxel if trunc is None else float(trunc)
     if not (trunc > 0 and math.isfinite(trunc)):
         raise ValueError(f"trunc must be a finite number > 0, got {trunc}")
-    lt = local_tensorfs
     if lt.fov == 360:
         raise ValueError("scene_mesh: the integration needs a pinhole camera: there is no reprojection at 360 degrees")
     depth_range = options.get("depth_range", (0.0, math.inf))
@@ -268,14 +262,6 @@ def scene_mesh(local_tensorfs, W, H, voxel, bounds=None, poses=None, trunc=None,
     if int(per_call) != per_call or int(per_call) < 1:
         raise ValueError(f"frames_per_call must be an integer >= 1, got {per_call!r}")
     per_call = int(per_call)
-    render = {k: options[k] for k in _RENDER_KEYS if k in options}
-    if poses is None:
-        n = len(lt.r_c2w)
-        render.setdefault("frame_indices", list(range(n)))
-    else:
-        n = int(novel_views._poses(poses).shape[0])
-    if n < 1:
-        raise ValueError("scene_mesh: no frame to render")
     if per_call * H * W > _INT32:
         raise ValueError(f"scene_mesh: {per_call} frames of {H} x {W} per call; one integration takes V H W < 2^31")
 
@@ -291,17 +277,10 @@ def scene_mesh(local_tensorfs, W, H, voxel, bounds=None, poses=None, trunc=None,
         if len(bounds) != 2:
             raise ValueError(f"bounds must be ((x0, y0, z0), (x1, y1, z1)), got {bounds!r}")
         lo, dims = volume_for(*_lattice_of_box(bounds[0], bounds[1], voxel))
-    dev = lt.blending_weights.device
-    if dev.type != "cuda":
-        raise NativeError(f"localrf_amd.mesh: the scene lives on {dev}; rendering runs only on an AMD GPU (HIP kernels). "
-                          "There is no CPU fallback.")
-    if poses is None:
-        with torch.no_grad():
-            poses = lt.get_cam2world().detach()
-    poses = novel_views._poses(poses)
+    poses = frames.cam2world()
     fi = render.pop("frame_indices", None)
     if fi is None:
-        fi = novel_views.nearest_frames(lt, poses)
+        fi = nearest_frames(lt, poses)
     fi = fi.tolist() if hasattr(fi, "tolist") else list(fi)
     if len(fi) < n:
         raise ValueError(f"frame_indices holds {len(fi)} entries for {n} poses")
@@ -313,7 +292,7 @@ def scene_mesh(local_tensorfs, W, H, voxel, bounds=None, poses=None, trunc=None,
             out = novel_views.render_poses(lt, poses[i0:i1], W, H, frame_indices=fi[i0:i1], encode=colours, **render)
             dmap = out["depth"]
             if depth == "median":
-                dmap = fusion_depth(lt, poses[i0:i1], W, H, max_spread, frame_indices=fi[i0:i1], **render)
+                dmap = depth_quantiles.fusion_depth(lt, poses[i0:i1], W, H, frames.max_spread, frame_indices=fi[i0:i1], **render)
             yield poses[i0:i1], dmap, out.get("rgb8") if colours else None
 
     if bounds is None:
@@ -327,7 +306,7 @@ def scene_mesh(local_tensorfs, W, H, voxel, bounds=None, poses=None, trunc=None,
             raise ValueError("scene_mesh: no rendered depth lies inside depth_range; there is no box to cover")
         box = box.double().cpu().numpy()                            # the box's read-back
         lo, dims = volume_for(*_lattice_of_box(box[0] - trunc, -box[1] + trunc, voxel))
-    vol = TsdfVolume(lo, voxel, dims, trunc, dev, colours=colours)
+    vol = TsdfVolume(lo, voxel, dims, trunc, lt.blending_weights.device, colours=colours)
     for p, dmap, rgb8 in batches():
         vol.integrate(dmap, p, focal, center, rgb=rgb8, depth_range=depth_range)
     mesh = vol.extract(level, min_weight, options.get("max_vertices"), options.get("max_faces"))

@@ -15,48 +15,7 @@ import torch
 
 from . import _native as N
 from . import novel_views
-from .scene_ops import scene_rays
-
-
-def _group_spans(lt, poses, vids, i0, i1, active, W, H, chunk):
-    """The per-field calls of frames i0..i1 (one active set), shared with depth_quantiles: yields (r0, r1, calls) per span of
-    rays, calls = [(f, z, flags, rays [r1 - r0, 6], blend_w)] over the active fields in the reference's field order, blend_w
-    being the field's weights from the span's first view on (per_view = H W).  A span holds whole views when chunk covers
-    one, else part of a single view."""
-    dev = lt.blending_weights.device
-    V, HW = i1 - i0, W * H
-    fields = [lt.tensorfs[rf] for rf in active]
-    for f in fields:
-        if f.device != dev:
-            f.to(dev)
-    pinhole = lt.fov != 360
-    ray_ids = torch.arange(V * HW, dtype=torch.int64, device=dev)
-    rays, _, _ = scene_rays(ray_ids, poses[i0:i1], lt._shifts(lt.world2rf, list(active)), lt.focal(W) if pinhole else None,
-                            lt.center(W, H) if pinhole else None, HW, W, H, not pinhole)
-    bw = lt.blending_weights[vids[i0:i1]].index_select(1, torch.tensor(active, dtype=torch.int64).to(dev, non_blocking=True))
-    bw = N.conform(bw.t())                                          # [n_active, V]: a field's weights are one contiguous row
-    plan = []
-    for f in fields:
-        z = f.z_schedule(False, -1, dev).detach().contiguous().float().view(-1)
-        flags = f._flags(True) | (N.LRF_FLAG_PE_OFF if (f.fea_pe > 0 and not lt.is_refining) else 0)
-        plan.append((f, z, flags))
-    if chunk >= HW:                                                 # whole views per call
-        step = (chunk // HW) * HW
-        spans = [(r0, min(V * HW, r0 + step)) for r0 in range(0, V * HW, step)]
-    else:                                                           # a call never crosses a view: one blend weight per call
-        spans = [(v * HW + r0, v * HW + min(HW, r0 + chunk)) for v in range(V) for r0 in range(0, HW, chunk)]
-    for r0, r1 in spans:
-        yield r0, r1, [(f, z, flags, rays[k, r0:r1], bw[k, r0 // HW:]) for k, (f, z, flags) in enumerate(plan)]
-
-
-def _render_group(lt, poses, vids, i0, i1, active, W, H, floater_thresh, chunk, normal, acc):
-    """Frames i0..i1 (one active set): per chunk of rays, the active fields in the reference's field order, the first
-    overwriting normal / acc and the others adding to them."""
-    normal, acc = normal[i0:i1].view(-1, 3), acc[i0:i1].view(-1)
-    for r0, r1, calls in _group_spans(lt, poses, vids, i0, i1, active, W, H, chunk):
-        for k, (f, z, flags, rays, bw) in enumerate(calls):
-            f._native_normals(rays, z, flags, floater_thresh, blend_w=bw, per_view=W * H, out=(normal[r0:r1], acc[r0:r1]),
-                              accumulate=k > 0)
+from .pose_plan import PosePlan
 
 
 def render_normals(local_tensorfs, poses, W, H, test_frames=(), frame_indices=None, start=0, floater_thresh=0, chunk=4096):
@@ -68,14 +27,18 @@ def render_normals(local_tensorfs, poses, W, H, test_frames=(), frame_indices=No
     Returns {"normal": [N,H,W,3] fp32, "acc": [N,H,W] fp32} on the scene's device: normal = sum_k blend_w N_k, acc =
     sum_k blend_w acc_k, |normal| <= acc.  Raises ValueError before any launch for a frame whose nearest frame has no
     active field."""
-    lt, poses, views, vids, _, groups, W, H, dev, _, _ = novel_views._prepare(
-        local_tensorfs, poses, W, H, test_frames, frame_indices, start, None, chunk, None, None, False)
-    n = len(views)
+    plan = PosePlan(local_tensorfs, poses, W, H, test_frames, frame_indices, start, None, chunk).on_device()
+    n, W, H, dev = plan.n, plan.W, plan.H, plan.dev
     normal = torch.empty(n, H, W, 3, dtype=torch.float32, device=dev)
     acc = torch.empty(n, H, W, dtype=torch.float32, device=dev)
     with torch.no_grad(), torch.cuda.device(dev):
-        for i0, i1, active in groups:
-            _render_group(lt, poses, vids, i0, i1, active, W, H, float(floater_thresh), int(chunk), normal, acc)
+        # per span of rays, the active fields in the reference's field order: the first overwrites normal / acc, the others add
+        for i0, i1, active in plan.calls:
+            nrm, a = normal[i0:i1].view(-1, 3), acc[i0:i1].view(-1)
+            for r0, r1, calls in plan.group_spans(i0, i1, active):
+                for k, (f, z, flags, rays, bw) in enumerate(calls):
+                    f._native_normals(rays, z, flags, float(floater_thresh), blend_w=bw, per_view=W * H,
+                                      out=(nrm[r0:r1], a[r0:r1]), accumulate=k > 0)
     return {"normal": normal, "acc": acc}
 
 

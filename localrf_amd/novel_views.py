@@ -18,8 +18,7 @@ import numpy as np
 import torch
 
 from . import _native as N
-from ._native import NativeError
-from .scene_ops import scene_forward
+from .pose_plan import PosePlan, nearest_frames  # noqa: F401  (nearest_frames: part of this module's interface)
 
 _ENC_MAX_PX = ((1 << 31) - 1) // 3           # lrf_encode_frames: 3 V H W < 2^31
 
@@ -169,125 +168,10 @@ def encode_frames(rgb, depth, minmax=(0, 5), cmap=None, return_index=False):
     return out + (idx.reshape(*lead, H, W),) if return_index else out
 
 
-# --------------------------------------------------------------------------------------------------- poses
-def _poses(poses):
-    if not torch.is_tensor(poses):
-        poses = torch.as_tensor(np.asarray(poses, dtype=np.float32))
-    if poses.dim() != 3 or poses.shape[1] not in (3, 4) or poses.shape[2] != 4:
-        raise ValueError(f"poses must be [N, 3, 4] (or [N, 4, 4]) camera-to-world matrices, got {tuple(poses.shape)}")
-    if not poses.is_floating_point():
-        raise ValueError(f"poses must hold floating-point values, got {poses.dtype}")
-    return poses[:, :3, :]
-
-
-def nearest_frames(local_tensorfs, poses):
-    """renderer.py:47-53 for all N poses at once: LongTensor [N], argmin_f |t_c2w[f] - pose[:, 3]| (first index on ties; a
-    NaN distance wins, as torch.argmin has it), on the scene's device.  No read-back."""
-    poses = _poses(poses)
-    t = torch.stack([p.detach() for p in local_tensorfs.t_c2w], dim=0)
-    if poses.shape[0] == 0:
-        return torch.empty(0, dtype=torch.int64, device=t.device)
-    dist = torch.norm(t[None] - poses.to(device=t.device, dtype=t.dtype)[:, None, :, 3], dim=-1)
-    return torch.argmin(dist, dim=1)
-
-
-def _plan(local_tensorfs, poses, W, H, test_frames, frame_indices, start, frames_per_call):
-    """Everything checked on the host, no render launch: (poses of the rendered frames, their nearest frames (list),
-    test flags (list), groups [(i0, i1, active)])."""
-    W, H = int(W), int(H)
-    if W <= 0 or H <= 0:
-        raise ValueError(f"need W, H > 0, got {W} x {H}")
-    if frames_per_call is not None and int(frames_per_call) < 1:
-        raise ValueError(f"frames_per_call must be >= 1, got {frames_per_call}")
-    start = int(start)
-    if start < 0:
-        raise ValueError(f"start must be >= 0, got {start}")
-    poses = _poses(poses)[start:]                               # renderer.py:45: poses_mtx = poses_mtx[start:]
-    n = max(0, int(poses.shape[0]) - start)                     # renderer.py:46: idxs = range(start, len(poses_mtx))
-    F = len(local_tensorfs.r_c2w)
-    if frame_indices is None:
-        frame_indices = nearest_frames(local_tensorfs, poses) if n else []
-    fi = frame_indices.tolist() if hasattr(frame_indices, "tolist") else list(frame_indices)   # one read-back per path
-    if n and len(fi) < start + n:
-        raise ValueError(f"frame_indices holds {len(fi)} entries; frame i uses frame_indices[start + i] up to {start + n - 1}")
-    views = [int(v) for v in fi[start:start + n]]               # renderer.py:60-63: view_ids = frame_indices[idx]
-    for i, v in enumerate(views):
-        if not 0 <= v < F:
-            raise ValueError(f"frame {i}: frame index {v} lies outside [0, {F})")
-    tests = set(int(t) for t in test_frames)
-    is_test = [v in tests for v in views]                       # renderer.py:47,74: is_test_id[view_ids.item()]
-    bw = local_tensorfs._blending_host()
-    groups = []
-    for i, v in enumerate(views):
-        active = tuple(torch.nonzero(bw[v])[:, 0].tolist())
-        if not active:                                          # the reference's forward returns a 5-tuple there and
-            raise ValueError(f"frame {i}: its nearest frame {v} has no active field (no blending weight)")   # renderer.py:65 fails
-        if groups and groups[-1][2] == active and (frames_per_call is None or i - groups[-1][0] < int(frames_per_call)):
-            groups[-1][1] = i + 1
-        else:
-            groups.append([i, i + 1, active])
-    return poses[:n], views, is_test, groups, W, H
-
-
-def _render_group(lt, poses, vids, i0, i1, active, W, H, floater_thresh, chunk, exposure):
-    """Frames i0..i1 (one active set) in one lrf_scene_fwd call: what LocalTensorfs.forward(ray_ids, [view], W, H,
-    is_train=False, cam2world=pose[None], test_id=...) computes for each of them."""
-    dev = lt.blending_weights.device
-    V = i1 - i0
-    fields = [lt.tensorfs[rf] for rf in active]
-    for f in fields:
-        if f.device != dev:
-            f.to(dev)
-    a0, a1 = active[0], active[-1]
-    bw = lt.blending_weights[vids[i0:i1]]
-    bw = bw[:, a0:a1 + 1] if list(active) == list(range(a0, a1 + 1)) else bw.index_select(
-        1, torch.tensor(active, dtype=torch.int64).to(dev, non_blocking=True))
-    pinhole = lt.fov != 360
-    ray_ids = torch.arange(V * W * H, dtype=torch.int64, device=dev)
-    per_field = max(1, chunk // len(active))
-    return scene_forward(ray_ids, poses[i0:i1], lt._shifts(lt.world2rf, list(active)), lt.focal(W) if pinhole else None,
-                         lt.center(W, H) if pinhole else None, W * H, W, H, not pinhole, fields, True, floater_thresh,
-                         lt._untaped_chunk(per_field, fields), bw, None if exposure is None else exposure[i0:i1],
-                         refine=lt.is_refining)
-
-
-def _split(groups, cap):
-    out = []
-    for i0, i1, active in groups:
-        for j in range(i0, i1, cap):
-            out.append((j, min(i1, j + cap), active))
-    return out
-
-
-def _prepare(local_tensorfs, poses, W, H, test_frames, frame_indices, start, frames_per_call, chunk, depth_minmax, cmap,
-             encode):
-    lt = local_tensorfs
-    if int(chunk) < 1:
-        raise ValueError(f"chunk must be >= 1, got {chunk}")
-    if encode and depth_minmax is not None:
+def _check_encoding(depth_minmax, cmap):
+    if depth_minmax is not None:
         fixed_range(depth_minmax)
-    if encode:
-        _check_lut(cmap)
-    poses, views, is_test, groups, W, H = _plan(lt, poses, W, H, test_frames, frame_indices, start, frames_per_call)
-    dev = lt.blending_weights.device
-    if dev.type != "cuda":
-        raise NativeError(f"localrf_amd.novel_views: the scene lives on {dev}; rendering runs only on an AMD GPU (HIP kernels). "
-                          "There is no CPU fallback.")
-    lut = _lut(cmap, dev) if encode else None
-    # frames per call: bounded by frames_per_call (in _plan) and by the scene's max_untaped_workspace over the per-call ray
-    # buffers of lrf_scene_fwd (rays, per-field colour and depth, directions, ij, blended colour and depth: 40 n_rf + 44 B)
-    cap = max(1, int(lt.max_untaped_workspace) // (W * H * (40 * max(len(g[2]) for g in groups) + 44))) if groups else 1
-    groups = _split(groups, cap)
-    poses = poses.detach().to(device=dev, dtype=torch.float32).contiguous()
-    vids = torch.tensor(views, dtype=torch.int64).to(dev, non_blocking=True)
-    exposure = None
-    if lt.lr_exposure_init > 0 and views:                      # local_tensorfs.py:481-496, test_id chosen per frame
-        with torch.no_grad():
-            own = lt._exposure_for(vids, False)
-            borrowed = lt._exposure_for(vids, True)
-            mask = torch.tensor(is_test, dtype=torch.bool).to(dev, non_blocking=True)
-            exposure = torch.where(mask[:, None, None], borrowed, own).contiguous()
-    return lt, poses, views, vids, is_test, groups, W, H, dev, lut, exposure
+    _check_lut(cmap)
 
 
 def render_poses(local_tensorfs, poses, W, H, test_frames=(), frame_indices=None, start=0, floater_thresh=0, chunk=4096,
@@ -307,17 +191,19 @@ def render_poses(local_tensorfs, poses, W, H, test_frames=(), frame_indices=None
     Returns a dict of device tensors: rgb [N,H,W,3] (rgb_maps_tb), depth [N,H,W] (the raw depth save_raw_depth writes),
     frame_indices [N] (int64), and with encode rgb8 / depth8 [N,H,W,3] uint8 (encode_frames with depth_minmax and cmap).
     Raises ValueError before any launch for a frame whose nearest frame has no active field."""
-    lt, poses, views, vids, is_test, groups, W, H, dev, lut, exposure = _prepare(
-        local_tensorfs, poses, W, H, test_frames, frame_indices, start, frames_per_call, chunk, depth_minmax, cmap, encode)
-    n = len(views)
+    if encode:
+        _check_encoding(depth_minmax, cmap)
+    plan = PosePlan(local_tensorfs, poses, W, H, test_frames, frame_indices, start, frames_per_call, chunk).on_device(exposure=True)
+    n, W, H, dev = plan.n, plan.W, plan.H, plan.dev
+    lut = _lut(cmap, dev) if encode else None
     rgb = torch.empty(n, H, W, 3, dtype=torch.float32, device=dev)
     depth = torch.empty(n, H, W, dtype=torch.float32, device=dev)
     with torch.no_grad():
-        for i0, i1, active in groups:
-            r, d, _, _ = _render_group(lt, poses, vids, i0, i1, active, W, H, floater_thresh, int(chunk), exposure)
+        for i0, i1, active in plan.calls:
+            r, d = plan.render_colour(i0, i1, active, floater_thresh)
             rgb[i0:i1].view(-1, 3).copy_(r)
             depth[i0:i1].view(-1).copy_(d)
-    out = {"rgb": rgb, "depth": depth, "frame_indices": vids}
+    out = {"rgb": rgb, "depth": depth, "frame_indices": plan.vids}
     if encode and n:
         out["rgb8"], out["depth8"], _, _ = _encode(rgb, depth, depth_minmax, lut, False, False)
     elif encode:
@@ -334,13 +220,13 @@ def iter_pose_frames(local_tensorfs, poses, W, H, test_frames=(), frame_indices=
     into one of two pinned host buffers without blocking, while the next group renders.  The host waits only on the copy
     event of the group whose frames it yields.  Closing the generator early synchronises both streams: nothing stays
     enqueued."""
-    lt, poses, views, vids, is_test, groups, W, H, dev, lut, exposure = _prepare(
-        local_tensorfs, poses, W, H, test_frames, frame_indices, start, frames_per_call, chunk, depth_minmax, cmap, True)
-    return _iter_frames(lt, poses, vids, is_test, groups, W, H, dev, lut, exposure, floater_thresh, int(chunk), depth_minmax,
-                        with_depth)
+    _check_encoding(depth_minmax, cmap)
+    plan = PosePlan(local_tensorfs, poses, W, H, test_frames, frame_indices, start, frames_per_call, chunk).on_device(exposure=True)
+    return _iter_frames(plan, _lut(cmap, plan.dev), floater_thresh, depth_minmax, with_depth)
 
 
-def _iter_frames(lt, poses, vids, is_test, groups, W, H, dev, lut, exposure, floater_thresh, chunk, depth_minmax, with_depth):
+def _iter_frames(plan, lut, floater_thresh, depth_minmax, with_depth):
+    groups, W, H, dev = plan.calls, plan.W, plan.H, plan.dev
     if not groups:
         return
     vmax = max(i1 - i0 for i0, i1, _ in groups)
@@ -354,7 +240,7 @@ def _iter_frames(lt, poses, vids, is_test, groups, W, H, dev, lut, exposure, flo
     def launch(k):
         i0, i1, active = groups[k]
         with torch.no_grad():
-            r, d, _, _ = _render_group(lt, poses, vids, i0, i1, active, W, H, floater_thresh, chunk, exposure)
+            r, d = plan.render_colour(i0, i1, active, floater_thresh)
             V = i1 - i0
             d = d.view(V, H, W)
             rgb8, depth8, _, _ = _encode(r.view(V, H, W, 3), d, depth_minmax, lut, False, False)

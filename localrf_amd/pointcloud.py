@@ -19,7 +19,8 @@ import numpy as np
 import torch
 
 from . import _native as N
-from ._native import NativeError
+from . import depth_quantiles, normals as normal_maps, novel_views
+from .pose_plan import check_poses
 
 _INT32 = (1 << 31) - 1
 BYTES_PER_RESIDENT_PIXEL = 7                   # scene_point_cloud keeps depth (4 B) and rgb8 (3 B) of every frame
@@ -40,15 +41,10 @@ def _check_depth(depth):
 
 
 def _check_poses(poses, V):
-    if not torch.is_tensor(poses):
-        poses = torch.as_tensor(np.asarray(poses, dtype=np.float32))
-    if poses.dim() != 3 or poses.shape[1] not in (3, 4) or poses.shape[2] != 4:
-        raise ValueError(f"poses must be [V, 3, 4] (or [V, 4, 4]) camera-to-world matrices, got {tuple(poses.shape)}")
-    if not poses.is_floating_point():
-        raise ValueError(f"poses must hold floating-point values, got {poses.dtype}")
+    poses = check_poses(poses)
     if poses.shape[0] != V:
         raise ValueError(f"{poses.shape[0]} poses for {V} depth frames")
-    return poses[:, :3, :]
+    return poses
 
 
 def _check_intrinsics(focal, center, fov360):
@@ -190,7 +186,43 @@ def fuse_points(rgb, depth, poses, focal, center, *, fov360=False, stride=1, dep
 
 
 _FUSE_KEYS = ("stride", "depth_range", "neighbours", "rel_tol", "min_consistent", "max_points")
-_RENDER_KEYS = ("test_frames", "frame_indices", "floater_thresh", "chunk", "frames_per_call")
+_RENDER_KEYS = ("test_frames", "frame_indices", "floater_thresh", "chunk", "frames_per_call")   # the last: render_poses' alone
+
+
+class SceneFrames:
+    """What scene_point_cloud and scene_mesh (`who`) share before their first render.  Construction checks on the host, in
+    this order: depth= / max_spread=, unknown options (TypeError), W and H, poses (None: the scene's own frames, each through
+    itself) and the frame count n >= 1.  own: the caller's options; render: those every renderer takes; colour: render plus
+    frames_per_call, which only render_poses takes, when the caller forwards it.  cam2world() is the device half, for after
+    the caller's own checks: it refuses a CPU scene and returns the poses [n, 3, 4]."""
+
+    def __init__(self, who, local_tensorfs, W, H, poses, depth, max_spread, options, own_keys, forwards_frames_per_call):
+        self.max_spread = depth_quantiles.check_fusion_depth(who, depth, max_spread)
+        unknown = sorted(set(options) - set(own_keys) - set(_RENDER_KEYS))
+        if unknown:
+            raise TypeError(f"{who}: unknown options {unknown}")
+        self.W, self.H = int(W), int(H)
+        if self.W <= 0 or self.H <= 0:
+            raise ValueError(f"need W, H > 0, got {self.W} x {self.H}")
+        self.lt = local_tensorfs
+        self.own = {k: options[k] for k in own_keys if k in options}
+        self.render = {k: options[k] for k in _RENDER_KEYS[:-1] if k in options}
+        self.poses = None if poses is None else check_poses(poses)
+        self.n = len(local_tensorfs.r_c2w) if poses is None else int(self.poses.shape[0])
+        if poses is None:
+            self.render.setdefault("frame_indices", list(range(self.n)))
+        if self.n < 1:
+            raise ValueError(f"{who}: no frame to render")
+        self.colour = dict(self.render)
+        if forwards_frames_per_call and "frames_per_call" in options:
+            self.colour["frames_per_call"] = options["frames_per_call"]
+
+    def cam2world(self):
+        N.require_gpu(self.lt.blending_weights, "the scene", "rendering")
+        if self.poses is None:
+            with torch.no_grad():
+                return self.lt.get_cam2world().detach()
+        return self.poses
 
 
 def scene_point_cloud(local_tensorfs, W, H, poses=None, max_bytes=4 << 30, normals=False, orient=False, depth="expected",
@@ -208,57 +240,34 @@ def scene_point_cloud(local_tensorfs, W, H, poses=None, max_bytes=4 << 30, norma
     render_poses' expected depth, which lies in empty space where a ray sees two surfaces; the colours stay render_poses'.
     max_spread (with "median" only) also drops the pixels whose interquartile depth range (d75 - d25) exceeds max_spread times
     their median, or that miss one of the three quartiles.  Any other depth= raises ValueError."""
-    from . import novel_views
-    from .depth_quantiles import check_fusion_depth, fusion_depth
-    max_spread = check_fusion_depth("scene_point_cloud", depth, max_spread)
     if orient and not normals:
         raise ValueError("scene_point_cloud: orient=True needs normals=True")
-    unknown = sorted(set(options) - set(_FUSE_KEYS) - set(_RENDER_KEYS))
-    if unknown:
-        raise TypeError(f"scene_point_cloud: unknown options {unknown}")
-    W, H = int(W), int(H)
-    if W <= 0 or H <= 0:
-        raise ValueError(f"need W, H > 0, got {W} x {H}")
     lt = local_tensorfs
+    frames = SceneFrames("scene_point_cloud", lt, W, H, poses, depth, max_spread, options, _FUSE_KEYS, True)
+    W, H, n, fuse = frames.W, frames.H, frames.n, frames.own
     fov360 = lt.fov == 360
-    fuse = {k: options[k] for k in _FUSE_KEYS if k in options}
-    render = {k: options[k] for k in _RENDER_KEYS if k in options}
     _check_filter(fuse.get("stride", 1), fuse.get("depth_range", (0.0, math.inf)), fuse.get("neighbours", ()),
                   fuse.get("rel_tol", 0.02), fuse.get("min_consistent", 1), fov360, fuse.get("max_points"))
-    if poses is None:
-        n = len(lt.r_c2w)
-        render.setdefault("frame_indices", list(range(n)))
-    else:
-        n = int(novel_views._poses(poses).shape[0])
     need = (BYTES_PER_RESIDENT_PIXEL + (BYTES_PER_NORMAL_PIXEL if normals else 0)) * n * H * W
     if need > int(max_bytes):
         raise ValueError(f"scene_point_cloud: {n} frames of {H} x {W} keep {need} bytes of depth and rgb8"
                          f"{' and normals' if normals else ''} resident; max_bytes is {int(max_bytes)}")
-    if n < 1:
-        raise ValueError("scene_point_cloud: no frame to render")
     if n * H * W > _INT32:
         raise ValueError(f"scene_point_cloud: {n * H * W} pixels; one fusion takes V H W < 2^31")
-    dev = lt.blending_weights.device
-    if dev.type != "cuda":
-        raise NativeError(f"localrf_amd.pointcloud: the scene lives on {dev}; rendering runs only on an AMD GPU (HIP kernels). "
-                          "There is no CPU fallback.")
-    if poses is None:
-        with torch.no_grad():
-            poses = lt.get_cam2world().detach()
-    out = novel_views.render_poses(lt, poses, W, H, **render)
+    poses = frames.cam2world()
+    out = novel_views.render_poses(lt, poses, W, H, **frames.colour)
     dmap, rgb8 = out["depth"], out["rgb8"]
     del out                                                         # the float colours go back to the allocator
     if depth == "median":
-        dmap = fusion_depth(lt, poses, W, H, max_spread, **{k: v for k, v in render.items() if k != "frames_per_call"})
-    cloud = fuse_points(rgb8, dmap, novel_views._poses(poses), None if fov360 else lt.focal(W),
-                        None if fov360 else lt.center(W, H), fov360=fov360, **fuse)
+        dmap = depth_quantiles.fusion_depth(lt, poses, W, H, frames.max_spread, **frames.render)
+    cloud = fuse_points(rgb8, dmap, poses, None if fov360 else lt.focal(W), None if fov360 else lt.center(W, H), fov360=fov360,
+                        **fuse)
     if normals:
-        from .normals import render_normals, unit_normals
-        nrm = render_normals(lt, poses, W, H, **{k: v for k, v in render.items() if k != "frames_per_call"})["normal"]
+        nrm = normal_maps.render_normals(lt, poses, W, H, **frames.render)["normal"]
         src = cloud["src"].long()
-        unit = unit_normals(nrm.view(n, H * W, 3)[src[:, 0], src[:, 1]])[0]
+        unit = normal_maps.unit_normals(nrm.view(n, H * W, 3)[src[:, 0], src[:, 1]])[0]
         if orient:
-            t_cam = novel_views._poses(poses)[:, :, 3].to(device=dev, dtype=torch.float32)[src[:, 0]]
+            t_cam = poses[:, :, 3].to(device=nrm.device, dtype=torch.float32)[src[:, 0]]
             away = ((cloud["xyz"] - t_cam) * unit).sum(-1) > 0
             unit = torch.where(away[:, None], -unit, unit)
         cloud["normal"] = unit

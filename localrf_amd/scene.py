@@ -17,7 +17,7 @@ Cited lines are relative to /root/reference/localTensoRF.
 """
 import torch
 
-from ._native import NativeError
+from ._native import require_gpu
 from .compat_lifecycle import SceneLifecycle
 from .rays import sixD_to_mtx
 from .scene_ops import pose_assemble, rows_gather, scene_blend, scene_forward, scene_rays
@@ -103,10 +103,8 @@ class LocalTensorfs(SceneLifecycle):
                 world2rf=None, blending_weights=None, chunk=16384, test_id=False, floater_thresh=0):
         """Pixel ids -> rays -> per-field native render -> blend -> exposure -> clamp
         (local_tensorfs.py:382-499).  Returns (rgbs [R,3], depth [R], directions [R,3], ij [R,2])."""
+        require_gpu(self.blending_weights, "the scene", "rendering")
         dev = self.blending_weights.device
-        if dev.type != "cuda":
-            raise NativeError("localrf_amd: LocalTensorfs.forward runs only on an AMD GPU (HIP kernels); "
-                              f"the scene lives on {dev}. There is no CPU fallback.")
         # Ids may arrive on the host (extension): they are staged through pinned memory without
         # blocking.  Device-resident view_ids (what train.py:352 passes) cost one host sync here,
         # as in the reference, which reads them one .item() at a time (local_tensorfs.py:294-295).
@@ -147,12 +145,7 @@ class LocalTensorfs(SceneLifecycle):
                 stage = torch.empty(blending_weights.shape, dtype=torch.float32, pin_memory=True)
                 stage.copy_(blending_weights)
                 blending_weights = stage.to(dev, non_blocking=True)
-            # blending_weights[:, active] with a Python list uploads the index with a pageable copy, which blocks the
-            # host until the stream drains (docs/GFX950_FINDINGS.md finding 7): slice when the active fields are contiguous
-            if active == list(range(active[0], active[-1] + 1)) if active else False:
-                bw = blending_weights[:, active[0]:active[-1] + 1]
-            else:
-                bw = blending_weights.index_select(1, _upload_ids(active, dev)) if active else blending_weights[:, :0]
+            bw = self._active_columns(blending_weights, active)
 
         pinhole = self.fov != 360
         focal = self.focal(W) if pinhole else None
@@ -202,6 +195,17 @@ class LocalTensorfs(SceneLifecycle):
         exposure = self._exposure_for(view_ids, test_id)
         rgbs, depth_maps = scene_blend(rgb_f, dep_f, bw, exposure, per_view)
         return rgbs, depth_maps, directions, ij
+
+    @staticmethod
+    def _active_columns(weights, active):
+        """weights[:, active] of device blending weights [V, n_rf].  Indexing with a Python list uploads the index with a
+        pageable copy, which blocks the host until the stream drains (docs/GFX950_FINDINGS.md finding 7): a slice when the
+        active fields are adjacent, else index_select through a pinned, non-blocking upload."""
+        if not active:
+            return weights[:, :0]
+        if active == list(range(active[0], active[-1] + 1)):
+            return weights[:, active[0]:active[-1] + 1]
+        return weights.index_select(1, _upload_ids(active, weights.device))
 
     def _untaped_chunk(self, per_field, fields):
         """Rays per field call of a forward without a tape: the caller's chunk // n_active, raised to self.min_chunk (an

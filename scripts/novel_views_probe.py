@@ -79,6 +79,7 @@ def main():
     assert torch.cuda.is_available(), "novel_views_probe needs the GPU"
     import bench
     from localrf_amd import novel_views
+    from localrf_amd.pose_plan import PosePlan
     from novel_views_cases import depth_idx_host, rgb8_host
     lt = bench.config3_scene(DEV)[0]
     n = 24 if args.quick else args.poses
@@ -113,8 +114,7 @@ def main():
                          ("host_loop", host_loop)):
             dt = timed(fn)
             row[name] = {"s": dt, "frames_per_s": n / dt}
-        groups = novel_views._plan(lt, poses, W, H, tests, None, 0, None)[3]
-        row["calls"] = len(groups)
+        row["calls"] = len(PosePlan(lt, poses, W, H, tests).groups)
         out = render()
         one = (out["rgb"][:1].contiguous(), out["depth"][:1].contiguous())
         many = (out["rgb"][:16].contiguous(), out["depth"][:16].contiguous())

@@ -70,6 +70,21 @@ def golden():
     return load_golden("novel_views")
 
 
+def gap_case(device):
+    """scene(device) with the blending weights of two training frames overwritten so that their active fields are not
+    adjacent, (0, 2) and (1, 3), and three poses through them: the two frames' own and the first shifted by 0.05.
+    Returns (lt, poses [3,3,4], views, W, H, test frames)."""
+    lt, g = scene(device)
+    views = [2, 6, 2]
+    with torch.no_grad():                                       # in place: _version moves and the host mirror refreshes
+        lt.blending_weights[2] = torch.tensor([0.25, 0.0, 0.75, 0.0])
+        lt.blending_weights[6] = torch.tensor([0.0, 0.5, 0.0, 0.5])
+        poses = lt.get_cam2world().detach()[views].clone()
+    poses[2, :, 3] += 0.05
+    assert [tuple(torch.nonzero(lt._blending_host()[v])[:, 0].tolist()) for v in views] == [(0, 2), (1, 3), (0, 2)]
+    return lt, poses, views, 24, 16, g["test_frames"].tolist()
+
+
 def scene(device):
     """Our LocalTensorfs holding the golden's scene (make_golden_geometry.build_scene, lr_exposure_init > 0): the four fields
     regenerated from the seed (3 x (3 frames, 1 field), density planes x 3) and checked against the reference's checksum,

@@ -148,9 +148,8 @@ def scene_case():
     return lt, poses, views, W, H, out
 
 
-def test_scene_normals_are_the_blend_of_the_fields(scene_case):
+def _assert_the_blend_of_the_fields(lt, poses, views, W, H, out):
     from localrf_amd.scene_ops import scene_rays
-    lt, poses, views, W, H, out = scene_case
     assert out["normal"].shape == (3, H, W, 3) and out["acc"].shape == (3, H, W)
     bw = lt.blending_weights.detach()
     want_n = torch.zeros(3, H * W, 3, device=DEV)
@@ -172,6 +171,20 @@ def test_scene_normals_are_the_blend_of_the_fields(scene_case):
     print(f"scene: max |normal - blend| {err_n:.3e}, max |acc - blend| {err_a:.3e}, max |N| {float(want_n.norm(dim=-1).max()):.3e}")
     assert err_n <= 1e-6 and err_a <= 1e-6
     assert float(want_n.norm(dim=-1).max()) > 1e-3
+
+
+def test_scene_normals_are_the_blend_of_the_fields(scene_case):
+    _assert_the_blend_of_the_fields(*scene_case)
+
+
+def test_scene_normals_over_an_active_set_with_a_gap():
+    """Active fields that are not adjacent, (0, 2) and (1, 3): the same restatement at the same bounds, whatever the chunk."""
+    from novel_views_cases import gap_case
+    lt, poses, views, W, H, _ = gap_case(DEV)
+    out = normals.render_normals(lt, poses, W, H, frame_indices=views, chunk=W * H * 3)
+    _assert_the_blend_of_the_fields(lt, poses, views, W, H, out)
+    small = normals.render_normals(lt, poses, W, H, frame_indices=views, chunk=7)
+    assert torch.equal(small["normal"], out["normal"]) and torch.equal(small["acc"], out["acc"])
 
 
 @pytest.mark.parametrize("chunk", [7, 64])

@@ -6,7 +6,8 @@ import pytest
 import torch
 
 from localrf_amd import novel_views
-from novel_views_cases import depth_idx_host, edge_depths, edge_rgbs, golden, rgb8_host, scene
+from localrf_amd.pose_plan import PosePlan
+from novel_views_cases import depth_idx_host, edge_depths, edge_rgbs, gap_case, golden, rgb8_host, scene
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -130,7 +131,7 @@ def test_batched_renders_are_bit_identical_to_per_frame_forward_calls():
     outs = [novel_views.render_poses(lt, poses, W, H, test_frames=tests, floater_thresh=0.5, frames_per_call=f)
             for f in (1, 3, None)]
     views = outs[0]["frame_indices"].tolist()
-    groups = novel_views._plan(lt, poses, W, H, tests, None, 0, None)[3]
+    groups = PosePlan(lt, poses, W, H, tests, None, 0, None).groups
     assert any(i1 - i0 > 3 for i0, i1, _ in groups)                       # batching happens
     assert len({a for _, _, a in groups}) >= 3                            # mixed active sets
     assert any(len({views[i] in tests for i in range(i0, i1)}) == 2 for i0, i1, _ in groups)   # mixed test_id in a group
@@ -149,6 +150,36 @@ def test_batched_renders_are_bit_identical_to_per_frame_forward_calls():
     assert torch.equal(a["rgb"], b["rgb"]) and torch.equal(a["depth8"], b["depth8"])
     rgb, depth = _per_frame_forward(lt, poses[1:8], fi[1:8], tests, W2, H2)
     assert torch.equal(rgb, a["rgb"]) and torch.equal(depth, a["depth"])
+
+
+def test_an_active_set_with_a_gap_renders_what_per_frame_forward_calls_render():
+    """Active fields that are not adjacent: the blend-weight columns are gathered, not sliced."""
+    lt, poses, views, W, H, tests = gap_case(DEV)
+    out = novel_views.render_poses(lt, poses, W, H, test_frames=tests, frame_indices=views, floater_thresh=0.5, chunk=W * H * 3)
+    assert [a for _, _, a in PosePlan(lt, poses, W, H, tests, views).groups] == [(0, 2), (1, 3), (0, 2)]
+    rgb, depth = _per_frame_forward(lt, poses, views, tests, W, H)
+    assert torch.equal(rgb, out["rgb"]) and torch.equal(depth, out["depth"])
+    assert float(out["rgb"].std()) > 1e-3 and float(out["depth"].std()) > 1e-3
+    small = novel_views.render_poses(lt, poses, W, H, test_frames=tests, frame_indices=views, floater_thresh=0.5, chunk=7)
+    for k in ("rgb", "depth", "rgb8", "depth8"):
+        assert torch.equal(small[k], out[k]), k
+
+
+def test_normal_and_quantile_maps_compute_no_exposure(monkeypatch):
+    """Exposure does not apply to a normal or a depth: with lr_exposure_init > 0 neither map may even compute one."""
+    from localrf_amd import depth_quantiles, normals
+    lt, g = scene(DEV)
+    assert lt.lr_exposure_init > 0
+    poses = torch.from_numpy(g["poses"][:2]).to(DEV)
+
+    def forbidden(*a, **k):
+        raise AssertionError("an exposure was computed for a map that has none")
+    monkeypatch.setattr(lt, "_exposure_for", forbidden)
+    tests = g["test_frames"].tolist()
+    assert normals.render_normals(lt, poses, 12, 8, test_frames=tests)["normal"].shape == (2, 8, 12, 3)
+    assert depth_quantiles.render_depth_quantiles(lt, poses, 12, 8, test_frames=tests)["depth"].shape == (1, 2, 8, 12)
+    with pytest.raises(AssertionError, match="exposure"):
+        novel_views.render_poses(lt, poses, 12, 8, test_frames=tests)
 
 
 def test_iter_pose_frames_yields_the_encoded_frames_in_order():

@@ -150,10 +150,10 @@ def scene_case():
     return lt, poses, views, W, H, out
 
 
-def test_scene_quantiles_are_the_blend_of_the_fields(scene_case):
+def _assert_the_blend_of_the_fields(lt, poses, views, W, H, out, q):
+    """-> the mask [K, 3, H W] of the pixels no field crosses."""
     from localrf_amd.scene_ops import scene_rays
-    lt, poses, views, W, H, out = scene_case
-    K = len(SCENE_Q)
+    K = len(q)
     assert out["depth"].shape == (K, 3, H, W) and out["acc"].shape == (3, H, W)
     bw = lt.blending_weights.detach()
     dsum = torch.zeros(K, 3, H * W, device=DEV)
@@ -167,7 +167,7 @@ def test_scene_quantiles_are_the_blend_of_the_fields(scene_case):
         with torch.no_grad():
             rays, _, _ = scene_rays(ids, poses[i:i + 1], lt._shifts(lt.world2rf, active), lt.focal(W), lt.center(W, H), H * W, W, H)
         for k, rf in enumerate(active):
-            d_k, a_k, i_k = lt.tensorfs[rf].render_depth_quantiles(rays[k], SCENE_Q, return_index=True)
+            d_k, a_k, i_k = lt.tensorfs[rf].render_depth_quantiles(rays[k], q, return_index=True)
             found = (i_k >= 0).float()
             assert (d_k[i_k < 0] == 0).all()
             dsum[:, i] += bw[v, rf] * d_k
@@ -180,9 +180,28 @@ def test_scene_quantiles_are_the_blend_of_the_fields(scene_case):
     print(f"scene: pixels no field crosses: {none.sum(dim=(1, 2)).tolist()} of {3 * H * W} per quantile; max depth {float(want.max()):.3e}")
     assert torch.equal(got.view(torch.int32), want.view(torch.int32))   # exactly
     assert float((out["acc"].view(3, -1) - want_a).abs().max()) <= 1e-6
-    assert none[1].any() and (got[none] == 0).all() and (got[~none] > 0).all()     # a pixel no field crosses is exactly 0
+    assert (got[none] == 0).all() and (got[~none] > 0).all()              # a pixel no field crosses is exactly 0
+    return none
+
+
+def test_scene_quantiles_are_the_blend_of_the_fields(scene_case):
+    lt, poses, views, W, H, out = scene_case
+    none = _assert_the_blend_of_the_fields(lt, poses, views, W, H, out, SCENE_Q)
+    assert none[1].any()
     med = depth_quantiles.median_depth(lt, poses, W, H, frame_indices=views)
     assert med.shape == (3, H, W) and torch.equal(med, out["depth"][0])
+
+
+def test_scene_quantiles_over_an_active_set_with_a_gap():
+    """Active fields that are not adjacent, (0, 2) and (1, 3): the same restatement at the same bounds, whatever the chunk."""
+    from novel_views_cases import gap_case
+    lt, poses, views, W, H, _ = gap_case(DEV)
+    q = (0.25, 0.5)
+    out = depth_quantiles.render_depth_quantiles(lt, poses, W, H, q=q, frame_indices=views, chunk=W * H * 3)
+    none = _assert_the_blend_of_the_fields(lt, poses, views, W, H, out, q)
+    assert not none.all()
+    small = depth_quantiles.render_depth_quantiles(lt, poses, W, H, q=q, frame_indices=views, chunk=7)
+    assert torch.equal(small["depth"].view(torch.int32), out["depth"].view(torch.int32)) and torch.equal(small["acc"], out["acc"])
 
 
 @pytest.mark.parametrize("chunk", [7, 64])

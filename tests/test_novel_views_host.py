@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from localrf_amd import NativeError, novel_views
+from localrf_amd.pose_plan import PosePlan
 from novel_views_cases import depth_idx_frames, depth_idx_host, edge_depths, edge_rgbs, golden, rgb8_host, scene
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -101,7 +102,8 @@ def test_start_and_frame_index_mapping_on_the_host():
     assert nearest.tolist() == ref.tolist()
     assert nearest[N - 5].item() == 6                           # frame 7 duplicates frame 6's translation: first index
     for s in (0, 2):
-        p, views, is_test, groups, _, _ = novel_views._plan(lt, poses, W, H, tests, None, s, None)
+        plan = PosePlan(lt, poses, W, H, tests, None, s, None)
+        p, views, is_test, groups = plan.poses, plan.views, plan.is_test, plan.groups
         n = N - 2 * s
         assert views == g[f"s{s}.frame_indices"].tolist() and len(views) == n
         assert torch.equal(p, poses[s:s + n])                   # frame i: pose poses[start + i]
@@ -113,13 +115,36 @@ def test_start_and_frame_index_mapping_on_the_host():
         for i0, i1, active in groups:
             assert all(tuple(torch.nonzero(bw[views[i]])[:, 0].tolist()) == active for i in range(i0, i1))
         for fpc in (1, 3):
-            gs = novel_views._plan(lt, poses, W, H, tests, None, s, fpc)[3]
+            gs = PosePlan(lt, poses, W, H, tests, None, s, fpc).groups
             assert max(i1 - i0 for i0, i1, _ in gs) <= fpc
             assert [i for i0, i1, _ in gs for i in range(i0, i1)] == list(range(n))
     fi = [i % len(lt.r_c2w) for i in range(N)]
-    _, views, _, _, _, _ = novel_views._plan(lt, poses, W, H, (), fi, 3, None)
+    views = PosePlan(lt, poses, W, H, (), fi, 3, None).views
     assert views == fi[3:3 + N - 6]
-    assert novel_views._plan(lt, poses[:3], W, H, (), None, 2, None)[1] == []     # start past the middle: no frame
+    assert PosePlan(lt, poses[:3], W, H, (), None, 2, None).views == []          # start past the middle: no frame
+
+
+def test_a_plan_on_a_cpu_scene_is_host_only(monkeypatch):
+    """Construction launches nothing and works on a CPU scene; only the device half refuses it."""
+    from localrf_amd import _native
+
+    def forbidden(*a, **k):
+        raise AssertionError("a native call was reached while planning")
+    for name in ("launch", "call"):
+        monkeypatch.setattr(_native, name, forbidden)
+    lt, g = scene("cpu")
+    poses = torch.from_numpy(g["poses"])
+    W, H = int(g["W"]), int(g["H"])
+    tests = g["test_frames"].tolist()
+    plan = PosePlan(lt, poses, W, H, tests, chunk=100)
+    assert (plan.lt, plan.W, plan.H, plan.chunk, plan.n) == (lt, W, H, 100, poses.shape[0])
+    assert plan.views == g["s0.frame_indices"].tolist() and plan.is_test == [v in tests for v in plan.views]
+    assert [i for i0, i1, _ in plan.groups for i in range(i0, i1)] == list(range(plan.n))
+    assert torch.equal(plan.poses, poses[:, :3])
+    for exposure in (False, True):
+        with pytest.raises(NativeError, match="no CPU fallback") as e:
+            plan.on_device(exposure=exposure)
+        assert "cpu" in str(e.value)
 
 
 def test_refusals_before_any_device_work():
