@@ -77,6 +77,8 @@ class FusedAdam(torch.optim.Optimizer):
                     st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
                 step = int(st["step"]) + 1      # int() also reads the tensor form torch.optim.Adam stores
                 st["step"] = step
+                if p.numel() == 0:              # nothing to step (torch.optim.Adam: state and counter, no update); a null
+                    continue                    # data_ptr() must not reach the table, which refuses null pointers
                 bc1 = 1.0 - b1 ** step
                 bc2_sqrt = math.sqrt(1.0 - b2 ** step)
                 g = p.grad if p.grad.is_contiguous() and p.grad.dtype == torch.float32 else p.grad.contiguous().float()
@@ -135,7 +137,9 @@ class StaticAdamPlan:
     per-tensor step_size / bc2_sqrt are read by the kernel from a DEVICE table at execution time (lrf_adam_step_dev), so
     that the launches can be captured once in a hipGraph and replayed with the learning rates, bias corrections and
     "this view was not sampled: skip" flags the host writes before each replay.  Same arithmetic and per-parameter
-    state (`step`, `exp_avg`, `exp_avg_sq`) as FusedAdam.step / torch.optim.Adam; state dicts stay interchangeable."""
+    state (`step`, `exp_avg`, `exp_avg_sq`) as FusedAdam.step / torch.optim.Adam; state dicts stay interchangeable.
+    An empty parameter is left alone, as torch.optim.Adam leaves it; between two others it splits their class into two
+    launches, which also gives up the fused layout refresh (_parts): put it at either end of the pairs to keep that."""
 
     def __init__(self, pairs):
         self.pairs = list(pairs)                                  # [(FusedAdam, parameter)], launch order
@@ -164,12 +168,30 @@ class StaticAdamPlan:
             classes.setdefault((tuple(grp["betas"]), grp["eps"], p.device), []).append(i)
         return classes
 
+    def _parts(self, idx):
+        """The launches of one class: runs of consecutive pair indices, LRF_ADAM_MAX at the most, without the empty parameters
+        (their null data_ptr() must not reach the table; torch.optim.Adam leaves them alone too).  Consecutive, because the
+        kernel reads row j of `scalars_dev[part[0]:]` for the j-th tensor of its table.  An empty parameter between two others
+        therefore splits a class that would fit one table into two launches, and a class of more than one launch is not
+        stepped through lrf_adam_step_pack (packs() says so; the next forward repacks the layout cache): correct, one
+        launch and one repack slower."""
+        parts = []
+        for i in idx:
+            if self.pairs[i][1].numel() == 0:
+                continue
+            if parts and parts[-1][-1] == i - 1 and len(parts[-1]) < N.LRF_ADAM_MAX:
+                parts[-1].append(i)
+            else:
+                parts.append([i])
+        return parts
+
     def packs(self, field):
         """Whether launch() would step this field through lrf_adam_step_pack right now, i.e. leave its layout cache holding
         the stepped values (the captured iteration then needs no refresh node in front of its forward)."""
         for idx in self._classes().values():
-            if len(idx) <= N.LRF_ADAM_MAX:
-                t = _pack_target(self.pairs[i][0].pack_field for i in idx)
+            parts = self._parts(idx)
+            if len(parts) == 1:
+                t = _pack_target(self.pairs[i][0].pack_field for i in parts[0])
                 if t is not None and t[0] is field:
                     return True
         return False
@@ -189,15 +211,15 @@ class StaticAdamPlan:
         if order != list(range(len(self.pairs))):
             raise ValueError("StaticAdamPlan: pairs must be grouped by (betas, eps, device)")
         for ((b1, b2), eps, dev), idx in classes.items():
-            for lo in range(0, len(idx), N.LRF_ADAM_MAX):
-                part = idx[lo:lo + N.LRF_ADAM_MAX]
+            parts = self._parts(idx)
+            for part in parts:
                 tab = (N.LrfAdamTensor * len(part))()
                 for t, i in zip(tab, part):
                     opt, p = self.pairs[i]
                     s = opt.state[p]
                     t.p, t.g, t.m, t.v = p.data_ptr(), p.grad.data_ptr(), s["exp_avg"].data_ptr(), s["exp_avg_sq"].data_ptr()
                     t.n, t.step_size, t.bc2_sqrt = p.numel(), 0.0, 0.0
-                fused = _pack_target(self.pairs[i][0].pack_field for i in part) if len(idx) <= N.LRF_ADAM_MAX else None
+                fused = _pack_target(self.pairs[i][0].pack_field for i in part) if len(parts) == 1 else None
                 if fused is not None:                         # the step leaves the field's layout cache holding the stepped values
                     field, (cp, keep, cache) = fused
                     N.launch("lrf_adam_step_pack", dev, tab, len(part), scalars_dev[part[0]:].data_ptr(), b1, b2, eps,

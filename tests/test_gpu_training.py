@@ -6,6 +6,7 @@ import pytest
 import torch
 
 from oracle import vm_render_torch as ot
+from optim_reg_cases import TVLoss, density_l1_expression, tv_expression
 from util import FIELD_KW, quiet, torch_scene_chain
 
 pytestmark = pytest.mark.gpu
@@ -313,13 +314,7 @@ def test_density_l1_kernel_vs_reference_formula(grid, act):
             p.mul_(6.0)                           # spread the features over both sides of the clamp / relu
 
     def reference(fld):                           # verbatim arithmetic of the reference method
-        n = int(torch.prod(fld.gridSize))
-        feat = torch.zeros((n,), device=DEV)
-        for i in range(3):
-            pl = fld.density_plane[i].view(-1, int(torch.prod(fld.gridSize[fld.matMode[i]])))
-            ln = fld.density_line[i].view(-1, int(fld.gridSize[fld.vecMode[i]]))
-            feat = feat + torch.sum(torch.bmm(pl[..., None], ln[:, None]).view(-1, n), dim=0)
-        return torch.sqrt(fld.feature2density(feat).clamp(1e-5)).mean()
+        return density_l1_expression(list(fld.density_plane), list(fld.density_line), fld.feature2density)
     res = []
     for fn in (f.density_L1, lambda: reference(f)):
         for p in f.parameters():
@@ -412,27 +407,11 @@ def test_tv_loss_kernel_vs_reference_module():
     applied as tensoRF.py:94-110, non-cubic grid, non-default weight."""
     from util import make_field
 
-    class TVLoss(torch.nn.Module):                      # the reference module, verbatim arithmetic
-        def __init__(self, TVLoss_weight=1):
-            super().__init__()
-            self.TVLoss_weight = TVLoss_weight
-
-        def forward(self, x):
-            h_x, w_x = x.size()[2], x.size()[3]
-            tv = 0
-            if h_x > 1:
-                tv += torch.pow((x[:, :, 1:, :] - x[:, :, :h_x - 1, :]), 2).mean()
-            if w_x > 1:
-                tv += torch.pow((x[:, :, :, 1:] - x[:, :, :, :w_x - 1]), 2).mean()
-            return self.TVLoss_weight * 2 * tv
     f = quiet(make_field, [37, 41, 29], "cpu", seed=9).to(DEV)
-    reg = TVLoss(0.7)
+    reg = TVLoss(0.7)                                   # the reference module, verbatim arithmetic
 
     def reference(planes, lines):
-        total = 0
-        for i in range(3):
-            total = total + reg(planes[i].transpose(0, 1)) * 1e-2 + reg(lines[i].transpose(0, 1)) * 1e-3
-        return total
+        return tv_expression(planes, lines, reg)
     for native, ref_args in ((f.TV_loss_density, (f.density_plane, f.density_line)),
                              (f.TV_loss_app, (f.app_plane, f.app_line))):
         res = []
