@@ -13,6 +13,10 @@ extern "C" {
 /* When set (device buffer of n_CUs * 8 waves * 8 uint64), lrf_render_fwd runs k_shade3<TIMED> and leaves per-wave
  * s_memtime totals there: {prologue, header + position, gather + split, -, -, chain, tiles, finalize}; NULL = off. */
 void    lrf_debug_set_dump(float* buf);
+/* When set (device buffer of R * 4 uint64, R = the rays of the largest march that follows), every single-field k_march runs
+ * with phase clocks and leaves per ray (= per wave) the shader-cycle totals {line and z staging with its barrier, pass A
+ * (gathers -> alpha), pass B (scans, weights, compaction), epilogue}; same results as the production kernel.  NULL = off. */
+void    lrf_debug_march_phases(uint64_t* buf);
 void    lrf_debug_set_lds_lines(int on);          /* k_march: density lines staged in LDS (default on when they fit) */
 void    lrf_debug_set_pipe_chunk(int rays);       /* rays per chunk of lrf_render_fwd's two-stream large-batch mode (default 16384; batches of at least two chunks); 0: one pass over the whole batch.  Changes lrf_workspace_bytes: set it before sizing a workspace */
 void    lrf_debug_set_scene_fuse(int on);         /* lrf_scene_fwd: several fields per march / colour launch (default on); 0 = field by field */

@@ -144,6 +144,7 @@ SYMBOLS = {
     "lrf_last_error": (C.c_char_p, []),
     "lrf_error_slot": (C.c_void_p, []),
     "lrf_debug_set_dump": (None, [C.c_void_p]),
+    "lrf_debug_march_phases": (None, [C.c_void_p]),
     "lrf_debug_set_lds_lines": (None, [C.c_int]),
     "lrf_debug_set_pipe_chunk": (None, [C.c_int]),
     "lrf_debug_set_scene_fuse": (None, [C.c_int]),

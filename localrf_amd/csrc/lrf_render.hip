@@ -258,14 +258,24 @@ template <> struct FieldArg<true> { typedef MultiF type; };
 __device__ __forceinline__ const DField& field_of(const DField& f, int) { return f; }
 __device__ __forceinline__ const DField& field_of(const MultiF& m, int k) { return m.f[k]; }
 
-template <bool LDSL, bool MULTI = false>
-__global__ __launch_bounds__(1024) void k_march(
-    typename FieldArg<MULTI>::type fin, const float* __restrict__ rays, const float* __restrict__ z, int R, int S,
+// Pass B runs the in-chunk scans of MARCH_G chunks together (see there).
+constexpr int MARCH_G = 8;
+constexpr int MARCH_SR = 3;         // rounds of the line staging whose loads are issued together
+// TIMED (debug, lrf_debug_march_phases): __builtin_readcyclecounter() totals per wave -> dump[ray][4] = {line / z staging
+// with its barrier, pass A, pass B, epilogue}; the production kernels carry none of it.
+// ZLDS: the sample schedule z[0..S) sits in LDS behind the lines (it is the same 4 * S bytes for every ray: pass A read
+// z[k] and z[k + 1] and pass B z[k] again per lane through the vector-memory path); launch_march decides.
+template <bool LDSL, bool MULTI, bool TIMED>
+__device__ __forceinline__ void march_body(
+    const typename FieldArg<MULTI>::type& fin, const float* __restrict__ rays, const float* __restrict__ z, int R, int S,
     uint32_t flags, float floater,
     float* __restrict__ depth, float* __restrict__ acc_ws, float* __restrict__ w_all,
     int* __restrict__ ncomp, uint16_t* __restrict__ cidx, float* __restrict__ cw,
-    float* __restrict__ feat_out /* [R,S] density feature, -inf where not evaluated; or null */) {
+    float* __restrict__ feat_out, const bool zlds) {
   extern __shared__ float s_alpha_all[];
+  unsigned long long tk[4] = {0, 0, 0, 0}, tlast = 0;
+#define LRF_MTICK(i) do { if (TIMED) { const unsigned long long now_ = __builtin_readcyclecounter(); tk[i] += now_ - tlast; tlast = now_; } } while (0)
+  if (TIMED) tlast = __builtin_readcyclecounter();
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int nb = gridDim.x;                              // XCD-aware block order, see tile_walk_begin
   const int lb = (nb % 8 == 0) ? (int)(blockIdx.x % 8) * (nb / 8) + (int)(blockIdx.x / 8) : (int)blockIdx.x;
@@ -277,19 +287,50 @@ __global__ __launch_bounds__(1024) void k_march(
   int io_ray = ray;                                        // where the caller keeps this ray (rays in, depth out)
   if constexpr (MULTI) io_ray = multi_io(fin, fk_, ray);
   const float* s_line[3] = {nullptr, nullptr, nullptr};
+  float* s_z = s_alpha_all + (size_t)nw * S;               // the schedule, behind the alpha slices and the lines
+  const int zi0 = threadIdx.x, zi1 = threadIdx.x + blockDim.x;
+  float z0 = 0.0f, z1 = 0.0f;                              // its first two rounds are loaded here, in flight under the line loads
+  if (zlds && zi0 < S) z0 = z[zi0];
+  if (zlds && zi1 < S) z1 = z[zi1];
   if (LDSL) {                                              // lines behind the alpha slices (whole block: before any return)
+    // All loads of a thread's share first, then the LDS stores: MARCH_SR rounds of the three lines are 3 * MARCH_SR
+    // independent loads in flight (branch-free: a clamped index, the store is what is predicated).  Line by line and
+    // round by round, as this was, each load was waited for before the next one was issued -- nine memory latencies in
+    // a row in front of the barrier at 300^3 (the phase clocks: 6.8 K of a wave's 92 K cycles).
     float* base = s_alpha_all + (size_t)nw * S;
+    float4* dst[3]; const float4* src[3]; int n[3];
 #pragma unroll
     for (int p = 0; p < 3; ++p) {
-      const int n = f.ll[p] * LRF_CD / 4;
-      float4* dst = reinterpret_cast<float4*>(base);
-      const float4* src = reinterpret_cast<const float4*>(f.dline[p]);
-      for (int i = threadIdx.x; i < n; i += blockDim.x) dst[i] = src[i];
+      n[p] = f.ll[p] * LRF_CD / 4;
+      dst[p] = reinterpret_cast<float4*>(base);
+      src[p] = reinterpret_cast<const float4*>(f.dline[p]);
       s_line[p] = base;
       base += f.ll[p] * LRF_CD;
     }
-    __syncthreads();
+    s_z = base;
+    const int nmax = max(n[0], max(n[1], n[2])), bd = blockDim.x;
+    for (int i0 = threadIdx.x; i0 < nmax; i0 += MARCH_SR * bd) {
+      float4 v[3][MARCH_SR];
+#pragma unroll
+      for (int p = 0; p < 3; ++p)
+#pragma unroll
+        for (int r = 0; r < MARCH_SR; ++r) v[p][r] = src[p][min(i0 + r * bd, n[p] - 1)];
+#pragma unroll
+      for (int p = 0; p < 3; ++p)
+#pragma unroll
+        for (int r = 0; r < MARCH_SR; ++r) {               // (keeps the compiler from sinking each load into its predicated store)
+          asm volatile("" : "+v"(v[p][r].x), "+v"(v[p][r].y), "+v"(v[p][r].z), "+v"(v[p][r].w));
+          if (i0 + r * bd < n[p]) dst[p][i0 + r * bd] = v[p][r];
+        }
+    }
   }
+  if (zlds) {
+    if (zi0 < S) s_z[zi0] = z0;
+    if (zi1 < S) s_z[zi1] = z1;
+    for (int i = zi1 + blockDim.x; i < S; i += blockDim.x) s_z[i] = z[i];
+  }
+  if (LDSL || zlds) __syncthreads();
+  LRF_MTICK(0);
   if (ray >= R) return;
   float* s_alpha = s_alpha_all + (size_t)wave * S;
   const int oray = f.perm ? f.perm[ray] : io_ray;          // where the caller sees this ray (ray sorting / a chunk of a multi-field batch)
@@ -318,7 +359,7 @@ __global__ __launch_bounds__(1024) void k_march(
       const int k = (c << 6) + lane;
       float alpha = 0.0f, fk = -INFINITY;
       if (live && k < S - 1) {                             // last sample is never valid (:600)
-        const float zk = z[k];
+        const float zk = zlds ? s_z[k] : z[k];
         float x[3], u[3];
         sample_point(f, o, dh, zk, x, u);
         bool valid = true;
@@ -326,7 +367,7 @@ __global__ __launch_bounds__(1024) void k_march(
         if (valid) {
           fk = density_feature_m<LDSL>(f, u, s_line);
           const float sigma = feature2density(fk, f.density_shift, relu);            // :603-608
-          const float dist = z[k + 1] - zk;                                          // :584-587
+          const float dist = (zlds ? s_z[k + 1] : z[k + 1]) - zk;                    // :584-587
           alpha = 1.0f - expf(-sigma * dist * f.distance_scale);                     // :610
         }
       }
@@ -344,42 +385,72 @@ __global__ __launch_bounds__(1024) void k_march(
     }
   }
   // (each wave only touches its own LDS slice: no barrier needed, LDS ops are in order per wave)
+  LRF_MTICK(1);
 
+  // pass B: transmittance, weights, compaction.  Only `carry` links the 64-sample chunks of a ray; the scan inside a chunk
+  // (wave_scan_prod: eight dependent cross-lane round trips) does not depend on it.  So the chunks are taken MARCH_G at a
+  // time: step one reads their alphas and runs their MARCH_G shuffle ladders side by side (step d of every chunk before
+  // step 2d: the round trips overlap instead of queueing), step two walks them in order with `carry` as before.  Per chunk
+  // the arithmetic is wave_scan_prod's, product for product, so every output keeps its bits.
   float acc = 0.0f, dsum = 0.0f, kbar = 0.0f;
   int nsh = 0;
   const int npass = floater > 0.0f ? 2 : 1;
   for (int pass = 0; pass < npass; ++pass) {
     const bool emit = (pass == npass - 1);
     float carry = 1.0f, a_acc = 0.0f, a_d = 0.0f, a_k = 0.0f;
-    for (int c = 0; c < nchunk; ++c) {
-      const int k = (c << 6) + lane;
-      float alpha = 0.0f;
-      if (k < S) {
-        alpha = s_alpha[k];
-        if (pass == 1 && (float)k < kbar * floater) alpha = 0.0f;                  // :617-619
-        if (k == S - 1) alpha = 1.0f;                                               // :24
-      }
-      const float v = (k < S) ? (1.0f - alpha + 1e-10f) : 1.0f;                    // :25-29
-      float excl, total;
-      wave_scan_prod(v, lane, excl, total);
-      const float T = carry * excl;
-      carry *= total;
-      const float w = alpha * T;                                                    // :31
-      if (pass == 0) {
-        a_acc += w;
-        a_d += (k < S) ? w * z[k] : 0.0f;
-        a_k += w * (float)k;
-      }
-      if (emit) {
-        if (w_all && k < S) w_all[(size_t)oray * S + k] = w;
-        const bool sh = (k < S) && (w > f.weight_thres);                            // :622
-        const unsigned long long m = __ballot(sh);
-        if (sh) {
-          const int pos = nsh + __popcll(m & ((1ull << lane) - 1ull));
-          cidx[(size_t)ray * S + pos] = (uint16_t)k;
-          cw[(size_t)ray * S + pos] = w;
+    for (int c0 = 0; c0 < nchunk; c0 += MARCH_G) {
+      float al[MARCH_G], p[MARCH_G], ex[MARCH_G];
+#pragma unroll
+      for (int j = 0; j < MARCH_G; ++j) {                  // (chunks past the last one: k >= S, a scan of ones)
+        const int k = ((c0 + j) << 6) + lane;
+        float alpha = 0.0f;
+        if (k < S) {
+          alpha = s_alpha[k];
+          if (pass == 1 && (float)k < kbar * floater) alpha = 0.0f;                  // :617-619
+          if (k == S - 1) alpha = 1.0f;                                               // :24
         }
-        nsh += __popcll(m);
+        al[j] = alpha;
+        p[j] = (k < S) ? (1.0f - alpha + 1e-10f) : 1.0f;                              // :25-29
+      }
+#pragma unroll
+      for (int d = 1; d < 64; d <<= 1) {
+        float t[MARCH_G];
+#pragma unroll
+        for (int j = 0; j < MARCH_G; ++j) t[j] = __shfl_up(p[j], d, 64);
+#pragma unroll
+        for (int j = 0; j < MARCH_G; ++j) if (lane >= d) p[j] *= t[j];
+      }
+#pragma unroll
+      for (int j = 0; j < MARCH_G; ++j) {
+        ex[j] = __shfl_up(p[j], 1, 64);
+        if (lane == 0) ex[j] = 1.0f;
+      }
+#pragma unroll
+      for (int j = 0; j < MARCH_G; ++j) p[j] = __shfl(p[j], 63, 64);               // the chunk's total
+#pragma unroll
+      for (int j = 0; j < MARCH_G; ++j) {
+        if (c0 + j >= nchunk) break;
+        const int k = ((c0 + j) << 6) + lane;
+        const float alpha = al[j];
+        const float T = carry * ex[j];
+        carry *= p[j];
+        const float w = alpha * T;                                                    // :31
+        if (pass == 0) {
+          a_acc += w;
+          a_d += (k < S) ? w * (zlds ? s_z[k] : z[k]) : 0.0f;
+          a_k += w * (float)k;
+        }
+        if (emit) {
+          if (w_all && k < S) w_all[(size_t)oray * S + k] = w;
+          const bool sh = (k < S) && (w > f.weight_thres);                            // :622
+          const unsigned long long m = __ballot(sh);
+          if (sh) {
+            const int pos = nsh + __popcll(m & ((1ull << lane) - 1ull));
+            cidx[(size_t)ray * S + pos] = (uint16_t)k;
+            cw[(size_t)ray * S + pos] = w;
+          }
+          nsh += __popcll(m);
+        }
       }
     }
     if (pass == 0) {
@@ -388,12 +459,40 @@ __global__ __launch_bounds__(1024) void k_march(
       kbar = wave_sum(a_k);
     }
   }
+  LRF_MTICK(2);
   if (lane == 0) {
     depth[oray] = dsum / dn;                                                        // :615
     acc_ws[ray] = acc;
     ncomp[ray] = nsh;
     if (f.rdir) *reinterpret_cast<float4*>(f.rdir + (size_t)ray * 4) = make_float4(dh[0], dh[1], dh[2], dn);
   }
+  LRF_MTICK(3);
+  if (TIMED && f.dump && lane == 0) {
+    unsigned long long* dp = reinterpret_cast<unsigned long long*>(f.dump) + (size_t)ray * 4;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) dp[i] = tk[i];
+  }
+#undef LRF_MTICK
+}
+
+template <bool LDSL, bool MULTI = false>
+__global__ __launch_bounds__(1024) void k_march(
+    typename FieldArg<MULTI>::type fin, const float* __restrict__ rays, const float* __restrict__ z, int R, int S,
+    uint32_t flags, float floater,
+    float* __restrict__ depth, float* __restrict__ acc_ws, float* __restrict__ w_all,
+    int* __restrict__ ncomp, uint16_t* __restrict__ cidx, float* __restrict__ cw,
+    float* __restrict__ feat_out /* [R,S] density feature, -inf where not evaluated; or null */, int zlds) {
+  march_body<LDSL, MULTI, false>(fin, rays, z, R, S, flags, floater, depth, acc_ws, w_all, ncomp, cidx, cw, feat_out, zlds != 0);
+}
+// the same with the phase clocks (fin.dump: [R][4] uint64)
+template <bool LDSL>
+__global__ __launch_bounds__(1024) void k_march_timed(
+    DField fin, const float* __restrict__ rays, const float* __restrict__ z, int R, int S,
+    uint32_t flags, float floater,
+    float* __restrict__ depth, float* __restrict__ acc_ws, float* __restrict__ w_all,
+    int* __restrict__ ncomp, uint16_t* __restrict__ cidx, float* __restrict__ cw,
+    float* __restrict__ feat_out, int zlds) {
+  march_body<LDSL, false, true>(fin, rays, z, R, S, flags, floater, depth, acc_ws, w_all, ncomp, cidx, cw, feat_out, zlds != 0);
 }
 
 // Exclusive prefix sum of per-ray tile counts: toff[r] = sum_{q<r} ceil(ncomp[q]/16),
@@ -912,6 +1011,7 @@ static Workspace carve(void* ws, int R, int S) {
 
 // Test hooks (include/lrf_debug.h): process-wide, not part of the re-entrant ABI.
 static float* g_dump = nullptr;    // lrf_debug_set_dump: device buffer for the s_memtime totals of k_shade3<TIMED>
+static unsigned long long* g_march_dump = nullptr;   // lrf_debug_march_phases: device buffer [R][4] for the phase clocks of k_march_timed
 static int g_no_lds_lines = 0;     // lrf_debug_set_lds_lines(0): k_march reads its lines from global memory
 static int g_pipe_chunk = 16384;    // lrf_debug_set_pipe_chunk: rays per chunk of lrf_render_fwd's large-batch mode (0: one pass over the whole batch, as rounds 1-5)
 static int g_no_scene_fuse = 0;    // lrf_debug_set_scene_fuse(0): lrf_scene_fwd renders field by field (the tests compare the two forms)
@@ -1013,27 +1113,46 @@ static int march_lds_rays(const int32_t ll[3], int S) {
     if (((size_t)cand * S * sizeof(float) + lds_l) * (16 / cand) <= 156 * 1024) return cand;
   return 0;
 }
+// whether the schedule's S floats go into LDS too: the choice of march_lds_rays() stands, z joins where the same budget still
+// holds with it (300^3 at S = 512: (8 + 28.8 + 2 KB) x 4 = 155.2 KB; 500^3 at 576 and 640^3 at 738 fit as well); nw = 0 is
+// k_march<false>, four alpha slices inside the 64 KB every kernel may ask for
+static bool march_lds_z(const int32_t ll[3], int S, int nw) {
+  if (!nw) return (size_t)5 * S * sizeof(float) <= 64 * 1024;
+  const size_t lds_l = (size_t)(ll[0] + ll[1] + ll[2]) * LRF_CD * sizeof(float);
+  return ((size_t)(nw + 1) * S * sizeof(float) + lds_l) * (16 / nw) <= 156 * 1024;
+}
 // k_march launch: lines in LDS when the three of them (+ the alpha slices) leave four workgroups per CU.  mf (the fused
 // multi-field form) exists with the lines in LDS only: lrf_scene_fwd does not fuse when march_lds_rays() is 0.
 static void launch_march(const DField& d, const float* rays, const float* z, int R, int S, uint32_t flags, float floater,
                          float* depth, float* acc, float* w_all, int* ncomp, uint16_t* cidx, float* cw, float* feat,
                          hipStream_t st, const MultiF* mf = nullptr) {
-  // 4 waves per SIMD either way (123 VGPRs): 4 / 2 / 1 workgroups of 4 / 8 / 16 rays per CU, whichever keeps
+  // 4 waves per SIMD either way: 4 / 2 / 1 workgroups of 4 / 8 / 16 rays per CU, whichever keeps
   // alpha slices + lines within the CU's 160 KB (300^3: 8 + 29 KB x 4; 500^3: 18 + 48 KB x 2; 640^3: 47 + 61 KB x 1)
   const size_t lds_l = (size_t)(d.ll[0] + d.ll[1] + d.ll[2]) * LRF_CD * sizeof(float);
   const int nw = march_lds_rays(d.ll, S);
+  const int zlds = march_lds_z(d.ll, S, nw) ? 1 : 0;
+  const size_t lds_z = zlds ? (size_t)S * sizeof(float) : 0;
+  if (g_march_dump && !mf) {                               // test hook: phase clocks -> the dump buffer
+    DField dt = d;
+    dt.dump = reinterpret_cast<float*>(g_march_dump);
+    if (nw) hipLaunchKernelGGL(k_march_timed<true>, dim3((R + nw - 1) / nw), dim3(64 * nw), (size_t)nw * S * sizeof(float) + lds_l + lds_z, st,
+                               dt, rays, z, R, S, flags, floater, depth, acc, w_all, ncomp, cidx, cw, feat, zlds);
+    else    hipLaunchKernelGGL(k_march_timed<false>, dim3((R + 3) / 4), dim3(256), (size_t)4 * S * sizeof(float) + lds_z, st,
+                               dt, rays, z, R, S, flags, floater, depth, acc, w_all, ncomp, cidx, cw, feat, zlds);
+    return;
+  }
   if (nw) {
-    const size_t lds = (size_t)nw * S * sizeof(float) + lds_l;
+    const size_t lds = (size_t)nw * S * sizeof(float) + lds_l + lds_z;
     if (mf) {                                              // (the caller made sure that Rf is a multiple of 16 >= nw)
       hipLaunchKernelGGL((k_march<true, true>), dim3((R + nw - 1) / nw), dim3(64 * nw), lds, st,
-                         *mf, rays, z, R, S, flags, floater, depth, acc, w_all, ncomp, cidx, cw, feat);
+                         *mf, rays, z, R, S, flags, floater, depth, acc, w_all, ncomp, cidx, cw, feat, zlds);
       return;
     }
     hipLaunchKernelGGL(k_march<true>, dim3((R + nw - 1) / nw), dim3(64 * nw), lds, st,
-                       d, rays, z, R, S, flags, floater, depth, acc, w_all, ncomp, cidx, cw, feat);
+                       d, rays, z, R, S, flags, floater, depth, acc, w_all, ncomp, cidx, cw, feat, zlds);
   } else {
-    hipLaunchKernelGGL(k_march<false>, dim3((R + 3) / 4), dim3(256), (size_t)4 * S * sizeof(float), st,
-                       d, rays, z, R, S, flags, floater, depth, acc, w_all, ncomp, cidx, cw, feat);
+    hipLaunchKernelGGL(k_march<false>, dim3((R + 3) / 4), dim3(256), (size_t)4 * S * sizeof(float) + lds_z, st,
+                       d, rays, z, R, S, flags, floater, depth, acc, w_all, ncomp, cidx, cw, feat, zlds);
   }
 }
 
@@ -1111,6 +1230,7 @@ static hipError_t lds_opt_in() {
     {reinterpret_cast<const void*>(&k_sort_rays), LRF_SORT_MAX_R * 4},
     {reinterpret_cast<const void*>(&k_march<true>), L160},
     {reinterpret_cast<const void*>(&k_march<true, true>), L160},
+    {reinterpret_cast<const void*>(&k_march_timed<true>), L160},
     {reinterpret_cast<const void*>(&k_shade3<8, true, false>), L160 - 256},
     {reinterpret_cast<const void*>(&k_shade3<8, false, false>), L160 - 256},
     {reinterpret_cast<const void*>(&k_shade3<8, true, true>), L160 - 256},
@@ -1172,6 +1292,7 @@ extern "C" {
 
 int lrf_abi_version(void) { return LRF_ABI_VERSION; }
 void lrf_debug_set_dump(float* buf) { g_dump = buf; }
+void lrf_debug_march_phases(uint64_t* buf) { g_march_dump = reinterpret_cast<unsigned long long*>(buf); }
 void lrf_debug_set_bwd_overlap(int on) { g_bwd_overlap = (on & 1) ? 1 : 0; if (on > 1) g_wgrad_split = (on >> 1) - 1; }   // on = 1 + 2 * (n + 1): k_wgrad_w2w3 on the caller's stream (n > 0) or on the side stream (n = 0)
 void lrf_debug_set_lds_lines(int on) { g_no_lds_lines = on ? 0 : 1; }
 void lrf_debug_set_pipe_chunk(int rays) { g_pipe_chunk = rays > 0 ? rays : 0; }
