@@ -87,7 +87,9 @@ def flow_loss(depth_map, directions, ij, cam2world, view_ids, starting_frame_id,
     cam2world = local_tensorfs.get_cam2world(starting_id=starting_frame_id) [F,3,4]; view_ids [V]; flows [V*n,2],
     masks [V*n]; focal = local_tensorfs.focal(W) (tensor [1] or float), center = local_tensorfs.center(W, H) [2].
     per_view: return the V per-view sums of the clipped array instead of its mean (mean = sum / (V n): `combine` folds that
-    factor into the term's weight).  frame_ids: int32 device [2, V] = (view - starting_frame_id, view == F - 1) prepared by the
+    factor into the term's weight).  Contract of per_view=True: the backward reads element 0 of the incoming gradient and
+    applies it to every view, so the V sums must enter the total with one and the same weight, as `combine` gives them;
+    unequal weights over views are not honoured (the C signatures carry one gradient scalar).  frame_ids: int32 device [2, V] = (view - starting_frame_id, view == F - 1) prepared by the
     caller (the captured iteration stages it with its other inputs) -- otherwise formed here from view_ids."""
     N.require_gpu(depth_map, "depth_map", _FEATURE)
     dev = depth_map.device
@@ -149,7 +151,9 @@ class _DepthLossFn(torch.autograd.Function):
 
 def depth_loss(depth_map, invdepths, n_views, quantile=0.8, return_arr=False, per_view=False):
     """`depth_loss_arr.mean()` of train.py:414-421: compute_depth_loss(1 / depth_map.clamp(1e-6), invdepths) per view,
-    entries above the view's 0.8-quantile zeroed.  per_view: the n_views per-view sums instead of the mean (see flow_loss)."""
+    entries above the view's 0.8-quantile zeroed.  per_view: the n_views per-view sums instead of the mean, under flow_loss's
+    contract: the backward reads element 0 of the incoming gradient, so every view's sum must carry the same weight (as
+    through `combine`); unequal weights over views are not honoured."""
     N.require_gpu(depth_map, "depth_map", _FEATURE)
     depth = depth_map.reshape(int(n_views), -1)
     if depth.shape[1] > N.LRF_LOSS_MAX_PER_VIEW:

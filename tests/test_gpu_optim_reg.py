@@ -15,11 +15,10 @@ from localrf_amd import FusedAdam
 from localrf_amd import _native as N
 from localrf_amd.field import _DensityL1Fn, _TVLossFn
 from localrf_amd.optim import StaticAdamPlan
-from util import make_field, make_rays, quiet
+from util import PAD, Pool, make_field, make_rays, quiet
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-PAD = 8                           # sentinel floats between two views
 
 
 def _kernel_constant(name, file="lrf_adam.inl"):
@@ -34,33 +33,6 @@ def _kernel_constant(name, file="lrf_adam.inl"):
 
 
 ADAM_SMALL_CAP = _kernel_constant("ADAM_SMALL_CAP")      # the small tensors k_adam_pack takes along
-
-
-class Pool:
-    """A device buffer filled with a sentinel (quiet NaNs whose payload is the element's index: a kernel that reads one
-    produces a NaN, a kernel that writes one changes bits) out of which the tests carve their tensors."""
-
-    def __init__(self, capacity):
-        self.pattern = torch.arange(capacity, dtype=torch.int32) | 0x7FC00000
-        self.buf = self.pattern.clone().to(DEV).view(torch.float32)
-        self.free = torch.ones(capacity, dtype=torch.bool)
-        self.at = PAD
-
-    def take(self, arr, mis=0):
-        """A view holding `arr`, 16-byte aligned (the buffer is) or, with mis=1, one float past that."""
-        arr = np.ascontiguousarray(arr, np.float32)
-        off = (self.at + 3) // 4 * 4 + mis
-        self.at = off + arr.size + PAD
-        assert self.at <= self.free.numel()
-        v = self.buf[off:off + arr.size]
-        v.copy_(torch.from_numpy(arr.reshape(-1)))
-        self.free[off:off + arr.size] = False
-        assert v.data_ptr() % 16 == 4 * mis
-        return v.view(arr.shape)
-
-    def intact(self):
-        got = self.buf.view(torch.int32).cpu()
-        return torch.equal(got[self.free], self.pattern[self.free])
 
 
 def _bits(t):

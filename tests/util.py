@@ -262,3 +262,34 @@ def check_grads(mine, ref, tol=1e-4, subset=None, gmax=None, tol_for=None):
         worst[name] = float((gm - gr).abs().max()) / den
         assert worst[name] <= (tol_for or {}).get(name, tol), (name, worst[name])
     return worst
+
+
+# ----------------------------------------------------------------- sentinel pools for direct kernel calls
+PAD = 8                           # sentinel floats between two views
+
+
+class Pool:
+    """A device buffer filled with a sentinel (quiet NaNs whose payload is the element's index: a kernel that reads one
+    produces a NaN, a kernel that writes one changes bits) out of which the tests carve their tensors."""
+
+    def __init__(self, capacity):
+        self.pattern = torch.arange(capacity, dtype=torch.int32) | 0x7FC00000
+        self.buf = self.pattern.clone().to("cuda:0").view(torch.float32)
+        self.free = torch.ones(capacity, dtype=torch.bool)
+        self.at = PAD
+
+    def take(self, arr, mis=0):
+        """A view holding `arr`, 16-byte aligned (the buffer is) or, with mis=1, one float past that."""
+        arr = np.ascontiguousarray(arr, np.float32)
+        off = (self.at + 3) // 4 * 4 + mis
+        self.at = off + arr.size + PAD
+        assert self.at <= self.free.numel()
+        v = self.buf[off:off + arr.size]
+        v.copy_(torch.from_numpy(arr.reshape(-1)))
+        self.free[off:off + arr.size] = False
+        assert v.data_ptr() % 16 == 4 * mis
+        return v.view(arr.shape)
+
+    def intact(self):
+        got = self.buf.view(torch.int32).cpu()
+        return torch.equal(got[self.free], self.pattern[self.free])
