@@ -664,6 +664,52 @@ int lrf_mesh_extract(const LrfMeshExtract* m, int64_t max_vertices, int64_t max_
                      uint8_t* rgb8_out /* nullable */, int32_t* faces, int64_t* counts /* device [2] */, void* workspace,
                      void* stream);
 
+/* A block-sparse TSDF volume: the dense volume above, of which only the 8 x 8 x 8 blocks that some depth pixel's truncation
+ * band reaches are stored (csrc/lrf_tsdf_blocks.inl states the arithmetic, fp32 without contraction).  The virtual lattice
+ * has 8Bx x 8By x 8Bz points at origin + (ix, iy, iz) * voxel.  marks uint8 [Bz,By,Bx] (starts at 0), table int32 [Bz,By,Bx]
+ * (-1, or the block's pool index; starts at -1), coords int32 [capacity,3] ((bx, by, bz) in pool order), pools tsdf
+ * [n_blocks,8,8,8] (a new block starts at 1), weight [n_blocks,8,8,8] (0) and rgb [n_blocks,8,8,8,3] (nullable; 0), x fastest;
+ * n_blocks: the blocks the table and the pools hold.  No hash, no atomics, no workgroup waits on another: a block's pool
+ * index is a fixed function of the frames and the call sequence, and every run leaves the same bytes.
+ * lrf_tsdf_blocks_touch: one lane per depth pixel (finite, positive, in [d_min, d_max]); with a, b the pixel's world points at
+ * depths max(d - trunc, 0) and d + trunc and m = voxel + (d + trunc) / focal, marks every block of the grid that meets the box
+ * [min(a, b) - m, max(a, b) + m], per axis floor((box - origin) / (8 voxel)) clipped to the grid.  Needs marks; pools unused.
+ * lrf_tsdf_blocks_assign: every marked block without a pool index gets the next indices, in block-linear (z, y, x) order, after
+ * the n_blocks that exist; count (device int64 [1]) receives the number of such blocks.  When n_blocks + count exceeds
+ * max_blocks the table is left as it was.  coords rows below coords_capacity are (re)written for every block of the table.
+ * With max_blocks = n_blocks nothing could fit: a counting call of two launches that writes count alone.  The caller counts,
+ * reads count back, grows coords and the pools, calls again (three launches) and adds count to n_blocks.  Needs marks;
+ * pools unused.  workspace: lrf_tsdf_blocks_assign_workspace_bytes(Bx, By, Bz) bytes (0 for a refused grid).
+ * lrf_tsdf_blocks_integrate: lrf_tsdf_integrate over the stored blocks, one workgroup per block, the pools read and written
+ * once per call: a stored point ends with the bits lrf_tsdf_integrate gives the same lattice point over the same frames.
+ * n_blocks = 0 launches nothing.
+ * lrf_mesh_extract_blocks: lrf_mesh_extract of the tsdf pool with the weight pool (min_weight > 0: always gated); a lattice
+ * point in no block reads as (tsdf 1, weight 0), so a missing block can leave a hole but never creates or moves a face.
+ * Vertices come in pool order, then (z, y, x, edge) inside the block; faces in the pool order of the cell's lowest corner,
+ * then (tetrahedron, triangle).  counts, capacities and the counting call as lrf_mesh_extract has them.  workspace:
+ * lrf_mesh_extract_blocks_workspace_bytes(n_blocks) bytes (0 for a refused count).
+ * Refused before any launch: null or misaligned pointers, Bx, By or Bz < 1, 8 B >= 2^31 on an axis, Bx By Bz >= 2^31, n_blocks
+ * < 0 or 512 n_blocks >= 2^31, voxel <= 0, trunc <= 0 (or NaN), d_min > d_max (or NaN), V, H or W < 1, V H W >= 2^31, rgb
+ * without rgb8 / rgb8_out or the reverse, a NaN level, min_weight <= 0, capacities outside [0, 2^31). */
+typedef struct LrfTsdfBlocks {
+  uint8_t* marks; int32_t* table; int32_t* coords;
+  float* tsdf; float* weight; float* rgb /* nullable */;
+  int32_t Bx, By, Bz, n_blocks;
+  float origin[3], voxel, trunc;
+} LrfTsdfBlocks;
+int lrf_tsdf_blocks_touch(const LrfTsdfBlocks* g, const float* depth, const float* cam2world, const float* focal,
+                          const float* center, int32_t V, int32_t H, int32_t W, float d_min, float d_max, void* stream);
+size_t lrf_tsdf_blocks_assign_workspace_bytes(int32_t Bx, int32_t By, int32_t Bz);
+int lrf_tsdf_blocks_assign(const LrfTsdfBlocks* g, int64_t max_blocks, int64_t coords_capacity, int64_t* count /* device [1] */,
+                           void* workspace, void* stream);
+int lrf_tsdf_blocks_integrate(const LrfTsdfBlocks* g, const float* depth, const uint8_t* rgb8 /* nullable */,
+                              const float* cam2world, const float* focal, const float* center, int32_t V, int32_t H, int32_t W,
+                              float d_min, float d_max, void* stream);
+size_t lrf_mesh_extract_blocks_workspace_bytes(int32_t n_blocks);
+int lrf_mesh_extract_blocks(const LrfTsdfBlocks* g, float level, float min_weight, int64_t max_vertices, int64_t max_faces,
+                            float* vertices, uint8_t* rgb8_out /* nullable */, int32_t* faces, int64_t* counts /* device [2] */,
+                            void* workspace, void* stream);
+
 /* Depth quantiles of a ray: the distance at which its accumulated weight first reaches q; q = 0.5 is the median depth, which
  * always lies on a surface the ray met (csrc/lrf_quantile.inl states the arithmetic: fp32 without contraction, one fixed
  * summation order per ray).  With C_i the inclusive prefix sum of the weights lrf_render_fwd leaves in weight_out and i* the

@@ -20,6 +20,8 @@ Public surface mirrors the reference's names:
                                     (median and quantile ray depth: the depth a fusion wants; no reference row)
   mesh.TsdfVolume / extract_mesh / scene_mesh
                                     (rendered depth fused into a TSDF volume, marching tetrahedra, PLY faces; no reference row)
+  mesh.SparseTsdfVolume / scene_mesh(sparse=True)
+                                    (the same volume stored in 8 x 8 x 8 blocks where depth reaches: long scenes; no reference row)
 The arithmetic of TensorVMSplit.forward and of LocalTensorfs.forward (ray generation, field
 blend, exposure) runs in hand-written HIP kernels for gfx950 (csrc/), reached through the C ABI
 of include/lrf.h.

@@ -138,6 +138,12 @@ class LrfMeshExtract(C.Structure):
                 ("origin", C.c_float * 3), ("voxel", C.c_float), ("level", C.c_float), ("min_weight", C.c_float)]
 
 
+class LrfTsdfBlocks(C.Structure):
+    _fields_ = [("marks", C.c_void_p), ("table", C.c_void_p), ("coords", C.c_void_p), ("tsdf", _f), ("weight", _f), ("rgb", _f),
+                ("Bx", C.c_int32), ("By", C.c_int32), ("Bz", C.c_int32), ("n_blocks", C.c_int32),
+                ("origin", C.c_float * 3), ("voxel", C.c_float), ("trunc", C.c_float)]
+
+
 # every symbol include/lrf.h and include/lrf_debug.h declare: (restype, argtypes)
 SYMBOLS = {
     "lrf_abi_version": (C.c_int, []),
@@ -239,6 +245,15 @@ SYMBOLS = {
     "lrf_mesh_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "lrf_mesh_extract": (C.c_int, [C.POINTER(LrfMeshExtract), C.c_int64, C.c_int64, _f, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_void_p, C.c_void_p]),
+    "lrf_tsdf_blocks_touch": (C.c_int, [C.POINTER(LrfTsdfBlocks), _f, _f, _f, _f, C.c_int32, C.c_int32, C.c_int32, C.c_float,
+                                        C.c_float, C.c_void_p]),
+    "lrf_tsdf_blocks_assign_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "lrf_tsdf_blocks_assign": (C.c_int, [C.POINTER(LrfTsdfBlocks), C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "lrf_tsdf_blocks_integrate": (C.c_int, [C.POINTER(LrfTsdfBlocks), _f, C.c_void_p, _f, _f, _f, C.c_int32, C.c_int32,
+                                            C.c_int32, C.c_float, C.c_float, C.c_void_p]),
+    "lrf_mesh_extract_blocks_workspace_bytes": (C.c_size_t, [C.c_int32]),
+    "lrf_mesh_extract_blocks": (C.c_int, [C.POINTER(LrfTsdfBlocks), C.c_float, C.c_float, C.c_int64, C.c_int64, _f, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "lrf_density_gradient": (C.c_int, [C.POINTER(LrfField), _f, C.c_int64, _f, _f, C.c_void_p]),
     "lrf_normals_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "lrf_render_normals": (C.c_int, [C.POINTER(LrfField), _f, _f, C.c_int32, C.c_int32, C.c_uint32, C.c_float, _f, C.c_int32,

@@ -1,7 +1,9 @@
 """Rendered depth fused into a TSDF volume and a triangle mesh extracted from it on the GPU (csrc/lrf_mesh.inl through
-lrf_tsdf_integrate and lrf_mesh_extract).
+lrf_tsdf_integrate and lrf_mesh_extract; csrc/lrf_tsdf_blocks.inl through lrf_tsdf_blocks_* and lrf_mesh_extract_blocks).
 
   TsdfVolume(origin, voxel, dims, trunc, device)   the three volume tensors; .integrate(frames) and .extract() -> mesh
+  SparseTsdfVolume(origin, voxel, blocks, trunc, device)  the same lattice stored in 8 x 8 x 8 blocks where depth reaches:
+                                                   .touch(frames), .allocate(), .integrate(frames), .extract(), .to_dense()
   extract_mesh(values, origin, voxel, level, ...)  marching tetrahedra of any [Nz,Ny,Nx] device tensor
   scene_mesh(local_tensorfs, W, H, voxel=...)      novel_views.render_poses in batches, each integrated and dropped, then extract
   pointcloud.write_ply(path, vertices, rgb8, faces=faces) writes the result
@@ -66,25 +68,50 @@ def _check_range(depth_range):
     return d_min, d_max
 
 
-def _extract(value, weight, rgb, origin, voxel, dims, level, min_weight, max_vertices, max_faces):
-    """Checked arguments, contiguous fp32 device tensors -> the mesh dict."""
-    dev = value.device
-    Nx, Ny, Nz = dims
-    ws = N.workspace("lrf_mesh", dev, Nx, Ny, Nz)
+def _check_frames(colours, dev, depth, poses, focal, center, rgb, depth_range, what="TsdfVolume"):
+    """The frame arguments of an integration into a volume on dev that keeps colours or not, checked on the host ->
+    (depth, rgb8 or None, poses, focal, center as contiguous device tensors, (V, H, W), (d_min, d_max))."""
+    V, H, W = _check_depth(depth)
+    if (rgb is not None) != colours:
+        raise ValueError(f"rgb goes with a volume that keeps colours: pass rgb to a {what}(colours=True) and only to it")
+    if rgb is not None:
+        if not torch.is_tensor(rgb):
+            raise TypeError("rgb must be a torch tensor or None")
+        if not (rgb.is_floating_point() or rgb.dtype is torch.uint8):
+            raise ValueError(f"rgb must hold floating-point or uint8 values, got {rgb.dtype}")
+        if tuple(rgb.shape) != (V, H, W, 3):
+            raise ValueError(f"rgb must be {(V, H, W, 3)} to go with depth {tuple(depth.shape)}, got {tuple(rgb.shape)}")
+        if rgb.device != depth.device:
+            raise ValueError("rgb and depth must live on the same device")
+    poses = _check_poses(poses, V)
+    focal, center = _check_intrinsics(focal, center, False)
+    d_min, d_max = _check_range(depth_range)
+    N.require_gpu(depth, "depth", "the TSDF integration")
+    if depth.device != dev:
+        raise ValueError(f"depth lives on {depth.device}, the volume on {dev}")
+    rgb8 = None
+    if rgb is not None:
+        if rgb.dtype is torch.uint8:
+            rgb8 = rgb.contiguous()
+        else:
+            from .novel_views import encode_frames
+            rgb8 = encode_frames(rgb.detach(), depth.detach())[0]
+    depth = N.conform(depth)
+    poses = poses.detach().to(device=dev, dtype=torch.float32).contiguous()
+    return depth, rgb8, poses, _dev_f32(focal, 1, dev), _dev_f32(center, 2, dev), (V, H, W), (d_min, d_max)
+
+
+def _sized_extract(dev, colours, launch, max_vertices, max_faces):
+    """The capacity protocol of both extractions.  launch(cap_v, cap_f, v, f, c, counts) enqueues one extraction into
+    buffers of that many rows -> the mesh dict."""
     counts = torch.empty(2, dtype=torch.int64, device=dev)
-    a = N.LrfMeshExtract()
-    a.value, a.weight, a.rgb = value.data_ptr(), None if weight is None else weight.data_ptr(), None if rgb is None else rgb.data_ptr()
-    a.Nx, a.Ny, a.Nz = Nx, Ny, Nz
-    a.origin[0], a.origin[1], a.origin[2] = origin
-    a.voxel, a.level, a.min_weight = voxel, level, min_weight
 
     def run(cap_v, cap_f):
         v = torch.empty(max(cap_v, 1), 3, dtype=torch.float32, device=dev)
         f = torch.empty(max(cap_f, 1), 3, dtype=torch.int32, device=dev)
-        c = None if rgb is None else torch.empty(max(cap_v, 1), 3, dtype=torch.uint8, device=dev)
-        N.launch("lrf_mesh_extract", dev, C.byref(a), cap_v, cap_f, v.data_ptr(), None if c is None else c.data_ptr(),
-                 f.data_ptr(), counts.data_ptr(), ws.data_ptr(), guard=True)
-        nv, nf = (int(x) for x in counts.tolist())                  # the read-back (it also orders ws's release)
+        c = torch.empty(max(cap_v, 1), 3, dtype=torch.uint8, device=dev) if colours else None
+        launch(cap_v, cap_f, v, f, c, counts)
+        nv, nf = (int(x) for x in counts.tolist())                  # the read-back (it also orders the workspace's release)
         return v, f, c, nv, nf
 
     if max_vertices is None or max_faces is None:                   # a counting call sizes the buffers: one more read-back
@@ -103,6 +130,24 @@ def _extract(value, weight, rgb, origin, voxel, dims, level, min_weight, max_ver
                        "counts": (nv, nf)}                          # the rows inside capacity, as written
         raise err
     return {"vertices": v[:nv], "faces": f[:nf], "rgb8": None if c is None else c[:nv], "counts": (nv, nf)}
+
+
+def _extract(value, weight, rgb, origin, voxel, dims, level, min_weight, max_vertices, max_faces):
+    """Checked arguments, contiguous fp32 device tensors -> the mesh dict."""
+    dev = value.device
+    Nx, Ny, Nz = dims
+    ws = N.workspace("lrf_mesh", dev, Nx, Ny, Nz)
+    a = N.LrfMeshExtract()
+    a.value, a.weight, a.rgb = value.data_ptr(), None if weight is None else weight.data_ptr(), None if rgb is None else rgb.data_ptr()
+    a.Nx, a.Ny, a.Nz = Nx, Ny, Nz
+    a.origin[0], a.origin[1], a.origin[2] = origin
+    a.voxel, a.level, a.min_weight = voxel, level, min_weight
+
+    def launch(cap_v, cap_f, v, f, c, counts):
+        N.launch("lrf_mesh_extract", dev, C.byref(a), cap_v, cap_f, v.data_ptr(), None if c is None else c.data_ptr(),
+                 f.data_ptr(), counts.data_ptr(), ws.data_ptr(), guard=True)
+
+    return _sized_extract(dev, rgb is not None, launch, max_vertices, max_faces)
 
 
 def extract_mesh(values, origin, voxel, level, weight=None, rgb=None, min_weight=1.0, max_vertices=None, max_faces=None):
@@ -168,35 +213,9 @@ class TsdfVolume:
         sdf < -trunc (the point lies behind the surface by more than trunc), else s = min(1, sdf / trunc) enters the running
         means tsdf = (tsdf weight + s) / (weight + 1) and rgb, and weight += 1.  One launch, the volume read and written
         once; no read-back.  Calls add up: frames k..V on top of frames 0..k leave the bits of one call over 0..V."""
-        V, H, W = _check_depth(depth)
-        if (rgb is not None) != (self.rgb is not None):
-            raise ValueError("rgb goes with a volume that keeps colours: pass rgb to a TsdfVolume(colours=True) and only to it")
-        if rgb is not None:
-            if not torch.is_tensor(rgb):
-                raise TypeError("rgb must be a torch tensor or None")
-            if not (rgb.is_floating_point() or rgb.dtype is torch.uint8):
-                raise ValueError(f"rgb must hold floating-point or uint8 values, got {rgb.dtype}")
-            if tuple(rgb.shape) != (V, H, W, 3):
-                raise ValueError(f"rgb must be {(V, H, W, 3)} to go with depth {tuple(depth.shape)}, got {tuple(rgb.shape)}")
-            if rgb.device != depth.device:
-                raise ValueError("rgb and depth must live on the same device")
-        poses = _check_poses(poses, V)
-        focal, center = _check_intrinsics(focal, center, False)
-        d_min, d_max = _check_range(depth_range)
-        N.require_gpu(depth, "depth", "the TSDF integration")
         dev = self.tsdf.device
-        if depth.device != dev:
-            raise ValueError(f"depth lives on {depth.device}, the volume on {dev}")
-        rgb8 = None
-        if rgb is not None:
-            if rgb.dtype is torch.uint8:
-                rgb8 = rgb.contiguous()
-            else:
-                from .novel_views import encode_frames
-                rgb8 = encode_frames(rgb.detach(), depth.detach())[0]
-        depth = N.conform(depth)
-        poses = poses.detach().to(device=dev, dtype=torch.float32).contiguous()
-        f, c = _dev_f32(focal, 1, dev), _dev_f32(center, 2, dev)
+        depth, rgb8, poses, f, c, (V, H, W), (d_min, d_max) = _check_frames(self.rgb is not None, dev, depth, poses, focal, center,
+                                                                            rgb, depth_range)
         a = N.LrfTsdfVolume()
         a.tsdf, a.weight, a.rgb = self.tsdf.data_ptr(), self.weight.data_ptr(), None if self.rgb is None else self.rgb.data_ptr()
         a.Nx, a.Ny, a.Nz = self.dims
@@ -214,6 +233,186 @@ class TsdfVolume:
                         max_faces)
 
 
+BLOCK = 8                                      # lattice points per block edge
+BLOCK_POINTS = BLOCK ** 3
+MAX_BLOCKS = (1 << 22) - 1                     # 512 n < 2^31
+
+
+def _check_blocks(blocks):
+    if len(blocks) != 3 or any(int(b) != b or int(b) < 1 for b in blocks):
+        raise ValueError(f"blocks must be (Bx, By, Bz) integers >= 1, got {blocks!r}")
+    blocks = tuple(int(b) for b in blocks)
+    if any(BLOCK * b > _INT32 for b in blocks):
+        raise ValueError(f"blocks {blocks}: an axis takes 8 B < 2^31 lattice points")
+    if blocks[0] * blocks[1] * blocks[2] > _INT32:
+        raise ValueError(f"blocks {blocks} make {blocks[0] * blocks[1] * blocks[2]} table entries; a grid takes Bx By Bz < 2^31")
+    return blocks
+
+
+class SparseTsdfVolume:
+    """A TsdfVolume of dims 8 * blocks of which only the 8 x 8 x 8 blocks that some depth pixel's truncation band reaches are
+    stored (csrc/lrf_tsdf_blocks.inl).  blocks = (Bx, By, Bz).  marks uint8 and table int32 [Bz,By,Bx] (-1, or the block's
+    pool index), coords int32 [n,3] ((bx, by, bz) in pool order) and the pools tsdf, weight [n,8,8,8] and, with colours, rgb
+    [n,8,8,8,3], x fastest.  touch() marks, allocate() gives the marked blocks their pool indices -- in (z, y, x) order after
+    the blocks that exist, which keep index and contents --, integrate() updates the stored blocks only and leaves in each of
+    their points the bits TsdfVolume.integrate leaves in the same lattice point, extract() meshes them.  A point in no block
+    reads as (tsdf 1, weight 0): a missing block can leave a hole, never create or move a face.  No hash, no atomics: the
+    same call sequence gives the same bytes."""
+
+    def __init__(self, origin, voxel, blocks, trunc, device, colours=True):
+        self.blocks = _check_blocks(blocks)
+        self.dims = tuple(BLOCK * b for b in self.blocks)
+        self.origin, self.voxel, _ = _check_lattice(origin, voxel, (1, 1, 1))
+        self.trunc = float(trunc)
+        if not (self.trunc > 0 and math.isfinite(self.trunc)):
+            raise ValueError(f"trunc must be a finite number > 0, got {trunc}")
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise NativeError(f"localrf_amd.mesh: a SparseTsdfVolume on {dev}; the integration can run only on an AMD GPU (HIP "
+                              "kernels). There is no CPU fallback.")
+        Bx, By, Bz = self.blocks
+        self.colours = bool(colours)
+        self.marks = torch.zeros(Bz, By, Bx, dtype=torch.uint8, device=dev)
+        self.table = torch.full((Bz, By, Bx), -1, dtype=torch.int32, device=dev)
+        self.n_blocks = 0
+        self._coords = torch.zeros(1, 3, dtype=torch.int32, device=dev)
+        self._tsdf = torch.ones(0, BLOCK, BLOCK, BLOCK, dtype=torch.float32, device=dev)
+        self._weight = torch.zeros(0, BLOCK, BLOCK, BLOCK, dtype=torch.float32, device=dev)
+        self._rgb = torch.zeros(0, BLOCK, BLOCK, BLOCK, 3, dtype=torch.float32, device=dev) if self.colours else None
+
+    coords = property(lambda self: self._coords[:self.n_blocks])
+    tsdf = property(lambda self: self._tsdf[:self.n_blocks])
+    weight = property(lambda self: self._weight[:self.n_blocks])
+    rgb = property(lambda self: None if self._rgb is None else self._rgb[:self.n_blocks])
+
+    @staticmethod
+    def bytes_for(blocks, n_blocks, colours=True):
+        """marks and table of the grid, and coords and pools of n_blocks blocks."""
+        per_block = 12 + BLOCK_POINTS * (BYTES_PER_VOXEL + (BYTES_PER_VOXEL_RGB if colours else 0))
+        return int(blocks[0]) * int(blocks[1]) * int(blocks[2]) * 5 + int(n_blocks) * per_block
+
+    @property
+    def nbytes(self):
+        return self.bytes_for(self.blocks, self.n_blocks, self.colours)
+
+    def _args(self):
+        a = N.LrfTsdfBlocks()
+        a.marks, a.table, a.coords = self.marks.data_ptr(), self.table.data_ptr(), self._coords.data_ptr()
+        a.tsdf, a.weight = self._tsdf.data_ptr() or None, self._weight.data_ptr() or None      # an empty pool has no address
+        a.rgb = None if self._rgb is None else self._rgb.data_ptr() or None
+        a.Bx, a.By, a.Bz = self.blocks
+        a.n_blocks = self.n_blocks
+        a.origin[0], a.origin[1], a.origin[2] = self.origin
+        a.voxel, a.trunc = self.voxel, self.trunc
+        return a
+
+    def touch(self, depth, poses, focal, center, depth_range=(0.0, math.inf)):
+        """Mark the blocks that the truncation bands of V frames reach; arguments as integrate takes them, without rgb.  Per
+        pixel with a depth d that is finite, positive and inside depth_range: the world points a, b at depths max(d - trunc, 0)
+        and d + trunc, the margin m = voxel + (d + trunc) / focal (half a pixel footprint and one voxel of slack), and every
+        block that meets the box [min(a, b) - m, max(a, b) + m].  One launch, no read-back; marks add up over calls."""
+        dev = self.table.device
+        depth, _, poses, f, c, (V, H, W), (d_min, d_max) = _check_frames(False, dev, depth, poses, focal, center, None, depth_range)
+        N.launch("lrf_tsdf_blocks_touch", dev, C.byref(self._args()), depth.data_ptr(), poses.data_ptr(), f.data_ptr(),
+                 c.data_ptr(), V, H, W, d_min, d_max, guard=True)
+        return self
+
+    def allocate(self, max_bytes=None):
+        """Give every marked block that has none a pool index -- the next ones, in block-linear (z, y, x) order -- and grow
+        coords and the pools (new blocks: tsdf 1, weight 0, rgb 0).  A counting call (two launches), one read-back -- the
+        number of new blocks, which is returned --, then, with new blocks only, the grown tensors and the assigning call (three
+        launches).  A volume that would exceed max_bytes (nbytes with the new blocks) or 2^22 - 1 blocks raises ValueError
+        and stays as it was."""
+        dev = self.table.device
+        limit = MAX_BLOCKS
+        if max_bytes is not None:
+            limit = min(limit, max(-1, (int(max_bytes) - self.bytes_for(self.blocks, 0, self.colours))
+                                   // self.bytes_for((0, 0, 0), 1, self.colours)))
+        if limit < self.n_blocks:
+            raise ValueError(f"a volume of {self.n_blocks} blocks takes {self.nbytes} bytes; max_bytes is {int(max_bytes)}")
+        ws = N.workspace("lrf_tsdf_blocks_assign", dev, *self.blocks)
+        count = torch.empty(1, dtype=torch.int64, device=dev)
+
+        def assign(max_blocks):
+            N.launch("lrf_tsdf_blocks_assign", dev, C.byref(self._args()), max_blocks, self._coords.shape[0], count.data_ptr(),
+                     ws.data_ptr(), guard=True)
+        assign(self.n_blocks)                                       # a counting call: the table stays as it is
+        new = int(count.item())                                     # the read-back (it also orders ws's release)
+        n = self.n_blocks + new
+        if n > MAX_BLOCKS:
+            raise ValueError(f"the frames reach {n} blocks; a volume takes 512 n < 2^31 lattice points")
+        if n > limit:
+            raise ValueError(f"a volume of {n} blocks takes {self.bytes_for(self.blocks, n, self.colours)} bytes; max_bytes is "
+                             f"{int(max_bytes)}")
+        if new == 0:
+            return 0
+
+        def grown(old, fill):
+            out = torch.full((n,) + tuple(old.shape[1:]), fill, dtype=old.dtype, device=dev)
+            out[:self.n_blocks] = old[:self.n_blocks]
+            return out
+        # every allocation comes before the table changes: one that fails leaves the volume as it was
+        coords = torch.zeros(n, 3, dtype=torch.int32, device=dev)
+        tsdf, weight = grown(self._tsdf, 1.0), grown(self._weight, 0.0)
+        rgb = None if self._rgb is None else grown(self._rgb, 0.0)
+        old, self._coords = self._coords, coords                    # the pass below rewrites every row, the old ones too
+        try:
+            assign(n)
+        except BaseException:
+            self._coords = old
+            raise
+        self._tsdf, self._weight, self._rgb, self.n_blocks = tsdf, weight, rgb, n
+        return new
+
+    def integrate(self, depth, poses, focal, center, rgb=None, depth_range=(0.0, math.inf)):
+        """TsdfVolume.integrate over the stored blocks: same arguments, same checks, same arithmetic per lattice point.  One
+        launch of one workgroup per block, the pools read and written once; no read-back.  Blocks that are not stored see
+        nothing: touch and allocate first.  With zero blocks nothing is launched."""
+        dev = self.table.device
+        depth, rgb8, poses, f, c, (V, H, W), (d_min, d_max) = _check_frames(self.colours, dev, depth, poses, focal, center, rgb,
+                                                                            depth_range, "SparseTsdfVolume")
+        if self.n_blocks:
+            N.launch("lrf_tsdf_blocks_integrate", dev, C.byref(self._args()), depth.data_ptr(),
+                     None if rgb8 is None else rgb8.data_ptr(), poses.data_ptr(), f.data_ptr(), c.data_ptr(), V, H, W, d_min, d_max,
+                     guard=True)
+        return self
+
+    def extract(self, level=0.0, min_weight=1.0, max_vertices=None, max_faces=None):
+        """The mesh of the surface tsdf = level over the cells every corner of which is stored and was seen by at least
+        min_weight frames.  Vertices come in pool order, then (z, y, x, edge) inside the block; faces in the pool order of
+        the cell's lowest corner, then (z, y, x) inside the block, then (tetrahedron, triangle).  Capacities and read-backs as
+        extract_mesh has them.  With zero blocks nothing is launched and the mesh is empty."""
+        level, min_weight = _check_extract(level, min_weight, max_vertices, max_faces)
+        dev = self.table.device
+        if not self.n_blocks:
+            return {"vertices": torch.empty(0, 3, dtype=torch.float32, device=dev), "faces": torch.empty(0, 3, dtype=torch.int32, device=dev),
+                    "rgb8": torch.empty(0, 3, dtype=torch.uint8, device=dev) if self.colours else None, "counts": (0, 0)}
+        ws = N.workspace("lrf_mesh_extract_blocks", dev, self.n_blocks)
+        a = self._args()
+
+        def launch(cap_v, cap_f, v, f, c, counts):
+            N.launch("lrf_mesh_extract_blocks", dev, C.byref(a), level, min_weight, cap_v, cap_f, v.data_ptr(),
+                     None if c is None else c.data_ptr(), f.data_ptr(), counts.data_ptr(), ws.data_ptr(), guard=True)
+
+        return _sized_extract(dev, self.colours, launch, max_vertices, max_faces)
+
+    def to_dense(self):
+        """(tsdf, weight, rgb or None, stored) as [8Bz,8By,8Bx] tensors of the virtual lattice (rgb [...,3]; stored: bool, the
+        points of stored blocks); a point in no block holds (1, 0, 0).  For tests and debugging of small volumes."""
+        Bx, By, Bz = self.blocks
+        dev = self.table.device
+        bx, by, bz = (self.coords[:, k].long() for k in range(3))
+
+        def scatter(pool, fill, tail=()):
+            out = torch.full((Bz, By, Bx, BLOCK, BLOCK, BLOCK) + tail, fill, dtype=pool.dtype, device=dev)
+            out[bz, by, bx] = pool
+            order = (0, 3, 1, 4, 2, 5) + tuple(range(6, 6 + len(tail)))
+            return out.permute(*order).reshape((BLOCK * Bz, BLOCK * By, BLOCK * Bx) + tail)
+        stored = scatter(torch.ones(self.n_blocks, BLOCK, BLOCK, BLOCK, dtype=torch.bool, device=dev), False)
+        return (scatter(self.tsdf, 1.0), scatter(self.weight, 0.0), None if self._rgb is None else scatter(self.rgb, 0.0, (3,)),
+                stored)
+
+
 _MESH_KEYS = ("depth_range", "level", "min_weight", "max_vertices", "max_faces", "colours", "frames_per_call")
 
 
@@ -226,7 +425,7 @@ def _lattice_of_box(lo, hi, voxel):
 
 
 def scene_mesh(local_tensorfs, W, H, voxel, bounds=None, poses=None, trunc=None, max_bytes=4 << 30, depth="expected",
-               max_spread=None, **options):
+               max_spread=None, sparse=False, **options):
     """A scene's surface as a triangle mesh: its frames rendered by novel_views.render_poses frames_per_call (default 8) at
     a time, each batch integrated into one TsdfVolume and dropped -- only the volume stays resident, not the frames -- then
     TsdfVolume.extract.  poses=None renders the scene's own get_cam2world(), each frame through itself; otherwise poses
@@ -241,7 +440,13 @@ def scene_mesh(local_tensorfs, W, H, voxel, bounds=None, poses=None, trunc=None,
     batch) instead of render_poses' expected depth, which carves a phantom sheet between two surfaces a ray sees; the colours
     stay render_poses'.  max_spread (with "median" only) also drops the pixels whose interquartile depth range (d75 - d25)
     exceeds max_spread times their median, or that miss one of the three quartiles.  Any other depth= raises ValueError.
-    Pinhole scenes only.  Returns the mesh dict of the module docstring with "volume": the TsdfVolume."""
+    sparse=True fuses into a SparseTsdfVolume instead: the lattice of the box is rounded up to whole 8 x 8 x 8 blocks, one
+    render pass touches the blocks the depths reach and allocates them, a second pass integrates every frame into every stored
+    block (so that a stored point holds the bits of the dense volume), and bounds=None keeps its box pass in front of those
+    two.  The 2^31-point limit of the dense lattice does not apply; max_bytes is checked against marks and table before anything
+    is rendered (with bounds given) and against those plus the pools once the block count is known, before the pools are
+    allocated.  The faces are those of the dense mesh whose cells lie in stored blocks, in SparseTsdfVolume.extract's order.
+    Pinhole scenes only.  Returns the mesh dict of the module docstring with "volume": the TsdfVolume or SparseTsdfVolume."""
     lt = local_tensorfs
     frames = SceneFrames("scene_mesh", lt, W, H, poses, depth, max_spread, options, _MESH_KEYS, False)
     W, H, n, options, render = frames.W, frames.H, frames.n, frames.own, frames.render
@@ -265,7 +470,14 @@ def scene_mesh(local_tensorfs, W, H, voxel, bounds=None, poses=None, trunc=None,
     if per_call * H * W > _INT32:
         raise ValueError(f"scene_mesh: {per_call} frames of {H} x {W} per call; one integration takes V H W < 2^31")
 
-    def volume_for(lo, dims):
+    def volume_for(lo, dims):                                       # -> origin and dims, or (sparse) blocks
+        if sparse:
+            blocks = _check_blocks(tuple(-(-d // BLOCK) for d in dims))
+            need = SparseTsdfVolume.bytes_for(blocks, 0, colours)
+            if need > int(max_bytes):
+                raise ValueError(f"scene_mesh: the table of {blocks[0]} x {blocks[1]} x {blocks[2]} blocks takes {need} bytes; "
+                                 f"max_bytes is {int(max_bytes)}")
+            return lo, blocks
         _check_lattice(lo, voxel, dims)
         need = TsdfVolume.nbytes(dims, colours)
         if need > int(max_bytes):
@@ -276,7 +488,7 @@ def scene_mesh(local_tensorfs, W, H, voxel, bounds=None, poses=None, trunc=None,
     if bounds is not None:
         if len(bounds) != 2:
             raise ValueError(f"bounds must be ((x0, y0, z0), (x1, y1, z1)), got {bounds!r}")
-        lo, dims = volume_for(*_lattice_of_box(bounds[0], bounds[1], voxel))
+        lo, shape = volume_for(*_lattice_of_box(bounds[0], bounds[1], voxel))
     poses = frames.cam2world()
     fi = render.pop("frame_indices", None)
     if fi is None:
@@ -305,8 +517,14 @@ def scene_mesh(local_tensorfs, W, H, voxel, bounds=None, poses=None, trunc=None,
         if box is None:
             raise ValueError("scene_mesh: no rendered depth lies inside depth_range; there is no box to cover")
         box = box.double().cpu().numpy()                            # the box's read-back
-        lo, dims = volume_for(*_lattice_of_box(box[0] - trunc, -box[1] + trunc, voxel))
-    vol = TsdfVolume(lo, voxel, dims, trunc, lt.blending_weights.device, colours=colours)
+        lo, shape = volume_for(*_lattice_of_box(box[0] - trunc, -box[1] + trunc, voxel))
+    if sparse:
+        vol = SparseTsdfVolume(lo, voxel, shape, trunc, lt.blending_weights.device, colours=colours)
+        for p, dmap, _ in batches():
+            vol.touch(dmap, p, focal, center, depth_range=depth_range)
+        vol.allocate(max_bytes=max_bytes)
+    else:
+        vol = TsdfVolume(lo, voxel, shape, trunc, lt.blending_weights.device, colours=colours)
     for p, dmap, rgb8 in batches():
         vol.integrate(dmap, p, focal, center, rgb=rgb8, depth_range=depth_range)
     mesh = vol.extract(level, min_weight, options.get("max_vertices"), options.get("max_faces"))
