@@ -710,6 +710,47 @@ int lrf_mesh_extract_blocks(const LrfTsdfBlocks* g, float level, float min_weigh
                             float* vertices, uint8_t* rgb8_out /* nullable */, int32_t* faces, int64_t* counts /* device [2] */,
                             void* workspace, void* stream);
 
+/* The connected components of an indexed triangle mesh, and the mesh without its small components (csrc/lrf_mesh_clean.inl
+ * states the algorithm).  Integers only: positions and colours are copied bit for bit, and every call leaves the same bytes on
+ * every run.  A mesh is vertices [Nv,3] fp32, rgb8 [Nv,3] uint8 (nullable), faces [Nf,3] int32 (null allowed when Nf = 0).  Two
+ * vertices are connected when a face holds both; the label of a vertex is the smallest vertex index of its component; a vertex
+ * that no face holds is a component of its own with 0 faces.
+ * lrf_mesh_components_init: parent[v] = v.  One launch.
+ * lrf_mesh_components_round: one round of min-label hooking on parent (int32 [Nv], from _init or an earlier round): changed
+ * (device int32 [1]) = 0; per face with roots ra, rb, rc = parent[a], parent[b], parent[c] and m their minimum, an int32
+ * atomicMin(&parent[r], m) for each r > m, and bit 0 of changed when one lowered its target; then every vertex walks its
+ * strictly decreasing parents (at most Nv steps) and stores the root it reaches.  A face with an index outside [0, Nv) -- or,
+ * from a foreign parent array, a parent outside it -- is never dereferenced: it is skipped and sets bit 1 of changed.  The
+ * caller reads changed back; the first round that leaves bit 0 clear found every face inside one tree: parent then holds the
+ * labels.  No compare-and-swap loop, no waiting on another lane, wave or workgroup.  Three launches (two with Nf = 0: no face
+ * kernel).
+ * lrf_mesh_components_count: faces_of[l] = the faces whose first vertex has label l (faces with an index out of range are
+ * skipped), vertices_of[l] = the vertices with label l, both int32 [Nv] and 0 where l is no label; summary (device int64 [3]) =
+ * the number of components, the number of components with at least one face, the face count of the largest component.  Integer
+ * atomics.  Four launches (three with Nf = 0).
+ * lrf_mesh_filter: keeps the components with faces_of[label] >= threshold.  vertices_out [Nv,3], rgb8_out [Nv,3] (nullable, with
+ * rgb8) and faces_out [Nf,3] (null allowed when Nf = 0) must hold the input's rows; the kept vertices and faces are written in
+ * the input's order from row 0, a kept vertex's new index is the number of kept vertices before it, and kept faces are
+ * rewritten through that map.  counts (device int64 [3]) receives the kept vertices, kept faces and kept components.  labels
+ * and faces_of must come from the calls above (a label outside [0, Nv) drops its vertex; a face with an index outside [0, Nv) is
+ * dropped without being dereferenced).  Three launches, no atomics, no host synchronisation.  workspace:
+ * lrf_mesh_filter_workspace_bytes(Nv, Nf) bytes (0 for a refused shape), 8-byte aligned.
+ * Refused before any launch: null or misaligned pointers (int32 and float arrays 4 bytes; summary, counts and workspace 8),
+ * Nv < 1, Nf < 0, Nv or Nf >= 2^31, a negative threshold, rgb8 without rgb8_out or the reverse. */
+typedef struct LrfMeshFilter {
+  const float* vertices; const uint8_t* rgb8 /* nullable */; const int32_t* faces;
+  const int32_t* labels; const int32_t* faces_of;
+  int64_t Nv, Nf;
+} LrfMeshFilter;
+int lrf_mesh_components_init(int32_t* parent, int64_t Nv, void* stream);
+int lrf_mesh_components_round(int32_t* parent, const int32_t* faces, int64_t Nv, int64_t Nf, int32_t* changed /* device [1] */,
+                              void* stream);
+int lrf_mesh_components_count(const int32_t* labels, const int32_t* faces, int64_t Nv, int64_t Nf, int32_t* faces_of,
+                              int32_t* vertices_of, int64_t* summary /* device [3] */, void* stream);
+size_t lrf_mesh_filter_workspace_bytes(int64_t Nv, int64_t Nf);
+int lrf_mesh_filter(const LrfMeshFilter* m, int32_t threshold, float* vertices_out, uint8_t* rgb8_out /* nullable */,
+                    int32_t* faces_out, int64_t* counts /* device [3] */, void* workspace, void* stream);
+
 /* Depth quantiles of a ray: the distance at which its accumulated weight first reaches q; q = 0.5 is the median depth, which
  * always lies on a surface the ray met (csrc/lrf_quantile.inl states the arithmetic: fp32 without contraction, one fixed
  * summation order per ray).  With C_i the inclusive prefix sum of the weights lrf_render_fwd leaves in weight_out and i* the

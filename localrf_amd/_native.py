@@ -138,6 +138,11 @@ class LrfMeshExtract(C.Structure):
                 ("origin", C.c_float * 3), ("voxel", C.c_float), ("level", C.c_float), ("min_weight", C.c_float)]
 
 
+class LrfMeshFilter(C.Structure):
+    _fields_ = [("vertices", _f), ("rgb8", C.c_void_p), ("faces", C.c_void_p), ("labels", C.c_void_p), ("faces_of", C.c_void_p),
+                ("Nv", C.c_int64), ("Nf", C.c_int64)]
+
+
 class LrfTsdfBlocks(C.Structure):
     _fields_ = [("marks", C.c_void_p), ("table", C.c_void_p), ("coords", C.c_void_p), ("tsdf", _f), ("weight", _f), ("rgb", _f),
                 ("Bx", C.c_int32), ("By", C.c_int32), ("Bz", C.c_int32), ("n_blocks", C.c_int32),
@@ -254,6 +259,13 @@ SYMBOLS = {
     "lrf_mesh_extract_blocks_workspace_bytes": (C.c_size_t, [C.c_int32]),
     "lrf_mesh_extract_blocks": (C.c_int, [C.POINTER(LrfTsdfBlocks), C.c_float, C.c_float, C.c_int64, C.c_int64, _f, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "lrf_mesh_components_init": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p]),
+    "lrf_mesh_components_round": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    "lrf_mesh_components_count": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p]),
+    "lrf_mesh_filter_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
+    "lrf_mesh_filter": (C.c_int, [C.POINTER(LrfMeshFilter), C.c_int32, _f, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_void_p]),
     "lrf_density_gradient": (C.c_int, [C.POINTER(LrfField), _f, C.c_int64, _f, _f, C.c_void_p]),
     "lrf_normals_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "lrf_render_normals": (C.c_int, [C.POINTER(LrfField), _f, _f, C.c_int32, C.c_int32, C.c_uint32, C.c_float, _f, C.c_int32,

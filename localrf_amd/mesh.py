@@ -5,6 +5,8 @@ lrf_tsdf_integrate and lrf_mesh_extract; csrc/lrf_tsdf_blocks.inl through lrf_ts
   SparseTsdfVolume(origin, voxel, blocks, trunc, device)  the same lattice stored in 8 x 8 x 8 blocks where depth reaches:
                                                    .touch(frames), .allocate(), .integrate(frames), .extract(), .to_dense()
   extract_mesh(values, origin, voxel, level, ...)  marching tetrahedra of any [Nz,Ny,Nx] device tensor
+  components(faces, n_vertices)                    connected-component labels and sizes of an indexed mesh (csrc/lrf_mesh_clean.inl)
+  filter_components(mesh, min_faces, min_fraction) the mesh without its small components, order and bytes preserved
   scene_mesh(local_tensorfs, W, H, voxel=...)      novel_views.render_poses in batches, each integrated and dropped, then extract
   pointcloud.write_ply(path, vertices, rgb8, faces=faces) writes the result
 
@@ -182,6 +184,169 @@ def extract_mesh(values, origin, voxel, level, weight=None, rgb=None, min_weight
                     origin, voxel, dims, level, min_weight, max_vertices, max_faces)
 
 
+_NO_FILTER = {"min_component_faces": 0, "min_component_fraction": 0.0}
+
+
+def _check_rounds(max_rounds):
+    if isinstance(max_rounds, bool) or int(max_rounds) != max_rounds or int(max_rounds) < 1:
+        raise ValueError(f"max_rounds must be an integer >= 1, got {max_rounds!r}")
+    return int(max_rounds)
+
+
+def _check_keep(min_faces, min_fraction, what=("min_faces", "min_fraction")):
+    try:
+        ok = not isinstance(min_faces, bool) and int(min_faces) == min_faces and int(min_faces) >= 0
+    except (TypeError, ValueError, OverflowError):
+        ok = False
+    if not ok:
+        raise ValueError(f"{what[0]} must be an integer >= 0, got {min_faces!r}")
+    try:
+        fraction = float(min_fraction)
+    except (TypeError, ValueError):
+        fraction = math.nan
+    if not 0.0 <= fraction <= 1.0:                                  # NaN fails
+        raise ValueError(f"{what[1]} must lie in [0, 1], got {min_fraction!r}")
+    return int(min_faces), fraction
+
+
+def _check_faces(faces, n_vertices):
+    """type, then dtype and shape -> (Nv, Nf); the device check is the caller's, after its other arguments."""
+    if not torch.is_tensor(faces):
+        raise TypeError("faces must be a torch tensor")
+    if faces.dtype is not torch.int32 or faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError(f"faces must be [Nf, 3] int32, got {faces.dtype} {tuple(faces.shape)}")
+    if isinstance(n_vertices, bool) or int(n_vertices) != n_vertices or not 0 <= int(n_vertices) <= _INT32:
+        raise ValueError(f"n_vertices must be an integer in [0, 2^31), got {n_vertices!r}")
+    if faces.shape[0] > _INT32:
+        raise ValueError(f"faces holds {faces.shape[0]} rows; a mesh takes Nf < 2^31")
+    if int(n_vertices) == 0 and faces.shape[0]:
+        raise ValueError(f"faces holds {faces.shape[0]} rows for a mesh without vertices")
+    return int(n_vertices), int(faces.shape[0])
+
+
+def _components(faces, Nv, Nf, max_rounds):
+    """Checked arguments, faces a contiguous int32 device tensor -> the dict of components()."""
+    dev = faces.device
+    labels = torch.empty(Nv, dtype=torch.int32, device=dev)
+    faces_of = torch.empty(Nv, dtype=torch.int32, device=dev)
+    vertices_of = torch.empty(Nv, dtype=torch.int32, device=dev)
+    if Nv == 0:
+        return {"labels": labels, "faces_of": faces_of, "vertices_of": vertices_of, "n_components": 0, "n_with_faces": 0,
+                "largest_faces": 0, "rounds": 0}
+    fp = faces.data_ptr() if Nf else None
+    changed = torch.empty(1, dtype=torch.int32, device=dev)
+    N.launch("lrf_mesh_components_init", dev, labels.data_ptr(), Nv, guard=True)
+    rounds = 0
+    while True:
+        N.launch("lrf_mesh_components_round", dev, labels.data_ptr(), fp, Nv, Nf, changed.data_ptr(), guard=True)
+        rounds += 1
+        word = int(changed.item())                                  # the round's read-back: 4 bytes
+        if word & 2:
+            raise ValueError(f"faces holds an index outside [0, {Nv}): the mesh has {Nv} vertices")
+        if not word & 1:
+            break
+        if rounds >= max_rounds:
+            raise RuntimeError(f"components: the labels still changed in round {rounds}; max_rounds is {max_rounds}")
+    summary = torch.empty(3, dtype=torch.int64, device=dev)
+    N.launch("lrf_mesh_components_count", dev, labels.data_ptr(), fp, Nv, Nf, faces_of.data_ptr(), vertices_of.data_ptr(),
+             summary.data_ptr(), guard=True)
+    n_components, n_with_faces, largest = (int(x) for x in summary.tolist())     # the summary's read-back
+    return {"labels": labels, "faces_of": faces_of, "vertices_of": vertices_of, "n_components": n_components,
+            "n_with_faces": n_with_faces, "largest_faces": largest, "rounds": rounds}
+
+
+def components(faces, n_vertices, max_rounds=64):
+    """The connected components of the mesh whose faces [Nf,3] int32 (device) index n_vertices vertices.  Two vertices are
+    connected when a face holds both; a vertex that no face holds is a component of its own with 0 faces.  Returns a dict:
+    labels [Nv] int32 (the smallest vertex index of each vertex's component), faces_of and vertices_of [Nv] int32 (the
+    component's face and vertex counts at its label, 0 elsewhere), all on the device, and the Python ints n_components,
+    n_with_faces (components with at least one face), largest_faces (the face count of the largest) and rounds.
+    Min-label hooking with atomicMin and a bounded walk (csrc/lrf_mesh_clean.inl): the host launches one round after the
+    other and reads 4 bytes back after each; the first round whose hooking pass changes nothing ends the loop, and rounds
+    counts it.  max_rounds guards against a loop that never ends -- it is not tuned -- and raises RuntimeError naming the
+    count when it is reached.  A face index outside [0, n_vertices) is never dereferenced and raises ValueError.  One more
+    read-back brings the three summary words.  The labels are a unique fixed point: the same bytes on every run."""
+    Nv, Nf = _check_faces(faces, n_vertices)
+    max_rounds = _check_rounds(max_rounds)
+    N.require_gpu(faces, "faces", "the component labelling")
+    return _components(faces.detach().contiguous(), Nv, Nf, max_rounds)
+
+
+def _check_mesh(mesh):
+    """type, then dtype and shape, then device -> (vertices, faces, rgb8 or None, Nv, Nf), contiguous."""
+    if not isinstance(mesh, dict) or "vertices" not in mesh or "faces" not in mesh:
+        raise TypeError("mesh must be a dict with vertices and faces, as extract_mesh returns it")
+    v, f, c = mesh["vertices"], mesh["faces"], mesh.get("rgb8")
+    for name, t in (("vertices", v), ("faces", f)) + ((("rgb8", c),) if c is not None else ()):
+        if not torch.is_tensor(t):
+            raise TypeError(f"{name} must be a torch tensor" + (" or None" if name == "rgb8" else ""))
+    if v.dtype is not torch.float32 or v.dim() != 2 or v.shape[1] != 3:
+        raise ValueError(f"vertices must be [Nv, 3] float32, got {v.dtype} {tuple(v.shape)}")
+    Nv, Nf = _check_faces(f, int(v.shape[0]))
+    if c is not None and (c.dtype is not torch.uint8 or tuple(c.shape) != (Nv, 3)):
+        raise ValueError(f"rgb8 must be {(Nv, 3)} uint8 or None, got {c.dtype} {tuple(c.shape)}")
+    return v, f, c, Nv, Nf
+
+
+def filter_components(mesh, min_faces=0, min_fraction=0.0, max_rounds=64):
+    """The mesh (the dict of the module docstring) without its small connected components: a component is kept when it holds
+    at least threshold = max(min_faces, ceil(min_fraction * largest_faces)) faces, largest_faces being the face count of the
+    largest component.  min_fraction=1.0 keeps the largest component and every tie with it; min_faces=1 drops exactly the
+    vertices that no face holds; with both 0 the result holds the input's bytes.  Kept vertices and faces keep their order,
+    a kept vertex's new index is the number of kept vertices before it, rgb8 follows the vertices, and positions and colours
+    are copied bit for bit: the output bytes are a fixed function of the input.  components() runs first (its read-backs);
+    the threshold is computed on the host from its summary; the output buffers are allocated at the input's sizes and
+    sliced once the filter's three counts come back: one more read-back.  An empty result is a mesh with shapes [0,3] and
+    counts (0, 0).  Returns a new mesh dict -- every other entry of the input is carried over -- with "components": the
+    Python ints of components() (n_components, n_with_faces, largest_faces, rounds), "threshold" and "kept", the number of
+    kept components."""
+    v, f, c, Nv, Nf = _check_mesh(mesh)
+    min_faces, min_fraction = _check_keep(min_faces, min_fraction)
+    max_rounds = _check_rounds(max_rounds)
+    N.require_gpu(v, "vertices", "the component filter")
+    N.require_gpu(f, "faces", "the component filter")
+    if c is not None:
+        N.require_gpu(c, "rgb8", "the component filter")
+    dev = v.device
+    if f.device != dev or (c is not None and c.device != dev):
+        raise ValueError("vertices, faces and rgb8 must live on the same device")
+    v, f = v.detach().contiguous(), f.detach().contiguous()
+    c = None if c is None else c.contiguous()
+    comp = _components(f, Nv, Nf, max_rounds)
+    threshold = max(min_faces, int(math.ceil(min_fraction * comp["largest_faces"])))
+    out = dict(mesh)
+    info = {k: comp[k] for k in ("n_components", "n_with_faces", "largest_faces", "rounds")}
+    info["threshold"] = threshold
+    if Nv == 0:
+        info["kept"] = 0
+        out.update(vertices=v, faces=f, rgb8=c, counts=(0, 0), components=info)
+        return out
+    if threshold > _INT32:                                          # no component holds 2^31 faces
+        threshold = _INT32
+    vo, fo = torch.empty_like(v), torch.empty_like(f)
+    co = None if c is None else torch.empty_like(c)
+    counts = torch.empty(3, dtype=torch.int64, device=dev)
+    ws = N.workspace("lrf_mesh_filter", dev, Nv, Nf)
+    a = N.LrfMeshFilter()
+    a.vertices, a.rgb8, a.faces = v.data_ptr(), None if c is None else c.data_ptr(), f.data_ptr() if Nf else None
+    a.labels, a.faces_of = comp["labels"].data_ptr(), comp["faces_of"].data_ptr()
+    a.Nv, a.Nf = Nv, Nf
+    N.launch("lrf_mesh_filter", dev, C.byref(a), threshold, vo.data_ptr(), None if co is None else co.data_ptr(),
+             fo.data_ptr() if Nf else None, counts.data_ptr(), ws.data_ptr(), guard=True)
+    nv, nf, kept = (int(x) for x in counts.tolist())                # the read-back (it also orders the workspace's release)
+    info["kept"] = kept
+    out.update(vertices=vo[:nv], faces=fo[:nf], rgb8=None if co is None else co[:nv], counts=(nv, nf), components=info)
+    return out
+
+
+def _filtered(mesh, min_component_faces, min_component_fraction):
+    """extract's tail: the mesh itself with both options at their defaults -- nothing new is launched --, else
+    filter_components of it."""
+    if min_component_faces == 0 and min_component_fraction == 0.0:
+        return mesh
+    return filter_components(mesh, min_component_faces, min_component_fraction)
+
+
 class TsdfVolume:
     """A truncated signed-distance volume on the device: tsdf [Nz,Ny,Nx] (starts at 1), weight [Nz,Ny,Nx] (starts at 0: the
     number of frames that saw the point) and, with colours, rgb [Nz,Ny,Nx,3] in [0, 1] (starts at 0).  dims = (Nx, Ny, Nz);
@@ -225,12 +390,16 @@ class TsdfVolume:
                  poses.data_ptr(), f.data_ptr(), c.data_ptr(), V, H, W, d_min, d_max, guard=True)
         return self
 
-    def extract(self, level=0.0, min_weight=1.0, max_vertices=None, max_faces=None):
+    def extract(self, level=0.0, min_weight=1.0, max_vertices=None, max_faces=None, *, min_component_faces=0,
+                min_component_fraction=0.0):
         """The mesh of the surface tsdf = level over the cells every corner of which at least min_weight frames saw:
-        extract_mesh(self.tsdf, ..., weight=self.weight, rgb=self.rgb); see there for the capacities and the read-backs."""
+        extract_mesh(self.tsdf, ..., weight=self.weight, rgb=self.rgb); see there for the capacities and the read-backs.
+        With min_component_faces or min_component_fraction above 0 the result is filter_components(that mesh, min_faces,
+        min_fraction): its small connected components are gone."""
         level, min_weight = _check_extract(level, min_weight, max_vertices, max_faces)
-        return _extract(self.tsdf, self.weight, self.rgb, self.origin, self.voxel, self.dims, level, min_weight, max_vertices,
-                        max_faces)
+        keep = _check_keep(min_component_faces, min_component_fraction, tuple(_NO_FILTER))
+        return _filtered(_extract(self.tsdf, self.weight, self.rgb, self.origin, self.voxel, self.dims, level, min_weight,
+                                  max_vertices, max_faces), *keep)
 
 
 BLOCK = 8                                      # lattice points per block edge
@@ -377,12 +546,15 @@ class SparseTsdfVolume:
                      guard=True)
         return self
 
-    def extract(self, level=0.0, min_weight=1.0, max_vertices=None, max_faces=None):
+    def extract(self, level=0.0, min_weight=1.0, max_vertices=None, max_faces=None, *, min_component_faces=0,
+                min_component_fraction=0.0):
         """The mesh of the surface tsdf = level over the cells every corner of which is stored and was seen by at least
         min_weight frames.  Vertices come in pool order, then (z, y, x, edge) inside the block; faces in the pool order of
         the cell's lowest corner, then (z, y, x) inside the block, then (tetrahedron, triangle).  Capacities and read-backs as
-        extract_mesh has them.  With zero blocks nothing is launched and the mesh is empty."""
+        extract_mesh has them.  With zero blocks nothing is launched and the mesh is empty.  min_component_faces and
+        min_component_fraction as TsdfVolume.extract takes them."""
         level, min_weight = _check_extract(level, min_weight, max_vertices, max_faces)
+        keep = _check_keep(min_component_faces, min_component_fraction, tuple(_NO_FILTER))
         dev = self.table.device
         if not self.n_blocks:
             return {"vertices": torch.empty(0, 3, dtype=torch.float32, device=dev), "faces": torch.empty(0, 3, dtype=torch.int32, device=dev),
@@ -394,7 +566,7 @@ class SparseTsdfVolume:
             N.launch("lrf_mesh_extract_blocks", dev, C.byref(a), level, min_weight, cap_v, cap_f, v.data_ptr(),
                      None if c is None else c.data_ptr(), f.data_ptr(), counts.data_ptr(), ws.data_ptr(), guard=True)
 
-        return _sized_extract(dev, self.colours, launch, max_vertices, max_faces)
+        return _filtered(_sized_extract(dev, self.colours, launch, max_vertices, max_faces), *keep)
 
     def to_dense(self):
         """(tsdf, weight, rgb or None, stored) as [8Bz,8By,8Bx] tensors of the virtual lattice (rgb [...,3]; stored: bool, the
@@ -413,7 +585,8 @@ class SparseTsdfVolume:
                 stored)
 
 
-_MESH_KEYS = ("depth_range", "level", "min_weight", "max_vertices", "max_faces", "colours", "frames_per_call")
+_MESH_KEYS = ("depth_range", "level", "min_weight", "max_vertices", "max_faces", "colours", "frames_per_call",
+              "min_component_faces", "min_component_fraction")
 
 
 def _lattice_of_box(lo, hi, voxel):
@@ -434,7 +607,9 @@ def scene_mesh(local_tensorfs, W, H, voxel, bounds=None, poses=None, trunc=None,
     beforehand and takes the box of pointcloud.fuse_points over the depths inside depth_range, grown by trunc on every
     side: one more render pass and one more read-back of the box.  trunc=None means 3 * voxel: a convenience, not a measured
     optimum -- it should exceed the depth noise of the scene.  options: depth_range, level, min_weight, max_vertices,
-    max_faces, colours (default True), frames_per_call and render_poses' test_frames, frame_indices, floater_thresh, chunk.
+    max_faces, colours (default True), frames_per_call, min_component_faces and min_component_fraction (both default 0: with
+    either above 0 the extracted mesh goes through filter_components, which drops its small connected components) and
+    render_poses' test_frames, frame_indices, floater_thresh, chunk.
     A volume above max_bytes raises ValueError before it is allocated and, with bounds given, before anything is rendered.
     depth="median" integrates the median depth of the same frames (depth_quantiles.median_depth: one more render pass per
     batch) instead of render_poses' expected depth, which carves a phantom sheet between two surfaces a ray sees; the colours
@@ -463,6 +638,7 @@ def scene_mesh(local_tensorfs, W, H, voxel, bounds=None, poses=None, trunc=None,
     level, min_weight = _check_extract(options.get("level", 0.0), options.get("min_weight", 1.0), options.get("max_vertices"),
                                        options.get("max_faces"))
     colours = bool(options.get("colours", True))
+    keep = _check_keep(options.get("min_component_faces", 0), options.get("min_component_fraction", 0.0), tuple(_NO_FILTER))
     per_call = options.get("frames_per_call", 8)
     if int(per_call) != per_call or int(per_call) < 1:
         raise ValueError(f"frames_per_call must be an integer >= 1, got {per_call!r}")
@@ -527,6 +703,7 @@ def scene_mesh(local_tensorfs, W, H, voxel, bounds=None, poses=None, trunc=None,
         vol = TsdfVolume(lo, voxel, shape, trunc, lt.blending_weights.device, colours=colours)
     for p, dmap, rgb8 in batches():
         vol.integrate(dmap, p, focal, center, rgb=rgb8, depth_range=depth_range)
-    mesh = vol.extract(level, min_weight, options.get("max_vertices"), options.get("max_faces"))
+    mesh = vol.extract(level, min_weight, options.get("max_vertices"), options.get("max_faces"), min_component_faces=keep[0],
+                       min_component_fraction=keep[1])
     mesh["volume"] = vol
     return mesh
