@@ -152,8 +152,10 @@ class LocalTensorfs(SceneLifecycle):
         center = self.center(W, H) if pinhole else None
         if len(active) == 0:                                    # degenerate 5-tuple (:420-422)
             print("****** No valid RF")
-            _, directions, ij = scene_rays(ray_ids, cam2world, torch.zeros(1, 3, device=dev), focal, center,
-                                           max(1, n_rays // max(1, n_views)), W, H, not pinhole)
+            # directions and ij depend on the ids and the intrinsics alone (:397-401,419), and the reference returns here
+            # before it divides the rays among the views (:437): all rays as one view, whatever n_rays / n_views is
+            _, directions, ij = scene_rays(ray_ids, cam2world[:1], torch.zeros(1, 3, device=dev), focal, center,
+                                           max(1, n_rays), W, H, not pinhole)
             return (torch.ones([n_rays, 3]), torch.ones_like(ray_ids).float(),
                     torch.ones_like(ray_ids).float(), directions, ij)
         if n_rays % n_views:
