@@ -1,14 +1,15 @@
 // lrf_mesh.inl -- rendered depth fused into a truncated signed-distance (TSDF) volume, and a triangle mesh extracted from a
 // scalar volume (included by lrf_render.hip after lrf_encode.inl and lrf_points.inl, whose enc_rgb_byte, pts_finite_pos,
-// reproject and k_points_scan it shares).
+// reproject and k_points_scan it shares).  The fusion and the extraction are each written once, here, for the dense volume
+// of this file and for the block-sparse one of lrf_tsdf_blocks.inl: the two differ only in where a lattice point is stored.
 //
-// A volume is a lattice of Nx x Ny x Nz points at origin + (ix, iy, iz) * voxel, x fastest in memory: tsdf [Nz,Ny,Nx] (starts
-// at 1), weight [Nz,Ny,Nx] (starts at 0), rgb [Nz,Ny,Nx,3] in [0, 1] (nullable, starts at 0).
+// A lattice has Nx x Ny x Nz points at origin + (ix, iy, iz) * voxel.  Per point: tsdf (starts at 1), weight (starts at 0), rgb
+// in [0, 1] (3 floats, nullable, starts at 0).  The dense volume stores every point, x fastest: [Nz,Ny,Nx] and [Nz,Ny,Nx,3].
 //
-// k_tsdf_integrate: one lane per lattice point, a wave covers 64 consecutive x of one (z, y) row, so its reprojections land on
-// neighbouring pixels.  The point's tsdf, weight and rgb are read once, kept in registers over the frame loop and written
-// once.  Per frame v in frame order, in fp32 with contraction off so that a numpy restatement matches bit for bit:
-//   0. p = origin + (float)(ix, iy, iz) * voxel, one multiply and one add per axis;
+// Fusion (tsdf_fuse_point): one lane per stored point.  The point's tsdf, weight and rgb are read once, kept in registers over
+// the frame loop and written once.  Per frame v in frame order, in fp32 with contraction off so that a numpy restatement
+// matches bit for bit:
+//   0. p = origin + (float)(ix, iy, iz) * voxel, one multiply and one add per axis (the kernel's part);
 //   1. reproject (lrf_points.inl): q = R_v^T (p - t_v), nz = -q.z; skipped behind the camera or outside the image;
 //   2. dn = depth[v,iw,iu]; skipped unless finite, positive and d_min <= dn <= d_max;
 //   3. sdf = dn - nz (both in units of the un-normalised direction whose z is -1); skipped if sdf < -trunc;
@@ -17,6 +18,7 @@
 //      weight = weight + 1.
 // The frame's camera-to-world matrix is addressed by the loop counter alone, so it is read with scalar loads into scalar
 // registers.  No atomics; integrating frames k..V on the state frames 0..k left gives the bits of one call over 0..V.
+// k_tsdf_integrate: a wave covers 64 consecutive x of one (z, y) row, so its reprojections land on neighbouring pixels.
 //
 // Extraction: marching tetrahedra on the Kuhn split of each cell.  Corners of a cell are numbered by their offset bits
 // (bit 0 = x, bit 1 = y, bit 2 = z).  Tetrahedron t = 0..5 is the monotone path 000 -> 111 of the t-th permutation (a, b, c)
@@ -34,12 +36,21 @@
 //   faces    per valid cell, tetrahedron by tetrahedron: one inside corner i -> (ij, ik, il) for the even permutation
 //            (i, j, k, l); three inside -> the outside corner's triangle reversed; two inside i, j -> (ik, il, jl) and
 //            (ik, jl, jk).  The normal points towards value > level.
-// Three launches, no atomics, no host synchronisation:
-//   k_mesh_count  per lattice point the 7-bit mask of its vertices, the triangles of its cell and the vertices before it in
-//                 its workgroup -> info; per workgroup the vertex and face totals
+// The rules read the lattice through a view (MeshArgs here, BlocksMeshArgs in lrf_tsdf_blocks.inl) that maps storage to it:
+//   point(p)               storage point p -> MeshPoint: its storage index and lattice coordinates
+//   beside(q, dx, dy, dz)  offsets in -1..1 -> the neighbour's storage index; -2 beyond the lattice, -1 on the lattice but
+//                          not stored (never from the dense view)
+//   corner(q, d)           beside() for the corner d of the cell at q, for a cell known to be valid (the dense view skips the
+//                          bounds checks)
+//   stored(o)              o >= 0; val(o), passes(o), colour(o, c): the value, weight >= min_weight and rgb at o, where -1
+//                          reads as value 1, weight 0, rgb 0.  A negative index is never dereferenced nor owns a vertex.
+// Three launches, no atomics, no host synchronisation; storage order is (z, y, x) for the dense view:
+//   count (mesh_count_body)  per storage point the 7-bit mask of its vertices, the triangles of its cell and the vertices
+//                 before it in its workgroup -> info; per workgroup the vertex and face totals
 //   k_points_scan two workgroups: exclusive vertex and face bases per workgroup, the true totals in counts[0..1]
-//   k_mesh_emit   vertices in (z, y, x, edge) order, faces in (cell, tetrahedron, triangle) order; a face's vertex index is
-//                 its owner's base + popcount(owner's mask below the edge).  Rows at or beyond capacity are not written.
+//   emit (mesh_emit_body)  vertices in (storage point, edge) order, faces in (cell, tetrahedron, triangle) order; a face's
+//                 vertex index is its owner's base + popcount(owner's mask below the edge).  Rows at or beyond capacity are
+//                 not written.
 namespace lrf {
 
 constexpr int TSDF_NT = 256;
@@ -55,6 +66,40 @@ struct TsdfArgs {
   float d_min, d_max;
 };
 
+// steps 1..4 over the V frames for the point at pw whose state is stored at index p
+__device__ __forceinline__ void tsdf_fuse_point(size_t p, const float (&pw)[3], float* tsdf, float* weight, float* rgb, float trunc,
+                                                const float* __restrict__ depth, const uint8_t* __restrict__ rgb8,
+                                                const float* __restrict__ c2w, const float* __restrict__ focal,
+                                                const float* __restrict__ center, int V, int H, int W, float d_min, float d_max) {
+#pragma clang fp contract(off)
+  const float f = focal[0], cx = center[0], cy = center[1];
+  float t = tsdf[p], wt = weight[p];
+  float c0 = 0.0f, c1 = 0.0f, c2 = 0.0f;
+  if (rgb) { c0 = rgb[3 * p]; c1 = rgb[3 * p + 1]; c2 = rgb[3 * p + 2]; }
+  for (int v = 0; v < V; ++v) {
+    float nz;
+    int iu, iw;
+    if (!reproject(c2w + (size_t)v * 12, pw, f, cx, cy, W, H, nz, iu, iw)) continue;
+    const size_t px = (size_t)v * H * W + (size_t)iw * W + iu;
+    const float dn = depth[px];
+    if (!(pts_finite_pos(dn) && dn >= d_min && dn <= d_max)) continue;
+    const float sdf = dn - nz;
+    if (sdf < -trunc) continue;
+    const float s = fminf(1.0f, sdf / trunc);
+    const float w1 = wt + 1.0f;
+    t = (t * wt + s) / w1;
+    if (rgb) {
+      const uint8_t* c = rgb8 + 3 * px;
+      c0 = (c0 * wt + (float)c[0] / 255.0f) / w1;
+      c1 = (c1 * wt + (float)c[1] / 255.0f) / w1;
+      c2 = (c2 * wt + (float)c[2] / 255.0f) / w1;
+    }
+    wt = w1;
+  }
+  tsdf[p] = t; weight[p] = wt;
+  if (rgb) { rgb[3 * p] = c0; rgb[3 * p + 1] = c1; rgb[3 * p + 2] = c2; }
+}
+
 __global__ __launch_bounds__(TSDF_NT) void k_tsdf_integrate(TsdfArgs a, const float* __restrict__ depth,
                                                             const uint8_t* __restrict__ rgb8, const float* __restrict__ c2w,
                                                             const float* __restrict__ focal, const float* __restrict__ center) {
@@ -66,34 +111,9 @@ __global__ __launch_bounds__(TSDF_NT) void k_tsdf_integrate(TsdfArgs a, const fl
   const int iy = (int)(row % a.Ny), iz = (int)(row / a.Ny);
   const int ix = xc * 64 + (threadIdx.x & 63);
   if (ix >= a.Nx) return;
-  const size_t p = (size_t)row * a.Nx + ix;
   const float pw[3] = {a.ox + (float)ix * a.voxel, a.oy + (float)iy * a.voxel, a.oz + (float)iz * a.voxel};
-  const float f = focal[0], cx = center[0], cy = center[1];
-  float t = a.tsdf[p], wt = a.weight[p];
-  float c0 = 0.0f, c1 = 0.0f, c2 = 0.0f;
-  if (a.rgb) { c0 = a.rgb[3 * p]; c1 = a.rgb[3 * p + 1]; c2 = a.rgb[3 * p + 2]; }
-  for (int v = 0; v < a.V; ++v) {
-    float nz;
-    int iu, iw;
-    if (!reproject(c2w + (size_t)v * 12, pw, f, cx, cy, a.W, a.H, nz, iu, iw)) continue;
-    const size_t px = (size_t)v * a.H * a.W + (size_t)iw * a.W + iu;
-    const float dn = depth[px];
-    if (!(pts_finite_pos(dn) && dn >= a.d_min && dn <= a.d_max)) continue;
-    const float sdf = dn - nz;
-    if (sdf < -a.trunc) continue;
-    const float s = fminf(1.0f, sdf / a.trunc);
-    const float w1 = wt + 1.0f;
-    t = (t * wt + s) / w1;
-    if (a.rgb) {
-      const uint8_t* c = rgb8 + 3 * px;
-      c0 = (c0 * wt + (float)c[0] / 255.0f) / w1;
-      c1 = (c1 * wt + (float)c[1] / 255.0f) / w1;
-      c2 = (c2 * wt + (float)c[2] / 255.0f) / w1;
-    }
-    wt = w1;
-  }
-  a.tsdf[p] = t; a.weight[p] = wt;
-  if (a.rgb) { a.rgb[3 * p] = c0; a.rgb[3 * p + 1] = c1; a.rgb[3 * p + 2] = c2; }
+  tsdf_fuse_point((size_t)row * a.Nx + ix, pw, a.tsdf, a.weight, a.rgb, a.trunc, depth, rgb8, c2w, focal, center, a.V, a.H, a.W,
+                  a.d_min, a.d_max);
 }
 
 // ------------------------------------------------------------------------------------------------ the case tables, in code
@@ -145,16 +165,35 @@ __constant__ unsigned MT_CASE[16] = {mt_case(0), mt_case(1), mt_case(2), mt_case
                                      mt_case(8), mt_case(9), mt_case(10), mt_case(11), mt_case(12), mt_case(13), mt_case(14),
                                      mt_case(15)};
 
+// a lattice point: its storage index and its lattice coordinates
+struct MeshPoint { int p, x, y, z; };
+
+// the dense view: storage index = (z Ny + y) Nx + x
 struct MeshArgs {
   const float* value; const float* weight; const float* rgb;        // weight, rgb nullable
   int Nx, Ny, Nz, n;                                                // n = Nx Ny Nz < 2^31
   float ox, oy, oz, voxel, level, min_weight;
-};
 
-// lattice offset of the corner / direction with offset bits d
-__device__ __forceinline__ long long mesh_off(const MeshArgs& a, int d) {
-  return (d & 1) + (long long)((d >> 1) & 1) * a.Nx + (long long)((d >> 2) & 1) * a.Nx * a.Ny;
-}
+  __device__ __forceinline__ MeshPoint point(int p) const {
+    const int r = p / Nx;
+    return {p, p % Nx, r % Ny, r / Ny};
+  }
+  __device__ __forceinline__ int offset(int dx, int dy, int dz) const {
+    return (int)(dx + (long long)dy * Nx + (long long)dz * Nx * Ny);
+  }
+  // q lies on the lattice, so an axis can only be left on the side its offset points to
+  __device__ __forceinline__ int beside(const MeshPoint& q, int dx, int dy, int dz) const {
+    if ((dx < 0 && q.x == 0) || (dx > 0 && q.x + 1 >= Nx) || (dy < 0 && q.y == 0) || (dy > 0 && q.y + 1 >= Ny) ||
+        (dz < 0 && q.z == 0) || (dz > 0 && q.z + 1 >= Nz))
+      return -2;
+    return q.p + offset(dx, dy, dz);
+  }
+  __device__ __forceinline__ int corner(const MeshPoint& q, int d) const { return q.p + offset(d & 1, (d >> 1) & 1, (d >> 2) & 1); }
+  __device__ __forceinline__ bool stored(int) const { return true; }
+  __device__ __forceinline__ float val(int o) const { return value[o]; }
+  __device__ __forceinline__ bool passes(int o) const { return !weight || weight[o] >= min_weight; }
+  __device__ __forceinline__ float colour(int o, int c) const { return rgb[3 * (size_t)o + c]; }
+};
 
 // exclusive prefix of v over the workgroup's MESH_NT threads (every thread calls), total = the workgroup's sum
 __device__ __forceinline__ unsigned mesh_block_scan(unsigned v, unsigned* part, unsigned& total) {
@@ -188,21 +227,21 @@ __device__ __forceinline__ unsigned mesh_tet_tris(unsigned m) {
   return pc == 2 ? 2u : (pc == 1 || pc == 3) ? 1u : 0u;
 }
 
-// info[p] = vertex mask | triangles of the cell << 7 | vertices before p in its workgroup << 11
-__global__ __launch_bounds__(MESH_NT) void k_mesh_count(MeshArgs a, unsigned* __restrict__ info, unsigned* __restrict__ wgv,
-                                                        unsigned* __restrict__ wgf) {
-  __shared__ unsigned part[MESH_NT / 64];
+// info[p] = vertex mask | triangles of the cell << 7 | vertices before p in its workgroup << 11; part: MESH_NT / 64 words of LDS
+template <class View>
+__device__ __forceinline__ void mesh_count_body(const View& a, unsigned* part, unsigned* __restrict__ info,
+                                                unsigned* __restrict__ wgv, unsigned* __restrict__ wgf) {
   const long long pl = (long long)blockIdx.x * MESH_NT + threadIdx.x;
   unsigned mask = 0, ntri = 0;
   if (pl < a.n) {
-    const int p = (int)pl;
-    const int ix = p % a.Nx, r = p / a.Nx, iy = r % a.Ny, iz = r / a.Ny;
-    const bool ina = a.value[p] < a.level;
+    const MeshPoint q = a.point((int)pl);
+    const bool ina = a.val(q.p) < a.level;
     unsigned cm = ina ? 1u : 0u, present = 1u, strad = 0u;
 #pragma unroll
     for (int d = 1; d < 8; ++d) {
-      if (ix + (d & 1) >= a.Nx || iy + ((d >> 1) & 1) >= a.Ny || iz + ((d >> 2) & 1) >= a.Nz) continue;
-      const bool inb = a.value[p + mesh_off(a, d)] < a.level;
+      const int o = a.beside(q, d & 1, (d >> 1) & 1, (d >> 2) & 1);
+      if (o == -2) continue;
+      const bool inb = a.val(o) < a.level;
       present |= 1u << d;
       cm |= (inb ? 1u : 0u) << d;
       if (inb != ina) strad |= 1u << (d - 1);
@@ -211,10 +250,8 @@ __global__ __launch_bounds__(MESH_NT) void k_mesh_count(MeshArgs a, unsigned* __
       unsigned ok = 0;                                              // bit (dz+1) 9 + (dy+1) 3 + (dx+1): that neighbour can be a cell's corner
 #pragma unroll
       for (int k = 0; k < 27; ++k) {
-        const int dx = k % 3 - 1, dy = (k / 3) % 3 - 1, dz = k / 9 - 1;
-        const int jx = ix + dx, jy = iy + dy, jz = iz + dz;
-        if (jx < 0 || jx >= a.Nx || jy < 0 || jy >= a.Ny || jz < 0 || jz >= a.Nz) continue;
-        if (!a.weight || a.weight[p + dx + (long long)dy * a.Nx + (long long)dz * a.Nx * a.Ny] >= a.min_weight) ok |= 1u << k;
+        const int o = a.beside(q, k % 3 - 1, (k / 3) % 3 - 1, k / 9 - 1);
+        if (o != -2 && a.passes(o)) ok |= 1u << k;
       }
 #pragma unroll
       for (int e = 0; e < 7; ++e) {
@@ -240,18 +277,11 @@ __global__ __launch_bounds__(MESH_NT) void k_mesh_count(MeshArgs a, unsigned* __
   if (threadIdx.x == 0) { wgv[blockIdx.x] = vtot; wgf[blockIdx.x] = ftot; }
 }
 
-// the index of the vertex on edge (code >> 3) - 1 of the point at corner (code & 7) of the cell at p
-__device__ __forceinline__ int mesh_vertex_index(const MeshArgs& a, const unsigned* __restrict__ info,
-                                                 const unsigned* __restrict__ wgv, int p, unsigned code) {
-  const long long o = p + mesh_off(a, (int)(code & 7u));
-  const unsigned oi = info[o];
-  return (int)(wgv[o / MESH_NT] + (oi >> 11) + __popc(oi & ((1u << ((code >> 3) - 1u)) - 1u)));
-}
-
-template <int T>
-__device__ __forceinline__ void mesh_tet_faces(const MeshArgs& a, const unsigned* __restrict__ info,
-                                               const unsigned* __restrict__ wgv, int p, unsigned cm, long long& row,
-                                               long long max_faces, int* __restrict__ faces) {
+// the faces of tetrahedron T of the valid cell at q; a vertex is indexed through the point that owns its edge
+template <int T, class View>
+__device__ __forceinline__ void mesh_tet_faces(const View& a, const unsigned* __restrict__ info, const unsigned* __restrict__ wgv,
+                                               const MeshPoint& q, unsigned cm, long long& row, long long max_faces,
+                                               int* __restrict__ faces) {
   constexpr unsigned long long edges = mt_tet_edges(T);
   const unsigned m = mesh_tet_mask<T>(cm);
   if (m == 0u || m == 15u) return;
@@ -261,43 +291,46 @@ __device__ __forceinline__ void mesh_tet_faces(const MeshArgs& a, const unsigned
     if (row >= max_faces) continue;
     for (int k = 0; k < 3; ++k) {
       const unsigned ek = (cs >> (2 + 9 * j + 3 * k)) & 7u;
-      faces[3 * row + k] = mesh_vertex_index(a, info, wgv, p, (unsigned)(edges >> (6 * ek)) & 63u);
+      const unsigned code = (unsigned)(edges >> (6 * ek)) & 63u;    // owner corner | direction << 3
+      const int o = a.corner(q, (int)(code & 7u));
+      if (!a.stored(o)) continue;                                   // only under a block table that does not match the pools
+      const unsigned oi = info[o];
+      faces[3 * row + k] = (int)(wgv[(unsigned)o / MESH_NT] + (oi >> 11) + __popc(oi & ((1u << ((code >> 3) - 1u)) - 1u)));
     }
   }
 }
 
-__global__ __launch_bounds__(MESH_NT) void k_mesh_emit(MeshArgs a, const unsigned* __restrict__ info,
-                                                       const unsigned* __restrict__ wgv, const unsigned* __restrict__ wgf,
-                                                       long long max_vertices, long long max_faces, float* __restrict__ vertices,
-                                                       uint8_t* __restrict__ rgb8_out, int* __restrict__ faces) {
+template <class View>
+__device__ __forceinline__ void mesh_emit_body(const View& a, unsigned* part, const unsigned* __restrict__ info,
+                                               const unsigned* __restrict__ wgv, const unsigned* __restrict__ wgf,
+                                               long long max_vertices, long long max_faces, float* __restrict__ vertices,
+                                               uint8_t* __restrict__ rgb8_out, int* __restrict__ faces) {
 #pragma clang fp contract(off)
-  __shared__ unsigned part[MESH_NT / 64];
   const long long pl = (long long)blockIdx.x * MESH_NT + threadIdx.x;
   const unsigned me = pl < a.n ? info[pl] : 0u;
   const unsigned mask = me & 127u, ntri = (me >> 7) & 15u;
   unsigned ftot;
   const unsigned fpre = mesh_block_scan(ntri, part, ftot);
   if (!(mask | ntri)) return;
-  const int p = (int)pl;
-  const int ix = p % a.Nx, r = p / a.Nx, iy = r % a.Ny, iz = r / a.Ny;
+  const MeshPoint q = a.point((int)pl);
   if (mask) {
     long long row = (long long)wgv[blockIdx.x] + (me >> 11);
-    const float va = a.value[p];
-    const float pa[3] = {a.ox + (float)ix * a.voxel, a.oy + (float)iy * a.voxel, a.oz + (float)iz * a.voxel};
+    const float va = a.val(q.p);
+    const float pa[3] = {a.ox + (float)q.x * a.voxel, a.oy + (float)q.y * a.voxel, a.oz + (float)q.z * a.voxel};
 #pragma unroll
     for (int e = 0; e < 7; ++e) {
       if (!((mask >> e) & 1u)) continue;
       const int d = e + 1;
       if (row < max_vertices) {
-        const size_t q = (size_t)(p + mesh_off(a, d));
-        const float vb = a.value[q];
+        const int o = a.corner(q, d);                               // an edge of a valid cell: both ends are stored
+        const float vb = a.val(o);
         const float t = (a.level - va) / (vb - va);
-        const float pb[3] = {a.ox + (float)(ix + (d & 1)) * a.voxel, a.oy + (float)(iy + ((d >> 1) & 1)) * a.voxel,
-                             a.oz + (float)(iz + ((d >> 2) & 1)) * a.voxel};
+        const float pb[3] = {a.ox + (float)(q.x + (d & 1)) * a.voxel, a.oy + (float)(q.y + ((d >> 1) & 1)) * a.voxel,
+                             a.oz + (float)(q.z + ((d >> 2) & 1)) * a.voxel};
         for (int c = 0; c < 3; ++c) vertices[3 * row + c] = pa[c] + t * (pb[c] - pa[c]);
         if (rgb8_out) {
           for (int c = 0; c < 3; ++c) {
-            const float ca = a.rgb[3 * (size_t)p + c], cb = a.rgb[3 * q + c];
+            const float ca = a.colour(q.p, c), cb = a.colour(o, c);
             rgb8_out[3 * row + c] = (uint8_t)enc_rgb_byte(ca + t * (cb - ca));
           }
         }
@@ -305,18 +338,32 @@ __global__ __launch_bounds__(MESH_NT) void k_mesh_emit(MeshArgs a, const unsigne
       ++row;
     }
   }
-  if (ntri) {                                                       // the cell at p is valid: its eight corners exist
+  if (ntri) {                                                       // the cell at q is valid: its eight corners are stored
     unsigned cm = 0;
 #pragma unroll
-    for (int d = 0; d < 8; ++d) cm |= (a.value[p + mesh_off(a, d)] < a.level ? 1u : 0u) << d;
+    for (int d = 0; d < 8; ++d) cm |= (a.val(a.corner(q, d)) < a.level ? 1u : 0u) << d;
     long long row = (long long)wgf[blockIdx.x] + fpre;
-    mesh_tet_faces<0>(a, info, wgv, p, cm, row, max_faces, faces);
-    mesh_tet_faces<1>(a, info, wgv, p, cm, row, max_faces, faces);
-    mesh_tet_faces<2>(a, info, wgv, p, cm, row, max_faces, faces);
-    mesh_tet_faces<3>(a, info, wgv, p, cm, row, max_faces, faces);
-    mesh_tet_faces<4>(a, info, wgv, p, cm, row, max_faces, faces);
-    mesh_tet_faces<5>(a, info, wgv, p, cm, row, max_faces, faces);
+    mesh_tet_faces<0>(a, info, wgv, q, cm, row, max_faces, faces);
+    mesh_tet_faces<1>(a, info, wgv, q, cm, row, max_faces, faces);
+    mesh_tet_faces<2>(a, info, wgv, q, cm, row, max_faces, faces);
+    mesh_tet_faces<3>(a, info, wgv, q, cm, row, max_faces, faces);
+    mesh_tet_faces<4>(a, info, wgv, q, cm, row, max_faces, faces);
+    mesh_tet_faces<5>(a, info, wgv, q, cm, row, max_faces, faces);
   }
+}
+
+__global__ __launch_bounds__(MESH_NT) void k_mesh_count(MeshArgs a, unsigned* __restrict__ info, unsigned* __restrict__ wgv,
+                                                        unsigned* __restrict__ wgf) {
+  __shared__ unsigned part[MESH_NT / 64];
+  mesh_count_body(a, part, info, wgv, wgf);
+}
+
+__global__ __launch_bounds__(MESH_NT) void k_mesh_emit(MeshArgs a, const unsigned* __restrict__ info,
+                                                       const unsigned* __restrict__ wgv, const unsigned* __restrict__ wgf,
+                                                       long long max_vertices, long long max_faces, float* __restrict__ vertices,
+                                                       uint8_t* __restrict__ rgb8_out, int* __restrict__ faces) {
+  __shared__ unsigned part[MESH_NT / 64];
+  mesh_emit_body(a, part, info, wgv, wgf, max_vertices, max_faces, vertices, rgb8_out, faces);
 }
 
 // lattice points of a shape, or 0 when the entry points refuse it
@@ -324,6 +371,40 @@ static long long mesh_points(int Nx, int Ny, int Nz) {
   if (Nx < 1 || Ny < 1 || Nz < 1) return 0;
   const long long n = (long long)Nx * Ny;                            // < 2^62
   return n >= (1ll << 31) || n * Nz >= (1ll << 31) ? 0 : n * Nz;
+}
+
+// refuses with "<who>: <what>"
+static int mesh_refuse(const char* who, const char* what) {
+  char msg[160];
+  snprintf(msg, sizeof msg, "%s: %s", who, what);
+  return set_err(msg);
+}
+
+// the checks of the frames every fusion entry point takes (dense and block-sparse); 0 when they pass
+static int tsdf_check_frames(const char* who, const float* depth, const float* c2w, const float* focal, const float* center, int V,
+                             int H, int W, float d_min, float d_max) {
+  if (V < 1 || H < 1 || W < 1 || (long long)V * H * W >= (1ll << 31)) return mesh_refuse(who, "need V, H, W >= 1 and V H W < 2^31");
+  if (!depth || !c2w || !focal || !center) return mesh_refuse(who, "null argument");
+  if (!(d_min <= d_max)) return mesh_refuse(who, "need d_min <= d_max");
+  if (((uintptr_t)depth | (uintptr_t)c2w | (uintptr_t)focal | (uintptr_t)center) & 3)
+    return mesh_refuse(who, "float and int32 arrays must be 4-byte aligned");
+  return 0;
+}
+
+// the checks of the level, the gate and the outputs both extract entry points take; 0 when they pass
+static int mesh_check_outputs(const char* who, bool has_rgb, float level, bool gated, float min_weight, int64_t max_vertices,
+                              int64_t max_faces, const float* vertices, const uint8_t* rgb8_out, const int32_t* faces,
+                              const int64_t* counts, const void* workspace) {
+  if (!vertices || !faces || !counts || !workspace) return mesh_refuse(who, "null argument");
+  if (has_rgb != !!rgb8_out) return mesh_refuse(who, "rgb and rgb8_out go together");
+  if (level != level) return mesh_refuse(who, "level must not be NaN");
+  if (gated && !(min_weight > 0.0f)) return mesh_refuse(who, "min_weight must be > 0");
+  if (max_vertices < 0 || max_faces < 0 || max_vertices >= (1ll << 31) || max_faces >= (1ll << 31))
+    return mesh_refuse(who, "max_vertices and max_faces must lie in [0, 2^31)");
+  if (((uintptr_t)vertices | (uintptr_t)faces | (uintptr_t)workspace) & 3)
+    return mesh_refuse(who, "float and int32 arrays and the workspace must be 4-byte aligned");
+  if ((uintptr_t)counts & 7) return mesh_refuse(who, "counts must be 8-byte aligned");
+  return 0;
 }
 
 }  // namespace lrf
@@ -335,15 +416,12 @@ extern "C" int lrf_tsdf_integrate(const LrfTsdfVolume* vol, const float* depth, 
   if (!vol) return set_err("lrf_tsdf_integrate: null argument");
   const long long n = mesh_points(vol->Nx, vol->Ny, vol->Nz);
   if (!n) return set_err("lrf_tsdf_integrate: need Nx, Ny, Nz >= 1 and Nx Ny Nz < 2^31");
-  if (V < 1 || H < 1 || W < 1 || (long long)V * H * W >= (1ll << 31))
-    return set_err("lrf_tsdf_integrate: need V, H, W >= 1 and V H W < 2^31");
-  if (!vol->tsdf || !vol->weight || !depth || !cam2world || !focal || !center) return set_err("lrf_tsdf_integrate: null argument");
+  if (!vol->tsdf || !vol->weight) return set_err("lrf_tsdf_integrate: null argument");
+  if (tsdf_check_frames("lrf_tsdf_integrate", depth, cam2world, focal, center, V, H, W, d_min, d_max)) return 1;
   if (!vol->rgb != !rgb8) return set_err("lrf_tsdf_integrate: the volume's rgb and the frames' rgb8 go together");
   if (!(vol->voxel > 0.0f)) return set_err("lrf_tsdf_integrate: voxel must be > 0");
   if (!(vol->trunc > 0.0f)) return set_err("lrf_tsdf_integrate: trunc must be > 0");
-  if (!(d_min <= d_max)) return set_err("lrf_tsdf_integrate: need d_min <= d_max");
-  if (((uintptr_t)vol->tsdf | (uintptr_t)vol->weight | (uintptr_t)vol->rgb | (uintptr_t)depth | (uintptr_t)cam2world |
-       (uintptr_t)focal | (uintptr_t)center) & 3)
+  if (((uintptr_t)vol->tsdf | (uintptr_t)vol->weight | (uintptr_t)vol->rgb) & 3)
     return set_err("lrf_tsdf_integrate: float arrays must be 4-byte aligned");
   TsdfArgs a;
   memset(&a, 0, sizeof(a));
@@ -373,16 +451,13 @@ extern "C" int lrf_mesh_extract(const LrfMeshExtract* m, int64_t max_vertices, i
   if (!m) return set_err("lrf_mesh_extract: null argument");
   const long long n = mesh_points(m->Nx, m->Ny, m->Nz);
   if (!n) return set_err("lrf_mesh_extract: need Nx, Ny, Nz >= 1 and Nx Ny Nz < 2^31");
-  if (!m->value || !vertices || !faces || !counts || !workspace) return set_err("lrf_mesh_extract: null argument");
-  if (!m->rgb != !rgb8_out) return set_err("lrf_mesh_extract: rgb and rgb8_out go together");
+  if (!m->value) return set_err("lrf_mesh_extract: null argument");
   if (!(m->voxel > 0.0f)) return set_err("lrf_mesh_extract: voxel must be > 0");
-  if (m->level != m->level) return set_err("lrf_mesh_extract: level must not be NaN");
-  if (m->weight && !(m->min_weight > 0.0f)) return set_err("lrf_mesh_extract: min_weight must be > 0");
-  if (max_vertices < 0 || max_faces < 0 || max_vertices >= (1ll << 31) || max_faces >= (1ll << 31))
-    return set_err("lrf_mesh_extract: max_vertices and max_faces must lie in [0, 2^31)");
-  if (((uintptr_t)m->value | (uintptr_t)m->weight | (uintptr_t)m->rgb | (uintptr_t)vertices | (uintptr_t)faces | (uintptr_t)workspace) & 3)
-    return set_err("lrf_mesh_extract: float and int32 arrays and the workspace must be 4-byte aligned");
-  if ((uintptr_t)counts & 7) return set_err("lrf_mesh_extract: counts must be 8-byte aligned");
+  if (((uintptr_t)m->value | (uintptr_t)m->weight | (uintptr_t)m->rgb) & 3)
+    return set_err("lrf_mesh_extract: float arrays must be 4-byte aligned");
+  if (mesh_check_outputs("lrf_mesh_extract", m->rgb != nullptr, m->level, m->weight != nullptr, m->min_weight, max_vertices,
+                         max_faces, vertices, rgb8_out, faces, counts, workspace))
+    return 1;
   MeshArgs a;
   memset(&a, 0, sizeof(a));
   a.value = m->value; a.weight = m->weight; a.rgb = m->rgb;

@@ -50,6 +50,16 @@ __device__ __forceinline__ bool pts_finite_pos(float d) {
   return (__float_as_uint(d) & 0x7FFFFFFFu) < 0x7F800000u && d > 0.0f;
 }
 
+// step 2's arithmetic, shared with the block touch (lrf_tsdf_blocks.inl): the world point at `depth` along the pixel's direction
+// under the camera M [3,4] (camera-to-world)
+__device__ __forceinline__ void world_point(const float* __restrict__ M, const PixDir& p, float depth, float (&pw)[3]) {
+#pragma clang fp contract(off)
+  const float x = p.x * depth, y = p.y * depth, z = p.z * depth;
+  pw[0] = ((M[0] * x + M[1] * y) + M[2] * z) + M[3];
+  pw[1] = ((M[4] * x + M[5] * y) + M[6] * z) + M[7];
+  pw[2] = ((M[8] * x + M[9] * y) + M[10] * z) + M[11];
+}
+
 // candidate c -> frame v, pixel id pix; false when its depth fails step 1, else pw = the world point
 __device__ __forceinline__ bool pts_world(const PointsArgs& a, int c, float f, float cx, float cy, int& v, int& pix,
                                           float (&pw)[3]) {
@@ -61,12 +71,7 @@ __device__ __forceinline__ bool pts_world(const PointsArgs& a, int c, float f, f
   pix = js * a.stride * a.W + is * a.stride;
   const float d = a.depth[(size_t)v * a.H * a.W + pix];
   if (!(pts_finite_pos(d) && d >= a.d_min && d <= a.d_max)) return false;
-  const PixDir p = pixel_dir(pix, a.W, a.H, a.fov360, f, cx, cy);
-  const float x = p.x * d, y = p.y * d, z = p.z * d;
-  const float* M = a.c2w + (size_t)v * 12;
-  pw[0] = ((M[0] * x + M[1] * y) + M[2] * z) + M[3];
-  pw[1] = ((M[4] * x + M[5] * y) + M[6] * z) + M[7];
-  pw[2] = ((M[8] * x + M[9] * y) + M[10] * z) + M[11];
+  world_point(a.c2w + (size_t)v * 12, pixel_dir(pix, a.W, a.H, a.fov360, f, cx, cy), d, pw);
   return true;
 }
 

@@ -1,7 +1,7 @@
 // lrf_tsdf_blocks.inl -- a block-sparse TSDF volume: only the 8 x 8 x 8 blocks that some depth pixel's truncation band reaches
-// are stored, fused and meshed (included by lrf_render.hip after lrf_mesh.inl, whose k_tsdf_integrate arithmetic, case tables,
-// mesh_block_scan and tetrahedron helpers it shares, with lrf_points.inl's reproject and k_points_scan and lrf_encode.inl's
-// enc_rgb_byte).
+// are stored, fused and meshed (included by lrf_render.hip after lrf_mesh.inl, which states the fusion and the meshing rules
+// and holds their code: tsdf_fuse_point, mesh_count_body, mesh_emit_body.  This file adds what is its own: which blocks
+// exist, where a lattice point is stored, and in which order the pool is walked).
 //
 // The virtual lattice has 8Bx x 8By x 8Bz points at origin + (ix, iy, iz) * voxel: the dense lattice of those dims.  Stored:
 //   marks  uint8 [Bz,By,Bx]   1 once a pixel's band met the block (cumulative over touch calls), else 0
@@ -14,7 +14,7 @@
 // k_blocks_touch: one lane per depth pixel (v, row, col), plain byte stores of the value 1, no atomics:
 //   1. d = depth[v,row,col]; skipped unless finite, positive and d_min <= d <= d_max;
 //   2. dir = pixel_dir (lrf_scene.inl; z = -1); da = max(d - trunc, 0), db = d + trunc; the world points a, b at those depths
-//      as lrf_points.inl states them: pc = dir * depth, pw = ((r0 x + r1 y) + r2 z) + t;
+//      (world_point, lrf_points.inl);
 //   3. m = voxel + db / focal: the lattice points whose nearest pixel this is lie within half a pixel footprint of the centre
 //      ray (db / focal bounds it), and one voxel of rounding slack;
 //   4. per axis l = min(a, b) - m, h = max(a, b) + m (skipped unless l <= h: a NaN marks nothing);
@@ -30,13 +30,11 @@
 //   With max_blocks = n_blocks no fresh block could fit: a counting call, flag and scan only.  The host counts, grows coords and
 //   the pools, and only then lets the table change.
 // k_blocks_fuse: one workgroup of 512 lanes per pool block, a wave is the 8 x 8 slab of consecutive x, y at one z.  The
-//   block's coordinates come from coords[blockIdx]; ix = 8 bx + lx and so on; from there on the per-point, per-frame
-//   arithmetic is k_tsdf_integrate's steps 0..4 (lrf_mesh.inl), so an allocated point ends with the bits the dense kernel gives
-//   the same lattice point over the same frames.  The camera matrix is addressed by the loop counter alone.
-// Extraction: the marching tetrahedra of lrf_mesh.inl over the pool points, count / scan / emit.  A neighbour inside the
-//   block is the pool point beside it, one outside is fetched through the table; a lattice point in no block reads as
-//   (tsdf 1, weight 0), one beyond the lattice is absent.  Weight gating is always on (min_weight > 0), so a cell with a corner in
-//   no block is not valid: a missing block can leave a hole but never creates or moves a face.
+//   block's coordinates come from coords[blockIdx]; ix = 8 bx + lx and so on; the rest is tsdf_fuse_point, so an allocated point
+//   ends with the bits the dense kernel gives the same lattice point over the same frames.
+// Extraction: BlocksMeshArgs is the view of the pool points.  A neighbour inside the block is the pool point beside it, one
+//   outside is fetched through the table; a lattice point in no block is -1.  Weight gating is always on (min_weight > 0), so a
+//   cell with a corner in no block is not valid: a missing block can leave a hole but never creates or moves a face.
 //   Order: vertices in pool order, then (z, y, x, edge) inside the block; faces in pool order of the cell's lowest corner,
 //   then (z, y, x) inside the block, then (tetrahedron, triangle).  Both depend on the block list alone.
 namespace lrf {
@@ -53,16 +51,6 @@ struct BlocksArgs {
   float ox, oy, oz, voxel, trunc;
 };
 
-// pts_world's two lines (lrf_points.inl: pc = dir * depth; pw = ((r0 x + r1 y) + r2 z) + t) at a depth of the caller's: keep
-// the two in step
-__device__ __forceinline__ void blocks_world(const float* __restrict__ M, const PixDir& p, float depth, float (&pw)[3]) {
-#pragma clang fp contract(off)
-  const float x = p.x * depth, y = p.y * depth, z = p.z * depth;
-  pw[0] = ((M[0] * x + M[1] * y) + M[2] * z) + M[3];
-  pw[1] = ((M[4] * x + M[5] * y) + M[6] * z) + M[7];
-  pw[2] = ((M[8] * x + M[9] * y) + M[10] * z) + M[11];
-}
-
 __global__ __launch_bounds__(BLK_NT) void k_blocks_touch(BlocksArgs a, const float* __restrict__ depth,
                                                          const float* __restrict__ c2w, const float* __restrict__ focal,
                                                          const float* __restrict__ center, int H, int W, long long n_px,
@@ -78,8 +66,8 @@ __global__ __launch_bounds__(BLK_NT) void k_blocks_touch(BlocksArgs a, const flo
   const PixDir p = pixel_dir(pix, W, H, 0, f, center[0], center[1]);
   const float da = fmaxf(d - a.trunc, 0.0f), db = d + a.trunc;
   float pa[3], pb[3];
-  blocks_world(c2w + (size_t)v * 12, p, da, pa);
-  blocks_world(c2w + (size_t)v * 12, p, db, pb);
+  world_point(c2w + (size_t)v * 12, p, da, pa);
+  world_point(c2w + (size_t)v * 12, p, db, pb);
   const float m = a.voxel + db / f;
   const float bs = 8.0f * a.voxel;
   const float o[3] = {a.ox, a.oy, a.oz};
@@ -139,190 +127,51 @@ __global__ __launch_bounds__(BLK_PTS) void k_blocks_fuse(BlocksArgs a, const flo
   const int b = blockIdx.x;
   const int ix = 8 * a.coords[3 * b] + (threadIdx.x & 7), iy = 8 * a.coords[3 * b + 1] + ((threadIdx.x >> 3) & 7),
             iz = 8 * a.coords[3 * b + 2] + (threadIdx.x >> 6);
-  const size_t p = (size_t)b * BLK_PTS + threadIdx.x;
   const float pw[3] = {a.ox + (float)ix * a.voxel, a.oy + (float)iy * a.voxel, a.oz + (float)iz * a.voxel};
-  const float f = focal[0], cx = center[0], cy = center[1];
-  float t = a.tsdf[p], wt = a.weight[p];
-  float c0 = 0.0f, c1 = 0.0f, c2 = 0.0f;
-  if (a.rgb) { c0 = a.rgb[3 * p]; c1 = a.rgb[3 * p + 1]; c2 = a.rgb[3 * p + 2]; }
-  for (int v = 0; v < V; ++v) {
-    float nz;
-    int iu, iw;
-    if (!reproject(c2w + (size_t)v * 12, pw, f, cx, cy, W, H, nz, iu, iw)) continue;
-    const size_t px = (size_t)v * H * W + (size_t)iw * W + iu;
-    const float dn = depth[px];
-    if (!(pts_finite_pos(dn) && dn >= d_min && dn <= d_max)) continue;
-    const float sdf = dn - nz;
-    if (sdf < -a.trunc) continue;
-    const float s = fminf(1.0f, sdf / a.trunc);
-    const float w1 = wt + 1.0f;
-    t = (t * wt + s) / w1;
-    if (a.rgb) {
-      const uint8_t* c = rgb8 + 3 * px;
-      c0 = (c0 * wt + (float)c[0] / 255.0f) / w1;
-      c1 = (c1 * wt + (float)c[1] / 255.0f) / w1;
-      c2 = (c2 * wt + (float)c[2] / 255.0f) / w1;
-    }
-    wt = w1;
-  }
-  a.tsdf[p] = t; a.weight[p] = wt;
-  if (a.rgb) { a.rgb[3 * p] = c0; a.rgb[3 * p + 1] = c1; a.rgb[3 * p + 2] = c2; }
+  tsdf_fuse_point((size_t)b * BLK_PTS + threadIdx.x, pw, a.tsdf, a.weight, a.rgb, a.trunc, depth, rgb8, c2w, focal, center, V, H, W,
+                  d_min, d_max);
 }
 
 // ------------------------------------------------------------------------------------------------ extraction
+// the view of the pool points: storage index = 512 block + (lz 8 + ly) 8 + lx
 struct BlocksMeshArgs {
   const int* table; const int* coords; const float* value; const float* weight; const float* rgb;   // rgb nullable
   int Bx, By, Bz, n;                                                // n = 512 n_blocks < 2^31
   float ox, oy, oz, voxel, level, min_weight;
+
+  __device__ __forceinline__ MeshPoint point(int p) const {
+    __builtin_assume(p >= 0);                                       // a stored point: its own reads need no guard
+    const int b = p >> 9;
+    return {p, 8 * coords[3 * b] + (p & 7), 8 * coords[3 * b + 1] + ((p >> 3) & 7), 8 * coords[3 * b + 2] + ((p >> 6) & 7)};
+  }
+  __device__ __forceinline__ int beside(const MeshPoint& q, int dx, int dy, int dz) const {
+    const int nx = (q.p & 7) + dx, ny = ((q.p >> 3) & 7) + dy, nz = ((q.p >> 6) & 7) + dz;
+    if (!((nx | ny | nz) & ~7)) return q.p + dx + 8 * dy + 64 * dz;   // inside the block
+    const int gx = q.x + dx, gy = q.y + dy, gz = q.z + dz;            // 8 B < 2^31: no overflow
+    if (gx < 0 || gy < 0 || gz < 0 || gx >= 8 * Bx || gy >= 8 * By || gz >= 8 * Bz) return -2;
+    const int b = table[((size_t)(gz >> 3) * By + (gy >> 3)) * Bx + (gx >> 3)];
+    if (b < 0 || b >= (n >> 9)) return -1;
+    return b * BLK_PTS + ((gz & 7) << 6 | (gy & 7) << 3 | (gx & 7));
+  }
+  __device__ __forceinline__ int corner(const MeshPoint& q, int d) const { return beside(q, d & 1, (d >> 1) & 1, (d >> 2) & 1); }
+  __device__ __forceinline__ bool stored(int o) const { return o >= 0; }
+  __device__ __forceinline__ float val(int o) const { return o >= 0 ? value[o] : 1.0f; }
+  __device__ __forceinline__ bool passes(int o) const { return o >= 0 && weight[o] >= min_weight; }
+  __device__ __forceinline__ float colour(int o, int c) const { return o >= 0 ? rgb[3 * (size_t)o + c] : 0.0f; }
 };
 
-// a pool point: its index, its place in its block and on the lattice
-struct BlocksPoint { int p, lx, ly, lz, gx, gy, gz; };
-
-__device__ __forceinline__ BlocksPoint blocks_point(const BlocksMeshArgs& a, int p) {
-  BlocksPoint q;
-  const int b = p >> 9;
-  q.p = p; q.lx = p & 7; q.ly = (p >> 3) & 7; q.lz = (p >> 6) & 7;
-  q.gx = 8 * a.coords[3 * b] + q.lx; q.gy = 8 * a.coords[3 * b + 1] + q.ly; q.gz = 8 * a.coords[3 * b + 2] + q.lz;
-  return q;
-}
-
-// the pool index of the lattice point (dx, dy, dz) from q (each in -1..1); -1: in no block, -2: beyond the lattice
-__device__ __forceinline__ int blocks_beside(const BlocksMeshArgs& a, const BlocksPoint& q, int dx, int dy, int dz) {
-  const int nx = q.lx + dx, ny = q.ly + dy, nz = q.lz + dz;
-  if (!((nx | ny | nz) & ~7)) return q.p + dx + 8 * dy + 64 * dz;   // inside the block
-  const int gx = q.gx + dx, gy = q.gy + dy, gz = q.gz + dz;         // 8 B < 2^31: no overflow
-  if (gx < 0 || gy < 0 || gz < 0 || gx >= 8 * a.Bx || gy >= 8 * a.By || gz >= 8 * a.Bz) return -2;
-  const int b = a.table[((size_t)(gz >> 3) * a.By + (gy >> 3)) * a.Bx + (gx >> 3)];
-  if (b < 0 || b >= (a.n >> 9)) return -1;
-  return b * BLK_PTS + ((gz & 7) << 6 | (gy & 7) << 3 | (gx & 7));
-}
-
-// info[p] = vertex mask | triangles of the cell << 7 | vertices before p in its workgroup << 11, as k_mesh_count leaves it
 __global__ __launch_bounds__(BLK_NT) void k_blocks_count(BlocksMeshArgs a, unsigned* __restrict__ info, unsigned* __restrict__ wgv,
                                                          unsigned* __restrict__ wgf) {
   __shared__ unsigned part[BLK_NT / 64];
-  const long long pl = (long long)blockIdx.x * BLK_NT + threadIdx.x;
-  unsigned mask = 0, ntri = 0;
-  if (pl < a.n) {
-    const BlocksPoint q = blocks_point(a, (int)pl);
-    const bool ina = a.value[q.p] < a.level;
-    unsigned cm = ina ? 1u : 0u, present = 1u, strad = 0u;
-#pragma unroll
-    for (int d = 1; d < 8; ++d) {
-      const int o = blocks_beside(a, q, d & 1, (d >> 1) & 1, (d >> 2) & 1);
-      if (o == -2) continue;
-      const bool inb = (o >= 0 ? a.value[o] : 1.0f) < a.level;
-      present |= 1u << d;
-      cm |= (inb ? 1u : 0u) << d;
-      if (inb != ina) strad |= 1u << (d - 1);
-    }
-    if (strad) {
-      unsigned ok = 0;                                              // bit (dz+1) 9 + (dy+1) 3 + (dx+1): that neighbour can be a cell's corner
-#pragma unroll
-      for (int k = 0; k < 27; ++k) {
-        const int o = blocks_beside(a, q, k % 3 - 1, (k / 3) % 3 - 1, k / 9 - 1);
-        if (o >= 0 && a.weight[o] >= a.min_weight) ok |= 1u << k;
-      }
-#pragma unroll
-      for (int e = 0; e < 7; ++e) {
-        const int d = e + 1, fr = ~d & 7;
-        bool any = false;
-#pragma unroll
-        for (int s = 0; s < 8; ++s) {
-          if (s & ~fr) continue;                                    // s: the axes along which the cell starts one point before P
-          const int shift = 13 - (s & 1) - 3 * ((s >> 1) & 1) - 9 * ((s >> 2) & 1);
-          any = any || ((ok >> shift) & MESH_CELL) == MESH_CELL;
-        }
-        if (((strad >> e) & 1u) && any) mask |= 1u << e;
-      }
-      if (present == 0xFFu && ((ok >> 13) & MESH_CELL) == MESH_CELL)
-        ntri = mesh_tet_tris(mesh_tet_mask<0>(cm)) + mesh_tet_tris(mesh_tet_mask<1>(cm)) + mesh_tet_tris(mesh_tet_mask<2>(cm)) +
-               mesh_tet_tris(mesh_tet_mask<3>(cm)) + mesh_tet_tris(mesh_tet_mask<4>(cm)) + mesh_tet_tris(mesh_tet_mask<5>(cm));
-    }
-  }
-  unsigned vtot, ftot;
-  const unsigned vpre = mesh_block_scan(__popc(mask), part, vtot);
-  mesh_block_scan(ntri, part, ftot);
-  if (pl < a.n) info[pl] = mask | ntri << 7 | vpre << 11;
-  if (threadIdx.x == 0) { wgv[blockIdx.x] = vtot; wgf[blockIdx.x] = ftot; }
-}
-
-template <int T>
-__device__ __forceinline__ void blocks_tet_faces(const BlocksMeshArgs& a, const unsigned* __restrict__ info,
-                                                 const unsigned* __restrict__ wgv, const BlocksPoint& q, unsigned cm, long long& row,
-                                                 long long max_faces, int* __restrict__ faces) {
-  constexpr unsigned long long edges = mt_tet_edges(T);
-  const unsigned m = mesh_tet_mask<T>(cm);
-  if (m == 0u || m == 15u) return;
-  const unsigned cs = MT_CASE[m];
-  const int nt = (int)(cs & 3u);
-  for (int j = 0; j < nt; ++j, ++row) {
-    if (row >= max_faces) continue;
-    for (int k = 0; k < 3; ++k) {
-      const unsigned ek = (cs >> (2 + 9 * j + 3 * k)) & 7u;
-      const unsigned code = (unsigned)(edges >> (6 * ek)) & 63u;    // owner corner | direction << 3
-      const int o = blocks_beside(a, q, (int)(code & 1u), (int)((code >> 1) & 1u), (int)((code >> 2) & 1u));   // a valid cell's corner: >= 0
-      if (o < 0) continue;                                          // only under a table that does not match the pools
-      const unsigned oi = info[o];
-      faces[3 * row + k] = (int)(wgv[o / BLK_NT] + (oi >> 11) + __popc(oi & ((1u << ((code >> 3) - 1u)) - 1u)));
-    }
-  }
+  mesh_count_body(a, part, info, wgv, wgf);
 }
 
 __global__ __launch_bounds__(BLK_NT) void k_blocks_emit(BlocksMeshArgs a, const unsigned* __restrict__ info,
                                                         const unsigned* __restrict__ wgv, const unsigned* __restrict__ wgf,
                                                         long long max_vertices, long long max_faces, float* __restrict__ vertices,
                                                         uint8_t* __restrict__ rgb8_out, int* __restrict__ faces) {
-#pragma clang fp contract(off)
   __shared__ unsigned part[BLK_NT / 64];
-  const long long pl = (long long)blockIdx.x * BLK_NT + threadIdx.x;
-  const unsigned me = pl < a.n ? info[pl] : 0u;
-  const unsigned mask = me & 127u, ntri = (me >> 7) & 15u;
-  unsigned ftot;
-  const unsigned fpre = mesh_block_scan(ntri, part, ftot);
-  if (!(mask | ntri)) return;
-  const BlocksPoint q = blocks_point(a, (int)pl);
-  if (mask) {
-    long long row = (long long)wgv[blockIdx.x] + (me >> 11);
-    const float va = a.value[q.p];
-    const float pa[3] = {a.ox + (float)q.gx * a.voxel, a.oy + (float)q.gy * a.voxel, a.oz + (float)q.gz * a.voxel};
-#pragma unroll
-    for (int e = 0; e < 7; ++e) {
-      if (!((mask >> e) & 1u)) continue;
-      const int d = e + 1;
-      if (row < max_vertices) {
-        const int o = blocks_beside(a, q, d & 1, (d >> 1) & 1, (d >> 2) & 1);   // an edge of a valid cell: both ends are stored
-        const float vb = o >= 0 ? a.value[o] : 1.0f;
-        const float t = (a.level - va) / (vb - va);
-        const float pb[3] = {a.ox + (float)(q.gx + (d & 1)) * a.voxel, a.oy + (float)(q.gy + ((d >> 1) & 1)) * a.voxel,
-                             a.oz + (float)(q.gz + ((d >> 2) & 1)) * a.voxel};
-        for (int c = 0; c < 3; ++c) vertices[3 * row + c] = pa[c] + t * (pb[c] - pa[c]);
-        if (rgb8_out) {
-          for (int c = 0; c < 3; ++c) {
-            const float ca = a.rgb[3 * (size_t)q.p + c], cb = o >= 0 ? a.rgb[3 * (size_t)o + c] : 0.0f;
-            rgb8_out[3 * row + c] = (uint8_t)enc_rgb_byte(ca + t * (cb - ca));
-          }
-        }
-      }
-      ++row;
-    }
-  }
-  if (ntri) {                                                       // the cell at q is valid: its eight corners are stored
-    unsigned cm = 0;
-#pragma unroll
-    for (int d = 0; d < 8; ++d) {
-      const int o = blocks_beside(a, q, d & 1, (d >> 1) & 1, (d >> 2) & 1);
-      cm |= ((o >= 0 ? a.value[o] : 1.0f) < a.level ? 1u : 0u) << d;
-    }
-    long long row = (long long)wgf[blockIdx.x] + fpre;
-    blocks_tet_faces<0>(a, info, wgv, q, cm, row, max_faces, faces);
-    blocks_tet_faces<1>(a, info, wgv, q, cm, row, max_faces, faces);
-    blocks_tet_faces<2>(a, info, wgv, q, cm, row, max_faces, faces);
-    blocks_tet_faces<3>(a, info, wgv, q, cm, row, max_faces, faces);
-    blocks_tet_faces<4>(a, info, wgv, q, cm, row, max_faces, faces);
-    blocks_tet_faces<5>(a, info, wgv, q, cm, row, max_faces, faces);
-  }
+  mesh_emit_body(a, part, info, wgv, wgf, max_vertices, max_faces, vertices, rgb8_out, faces);
 }
 
 // blocks of a grid, or 0 when the entry points refuse it: each of Bx, By, Bz >= 1, 8 B < 2^31, Bx By Bz < 2^31
@@ -334,48 +183,19 @@ static long long blocks_grid(int Bx, int By, int Bz) {
 
 // the checks the four entry points share; 0 when the volume passes
 static int blocks_check(const char* who, const LrfTsdfBlocks* g, bool pools, BlocksArgs& a) {
-  char msg[160];
-  if (!g) { snprintf(msg, sizeof msg, "%s: null argument", who); return set_err(msg); }
+  if (!g) return mesh_refuse(who, "null argument");
   const long long nb = blocks_grid(g->Bx, g->By, g->Bz);
-  if (!nb) {
-    snprintf(msg, sizeof msg, "%s: need Bx, By, Bz >= 1, 8 B < 2^31 per axis and Bx By Bz < 2^31", who);
-    return set_err(msg);
-  }
-  if (g->n_blocks < 0 || g->n_blocks > BLK_MAX_BLOCKS) {
-    snprintf(msg, sizeof msg, "%s: need 0 <= n_blocks and 512 n_blocks < 2^31", who);
-    return set_err(msg);
-  }
-  if (!g->table || !g->coords || (pools ? !g->tsdf || !g->weight : !g->marks)) {
-    snprintf(msg, sizeof msg, "%s: null argument", who);
-    return set_err(msg);
-  }
-  if (!(g->voxel > 0.0f)) { snprintf(msg, sizeof msg, "%s: voxel must be > 0", who); return set_err(msg); }
-  if (!(g->trunc > 0.0f)) { snprintf(msg, sizeof msg, "%s: trunc must be > 0", who); return set_err(msg); }
-  if (((uintptr_t)g->table | (uintptr_t)g->coords | (uintptr_t)g->tsdf | (uintptr_t)g->weight | (uintptr_t)g->rgb) & 3) {
-    snprintf(msg, sizeof msg, "%s: float and int32 arrays must be 4-byte aligned", who);
-    return set_err(msg);
-  }
+  if (!nb) return mesh_refuse(who, "need Bx, By, Bz >= 1, 8 B < 2^31 per axis and Bx By Bz < 2^31");
+  if (g->n_blocks < 0 || g->n_blocks > BLK_MAX_BLOCKS) return mesh_refuse(who, "need 0 <= n_blocks and 512 n_blocks < 2^31");
+  if (!g->table || !g->coords || (pools ? !g->tsdf || !g->weight : !g->marks)) return mesh_refuse(who, "null argument");
+  if (!(g->voxel > 0.0f)) return mesh_refuse(who, "voxel must be > 0");
+  if (!(g->trunc > 0.0f)) return mesh_refuse(who, "trunc must be > 0");
+  if (((uintptr_t)g->table | (uintptr_t)g->coords | (uintptr_t)g->tsdf | (uintptr_t)g->weight | (uintptr_t)g->rgb) & 3)
+    return mesh_refuse(who, "float and int32 arrays must be 4-byte aligned");
   memset(&a, 0, sizeof(a));
   a.marks = g->marks; a.table = g->table; a.coords = g->coords; a.tsdf = g->tsdf; a.weight = g->weight; a.rgb = g->rgb;
   a.Bx = g->Bx; a.By = g->By; a.Bz = g->Bz; a.n_blocks = g->n_blocks; a.nb = nb;
   a.ox = g->origin[0]; a.oy = g->origin[1]; a.oz = g->origin[2]; a.voxel = g->voxel; a.trunc = g->trunc;
-  return 0;
-}
-
-// the checks of the frames touch and integrate take; 0 when they pass
-static int blocks_check_frames(const char* who, const float* depth, const float* c2w, const float* focal, const float* center,
-                               int V, int H, int W, float d_min, float d_max) {
-  char msg[160];
-  if (V < 1 || H < 1 || W < 1 || (long long)V * H * W >= (1ll << 31)) {
-    snprintf(msg, sizeof msg, "%s: need V, H, W >= 1 and V H W < 2^31", who);
-    return set_err(msg);
-  }
-  if (!depth || !c2w || !focal || !center) { snprintf(msg, sizeof msg, "%s: null argument", who); return set_err(msg); }
-  if (!(d_min <= d_max)) { snprintf(msg, sizeof msg, "%s: need d_min <= d_max", who); return set_err(msg); }
-  if (((uintptr_t)depth | (uintptr_t)c2w | (uintptr_t)focal | (uintptr_t)center) & 3) {
-    snprintf(msg, sizeof msg, "%s: float and int32 arrays must be 4-byte aligned", who);
-    return set_err(msg);
-  }
   return 0;
 }
 
@@ -387,7 +207,7 @@ extern "C" int lrf_tsdf_blocks_touch(const LrfTsdfBlocks* g, const float* depth,
   using namespace lrf;
   BlocksArgs a;
   if (blocks_check("lrf_tsdf_blocks_touch", g, false, a)) return 1;
-  if (blocks_check_frames("lrf_tsdf_blocks_touch", depth, cam2world, focal, center, V, H, W, d_min, d_max)) return 1;
+  if (tsdf_check_frames("lrf_tsdf_blocks_touch", depth, cam2world, focal, center, V, H, W, d_min, d_max)) return 1;
   const long long n_px = (long long)V * H * W;
   hipLaunchKernelGGL(k_blocks_touch, dim3((unsigned)((n_px + BLK_NT - 1) / BLK_NT)), dim3(BLK_NT), 0,
                      reinterpret_cast<hipStream_t>(stream), a, depth, cam2world, focal, center, H, W, n_px, d_min, d_max);
@@ -433,7 +253,7 @@ extern "C" int lrf_tsdf_blocks_integrate(const LrfTsdfBlocks* g, const float* de
   using namespace lrf;
   BlocksArgs a;
   if (blocks_check("lrf_tsdf_blocks_integrate", g, true, a)) return 1;
-  if (blocks_check_frames("lrf_tsdf_blocks_integrate", depth, cam2world, focal, center, V, H, W, d_min, d_max)) return 1;
+  if (tsdf_check_frames("lrf_tsdf_blocks_integrate", depth, cam2world, focal, center, V, H, W, d_min, d_max)) return 1;
   if (!g->rgb != !rgb8) return set_err("lrf_tsdf_blocks_integrate: the volume's rgb and the frames' rgb8 go together");
   if (a.n_blocks == 0) return 0;                                     // no block: nothing to launch
   hipLaunchKernelGGL(k_blocks_fuse, dim3(a.n_blocks), dim3(BLK_PTS), 0, reinterpret_cast<hipStream_t>(stream), a, depth, rgb8,
@@ -455,15 +275,9 @@ extern "C" int lrf_mesh_extract_blocks(const LrfTsdfBlocks* g, float level, floa
   using namespace lrf;
   BlocksArgs b;
   if (blocks_check("lrf_mesh_extract_blocks", g, true, b)) return 1;
-  if (!vertices || !faces || !counts || !workspace) return set_err("lrf_mesh_extract_blocks: null argument");
-  if (!g->rgb != !rgb8_out) return set_err("lrf_mesh_extract_blocks: rgb and rgb8_out go together");
-  if (level != level) return set_err("lrf_mesh_extract_blocks: level must not be NaN");
-  if (!(min_weight > 0.0f)) return set_err("lrf_mesh_extract_blocks: min_weight must be > 0");
-  if (max_vertices < 0 || max_faces < 0 || max_vertices >= (1ll << 31) || max_faces >= (1ll << 31))
-    return set_err("lrf_mesh_extract_blocks: max_vertices and max_faces must lie in [0, 2^31)");
-  if (((uintptr_t)vertices | (uintptr_t)faces | (uintptr_t)workspace) & 3)
-    return set_err("lrf_mesh_extract_blocks: float and int32 arrays must be 4-byte aligned");
-  if ((uintptr_t)counts & 7) return set_err("lrf_mesh_extract_blocks: counts must be 8-byte aligned");
+  if (mesh_check_outputs("lrf_mesh_extract_blocks", g->rgb != nullptr, level, true, min_weight, max_vertices, max_faces, vertices,
+                         rgb8_out, faces, counts, workspace))
+    return 1;
   BlocksMeshArgs a;
   memset(&a, 0, sizeof(a));
   a.table = b.table; a.coords = b.coords; a.value = b.tsdf; a.weight = b.weight; a.rgb = b.rgb;

@@ -347,6 +347,18 @@ def _filtered(mesh, min_component_faces, min_component_fraction):
     return filter_components(mesh, min_component_faces, min_component_fraction)
 
 
+def _check_trunc_device(name, trunc, device):
+    """The constructors' tail of checks -> (trunc, torch.device); the refusal names the class."""
+    trunc_f = float(trunc)
+    if not (trunc_f > 0 and math.isfinite(trunc_f)):
+        raise ValueError(f"trunc must be a finite number > 0, got {trunc}")
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise NativeError(f"localrf_amd.mesh: a {name} on {dev}; the integration can run only on an AMD GPU (HIP "
+                          "kernels). There is no CPU fallback.")
+    return trunc_f, dev
+
+
 class TsdfVolume:
     """A truncated signed-distance volume on the device: tsdf [Nz,Ny,Nx] (starts at 1), weight [Nz,Ny,Nx] (starts at 0: the
     number of frames that saw the point) and, with colours, rgb [Nz,Ny,Nx,3] in [0, 1] (starts at 0).  dims = (Nx, Ny, Nz);
@@ -354,13 +366,7 @@ class TsdfVolume:
 
     def __init__(self, origin, voxel, dims, trunc, device, colours=True):
         self.origin, self.voxel, self.dims = _check_lattice(origin, voxel, dims)
-        self.trunc = float(trunc)
-        if not (self.trunc > 0 and math.isfinite(self.trunc)):
-            raise ValueError(f"trunc must be a finite number > 0, got {trunc}")
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise NativeError(f"localrf_amd.mesh: a TsdfVolume on {dev}; the integration can run only on an AMD GPU (HIP kernels). "
-                              "There is no CPU fallback.")
+        self.trunc, dev = _check_trunc_device("TsdfVolume", trunc, device)
         Nx, Ny, Nz = self.dims
         self.tsdf = torch.ones(Nz, Ny, Nx, dtype=torch.float32, device=dev)
         self.weight = torch.zeros(Nz, Ny, Nx, dtype=torch.float32, device=dev)
@@ -432,13 +438,7 @@ class SparseTsdfVolume:
         self.blocks = _check_blocks(blocks)
         self.dims = tuple(BLOCK * b for b in self.blocks)
         self.origin, self.voxel, _ = _check_lattice(origin, voxel, (1, 1, 1))
-        self.trunc = float(trunc)
-        if not (self.trunc > 0 and math.isfinite(self.trunc)):
-            raise ValueError(f"trunc must be a finite number > 0, got {trunc}")
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise NativeError(f"localrf_amd.mesh: a SparseTsdfVolume on {dev}; the integration can run only on an AMD GPU (HIP "
-                              "kernels). There is no CPU fallback.")
+        self.trunc, dev = _check_trunc_device("SparseTsdfVolume", trunc, device)
         Bx, By, Bz = self.blocks
         self.colours = bool(colours)
         self.marks = torch.zeros(Bz, By, Bx, dtype=torch.uint8, device=dev)
