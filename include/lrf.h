@@ -751,6 +751,37 @@ size_t lrf_mesh_filter_workspace_bytes(int64_t Nv, int64_t Nf);
 int lrf_mesh_filter(const LrfMeshFilter* m, int32_t threshold, float* vertices_out, uint8_t* rgb8_out /* nullable */,
                     int32_t* faces_out, int64_t* counts /* device [3] */, void* workspace, void* stream);
 
+/* An indexed triangle mesh simplified by uniform vertex clustering (csrc/lrf_mesh_simplify.inl states the semantics and the
+ * kernels): the vertices of one cell of a uniform grid of edge `cell`, anchored at `origin`, become one vertex at their mean,
+ * faces follow their vertices, faces that collapse are dropped and, with dedupe, so are all but the first of the faces that
+ * have become equal.  Integer sums, fp64 operations each rounded on its own and an order-independent choice among duplicates:
+ * every call leaves the same bytes on every run.  No sort, no floating-point atomics, no loop that waits on another lane.
+ * lrf_mesh_simplify_bounds: out (device int32 [7]) = lo[3], hi[3], the per-axis minimum and maximum of the vertices' cell
+ * indices floor((v - origin) / cell), and a flag word whose bit 0 says that some vertex is bad -- a coordinate that is not finite
+ * or a cell index outside (-2^30, 2^30) --; bad vertices enter neither bound.  origin: HOST array of 3 doubles.  Two launches.
+ * lrf_mesh_simplify: the box lo, dims = hi - lo + 1 of the call above (cells = dims[0] dims[1] dims[2] < 2^31).  vertices_out
+ * [Nv,3], rgb8_out [Nv,3] (nullable, with rgb8) and faces_out [Nf,3] (null allowed when Nf = 0) must hold the input's rows.
+ * counts (device int64 [5]) = vertices out, faces out, occupied cells, degenerate faces, duplicate faces; counts[1] = -1 when a
+ * face held an index outside [0, Nv) (such a face is never dereferenced), counts[0] = -1 when a vertex was bad or outside the
+ * box (never used as an index): the outputs then mean nothing.  Twelve launches (eleven without dedupe, five -- and an empty
+ * mesh -- with Nf = 0: no face kernel), no host synchronisation.  workspace: lrf_mesh_simplify_workspace_bytes(Nv, Nf, cells)
+ * bytes (0 for refused arguments), 8-byte aligned.
+ * Refused before any launch: null or misaligned pointers (float and int32 arrays 4 bytes; counts and workspace 8), Nv < 1,
+ * Nf < 0, Nv or Nf >= 2^31, rgb8 without rgb8_out or the reverse, a dims entry < 1, cells >= 2^31, a box outside (-2^30, 2^30),
+ * a non-finite origin, a cell that is not finite and positive. */
+typedef struct LrfMeshSimplify {
+  const float* vertices; const uint8_t* rgb8 /* nullable */; const int32_t* faces;
+  int64_t Nv, Nf;
+  double origin[3], cell;
+  int32_t lo[3], dims[3];
+  int32_t dedupe, reserved;
+} LrfMeshSimplify;
+int lrf_mesh_simplify_bounds(const float* vertices, int64_t Nv, const double* origin /* host [3] */, double cell,
+                             int32_t* out /* device [7] */, void* stream);
+size_t lrf_mesh_simplify_workspace_bytes(int64_t Nv, int64_t Nf, int64_t cells);
+int lrf_mesh_simplify(const LrfMeshSimplify* m, float* vertices_out, uint8_t* rgb8_out /* nullable */, int32_t* faces_out,
+                      int64_t* counts /* device [5] */, void* workspace, void* stream);
+
 /* Depth quantiles of a ray: the distance at which its accumulated weight first reaches q; q = 0.5 is the median depth, which
  * always lies on a surface the ray met (csrc/lrf_quantile.inl states the arithmetic: fp32 without contraction, one fixed
  * summation order per ray).  With C_i the inclusive prefix sum of the weights lrf_render_fwd leaves in weight_out and i* the

@@ -143,6 +143,12 @@ class LrfMeshFilter(C.Structure):
                 ("Nv", C.c_int64), ("Nf", C.c_int64)]
 
 
+class LrfMeshSimplify(C.Structure):
+    _fields_ = [("vertices", _f), ("rgb8", C.c_void_p), ("faces", C.c_void_p), ("Nv", C.c_int64), ("Nf", C.c_int64),
+                ("origin", C.c_double * 3), ("cell", C.c_double), ("lo", C.c_int32 * 3), ("dims", C.c_int32 * 3),
+                ("dedupe", C.c_int32), ("reserved", C.c_int32)]
+
+
 class LrfTsdfBlocks(C.Structure):
     _fields_ = [("marks", C.c_void_p), ("table", C.c_void_p), ("coords", C.c_void_p), ("tsdf", _f), ("weight", _f), ("rgb", _f),
                 ("Bx", C.c_int32), ("By", C.c_int32), ("Bz", C.c_int32), ("n_blocks", C.c_int32),
@@ -266,6 +272,9 @@ SYMBOLS = {
     "lrf_mesh_filter_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
     "lrf_mesh_filter": (C.c_int, [C.POINTER(LrfMeshFilter), C.c_int32, _f, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p]),
+    "lrf_mesh_simplify_bounds": (C.c_int, [_f, C.c_int64, C.POINTER(C.c_double), C.c_double, C.c_void_p, C.c_void_p]),
+    "lrf_mesh_simplify_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64]),
+    "lrf_mesh_simplify": (C.c_int, [C.POINTER(LrfMeshSimplify), _f, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "lrf_density_gradient": (C.c_int, [C.POINTER(LrfField), _f, C.c_int64, _f, _f, C.c_void_p]),
     "lrf_normals_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "lrf_render_normals": (C.c_int, [C.POINTER(LrfField), _f, _f, C.c_int32, C.c_int32, C.c_uint32, C.c_float, _f, C.c_int32,

@@ -7,6 +7,7 @@ lrf_tsdf_integrate and lrf_mesh_extract; csrc/lrf_tsdf_blocks.inl through lrf_ts
   extract_mesh(values, origin, voxel, level, ...)  marching tetrahedra of any [Nz,Ny,Nx] device tensor
   components(faces, n_vertices)                    connected-component labels and sizes of an indexed mesh (csrc/lrf_mesh_clean.inl)
   filter_components(mesh, min_faces, min_fraction) the mesh without its small components, order and bytes preserved
+  simplify(mesh, cell, origin)                     the mesh with the vertices of every grid cell merged into one (csrc/lrf_mesh_simplify.inl)
   scene_mesh(local_tensorfs, W, H, voxel=...)      novel_views.render_poses in batches, each integrated and dropped, then extract
   pointcloud.write_ply(path, vertices, rgb8, faces=faces) writes the result
 
@@ -339,12 +340,118 @@ def filter_components(mesh, min_faces=0, min_fraction=0.0, max_rounds=64):
     return out
 
 
-def _filtered(mesh, min_component_faces, min_component_fraction):
-    """extract's tail: the mesh itself with both options at their defaults -- nothing new is launched --, else
-    filter_components of it."""
-    if min_component_faces == 0 and min_component_fraction == 0.0:
-        return mesh
-    return filter_components(mesh, min_component_faces, min_component_fraction)
+def _check_cell(cell, what="cell"):
+    try:
+        ok = not isinstance(cell, bool) and math.isfinite(float(cell)) and float(cell) > 0
+    except (TypeError, ValueError, OverflowError):
+        ok = False
+    if not ok:
+        raise ValueError(f"{what} must be a finite number > 0, got {cell!r}")
+    return float(cell)
+
+
+def _check_anchor(origin):
+    try:
+        o = np.asarray(origin.detach().cpu() if torch.is_tensor(origin) else origin, dtype=np.float64).reshape(-1)
+    except (TypeError, ValueError):
+        o = np.zeros(0)
+    if o.size != 3 or not np.isfinite(o).all():
+        raise ValueError(f"origin must hold 3 finite values, got {origin!r}")
+    return tuple(float(x) for x in o)
+
+
+def _check_simplify_cell(simplify_cell):
+    """extract's option: None, or a cell edge."""
+    return None if simplify_cell is None else _check_cell(simplify_cell, "simplify_cell")
+
+
+def simplify(mesh, cell, origin=(0.0, 0.0, 0.0), dedupe=True, max_bytes=1 << 30):
+    """The mesh (the dict of the module docstring) simplified by uniform vertex clustering (csrc/lrf_mesh_simplify.inl states
+    every rule): the vertices that fall into one cell of the grid of edge `cell` anchored at `origin` become one vertex at
+    their mean position and mean colour; every face index becomes its vertex's cluster; a face that has lost a corner is
+    dropped; with dedupe, of the faces that have become equal (up to rotation; a mirrored face is another face) the one that
+    came first stays.  Clusters are ordered by cell (x fastest), only those a surviving face holds are emitted, surviving
+    faces keep their order, and each starts at its smallest index.  A mesh without faces gives the empty mesh.  Manifoldness
+    is not preserved.  The output bytes are a fixed function of the input -- integer sums, fp64 operations rounded one by
+    one, the smallest face index per key -- and do not depend on the order of the input's vertices.
+    Two read-backs: the 7 words of the bounds pass (a vertex that is not finite, or more than 2^30 cells from the origin,
+    raises ValueError; so does a cell box of 2^31 cells or more, or one whose workspace exceeds max_bytes: a larger cell is
+    needed), then the 5 counts (a face index outside [0, Nv) is never dereferenced and raises ValueError); the output buffers
+    are allocated at the input's sizes and sliced.  Returns a new mesh dict -- every other entry of the input is carried over
+    -- with "simplify": the Python values cell, origin, box (lo, dims: the cell box of the input), occupied (cells that hold
+    a vertex), degenerate_faces and duplicate_faces."""
+    v, f, c, Nv, Nf = _check_mesh(mesh)
+    cell = _check_cell(cell)
+    origin = _check_anchor(origin)
+    if not isinstance(dedupe, (bool, np.bool_)):
+        raise ValueError(f"dedupe must be True or False, got {dedupe!r}")
+    try:
+        ok = not isinstance(max_bytes, bool) and int(max_bytes) == max_bytes and int(max_bytes) >= 0
+    except (TypeError, ValueError, OverflowError):
+        ok = False
+    if not ok:
+        raise ValueError(f"max_bytes must be an integer >= 0, got {max_bytes!r}")
+    max_bytes = int(max_bytes)
+    N.require_gpu(v, "vertices", "the mesh simplification")
+    N.require_gpu(f, "faces", "the mesh simplification")
+    if c is not None:
+        N.require_gpu(c, "rgb8", "the mesh simplification")
+    dev = v.device
+    if f.device != dev or (c is not None and c.device != dev):
+        raise ValueError("vertices, faces and rgb8 must live on the same device")
+    v, f = v.detach().contiguous(), f.detach().contiguous()
+    c = None if c is None else c.contiguous()
+    out = dict(mesh)
+    info = {"cell": cell, "origin": origin, "box": {"lo": (0, 0, 0), "dims": (0, 0, 0)}, "occupied": 0, "degenerate_faces": 0,
+            "duplicate_faces": 0}
+    if Nv == 0:
+        out.update(vertices=v, faces=f, rgb8=c, counts=(0, 0), simplify=info)
+        return out
+    o3 = (C.c_double * 3)(*origin)
+    words = torch.empty(7, dtype=torch.int32, device=dev)
+    N.launch("lrf_mesh_simplify_bounds", dev, v.data_ptr(), Nv, o3, cell, words.data_ptr(), guard=True)
+    words = words.tolist()                                          # read-back one
+    if words[6]:
+        raise ValueError(f"vertices holds a value that is not finite or lies 2^30 cells of {cell} or more from origin {origin}")
+    lo, dims = tuple(words[:3]), tuple(h - l + 1 for l, h in zip(words[:3], words[3:6]))
+    cells = dims[0] * dims[1] * dims[2]
+    box = f"the cell box {dims[0]} x {dims[1]} x {dims[2]} from {lo}"
+    if cells > _INT32:
+        raise ValueError(f"{box} holds {cells} cells; a simplification takes fewer than 2^31: a larger cell is needed")
+    need = int(N.lib().lrf_mesh_simplify_workspace_bytes(Nv, Nf, cells))
+    if need == 0:
+        raise NativeError(f"lrf_mesh_simplify: refused shape {(Nv, Nf, cells)}")
+    if need > max_bytes:
+        raise ValueError(f"{box} takes a workspace of {need} bytes; max_bytes is {max_bytes}: a larger cell is needed")
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    vo, fo = torch.empty_like(v), torch.empty_like(f)
+    co = None if c is None else torch.empty_like(c)
+    counts = torch.empty(5, dtype=torch.int64, device=dev)
+    a = N.LrfMeshSimplify()
+    a.vertices, a.rgb8, a.faces = v.data_ptr(), None if c is None else c.data_ptr(), f.data_ptr() if Nf else None
+    a.Nv, a.Nf, a.cell, a.dedupe = Nv, Nf, cell, int(bool(dedupe))
+    for k in range(3):
+        a.origin[k], a.lo[k], a.dims[k] = origin[k], lo[k], dims[k]
+    N.launch("lrf_mesh_simplify", dev, C.byref(a), vo.data_ptr(), None if co is None else co.data_ptr(),
+             fo.data_ptr() if Nf else None, counts.data_ptr(), ws.data_ptr(), guard=True)
+    nv, nf, occupied, degenerate, duplicate = (int(x) for x in counts.tolist())    # read-back two (it also orders ws's release)
+    if nf < 0:
+        raise ValueError(f"faces holds an index outside [0, {Nv}): the mesh has {Nv} vertices")
+    if nv < 0:
+        raise ValueError(f"vertices changed between the bounds pass and the simplification: one lies outside {box}")
+    info.update(box={"lo": lo, "dims": dims}, occupied=occupied, degenerate_faces=degenerate, duplicate_faces=duplicate)
+    out.update(vertices=vo[:nv], faces=fo[:nf], rgb8=None if co is None else co[:nv], counts=(nv, nf), simplify=info)
+    return out
+
+
+def _filtered(mesh, min_component_faces, min_component_fraction, simplify_cell=None, origin=(0.0, 0.0, 0.0)):
+    """extract's tail: the mesh itself with every option at its default -- nothing new is launched --, else
+    filter_components of it, then (the floaters having been judged at full resolution) simplify of that."""
+    if not (min_component_faces == 0 and min_component_fraction == 0.0):
+        mesh = filter_components(mesh, min_component_faces, min_component_fraction)
+    if simplify_cell is not None:
+        mesh = simplify(mesh, simplify_cell, origin=origin)
+    return mesh
 
 
 def _check_trunc_device(name, trunc, device):
@@ -397,15 +504,17 @@ class TsdfVolume:
         return self
 
     def extract(self, level=0.0, min_weight=1.0, max_vertices=None, max_faces=None, *, min_component_faces=0,
-                min_component_fraction=0.0):
+                min_component_fraction=0.0, simplify_cell=None):
         """The mesh of the surface tsdf = level over the cells every corner of which at least min_weight frames saw:
         extract_mesh(self.tsdf, ..., weight=self.weight, rgb=self.rgb); see there for the capacities and the read-backs.
         With min_component_faces or min_component_fraction above 0 the result is filter_components(that mesh, min_faces,
-        min_fraction): its small connected components are gone."""
+        min_fraction): its small connected components are gone.  With simplify_cell (a cell edge in world units) the result
+        of that is simplify(mesh, simplify_cell, origin=self.origin): the grid is anchored at the volume's origin."""
         level, min_weight = _check_extract(level, min_weight, max_vertices, max_faces)
         keep = _check_keep(min_component_faces, min_component_fraction, tuple(_NO_FILTER))
+        simplify_cell = _check_simplify_cell(simplify_cell)
         return _filtered(_extract(self.tsdf, self.weight, self.rgb, self.origin, self.voxel, self.dims, level, min_weight,
-                                  max_vertices, max_faces), *keep)
+                                  max_vertices, max_faces), *keep, simplify_cell, self.origin)
 
 
 BLOCK = 8                                      # lattice points per block edge
@@ -547,14 +656,15 @@ class SparseTsdfVolume:
         return self
 
     def extract(self, level=0.0, min_weight=1.0, max_vertices=None, max_faces=None, *, min_component_faces=0,
-                min_component_fraction=0.0):
+                min_component_fraction=0.0, simplify_cell=None):
         """The mesh of the surface tsdf = level over the cells every corner of which is stored and was seen by at least
         min_weight frames.  Vertices come in pool order, then (z, y, x, edge) inside the block; faces in the pool order of
         the cell's lowest corner, then (z, y, x) inside the block, then (tetrahedron, triangle).  Capacities and read-backs as
-        extract_mesh has them.  With zero blocks nothing is launched and the mesh is empty.  min_component_faces and
-        min_component_fraction as TsdfVolume.extract takes them."""
+        extract_mesh has them.  With zero blocks nothing is launched and the mesh is empty.  min_component_faces,
+        min_component_fraction and simplify_cell as TsdfVolume.extract takes them."""
         level, min_weight = _check_extract(level, min_weight, max_vertices, max_faces)
         keep = _check_keep(min_component_faces, min_component_fraction, tuple(_NO_FILTER))
+        simplify_cell = _check_simplify_cell(simplify_cell)
         dev = self.table.device
         if not self.n_blocks:
             return {"vertices": torch.empty(0, 3, dtype=torch.float32, device=dev), "faces": torch.empty(0, 3, dtype=torch.int32, device=dev),
@@ -566,7 +676,7 @@ class SparseTsdfVolume:
             N.launch("lrf_mesh_extract_blocks", dev, C.byref(a), level, min_weight, cap_v, cap_f, v.data_ptr(),
                      None if c is None else c.data_ptr(), f.data_ptr(), counts.data_ptr(), ws.data_ptr(), guard=True)
 
-        return _filtered(_sized_extract(dev, self.colours, launch, max_vertices, max_faces), *keep)
+        return _filtered(_sized_extract(dev, self.colours, launch, max_vertices, max_faces), *keep, simplify_cell, self.origin)
 
     def to_dense(self):
         """(tsdf, weight, rgb or None, stored) as [8Bz,8By,8Bx] tensors of the virtual lattice (rgb [...,3]; stored: bool, the
@@ -586,7 +696,7 @@ class SparseTsdfVolume:
 
 
 _MESH_KEYS = ("depth_range", "level", "min_weight", "max_vertices", "max_faces", "colours", "frames_per_call",
-              "min_component_faces", "min_component_fraction")
+              "min_component_faces", "min_component_fraction", "simplify_cell")
 
 
 def _lattice_of_box(lo, hi, voxel):
@@ -608,8 +718,9 @@ def scene_mesh(local_tensorfs, W, H, voxel, bounds=None, poses=None, trunc=None,
     side: one more render pass and one more read-back of the box.  trunc=None means 3 * voxel: a convenience, not a measured
     optimum -- it should exceed the depth noise of the scene.  options: depth_range, level, min_weight, max_vertices,
     max_faces, colours (default True), frames_per_call, min_component_faces and min_component_fraction (both default 0: with
-    either above 0 the extracted mesh goes through filter_components, which drops its small connected components) and
-    render_poses' test_frames, frame_indices, floater_thresh, chunk.
+    either above 0 the extracted mesh goes through filter_components, which drops its small connected components),
+    simplify_cell (default None; a cell edge in world units sends the mesh, after that filter, through simplify on a grid
+    anchored at the volume's origin) and render_poses' test_frames, frame_indices, floater_thresh, chunk.
     A volume above max_bytes raises ValueError before it is allocated and, with bounds given, before anything is rendered.
     depth="median" integrates the median depth of the same frames (depth_quantiles.median_depth: one more render pass per
     batch) instead of render_poses' expected depth, which carves a phantom sheet between two surfaces a ray sees; the colours
@@ -639,6 +750,7 @@ def scene_mesh(local_tensorfs, W, H, voxel, bounds=None, poses=None, trunc=None,
                                        options.get("max_faces"))
     colours = bool(options.get("colours", True))
     keep = _check_keep(options.get("min_component_faces", 0), options.get("min_component_fraction", 0.0), tuple(_NO_FILTER))
+    simplify_cell = _check_simplify_cell(options.get("simplify_cell"))
     per_call = options.get("frames_per_call", 8)
     if int(per_call) != per_call or int(per_call) < 1:
         raise ValueError(f"frames_per_call must be an integer >= 1, got {per_call!r}")
@@ -704,6 +816,6 @@ def scene_mesh(local_tensorfs, W, H, voxel, bounds=None, poses=None, trunc=None,
     for p, dmap, rgb8 in batches():
         vol.integrate(dmap, p, focal, center, rgb=rgb8, depth_range=depth_range)
     mesh = vol.extract(level, min_weight, options.get("max_vertices"), options.get("max_faces"), min_component_faces=keep[0],
-                       min_component_fraction=keep[1])
+                       min_component_fraction=keep[1], simplify_cell=simplify_cell)
     mesh["volume"] = vol
     return mesh
