@@ -19,6 +19,14 @@ void    lrf_debug_set_dump(float* buf);
 void    lrf_debug_march_phases(uint64_t* buf);
 void    lrf_debug_set_lds_lines(int on);          /* k_march: density lines staged in LDS (default on when they fit) */
 void    lrf_debug_set_pipe_chunk(int rays);       /* rays per chunk of lrf_render_fwd's two-stream large-batch mode (default 16384; batches of at least two chunks); 0: one pass over the whole batch.  Changes lrf_workspace_bytes: set it before sizing a workspace */
+void    lrf_debug_set_march_rays(int rays);       /* k_march: 4, 8 or 16 rays per workgroup where that many fit in LDS with the density lines (else, and with 0: the default choice); k_shade3 reads its group sums at the same size */
+void    lrf_debug_set_lds_toff(int on);           /* k_shade3: tile offsets built inside the kernel from k_march's group sums (default on when they fit in LDS); 0 = k_scan_tiles_n first and global offsets, at every batch size */
+/* tile_range_fill + tile_range_finish (the prologue of k_shade3) in a kernel of its own: ncomp [R] shaded counts (device), G in {4, 8, 16} rays per
+ * group, nb workgroups -> gsum [ceil(R / G)] (scratch), ranges [nb][4] = {ra, rb, T0, T1} of workgroup b, toff_out [nb][R + 1]
+ * and nc_out [nb][R]: the offsets of rays ra .. rb and the counts of rays ra .. rb - 1 as workgroup b holds them; other entries
+ * are left as the caller filled them.  R up to about 10000 (64 KB of LDS). */
+int     lrf_debug_tile_ranges(const int32_t* ncomp, int32_t R, int32_t G, int32_t nb, int32_t* gsum, int32_t* ranges,
+                              int32_t* toff_out, int32_t* nc_out, void* stream);
 void    lrf_debug_set_scene_fuse(int on);         /* lrf_scene_fwd: several fields per march / colour launch (default on); 0 = field by field */
 void    lrf_debug_set_bwd_overlap(int on);        /* lrf_render_bwd: two branches on two streams (default on); 1 + 2 * (n + 1): k_wgrad_w2w3 on the caller's stream (n > 0, default) or on the side stream behind the density scatter (n = 0) */
 void    lrf_debug_set_train_fwd_engine(int bits); /* 8: plane and line gradients by separate scatter kernels; 16: the gradient scatters with fp32 compare-and-swap adds (k_scatter_plane, rounds 2-5) instead of 64-bit fixed point (k_scatter_fix); 256: fixed point for the density tensors only (default: the appearance tensors too where their accumulators fit in LDS, lines up to 479 cells); 1024: no four-channel sweeps (lines of 480 .. 640 cells: the appearance tensors through the compare-and-swap kernel, as before); 512: k_wgrad_w2w3 in its single-buffered 128-row form (rounds 4-5) instead of the double-buffered 64-row one; 32 / 64 / 128: k_train_dgrad3 + k_train_app3 without their row stores / position gradient and X / dz1 products (timing experiments, wrong results) */

@@ -1883,7 +1883,7 @@ extern "C" int lrf_render_fwd_train(const LrfField* f, const float* rays, const 
   const Workspace& w = b.fw;
   rays = sort_rays_if_asked(d, rays, R, flags, w, st);
   d.rdir = w.rdir;
-  launch_march(d, rays, z, R, S, flags, 0.0f, depth, w.acc, nullptr, w.ncomp, w.cidx, w.cw, b.feat, st);
+  launch_march(d, rays, z, R, S, flags, 0.0f, depth, w.acc, nullptr, w.ncomp, w.gsum, w.cidx, w.cw, b.feat, st);
   LRF_HIP(launch_shade_save(d, rays, z, S, R, flags, w, b, rgb, st));
   LRF_HIP(hipGetLastError());
   return 0;
@@ -2053,7 +2053,7 @@ static int bwd_forward_rows(BwdPlan& P, hipStream_t s) {
   const BwdWorkspace& b = P.b; const Workspace& w = b.fw;
   if (P.flags & LRF_FLAG_ROWS_SAVED) { if (P.sort) { P.d.perm = w.perm; P.rays = w.rays_s; } return 0; }
   P.rays = sort_rays_if_asked(P.d, P.rays, P.R, P.flags, w, s);
-  launch_march(P.d, P.rays, P.z, P.R, P.S, P.flags, 0.0f, b.depth, w.acc, nullptr, w.ncomp, w.cidx, w.cw, b.feat, s);
+  launch_march(P.d, P.rays, P.z, P.R, P.S, P.flags, 0.0f, b.depth, w.acc, nullptr, w.ncomp, w.gsum, w.cidx, w.cw, b.feat, s);
   LRF_HIP(launch_shade_save(P.d, P.rays, P.z, P.S, P.R, P.flags, w, b, b.rgb, s));
   return 0;
 }

@@ -261,6 +261,8 @@ __device__ __forceinline__ const DField& field_of(const MultiF& m, int k) { retu
 // Pass B runs the in-chunk scans of MARCH_G chunks together (see there).
 constexpr int MARCH_G = 8;
 constexpr int MARCH_SR = 3;         // rounds of the line staging whose loads are issued together
+constexpr int MARCH_LDS_TAIL = 16;  // bytes of dynamic LDS behind alpha slices, lines and z: the combine word of gsum
+constexpr int MARCH_TILE = 32;      // samples per tile of the colour kernel (ITEM3, lrf_shade3.inl): the unit of gsum
 // TIMED (debug, lrf_debug_march_phases): __builtin_readcyclecounter() totals per wave -> dump[ray][4] = {line / z staging
 // with its barrier, pass A, pass B, epilogue}; the production kernels carry none of it.
 // ZLDS: the sample schedule z[0..S) sits in LDS behind the lines (it is the same 4 * S bytes for every ray: pass A read
@@ -270,7 +272,7 @@ __device__ __forceinline__ void march_body(
     const typename FieldArg<MULTI>::type& fin, const float* __restrict__ rays, const float* __restrict__ z, int R, int S,
     uint32_t flags, float floater,
     float* __restrict__ depth, float* __restrict__ acc_ws, float* __restrict__ w_all,
-    int* __restrict__ ncomp, uint16_t* __restrict__ cidx, float* __restrict__ cw,
+    int* __restrict__ ncomp, int* __restrict__ gsum, uint16_t* __restrict__ cidx, float* __restrict__ cw,
     float* __restrict__ feat_out, const bool zlds) {
   extern __shared__ float s_alpha_all[];
   unsigned long long tk[4] = {0, 0, 0, 0}, tlast = 0;
@@ -329,7 +331,11 @@ __device__ __forceinline__ void march_body(
     if (zi1 < S) s_z[zi1] = z1;
     for (int i = zi1 + blockDim.x; i < S; i += blockDim.x) s_z[i] = z[i];
   }
-  if (LDSL || zlds) __syncthreads();
+  // the workgroup's tile total (gsum): waves done << 20 | 32-sample tiles, in the 16 bytes launch_march adds behind everything
+  // else (a static __shared__ word would move the dynamic part off its 16-byte alignment: the lines are read as float4)
+  unsigned* s_gcomb = reinterpret_cast<unsigned*>(s_z + (zlds ? S : 0));
+  if (gsum && threadIdx.x == 0) *s_gcomb = 0u;
+  if (LDSL || zlds || gsum) __syncthreads();
   LRF_MTICK(0);
   if (ray >= R) return;
   float* s_alpha = s_alpha_all + (size_t)wave * S;
@@ -465,6 +471,14 @@ __device__ __forceinline__ void march_body(
     acc_ws[ray] = acc;
     ncomp[ray] = nsh;
     if (f.rdir) *reinterpret_cast<float4*>(f.rdir + (size_t)ray * 4) = make_float4(dh[0], dh[1], dh[2], dn);
+    if (gsum) {
+      // gsum[lb] = the 32-sample tiles of this workgroup's rays (k_shade3 scans these sums instead of every ray's count).
+      // One LDS add per wave, no barrier behind the early return above: the wave that finds all the others' adds
+      // in front of its own writes the sum (at most 16 rays x 128 tiles: the count of waves sits above bit 20).
+      const unsigned tiles = (unsigned)((nsh + MARCH_TILE - 1) / MARCH_TILE);
+      const unsigned old = atomicAdd(s_gcomb, (1u << 20) | tiles);
+      if ((int)(old >> 20) + 1 == min(nw, R - lb * nw)) gsum[lb] = (int)((old & 0xfffffu) + tiles);
+    }
   }
   LRF_MTICK(3);
   if (TIMED && f.dump && lane == 0) {
@@ -480,9 +494,10 @@ __global__ __launch_bounds__(1024) void k_march(
     typename FieldArg<MULTI>::type fin, const float* __restrict__ rays, const float* __restrict__ z, int R, int S,
     uint32_t flags, float floater,
     float* __restrict__ depth, float* __restrict__ acc_ws, float* __restrict__ w_all,
-    int* __restrict__ ncomp, uint16_t* __restrict__ cidx, float* __restrict__ cw,
+    int* __restrict__ ncomp, int* __restrict__ gsum /* [workgroups] tiles of each workgroup's rays; or null */,
+    uint16_t* __restrict__ cidx, float* __restrict__ cw,
     float* __restrict__ feat_out /* [R,S] density feature, -inf where not evaluated; or null */, int zlds) {
-  march_body<LDSL, MULTI, false>(fin, rays, z, R, S, flags, floater, depth, acc_ws, w_all, ncomp, cidx, cw, feat_out, zlds != 0);
+  march_body<LDSL, MULTI, false>(fin, rays, z, R, S, flags, floater, depth, acc_ws, w_all, ncomp, gsum, cidx, cw, feat_out, zlds != 0);
 }
 // the same with the phase clocks (fin.dump: [R][4] uint64)
 template <bool LDSL>
@@ -490,9 +505,9 @@ __global__ __launch_bounds__(1024) void k_march_timed(
     DField fin, const float* __restrict__ rays, const float* __restrict__ z, int R, int S,
     uint32_t flags, float floater,
     float* __restrict__ depth, float* __restrict__ acc_ws, float* __restrict__ w_all,
-    int* __restrict__ ncomp, uint16_t* __restrict__ cidx, float* __restrict__ cw,
+    int* __restrict__ ncomp, int* __restrict__ gsum, uint16_t* __restrict__ cidx, float* __restrict__ cw,
     float* __restrict__ feat_out, int zlds) {
-  march_body<LDSL, false, true>(fin, rays, z, R, S, flags, floater, depth, acc_ws, w_all, ncomp, cidx, cw, feat_out, zlds != 0);
+  march_body<LDSL, false, true>(fin, rays, z, R, S, flags, floater, depth, acc_ws, w_all, ncomp, gsum, cidx, cw, feat_out, zlds != 0);
 }
 
 // Exclusive prefix sum of per-ray tile counts: toff[r] = sum_{q<r} ceil(ncomp[q]/16),
@@ -986,6 +1001,7 @@ static DField make_dfield(const LrfField* f) {
 
 struct Workspace {
   int* toff; int* ncomp; float* acc; uint16_t* cidx; float* cw; float* part;
+  int* gsum;               // k_march -> k_shade3: 32-sample tiles of each march workgroup's rays (at most ceil(R / 4) of them)
   float* rdir;             // k_march -> k_shade3: unit direction and length per ray
   int* perm; float* rays_s;  // ray sorting: slot -> ray, sorted copy of the rays
   int pmax; size_t bytes;
@@ -1005,6 +1021,7 @@ static Workspace carve(void* ws, int R, int S) {
   w.rdir  = reinterpret_cast<float*>(p + off);     off += up256((size_t)R * 16);
   w.perm  = reinterpret_cast<int*>(p + off);       off += up256((size_t)R * 4);
   w.rays_s = reinterpret_cast<float*>(p + off);    off += up256((size_t)R * 24);
+  w.gsum  = reinterpret_cast<int*>(p + off);       off += up256((size_t)((R + 3) / 4) * 4);
   w.bytes = off;
   return w;
 }
@@ -1014,6 +1031,8 @@ static float* g_dump = nullptr;    // lrf_debug_set_dump: device buffer for the 
 static unsigned long long* g_march_dump = nullptr;   // lrf_debug_march_phases: device buffer [R][4] for the phase clocks of k_march_timed
 static int g_no_lds_lines = 0;     // lrf_debug_set_lds_lines(0): k_march reads its lines from global memory
 static int g_pipe_chunk = 16384;    // lrf_debug_set_pipe_chunk: rays per chunk of lrf_render_fwd's large-batch mode (0: one pass over the whole batch, as rounds 1-5)
+static int g_march_rays = 0;       // lrf_debug_set_march_rays: rays per k_march workgroup (4, 8, 16) where that many fit; 0: march_lds_rays' own choice
+static int g_no_lds_toff = 0;      // lrf_debug_set_lds_toff(0): k_shade3 behind k_scan_tiles_n (global tile offsets) at every batch size
 static int g_no_scene_fuse = 0;    // lrf_debug_set_scene_fuse(0): lrf_scene_fwd renders field by field (the tests compare the two forms)
 
 static int device_cus() {                 // of the current device (one process may drive several)
@@ -1109,13 +1128,19 @@ static const float* sort_rays_if_asked(DField& d, const float* rays, int R, uint
 static int march_lds_rays(const int32_t ll[3], int S) {
   if (g_no_lds_lines) return 0;
   const size_t lds_l = (size_t)(ll[0] + ll[1] + ll[2]) * LRF_CD * sizeof(float);
+  int first = 0;
   for (int cand = 4; cand <= 16; cand *= 2)
-    if (((size_t)cand * S * sizeof(float) + lds_l) * (16 / cand) <= 156 * 1024) return cand;
-  return 0;
+    if (((size_t)cand * S * sizeof(float) + lds_l) * (16 / cand) <= 156 * 1024) {
+      if (!first) first = cand;
+      if (cand == g_march_rays) return cand;               // (test hook: a larger workgroup than the smallest that fits)
+    }
+  return first;
 }
+// rays per k_march workgroup, with or without the lines in LDS: the unit of Workspace::gsum
+static int march_group_rays(const int32_t ll[3], int S) { const int nw = march_lds_rays(ll, S); return nw ? nw : 4; }
 // whether the schedule's S floats go into LDS too: the choice of march_lds_rays() stands, z joins where the same budget still
 // holds with it (300^3 at S = 512: (8 + 28.8 + 2 KB) x 4 = 155.2 KB; 500^3 at 576 and 640^3 at 738 fit as well); nw = 0 is
-// k_march<false>, four alpha slices inside the 64 KB every kernel may ask for
+// k_march<false>, four alpha slices (+ z) inside 64 KB; with MARCH_LDS_TAIL behind them the kernel is opted in for 64 KB + 16 B
 static bool march_lds_z(const int32_t ll[3], int S, int nw) {
   if (!nw) return (size_t)5 * S * sizeof(float) <= 64 * 1024;
   const size_t lds_l = (size_t)(ll[0] + ll[1] + ll[2]) * LRF_CD * sizeof(float);
@@ -1124,7 +1149,7 @@ static bool march_lds_z(const int32_t ll[3], int S, int nw) {
 // k_march launch: lines in LDS when the three of them (+ the alpha slices) leave four workgroups per CU.  mf (the fused
 // multi-field form) exists with the lines in LDS only: lrf_scene_fwd does not fuse when march_lds_rays() is 0.
 static void launch_march(const DField& d, const float* rays, const float* z, int R, int S, uint32_t flags, float floater,
-                         float* depth, float* acc, float* w_all, int* ncomp, uint16_t* cidx, float* cw, float* feat,
+                         float* depth, float* acc, float* w_all, int* ncomp, int* gsum, uint16_t* cidx, float* cw, float* feat,
                          hipStream_t st, const MultiF* mf = nullptr) {
   // 4 waves per SIMD either way: 4 / 2 / 1 workgroups of 4 / 8 / 16 rays per CU, whichever keeps
   // alpha slices + lines within the CU's 160 KB (300^3: 8 + 29 KB x 4; 500^3: 18 + 48 KB x 2; 640^3: 47 + 61 KB x 1)
@@ -1135,56 +1160,59 @@ static void launch_march(const DField& d, const float* rays, const float* z, int
   if (g_march_dump && !mf) {                               // test hook: phase clocks -> the dump buffer
     DField dt = d;
     dt.dump = reinterpret_cast<float*>(g_march_dump);
-    if (nw) hipLaunchKernelGGL(k_march_timed<true>, dim3((R + nw - 1) / nw), dim3(64 * nw), (size_t)nw * S * sizeof(float) + lds_l + lds_z, st,
-                               dt, rays, z, R, S, flags, floater, depth, acc, w_all, ncomp, cidx, cw, feat, zlds);
-    else    hipLaunchKernelGGL(k_march_timed<false>, dim3((R + 3) / 4), dim3(256), (size_t)4 * S * sizeof(float) + lds_z, st,
-                               dt, rays, z, R, S, flags, floater, depth, acc, w_all, ncomp, cidx, cw, feat, zlds);
+    if (nw) hipLaunchKernelGGL(k_march_timed<true>, dim3((R + nw - 1) / nw), dim3(64 * nw), (size_t)nw * S * sizeof(float) + lds_l + lds_z + MARCH_LDS_TAIL, st,
+                               dt, rays, z, R, S, flags, floater, depth, acc, w_all, ncomp, gsum, cidx, cw, feat, zlds);
+    else    hipLaunchKernelGGL(k_march_timed<false>, dim3((R + 3) / 4), dim3(256), (size_t)4 * S * sizeof(float) + lds_z + MARCH_LDS_TAIL, st,
+                               dt, rays, z, R, S, flags, floater, depth, acc, w_all, ncomp, gsum, cidx, cw, feat, zlds);
     return;
   }
   if (nw) {
-    const size_t lds = (size_t)nw * S * sizeof(float) + lds_l + lds_z;
+    const size_t lds = (size_t)nw * S * sizeof(float) + lds_l + lds_z + MARCH_LDS_TAIL;
     if (mf) {                                              // (the caller made sure that Rf is a multiple of 16 >= nw)
       hipLaunchKernelGGL((k_march<true, true>), dim3((R + nw - 1) / nw), dim3(64 * nw), lds, st,
-                         *mf, rays, z, R, S, flags, floater, depth, acc, w_all, ncomp, cidx, cw, feat, zlds);
+                         *mf, rays, z, R, S, flags, floater, depth, acc, w_all, ncomp, gsum, cidx, cw, feat, zlds);
       return;
     }
     hipLaunchKernelGGL(k_march<true>, dim3((R + nw - 1) / nw), dim3(64 * nw), lds, st,
-                       d, rays, z, R, S, flags, floater, depth, acc, w_all, ncomp, cidx, cw, feat, zlds);
+                       d, rays, z, R, S, flags, floater, depth, acc, w_all, ncomp, gsum, cidx, cw, feat, zlds);
   } else {
-    hipLaunchKernelGGL(k_march<false>, dim3((R + 3) / 4), dim3(256), (size_t)4 * S * sizeof(float) + lds_z, st,
-                       d, rays, z, R, S, flags, floater, depth, acc, w_all, ncomp, cidx, cw, feat, zlds);
+    hipLaunchKernelGGL(k_march<false>, dim3((R + 3) / 4), dim3(256), (size_t)4 * S * sizeof(float) + lds_z + MARCH_LDS_TAIL, st,
+                       d, rays, z, R, S, flags, floater, depth, acc, w_all, ncomp, gsum, cidx, cw, feat, zlds);
   }
 }
 
-// k_march's output -> colours: k_shade3 behind an in-kernel scan of the tile offsets when they fit in LDS beside the image,
-// behind k_scan_tiles_n otherwise (toff32: R + 1 ints).  sv == nullptr: the eval forward; else the training forward, which
+// k_march's output -> colours: k_shade3 with its tile offsets built in the kernel from k_march's group sums (w.gsum) when they
+// fit in LDS beside the image, behind k_scan_tiles_n otherwise (toff32: R + 1 ints).  sv == nullptr: the eval forward; else the training forward, which
 // also leaves the rows of SaveOut3 (and sv->toff16 must not be toff32).  dump: lrf_debug_set_dump's buffer (eval only).
 static void launch_shade3(DField d, const float* rays, const float* z, int R, int S, uint32_t flags, const Workspace& w,
                          int* toff32, float* rgb, float* acc_out, const SaveOut3* sv, float* dump, hipStream_t st) {
   const size_t lds_base = (size_t)W32_ALL_U4 * sizeof(uint4) + (size_t)S * sizeof(float);
   const size_t lds_toff = (size_t)(R + 1) * sizeof(int) + (size_t)R * sizeof(unsigned short) + 16;
-  const bool in_lds = lds_base + lds_toff + 64 <= 160 * 1024 - 256;
+  const int gsz = march_group_rays(d.ll, S);      // k_march left w.gsum at this many rays per entry
+  // in LDS: R + 1 offsets and R 16-bit counts (absolute ray index; a workgroup fills only its own window) beside image and z,
+  // and no more group sums than one workgroup holds in registers
+  const bool in_lds = !g_no_lds_toff && lds_base + lds_toff + 64 <= 160 * 1024 - 256 && (R + gsz - 1) / gsz <= 512 * TILE_GPT;
   const dim3 grid(device_cus()), block(512);
   if (sv) {
     if (in_lds) {
       hipLaunchKernelGGL((k_shade3<8, true, false, true>), grid, block, lds_base + lds_toff, st,
-                         d, rays, z, S, toff32, R, w.ncomp, w.cidx, w.cw, w.part, w.pmax, flags, w.acc, rgb, acc_out, *sv);
+                         d, rays, z, S, w.gsum, R, w.ncomp, w.cidx, w.cw, w.part, w.pmax, flags, w.acc, rgb, acc_out, *sv, gsz);
     } else {
       hipLaunchKernelGGL(k_scan_tiles_n<ITEM3>, dim3(1), dim3(1024), 0, st, w.ncomp, R, toff32);
       hipLaunchKernelGGL((k_shade3<8, false, false, true>), grid, block, lds_base, st,
-                         d, rays, z, S, toff32, R, w.ncomp, w.cidx, w.cw, w.part, w.pmax, flags, w.acc, rgb, acc_out, *sv);
+                         d, rays, z, S, toff32, R, w.ncomp, w.cidx, w.cw, w.part, w.pmax, flags, w.acc, rgb, acc_out, *sv, gsz);
     }
   } else if (in_lds && dump) {                    // test hook: phase timing, s_memtime totals -> the dump buffer
     d.dump = dump;
     hipLaunchKernelGGL((k_shade3<8, true, true>), grid, block, lds_base + lds_toff, st,
-                       d, rays, z, S, toff32, R, w.ncomp, w.cidx, w.cw, w.part, w.pmax, flags, w.acc, rgb, acc_out, SaveOut3{});
+                       d, rays, z, S, w.gsum, R, w.ncomp, w.cidx, w.cw, w.part, w.pmax, flags, w.acc, rgb, acc_out, SaveOut3{}, gsz);
   } else if (in_lds) {
     hipLaunchKernelGGL((k_shade3<8, true, false>), grid, block, lds_base + lds_toff, st,
-                       d, rays, z, S, toff32, R, w.ncomp, w.cidx, w.cw, w.part, w.pmax, flags, w.acc, rgb, acc_out, SaveOut3{});
+                       d, rays, z, S, w.gsum, R, w.ncomp, w.cidx, w.cw, w.part, w.pmax, flags, w.acc, rgb, acc_out, SaveOut3{}, gsz);
   } else {
     hipLaunchKernelGGL(k_scan_tiles_n<ITEM3>, dim3(1), dim3(1024), 0, st, w.ncomp, R, toff32);
     hipLaunchKernelGGL((k_shade3<8, false, false>), grid, block, lds_base, st,
-                       d, rays, z, S, toff32, R, w.ncomp, w.cidx, w.cw, w.part, w.pmax, flags, w.acc, rgb, acc_out, SaveOut3{});
+                       d, rays, z, S, toff32, R, w.ncomp, w.cidx, w.cw, w.part, w.pmax, flags, w.acc, rgb, acc_out, SaveOut3{}, gsz);
   }
 }
 
@@ -1194,7 +1222,7 @@ static void launch_shade3_multi(const MultiF& mf, const float* rays, const float
   const size_t lds_base = (size_t)W32_ALL_U4 * sizeof(uint4) + (size_t)S * sizeof(float);
   hipLaunchKernelGGL(k_scan_tiles_n<ITEM3>, dim3(1), dim3(1024), 0, st, w.ncomp, Rv, w.toff);
   hipLaunchKernelGGL((k_shade3m<8, false>), dim3(device_cus()), dim3(512), lds_base, st,
-                     mf, rays, z, S, w.toff, Rv, w.ncomp, w.cidx, w.cw, w.part, w.pmax, flags, w.acc, rgb, (float*)nullptr, SaveOut3{});
+                     mf, rays, z, S, w.toff, Rv, w.ncomp, w.cidx, w.cw, w.part, w.pmax, flags, w.acc, rgb, (float*)nullptr, SaveOut3{}, 0);
 }
 
 }  // namespace lrf
@@ -1231,6 +1259,8 @@ static hipError_t lds_opt_in() {
     {reinterpret_cast<const void*>(&k_march<true>), L160},
     {reinterpret_cast<const void*>(&k_march<true, true>), L160},
     {reinterpret_cast<const void*>(&k_march_timed<true>), L160},
+    {reinterpret_cast<const void*>(&k_march<false>), 64 * 1024 + MARCH_LDS_TAIL},       // four alpha slices of S = 4096 are 64 KB, + the combine word of gsum
+    {reinterpret_cast<const void*>(&k_march_timed<false>), 64 * 1024 + MARCH_LDS_TAIL},
     {reinterpret_cast<const void*>(&k_shade3<8, true, false>), L160 - 256},
     {reinterpret_cast<const void*>(&k_shade3<8, false, false>), L160 - 256},
     {reinterpret_cast<const void*>(&k_shade3<8, true, true>), L160 - 256},
@@ -1299,6 +1329,22 @@ void lrf_debug_march_phases(uint64_t* buf) { g_march_dump = reinterpret_cast<uns
 void lrf_debug_set_bwd_overlap(int on) { g_bwd_overlap = (on & 1) ? 1 : 0; if (on > 1) g_wgrad_split = (on >> 1) - 1; }   // on = 1 + 2 * (n + 1): k_wgrad_w2w3 on the caller's stream (n > 0) or on the side stream (n = 0)
 void lrf_debug_set_lds_lines(int on) { g_no_lds_lines = on ? 0 : 1; }
 void lrf_debug_set_pipe_chunk(int rays) { g_pipe_chunk = rays > 0 ? rays : 0; }
+void lrf_debug_set_march_rays(int rays) { g_march_rays = (rays == 4 || rays == 8 || rays == 16) ? rays : 0; }
+void lrf_debug_set_lds_toff(int on) { g_no_lds_toff = on ? 0 : 1; }
+int lrf_debug_tile_ranges(const int32_t* ncomp, int32_t R, int32_t G, int32_t nb, int32_t* gsum, int32_t* ranges,
+                          int32_t* toff_out, int32_t* nc_out, void* stream) {
+  if (!ncomp || !gsum || !ranges || !toff_out || !nc_out) return set_err("lrf_debug_tile_ranges: null argument");
+  if (R <= 0 || nb <= 0 || (G != 4 && G != 8 && G != 16)) return set_err("lrf_debug_tile_ranges: need R > 0, nb > 0 and G in {4, 8, 16}");
+  const size_t lds = (size_t)(R + 1) * sizeof(int) + (size_t)R * sizeof(unsigned short) + 16;
+  if (lds > 64 * 1024) return set_err("lrf_debug_tile_ranges: R too large for 64 KB of LDS");
+  if ((R + G - 1) / G > 512 * TILE_GPT) return set_err("lrf_debug_tile_ranges: more groups than one workgroup scans");
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int NG = (R + G - 1) / G;
+  hipLaunchKernelGGL(k_group_tiles, dim3((NG + 255) / 256), dim3(256), 0, st, ncomp, R, G, gsum);
+  hipLaunchKernelGGL(k_tile_ranges_dbg, dim3(nb), dim3(512), lds, st, gsum, ncomp, R, G, reinterpret_cast<int4*>(ranges), toff_out, nc_out);
+  LRF_HIP(hipGetLastError());
+  return 0;
+}
 #ifdef LRF_SCATTER_PROF
 int lrf_debug_scatter_prof(unsigned long long* host_out /* [2][2048][12] */) {
   return (int)hipMemcpyFromSymbol(host_out, HIP_SYMBOL(lrf::g_scat_prof), sizeof(unsigned long long) * 2 * 2048 * 12);
@@ -1391,9 +1437,10 @@ static int render_fwd_impl(const LrfField* f, const float* rays, const float* z,
   rays = sort_rays_if_asked(d, rays, R, flags, w, st);
   if (fwd_shade3(f, flags)) {
     // Default engine: k_march -> k_shade3 (32 samples per wave on v_mfma_f32_32x32x16_bf16, lrf_shade3.inl); the tile
-    // offsets are scanned inside the colour kernel when they fit in LDS beside the image, by k_scan_tiles_n otherwise.
+    // offsets are built inside the colour kernel from k_march's group sums (w.gsum) when they fit in LDS beside the image,
+    // scanned by k_scan_tiles_n otherwise.
     d.rdir = w.rdir;
-    launch_march(d, rays, z, R, S, flags, floater_thresh, depth, w.acc, weight_out, w.ncomp, w.cidx, w.cw, nullptr, st);
+    launch_march(d, rays, z, R, S, flags, floater_thresh, depth, w.acc, weight_out, w.ncomp, w.gsum, w.cidx, w.cw, nullptr, st);
     if (ev) LRF_HIP(hipEventRecord(ev[1], st));
     launch_shade3(d, rays, z, R, S, flags, w, w.toff, rgb, acc_out, nullptr, g_dump, st);
     if (ev) { LRF_HIP(hipEventRecord(ev[2], st)); LRF_HIP(hipEventRecord(ev[3], st)); }
@@ -1401,7 +1448,7 @@ static int render_fwd_impl(const LrfField* f, const float* rays, const float* z,
     return 0;
   }
   // exact-fp32 / plain-loop engines: 16-sample tiles, k_march -> [k_scan_tiles ->] colour kernel -> k_finalize
-  launch_march(d, rays, z, R, S, flags, floater_thresh, depth, w.acc, weight_out, w.ncomp, w.cidx, w.cw, nullptr, st);
+  launch_march(d, rays, z, R, S, flags, floater_thresh, depth, w.acc, weight_out, w.ncomp, nullptr /* no group sums: these engines scan the counts */, w.cidx, w.cw, nullptr, st);
   if (ev) LRF_HIP(hipEventRecord(ev[1], st));
   if (!default_net(f) || (flags & LRF_FLAG_MLP_VALU)) {
     const GenCfg gc = gen_cfg(d.fea_pe, d.view_pe, d.fc, !(flags & LRF_FLAG_PE_OFF));
@@ -1515,7 +1562,7 @@ int lrf_scene_fwd(const int64_t* ray_ids, int32_t R, int32_t per_view, const flo
       for (int k = nf; k < LRF_MULTI_MAX; ++k) mf.f[k] = mf.f[0];
       const float* rv = rays + (size_t)k0 * R * 6;             // field k of the group: rays [k0 + k][lo + r], outputs likewise (multi_io)
       launch_march(mf.f[0], rv, fields[k0].z, Rv, S, fields[k0].flags, 0.0f, depth_f + (size_t)k0 * R, w.acc, nullptr,
-                   w.ncomp, w.cidx, w.cw, nullptr, st, &mf);
+                   w.ncomp, nullptr /* k_shade3m reads k_scan_tiles_n's offsets */, w.cidx, w.cw, nullptr, st, &mf);
       launch_shade3_multi(mf, rv, fields[k0].z, Rv, S, fields[k0].flags, w, rgb_f + (size_t)k0 * R * 3, st);
     }
   }

@@ -138,6 +138,140 @@ __device__ __forceinline__ int toff_lower_bound_p(P toff, int n, int v) {
   return lo < n ? lo : n;
 }
 
+// A colour workgroup's rays [ra, rb) and tiles [T0, T1) of the even split of the tile list (cut at ray boundaries), from
+// k_march's group sums instead of a scan over every ray: gsum[g] = tiles of rays [g G, (g + 1) G) (G = 4, 8 or 16, a power of
+// two), so toff[g G] is the exclusive scan of gsum -- ceil(R / G) values instead of R.  Every workgroup
+//   1. scans the group sums into s_toff[g G] (absolute ray index, as the tile loop reads it) and s_toff[R] = T,
+//   2. finds the groups its two cut points fall into (lower bound at group granularity: a count over the registers of step 1),
+//   3. loads ncomp for the rays of those groups and the groups between them only, and fills s_toff / s_nc there,
+//   4. finishes the two lower bounds inside their groups.
+// ra, rb, T0, T1 and every s_toff[r], r in [ra, rb], and s_nc[r], r in [ra, rb), are the integers of the full scan with
+// toff_lower_bound_p(toff, R, v) (rb = R for the last workgroup); entries outside [win0, win1] hold nothing.
+// Two calls, by all NT threads, with a workgroup barrier between them that the caller places: tile_range_fill (steps 1 - 3; its
+// LDS stores are not yet visible), whatever else the caller wants in front of that barrier, __syncthreads(),
+// tile_range_finish (step 4).  s_wave: NT / 64 + 2 ints.
+typedef __attribute__((address_space(3))) unsigned short lds_u16;
+constexpr int TILE_GPT = 8;                                    // group sums per thread: 512 threads hold those of 16384 rays at 4 per group
+struct TileRange { int ra, rb, T0, T1, win0, win1; int ga, gb, v0, v1; };   // ga .. v1: from tile_range_fill to tile_range_finish
+// step 1's loads on their own: k_shade3 requests them in front of its weight image, whose loads are answered first otherwise
+struct GroupSums { int v[TILE_GPT]; };
+__device__ __forceinline__ GroupSums tile_group_sums(const int* __restrict__ gsum, int R, int G) {
+  const int NG = (R + G - 1) / G, g0 = threadIdx.x * TILE_GPT;
+  GroupSums s;
+#pragma unroll
+  for (int i = 0; i < TILE_GPT; ++i) s.v[i] = g0 + i < NG ? gsum[g0 + i] : 0;
+  return s;
+}
+template <int NT>
+__device__ __forceinline__ TileRange tile_range_fill(const GroupSums& gs, const int* __restrict__ ncomp, int R, int G,
+                                                     int lb, int nb, lds_int* s_toff, lds_u16* s_nc, int* s_wave) {
+  constexpr int NWV = NT / 64;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int NG = (R + G - 1) / G;                              // at most NT * TILE_GPT (the caller's check)
+  const int g0 = tid * TILE_GPT;
+  int v[TILE_GPT];
+#pragma unroll
+  for (int i = 0; i < TILE_GPT; ++i) v[i] = gs.v[i];
+  if (tid < 2) s_wave[NWV + tid] = 0;                          // the two group counts of step 2
+#pragma unroll
+  for (int i = 1; i < TILE_GPT; ++i) v[i] += v[i - 1];
+  int incl = v[TILE_GPT - 1];
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const int t = __shfl_up(incl, d, 64);
+    if (lane >= d) incl += t;
+  }
+  if (lane == 63) s_wave[wave] = incl;
+  __syncthreads();
+  int woff = 0, T = 0;
+#pragma unroll
+  for (int q = 0; q < NWV; ++q) { const int x = s_wave[q]; woff += q < wave ? x : 0; T += x; }
+  const int excl = woff + incl - v[TILE_GPT - 1];
+  const int v0 = (int)((long long)lb * T / nb), v1 = (int)((long long)(lb + 1) * T / nb);
+  const bool last = lb == nb - 1;
+  // The first group g in [0, NG] whose first ray's offset (the total, for g = NG) is >= v is the number of groups whose
+  // offset is below v (the offsets do not decrease): every thread counts its own, from registers.
+  int c0 = 0, c1 = 0;
+#pragma unroll
+  for (int i = 0; i < TILE_GPT; ++i) {
+    const int o = excl + (i ? v[i - 1] : 0);
+    const bool in = g0 + i < NG;
+    if (in) s_toff[(g0 + i) * G] = o;
+    c0 += __popcll(__ballot(in && o < v0));
+    c1 += __popcll(__ballot(in && o < v1));
+  }
+  if (lane == 0 && c0) atomicAdd(&s_wave[NWV], c0);
+  if (lane == 0 && c1) atomicAdd(&s_wave[NWV + 1], c1);
+  if (tid == 0) s_toff[R] = T;
+  __syncthreads();
+  const int ga = __builtin_amdgcn_readfirstlane(s_wave[NWV]);
+  const int gb = last ? NG : __builtin_amdgcn_readfirstlane(s_wave[NWV + 1]);
+  // the cut for v lies in ((g - 1) G, g G]: groups ga - 1 .. gb (one more than rb needs: the tile loop looks at toff[ra + 1])
+  TileRange tr;
+  tr.win0 = max(ga - 1, 0) * G;
+  tr.win1 = min((gb + 1) * G, R);
+  for (int r0 = tr.win0; r0 < tr.win1; r0 += NT) {             // (win0 and NT are multiples of G: lane & (G - 1) is the ray's place in its group)
+    const int r = r0 + tid, k = lane & (G - 1);
+    const int nc = r < tr.win1 ? ncomp[r] : 0;
+    const int t = (nc + ITEM3 - 1) / ITEM3;
+    int incl = t;
+    for (int d = 1; d < G; d <<= 1) {
+      const int x = __shfl_up(incl, d, 64);
+      if (k >= d) incl += x;
+    }
+    if (r < tr.win1) {
+      s_nc[r] = (unsigned short)nc;
+      if (k) s_toff[r] = s_toff[r - k] + incl - t;
+    }
+  }
+  tr.ga = ga; tr.gb = gb; tr.v0 = v0; tr.v1 = v1;
+  return tr;
+}
+__device__ __forceinline__ void tile_range_finish(TileRange& tr, int R, int G, int lb, int nb, lds_int* s_toff) {
+  const bool last = lb == nb - 1;
+  const int ga = tr.ga, gb = tr.gb, v0 = tr.v0, v1 = tr.v1;
+  auto ray_lb = [&](int g, int v) {                            // toff_lower_bound_p's answer, searched inside group g - 1
+    if (g == 0) return 0;
+    int lo = (g - 1) * G + 1, hi = min(g * G, R);
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (s_toff[mid] >= v) hi = mid; else lo = mid + 1;
+    }
+    return lo;
+  };
+  tr.ra = __builtin_amdgcn_readfirstlane(ray_lb(ga, v0));
+  tr.rb = __builtin_amdgcn_readfirstlane(last ? R : ray_lb(gb, v1));
+  tr.T0 = __builtin_amdgcn_readfirstlane(s_toff[tr.ra]);
+  tr.T1 = __builtin_amdgcn_readfirstlane(s_toff[tr.rb]);
+}
+
+// Test hook (lrf_debug_tile_ranges): tile_range_fill / tile_range_finish in a kernel of its own, with group sums that k_group_tiles forms from
+// the counts.  Workgroup b (its blockIdx is its place lb in the split: no XCD order here) leaves ranges[b] = {ra, rb, T0,
+// T1}, its offsets toff_out[b][ra .. rb] and counts nc_out[b][ra .. rb - 1]; everything else keeps the caller's fill.
+__global__ void k_group_tiles(const int* __restrict__ ncomp, int R, int G, int* __restrict__ gsum) {
+  const int g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g * G >= R) return;
+  int t = 0;
+  for (int r = g * G; r < min(g * G + G, R); ++r) t += (ncomp[r] + ITEM3 - 1) / ITEM3;
+  gsum[g] = t;
+}
+__global__ __launch_bounds__(512) void k_tile_ranges_dbg(const int* __restrict__ gsum, const int* __restrict__ ncomp, int R, int G,
+                                                         int4* __restrict__ ranges, int* __restrict__ toff_out, int* __restrict__ nc_out) {
+  extern __shared__ uint4 s_dyn[];
+  __shared__ int s_wave[8 + 2];
+  lds_int* s_toff = (lds_int*)s_dyn;
+  lds_u16* s_nc = (lds_u16*)(s_toff + R + 1);
+  const int lb = blockIdx.x, tid = threadIdx.x;
+  TileRange tr = tile_range_fill<512>(tile_group_sums(gsum, R, G), ncomp, R, G, lb, (int)gridDim.x, s_toff, s_nc, s_wave);
+  __syncthreads();
+  tile_range_finish(tr, R, G, lb, (int)gridDim.x, s_toff);
+  if (tid == 0) ranges[lb] = make_int4(tr.ra, tr.rb, tr.T0, tr.T1);
+  for (int r = tr.ra + tid; r <= tr.rb; r += 512) {
+    toff_out[(size_t)lb * (R + 1) + r] = s_toff[r];
+    if (r < tr.rb) nc_out[(size_t)lb * R + r] = s_nc[r];
+  }
+}
+
 // What one wave needs to know about a tile before it can gather.  The loads are issued one tile ahead and first used at
 // the top of the next tile, so the dependent chain tile -> ray -> sample index -> distance is off the critical path.
 struct Hdr3 {

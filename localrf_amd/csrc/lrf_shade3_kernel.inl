@@ -1,9 +1,10 @@
 // lrf_shade3_kernel.inl -- the colour kernel of lrf_shade3.inl, included twice (k_shade3: one field; k_shade3m: several fields)
-// NW waves per workgroup (one workgroup per CU).  LDSTOFF: the tile offsets are scanned by every workgroup itself into
-// LDS (R + 1 ints beside the image: two launches per render, k_march -> k_shade3); otherwise k_scan_tiles_n<32> ran before
-// and toff_g holds them.
+// NW waves per workgroup (one workgroup per CU).  LDSTOFF: every workgroup builds the tile offsets of its own rays in LDS
+// from k_march's group sums (toff_g: one int per gsz rays; tile_range_fill, lrf_shade3.inl; two launches per render,
+// k_march -> k_shade3); otherwise k_scan_tiles_n<32> ran before and toff_g holds the R + 1 offsets.
 // TIMED (debug, lrf_debug_set_dump): s_memtime totals per wave -> dump[block][wave][8] =
-// {rest of the prologue, header + position, gather + split, image copy, scan, chain, tiles, finalize}
+// {rest of the prologue, header + position, gather + split, image requested + z stored, tile offsets and range (ends behind
+// the image's arrival), chain, tiles, finalize}
 // SAVE: the training forward -- the same tile loop additionally writes what SaveOut3 lists (128 B of feat + 32 B of mask bits
 // + 12 B of colour per shaded sample): the eval kernel IS the row-saving forward, its rgb is bit-identical to the eval's.
 // LRF_SHADE3_MULTI (this file is included twice, lrf_shade3.inl): the second kernel, k_shade3m, renders several fields in one
@@ -21,7 +22,7 @@ __global__ __launch_bounds__(NW * 64) void LRF_SHADE3_NAME(
     const float* __restrict__ rays, const float* __restrict__ z, int S,
     const int* __restrict__ toff_g, int R, const int* __restrict__ ncomp, const uint16_t* __restrict__ cidx,
     const float* __restrict__ cw, float* __restrict__ part, int pmax,
-    uint32_t flags, const float* __restrict__ acc, float* __restrict__ rgb_out, float* __restrict__ acc_out, SaveOut3 sv) {
+    uint32_t flags, const float* __restrict__ acc, float* __restrict__ rgb_out, float* __restrict__ acc_out, SaveOut3 sv, int gsz) {
   constexpr int NT = NW * 64;
   extern __shared__ uint4 s_dyn[];                             // image, tail, z[S][, toff[R + 1]]
   unsigned long long tk[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tlast = 0;
@@ -31,76 +32,75 @@ __global__ __launch_bounds__(NW * 64) void LRF_SHADE3_NAME(
   float* tail = reinterpret_cast<float*>(s_dyn + W32_U4);
   float* s_z = tail + W32_T_FLOATS;
   lds_int* s_toff = (lds_int*)(s_z + S);
-  typedef __attribute__((address_space(3))) unsigned short lds_u16;
   lds_u16* s_nc = (lds_u16*)(s_toff + (LDSTOFF ? R + 1 : 0));  // per-ray shaded-sample counts beside the offsets (LDSTOFF)
-  __shared__ int s_wave[NW];
+  __shared__ int s_wave[NW + 2];                               // (+ 2: tile_range_fill)
   __shared__ int s_next;                                       // tile queue of this workgroup
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = lane & 31, h = lane >> 5;
+  // requested in front of the image (loads are answered in order): the group sums of the tile offsets, the first round of z
+  GroupSums gs;
+  if constexpr (LDSTOFF) gs = tile_group_sums(toff_g, R, gsz);
+  const float z_first = tid < S ? z[tid] : 0.0f;
+  if constexpr (LDSTOFF) asm volatile("" : "+v"(gs.v[0]), "+v"(gs.v[TILE_GPT - 1]));   // (here, not behind the image)
 #if LRF_SHADE3_MULTI
   static_assert(!LDSTOFF && !SAVE && !TIMED, "the multi-field kernel reads global tile offsets and saves nothing");
   const DField& f = mf.f[0];                                   // (the tile loop below names its segment's field `f` again)
 #else
   {
-    // Every workgroup starts its copy of the 95 KB image at a different place.  Started at the same place, the CUs of an
-    // XCD ask the same L2 channel for the same line at the same time and the copy runs at ~11 B / cycle / CU (8.2 K
-    // cycles); rotated it takes 5.0 K (colour stage 120.6 -> 119.4 us, scripts/ab_shade.sh).  Rotating the reads of the
+    // The 95 KB image goes from global memory straight into LDS (global_load_lds_dwordx4: no register round trip), in pieces
+    // of 64 uint4 = one wave instruction, LDS base in M0; requested here, awaited in front of the barrier that ends the
+    // prologue.  Nothing of it overlaps the tile loop.  (The compiler makes every LDS access behind such a load wait for
+    // it, so the tile offsets below do not run under the copy; requesting it later, behind their first steps, or as a
+    // fixed number of loads per wave that the compiler can count, was measured and lost in the loop's register
+    // allocation: profiles/r23_forward_fixed_cost.md.)
+    // Every workgroup starts at a different piece.  Started at the same place, the CUs of an XCD ask the same L2 channel
+    // for the same line at the same time and the copy (through registers, as it was) ran at ~11 B / cycle / CU (8.2 K
+    // cycles); rotated it took 5.0 K (colour stage 120.6 -> 119.4 us, scripts/ab_shade.sh).  Rotating the reads of the
     // per-ray counts and of k_march's line staging the same way gains nothing measurable.
-    const int rot = (int)((blockIdx.x * 37u) % 93u) * 64;
-    for (int i = tid; i < W32_ALL_U4; i += NT) { int j = i + rot; if (j >= W32_ALL_U4) j -= W32_ALL_U4; img[j] = f.mlpw[j]; }
+    constexpr int NPIECE = (W32_ALL_U4 + 63) / 64;
+    static_assert(NPIECE == 93, "the rotation below is taken modulo the number of pieces");
+    const int rot = (int)((blockIdx.x * 37u) % 93u);
+    for (int p = __builtin_amdgcn_readfirstlane(wave); p < NPIECE; p += NW) {
+      int j = p + rot; if (j >= NPIECE) j -= NPIECE;
+      if (j * 64 + lane < W32_ALL_U4)
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(f.mlpw + j * 64 + lane),
+                                         (__attribute__((address_space(3))) void*)(img + j * 64), 16, 0, 0);
+    }
   }
 #endif
-  for (int i = tid; i < S; i += NT) s_z[i] = z[i];
-  if (TIMED) { __syncthreads(); LRF_TICK(3); }                 // (TIMED only: image + z in LDS)
-  if (LDSTOFF) {                                               // exclusive scan of ceil(ncomp / 32): eight rays per thread and round
-    int carry = 0;
-    for (int base = 0; base < R; base += NT * 8) {
-      const int r0 = base + tid * 8;
-      int v[8];
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const int nc = r0 + i < R ? ncomp[r0 + i] : 0;
-        if (r0 + i < R) s_nc[r0 + i] = (unsigned short)nc;
-        v[i] = (nc + ITEM3 - 1) / ITEM3;
-      }
-#pragma unroll
-      for (int i = 1; i < 8; ++i) v[i] += v[i - 1];
-      int incl = v[7];
-#pragma unroll
-      for (int d = 1; d < 64; d <<= 1) {
-        const int t = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += t;
-      }
-      __syncthreads();                                         // s_wave of the previous round has been read
-      if (lane == 63) s_wave[wave] = incl;
-      __syncthreads();
-      int woff = 0, tot = 0;
-#pragma unroll
-      for (int q = 0; q < NW; ++q) { const int x = s_wave[q]; woff += q < wave ? x : 0; tot += x; }
-      const int excl = carry + woff + incl - v[7];
-      if (r0 < R) s_toff[r0] = excl;
-#pragma unroll
-      for (int i = 1; i < 8; ++i) if (r0 + i < R) s_toff[r0 + i] = excl + v[i - 1];
-      carry += tot;
-    }
-    if (tid == 0) s_toff[R] = carry;
-  }
-  __syncthreads();
-  LRF_TICK(4);                                                 // (TIMED only: scan done)
+  if (tid < S) s_z[tid] = z_first;
+  for (int i = tid + NT; i < S; i += NT) s_z[i] = z[i];
+  LRF_TICK(3);                                                 // (TIMED only: image requested, z stored)
   typedef typename std::conditional<LDSTOFF, const lds_int*, const int*>::type ToffP;
   ToffP toff;
   if constexpr (LDSTOFF) toff = s_toff; else toff = toff_g;
-  if constexpr (SAVE) {
-    if (blockIdx.x == 0) for (int r = tid; r <= R; r += NT) sv.toff16[r] = 2 * (int)toff[r];
-  }
-
   // this workgroup's rays [ra, rb) and tiles [T0, T1): the even split of the tile list, moved to ray boundaries
   const int nb = gridDim.x;
   const int lb = (nb % 8 == 0) ? (int)(blockIdx.x % 8) * (nb / 8) + (int)(blockIdx.x / 8) : (int)blockIdx.x;   // XCD-aware order
-  const int T = toff[R];
-  const int ra = __builtin_amdgcn_readfirstlane(toff_lower_bound_p(toff, R, (int)((long long)lb * T / nb)));
-  const int rb = __builtin_amdgcn_readfirstlane(lb == nb - 1 ? R : toff_lower_bound_p(toff, R, (int)((long long)(lb + 1) * T / nb)));
-  const int T0 = __builtin_amdgcn_readfirstlane(toff[ra]), T1 = __builtin_amdgcn_readfirstlane(toff[rb]);
+  TileRange tr;
+  if constexpr (LDSTOFF) {                                     // toff_g: k_march's group sums, gsz rays each (tile_range_fill)
+    tr = tile_range_fill<NT>(gs, ncomp, R, gsz, lb, nb, s_toff, s_nc, s_wave);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");            // the image
+    __syncthreads();
+    tile_range_finish(tr, R, gsz, lb, nb, s_toff);
+  } else {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");            // the image
+    __syncthreads();
+    const int T = toff[R];
+    tr.ra = __builtin_amdgcn_readfirstlane(toff_lower_bound_p(toff, R, (int)((long long)lb * T / nb)));
+    tr.rb = __builtin_amdgcn_readfirstlane(lb == nb - 1 ? R : toff_lower_bound_p(toff, R, (int)((long long)(lb + 1) * T / nb)));
+    tr.T0 = __builtin_amdgcn_readfirstlane(toff[tr.ra]); tr.T1 = __builtin_amdgcn_readfirstlane(toff[tr.rb]);
+  }
+  const int ra = tr.ra, rb = tr.rb, T0 = tr.T0, T1 = tr.T1;
+  LRF_TICK(4);                                                 // (TIMED only: offsets and tile range done)
+  if constexpr (SAVE) {                                        // the backward's offsets: every workgroup leaves those of its own rays
+    if constexpr (LDSTOFF) {
+      for (int r = ra + tid; r < rb; r += NT) sv.toff16[r] = 2 * (int)toff[r];
+      if (lb == nb - 1 && tid == 0) sv.toff16[R] = 2 * (int)toff[R];
+    } else {
+      if (blockIdx.x == 0) for (int r = tid; r <= R; r += NT) sv.toff16[r] = 2 * (int)toff[r];
+    }
+  }
 #if LRF_SHADE3_MULTI
   for (int fk = ra / mf.Rf; fk < mf.nf; ++fk) {                // the segments of this workgroup's range, one field each
     const int ra_k = max(ra, fk * mf.Rf), rb_k = min(rb, (fk + 1) * mf.Rf);
