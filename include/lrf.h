@@ -782,6 +782,50 @@ size_t lrf_mesh_simplify_workspace_bytes(int64_t Nv, int64_t Nf, int64_t cells);
 int lrf_mesh_simplify(const LrfMeshSimplify* m, float* vertices_out, uint8_t* rgb8_out /* nullable */, int32_t* faces_out,
                       int64_t* counts /* device [5] */, void* workspace, void* stream);
 
+/* The faces around each vertex of an indexed triangle mesh, and what is built on them: boundary and non-manifold edge counts,
+ * area-weighted vertex normals and Taubin lambda|mu smoothing (csrc/lrf_mesh_smooth.inl states the semantics and the kernels).
+ * Integer counts, int64 sums of fixed-point values and fp64 operations each rounded on its own: every call leaves the same
+ * bytes on every run.  No sort, no floating-point atomics, no loop that waits on another lane.  A face with an index outside
+ * [0, Nv) is never dereferenced; a face with two equal indices is degenerate; both take part in nothing.
+ * info (device int64 [8], written by every call) = flag bits, degenerate faces, boundary edges, non-manifold edges, zero
+ * normals, pinned vertices, incidence entries, 0.  Flag bits: 1 a face index outside [0, Nv); 2 a vertex held by 2^20 faces
+ * or more; 4 a vertex coordinate that is not finite (normals); 8 a smoothing step left the fixed-point range (diverged).  With
+ * a flag set the other outputs mean nothing.
+ * lrf_mesh_incidence: the lists alone, in the workspace (E 8 bytes, row_start int32 [Nv + 1], a cursor int32 [Nv], int32
+ * [ceil(Nv / 256)], row_faces int32 [3 Nf], a byte mask [Nv]).  Six launches, four with Nf = 0.
+ * lrf_mesh_topology: the lists, then per directed edge (a, b) of a valid face the counts opp (edges (b, a)) and same (edges
+ * (a, b) of other faces): info[2] = edges with opp == 0, info[3] = edges with same > 0 or opp > 1, boundary (device uint8
+ * [Nv]) = 1 at both ends of every edge with opp == 0, else 0.  Seven launches.
+ * lrf_mesh_vertex_normals: normals (device fp32 [Nv,3]) = the unit sum of the face normals around each vertex, (0, 0, 0) --
+ * counted in info[4] -- where that sum is 0.  Eight launches.
+ * The three above take a workspace of lrf_mesh_incidence_workspace_bytes(Nv, Nf) bytes (0 for refused arguments).
+ * lrf_mesh_smooth_bounds: out (device int32 [7]) = the per-axis minimum [3] and maximum [3] of the vertices as order-preserving
+ * integers (bits ^ ((bits >> 31) & 0x7fffffff), -0 read as +0) and a flag word, 1 when a coordinate is not finite.  Two launches.
+ * lrf_mesh_smooth: the lists, the topology, then `iterations` times a step with factor lam and (mu != 0) a step with factor mu,
+ * each reading one position buffer and writing the other; the last writes vertices_out [Nv,3], which must not be the input.
+ * lo (the minima above, as doubles) and s (36 - the binary exponent of the largest extent; 0 for a box of zero extent) fix
+ * the fixed point of the whole call.  pin_boundary != 0 keeps the vertices of the boundary mask where they are; info[5]
+ * counts them.  All launches are queued by this one call, with no host synchronisation.  workspace:
+ * lrf_mesh_smooth_workspace_bytes(Nv, Nf) bytes.
+ * Refused before any launch: null or misaligned pointers (float and int32 arrays 4 bytes; info and workspace 8), Nv < 1,
+ * Nf < 0, Nv >= 2^31, 3 Nf >= 2^31, iterations outside [0, 1000], lam outside (0, 1], mu outside [-1, 0], a non-finite lo,
+ * |s| > 256. */
+typedef struct LrfMeshSmooth {
+  const float* vertices; const int32_t* faces;
+  int64_t Nv, Nf;
+  double lo[3], lam, mu;
+  int32_t s, iterations, pin_boundary, reserved;
+} LrfMeshSmooth;
+size_t lrf_mesh_incidence_workspace_bytes(int64_t Nv, int64_t Nf);
+int lrf_mesh_incidence(const int32_t* faces, int64_t Nv, int64_t Nf, int64_t* info /* device [8] */, void* workspace, void* stream);
+int lrf_mesh_topology(const int32_t* faces, int64_t Nv, int64_t Nf, uint8_t* boundary /* device [Nv] */,
+                      int64_t* info /* device [8] */, void* workspace, void* stream);
+int lrf_mesh_vertex_normals(const float* vertices, const int32_t* faces, int64_t Nv, int64_t Nf, float* normals,
+                            int64_t* info /* device [8] */, void* workspace, void* stream);
+int lrf_mesh_smooth_bounds(const float* vertices, int64_t Nv, int32_t* out /* device [7] */, void* stream);
+size_t lrf_mesh_smooth_workspace_bytes(int64_t Nv, int64_t Nf);
+int lrf_mesh_smooth(const LrfMeshSmooth* m, float* vertices_out, int64_t* info /* device [8] */, void* workspace, void* stream);
+
 /* Depth quantiles of a ray: the distance at which its accumulated weight first reaches q; q = 0.5 is the median depth, which
  * always lies on a surface the ray met (csrc/lrf_quantile.inl states the arithmetic: fp32 without contraction, one fixed
  * summation order per ray).  With C_i the inclusive prefix sum of the weights lrf_render_fwd leaves in weight_out and i* the

@@ -39,6 +39,12 @@ int64_t lrf_debug_saved_row_offset(int buffer, uint64_t row, int col);
 int     lrf_depth_quantiles_from_weights(const float* w, const float* z, const float* rays, int32_t R, int32_t S, const float* q,
                                          int32_t K, float* depth, int32_t* index, void* stream);
 
+/* lrf_mesh_vertex_normals (include/lrf.h) that also writes the integers behind the normals: S (device int64 [Nv,3]), the sum of
+ * the fixed-point face normals around each vertex, and E (device int32 [1]), the exponent they share (INT32_MIN when every
+ * face normal is zero). */
+int     lrf_debug_mesh_vertex_normals(const float* vertices, const int32_t* faces, int64_t Nv, int64_t Nf, float* normals, int64_t* S,
+                                      int32_t* E, int64_t* info, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

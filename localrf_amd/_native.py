@@ -149,6 +149,12 @@ class LrfMeshSimplify(C.Structure):
                 ("dedupe", C.c_int32), ("reserved", C.c_int32)]
 
 
+class LrfMeshSmooth(C.Structure):
+    _fields_ = [("vertices", _f), ("faces", C.c_void_p), ("Nv", C.c_int64), ("Nf", C.c_int64),
+                ("lo", C.c_double * 3), ("lam", C.c_double), ("mu", C.c_double),
+                ("s", C.c_int32), ("iterations", C.c_int32), ("pin_boundary", C.c_int32), ("reserved", C.c_int32)]
+
+
 class LrfTsdfBlocks(C.Structure):
     _fields_ = [("marks", C.c_void_p), ("table", C.c_void_p), ("coords", C.c_void_p), ("tsdf", _f), ("weight", _f), ("rgb", _f),
                 ("Bx", C.c_int32), ("By", C.c_int32), ("Bz", C.c_int32), ("n_blocks", C.c_int32),
@@ -278,6 +284,15 @@ SYMBOLS = {
     "lrf_mesh_simplify_bounds": (C.c_int, [_f, C.c_int64, C.POINTER(C.c_double), C.c_double, C.c_void_p, C.c_void_p]),
     "lrf_mesh_simplify_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64]),
     "lrf_mesh_simplify": (C.c_int, [C.POINTER(LrfMeshSimplify), _f, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "lrf_mesh_incidence_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
+    "lrf_mesh_incidence": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "lrf_mesh_topology": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "lrf_mesh_vertex_normals": (C.c_int, [_f, C.c_void_p, C.c_int64, C.c_int64, _f, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "lrf_debug_mesh_vertex_normals": (C.c_int, [_f, C.c_void_p, C.c_int64, C.c_int64, _f, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_void_p]),
+    "lrf_mesh_smooth_bounds": (C.c_int, [_f, C.c_int64, C.c_void_p, C.c_void_p]),
+    "lrf_mesh_smooth_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
+    "lrf_mesh_smooth": (C.c_int, [C.POINTER(LrfMeshSmooth), _f, C.c_void_p, C.c_void_p, C.c_void_p]),
     "lrf_density_gradient": (C.c_int, [C.POINTER(LrfField), _f, C.c_int64, _f, _f, C.c_void_p]),
     "lrf_normals_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "lrf_render_normals": (C.c_int, [C.POINTER(LrfField), _f, _f, C.c_int32, C.c_int32, C.c_uint32, C.c_float, _f, C.c_int32,

@@ -8,8 +8,11 @@ lrf_tsdf_integrate and lrf_mesh_extract; csrc/lrf_tsdf_blocks.inl through lrf_ts
   components(faces, n_vertices)                    connected-component labels and sizes of an indexed mesh (csrc/lrf_mesh_clean.inl)
   filter_components(mesh, min_faces, min_fraction) the mesh without its small components, order and bytes preserved
   simplify(mesh, cell, origin)                     the mesh with the vertices of every grid cell merged into one (csrc/lrf_mesh_simplify.inl)
+  topology(mesh)                                   boundary and non-manifold edge counts, the boundary-vertex mask (csrc/lrf_mesh_smooth.inl)
+  vertex_normals(mesh)                             the mesh with area-weighted unit normals per vertex
+  smooth(mesh, iterations, lam, mu, boundary)      the mesh after Taubin lambda|mu smoothing of its vertices
   scene_mesh(local_tensorfs, W, H, voxel=...)      novel_views.render_poses in batches, each integrated and dropped, then extract
-  pointcloud.write_ply(path, vertices, rgb8, faces=faces) writes the result
+  pointcloud.write_ply(path, vertices, rgb8, normals=normals, faces=faces) writes the result
 
 A volume is a lattice of Nx x Ny x Nz points at origin + (ix, iy, iz) * voxel, x fastest in memory.  Depth follows the
 convention of pointcloud.py: a multiple of the un-normalised camera direction whose z is -1, so the signed distance of a
@@ -444,13 +447,180 @@ def simplify(mesh, cell, origin=(0.0, 0.0, 0.0), dedupe=True, max_bytes=1 << 30)
     return out
 
 
-def _filtered(mesh, min_component_faces, min_component_fraction, simplify_cell=None, origin=(0.0, 0.0, 0.0)):
+def _check_iterations(iterations, what="iterations"):
+    try:
+        ok = not isinstance(iterations, (bool, np.bool_)) and int(iterations) == iterations and 0 <= int(iterations) <= 1000
+    except (TypeError, ValueError, OverflowError):
+        ok = False
+    if not ok:
+        raise ValueError(f"{what} must be an integer in [0, 1000], got {iterations!r}")
+    return int(iterations)
+
+
+def _check_post(smooth_iterations, normals):
+    """extract's options: the smoothing iterations (0: none) and whether vertex normals are wanted."""
+    smooth_iterations = _check_iterations(smooth_iterations, "smooth_iterations")
+    if not isinstance(normals, (bool, np.bool_)):
+        raise ValueError(f"normals must be True or False, got {normals!r}")
+    return smooth_iterations, bool(normals)
+
+
+def _mesh_on_device(mesh, feature, checks=None):
+    """_check_mesh, then checks() (the call's other arguments), then the device -> (vertices, faces, Nv, Nf, device)."""
+    v, f, c, Nv, Nf = _check_mesh(mesh)
+    if 3 * Nf > _INT32:
+        raise ValueError(f"faces holds {Nf} rows; the incidence lists take 3 Nf < 2^31")
+    if checks is not None:
+        checks()
+    N.require_gpu(v, "vertices", feature)
+    N.require_gpu(f, "faces", feature)
+    if f.device != v.device:
+        raise ValueError("vertices and faces must live on the same device")
+    return v.detach().contiguous(), f.detach().contiguous(), Nv, Nf, v.device
+
+
+def _raise_flags(flags, Nv):
+    """The flag word of csrc/lrf_mesh_smooth.inl after a call's read-back."""
+    if flags & 1:
+        raise ValueError(f"faces holds an index outside [0, {Nv}): the mesh has {Nv} vertices")
+    if flags & 2:
+        raise ValueError("a vertex is held by 2^20 faces or more: the int64 sums have no headroom for it")
+    if flags & 4:
+        raise ValueError("vertices holds a value that is not finite")
+    if flags & 8:
+        raise ValueError("the smoothing diverged: a coordinate left the fixed-point range (32 times the input's largest extent)")
+
+
+def topology(mesh):
+    """Boundary and non-manifold edges of the mesh (the dict of the module docstring; csrc/lrf_mesh_smooth.inl states every
+    rule).  A face with two equal indices is degenerate: it is counted and takes part in nothing.  For each directed edge (a, b)
+    of each other face f: opp = the directed edges (b, a) among those faces, same = the directed edges (a, b) in faces other
+    than f.  Returns a dict of Python values -- boundary_edges (directed edges with opp == 0), nonmanifold_edges (same > 0 or
+    opp > 1), degenerate_faces, closed (both edge counts are 0) -- and boundary_vertices: a device [Nv] uint8 mask, 1 at both
+    ends of every edge with opp == 0.  Integer counts: the same values on every run.  One call, one read-back; a face index
+    outside [0, Nv) is never dereferenced and raises ValueError, and so does a vertex held by 2^20 faces or more."""
+    v, f, Nv, Nf, dev = _mesh_on_device(mesh, "the mesh topology")
+    mask = torch.empty(Nv, dtype=torch.uint8, device=dev)
+    if Nv == 0:
+        return {"boundary_edges": 0, "nonmanifold_edges": 0, "degenerate_faces": 0, "closed": True, "boundary_vertices": mask}
+    info = torch.empty(8, dtype=torch.int64, device=dev)
+    ws = N.workspace("lrf_mesh_incidence", dev, Nv, Nf)
+    N.launch("lrf_mesh_topology", dev, f.data_ptr() if Nf else None, Nv, Nf, mask.data_ptr(), info.data_ptr(), ws.data_ptr(), guard=True)
+    words = [int(x) for x in info.tolist()]                         # the read-back (it also orders ws's release)
+    _raise_flags(words[0], Nv)
+    return {"boundary_edges": words[2], "nonmanifold_edges": words[3], "degenerate_faces": words[1],
+            "closed": words[2] == 0 and words[3] == 0, "boundary_vertices": mask}
+
+
+def vertex_normals(mesh):
+    """The mesh with "normals": [Nv,3] fp32 unit normals, area-weighted (csrc/lrf_mesh_smooth.inl states every rule).  The
+    normal of face (a, b, c) is (v_b - v_a) x (v_c - v_a) in fp64; every face normal is rounded to fixed point at one shared
+    exponent (41 bits for the largest component of the largest face), a vertex's normal is the int64 sum over the faces around
+    it -- exact, so it does not depend on the order of the faces -- divided by its length in fp64 and rounded to fp32.  Faces
+    keep extract_mesh's winding, so the normals of a TSDF mesh point towards free space.  A vertex whose sum is zero (one that
+    no face holds among them) gets (0, 0, 0).  Degenerate faces (two equal indices) contribute nothing.  One call, one
+    read-back; a face index outside [0, Nv), a vertex held by 2^20 faces or more and a vertex coordinate that is not finite raise
+    ValueError.  Returns a new mesh dict -- every other entry of the input is carried over -- with "normals" and
+    "normal_info": the Python ints zero_normals and degenerate_faces.  pointcloud.write_ply(path, vertices, rgb8,
+    normals=mesh["normals"], faces=mesh["faces"]) writes them."""
+    v, f, Nv, Nf, dev = _mesh_on_device(mesh, "the vertex normals")
+    out = dict(mesh)
+    normals = torch.empty(Nv, 3, dtype=torch.float32, device=dev)
+    if Nv == 0:
+        out.update(normals=normals, normal_info={"zero_normals": 0, "degenerate_faces": 0})
+        return out
+    info = torch.empty(8, dtype=torch.int64, device=dev)
+    ws = N.workspace("lrf_mesh_incidence", dev, Nv, Nf)
+    N.launch("lrf_mesh_vertex_normals", dev, v.data_ptr(), f.data_ptr() if Nf else None, Nv, Nf, normals.data_ptr(), info.data_ptr(),
+             ws.data_ptr(), guard=True)
+    words = [int(x) for x in info.tolist()]                         # the read-back (it also orders ws's release)
+    _raise_flags(words[0], Nv)
+    out.update(normals=normals, normal_info={"zero_normals": words[4], "degenerate_faces": words[1]})
+    return out
+
+
+def _float_of_key(key):
+    """The fp32 value of k_sm_bounds' order-preserving integer, as a Python float."""
+    bits = (key ^ ((key >> 31) & 0x7FFFFFFF)) & 0xFFFFFFFF
+    return float(np.array([bits], np.uint32).view(np.float32)[0])
+
+
+def smooth(mesh, iterations=10, lam=0.5, mu=-0.53, boundary="fixed"):
+    """The mesh after `iterations` iterations of Taubin lambda|mu smoothing (csrc/lrf_mesh_smooth.inl states every rule): one
+    iteration moves every vertex by lam times the way to the mean of its neighbours, then by mu (negative: back out, which keeps
+    the shape from shrinking); mu == 0 skips the second step and gives plain Laplacian smoothing.  The neighbours of a vertex
+    are the two other corners of every face around it, each face counted once: on a closed manifold every neighbour is
+    counted twice and this is the uniform umbrella; along an open border the two border neighbours are counted once, so they
+    weigh half.  Degenerate faces (two equal indices) take part in nothing.  boundary="fixed" pins the vertices of
+    topology()'s boundary_vertices; "free" pins none.  Pinned vertices and vertices no face holds keep their bits; faces, rgb8
+    and every other entry are carried over.  The means are exact: positions are rounded to fixed point (36 bits over the
+    largest extent of the input's box, from its per-axis minimum) and summed in int64, and every fp64 operation around them is
+    rounded on its own, so the output bytes are a fixed function of the input and do not depend on the order of the faces.
+    Two read-backs: the 7 words of the bounds pass (a vertex that is not finite raises ValueError; a box of zero extent returns
+    the input's bytes), then the counts and flags after all iterations, which one native call queues with no host
+    synchronisation between them (a face index outside [0, Nv) is never dereferenced and raises ValueError; so do a vertex held
+    by 2^20 faces or more and an iteration that leaves 32 times the input's extent).  Returns a new mesh dict with "smooth":
+    iterations, lam, mu, boundary, pinned, boundary_edges, nonmanifold_edges, degenerate_faces."""
+    state = {}
+
+    def checks():
+        state["iterations"] = _check_iterations(iterations)
+        for name, x, ok in (("lam", lam, lambda t: 0.0 < t <= 1.0), ("mu", mu, lambda t: -1.0 <= t <= 0.0)):
+            try:
+                t = math.nan if isinstance(x, (bool, np.bool_)) else float(x)
+            except (TypeError, ValueError):
+                t = math.nan
+            if not ok(t):                                           # NaN fails
+                raise ValueError(f"{name} must satisfy " + ("0 < lam <= 1" if name == "lam" else "-1 <= mu <= 0") + f", got {x!r}")
+            state[name] = t
+        if boundary not in ("fixed", "free"):
+            raise ValueError(f"boundary must be 'fixed' or 'free', got {boundary!r}")
+
+    v, f, Nv, Nf, dev = _mesh_on_device(mesh, "the mesh smoothing", checks)
+    out = dict(mesh)
+    info = {"iterations": state["iterations"], "lam": state["lam"], "mu": state["mu"], "boundary": boundary, "pinned": 0,
+            "boundary_edges": 0, "nonmanifold_edges": 0, "degenerate_faces": 0}
+    if Nv == 0:
+        out.update(vertices=v, smooth=info)
+        return out
+    keys = torch.empty(7, dtype=torch.int32, device=dev)
+    N.launch("lrf_mesh_smooth_bounds", dev, v.data_ptr(), Nv, keys.data_ptr(), guard=True)
+    keys = keys.tolist()                                            # read-back one
+    if keys[6]:
+        raise ValueError("vertices holds a value that is not finite")
+    lo = [_float_of_key(k) for k in keys[:3]]
+    extent = max(_float_of_key(k) - l for k, l in zip(keys[3:6], lo))
+    a = N.LrfMeshSmooth()
+    a.vertices, a.faces, a.Nv, a.Nf = v.data_ptr(), f.data_ptr() if Nf else None, Nv, Nf
+    a.lam, a.mu, a.pin_boundary = state["lam"], state["mu"], int(boundary == "fixed")
+    # a box of zero extent: nothing can move, the call copies the input's bytes (and still counts)
+    a.s, a.iterations = (36 - math.frexp(extent)[1], state["iterations"]) if extent > 0.0 else (0, 0)
+    for k in range(3):
+        a.lo[k] = lo[k]
+    vo = torch.empty_like(v)
+    words = torch.empty(8, dtype=torch.int64, device=dev)
+    ws = N.workspace("lrf_mesh_smooth", dev, Nv, Nf)
+    N.launch("lrf_mesh_smooth", dev, C.byref(a), vo.data_ptr(), words.data_ptr(), ws.data_ptr(), guard=True)
+    words = [int(x) for x in words.tolist()]                        # read-back two (it also orders ws's release)
+    _raise_flags(words[0], Nv)
+    info.update(pinned=words[5], boundary_edges=words[2], nonmanifold_edges=words[3], degenerate_faces=words[1])
+    out.update(vertices=vo, smooth=info)
+    return out
+
+
+def _filtered(mesh, min_component_faces, min_component_fraction, simplify_cell=None, origin=(0.0, 0.0, 0.0), smooth_iterations=0,
+              normals=False):
     """extract's tail: the mesh itself with every option at its default -- nothing new is launched --, else
-    filter_components of it, then (the floaters having been judged at full resolution) simplify of that."""
+    filter_components of it, then (the floaters having been judged at full resolution) simplify of that, then smooth of that
+    with the defaults of smooth(), then vertex_normals of the smoothed positions."""
     if not (min_component_faces == 0 and min_component_fraction == 0.0):
         mesh = filter_components(mesh, min_component_faces, min_component_fraction)
     if simplify_cell is not None:
         mesh = simplify(mesh, simplify_cell, origin=origin)
+    if smooth_iterations:
+        mesh = smooth(mesh, smooth_iterations)
+    if normals:
+        mesh = vertex_normals(mesh)
     return mesh
 
 
@@ -504,17 +674,20 @@ class TsdfVolume:
         return self
 
     def extract(self, level=0.0, min_weight=1.0, max_vertices=None, max_faces=None, *, min_component_faces=0,
-                min_component_fraction=0.0, simplify_cell=None):
+                min_component_fraction=0.0, simplify_cell=None, smooth_iterations=0, normals=False):
         """The mesh of the surface tsdf = level over the cells every corner of which at least min_weight frames saw:
         extract_mesh(self.tsdf, ..., weight=self.weight, rgb=self.rgb); see there for the capacities and the read-backs.
         With min_component_faces or min_component_fraction above 0 the result is filter_components(that mesh, min_faces,
         min_fraction): its small connected components are gone.  With simplify_cell (a cell edge in world units) the result
-        of that is simplify(mesh, simplify_cell, origin=self.origin): the grid is anchored at the volume's origin."""
+        of that is simplify(mesh, simplify_cell, origin=self.origin): the grid is anchored at the volume's origin.  With
+        smooth_iterations above 0 the result of that is smooth(mesh, smooth_iterations), and with normals=True the result of
+        that is vertex_normals(mesh): the normals of the smoothed surface.  The defaults launch nothing new."""
         level, min_weight = _check_extract(level, min_weight, max_vertices, max_faces)
         keep = _check_keep(min_component_faces, min_component_fraction, tuple(_NO_FILTER))
         simplify_cell = _check_simplify_cell(simplify_cell)
+        post = _check_post(smooth_iterations, normals)
         return _filtered(_extract(self.tsdf, self.weight, self.rgb, self.origin, self.voxel, self.dims, level, min_weight,
-                                  max_vertices, max_faces), *keep, simplify_cell, self.origin)
+                                  max_vertices, max_faces), *keep, simplify_cell, self.origin, *post)
 
 
 BLOCK = 8                                      # lattice points per block edge
@@ -656,19 +829,21 @@ class SparseTsdfVolume:
         return self
 
     def extract(self, level=0.0, min_weight=1.0, max_vertices=None, max_faces=None, *, min_component_faces=0,
-                min_component_fraction=0.0, simplify_cell=None):
+                min_component_fraction=0.0, simplify_cell=None, smooth_iterations=0, normals=False):
         """The mesh of the surface tsdf = level over the cells every corner of which is stored and was seen by at least
         min_weight frames.  Vertices come in pool order, then (z, y, x, edge) inside the block; faces in the pool order of
         the cell's lowest corner, then (z, y, x) inside the block, then (tetrahedron, triangle).  Capacities and read-backs as
         extract_mesh has them.  With zero blocks nothing is launched and the mesh is empty.  min_component_faces,
-        min_component_fraction and simplify_cell as TsdfVolume.extract takes them."""
+        min_component_fraction, simplify_cell, smooth_iterations and normals as TsdfVolume.extract takes them."""
         level, min_weight = _check_extract(level, min_weight, max_vertices, max_faces)
         keep = _check_keep(min_component_faces, min_component_fraction, tuple(_NO_FILTER))
         simplify_cell = _check_simplify_cell(simplify_cell)
+        post = _check_post(smooth_iterations, normals)
         dev = self.table.device
         if not self.n_blocks:
-            return {"vertices": torch.empty(0, 3, dtype=torch.float32, device=dev), "faces": torch.empty(0, 3, dtype=torch.int32, device=dev),
-                    "rgb8": torch.empty(0, 3, dtype=torch.uint8, device=dev) if self.colours else None, "counts": (0, 0)}
+            empty = {"vertices": torch.empty(0, 3, dtype=torch.float32, device=dev), "faces": torch.empty(0, 3, dtype=torch.int32, device=dev),
+                     "rgb8": torch.empty(0, 3, dtype=torch.uint8, device=dev) if self.colours else None, "counts": (0, 0)}
+            return _filtered(empty, 0, 0.0, None, self.origin, *post)   # an empty mesh has nothing to filter or simplify
         ws = N.workspace("lrf_mesh_extract_blocks", dev, self.n_blocks)
         a = self._args()
 
@@ -676,7 +851,8 @@ class SparseTsdfVolume:
             N.launch("lrf_mesh_extract_blocks", dev, C.byref(a), level, min_weight, cap_v, cap_f, v.data_ptr(),
                      None if c is None else c.data_ptr(), f.data_ptr(), counts.data_ptr(), ws.data_ptr(), guard=True)
 
-        return _filtered(_sized_extract(dev, self.colours, launch, max_vertices, max_faces), *keep, simplify_cell, self.origin)
+        return _filtered(_sized_extract(dev, self.colours, launch, max_vertices, max_faces), *keep, simplify_cell, self.origin,
+                         *post)
 
     def to_dense(self):
         """(tsdf, weight, rgb or None, stored) as [8Bz,8By,8Bx] tensors of the virtual lattice (rgb [...,3]; stored: bool, the
@@ -696,7 +872,7 @@ class SparseTsdfVolume:
 
 
 _MESH_KEYS = ("depth_range", "level", "min_weight", "max_vertices", "max_faces", "colours", "frames_per_call",
-              "min_component_faces", "min_component_fraction", "simplify_cell")
+              "min_component_faces", "min_component_fraction", "simplify_cell", "smooth_iterations", "normals")
 
 
 def _lattice_of_box(lo, hi, voxel):
@@ -720,7 +896,8 @@ def scene_mesh(local_tensorfs, W, H, voxel, bounds=None, poses=None, trunc=None,
     max_faces, colours (default True), frames_per_call, min_component_faces and min_component_fraction (both default 0: with
     either above 0 the extracted mesh goes through filter_components, which drops its small connected components),
     simplify_cell (default None; a cell edge in world units sends the mesh, after that filter, through simplify on a grid
-    anchored at the volume's origin) and render_poses' test_frames, frame_indices, floater_thresh, chunk.
+    anchored at the volume's origin), smooth_iterations (default 0; above 0 the mesh then goes through smooth) and normals
+    (default False; True adds vertex_normals' "normals" of the final positions) and render_poses' test_frames, frame_indices, floater_thresh, chunk.
     A volume above max_bytes raises ValueError before it is allocated and, with bounds given, before anything is rendered.
     depth="median" integrates the median depth of the same frames (depth_quantiles.median_depth: one more render pass per
     batch) instead of render_poses' expected depth, which carves a phantom sheet between two surfaces a ray sees; the colours
@@ -751,6 +928,7 @@ def scene_mesh(local_tensorfs, W, H, voxel, bounds=None, poses=None, trunc=None,
     colours = bool(options.get("colours", True))
     keep = _check_keep(options.get("min_component_faces", 0), options.get("min_component_fraction", 0.0), tuple(_NO_FILTER))
     simplify_cell = _check_simplify_cell(options.get("simplify_cell"))
+    post = _check_post(options.get("smooth_iterations", 0), options.get("normals", False))
     per_call = options.get("frames_per_call", 8)
     if int(per_call) != per_call or int(per_call) < 1:
         raise ValueError(f"frames_per_call must be an integer >= 1, got {per_call!r}")
@@ -816,6 +994,6 @@ def scene_mesh(local_tensorfs, W, H, voxel, bounds=None, poses=None, trunc=None,
     for p, dmap, rgb8 in batches():
         vol.integrate(dmap, p, focal, center, rgb=rgb8, depth_range=depth_range)
     mesh = vol.extract(level, min_weight, options.get("max_vertices"), options.get("max_faces"), min_component_faces=keep[0],
-                       min_component_fraction=keep[1], simplify_cell=simplify_cell)
+                       min_component_fraction=keep[1], simplify_cell=simplify_cell, smooth_iterations=post[0], normals=post[1])
     mesh["volume"] = vol
     return mesh
