@@ -10,8 +10,9 @@
 extern "C" {
 #endif
 
-/* When set (device buffer of n_CUs * 8 waves * 8 uint64), lrf_render_fwd runs k_shade3<TIMED> and leaves per-wave
- * s_memtime totals there: {prologue, header + position, gather + split, -, -, chain, tiles, finalize}; NULL = off. */
+/* When set (device buffer of n_CUs * 8 waves * 10 uint64), lrf_render_fwd runs k_shade3<TIMED> and leaves per-wave
+ * s_memtime totals there: {prologue, position + taps, gather + split, image requested, tile offsets, chain + head, tiles,
+ * finalize, tail (joins, sigmoid, tile sum, store), loop top up to the next header's loads issued}; NULL = off. */
 void    lrf_debug_set_dump(float* buf);
 /* When set (device buffer of R * 4 uint64, R = the rays of the largest march that follows), every single-field k_march runs
  * with phase clocks and leaves per ray (= per wave) the shader-cycle totals {line and z staging with its barrier, pass A
@@ -27,6 +28,10 @@ void    lrf_debug_set_lds_toff(int on);           /* k_shade3: tile offsets buil
  * are left as the caller filled them.  R up to about 10000 (64 KB of LDS). */
 int     lrf_debug_tile_ranges(const int32_t* ncomp, int32_t R, int32_t G, int32_t nb, int32_t* gsum, int32_t* ranges,
                               int32_t* toff_out, int32_t* nc_out, void* stream);
+/* k_shade3's tail reductions (csrc/lrf_shade3.inl) on their own: in [T][64] floats (device), one wave per row ->
+ * join[t][l] = join_halves32 (in[t][l] + in[t][l ^ 32]) and sum[t][l] = half_sum32 (the sum of the 32-lane half of lane l, in
+ * the butterfly's order), every lane's value. */
+int     lrf_debug_tile_reduce(const float* in, int32_t T, float* join, float* sum, void* stream);
 void    lrf_debug_set_scene_fuse(int on);         /* lrf_scene_fwd: several fields per march / colour launch (default on); 0 = field by field */
 void    lrf_debug_set_bwd_overlap(int on);        /* lrf_render_bwd: two branches on two streams (default on); 1 + 2 * (n + 1): k_wgrad_w2w3 on the caller's stream (n > 0, default) or on the side stream behind the density scatter (n = 0) */
 void    lrf_debug_set_train_fwd_engine(int bits); /* 8: plane and line gradients by separate scatter kernels; 16: the gradient scatters with fp32 compare-and-swap adds (k_scatter_plane, rounds 2-5) instead of 64-bit fixed point (k_scatter_fix); 256: fixed point for the density tensors only (default: the appearance tensors too where their accumulators fit in LDS, lines up to 479 cells); 1024: no four-channel sweeps (lines of 480 .. 640 cells: the appearance tensors through the compare-and-swap kernel, as before); 512: k_wgrad_w2w3 in its single-buffered 128-row form (rounds 4-5) instead of the double-buffered 64-row one; 32 / 64 / 128: k_train_dgrad3 + k_train_app3 without their row stores / position gradient and X / dz1 products (timing experiments, wrong results) */

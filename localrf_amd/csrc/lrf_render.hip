@@ -1015,7 +1015,7 @@ static Workspace carve(void* ws, int R, int S) {
   w.toff  = reinterpret_cast<int*>(p + off);       off += up256((size_t)(R + 1) * 4);
   w.ncomp = reinterpret_cast<int*>(p + off);       off += up256((size_t)R * 4);
   w.acc   = reinterpret_cast<float*>(p + off);     off += up256((size_t)R * 4);
-  w.cidx  = reinterpret_cast<uint16_t*>(p + off);  off += up256((size_t)R * S * 2);
+  w.cidx  = reinterpret_cast<uint16_t*>(p + off);  off += up256((size_t)R * S * 2);   // (k_shade3 reads aligned dwords of it: an odd R * S ends 2 bytes short of a dword, inside the padding)
   w.cw    = reinterpret_cast<float*>(p + off);     off += up256((size_t)R * S * 4);
   w.part  = reinterpret_cast<float*>(p + off);     off += up256((size_t)R * w.pmax * 12);
   w.rdir  = reinterpret_cast<float*>(p + off);     off += up256((size_t)R * 16);
@@ -1343,6 +1343,13 @@ int lrf_debug_tile_ranges(const int32_t* ncomp, int32_t R, int32_t G, int32_t nb
   const int NG = (R + G - 1) / G;
   hipLaunchKernelGGL(k_group_tiles, dim3((NG + 255) / 256), dim3(256), 0, st, ncomp, R, G, gsum);
   hipLaunchKernelGGL(k_tile_ranges_dbg, dim3(nb), dim3(512), lds, st, gsum, ncomp, R, G, reinterpret_cast<int4*>(ranges), toff_out, nc_out);
+  LRF_HIP(hipGetLastError());
+  return 0;
+}
+int lrf_debug_tile_reduce(const float* in, int32_t T, float* join, float* sum, void* stream) {
+  if (!in || !join || !sum) return set_err("lrf_debug_tile_reduce: null argument");
+  if (T <= 0) return set_err("lrf_debug_tile_reduce: need T > 0");
+  hipLaunchKernelGGL(k_tile_reduce_dbg, dim3(T), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), in, join, sum);
   LRF_HIP(hipGetLastError());
   return 0;
 }

@@ -67,6 +67,34 @@ __device__ __forceinline__ void mma3_step(const uint4* img, int frag0, int strid
   for (int m = 0; m < NM; ++m) acc[m] = mfma32(ah[m], bh, acc[m]);
 }
 
+// The tail's lane sums without LDS round trips (ds_bpermute_b32 shares the LDS pipe with the SIMD partner's fragment reads).
+// Both give, in every lane and bit for bit, what the __shfl_xor butterflies gave (fp32 addition commutes; no NaNs):
+//   join_halves32(v) = v + __shfl_xor(v, 32): v_permlane32_swap of v with itself leaves the low half twice in one
+//     register and the high half twice in the other.
+//   half_sum32(v) = the ladder v += __shfl_xor(v, d), d = 1, 2, 4, 8, 16, every level with the lane's true xor partner:
+//     quad_perm [1,0,3,2] and [2,3,0,1]; lane + 4 for banks 0 and 2 of a row and lane - 4 for banks 1 and 3 (two moves under
+//     bank masks); row_ror:8; v_permlane16_swap pairs the two rows of a half.  Mirrors (row_half_mirror, row_mirror) would
+//     save the second move of the xor 4 level, but they equal the xor partner only while all lanes of a group hold the same
+//     value, and in the tile loop they do not: the compiler contracts the first level of half_sum32(w * s) into
+//     fma(w, s, partner's rounded product), so the two lanes of a pair differ in the last bit and lane 0's sum is the tree
+//     over its true partners.
+// All 64 lanes must be enabled (finding 20: a DPP read from a disabled lane returns 0): the tile loop is wave-uniform.
+template <int CTRL, int BANKS = 0xf>
+__device__ __forceinline__ float dpp_mov(float old, float v) {
+  return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(old), __float_as_int(v), CTRL, 0xf, BANKS, BANKS == 0xf));
+}
+__device__ __forceinline__ float join_halves32(float v) {
+  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
+}
+__device__ __forceinline__ float half_sum32(float v) {
+  v += dpp_mov<0xB1>(0.0f, v);                                 // quad_perm [1,0,3,2]
+  v += dpp_mov<0x4E>(0.0f, v);                                 // quad_perm [2,3,0,1]
+  v += dpp_mov<0x114, 0xa>(dpp_mov<0x104, 0x5>(0.0f, v), v);   // row_shl:4 into banks 0, 2; row_shr:4 into banks 1, 3
+  v += dpp_mov<0x128>(0.0f, v);                                // row_ror:8
+  const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
+}
 
 // the 12 appearance products of lane half h for plane p: channels 12 h .. 12 h + 11 of the dense texel, three aligned
 // float4 per tap (tensoRF.py:153-195); same per-channel arithmetic, in the same order, as gather_app6_plane32
@@ -272,10 +300,20 @@ __global__ __launch_bounds__(512) void k_tile_ranges_dbg(const int* __restrict__
   }
 }
 
-// What one wave needs to know about a tile before it can gather.  The loads are issued one tile ahead and first used at
-// the top of the next tile, so the dependent chain tile -> ray -> sample index -> distance is off the critical path.
+// Test hook (lrf_debug_tile_reduce): the tail's two lane sums on a caller's rows, one wave per row of 64 floats; every lane's result.
+__global__ __launch_bounds__(64) void k_tile_reduce_dbg(const float* __restrict__ in, float* __restrict__ join, float* __restrict__ sum) {
+  const size_t i = (size_t)blockIdx.x * 64 + threadIdx.x;
+  const float v = in[i];
+  join[i] = join_halves32(v);
+  sum[i] = half_sum32(v);
+}
+
+// What one wave needs to know about a tile before it can gather.  Its vector loads (sample index, weight, direction) are
+// issued one tile ahead and first used at the top of the next tile, so the chain sample index -> distance is off the
+// critical path; the walk tile -> ray (LDS) and the origin (scalar loads) are waited for where they are issued.
 struct Hdr3 {
-  int ray, tile_in_ray, k;       // ray, tile number inside the ray, this lane's sample index into z
+  int ray, tile_in_ray;          // ray, tile number inside the ray
+  uint32_t k2, ksh;              // this lane's sample index into z: bits ksh .. ksh + 15 (ksh = 0 or 16) of the dword k2
   int cnt;                       // samples in the tile (SAVE)
   float wgt;                     // this lane's compositing weight (0 for lanes beyond the tile's count and for K half 1)
   float o[3], d[3];              // ray origin, unit direction

@@ -2,9 +2,18 @@
 // NW waves per workgroup (one workgroup per CU).  LDSTOFF: every workgroup builds the tile offsets of its own rays in LDS
 // from k_march's group sums (toff_g: one int per gsz rays; tile_range_fill, lrf_shade3.inl; two launches per render,
 // k_march -> k_shade3); otherwise k_scan_tiles_n<32> ran before and toff_g holds the R + 1 offsets.
-// TIMED (debug, lrf_debug_set_dump): s_memtime totals per wave -> dump[block][wave][8] =
-// {rest of the prologue, header + position, gather + split, image requested + z stored, tile offsets and range (ends behind
-// the image's arrival), chain, tiles, finalize}
+// TIMED (debug, lrf_debug_set_dump): s_memtime totals per wave -> dump[block][wave][10] =
+// {rest of the prologue, position + taps, gather + split, image requested + z stored, tile offsets and range (ends behind
+// the image's arrival), chain + head (up to s_setprio 0), tiles, finalize, tail (joins, sigmoid, tile sum, store), top of the
+// loop up to the next header's loads issued}
+// Round trips in the tile loop (profiles/r24_shade3_round_trips.md; a wave's tile time is a serial sum, two waves per SIMD hide
+// only part of it).  Gone: the tail's six dependent ds_bpermute_b32 trips (join_halves32 / half_sum32: lane swaps and DPP
+// adds, same bits) and the wait for the next tile's sample index (loaded as the aligned dword of the 16-bit list, taken
+// apart at its use).  Still exposed per tile, measured and left: the queue pull (the compiler's wave-level rewrite of the
+// atomic waits for the DS return at once), the offset walk and the ray's count (LDS, waited where read), the ray origin
+// (uniform address: scalar loads, waited at once; forcing them onto the vector path gained nothing beside the index
+// dword), and vmcnt(0) at the loop top, which on the back edge waits for the previous tile's partial store (a wait in
+// front of the loop that takes it off the back edge made the step slower).
 // SAVE: the training forward -- the same tile loop additionally writes what SaveOut3 lists (128 B of feat + 32 B of mask bits
 // + 12 B of colour per shaded sample): the eval kernel IS the row-saving forward, its rgb is bit-identical to the eval's.
 // LRF_SHADE3_MULTI (this file is included twice, lrf_shade3.inl): the second kernel, k_shade3m, renders several fields in one
@@ -25,7 +34,7 @@ __global__ __launch_bounds__(NW * 64) void LRF_SHADE3_NAME(
     uint32_t flags, const float* __restrict__ acc, float* __restrict__ rgb_out, float* __restrict__ acc_out, SaveOut3 sv, int gsz) {
   constexpr int NT = NW * 64;
   extern __shared__ uint4 s_dyn[];                             // image, tail, z[S][, toff[R + 1]]
-  unsigned long long tk[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tlast = 0;
+  unsigned long long tk[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, tlast = 0;
 #define LRF_TICK(i) do { if (TIMED) { const unsigned long long now_ = __builtin_readcyclecounter(); tk[i] += now_ - tlast; tlast = now_; } } while (0)
   if (TIMED) tlast = __builtin_readcyclecounter();
   uint4* img = s_dyn;
@@ -134,7 +143,9 @@ __global__ __launch_bounds__(NW * 64) void LRF_SHADE3_NAME(
     const int cnt = min(ITEM3, w_nc - j0);
     hd.cnt = cnt;
     const size_t ci = (size_t)w_ray * S + j0 + (n < cnt ? n : 0);
-    hd.k = cidx[ci];
+    // the aligned dword that holds the 16-bit index, taken apart where it is used: a global_load_ushort is zero-extended -- and
+    // so waited for -- right here (the last dword of the list ends inside cidx's 256-byte padding when R * S is odd: carve())
+    hd.k2 = reinterpret_cast<const uint32_t*>(cidx)[ci >> 1]; hd.ksh = (uint32_t)(ci & 1) << 4;
     hd.wgt = (n < cnt && h == 0) ? cw[ci] : 0.0f;              // the two K halves of a sample hold the same colour: count it once
 #if LRF_SHADE3_MULTI
     const float* rp = rays + (size_t)multi_io(mf, fk, w_ray) * 6;       // (a chunk of a larger batch: the caller's ray index)
@@ -151,10 +162,11 @@ __global__ __launch_bounds__(NW * 64) void LRF_SHADE3_NAME(
   if (t_cur < T1) cur = issue_header(t_cur);
   while (t_cur < T1) {
     asm volatile("" ::: "memory");                             // keep the LDS fragment reads inside the loop
-    int t_after = 0;                                           // the tile after next: its number is back long before it is needed
+    int t_after = 0;                                           // the tile after next (first used at the end of the iteration, but the DS return is awaited here: see the top of the file)
     if (lane == 0) t_after = atomicAdd(&s_next, 1);
     Hdr3 nxt = cur;
     if (t_nxt < T1) nxt = issue_header(t_nxt);
+    LRF_TICK(9);                                               // (TIMED only: queue pull, offset walk, header loads issued)
     // ------------------------------------------------------------------ gather
     bf16x8 xh[5], xl[5];
     float vb[3];
@@ -166,7 +178,7 @@ __global__ __launch_bounds__(NW * 64) void LRF_SHADE3_NAME(
         vb[c] = tail[W32_T_B3 + c] + wv.x * dh[0] + wv.y * dh[1] + wv.z * dh[2];
       }
       float x[3], u[3];
-      sample_point(f, cur.o, dh, s_z[cur.k], x, u);
+      sample_point(f, cur.o, dh, s_z[__builtin_amdgcn_ubfe(cur.k2, cur.ksh, 16u)], x, u);
       const AxisTaps at = axis_taps(f.pw[0], f.ph[0], f.ll[0], u);
       if (TIMED) { asm volatile("" : "+v"(u[0]), "+v"(u[1]), "+v"(u[2])); LRF_TICK(1); }
       float X[40];
@@ -289,7 +301,10 @@ __global__ __launch_bounds__(NW * 64) void LRF_SHADE3_NAME(
         }
     }
     __builtin_amdgcn_s_setprio(0);
-    o0 += __shfl_xor(o0, 32, 64); o1 += __shfl_xor(o1, 32, 64); o2 += __shfl_xor(o2, 32, 64);
+    if (TIMED) { asm volatile("" : "+v"(o0), "+v"(o1), "+v"(o2)); LRF_TICK(5); }
+    // The tail moves lanes in the VALU (join_halves32, half_sum32: lane swaps and DPP adds), not through the LDS pipe: six
+    // dependent ds_bpermute_b32 round trips per tile stood here, behind the SIMD partner's fragment reads.  Same bits.
+    o0 = join_halves32(o0); o1 = join_halves32(o1); o2 = join_halves32(o2);
     // w * sigmoid(x) (:133, :632), hardware exp2 / reciprocal; partial colour of the tile = sum over its samples
     const float s0 = __frcp_rn(1.0f + __expf(-(o0 + vb[0]))), s1 = __frcp_rn(1.0f + __expf(-(o1 + vb[1]))), s2 = __frcp_rn(1.0f + __expf(-(o2 + vb[2])));
     if constexpr (SAVE) {
@@ -300,19 +315,15 @@ __global__ __launch_bounds__(NW * 64) void LRF_SHADE3_NAME(
         cp[0] = s0; cp[1] = s1; cp[2] = s2;
       }
     }
-    float cr = cur.wgt * s0;
-    float cg = cur.wgt * s1;
-    float cb = cur.wgt * s2;
-#pragma unroll
-    for (int dd = 1; dd < 32; dd <<= 1) {
-      cr += __shfl_xor(cr, dd, 64); cg += __shfl_xor(cg, dd, 64); cb += __shfl_xor(cb, dd, 64);
-    }
+    const float cr = half_sum32(cur.wgt * s0);
+    const float cg = half_sum32(cur.wgt * s1);
+    const float cb = half_sum32(cur.wgt * s2);
     if (lane == 0) {
       float* pp = part + ((size_t)cur.ray * pmax + cur.tile_in_ray) * 3;
       pp[0] = cr; pp[1] = cg; pp[2] = cb;
     }
     cur = nxt; t_cur = t_nxt; t_nxt = __builtin_amdgcn_readfirstlane(t_after);
-    LRF_TICK(5);
+    LRF_TICK(8);                                               // (TIMED only: the tail; its store is not waited for here)
     tk[6] += 1;
   }
 #if LRF_SHADE3_MULTI
@@ -330,8 +341,8 @@ __global__ __launch_bounds__(NW * 64) void LRF_SHADE3_NAME(
 #endif
   LRF_TICK(7);
   if (TIMED && f.dump && lane == 0) {
-    unsigned long long* dp = reinterpret_cast<unsigned long long*>(f.dump) + ((size_t)blockIdx.x * NW + wave) * 8;
-    for (int i = 0; i < 8; ++i) dp[i] = tk[i];
+    unsigned long long* dp = reinterpret_cast<unsigned long long*>(f.dump) + ((size_t)blockIdx.x * NW + wave) * 10;
+    for (int i = 0; i < 10; ++i) dp[i] = tk[i];
   }
 #undef LRF_TICK
 }

@@ -78,19 +78,19 @@ def stage_shade3_phases():
     with torch.no_grad():
         for _ in range(300):
             f(rays, white_bg=True, is_train=False, N_samples=1536)
-    names = ["prologue rest", "header+position", "gather+split", "image copy", "scan", "chain", "tiles", "finalize"]
+    names = ["prologue rest", "position+taps", "gather+split", "image copy", "scan", "chain+head", "tiles", "finalize", "tail", "loop top"]
     nw = int(os.environ.get("DIAG_NW", "8"))                 # waves per workgroup of the build under test
-    buf = torch.zeros(256 * nw * 8, dtype=torch.int64, device="cuda")
+    buf = torch.zeros(256 * nw * 10, dtype=torch.int64, device="cuda")
     with torch.no_grad():
         lib.lrf_debug_set_dump(buf.data_ptr())
         f(rays, white_bg=True, is_train=False, N_samples=1536)
         torch.cuda.synchronize()
         lib.lrf_debug_set_dump(None)
-    t = buf.view(256 * nw, 8).double()
+    t = buf.view(256 * nw, 10).double()
     tiles = t[:, 6].sum()
-    tot = t[:, [0, 1, 2, 3, 4, 5, 7]].sum(1)
+    tot = t[:, [0, 1, 2, 3, 4, 5, 7, 8, 9]].sum(1)
     log(f"k_shade3 {nw} waves: tiles {int(tiles)} | cycles per wave: prologue {float(t[:, 0].mean()):.0f} (+ image copy {float(t[:, 3].mean()):.0f}, scan {float(t[:, 4].mean()):.0f}) finalize {float(t[:, 7].mean()):.0f} | per tile: " +
-        " ".join(f"{names[i]} {float(t[:, i].sum() / tiles):.0f}" for i in (1, 2, 5)) +
+        " ".join(f"{names[i]} {float(t[:, i].sum() / tiles):.0f}" for i in (9, 1, 2, 5, 8)) +
         f" | per-wave total mean/min/max {float(tot.mean()):.0f}/{float(tot.min()):.0f}/{float(tot.max()):.0f}")
     for eng in ("bf16x3", "f32"):
         f.mlp_engine = eng
