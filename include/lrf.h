@@ -826,6 +826,46 @@ int lrf_mesh_smooth_bounds(const float* vertices, int64_t Nv, int32_t* out /* de
 size_t lrf_mesh_smooth_workspace_bytes(int64_t Nv, int64_t Nf);
 int lrf_mesh_smooth(const LrfMeshSmooth* m, float* vertices_out, int64_t* info /* device [8] */, void* workspace, void* stream);
 
+/* An indexed triangle mesh rasterised into V pinhole cameras, and two depth maps compared (csrc/lrf_mesh_raster.inl states the
+ * coverage rule, the arithmetic and the kernels).  The inverse of lrf_tsdf_integrate: depth [V,H,W] comes out in the convention
+ * that call takes (a multiple of the un-normalised pixel direction whose z is -1), 0.0 where no face was hit.  One ray per pixel
+ * tested against every face with edge functions of exact sign, the nearest kept hit chosen by a 64-bit unsigned atomicMin over
+ * (depth bits, face index): every call leaves the same bytes on every run, for every launch geometry and stream.
+ * lrf_mesh_rasterize: vertices [Nv,3], faces [Nf,3] (both may be null when Nf = 0), rgb8 [Nv,3] (nullable, with rgb8_out),
+ * cam2world [V,3,4], focal [1] and center [2] on the device.  cull: 0 keeps both orientations, 1 drops the faces seen from
+ * behind their winding's normal, 2 those seen from its side.  A hit is kept when its depth is finite, positive and inside
+ * [d_min, d_max].  Outputs: depth [V,H,W], face int32 [V,H,W] (-1: none), rgb8_out uint8 [V,H,W,3] (the vertex colours under the
+ * hit's barycentric weights in fp64, rounded to nearest, ties to even), weights fp32 [V,H,W,3] (nullable: those weights),
+ * crossings int32 [V,H,W] (nullable: the kept hits of both orientations, whatever cull is), info (device int64 [4]) = faces
+ * skipped for an index outside [0, Nv) (never dereferenced), for two equal indices, for a coordinate that is not finite, 0.
+ * Four launches (two with Nf = 0), no host synchronisation.  workspace: lrf_mesh_rasterize_workspace_bytes(V, H, W, Nf) bytes (0
+ * for refused arguments) = 8 V H W of keys, 8 V Nf of (frame, face) list and its cursor; 8-byte aligned.
+ * Refused before any launch: null or misaligned pointers (float and int32 arrays 4 bytes; info and workspace 8), V, H or W < 1,
+ * V H W >= 2^31, Nv < 0 or >= 2^31, Nf < 0, V Nf >= 2^31, faces without vertices, rgb8 without rgb8_out or the reverse, cull
+ * outside {0, 1, 2}, d_min > d_max (or NaN).
+ * lrf_depth_agreement: mesh_depth and depth [V,H,W] -> counts (device int64 [V,16]) per frame = pixels valid (finite, positive,
+ * inside [d_min, d_max]) in both maps, in mesh_depth only, in depth only, in neither; the sum over the both-valid pixels of
+ * llrint(min(|mesh_depth - depth| / depth, 16) 2^24); three zeros; and at 8 + k the both-valid pixels with |mesh_depth - depth|
+ * <= rel_tols[k] depth.  rel_tols: HOST array of n_tols values >= 0, n_tols <= LRF_AGREEMENT_MAX_TOLS.  error_map [V,H,W]
+ * (nullable): the relative error unclamped, NaN where not both are valid.  Two launches.  Refused before any launch: null or
+ * misaligned pointers, V outside [1, 65535], H or W < 1, V H W >= 2^31, n_tols outside [0, 8], a tolerance that is negative or
+ * NaN, d_min > d_max. */
+#define LRF_AGREEMENT_MAX_TOLS 8
+typedef struct LrfMeshRaster {
+  const float* vertices; const uint8_t* rgb8 /* nullable */; const int32_t* faces;
+  const float* cam2world; const float* focal; const float* center;
+  int64_t Nv, Nf;
+  int32_t V, H, W, cull;
+  float d_min, d_max;
+} LrfMeshRaster;
+size_t lrf_mesh_rasterize_workspace_bytes(int32_t V, int32_t H, int32_t W, int64_t Nf);
+int lrf_mesh_rasterize(const LrfMeshRaster* m, float* depth, int32_t* face, uint8_t* rgb8_out /* nullable */,
+                       float* weights /* nullable */, int32_t* crossings /* nullable */, int64_t* info /* device [4] */,
+                       void* workspace, void* stream);
+int lrf_depth_agreement(const float* mesh_depth, const float* depth, int32_t V, int32_t H, int32_t W,
+                        const float* rel_tols /* host [n_tols] */, int32_t n_tols, float d_min, float d_max,
+                        int64_t* counts /* device [V,16] */, float* error_map /* nullable */, void* stream);
+
 /* Depth quantiles of a ray: the distance at which its accumulated weight first reaches q; q = 0.5 is the median depth, which
  * always lies on a surface the ray met (csrc/lrf_quantile.inl states the arithmetic: fp32 without contraction, one fixed
  * summation order per ray).  With C_i the inclusive prefix sum of the weights lrf_render_fwd leaves in weight_out and i* the

@@ -50,6 +50,12 @@ int     lrf_depth_quantiles_from_weights(const float* w, const float* z, const f
 int     lrf_debug_mesh_vertex_normals(const float* vertices, const int32_t* faces, int64_t Nv, int64_t Nf, float* normals, int64_t* S,
                                       int32_t* E, int64_t* info, void* workspace, void* stream);
 
+/* lrf_mesh_rasterize (include/lrf.h) with the tier threshold given: a (frame, face) pair whose pixel box holds at most small_max
+ * pixels is walked by its own lane, a larger one by a wavefront.  0 sends every pair to the wavefronts, 2^31 - 1 every pair to
+ * its lane; the outputs do not depend on it.  small_max < 0 is refused. */
+int     lrf_debug_mesh_rasterize(const struct LrfMeshRaster* m,float* depth, int32_t* face, uint8_t* rgb8_out, float* weights,
+                                 int32_t* crossings, int64_t* info, void* workspace, int32_t small_max, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -155,6 +155,15 @@ class LrfMeshSmooth(C.Structure):
                 ("s", C.c_int32), ("iterations", C.c_int32), ("pin_boundary", C.c_int32), ("reserved", C.c_int32)]
 
 
+LRF_AGREEMENT_MAX_TOLS = 8
+
+
+class LrfMeshRaster(C.Structure):
+    _fields_ = [("vertices", _f), ("rgb8", C.c_void_p), ("faces", C.c_void_p), ("cam2world", _f), ("focal", _f), ("center", _f),
+                ("Nv", C.c_int64), ("Nf", C.c_int64), ("V", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("cull", C.c_int32),
+                ("d_min", C.c_float), ("d_max", C.c_float)]
+
+
 class LrfTsdfBlocks(C.Structure):
     _fields_ = [("marks", C.c_void_p), ("table", C.c_void_p), ("coords", C.c_void_p), ("tsdf", _f), ("weight", _f), ("rgb", _f),
                 ("Bx", C.c_int32), ("By", C.c_int32), ("Bz", C.c_int32), ("n_blocks", C.c_int32),
@@ -294,6 +303,13 @@ SYMBOLS = {
     "lrf_mesh_smooth_bounds": (C.c_int, [_f, C.c_int64, C.c_void_p, C.c_void_p]),
     "lrf_mesh_smooth_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
     "lrf_mesh_smooth": (C.c_int, [C.POINTER(LrfMeshSmooth), _f, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "lrf_mesh_rasterize_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int64]),
+    "lrf_mesh_rasterize": (C.c_int, [C.POINTER(LrfMeshRaster), _f, C.c_void_p, C.c_void_p, _f, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p]),
+    "lrf_debug_mesh_rasterize": (C.c_int, [C.POINTER(LrfMeshRaster), _f, C.c_void_p, C.c_void_p, _f, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_int32, C.c_void_p]),
+    "lrf_depth_agreement": (C.c_int, [_f, _f, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float), C.c_int32, C.c_float,
+                                      C.c_float, C.c_void_p, _f, C.c_void_p]),
     "lrf_density_gradient": (C.c_int, [C.POINTER(LrfField), _f, C.c_int64, _f, _f, C.c_void_p]),
     "lrf_normals_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "lrf_render_normals": (C.c_int, [C.POINTER(LrfField), _f, _f, C.c_int32, C.c_int32, C.c_uint32, C.c_float, _f, C.c_int32,

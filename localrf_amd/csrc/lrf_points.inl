@@ -75,16 +75,25 @@ __device__ __forceinline__ bool pts_world(const PointsArgs& a, int c, float f, f
   return true;
 }
 
+// the first half of step 3, shared with the mesh rasteriser (lrf_mesh_raster.inl): world point pw into the frame of the camera
+// M [3,4] (camera-to-world): d = pw - t, q = R^T d column by column as (c0 dx + c1 dy) + c2 dz
+__device__ __forceinline__ void to_camera(const float* __restrict__ M, const float (&pw)[3], float (&q)[3]) {
+#pragma clang fp contract(off)
+  const float dx = pw[0] - M[3], dy = pw[1] - M[7], dz = pw[2] - M[11];
+  q[0] = (M[0] * dx + M[4] * dy) + M[8] * dz;
+  q[1] = (M[1] * dx + M[5] * dy) + M[9] * dz;
+  q[2] = (M[2] * dx + M[6] * dy) + M[10] * dz;
+}
+
 // step 3's projection, shared with the TSDF integration (lrf_mesh.inl): world point pw into the camera M [3,4] (camera-to-world)
 // of an H x W pinhole image.  false behind the camera (nz = -q.z <= 0) or outside the image; else nz and the nearest pixel
 // (iu, iw), ties to even.
 __device__ __forceinline__ bool reproject(const float* __restrict__ M, const float (&pw)[3], float f, float cx, float cy, int W,
                                           int H, float& nz, int& iu, int& iw) {
 #pragma clang fp contract(off)
-  const float dx = pw[0] - M[3], dy = pw[1] - M[7], dz = pw[2] - M[11];
-  const float qx = (M[0] * dx + M[4] * dy) + M[8] * dz;
-  const float qy = (M[1] * dx + M[5] * dy) + M[9] * dz;
-  const float qz = (M[2] * dx + M[6] * dy) + M[10] * dz;
+  float q[3];
+  to_camera(M, pw, q);
+  const float qx = q[0], qy = q[1], qz = q[2];
   nz = -qz;
   if (!(nz > 0.0f)) return false;
   const float u = qx / nz * f + cx - 0.5f;

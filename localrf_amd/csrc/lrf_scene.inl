@@ -16,6 +16,11 @@ constexpr int SCENE_TPB = 256;
 
 struct PixDir { float x, y, z; long long col, row; };
 
+// the x and y of a pinhole direction (z = -1) at column col and row row, shared with the mesh rasteriser (lrf_mesh_raster.inl),
+// which walks pixel boxes and has no pixel id to divide
+__device__ __forceinline__ float pinhole_x(float col, float f, float cx) { return (col + 0.5f - cx) / f; }
+__device__ __forceinline__ float pinhole_y(float row, float f, float cy) { return -(row + 0.5f - cy) / f; }
+
 // ids2pixel + get_ray_directions_lean / _360 (same operation order as the torch expressions)
 __device__ __forceinline__ PixDir pixel_dir(long long id, int W, int H, int fov360, float f, float cx, float cy) {
   PixDir p;
@@ -29,8 +34,8 @@ __device__ __forceinline__ PixDir pixel_dir(long long id, int W, int H, int fov3
     p.y = sinf(phi);
     p.z = cosf(phi) * cosf(th);
   } else {
-    p.x = ((float)p.col + 0.5f - cx) / f;
-    p.y = -((float)p.row + 0.5f - cy) / f;
+    p.x = pinhole_x((float)p.col, f, cx);
+    p.y = pinhole_y((float)p.row, f, cy);
     p.z = -1.0f;
   }
   return p;
