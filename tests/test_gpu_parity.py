@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 import torch
 
+import upkeep_cases
 from oracle import vm_render_np as oracle
 from util import (capture_train_ws, check_grads, field_from_golden, field_from_seed, golden_field_dict, kernel_relu_masks,
                   load_golden, make_field, make_rays, port_gradients, quiet, rel_err)
@@ -151,6 +152,19 @@ def test_local_tensorfs_blend_vs_reference_golden(built_lib):
     _check_rays(_np(depths_t), g["depths_testid"])
 
 
+def _decided_inside_flags_are_exact(inside, rays, step, n, near_far, jitter=None):
+    """The flags that may legitimately differ are the undecidable ones (upkeep_cases.flag_sets: the float64 point within the
+    pts tolerance of the box's surface): every other flag is exact, and at most 0.2 % are undecidable."""
+    r = np.asarray(rays, np.float32)
+    assert np.array_equal(np.float32(2) * np.array([[-1, -1, -1], [1, 1, 1]], np.float32), upkeep_cases.AABB)
+    run = lambda dt: oracle.sample_ray_aabb(r[:, :3].astype(dt), r[:, 3:].astype(dt), upkeep_cases.AABB.astype(dt), step, n, near_far,
+                                            None if jitter is None else np.asarray(jitter, dt))
+    (p64, _, i64), (p32, _, _) = run(np.float64), run(np.float32)
+    ins, out = upkeep_cases.flag_sets(p64, upkeep_cases.tolerance(upkeep_cases.rel1_err(p32, p64), "pts"))
+    dec = ins | out
+    assert (~dec).mean() <= 0.002 and np.array_equal(np.asarray(inside, bool)[dec], i64[dec])
+
+
 def test_sample_ray_aabb_vs_oracle(built_lib):
     f = quiet(make_field, [32, 32, 32], "cpu", seed=5).to(DEV)
     rays = make_rays(64, 9, pinhole=True)
@@ -160,6 +174,7 @@ def test_sample_ray_aabb_vs_oracle(built_lib):
                                         f.aabb.cpu().numpy(), float(f.stepSize), 50, f.near_far)
     assert np.abs(_np(t) - to).max() < 1e-5 and np.abs(_np(pts) - po).max() < 1e-4
     assert (inside.cpu().numpy() != io).mean() < 0.002     # points within rounding of the box faces
+    _decided_inside_flags_are_exact(inside.cpu().numpy(), rays.numpy(), float(f.stepSize), 50, f.near_far)
 
 
 def test_sample_ray_aabb_vs_reference_golden(built_lib):
@@ -173,6 +188,8 @@ def test_sample_ray_aabb_vs_reference_golden(built_lib):
         assert np.abs(_np(t) - g["t" + sfx]).max() < 2e-6 * np.abs(g["t" + sfx]).max()
         assert (np.abs(_np(pts) - g["pts" + sfx]) / np.maximum(np.abs(g["pts" + sfx]), 1.0)).max() < 2e-6
         assert (inside.cpu().numpy() != g["inside" + sfx]).mean() < 0.002   # points within rounding of a box face
+        _decided_inside_flags_are_exact(inside.cpu().numpy(), g["rays"], float(g["stepSize"]), int(g["N_samples"]),
+                                        [float(v) for v in g["near_far"]], None if jit is None else g["U"])
 
 
 @pytest.mark.parametrize("name", ["field_small_eval", "field_small_floater", "field_small_train_grad"])
