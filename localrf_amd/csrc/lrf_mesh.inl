@@ -1,6 +1,6 @@
 // lrf_mesh.inl -- rendered depth fused into a truncated signed-distance (TSDF) volume, and a triangle mesh extracted from a
-// scalar volume (included by lrf_render.hip after lrf_encode.inl and lrf_points.inl, whose enc_rgb_byte, pts_finite_pos,
-// reproject and k_points_scan it shares).  The fusion and the extraction are each written once, here, for the dense volume
+// scalar volume (included by lrf_render.hip after lrf_encode.inl and lrf_points.inl, whose enc_rgb_byte, pts_finite_pos and
+// reproject it shares; the scans and the host helpers are lrf_compact.inl's).  The fusion and the extraction are each written once, here, for the dense volume
 // of this file and for the block-sparse one of lrf_tsdf_blocks.inl: the two differ only in where a lattice point is stored.
 //
 // A lattice has Nx x Ny x Nz points at origin + (ix, iy, iz) * voxel.  Per point: tsdf (starts at 1), weight (starts at 0), rgb
@@ -195,27 +195,6 @@ struct MeshArgs {
   __device__ __forceinline__ float colour(int o, int c) const { return rgb[3 * (size_t)o + c]; }
 };
 
-// exclusive prefix of v over the workgroup's MESH_NT threads (every thread calls), total = the workgroup's sum
-__device__ __forceinline__ unsigned mesh_block_scan(unsigned v, unsigned* part, unsigned& total) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  unsigned s = v;
-  for (int off = 1; off < 64; off <<= 1) {
-    const unsigned t = __shfl_up(s, off, 64);
-    if (lane >= off) s += t;
-  }
-  if (lane == 63) part[wv] = s;
-  __syncthreads();
-  unsigned pre = 0;
-  total = 0;
-  for (int w = 0; w < MESH_NT / 64; ++w) {
-    const unsigned q = part[w];
-    if (w < wv) pre += q;
-    total += q;
-  }
-  __syncthreads();
-  return pre + (s - v);
-}
-
 // the inside bits of tetrahedron T's four corners, from the cell's eight
 template <int T>
 __device__ __forceinline__ unsigned mesh_tet_mask(unsigned cm) {
@@ -271,8 +250,8 @@ __device__ __forceinline__ void mesh_count_body(const View& a, unsigned* part, u
     }
   }
   unsigned vtot, ftot;
-  const unsigned vpre = mesh_block_scan(__popc(mask), part, vtot);
-  mesh_block_scan(ntri, part, ftot);
+  const unsigned vpre = block_scan_excl<MESH_NT>(__popc(mask), part, vtot);
+  block_scan_excl<MESH_NT>(ntri, part, ftot);
   if (pl < a.n) info[pl] = mask | ntri << 7 | vpre << 11;
   if (threadIdx.x == 0) { wgv[blockIdx.x] = vtot; wgf[blockIdx.x] = ftot; }
 }
@@ -310,7 +289,7 @@ __device__ __forceinline__ void mesh_emit_body(const View& a, unsigned* part, co
   const unsigned me = pl < a.n ? info[pl] : 0u;
   const unsigned mask = me & 127u, ntri = (me >> 7) & 15u;
   unsigned ftot;
-  const unsigned fpre = mesh_block_scan(ntri, part, ftot);
+  const unsigned fpre = block_scan_excl<MESH_NT>(ntri, part, ftot);
   if (!(mask | ntri)) return;
   const MeshPoint q = a.point((int)pl);
   if (mask) {
@@ -373,21 +352,13 @@ static long long mesh_points(int Nx, int Ny, int Nz) {
   return n >= (1ll << 31) || n * Nz >= (1ll << 31) ? 0 : n * Nz;
 }
 
-// refuses with "<who>: <what>"
-static int mesh_refuse(const char* who, const char* what) {
-  char msg[160];
-  snprintf(msg, sizeof msg, "%s: %s", who, what);
-  return set_err(msg);
-}
-
 // the checks of the frames every fusion entry point takes (dense and block-sparse); 0 when they pass
 static int tsdf_check_frames(const char* who, const float* depth, const float* c2w, const float* focal, const float* center, int V,
                              int H, int W, float d_min, float d_max) {
-  if (V < 1 || H < 1 || W < 1 || (long long)V * H * W >= (1ll << 31)) return mesh_refuse(who, "need V, H, W >= 1 and V H W < 2^31");
-  if (!depth || !c2w || !focal || !center) return mesh_refuse(who, "null argument");
-  if (!(d_min <= d_max)) return mesh_refuse(who, "need d_min <= d_max");
-  if (((uintptr_t)depth | (uintptr_t)c2w | (uintptr_t)focal | (uintptr_t)center) & 3)
-    return mesh_refuse(who, "float and int32 arrays must be 4-byte aligned");
+  if (V < 1 || H < 1 || W < 1 || (long long)V * H * W >= (1ll << 31)) return refuse(who, "need V, H, W >= 1 and V H W < 2^31");
+  if (!depth || !c2w || !focal || !center) return refuse(who, "null argument");
+  if (!(d_min <= d_max)) return refuse(who, "need d_min <= d_max");
+  if (misaligned(3, depth, c2w, focal, center)) return refuse(who, "float and int32 arrays must be 4-byte aligned");
   return 0;
 }
 
@@ -395,16 +366,30 @@ static int tsdf_check_frames(const char* who, const float* depth, const float* c
 static int mesh_check_outputs(const char* who, bool has_rgb, float level, bool gated, float min_weight, int64_t max_vertices,
                               int64_t max_faces, const float* vertices, const uint8_t* rgb8_out, const int32_t* faces,
                               const int64_t* counts, const void* workspace) {
-  if (!vertices || !faces || !counts || !workspace) return mesh_refuse(who, "null argument");
-  if (has_rgb != !!rgb8_out) return mesh_refuse(who, "rgb and rgb8_out go together");
-  if (level != level) return mesh_refuse(who, "level must not be NaN");
-  if (gated && !(min_weight > 0.0f)) return mesh_refuse(who, "min_weight must be > 0");
+  if (!vertices || !faces || !counts || !workspace) return refuse(who, "null argument");
+  if (has_rgb != !!rgb8_out) return refuse(who, "rgb and rgb8_out go together");
+  if (level != level) return refuse(who, "level must not be NaN");
+  if (gated && !(min_weight > 0.0f)) return refuse(who, "min_weight must be > 0");
   if (max_vertices < 0 || max_faces < 0 || max_vertices >= (1ll << 31) || max_faces >= (1ll << 31))
-    return mesh_refuse(who, "max_vertices and max_faces must lie in [0, 2^31)");
-  if (((uintptr_t)vertices | (uintptr_t)faces | (uintptr_t)workspace) & 3)
-    return mesh_refuse(who, "float and int32 arrays and the workspace must be 4-byte aligned");
-  if ((uintptr_t)counts & 7) return mesh_refuse(who, "counts must be 8-byte aligned");
+    return refuse(who, "max_vertices and max_faces must lie in [0, 2^31)");
+  if (misaligned(3, vertices, faces, workspace)) return refuse(who, "float and int32 arrays and the workspace must be 4-byte aligned");
+  if (misaligned(7, counts)) return refuse(who, "counts must be 8-byte aligned");
   return 0;
+}
+
+// the workspace of an extraction over n storage points (dense and block-sparse): info, then the vertex and the face counts of
+// the n_wg workgroups, one array of two rows for the scan; pad: a byte that keeps the size above 0 for an empty pool
+struct MeshWs { int n_wg; unsigned* info; unsigned* wgv; unsigned* wgf; size_t bytes; };
+static MeshWs mesh_carve(void* workspace, long long n, size_t pad) {
+  Carver c(workspace);
+  MeshWs w;
+  w.n_wg = (int)blocks_for(n, MESH_NT);
+  w.info = c.take<unsigned>((size_t)n);
+  w.wgv = c.take<unsigned>(w.n_wg);
+  w.wgf = c.take<unsigned>(w.n_wg);
+  c.take<char>(pad);
+  w.bytes = c.bytes();
+  return w;
 }
 
 }  // namespace lrf
@@ -421,8 +406,7 @@ extern "C" int lrf_tsdf_integrate(const LrfTsdfVolume* vol, const float* depth, 
   if (!vol->rgb != !rgb8) return set_err("lrf_tsdf_integrate: the volume's rgb and the frames' rgb8 go together");
   if (!(vol->voxel > 0.0f)) return set_err("lrf_tsdf_integrate: voxel must be > 0");
   if (!(vol->trunc > 0.0f)) return set_err("lrf_tsdf_integrate: trunc must be > 0");
-  if (((uintptr_t)vol->tsdf | (uintptr_t)vol->weight | (uintptr_t)vol->rgb) & 3)
-    return set_err("lrf_tsdf_integrate: float arrays must be 4-byte aligned");
+  if (misaligned(3, vol->tsdf, vol->weight, vol->rgb)) return set_err("lrf_tsdf_integrate: float arrays must be 4-byte aligned");
   TsdfArgs a;
   memset(&a, 0, sizeof(a));
   a.tsdf = vol->tsdf; a.weight = vol->weight; a.rgb = vol->rgb;
@@ -430,19 +414,14 @@ extern "C" int lrf_tsdf_integrate(const LrfTsdfVolume* vol, const float* depth, 
   a.n_items = (long long)vol->Nz * vol->Ny * a.nxc;
   a.ox = vol->origin[0]; a.oy = vol->origin[1]; a.oz = vol->origin[2]; a.voxel = vol->voxel; a.trunc = vol->trunc;
   a.V = V; a.H = H; a.W = W; a.d_min = d_min; a.d_max = d_max;
-  const long long n_wg = (a.n_items + TSDF_NT / 64 - 1) / (TSDF_NT / 64);   // <= 2^31 / 4
-  hipLaunchKernelGGL(k_tsdf_integrate, dim3((unsigned)n_wg), dim3(TSDF_NT), 0, reinterpret_cast<hipStream_t>(stream), a, depth,
-                     rgb8, cam2world, focal, center);
-  LRF_HIP(hipGetLastError());
-  return 0;
+  return launch(k_tsdf_integrate, blocks_for(a.n_items, TSDF_NT / 64), TSDF_NT, reinterpret_cast<hipStream_t>(stream), a, depth, rgb8,
+                cam2world, focal, center);                          // <= 2^31 / 4 workgroups
 }
 
 extern "C" size_t lrf_mesh_workspace_bytes(int32_t Nx, int32_t Ny, int32_t Nz) {
   using namespace lrf;
   const long long n = mesh_points(Nx, Ny, Nz);
-  if (!n) return 0;
-  const size_t n_wg = (size_t)((n + MESH_NT - 1) / MESH_NT);
-  return ((size_t)n * sizeof(unsigned) + 2 * n_wg * sizeof(unsigned) + 255) & ~(size_t)255;
+  return n ? mesh_carve(nullptr, n, 0).bytes : 0;
 }
 
 extern "C" int lrf_mesh_extract(const LrfMeshExtract* m, int64_t max_vertices, int64_t max_faces, float* vertices,
@@ -453,8 +432,7 @@ extern "C" int lrf_mesh_extract(const LrfMeshExtract* m, int64_t max_vertices, i
   if (!n) return set_err("lrf_mesh_extract: need Nx, Ny, Nz >= 1 and Nx Ny Nz < 2^31");
   if (!m->value) return set_err("lrf_mesh_extract: null argument");
   if (!(m->voxel > 0.0f)) return set_err("lrf_mesh_extract: voxel must be > 0");
-  if (((uintptr_t)m->value | (uintptr_t)m->weight | (uintptr_t)m->rgb) & 3)
-    return set_err("lrf_mesh_extract: float arrays must be 4-byte aligned");
+  if (misaligned(3, m->value, m->weight, m->rgb)) return set_err("lrf_mesh_extract: float arrays must be 4-byte aligned");
   if (mesh_check_outputs("lrf_mesh_extract", m->rgb != nullptr, m->level, m->weight != nullptr, m->min_weight, max_vertices,
                          max_faces, vertices, rgb8_out, faces, counts, workspace))
     return 1;
@@ -464,18 +442,10 @@ extern "C" int lrf_mesh_extract(const LrfMeshExtract* m, int64_t max_vertices, i
   a.Nx = m->Nx; a.Ny = m->Ny; a.Nz = m->Nz; a.n = (int)n;
   a.ox = m->origin[0]; a.oy = m->origin[1]; a.oz = m->origin[2]; a.voxel = m->voxel;
   a.level = m->level; a.min_weight = m->min_weight;
-  const int n_wg = (int)((n + MESH_NT - 1) / MESH_NT);
-  unsigned* info = static_cast<unsigned*>(workspace);
-  unsigned* wgv = info + n;
-  unsigned* wgf = wgv + n_wg;
+  const MeshWs w = mesh_carve(workspace, n, 0);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(k_mesh_count, dim3(n_wg), dim3(MESH_NT), 0, st, a, info, wgv, wgf);
-  LRF_HIP(hipGetLastError());
-  hipLaunchKernelGGL(k_points_scan, dim3(2), dim3(PTS_SCAN_NT), 0, st, wgv, n_wg, reinterpret_cast<long long*>(counts));
-  LRF_HIP(hipGetLastError());
+  LRF_TRY(launch(k_mesh_count, w.n_wg, MESH_NT, st, a, w.info, w.wgv, w.wgf));
+  LRF_TRY(launch(k_points_scan, 2, PTS_SCAN_NT, st, w.wgv, w.n_wg, reinterpret_cast<long long*>(counts)));
   if (max_vertices == 0 && max_faces == 0) return 0;                 // a counting call: no row could be written
-  hipLaunchKernelGGL(k_mesh_emit, dim3(n_wg), dim3(MESH_NT), 0, st, a, info, wgv, wgf, (long long)max_vertices,
-                     (long long)max_faces, vertices, rgb8_out, faces);
-  LRF_HIP(hipGetLastError());
-  return 0;
+  return launch(k_mesh_emit, w.n_wg, MESH_NT, st, a, w.info, w.wgv, w.wgf, max_vertices, max_faces, vertices, rgb8_out, faces);
 }

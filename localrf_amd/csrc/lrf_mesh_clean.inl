@@ -1,5 +1,5 @@
 // lrf_mesh_clean.inl -- the connected components of an indexed triangle mesh, and the mesh without its small components
-// (included by lrf_render.hip after lrf_mesh.inl; it calls k_points_scan of lrf_points.inl).  Integers only: no float
+// (included by lrf_render.hip; the scan, the keep list and the host helpers are lrf_compact.inl's).  Integers only: no float
 // arithmetic touches the data, positions and colours are copied bit for bit.
 //
 // A mesh is vertices [Nv,3] fp32, rgb8 [Nv,3] uint8 (nullable) and faces [Nf,3] int32.  Two vertices are connected when a face
@@ -52,8 +52,7 @@ constexpr int MF_NT = 256;
 constexpr int MF_WORDS_WAVE = 4;                                    // 64-item steps per wave
 constexpr int MF_WORDS_WG = (MF_NT / 64) * MF_WORDS_WAVE;           // keep words per workgroup
 constexpr int MF_ITEMS_WG = 64 * MF_WORDS_WG;
-
-__device__ __forceinline__ bool cc_in(int i, int n) { return (unsigned)i < (unsigned)n; }
+static_assert(MF_WORDS_WG == KEEP_GROUP, "a workgroup marks one group of a keep list");
 
 __global__ __launch_bounds__(CC_NT) void k_cc_init(int* __restrict__ parent, int Nv) {
   const long long i = (long long)blockIdx.x * CC_NT + threadIdx.x;
@@ -69,11 +68,11 @@ __global__ __launch_bounds__(CC_NT) void k_cc_hook(int* parent, const int* __res
   int flag = 0;
   if (f < Nf) {
     const int a = faces[3 * f], b = faces[3 * f + 1], c = faces[3 * f + 2];
-    if (!(cc_in(a, Nv) && cc_in(b, Nv) && cc_in(c, Nv))) {
+    if (!(in_range(a, Nv) && in_range(b, Nv) && in_range(c, Nv))) {
       flag = 2;
     } else {
       const int ra = parent[a], rb = parent[b], rc = parent[c];
-      if (!(cc_in(ra, Nv) && cc_in(rb, Nv) && cc_in(rc, Nv))) {     // not a parent array of k_cc_init: refused like a bad face
+      if (!(in_range(ra, Nv) && in_range(rb, Nv) && in_range(rc, Nv))) {     // not a parent array of k_cc_init: refused like a bad face
         flag = 2;
       } else {
         const int m = min(ra, min(rb, rc));
@@ -92,7 +91,7 @@ __global__ __launch_bounds__(CC_NT) void k_cc_shorten(int* parent, int Nv) {
   const long long i = (long long)blockIdx.x * CC_NT + threadIdx.x;
   if (i >= Nv) return;
   int r = parent[i];
-  if (!cc_in(r, Nv)) return;
+  if (!in_range(r, Nv)) return;
   // parents strictly decrease along the walk (parent[x] <= x, equal only at a root), so it ends within Nv steps
   for (int step = 0; step < Nv; ++step) {
     const int p = parent[r];
@@ -128,15 +127,15 @@ __global__ __launch_bounds__(CC_NT) void k_cc_count_faces(const int* __restrict_
   int label = -1;
   if (f < Nf) {
     const int a = faces[3 * f], b = faces[3 * f + 1], c = faces[3 * f + 2];
-    if (cc_in(a, Nv) && cc_in(b, Nv) && cc_in(c, Nv)) label = labels[a];
+    if (in_range(a, Nv) && in_range(b, Nv) && in_range(c, Nv)) label = labels[a];
   }
-  cc_count(faces_of, label, cc_in(label, Nv));
+  cc_count(faces_of, label, in_range(label, Nv));
 }
 
 __global__ __launch_bounds__(CC_NT) void k_cc_count_vertices(const int* __restrict__ labels, int Nv, int* __restrict__ vertices_of) {
   const long long i = (long long)blockIdx.x * CC_NT + threadIdx.x;
   const int label = i < Nv ? labels[i] : -1;
-  cc_count(vertices_of, label, cc_in(label, Nv));
+  cc_count(vertices_of, label, in_range(label, Nv));
 }
 
 __global__ __launch_bounds__(CC_NT) void k_cc_summary(const int* __restrict__ labels, const int* __restrict__ faces_of, int Nv,
@@ -144,15 +143,10 @@ __global__ __launch_bounds__(CC_NT) void k_cc_summary(const int* __restrict__ la
   const long long i = (long long)blockIdx.x * CC_NT + threadIdx.x;
   const bool root = i < Nv && labels[i] == (int)i;
   int nf = root ? faces_of[i] : 0;
-  const unsigned long long roots = __ballot(root), with = __ballot(nf > 0);
+  wave_count(&summary[0], root);
+  wave_count(&summary[1], nf > 0);
   for (int off = 32; off > 0; off >>= 1) nf = max(nf, __shfl_xor(nf, off, 64));
-  if ((threadIdx.x & 63) == 0 && roots) {
-    atomicAdd(&summary[0], (unsigned long long)__popcll(roots));
-    if (with) {
-      atomicAdd(&summary[1], (unsigned long long)__popcll(with));
-      atomicMax(&summary[2], (unsigned long long)nf);
-    }
-  }
+  if ((threadIdx.x & 63) == 0 && nf > 0) atomicMax(&summary[2], (unsigned long long)nf);
 }
 
 struct MeshFilterArgs {
@@ -179,11 +173,11 @@ __global__ __launch_bounds__(MF_NT) void k_mesh_filter_mark(MeshFilterArgs a, un
       int v = (int)i;
       if (which) {
         const int fa = a.faces[3 * i], fb = a.faces[3 * i + 1], fc = a.faces[3 * i + 2];
-        v = cc_in(fa, a.Nv) && cc_in(fb, a.Nv) && cc_in(fc, a.Nv) ? fa : -1;
+        v = in_range(fa, a.Nv) && in_range(fb, a.Nv) && in_range(fc, a.Nv) ? fa : -1;
       }
       if (v >= 0) {
         const int l = a.labels[v];
-        keep = cc_in(l, a.Nv) && a.faces_of[l] >= a.threshold;
+        keep = in_range(l, a.Nv) && a.faces_of[l] >= a.threshold;
         root = keep && !which && l == v;
       }
     }
@@ -213,136 +207,112 @@ __global__ __launch_bounds__(MF_NT) void k_mesh_filter_mark(MeshFilterArgs a, un
   }
 }
 
-// the row of kept vertex v (bits, pre, wg: the vertex halves)
-__device__ __forceinline__ int mf_row(const unsigned long long* __restrict__ bits, const unsigned* __restrict__ pre,
-                                      const unsigned* __restrict__ wg, int v) {
-  const int w = v >> 6;
-  return (int)(wg[w / MF_WORDS_WG] + pre[w] + (unsigned)__popcll(bits[w] & ((1ull << (v & 63)) - 1ull)));
-}
-
 __global__ __launch_bounds__(MF_NT) void k_mesh_filter_write(MeshFilterArgs a, const unsigned long long* __restrict__ bits,
                                                              const unsigned* __restrict__ pre, const unsigned* __restrict__ wg,
                                                              unsigned* __restrict__ vertices_out, uint8_t* __restrict__ rgb8_out,
                                                              int* __restrict__ faces_out) {
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int which = blockIdx.y;
-  const size_t words = (size_t)a.n_wg * MF_WORDS_WG;
+  const KeepList verts{bits, pre, wg}, mine = verts.pick(which, (size_t)a.n_wg * MF_WORDS_WG);
   const long long word0 = (long long)blockIdx.x * MF_WORDS_WG + wv * MF_WORDS_WAVE;
-  const unsigned base = wg[(size_t)which * a.n_wg + blockIdx.x];
 #pragma unroll
   for (int k = 0; k < MF_WORDS_WAVE; ++k) {
-    const unsigned long long m = bits[which * words + word0 + k];
-    if (!((m >> lane) & 1ull)) continue;                            // a set bit: the item exists, a face's indices are in range
-    const size_t row = (size_t)base + pre[which * words + word0 + k] + (unsigned)__popcll(m & ((1ull << lane) - 1ull));
     const size_t i = (size_t)(word0 + k) * 64 + lane;
+    if (!mine.kept(i)) continue;                                    // a set bit: the item exists, a face's indices are in range
+    const size_t row = mine.rank(i);
     if (!which) {
       for (int c = 0; c < 3; ++c) vertices_out[3 * row + c] = a.vertices[3 * i + c];
       if (rgb8_out)
         for (int c = 0; c < 3; ++c) rgb8_out[3 * row + c] = a.rgb8[3 * i + c];
     } else {
-      for (int c = 0; c < 3; ++c) faces_out[3 * row + c] = mf_row(bits, pre, wg, a.faces[3 * i + c]);
+      for (int c = 0; c < 3; ++c) faces_out[3 * row + c] = (int)verts.rank(a.faces[3 * i + c]);
     }
   }
 }
 
-static bool cc_shape(long long Nv, long long Nf) { return Nv >= 1 && Nf >= 0 && Nv < (1ll << 31) && Nf < (1ll << 31); }
-static unsigned cc_blocks(long long n) { return (unsigned)((n + CC_NT - 1) / CC_NT); }
 static long long mf_workgroups(long long Nv, long long Nf) {
   const long long n = Nv > Nf ? Nv : Nf;
   return (n + MF_ITEMS_WG - 1) / MF_ITEMS_WG;                       // >= 1, < 2^21
+}
+
+// the workspace of a filter: the keep lists of the vertices and the faces, each padded to n_wg workgroups, and a third row of
+// counts (the kept roots) for the scan
+struct MeshFilterWs { int n_wg; unsigned long long* bits; unsigned* pre; unsigned* wg; size_t bytes; };
+static MeshFilterWs mf_carve(void* workspace, long long Nv, long long Nf) {
+  Carver c(workspace);
+  MeshFilterWs w;
+  w.n_wg = (int)mf_workgroups(Nv, Nf);
+  const size_t words = (size_t)w.n_wg * MF_WORDS_WG;
+  w.bits = c.take<unsigned long long>(2 * words);
+  w.pre = c.take<unsigned>(2 * words);
+  w.wg = c.take<unsigned>(3 * (size_t)w.n_wg);
+  w.bytes = c.bytes();
+  return w;
 }
 
 }  // namespace lrf
 
 extern "C" int lrf_mesh_components_init(int32_t* parent, int64_t Nv, void* stream) {
   using namespace lrf;
-  if (!cc_shape(Nv, 0)) return set_err("lrf_mesh_components_init: need 1 <= Nv < 2^31");
+  if (!mesh_shape(Nv, 0)) return set_err("lrf_mesh_components_init: need 1 <= Nv < 2^31");
   if (!parent) return set_err("lrf_mesh_components_init: null argument");
-  if ((uintptr_t)parent & 3) return set_err("lrf_mesh_components_init: parent must be 4-byte aligned");
-  hipLaunchKernelGGL(k_cc_init, dim3(cc_blocks(Nv)), dim3(CC_NT), 0, reinterpret_cast<hipStream_t>(stream), parent, (int)Nv);
-  LRF_HIP(hipGetLastError());
-  return 0;
+  if (misaligned(3, parent)) return set_err("lrf_mesh_components_init: parent must be 4-byte aligned");
+  return launch(k_cc_init, blocks_for(Nv, CC_NT), CC_NT, reinterpret_cast<hipStream_t>(stream), parent, Nv);
 }
 
 extern "C" int lrf_mesh_components_round(int32_t* parent, const int32_t* faces, int64_t Nv, int64_t Nf, int32_t* changed,
                                          void* stream) {
   using namespace lrf;
-  if (!cc_shape(Nv, Nf)) return set_err("lrf_mesh_components_round: need 1 <= Nv < 2^31 and 0 <= Nf < 2^31");
+  if (!mesh_shape(Nv, Nf)) return set_err("lrf_mesh_components_round: need 1 <= Nv < 2^31 and 0 <= Nf < 2^31");
   if (!parent || !changed || (Nf && !faces)) return set_err("lrf_mesh_components_round: null argument");
-  if (((uintptr_t)parent | (uintptr_t)faces | (uintptr_t)changed) & 3)
-    return set_err("lrf_mesh_components_round: int32 arrays must be 4-byte aligned");
+  if (misaligned(3, parent, faces, changed)) return set_err("lrf_mesh_components_round: int32 arrays must be 4-byte aligned");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(k_cc_clear, dim3(1), dim3(64), 0, st, changed);
-  LRF_HIP(hipGetLastError());
-  if (Nf) {
-    hipLaunchKernelGGL(k_cc_hook, dim3(cc_blocks(Nf)), dim3(CC_NT), 0, st, parent, faces, (int)Nv, (int)Nf, changed);
-    LRF_HIP(hipGetLastError());
-  }
-  hipLaunchKernelGGL(k_cc_shorten, dim3(cc_blocks(Nv)), dim3(CC_NT), 0, st, parent, (int)Nv);
-  LRF_HIP(hipGetLastError());
-  return 0;
+  LRF_TRY(launch(k_cc_clear, 1, 64, st, changed));
+  if (Nf) LRF_TRY(launch(k_cc_hook, blocks_for(Nf, CC_NT), CC_NT, st, parent, faces, Nv, Nf, changed));
+  return launch(k_cc_shorten, blocks_for(Nv, CC_NT), CC_NT, st, parent, Nv);
 }
 
 extern "C" int lrf_mesh_components_count(const int32_t* labels, const int32_t* faces, int64_t Nv, int64_t Nf, int32_t* faces_of,
                                          int32_t* vertices_of, int64_t* summary, void* stream) {
   using namespace lrf;
-  if (!cc_shape(Nv, Nf)) return set_err("lrf_mesh_components_count: need 1 <= Nv < 2^31 and 0 <= Nf < 2^31");
+  if (!mesh_shape(Nv, Nf)) return set_err("lrf_mesh_components_count: need 1 <= Nv < 2^31 and 0 <= Nf < 2^31");
   if (!labels || !faces_of || !vertices_of || !summary || (Nf && !faces)) return set_err("lrf_mesh_components_count: null argument");
-  if (((uintptr_t)labels | (uintptr_t)faces | (uintptr_t)faces_of | (uintptr_t)vertices_of) & 3)
-    return set_err("lrf_mesh_components_count: int32 arrays must be 4-byte aligned");
-  if ((uintptr_t)summary & 7) return set_err("lrf_mesh_components_count: summary must be 8-byte aligned");
+  if (misaligned(3, labels, faces, faces_of, vertices_of)) return set_err("lrf_mesh_components_count: int32 arrays must be 4-byte aligned");
+  if (misaligned(7, summary)) return set_err("lrf_mesh_components_count: summary must be 8-byte aligned");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(k_cc_zero, dim3(cc_blocks(Nv)), dim3(CC_NT), 0, st, faces_of, vertices_of, (int)Nv,
-                     reinterpret_cast<long long*>(summary));
-  LRF_HIP(hipGetLastError());
-  if (Nf) {
-    hipLaunchKernelGGL(k_cc_count_faces, dim3(cc_blocks(Nf)), dim3(CC_NT), 0, st, labels, faces, (int)Nv, (int)Nf, faces_of);
-    LRF_HIP(hipGetLastError());
-  }
-  hipLaunchKernelGGL(k_cc_count_vertices, dim3(cc_blocks(Nv)), dim3(CC_NT), 0, st, labels, (int)Nv, vertices_of);
-  LRF_HIP(hipGetLastError());
-  hipLaunchKernelGGL(k_cc_summary, dim3(cc_blocks(Nv)), dim3(CC_NT), 0, st, labels, faces_of, (int)Nv,
-                     reinterpret_cast<unsigned long long*>(summary));
-  LRF_HIP(hipGetLastError());
-  return 0;
+  const unsigned nbv = blocks_for(Nv, CC_NT);
+  LRF_TRY(launch(k_cc_zero, nbv, CC_NT, st, faces_of, vertices_of, Nv, reinterpret_cast<long long*>(summary)));
+  if (Nf) LRF_TRY(launch(k_cc_count_faces, blocks_for(Nf, CC_NT), CC_NT, st, labels, faces, Nv, Nf, faces_of));
+  LRF_TRY(launch(k_cc_count_vertices, nbv, CC_NT, st, labels, Nv, vertices_of));
+  return launch(k_cc_summary, nbv, CC_NT, st, labels, faces_of, Nv, reinterpret_cast<unsigned long long*>(summary));
 }
 
 extern "C" size_t lrf_mesh_filter_workspace_bytes(int64_t Nv, int64_t Nf) {
   using namespace lrf;
-  if (!cc_shape(Nv, Nf)) return 0;
-  const size_t n_wg = (size_t)mf_workgroups(Nv, Nf);
-  return (n_wg * (2 * MF_WORDS_WG * (sizeof(unsigned long long) + sizeof(unsigned)) + 3 * sizeof(unsigned)) + 255) & ~(size_t)255;
+  return mesh_shape(Nv, Nf) ? mf_carve(nullptr, Nv, Nf).bytes : 0;
 }
 
 extern "C" int lrf_mesh_filter(const LrfMeshFilter* m, int32_t threshold, float* vertices_out, uint8_t* rgb8_out,
                                int32_t* faces_out, int64_t* counts, void* workspace, void* stream) {
   using namespace lrf;
   if (!m) return set_err("lrf_mesh_filter: null argument");
-  if (!cc_shape(m->Nv, m->Nf)) return set_err("lrf_mesh_filter: need 1 <= Nv < 2^31 and 0 <= Nf < 2^31");
+  if (!mesh_shape(m->Nv, m->Nf)) return set_err("lrf_mesh_filter: need 1 <= Nv < 2^31 and 0 <= Nf < 2^31");
   if (!m->vertices || !m->labels || !m->faces_of || !vertices_out || !counts || !workspace || (m->Nf && (!m->faces || !faces_out)))
     return set_err("lrf_mesh_filter: null argument");
   if (!m->rgb8 != !rgb8_out) return set_err("lrf_mesh_filter: rgb8 and rgb8_out go together");
   if (threshold < 0) return set_err("lrf_mesh_filter: threshold must be >= 0");
-  if (((uintptr_t)m->vertices | (uintptr_t)m->faces | (uintptr_t)m->labels | (uintptr_t)m->faces_of | (uintptr_t)vertices_out |
-       (uintptr_t)faces_out) & 3)
+  if (misaligned(3, m->vertices, m->faces, m->labels, m->faces_of, vertices_out, faces_out))
     return set_err("lrf_mesh_filter: float and int32 arrays must be 4-byte aligned");
-  if (((uintptr_t)counts | (uintptr_t)workspace) & 7) return set_err("lrf_mesh_filter: counts and workspace must be 8-byte aligned");
+  if (misaligned(7, counts, workspace)) return set_err("lrf_mesh_filter: counts and workspace must be 8-byte aligned");
+  const MeshFilterWs w = mf_carve(workspace, m->Nv, m->Nf);
   MeshFilterArgs a;
   memset(&a, 0, sizeof(a));
   a.vertices = reinterpret_cast<const unsigned*>(m->vertices); a.rgb8 = m->rgb8; a.faces = m->faces;
   a.labels = m->labels; a.faces_of = m->faces_of;
-  a.Nv = (int)m->Nv; a.Nf = (int)m->Nf; a.threshold = threshold; a.n_wg = (int)mf_workgroups(m->Nv, m->Nf);
-  const size_t words = (size_t)a.n_wg * MF_WORDS_WG;
-  unsigned long long* bits = static_cast<unsigned long long*>(workspace);
-  unsigned* pre = reinterpret_cast<unsigned*>(bits + 2 * words);
-  unsigned* wg = pre + 2 * words;
+  a.Nv = (int)m->Nv; a.Nf = (int)m->Nf; a.threshold = threshold; a.n_wg = w.n_wg;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(k_mesh_filter_mark, dim3(a.n_wg, 2), dim3(MF_NT), 0, st, a, bits, pre, wg);
-  LRF_HIP(hipGetLastError());
-  hipLaunchKernelGGL(k_points_scan, dim3(3), dim3(PTS_SCAN_NT), 0, st, wg, a.n_wg, reinterpret_cast<long long*>(counts));
-  LRF_HIP(hipGetLastError());
-  hipLaunchKernelGGL(k_mesh_filter_write, dim3(a.n_wg, a.Nf ? 2 : 1), dim3(MF_NT), 0, st, a, bits, pre, wg,
-                     reinterpret_cast<unsigned*>(vertices_out), rgb8_out, faces_out);
-  LRF_HIP(hipGetLastError());
-  return 0;
+  LRF_TRY(launch(k_mesh_filter_mark, dim3(w.n_wg, 2), MF_NT, st, a, w.bits, w.pre, w.wg));
+  LRF_TRY(launch(k_points_scan, 3, PTS_SCAN_NT, st, w.wg, w.n_wg, reinterpret_cast<long long*>(counts)));
+  return launch(k_mesh_filter_write, dim3(w.n_wg, a.Nf ? 2 : 1), MF_NT, st, a, w.bits, w.pre, w.wg,
+                reinterpret_cast<unsigned*>(vertices_out), rgb8_out, faces_out);
 }

@@ -1,6 +1,6 @@
 // lrf_mesh_raster.inl -- an indexed triangle mesh rasterised into V pinhole cameras, and two depth maps compared (included by
-// lrf_render.hip after lrf_mesh_smooth.inl; it reuses to_camera and pts_finite_pos of lrf_points.inl, pinhole_x / pinhole_y of
-// lrf_scene.inl and sm_face of lrf_mesh_smooth.inl).  The inverse of k_tsdf_integrate: mesh -> depth at a pose, in the depth
+// lrf_render.hip; it reuses to_camera and pts_finite_pos of lrf_points.inl, pinhole_x / pinhole_y of lrf_scene.inl and sm_face of
+// lrf_mesh_smooth.inl; the wave-leader counts and the host helpers are lrf_compact.inl's).  The inverse of k_tsdf_integrate: mesh -> depth at a pose, in the depth
 // convention of lrf_points.inl (a multiple of the un-normalised pixel direction whose z is -1).  The output bytes are a fixed
 // function of the input: one consistent ray per pixel, an exact-sign coverage test, and an integer minimum per pixel.
 //
@@ -195,12 +195,9 @@ __global__ __launch_bounds__(RS_NT) void k_rs_faces(RasterArgs a, unsigned long 
     kind = rs_face(a, v, f, q, idx);
   }
   const bool first = v == 0;
-  const unsigned long long b1 = __ballot(first && kind == 1), b2 = __ballot(first && kind == 2), b3 = __ballot(first && kind == 3);
-  if ((threadIdx.x & 63) == 0) {
-    if (b1) atomicAdd(&info[0], (unsigned long long)__popcll(b1));
-    if (b2) atomicAdd(&info[1], (unsigned long long)__popcll(b2));
-    if (b3) atomicAdd(&info[2], (unsigned long long)__popcll(b3));
-  }
+  wave_count(&info[0], first && kind == 1);
+  wave_count(&info[1], first && kind == 2);
+  wave_count(&info[2], first && kind == 3);
   const float fo = a.focal[0], cx = a.center[0], cy = a.center[1];
   int i0 = 0, i1 = -1, j0 = 0, j1 = -1;
   const bool boxed = kind == 0 && rs_box(q, fo, cx, cy, a.W, a.H, i0, i1, j0, j1);
@@ -351,54 +348,55 @@ static bool raster_shape(long long V, long long H, long long W, long long Nf) {
   return V >= 1 && H >= 1 && W >= 1 && Nf >= 0 && V * H * W < (1ll << 31) && Nf < (1ll << 31) && V * Nf < (1ll << 31);
 }
 
+// the workspace: a key per pixel, the list of large (frame, face) pairs, its cursor (8 bytes)
+struct RasterWs { unsigned long long* keys; int2* list; int* cursor; size_t bytes; };
+static RasterWs raster_carve(void* workspace, long long n_px, long long n_pairs) {
+  Carver c(workspace);
+  RasterWs w;
+  w.keys = c.take<unsigned long long>((size_t)n_px);
+  w.list = c.take<int2>((size_t)n_pairs);
+  w.cursor = c.take<int>(2);
+  w.bytes = c.bytes();
+  return w;
+}
+
 static int raster_run(const char* who, const LrfMeshRaster* m, float* depth, int32_t* face, uint8_t* rgb8_out, float* weights,
                       int32_t* crossings, int64_t* info, void* workspace, int small_max, void* stream) {
-  char msg[160];
-  auto refuse = [&](const char* what) { snprintf(msg, sizeof msg, "%s: %s", who, what); return set_err(msg); };
-  if (!m) return refuse("null argument");
+  if (!m) return refuse(who, "null argument");
   if (!raster_shape(m->V, m->H, m->W, m->Nf) || m->Nv < 0 || m->Nv >= (1ll << 31) || (m->Nf > 0 && m->Nv < 1))
-    return refuse("need V, H, W >= 1, V H W < 2^31, 0 <= Nv < 2^31, 0 <= Nf, V Nf < 2^31 and vertices for the faces");
-  if (!m->cam2world || !m->focal || !m->center || !depth || !face || !info || !workspace) return refuse("null argument");
-  if (m->Nf > 0 && (!m->vertices || !m->faces)) return refuse("null argument");
-  if (!m->rgb8 != !rgb8_out) return refuse("rgb8 and rgb8_out go together");
-  if (m->cull < 0 || m->cull > 2) return refuse("cull must be 0 (none), 1 (back) or 2 (front)");
-  if (!(m->d_min <= m->d_max)) return refuse("need d_min <= d_max");
-  if (small_max < 0) return refuse("small_max must be >= 0");
-  if (((uintptr_t)m->vertices | (uintptr_t)m->faces | (uintptr_t)m->cam2world | (uintptr_t)m->focal | (uintptr_t)m->center |
-       (uintptr_t)depth | (uintptr_t)face | (uintptr_t)weights | (uintptr_t)crossings) & 3)
-    return refuse("float and int32 arrays must be 4-byte aligned");
-  if (((uintptr_t)info | (uintptr_t)workspace) & 7) return refuse("info and workspace must be 8-byte aligned");
+    return refuse(who, "need V, H, W >= 1, V H W < 2^31, 0 <= Nv < 2^31, 0 <= Nf, V Nf < 2^31 and vertices for the faces");
+  if (!m->cam2world || !m->focal || !m->center || !depth || !face || !info || !workspace) return refuse(who, "null argument");
+  if (m->Nf > 0 && (!m->vertices || !m->faces)) return refuse(who, "null argument");
+  if (!m->rgb8 != !rgb8_out) return refuse(who, "rgb8 and rgb8_out go together");
+  if (m->cull < 0 || m->cull > 2) return refuse(who, "cull must be 0 (none), 1 (back) or 2 (front)");
+  if (!(m->d_min <= m->d_max)) return refuse(who, "need d_min <= d_max");
+  if (small_max < 0) return refuse(who, "small_max must be >= 0");
+  if (misaligned(3, m->vertices, m->faces, m->cam2world, m->focal, m->center, depth, face, weights, crossings))
+    return refuse(who, "float and int32 arrays must be 4-byte aligned");
+  if (misaligned(7, info, workspace)) return refuse(who, "info and workspace must be 8-byte aligned");
   RasterArgs a;
   memset(&a, 0, sizeof(a));
   a.vertices = m->vertices; a.rgb8 = m->rgb8; a.faces = m->faces; a.c2w = m->cam2world; a.focal = m->focal; a.center = m->center;
   a.Nv = (int)m->Nv; a.Nf = (int)m->Nf; a.V = m->V; a.H = m->H; a.W = m->W; a.cull = m->cull;
   a.d_min = m->d_min; a.d_max = m->d_max; a.small_max = small_max;
   const long long n_px = (long long)m->V * m->H * m->W, n_pairs = (long long)m->V * m->Nf;
-  unsigned long long* keys = static_cast<unsigned long long*>(workspace);
-  int2* list = reinterpret_cast<int2*>(keys + n_px);
-  int* cursor = reinterpret_cast<int*>(list + n_pairs);
+  const RasterWs w = raster_carve(workspace, n_px, n_pairs);
   unsigned long long* inf = reinterpret_cast<unsigned long long*>(info);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(k_rs_init, dim3((unsigned)((n_px + RS_NT - 1) / RS_NT)), dim3(RS_NT), 0, st, keys, crossings, n_px, cursor, inf);
-  LRF_HIP(hipGetLastError());
+  LRF_TRY(launch(k_rs_init, blocks_for(n_px, RS_NT), RS_NT, st, w.keys, crossings, n_px, w.cursor, inf));
   if (n_pairs) {
-    hipLaunchKernelGGL(k_rs_faces, dim3((unsigned)((n_pairs + RS_NT - 1) / RS_NT)), dim3(RS_NT), 0, st, a, keys, crossings, cursor, list, inf);
-    LRF_HIP(hipGetLastError());
-    const long long wgs = std::min<long long>(RS_LARGE_WGS, (n_pairs + RS_NT / 64 - 1) / (RS_NT / 64));
-    hipLaunchKernelGGL(k_rs_large, dim3((unsigned)wgs, RS_LARGE_SLICES), dim3(RS_NT), 0, st, a, keys, crossings, cursor, list);
-    LRF_HIP(hipGetLastError());
+    LRF_TRY(launch(k_rs_faces, blocks_for(n_pairs, RS_NT), RS_NT, st, a, w.keys, crossings, w.cursor, w.list, inf));
+    const unsigned wgs = std::min<unsigned>(RS_LARGE_WGS, blocks_for(n_pairs, RS_NT / 64));
+    LRF_TRY(launch(k_rs_large, dim3(wgs, RS_LARGE_SLICES), RS_NT, st, a, w.keys, crossings, w.cursor, w.list));
   }
-  hipLaunchKernelGGL(k_rs_resolve, dim3((unsigned)((n_px + RS_NT - 1) / RS_NT)), dim3(RS_NT), 0, st, a, keys, depth, face, rgb8_out, weights);
-  LRF_HIP(hipGetLastError());
-  return 0;
+  return launch(k_rs_resolve, blocks_for(n_px, RS_NT), RS_NT, st, a, w.keys, depth, face, rgb8_out, weights);
 }
 
 }  // namespace lrf
 
 extern "C" size_t lrf_mesh_rasterize_workspace_bytes(int32_t V, int32_t H, int32_t W, int64_t Nf) {
   using namespace lrf;
-  if (!raster_shape(V, H, W, Nf)) return 0;
-  return ((size_t)V * H * W * 8 + (size_t)V * (size_t)Nf * 8 + 8 + 255) & ~(size_t)255;
+  return raster_shape(V, H, W, Nf) ? raster_carve(nullptr, (long long)V * H * W, V * Nf).bytes : 0;
 }
 
 extern "C" int lrf_mesh_rasterize(const LrfMeshRaster* m, float* depth, int32_t* face, uint8_t* rgb8_out, float* weights,
@@ -421,8 +419,8 @@ extern "C" int lrf_depth_agreement(const float* mesh_depth, const float* depth, 
   if (!(d_min <= d_max)) return set_err("lrf_depth_agreement: need d_min <= d_max");
   for (int k = 0; k < n_tols; ++k)
     if (!(rel_tols[k] >= 0.0f)) return set_err("lrf_depth_agreement: a tolerance must be >= 0");
-  if (((uintptr_t)mesh_depth | (uintptr_t)depth | (uintptr_t)error_map) & 3) return set_err("lrf_depth_agreement: float arrays must be 4-byte aligned");
-  if ((uintptr_t)counts & 7) return set_err("lrf_depth_agreement: counts must be 8-byte aligned");
+  if (misaligned(3, mesh_depth, depth, error_map)) return set_err("lrf_depth_agreement: float arrays must be 4-byte aligned");
+  if (misaligned(7, counts)) return set_err("lrf_depth_agreement: counts must be 8-byte aligned");
   AgreeArgs g;
   memset(&g, 0, sizeof(g));
   g.a = mesh_depth; g.b = depth; g.V = V; g.H = H; g.W = W; g.n_tol = n_tols; g.d_min = d_min; g.d_max = d_max;
@@ -430,10 +428,6 @@ extern "C" int lrf_depth_agreement(const float* mesh_depth, const float* depth, 
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   unsigned long long* c = reinterpret_cast<unsigned long long*>(counts);
   const long long words = (long long)V * AG_WORDS;
-  hipLaunchKernelGGL(k_ag_zero, dim3((unsigned)((words + RS_NT - 1) / RS_NT)), dim3(RS_NT), 0, st, c, words);
-  LRF_HIP(hipGetLastError());
-  const int per = AG_NT * AG_PX;
-  hipLaunchKernelGGL(k_depth_agreement, dim3((unsigned)(((long long)H * W + per - 1) / per), (unsigned)V), dim3(AG_NT), 0, st, g, c, error_map);
-  LRF_HIP(hipGetLastError());
-  return 0;
+  LRF_TRY(launch(k_ag_zero, blocks_for(words, RS_NT), RS_NT, st, c, words));
+  return launch(k_depth_agreement, dim3(blocks_for((long long)H * W, AG_NT * AG_PX), (unsigned)V), AG_NT, st, g, c, error_map);
 }

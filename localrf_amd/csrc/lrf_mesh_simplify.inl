@@ -1,6 +1,7 @@
 // lrf_mesh_simplify.inl -- an indexed triangle mesh simplified by uniform vertex clustering (Rossignac-Borrel): every vertex
 // falls into a cell of a uniform grid, the vertices of a cell become one vertex at their mean, faces follow their vertices
-// (included by lrf_render.hip after lrf_mesh_clean.inl; it reuses cc_in, the MF_* word layout and k_points_scan unchanged).
+// (included by lrf_render.hip; the keep lists, their scans and the host helpers are lrf_compact.inl's; lrf_mesh_clean.inl's
+// mf_workgroups sizes the face lists).
 // The output bytes are a fixed function of the input: integer sums, fp64 operations that are each rounded on their own, and a
 // choice among duplicate faces that does not depend on the order of arrival.  No sort, no floating-point atomics.
 //
@@ -93,13 +94,6 @@ __device__ __forceinline__ long long ms_linear(const MsGrid& g, const int* i) {
   return (c[2] * g.dims[1] + c[1]) * g.dims[0] + c[0];
 }
 
-// the rank of set bit i: bits, pre per word, wg per MF_WORDS_WG words (after its scan)
-__device__ __forceinline__ int ms_rank(const unsigned long long* __restrict__ bits, const unsigned* __restrict__ pre,
-                                       const unsigned* __restrict__ wg, long long i) {
-  const long long w = i >> 6;
-  return (int)(wg[w / MF_WORDS_WG] + pre[w] + (unsigned)__popcll(bits[w] & ((1ull << (i & 63)) - 1ull)));
-}
-
 __global__ __launch_bounds__(64) void k_ms_bounds_init(int* __restrict__ out) {
   const int t = threadIdx.x;
   if (t < 3) out[t] = 0x7fffffff;
@@ -113,7 +107,7 @@ __global__ __launch_bounds__(MS_NT) void k_ms_bounds(const float* __restrict__ v
   unsigned long long q[3];
   const bool have = v < Nv;
   const bool ok = have && ms_cell(vertices + 3 * v, g.origin, g.cell, i, q);
-  const unsigned long long good = __ballot(ok), bad = __ballot(have && !ok);
+  const unsigned long long good = __ballot(ok);
   int lo[3], hi[3];
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
@@ -124,13 +118,11 @@ __global__ __launch_bounds__(MS_NT) void k_ms_bounds(const float* __restrict__ v
       hi[k] = max(hi[k], __shfl_xor(hi[k], off, 64));
     }
   }
-  if ((threadIdx.x & 63) == 0) {
-    if (good) {
+  if ((threadIdx.x & 63) == 0 && good) {
 #pragma unroll
-      for (int k = 0; k < 3; ++k) { atomicMin(&out[k], lo[k]); atomicMax(&out[3 + k], hi[k]); }
-    }
-    if (bad) atomicOr(&out[6], 1);
+    for (int k = 0; k < 3; ++k) { atomicMin(&out[k], lo[k]); atomicMax(&out[3 + k], hi[k]); }
   }
+  wave_or(&out[6], have && !ok, 1);
 }
 
 __global__ __launch_bounds__(MS_NT) void k_ms_zero(unsigned long long* __restrict__ zero, size_t n_zero,
@@ -154,25 +146,19 @@ __global__ __launch_bounds__(MS_NT) void k_ms_mark(const float* __restrict__ ver
   // a mesh in extraction order has runs of one cell: the first lane of a run of equal cells speaks for it
   const long long before = __shfl_up(lin, 1, 64);
   if (lin >= 0 && ((threadIdx.x & 63) == 0 || before != lin)) atomicOr(&cell_bits[lin >> 6], 1ull << (lin & 63));
-  const unsigned long long out = __ballot(have && lin < 0);
-  if ((threadIdx.x & 63) == 0 && out) atomicOr(flag, 2);
+  wave_or(flag, have && lin < 0, 2);
 }
 
-// bits, pre: [gridDim.y][words]; wg: [gridDim.y][words / MF_WORDS_WG]; words is a multiple of MF_WORDS_WG
+// the pre and wg of gridDim.y stacked keep lists (KeepList::pick) from their bits; words is a multiple of KEEP_GROUP
 __global__ __launch_bounds__(MS_NT) void k_ms_count_words(const unsigned long long* __restrict__ bits, unsigned* __restrict__ pre,
                                                           unsigned* __restrict__ wg, long long words) {
   const long long w = (long long)blockIdx.x * MS_NT + threadIdx.x;
   const size_t at = (size_t)blockIdx.y * words;
   const unsigned c = w < words ? (unsigned)__popcll(bits[at + w]) : 0u;
-  unsigned s = c;
-#pragma unroll
-  for (int off = 1; off < MF_WORDS_WG; off <<= 1) {
-    const unsigned t = __shfl_up(s, off, MF_WORDS_WG);
-    if ((threadIdx.x & (MF_WORDS_WG - 1)) >= off) s += t;
-  }
+  const unsigned s = wave_scan_incl<KEEP_GROUP>(c);
   if (w < words) {
     pre[at + w] = s - c;
-    if ((threadIdx.x & (MF_WORDS_WG - 1)) == MF_WORDS_WG - 1) wg[(size_t)blockIdx.y * (words / MF_WORDS_WG) + w / MF_WORDS_WG] = s;
+    if ((threadIdx.x & (KEEP_GROUP - 1)) == KEEP_GROUP - 1) wg[(size_t)blockIdx.y * (words / KEEP_GROUP) + w / KEEP_GROUP] = s;
   }
 }
 
@@ -190,8 +176,8 @@ __global__ __launch_bounds__(MS_NT) void k_ms_accumulate(const float* __restrict
   int cl = -1;
   if (v < Nv) {
     if (ms_cell(vertices + 3 * v, g.origin, g.cell, i, s)) lin = ms_linear(g, i);
-    if (lin >= 0) cl = ms_rank(cell_bits, pre, wg, lin);
-    if (!cc_in(cl, Nv)) cl = -1;                                    // cannot happen after k_ms_mark of the same vertices
+    if (lin >= 0) cl = (int)KeepList{cell_bits, pre, wg}.rank(lin);
+    if (!in_range(cl, Nv)) cl = -1;                                    // cannot happen after k_ms_mark of the same vertices
     if (cl >= 0 && rgb8) {
 #pragma unroll
       for (int c = 0; c < 3; ++c) n[1 + c] = rgb8[3 * v + c];
@@ -239,7 +225,7 @@ __global__ __launch_bounds__(MS_NT) void k_ms_faces_map(const int* __restrict__ 
   if (f < Nf) {
     const int a = faces[3 * f], b = faces[3 * f + 1], c = faces[3 * f + 2];
     int k0 = -1, k1 = -1, k2 = -1;
-    if (!(cc_in(a, Nv) && cc_in(b, Nv) && cc_in(c, Nv))) {
+    if (!(in_range(a, Nv) && in_range(b, Nv) && in_range(c, Nv))) {
       bad = true;
     } else {
       const int ca = cluster_of[a], cb = cluster_of[b], cc = cluster_of[c];
@@ -257,11 +243,8 @@ __global__ __launch_bounds__(MS_NT) void k_ms_faces_map(const int* __restrict__ 
     }
     tri[3 * f] = k0; tri[3 * f + 1] = k1; tri[3 * f + 2] = k2;
   }
-  const unsigned long long nb = __ballot(bad), nd = __ballot(degenerate);
-  if ((threadIdx.x & 63) == 0) {
-    if (nb) atomicOr(flag, 1);
-    if (nd) atomicAdd(&counts[3], (unsigned long long)__popcll(nd));
-  }
+  wave_or(flag, bad, 1);
+  wave_count(&counts[3], degenerate);
 }
 
 __device__ __forceinline__ unsigned long long ms_hash(int k0, int k1, int k2) {
@@ -283,7 +266,7 @@ __global__ __launch_bounds__(MS_NT) void k_ms_faces_insert(const int* __restrict
   for (unsigned long long step = 0; step <= mask; ++step) {
     const int old = atomicCAS(&table[slot], -1, (int)f);
     if (old == -1) return;
-    if (!cc_in(old, Nf)) return;                                    // not a table of k_ms_zero
+    if (!in_range(old, Nf)) return;                                    // not a table of k_ms_zero
     if (tri[3 * (size_t)old] == k0 && tri[3 * (size_t)old + 1] == k1 && tri[3 * (size_t)old + 2] == k2) {
       atomicMin(&table[slot], (int)f);
       return;
@@ -302,7 +285,7 @@ __global__ __launch_bounds__(MS_NT) void k_ms_faces_keep(const int* __restrict__
   int k0 = -1, k1 = -1, k2 = -1;
   if (f < Nf) {
     k0 = tri[3 * f]; k1 = tri[3 * f + 1]; k2 = tri[3 * f + 2];
-    keyed = cc_in(k0, n_clusters_max) && cc_in(k1, n_clusters_max) && cc_in(k2, n_clusters_max);
+    keyed = in_range(k0, n_clusters_max) && in_range(k1, n_clusters_max) && in_range(k2, n_clusters_max);
   }
   if (keyed) {
     if (!dedupe) {
@@ -311,7 +294,7 @@ __global__ __launch_bounds__(MS_NT) void k_ms_faces_keep(const int* __restrict__
       unsigned long long slot = ms_hash(k0, k1, k2) & mask;
       for (unsigned long long step = 0; step <= mask; ++step) {     // read-only: the table is the launch before's
         const int s = table[slot];
-        if (!cc_in(s, Nf)) break;                                   // an empty slot: cannot happen for an inserted key
+        if (!in_range(s, Nf)) break;                                   // an empty slot: cannot happen for an inserted key
         if (tri[3 * (size_t)s] == k0 && tri[3 * (size_t)s + 1] == k1 && tri[3 * (size_t)s + 2] == k2) { keep = s == (int)f; break; }
         slot = (slot + 1) & mask;
       }
@@ -322,11 +305,9 @@ __global__ __launch_bounds__(MS_NT) void k_ms_faces_keep(const int* __restrict__
     atomicOr(&ref_bits[k1 >> 6], 1ull << (k1 & 63));
     atomicOr(&ref_bits[k2 >> 6], 1ull << (k2 & 63));
   }
-  const unsigned long long m = __ballot(keep), dup = __ballot(keyed && !keep);
-  if ((threadIdx.x & 63) == 0) {
-    face_bits[f >> 6] = m;
-    if (dup) atomicAdd(&counts[4], (unsigned long long)__popcll(dup));
-  }
+  const unsigned long long m = __ballot(keep);
+  if ((threadIdx.x & 63) == 0) face_bits[f >> 6] = m;
+  wave_count(&counts[4], keyed && !keep);
 }
 
 // item 4's position: every operation is rounded on its own
@@ -339,7 +320,7 @@ __device__ __forceinline__ float ms_position(double origin, double cell, int i, 
   return (float)(origin + x);
 }
 
-// bits, pre: [2][words] (referenced clusters, faces); wg: [2][words / MF_WORDS_WG], scanned
+// bits, pre, wg: two stacked keep lists of `words` words each (referenced clusters, faces), scanned
 __global__ __launch_bounds__(MS_NT) void k_ms_write(MsGrid g, const unsigned long long* __restrict__ S, const unsigned* __restrict__ nC,
                                                     const int* __restrict__ cell_of, const int* __restrict__ tri,
                                                     const unsigned long long* __restrict__ bits, const unsigned* __restrict__ pre,
@@ -348,11 +329,9 @@ __global__ __launch_bounds__(MS_NT) void k_ms_write(MsGrid g, const unsigned lon
   const long long i = (long long)blockIdx.x * MS_NT + threadIdx.x;
   const int which = blockIdx.y;
   if (i >= words * 64) return;
-  const unsigned long long* b = bits + (size_t)which * words;
-  const unsigned* p = pre + (size_t)which * words;
-  const unsigned* w = wg + (size_t)which * (words / MF_WORDS_WG);
-  if (!((b[i >> 6] >> (i & 63)) & 1ull)) return;                    // a set bit: the cluster has vertices, the face has a key
-  const size_t row = (size_t)ms_rank(b, p, w, i);
+  const KeepList clusters{bits, pre, wg}, mine = clusters.pick(which, (size_t)words);
+  if (!mine.kept(i)) return;                                        // a set bit: the cluster has vertices, the face has a key
+  const size_t row = (size_t)(int)mine.rank(i);
   if (!which) {
     const int lin = cell_of[i];
     const int c[3] = {lin % g.dims[0], (lin / g.dims[0]) % g.dims[1], lin / g.dims[0] / g.dims[1]};
@@ -366,7 +345,7 @@ __global__ __launch_bounds__(MS_NT) void k_ms_write(MsGrid g, const unsigned lon
     }
   } else {
 #pragma unroll
-    for (int k = 0; k < 3; ++k) faces_out[3 * row + k] = ms_rank(bits, pre, wg, tri[3 * i + k]);
+    for (int k = 0; k < 3; ++k) faces_out[3 * row + k] = (int)clusters.rank((long long)tri[3 * i + k]);
   }
 }
 
@@ -378,80 +357,76 @@ __global__ __launch_bounds__(64) void k_ms_finish(const int* __restrict__ flag, 
 }
 
 static bool ms_shape(long long Nv, long long Nf, long long cells) {
-  return cc_shape(Nv, Nf) && cells >= 1 && cells < (1ll << 31);
+  return mesh_shape(Nv, Nf) && cells >= 1 && cells < (1ll << 31);
 }
 static size_t ms_capacity(long long Nf) {
   size_t cap = 64;
   while (cap < 2 * (size_t)Nf) cap <<= 1;
   return cap;
 }
-static size_t ms_up(size_t n, size_t to) { return (n + to - 1) / to * to; }
 
-// the workspace, in 8-byte words first: [zeroed: flag | cell bits | referenced bits | face bits | S | n, C] [table] then the
-// 4-byte arrays [pre of the cells | pre of referenced, faces | wg of the cells | wg of referenced, faces | cell_of | cluster_of | tri]
-struct MsLayout {
-  size_t words_c, words_2, n_zero, cap;                             // keep words of the cells / of clusters and faces (each)
-  size_t flag, cell_bits, bits_2, S, nC, table, pre_c, pre_2, wg_c, wg_2, cell_of, cluster_of, tri, bytes;
+// the workspace, 8-byte words first: [zeroed: flag | cell bits | referenced bits, face bits | S | n, C] [table], then the 4-byte
+// arrays.  words_c, words_2: the keep words of the cells / of the clusters and of the faces (each); n_zero: the 8-byte words
+// k_ms_zero clears; cap: the table's slots
+struct MsWs {
+  size_t words_c, words_2, n_zero, cap, bytes;
+  int* flag; unsigned long long* cell_bits; unsigned long long* bits_2; unsigned long long* S; unsigned* nC; int* table;
+  unsigned* pre_c; unsigned* pre_2; unsigned* wg_c; unsigned* wg_2; int* cell_of; int* cluster_of; int* tri;
 };
-static MsLayout ms_layout(long long Nv, long long Nf, long long cells) {
-  MsLayout l;
-  l.words_c = ms_up(((size_t)cells + 63) / 64, MF_WORDS_WG);
-  l.words_2 = (size_t)mf_workgroups(Nv, Nf) * MF_WORDS_WG;
-  l.cap = ms_capacity(Nf);
-  size_t at = 0;
-  l.flag = at; at += 8;
-  l.cell_bits = at; at += 8 * l.words_c;
-  l.bits_2 = at; at += 8 * 2 * l.words_2;
-  l.S = at; at += 8 * 3 * (size_t)Nv;
-  l.nC = at; at += 4 * 4 * (size_t)Nv;
-  l.n_zero = at / 8;
-  l.table = at; at += 4 * l.cap;
-  l.pre_c = at; at += 4 * l.words_c;
-  l.pre_2 = at; at += 4 * 2 * l.words_2;
-  l.wg_c = at; at += 4 * (l.words_c / MF_WORDS_WG);
-  l.wg_2 = at; at += 4 * 2 * (l.words_2 / MF_WORDS_WG);
-  l.cell_of = at; at += 4 * (size_t)Nv;
-  l.cluster_of = at; at += 4 * (size_t)Nv;
-  l.tri = at; at += 4 * 3 * (size_t)Nf;
-  l.bytes = ms_up(at, 256);
-  return l;
+static MsWs ms_carve(void* workspace, long long Nv, long long Nf, long long cells) {
+  Carver c(workspace);
+  MsWs w;
+  w.words_c = round_up(((size_t)cells + 63) / 64, KEEP_GROUP);
+  w.words_2 = (size_t)mf_workgroups(Nv, Nf) * KEEP_GROUP;
+  w.cap = ms_capacity(Nf);
+  w.flag = c.take<int>(2);
+  w.cell_bits = c.take<unsigned long long>(w.words_c);
+  w.bits_2 = c.take<unsigned long long>(2 * w.words_2);
+  w.S = c.take<unsigned long long>(3 * (size_t)Nv);
+  w.nC = c.take<unsigned>(4 * (size_t)Nv);
+  w.n_zero = c.at / 8;
+  w.table = c.take<int>(w.cap);
+  w.pre_c = c.take<unsigned>(w.words_c);
+  w.pre_2 = c.take<unsigned>(2 * w.words_2);
+  w.wg_c = c.take<unsigned>(w.words_c / KEEP_GROUP);
+  w.wg_2 = c.take<unsigned>(2 * (w.words_2 / KEEP_GROUP));
+  w.cell_of = c.take<int>((size_t)Nv);
+  w.cluster_of = c.take<int>((size_t)Nv);
+  w.tri = c.take<int>(3 * (size_t)Nf);
+  w.bytes = c.bytes();
+  return w;
 }
-static bool ms_finite(double x) { return x - x == 0.0; }
 
 }  // namespace lrf
 
 extern "C" int lrf_mesh_simplify_bounds(const float* vertices, int64_t Nv, const double* origin, double cell, int32_t* out,
                                         void* stream) {
   using namespace lrf;
-  if (!cc_shape(Nv, 0)) return set_err("lrf_mesh_simplify_bounds: need 1 <= Nv < 2^31");
+  if (!mesh_shape(Nv, 0)) return set_err("lrf_mesh_simplify_bounds: need 1 <= Nv < 2^31");
   if (!vertices || !origin || !out) return set_err("lrf_mesh_simplify_bounds: null argument");
-  if (!(ms_finite(origin[0]) && ms_finite(origin[1]) && ms_finite(origin[2])))
+  if (!(is_finite(origin[0]) && is_finite(origin[1]) && is_finite(origin[2])))
     return set_err("lrf_mesh_simplify_bounds: origin must hold 3 finite values");
-  if (!(cell > 0.0 && ms_finite(cell))) return set_err("lrf_mesh_simplify_bounds: cell must be finite and > 0");
-  if (((uintptr_t)vertices | (uintptr_t)out) & 3) return set_err("lrf_mesh_simplify_bounds: float and int32 arrays must be 4-byte aligned");
+  if (!(cell > 0.0 && is_finite(cell))) return set_err("lrf_mesh_simplify_bounds: cell must be finite and > 0");
+  if (misaligned(3, vertices, out)) return set_err("lrf_mesh_simplify_bounds: float and int32 arrays must be 4-byte aligned");
   MsGrid g;
   memset(&g, 0, sizeof(g));
   for (int k = 0; k < 3; ++k) g.origin[k] = origin[k];
   g.cell = cell;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(k_ms_bounds_init, dim3(1), dim3(64), 0, st, out);
-  LRF_HIP(hipGetLastError());
-  hipLaunchKernelGGL(k_ms_bounds, dim3(cc_blocks(Nv)), dim3(MS_NT), 0, st, vertices, (int)Nv, g, out);
-  LRF_HIP(hipGetLastError());
-  return 0;
+  LRF_TRY(launch(k_ms_bounds_init, 1, 64, st, out));
+  return launch(k_ms_bounds, blocks_for(Nv, MS_NT), MS_NT, st, vertices, Nv, g, out);
 }
 
 extern "C" size_t lrf_mesh_simplify_workspace_bytes(int64_t Nv, int64_t Nf, int64_t cells) {
   using namespace lrf;
-  if (!ms_shape(Nv, Nf, cells)) return 0;
-  return ms_layout(Nv, Nf, cells).bytes;
+  return ms_shape(Nv, Nf, cells) ? ms_carve(nullptr, Nv, Nf, cells).bytes : 0;
 }
 
 extern "C" int lrf_mesh_simplify(const LrfMeshSimplify* m, float* vertices_out, uint8_t* rgb8_out, int32_t* faces_out,
                                  int64_t* counts, void* workspace, void* stream) {
   using namespace lrf;
   if (!m) return set_err("lrf_mesh_simplify: null argument");
-  if (!cc_shape(m->Nv, m->Nf)) return set_err("lrf_mesh_simplify: need 1 <= Nv < 2^31 and 0 <= Nf < 2^31");
+  if (!mesh_shape(m->Nv, m->Nf)) return set_err("lrf_mesh_simplify: need 1 <= Nv < 2^31 and 0 <= Nf < 2^31");
   if (!m->vertices || !vertices_out || !counts || !workspace || (m->Nf && (!m->faces || !faces_out)))
     return set_err("lrf_mesh_simplify: null argument");
   if (!m->rgb8 != !rgb8_out) return set_err("lrf_mesh_simplify: rgb8 and rgb8_out go together");
@@ -464,73 +439,44 @@ extern "C" int lrf_mesh_simplify(const LrfMeshSimplify* m, float* vertices_out, 
   for (int k = 0; k < 3; ++k)
     if (m->lo[k] <= -(1 << 30) || (long long)m->lo[k] + m->dims[k] > (1 << 30))
       return set_err("lrf_mesh_simplify: the box must lie inside (-2^30, 2^30)");
-  if (!(ms_finite(m->origin[0]) && ms_finite(m->origin[1]) && ms_finite(m->origin[2])))
+  if (!(is_finite(m->origin[0]) && is_finite(m->origin[1]) && is_finite(m->origin[2])))
     return set_err("lrf_mesh_simplify: origin must hold 3 finite values");
-  if (!(m->cell > 0.0 && ms_finite(m->cell))) return set_err("lrf_mesh_simplify: cell must be finite and > 0");
-  if (((uintptr_t)m->vertices | (uintptr_t)m->faces | (uintptr_t)vertices_out | (uintptr_t)faces_out) & 3)
+  if (!(m->cell > 0.0 && is_finite(m->cell))) return set_err("lrf_mesh_simplify: cell must be finite and > 0");
+  if (misaligned(3, m->vertices, m->faces, vertices_out, faces_out))
     return set_err("lrf_mesh_simplify: float and int32 arrays must be 4-byte aligned");
-  if (((uintptr_t)counts | (uintptr_t)workspace) & 7) return set_err("lrf_mesh_simplify: counts and workspace must be 8-byte aligned");
+  if (misaligned(7, counts, workspace)) return set_err("lrf_mesh_simplify: counts and workspace must be 8-byte aligned");
   const int Nv = (int)m->Nv, Nf = (int)m->Nf;
-  const MsLayout l = ms_layout(m->Nv, m->Nf, cells);
+  const MsWs w = ms_carve(workspace, m->Nv, m->Nf, cells);
   MsGrid g;
   memset(&g, 0, sizeof(g));
   for (int k = 0; k < 3; ++k) { g.origin[k] = m->origin[k]; g.lo[k] = m->lo[k]; g.dims[k] = m->dims[k]; }
   g.cell = m->cell;
-  char* ws = static_cast<char*>(workspace);
-  int* flag = reinterpret_cast<int*>(ws + l.flag);
-  unsigned long long* cell_bits = reinterpret_cast<unsigned long long*>(ws + l.cell_bits);
-  unsigned long long* bits_2 = reinterpret_cast<unsigned long long*>(ws + l.bits_2);
-  unsigned long long* S = reinterpret_cast<unsigned long long*>(ws + l.S);
-  unsigned* nC = reinterpret_cast<unsigned*>(ws + l.nC);
-  int* table = reinterpret_cast<int*>(ws + l.table);
-  unsigned* pre_c = reinterpret_cast<unsigned*>(ws + l.pre_c);
-  unsigned* pre_2 = reinterpret_cast<unsigned*>(ws + l.pre_2);
-  unsigned* wg_c = reinterpret_cast<unsigned*>(ws + l.wg_c);
-  unsigned* wg_2 = reinterpret_cast<unsigned*>(ws + l.wg_2);
-  int* cell_of = reinterpret_cast<int*>(ws + l.cell_of);
-  int* cluster_of = reinterpret_cast<int*>(ws + l.cluster_of);
-  int* tri = reinterpret_cast<int*>(ws + l.tri);
   long long* cnt = reinterpret_cast<long long*>(counts);
   unsigned long long* ucnt = reinterpret_cast<unsigned long long*>(counts);
-  const unsigned long long mask = l.cap - 1;
+  const unsigned long long mask = w.cap - 1;
   const bool dedupe = m->dedupe != 0 && Nf > 0;
-  const size_t n_table = dedupe ? l.cap / 2 : 0;                    // 8-byte words
-  const size_t most = l.n_zero > n_table ? l.n_zero : n_table;
+  const size_t n_table = dedupe ? w.cap / 2 : 0;                    // 8-byte words
+  const size_t most = w.n_zero > n_table ? w.n_zero : n_table;
   const size_t zero_blocks = (most + MS_NT - 1) / MS_NT;
+  const unsigned nbv = blocks_for(Nv, MS_NT), nbf = blocks_for(Nf, MS_NT);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(k_ms_zero, dim3((unsigned)(zero_blocks < MS_ZERO_BLOCKS ? zero_blocks : MS_ZERO_BLOCKS)), dim3(MS_NT), 0, st,
-                     reinterpret_cast<unsigned long long*>(ws), l.n_zero, reinterpret_cast<unsigned long long*>(table), n_table, cnt);
-  LRF_HIP(hipGetLastError());
-  hipLaunchKernelGGL(k_ms_mark, dim3(cc_blocks(Nv)), dim3(MS_NT), 0, st, m->vertices, Nv, g, cell_bits, flag);
-  LRF_HIP(hipGetLastError());
-  hipLaunchKernelGGL(k_ms_count_words, dim3(cc_blocks((long long)l.words_c)), dim3(MS_NT), 0, st, cell_bits, pre_c, wg_c,
-                     (long long)l.words_c);
-  LRF_HIP(hipGetLastError());
-  hipLaunchKernelGGL(k_points_scan, dim3(1), dim3(PTS_SCAN_NT), 0, st, wg_c, (int)(l.words_c / MF_WORDS_WG), cnt + 2);
-  LRF_HIP(hipGetLastError());
+  LRF_TRY(launch(k_ms_zero, (unsigned)(zero_blocks < MS_ZERO_BLOCKS ? zero_blocks : MS_ZERO_BLOCKS), MS_NT, st,
+                 static_cast<unsigned long long*>(workspace), w.n_zero, reinterpret_cast<unsigned long long*>(w.table), n_table, cnt));
+  LRF_TRY(launch(k_ms_mark, nbv, MS_NT, st, m->vertices, Nv, g, w.cell_bits, w.flag));
+  LRF_TRY(launch(k_ms_count_words, blocks_for((long long)w.words_c, MS_NT), MS_NT, st, w.cell_bits, w.pre_c, w.wg_c, w.words_c));
+  LRF_TRY(launch(k_points_scan, 1, PTS_SCAN_NT, st, w.wg_c, w.words_c / KEEP_GROUP, cnt + 2));
   if (Nf) {
-    const long long words = (long long)l.words_2;
-    hipLaunchKernelGGL(k_ms_accumulate, dim3(cc_blocks(Nv)), dim3(MS_NT), 0, st, m->vertices, m->rgb8, Nv, g, cell_bits, pre_c, wg_c,
-                       S, nC, cell_of, cluster_of);
-    LRF_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_ms_faces_map, dim3(cc_blocks(Nf)), dim3(MS_NT), 0, st, m->faces, Nf, Nv, cluster_of, tri, flag, ucnt);
-    LRF_HIP(hipGetLastError());
-    if (dedupe) {
-      hipLaunchKernelGGL(k_ms_faces_insert, dim3(cc_blocks(Nf)), dim3(MS_NT), 0, st, tri, Nf, table, mask);
-      LRF_HIP(hipGetLastError());
-    }
-    hipLaunchKernelGGL(k_ms_faces_keep, dim3(cc_blocks(words * 64)), dim3(MS_NT), 0, st, tri, Nf, Nv, table, mask, dedupe ? 1 : 0,
-                       bits_2 + words, bits_2, ucnt);
-    LRF_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_ms_count_words, dim3(cc_blocks(words), 2), dim3(MS_NT), 0, st, bits_2, pre_2, wg_2, words);
-    LRF_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_points_scan, dim3(2), dim3(PTS_SCAN_NT), 0, st, wg_2, (int)(words / MF_WORDS_WG), cnt);
-    LRF_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_ms_write, dim3(cc_blocks(words * 64), 2), dim3(MS_NT), 0, st, g, S, nC, cell_of, tri, bits_2, pre_2, wg_2,
-                       words, vertices_out, rgb8_out, faces_out);
-    LRF_HIP(hipGetLastError());
+    const long long words = (long long)w.words_2;
+    LRF_TRY(launch(k_ms_accumulate, nbv, MS_NT, st, m->vertices, m->rgb8, Nv, g, w.cell_bits, w.pre_c, w.wg_c, w.S, w.nC, w.cell_of,
+                   w.cluster_of));
+    LRF_TRY(launch(k_ms_faces_map, nbf, MS_NT, st, m->faces, Nf, Nv, w.cluster_of, w.tri, w.flag, ucnt));
+    if (dedupe) LRF_TRY(launch(k_ms_faces_insert, nbf, MS_NT, st, w.tri, Nf, w.table, mask));
+    LRF_TRY(launch(k_ms_faces_keep, blocks_for(words * 64, MS_NT), MS_NT, st, w.tri, Nf, Nv, w.table, mask, dedupe ? 1 : 0,
+                   w.bits_2 + words, w.bits_2, ucnt));
+    LRF_TRY(launch(k_ms_count_words, dim3(blocks_for(words, MS_NT), 2), MS_NT, st, w.bits_2, w.pre_2, w.wg_2, words));
+    LRF_TRY(launch(k_points_scan, 2, PTS_SCAN_NT, st, w.wg_2, words / KEEP_GROUP, cnt));
+    LRF_TRY(launch(k_ms_write, dim3(blocks_for(words * 64, MS_NT), 2), MS_NT, st, g, w.S, w.nC, w.cell_of, w.tri, w.bits_2, w.pre_2,
+                   w.wg_2, words, vertices_out, rgb8_out, faces_out));
   }
-  hipLaunchKernelGGL(k_ms_finish, dim3(1), dim3(64), 0, st, flag, cnt);
-  LRF_HIP(hipGetLastError());
-  return 0;
+  return launch(k_ms_finish, 1, 64, st, w.flag, cnt);
 }

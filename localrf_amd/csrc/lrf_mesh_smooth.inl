@@ -1,6 +1,6 @@
 // lrf_mesh_smooth.inl -- the faces around each vertex of an indexed triangle mesh (incidence lists), and the three things built
 // on them: boundary and non-manifold edge counts, area-weighted vertex normals, and Taubin lambda|mu smoothing (included by
-// lrf_render.hip after lrf_mesh_simplify.inl; it reuses cc_in, cc_shape, cc_blocks, k_ms_bounds_init and k_points_scan).
+// lrf_render.hip; the scans and the host helpers are lrf_compact.inl's, k_ms_bounds_init is lrf_mesh_simplify.inl's).
 // The output bytes are a fixed function of the input: integer counts, integer sums of fixed-point values, and fp64 operations
 // that are each rounded on their own (the functions that hold them switch contraction off).  No sort, no floating-point atomics.
 //
@@ -64,7 +64,7 @@ struct SmLo { double lo[3]; };
 // 0: a valid face, 1: an index outside [0, Nv), 2: degenerate
 __device__ __forceinline__ int sm_face(const int* __restrict__ faces, long long f, int Nv, int* a, int* b, int* c) {
   *a = faces[3 * f]; *b = faces[3 * f + 1]; *c = faces[3 * f + 2];
-  if (!(cc_in(*a, Nv) && cc_in(*b, Nv) && cc_in(*c, Nv))) return 1;
+  if (!(in_range(*a, Nv) && in_range(*b, Nv) && in_range(*c, Nv))) return 1;
   return (*a == *b || *b == *c || *a == *c) ? 2 : 0;
 }
 
@@ -83,37 +83,20 @@ __global__ __launch_bounds__(SM_NT) void k_sm_count(const int* __restrict__ face
     kind = sm_face(faces, f, Nv, &a, &b, &c);
     if (kind == 0) { atomicAdd(&deg[a], 1); atomicAdd(&deg[b], 1); atomicAdd(&deg[c], 1); }
   }
-  const unsigned long long nb = __ballot(kind == 1), nd = __ballot(kind == 2);
-  if ((threadIdx.x & 63) == 0) {
-    if (nb) atomicOr(&info[0], SM_BAD_FACE);
-    if (nd) atomicAdd(&info[1], (unsigned long long)__popcll(nd));
-  }
+  wave_or(&info[0], kind == 1, SM_BAD_FACE);
+  wave_count(&info[1], kind == 2);
 }
 
 __global__ __launch_bounds__(SM_NT) void k_sm_rows(const int* __restrict__ deg, int Nv, int* __restrict__ row_start,
                                                    unsigned* __restrict__ wg, unsigned long long* info) {
   __shared__ unsigned part[SM_NT / 64];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const long long i = (long long)blockIdx.x * SM_NT + threadIdx.x;
   const unsigned c = i < Nv ? (unsigned)deg[i] : 0u;
-  const unsigned long long too_long = __ballot(c >= (unsigned)SM_ROW_LIMIT);
-  unsigned s = c;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const unsigned t = __shfl_up(s, off, 64);
-    if (lane >= off) s += t;
-  }
-  if (lane == 63) part[wv] = s;
-  __syncthreads();
-  unsigned before = 0, total = 0;
-#pragma unroll
-  for (int w = 0; w < SM_NT / 64; ++w) {
-    if (w < wv) before += part[w];
-    total += part[w];
-  }
-  if (i < Nv) row_start[i] = (int)(before + s - c);
+  unsigned total;
+  const unsigned before = block_scan_excl<SM_NT>(c, part, total);
+  if (i < Nv) row_start[i] = (int)before;
   if (threadIdx.x == 0) wg[blockIdx.x] = total;
-  if (lane == 0 && too_long) atomicOr(&info[0], SM_LONG);
+  wave_or(&info[0], c >= (unsigned)SM_ROW_LIMIT, SM_LONG);
 }
 
 __global__ __launch_bounds__(SM_NT) void k_sm_starts(int* __restrict__ row_start, int Nv, const unsigned* __restrict__ wg,
@@ -155,7 +138,7 @@ __global__ __launch_bounds__(SM_NT) void k_sm_edges(const int* __restrict__ face
       int opp = 0, same = 0;
       for (int i = 0; i < n; ++i) {                                 // bounded by the row length
         const int g = row_faces[at + i];
-        if (!cc_in(g, Nf)) continue;                                // not a row of k_sm_fill
+        if (!in_range(g, Nf)) continue;                                // not a row of k_sm_fill
         const int g0 = faces[3 * (size_t)g], g1 = faces[3 * (size_t)g + 1], g2 = faces[3 * (size_t)g + 2];
         if (sm_has_edge(g0, g1, g2, b, a)) ++opp;
         if (g != (int)f && sm_has_edge(g0, g1, g2, a, b)) ++same;
@@ -165,17 +148,13 @@ __global__ __launch_bounds__(SM_NT) void k_sm_edges(const int* __restrict__ face
       if (boundary) { mask[a] = 1; mask[b] = 1; }                   // plain byte stores of one value
     }
   }
-  const unsigned long long nb = __ballot(boundary), nn = __ballot(nonmanifold);
-  if ((threadIdx.x & 63) == 0) {
-    if (nb) atomicAdd(&info[2], (unsigned long long)__popcll(nb));
-    if (nn) atomicAdd(&info[3], (unsigned long long)__popcll(nn));
-  }
+  wave_count(&info[2], boundary);
+  wave_count(&info[3], nonmanifold);
 }
 
 __global__ __launch_bounds__(SM_NT) void k_sm_pinned(const uint8_t* __restrict__ mask, int Nv, unsigned long long* info) {
   const long long i = (long long)blockIdx.x * SM_NT + threadIdx.x;
-  const unsigned long long m = __ballot(i < Nv && mask[i] != 0);
-  if ((threadIdx.x & 63) == 0 && m) atomicAdd(&info[5], (unsigned long long)__popcll(m));
+  wave_count(&info[5], i < Nv && mask[i] != 0);
 }
 
 // the sum over row [begin, begin + n) of vertex v of what add(face, v, acc) adds to acc[3]; EVERY lane of the wave calls it,
@@ -201,8 +180,6 @@ __device__ __forceinline__ void sm_row_sum(const int* __restrict__ row_faces, in
   }
 }
 
-__device__ __forceinline__ bool sm_finite(double x) { return x - x == 0.0; }
-
 // item 3's face normal -> false when a coordinate is not finite (n = 0 then)
 __device__ __forceinline__ bool sm_face_normal(const float* __restrict__ vertices, int a, int b, int c, double* n) {
 #pragma clang fp contract(off)
@@ -212,7 +189,7 @@ __device__ __forceinline__ bool sm_face_normal(const float* __restrict__ vertice
   for (int k = 0; k < 3; ++k) {
     pa[k] = (double)vertices[3 * (size_t)a + k];
     const double pb = (double)vertices[3 * (size_t)b + k], pc = (double)vertices[3 * (size_t)c + k];
-    ok = ok && sm_finite(pa[k]) && sm_finite(pb) && sm_finite(pc);
+    ok = ok && is_finite(pa[k]) && is_finite(pb) && is_finite(pc);
     e1[k] = pb - pa[k];
     e2[k] = pc - pa[k];
   }
@@ -266,7 +243,7 @@ __global__ __launch_bounds__(SM_NT) void k_sm_normals(const float* __restrict__ 
   const int begin = have ? row_start[i] : 0, n = have ? row_start[i + 1] - begin : 0;
   long long S[3];
   sm_row_sum(row_faces, (int)i, begin, n, have && n > 0 && e != SM_E_NONE, S, [&](int g, int, long long* acc) {
-    if (!cc_in(g, Nf)) return;                                      // not a row of k_sm_fill
+    if (!in_range(g, Nf)) return;                                      // not a row of k_sm_fill
     double fn[3];
     sm_face_normal(vertices, faces[3 * (size_t)g], faces[3 * (size_t)g + 1], faces[3 * (size_t)g + 2], fn);
 #pragma unroll
@@ -278,17 +255,14 @@ __global__ __launch_bounds__(SM_NT) void k_sm_normals(const float* __restrict__ 
     zero = !sm_unit(S, out);
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-      bad = bad || !sm_finite((double)vertices[3 * i + k]);
+      bad = bad || !is_finite((double)vertices[3 * i + k]);
       normals[3 * i + k] = out[k];
       if (S_out) S_out[3 * i + k] = S[k];
     }
     if (i == 0 && E_out) *E_out = e;
   }
-  const unsigned long long nz = __ballot(zero), nb = __ballot(bad);
-  if ((threadIdx.x & 63) == 0) {
-    if (nz) atomicAdd(&info[4], (unsigned long long)__popcll(nz));
-    if (nb) atomicOr(&info[0], SM_NOT_FINITE);
-  }
+  wave_count(&info[4], zero);
+  wave_or(&info[0], bad, SM_NOT_FINITE);
 }
 
 // fp32 -> int32 that orders as the floats do (-0 first made +0)
@@ -305,9 +279,9 @@ __global__ __launch_bounds__(SM_NT) void k_sm_bounds(const float* __restrict__ v
   bool ok = have;
   if (have) {
 #pragma unroll
-    for (int k = 0; k < 3; ++k) { x[k] = vertices[3 * v + k]; ok = ok && sm_finite((double)x[k]); }
+    for (int k = 0; k < 3; ++k) { x[k] = vertices[3 * v + k]; ok = ok && is_finite((double)x[k]); }
   }
-  const unsigned long long good = __ballot(ok), bad = __ballot(have && !ok);
+  const unsigned long long good = __ballot(ok);
   int lo[3], hi[3];
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
@@ -318,13 +292,11 @@ __global__ __launch_bounds__(SM_NT) void k_sm_bounds(const float* __restrict__ v
       hi[k] = max(hi[k], __shfl_xor(hi[k], off, 64));
     }
   }
-  if ((threadIdx.x & 63) == 0) {
-    if (good) {
+  if ((threadIdx.x & 63) == 0 && good) {
 #pragma unroll
-      for (int k = 0; k < 3; ++k) { atomicMin(&out[k], lo[k]); atomicMax(&out[3 + k], hi[k]); }
-    }
-    if (bad) atomicOr(&out[6], 1);
+    for (int k = 0; k < 3; ++k) { atomicMin(&out[k], lo[k]); atomicMax(&out[3 + k], hi[k]); }
   }
+  wave_or(&out[6], have && !ok, 1);
 }
 
 // item 4's q -> false when it had to be clamped
@@ -360,11 +332,11 @@ __global__ __launch_bounds__(SM_NT) void k_sm_step(const float* __restrict__ in,
   bool diverged = false;
   long long S[3];
   sm_row_sum(row_faces, (int)i, begin, n, moves, S, [&](int g, int v, long long* acc) {
-    if (!cc_in(g, Nf)) return;                                      // not a row of k_sm_fill
+    if (!in_range(g, Nf)) return;                                      // not a row of k_sm_fill
 #pragma unroll
     for (int t = 0; t < 3; ++t) {
       const int j = faces[3 * (size_t)g + t];
-      if (j == v || !cc_in(j, Nv)) continue;                        // the two other corners
+      if (j == v || !in_range(j, Nv)) continue;                        // the two other corners
 #pragma unroll
       for (int k = 0; k < 3; ++k) {
         long long q;
@@ -382,6 +354,7 @@ __global__ __launch_bounds__(SM_NT) void k_sm_step(const float* __restrict__ in,
 #pragma unroll
     for (int k = 0; k < 3; ++k) dst[3 * i + k] = src[3 * i + k];    // the bits stay
   }
+  // not wave_or: as an argument `diverged` becomes a lane mask that the row loop above would have to merge on every entry
   const unsigned long long nd = __ballot(diverged);
   if ((threadIdx.x & 63) == 0 && nd) atomicOr(&info[0], SM_DIVERGED);
 }
@@ -391,116 +364,78 @@ __global__ __launch_bounds__(SM_NT) void k_sm_copy(const unsigned* __restrict__ 
   if (i < n) out[i] = in[i];
 }
 
-static bool sm_shape(long long Nv, long long Nf) { return cc_shape(Nv, Nf) && 3 * Nf < (1ll << 31); }
-static unsigned sm_blocks(long long n) { return (unsigned)((n + SM_NT - 1) / SM_NT); }
-static size_t sm_up(size_t n, size_t to) { return (n + to - 1) / to * to; }
+static bool sm_shape(long long Nv, long long Nf) { return mesh_shape(Nv, Nf) && 3 * Nf < (1ll << 31); }
+static unsigned sm_blocks(long long n) { return blocks_for(n, SM_NT); }
 
 // the workspace: [E, 8 bytes | row_start Nv + 1 | deg Nv | wg ceil(Nv / 256) | row_faces 3 Nf] int32, [mask Nv] bytes, rounded
-// up to 256; lrf_mesh_smooth adds a second position buffer [Nv,3] fp32 behind it
-struct SmLayout { size_t E, row_start, deg, wg, row_faces, mask, lists, tmp, bytes; };
-static SmLayout sm_layout(long long Nv, long long Nf) {
-  SmLayout l;
-  size_t at = 0;
-  l.E = at; at += 8;
-  l.row_start = at; at += 4 * ((size_t)Nv + 1);
-  l.deg = at; at += 4 * (size_t)Nv;
-  l.wg = at; at += 4 * (size_t)sm_blocks(Nv);
-  l.row_faces = at; at += 4 * 3 * (size_t)Nf;
-  l.mask = at; at += (size_t)Nv;
-  l.lists = sm_up(at, 256);
-  l.tmp = l.lists;
-  l.bytes = sm_up(l.lists + 4 * 3 * (size_t)Nv, 256);
-  return l;
-}
-
-struct SmLists { int* E; int* row_start; int* deg; unsigned* wg; int* row_faces; uint8_t* mask; float* tmp; };
+// up to 256 (lists: the incidence lists' bytes); lrf_mesh_smooth adds a second position buffer [Nv,3] fp32 behind it (bytes)
+struct SmLists { int* E; int* row_start; int* deg; unsigned* wg; int* row_faces; uint8_t* mask; float* tmp; size_t lists, bytes; };
 static SmLists sm_lists(void* workspace, long long Nv, long long Nf) {
-  const SmLayout l = sm_layout(Nv, Nf);
-  char* ws = static_cast<char*>(workspace);
+  Carver c(workspace);
   SmLists p;
-  p.E = reinterpret_cast<int*>(ws + l.E);
-  p.row_start = reinterpret_cast<int*>(ws + l.row_start);
-  p.deg = reinterpret_cast<int*>(ws + l.deg);
-  p.wg = reinterpret_cast<unsigned*>(ws + l.wg);
-  p.row_faces = reinterpret_cast<int*>(ws + l.row_faces);
-  p.mask = reinterpret_cast<uint8_t*>(ws + l.mask);
-  p.tmp = reinterpret_cast<float*>(ws + l.tmp);
+  p.E = c.take<int>(2);
+  p.row_start = c.take<int>((size_t)Nv + 1);
+  p.deg = c.take<int>((size_t)Nv);
+  p.wg = c.take<unsigned>(sm_blocks(Nv));
+  p.row_faces = c.take<int>(3 * (size_t)Nf);
+  p.mask = c.take<uint8_t>((size_t)Nv);
+  p.lists = c.at = c.bytes();
+  p.tmp = c.take<float>(3 * (size_t)Nv);
+  p.bytes = c.bytes();
   return p;
 }
 
 // item 1: six launches (four without faces); the mask zeroed is `mask`
 static int sm_build(const int* faces, int Nv, int Nf, const SmLists& p, uint8_t* mask, unsigned long long* info, hipStream_t st) {
-  hipLaunchKernelGGL(k_sm_zero, dim3(sm_blocks((long long)Nv + 9)), dim3(SM_NT), 0, st, p.deg, mask, Nv, info, p.E);
-  LRF_HIP(hipGetLastError());
-  if (Nf) {
-    hipLaunchKernelGGL(k_sm_count, dim3(sm_blocks(Nf)), dim3(SM_NT), 0, st, faces, Nf, Nv, p.deg, info);
-    LRF_HIP(hipGetLastError());
-  }
-  hipLaunchKernelGGL(k_sm_rows, dim3(sm_blocks(Nv)), dim3(SM_NT), 0, st, p.deg, Nv, p.row_start, p.wg, info);
-  LRF_HIP(hipGetLastError());
-  hipLaunchKernelGGL(k_points_scan, dim3(1), dim3(PTS_SCAN_NT), 0, st, p.wg, (int)sm_blocks(Nv), reinterpret_cast<long long*>(info + 6));
-  LRF_HIP(hipGetLastError());
-  hipLaunchKernelGGL(k_sm_starts, dim3(sm_blocks((long long)Nv + 1)), dim3(SM_NT), 0, st, p.row_start, Nv, p.wg, info);
-  LRF_HIP(hipGetLastError());
-  if (Nf) {
-    hipLaunchKernelGGL(k_sm_fill, dim3(sm_blocks(Nf)), dim3(SM_NT), 0, st, faces, Nf, Nv, p.row_start, p.deg, p.row_faces);
-    LRF_HIP(hipGetLastError());
-  }
+  LRF_TRY(launch(k_sm_zero, sm_blocks((long long)Nv + 9), SM_NT, st, p.deg, mask, Nv, info, p.E));
+  if (Nf) LRF_TRY(launch(k_sm_count, sm_blocks(Nf), SM_NT, st, faces, Nf, Nv, p.deg, info));
+  LRF_TRY(launch(k_sm_rows, sm_blocks(Nv), SM_NT, st, p.deg, Nv, p.row_start, p.wg, info));
+  LRF_TRY(launch(k_points_scan, 1, PTS_SCAN_NT, st, p.wg, sm_blocks(Nv), reinterpret_cast<long long*>(info + 6)));
+  LRF_TRY(launch(k_sm_starts, sm_blocks((long long)Nv + 1), SM_NT, st, p.row_start, Nv, p.wg, info));
+  if (Nf) LRF_TRY(launch(k_sm_fill, sm_blocks(Nf), SM_NT, st, faces, Nf, Nv, p.row_start, p.deg, p.row_faces));
   return 0;
 }
 
 static int sm_edges(const int* faces, int Nv, int Nf, const SmLists& p, uint8_t* mask, unsigned long long* info, hipStream_t st) {
   if (!Nf) return 0;
-  hipLaunchKernelGGL(k_sm_edges, dim3(sm_blocks(3ll * Nf)), dim3(SM_NT), 0, st, faces, Nf, Nv, p.row_start, p.row_faces, mask, info);
-  LRF_HIP(hipGetLastError());
-  return 0;
-}
-
-static int sm_err(const char* who, const char* why) {
-  snprintf(lrf_error_slot(), 512, "%s: %s", who, why);
-  return 1;
+  return launch(k_sm_edges, sm_blocks(3ll * Nf), SM_NT, st, faces, Nf, Nv, p.row_start, p.row_faces, mask, info);
 }
 
 // the checks every entry point shares -> the refusal's text, or null
 static const char* sm_refuse(const void* faces, int64_t Nv, int64_t Nf, const void* info, const void* workspace) {
   if (!sm_shape(Nv, Nf)) return "need 1 <= Nv < 2^31, 0 <= Nf and 3 Nf < 2^31";
   if (!info || !workspace || (Nf && !faces)) return "null argument";
-  if ((uintptr_t)faces & 3) return "float and int32 arrays must be 4-byte aligned";
-  if (((uintptr_t)info | (uintptr_t)workspace) & 7) return "info and workspace must be 8-byte aligned";
+  if (misaligned(3, faces)) return "float and int32 arrays must be 4-byte aligned";
+  if (misaligned(7, info, workspace)) return "info and workspace must be 8-byte aligned";
   return nullptr;
 }
 
 static int sm_normals(const char* who, const float* vertices, const int32_t* faces, int64_t Nv64, int64_t Nf64, float* normals,
                       int64_t* S_out, int32_t* E_out, int64_t* info64, void* workspace, void* stream) {
-  if (const char* why = sm_refuse(faces, Nv64, Nf64, info64, workspace)) return sm_err(who, why);
-  if (!vertices || !normals) return sm_err(who, "null argument");
-  if (((uintptr_t)vertices | (uintptr_t)normals | (uintptr_t)E_out) & 3) return sm_err(who, "float and int32 arrays must be 4-byte aligned");
-  if ((uintptr_t)S_out & 7) return sm_err(who, "S must be 8-byte aligned");
+  if (const char* why = sm_refuse(faces, Nv64, Nf64, info64, workspace)) return refuse(who, why);
+  if (!vertices || !normals) return refuse(who, "null argument");
+  if (misaligned(3, vertices, normals, E_out)) return refuse(who, "float and int32 arrays must be 4-byte aligned");
+  if (misaligned(7, S_out)) return refuse(who, "S must be 8-byte aligned");
   const int Nv = (int)Nv64, Nf = (int)Nf64;
   const SmLists p = sm_lists(workspace, Nv, Nf);
   unsigned long long* info = reinterpret_cast<unsigned long long*>(info64);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (int rc = sm_build(faces, Nv, Nf, p, p.mask, info, st)) return rc;
-  if (Nf) {
-    hipLaunchKernelGGL(k_sm_exponent, dim3(sm_blocks(Nf)), dim3(SM_NT), 0, st, vertices, faces, Nf, Nv, p.E);
-    LRF_HIP(hipGetLastError());
-  }
-  hipLaunchKernelGGL(k_sm_normals, dim3(sm_blocks(Nv)), dim3(SM_NT), 0, st, vertices, faces, Nv, Nf, p.row_start, p.row_faces, p.E,
-                     normals, reinterpret_cast<long long*>(S_out), E_out, info);
-  LRF_HIP(hipGetLastError());
-  return 0;
+  LRF_TRY(sm_build(faces, Nv, Nf, p, p.mask, info, st));
+  if (Nf) LRF_TRY(launch(k_sm_exponent, sm_blocks(Nf), SM_NT, st, vertices, faces, Nf, Nv, p.E));
+  return launch(k_sm_normals, sm_blocks(Nv), SM_NT, st, vertices, faces, Nv, Nf, p.row_start, p.row_faces, p.E, normals,
+                reinterpret_cast<long long*>(S_out), E_out, info);
 }
 
 }  // namespace lrf
 
 extern "C" size_t lrf_mesh_incidence_workspace_bytes(int64_t Nv, int64_t Nf) {
   using namespace lrf;
-  return sm_shape(Nv, Nf) ? sm_layout(Nv, Nf).lists : 0;
+  return sm_shape(Nv, Nf) ? sm_lists(nullptr, Nv, Nf).lists : 0;
 }
 
 extern "C" int lrf_mesh_incidence(const int32_t* faces, int64_t Nv, int64_t Nf, int64_t* info, void* workspace, void* stream) {
   using namespace lrf;
-  if (const char* why = sm_refuse(faces, Nv, Nf, info, workspace)) return sm_err("lrf_mesh_incidence", why);
+  if (const char* why = sm_refuse(faces, Nv, Nf, info, workspace)) return refuse("lrf_mesh_incidence", why);
   const SmLists p = sm_lists(workspace, Nv, Nf);
   return sm_build(faces, (int)Nv, (int)Nf, p, p.mask, reinterpret_cast<unsigned long long*>(info), reinterpret_cast<hipStream_t>(stream));
 }
@@ -508,12 +443,12 @@ extern "C" int lrf_mesh_incidence(const int32_t* faces, int64_t Nv, int64_t Nf, 
 extern "C" int lrf_mesh_topology(const int32_t* faces, int64_t Nv, int64_t Nf, uint8_t* boundary, int64_t* info, void* workspace,
                                  void* stream) {
   using namespace lrf;
-  if (const char* why = sm_refuse(faces, Nv, Nf, info, workspace)) return sm_err("lrf_mesh_topology", why);
+  if (const char* why = sm_refuse(faces, Nv, Nf, info, workspace)) return refuse("lrf_mesh_topology", why);
   if (!boundary) return set_err("lrf_mesh_topology: null argument");
   const SmLists p = sm_lists(workspace, Nv, Nf);
   unsigned long long* words = reinterpret_cast<unsigned long long*>(info);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (int rc = sm_build(faces, (int)Nv, (int)Nf, p, boundary, words, st)) return rc;
+  LRF_TRY(sm_build(faces, (int)Nv, (int)Nf, p, boundary, words, st));
   return sm_edges(faces, (int)Nv, (int)Nf, p, boundary, words, st);
 }
 
@@ -530,62 +465,51 @@ extern "C" int lrf_debug_mesh_vertex_normals(const float* vertices, const int32_
 
 extern "C" int lrf_mesh_smooth_bounds(const float* vertices, int64_t Nv, int32_t* out, void* stream) {
   using namespace lrf;
-  if (!cc_shape(Nv, 0)) return set_err("lrf_mesh_smooth_bounds: need 1 <= Nv < 2^31");
+  if (!mesh_shape(Nv, 0)) return set_err("lrf_mesh_smooth_bounds: need 1 <= Nv < 2^31");
   if (!vertices || !out) return set_err("lrf_mesh_smooth_bounds: null argument");
-  if (((uintptr_t)vertices | (uintptr_t)out) & 3) return set_err("lrf_mesh_smooth_bounds: float and int32 arrays must be 4-byte aligned");
+  if (misaligned(3, vertices, out)) return set_err("lrf_mesh_smooth_bounds: float and int32 arrays must be 4-byte aligned");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(k_ms_bounds_init, dim3(1), dim3(64), 0, st, out);
-  LRF_HIP(hipGetLastError());
-  hipLaunchKernelGGL(k_sm_bounds, dim3(sm_blocks(Nv)), dim3(SM_NT), 0, st, vertices, (int)Nv, out);
-  LRF_HIP(hipGetLastError());
-  return 0;
+  LRF_TRY(launch(k_ms_bounds_init, 1, 64, st, out));
+  return launch(k_sm_bounds, sm_blocks(Nv), SM_NT, st, vertices, Nv, out);
 }
 
 extern "C" size_t lrf_mesh_smooth_workspace_bytes(int64_t Nv, int64_t Nf) {
   using namespace lrf;
-  return sm_shape(Nv, Nf) ? sm_layout(Nv, Nf).bytes : 0;
+  return sm_shape(Nv, Nf) ? sm_lists(nullptr, Nv, Nf).bytes : 0;
 }
 
 extern "C" int lrf_mesh_smooth(const LrfMeshSmooth* m, float* vertices_out, int64_t* info, void* workspace, void* stream) {
   using namespace lrf;
   if (!m) return set_err("lrf_mesh_smooth: null argument");
-  if (const char* why = sm_refuse(m->faces, m->Nv, m->Nf, info, workspace)) return sm_err("lrf_mesh_smooth", why);
+  if (const char* why = sm_refuse(m->faces, m->Nv, m->Nf, info, workspace)) return refuse("lrf_mesh_smooth", why);
   if (!m->vertices || !vertices_out) return set_err("lrf_mesh_smooth: null argument");
-  if (((uintptr_t)m->vertices | (uintptr_t)vertices_out) & 3) return set_err("lrf_mesh_smooth: float and int32 arrays must be 4-byte aligned");
+  if (misaligned(3, m->vertices, vertices_out)) return set_err("lrf_mesh_smooth: float and int32 arrays must be 4-byte aligned");
   if (m->vertices == vertices_out) return set_err("lrf_mesh_smooth: vertices_out must not be the input");
   if (m->iterations < 0 || m->iterations > 1000) return set_err("lrf_mesh_smooth: iterations must lie in [0, 1000]");
   if (!(m->lam > 0.0 && m->lam <= 1.0)) return set_err("lrf_mesh_smooth: need 0 < lam <= 1");
   if (!(m->mu >= -1.0 && m->mu <= 0.0)) return set_err("lrf_mesh_smooth: need -1 <= mu <= 0");
-  if (!(ms_finite(m->lo[0]) && ms_finite(m->lo[1]) && ms_finite(m->lo[2]))) return set_err("lrf_mesh_smooth: lo must hold 3 finite values");
+  if (!(is_finite(m->lo[0]) && is_finite(m->lo[1]) && is_finite(m->lo[2]))) return set_err("lrf_mesh_smooth: lo must hold 3 finite values");
   if (m->s < -SM_S_LIMIT || m->s > SM_S_LIMIT) return set_err("lrf_mesh_smooth: s must lie in [-256, 256]");
   const int Nv = (int)m->Nv, Nf = (int)m->Nf;
   const SmLists p = sm_lists(workspace, Nv, Nf);
   unsigned long long* words = reinterpret_cast<unsigned long long*>(info);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (int rc = sm_build(m->faces, Nv, Nf, p, p.mask, words, st)) return rc;
-  if (int rc = sm_edges(m->faces, Nv, Nf, p, p.mask, words, st)) return rc;
+  LRF_TRY(sm_build(m->faces, Nv, Nf, p, p.mask, words, st));
+  LRF_TRY(sm_edges(m->faces, Nv, Nf, p, p.mask, words, st));
   const uint8_t* pinned = m->pin_boundary ? p.mask : nullptr;
-  if (pinned) {
-    hipLaunchKernelGGL(k_sm_pinned, dim3(sm_blocks(Nv)), dim3(SM_NT), 0, st, pinned, Nv, words);
-    LRF_HIP(hipGetLastError());
-  }
+  if (pinned) LRF_TRY(launch(k_sm_pinned, sm_blocks(Nv), SM_NT, st, pinned, Nv, words));
   const int per = m->mu == 0.0 ? 1 : 2;
   const int steps = m->iterations * per;
-  if (!steps) {
-    hipLaunchKernelGGL(k_sm_copy, dim3(sm_blocks(3ll * Nv)), dim3(SM_NT), 0, st, reinterpret_cast<const unsigned*>(m->vertices),
-                       reinterpret_cast<unsigned*>(vertices_out), 3ll * Nv);
-    LRF_HIP(hipGetLastError());
-    return 0;
-  }
+  if (!steps)
+    return launch(k_sm_copy, sm_blocks(3ll * Nv), SM_NT, st, reinterpret_cast<const unsigned*>(m->vertices),
+                  reinterpret_cast<unsigned*>(vertices_out), 3ll * Nv);
   SmLo lo;
   for (int k = 0; k < 3; ++k) lo.lo[k] = m->lo[k];
   const float* in = m->vertices;
   for (int t = 0; t < steps; ++t) {                                 // ping-pong: the last step writes vertices_out
     float* out = ((steps - 1 - t) & 1) ? p.tmp : vertices_out;
     const double f = (per == 2 && (t & 1)) ? m->mu : m->lam;
-    hipLaunchKernelGGL(k_sm_step, dim3(sm_blocks(Nv)), dim3(SM_NT), 0, st, in, out, m->faces, Nv, Nf, p.row_start, p.row_faces, pinned,
-                       lo, m->s, f, words);
-    LRF_HIP(hipGetLastError());
+    LRF_TRY(launch(k_sm_step, sm_blocks(Nv), SM_NT, st, in, out, m->faces, Nv, Nf, p.row_start, p.row_faces, pinned, lo, m->s, f, words));
     in = out;
   }
   return 0;

@@ -1,6 +1,7 @@
 // lrf_points.inl -- rendered depth fused into ONE filtered, ordered, coloured world-space point list (included by
-// lrf_render.hip).  V depth images [V,H,W] with their camera-to-world matrices go in; the points of the kept pixels come out in
-// (frame, row, column) order, the same list on every run and for every launch geometry.
+// lrf_render.hip; the scan and the host helpers are lrf_compact.inl's).  V depth images [V,H,W] with their camera-to-world
+// matrices go in; the points of the kept pixels come out in (frame, row, column) order, the same list on every run and for
+// every launch geometry.
 //
 // A candidate is a pixel (i, j) of frame v with i % stride == 0 and j % stride == 0; candidates are numbered in (frame, row,
 // column) order.  Per candidate, in fp32 with contraction off so that a numpy restatement matches bit for bit:
@@ -19,11 +20,8 @@
 //                   depth loads coalesce at stride 1, the neighbour gathers land on nearby lines).  The wave's ballot is the
 //                   keep word of its 64 candidates, stored by one lane; a workgroup covers PTS_WORDS_WG words and leaves
 //                   their popcount.
-//   k_points_scan   ONE workgroup turns the workgroup counts into exclusive bases in place and leaves the total in count[0]
-//                   (a second workgroup would scan a second array: lrf_mesh.inl).
-//                   One small launch rather than decoupled look-back: there is one uint32 per 1024 candidates (14 400 for 64
-//                   frames of 360 x 640), the scan is a fixed sequence with no spinning on other workgroups' progress, it
-//                   is capturable and it cannot deadlock under any scheduling.
+//   k_points_scan   (lrf_compact.inl) ONE workgroup turns the workgroup counts into exclusive bases in place and leaves the
+//                   total in count[0].
 //   k_points_write  reads the keep words, recomputes pw of the kept candidates with the same instructions and writes row
 //                   base + popcount(word & lanes_below).  Rows at or beyond `capacity` are not written; count[0] is the
 //                   true total.
@@ -34,7 +32,6 @@ constexpr int PTS_NT = 256;
 constexpr int PTS_WORDS_WAVE = 4;                                   // 64-candidate steps per wave
 constexpr int PTS_WORDS_WG = (PTS_NT / 64) * PTS_WORDS_WAVE;        // keep words per workgroup
 constexpr int PTS_CAND_WG = 64 * PTS_WORDS_WG;                      // candidates per workgroup
-constexpr int PTS_SCAN_NT = 1024;
 
 struct PointsArgs {
   const float* depth; const uint8_t* rgb8; const float* c2w; const float* focal; const float* center;
@@ -150,36 +147,6 @@ __global__ __launch_bounds__(PTS_NT) void k_points_mark(PointsArgs a, unsigned l
   }
 }
 
-// one workgroup per array: workgroup b turns wg[b n_wg + i] into the sum of wg[b n_wg + 0..i) (modulo 2^32) and leaves the
-// true total in count[b].  The point fusion scans one array; the mesh extraction (lrf_mesh.inl) its vertex and face counts.
-__global__ __launch_bounds__(PTS_SCAN_NT) void k_points_scan(unsigned* __restrict__ wg, int n_wg, long long* __restrict__ count) {
-  __shared__ unsigned part[PTS_SCAN_NT / 64];
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  wg += (size_t)blockIdx.x * n_wg;
-  unsigned long long carry = 0;
-  for (int base = 0; base < n_wg; base += PTS_SCAN_NT) {
-    const int i = base + tid;
-    const unsigned c = i < n_wg ? wg[i] : 0u;
-    unsigned s = c;
-    for (int off = 1; off < 64; off <<= 1) {
-      const unsigned t = __shfl_up(s, off, 64);
-      if (lane >= off) s += t;
-    }
-    if (lane == 63) part[wv] = s;
-    __syncthreads();
-    unsigned pre = 0, tot = 0;
-    for (int w = 0; w < PTS_SCAN_NT / 64; ++w) {
-      const unsigned p = part[w];
-      if (w < wv) pre += p;
-      tot += p;
-    }
-    if (i < n_wg) wg[i] = (unsigned)carry + pre + (s - c);
-    carry += tot;
-    __syncthreads();
-  }
-  if (tid == 0) count[blockIdx.x] = (long long)carry;
-}
-
 __global__ __launch_bounds__(PTS_NT) void k_points_write(PointsArgs a, const unsigned long long* __restrict__ bits,
                                                          const unsigned* __restrict__ wg, long long capacity,
                                                          float* __restrict__ xyz, uint8_t* __restrict__ rgb8_out,
@@ -214,14 +181,24 @@ static long long points_candidates(int V, int H, int W, int stride) {
   return (long long)V * ((H + stride - 1) / stride) * ((W + stride - 1) / stride);
 }
 
+// the workspace of n candidates: the keep words, then the workgroup counts
+struct PointsWs { int n_wg; unsigned long long* bits; unsigned* wg; size_t bytes; };
+static PointsWs points_carve(void* workspace, long long n) {
+  Carver c(workspace);
+  PointsWs w;
+  w.n_wg = (int)blocks_for(n, PTS_CAND_WG);
+  w.bits = c.take<unsigned long long>((size_t)w.n_wg * PTS_WORDS_WG);
+  w.wg = c.take<unsigned>(w.n_wg);
+  w.bytes = c.bytes();
+  return w;
+}
+
 }  // namespace lrf
 
 extern "C" size_t lrf_points_workspace_bytes(int32_t V, int32_t H, int32_t W, int32_t stride) {
   using namespace lrf;
   const long long n = points_candidates(V, H, W, stride);
-  if (!n) return 0;
-  const size_t n_wg = (size_t)((n + PTS_CAND_WG - 1) / PTS_CAND_WG);
-  return (n_wg * (PTS_WORDS_WG * sizeof(unsigned long long) + sizeof(unsigned)) + 255) & ~(size_t)255;
+  return n ? points_carve(nullptr, n).bytes : 0;
 }
 
 extern "C" int lrf_points_fuse(const LrfPointsFuse* p, int64_t capacity, float* xyz, uint8_t* rgb8_out, int32_t* src,
@@ -244,9 +221,9 @@ extern "C" int lrf_points_fuse(const LrfPointsFuse* p, int64_t capacity, float* 
   }
   if (p->n_neigh && !(p->rel_tol >= 0.0f)) return set_err("lrf_points_fuse: rel_tol must be >= 0");
   if (p->n_neigh && p->min_consistent < 0) return set_err("lrf_points_fuse: min_consistent must be >= 0");
-  if (((uintptr_t)p->depth | (uintptr_t)p->cam2world | (uintptr_t)p->focal | (uintptr_t)p->center | (uintptr_t)xyz | (uintptr_t)src) & 3)
+  if (misaligned(3, p->depth, p->cam2world, p->focal, p->center, xyz, src))
     return set_err("lrf_points_fuse: float and int32 arrays must be 4-byte aligned");
-  if (((uintptr_t)count | (uintptr_t)workspace) & 7) return set_err("lrf_points_fuse: count and workspace must be 8-byte aligned");
+  if (misaligned(7, count, workspace)) return set_err("lrf_points_fuse: count and workspace must be 8-byte aligned");
   PointsArgs a;
   memset(&a, 0, sizeof(a));
   a.depth = p->depth; a.rgb8 = p->rgb8; a.c2w = p->cam2world; a.focal = p->focal; a.center = p->center;
@@ -257,15 +234,10 @@ extern "C" int lrf_points_fuse(const LrfPointsFuse* p, int64_t capacity, float* 
   a.n_neigh = p->n_neigh;
   for (int i = 0; i < p->n_neigh; ++i) a.neigh[i] = p->neigh[i];
   a.rel_tol = p->rel_tol; a.min_consistent = p->min_consistent;
-  const int n_wg = (int)((n + PTS_CAND_WG - 1) / PTS_CAND_WG);
-  unsigned long long* bits = static_cast<unsigned long long*>(workspace);
-  unsigned* wg = reinterpret_cast<unsigned*>(bits + (size_t)n_wg * PTS_WORDS_WG);
+  const PointsWs w = points_carve(workspace, n);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(k_points_mark, dim3(n_wg), dim3(PTS_NT), 0, st, a, bits, wg);
-  LRF_HIP(hipGetLastError());
-  hipLaunchKernelGGL(k_points_scan, dim3(1), dim3(PTS_SCAN_NT), 0, st, wg, n_wg, reinterpret_cast<long long*>(count));
-  LRF_HIP(hipGetLastError());
-  hipLaunchKernelGGL(k_points_write, dim3(n_wg), dim3(PTS_NT), 0, st, a, bits, wg, (long long)capacity, xyz, rgb8_out, src);
-  LRF_HIP(hipGetLastError());
+  LRF_TRY(launch(k_points_mark, w.n_wg, PTS_NT, st, a, w.bits, w.wg));
+  LRF_TRY(launch(k_points_scan, 1, PTS_SCAN_NT, st, w.wg, w.n_wg, reinterpret_cast<long long*>(count)));
+  LRF_TRY(launch(k_points_write, w.n_wg, PTS_NT, st, a, w.bits, w.wg, capacity, xyz, rgb8_out, src));
   return 0;
 }

@@ -1311,6 +1311,7 @@ static hipError_t lds_opt_in() {
 #include "lrf_select.inl"
 #include "lrf_evalgeo.inl"
 #include "lrf_encode.inl"
+#include "lrf_compact.inl"
 #include "lrf_points.inl"
 #include "lrf_mesh.inl"
 #include "lrf_mesh_clean.inl"

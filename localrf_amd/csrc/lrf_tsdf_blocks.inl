@@ -1,6 +1,6 @@
 // lrf_tsdf_blocks.inl -- a block-sparse TSDF volume: only the 8 x 8 x 8 blocks that some depth pixel's truncation band reaches
 // are stored, fused and meshed (included by lrf_render.hip after lrf_mesh.inl, which states the fusion and the meshing rules
-// and holds their code: tsdf_fuse_point, mesh_count_body, mesh_emit_body.  This file adds what is its own: which blocks
+// and holds their code: tsdf_fuse_point, mesh_count_body, mesh_emit_body, mesh_carve.  This file adds what is its own: which blocks
 // exist, where a lattice point is stored, and in which order the pool is walked).
 //
 // The virtual lattice has 8Bx x 8By x 8Bz points at origin + (ix, iy, iz) * voxel: the dense lattice of those dims.  Stored:
@@ -40,9 +40,8 @@
 namespace lrf {
 
 constexpr int BLK_PTS = 512;                                        // 8 x 8 x 8
-constexpr int BLK_NT = 256;                                         // table entries / pool points per workgroup
+constexpr int BLK_NT = 256;                                         // table entries per workgroup (pool points: MESH_NT)
 constexpr long long BLK_MAX_BLOCKS = (1ll << 22) - 1;               // 512 n < 2^31
-static_assert(BLK_NT == MESH_NT, "mesh_block_scan scans MESH_NT threads");
 
 struct BlocksArgs {
   uint8_t* marks; int* table; int* coords; float* tsdf; float* weight; float* rgb;
@@ -95,7 +94,7 @@ __global__ __launch_bounds__(BLK_NT) void k_blocks_flag(BlocksArgs a, unsigned* 
   __shared__ unsigned part[BLK_NT / 64];
   const long long i = (long long)blockIdx.x * BLK_NT + threadIdx.x;
   unsigned tot;
-  mesh_block_scan(blocks_fresh(a, i) ? 1u : 0u, part, tot);
+  block_scan_excl<BLK_NT>(blocks_fresh(a, i) ? 1u : 0u, part, tot);
   if (threadIdx.x == 0) wg[blockIdx.x] = tot;
 }
 
@@ -106,7 +105,7 @@ __global__ __launch_bounds__(BLK_NT) void k_blocks_assign(BlocksArgs a, const un
   const long long i = (long long)blockIdx.x * BLK_NT + threadIdx.x;
   const bool fresh = blocks_fresh(a, i);
   unsigned tot;
-  const unsigned pre = mesh_block_scan(fresh ? 1u : 0u, part, tot);
+  const unsigned pre = block_scan_excl<BLK_NT>(fresh ? 1u : 0u, part, tot);
   if (i >= a.nb) return;
   long long idx = a.table[i];
   if (fresh && a.n_blocks + count[0] <= max_blocks) {
@@ -160,17 +159,17 @@ struct BlocksMeshArgs {
   __device__ __forceinline__ float colour(int o, int c) const { return o >= 0 ? rgb[3 * (size_t)o + c] : 0.0f; }
 };
 
-__global__ __launch_bounds__(BLK_NT) void k_blocks_count(BlocksMeshArgs a, unsigned* __restrict__ info, unsigned* __restrict__ wgv,
-                                                         unsigned* __restrict__ wgf) {
-  __shared__ unsigned part[BLK_NT / 64];
+__global__ __launch_bounds__(MESH_NT) void k_blocks_count(BlocksMeshArgs a, unsigned* __restrict__ info, unsigned* __restrict__ wgv,
+                                                          unsigned* __restrict__ wgf) {
+  __shared__ unsigned part[MESH_NT / 64];
   mesh_count_body(a, part, info, wgv, wgf);
 }
 
-__global__ __launch_bounds__(BLK_NT) void k_blocks_emit(BlocksMeshArgs a, const unsigned* __restrict__ info,
+__global__ __launch_bounds__(MESH_NT) void k_blocks_emit(BlocksMeshArgs a, const unsigned* __restrict__ info,
                                                         const unsigned* __restrict__ wgv, const unsigned* __restrict__ wgf,
                                                         long long max_vertices, long long max_faces, float* __restrict__ vertices,
                                                         uint8_t* __restrict__ rgb8_out, int* __restrict__ faces) {
-  __shared__ unsigned part[BLK_NT / 64];
+  __shared__ unsigned part[MESH_NT / 64];
   mesh_emit_body(a, part, info, wgv, wgf, max_vertices, max_faces, vertices, rgb8_out, faces);
 }
 
@@ -181,17 +180,19 @@ static long long blocks_grid(int Bx, int By, int Bz) {
   return n >= (1ll << 31) || n * Bz >= (1ll << 31) ? 0 : n * Bz;
 }
 
+// the workspace of an assignment: the fresh blocks of each workgroup of BLK_NT table entries
+static unsigned* blocks_assign_wg(Carver& c, long long nb) { return c.take<unsigned>(blocks_for(nb, BLK_NT)); }
+
 // the checks the four entry points share; 0 when the volume passes
 static int blocks_check(const char* who, const LrfTsdfBlocks* g, bool pools, BlocksArgs& a) {
-  if (!g) return mesh_refuse(who, "null argument");
+  if (!g) return refuse(who, "null argument");
   const long long nb = blocks_grid(g->Bx, g->By, g->Bz);
-  if (!nb) return mesh_refuse(who, "need Bx, By, Bz >= 1, 8 B < 2^31 per axis and Bx By Bz < 2^31");
-  if (g->n_blocks < 0 || g->n_blocks > BLK_MAX_BLOCKS) return mesh_refuse(who, "need 0 <= n_blocks and 512 n_blocks < 2^31");
-  if (!g->table || !g->coords || (pools ? !g->tsdf || !g->weight : !g->marks)) return mesh_refuse(who, "null argument");
-  if (!(g->voxel > 0.0f)) return mesh_refuse(who, "voxel must be > 0");
-  if (!(g->trunc > 0.0f)) return mesh_refuse(who, "trunc must be > 0");
-  if (((uintptr_t)g->table | (uintptr_t)g->coords | (uintptr_t)g->tsdf | (uintptr_t)g->weight | (uintptr_t)g->rgb) & 3)
-    return mesh_refuse(who, "float and int32 arrays must be 4-byte aligned");
+  if (!nb) return refuse(who, "need Bx, By, Bz >= 1, 8 B < 2^31 per axis and Bx By Bz < 2^31");
+  if (g->n_blocks < 0 || g->n_blocks > BLK_MAX_BLOCKS) return refuse(who, "need 0 <= n_blocks and 512 n_blocks < 2^31");
+  if (!g->table || !g->coords || (pools ? !g->tsdf || !g->weight : !g->marks)) return refuse(who, "null argument");
+  if (!(g->voxel > 0.0f)) return refuse(who, "voxel must be > 0");
+  if (!(g->trunc > 0.0f)) return refuse(who, "trunc must be > 0");
+  if (misaligned(3, g->table, g->coords, g->tsdf, g->weight, g->rgb)) return refuse(who, "float and int32 arrays must be 4-byte aligned");
   memset(&a, 0, sizeof(a));
   a.marks = g->marks; a.table = g->table; a.coords = g->coords; a.tsdf = g->tsdf; a.weight = g->weight; a.rgb = g->rgb;
   a.Bx = g->Bx; a.By = g->By; a.Bz = g->Bz; a.n_blocks = g->n_blocks; a.nb = nb;
@@ -209,17 +210,17 @@ extern "C" int lrf_tsdf_blocks_touch(const LrfTsdfBlocks* g, const float* depth,
   if (blocks_check("lrf_tsdf_blocks_touch", g, false, a)) return 1;
   if (tsdf_check_frames("lrf_tsdf_blocks_touch", depth, cam2world, focal, center, V, H, W, d_min, d_max)) return 1;
   const long long n_px = (long long)V * H * W;
-  hipLaunchKernelGGL(k_blocks_touch, dim3((unsigned)((n_px + BLK_NT - 1) / BLK_NT)), dim3(BLK_NT), 0,
-                     reinterpret_cast<hipStream_t>(stream), a, depth, cam2world, focal, center, H, W, n_px, d_min, d_max);
-  LRF_HIP(hipGetLastError());
-  return 0;
+  return launch(k_blocks_touch, blocks_for(n_px, BLK_NT), BLK_NT, reinterpret_cast<hipStream_t>(stream), a, depth, cam2world, focal,
+                center, H, W, n_px, d_min, d_max);
 }
 
 extern "C" size_t lrf_tsdf_blocks_assign_workspace_bytes(int32_t Bx, int32_t By, int32_t Bz) {
   using namespace lrf;
   const long long nb = blocks_grid(Bx, By, Bz);
   if (!nb) return 0;
-  return ((size_t)((nb + BLK_NT - 1) / BLK_NT) * sizeof(unsigned) + 255) & ~(size_t)255;
+  Carver c(nullptr);
+  blocks_assign_wg(c, nb);
+  return c.bytes();
 }
 
 extern "C" int lrf_tsdf_blocks_assign(const LrfTsdfBlocks* g, int64_t max_blocks, int64_t coords_capacity, int64_t* count,
@@ -231,20 +232,16 @@ extern "C" int lrf_tsdf_blocks_assign(const LrfTsdfBlocks* g, int64_t max_blocks
   if (max_blocks < 0 || max_blocks > BLK_MAX_BLOCKS) return set_err("lrf_tsdf_blocks_assign: need 0 <= max_blocks and 512 max_blocks < 2^31");
   if (coords_capacity < 0 || coords_capacity >= (1ll << 31))
     return set_err("lrf_tsdf_blocks_assign: coords_capacity must lie in [0, 2^31)");
-  if ((uintptr_t)workspace & 3) return set_err("lrf_tsdf_blocks_assign: float and int32 arrays must be 4-byte aligned");
-  if ((uintptr_t)count & 7) return set_err("lrf_tsdf_blocks_assign: count must be 8-byte aligned");
-  const int n_wg = (int)((a.nb + BLK_NT - 1) / BLK_NT);
-  unsigned* wg = static_cast<unsigned*>(workspace);
+  if (misaligned(3, workspace)) return set_err("lrf_tsdf_blocks_assign: float and int32 arrays must be 4-byte aligned");
+  if (misaligned(7, count)) return set_err("lrf_tsdf_blocks_assign: count must be 8-byte aligned");
+  const int n_wg = (int)blocks_for(a.nb, BLK_NT);
+  Carver c(workspace);
+  unsigned* wg = blocks_assign_wg(c, a.nb);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(k_blocks_flag, dim3(n_wg), dim3(BLK_NT), 0, st, a, wg);
-  LRF_HIP(hipGetLastError());
-  hipLaunchKernelGGL(k_points_scan, dim3(1), dim3(PTS_SCAN_NT), 0, st, wg, n_wg, reinterpret_cast<long long*>(count));
-  LRF_HIP(hipGetLastError());
+  LRF_TRY(launch(k_blocks_flag, n_wg, BLK_NT, st, a, wg));
+  LRF_TRY(launch(k_points_scan, 1, PTS_SCAN_NT, st, wg, n_wg, reinterpret_cast<long long*>(count)));
   if (max_blocks == a.n_blocks) return 0;                            // a counting call: no fresh block could fit
-  hipLaunchKernelGGL(k_blocks_assign, dim3(n_wg), dim3(BLK_NT), 0, st, a, wg, reinterpret_cast<const long long*>(count),
-                     (long long)max_blocks, (long long)coords_capacity);
-  LRF_HIP(hipGetLastError());
-  return 0;
+  return launch(k_blocks_assign, n_wg, BLK_NT, st, a, wg, reinterpret_cast<const long long*>(count), max_blocks, coords_capacity);
 }
 
 extern "C" int lrf_tsdf_blocks_integrate(const LrfTsdfBlocks* g, const float* depth, const uint8_t* rgb8, const float* cam2world,
@@ -256,17 +253,14 @@ extern "C" int lrf_tsdf_blocks_integrate(const LrfTsdfBlocks* g, const float* de
   if (tsdf_check_frames("lrf_tsdf_blocks_integrate", depth, cam2world, focal, center, V, H, W, d_min, d_max)) return 1;
   if (!g->rgb != !rgb8) return set_err("lrf_tsdf_blocks_integrate: the volume's rgb and the frames' rgb8 go together");
   if (a.n_blocks == 0) return 0;                                     // no block: nothing to launch
-  hipLaunchKernelGGL(k_blocks_fuse, dim3(a.n_blocks), dim3(BLK_PTS), 0, reinterpret_cast<hipStream_t>(stream), a, depth, rgb8,
-                     cam2world, focal, center, V, H, W, d_min, d_max);
-  LRF_HIP(hipGetLastError());
-  return 0;
+  return launch(k_blocks_fuse, a.n_blocks, BLK_PTS, reinterpret_cast<hipStream_t>(stream), a, depth, rgb8, cam2world, focal, center,
+                V, H, W, d_min, d_max);
 }
 
 extern "C" size_t lrf_mesh_extract_blocks_workspace_bytes(int32_t n_blocks) {
   using namespace lrf;
   if (n_blocks < 0 || n_blocks > BLK_MAX_BLOCKS) return 0;
-  const size_t n = (size_t)n_blocks * BLK_PTS, n_wg = n / BLK_NT;
-  return (n * sizeof(unsigned) + 2 * n_wg * sizeof(unsigned) + 256) & ~(size_t)255;   // never 0 for an accepted count
+  return mesh_carve(nullptr, (long long)n_blocks * BLK_PTS, 1).bytes;   // never 0 for an accepted count
 }
 
 extern "C" int lrf_mesh_extract_blocks(const LrfTsdfBlocks* g, float level, float min_weight, int64_t max_vertices,
@@ -283,20 +277,10 @@ extern "C" int lrf_mesh_extract_blocks(const LrfTsdfBlocks* g, float level, floa
   a.table = b.table; a.coords = b.coords; a.value = b.tsdf; a.weight = b.weight; a.rgb = b.rgb;
   a.Bx = b.Bx; a.By = b.By; a.Bz = b.Bz; a.n = b.n_blocks * BLK_PTS;
   a.ox = b.ox; a.oy = b.oy; a.oz = b.oz; a.voxel = b.voxel; a.level = level; a.min_weight = min_weight;
-  const int n_wg = a.n / BLK_NT;
-  unsigned* info = static_cast<unsigned*>(workspace);
-  unsigned* wgv = info + a.n;
-  unsigned* wgf = wgv + n_wg;
+  const MeshWs w = mesh_carve(workspace, a.n, 1);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (n_wg) {
-    hipLaunchKernelGGL(k_blocks_count, dim3(n_wg), dim3(BLK_NT), 0, st, a, info, wgv, wgf);
-    LRF_HIP(hipGetLastError());
-  }
-  hipLaunchKernelGGL(k_points_scan, dim3(2), dim3(PTS_SCAN_NT), 0, st, wgv, n_wg, reinterpret_cast<long long*>(counts));
-  LRF_HIP(hipGetLastError());
-  if (!n_wg || (max_vertices == 0 && max_faces == 0)) return 0;       // no block, or a counting call: no row could be written
-  hipLaunchKernelGGL(k_blocks_emit, dim3(n_wg), dim3(BLK_NT), 0, st, a, info, wgv, wgf, (long long)max_vertices,
-                     (long long)max_faces, vertices, rgb8_out, faces);
-  LRF_HIP(hipGetLastError());
-  return 0;
+  if (w.n_wg) LRF_TRY(launch(k_blocks_count, w.n_wg, MESH_NT, st, a, w.info, w.wgv, w.wgf));
+  LRF_TRY(launch(k_points_scan, 2, PTS_SCAN_NT, st, w.wgv, w.n_wg, reinterpret_cast<long long*>(counts)));
+  if (!w.n_wg || (max_vertices == 0 && max_faces == 0)) return 0;     // no block, or a counting call: no row could be written
+  return launch(k_blocks_emit, w.n_wg, MESH_NT, st, a, w.info, w.wgv, w.wgf, max_vertices, max_faces, vertices, rgb8_out, faces);
 }
