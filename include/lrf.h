@@ -866,6 +866,41 @@ int lrf_depth_agreement(const float* mesh_depth, const float* depth, int32_t V, 
                         const float* rel_tols /* host [n_tols] */, int32_t n_tols, float d_min, float d_max,
                         int64_t* counts /* device [V,16] */, float* error_map /* nullable */, void* stream);
 
+/* A texture atlas baked for an indexed triangle mesh from encoded frames (csrc/lrf_mesh_texture.inl states the layout, the
+ * arithmetic and the kernels).  Layout: a patch of patch x patch texels (4 <= patch <= 64) per pair of faces, cols cells per
+ * row, rows = ceil(ceil(Nf / 2) / cols); the atlas is rows patch by cols patch texels.  state: device float4 per texel
+ * [rows patch, cols patch, 4] = (c_r, c_g, c_b, w), zero before the first bake.
+ * bake: per texel the frames [V,H,W,3] uint8 in frame order -- projected into the frame (cam2world [V,3,4], focal [1],
+ * center [2] on the device), tested against mesh_depth [V,H,W] (the mesh's own depth at those poses: |nz - dm| <= vis_tol dm)
+ * and for facing (cos >= min_cos; two_sided = 0 also drops the frames behind the face's winding normal), weighted by
+ * cos^2 / distance^2, sampled bilinearly, and folded into the state: blend 0 adds w c and w, blend 1 keeps the sample of the
+ * largest weight (the earliest frame of equal ones).  One launch (none with Nf = 0), state read and written once, no atomics:
+ * calls add up, frames k..V on top of 0..k leave the bytes of one call over 0..V.  rgb8 is not read.
+ * resolve: atlas uint8 [rows patch, cols patch, 3] = c / w (blend 0) or c (blend 1) rounded to nearest, ties to even; mask
+ * uint8 [rows patch, cols patch] = w > 0.  A texel no frame saw takes its face's vertex colours (rgb8 [Nv,3], nullable) under
+ * its barycentric weights, else fill (HOST uint8 [3]); a texel without a face takes fill.  info (device int64 [8]) = faces with
+ * an index outside [0, Nv) (never dereferenced), with two equal indices, with a coordinate not finite, with a zero normal (none
+ * of them is baked); texels that belong to a face, observed, coloured from the vertices, without a face.  Two launches (one
+ * with Nf = 0); only the mesh, layout and blend members are read.
+ * lrf_mesh_texture_state_bytes: 16 bytes per texel; cols <= 0 takes the default ceil(sqrt(ceil(Nf / 2))) (1 for Nf = 0); 0
+ * for refused arguments and for Nf = 0.
+ * Refused before any launch: null or misaligned pointers (float and int32 arrays 4 bytes, info 8, state 16), patch outside
+ * [4, 64], cols < 1, Nf < 0, Nv < 0 or >= 2^31, faces without vertices, 2^31 texels or more, blend outside {0, 1}; bake also
+ * V, H or W < 1, V H W >= 2^31, two_sided outside {0, 1}, vis_tol < 0 or NaN, min_cos outside [0, 1]. */
+typedef struct LrfMeshTexture {
+  const float* vertices; const uint8_t* rgb8 /* nullable */; const int32_t* faces;
+  const uint8_t* frames; const float* mesh_depth; const float* cam2world; const float* focal; const float* center;
+  int64_t Nv, Nf;
+  int32_t patch, cols, blend, two_sided;
+  int32_t V, H, W;
+  float vis_tol, min_cos;
+  int32_t reserved;
+} LrfMeshTexture;
+size_t lrf_mesh_texture_state_bytes(int64_t Nf, int32_t patch, int32_t cols);
+int lrf_mesh_texture_bake(const LrfMeshTexture* m, float* state, void* stream);
+int lrf_mesh_texture_resolve(const LrfMeshTexture* m, const float* state, const uint8_t* fill /* host [3] */, uint8_t* atlas,
+                             uint8_t* mask, int64_t* info /* device [8] */, void* stream);
+
 /* Depth quantiles of a ray: the distance at which its accumulated weight first reaches q; q = 0.5 is the median depth, which
  * always lies on a surface the ray met (csrc/lrf_quantile.inl states the arithmetic: fp32 without contraction, one fixed
  * summation order per ray).  With C_i the inclusive prefix sum of the weights lrf_render_fwd leaves in weight_out and i* the

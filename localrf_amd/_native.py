@@ -164,6 +164,14 @@ class LrfMeshRaster(C.Structure):
                 ("d_min", C.c_float), ("d_max", C.c_float)]
 
 
+class LrfMeshTexture(C.Structure):
+    _fields_ = [("vertices", _f), ("rgb8", C.c_void_p), ("faces", C.c_void_p), ("frames", C.c_void_p), ("mesh_depth", _f),
+                ("cam2world", _f), ("focal", _f), ("center", _f), ("Nv", C.c_int64), ("Nf", C.c_int64),
+                ("patch", C.c_int32), ("cols", C.c_int32), ("blend", C.c_int32), ("two_sided", C.c_int32),
+                ("V", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("vis_tol", C.c_float), ("min_cos", C.c_float),
+                ("reserved", C.c_int32)]
+
+
 class LrfTsdfBlocks(C.Structure):
     _fields_ = [("marks", C.c_void_p), ("table", C.c_void_p), ("coords", C.c_void_p), ("tsdf", _f), ("weight", _f), ("rgb", _f),
                 ("Bx", C.c_int32), ("By", C.c_int32), ("Bz", C.c_int32), ("n_blocks", C.c_int32),
@@ -310,6 +318,10 @@ SYMBOLS = {
                                            C.c_void_p, C.c_int32, C.c_void_p]),
     "lrf_depth_agreement": (C.c_int, [_f, _f, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float), C.c_int32, C.c_float,
                                       C.c_float, C.c_void_p, _f, C.c_void_p]),
+    "lrf_mesh_texture_state_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
+    "lrf_mesh_texture_bake": (C.c_int, [C.POINTER(LrfMeshTexture), _f, C.c_void_p]),
+    "lrf_mesh_texture_resolve": (C.c_int, [C.POINTER(LrfMeshTexture), _f, C.POINTER(C.c_uint8), C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p]),
     "lrf_density_gradient": (C.c_int, [C.POINTER(LrfField), _f, C.c_int64, _f, _f, C.c_void_p]),
     "lrf_normals_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "lrf_render_normals": (C.c_int, [C.POINTER(LrfField), _f, _f, C.c_int32, C.c_int32, C.c_uint32, C.c_float, _f, C.c_int32,
