@@ -901,6 +901,50 @@ int lrf_mesh_texture_bake(const LrfMeshTexture* m, float* state, void* stream);
 int lrf_mesh_texture_resolve(const LrfMeshTexture* m, const float* state, const uint8_t* fill /* host [3] */, uint8_t* atlas,
                              uint8_t* mask, int64_t* info /* device [8] */, void* stream);
 
+/* The closest point of an indexed triangle mesh for a batch of points, surface samples of a mesh, and a distance tensor
+ * summarised (csrc/lrf_mesh_distance.inl states the pair arithmetic, the grid, the search and its stopping rule, the sampling
+ * hash and the summary words).  Unsigned distance.  Faces with an index outside [0, Nv) (never dereferenced) or a corner that is
+ * not finite are skipped and counted; zero-area faces are kept as the segments or points they are.  Every call leaves the same
+ * bytes on every run.
+ * lrf_mesh_index_bounds: out (device int64 [8]) = bad_index_faces, nonfinite_faces, used_faces, 0, then six int32 -- the
+ * order-preserving keys (lrf_mesh_smooth_bounds') of the used faces' per-axis minima and maxima --, 0.  Two launches.
+ * The index: grid, lrf_mesh_index_workspace_bytes(cells) bytes (a start and an end per cell; 0 when cells is outside
+ * [1, 2^31)), and list, int32 [entries].  lo, cell, dims: the grid; a point's cell on axis k is floor((x - lo_k) / cell) in
+ * fp64, clamped to [0, dims_k - 1].  lrf_mesh_index_build with list null is the count pass (three launches): it leaves the
+ * cells' starts in grid and the number of entries in total (device int64 [1]); the caller reads it back, allocates list, and
+ * calls again with list and entries: the fill pass (two launches).
+ * lrf_mesh_closest: points [N,3] -> distance [N] ((float)sqrt of the fp64 squared distance; +inf without a face within
+ * max_distance; NaN for a point that is not finite), face int32 [N] (the smallest index among equal distances; -1), closest
+ * [N,3] (nullable; NaN without a face).  One launch, no atomics.  The result does not depend on cell.
+ * lrf_mesh_sample_count: offsets (device uint32 [Nf]) = the samples before each face, info (device int64 [4]) = the total,
+ * bad_index_faces, nonfinite_faces, faces that would take more than 2^21 samples (the caller refuses).  Three launches.
+ * lrf_mesh_sample_emit: points [M,3] and face int32 [M] in face order; rows at M and beyond are not written.  One launch.
+ * lrf_distance_summary: distance [N] -> words (device int64 [16]) = finite, infinite, NaN entries, sum1, sum2, the largest
+ * finite bits, 0, 0, and at 8 + k the finite entries <= thresholds[k].  thresholds: HOST array.  Two launches (one with N = 0).
+ * Refused before any launch: null or misaligned pointers (float and int32 arrays 4 bytes; out, info, total, words and grid 8),
+ * Nv outside [1, 2^31), Nf outside [0, 2^31) (index build, closest and sampling: Nf < 1), dims < 1 or 2^31 cells or more, cell
+ * or lo not finite, cell <= 0, entries outside [0, 2^31), N outside [1, 2^31) (summary: [0, 2^31)), max_distance < 0 or NaN,
+ * spacing, unit or a threshold not finite or <= 0, M outside [1, 2^31), n_thresholds outside [0, 8]. */
+#define LRF_DISTANCE_MAX_THRESHOLDS 8
+typedef struct LrfMeshIndex {
+  const float* vertices; const int32_t* faces; void* grid; int32_t* list /* null: the count pass */;
+  int64_t Nv, Nf, entries;
+  double lo[3]; double cell;
+  int32_t dims[3]; int32_t reserved;
+} LrfMeshIndex;
+int lrf_mesh_index_bounds(const float* vertices, const int32_t* faces, int64_t Nv, int64_t Nf, int64_t* out /* device [8] */,
+                          void* stream);
+size_t lrf_mesh_index_workspace_bytes(int64_t cells);
+int lrf_mesh_index_build(const LrfMeshIndex* m, int64_t* total /* device [1]; nullable in the fill pass */, void* stream);
+int lrf_mesh_closest(const LrfMeshIndex* m, const float* points, int64_t N, double max_distance, float* distance, int32_t* face,
+                     float* closest /* nullable */, void* stream);
+int lrf_mesh_sample_count(const float* vertices, const int32_t* faces, int64_t Nv, int64_t Nf, double spacing,
+                          uint32_t* offsets /* device [Nf] */, int64_t* info /* device [4] */, void* stream);
+int lrf_mesh_sample_emit(const float* vertices, const int32_t* faces, int64_t Nv, int64_t Nf, double spacing,
+                         const uint32_t* offsets, int64_t M, float* points, int32_t* face, void* stream);
+int lrf_distance_summary(const float* distance, int64_t N, const float* thresholds /* host [n_thresholds] */,
+                         int32_t n_thresholds, float unit, int64_t* words /* device [16] */, void* stream);
+
 /* Depth quantiles of a ray: the distance at which its accumulated weight first reaches q; q = 0.5 is the median depth, which
  * always lies on a surface the ray met (csrc/lrf_quantile.inl states the arithmetic: fp32 without contraction, one fixed
  * summation order per ray).  With C_i the inclusive prefix sum of the weights lrf_render_fwd leaves in weight_out and i* the

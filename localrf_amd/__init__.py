@@ -26,6 +26,8 @@ Public surface mirrors the reference's names:
                                     (a mesh rasterised back into camera poses and compared with rendered depth; no reference row)
   mesh_texture.TextureBaker / scene_texture / face_uv / sample_texture / write_obj
                                     (a texture atlas baked for a mesh from rendered frames, OBJ + PNG export; no reference row)
+  mesh_distance.MeshIndex / sample_surface / distance_summary / cloud_to_mesh / mesh_distance
+                                    (point-to-mesh distance: surface error, Chamfer, Hausdorff and F-score; no reference row)
 The arithmetic of TensorVMSplit.forward and of LocalTensorfs.forward (ray generation, field
 blend, exposure) runs in hand-written HIP kernels for gfx950 (csrc/), reached through the C ABI
 of include/lrf.h.
@@ -45,6 +47,7 @@ from . import depth_quantiles  # noqa: F401
 from . import mesh  # noqa: F401
 from . import mesh_raster  # noqa: F401
 from . import mesh_texture  # noqa: F401
+from . import mesh_distance  # noqa: F401
 from .frames import DeviceFrames  # noqa: F401
 
-__all__ = ["TensorVMSplit", "AlphaGridMask", "MLPRender_Fea_late_view", "LocalTensorfs", "rays", "losses", "metrics", "diagnostics", "novel_views", "pointcloud", "normals", "depth_quantiles", "mesh", "mesh_raster", "mesh_texture", "NativeError", "FusedAdam", "DeviceFrames"]
+__all__ = ["TensorVMSplit", "AlphaGridMask", "MLPRender_Fea_late_view", "LocalTensorfs", "rays", "losses", "metrics", "diagnostics", "novel_views", "pointcloud", "normals", "depth_quantiles", "mesh", "mesh_raster", "mesh_texture", "mesh_distance", "NativeError", "FusedAdam", "DeviceFrames"]

@@ -164,6 +164,15 @@ class LrfMeshRaster(C.Structure):
                 ("d_min", C.c_float), ("d_max", C.c_float)]
 
 
+LRF_DISTANCE_MAX_THRESHOLDS = 8
+
+
+class LrfMeshIndex(C.Structure):
+    _fields_ = [("vertices", _f), ("faces", C.c_void_p), ("grid", C.c_void_p), ("list", C.c_void_p),
+                ("Nv", C.c_int64), ("Nf", C.c_int64), ("entries", C.c_int64),
+                ("lo", C.c_double * 3), ("cell", C.c_double), ("dims", C.c_int32 * 3), ("reserved", C.c_int32)]
+
+
 class LrfMeshTexture(C.Structure):
     _fields_ = [("vertices", _f), ("rgb8", C.c_void_p), ("faces", C.c_void_p), ("frames", C.c_void_p), ("mesh_depth", _f),
                 ("cam2world", _f), ("focal", _f), ("center", _f), ("Nv", C.c_int64), ("Nf", C.c_int64),
@@ -318,6 +327,14 @@ SYMBOLS = {
                                            C.c_void_p, C.c_int32, C.c_void_p]),
     "lrf_depth_agreement": (C.c_int, [_f, _f, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float), C.c_int32, C.c_float,
                                       C.c_float, C.c_void_p, _f, C.c_void_p]),
+    "lrf_mesh_index_bounds": (C.c_int, [_f, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    "lrf_mesh_index_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "lrf_mesh_index_build": (C.c_int, [C.POINTER(LrfMeshIndex), C.c_void_p, C.c_void_p]),
+    "lrf_mesh_closest": (C.c_int, [C.POINTER(LrfMeshIndex), _f, C.c_int64, C.c_double, _f, C.c_void_p, _f, C.c_void_p]),
+    "lrf_mesh_sample_count": (C.c_int, [_f, C.c_void_p, C.c_int64, C.c_int64, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "lrf_mesh_sample_emit": (C.c_int, [_f, C.c_void_p, C.c_int64, C.c_int64, C.c_double, C.c_void_p, C.c_int64, _f, C.c_void_p,
+                                       C.c_void_p]),
+    "lrf_distance_summary": (C.c_int, [_f, C.c_int64, C.POINTER(C.c_float), C.c_int32, C.c_float, C.c_void_p, C.c_void_p]),
     "lrf_mesh_texture_state_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
     "lrf_mesh_texture_bake": (C.c_int, [C.POINTER(LrfMeshTexture), _f, C.c_void_p]),
     "lrf_mesh_texture_resolve": (C.c_int, [C.POINTER(LrfMeshTexture), _f, C.POINTER(C.c_uint8), C.c_void_p, C.c_void_p, C.c_void_p,
