@@ -29,28 +29,26 @@ import torch
 
 from . import _native as N
 from ._native import NativeError
-from . import depth_quantiles, novel_views, pointcloud
-from .pointcloud import SceneFrames, _check_depth, _check_intrinsics, _check_poses, _dev_f32
-from .pose_plan import nearest_frames
+from . import pointcloud
+from ._checks import INT32 as _INT32
+from ._checks import (check_bytes, check_depth, check_faces, check_flag, check_frame_poses, check_int, check_interval, check_intrinsics,
+                      check_mesh, check_origin, check_positive, check_range, check_rgb, dev_f32, float_of_key, mesh_on_device,
+                      rgb8_frames)
+from .pointcloud import SceneFrames
 
-_INT32 = (1 << 31) - 1
 BYTES_PER_VOXEL = 8                            # tsdf and weight
 BYTES_PER_VOXEL_RGB = 12
 
 
 def _check_lattice(origin, voxel, dims):
-    o = np.asarray(origin.detach().cpu() if torch.is_tensor(origin) else origin, dtype=np.float64).reshape(-1)
-    if o.size != 3 or not np.isfinite(o).all():
-        raise ValueError(f"origin must hold 3 finite values, got {origin!r}")
-    voxel = float(voxel)
-    if not (voxel > 0 and math.isfinite(voxel)):
-        raise ValueError(f"voxel must be a finite number > 0, got {voxel}")
+    origin = check_origin(origin)
+    voxel = check_positive("voxel", float(voxel))
     if len(dims) != 3 or any(int(d) != d or int(d) < 1 for d in dims):
         raise ValueError(f"dims must be (Nx, Ny, Nz) integers >= 1, got {dims!r}")
     dims = tuple(int(d) for d in dims)
     if dims[0] * dims[1] * dims[2] > _INT32:
         raise ValueError(f"dims {dims} hold {dims[0] * dims[1] * dims[2]} lattice points; a volume takes Nx Ny Nz < 2^31")
-    return tuple(float(v) for v in o), voxel, dims
+    return origin, voxel, dims
 
 
 def _check_extract(level, min_weight, max_vertices, max_faces):
@@ -60,51 +58,28 @@ def _check_extract(level, min_weight, max_vertices, max_faces):
     if not min_weight > 0:
         raise ValueError(f"min_weight must be > 0, got {min_weight}")
     for name, cap in (("max_vertices", max_vertices), ("max_faces", max_faces)):
-        if cap is not None and (int(cap) != cap or not 0 <= int(cap) <= _INT32):
-            raise ValueError(f"{name} must be None or an integer in [0, 2^31), got {cap!r}")
+        check_int(name, cap, 0, _INT32, "None or an integer in [0, 2^31)", none_ok=True)
     return level, min_weight
-
-
-def _check_range(depth_range):
-    if len(depth_range) != 2:
-        raise ValueError(f"depth_range must be (d_min, d_max), got {depth_range!r}")
-    d_min, d_max = float(depth_range[0]), float(depth_range[1])
-    if not d_min <= d_max:
-        raise ValueError(f"depth_range needs d_min <= d_max, got {depth_range!r}")
-    return d_min, d_max
 
 
 def _check_frames(colours, dev, depth, poses, focal, center, rgb, depth_range, what="TsdfVolume"):
     """The frame arguments of an integration into a volume on dev that keeps colours or not, checked on the host ->
     (depth, rgb8 or None, poses, focal, center as contiguous device tensors, (V, H, W), (d_min, d_max))."""
-    V, H, W = _check_depth(depth)
+    V, H, W = check_depth(depth)
     if (rgb is not None) != colours:
         raise ValueError(f"rgb goes with a volume that keeps colours: pass rgb to a {what}(colours=True) and only to it")
     if rgb is not None:
-        if not torch.is_tensor(rgb):
-            raise TypeError("rgb must be a torch tensor or None")
-        if not (rgb.is_floating_point() or rgb.dtype is torch.uint8):
-            raise ValueError(f"rgb must hold floating-point or uint8 values, got {rgb.dtype}")
-        if tuple(rgb.shape) != (V, H, W, 3):
-            raise ValueError(f"rgb must be {(V, H, W, 3)} to go with depth {tuple(depth.shape)}, got {tuple(rgb.shape)}")
-        if rgb.device != depth.device:
-            raise ValueError("rgb and depth must live on the same device")
-    poses = _check_poses(poses, V)
-    focal, center = _check_intrinsics(focal, center, False)
-    d_min, d_max = _check_range(depth_range)
+        check_rgb(rgb, depth)
+    poses = check_frame_poses(poses, V)
+    focal, center = check_intrinsics(focal, center, False)
+    d_min, d_max = check_range(depth_range)
     N.require_gpu(depth, "depth", "the TSDF integration")
     if depth.device != dev:
         raise ValueError(f"depth lives on {depth.device}, the volume on {dev}")
-    rgb8 = None
-    if rgb is not None:
-        if rgb.dtype is torch.uint8:
-            rgb8 = rgb.contiguous()
-        else:
-            from .novel_views import encode_frames
-            rgb8 = encode_frames(rgb.detach(), depth.detach())[0]
+    rgb8 = None if rgb is None else rgb8_frames(rgb, depth)
     depth = N.conform(depth)
     poses = poses.detach().to(device=dev, dtype=torch.float32).contiguous()
-    return depth, rgb8, poses, _dev_f32(focal, 1, dev), _dev_f32(center, 2, dev), (V, H, W), (d_min, d_max)
+    return depth, rgb8, poses, dev_f32(focal, 1, dev), dev_f32(center, 2, dev), (V, H, W), (d_min, d_max)
 
 
 def _sized_extract(dev, colours, launch, max_vertices, max_faces):
@@ -192,40 +167,12 @@ _NO_FILTER = {"min_component_faces": 0, "min_component_fraction": 0.0}
 
 
 def _check_rounds(max_rounds):
-    if isinstance(max_rounds, bool) or int(max_rounds) != max_rounds or int(max_rounds) < 1:
-        raise ValueError(f"max_rounds must be an integer >= 1, got {max_rounds!r}")
-    return int(max_rounds)
+    return check_int("max_rounds", max_rounds, 1, wording="an integer >= 1")
 
 
 def _check_keep(min_faces, min_fraction, what=("min_faces", "min_fraction")):
-    try:
-        ok = not isinstance(min_faces, bool) and int(min_faces) == min_faces and int(min_faces) >= 0
-    except (TypeError, ValueError, OverflowError):
-        ok = False
-    if not ok:
-        raise ValueError(f"{what[0]} must be an integer >= 0, got {min_faces!r}")
-    try:
-        fraction = float(min_fraction)
-    except (TypeError, ValueError):
-        fraction = math.nan
-    if not 0.0 <= fraction <= 1.0:                                  # NaN fails
-        raise ValueError(f"{what[1]} must lie in [0, 1], got {min_fraction!r}")
-    return int(min_faces), fraction
-
-
-def _check_faces(faces, n_vertices):
-    """type, then dtype and shape -> (Nv, Nf); the device check is the caller's, after its other arguments."""
-    if not torch.is_tensor(faces):
-        raise TypeError("faces must be a torch tensor")
-    if faces.dtype is not torch.int32 or faces.dim() != 2 or faces.shape[1] != 3:
-        raise ValueError(f"faces must be [Nf, 3] int32, got {faces.dtype} {tuple(faces.shape)}")
-    if isinstance(n_vertices, bool) or int(n_vertices) != n_vertices or not 0 <= int(n_vertices) <= _INT32:
-        raise ValueError(f"n_vertices must be an integer in [0, 2^31), got {n_vertices!r}")
-    if faces.shape[0] > _INT32:
-        raise ValueError(f"faces holds {faces.shape[0]} rows; a mesh takes Nf < 2^31")
-    if int(n_vertices) == 0 and faces.shape[0]:
-        raise ValueError(f"faces holds {faces.shape[0]} rows for a mesh without vertices")
-    return int(n_vertices), int(faces.shape[0])
+    return (check_int(what[0], min_faces, 0, wording="an integer >= 0"),
+            check_interval(what[1], min_fraction, 0.0, 1.0, "lie in [0, 1]"))
 
 
 def _components(faces, Nv, Nf, max_rounds):
@@ -270,26 +217,10 @@ def components(faces, n_vertices, max_rounds=64):
     counts it.  max_rounds guards against a loop that never ends -- it is not tuned -- and raises RuntimeError naming the
     count when it is reached.  A face index outside [0, n_vertices) is never dereferenced and raises ValueError.  One more
     read-back brings the three summary words.  The labels are a unique fixed point: the same bytes on every run."""
-    Nv, Nf = _check_faces(faces, n_vertices)
+    Nv, Nf = check_faces(faces, n_vertices)
     max_rounds = _check_rounds(max_rounds)
     N.require_gpu(faces, "faces", "the component labelling")
     return _components(faces.detach().contiguous(), Nv, Nf, max_rounds)
-
-
-def _check_mesh(mesh):
-    """type, then dtype and shape, then device -> (vertices, faces, rgb8 or None, Nv, Nf), contiguous."""
-    if not isinstance(mesh, dict) or "vertices" not in mesh or "faces" not in mesh:
-        raise TypeError("mesh must be a dict with vertices and faces, as extract_mesh returns it")
-    v, f, c = mesh["vertices"], mesh["faces"], mesh.get("rgb8")
-    for name, t in (("vertices", v), ("faces", f)) + ((("rgb8", c),) if c is not None else ()):
-        if not torch.is_tensor(t):
-            raise TypeError(f"{name} must be a torch tensor" + (" or None" if name == "rgb8" else ""))
-    if v.dtype is not torch.float32 or v.dim() != 2 or v.shape[1] != 3:
-        raise ValueError(f"vertices must be [Nv, 3] float32, got {v.dtype} {tuple(v.shape)}")
-    Nv, Nf = _check_faces(f, int(v.shape[0]))
-    if c is not None and (c.dtype is not torch.uint8 or tuple(c.shape) != (Nv, 3)):
-        raise ValueError(f"rgb8 must be {(Nv, 3)} uint8 or None, got {c.dtype} {tuple(c.shape)}")
-    return v, f, c, Nv, Nf
 
 
 def filter_components(mesh, min_faces=0, min_fraction=0.0, max_rounds=64):
@@ -304,18 +235,10 @@ def filter_components(mesh, min_faces=0, min_fraction=0.0, max_rounds=64):
     counts (0, 0).  Returns a new mesh dict -- every other entry of the input is carried over -- with "components": the
     Python ints of components() (n_components, n_with_faces, largest_faces, rounds), "threshold" and "kept", the number of
     kept components."""
-    v, f, c, Nv, Nf = _check_mesh(mesh)
+    v, f, c, Nv, Nf = check_mesh(mesh)
     min_faces, min_fraction = _check_keep(min_faces, min_fraction)
     max_rounds = _check_rounds(max_rounds)
-    N.require_gpu(v, "vertices", "the component filter")
-    N.require_gpu(f, "faces", "the component filter")
-    if c is not None:
-        N.require_gpu(c, "rgb8", "the component filter")
-    dev = v.device
-    if f.device != dev or (c is not None and c.device != dev):
-        raise ValueError("vertices, faces and rgb8 must live on the same device")
-    v, f = v.detach().contiguous(), f.detach().contiguous()
-    c = None if c is None else c.contiguous()
+    v, f, c, dev = mesh_on_device(v, f, c, "the component filter")
     comp = _components(f, Nv, Nf, max_rounds)
     threshold = max(min_faces, int(math.ceil(min_fraction * comp["largest_faces"])))
     out = dict(mesh)
@@ -343,29 +266,9 @@ def filter_components(mesh, min_faces=0, min_fraction=0.0, max_rounds=64):
     return out
 
 
-def _check_cell(cell, what="cell"):
-    try:
-        ok = not isinstance(cell, bool) and math.isfinite(float(cell)) and float(cell) > 0
-    except (TypeError, ValueError, OverflowError):
-        ok = False
-    if not ok:
-        raise ValueError(f"{what} must be a finite number > 0, got {cell!r}")
-    return float(cell)
-
-
-def _check_anchor(origin):
-    try:
-        o = np.asarray(origin.detach().cpu() if torch.is_tensor(origin) else origin, dtype=np.float64).reshape(-1)
-    except (TypeError, ValueError):
-        o = np.zeros(0)
-    if o.size != 3 or not np.isfinite(o).all():
-        raise ValueError(f"origin must hold 3 finite values, got {origin!r}")
-    return tuple(float(x) for x in o)
-
-
 def _check_simplify_cell(simplify_cell):
     """extract's option: None, or a cell edge."""
-    return None if simplify_cell is None else _check_cell(simplify_cell, "simplify_cell")
+    return None if simplify_cell is None else check_positive("simplify_cell", simplify_cell)
 
 
 def simplify(mesh, cell, origin=(0.0, 0.0, 0.0), dedupe=True, max_bytes=1 << 30):
@@ -383,27 +286,12 @@ def simplify(mesh, cell, origin=(0.0, 0.0, 0.0), dedupe=True, max_bytes=1 << 30)
     are allocated at the input's sizes and sliced.  Returns a new mesh dict -- every other entry of the input is carried over
     -- with "simplify": the Python values cell, origin, box (lo, dims: the cell box of the input), occupied (cells that hold
     a vertex), degenerate_faces and duplicate_faces."""
-    v, f, c, Nv, Nf = _check_mesh(mesh)
-    cell = _check_cell(cell)
-    origin = _check_anchor(origin)
-    if not isinstance(dedupe, (bool, np.bool_)):
-        raise ValueError(f"dedupe must be True or False, got {dedupe!r}")
-    try:
-        ok = not isinstance(max_bytes, bool) and int(max_bytes) == max_bytes and int(max_bytes) >= 0
-    except (TypeError, ValueError, OverflowError):
-        ok = False
-    if not ok:
-        raise ValueError(f"max_bytes must be an integer >= 0, got {max_bytes!r}")
-    max_bytes = int(max_bytes)
-    N.require_gpu(v, "vertices", "the mesh simplification")
-    N.require_gpu(f, "faces", "the mesh simplification")
-    if c is not None:
-        N.require_gpu(c, "rgb8", "the mesh simplification")
-    dev = v.device
-    if f.device != dev or (c is not None and c.device != dev):
-        raise ValueError("vertices, faces and rgb8 must live on the same device")
-    v, f = v.detach().contiguous(), f.detach().contiguous()
-    c = None if c is None else c.contiguous()
+    v, f, c, Nv, Nf = check_mesh(mesh)
+    cell = check_positive("cell", cell)
+    origin = check_origin(origin)
+    dedupe = check_flag("dedupe", dedupe)
+    max_bytes = check_bytes(max_bytes)
+    v, f, c, dev = mesh_on_device(v, f, c, "the mesh simplification")
     out = dict(mesh)
     info = {"cell": cell, "origin": origin, "box": {"lo": (0, 0, 0), "dims": (0, 0, 0)}, "occupied": 0, "degenerate_faces": 0,
             "duplicate_faces": 0}
@@ -432,7 +320,7 @@ def simplify(mesh, cell, origin=(0.0, 0.0, 0.0), dedupe=True, max_bytes=1 << 30)
     counts = torch.empty(5, dtype=torch.int64, device=dev)
     a = N.LrfMeshSimplify()
     a.vertices, a.rgb8, a.faces = v.data_ptr(), None if c is None else c.data_ptr(), f.data_ptr() if Nf else None
-    a.Nv, a.Nf, a.cell, a.dedupe = Nv, Nf, cell, int(bool(dedupe))
+    a.Nv, a.Nf, a.cell, a.dedupe = Nv, Nf, cell, int(dedupe)
     for k in range(3):
         a.origin[k], a.lo[k], a.dims[k] = origin[k], lo[k], dims[k]
     N.launch("lrf_mesh_simplify", dev, C.byref(a), vo.data_ptr(), None if co is None else co.data_ptr(),
@@ -447,36 +335,17 @@ def simplify(mesh, cell, origin=(0.0, 0.0, 0.0), dedupe=True, max_bytes=1 << 30)
     return out
 
 
-def _check_iterations(iterations, what="iterations"):
-    try:
-        ok = not isinstance(iterations, (bool, np.bool_)) and int(iterations) == iterations and 0 <= int(iterations) <= 1000
-    except (TypeError, ValueError, OverflowError):
-        ok = False
-    if not ok:
-        raise ValueError(f"{what} must be an integer in [0, 1000], got {iterations!r}")
-    return int(iterations)
-
-
 def _check_post(smooth_iterations, normals):
     """extract's options: the smoothing iterations (0: none) and whether vertex normals are wanted."""
-    smooth_iterations = _check_iterations(smooth_iterations, "smooth_iterations")
-    if not isinstance(normals, (bool, np.bool_)):
-        raise ValueError(f"normals must be True or False, got {normals!r}")
-    return smooth_iterations, bool(normals)
+    return check_int("smooth_iterations", smooth_iterations, 0, 1000), check_flag("normals", normals)
 
 
-def _mesh_on_device(mesh, feature, checks=None):
-    """_check_mesh, then checks() (the call's other arguments), then the device -> (vertices, faces, Nv, Nf, device)."""
-    v, f, c, Nv, Nf = _check_mesh(mesh)
+def _check_incidence_mesh(mesh):
+    """check_mesh and the bound of the incidence lists -> (vertices, faces, Nv, Nf); rgb8 is not read."""
+    v, f, _, Nv, Nf = check_mesh(mesh)
     if 3 * Nf > _INT32:
         raise ValueError(f"faces holds {Nf} rows; the incidence lists take 3 Nf < 2^31")
-    if checks is not None:
-        checks()
-    N.require_gpu(v, "vertices", feature)
-    N.require_gpu(f, "faces", feature)
-    if f.device != v.device:
-        raise ValueError("vertices and faces must live on the same device")
-    return v.detach().contiguous(), f.detach().contiguous(), Nv, Nf, v.device
+    return v, f, Nv, Nf
 
 
 def _raise_flags(flags, Nv):
@@ -499,7 +368,8 @@ def topology(mesh):
     opp > 1), degenerate_faces, closed (both edge counts are 0) -- and boundary_vertices: a device [Nv] uint8 mask, 1 at both
     ends of every edge with opp == 0.  Integer counts: the same values on every run.  One call, one read-back; a face index
     outside [0, Nv) is never dereferenced and raises ValueError, and so does a vertex held by 2^20 faces or more."""
-    v, f, Nv, Nf, dev = _mesh_on_device(mesh, "the mesh topology")
+    v, f, Nv, Nf = _check_incidence_mesh(mesh)
+    v, f, _, dev = mesh_on_device(v, f, None, "the mesh topology")
     mask = torch.empty(Nv, dtype=torch.uint8, device=dev)
     if Nv == 0:
         return {"boundary_edges": 0, "nonmanifold_edges": 0, "degenerate_faces": 0, "closed": True, "boundary_vertices": mask}
@@ -523,7 +393,8 @@ def vertex_normals(mesh):
     ValueError.  Returns a new mesh dict -- every other entry of the input is carried over -- with "normals" and
     "normal_info": the Python ints zero_normals and degenerate_faces.  pointcloud.write_ply(path, vertices, rgb8,
     normals=mesh["normals"], faces=mesh["faces"]) writes them."""
-    v, f, Nv, Nf, dev = _mesh_on_device(mesh, "the vertex normals")
+    v, f, Nv, Nf = _check_incidence_mesh(mesh)
+    v, f, _, dev = mesh_on_device(v, f, None, "the vertex normals")
     out = dict(mesh)
     normals = torch.empty(Nv, 3, dtype=torch.float32, device=dev)
     if Nv == 0:
@@ -537,12 +408,6 @@ def vertex_normals(mesh):
     _raise_flags(words[0], Nv)
     out.update(normals=normals, normal_info={"zero_normals": words[4], "degenerate_faces": words[1]})
     return out
-
-
-def _float_of_key(key):
-    """The fp32 value of k_sm_bounds' order-preserving integer, as a Python float."""
-    bits = (key ^ ((key >> 31) & 0x7FFFFFFF)) & 0xFFFFFFFF
-    return float(np.array([bits], np.uint32).view(np.float32)[0])
 
 
 def smooth(mesh, iterations=10, lam=0.5, mu=-0.53, boundary="fixed"):
@@ -561,24 +426,15 @@ def smooth(mesh, iterations=10, lam=0.5, mu=-0.53, boundary="fixed"):
     synchronisation between them (a face index outside [0, Nv) is never dereferenced and raises ValueError; so do a vertex held
     by 2^20 faces or more and an iteration that leaves 32 times the input's extent).  Returns a new mesh dict with "smooth":
     iterations, lam, mu, boundary, pinned, boundary_edges, nonmanifold_edges, degenerate_faces."""
-    state = {}
-
-    def checks():
-        state["iterations"] = _check_iterations(iterations)
-        for name, x, ok in (("lam", lam, lambda t: 0.0 < t <= 1.0), ("mu", mu, lambda t: -1.0 <= t <= 0.0)):
-            try:
-                t = math.nan if isinstance(x, (bool, np.bool_)) else float(x)
-            except (TypeError, ValueError):
-                t = math.nan
-            if not ok(t):                                           # NaN fails
-                raise ValueError(f"{name} must satisfy " + ("0 < lam <= 1" if name == "lam" else "-1 <= mu <= 0") + f", got {x!r}")
-            state[name] = t
-        if boundary not in ("fixed", "free"):
-            raise ValueError(f"boundary must be 'fixed' or 'free', got {boundary!r}")
-
-    v, f, Nv, Nf, dev = _mesh_on_device(mesh, "the mesh smoothing", checks)
+    v, f, Nv, Nf = _check_incidence_mesh(mesh)
+    iterations = check_int("iterations", iterations, 0, 1000)
+    lam = check_interval("lam", lam, 0.0, 1.0, "satisfy 0 < lam <= 1", open_lo=True)
+    mu = check_interval("mu", mu, -1.0, 0.0, "satisfy -1 <= mu <= 0")
+    if boundary not in ("fixed", "free"):
+        raise ValueError(f"boundary must be 'fixed' or 'free', got {boundary!r}")
+    v, f, _, dev = mesh_on_device(v, f, None, "the mesh smoothing")
     out = dict(mesh)
-    info = {"iterations": state["iterations"], "lam": state["lam"], "mu": state["mu"], "boundary": boundary, "pinned": 0,
+    info = {"iterations": iterations, "lam": lam, "mu": mu, "boundary": boundary, "pinned": 0,
             "boundary_edges": 0, "nonmanifold_edges": 0, "degenerate_faces": 0}
     if Nv == 0:
         out.update(vertices=v, smooth=info)
@@ -588,13 +444,13 @@ def smooth(mesh, iterations=10, lam=0.5, mu=-0.53, boundary="fixed"):
     keys = keys.tolist()                                            # read-back one
     if keys[6]:
         raise ValueError("vertices holds a value that is not finite")
-    lo = [_float_of_key(k) for k in keys[:3]]
-    extent = max(_float_of_key(k) - l for k, l in zip(keys[3:6], lo))
+    lo = [float_of_key(k) for k in keys[:3]]
+    extent = max(float_of_key(k) - l for k, l in zip(keys[3:6], lo))
     a = N.LrfMeshSmooth()
     a.vertices, a.faces, a.Nv, a.Nf = v.data_ptr(), f.data_ptr() if Nf else None, Nv, Nf
-    a.lam, a.mu, a.pin_boundary = state["lam"], state["mu"], int(boundary == "fixed")
+    a.lam, a.mu, a.pin_boundary = lam, mu, int(boundary == "fixed")
     # a box of zero extent: nothing can move, the call copies the input's bytes (and still counts)
-    a.s, a.iterations = (36 - math.frexp(extent)[1], state["iterations"]) if extent > 0.0 else (0, 0)
+    a.s, a.iterations = (36 - math.frexp(extent)[1], iterations) if extent > 0.0 else (0, 0)
     for k in range(3):
         a.lo[k] = lo[k]
     vo = torch.empty_like(v)
@@ -626,9 +482,7 @@ def _filtered(mesh, min_component_faces, min_component_fraction, simplify_cell=N
 
 def _check_trunc_device(name, trunc, device):
     """The constructors' tail of checks -> (trunc, torch.device); the refusal names the class."""
-    trunc_f = float(trunc)
-    if not (trunc_f > 0 and math.isfinite(trunc_f)):
-        raise ValueError(f"trunc must be a finite number > 0, got {trunc}")
+    trunc_f = check_positive("trunc", trunc)
     dev = torch.device(device)
     if dev.type != "cuda":
         raise NativeError(f"localrf_amd.mesh: a {name} on {dev}; the integration can run only on an AMD GPU (HIP "
@@ -912,29 +766,20 @@ def scene_mesh(local_tensorfs, W, H, voxel, bounds=None, poses=None, trunc=None,
     Pinhole scenes only.  Returns the mesh dict of the module docstring with "volume": the TsdfVolume or SparseTsdfVolume."""
     lt = local_tensorfs
     frames = SceneFrames("scene_mesh", lt, W, H, poses, depth, max_spread, options, _MESH_KEYS, False)
-    W, H, n, options, render = frames.W, frames.H, frames.n, frames.own, frames.render
-    voxel = float(voxel)
-    if not (voxel > 0 and math.isfinite(voxel)):
-        raise ValueError(f"voxel must be a finite number > 0, got {voxel}")
-    trunc = 3.0 * voxel if trunc is None else float(trunc)
-    if not (trunc > 0 and math.isfinite(trunc)):
-        raise ValueError(f"trunc must be a finite number > 0, got {trunc}")
+    W, H, options = frames.W, frames.H, frames.own
+    voxel = check_positive("voxel", float(voxel))
+    trunc = check_positive("trunc", 3.0 * voxel if trunc is None else float(trunc))
     if lt.fov == 360:
         raise ValueError("scene_mesh: the integration needs a pinhole camera: there is no reprojection at 360 degrees")
     depth_range = options.get("depth_range", (0.0, math.inf))
-    _check_range(depth_range)
+    check_range(depth_range)
     level, min_weight = _check_extract(options.get("level", 0.0), options.get("min_weight", 1.0), options.get("max_vertices"),
                                        options.get("max_faces"))
     colours = bool(options.get("colours", True))
     keep = _check_keep(options.get("min_component_faces", 0), options.get("min_component_fraction", 0.0), tuple(_NO_FILTER))
     simplify_cell = _check_simplify_cell(options.get("simplify_cell"))
     post = _check_post(options.get("smooth_iterations", 0), options.get("normals", False))
-    per_call = options.get("frames_per_call", 8)
-    if int(per_call) != per_call or int(per_call) < 1:
-        raise ValueError(f"frames_per_call must be an integer >= 1, got {per_call!r}")
-    per_call = int(per_call)
-    if per_call * H * W > _INT32:
-        raise ValueError(f"scene_mesh: {per_call} frames of {H} x {W} per call; one integration takes V H W < 2^31")
+    frames.check_per_call("integration")
 
     def volume_for(lo, dims):                                       # -> origin and dims, or (sparse) blocks
         if sparse:
@@ -955,27 +800,15 @@ def scene_mesh(local_tensorfs, W, H, voxel, bounds=None, poses=None, trunc=None,
         if len(bounds) != 2:
             raise ValueError(f"bounds must be ((x0, y0, z0), (x1, y1, z1)), got {bounds!r}")
         lo, shape = volume_for(*_lattice_of_box(bounds[0], bounds[1], voxel))
-    poses = frames.cam2world()
-    fi = render.pop("frame_indices", None)
-    if fi is None:
-        fi = nearest_frames(lt, poses)
-    fi = fi.tolist() if hasattr(fi, "tolist") else list(fi)
-    if len(fi) < n:
-        raise ValueError(f"frame_indices holds {len(fi)} entries for {n} poses")
-    focal, center = lt.focal(W), lt.center(W, H)
+    frames.on_device()
+    focal, center = frames.focal, frames.center
 
-    def batches():
-        for i0 in range(0, n, per_call):
-            i1 = min(n, i0 + per_call)
-            out = novel_views.render_poses(lt, poses[i0:i1], W, H, frame_indices=fi[i0:i1], encode=colours, **render)
-            dmap = out["depth"]
-            if depth == "median":
-                dmap = depth_quantiles.fusion_depth(lt, poses[i0:i1], W, H, frames.max_spread, frame_indices=fi[i0:i1], **render)
-            yield poses[i0:i1], dmap, out.get("rgb8") if colours else None
+    def batches():                                                  # every pass renders again: no frame stays resident
+        return frames.batches(depth, encode=colours)
 
     if bounds is None:
         box = None
-        for p, dmap, _ in batches():
+        for p, _, dmap in batches():
             xyz = pointcloud.fuse_points(None, dmap, p, focal, center, depth_range=depth_range)["xyz"]
             if xyz.shape[0]:
                 cur = torch.stack([xyz.amin(0), -xyz.amax(0)])
@@ -986,13 +819,13 @@ def scene_mesh(local_tensorfs, W, H, voxel, bounds=None, poses=None, trunc=None,
         lo, shape = volume_for(*_lattice_of_box(box[0] - trunc, -box[1] + trunc, voxel))
     if sparse:
         vol = SparseTsdfVolume(lo, voxel, shape, trunc, lt.blending_weights.device, colours=colours)
-        for p, dmap, _ in batches():
+        for p, _, dmap in batches():
             vol.touch(dmap, p, focal, center, depth_range=depth_range)
         vol.allocate(max_bytes=max_bytes)
     else:
         vol = TsdfVolume(lo, voxel, shape, trunc, lt.blending_weights.device, colours=colours)
-    for p, dmap, rgb8 in batches():
-        vol.integrate(dmap, p, focal, center, rgb=rgb8, depth_range=depth_range)
+    for p, out, dmap in batches():
+        vol.integrate(dmap, p, focal, center, rgb=out["rgb8"] if colours else None, depth_range=depth_range)
     mesh = vol.extract(level, min_weight, options.get("max_vertices"), options.get("max_faces"), min_component_faces=keep[0],
                        min_component_fraction=keep[1], simplify_cell=simplify_cell, smooth_iterations=post[0], normals=post[1])
     mesh["volume"] = vol

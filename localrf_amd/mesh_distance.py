@@ -23,10 +23,9 @@ import torch
 
 from . import _native as N
 from ._native import NativeError  # noqa: F401
-from .mesh import _check_cell, _check_mesh, _float_of_key
-from .mesh_raster import _check_bytes, _check_flag
+from ._checks import INT32 as _INT32
+from ._checks import check_bytes, check_flag, check_int, check_mesh, check_positive, float_of_key, mesh_on_device
 
-_INT32 = (1 << 31) - 1
 DISTANCE_SCALE = 1 << 24                       # the fixed point of the two sums
 DISTANCE_CLAMP = 8.0                           # a distance enters the sums as min(d / unit, this)
 MAX_FACE_SAMPLES = 1 << 21                     # samples one face may take
@@ -62,20 +61,14 @@ def _check_thresholds(thresholds):
 
 
 def _check_unit(unit):
-    unit = _check_cell(unit, "unit")
+    unit = check_positive("unit", unit)
     if not (math.isfinite(float(np.float32(unit))) and float(np.float32(unit)) > 0):
         raise ValueError(f"unit must be finite and > 0 as float32, got {unit!r}")
     return unit
 
 
-def _check_count(max_points, what="max_points"):
-    try:
-        ok = not isinstance(max_points, (bool, np.bool_)) and int(max_points) == max_points and 0 <= int(max_points) <= _INT32
-    except (TypeError, ValueError, OverflowError):
-        ok = False
-    if not ok:
-        raise ValueError(f"{what} must be an integer in [0, 2^31), got {max_points!r}")
-    return int(max_points)
+def _check_count(max_points):
+    return check_int("max_points", max_points, 0, _INT32, "an integer in [0, 2^31)")
 
 
 def _check_points(points):
@@ -84,18 +77,6 @@ def _check_points(points):
     if points.dtype is not torch.float32 or points.dim() != 2 or points.shape[1] != 3:
         raise ValueError(f"points must be [N, 3] float32, got {points.dtype} {tuple(points.shape)}")
     return int(points.shape[0])
-
-
-def _mesh_tensors(mesh, feature, checks=None):
-    """_check_mesh, then checks() (the call's other arguments), then the device -> (vertices, faces, Nv, Nf, device)."""
-    v, f, _, Nv, Nf = _check_mesh(mesh)
-    if checks is not None:
-        checks()
-    N.require_gpu(v, "vertices", feature)
-    N.require_gpu(f, "faces", feature)
-    if f.device != v.device:
-        raise ValueError("vertices and faces must live on the same device")
-    return v.detach().contiguous(), f.detach().contiguous(), Nv, Nf, v.device
 
 
 def default_cell(lo, hi, used_faces):
@@ -127,11 +108,11 @@ class MeshIndex:
     index's own device memory.  The index holds the mesh's tensors, not copies: a mesh changed in place needs a new index."""
 
     def __init__(self, mesh, cell=None, max_bytes=1 << 30):
-        def checks():
-            if cell is not None:
-                _check_cell(cell)
-            _check_bytes(max_bytes)
-        v, f, Nv, Nf, dev = _mesh_tensors(mesh, "the mesh index", checks)
+        v, f, _, Nv, Nf = check_mesh(mesh)
+        if cell is not None:
+            check_positive("cell", cell)
+        check_bytes(max_bytes)
+        v, f, _, dev = mesh_on_device(v, f, None, "the mesh index")
         self.vertices, self.faces, self.device, self.counts = v, f, dev, (Nv, Nf)
         self._grid = self._list = None
         self.info = {"cell": None if cell is None else float(cell), "box": None, "dims": (0, 0, 0), "entries": 0, "bad_index_faces": 0,
@@ -145,7 +126,7 @@ class MeshIndex:
         self.info.update(bad_index_faces=int(counts[0]), nonfinite_faces=int(counts[1]), used_faces=int(counts[2]))
         if counts[2] == 0:
             return
-        lo, hi = tuple(_float_of_key(k) for k in keys[:3]), tuple(_float_of_key(k) for k in keys[3:6])
+        lo, hi = tuple(float_of_key(k) for k in keys[:3]), tuple(float_of_key(k) for k in keys[3:6])
         cell = default_cell(lo, hi, int(counts[2])) if cell is None else float(cell)
         dims = grid_dims(lo, hi, cell)
         cells = dims[0] * dims[1] * dims[2]
@@ -189,7 +170,7 @@ class MeshIndex:
         distance D walks about (2 D / cell)^3 cells, empty or not: give clouds with far outliers a max_distance."""
         n = _check_points(points)
         max_distance = _check_max_distance(max_distance)
-        closest = _check_flag("closest", closest)
+        closest = check_flag("closest", closest)
         N.require_gpu(points, "points", "the mesh distance")
         dev = self.device
         if points.device != dev:
@@ -222,11 +203,9 @@ def sample_surface(mesh, spacing, max_points=1 << 26):
     index or a corner that is not finite.  Returns {"points": [M,3] fp32, "face": [M] int32 (the face each sample lies on), in
     face order, "counts": (M,), "info": spacing, bad_index_faces, nonfinite_faces}.  One read-back, after the count; a total
     above max_points, or a single face above 2^21 samples, raises ValueError before anything is emitted."""
-    def checks():
-        _check_cell(spacing, "spacing")
-        _check_count(max_points)
-    v, f, Nv, Nf, dev = _mesh_tensors(mesh, "the surface sampling", checks)
-    spacing, max_points = float(spacing), int(max_points)
+    v, f, _, Nv, Nf = check_mesh(mesh)
+    spacing, max_points = check_positive("spacing", spacing), _check_count(max_points)
+    v, f, _, dev = mesh_on_device(v, f, None, "the surface sampling")
     info = {"spacing": spacing, "bad_index_faces": 0, "nonfinite_faces": 0}
     if Nf == 0 or Nv == 0:
         return {"points": torch.empty(0, 3, dtype=torch.float32, device=dev), "face": torch.empty(0, dtype=torch.int32, device=dev),
@@ -300,7 +279,7 @@ def _as_index(mesh_or_index, max_bytes, checks, name="mesh_or_index"):
         return mesh_or_index
     if not isinstance(mesh_or_index, dict):
         raise TypeError(f"{name} must be a mesh dict or a MeshIndex")
-    _check_mesh(mesh_or_index)
+    check_mesh(mesh_or_index)
     checks()
     return MeshIndex(mesh_or_index, max_bytes=max_bytes)
 
@@ -316,7 +295,7 @@ def cloud_to_mesh(points, mesh_or_index, thresholds=(), max_distance=math.inf, u
         _check_max_distance(max_distance)
         if unit is not None:
             _check_unit(unit)
-        _check_bytes(max_bytes)
+        check_bytes(max_bytes)
     index = _as_index(mesh_or_index, max_bytes, checks)
     taus, max_distance = _check_thresholds(thresholds), _check_max_distance(max_distance)
     if unit is None:
@@ -341,13 +320,13 @@ def mesh_distance(a, b, spacing, thresholds=(), max_distance=math.inf, max_bytes
     undefined; and samples = (M_a, M_b).  With a the reconstruction and b the reference these are the figures of the
     reconstruction benchmarks.  The same integers on every run, and for every order of the faces of either mesh."""
     def checks():
-        _check_cell(spacing, "spacing")
+        check_positive("spacing", spacing)
         _check_thresholds(thresholds)
         _check_max_distance(max_distance)
-        _check_bytes(max_bytes)
+        check_bytes(max_bytes)
         _check_count(max_points)
-    _check_mesh(a)
-    _check_mesh(b)
+    check_mesh(a)
+    check_mesh(b)
     checks()
     taus = _check_thresholds(thresholds)
     sides = {}

@@ -16,37 +16,20 @@ fallback.
 import ctypes as C
 import math
 
-import numpy as np
 import torch
 
 from . import _native as N
 from ._native import NativeError  # noqa: F401
-from . import depth_quantiles, novel_views
-from .mesh import _check_mesh, _check_range
-from .pointcloud import SceneFrames, _check_depth, _check_intrinsics, _dev_f32
-from .pose_plan import check_poses, nearest_frames
+from ._checks import INT32 as _INT32
+from ._checks import (check_bytes, check_depth, check_flag, check_int, check_intrinsics, check_mesh, check_range, check_size, dev_f32,
+                      mesh_on_device)
+from .pointcloud import SceneFrames
+from .pose_plan import check_poses
 
-_INT32 = (1 << 31) - 1
 _CULL = {None: 0, "back": 1, "front": 2}
 AGREEMENT_SCALE = 1 << 24                      # the fixed point of the relative-error sum
 AGREEMENT_CLAMP = 16.0                         # a pixel's relative error enters the sum clamped to this
 _MAX_FRAMES = 65535                            # frames per lrf_depth_agreement call
-
-
-def _check_flag(name, x):
-    if not isinstance(x, (bool, np.bool_)):
-        raise ValueError(f"{name} must be True or False, got {x!r}")
-    return bool(x)
-
-
-def _check_bytes(max_bytes):
-    try:
-        ok = not isinstance(max_bytes, bool) and int(max_bytes) == max_bytes and int(max_bytes) >= 0
-    except (TypeError, ValueError, OverflowError):
-        ok = False
-    if not ok:
-        raise ValueError(f"max_bytes must be an integer >= 0, got {max_bytes!r}")
-    return int(max_bytes)
 
 
 def _check_cull(cull):
@@ -55,24 +38,8 @@ def _check_cull(cull):
     return _CULL[cull]
 
 
-def _check_size(W, H):
-    try:
-        ok = all(not isinstance(s, bool) and int(s) == s and int(s) >= 1 for s in (W, H))
-    except (TypeError, ValueError, OverflowError):
-        ok = False
-    if not ok:
-        raise ValueError(f"need integers W, H > 0, got {W!r} x {H!r}")
-    if int(W) * int(H) > _INT32:
-        raise ValueError(f"an image of {H} x {W} pixels; one rasterisation takes H W < 2^31")
-    return int(W), int(H)
-
-
 def _check_small_max(small_max):
-    if small_max is None:
-        return None
-    if isinstance(small_max, bool) or int(small_max) != small_max or not 0 <= int(small_max) <= _INT32:
-        raise ValueError(f"small_max must be None or an integer in [0, 2^31), got {small_max!r}")
-    return int(small_max)
+    return check_int("small_max", small_max, 0, _INT32, "None or an integer in [0, 2^31)", none_ok=True)
 
 
 def frames_per_call(W, H, Nf, max_bytes):
@@ -103,30 +70,22 @@ def rasterize(mesh, poses, W, H, focal, center, *, depth_range=(0.0, math.inf), 
     single frame above max_bytes raises ValueError); the outputs stay resident.  One read-back: info.  small_max (None: the
     library's measured default) is the largest pixel box a face's own lane walks, larger ones go to a wavefront
     (lrf_debug_mesh_rasterize); the outputs do not depend on it."""
-    v, f, c, Nv, Nf = _check_mesh(mesh)
+    v, f, c, Nv, Nf = check_mesh(mesh)
     poses = check_poses(poses)
     V = int(poses.shape[0])
     if V < 1:
         raise ValueError("rasterize: no pose to rasterise into")
-    W, H = _check_size(W, H)
-    focal, center = _check_intrinsics(focal, center, False)
-    d_min, d_max = _check_range(depth_range)
+    W, H = check_size(W, H)
+    focal, center = check_intrinsics(focal, center, False)
+    d_min, d_max = check_range(depth_range)
     cull = _check_cull(cull)
-    crossings, weights = _check_flag("crossings", crossings), _check_flag("weights", weights)
-    max_bytes = _check_bytes(max_bytes)
+    crossings, weights = check_flag("crossings", crossings), check_flag("weights", weights)
+    max_bytes = check_bytes(max_bytes)
     small_max = _check_small_max(small_max)
     per_call = frames_per_call(W, H, Nf, max_bytes)
-    N.require_gpu(v, "vertices", "the mesh rasterisation")
-    N.require_gpu(f, "faces", "the mesh rasterisation")
-    if c is not None:
-        N.require_gpu(c, "rgb8", "the mesh rasterisation")
-    dev = v.device
-    if f.device != dev or (c is not None and c.device != dev):
-        raise ValueError("vertices, faces and rgb8 must live on the same device")
-    v, f = v.detach().contiguous(), f.detach().contiguous()
-    c = None if c is None else c.contiguous()
+    v, f, c, dev = mesh_on_device(v, f, c, "the mesh rasterisation")
     poses = poses.detach().to(device=dev, dtype=torch.float32).contiguous()
-    fo, ce = _dev_f32(focal, 1, dev), _dev_f32(center, 2, dev)
+    fo, ce = dev_f32(focal, 1, dev), dev_f32(center, 2, dev)
     depth = torch.empty(V, H, W, dtype=torch.float32, device=dev)
     face = torch.empty(V, H, W, dtype=torch.int32, device=dev)
     rgb8 = None if c is None else torch.empty(V, H, W, 3, dtype=torch.uint8, device=dev)
@@ -169,7 +128,7 @@ def _check_tols(rel_tols):
 
 
 def _check_maps(mesh_depth, depth):
-    V, H, W = _check_depth(depth)
+    V, H, W = check_depth(depth)
     if not torch.is_tensor(mesh_depth):
         raise TypeError("mesh_depth must be a torch tensor")
     if not mesh_depth.is_floating_point() or tuple(mesh_depth.shape) != (V, H, W):
@@ -215,8 +174,8 @@ def depth_agreement(mesh_depth, depth, *, rel_tols=(0.01, 0.05), depth_range=(0.
     are valid; diagnostics.quantile takes exact medians of it.  One read-back: the counts."""
     V, H, W = _check_maps(mesh_depth, depth)
     tols = _check_tols(rel_tols)
-    d_min, d_max = _check_range(depth_range)
-    error_map = _check_flag("error_map", error_map)
+    d_min, d_max = check_range(depth_range)
+    error_map = check_flag("error_map", error_map)
     N.require_gpu(depth, "depth", "the depth agreement")
     counts, err = _agreement_counts(mesh_depth, depth, tols, d_min, d_max, error_map)
     words = counts.cpu().numpy()                                    # the read-back
@@ -244,42 +203,25 @@ def scene_mesh_agreement(local_tensorfs, mesh, W, H, poses=None, depth="expected
     (frames = the number of poses) and with "info": rasterize's.  One read-back per batch (rasterize's info) and one at the end."""
     lt = local_tensorfs
     frames = SceneFrames("scene_mesh_agreement", lt, W, H, poses, depth, max_spread, options, _AGREE_KEYS, False)
-    W, H, n, own, render = frames.W, frames.H, frames.n, frames.own, frames.render
-    v, f, c, Nv, Nf = _check_mesh(mesh)
+    W, H, n, own = frames.W, frames.H, frames.n, frames.own
+    v, f, c, Nv, Nf = check_mesh(mesh)
     if lt.fov == 360:
         raise ValueError("scene_mesh_agreement: the rasterisation needs a pinhole camera: there is no reprojection at 360 degrees")
-    W, H = _check_size(W, H)
+    W, H = check_size(W, H)
     depth_range = own.get("depth_range", (0.0, math.inf))
-    d_min, d_max = _check_range(depth_range)
+    d_min, d_max = check_range(depth_range)
     _check_cull(own.get("cull"))
     _check_small_max(own.get("small_max"))
     tols = _check_tols(own.get("rel_tols", (0.01, 0.05)))
-    per_call = own.get("frames_per_call", 8)
-    if isinstance(per_call, bool) or int(per_call) != per_call or int(per_call) < 1:
-        raise ValueError(f"frames_per_call must be an integer >= 1, got {per_call!r}")
-    per_call = int(per_call)
-    if per_call * H * W > _INT32:
-        raise ValueError(f"scene_mesh_agreement: {per_call} frames of {H} x {W} per call; one comparison takes V H W < 2^31")
-    max_bytes = _check_bytes(max_bytes)
+    frames.check_per_call("comparison")
+    max_bytes = check_bytes(max_bytes)
     frames_per_call(W, H, Nf, max_bytes)                            # a single frame must fit; rasterize splits a batch further
-    poses = frames.cam2world()
-    fi = render.pop("frame_indices", None)
-    if fi is None:
-        fi = nearest_frames(lt, poses)
-    fi = fi.tolist() if hasattr(fi, "tolist") else list(fi)
-    if len(fi) < n:
-        raise ValueError(f"frame_indices holds {len(fi)} entries for {n} poses")
-    focal, center = lt.focal(W), lt.center(W, H)
+    frames.on_device()
     flat = {"vertices": v, "faces": f, "rgb8": None}                # colours are not compared
     total, info = None, None
-    for i0 in range(0, n, per_call):
-        i1 = min(n, i0 + per_call)
-        if depth == "median":
-            dmap = depth_quantiles.fusion_depth(lt, poses[i0:i1], W, H, frames.max_spread, frame_indices=fi[i0:i1], **render)
-        else:
-            dmap = novel_views.render_poses(lt, poses[i0:i1], W, H, frame_indices=fi[i0:i1], encode=False, **render)["depth"]
-        out = rasterize(flat, poses[i0:i1], W, H, focal, center, depth_range=depth_range, cull=own.get("cull"), max_bytes=max_bytes,
-                        small_max=own.get("small_max"))
+    for poses, _, dmap in frames.batches(depth, colour=False, encode=False):      # "median" never calls render_poses
+        out = rasterize(flat, poses, W, H, frames.focal, frames.center, depth_range=depth_range, cull=own.get("cull"),
+                        max_bytes=max_bytes, small_max=own.get("small_max"))
         info = out["info"] if info is None else info
         counts = _agreement_counts(out["depth"], dmap, tols, d_min, d_max, False)[0].sum(0)
         total = counts if total is None else total + counts

@@ -26,38 +26,27 @@ import torch
 
 from . import _native as N
 from ._native import NativeError  # noqa: F401
-from . import mesh_raster, novel_views
-from .mesh import _check_mesh, _check_range
-from .mesh_raster import _check_bytes, _check_flag, _check_size
-from .pointcloud import SceneFrames, _check_intrinsics, _dev_f32
-from .pose_plan import check_poses, nearest_frames
+from . import mesh_raster
+from ._checks import INT32 as _INT32
+from ._checks import (check_bytes, check_flag, check_frame_poses, check_int, check_interval, check_intrinsics, check_mesh, check_range,
+                      check_size, dev_f32, mesh_on_device, rgb8_frames)
+from .pointcloud import SceneFrames
 
-_INT32 = (1 << 31) - 1
 _BLEND = {"mean": 0, "best": 1}
 INFO_KEYS = ("bad_index_faces", "degenerate_faces", "nonfinite_faces", "zero_area_faces", "used_texels", "observed_texels",
              "fallback_texels", "empty_texels")
-
-
-def _check_int(name, x, lo, hi):
-    try:
-        ok = not isinstance(x, (bool, np.bool_)) and int(x) == x and lo <= int(x) <= hi
-    except (TypeError, ValueError, OverflowError):
-        ok = False
-    if not ok:
-        raise ValueError(f"{name} must be an integer in [{lo}, {hi}], got {x!r}")
-    return int(x)
 
 
 def atlas_layout(Nf, patch=8, cols=None):
     """-> (rows, cols, Ht, Wt): faces 2c and 2c + 1 share cell c of patch x patch texels, cols cells per row (None:
     ceil(sqrt(n_cells)) by integer arithmetic, 1 for no face), rows = ceil(n_cells / cols), the atlas Ht = rows patch by
     Wt = cols patch.  Refuses 2^31 texels or more: one bake takes fewer."""
-    Nf = _check_int("Nf", Nf, 0, _INT32)
-    P = _check_int("patch", patch, 4, 64)
+    Nf = check_int("Nf", Nf, 0, _INT32)
+    P = check_int("patch", patch, 4, 64)
     cells = (Nf + 1) // 2
     if cols is None:
         cols = max(1, math.isqrt(cells - 1) + 1 if cells > 0 else 1)
-    cols = _check_int("cols", cols, 1, _INT32)
+    cols = check_int("cols", cols, 1, _INT32)
     rows = -(-cells // cols)
     if rows * cols * P * P > _INT32:
         raise ValueError(f"an atlas of {rows} x {cols} cells of {P} x {P} texels; one bake takes fewer than 2^31 texels")
@@ -90,9 +79,7 @@ def _check_options(blend, vis_tol, min_cos, two_sided):
         raise ValueError(f"vis_tol and min_cos must be numbers, got {vis_tol!r} and {min_cos!r}") from None
     if not vis_tol >= 0:
         raise ValueError(f"vis_tol must be >= 0, got {vis_tol}")
-    if not 0 <= min_cos <= 1:
-        raise ValueError(f"min_cos must lie in [0, 1], got {min_cos}")
-    return _BLEND[blend], vis_tol, min_cos, _check_flag("two_sided", two_sided)
+    return _BLEND[blend], vis_tol, check_interval("min_cos", min_cos, 0.0, 1.0, "lie in [0, 1]"), check_flag("two_sided", two_sided)
 
 
 def _check_fill(fill):
@@ -116,7 +103,7 @@ class TextureBaker:
     the host only, the device is looked at by the first add(), finish() or state."""
 
     def __init__(self, mesh, patch=8, cols=None, blend="mean", vis_tol=0.02, min_cos=0.2, two_sided=False):
-        v, f, c, Nv, Nf = _check_mesh(mesh)
+        v, f, c, Nv, Nf = check_mesh(mesh)
         self.rows, self.cols, self.Ht, self.Wt = atlas_layout(Nf, patch, cols)
         self.patch = int(patch)
         self.blend, self.vis_tol, self.min_cos, self.two_sided = _check_options(blend, vis_tol, min_cos, two_sided)
@@ -127,18 +114,8 @@ class TextureBaker:
         """The device half of the construction, at the first add(), finish() or state: after every host check."""
         if self._state is not None:
             return
-        v, f, c = self._mesh
-        N.require_gpu(v, "vertices", "the texture bake")
-        N.require_gpu(f, "faces", "the texture bake")
-        if c is not None:
-            N.require_gpu(c, "rgb8", "the texture bake")
-        dev = v.device
-        if f.device != dev or (c is not None and c.device != dev):
-            raise ValueError("vertices, faces and rgb8 must live on the same device")
-        self.device = dev
-        self._v, self._f = v.detach().contiguous(), f.detach().contiguous()
-        self._c = None if c is None else c.contiguous()
-        self._state = torch.zeros(self.Ht, self.Wt, 4, dtype=torch.float32, device=dev)
+        self._v, self._f, self._c, self.device = mesh_on_device(*self._mesh, "the texture bake")
+        self._state = torch.zeros(self.Ht, self.Wt, 4, dtype=torch.float32, device=self.device)
 
     @property
     def state(self):
@@ -166,19 +143,17 @@ class TextureBaker:
         if rgb.dim() != 4 or rgb.shape[3] != 3 or min(rgb.shape) < 1:
             raise ValueError(f"rgb must be [V, H, W, 3] with V, H, W > 0, got {tuple(rgb.shape)}")
         V, H, W = (int(s) for s in rgb.shape[:3])
-        _check_size(W, H)
+        check_size(W, H)
         if mesh_depth is not None:
             if not torch.is_tensor(mesh_depth):
                 raise TypeError("mesh_depth must be a torch tensor or None")
             if not mesh_depth.is_floating_point() or tuple(mesh_depth.shape) != (V, H, W):
                 raise ValueError(f"mesh_depth must be a floating-point tensor of shape {(V, H, W)} to go with rgb, got "
                                  f"{mesh_depth.dtype} {tuple(mesh_depth.shape)}")
-        poses = check_poses(poses)
-        if poses.shape[0] != V:
-            raise ValueError(f"{poses.shape[0]} poses for {V} frames")
-        focal, center = _check_intrinsics(focal, center, False)
-        depth_range = _check_range(depth_range)
-        max_bytes = _check_bytes(max_bytes)
+        poses = check_frame_poses(poses, V, "frames")
+        focal, center = check_intrinsics(focal, center, False)
+        depth_range = check_range(depth_range)
+        max_bytes = check_bytes(max_bytes)
         per_call = mesh_raster.frames_per_call(W, H, self.Nf, max_bytes)
         self._ready()
         N.require_gpu(rgb, "rgb", "the texture bake")
@@ -188,7 +163,7 @@ class TextureBaker:
         if rgb.device != dev or (mesh_depth is not None and mesh_depth.device != dev):
             raise ValueError(f"rgb and mesh_depth must live on the mesh's device {dev}")
         poses = poses.detach().to(device=dev, dtype=torch.float32).contiguous()
-        fo, ce = _dev_f32(focal, 1, dev), _dev_f32(center, 2, dev)
+        fo, ce = dev_f32(focal, 1, dev), dev_f32(center, 2, dev)
         mesh = {"vertices": self._v, "faces": self._f, "rgb8": None}
         a = self._args()
         a.focal, a.center, a.H, a.W = fo.data_ptr(), ce.data_ptr(), H, W
@@ -199,10 +174,7 @@ class TextureBaker:
                                            cull=None if self.two_sided else "back", max_bytes=max_bytes)["depth"]
             else:
                 dm = N.conform(mesh_depth[i0:i1])
-            if rgb.dtype is torch.uint8:
-                rgb8 = rgb[i0:i1].contiguous()
-            else:
-                rgb8 = novel_views.encode_frames(rgb[i0:i1].detach(), dm)[0].contiguous()
+            rgb8 = rgb8_frames(rgb[i0:i1], dm)
             if self.Nf:
                 a.frames, a.mesh_depth, a.cam2world, a.V = rgb8.data_ptr(), dm.data_ptr(), poses[i0:].data_ptr(), i1 - i0
                 N.launch("lrf_mesh_texture_bake", dev, C.byref(a), self.state.data_ptr(), guard=True)
@@ -242,39 +214,25 @@ def scene_texture(local_tensorfs, mesh, W, H, poses=None, max_bytes=4 << 30, **o
     anything is rendered.  Pinhole scenes only.  Returns finish()'s dict with "frames": the number of poses."""
     lt = local_tensorfs
     frames = SceneFrames("scene_texture", lt, W, H, poses, "expected", None, options, _TEXTURE_KEYS, False)
-    W, H, n, own, render = frames.W, frames.H, frames.n, frames.own, frames.render
-    v, f, c, Nv, Nf = _check_mesh(mesh)
+    W, H, own = frames.W, frames.H, frames.own
+    v, f, c, Nv, Nf = check_mesh(mesh)
     atlas_layout(Nf, own.get("patch", 8), own.get("cols"))
     if lt.fov == 360:
         raise ValueError("scene_texture: the bake needs a pinhole camera: there is no reprojection at 360 degrees")
-    W, H = _check_size(W, H)
+    W, H = check_size(W, H)
     _check_options(own.get("blend", "mean"), own.get("vis_tol", 0.02), own.get("min_cos", 0.2), own.get("two_sided", False))
     depth_range = own.get("depth_range", (0.0, math.inf))
-    _check_range(depth_range)
+    check_range(depth_range)
     fill = _check_fill(own.get("fill", (0, 0, 0)))
-    per_call = own.get("frames_per_call", 8)
-    if isinstance(per_call, bool) or int(per_call) != per_call or int(per_call) < 1:
-        raise ValueError(f"frames_per_call must be an integer >= 1, got {per_call!r}")
-    per_call = int(per_call)
-    if per_call * H * W > _INT32:
-        raise ValueError(f"scene_texture: {per_call} frames of {H} x {W} per call; one bake takes V H W < 2^31")
-    max_bytes = _check_bytes(max_bytes)
+    frames.check_per_call("bake")
+    max_bytes = check_bytes(max_bytes)
     mesh_raster.frames_per_call(W, H, Nf, max_bytes)                # a single frame must fit; add splits a batch further
-    cam = frames.cam2world()
+    frames.on_device()
     baker = TextureBaker(mesh, **{k: own[k] for k in _BAKE_KEYS if k in own})
-    fi = render.pop("frame_indices", None)
-    if fi is None:
-        fi = nearest_frames(lt, cam)
-    fi = fi.tolist() if hasattr(fi, "tolist") else list(fi)
-    if len(fi) < n:
-        raise ValueError(f"frame_indices holds {len(fi)} entries for {n} poses")
-    focal, center = lt.focal(W), lt.center(W, H)
-    for i0 in range(0, n, per_call):
-        i1 = min(n, i0 + per_call)
-        rgb8 = novel_views.render_poses(lt, cam[i0:i1], W, H, frame_indices=fi[i0:i1], **render)["rgb8"]
-        baker.add(rgb8, cam[i0:i1], focal, center, depth_range=depth_range, max_bytes=max_bytes)
+    for poses, out, _ in frames.batches():                          # only rgb8 is taken
+        baker.add(out["rgb8"], poses, frames.focal, frames.center, depth_range=depth_range, max_bytes=max_bytes)
     out = baker.finish(fill)
-    out["frames"] = n
+    out["frames"] = frames.n
     return out
 
 
@@ -318,7 +276,7 @@ def write_obj(path, mesh, tex):
     """The textured mesh as Wavefront OBJ: path (v, vt, f lines), beside it <stem>.mtl (one material, map_Kd) and <stem>.png (the
     atlas, written with zlib alone).  One vt per face corner, vt 3 f + k + 1 for corner k of face f, and f a/ta b/tb c/tc with
     1-based indices.  The mesh must hold at least one face (a PNG cannot be empty)."""
-    v, f, _, Nv, Nf = _check_mesh(mesh)
+    v, f, _, Nv, Nf = check_mesh(mesh)
     atlas, uv = tex["atlas"], tex["uv"]
     if Nf < 1 or atlas.numel() == 0:
         raise ValueError("write_obj: the mesh holds no face")

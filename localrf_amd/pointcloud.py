@@ -20,54 +20,18 @@ import torch
 
 from . import _native as N
 from . import depth_quantiles, normals as normal_maps, novel_views
-from .pose_plan import check_poses
+from ._checks import INT32 as _INT32
+from ._checks import check_depth, check_frame_poses, check_int, check_intrinsics, check_range, check_rgb, dev_f32, rgb8_frames
+from .pose_plan import check_poses, nearest_frames
 
-_INT32 = (1 << 31) - 1
 BYTES_PER_RESIDENT_PIXEL = 7                   # scene_point_cloud keeps depth (4 B) and rgb8 (3 B) of every frame
 BYTES_PER_NORMAL_PIXEL = 16                    # and with normals=True the normal map (12 B) and its acc (4 B)
-
-
-def _check_depth(depth):
-    if not torch.is_tensor(depth):
-        raise TypeError("depth must be a torch tensor")
-    if not depth.is_floating_point():
-        raise ValueError(f"depth must hold floating-point values, got {depth.dtype}")
-    if depth.dim() != 3 or min(depth.shape) < 1:
-        raise ValueError(f"depth must be [V, H, W] with V, H, W > 0, got {tuple(depth.shape)}")
-    V, H, W = (int(s) for s in depth.shape)
-    if V * H * W > _INT32:
-        raise ValueError(f"depth holds {V * H * W} pixels; one call takes V H W < 2^31")
-    return V, H, W
-
-
-def _check_poses(poses, V):
-    poses = check_poses(poses)
-    if poses.shape[0] != V:
-        raise ValueError(f"{poses.shape[0]} poses for {V} depth frames")
-    return poses
-
-
-def _check_intrinsics(focal, center, fov360):
-    """-> (focal, center) as given (tensors or numbers), shapes checked; None, None for 360."""
-    if fov360:
-        return None, None
-    if focal is None or center is None:
-        raise ValueError("a pinhole camera needs focal and center (or pass fov360=True)")
-    nf = focal.numel() if torch.is_tensor(focal) else np.size(focal)
-    nc = center.numel() if torch.is_tensor(center) else np.size(center)
-    if nf != 1 or nc != 2:
-        raise ValueError(f"focal must hold 1 value and center 2 (cx, cy), got {nf} and {nc}")
-    return focal, center
 
 
 def _check_filter(stride, depth_range, neighbours, rel_tol, min_consistent, fov360, max_points):
     if int(stride) != stride or int(stride) < 1:
         raise ValueError(f"stride must be an integer >= 1, got {stride!r}")
-    if len(depth_range) != 2:
-        raise ValueError(f"depth_range must be (d_min, d_max), got {depth_range!r}")
-    d_min, d_max = float(depth_range[0]), float(depth_range[1])
-    if not d_min <= d_max:
-        raise ValueError(f"depth_range needs d_min <= d_max, got {depth_range!r}")
+    d_min, d_max = check_range(depth_range)
     neigh = [int(o) for o in neighbours]
     if any(int(o) != o for o in neighbours):
         raise ValueError(f"neighbours must be integer frame offsets, got {neighbours!r}")
@@ -91,11 +55,6 @@ def _check_filter(stride, depth_range, neighbours, rel_tol, min_consistent, fov3
     return int(stride), d_min, d_max, neigh, rel_tol, min(int(min_consistent), _INT32)
 
 
-def _dev_f32(x, n, dev):
-    t = x if torch.is_tensor(x) else torch.tensor(np.asarray(x, np.float32).reshape(n))
-    return t.detach().reshape(n).to(device=dev, dtype=torch.float32).contiguous()
-
-
 def _fuse(depth, rgb8, poses, focal, center, fov360, stride, d_min, d_max, neigh, rel_tol, min_consistent, max_points):
     """Checked arguments, device tensors -> (xyz, rgb8 or None, src, count).  The one read-back is count."""
     dev = depth.device
@@ -104,7 +63,7 @@ def _fuse(depth, rgb8, poses, focal, center, fov360, stride, d_min, d_max, neigh
     poses = poses.detach().to(device=dev, dtype=torch.float32).contiguous()
     f = c = None
     if not fov360:
-        f, c = _dev_f32(focal, 1, dev), _dev_f32(center, 2, dev)
+        f, c = dev_f32(focal, 1, dev), dev_f32(center, 2, dev)
     n_cand = V * (-(-H // stride)) * (-(-W // stride))
     cap = n_cand if max_points is None else min(int(max_points), n_cand)
     rows = max(cap, 1)
@@ -134,11 +93,11 @@ def backproject(depth, poses, W, H, focal=None, center=None, fov360=False):
     """depth [V,H,W] (device), poses [V,3,4] camera-to-world -> (xyz [M,3] fp32, src [M,2] int32 = (frame, pixel id j W + i)):
     the world point of every pixel with a finite positive depth, no other filter, in (frame, row, column) order.  focal (one
     value) and center (cx, cy) may be tensors or numbers; fov360=True takes the equirectangular directions instead."""
-    V, Hd, Wd = _check_depth(depth)
+    V, Hd, Wd = check_depth(depth)
     if (int(H), int(W)) != (Hd, Wd):
         raise ValueError(f"depth is {Hd} x {Wd} (H x W) but H, W = {H}, {W}")
-    poses = _check_poses(poses, V)
-    focal, center = _check_intrinsics(focal, center, fov360)
+    poses = check_frame_poses(poses, V)
+    focal, center = check_intrinsics(focal, center, fov360)
     N.require_gpu(depth, "depth", "the point fusion")
     xyz, _, src, _ = _fuse(depth, None, poses, focal, center, bool(fov360), 1, 0.0, math.inf, [], 0.0, 0, None)
     return xyz, src
@@ -158,28 +117,15 @@ def fuse_points(rgb, depth, poses, focal, center, *, fov360=False, stride=1, dep
     Returns a dict: xyz [M,3] fp32, rgb8 [M,3] uint8 (None without rgb), src [M,2] int32 (frame, pixel id j W + i) -- device
     tensors in (frame, row, column) order, views of buffers sized for max_points rows (None: for every candidate) -- and
     count = M, a Python int: the one read-back.  A result that does not fit max_points raises ValueError naming the true count."""
-    V, H, W = _check_depth(depth)
+    V, H, W = check_depth(depth)
     if rgb is not None:
-        if not torch.is_tensor(rgb):
-            raise TypeError("rgb must be a torch tensor or None")
-        if not (rgb.is_floating_point() or rgb.dtype is torch.uint8):
-            raise ValueError(f"rgb must hold floating-point or uint8 values, got {rgb.dtype}")
-        if tuple(rgb.shape) != (V, H, W, 3):
-            raise ValueError(f"rgb must be {(V, H, W, 3)} to go with depth {tuple(depth.shape)}, got {tuple(rgb.shape)}")
-        if rgb.device != depth.device:
-            raise ValueError("rgb and depth must live on the same device")
-    poses = _check_poses(poses, V)
-    focal, center = _check_intrinsics(focal, center, fov360)
+        check_rgb(rgb, depth)
+    poses = check_frame_poses(poses, V)
+    focal, center = check_intrinsics(focal, center, fov360)
     stride, d_min, d_max, neigh, rel_tol, min_consistent = _check_filter(stride, depth_range, neighbours, rel_tol, min_consistent,
                                                                          fov360, max_points)
     N.require_gpu(depth, "depth", "the point fusion")
-    rgb8 = None
-    if rgb is not None:
-        if rgb.dtype is torch.uint8:
-            rgb8 = rgb.contiguous()
-        else:
-            from .novel_views import encode_frames
-            rgb8 = encode_frames(rgb.detach(), depth.detach())[0]
+    rgb8 = None if rgb is None else rgb8_frames(rgb, depth)
     xyz, out8, src, m = _fuse(depth, rgb8, poses, focal, center, bool(fov360), stride, d_min, d_max, neigh, rel_tol,
                               min_consistent, max_points)
     return {"xyz": xyz, "rgb8": out8, "src": src, "count": m}
@@ -190,13 +136,16 @@ _RENDER_KEYS = ("test_frames", "frame_indices", "floater_thresh", "chunk", "fram
 
 
 class SceneFrames:
-    """What scene_point_cloud and scene_mesh (`who`) share before their first render.  Construction checks on the host, in
-    this order: depth= / max_spread=, unknown options (TypeError), W and H, poses (None: the scene's own frames, each through
-    itself) and the frame count n >= 1.  own: the caller's options; render: those every renderer takes; colour: render plus
-    frames_per_call, which only render_poses takes, when the caller forwards it.  cam2world() is the device half, for after
-    the caller's own checks: it refuses a CPU scene and returns the poses [n, 3, 4]."""
+    """What the scene functions (`who`: scene_point_cloud, scene_mesh, scene_mesh_agreement, scene_texture) share.
+    Construction checks on the host, in this order: depth= / max_spread=, unknown options (TypeError), W and H, poses (None:
+    the scene's own frames, each through itself) and the frame count n >= 1.  own: the caller's options; render: those every
+    renderer takes; colour: render plus frames_per_call, which only render_poses takes, when the caller forwards it.
+    cam2world() is the device half, for after the caller's own checks: it refuses a CPU scene and returns the poses [n, 3, 4].
+    A caller that renders frames_per_call frames at a time and keeps none calls check_per_call(noun) among its host checks,
+    on_device() after them and then loops over batches(), once per pass."""
 
     def __init__(self, who, local_tensorfs, W, H, poses, depth, max_spread, options, own_keys, forwards_frames_per_call):
+        self.who = who
         self.max_spread = depth_quantiles.check_fusion_depth(who, depth, max_spread)
         unknown = sorted(set(options) - set(own_keys) - set(_RENDER_KEYS))
         if unknown:
@@ -223,6 +172,43 @@ class SceneFrames:
             with torch.no_grad():
                 return self.lt.get_cam2world().detach()
         return self.poses
+
+    def check_per_call(self, noun):
+        """The caller's own frames_per_call option (default 8): an integer >= 1 whose frames one `noun` call can take."""
+        per_call = check_int("frames_per_call", self.own.get("frames_per_call", 8), 1, wording="an integer >= 1")
+        if per_call * self.H * self.W > _INT32:
+            raise ValueError(f"{self.who}: {per_call} frames of {self.H} x {self.W} per call; one {noun} takes V H W < 2^31")
+        self.per_call = per_call
+
+    def on_device(self):
+        """The device half of a batched caller: cam, the poses of cam2world(); fi, the training frame of every pose as a list
+        (the frame_indices option, else nearest_frames: one read-back), at least n long; the scene's focal and center."""
+        self.cam = self.cam2world()
+        fi = self.render.pop("frame_indices", None)
+        if fi is None:
+            fi = nearest_frames(self.lt, self.cam)
+        self.fi = fi.tolist() if hasattr(fi, "tolist") else list(fi)
+        if len(self.fi) < self.n:
+            raise ValueError(f"frame_indices holds {len(self.fi)} entries for {self.n} poses")
+        self.focal, self.center = self.lt.focal(self.W), self.lt.center(self.W, self.H)
+        return self
+
+    def batches(self, depth=None, colour=True, encode=True):
+        """One pass over the frames, per_call at a time -> (poses [V,3,4], out, dmap) per batch, nothing kept.  out is
+        novel_views.render_poses' dict (with `encode` as given) when colour or the expected depth is wanted, else None: that
+        render is skipped.  dmap [V,H,W] is what depth= selects: out["depth"] for "expected", depth_quantiles.fusion_depth
+        (one more render) for "median", None for None.  Both renderers are looked up when a batch is rendered."""
+        lt, W, H = self.lt, self.W, self.H
+        for i0 in range(0, self.n, self.per_call):
+            i1 = min(self.n, i0 + self.per_call)
+            poses, fi = self.cam[i0:i1], self.fi[i0:i1]
+            out = dmap = None
+            if colour or depth == "expected":
+                out = novel_views.render_poses(lt, poses, W, H, frame_indices=fi, encode=encode, **self.render)
+                dmap = out["depth"] if depth == "expected" else None
+            if depth == "median":
+                dmap = depth_quantiles.fusion_depth(lt, poses, W, H, self.max_spread, frame_indices=fi, **self.render)
+            yield poses, out, dmap
 
 
 def scene_point_cloud(local_tensorfs, W, H, poses=None, max_bytes=4 << 30, normals=False, orient=False, depth="expected",

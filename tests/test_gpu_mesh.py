@@ -186,17 +186,25 @@ def test_capacity_one_too_small_raises_with_the_true_counts():
         assert np.array_equal(part["faces"].cpu().numpy(), want["faces"][:cap_f])
 
 
-def test_scene_mesh_equals_integrate_and_extract_over_render_poses(monkeypatch):
+SCENE_RANGE = (0.05, 50.0)
+
+
+@functools.lru_cache(maxsize=None)
+def _scene_and_box():
+    """scene(DEV), its own poses, render_poses of them, and the box of fuse_points over that depth with voxel = extent / 28."""
     lt, g = scene(DEV)
     W, H = int(g["W"]), int(g["H"])
-    F = len(lt.r_c2w)
-    rng = (0.05, 50.0)
     with torch.no_grad():
         own = lt.get_cam2world().detach()
-    out = novel_views.render_poses(lt, own, W, H, frame_indices=list(range(F)), floater_thresh=0.5)
-    xyz = pointcloud.fuse_points(None, out["depth"], own, lt.focal(W), lt.center(W, H), depth_range=rng)["xyz"]
+    out = novel_views.render_poses(lt, own, W, H, frame_indices=list(range(len(lt.r_c2w))), floater_thresh=0.5)
+    xyz = pointcloud.fuse_points(None, out["depth"], own, lt.focal(W), lt.center(W, H), depth_range=SCENE_RANGE)["xyz"]
     lo, hi = xyz.amin(0).double().cpu().numpy(), xyz.amax(0).double().cpu().numpy()
-    voxel = float((hi - lo).max()) / 28
+    return lt, g, W, H, own, out, lo, hi, float((hi - lo).max()) / 28
+
+
+def test_scene_mesh_equals_integrate_and_extract_over_render_poses(monkeypatch):
+    lt, g, W, H, own, out, lo, hi, voxel = _scene_and_box()
+    rng = SCENE_RANGE
     got = mesh.scene_mesh(lt, W, H, voxel=voxel, floater_thresh=0.5, depth_range=rng, frames_per_call=2)
     vol = got["volume"]
     assert vol.trunc == 3 * voxel
@@ -228,3 +236,25 @@ def test_scene_mesh_equals_integrate_and_extract_over_render_poses(monkeypatch):
     monkeypatch.setattr(novel_views, "render_poses", forbidden)
     with pytest.raises(ValueError, match="max_bytes"):
         mesh.scene_mesh(lt, W, H, voxel=voxel, bounds=box, max_bytes=1000)
+
+
+@pytest.mark.parametrize("kind", [dict(depth="expected"), dict(sparse=True, depth="median")], ids=["dense expected", "sparse median"])
+def test_scene_mesh_does_not_depend_on_frames_per_call(kind):
+    """The same volume bits and mesh bytes whether the scene's 14 frames are rendered 1, 3 or (the default) 8 at a time."""
+    lt, g, W, H, own, out, lo, hi, voxel = _scene_and_box()
+    assert own.shape[0] % 3 and 8 < own.shape[0] < 16                   # batches of 1; of 3 and of 8, each with a shorter last one
+    box = (tuple(lo - 3 * voxel), tuple(hi + 3 * voxel))
+    want = None
+    for extra in ({}, {"frames_per_call": 3}, {"frames_per_call": 1}):
+        got = mesh.scene_mesh(lt, W, H, voxel=voxel, bounds=box, floater_thresh=0.5, depth_range=SCENE_RANGE, **kind, **extra)
+        assert got["counts"][0] > 0 and got["counts"][1] > 0
+        if want is None:
+            want = got
+            continue
+        assert got["counts"] == want["counts"], extra
+        for k in ("tsdf", "weight", "rgb"):
+            assert torch.equal(getattr(got["volume"], k).view(torch.int32), getattr(want["volume"], k).view(torch.int32)), (extra, k)
+        for k in ("vertices", "faces", "rgb8"):
+            assert torch.equal(got[k], want[k]), (extra, k)
+        if kind.get("sparse"):
+            assert torch.equal(got["volume"].coords, want["volume"].coords) and torch.equal(got["volume"].table, want["volume"].table)
