@@ -82,27 +82,25 @@ __global__ __launch_bounds__(ADAM_TPB) void k_adam_multi(AdamTable tab, float b1
 static int adam_step_impl(const LrfAdamTensor* tensors, int32_t count, const float* dev_scalars, float beta1, float beta2, float eps,
                           void* stream) {
   using namespace lrf;
-  if (count < 0 || count > LRF_ADAM_MAX) return set_err("lrf_adam_step: count must be in [0, LRF_ADAM_MAX]");
+  const char* who = "lrf_adam_step";
+  if (count < 0 || count > LRF_ADAM_MAX) return refuse(who, "count must be in [0, LRF_ADAM_MAX]");
   if (!count) return 0;
-  if (!tensors) return set_err("lrf_adam_step: null argument");
+  if (!tensors) return refuse(who, "null argument");
   AdamTable tab;
   tab.count = count;
   int blocks = 0;
   for (int i = 0; i < count; ++i) {
     const LrfAdamTensor& t = tensors[i];
-    if (!t.p || !t.g || !t.m || !t.v || t.n < 0) return set_err("lrf_adam_step: null tensor pointer or negative size");
-    if (t.n > (int64_t)2000000000) return set_err("lrf_adam_step: tensor too large");
+    if (!t.p || !t.g || !t.m || !t.v || t.n < 0) return refuse(who, "null tensor pointer or negative size");
+    if (t.n > (int64_t)2000000000) return refuse(who, "tensor too large");
     tab.t[i] = t;
     tab.row[i] = (short)i;
     tab.first_block[i] = blocks;
-    blocks += (int)((t.n + ADAM_CHUNK - 1) / ADAM_CHUNK);
+    blocks += (int)blocks_for(t.n, ADAM_CHUNK);
   }
   tab.first_block[count] = blocks;
   if (!blocks) return 0;
-  hipLaunchKernelGGL(k_adam_multi, dim3(blocks), dim3(ADAM_TPB), 0, reinterpret_cast<hipStream_t>(stream), tab,
-                     beta1, beta2, eps, dev_scalars);
-  LRF_HIP(hipGetLastError());
-  return 0;
+  return launch(k_adam_multi, blocks, ADAM_TPB, reinterpret_cast<hipStream_t>(stream), tab, beta1, beta2, eps, dev_scalars);
 }
 
 extern "C" int lrf_adam_step(const LrfAdamTensor* tensors, int32_t count, float beta1, float beta2, float eps, void* stream) {
@@ -111,7 +109,7 @@ extern "C" int lrf_adam_step(const LrfAdamTensor* tensors, int32_t count, float 
 
 extern "C" int lrf_adam_step_dev(const LrfAdamTensor* tensors, int32_t count, const float* dev_scalars, float beta1, float beta2,
                                  float eps, void* stream) {
-  if (!dev_scalars) return lrf::set_err("lrf_adam_step_dev: null scalar table");
+  if (!dev_scalars) return lrf::refuse("lrf_adam_step_dev", "null scalar table");
   return adam_step_impl(tensors, count, dev_scalars, beta1, beta2, eps, stream);
 }
 
@@ -233,8 +231,9 @@ __global__ __launch_bounds__(128) void k_adam_pack(AdamPackTab tab, AdamTableS s
 extern "C" int lrf_adam_step_pack(const LrfAdamTensor* tensors, int32_t count, const float* dev_scalars, float beta1, float beta2,
                                   float eps, const LrfParams* p, void* cache, void* stream) {
   using namespace lrf;
-  if (count < 0 || count > LRF_ADAM_MAX) return set_err("lrf_adam_step_pack: count must be in [0, LRF_ADAM_MAX]");
-  if ((count && !tensors) || !p || !cache) return set_err("lrf_adam_step_pack: null argument");
+  const char* who = "lrf_adam_step_pack";
+  if (count < 0 || count > LRF_ADAM_MAX) return refuse(who, "count must be in [0, LRF_ADAM_MAX]");
+  if ((count && !tensors) || !p || !cache) return refuse(who, "null argument");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const Layout L = make_layout(p->grid);
   float* base = reinterpret_cast<float*>(cache);
@@ -248,12 +247,12 @@ extern "C" int lrf_adam_step_pack(const LrfAdamTensor* tensors, int32_t count, c
     const int Cs[4] = {LRF_CD, LRF_CD, LRF_CA, LRF_CA}, Hs[4] = {L.ph[q], 1, L.ph[q], 1}, Ws[4] = {L.pw[q], L.ll[q], L.pw[q], L.ll[q]};
     for (int k = 0; k < 4; ++k) {
       AdamPackSeg& sg = pt.s[4 * q + k];
-      if (!prm[k]) return set_err("lrf_adam_step_pack: null parameter pointer");
+      if (!prm[k]) return refuse(who, "null parameter pointer");
       sg.t = LrfAdamTensor{const_cast<float*>(prm[k]), nullptr, nullptr, nullptr, (int64_t)Cs[k] * Hs[k] * Ws[k], 0.0f, 0.0f};
       sg.row = -1;
       for (int j = 0; j < count; ++j)
         if (tensors[j].p == prm[k]) {
-          if (!tensors[j].g || !tensors[j].m || !tensors[j].v || tensors[j].n != sg.t.n) return set_err("lrf_adam_step_pack: a field tensor's Adam entry has null state or another size");
+          if (!tensors[j].g || !tensors[j].m || !tensors[j].v || tensors[j].n != sg.t.n) return refuse(who, "a field tensor's Adam entry has null state or another size");
           sg.t = tensors[j]; sg.row = dev_scalars ? j : -1; taken[j] = true;
           break;
         }
@@ -269,8 +268,8 @@ extern "C" int lrf_adam_step_pack(const LrfAdamTensor* tensors, int32_t count, c
   for (int j = 0; j < count; ++j) {
     if (taken[j]) continue;
     const LrfAdamTensor& t = tensors[j];
-    if (!t.p || !t.g || !t.m || !t.v || t.n < 0) return set_err("lrf_adam_step_pack: null tensor pointer or negative size");
-    if (t.n > (int64_t)2000000000) return set_err("lrf_adam_step_pack: tensor too large");
+    if (!t.p || !t.g || !t.m || !t.v || t.n < 0) return refuse(who, "null tensor pointer or negative size");
+    if (t.n > (int64_t)2000000000) return refuse(who, "tensor too large");
     ++n_small;
   }
   AdamTableS small;
@@ -281,7 +280,7 @@ extern "C" int lrf_adam_step_pack(const LrfAdamTensor* tensors, int32_t count, c
     for (int j = 0; j < count; ++j) {
       if (taken[j]) continue;
       small.t[small.count] = tensors[j]; small.row[small.count] = (short)j; small.first_block[small.count] = tb;
-      tb += (int)((tensors[j].n + ADAM_PACK_CHUNK - 1) / ADAM_PACK_CHUNK);
+      tb += (int)blocks_for(tensors[j].n, ADAM_PACK_CHUNK);
       ++small.count;
     }
     small.first_block[small.count] = tb;
@@ -292,20 +291,18 @@ extern "C" int lrf_adam_step_pack(const LrfAdamTensor* tensors, int32_t count, c
     for (int j = 0; j < count; ++j) {
       if (taken[j]) continue;
       tab.t[tab.count] = tensors[j]; tab.row[tab.count] = (short)j; tab.first_block[tab.count] = nb;
-      nb += (int)((tensors[j].n + ADAM_CHUNK - 1) / ADAM_CHUNK);
+      nb += (int)blocks_for(tensors[j].n, ADAM_CHUNK);
       ++tab.count;
     }
     tab.first_block[tab.count] = nb;
-    if (nb) hipLaunchKernelGGL(k_adam_multi, dim3(nb), dim3(ADAM_TPB), 0, st, tab, beta1, beta2, eps, dev_scalars);
+    if (nb) LRF_TRY(launch(k_adam_multi, nb, ADAM_TPB, st, tab, beta1, beta2, eps, dev_scalars));
   }
-  hipLaunchKernelGGL(k_adam_pack, dim3(blocks + tb), dim3(128), 0, st, pt, small, beta1, beta2, eps, dev_scalars);
+  LRF_TRY(launch(k_adam_pack, blocks + tb, 128, st, pt, small, beta1, beta2, eps, dev_scalars));
   // the fragment-ordered images of the colour network, from the weights the table kernel just stepped (slice 18 of k_pack_planes)
   PackTab none = {};
   PackMlp pm;
   pm.mlp = base + L.mlp; pm.mlpb = reinterpret_cast<uint32_t*>(base + L.mlpb); pm.mlpw = reinterpret_cast<uint32_t*>(base + L.mlpw);
   pm.mlpwt = reinterpret_cast<uint32_t*>(base + L.mlpwt);
   pm.mode = gen_is_default(p->fea_pe, p->view_pe, p->feature_c ? p->feature_c : LRF_FEATC) ? 0 : 1;
-  hipLaunchKernelGGL(k_pack_planes, dim3(8, 8, 1), dim3(128), 0, st, none, *p, pm, 18);
-  LRF_HIP(hipGetLastError());
-  return 0;
+  return launch(k_pack_planes, dim3(8, 8, 1), 128, st, none, *p, pm, 18);
 }

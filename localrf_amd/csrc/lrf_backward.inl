@@ -1755,12 +1755,12 @@ static BwdWorkspace carve_bwd(void* ws, int R, int S, const int32_t grid[3], int
                               bool det = false /* LRF_FLAG_DETERMINISTIC: + the int64 gradient image, behind everything else */) {
   BwdWorkspace b;
   b.fw = carve(ws, R, S);
-  char* p = reinterpret_cast<char*>(ws);
-  size_t off = b.fw.bytes;
+  Carver c(ws);
+  c.take<char>(b.fw.bytes);                                     // the forward's layout is the first piece
   const Layout L = make_layout(grid);
   const size_t rows = (size_t)R * b.fw.pmax * 16;
   const size_t nch = WGRAD_MAXCH;
-  auto take = [&](size_t nfloat) { float* q = reinterpret_cast<float*>(p + off); off += up256(nfloat * 4); return q; };
+  auto take = [&](size_t nfloat) { return c.take<float>(nfloat, 256); };
   auto take_bins = [&] {
     BinBufs B;
     B.tid = reinterpret_cast<uint16_t*>(take((3 * rows + 1) / 2 + 2));
@@ -1789,16 +1789,16 @@ static BwdWorkspace carve_bwd(void* ws, int R, int S, const int32_t grid[3], int
   b.gen = gen_ld ? take(rows * (size_t)gen_ld) : nullptr;
   b.det_img = nullptr; b.det_words = 0; b.det_d = DetDst{}; b.det_a = DetDst{};
   if (det) {
-    const size_t img0 = off;
-    auto take64 = [&](size_t n) { return reinterpret_cast<unsigned long long*>(take(2 * n)); };
+    const size_t img0 = c.at;
+    auto take64 = [&](size_t n) { return c.take<unsigned long long>(n, 256); };
     for (int q = 0; q < 3; ++q) {
       b.det_d.plane[q] = take64((size_t)LRF_CD * L.pw[q] * L.ph[q]); b.det_d.line[q] = take64((size_t)LRF_CD * L.ll[q]);
       b.det_a.plane[q] = take64((size_t)LRF_CA * L.pw[q] * L.ph[q]); b.det_a.line[q] = take64((size_t)LRF_CA * L.ll[q]);
     }
-    b.det_img = reinterpret_cast<unsigned long long*>(p + img0);
-    b.det_words = (long long)((off - img0) / 8);          // (a multiple of 32: every piece is rounded up to 256 bytes)
+    b.det_img = b.det_d.plane[0];
+    b.det_words = (long long)((c.at - img0) / 8);         // (a multiple of 32: every piece is rounded up to 256 bytes)
   }
-  b.bytes = off;
+  b.bytes = c.bytes();
   return b;
 }
 

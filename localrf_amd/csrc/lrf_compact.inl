@@ -1,6 +1,7 @@
 // lrf_compact.inl -- what the scene-end geometry files (lrf_points.inl, lrf_mesh*.inl, lrf_tsdf_blocks.inl) share: the ordered
-// compaction's scans and keep-list rank, the wave-leader atomics, and the host helpers of their entry points (included by
-// lrf_render.hip ahead of lrf_points.inl).  Nothing here has fewer than two call sites.
+// compaction's scans and keep-list rank, the wave-leader atomics, k_points_scan and the small predicates in_range, is_finite
+// and mesh_shape (included by lrf_render.hip ahead of lrf_points.inl).  Nothing here has fewer than two call sites.  The host
+// helpers of the entry points (refuse, launch, misaligned, blocks_for, round_up, Carver) live in lrf_host.inl.
 //
 // Ordered compaction, as every one of those files does it: a mark pass leaves one keep bit per item (64-bit words) and a count
 // per group of items, k_points_scan turns the group counts into exclusive bases, and a write pass sends a kept item to row
@@ -94,42 +95,6 @@ __global__ __launch_bounds__(PTS_SCAN_NT) void k_points_scan(unsigned* __restric
   if (threadIdx.x == 0) count[blockIdx.x] = (long long)carry;
 }
 
-// ------------------------------------------------------------------------------------------------ host side
-static size_t round_up(size_t n, size_t to) { return (n + to - 1) / to * to; }
-static unsigned blocks_for(long long n, int nt) { return (unsigned)((n + nt - 1) / nt); }
 static bool mesh_shape(long long Nv, long long Nf) { return Nv >= 1 && Nf >= 0 && Nv < (1ll << 31) && Nf < (1ll << 31); }
-
-// any of the pointers (null passes) off the alignment mask + 1
-template <class... P>
-static bool misaligned(uintptr_t mask, const P*... p) { return ((uintptr_t)0 | ... | (uintptr_t)p) & mask; }
-
-// refuses with "<who>: <what>"
-static int refuse(const char* who, const char* what) {
-  snprintf(lrf_error_slot(), 512, "%s: %s", who, what);
-  return 1;
-}
-
-// enqueues k and checks the launch; used as LRF_TRY(launch(k, grid, nt, st, args...)), the arguments converted as by a call
-template <class... P, class... A>
-static int launch(void (*k)(P...), dim3 grid, int nt, hipStream_t st, const A&... args) {
-  hipLaunchKernelGGL(k, grid, dim3(nt), 0, st, static_cast<P>(args)...);
-  LRF_HIP(hipGetLastError());
-  return 0;
-}
-
-// a workspace layout is written once, as a function that takes its arrays from a Carver in order: over a null base it gives
-// the size (bytes()), over the caller's workspace the pointers
-struct Carver {
-  char* base;
-  size_t at = 0;
-  explicit Carver(void* ws) : base(static_cast<char*>(ws)) {}
-  template <class T>
-  T* take(size_t count) {
-    T* p = reinterpret_cast<T*>(reinterpret_cast<uintptr_t>(base) + at);
-    at += count * sizeof(T);
-    return p;
-  }
-  size_t bytes() const { return round_up(at, 256); }
-};
 
 }  // namespace lrf

@@ -175,44 +175,44 @@ __global__ __launch_bounds__(ENC_NT) void k_encode(EncodeArgs a) {
 static bool enc_shape_ok(int V, int H, int W) {
   return V >= 1 && H > 0 && W > 0 && (long long)V * H * W * 3 < (1ll << 31);
 }
+// [V x ENC_RANGE_WG x (min, max) keys]; its size is c.at, not rounded
+static unsigned* carve_encode(Carver& c, int V) { return c.take<unsigned>((size_t)V * ENC_RANGE_WG * 2); }
 
 }  // namespace lrf
 
 extern "C" size_t lrf_encode_frames_workspace_bytes(int32_t V) {
   using namespace lrf;
   if (V < 1 || V > (1 << 24)) return 0;
-  return (size_t)V * ENC_RANGE_WG * 2 * sizeof(unsigned);
+  Carver c(nullptr);
+  carve_encode(c, V);
+  return c.at;
 }
 
 extern "C" int lrf_encode_frames(const float* rgb, const float* depth, int32_t V, int32_t H, int32_t W, const uint8_t* lut,
                                  const float* fixed_range, uint8_t* rgb8, uint8_t* depth8, uint8_t* depth_idx, float* range_out,
                                  void* workspace, void* stream) {
   using namespace lrf;
-  if (!enc_shape_ok(V, H, W)) return set_err("lrf_encode_frames: need V >= 1, H, W > 0 and 3 V H W < 2^31");
-  if (!depth || !lut || !depth8) return set_err("lrf_encode_frames: null argument");
-  if (!rgb != !rgb8) return set_err("lrf_encode_frames: rgb and rgb8 go together");
-  if (!fixed_range && !workspace) return set_err("lrf_encode_frames: the automatic range needs a workspace");
-  if (!fixed_range && V > (1 << 24)) return set_err("lrf_encode_frames: need V <= 2^24 for the automatic range");
-  if (((uintptr_t)rgb | (uintptr_t)depth) & 15) return set_err("lrf_encode_frames: rgb and depth must be 16-byte aligned");
-  if (((uintptr_t)rgb8 | (uintptr_t)depth8 | (uintptr_t)depth_idx | (uintptr_t)range_out | (uintptr_t)workspace) & 3)
-    return set_err("lrf_encode_frames: outputs and workspace must be 4-byte aligned");
+  const char* who = "lrf_encode_frames";
+  if (!enc_shape_ok(V, H, W)) return refuse(who, "need V >= 1, H, W > 0 and 3 V H W < 2^31");
+  if (!depth || !lut || !depth8) return refuse(who, "null argument");
+  if (!rgb != !rgb8) return refuse(who, "rgb and rgb8 go together");
+  if (!fixed_range && !workspace) return refuse(who, "the automatic range needs a workspace");
+  if (!fixed_range && V > (1 << 24)) return refuse(who, "need V <= 2^24 for the automatic range");
+  if (misaligned(15, rgb, depth)) return refuse(who, "rgb and depth must be 16-byte aligned");
+  if (misaligned(3, rgb8, depth8, depth_idx, range_out, workspace)) return refuse(who, "outputs and workspace must be 4-byte aligned");
+  Carver c(workspace);
+  unsigned* range = carve_encode(c, V);
   EncodeArgs a;
   memset(&a, 0, sizeof(a));
   a.rgb = rgb; a.depth = depth; a.lut = lut;
   a.rgb8 = rgb8; a.depth8 = depth8; a.idx = depth_idx; a.range_out = range_out;
-  a.ws = static_cast<const unsigned*>(workspace);
+  a.ws = range;
   a.HW = H * W; a.V = V;
   a.n = V * a.HW;
   if (fixed_range) { a.mi = fixed_range[0]; a.ma = fixed_range[1]; a.D = fixed_range[2]; }
-  const unsigned blocks = (unsigned)((a.n + ENC_PX - 1) / ENC_PX);
+  const unsigned blocks = blocks_for(a.n, ENC_PX);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (fixed_range) {
-    hipLaunchKernelGGL(k_encode<false>, dim3(blocks), dim3(ENC_NT), 0, st, a);
-  } else {
-    hipLaunchKernelGGL(k_encode_range, dim3(ENC_RANGE_WG, V), dim3(ENC_NT), 0, st, depth, a.HW, static_cast<unsigned*>(workspace));
-    LRF_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_encode<true>, dim3(blocks), dim3(ENC_NT), 0, st, a);
-  }
-  LRF_HIP(hipGetLastError());
-  return 0;
+  if (fixed_range) return launch(k_encode<false>, blocks, ENC_NT, st, a);
+  LRF_TRY(launch(k_encode_range, dim3(ENC_RANGE_WG, V), ENC_NT, st, depth, a.HW, range));
+  return launch(k_encode<true>, blocks, ENC_NT, st, a);
 }

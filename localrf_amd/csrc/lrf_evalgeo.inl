@@ -153,89 +153,94 @@ __global__ __launch_bounds__(EG_NT) void k_depth_out(const float* __restrict__ s
   o[2 * HW + p] = clamp01_nan(d * d);
 }
 
-static size_t eg_align(size_t b) { return (b + 255) & ~(size_t)255; }
 static bool eg_frame_ok(int H, int W) { return H > 0 && W > 0 && (long long)H * W * 6 < (1ll << 31); }
 static int depth_chunks(int HW) { return (HW + EG_NT * 16 - 1) / (EG_NT * 16); }
+
+// [select of 4 V rows] [the 8 V H W floats it selects from]
+struct FlowCmpWs { void* select; float* sel; size_t bytes; };
+static FlowCmpWs carve_flow_cmp(void* ws, int V, int HW) {
+  FlowCmpWs w;
+  Carver c(ws);
+  w.select = c.take<char>(select_ws_bytes(4 * V));
+  w.sel = c.take<float>((size_t)V * 8 * HW, 256);
+  w.bytes = c.bytes();
+  return w;
+}
+// [select of 2 V rows] [2 V H W floats] [2 V chunks partial sums] [2 V medians]
+struct DepthCmpWs { void* select; float* sel; double* part; float* med; size_t bytes; };
+static DepthCmpWs carve_depth_cmp(void* ws, int V, int HW) {
+  DepthCmpWs w;
+  Carver c(ws);
+  w.select = c.take<char>(select_ws_bytes(2 * V));
+  w.sel = c.take<float>((size_t)2 * V * HW, 256);
+  w.part = c.take<double>((size_t)2 * V * depth_chunks(HW), 256);
+  w.med = c.take<float>((size_t)2 * V, 256);
+  w.bytes = c.bytes();
+  return w;
+}
 
 }  // namespace lrf
 
 extern "C" size_t lrf_flow_comparison_workspace_bytes(int32_t V, int32_t H, int32_t W) {
   using namespace lrf;
   if (V < 1 || V > LRF_EVAL_MAX_VIEWS || !eg_frame_ok(H, W)) return 0;
-  return select_ws_bytes(4 * V) + eg_align((size_t)V * 8 * H * W * sizeof(float));
+  return carve_flow_cmp(nullptr, V, H * W).bytes;
 }
 
 extern "C" int lrf_flow_comparison(const LrfFlowComparison* c, float* fwd_cmp, float* bwd_cmp, float* fwd_raw, float* bwd_raw,
                                    float* quantiles, void* workspace, void* stream) {
   using namespace lrf;
-  if (!c) return set_err("lrf_flow_comparison: null argument");
+  const char* who = "lrf_flow_comparison";
+  if (!c) return refuse(who, "null argument");
   const int V = c->V, H = c->H, W = c->W, F = c->F;
-  if (V < 1 || V > LRF_EVAL_MAX_VIEWS) return set_err("lrf_flow_comparison: need 1 <= V <= LRF_EVAL_MAX_VIEWS");
-  if (!eg_frame_ok(H, W)) return set_err("lrf_flow_comparison: need H, W > 0 and 6 H W < 2^31");
-  if (F < 1) return set_err("lrf_flow_comparison: need F >= 1 poses");
+  if (V < 1 || V > LRF_EVAL_MAX_VIEWS) return refuse(who, "need 1 <= V <= LRF_EVAL_MAX_VIEWS");
+  if (!eg_frame_ok(H, W)) return refuse(who, "need H, W > 0 and 6 H W < 2^31");
+  if (F < 1) return refuse(who, "need F >= 1 poses");
   for (int v = 0; v < V; ++v)
-    if (c->idx[v] < 0 || c->idx[v] >= F) return set_err("lrf_flow_comparison: a view index lies outside [0, F)");
+    if (c->idx[v] < 0 || c->idx[v] >= F) return refuse(who, "a view index lies outside [0, F)");
   if (!c->cam2world || !c->depth || !c->dirs || !c->ij || !c->fwd_flow || !c->fwd_mask || !c->bwd_flow || !c->bwd_mask ||
       !c->focal || !c->center || !fwd_cmp || !bwd_cmp || !quantiles || !workspace)
-    return set_err("lrf_flow_comparison: null argument");
-  if ((fwd_raw == nullptr) != (bwd_raw == nullptr)) return set_err("lrf_flow_comparison: fwd_raw and bwd_raw go together");
+    return refuse(who, "null argument");
+  if ((fwd_raw == nullptr) != (bwd_raw == nullptr)) return refuse(who, "fwd_raw and bwd_raw go together");
 
+  const int HW = H * W;
+  const FlowCmpWs w = carve_flow_cmp(workspace, V, HW);
   FlowCmpArgs a;
   memset(&a, 0, sizeof(a));
   a.c2w = c->cam2world; a.depth = c->depth; a.dirs = c->dirs; a.ij = reinterpret_cast<const long long*>(c->ij);
   a.flow[0] = c->fwd_flow; a.flow[1] = c->bwd_flow; a.mask[0] = c->fwd_mask; a.mask[1] = c->bwd_mask;
   a.focal = c->focal; a.center = c->center;
   a.raw[0] = fwd_raw ? fwd_raw : fwd_cmp; a.raw[1] = bwd_raw ? bwd_raw : bwd_cmp;
-  char* ws = static_cast<char*>(workspace);
-  void* sel_ws = ws;
-  a.sel = reinterpret_cast<float*>(ws + select_ws_bytes(4 * V));
+  a.sel = w.sel;
   a.F = F; a.V = V; a.H = H; a.W = W;
   for (int v = 0; v < V; ++v) a.idx[v] = c->idx[v];
-  const int HW = H * W;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(k_flow_cmp, dim3((HW + EG_NT - 1) / EG_NT, V), dim3(EG_NT), 0, st, a);
-  LRF_HIP(hipGetLastError());
+  LRF_TRY(launch(k_flow_cmp, dim3(blocks_for(HW, EG_NT), V), EG_NT, st, a));
   const int64_t n = 2ll * HW;
-  if (int rc = select_launch(a.sel, n, &n, 1, 4 * V, LRF_SELECT_QUANTILE, EG_FLOW_Q, quantiles, sel_ws, st)) return rc;
-  hipLaunchKernelGGL(k_flow_norm, dim3((6 * HW + EG_NT - 1) / EG_NT, 2 * V), dim3(EG_NT), 0, st, a.raw[0], a.raw[1], fwd_cmp, bwd_cmp,
-                     quantiles, H, W);
-  LRF_HIP(hipGetLastError());
-  return 0;
+  LRF_TRY(select_launch(a.sel, n, &n, 1, 4 * V, LRF_SELECT_QUANTILE, EG_FLOW_Q, quantiles, w.select, st));
+  return launch(k_flow_norm, dim3(blocks_for(6ll * HW, EG_NT), 2 * V), EG_NT, st, a.raw[0], a.raw[1], fwd_cmp, bwd_cmp, quantiles, H, W);
 }
 
 extern "C" size_t lrf_depth_comparison_workspace_bytes(int32_t V, int32_t H, int32_t W) {
   using namespace lrf;
   if (V < 1 || V > 32767 || !eg_frame_ok(H, W)) return 0;
-  const int HW = H * W;
-  return select_ws_bytes(2 * V) + eg_align((size_t)2 * V * HW * sizeof(float)) + eg_align((size_t)2 * V * depth_chunks(HW) * sizeof(double)) +
-         eg_align((size_t)2 * V * sizeof(float));
+  return carve_depth_cmp(nullptr, V, H * W).bytes;
 }
 
 extern "C" int lrf_depth_comparison(const float* depth, const float* invdepth, int32_t V, int32_t H, int32_t W, float* out, float* stats,
                                     void* workspace, void* stream) {
   using namespace lrf;
-  if (V < 1 || V > 32767) return set_err("lrf_depth_comparison: need 1 <= V <= 32767");
-  if (!eg_frame_ok(H, W)) return set_err("lrf_depth_comparison: need H, W > 0 and 6 H W < 2^31");
-  if (!depth || !invdepth || !out || !stats || !workspace) return set_err("lrf_depth_comparison: null argument");
+  const char* who = "lrf_depth_comparison";
+  if (V < 1 || V > 32767) return refuse(who, "need 1 <= V <= 32767");
+  if (!eg_frame_ok(H, W)) return refuse(who, "need H, W > 0 and 6 H W < 2^31");
+  if (!depth || !invdepth || !out || !stats || !workspace) return refuse(who, "null argument");
   const int HW = H * W, chunks = depth_chunks(HW);
-  char* ws = static_cast<char*>(workspace);
-  void* sel_ws = ws;
-  ws += select_ws_bytes(2 * V);
-  float* sel = reinterpret_cast<float*>(ws);
-  ws += eg_align((size_t)2 * V * HW * sizeof(float));
-  double* part = reinterpret_cast<double*>(ws);
-  ws += eg_align((size_t)2 * V * chunks * sizeof(double));
-  float* med = reinterpret_cast<float*>(ws);
+  const DepthCmpWs w = carve_depth_cmp(workspace, V, HW);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(k_depth_prep, dim3((HW + EG_NT - 1) / EG_NT, V), dim3(EG_NT), 0, st, depth, invdepth, sel, V, HW);
-  LRF_HIP(hipGetLastError());
+  LRF_TRY(launch(k_depth_prep, dim3(blocks_for(HW, EG_NT), V), EG_NT, st, depth, invdepth, w.sel, V, HW));
   const int64_t n = HW;
-  if (int rc = select_launch(sel, n, &n, 1, 2 * V, LRF_SELECT_MEDIAN, 0.0f, med, sel_ws, st)) return rc;
-  hipLaunchKernelGGL(k_depth_mad, dim3(chunks, 2 * V), dim3(EG_NT), 0, st, sel, med, part, HW, chunks);
-  LRF_HIP(hipGetLastError());
-  hipLaunchKernelGGL(k_depth_mad_reduce, dim3(2 * V), dim3(EG_NT), 0, st, part, med, chunks, V, (double)HW, stats);
-  LRF_HIP(hipGetLastError());
-  hipLaunchKernelGGL(k_depth_out, dim3((HW + EG_NT - 1) / EG_NT, V), dim3(EG_NT), 0, st, sel, stats, out, V, HW);
-  LRF_HIP(hipGetLastError());
-  return 0;
+  LRF_TRY(select_launch(w.sel, n, &n, 1, 2 * V, LRF_SELECT_MEDIAN, 0.0f, w.med, w.select, st));
+  LRF_TRY(launch(k_depth_mad, dim3(chunks, 2 * V), EG_NT, st, w.sel, w.med, w.part, HW, chunks));
+  LRF_TRY(launch(k_depth_mad_reduce, 2 * V, EG_NT, st, w.part, w.med, chunks, V, (double)HW, stats));
+  return launch(k_depth_out, dim3(blocks_for(HW, EG_NT), V), EG_NT, st, w.sel, stats, out, V, HW);
 }

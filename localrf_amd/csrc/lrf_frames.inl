@@ -157,56 +157,60 @@ extern "C" int lrf_frames_gather(const LrfFrameWindow* w, const int64_t* view_id
                                  float* rgbs, float* loss_weights, float* invdepths, float* fwd_flow, float* fwd_mask,
                                  float* bwd_flow, float* bwd_mask, void* stream) {
   using namespace lrf;
-  if (const char* bad = frames_check(w)) return set_err(bad);
-  if (V <= 0 || n <= 0 || (long long)V * n > INT32_MAX / 4) return set_err("lrf_frames_gather: need V > 0, n > 0 and V * n < 2^29");
-  if (!view_ids || !ray_ids) return set_err("lrf_frames_gather: null ids");
+  const char* who = "lrf_frames_gather";
+  if (const char* bad = frames_check(w)) return refuse(bad);
+  if (V <= 0 || n <= 0 || (long long)V * n > INT32_MAX / 4) return refuse(who, "need V > 0, n > 0 and V * n < 2^29");
+  if (!view_ids || !ray_ids) return refuse(who, "null ids");
   if ((invdepths && !w->invdepth) || ((fwd_flow || fwd_mask) && !w->fwd_flow) || ((bwd_flow || bwd_mask) && !w->bwd_flow))
-    return set_err("lrf_frames_gather: an output was asked for a plane the window does not hold");
+    return refuse(who, "an output was asked for a plane the window does not hold");
   const long long B = (long long)V * n;
-  hipLaunchKernelGGL(k_frames_gather, dim3((unsigned)((B + FR_NT - 1) / FR_NT)), dim3(FR_NT), 0, reinterpret_cast<hipStream_t>(stream), *w,
-                     reinterpret_cast<const long long*>(view_ids), reinterpret_cast<const long long*>(ray_ids), V, n,
-                     rgbs, loss_weights, invdepths, fwd_flow, fwd_mask, bwd_flow, bwd_mask);
-  LRF_HIP(hipGetLastError());
-  return 0;
+  return launch(k_frames_gather, blocks_for(B, FR_NT), FR_NT, reinterpret_cast<hipStream_t>(stream), *w,
+                reinterpret_cast<const long long*>(view_ids), reinterpret_cast<const long long*>(ray_ids), V, n,
+                rgbs, loss_weights, invdepths, fwd_flow, fwd_mask, bwd_flow, bwd_mask);
 }
 
 extern "C" int lrf_decode_flow(const LrfFrameWindow* w, int32_t slot, int32_t backward, const uint16_t* encoded, int32_t H, int32_t W,
                                double flow_scale, void* stream) {
   using namespace lrf;
-  if (const char* bad = frames_check(w)) return set_err(bad);
-  if (slot < 0 || slot >= w->capacity) return set_err("lrf_decode_flow: slot outside the window");
-  if (H <= 0 || W <= 0 || (long long)H * W != w->n_px) return set_err("lrf_decode_flow: H * W must equal the window's n_px");
-  if (!encoded) return set_err("lrf_decode_flow: null encoded flow");
+  const char* who = "lrf_decode_flow";
+  if (const char* bad = frames_check(w)) return refuse(bad);
+  if (slot < 0 || slot >= w->capacity) return refuse(who, "slot outside the window");
+  if (H <= 0 || W <= 0 || (long long)H * W != w->n_px) return refuse(who, "H * W must equal the window's n_px");
+  if (!encoded) return refuse(who, "null encoded flow");
   float* flow = backward ? w->bwd_flow : w->fwd_flow;
   float* mask = backward ? w->bwd_mask : w->fwd_mask;
-  if (!flow) return set_err("lrf_decode_flow: the window holds no flow planes");
+  if (!flow) return refuse(who, "the window holds no flow planes");
   const float scale = (float)flow_scale;                      // numpy: float32 array * Python float -> the float rounded to fp32
-  if (!__builtin_isfinite(scale)) return set_err("lrf_decode_flow: flow_scale must be finite in fp32");
+  if (!__builtin_isfinite(scale)) return refuse(who, "flow_scale must be finite in fp32");
   const size_t off = (size_t)slot * w->n_px;
-  hipLaunchKernelGGL(k_decode_flow, dim3((w->n_px + FR_NT - 1) / FR_NT), dim3(FR_NT), 0, reinterpret_cast<hipStream_t>(stream),
-                     reinterpret_cast<const unsigned short*>(encoded), w->n_px, scale, flow + 2 * off, mask + off);
-  LRF_HIP(hipGetLastError());
-  return 0;
+  return launch(k_decode_flow, blocks_for(w->n_px, FR_NT), FR_NT, reinterpret_cast<hipStream_t>(stream),
+                reinterpret_cast<const unsigned short*>(encoded), w->n_px, scale, flow + 2 * off, mask + off);
 }
 
-extern "C" size_t lrf_frame_sharpness_workspace_bytes(void) { return (size_t)lrf::SH_PARTS * 2 * sizeof(long long); }
+// [SH_PARTS x (sum, sum of squares)]; its size is c.at, not rounded
+static long long* carve_sharpness(lrf::Carver& c) { return c.take<long long>((size_t)lrf::SH_PARTS * 2); }
+
+extern "C" size_t lrf_frame_sharpness_workspace_bytes(void) {
+  lrf::Carver c(nullptr);
+  carve_sharpness(c);
+  return c.at;
+}
 
 extern "C" int lrf_frame_sharpness(const LrfFrameWindow* w, int32_t slot, int32_t H, int32_t W, const uint8_t* motion_mask,
                                    void* workspace, void* stream) {
   using namespace lrf;
-  if (const char* bad = frames_check(w)) return set_err(bad);
-  if (slot < 0 || slot >= w->capacity) return set_err("lrf_frame_sharpness: slot outside the window");
-  if (H <= 0 || W <= 0 || (long long)H * W != w->n_px) return set_err("lrf_frame_sharpness: H * W must equal the window's n_px");
-  if (w->n_px > SH_MAX_PX) return set_err("lrf_frame_sharpness: at most 2^21 pixels per frame (the int64 variance bound)");
-  if (!workspace) return set_err("lrf_frame_sharpness: null workspace");
+  const char* who = "lrf_frame_sharpness";
+  if (const char* bad = frames_check(w)) return refuse(bad);
+  if (slot < 0 || slot >= w->capacity) return refuse(who, "slot outside the window");
+  if (H <= 0 || W <= 0 || (long long)H * W != w->n_px) return refuse(who, "H * W must equal the window's n_px");
+  if (w->n_px > SH_MAX_PX) return refuse(who, "at most 2^21 pixels per frame (the int64 variance bound)");
+  if (!workspace) return refuse(who, "null workspace");
   const size_t off = (size_t)slot * w->n_px;
-  long long* part = static_cast<long long*>(workspace);
+  Carver c(workspace);
+  long long* part = carve_sharpness(c);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(k_frame_sharpness, dim3(SH_PARTS), dim3(FR_NT), 0, st, w->rgb + 3 * off, H, W, part);
-  LRF_HIP(hipGetLastError());
-  const int blocks = (w->n_px + FR_NT * 8 - 1) / (FR_NT * 8);
-  hipLaunchKernelGGL(k_frame_weight, dim3(blocks < 1024 ? blocks : 1024), dim3(FR_NT), 0, st, part, w->n_px,
-                     reinterpret_cast<const unsigned char*>(motion_mask), w->loss_weight + off);
-  LRF_HIP(hipGetLastError());
-  return 0;
+  LRF_TRY(launch(k_frame_sharpness, SH_PARTS, FR_NT, st, w->rgb + 3 * off, H, W, part));
+  const unsigned blocks = blocks_for(w->n_px, FR_NT * 8);
+  return launch(k_frame_weight, blocks < 1024 ? blocks : 1024, FR_NT, st, part, w->n_px,
+                reinterpret_cast<const unsigned char*>(motion_mask), w->loss_weight + off);
 }

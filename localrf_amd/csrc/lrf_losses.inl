@@ -381,12 +381,10 @@ __global__ __launch_bounds__(LOSS_NT) void k_depth_loss_bwd(DepthArgs a, const f
 
 extern "C" int lrf_upsample_bilinear(const float* src, int32_t C, int32_t H, int32_t W, float* dst, int32_t H2, int32_t W2, void* stream) {
   using namespace lrf;
-  if (!src || !dst || C <= 0 || H <= 0 || W <= 0 || H2 <= 0 || W2 <= 0) return set_err("lrf_upsample_bilinear: bad argument");
+  if (!src || !dst || C <= 0 || H <= 0 || W <= 0 || H2 <= 0 || W2 <= 0) return refuse("lrf_upsample_bilinear", "bad argument");
   const long long n = (long long)C * H2 * W2;
   const int blocks = (int)min((n + 255) / 256, (long long)65535 * 4);
-  hipLaunchKernelGGL(k_upsample_bilinear, dim3(blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), src, dst, C, H, W, H2, W2);
-  LRF_HIP(hipGetLastError());
-  return 0;
+  return launch(k_upsample_bilinear, blocks, 256, reinterpret_cast<hipStream_t>(stream), src, dst, C, H, W, H2, W2);
 }
 
 static int flow_args_ok(const LrfFlowLoss* a) {
@@ -403,41 +401,33 @@ static lrf::FlowArgs flow_args(const LrfFlowLoss* a) {
 }
 extern "C" int lrf_flow_loss_fwd(const LrfFlowLoss* a, float* arr_out, float* view_sum, void* stream) {
   using namespace lrf;
-  if (!flow_args_ok(a) || !arr_out || !view_sum) return set_err("lrf_flow_loss_fwd: bad argument (1 <= rays per view <= LRF_LOSS_MAX_PER_VIEW)");
-  hipLaunchKernelGGL(k_flow_loss_fwd, dim3(a->V), dim3(LOSS_NT), 0, reinterpret_cast<hipStream_t>(stream), flow_args(a), arr_out, view_sum);
-  LRF_HIP(hipGetLastError());
-  return 0;
+  if (!flow_args_ok(a) || !arr_out || !view_sum) return refuse("lrf_flow_loss_fwd", "bad argument (1 <= rays per view <= LRF_LOSS_MAX_PER_VIEW)");
+  return launch(k_flow_loss_fwd, a->V, LOSS_NT, reinterpret_cast<hipStream_t>(stream), flow_args(a), arr_out, view_sum);
 }
 extern "C" int lrf_flow_loss_bwd(const LrfFlowLoss* a, const float* arr_out, const float* g_loss, float scale, float* g_depth,
                                  float* g_dirs, float* g_cam2world, float* g_intr, float* workspace, void* stream) {
   using namespace lrf;
   if (!flow_args_ok(a) || !arr_out || !g_loss || !g_depth || !g_dirs || !g_cam2world || !g_intr || !workspace)
-    return set_err("lrf_flow_loss_bwd: bad argument");
+    return refuse("lrf_flow_loss_bwd", "bad argument");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(k_flow_loss_bwd, dim3(a->V), dim3(LOSS_NT), 0, st, flow_args(a), arr_out, g_loss, scale, g_depth, g_dirs, workspace, g_intr);
-  hipLaunchKernelGGL(k_flow_pose_reduce, dim3((a->F * 12 + 255) / 256), dim3(256), 0, st, workspace, a->frame, a->V, a->F, g_cam2world);
-  LRF_HIP(hipGetLastError());
-  return 0;
+  LRF_TRY(launch(k_flow_loss_bwd, a->V, LOSS_NT, st, flow_args(a), arr_out, g_loss, scale, g_depth, g_dirs, workspace, g_intr));
+  return launch(k_flow_pose_reduce, blocks_for(a->F * 12, 256), 256, st, workspace, a->frame, a->V, a->F, g_cam2world);
 }
 extern "C" int lrf_depth_loss_fwd(const float* depth, const float* gt, int32_t V, int32_t n, float quantile, float* arr_out,
                                   float* stats, float* view_sum, void* stream) {
   using namespace lrf;
   if (!depth || !gt || !arr_out || !stats || !view_sum || V <= 0 || n <= 0 || n > LRF_LOSS_MAX_PER_VIEW)
-    return set_err("lrf_depth_loss_fwd: bad argument (1 <= rays per view <= LRF_LOSS_MAX_PER_VIEW)");
+    return refuse("lrf_depth_loss_fwd", "bad argument (1 <= rays per view <= LRF_LOSS_MAX_PER_VIEW)");
   const DepthArgs a{depth, gt, V, n, quantile};
-  hipLaunchKernelGGL(k_depth_loss_fwd, dim3(V), dim3(LOSS_NT), 0, reinterpret_cast<hipStream_t>(stream), a, arr_out, stats, view_sum);
-  LRF_HIP(hipGetLastError());
-  return 0;
+  return launch(k_depth_loss_fwd, V, LOSS_NT, reinterpret_cast<hipStream_t>(stream), a, arr_out, stats, view_sum);
 }
 extern "C" int lrf_depth_loss_bwd(const float* depth, const float* gt, int32_t V, int32_t n, const float* arr_out, const float* stats,
                                   const float* g_loss, float scale, float* g_depth, void* stream) {
   using namespace lrf;
   if (!depth || !gt || !arr_out || !stats || !g_loss || !g_depth || V <= 0 || n <= 0 || n > LRF_LOSS_MAX_PER_VIEW)
-    return set_err("lrf_depth_loss_bwd: bad argument");
+    return refuse("lrf_depth_loss_bwd", "bad argument");
   const DepthArgs a{depth, gt, V, n, 0.0f};
-  hipLaunchKernelGGL(k_depth_loss_bwd, dim3(V), dim3(LOSS_NT), 0, reinterpret_cast<hipStream_t>(stream), a, arr_out, stats, g_loss, scale, g_depth);
-  LRF_HIP(hipGetLastError());
-  return 0;
+  return launch(k_depth_loss_bwd, V, LOSS_NT, reinterpret_cast<hipStream_t>(stream), a, arr_out, stats, g_loss, scale, g_depth);
 }
 
 // ------------------------------------------------------------------------------------------- photometric loss, row gather
@@ -512,31 +502,23 @@ __global__ void k_rows_gather_bwd(const float* __restrict__ g_out, const long lo
 
 extern "C" int lrf_photo_loss_fwd(const float* rgb, const float* target, const float* w, const float* w_mean, int32_t R, float* loss, float* aux, void* stream) {
   using namespace lrf;
-  if (!rgb || !target || !loss || !aux || R <= 0) return set_err("lrf_photo_loss_fwd: bad argument");
-  hipLaunchKernelGGL(k_photo_loss_fwd, dim3(1), dim3(1024), 0, reinterpret_cast<hipStream_t>(stream), rgb, target, w, w_mean, R, loss, aux);
-  LRF_HIP(hipGetLastError());
-  return 0;
+  if (!rgb || !target || !loss || !aux || R <= 0) return refuse("lrf_photo_loss_fwd", "bad argument");
+  return launch(k_photo_loss_fwd, 1, 1024, reinterpret_cast<hipStream_t>(stream), rgb, target, w, w_mean, R, loss, aux);
 }
 extern "C" int lrf_photo_loss_bwd(const float* rgb, const float* target, const float* w, const float* aux, const float* g_loss, int32_t R, float* g_rgb, void* stream) {
   using namespace lrf;
-  if (!rgb || !target || !aux || !g_loss || !g_rgb || R <= 0) return set_err("lrf_photo_loss_bwd: bad argument");
-  hipLaunchKernelGGL(k_photo_loss_bwd, dim3((3 * R + 255) / 256), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), rgb, target, w, aux, g_loss, R, g_rgb);
-  LRF_HIP(hipGetLastError());
-  return 0;
+  if (!rgb || !target || !aux || !g_loss || !g_rgb || R <= 0) return refuse("lrf_photo_loss_bwd", "bad argument");
+  return launch(k_photo_loss_bwd, blocks_for(3 * R, 256), 256, reinterpret_cast<hipStream_t>(stream), rgb, target, w, aux, g_loss, R, g_rgb);
 }
 extern "C" int lrf_rows_gather(const float* src, const int64_t* idx, int32_t V, int32_t K, int32_t F, float* out, void* stream) {
   using namespace lrf;
-  if (!src || !idx || !out || V <= 0 || K <= 0 || F <= 0) return set_err("lrf_rows_gather: bad argument");
-  hipLaunchKernelGGL(k_rows_gather, dim3((V * K + 255) / 256), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), src, reinterpret_cast<const long long*>(idx), V, K, F, out);
-  LRF_HIP(hipGetLastError());
-  return 0;
+  if (!src || !idx || !out || V <= 0 || K <= 0 || F <= 0) return refuse("lrf_rows_gather", "bad argument");
+  return launch(k_rows_gather, blocks_for(V * K, 256), 256, reinterpret_cast<hipStream_t>(stream), src, reinterpret_cast<const long long*>(idx), V, K, F, out);
 }
 extern "C" int lrf_rows_gather_bwd(const float* g_out, const int64_t* idx, int32_t V, int32_t K, int32_t F, float* g_src, void* stream) {
   using namespace lrf;
-  if (!g_out || !idx || !g_src || V <= 0 || K <= 0 || F <= 0) return set_err("lrf_rows_gather_bwd: bad argument");
-  hipLaunchKernelGGL(k_rows_gather_bwd, dim3((F * K + 255) / 256), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), g_out, reinterpret_cast<const long long*>(idx), V, K, F, g_src);
-  LRF_HIP(hipGetLastError());
-  return 0;
+  if (!g_out || !idx || !g_src || V <= 0 || K <= 0 || F <= 0) return refuse("lrf_rows_gather_bwd", "bad argument");
+  return launch(k_rows_gather_bwd, blocks_for(F * K, 256), 256, reinterpret_cast<hipStream_t>(stream), g_out, reinterpret_cast<const long long*>(idx), V, K, F, g_src);
 }
 
 // ---------------------------------------------------------------- batch assembly, loss assembly (round 6)
@@ -584,24 +566,19 @@ __global__ __launch_bounds__(64) void k_loss_combine_bwd(const float* __restrict
 extern "C" int lrf_batch_gather(const LrfBatchGather* a, float* target, float* fwd_flow, float* fwd_mask, float* bwd_flow,
                                 float* bwd_mask, float* invdepth, void* stream) {
   using namespace lrf;
-  if (!a || !a->view_ids || !a->pix || a->V <= 0 || a->n <= 0 || a->HW <= 0 || a->n_images <= 0) return set_err("lrf_batch_gather: bad argument");
-  hipLaunchKernelGGL(k_batch_gather, dim3((a->V * a->n + 255) / 256), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), *a,
-                     target, fwd_flow, fwd_mask, bwd_flow, bwd_mask, invdepth);
-  LRF_HIP(hipGetLastError());
-  return 0;
+  if (!a || !a->view_ids || !a->pix || a->V <= 0 || a->n <= 0 || a->HW <= 0 || a->n_images <= 0) return refuse("lrf_batch_gather", "bad argument");
+  return launch(k_batch_gather, blocks_for(a->V * a->n, 256), 256, reinterpret_cast<hipStream_t>(stream), *a,
+                target, fwd_flow, fwd_mask, bwd_flow, bwd_mask, invdepth);
 }
 extern "C" int lrf_loss_combine_fwd(const LrfLossTerms* t, float* total, float* w_out, void* stream) {
   using namespace lrf;
-  if (!t || !total || !w_out || t->count <= 0 || t->count > LRF_LOSS_TERMS_MAX) return set_err("lrf_loss_combine_fwd: bad argument");
-  for (int k = 0; k < t->count; ++k) if (!t->x[k] || t->n[k] <= 0) return set_err("lrf_loss_combine_fwd: null or empty term");
-  hipLaunchKernelGGL(k_loss_combine_fwd, dim3(1), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), *t, total, w_out);
-  LRF_HIP(hipGetLastError());
-  return 0;
+  const char* who = "lrf_loss_combine_fwd";
+  if (!t || !total || !w_out || t->count <= 0 || t->count > LRF_LOSS_TERMS_MAX) return refuse(who, "bad argument");
+  for (int k = 0; k < t->count; ++k) if (!t->x[k] || t->n[k] <= 0) return refuse(who, "null or empty term");
+  return launch(k_loss_combine_fwd, 1, 64, reinterpret_cast<hipStream_t>(stream), *t, total, w_out);
 }
 extern "C" int lrf_loss_combine_bwd(const float* w, const float* g_total, int32_t count, float* g, void* stream) {
   using namespace lrf;
-  if (!w || !g_total || !g || count <= 0 || count > LRF_LOSS_TERMS_MAX) return set_err("lrf_loss_combine_bwd: bad argument");
-  hipLaunchKernelGGL(k_loss_combine_bwd, dim3(1), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), w, g_total, count, g);
-  LRF_HIP(hipGetLastError());
-  return 0;
+  if (!w || !g_total || !g || count <= 0 || count > LRF_LOSS_TERMS_MAX) return refuse("lrf_loss_combine_bwd", "bad argument");
+  return launch(k_loss_combine_bwd, 1, 64, reinterpret_cast<hipStream_t>(stream), w, g_total, count, g);
 }

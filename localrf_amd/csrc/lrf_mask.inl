@@ -60,23 +60,20 @@ extern "C" int lrf_dense_alpha(const LrfField* f, const float* lin_x, const floa
                                int32_t gx, int32_t gy, int32_t gz, float length, uint32_t flags, float* alpha,
                                void* stream) {
   using namespace lrf;
-  if (!f || !f->cache || !lin_x || !lin_y || !lin_z || !alpha) return set_err("lrf_dense_alpha: null argument");
-  if (gx <= 0 || gy <= 0 || gz <= 0) return set_err("lrf_dense_alpha: bad lattice size");
+  const char* who = "lrf_dense_alpha";
+  if (!f || !f->cache || !lin_x || !lin_y || !lin_z || !alpha) return refuse(who, "null argument");
+  if (gx <= 0 || gy <= 0 || gz <= 0) return refuse(who, "bad lattice size");
   const size_t n = (size_t)gx * gy * gz;
-  hipLaunchKernelGGL(k_dense_alpha, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
-                     make_dfield(f), lin_x, lin_y, lin_z, gx, gy, gz, length, flags, alpha);
-  LRF_HIP(hipGetLastError());
-  return 0;
+  return launch(k_dense_alpha, (unsigned)((n + 255) / 256), 256, reinterpret_cast<hipStream_t>(stream),
+                make_dfield(f), lin_x, lin_y, lin_z, gx, gy, gz, length, flags, alpha);
 }
 
 extern "C" int lrf_alpha_pool_threshold(const float* alpha, int32_t gx, int32_t gy, int32_t gz, float thres, float* out,
                                         void* stream) {
   using namespace lrf;
-  if (!alpha || !out) return set_err("lrf_alpha_pool_threshold: null argument");
-  if (gx <= 0 || gy <= 0 || gz <= 0) return set_err("lrf_alpha_pool_threshold: bad lattice size");
+  const char* who = "lrf_alpha_pool_threshold";
+  if (!alpha || !out) return refuse(who, "null argument");
+  if (gx <= 0 || gy <= 0 || gz <= 0) return refuse(who, "bad lattice size");
   const size_t n = (size_t)gx * gy * gz;
-  hipLaunchKernelGGL(k_alpha_pool, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
-                     alpha, gx, gy, gz, thres, out);
-  LRF_HIP(hipGetLastError());
-  return 0;
+  return launch(k_alpha_pool, (unsigned)((n + 255) / 256), 256, reinterpret_cast<hipStream_t>(stream), alpha, gx, gy, gz, thres, out);
 }

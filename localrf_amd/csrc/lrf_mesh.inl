@@ -1,6 +1,6 @@
 // lrf_mesh.inl -- rendered depth fused into a truncated signed-distance (TSDF) volume, and a triangle mesh extracted from a
 // scalar volume (included by lrf_render.hip after lrf_encode.inl and lrf_points.inl, whose enc_rgb_byte, pts_finite_pos and
-// reproject it shares; the scans and the host helpers are lrf_compact.inl's).  The fusion and the extraction are each written once, here, for the dense volume
+// reproject it shares; the scans are lrf_compact.inl's, the host helpers lrf_host.inl's).  The fusion and the extraction are each written once, here, for the dense volume
 // of this file and for the block-sparse one of lrf_tsdf_blocks.inl: the two differ only in where a lattice point is stored.
 //
 // A lattice has Nx x Ny x Nz points at origin + (ix, iy, iz) * voxel.  Per point: tsdf (starts at 1), weight (starts at 0), rgb

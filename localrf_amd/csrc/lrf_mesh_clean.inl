@@ -1,5 +1,5 @@
 // lrf_mesh_clean.inl -- the connected components of an indexed triangle mesh, and the mesh without its small components
-// (included by lrf_render.hip; the scan, the keep list and the host helpers are lrf_compact.inl's).  Integers only: no float
+// (included by lrf_render.hip; the scan and the keep list are lrf_compact.inl's, the host helpers lrf_host.inl's).  Integers only: no float
 // arithmetic touches the data, positions and colours are copied bit for bit.
 //
 // A mesh is vertices [Nv,3] fp32, rgb8 [Nv,3] uint8 (nullable) and faces [Nf,3] int32.  Two vertices are connected when a face

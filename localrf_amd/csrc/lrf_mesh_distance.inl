@@ -1,6 +1,6 @@
 // lrf_mesh_distance.inl -- the closest point of an indexed triangle mesh for a batch of query points, surface samples of a mesh,
 // and a distance tensor summarised (included by lrf_render.hip after lrf_mesh_smooth.inl, whose sm_key and k_sm_copy it reuses;
-// the scan, the wave-leader counts and the host helpers are lrf_compact.inl's).  Unsigned distance only.  The output bytes are a
+// the scan and the wave-leader counts are lrf_compact.inl's, the host helpers lrf_host.inl's).  Unsigned distance only.  The output bytes are a
 // fixed function of the input: exact minima with an index tie-break, integer sums, no float atomics.
 //
 // Every function below with contraction off; "fp64" means every operation rounded on its own, in the order written.

@@ -1,6 +1,6 @@
 // lrf_mesh_raster.inl -- an indexed triangle mesh rasterised into V pinhole cameras, and two depth maps compared (included by
 // lrf_render.hip; it reuses to_camera and pts_finite_pos of lrf_points.inl, pinhole_x / pinhole_y of lrf_scene.inl and sm_face of
-// lrf_mesh_smooth.inl; the wave-leader counts and the host helpers are lrf_compact.inl's).  The inverse of k_tsdf_integrate: mesh -> depth at a pose, in the depth
+// lrf_mesh_smooth.inl; the wave-leader counts are lrf_compact.inl's, the host helpers lrf_host.inl's).  The inverse of k_tsdf_integrate: mesh -> depth at a pose, in the depth
 // convention of lrf_points.inl (a multiple of the un-normalised pixel direction whose z is -1).  The output bytes are a fixed
 // function of the input: one consistent ray per pixel, an exact-sign coverage test, and an integer minimum per pixel.
 //

@@ -1,6 +1,6 @@
 // lrf_mesh_simplify.inl -- an indexed triangle mesh simplified by uniform vertex clustering (Rossignac-Borrel): every vertex
 // falls into a cell of a uniform grid, the vertices of a cell become one vertex at their mean, faces follow their vertices
-// (included by lrf_render.hip; the keep lists, their scans and the host helpers are lrf_compact.inl's; lrf_mesh_clean.inl's
+// (included by lrf_render.hip; the keep lists and their scans are lrf_compact.inl's, the host helpers lrf_host.inl's; lrf_mesh_clean.inl's
 // mf_workgroups sizes the face lists).
 // The output bytes are a fixed function of the input: integer sums, fp64 operations that are each rounded on their own, and a
 // choice among duplicate faces that does not depend on the order of arrival.  No sort, no floating-point atomics.

@@ -1,6 +1,6 @@
 // lrf_mesh_smooth.inl -- the faces around each vertex of an indexed triangle mesh (incidence lists), and the three things built
 // on them: boundary and non-manifold edge counts, area-weighted vertex normals, and Taubin lambda|mu smoothing (included by
-// lrf_render.hip; the scans and the host helpers are lrf_compact.inl's, k_ms_bounds_init is lrf_mesh_simplify.inl's).
+// lrf_render.hip; the scans are lrf_compact.inl's, the host helpers lrf_host.inl's, k_ms_bounds_init is lrf_mesh_simplify.inl's).
 // The output bytes are a fixed function of the input: integer counts, integer sums of fixed-point values, and fp64 operations
 // that are each rounded on their own (the functions that hold them switch contraction off).  No sort, no floating-point atomics.
 //

@@ -1,6 +1,6 @@
 // lrf_mesh_texture.inl -- a texture atlas baked for an indexed triangle mesh from encoded frames (included by lrf_render.hip
 // after lrf_mesh_raster.inl; it reuses to_camera and pts_finite_pos of lrf_points.inl and sm_face of lrf_mesh_smooth.inl; the
-// wave-leader counts and the host helpers are lrf_compact.inl's).  Per texel and frame: project, test visibility against the
+// wave-leader counts are lrf_compact.inl's, the host helpers lrf_host.inl's).  Per texel and frame: project, test visibility against the
 // mesh's own rasterised depth, weight, sample, accumulate.  The state bytes are a fixed function of the frames in their order.
 //
 // 1. Layout: a fixed patch of P x P texels (4 <= P <= 64, K = P - 3) holds two faces; faces 2c and 2c + 1 share cell c of a grid

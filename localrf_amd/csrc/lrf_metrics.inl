@@ -164,6 +164,8 @@ static void metrics_tiles(int H, int W, int* tiles_x, int* tiles) {
   *tiles_x = (W + MT_TW - 1) / MT_TW;
   *tiles = *tiles_x * ((H + MT_TH - 1) / MT_TH);
 }
+// [B x tiles partial sums]; its size is c.at, not rounded
+static double2* carve_metrics(Carver& c, int B, int tiles) { return c.take<double2>((size_t)B * tiles); }
 
 }  // namespace lrf
 
@@ -173,21 +175,24 @@ extern "C" size_t lrf_image_metrics_workspace_bytes(int32_t B, int32_t H, int32_
       (long long)H * W * 3 > INT32_MAX / 2) return 0;
   int tx, tiles;
   metrics_tiles(H, W, &tx, &tiles);
-  return (size_t)B * tiles * sizeof(double2);
+  Carver c(nullptr);
+  carve_metrics(c, B, tiles);
+  return c.at;
 }
 
 extern "C" int lrf_image_metrics(const LrfImageMetrics* m, double* ssim_map, double* ssim_mean, double* mse, void* workspace, void* stream) {
   using namespace lrf;
-  if (!m) return set_err("lrf_image_metrics: null argument");
+  const char* who = "lrf_image_metrics";
+  if (!m) return refuse(who, "null argument");
   const int B = m->B, H = m->H, W = m->W, fs = m->filter_size;
-  if (B <= 0 || B > 65535 || H <= 0 || W <= 0) return set_err("lrf_image_metrics: need 1 <= B <= 65535, H > 0 and W > 0");
-  if ((long long)H * W * 3 > INT32_MAX / 2) return set_err("lrf_image_metrics: frame too large (H * W * 3 must stay below 2^30)");
-  if (fs < 1 || fs > MT_MAX_FS) return set_err("lrf_image_metrics: filter_size must lie in 1..31");
-  if (H < fs || W < fs) return set_err("lrf_image_metrics: H and W must be at least filter_size (the valid SSIM map would be empty)");
-  if (m->filter_sigma == 0.0 || !__builtin_isfinite(m->filter_sigma)) return set_err("lrf_image_metrics: filter_sigma must be finite and non-zero");
+  if (B <= 0 || B > 65535 || H <= 0 || W <= 0) return refuse(who, "need 1 <= B <= 65535, H > 0 and W > 0");
+  if ((long long)H * W * 3 > INT32_MAX / 2) return refuse(who, "frame too large (H * W * 3 must stay below 2^30)");
+  if (fs < 1 || fs > MT_MAX_FS) return refuse(who, "filter_size must lie in 1..31");
+  if (H < fs || W < fs) return refuse(who, "H and W must be at least filter_size (the valid SSIM map would be empty)");
+  if (m->filter_sigma == 0.0 || !__builtin_isfinite(m->filter_sigma)) return refuse(who, "filter_sigma must be finite and non-zero");
   if (!__builtin_isfinite(m->max_val) || !__builtin_isfinite(m->k1) || !__builtin_isfinite(m->k2))
-    return set_err("lrf_image_metrics: max_val, k1 and k2 must be finite");
-  if (!m->img0 || !m->img1 || !ssim_mean || !mse || !workspace) return set_err("lrf_image_metrics: null argument");
+    return refuse(who, "max_val, k1 and k2 must be finite");
+  if (!m->img0 || !m->img1 || !ssim_mean || !mse || !workspace) return refuse(who, "null argument");
 
   MetricsArgs a;
   memset(&a, 0, sizeof(a));
@@ -211,21 +216,19 @@ extern "C" int lrf_image_metrics(const LrfImageMetrics* m, double* ssim_map, dou
     sum = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
     for (; i < fs; ++i) sum += filt[i];
   }
-  if (!(sum > 0.0) || !__builtin_isfinite(sum)) return set_err("lrf_image_metrics: the Gaussian filter vanishes (filter_sigma too small)");
+  if (!(sum > 0.0) || !__builtin_isfinite(sum)) return refuse(who, "the Gaussian filter vanishes (filter_sigma too small)");
   for (int k = 0; k < fs; ++k) a.taps[k] = filt[fs - 1 - k] / sum;
 
-  a.img0 = m->img0; a.img1 = m->img1; a.map = ssim_map; a.part = static_cast<double2*>(workspace);
+  a.img0 = m->img0; a.img1 = m->img1; a.map = ssim_map;
   a.H = H; a.W = W; a.fs = fs; a.OH = H - fs + 1; a.OW = W - fs + 1;
   metrics_tiles(H, W, &a.tiles_x, &a.tiles);
+  Carver c(workspace);
+  a.part = carve_metrics(c, B, a.tiles);
   const double c1 = m->k1 * m->max_val, c2 = m->k2 * m->max_val;
   a.c1 = c1 * c1; a.c2 = c2 * c2;
   const int EW = MT_TW + fs - 1, EH = MT_TH + fs - 1;
   const size_t lds = (size_t)5 * MT_RS * EW * sizeof(double) + (size_t)2 * EH * EW * sizeof(float);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(k_img_metrics, dim3(a.tiles, B), dim3(MT_NT), lds, st, a);
-  LRF_HIP(hipGetLastError());
-  hipLaunchKernelGGL(k_img_metrics_reduce, dim3(B), dim3(MT_NT), 0, st, a.part, a.tiles, (double)a.OH * a.OW * 3, (double)H * W * 3,
-                     ssim_mean, mse);
-  LRF_HIP(hipGetLastError());
-  return 0;
+  LRF_TRY(launch_lds(k_img_metrics, dim3(a.tiles, B), MT_NT, lds, st, a));
+  return launch(k_img_metrics_reduce, B, MT_NT, st, a.part, a.tiles, (double)a.OH * a.OW * 3, (double)H * W * 3, ssim_mean, mse);
 }

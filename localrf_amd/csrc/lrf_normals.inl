@@ -137,17 +137,17 @@ __global__ __launch_bounds__(NRM_NT) void k_normals(DField f, const float* __res
   }
 }
 
-// [lrf_workspace_bytes(R, S)] [weights R S] [rgb 3 R] [depth R] [acc R]
+// [the forward's workspace] [weights R S] [rgb 3 R] [depth R] [acc R], every piece padded to 256 bytes
 struct NormalsWs { float* w; float* rgb; float* depth; float* acc; size_t bytes; };
 static NormalsWs carve_normals(void* ws, int R, int S) {
   NormalsWs n;
-  char* p = reinterpret_cast<char*>(ws);
-  size_t off = up256(lrf_workspace_bytes(R, S));
-  n.w = reinterpret_cast<float*>(p + off);      off += up256((size_t)R * S * 4);
-  n.rgb = reinterpret_cast<float*>(p + off);    off += up256((size_t)R * 12);
-  n.depth = reinterpret_cast<float*>(p + off);  off += up256((size_t)R * 4);
-  n.acc = reinterpret_cast<float*>(p + off);    off += up256((size_t)R * 4);
-  n.bytes = off;
+  Carver c(ws);
+  c.take<char>(lrf_workspace_bytes(R, S), 256);
+  n.w = c.take<float>((size_t)R * S, 256);
+  n.rgb = c.take<float>((size_t)R * 3, 256);
+  n.depth = c.take<float>(R, 256);
+  n.acc = c.take<float>(R, 256);
+  n.bytes = c.bytes();
   return n;
 }
 
@@ -155,15 +155,13 @@ static NormalsWs carve_normals(void* ws, int R, int S) {
 
 extern "C" int lrf_density_gradient(const LrfField* f, const float* u, int64_t P, float* grad_u, float* feat, void* stream) {
   using namespace lrf;
-  if (!f || !f->cache) return set_err("lrf_density_gradient: null argument");
-  if (P < 0 || P > 256ll * 0x7fffffffll) return set_err("lrf_density_gradient: need 0 <= P <= 256 (2^31 - 1)");
+  const char* who = "lrf_density_gradient";
+  if (!f || !f->cache) return refuse(who, "null argument");
+  if (P < 0 || P > 256ll * 0x7fffffffll) return refuse(who, "need 0 <= P <= 256 (2^31 - 1)");
   if (P == 0) return 0;                                             // (empty arrays may be null)
-  if (!u || !grad_u) return set_err("lrf_density_gradient: null argument");
-  if (((uintptr_t)u | (uintptr_t)grad_u | (uintptr_t)feat) & 3) return set_err("lrf_density_gradient: float arrays must be 4-byte aligned");
-  hipLaunchKernelGGL(k_density_grad, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
-                     make_dfield(f), u, (long long)P, grad_u, feat);
-  LRF_HIP(hipGetLastError());
-  return 0;
+  if (!u || !grad_u) return refuse(who, "null argument");
+  if (misaligned(3, u, grad_u, feat)) return refuse(who, "float arrays must be 4-byte aligned");
+  return launch(k_density_grad, blocks_for(P, 256), 256, reinterpret_cast<hipStream_t>(stream), make_dfield(f), u, (long long)P, grad_u, feat);
 }
 
 extern "C" size_t lrf_normals_workspace_bytes(int32_t R, int32_t S) {
@@ -175,20 +173,18 @@ extern "C" int lrf_render_normals(const LrfField* f, const float* rays, const fl
                                   float floater_thresh, const float* blend_w, int32_t per_view, int32_t accumulate,
                                   float* normals, float* acc, void* workspace, void* stream) {
   using namespace lrf;
-  if (!f || !f->cache || !rays || !z || !normals || !workspace) return set_err("lrf_render_normals: null argument");
-  if (R <= 0 || S < 2 || S > 4096) return set_err("lrf_render_normals: need R > 0 and 2 <= S <= 4096");
-  if (blend_w && per_view < 1) return set_err("lrf_render_normals: blend_w needs per_view >= 1");
-  if (accumulate != 0 && accumulate != 1) return set_err("lrf_render_normals: accumulate must be 0 or 1");
-  if (((uintptr_t)rays | (uintptr_t)z | (uintptr_t)blend_w | (uintptr_t)normals | (uintptr_t)acc) & 3)
-    return set_err("lrf_render_normals: float arrays must be 4-byte aligned");
-  if ((uintptr_t)workspace & 255) return set_err("lrf_render_normals: workspace must be 256-byte aligned");
+  const char* who = "lrf_render_normals";
+  if (!f || !f->cache || !rays || !z || !normals || !workspace) return refuse(who, "null argument");
+  if (R <= 0 || S < 2 || S > 4096) return refuse(who, "need R > 0 and 2 <= S <= 4096");
+  if (blend_w && per_view < 1) return refuse(who, "blend_w needs per_view >= 1");
+  if (accumulate != 0 && accumulate != 1) return refuse(who, "accumulate must be 0 or 1");
+  if (misaligned(3, rays, z, blend_w, normals, acc)) return refuse(who, "float arrays must be 4-byte aligned");
+  if (misaligned(255, workspace)) return refuse(who, "workspace must be 256-byte aligned");
   const NormalsWs n = carve_normals(workspace, R, S);
-  if (const char* bad = check_fwd(f, rays, z, n.rgb, n.depth, workspace, R, S, flags)) return set_err(bad);
+  if (const char* bad = check_fwd(f, rays, z, n.rgb, n.depth, workspace, R, S, flags)) return refuse(bad);
   LRF_HIP(lds_opt_in());
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (int rc = render_fwd_pipelined(f, rays, z, R, S, flags, floater_thresh, n.rgb, n.depth, n.w, n.acc, workspace, st)) return rc;
-  hipLaunchKernelGGL(k_normals, dim3((R + NRM_NT / 64 - 1) / (NRM_NT / 64)), dim3(NRM_NT), 0, st, make_dfield(f), rays, z, R, S,
-                     n.w, n.acc, blend_w, per_view, accumulate, normals, acc);
-  LRF_HIP(hipGetLastError());
-  return 0;
+  LRF_TRY(render_fwd_pipelined(f, rays, z, R, S, flags, floater_thresh, n.rgb, n.depth, n.w, n.acc, workspace, st));
+  return launch(k_normals, blocks_for(R, NRM_NT / 64), NRM_NT, st, make_dfield(f), rays, z, R, S, n.w, n.acc, blend_w, per_view,
+                accumulate, normals, acc);
 }

@@ -1,5 +1,5 @@
 // lrf_points.inl -- rendered depth fused into ONE filtered, ordered, coloured world-space point list (included by
-// lrf_render.hip; the scan and the host helpers are lrf_compact.inl's).  V depth images [V,H,W] with their camera-to-world
+// lrf_render.hip; the scan is lrf_compact.inl's, the host helpers lrf_host.inl's).  V depth images [V,H,W] with their camera-to-world
 // matrices go in; the points of the kept pixels come out in (frame, row, column) order, the same list on every run and for
 // every launch geometry.
 //

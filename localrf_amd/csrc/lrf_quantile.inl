@@ -115,11 +115,19 @@ static bool quantile_args(const float* q, int32_t K, QuantileQ& qs) {
   return true;
 }
 
-static void launch_quantiles(const float* rays, const float* z, int R, int S, const float* w, const float* acc_in,
-                             const QuantileQ& qs, const float* blend_w, int per_view, int accumulate, float* depth, float* wsum,
-                             int32_t* index, float* acc, hipStream_t st) {
-  hipLaunchKernelGGL(k_depth_quantiles, dim3((R + QNT_NT / 64 - 1) / (QNT_NT / 64)), dim3(QNT_NT), 0, st, rays, z, R, S, w, acc_in,
-                     qs, blend_w, per_view, accumulate, depth, wsum, index, acc);
+static int launch_quantiles(const float* rays, const float* z, int R, int S, const float* w, const float* acc_in,
+                            const QuantileQ& qs, const float* blend_w, int per_view, int accumulate, float* depth, float* wsum,
+                            int32_t* index, float* acc, hipStream_t st) {
+  return launch(k_depth_quantiles, blocks_for(R, QNT_NT / 64), QNT_NT, st, rays, z, R, S, w, acc_in, qs, blend_w, per_view, accumulate,
+                depth, wsum, index, acc);
+}
+
+// what the two entry points refuse alike; leaves the quantiles in qs
+static int quantile_shape(const char* who, int R, int S, const float* q, int K, QuantileQ& qs) {
+  if (R <= 0 || S < 2 || S > 4096) return refuse(who, "need R > 0 and 2 <= S <= 4096");
+  if (K < 1 || K > QNT_MAXK) return refuse(who, "need 1 <= K <= 4 quantiles");
+  if (!quantile_args(q, K, qs)) return refuse(who, "every q must lie in (0, 1]");
+  return 0;
 }
 
 }  // namespace lrf
@@ -134,40 +142,32 @@ extern "C" int lrf_render_depth_quantiles(const LrfField* f, const float* rays, 
                                           int32_t accumulate, float* depth, float* wsum, int32_t* index, float* acc,
                                           void* workspace, void* stream) {
   using namespace lrf;
-  if (!f || !f->cache || !rays || !z || !q || !depth || !workspace) return set_err("lrf_render_depth_quantiles: null argument");
-  if (R <= 0 || S < 2 || S > 4096) return set_err("lrf_render_depth_quantiles: need R > 0 and 2 <= S <= 4096");
-  if (K < 1 || K > QNT_MAXK) return set_err("lrf_render_depth_quantiles: need 1 <= K <= 4 quantiles");
+  const char* who = "lrf_render_depth_quantiles";
+  if (!f || !f->cache || !rays || !z || !q || !depth || !workspace) return refuse(who, "null argument");
   QuantileQ qs;
-  if (!quantile_args(q, K, qs)) return set_err("lrf_render_depth_quantiles: every q must lie in (0, 1]");
-  if (blend_w && per_view < 1) return set_err("lrf_render_depth_quantiles: blend_w needs per_view >= 1");
-  if (accumulate != 0 && accumulate != 1) return set_err("lrf_render_depth_quantiles: accumulate must be 0 or 1");
-  if (accumulate && index) return set_err("lrf_render_depth_quantiles: an index cannot be accumulated (accumulate = 1 needs index = NULL)");
-  if (blend_w && !wsum) return set_err("lrf_render_depth_quantiles: blend_w needs wsum (the divisor of the blended depth)");
-  if (((uintptr_t)rays | (uintptr_t)z | (uintptr_t)blend_w | (uintptr_t)depth | (uintptr_t)wsum | (uintptr_t)index | (uintptr_t)acc) & 3)
-    return set_err("lrf_render_depth_quantiles: float and int32 arrays must be 4-byte aligned");
-  if ((uintptr_t)workspace & 255) return set_err("lrf_render_depth_quantiles: workspace must be 256-byte aligned");
+  LRF_TRY(quantile_shape(who, R, S, q, K, qs));
+  if (blend_w && per_view < 1) return refuse(who, "blend_w needs per_view >= 1");
+  if (accumulate != 0 && accumulate != 1) return refuse(who, "accumulate must be 0 or 1");
+  if (accumulate && index) return refuse(who, "an index cannot be accumulated (accumulate = 1 needs index = NULL)");
+  if (blend_w && !wsum) return refuse(who, "blend_w needs wsum (the divisor of the blended depth)");
+  if (misaligned(3, rays, z, blend_w, depth, wsum, index, acc)) return refuse(who, "float and int32 arrays must be 4-byte aligned");
+  if (misaligned(255, workspace)) return refuse(who, "workspace must be 256-byte aligned");
   const NormalsWs n = carve_normals(workspace, R, S);
-  if (const char* bad = check_fwd(f, rays, z, n.rgb, n.depth, workspace, R, S, flags)) return set_err(bad);
+  if (const char* bad = check_fwd(f, rays, z, n.rgb, n.depth, workspace, R, S, flags)) return refuse(bad);
   LRF_HIP(lds_opt_in());
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (int rc = render_fwd_pipelined(f, rays, z, R, S, flags, floater_thresh, n.rgb, n.depth, n.w, n.acc, workspace, st)) return rc;
-  launch_quantiles(rays, z, R, S, n.w, n.acc, qs, blend_w, per_view, accumulate, depth, wsum, index, acc, st);
-  LRF_HIP(hipGetLastError());
-  return 0;
+  LRF_TRY(render_fwd_pipelined(f, rays, z, R, S, flags, floater_thresh, n.rgb, n.depth, n.w, n.acc, workspace, st));
+  return launch_quantiles(rays, z, R, S, n.w, n.acc, qs, blend_w, per_view, accumulate, depth, wsum, index, acc, st);
 }
 
 // the kernel alone on caller-supplied weights (include/lrf_debug.h)
 extern "C" int lrf_depth_quantiles_from_weights(const float* w, const float* z, const float* rays, int32_t R, int32_t S, const float* q,
                                                 int32_t K, float* depth, int32_t* index, void* stream) {
   using namespace lrf;
-  if (!w || !z || !rays || !q || !depth) return set_err("lrf_depth_quantiles_from_weights: null argument");
-  if (R <= 0 || S < 2 || S > 4096) return set_err("lrf_depth_quantiles_from_weights: need R > 0 and 2 <= S <= 4096");
-  if (K < 1 || K > QNT_MAXK) return set_err("lrf_depth_quantiles_from_weights: need 1 <= K <= 4 quantiles");
+  const char* who = "lrf_depth_quantiles_from_weights";
+  if (!w || !z || !rays || !q || !depth) return refuse(who, "null argument");
   QuantileQ qs;
-  if (!quantile_args(q, K, qs)) return set_err("lrf_depth_quantiles_from_weights: every q must lie in (0, 1]");
-  if (((uintptr_t)w | (uintptr_t)z | (uintptr_t)rays | (uintptr_t)depth | (uintptr_t)index) & 3)
-    return set_err("lrf_depth_quantiles_from_weights: float and int32 arrays must be 4-byte aligned");
-  launch_quantiles(rays, z, R, S, w, nullptr, qs, nullptr, 1, 0, depth, nullptr, index, nullptr, reinterpret_cast<hipStream_t>(stream));
-  LRF_HIP(hipGetLastError());
-  return 0;
+  LRF_TRY(quantile_shape(who, R, S, q, K, qs));
+  if (misaligned(3, w, z, rays, depth, index)) return refuse(who, "float and int32 arrays must be 4-byte aligned");
+  return launch_quantiles(rays, z, R, S, w, nullptr, qs, nullptr, 1, 0, depth, nullptr, index, nullptr, reinterpret_cast<hipStream_t>(stream));
 }

@@ -186,13 +186,23 @@ static size_t l1_lpart_floats(const int32_t hw[3], const int32_t ll[3]) {       
   for (int p = 0; p < 3; ++p) n += (size_t)((hw[p] + l1_qchunk(hw[p]) - 1) / l1_qchunk(hw[p])) * LRF_CD * (size_t)ll[p];
   return n;
 }
+// [density features of the n lattice points] [one partial per forward block] [the line gradients' partial blocks]; the size
+// the caller is told is c.at + 1024
+struct L1Ws { float* dfeat; float* partial; float* lpart; };
+static L1Ws carve_l1(Carver& c, const int32_t hw[3], const int32_t ll[3]) {
+  L1Ws w;
+  w.dfeat = c.take<float>((size_t)((long long)hw[0] * ll[0]));
+  w.partial = c.take<float>((size_t)device_cus() * 16);
+  w.lpart = c.take<float>(l1_lpart_floats(hw, ll));
+  return w;
+}
 
 }  // namespace lrf
 
 extern "C" size_t lrf_density_l1_workspace(const int32_t hw[3], const int32_t ll[3]) {
-  using namespace lrf;
-  const long long n = (long long)hw[0] * ll[0];
-  return sizeof(float) * ((size_t)n + (size_t)device_cus() * 16 + l1_lpart_floats(hw, ll)) + 1024;
+  lrf::Carver c(nullptr);
+  lrf::carve_l1(c, hw, ll);
+  return c.at + 1024;
 }
 
 extern "C" int lrf_density_l1_fwd(const float* const plane[3], const float* const line[3], const int32_t hw[3],
@@ -201,33 +211,32 @@ extern "C" int lrf_density_l1_fwd(const float* const plane[3], const float* cons
   using namespace lrf;
   L1Geo G;
   if (!plane || !line || !hw || !ll || !workspace || !out || l1_geo(plane, line, hw, ll, G))
-    return set_err("lrf_density_l1_fwd: null argument or planes/lines that do not span one lattice");
-  float* dfeat = static_cast<float*>(workspace);
-  float* partial = dfeat + G.n;
+    return refuse("lrf_density_l1_fwd", "null argument or planes/lines that do not span one lattice");
+  Carver c(workspace);
+  const L1Ws w = carve_l1(c, hw, ll);
   const int nb = l1_blocks(G.n);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(k_l1_fwd, dim3(nb), dim3(L1_TPB), 0, st, G, density_shift, relu, dfeat, partial);
-  hipLaunchKernelGGL(k_l1_mean, dim3(1), dim3(L1_TPB), 0, st, partial, nb, G.n, out);
-  LRF_HIP(hipGetLastError());
-  return 0;
+  LRF_TRY(launch(k_l1_fwd, nb, L1_TPB, st, G, density_shift, relu, w.dfeat, w.partial));
+  return launch(k_l1_mean, 1, L1_TPB, st, w.partial, nb, G.n, out);
 }
 
 static int density_l1_bwd_impl(const float* const plane[3], const float* const line[3], const int32_t hw[3],
                                const int32_t ll[3], const void* workspace, const float* g_out,
                                float* const g_plane[3], float* const g_line[3], void* stream, int acc_out) {
   using namespace lrf;
+  const char* who = "lrf_density_l1_bwd";
   L1Geo G;
   if (!plane || !line || !hw || !ll || !workspace || !g_out || !g_plane || !g_line || l1_geo(plane, line, hw, ll, G))
-    return set_err("lrf_density_l1_bwd: null argument or planes/lines that do not span one lattice");
-  const float* dfeat = static_cast<const float*>(workspace);
-  float* lpart = const_cast<float*>(dfeat) + G.n + (size_t)device_cus() * 16;
+    return refuse(who, "null argument or planes/lines that do not span one lattice");
+  Carver c(const_cast<void*>(workspace));
+  const L1Ws w = carve_l1(c, hw, ll);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   L1Out out;
   L1Blk Bp, Bl, Br;                                          // block offsets of the plane / line / reduce launches
   Bp.first[0] = Bl.first[0] = Br.first[0] = 0;
   size_t off = 0;
   for (int p = 0; p < 3; ++p) {
-    if (!g_plane[p] || !g_line[p]) return set_err("lrf_density_l1_bwd: null gradient pointer");
+    if (!g_plane[p] || !g_line[p]) return refuse(who, "null gradient pointer");
     out.plane[p] = g_plane[p]; out.line[p] = g_line[p];
     const int qc = l1_qchunk(G.hw[p]), nchunk = (G.hw[p] + qc - 1) / qc;
     Bp.first[p + 1] = Bp.first[p] + (G.hw[p] + L1_TPB / 64 - 1) / (L1_TPB / 64);
@@ -238,11 +247,9 @@ static int density_l1_bwd_impl(const float* const plane[3], const float* const l
     Bp.lpart_off[p] = Bl.lpart_off[p] = Br.lpart_off[p] = off;
     off += (size_t)nchunk * LRF_CD * (size_t)G.ll[p];
   }
-  hipLaunchKernelGGL(k_l1_bwd_plane, dim3(Bp.first[3]), dim3(L1_TPB), 0, st, G, Bp, dfeat, g_out, out, acc_out);
-  hipLaunchKernelGGL(k_l1_bwd_line, dim3(Bl.first[3]), dim3(L1_TPB), 0, st, G, Bl, dfeat, lpart);
-  hipLaunchKernelGGL(k_l1_bwd_line_reduce, dim3(Br.first[3]), dim3(L1_TPB), 0, st, G, Br, lpart, g_out, out, acc_out);
-  LRF_HIP(hipGetLastError());
-  return 0;
+  LRF_TRY(launch(k_l1_bwd_plane, Bp.first[3], L1_TPB, st, G, Bp, w.dfeat, g_out, out, acc_out));
+  LRF_TRY(launch(k_l1_bwd_line, Bl.first[3], L1_TPB, st, G, Bl, w.dfeat, w.lpart));
+  return launch(k_l1_bwd_line_reduce, Br.first[3], L1_TPB, st, G, Br, w.lpart, g_out, out, acc_out);
 }
 extern "C" int lrf_density_l1_bwd(const float* const plane[3], const float* const line[3], const int32_t hw[3],
                                   const int32_t ll[3], const void* workspace, const float* g_out,
@@ -342,13 +349,18 @@ static int tv_table(const LrfTvSeg* segs, int count, TvTable& tab) {
   tab.count = count;
   return blocks;
 }
+// [one float2 per block of k_tv_fwd]; the size the caller is told is c.at + 256
+static float2* carve_tv(Carver& c, int blocks) { return c.take<float2>(blocks); }
 
 }  // namespace lrf
 
 extern "C" size_t lrf_tv_workspace(const LrfTvSeg* segs, int32_t count) {
   lrf::TvTable tab;
   const int blocks = lrf::tv_table(segs, count, tab);
-  return blocks < 0 ? 0 : sizeof(float) * 2 * (size_t)blocks + 256;
+  if (blocks < 0) return 0;
+  lrf::Carver c(nullptr);
+  lrf::carve_tv(c, blocks);
+  return c.at + 256;
 }
 
 extern "C" int lrf_tv_loss_fwd(const LrfTvSeg* segs, int32_t count, float weight, void* workspace, float* out,
@@ -356,21 +368,20 @@ extern "C" int lrf_tv_loss_fwd(const LrfTvSeg* segs, int32_t count, float weight
   using namespace lrf;
   TvTable tab;
   const int blocks = tv_table(segs, count, tab);
-  if (blocks < 0 || !workspace || !out) return set_err("lrf_tv_loss_fwd: null argument or bad tensor table");
+  if (blocks < 0 || !workspace || !out) return refuse("lrf_tv_loss_fwd", "null argument or bad tensor table");
+  Carver c(workspace);
+  float2* part = carve_tv(c, blocks);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(k_tv_fwd, dim3(blocks), dim3(L1_TPB), 0, st, tab, static_cast<float2*>(workspace));
-  hipLaunchKernelGGL(k_tv_final, dim3(1), dim3(64), 0, st, tab, static_cast<const float2*>(workspace), weight, out);
-  LRF_HIP(hipGetLastError());
-  return 0;
+  LRF_TRY(launch(k_tv_fwd, blocks, L1_TPB, st, tab, part));
+  return launch(k_tv_final, 1, 64, st, tab, part, weight, out);
 }
 
 extern "C" int lrf_tv_loss_bwd(const LrfTvSeg* segs, int32_t count, float weight, const float* g_out, void* stream) {
   using namespace lrf;
   TvTable tab;
   const int blocks = tv_table(segs, count, tab);
-  if (blocks < 0 || !g_out) return set_err("lrf_tv_loss_bwd: null argument or bad tensor table");
-  for (int i = 0; i < count; ++i) if (!segs[i].g) return set_err("lrf_tv_loss_bwd: null gradient pointer");
-  hipLaunchKernelGGL(k_tv_bwd, dim3(blocks), dim3(L1_TPB), 0, reinterpret_cast<hipStream_t>(stream), tab, weight, g_out);
-  LRF_HIP(hipGetLastError());
-  return 0;
+  const char* who = "lrf_tv_loss_bwd";
+  if (blocks < 0 || !g_out) return refuse(who, "null argument or bad tensor table");
+  for (int i = 0; i < count; ++i) if (!segs[i].g) return refuse(who, "null gradient pointer");
+  return launch(k_tv_bwd, blocks, L1_TPB, reinterpret_cast<hipStream_t>(stream), tab, weight, g_out);
 }

@@ -1,6 +1,10 @@
 // lrf_render.hip -- gfx950 (MI355X / CDNA4) forward kernels of the localrf render path and the C ABI declared in
 // include/lrf.h.  One translation unit (this file + the .inl files it includes), built without the SLP vectoriser
-// (lrf_tu.h says why).
+// (lrf_tu.h says why).  In include order: lrf_common.h, lrf_host.inl (the host helpers of every entry point: refuse, launch,
+// misaligned, Carver), lrf_tiles.inl, lrf_shade3.inl (+ lrf_shade3_kernel.inl), lrf_generic.inl, lrf_backward.inl (+ lrf_train32.inl),
+// lrf_scene / adam / losses / metrics / frames / select / evalgeo / encode .inl, lrf_compact.inl and the geometry files
+// (lrf_points, lrf_mesh, lrf_mesh_clean / simplify / smooth / raster / texture / distance, lrf_tsdf_blocks), lrf_reg.inl,
+// lrf_mask.inl, and behind the C ABI of this file lrf_normals.inl and lrf_quantile.inl.
 //
 // Pipeline of lrf_render_fwd (one field, R rays x S samples), two launches, no atomics on floats:
 //   k_march      one wavefront per ray: contracted sampling, density VM gather (channel-last planes, 2 x float4 per tap,
@@ -23,20 +27,13 @@
 #include <stdlib.h>
 #include <mutex>
 #include "lrf_common.h"
+#include "lrf_host.inl"
 
 namespace lrf {
 
 constexpr int ITEM = 16;          // compact samples per shade work item = one 16-column MFMA tile
 
-thread_local char g_err[512] = "";       // one error text per thread for the whole library (lrf_error_slot)
-static int set_err(const char* msg, hipError_t e = hipSuccess) {
-  char* slot = lrf_error_slot();
-  if (e != hipSuccess) snprintf(slot, 512, "%s: %s", msg, hipGetErrorString(e));
-  else snprintf(slot, 512, "%s", msg);
-  return 1;
-}
-#define LRF_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return set_err(#call, e_); } while (0)
-#define LRF_TRY(call) do { if (int rc_ = (call)) return rc_; } while (0)     // a callee that has already set the error
+thread_local char g_err[512] = "";       // one error text per thread for the whole library (lrf_error_slot; written by refuse, lrf_host.inl)
 
 // ---------------------------------------------------------------------------- pack
 // [C,H,W] -> [H,W,CS] channel-last; app=1: padded appearance layout (slot app_pc(c), zero pads)
@@ -1006,23 +1003,21 @@ struct Workspace {
   int* perm; float* rays_s;  // ray sorting: slot -> ray, sorted copy of the rays
   int pmax; size_t bytes;
 };
-static size_t up256(size_t x) { return (x + 255) & ~size_t(255); }
-static Workspace carve(void* ws, int R, int S) {
+static Workspace carve(void* ws, int R, int S) {     // every piece padded to 256 bytes
   Workspace w;
-  char* p = reinterpret_cast<char*>(ws);
-  size_t off = 0;
+  Carver c(ws);
   w.pmax = 2 * ((S + ITEM3 - 1) / ITEM3);             // partial slots per ray: enough for 16-sample tiles, 32-sample tiles and the training rows (two 16-row tiles per 32-sample tile)
-  w.toff  = reinterpret_cast<int*>(p + off);       off += up256((size_t)(R + 1) * 4);
-  w.ncomp = reinterpret_cast<int*>(p + off);       off += up256((size_t)R * 4);
-  w.acc   = reinterpret_cast<float*>(p + off);     off += up256((size_t)R * 4);
-  w.cidx  = reinterpret_cast<uint16_t*>(p + off);  off += up256((size_t)R * S * 2);   // (k_shade3 reads aligned dwords of it: an odd R * S ends 2 bytes short of a dword, inside the padding)
-  w.cw    = reinterpret_cast<float*>(p + off);     off += up256((size_t)R * S * 4);
-  w.part  = reinterpret_cast<float*>(p + off);     off += up256((size_t)R * w.pmax * 12);
-  w.rdir  = reinterpret_cast<float*>(p + off);     off += up256((size_t)R * 16);
-  w.perm  = reinterpret_cast<int*>(p + off);       off += up256((size_t)R * 4);
-  w.rays_s = reinterpret_cast<float*>(p + off);    off += up256((size_t)R * 24);
-  w.gsum  = reinterpret_cast<int*>(p + off);       off += up256((size_t)((R + 3) / 4) * 4);
-  w.bytes = off;
+  w.toff  = c.take<int>((size_t)R + 1, 256);
+  w.ncomp = c.take<int>(R, 256);
+  w.acc   = c.take<float>(R, 256);
+  w.cidx  = c.take<uint16_t>((size_t)R * S, 256);     // (k_shade3 reads aligned dwords of it: an odd R * S ends 2 bytes short of a dword, inside the padding)
+  w.cw    = c.take<float>((size_t)R * S, 256);
+  w.part  = c.take<float>((size_t)R * w.pmax * 3, 256);
+  w.rdir  = c.take<float>((size_t)R * 4, 256);
+  w.perm  = c.take<int>(R, 256);
+  w.rays_s = c.take<float>((size_t)R * 6, 256);
+  w.gsum  = c.take<int>((R + 3) / 4, 256);
+  w.bytes = c.bytes();
   return w;
 }
 
@@ -1338,24 +1333,22 @@ void lrf_debug_set_march_rays(int rays) { g_march_rays = (rays == 4 || rays == 8
 void lrf_debug_set_lds_toff(int on) { g_no_lds_toff = on ? 0 : 1; }
 int lrf_debug_tile_ranges(const int32_t* ncomp, int32_t R, int32_t G, int32_t nb, int32_t* gsum, int32_t* ranges,
                           int32_t* toff_out, int32_t* nc_out, void* stream) {
-  if (!ncomp || !gsum || !ranges || !toff_out || !nc_out) return set_err("lrf_debug_tile_ranges: null argument");
-  if (R <= 0 || nb <= 0 || (G != 4 && G != 8 && G != 16)) return set_err("lrf_debug_tile_ranges: need R > 0, nb > 0 and G in {4, 8, 16}");
+  const char* who = "lrf_debug_tile_ranges";
+  if (!ncomp || !gsum || !ranges || !toff_out || !nc_out) return refuse(who, "null argument");
+  if (R <= 0 || nb <= 0 || (G != 4 && G != 8 && G != 16)) return refuse(who, "need R > 0, nb > 0 and G in {4, 8, 16}");
   const size_t lds = (size_t)(R + 1) * sizeof(int) + (size_t)R * sizeof(unsigned short) + 16;
-  if (lds > 64 * 1024) return set_err("lrf_debug_tile_ranges: R too large for 64 KB of LDS");
-  if ((R + G - 1) / G > 512 * TILE_GPT) return set_err("lrf_debug_tile_ranges: more groups than one workgroup scans");
+  if (lds > 64 * 1024) return refuse(who, "R too large for 64 KB of LDS");
+  const unsigned NG = blocks_for(R, G);
+  if (NG > 512 * TILE_GPT) return refuse(who, "more groups than one workgroup scans");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int NG = (R + G - 1) / G;
-  hipLaunchKernelGGL(k_group_tiles, dim3((NG + 255) / 256), dim3(256), 0, st, ncomp, R, G, gsum);
-  hipLaunchKernelGGL(k_tile_ranges_dbg, dim3(nb), dim3(512), lds, st, gsum, ncomp, R, G, reinterpret_cast<int4*>(ranges), toff_out, nc_out);
-  LRF_HIP(hipGetLastError());
-  return 0;
+  LRF_TRY(launch(k_group_tiles, blocks_for(NG, 256), 256, st, ncomp, R, G, gsum));
+  return launch_lds(k_tile_ranges_dbg, nb, 512, lds, st, gsum, ncomp, R, G, reinterpret_cast<int4*>(ranges), toff_out, nc_out);
 }
 int lrf_debug_tile_reduce(const float* in, int32_t T, float* join, float* sum, void* stream) {
-  if (!in || !join || !sum) return set_err("lrf_debug_tile_reduce: null argument");
-  if (T <= 0) return set_err("lrf_debug_tile_reduce: need T > 0");
-  hipLaunchKernelGGL(k_tile_reduce_dbg, dim3(T), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), in, join, sum);
-  LRF_HIP(hipGetLastError());
-  return 0;
+  const char* who = "lrf_debug_tile_reduce";
+  if (!in || !join || !sum) return refuse(who, "null argument");
+  if (T <= 0) return refuse(who, "need T > 0");
+  return launch(k_tile_reduce_dbg, T, 64, reinterpret_cast<hipStream_t>(stream), in, join, sum);
 }
 #ifdef LRF_SCATTER_PROF
 int lrf_debug_scatter_prof(unsigned long long* host_out /* [2][2048][12] */) {
@@ -1382,7 +1375,7 @@ char* lrf_error_slot(void) { return g_err; }
 size_t lrf_cache_bytes(const int32_t grid[3]) { return make_layout(grid).total * sizeof(float); }
 
 int lrf_pack_field(const LrfParams* p, void* cache, void* stream) {
-  if (!p || !cache) return set_err("lrf_pack_field: null argument");
+  if (!p || !cache) return refuse("lrf_pack_field", "null argument");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const Layout L = make_layout(p->grid);
   float* base = reinterpret_cast<float*>(cache);
@@ -1403,9 +1396,7 @@ int lrf_pack_field(const LrfParams* p, void* cache, void* stream) {
   pm.mlp = base + L.mlp; pm.mlpb = reinterpret_cast<uint32_t*>(base + L.mlpb); pm.mlpw = reinterpret_cast<uint32_t*>(base + L.mlpw);
   pm.mlpwt = reinterpret_cast<uint32_t*>(base + L.mlpwt);
   pm.mode = gen_is_default(p->fea_pe, p->view_pe, p->feature_c ? p->feature_c : LRF_FEATC) ? 0 : 1;   // the generic engine reads the parameter tensors themselves
-  hipLaunchKernelGGL(k_pack_planes, dim3((wmax + 127) / 128, hmax, 19), dim3(128), 0, st, tab, *p, pm, 0);
-  LRF_HIP(hipGetLastError());
-  return 0;
+  return launch(k_pack_planes, dim3(blocks_for(wmax, 128), hmax, 19), 128, st, tab, *p, pm, 0);
 }
 
 // Large batches (full-frame evaluation: renderer.py:65-77 renders an image 4096 rays at a time) go through the two kernels
@@ -1617,53 +1608,40 @@ int lrf_render_fwd_profile(const LrfField* f, const float* rays, const float* z,
 }
 
 int lrf_density_feature(const LrfField* f, const float* u, int32_t P, float* out, void* stream) {
-  if (!f || !f->cache || !u || !out) return set_err("lrf_density_feature: null argument");
+  if (!f || !f->cache || !u || !out) return refuse("lrf_density_feature", "null argument");
   if (P <= 0) return 0;
-  hipLaunchKernelGGL(k_density_feature, dim3((P + 255) / 256), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
-                     make_dfield(f), u, P, out);
-  LRF_HIP(hipGetLastError());
-  return 0;
+  return launch(k_density_feature, blocks_for(P, 256), 256, reinterpret_cast<hipStream_t>(stream), make_dfield(f), u, P, out);
 }
 
 int lrf_app_feature(const LrfField* f, const float* u, int32_t P, float* out, void* stream) {
-  if (!f || !f->cache || !u || !out || !f->basis) return set_err("lrf_app_feature: null argument");
+  if (!f || !f->cache || !u || !out || !f->basis) return refuse("lrf_app_feature", "null argument");
   if (P <= 0) return 0;
-  hipLaunchKernelGGL(k_app_feature, dim3((P + 127) / 128), dim3(128), 0, reinterpret_cast<hipStream_t>(stream),
-                     make_dfield(f), u, P, out);
-  LRF_HIP(hipGetLastError());
-  return 0;
+  return launch(k_app_feature, blocks_for(P, 128), 128, reinterpret_cast<hipStream_t>(stream), make_dfield(f), u, P, out);
 }
 
 int lrf_sample_ray_aabb(const float* rays, const float aabb[6], float step_size, float near_, float far_,
                         const float* jitter, int32_t R, int32_t N, float* pts, float* t, uint8_t* inside,
                         void* stream) {
-  if (!rays || !aabb || !pts || !t || !inside) return set_err("lrf_sample_ray_aabb: null argument");
+  if (!rays || !aabb || !pts || !t || !inside) return refuse("lrf_sample_ray_aabb", "null argument");
   const size_t n = (size_t)R * N;
   if (!n) return 0;
-  hipLaunchKernelGGL(k_sample_ray_aabb, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
-                     rays, aabb[0], aabb[1], aabb[2], aabb[3], aabb[4], aabb[5], step_size, near_, far_,
-                     jitter, R, N, pts, t, inside);
-  LRF_HIP(hipGetLastError());
-  return 0;
+  return launch(k_sample_ray_aabb, (unsigned)((n + 255) / 256), 256, reinterpret_cast<hipStream_t>(stream),
+                rays, aabb[0], aabb[1], aabb[2], aabb[3], aabb[4], aabb[5], step_size, near_, far_, jitter, R, N, pts, t, inside);
 }
 
 int lrf_z_schedule(int32_t h, const float* u1, const float* u2, float* z, void* stream) {
-  if (h <= 0 || !z) return set_err("lrf_z_schedule: need h > 0 and an output of 2 h floats");
-  if ((u1 == nullptr) != (u2 == nullptr)) return set_err("lrf_z_schedule: both jitters or none");
-  hipLaunchKernelGGL(k_z_schedule, dim3((unsigned)((h + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), h, u1, u2, z);
-  LRF_HIP(hipGetLastError());
-  return 0;
+  const char* who = "lrf_z_schedule";
+  if (h <= 0 || !z) return refuse(who, "need h > 0 and an output of 2 h floats");
+  if ((u1 == nullptr) != (u2 == nullptr)) return refuse(who, "both jitters or none");
+  return launch(k_z_schedule, blocks_for(h, 256), 256, reinterpret_cast<hipStream_t>(stream), h, u1, u2, z);
 }
 
 int lrf_sample_ray_contracted(const float* rays_o, const float* rays_d, const float* z, int32_t R, int32_t S,
                               float* pts, void* stream) {
-  if (!rays_o || !rays_d || !z || !pts) return set_err("lrf_sample_ray_contracted: null argument");
+  if (!rays_o || !rays_d || !z || !pts) return refuse("lrf_sample_ray_contracted", "null argument");
   const size_t n = (size_t)R * S;
   if (!n) return 0;
-  hipLaunchKernelGGL(k_sample_contracted, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
-                     rays_o, rays_d, z, R, S, pts);
-  LRF_HIP(hipGetLastError());
-  return 0;
+  return launch(k_sample_contracted, (unsigned)((n + 255) / 256), 256, reinterpret_cast<hipStream_t>(stream), rays_o, rays_d, z, R, S, pts);
 }
 
 }  // extern "C"

@@ -227,17 +227,15 @@ extern "C" int lrf_scene_rays(const int64_t* ray_ids, int32_t R, int32_t per_vie
                               int32_t W, int32_t H, int32_t fov360, float* rays, float* directions,
                               int64_t* ij, void* stream) {
   using namespace lrf;
-  if (!ray_ids || !cam2world || !world2rf || !rays || !directions || !ij) return set_err("lrf_scene_rays: null argument");
-  if (!fov360 && (!focal || !center)) return set_err("lrf_scene_rays: pinhole rays need focal and center");
-  if (R < 0 || per_view <= 0 || n_rf <= 0 || W <= 0 || H <= 0) return set_err("lrf_scene_rays: bad sizes");
-  if (R % per_view) return set_err("lrf_scene_rays: R must be a multiple of rays-per-view");
+  const char* who = "lrf_scene_rays";
+  if (!ray_ids || !cam2world || !world2rf || !rays || !directions || !ij) return refuse(who, "null argument");
+  if (!fov360 && (!focal || !center)) return refuse(who, "pinhole rays need focal and center");
+  if (R < 0 || per_view <= 0 || n_rf <= 0 || W <= 0 || H <= 0) return refuse(who, "bad sizes");
+  if (R % per_view) return refuse(who, "R must be a multiple of rays-per-view");
   if (!R) return 0;
-  hipLaunchKernelGGL(k_scene_rays, dim3((R + SCENE_TPB - 1) / SCENE_TPB), dim3(SCENE_TPB), 0,
-                     reinterpret_cast<hipStream_t>(stream), reinterpret_cast<const long long*>(ray_ids), R, per_view,
-                     cam2world, world2rf, n_rf, focal, center, W, H, fov360, rays, directions,
-                     reinterpret_cast<long long*>(ij));
-  LRF_HIP(hipGetLastError());
-  return 0;
+  return launch(k_scene_rays, blocks_for(R, SCENE_TPB), SCENE_TPB, reinterpret_cast<hipStream_t>(stream),
+                reinterpret_cast<const long long*>(ray_ids), R, per_view, cam2world, world2rf, n_rf, focal, center, W, H, fov360,
+                rays, directions, reinterpret_cast<long long*>(ij));
 }
 
 extern "C" int lrf_scene_rays_bwd(const int64_t* ray_ids, int32_t R, int32_t per_view, const float* cam2world,
@@ -245,15 +243,20 @@ extern "C" int lrf_scene_rays_bwd(const int64_t* ray_ids, int32_t R, int32_t per
                                   int32_t fov360, const float* g_rays, const float* g_directions,
                                   float* g_cam2world, float* g_intr, float* g_world2rf, void* stream) {
   using namespace lrf;
-  if (!ray_ids || !cam2world || !g_rays || !g_cam2world || !g_intr || !g_world2rf)
-    return set_err("lrf_scene_rays_bwd: null argument");
-  if (!fov360 && (!focal || !center)) return set_err("lrf_scene_rays_bwd: pinhole rays need focal and center");
-  if (R < 0 || per_view <= 0 || n_rf <= 0 || R % per_view) return set_err("lrf_scene_rays_bwd: bad sizes");
+  const char* who = "lrf_scene_rays_bwd";
+  if (!ray_ids || !cam2world || !g_rays || !g_cam2world || !g_intr || !g_world2rf) return refuse(who, "null argument");
+  if (!fov360 && (!focal || !center)) return refuse(who, "pinhole rays need focal and center");
+  if (R < 0 || per_view <= 0 || n_rf <= 0 || R % per_view) return refuse(who, "bad sizes");
   if (!R) return 0;
-  hipLaunchKernelGGL(k_scene_rays_bwd, dim3(R / per_view), dim3(SCENE_TPB), 0, reinterpret_cast<hipStream_t>(stream),
-                     reinterpret_cast<const long long*>(ray_ids), per_view, cam2world, n_rf, R, focal, center,
-                     W, H, fov360, g_rays, g_directions, g_cam2world, g_intr, g_world2rf);
-  LRF_HIP(hipGetLastError());
+  return launch(k_scene_rays_bwd, R / per_view, SCENE_TPB, reinterpret_cast<hipStream_t>(stream),
+                reinterpret_cast<const long long*>(ray_ids), per_view, cam2world, n_rf, R, focal, center,
+                W, H, fov360, g_rays, g_directions, g_cam2world, g_intr, g_world2rf);
+}
+
+// what lrf_scene_blend and lrf_scene_blend_bwd refuse alike; have_all: no required pointer is null
+static int scene_blend_args(const char* who, bool have_all, int R, int per_view, int n_rf) {
+  if (!have_all) return lrf::refuse(who, "null argument");
+  if (R < 0 || per_view <= 0 || n_rf <= 0 || R % per_view) return lrf::refuse(who, "bad sizes");
   return 0;
 }
 
@@ -261,27 +264,20 @@ extern "C" int lrf_scene_blend(const float* rgb_f, const float* depth_f, const f
                                int32_t R, int32_t per_view, int32_t n_rf, float* rgbs, float* depth, float* pre,
                                void* stream) {
   using namespace lrf;
-  if (!rgb_f || !depth_f || !blend_w || !rgbs || !depth) return set_err("lrf_scene_blend: null argument");
-  if (R < 0 || per_view <= 0 || n_rf <= 0 || R % per_view) return set_err("lrf_scene_blend: bad sizes");
+  LRF_TRY(scene_blend_args("lrf_scene_blend", rgb_f && depth_f && blend_w && rgbs && depth, R, per_view, n_rf));
   if (!R) return 0;
-  hipLaunchKernelGGL(k_scene_blend, dim3((R + SCENE_TPB - 1) / SCENE_TPB), dim3(SCENE_TPB), 0,
-                     reinterpret_cast<hipStream_t>(stream), rgb_f, depth_f, blend_w, exposure, R, per_view, n_rf,
-                     rgbs, depth, pre);
-  LRF_HIP(hipGetLastError());
-  return 0;
+  return launch(k_scene_blend, blocks_for(R, SCENE_TPB), SCENE_TPB, reinterpret_cast<hipStream_t>(stream), rgb_f, depth_f, blend_w,
+                exposure, R, per_view, n_rf, rgbs, depth, pre);
 }
 
 extern "C" int lrf_scene_blend_bwd(const float* g_rgbs, const float* g_depth, const float* pre, const float* blend_w,
                                    const float* exposure, int32_t R, int32_t per_view, int32_t n_rf,
                                    float* g_rgb_f, float* g_depth_f, float* g_exposure, void* stream) {
   using namespace lrf;
-  if (!g_rgbs || !pre || !blend_w || !g_rgb_f || !g_depth_f) return set_err("lrf_scene_blend_bwd: null argument");
-  if (R < 0 || per_view <= 0 || n_rf <= 0 || R % per_view) return set_err("lrf_scene_blend_bwd: bad sizes");
+  LRF_TRY(scene_blend_args("lrf_scene_blend_bwd", g_rgbs && pre && blend_w && g_rgb_f && g_depth_f, R, per_view, n_rf));
   if (!R) return 0;
-  hipLaunchKernelGGL(k_scene_blend_bwd, dim3(R / per_view), dim3(SCENE_TPB), 0, reinterpret_cast<hipStream_t>(stream),
-                     g_rgbs, g_depth, pre, blend_w, exposure, R, per_view, n_rf, g_rgb_f, g_depth_f, g_exposure);
-  LRF_HIP(hipGetLastError());
-  return 0;
+  return launch(k_scene_blend_bwd, R / per_view, SCENE_TPB, reinterpret_cast<hipStream_t>(stream),
+                g_rgbs, g_depth, pre, blend_w, exposure, R, per_view, n_rf, g_rgb_f, g_depth_f, g_exposure);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -365,12 +361,15 @@ __global__ void k_pose_assemble_bwd(PoseTable tab, int V, int cross_views, const
   }
 }
 
-static int pose_table(const float* const* r, const float* const* t, int V, PoseTable& tab) {
-  if (!r || V <= 0 || V > LRF_POSE_MAX) return 1;
-  for (int i = 0; i < V; ++i) {
-    if (!r[i] || (t && !t[i])) return 1;
-    tab.r[i] = r[i]; tab.t[i] = t ? t[i] : nullptr;
+// the table of a launch, and what lrf_pose_assemble and lrf_pose_assemble_bwd refuse alike; have_all: no other required pointer is null
+static int pose_table(const char* who, bool have_all, const float* const* r, const float* const* t, int V, int cross_views, PoseTable& tab) {
+  bool ok = have_all && r && V > 0 && V <= LRF_POSE_MAX;
+  for (int i = 0; ok && i < V; ++i) {
+    ok = r[i] && (!t || t[i]);
+    if (ok) { tab.r[i] = r[i]; tab.t[i] = t ? t[i] : nullptr; }
   }
+  if (!ok) return refuse(who, "null argument or V outside [1, LRF_POSE_MAX]");
+  if (cross_views && V != 3) return refuse(who, "cross_views needs exactly 3 views");
   return 0;
 }
 
@@ -380,23 +379,14 @@ extern "C" int lrf_pose_assemble(const float* const* r6d, const float* const* tr
                                  float* cam2world, void* stream) {
   using namespace lrf;
   PoseTable tab;
-  if (!trans || !cam2world || pose_table(r6d, trans, V, tab))
-    return set_err("lrf_pose_assemble: null argument or V outside [1, LRF_POSE_MAX]");
-  if (cross_views && V != 3) return set_err("lrf_pose_assemble: cross_views needs exactly 3 views");
-  hipLaunchKernelGGL(k_pose_assemble, dim3(1), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), tab, V, cross_views, cam2world);
-  LRF_HIP(hipGetLastError());
-  return 0;
+  LRF_TRY(pose_table("lrf_pose_assemble", trans && cam2world, r6d, trans, V, cross_views, tab));
+  return launch(k_pose_assemble, 1, 64, reinterpret_cast<hipStream_t>(stream), tab, V, cross_views, cam2world);
 }
 
 extern "C" int lrf_pose_assemble_bwd(const float* const* r6d, int32_t V, int32_t cross_views, const float* g_cam2world,
                                      float* g_r6d, float* g_trans, void* stream) {
   using namespace lrf;
   PoseTable tab;
-  if (!g_cam2world || !g_r6d || !g_trans || pose_table(r6d, nullptr, V, tab))
-    return set_err("lrf_pose_assemble_bwd: null argument or V outside [1, LRF_POSE_MAX]");
-  if (cross_views && V != 3) return set_err("lrf_pose_assemble_bwd: cross_views needs exactly 3 views");
-  hipLaunchKernelGGL(k_pose_assemble_bwd, dim3(1), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), tab, V, cross_views,
-                     g_cam2world, g_r6d, g_trans);
-  LRF_HIP(hipGetLastError());
-  return 0;
+  LRF_TRY(pose_table("lrf_pose_assemble_bwd", g_cam2world && g_r6d && g_trans, r6d, nullptr, V, cross_views, tab));
+  return launch(k_pose_assemble_bwd, 1, 64, reinterpret_cast<hipStream_t>(stream), tab, V, cross_views, g_cam2world, g_r6d, g_trans);
 }

@@ -55,7 +55,17 @@ __device__ __forceinline__ float sel_value(unsigned key) {
   return __uint_as_float((key & 0x80000000u) ? (key & 0x7FFFFFFFu) : ~key);
 }
 
-static size_t select_ws_bytes(int B) { return ((size_t)B * (sizeof(SelRow) + 4 * 256 * sizeof(unsigned)) + 255) & ~(size_t)255; }
+// [B rows] [B x 4 passes x 256 bins]
+struct SelectWs { SelRow* rows; unsigned* hist; size_t bytes; };
+static SelectWs carve_select(void* ws, int B) {
+  SelectWs w;
+  Carver c(ws);
+  w.rows = c.take<SelRow>(B);
+  w.hist = c.take<unsigned>((size_t)B * 4 * 256);
+  w.bytes = c.bytes();
+  return w;
+}
+static size_t select_ws_bytes(int B) { return carve_select(nullptr, B).bytes; }
 
 __global__ __launch_bounds__(SEL_NT) void k_select_init(SelectInit a, SelRow* __restrict__ rows, unsigned* __restrict__ hist) {
 #pragma clang fp contract(off)
@@ -189,24 +199,15 @@ static int select_launch(const float* x, long long stride, const int64_t* n, int
   a.B = B; a.uniform = uniform; a.mode = mode; a.q = q;
   long long max_n = 0;
   for (int b = 0; b < (uniform ? 1 : B); ++b) { a.n[b] = n[b]; max_n = n[b] > max_n ? n[b] : max_n; }
-  SelRow* rows = static_cast<SelRow*>(workspace);
-  unsigned* hist = reinterpret_cast<unsigned*>(rows + B);
-  const unsigned chunks = (unsigned)((max_n + SEL_CHUNK - 1) / SEL_CHUNK);
-  hipLaunchKernelGGL(k_select_init, dim3(B), dim3(SEL_NT), 0, st, a, rows, hist);
-  LRF_HIP(hipGetLastError());
+  const SelectWs w = carve_select(workspace, B);
+  const unsigned chunks = blocks_for(max_n, SEL_CHUNK);
+  LRF_TRY(launch(k_select_init, B, SEL_NT, st, a, w.rows, w.hist));
   for (int pass = 0; pass < 4; ++pass) {
-    hipLaunchKernelGGL(k_select_hist, dim3(chunks, B), dim3(SEL_NT), 0, st, x, stride, rows, hist, pass);
-    LRF_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_select_scan, dim3(B), dim3(SEL_NT), 0, st, rows, hist, pass);
-    LRF_HIP(hipGetLastError());
+    LRF_TRY(launch(k_select_hist, dim3(chunks, B), SEL_NT, st, x, stride, w.rows, w.hist, pass));
+    LRF_TRY(launch(k_select_scan, B, SEL_NT, st, w.rows, w.hist, pass));
   }
-  if (mode == LRF_SELECT_QUANTILE) {
-    hipLaunchKernelGGL(k_select_min, dim3(chunks, B), dim3(SEL_NT), 0, st, x, stride, rows);
-    LRF_HIP(hipGetLastError());
-  }
-  hipLaunchKernelGGL(k_select_finish, dim3((B + SEL_NT - 1) / SEL_NT), dim3(SEL_NT), 0, st, rows, B, mode, out);
-  LRF_HIP(hipGetLastError());
-  return 0;
+  if (mode == LRF_SELECT_QUANTILE) LRF_TRY(launch(k_select_min, dim3(chunks, B), SEL_NT, st, x, stride, w.rows));
+  return launch(k_select_finish, blocks_for(B, SEL_NT), SEL_NT, st, w.rows, B, mode, out);
 }
 
 static bool select_n_ok(long long n) { return n >= 1 && n < (1ll << 31); }
@@ -221,14 +222,15 @@ extern "C" size_t lrf_select_workspace_bytes(int32_t B, int64_t max_n) {
 extern "C" int lrf_select(const float* x, int64_t row_stride, const int64_t* n, int32_t n_count, int32_t B, int32_t mode, float q,
                           float* out, void* workspace, void* stream) {
   using namespace lrf;
-  if (!x || !n || !out || !workspace) return set_err("lrf_select: null argument");
-  if (B < 1 || B > 65535) return set_err("lrf_select: need 1 <= B <= 65535");
-  if (n_count != 1 && n_count != B) return set_err("lrf_select: n_count must be 1 (equal rows) or B");
-  if (n_count != 1 && B > LRF_SELECT_MAX_ROWS) return set_err("lrf_select: rows of individual lengths are limited to LRF_SELECT_MAX_ROWS");
+  const char* who = "lrf_select";
+  if (!x || !n || !out || !workspace) return refuse(who, "null argument");
+  if (B < 1 || B > 65535) return refuse(who, "need 1 <= B <= 65535");
+  if (n_count != 1 && n_count != B) return refuse(who, "n_count must be 1 (equal rows) or B");
+  if (n_count != 1 && B > LRF_SELECT_MAX_ROWS) return refuse(who, "rows of individual lengths are limited to LRF_SELECT_MAX_ROWS");
   for (int b = 0; b < n_count; ++b)
-    if (!select_n_ok(n[b])) return set_err("lrf_select: every row length n must satisfy 1 <= n < 2^31");
-  if (row_stride < 0) return set_err("lrf_select: row_stride must be >= 0");
-  if (mode != LRF_SELECT_QUANTILE && mode != LRF_SELECT_MEDIAN) return set_err("lrf_select: mode must be LRF_SELECT_QUANTILE or LRF_SELECT_MEDIAN");
-  if (mode == LRF_SELECT_QUANTILE && !(q >= 0.0f && q <= 1.0f)) return set_err("lrf_select: q must lie in [0, 1]");
+    if (!select_n_ok(n[b])) return refuse(who, "every row length n must satisfy 1 <= n < 2^31");
+  if (row_stride < 0) return refuse(who, "row_stride must be >= 0");
+  if (mode != LRF_SELECT_QUANTILE && mode != LRF_SELECT_MEDIAN) return refuse(who, "mode must be LRF_SELECT_QUANTILE or LRF_SELECT_MEDIAN");
+  if (mode == LRF_SELECT_QUANTILE && !(q >= 0.0f && q <= 1.0f)) return refuse(who, "q must lie in [0, 1]");
   return select_launch(x, row_stride, n, n_count == 1, B, mode, q, out, workspace, reinterpret_cast<hipStream_t>(stream));
 }
