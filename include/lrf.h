@@ -826,6 +826,39 @@ int lrf_mesh_smooth_bounds(const float* vertices, int64_t Nv, int32_t* out /* de
 size_t lrf_mesh_smooth_workspace_bytes(int64_t Nv, int64_t Nf);
 int lrf_mesh_smooth(const LrfMeshSmooth* m, float* vertices_out, int64_t* info /* device [8] */, void* workspace, void* stream);
 
+/* The small holes of an indexed triangle mesh found and closed (csrc/lrf_mesh_fill.inl states the semantics and the kernels).
+ * A boundary edge is a directed edge (a, b) of a valid face whose reverse no valid face holds (lrf_mesh_topology's opp == 0); a
+ * vertex is simple when exactly one boundary edge leaves it and exactly one enters it; next(a, b) is the boundary edge leaving b
+ * when b is simple.  A fillable loop is a cycle of next of 3 .. max_edges edges.  Loop r, ranked by its first edge in face
+ * order, adds vertex Nv + r at the mean of the loop's vertices -- positions in the fixed point of lrf_mesh_smooth (lo and s from
+ * lrf_mesh_smooth_bounds, the caller's to compute: lo the minima as doubles, s = 36 - the binary exponent of the largest
+ * extent), summed in int64; colours as the rounded integer mean per channel -- and every edge (a, b) of the loop, in face order,
+ * appends the face (b, a, Nv + r).  The input's vertices, colours and faces are the output's prefix, bit for bit.  Holes that
+ * touch in a vertex, rims through a non-manifold edge and loops of more than max_edges edges are left alone.  Integer counts,
+ * integer minima, exact sums: every call leaves the same bytes on every run.
+ * info (device int64 [8], written by both calls) = flag bits, degenerate faces, boundary edges, non-manifold edges, fillable
+ * loops, edges in fillable loops, the longest fillable loop, boundary edges in no fillable loop.  Flag bits: 1 a face index
+ * outside [0, Nv); 2 a vertex held by 2^20 faces or more; 8 a coordinate outside the fixed-point range of lo and s; 16 (fill) a
+ * capacity below Nv + loops or Nf + edges in loops -- nothing is written past cap_v or cap_f rows.  With a flag set the other
+ * outputs mean nothing.
+ * lrf_mesh_holes: the analysis alone.  lrf_mesh_fill: the same analysis, then vertices_out [cap_v,3], rgb8_out [cap_v,3]
+ * (nullable, with rgb8) and faces_out [cap_f,3], of which Nv + info[4] and Nf + info[5] rows are written.  All launches are
+ * queued by the one call, with no host synchronisation.  workspace: lrf_mesh_holes_workspace_bytes(Nv, Nf) bytes (0 for refused
+ * arguments) for either.
+ * Refused before any launch: null or misaligned pointers (float and int32 arrays 4 bytes; info and workspace 8), Nv < 1,
+ * Nf < 0, Nv >= 2^31, 3 Nf >= 2^31, max_edges outside [3, 4096] (the bound of the serial walk along a loop), a non-finite lo,
+ * |s| > 256, cap_v < Nv, cap_f < Nf, a capacity of 2^31 or more, rgb8 without rgb8_out or the reverse, an output that is its input. */
+typedef struct LrfMeshHoles {
+  const float* vertices; const uint8_t* rgb8 /* nullable */; const int32_t* faces;
+  int64_t Nv, Nf;
+  double lo[3];
+  int32_t max_edges, s;
+} LrfMeshHoles;
+size_t lrf_mesh_holes_workspace_bytes(int64_t Nv, int64_t Nf);
+int lrf_mesh_holes(const LrfMeshHoles* m, int64_t* info /* device [8] */, void* workspace, void* stream);
+int lrf_mesh_fill(const LrfMeshHoles* m, float* vertices_out, uint8_t* rgb8_out /* nullable */, int32_t* faces_out, int64_t cap_v,
+                  int64_t cap_f, int64_t* info /* device [8] */, void* workspace, void* stream);
+
 /* An indexed triangle mesh rasterised into V pinhole cameras, and two depth maps compared (csrc/lrf_mesh_raster.inl states the
  * coverage rule, the arithmetic and the kernels).  The inverse of lrf_tsdf_integrate: depth [V,H,W] comes out in the convention
  * that call takes (a multiple of the un-normalised pixel direction whose z is -1), 0.0 where no face was hit.  One ray per pixel

@@ -155,6 +155,11 @@ class LrfMeshSmooth(C.Structure):
                 ("s", C.c_int32), ("iterations", C.c_int32), ("pin_boundary", C.c_int32), ("reserved", C.c_int32)]
 
 
+class LrfMeshHoles(C.Structure):
+    _fields_ = [("vertices", _f), ("rgb8", C.c_void_p), ("faces", C.c_void_p), ("Nv", C.c_int64), ("Nf", C.c_int64),
+                ("lo", C.c_double * 3), ("max_edges", C.c_int32), ("s", C.c_int32)]
+
+
 LRF_AGREEMENT_MAX_TOLS = 8
 
 
@@ -320,6 +325,10 @@ SYMBOLS = {
     "lrf_mesh_smooth_bounds": (C.c_int, [_f, C.c_int64, C.c_void_p, C.c_void_p]),
     "lrf_mesh_smooth_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
     "lrf_mesh_smooth": (C.c_int, [C.POINTER(LrfMeshSmooth), _f, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "lrf_mesh_holes_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
+    "lrf_mesh_holes": (C.c_int, [C.POINTER(LrfMeshHoles), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "lrf_mesh_fill": (C.c_int, [C.POINTER(LrfMeshHoles), _f, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
+                                C.c_void_p]),
     "lrf_mesh_rasterize_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int64]),
     "lrf_mesh_rasterize": (C.c_int, [C.POINTER(LrfMeshRaster), _f, C.c_void_p, C.c_void_p, _f, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p]),

@@ -123,6 +123,23 @@ __device__ __forceinline__ bool sm_has_edge(int g0, int g1, int g2, int a, int b
   return (g0 == a && g1 == b) || (g1 == a && g2 == b) || (g2 == a && g0 == b);
 }
 
+// item 2's counts of the directed edge (a, b) of valid face f (lrf_mesh_fill.inl's boundary test is this one too)
+__device__ __forceinline__ void sm_edge_counts(const int* __restrict__ faces, int Nf, const int* __restrict__ row_start,
+                                               const int* __restrict__ row_faces, int f, int a, int b, int* opp_out, int* same_out) {
+  const int a0 = row_start[a], na = row_start[a + 1] - a0, b0 = row_start[b], nb = row_start[b + 1] - b0;
+  const int at = nb < na ? b0 : a0, n = nb < na ? nb : na;         // the shorter row, a tie goes to a
+  int opp = 0, same = 0;
+  for (int i = 0; i < n; ++i) {                                     // bounded by the row length
+    const int g = row_faces[at + i];
+    if (!in_range(g, Nf)) continue;                                    // not a row of k_sm_fill
+    const int g0 = faces[3 * (size_t)g], g1 = faces[3 * (size_t)g + 1], g2 = faces[3 * (size_t)g + 2];
+    if (sm_has_edge(g0, g1, g2, b, a)) ++opp;
+    if (g != f && sm_has_edge(g0, g1, g2, a, b)) ++same;
+  }
+  *opp_out = opp;
+  *same_out = same;
+}
+
 __global__ __launch_bounds__(SM_NT) void k_sm_edges(const int* __restrict__ faces, int Nf, int Nv, const int* __restrict__ row_start,
                                                     const int* __restrict__ row_faces, uint8_t* mask, unsigned long long* info) {
   const long long e = (long long)blockIdx.x * SM_NT + threadIdx.x;
@@ -133,16 +150,8 @@ __global__ __launch_bounds__(SM_NT) void k_sm_edges(const int* __restrict__ face
     int v[3];
     if (sm_face(faces, f, Nv, &v[0], &v[1], &v[2]) == 0) {
       const int a = v[k], b = v[k == 2 ? 0 : k + 1];
-      const int a0 = row_start[a], na = row_start[a + 1] - a0, b0 = row_start[b], nb = row_start[b + 1] - b0;
-      const int at = nb < na ? b0 : a0, n = nb < na ? nb : na;     // the shorter row, a tie goes to a
-      int opp = 0, same = 0;
-      for (int i = 0; i < n; ++i) {                                 // bounded by the row length
-        const int g = row_faces[at + i];
-        if (!in_range(g, Nf)) continue;                                // not a row of k_sm_fill
-        const int g0 = faces[3 * (size_t)g], g1 = faces[3 * (size_t)g + 1], g2 = faces[3 * (size_t)g + 2];
-        if (sm_has_edge(g0, g1, g2, b, a)) ++opp;
-        if (g != (int)f && sm_has_edge(g0, g1, g2, a, b)) ++same;
-      }
+      int opp, same;
+      sm_edge_counts(faces, Nf, row_start, row_faces, (int)f, a, b, &opp, &same);
       boundary = opp == 0;
       nonmanifold = same > 0 || opp > 1;
       if (boundary) { mask[a] = 1; mask[b] = 1; }                   // plain byte stores of one value

@@ -1312,6 +1312,7 @@ static hipError_t lds_opt_in() {
 #include "lrf_mesh_clean.inl"
 #include "lrf_mesh_simplify.inl"
 #include "lrf_mesh_smooth.inl"
+#include "lrf_mesh_fill.inl"
 #include "lrf_mesh_raster.inl"
 #include "lrf_mesh_texture.inl"
 #include "lrf_mesh_distance.inl"

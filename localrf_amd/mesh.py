@@ -11,6 +11,8 @@ lrf_tsdf_integrate and lrf_mesh_extract; csrc/lrf_tsdf_blocks.inl through lrf_ts
   topology(mesh)                                   boundary and non-manifold edge counts, the boundary-vertex mask (csrc/lrf_mesh_smooth.inl)
   vertex_normals(mesh)                             the mesh with area-weighted unit normals per vertex
   smooth(mesh, iterations, lam, mu, boundary)      the mesh after Taubin lambda|mu smoothing of its vertices
+  holes(mesh, max_edges)                           boundary edges, and the boundary loops that fill_holes would close (csrc/lrf_mesh_fill.inl)
+  fill_holes(mesh, max_edges)                      the mesh with every simple boundary loop of up to max_edges edges closed by a fan
   scene_mesh(local_tensorfs, W, H, voxel=...)      novel_views.render_poses in batches, each integrated and dropped, then extract
   pointcloud.write_ply(path, vertices, rgb8, normals=normals, faces=faces) writes the result
 
@@ -464,13 +466,132 @@ def smooth(mesh, iterations=10, lam=0.5, mu=-0.53, boundary="fixed"):
     return out
 
 
+_HOLE_KEYS = ("boundary_edges", "nonmanifold_edges", "degenerate_faces", "loops", "loop_edges", "longest_loop", "open_edges")
+MAX_HOLE_EDGES = 4096                          # HF_MAX_EDGES of csrc/lrf_mesh_fill.inl: the bound of the serial walk along a loop
+
+
+def _check_max_edges(max_edges):
+    return check_int("max_edges", max_edges, 3, MAX_HOLE_EDGES)
+
+
+def _check_fill(fill_holes):
+    """extract's option: 0 (no fill), or the max_edges of fill_holes."""
+    wording = f"0 or a max_edges value in [3, {MAX_HOLE_EDGES}]"
+    n = check_int("fill_holes", fill_holes, 0, MAX_HOLE_EDGES, wording)
+    return n if n == 0 else check_int("fill_holes", n, 3, MAX_HOLE_EDGES, wording)
+
+
+def _raise_fill_flags(flags, Nv):
+    """The flag word of csrc/lrf_mesh_fill.inl after a call's read-back."""
+    _raise_flags(flags & 7, Nv)
+    if flags & 8:
+        raise ValueError("vertices changed between the bounds pass and the hole analysis: a coordinate left the fixed-point range")
+    if flags & 16:
+        raise ValueError("the mesh changed between the hole analysis and the fill: the loops no longer fit the counted rows")
+
+
+def _holes(v, c, f, Nv, Nf, max_edges, dev):
+    """Checked arguments, Nv > 0: the bounds pass and lrf_mesh_holes, two read-backs -> (the dict of holes(), the filled-in
+    LrfMeshHoles, the workspace)."""
+    keys = torch.empty(7, dtype=torch.int32, device=dev)
+    N.launch("lrf_mesh_smooth_bounds", dev, v.data_ptr(), Nv, keys.data_ptr(), guard=True)
+    keys = keys.tolist()                                            # read-back one
+    if keys[6]:
+        raise ValueError("vertices holds a value that is not finite")
+    lo = [float_of_key(k) for k in keys[:3]]
+    extent = max(float_of_key(k) - l for k, l in zip(keys[3:6], lo))
+    a = N.LrfMeshHoles()
+    a.vertices, a.rgb8, a.faces = v.data_ptr(), None if c is None else c.data_ptr(), f.data_ptr() if Nf else None
+    a.Nv, a.Nf, a.max_edges = Nv, Nf, max_edges
+    a.s = 36 - math.frexp(extent)[1] if extent > 0.0 else 0
+    for k in range(3):
+        a.lo[k] = lo[k]
+    info = torch.empty(8, dtype=torch.int64, device=dev)
+    ws = N.workspace("lrf_mesh_holes", dev, Nv, Nf)
+    N.launch("lrf_mesh_holes", dev, C.byref(a), info.data_ptr(), ws.data_ptr(), guard=True)
+    words = [int(x) for x in info.tolist()]                         # read-back two
+    _raise_fill_flags(words[0], Nv)
+    counts = {"boundary_edges": words[2], "nonmanifold_edges": words[3], "degenerate_faces": words[1], "loops": words[4],
+              "loop_edges": words[5], "longest_loop": words[6], "open_edges": words[7]}
+    if not extent > 0.0:                                            # a box of zero extent fills nothing
+        counts.update(loops=0, loop_edges=0, longest_loop=0, open_edges=words[2])
+    return counts, a, ws
+
+
+def holes(mesh, max_edges=64):
+    """The boundary of the mesh (the dict of the module docstring) and what fill_holes(mesh, max_edges) would close
+    (csrc/lrf_mesh_fill.inl states every rule).  A boundary edge is a directed edge (a, b) of a face whose reverse no face holds
+    (topology()'s opp == 0; degenerate faces take part in nothing).  A vertex is simple when exactly one boundary edge leaves it
+    and exactly one enters it; following, from each boundary edge (a, b), the boundary edge that leaves b while b is simple
+    splits the boundary into simple cycles and open chains.  A fillable loop is a cycle of 3 .. max_edges edges.  Returns a dict
+    of Python ints: boundary_edges, nonmanifold_edges, degenerate_faces (as topology() counts them), loops (fillable loops),
+    loop_edges (the boundary edges in them), longest_loop (the edges of the longest of them) and open_edges (boundary_edges -
+    loop_edges: open chains, holes that touch in a vertex, rims through a non-manifold edge and loops above max_edges).
+    max_edges lies in [3, 4096].  Two read-backs: the 7 words of smooth()'s bounds pass (a vertex that is not finite raises
+    ValueError; in a box of zero extent nothing is fillable) and the 8 info words; a face index outside [0, Nv) is never
+    dereferenced and raises ValueError, and so does a vertex held by 2^20 faces or more."""
+    v, f, Nv, Nf = _check_incidence_mesh(mesh)
+    max_edges = _check_max_edges(max_edges)
+    v, f, _, dev = mesh_on_device(v, f, None, "the hole analysis")
+    if Nv == 0:
+        return dict.fromkeys(_HOLE_KEYS, 0)
+    return _holes(v, None, f, Nv, Nf, max_edges, dev)[0]
+
+
+def fill_holes(mesh, max_edges=64):
+    """The mesh (the dict of the module docstring) with every fillable loop of holes(mesh, max_edges) closed
+    (csrc/lrf_mesh_fill.inl states every rule).  The loops are ranked by their first boundary edge in face order; loop r adds
+    vertex Nv + r at the mean of the loop's vertices -- exact: positions are rounded to smooth()'s fixed point and summed in
+    int64, every fp64 operation around the sum rounded on its own -- with, where the mesh has rgb8, the rounded integer mean of
+    their colours, and every boundary edge (a, b) of a fillable loop appends, in face order, the face (b, a, Nv + r), wound as
+    the face that owns (a, b).  The input's vertices, colours and faces are the output's prefix, bit for bit, so the output
+    bytes are a fixed function of the input; the set of new positions does not depend on the order of the input's faces.  Every
+    edge of a filled loop is then shared by two faces, no new edge is non-manifold, and a second call with the same max_edges
+    adds nothing.  A hole is closed by a fan, whatever its shape: no minimal-area triangulation, no refinement; holes that touch
+    in a vertex, rims through a non-manifold edge and loops above max_edges (at most 4096) are left alone.
+    holes() runs first (its two read-backs: a vertex that is not finite, a face index outside [0, Nv) and a vertex held by 2^20
+    faces or more raise ValueError); then the buffers are allocated at Nv + loops and Nf + loop_edges rows and one native call
+    fills them: a third read-back.  With nothing fillable that call is skipped and the result holds the input's tensors; an
+    empty mesh returns itself.  Returns a new mesh dict -- every other entry of the input is carried over, except "normals",
+    whose rows no longer match -- with "fill": the Python ints of holes() and added_vertices and added_faces."""
+    v, f, Nv, Nf = _check_incidence_mesh(mesh)
+    c = mesh.get("rgb8")
+    max_edges = _check_max_edges(max_edges)
+    v, f, c, dev = mesh_on_device(v, f, c, "the hole filling")
+    out = dict(mesh)
+    out.pop("normals", None)
+    if Nv == 0:
+        out["fill"] = dict(dict.fromkeys(_HOLE_KEYS, 0), added_vertices=0, added_faces=0)
+        return out
+    counts, a, ws = _holes(v, c, f, Nv, Nf, max_edges, dev)
+    nv, nf = Nv + counts["loops"], Nf + counts["loop_edges"]
+    out["fill"] = dict(counts, added_vertices=nv - Nv, added_faces=nf - Nf)
+    if counts["loops"] == 0:
+        return out
+    if nv > _INT32 or 3 * nf > _INT32:
+        raise ValueError(f"the filled mesh holds {nv} vertices and {nf} faces; a mesh takes Nv < 2^31 and 3 Nf < 2^31")
+    vo = torch.empty(nv, 3, dtype=torch.float32, device=dev)
+    fo = torch.empty(nf, 3, dtype=torch.int32, device=dev)
+    co = None if c is None else torch.empty(nv, 3, dtype=torch.uint8, device=dev)
+    info = torch.empty(8, dtype=torch.int64, device=dev)
+    N.launch("lrf_mesh_fill", dev, C.byref(a), vo.data_ptr(), None if co is None else co.data_ptr(), fo.data_ptr(), nv, nf,
+             info.data_ptr(), ws.data_ptr(), guard=True)
+    words = [int(x) for x in info.tolist()]                         # read-back three (it also orders ws's release)
+    _raise_fill_flags(words[0] | (0 if (words[4], words[5]) == (nv - Nv, nf - Nf) else 16), Nv)
+    out.update(vertices=vo, faces=fo, rgb8=co, counts=(nv, nf))
+    return out
+
+
 def _filtered(mesh, min_component_faces, min_component_fraction, simplify_cell=None, origin=(0.0, 0.0, 0.0), smooth_iterations=0,
-              normals=False):
+              normals=False, fill_holes_edges=0):
     """extract's tail: the mesh itself with every option at its default -- nothing new is launched --, else
-    filter_components of it, then (the floaters having been judged at full resolution) simplify of that, then smooth of that
-    with the defaults of smooth(), then vertex_normals of the smoothed positions."""
+    filter_components of it, then fill_holes of that (the fill wants the manifold mesh at full resolution, and smooth then no
+    longer pins the closed rims), then (the floaters having been judged at full resolution) simplify of that, then smooth of
+    that with the defaults of smooth(), then vertex_normals of the smoothed positions."""
     if not (min_component_faces == 0 and min_component_fraction == 0.0):
         mesh = filter_components(mesh, min_component_faces, min_component_fraction)
+    if fill_holes_edges:
+        mesh = fill_holes(mesh, fill_holes_edges)
     if simplify_cell is not None:
         mesh = simplify(mesh, simplify_cell, origin=origin)
     if smooth_iterations:
@@ -528,20 +649,23 @@ class TsdfVolume:
         return self
 
     def extract(self, level=0.0, min_weight=1.0, max_vertices=None, max_faces=None, *, min_component_faces=0,
-                min_component_fraction=0.0, simplify_cell=None, smooth_iterations=0, normals=False):
+                min_component_fraction=0.0, simplify_cell=None, smooth_iterations=0, normals=False, fill_holes=0):
         """The mesh of the surface tsdf = level over the cells every corner of which at least min_weight frames saw:
         extract_mesh(self.tsdf, ..., weight=self.weight, rgb=self.rgb); see there for the capacities and the read-backs.
         With min_component_faces or min_component_fraction above 0 the result is filter_components(that mesh, min_faces,
         min_fraction): its small connected components are gone.  With simplify_cell (a cell edge in world units) the result
         of that is simplify(mesh, simplify_cell, origin=self.origin): the grid is anchored at the volume's origin.  With
         smooth_iterations above 0 the result of that is smooth(mesh, smooth_iterations), and with normals=True the result of
-        that is vertex_normals(mesh): the normals of the smoothed surface.  The defaults launch nothing new."""
+        that is vertex_normals(mesh): the normals of the smoothed surface.  With fill_holes (0, or a max_edges value) the
+        mesh goes through fill_holes(mesh, fill_holes) after the component filter and before simplify.  The defaults launch
+        nothing new."""
         level, min_weight = _check_extract(level, min_weight, max_vertices, max_faces)
         keep = _check_keep(min_component_faces, min_component_fraction, tuple(_NO_FILTER))
         simplify_cell = _check_simplify_cell(simplify_cell)
         post = _check_post(smooth_iterations, normals)
+        fill = _check_fill(fill_holes)
         return _filtered(_extract(self.tsdf, self.weight, self.rgb, self.origin, self.voxel, self.dims, level, min_weight,
-                                  max_vertices, max_faces), *keep, simplify_cell, self.origin, *post)
+                                  max_vertices, max_faces), *keep, simplify_cell, self.origin, *post, fill)
 
 
 BLOCK = 8                                      # lattice points per block edge
@@ -683,16 +807,17 @@ class SparseTsdfVolume:
         return self
 
     def extract(self, level=0.0, min_weight=1.0, max_vertices=None, max_faces=None, *, min_component_faces=0,
-                min_component_fraction=0.0, simplify_cell=None, smooth_iterations=0, normals=False):
+                min_component_fraction=0.0, simplify_cell=None, smooth_iterations=0, normals=False, fill_holes=0):
         """The mesh of the surface tsdf = level over the cells every corner of which is stored and was seen by at least
         min_weight frames.  Vertices come in pool order, then (z, y, x, edge) inside the block; faces in the pool order of
         the cell's lowest corner, then (z, y, x) inside the block, then (tetrahedron, triangle).  Capacities and read-backs as
         extract_mesh has them.  With zero blocks nothing is launched and the mesh is empty.  min_component_faces,
-        min_component_fraction, simplify_cell, smooth_iterations and normals as TsdfVolume.extract takes them."""
+        min_component_fraction, simplify_cell, smooth_iterations, normals and fill_holes as TsdfVolume.extract takes them."""
         level, min_weight = _check_extract(level, min_weight, max_vertices, max_faces)
         keep = _check_keep(min_component_faces, min_component_fraction, tuple(_NO_FILTER))
         simplify_cell = _check_simplify_cell(simplify_cell)
         post = _check_post(smooth_iterations, normals)
+        fill = _check_fill(fill_holes)
         dev = self.table.device
         if not self.n_blocks:
             empty = {"vertices": torch.empty(0, 3, dtype=torch.float32, device=dev), "faces": torch.empty(0, 3, dtype=torch.int32, device=dev),
@@ -706,7 +831,7 @@ class SparseTsdfVolume:
                      None if c is None else c.data_ptr(), f.data_ptr(), counts.data_ptr(), ws.data_ptr(), guard=True)
 
         return _filtered(_sized_extract(dev, self.colours, launch, max_vertices, max_faces), *keep, simplify_cell, self.origin,
-                         *post)
+                         *post, fill)
 
     def to_dense(self):
         """(tsdf, weight, rgb or None, stored) as [8Bz,8By,8Bx] tensors of the virtual lattice (rgb [...,3]; stored: bool, the
@@ -726,7 +851,7 @@ class SparseTsdfVolume:
 
 
 _MESH_KEYS = ("depth_range", "level", "min_weight", "max_vertices", "max_faces", "colours", "frames_per_call",
-              "min_component_faces", "min_component_fraction", "simplify_cell", "smooth_iterations", "normals")
+              "min_component_faces", "min_component_fraction", "simplify_cell", "smooth_iterations", "normals", "fill_holes")
 
 
 def _lattice_of_box(lo, hi, voxel):
@@ -751,7 +876,8 @@ def scene_mesh(local_tensorfs, W, H, voxel, bounds=None, poses=None, trunc=None,
     either above 0 the extracted mesh goes through filter_components, which drops its small connected components),
     simplify_cell (default None; a cell edge in world units sends the mesh, after that filter, through simplify on a grid
     anchored at the volume's origin), smooth_iterations (default 0; above 0 the mesh then goes through smooth) and normals
-    (default False; True adds vertex_normals' "normals" of the final positions) and render_poses' test_frames, frame_indices, floater_thresh, chunk.
+    (default False; True adds vertex_normals' "normals" of the final positions), fill_holes (default 0; a max_edges value sends
+    the mesh, after the component filter and before simplify, through fill_holes) and render_poses' test_frames, frame_indices, floater_thresh, chunk.
     A volume above max_bytes raises ValueError before it is allocated and, with bounds given, before anything is rendered.
     depth="median" integrates the median depth of the same frames (depth_quantiles.median_depth: one more render pass per
     batch) instead of render_poses' expected depth, which carves a phantom sheet between two surfaces a ray sees; the colours
@@ -779,6 +905,7 @@ def scene_mesh(local_tensorfs, W, H, voxel, bounds=None, poses=None, trunc=None,
     keep = _check_keep(options.get("min_component_faces", 0), options.get("min_component_fraction", 0.0), tuple(_NO_FILTER))
     simplify_cell = _check_simplify_cell(options.get("simplify_cell"))
     post = _check_post(options.get("smooth_iterations", 0), options.get("normals", False))
+    fill = _check_fill(options.get("fill_holes", 0))
     frames.check_per_call("integration")
 
     def volume_for(lo, dims):                                       # -> origin and dims, or (sparse) blocks
@@ -827,6 +954,7 @@ def scene_mesh(local_tensorfs, W, H, voxel, bounds=None, poses=None, trunc=None,
     for p, out, dmap in batches():
         vol.integrate(dmap, p, focal, center, rgb=out["rgb8"] if colours else None, depth_range=depth_range)
     mesh = vol.extract(level, min_weight, options.get("max_vertices"), options.get("max_faces"), min_component_faces=keep[0],
-                       min_component_fraction=keep[1], simplify_cell=simplify_cell, smooth_iterations=post[0], normals=post[1])
+                       min_component_fraction=keep[1], simplify_cell=simplify_cell, smooth_iterations=post[0], normals=post[1],
+                       fill_holes=fill)
     mesh["volume"] = vol
     return mesh
