@@ -165,16 +165,16 @@ def extract_mesh(values, origin, voxel, level, weight=None, rgb=None, min_weight
                     origin, voxel, dims, level, min_weight, max_vertices, max_faces)
 
 
-_NO_FILTER = {"min_component_faces": 0, "min_component_fraction": 0.0}
-
-
 def _check_rounds(max_rounds):
     return check_int("max_rounds", max_rounds, 1, wording="an integer >= 1")
 
 
-def _check_keep(min_faces, min_fraction, what=("min_faces", "min_fraction")):
-    return (check_int(what[0], min_faces, 0, wording="an integer >= 0"),
-            check_interval(what[1], min_fraction, 0.0, 1.0, "lie in [0, 1]"))
+def _check_min_faces(name, min_faces):
+    return check_int(name, min_faces, 0, wording="an integer >= 0")
+
+
+def _check_min_fraction(name, min_fraction):
+    return check_interval(name, min_fraction, 0.0, 1.0, "lie in [0, 1]")
 
 
 def _components(faces, Nv, Nf, max_rounds):
@@ -238,7 +238,7 @@ def filter_components(mesh, min_faces=0, min_fraction=0.0, max_rounds=64):
     Python ints of components() (n_components, n_with_faces, largest_faces, rounds), "threshold" and "kept", the number of
     kept components."""
     v, f, c, Nv, Nf = check_mesh(mesh)
-    min_faces, min_fraction = _check_keep(min_faces, min_fraction)
+    min_faces, min_fraction = _check_min_faces("min_faces", min_faces), _check_min_fraction("min_fraction", min_fraction)
     max_rounds = _check_rounds(max_rounds)
     v, f, c, dev = mesh_on_device(v, f, c, "the component filter")
     comp = _components(f, Nv, Nf, max_rounds)
@@ -266,11 +266,6 @@ def filter_components(mesh, min_faces=0, min_fraction=0.0, max_rounds=64):
     info["kept"] = kept
     out.update(vertices=vo[:nv], faces=fo[:nf], rgb8=None if co is None else co[:nv], counts=(nv, nf), components=info)
     return out
-
-
-def _check_simplify_cell(simplify_cell):
-    """extract's option: None, or a cell edge."""
-    return None if simplify_cell is None else check_positive("simplify_cell", simplify_cell)
 
 
 def simplify(mesh, cell, origin=(0.0, 0.0, 0.0), dedupe=True, max_bytes=1 << 30):
@@ -335,11 +330,6 @@ def simplify(mesh, cell, origin=(0.0, 0.0, 0.0), dedupe=True, max_bytes=1 << 30)
     info.update(box={"lo": lo, "dims": dims}, occupied=occupied, degenerate_faces=degenerate, duplicate_faces=duplicate)
     out.update(vertices=vo[:nv], faces=fo[:nf], rgb8=None if co is None else co[:nv], counts=(nv, nf), simplify=info)
     return out
-
-
-def _check_post(smooth_iterations, normals):
-    """extract's options: the smoothing iterations (0: none) and whether vertex normals are wanted."""
-    return check_int("smooth_iterations", smooth_iterations, 0, 1000), check_flag("normals", normals)
 
 
 def _check_incidence_mesh(mesh):
@@ -474,13 +464,6 @@ def _check_max_edges(max_edges):
     return check_int("max_edges", max_edges, 3, MAX_HOLE_EDGES)
 
 
-def _check_fill(fill_holes):
-    """extract's option: 0 (no fill), or the max_edges of fill_holes."""
-    wording = f"0 or a max_edges value in [3, {MAX_HOLE_EDGES}]"
-    n = check_int("fill_holes", fill_holes, 0, MAX_HOLE_EDGES, wording)
-    return n if n == 0 else check_int("fill_holes", n, 3, MAX_HOLE_EDGES, wording)
-
-
 def _raise_fill_flags(flags, Nv):
     """The flag word of csrc/lrf_mesh_fill.inl after a call's read-back."""
     _raise_flags(flags & 7, Nv)
@@ -582,23 +565,48 @@ def fill_holes(mesh, max_edges=64):
     return out
 
 
-def _filtered(mesh, min_component_faces, min_component_fraction, simplify_cell=None, origin=(0.0, 0.0, 0.0), smooth_iterations=0,
-              normals=False, fill_holes_edges=0):
-    """extract's tail: the mesh itself with every option at its default -- nothing new is launched --, else
-    filter_components of it, then fill_holes of that (the fill wants the manifold mesh at full resolution, and smooth then no
-    longer pins the closed rims), then (the floaters having been judged at full resolution) simplify of that, then smooth of
-    that with the defaults of smooth(), then vertex_normals of the smoothed positions."""
-    if not (min_component_faces == 0 and min_component_fraction == 0.0):
-        mesh = filter_components(mesh, min_component_faces, min_component_fraction)
-    if fill_holes_edges:
-        mesh = fill_holes(mesh, fill_holes_edges)
-    if simplify_cell is not None:
-        mesh = simplify(mesh, simplify_cell, origin=origin)
-    if smooth_iterations:
-        mesh = smooth(mesh, smooth_iterations)
-    if normals:
-        mesh = vertex_normals(mesh)
-    return mesh
+def _check_fill_option(name, max_edges):
+    """0 (no fill), or the max_edges of fill_holes."""
+    wording = f"0 or a max_edges value in [3, {MAX_HOLE_EDGES}]"
+    n = check_int(name, max_edges, 0, MAX_HOLE_EDGES, wording)
+    return n if n == 0 else check_int(name, n, 3, MAX_HOLE_EDGES, wording)
+
+
+class _Chain:
+    """The post-processing chain of an extracted mesh -- TsdfVolume.extract describes it -- and the only place that knows its
+    options: their names, defaults and checks (OPTIONS, in the order in which a call with several bad values reports them),
+    and the order in which they apply.  _Chain(mapping) reads its own keys from the mapping, checks them on the host and
+    keeps them in .options, the keywords that both extract methods take."""
+    OPTIONS = (("min_component_faces", 0, _check_min_faces),
+               ("min_component_fraction", 0.0, _check_min_fraction),
+               ("simplify_cell", None, lambda name, cell: None if cell is None else check_positive(name, cell)),
+               ("smooth_iterations", 0, lambda name, n: check_int(name, n, 0, 1000)),
+               ("normals", False, check_flag),
+               ("fill_holes", 0, _check_fill_option))
+    KEYS = tuple(name for name, _, _ in OPTIONS)
+
+    def __init__(self, options):
+        self.options = {name: check(name, options.get(name, default)) for name, default, check in self.OPTIONS}
+
+    def apply(self, mesh, origin, empty=False):
+        """The mesh itself with every option at its default -- nothing new is launched --, else filter_components of it, then
+        fill_holes of that (the fill wants the manifold mesh at full resolution, and smooth then no longer pins the closed
+        rims), then (the floaters having been judged at full resolution) simplify of that on the grid anchored at origin,
+        then smooth of that with the defaults of smooth(), then vertex_normals of the smoothed positions.  empty: the mesh of
+        a volume without blocks, which has nothing to filter, fill or simplify."""
+        o = self.options
+        if not empty:
+            if not (o["min_component_faces"] == 0 and o["min_component_fraction"] == 0.0):
+                mesh = filter_components(mesh, o["min_component_faces"], o["min_component_fraction"])
+            if o["fill_holes"]:
+                mesh = fill_holes(mesh, o["fill_holes"])
+            if o["simplify_cell"] is not None:
+                mesh = simplify(mesh, o["simplify_cell"], origin=origin)
+        if o["smooth_iterations"]:
+            mesh = smooth(mesh, o["smooth_iterations"])
+        if o["normals"]:
+            mesh = vertex_normals(mesh)
+        return mesh
 
 
 def _check_trunc_device(name, trunc, device):
@@ -652,20 +660,18 @@ class TsdfVolume:
                 min_component_fraction=0.0, simplify_cell=None, smooth_iterations=0, normals=False, fill_holes=0):
         """The mesh of the surface tsdf = level over the cells every corner of which at least min_weight frames saw:
         extract_mesh(self.tsdf, ..., weight=self.weight, rgb=self.rgb); see there for the capacities and the read-backs.
-        With min_component_faces or min_component_fraction above 0 the result is filter_components(that mesh, min_faces,
-        min_fraction): its small connected components are gone.  With simplify_cell (a cell edge in world units) the result
-        of that is simplify(mesh, simplify_cell, origin=self.origin): the grid is anchored at the volume's origin.  With
-        smooth_iterations above 0 the result of that is smooth(mesh, smooth_iterations), and with normals=True the result of
-        that is vertex_normals(mesh): the normals of the smoothed surface.  With fill_holes (0, or a max_edges value) the
-        mesh goes through fill_holes(mesh, fill_holes) after the component filter and before simplify.  The defaults launch
-        nothing new."""
+        The keyword-only options send that mesh through a chain of five steps, in this order, each skipped at its default:
+        with min_component_faces or min_component_fraction above 0, filter_components(mesh, min_faces, min_fraction): its
+        small connected components are gone.  With fill_holes (0, or a max_edges value), fill_holes(mesh, fill_holes): after
+        the component filter and before simplify.  With simplify_cell (a cell edge in world units), simplify(mesh,
+        simplify_cell, origin=self.origin): the grid is anchored at the volume's origin.  With smooth_iterations above 0,
+        smooth(mesh, smooth_iterations), and with normals=True, vertex_normals(mesh): the normals of the smoothed surface.
+        The defaults launch nothing new."""
         level, min_weight = _check_extract(level, min_weight, max_vertices, max_faces)
-        keep = _check_keep(min_component_faces, min_component_fraction, tuple(_NO_FILTER))
-        simplify_cell = _check_simplify_cell(simplify_cell)
-        post = _check_post(smooth_iterations, normals)
-        fill = _check_fill(fill_holes)
-        return _filtered(_extract(self.tsdf, self.weight, self.rgb, self.origin, self.voxel, self.dims, level, min_weight,
-                                  max_vertices, max_faces), *keep, simplify_cell, self.origin, *post, fill)
+        chain = _Chain(dict(min_component_faces=min_component_faces, min_component_fraction=min_component_fraction,
+                            simplify_cell=simplify_cell, smooth_iterations=smooth_iterations, normals=normals, fill_holes=fill_holes))
+        return chain.apply(_extract(self.tsdf, self.weight, self.rgb, self.origin, self.voxel, self.dims, level, min_weight,
+                                    max_vertices, max_faces), self.origin)
 
 
 BLOCK = 8                                      # lattice points per block edge
@@ -811,18 +817,16 @@ class SparseTsdfVolume:
         """The mesh of the surface tsdf = level over the cells every corner of which is stored and was seen by at least
         min_weight frames.  Vertices come in pool order, then (z, y, x, edge) inside the block; faces in the pool order of
         the cell's lowest corner, then (z, y, x) inside the block, then (tetrahedron, triangle).  Capacities and read-backs as
-        extract_mesh has them.  With zero blocks nothing is launched and the mesh is empty.  min_component_faces,
-        min_component_fraction, simplify_cell, smooth_iterations, normals and fill_holes as TsdfVolume.extract takes them."""
+        extract_mesh has them.  With zero blocks nothing is launched and the mesh is empty: of the chain only smooth and
+        vertex_normals see it.  The keyword-only options, their checks and the chain's order as TsdfVolume.extract has them."""
         level, min_weight = _check_extract(level, min_weight, max_vertices, max_faces)
-        keep = _check_keep(min_component_faces, min_component_fraction, tuple(_NO_FILTER))
-        simplify_cell = _check_simplify_cell(simplify_cell)
-        post = _check_post(smooth_iterations, normals)
-        fill = _check_fill(fill_holes)
+        chain = _Chain(dict(min_component_faces=min_component_faces, min_component_fraction=min_component_fraction,
+                            simplify_cell=simplify_cell, smooth_iterations=smooth_iterations, normals=normals, fill_holes=fill_holes))
         dev = self.table.device
         if not self.n_blocks:
             empty = {"vertices": torch.empty(0, 3, dtype=torch.float32, device=dev), "faces": torch.empty(0, 3, dtype=torch.int32, device=dev),
                      "rgb8": torch.empty(0, 3, dtype=torch.uint8, device=dev) if self.colours else None, "counts": (0, 0)}
-            return _filtered(empty, 0, 0.0, None, self.origin, *post)   # an empty mesh has nothing to filter or simplify
+            return chain.apply(empty, self.origin, empty=True)
         ws = N.workspace("lrf_mesh_extract_blocks", dev, self.n_blocks)
         a = self._args()
 
@@ -830,8 +834,7 @@ class SparseTsdfVolume:
             N.launch("lrf_mesh_extract_blocks", dev, C.byref(a), level, min_weight, cap_v, cap_f, v.data_ptr(),
                      None if c is None else c.data_ptr(), f.data_ptr(), counts.data_ptr(), ws.data_ptr(), guard=True)
 
-        return _filtered(_sized_extract(dev, self.colours, launch, max_vertices, max_faces), *keep, simplify_cell, self.origin,
-                         *post, fill)
+        return chain.apply(_sized_extract(dev, self.colours, launch, max_vertices, max_faces), self.origin)
 
     def to_dense(self):
         """(tsdf, weight, rgb or None, stored) as [8Bz,8By,8Bx] tensors of the virtual lattice (rgb [...,3]; stored: bool, the
@@ -850,8 +853,7 @@ class SparseTsdfVolume:
                 stored)
 
 
-_MESH_KEYS = ("depth_range", "level", "min_weight", "max_vertices", "max_faces", "colours", "frames_per_call",
-              "min_component_faces", "min_component_fraction", "simplify_cell", "smooth_iterations", "normals", "fill_holes")
+_MESH_KEYS = ("depth_range", "level", "min_weight", "max_vertices", "max_faces", "colours", "frames_per_call") + _Chain.KEYS
 
 
 def _lattice_of_box(lo, hi, voxel):
@@ -872,12 +874,10 @@ def scene_mesh(local_tensorfs, W, H, voxel, bounds=None, poses=None, trunc=None,
     beforehand and takes the box of pointcloud.fuse_points over the depths inside depth_range, grown by trunc on every
     side: one more render pass and one more read-back of the box.  trunc=None means 3 * voxel: a convenience, not a measured
     optimum -- it should exceed the depth noise of the scene.  options: depth_range, level, min_weight, max_vertices,
-    max_faces, colours (default True), frames_per_call, min_component_faces and min_component_fraction (both default 0: with
-    either above 0 the extracted mesh goes through filter_components, which drops its small connected components),
-    simplify_cell (default None; a cell edge in world units sends the mesh, after that filter, through simplify on a grid
-    anchored at the volume's origin), smooth_iterations (default 0; above 0 the mesh then goes through smooth) and normals
-    (default False; True adds vertex_normals' "normals" of the final positions), fill_holes (default 0; a max_edges value sends
-    the mesh, after the component filter and before simplify, through fill_holes) and render_poses' test_frames, frame_indices, floater_thresh, chunk.
+    max_faces, colours (default True), frames_per_call, the keyword-only options of TsdfVolume.extract (min_component_faces,
+    min_component_fraction, fill_holes, simplify_cell, smooth_iterations, normals: the chain of steps that the extracted mesh
+    goes through, described there; the defaults skip every step) and render_poses' test_frames, frame_indices,
+    floater_thresh, chunk.
     A volume above max_bytes raises ValueError before it is allocated and, with bounds given, before anything is rendered.
     depth="median" integrates the median depth of the same frames (depth_quantiles.median_depth: one more render pass per
     batch) instead of render_poses' expected depth, which carves a phantom sheet between two surfaces a ray sees; the colours
@@ -902,10 +902,7 @@ def scene_mesh(local_tensorfs, W, H, voxel, bounds=None, poses=None, trunc=None,
     level, min_weight = _check_extract(options.get("level", 0.0), options.get("min_weight", 1.0), options.get("max_vertices"),
                                        options.get("max_faces"))
     colours = bool(options.get("colours", True))
-    keep = _check_keep(options.get("min_component_faces", 0), options.get("min_component_fraction", 0.0), tuple(_NO_FILTER))
-    simplify_cell = _check_simplify_cell(options.get("simplify_cell"))
-    post = _check_post(options.get("smooth_iterations", 0), options.get("normals", False))
-    fill = _check_fill(options.get("fill_holes", 0))
+    chain = _Chain(options)
     frames.check_per_call("integration")
 
     def volume_for(lo, dims):                                       # -> origin and dims, or (sparse) blocks
@@ -953,8 +950,6 @@ def scene_mesh(local_tensorfs, W, H, voxel, bounds=None, poses=None, trunc=None,
         vol = TsdfVolume(lo, voxel, shape, trunc, lt.blending_weights.device, colours=colours)
     for p, out, dmap in batches():
         vol.integrate(dmap, p, focal, center, rgb=out["rgb8"] if colours else None, depth_range=depth_range)
-    mesh = vol.extract(level, min_weight, options.get("max_vertices"), options.get("max_faces"), min_component_faces=keep[0],
-                       min_component_fraction=keep[1], simplify_cell=simplify_cell, smooth_iterations=post[0], normals=post[1],
-                       fill_holes=fill)
+    mesh = vol.extract(level, min_weight, options.get("max_vertices"), options.get("max_faces"), **chain.options)
     mesh["volume"] = vol
     return mesh

@@ -9,17 +9,13 @@ import torch
 
 from localrf_amd import mesh, novel_views, pointcloud
 from mesh_cases import (H_ANALYTIC, closed_manifold_euler, extract_host, integrate_host, new_volume, sphere_field)
+from mesh_util import DEV, blob_volumes, forbid_render, record_launches, same_device_mesh, same_mesh, to_dev
 from novel_views_cases import scene
 from points_cases import random_case, trajectory_case
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 VOLUMES = [(1, 1, 1), (2, 2, 2), (3, 5, 4), (17, 23, 9), (33, 33, 33), (70, 3, 2)]
 CENTRE = np.array([0.1, -0.05, -3.05])
-
-
-def _t(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
 
 
 @functools.lru_cache(maxsize=None)
@@ -46,7 +42,7 @@ def _lattice_for(dims):
 def _integrate_device(dims, case, rng, colours=True, split=None):
     origin, voxel, trunc = _lattice_for(dims)
     vol = mesh.TsdfVolume(origin, voxel, dims, trunc, DEV, colours=colours)
-    d, r, p = _t(case["depth"]), _t(case["rgb8"]) if colours else None, _t(case["c2w"])
+    d, r, p = to_dev(case["depth"]), to_dev(case["rgb8"]) if colours else None, to_dev(case["c2w"])
     f, c = float(case["f"]), (float(case["cx"]), float(case["cy"]))
     V = d.shape[0]
     for i0, i1 in ((0, V),) if split is None else ((0, split), (split, V)):
@@ -69,26 +65,12 @@ def _same_volume(vol, want):
         assert np.array_equal(got.cpu().numpy().view(np.uint32), want[k].view(np.uint32)), k
 
 
-def _same_mesh(got, want):
-    """Counts, vertices (as uint32), faces and rgb8, all exact."""
-    assert got["counts"] == want["counts"], (got["counts"], want["counts"])
-    nv, nf = want["counts"]
-    assert tuple(got["vertices"].shape) == (nv, 3) and tuple(got["faces"].shape) == (nf, 3)
-    assert got["vertices"].dtype is torch.float32 and got["faces"].dtype is torch.int32
-    assert np.array_equal(got["vertices"].cpu().numpy().view(np.uint32), want["vertices"].view(np.uint32))
-    assert np.array_equal(got["faces"].cpu().numpy(), want["faces"])
-    if want["rgb8"] is None:
-        assert got["rgb8"] is None
-    else:
-        assert got["rgb8"].dtype is torch.uint8 and np.array_equal(got["rgb8"].cpu().numpy(), want["rgb8"])
-
-
 def _extract_both(vol, host, **kw):
     origin, voxel, _ = _lattice_for(vol.dims)
     got = vol.extract(**kw)
     want = extract_host(host["tsdf"], origin, voxel, level=kw.get("level", 0.0), weight=host["weight"], rgb=host["rgb"],
                         min_weight=kw.get("min_weight", 1.0))
-    _same_mesh(got, want)
+    same_mesh(got, want)
     return want["counts"]
 
 
@@ -107,7 +89,7 @@ def test_integrate_and_extract_equal_the_restatement_bit_for_bit(dims):
             # without weights every cell counts: the unobserved ones too, at tsdf = 1
             origin, voxel, _ = _lattice_for(dims)
             bare = mesh.extract_mesh(vol.tsdf, origin, voxel, 0.1)
-            _same_mesh(bare, extract_host(want["tsdf"], origin, voxel, level=0.1))
+            same_mesh(bare, extract_host(want["tsdf"], origin, voxel, level=0.1))
             print(f"{dims} {name} range {rng}: seen {int((want['weight'] > 0).sum())}, meshes {counts} {bare['counts']}")
             faces += counts[0][1]
     if dims == (1, 1, 1):
@@ -125,17 +107,17 @@ def test_extract_the_analytic_sphere_with_holes_levels_and_colours():
     w = rng.integers(0, 4, fld.shape).astype(np.float32)
     w[:, :, :12] = 3
     o = (0.0, 0.0, 0.0)
-    got = mesh.extract_mesh(_t(fld), o, H_ANALYTIC, 0.0)
-    _same_mesh(got, extract_host(fld, o, H_ANALYTIC))
+    got = mesh.extract_mesh(to_dev(fld), o, H_ANALYTIC, 0.0)
+    same_mesh(got, extract_host(fld, o, H_ANALYTIC))
     assert closed_manifold_euler({"vertices": got["vertices"].cpu().numpy(), "faces": got["faces"].cpu().numpy()}) == 2
     for level, mw in ((0.0, 1.0), (0.05, 2.0), (-0.02, 3.0)):
-        got = mesh.extract_mesh(_t(fld), o, H_ANALYTIC, level, weight=_t(w), rgb=_t(rgb), min_weight=mw)
+        got = mesh.extract_mesh(to_dev(fld), o, H_ANALYTIC, level, weight=to_dev(w), rgb=to_dev(rgb), min_weight=mw)
         want = extract_host(fld, o, H_ANALYTIC, level=level, weight=w, rgb=rgb, min_weight=mw)
-        _same_mesh(got, want)
+        same_mesh(got, want)
         assert 0 < want["counts"][1]
     one = mesh.extract_mesh(torch.zeros(1, 1, 1, device=DEV), o, 1.0, 0.5)
     assert one["counts"] == (0, 0) and tuple(one["faces"].shape) == (0, 3)
-    line = mesh.extract_mesh(_t(np.linspace(-1, 1, 300, dtype=np.float32).reshape(1, 1, 300)), o, 1.0, 0.0)
+    line = mesh.extract_mesh(to_dev(np.linspace(-1, 1, 300, dtype=np.float32).reshape(1, 1, 300)), o, 1.0, 0.0)
     assert line["counts"] == (0, 0)                                     # crossings, but no cell contains them
 
 
@@ -175,11 +157,11 @@ def test_capacity_one_too_small_raises_with_the_true_counts():
     o = (0.0, 0.0, 0.0)
     want = extract_host(fld, o, H_ANALYTIC)
     nv, nf = want["counts"]
-    _same_mesh(mesh.extract_mesh(_t(fld), o, H_ANALYTIC, 0.0, max_vertices=nv, max_faces=nf), want)
-    _same_mesh(mesh.extract_mesh(_t(fld), o, H_ANALYTIC, 0.0, max_vertices=nv + 100, max_faces=None), want)
+    same_mesh(mesh.extract_mesh(to_dev(fld), o, H_ANALYTIC, 0.0, max_vertices=nv, max_faces=nf), want)
+    same_mesh(mesh.extract_mesh(to_dev(fld), o, H_ANALYTIC, 0.0, max_vertices=nv + 100, max_faces=None), want)
     for cap_v, cap_f in ((nv - 1, nf), (nv, nf - 1), (5, 7), (0, 0)):
         with pytest.raises(ValueError, match=f"holds {nv} vertices and {nf} faces") as ei:
-            mesh.extract_mesh(_t(fld), o, H_ANALYTIC, 0.0, max_vertices=cap_v, max_faces=cap_f)
+            mesh.extract_mesh(to_dev(fld), o, H_ANALYTIC, 0.0, max_vertices=cap_v, max_faces=cap_f)
         part = ei.value.partial                                         # the rows inside capacity are the mesh's first rows
         assert part["counts"] == (nv, nf)
         assert np.array_equal(part["vertices"].cpu().numpy().view(np.uint32), want["vertices"][:cap_v].view(np.uint32))
@@ -230,10 +212,7 @@ def test_scene_mesh_equals_integrate_and_extract_over_render_poses(monkeypatch):
     want = ref.extract(min_weight=2.0)
     assert got["volume"].origin == tuple(lo) and got["rgb8"] is None and got["counts"] == want["counts"]
     assert torch.equal(got["vertices"], want["vertices"]) and torch.equal(got["faces"], want["faces"])
-
-    def forbidden(*a, **k):
-        raise AssertionError("a launch path was reached before the max_bytes guard")
-    monkeypatch.setattr(novel_views, "render_poses", forbidden)
+    forbid_render(monkeypatch)
     with pytest.raises(ValueError, match="max_bytes"):
         mesh.scene_mesh(lt, W, H, voxel=voxel, bounds=box, max_bytes=1000)
 
@@ -258,3 +237,54 @@ def test_scene_mesh_does_not_depend_on_frames_per_call(kind):
             assert torch.equal(got[k], want[k]), (extra, k)
         if kind.get("sparse"):
             assert torch.equal(got["volume"].coords, want["volume"].coords) and torch.equal(got["volume"].table, want["volume"].table)
+
+
+ROUND = "lrf_mesh_components_round"
+
+
+def _launches_of(names, info):
+    """The recorded symbol names with every run of component rounds as one entry.  How many rounds the labels take depends on
+    the scheduling of the hooks (csrc/lrf_mesh_clean.inl), so two runs may differ in that number and in nothing else: each
+    run's own count is checked against the rounds it reports."""
+    assert names.count(ROUND) == info["rounds"]
+    return [n for k, n in enumerate(names) if n != ROUND or names[k - 1] != ROUND]
+
+
+@pytest.mark.parametrize("which", ("dense", "sparse"))
+def test_every_chain_option_at_once_equals_the_five_calls_by_hand(which, monkeypatch):
+    """extract with all six options on is filter_components, fill_holes, simplify at the volume's origin, smooth and
+    vertex_normals of extract(), in that order: the same bytes from the same launches."""
+    vol = blob_volumes()[which == "sparse"]
+    cell = 2 * H_ANALYTIC
+    names = record_launches(monkeypatch)
+    got = vol.extract(min_component_faces=1, min_component_fraction=0.03, fill_holes=64, simplify_cell=cell, smooth_iterations=2,
+                      normals=True)
+    chain = list(names)
+    del names[:]
+    plain = vol.extract()
+    kept = mesh.filter_components(plain, 1, 0.03)
+    want = mesh.vertex_normals(mesh.smooth(mesh.simplify(mesh.fill_holes(kept, 64), cell, origin=vol.origin), 2))
+    assert plain["counts"] == (2902, 5780) and kept["components"]["kept"] == 5 and kept["counts"][1] == 5780 - 88
+    assert 0 < want["counts"][1] < kept["counts"][1] and want["simplify"]["occupied"] > 1
+    print(f"{which}: {plain['counts']} -> {got['counts']}, {len(chain)} launches, rounds {got['components']['rounds']}")
+    same_device_mesh(got, want)
+    assert set(got) == set(want) == {"vertices", "faces", "rgb8", "counts", "components", "fill", "simplify", "smooth", "normals", "normal_info"}
+    assert got["fill"] == want["fill"] and got["simplify"] == want["simplify"]
+    assert got["components"] == dict(want["components"], rounds=got["components"]["rounds"])
+    assert _launches_of(chain, got["components"]) == _launches_of(names, want["components"])
+
+
+def test_a_sparse_volume_without_blocks_gives_the_empty_mesh_to_smooth_and_normals_only(monkeypatch):
+    """smooth and vertex_normals of an empty mesh return before their first launch, so the chain launches nothing at all; the
+    component filter and the fill, asked for as well, leave no entry in the result."""
+    vol = mesh.SparseTsdfVolume((0.0, 0.0, 0.0), H_ANALYTIC, (3, 3, 3), 3 * H_ANALYTIC, DEV)
+    names = record_launches(monkeypatch)
+    got = vol.extract(smooth_iterations=2, normals=True, fill_holes=64, min_component_faces=5)
+    assert names == []
+    want = mesh.vertex_normals(mesh.smooth(vol.extract(), 2))
+    assert names == []
+    assert got["counts"] == (0, 0) and tuple(got["vertices"].shape) == (0, 3) and tuple(got["faces"].shape) == (0, 3)
+    assert tuple(got["rgb8"].shape) == (0, 3) and tuple(got["normals"].shape) == (0, 3)
+    assert set(got) == set(want) == {"vertices", "faces", "rgb8", "counts", "smooth", "normals", "normal_info"}
+    same_device_mesh(got, want)
+    assert got["smooth"]["iterations"] == 2 and got["normal_info"] == {"zero_normals": 0, "degenerate_faces": 0}

@@ -1,31 +1,20 @@
 """Mesh cleaning on the MI355X (csrc/lrf_mesh_clean.inl through localrf_amd.mesh): component labels, counts and the filtered
 mesh against the numpy restatement of tests/mesh_clean_cases.py, all exact; the scan's block boundary, reproducibility, a
 non-default stream, bad face indices and the extract options."""
-import functools
 
 import numpy as np
 import pytest
 import torch
 
 from localrf_amd import mesh, novel_views, pointcloud
-from mesh_cases import H_ANALYTIC
-from mesh_clean_cases import (FANS, MESH_NAMES, all_meshes, blobs_field, components_host, expected, fan, filter_host,
+from mesh_clean_cases import (FANS, MESH_NAMES, all_meshes, components_host, expected, fan, filter_host,
                               threshold_host)
+from mesh_util import DEV, blob_volumes, device_mesh, same_device_mesh, same_mesh, to_dev
 from novel_views_cases import scene
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 THRESHOLDS = (0, 1, 100, 601, 10 ** 6)
 FRACTIONS = (0.1, 1.0)
-
-
-def _t(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def _device_mesh(m, rgb=True):
-    return {"vertices": _t(m["vertices"]), "faces": _t(m["faces"]), "rgb8": _t(m["rgb8"]) if rgb and m["rgb8"] is not None else None,
-            "counts": m["counts"]}
 
 
 def _same_components(got, want, nv):
@@ -37,32 +26,11 @@ def _same_components(got, want, nv):
     assert type(got["rounds"]) is int and 1 <= got["rounds"] <= 64
 
 
-def _same_mesh(got, want):
-    """Counts, vertices (as uint32), faces and rgb8, all exact."""
-    assert got["counts"] == want["counts"], (got["counts"], want["counts"])
-    nv, nf = want["counts"]
-    assert tuple(got["vertices"].shape) == (nv, 3) and tuple(got["faces"].shape) == (nf, 3)
-    assert got["vertices"].dtype is torch.float32 and got["faces"].dtype is torch.int32
-    assert np.array_equal(got["vertices"].cpu().numpy().view(np.uint32), want["vertices"].view(np.uint32))
-    assert np.array_equal(got["faces"].cpu().numpy(), want["faces"])
-    if want["rgb8"] is None:
-        assert got["rgb8"] is None
-    else:
-        assert got["rgb8"].dtype is torch.uint8 and tuple(got["rgb8"].shape) == (nv, 3)
-        assert np.array_equal(got["rgb8"].cpu().numpy(), want["rgb8"])
-
-
-def _same_device_mesh(a, b):
-    assert a["counts"] == b["counts"]
-    assert torch.equal(a["vertices"].view(torch.int32), b["vertices"].view(torch.int32)) and torch.equal(a["faces"], b["faces"])
-    assert (a["rgb8"] is None) == (b["rgb8"] is None) and (a["rgb8"] is None or torch.equal(a["rgb8"], b["rgb8"]))
-
-
 @pytest.mark.parametrize("name", MESH_NAMES)
 def test_labels_and_counts_equal_the_restatement(name):
     m = all_meshes()[name]
     nv, nf = m["counts"]
-    got = mesh.components(_t(m["faces"]), nv)
+    got = mesh.components(to_dev(m["faces"]), nv)
     print(f"{name}: {nv} vertices, {nf} faces, {got['n_components']} components, rounds {got['rounds']}")
     _same_components(got, expected(name), nv)
 
@@ -77,7 +45,7 @@ def test_fans_across_a_wave_a_workgroup_and_a_keep_word_group(nv):
     for label, faces, n in (("fan", f["faces"], nv), ("fan and strays", f["faces"], nv + 70), ("two fans", two, 2 * nv),
                             ("reversed", rev, nv), ("reversed and strays", rev, nv + 1)):
         m = {"vertices": np.zeros((n, 3), np.float32), "faces": np.ascontiguousarray(faces, dtype=np.int32)}
-        got = mesh.components(_t(m["faces"]), n)
+        got = mesh.components(to_dev(m["faces"]), n)
         print(f"{label} Nv = {n}: {got['n_components']} components, rounds {got['rounds']}")
         _same_components(got, components_host(m), n)
 
@@ -87,13 +55,13 @@ def test_filter_equals_the_restatement_bit_for_bit(name):
     m, comp = all_meshes()[name], expected(name)
     once = {}
     for rgb in (True, False):
-        dm = _device_mesh(m, rgb)
+        dm = device_mesh(m, rgb)
         hm = m if rgb else dict(m, rgb8=None)
         for kw in [dict(min_faces=t) for t in THRESHOLDS] + [dict(min_fraction=q) for q in FRACTIONS] + [dict(min_faces=100, min_fraction=0.1)]:
             threshold = threshold_host(kw.get("min_faces", 0), kw.get("min_fraction", 0.0), comp["largest_faces"])
             want, kept = filter_host(hm, comp, threshold)
             got = mesh.filter_components(dm, **kw)
-            _same_mesh(got, want)
+            same_mesh(got, want)
             info = got["components"]
             assert info["kept"] == kept and info["threshold"] == threshold, (kw, info)
             assert (info["n_components"], info["n_with_faces"], info["largest_faces"]) == (comp["n_components"], comp["n_with_faces"],
@@ -101,13 +69,13 @@ def test_filter_equals_the_restatement_bit_for_bit(name):
             if rgb:
                 once[tuple(kw.items())] = (got, kw)
             if threshold == 0:                                          # the input's bytes
-                _same_device_mesh(got, dm)
+                same_device_mesh(got, dm)
             if kw.get("min_faces") == 10 ** 6:
                 assert got["counts"] == (0, 0) and tuple(got["vertices"].shape) == (0, 3) and tuple(got["faces"].shape) == (0, 3)
         print(f"{name} rgb {rgb}: rounds {info['rounds']}, largest {info['largest_faces']}")
     for got, kw in once.values():                                       # filtering twice equals filtering once
         again = mesh.filter_components(got, **kw)
-        _same_device_mesh(again, got)
+        same_device_mesh(again, got)
         assert again["components"]["kept"] == again["components"]["n_components"]       # nothing is left to drop
     assert dm["vertices"].data_ptr() != got["vertices"].data_ptr()      # a new mesh: the input is left alone
     assert np.array_equal(dm["faces"].cpu().numpy(), m["faces"])
@@ -125,21 +93,21 @@ def test_a_fan_across_the_scan_block_boundary():
          "rgb8": rng.integers(0, 256, (nv, 3), dtype=np.uint8), "counts": (nv, int(faces.shape[0]))}
     comp = components_host(m, big=True)
     assert comp["n_components"] == 1 + (nv - 2) // 1000 and comp["largest_faces"] == faces.shape[0]
-    dm = _device_mesh(m)
+    dm = device_mesh(m)
     got = mesh.components(dm["faces"], nv)
     print(f"fan of 2^20 + 1: rounds {got['rounds']}")
     _same_components(got, comp, nv)
     for threshold in (0, 1):
         want, kept = filter_host(m, comp, threshold)
         out = mesh.filter_components(dm, min_faces=threshold)
-        _same_mesh(out, want)
+        same_mesh(out, want)
         assert out["components"]["kept"] == kept
     assert out["counts"] == (nv - (nv - 2) // 1000, faces.shape[0])
 
 
 def test_two_runs_are_equal_and_a_side_stream_gives_the_same():
     m = all_meshes()["blobs noise / vertices permuted"]
-    dm = _device_mesh(m)
+    dm = device_mesh(m)
     runs = [(mesh.components(dm["faces"], m["counts"][0]), mesh.filter_components(dm, min_faces=100)) for _ in range(2)]
     side = torch.cuda.Stream(DEV)
     side.wait_stream(torch.cuda.current_stream(DEV))
@@ -152,9 +120,9 @@ def test_two_runs_are_equal_and_a_side_stream_gives_the_same():
         for k in ("labels", "faces_of", "vertices_of"):
             assert torch.equal(c[k], c0[k]), k
         assert all(c[k] == c0[k] for k in ("n_components", "n_with_faces", "largest_faces"))
-        _same_device_mesh(f, f0)
+        same_device_mesh(f, f0)
         assert f["components"]["kept"] == f0["components"]["kept"]
-    _same_mesh(f0, filter_host(m, expected("blobs noise / vertices permuted"), 100)[0])
+    same_mesh(f0, filter_host(m, expected("blobs noise / vertices permuted"), 100)[0])
 
 
 def test_bad_face_indices_raise_and_the_next_call_is_right():
@@ -165,44 +133,28 @@ def test_bad_face_indices_raise_and_the_next_call_is_right():
             faces = m["faces"].copy()
             faces[row, col] = bad
             with pytest.raises(ValueError, match=f"outside \\[0, {nv}\\)"):
-                mesh.components(_t(faces), nv)
+                mesh.components(to_dev(faces), nv)
             with pytest.raises(ValueError, match=f"outside \\[0, {nv}\\)"):
-                mesh.filter_components(dict(_device_mesh(m), faces=_t(faces)), min_faces=100)
-    got = mesh.components(_t(m["faces"]), nv)
+                mesh.filter_components(dict(device_mesh(m), faces=to_dev(faces)), min_faces=100)
+    got = mesh.components(to_dev(m["faces"]), nv)
     _same_components(got, expected("blobs"), nv)
-    _same_mesh(mesh.filter_components(_device_mesh(m), min_faces=100), filter_host(m, expected("blobs"), 100)[0])
+    same_mesh(mesh.filter_components(device_mesh(m), min_faces=100), filter_host(m, expected("blobs"), 100)[0])
     with pytest.raises(RuntimeError, match="max_rounds is 1"):          # the blobs need a changing round and a quiet one
-        mesh.components(_t(m["faces"]), nv, max_rounds=1)
-
-
-@functools.lru_cache(maxsize=None)
-def _blob_volumes():
-    fld = blobs_field()
-    o = (0.0, 0.0, 0.0)
-    rng = np.random.default_rng(12)
-    rgb = rng.uniform(0.0, 1.0, fld.shape + (3,)).astype(np.float32)
-    dense = mesh.TsdfVolume(o, H_ANALYTIC, (24, 24, 24), 3 * H_ANALYTIC, DEV)
-    dense.tsdf.copy_(_t(fld)); dense.weight.fill_(1.0); dense.rgb.copy_(_t(rgb))
-    sparse = mesh.SparseTsdfVolume(o, H_ANALYTIC, (3, 3, 3), 3 * H_ANALYTIC, DEV, colours=False)
-    sparse.marks.fill_(1)
-    assert sparse.allocate() == 27
-    sparse.tsdf.copy_(_t(np.ascontiguousarray(fld.reshape(3, 8, 3, 8, 3, 8).transpose(0, 2, 4, 1, 3, 5).reshape(27, 8, 8, 8))))
-    sparse.weight.fill_(1.0)
-    return dense, sparse
+        mesh.components(to_dev(m["faces"]), nv, max_rounds=1)
 
 
 @pytest.mark.parametrize("which", ("dense", "sparse"))
 def test_extract_options_equal_filter_components_of_extract(which):
-    vol = _blob_volumes()[which == "sparse"]
+    vol = blob_volumes()[which == "sparse"]
     plain = vol.extract()
     assert set(plain) == {"vertices", "faces", "rgb8", "counts"} and plain["counts"] == (2902, 5780)
-    _same_device_mesh(vol.extract(min_component_faces=0, min_component_fraction=0.0), plain)
+    same_device_mesh(vol.extract(min_component_faces=0, min_component_fraction=0.0), plain)
     assert set(vol.extract(min_component_faces=0)) == set(plain)        # the defaults: exactly today's dict
     for kw in (dict(min_component_faces=100), dict(min_component_faces=601), dict(min_component_fraction=0.1),
                dict(min_component_fraction=1.0), dict(min_component_faces=10 ** 6), dict(min_component_faces=500, min_component_fraction=0.05)):
         got = vol.extract(**kw)
         want = mesh.filter_components(plain, kw.get("min_component_faces", 0), kw.get("min_component_fraction", 0.0))
-        _same_device_mesh(got, want)
+        same_device_mesh(got, want)
         assert got["components"] == dict(want["components"], rounds=got["components"]["rounds"])
     assert vol.extract(min_component_faces=601)["counts"][1] == 4200 and vol.extract(min_component_fraction=1.0)["components"]["kept"] == 1
 
@@ -221,7 +173,7 @@ def test_scene_mesh_options_equal_scene_mesh_then_filter(tmp_path):
     assert set(plain) == {"vertices", "faces", "rgb8", "counts", "volume"}
     same = mesh.scene_mesh(lt, W, H, min_component_faces=0, min_component_fraction=0.0, **kw)
     assert set(same) == set(plain)
-    _same_device_mesh(same, plain)
+    same_device_mesh(same, plain)
     comp = mesh.components(plain["faces"], plain["counts"][0])
     k = max(2, comp["largest_faces"] // 2)
     print(f"scene_mesh: {plain['counts']} vertices / faces, {comp['n_components']} components, largest {comp['largest_faces']}, "
@@ -230,7 +182,7 @@ def test_scene_mesh_options_equal_scene_mesh_then_filter(tmp_path):
     for opts in (dict(min_component_faces=k), dict(min_component_fraction=1.0)):
         got = mesh.scene_mesh(lt, W, H, **opts, **kw)
         want = mesh.filter_components(plain, opts.get("min_component_faces", 0), opts.get("min_component_fraction", 0.0))
-        _same_device_mesh(got, want)
+        same_device_mesh(got, want)
         assert got["components"]["kept"] == want["components"]["kept"] and "volume" in got
         path = tmp_path / f"mesh{len(files)}.ply"
         pointcloud.write_ply(str(path), got["vertices"], got["rgb8"], faces=got["faces"])

@@ -14,19 +14,14 @@ from mesh_clean_cases import base_meshes
 from mesh_distance_cases import (CASE_NAMES, SAMPLE_CASES, SUMMARY_SIZES, SUMMARY_TAUS, _pairs, box_host, cases, default_cell_host,
                                  dims_host, expected, mesh_distance_host, sample_host, summary_host, summary_inputs)
 from mesh_raster_cases import octa_sphere
+from mesh_util import DEV, bits, device_mesh
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 U32 = np.uint32
 
 
 def dev_mesh(m):
-    return {"vertices": torch.from_numpy(np.ascontiguousarray(m["vertices"], np.float32)).to(DEV),
-            "faces": torch.from_numpy(np.ascontiguousarray(m["faces"], np.int32)).to(DEV), "rgb8": None, "counts": m["counts"]}
-
-
-def bits(t):
-    return t.detach().cpu().numpy().view(U32)
+    return device_mesh(m, rgb=False)
 
 
 def same(out, e, closest=True):

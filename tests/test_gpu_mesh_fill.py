@@ -13,30 +13,20 @@ from localrf_amd._checks import float_of_key
 from localrf_amd.mesh import fill_holes, holes  # noqa: F401  (what every test here is about)
 from mesh_clean_cases import fan
 from mesh_fill_cases import CASE_NAMES, CLOSABLE, E2E_H, E2E_N, HOLE_KEYS, UNCHANGED, cases, e2e_volume, expected
+from mesh_util import DEV, bits, device_mesh, to_dev
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-
-
-def _t(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
 
 
 @functools.lru_cache(maxsize=None)
-def _device_mesh(name):
+def _case_mesh(name):
     m = cases()[name][0]
-    return {"vertices": _t(m["vertices"]), "faces": _t(m["faces"]), "rgb8": None if m["rgb8"] is None else _t(m["rgb8"]),
-            "counts": (int(m["vertices"].shape[0]), int(m["faces"].shape[0])), "note": "kept",
-            "normals": torch.zeros(m["vertices"].shape[0], 3, device=DEV)}
-
-
-def _bits(t):
-    return t.detach().cpu().numpy().view(np.uint32)
+    return device_mesh(m, note="kept", normals=torch.zeros(m["vertices"].shape[0], 3, device=DEV))
 
 
 def _same_as_host(got, want):
     assert got["vertices"].dtype is torch.float32 and got["faces"].dtype is torch.int32
-    assert np.array_equal(_bits(got["vertices"]), np.ascontiguousarray(want["vertices"]).view(np.uint32))
+    assert np.array_equal(bits(got["vertices"]), np.ascontiguousarray(want["vertices"]).view(np.uint32))
     assert np.array_equal(got["faces"].cpu().numpy(), want["faces"])
     assert (got["rgb8"] is None) == (want["rgb8"] is None)
     if want["rgb8"] is not None:
@@ -46,8 +36,8 @@ def _same_as_host(got, want):
 
 @pytest.mark.parametrize("name", CASE_NAMES)
 def test_holes_and_fill_equal_the_restatement_bit_for_bit(name):
-    dm, max_edges, want = _device_mesh(name), cases()[name][1], expected(name)
-    before = (_bits(dm["vertices"]).copy(), dm["faces"].cpu().numpy().copy())
+    dm, max_edges, want = _case_mesh(name), cases()[name][1], expected(name)
+    before = (bits(dm["vertices"]).copy(), dm["faces"].cpu().numpy().copy())
     h = mesh.holes(dm, max_edges)
     print(f"{name}: {dm['counts']} max_edges {max_edges} {h}")
     assert tuple(h) == HOLE_KEYS and all(type(h[k]) is int for k in h)
@@ -60,7 +50,7 @@ def test_holes_and_fill_equal_the_restatement_bit_for_bit(name):
         assert got["vertices"] is dm["vertices"] and got["faces"] is dm["faces"] and got["rgb8"] is dm["rgb8"]
     else:
         assert got["vertices"].data_ptr() != dm["vertices"].data_ptr() and got["faces"].data_ptr() != dm["faces"].data_ptr()
-    assert np.array_equal(_bits(dm["vertices"]), before[0]) and np.array_equal(dm["faces"].cpu().numpy(), before[1])
+    assert np.array_equal(bits(dm["vertices"]), before[0]) and np.array_equal(dm["faces"].cpu().numpy(), before[1])
     again = mesh.fill_holes(dm, max_edges)                                      # two runs, the same bytes
     _same_as_host(again, want)
     twice = mesh.fill_holes(got, max_edges)                                     # a second fill adds nothing
@@ -70,7 +60,7 @@ def test_holes_and_fill_equal_the_restatement_bit_for_bit(name):
 
 @pytest.mark.parametrize("name", CLOSABLE)
 def test_the_filled_mesh_is_closed_and_smooth_pins_nothing(name):
-    dm, max_edges = _device_mesh(name), cases()[name][1]
+    dm, max_edges = _case_mesh(name), cases()[name][1]
     got = mesh.fill_holes(dm, max_edges)
     t = mesh.topology(got)
     assert t["closed"] is True and t["boundary_edges"] == 0 and not bool(t["boundary_vertices"].any())
@@ -83,7 +73,7 @@ def test_the_filled_mesh_is_closed_and_smooth_pins_nothing(name):
 
 def test_a_side_stream_gives_the_same_bytes():
     for name in ("sphere minus 90", "sphere caps 65", "fan 1025 / max_edges 1025"):
-        dm, max_edges, want = _device_mesh(name), cases()[name][1], expected(name)
+        dm, max_edges, want = _case_mesh(name), cases()[name][1], expected(name)
         side = torch.cuda.Stream(DEV)
         side.wait_stream(torch.cuda.current_stream(DEV))
         with torch.cuda.stream(side):
@@ -116,7 +106,7 @@ def _native_fill(dm, max_edges, cap_v, cap_f, rows_v, rows_f):
 
 def test_a_capacity_one_short_sets_the_flag_and_writes_nothing_past_it():
     name = "sphere minus 20 / no colours"
-    dm, max_edges, want = _device_mesh(name), cases()[name][1], expected(name)
+    dm, max_edges, want = _case_mesh(name), cases()[name][1], expected(name)
     nv, nf = want["vertices"].shape[0], want["faces"].shape[0]
     v, f, words = _native_fill(dm, max_edges, nv, nf, nv + 2, nf + 2)           # the exact capacities: no flag, the rows beyond stay
     assert words[0] == 0 and words[4:6] == [20, 60]
@@ -133,14 +123,14 @@ def test_a_capacity_one_short_sets_the_flag_and_writes_nothing_past_it():
 
 def _all_right(name="sphere caps 64"):
     """The next valid call is right."""
-    got = mesh.fill_holes(_device_mesh(name), cases()[name][1])
+    got = mesh.fill_holes(_case_mesh(name), cases()[name][1])
     assert got["fill"] == expected(name)["fill"]
     _same_as_host(got, expected(name))
 
 
 def test_bad_face_indices_and_vertices_that_are_not_finite_raise_and_the_next_call_is_right():
     name = "sphere caps 64"
-    m, dm = cases()[name][0], _device_mesh(name)
+    m, dm = cases()[name][0], _case_mesh(name)
     nv, nf = m["vertices"].shape[0], m["faces"].shape[0]
     for bad in (nv, -1, (1 << 31) - 1, -(1 << 31)):
         for row, col in ((0, 0), (nf - 1, 2)):
@@ -148,14 +138,14 @@ def test_bad_face_indices_and_vertices_that_are_not_finite_raise_and_the_next_ca
             faces[row, col] = bad
             for fn in (mesh.holes, mesh.fill_holes):
                 with pytest.raises(ValueError, match=f"outside \\[0, {nv}\\)"):
-                    fn(dict(dm, faces=_t(faces)))
+                    fn(dict(dm, faces=to_dev(faces)))
     for bad in (np.nan, np.inf, -np.inf):
         for row, col in ((0, 0), (nv - 1, 2)):
             v = m["vertices"].copy()
             v[row, col] = bad
             for fn in (mesh.holes, mesh.fill_holes):
                 with pytest.raises(ValueError, match="not finite"):
-                    fn(dict(dm, vertices=_t(v)))
+                    fn(dict(dm, vertices=to_dev(v)))
     _all_right()
 
 
@@ -166,9 +156,9 @@ def test_cpu_tensors_raise_native_error_and_a_row_of_2_to_the_20_raises():
         with pytest.raises(NativeError):
             fn(cpu)
         with pytest.raises(NativeError):
-            fn(dict(_device_mesh("tetrahedron minus one face"), faces=cpu["faces"]))
+            fn(dict(_case_mesh("tetrahedron minus one face"), faces=cpu["faces"]))
     big = fan((1 << 20) + 2)                                                    # its hub holds 2^20 faces
-    dm = {"vertices": _t(big["vertices"]), "faces": _t(big["faces"]), "rgb8": None}
+    dm = {"vertices": to_dev(big["vertices"]), "faces": to_dev(big["faces"]), "rgb8": None}
     for fn in (mesh.holes, mesh.fill_holes):
         with pytest.raises(ValueError, match="2\\^20 faces or more"):
             fn(dm)
@@ -182,7 +172,7 @@ def test_an_empty_mesh_and_a_mesh_without_faces():
     got = mesh.fill_holes(empty)
     assert got["vertices"] is empty["vertices"] and got["faces"] is empty["faces"] and got["note"] == "kept" and got["counts"] == (0, 0)
     assert got["fill"] == dict(dict.fromkeys(HOLE_KEYS, 0), added_vertices=0, added_faces=0)
-    dm = dict(_device_mesh("sphere"), faces=torch.empty(0, 3, dtype=torch.int32, device=DEV))
+    dm = dict(_case_mesh("sphere"), faces=torch.empty(0, 3, dtype=torch.int32, device=DEV))
     assert mesh.holes(dm) == dict.fromkeys(HOLE_KEYS, 0)
     got = mesh.fill_holes(dm)
     assert got["fill"]["loops"] == 0 and got["vertices"] is dm["vertices"] and "normals" not in got
@@ -193,14 +183,14 @@ def _punched_volumes():
     fld, w = e2e_volume()
     rgb = np.random.default_rng(13).uniform(0.0, 1.0, fld.shape + (3,)).astype(np.float32)
     dense = mesh.TsdfVolume((0.0, 0.0, 0.0), E2E_H, (E2E_N,) * 3, 3 * E2E_H, DEV)
-    dense.tsdf.copy_(_t(fld)); dense.weight.copy_(_t(w)); dense.rgb.copy_(_t(rgb))
+    dense.tsdf.copy_(to_dev(fld)); dense.weight.copy_(to_dev(w)); dense.rgb.copy_(to_dev(rgb))
     B = E2E_N // 8
     sparse = mesh.SparseTsdfVolume((0.0, 0.0, 0.0), E2E_H, (B, B, B), 3 * E2E_H, DEV, colours=False)
     sparse.marks.fill_(1)
     assert sparse.allocate() == B ** 3
 
     def pooled(a):
-        return _t(np.ascontiguousarray(a.reshape(B, 8, B, 8, B, 8).transpose(0, 2, 4, 1, 3, 5).reshape(B ** 3, 8, 8, 8)))
+        return to_dev(np.ascontiguousarray(a.reshape(B, 8, B, 8, B, 8).transpose(0, 2, 4, 1, 3, 5).reshape(B ** 3, 8, 8, 8)))
     sparse.tsdf.copy_(pooled(fld)); sparse.weight.copy_(pooled(w))
     return dense, sparse
 

@@ -13,26 +13,18 @@ from localrf_amd import NativeError, mesh, mesh_raster, novel_views, pointcloud
 from localrf_amd.mesh_raster import depth_agreement, rasterize, scene_mesh_agreement
 from mesh_raster_cases import (AGREEMENT_SHAPES, AGREEMENT_TOLS, BOX_FACE, CASE_NAMES, SPHERE_KIND, agreement_host, agreement_maps,
                                cases, expected)
+from mesh_util import DEV, device_mesh, to_dev
 from novel_views_cases import scene
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 MAPS = ("depth", "face", "rgb8", "weights", "crossings")
 ALL_LARGE, ALL_SMALL = 0, (1 << 31) - 1
-
-
-def _t(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def _device_mesh(m):
-    return {"vertices": _t(m["vertices"]), "faces": _t(m["faces"]), "rgb8": None if m["rgb8"] is None else _t(m["rgb8"])}
 
 
 @functools.lru_cache(maxsize=None)
 def _device_case(name):
     c = cases()[name]
-    return _device_mesh(c["mesh"]), _t(c["c2w"])
+    return device_mesh(c["mesh"]), to_dev(c["c2w"])
 
 
 def _run(name, mesh_=None, poses=None, **over):
@@ -86,7 +78,7 @@ def test_a_face_permutation_keeps_the_depth_bytes(name):
     base = _host(_run(name))
     nf = c["mesh"]["faces"].shape[0]
     p = np.random.default_rng(77).permutation(nf)                           # new face k is old face p[k]
-    dm = _device_mesh(dict(c["mesh"], faces=c["mesh"]["faces"][p]))
+    dm = device_mesh(dict(c["mesh"], faces=c["mesh"]["faces"][p]))
     got = _host(_run(name, mesh_=dm))
     for k in ("depth", "crossings"):
         assert np.array_equal(_bytes(got[k]), _bytes(base[k])), (name, k)
@@ -171,7 +163,7 @@ def test_depth_agreement_integers_equal_the_restatement(shape):
     a, b = agreement_maps(40 + shape[1], *shape)
     rng = (0.6, 30.0)
     words, err = agreement_host(a, b, AGREEMENT_TOLS, rng)
-    got = depth_agreement(_t(a), _t(b), rel_tols=AGREEMENT_TOLS, depth_range=rng, error_map=True)
+    got = depth_agreement(to_dev(a), to_dev(b), rel_tols=AGREEMENT_TOLS, depth_range=rng, error_map=True)
     pf = got["per_frame"]
     for k, col in (("both", 0), ("mesh_only", 1), ("render_only", 2), ("neither", 3), ("error_sum", 4)):
         assert np.array_equal(pf[k], words[:, col]), k
@@ -181,9 +173,9 @@ def test_depth_agreement_integers_equal_the_restatement(shape):
     assert np.array_equal(_bytes(got["error_map"].cpu().numpy()), _bytes(err))
     if got["both"]:
         assert got["mean_rel_error"] == got["error_sum"] / (1 << 24) / got["both"]
-    again = depth_agreement(_t(a), _t(b), rel_tols=AGREEMENT_TOLS, depth_range=rng)
+    again = depth_agreement(to_dev(a), to_dev(b), rel_tols=AGREEMENT_TOLS, depth_range=rng)
     assert "error_map" not in again and again["error_sum"] == got["error_sum"] and again["within"] == got["within"]
-    none = depth_agreement(_t(a), _t(b), rel_tols=())
+    none = depth_agreement(to_dev(a), to_dev(b), rel_tols=())
     assert none["within"] == () and none["both"] + none["mesh_only"] + none["render_only"] + none["neither"] == a.size
 
 
@@ -222,10 +214,10 @@ def test_round_trip_through_a_volume_stays_within_one_voxel():
     voxel = 3.4 / (RT_N - 1)
     vol = mesh.TsdfVolume((-1.7, -1.7, -4.7), voxel, (RT_N,) * 3, 3 * voxel, DEV, colours=False)
     centre = (RT_W / 2, RT_H / 2)
-    vol.integrate(_t(depth), _t(c2w), RT_FOCAL, centre)
+    vol.integrate(to_dev(depth), to_dev(c2w), RT_FOCAL, centre)
     m = vol.extract()
     assert m["counts"][1] > 1000
-    out = rasterize(m, _t(c2w), RT_W, RT_H, RT_FOCAL, centre, crossings=True)
+    out = rasterize(m, to_dev(c2w), RT_W, RT_H, RT_FOCAL, centre, crossings=True)
     got = out["depth"].cpu().numpy()
     assert out["info"] == {"bad_index_faces": 0, "degenerate_faces": 0, "nonfinite_faces": 0}
     step = np.zeros(depth.shape, bool)

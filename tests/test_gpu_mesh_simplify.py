@@ -1,7 +1,6 @@
 """Mesh simplification on the MI355X (csrc/lrf_mesh_simplify.inl through localrf_amd.mesh.simplify): every case of
 tests/mesh_simplify_cases.py against the numpy restatement, bit for bit -- no tolerance anywhere --, permuted inputs,
 reproducibility, a non-default stream, bad vertices and face indices, the workspace limit, and the extract options."""
-import functools
 
 import numpy as np
 import pytest
@@ -9,21 +8,11 @@ import torch
 
 from localrf_amd import _native, mesh, novel_views, pointcloud
 from mesh_cases import H_ANALYTIC
-from mesh_clean_cases import blobs_field
 from mesh_simplify_cases import CASE_NAMES, cases, expected_simplified
+from mesh_util import DEV, blob_volumes, device_mesh, record_launches, same_device_mesh, to_dev
 from novel_views_cases import scene
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-
-
-def _t(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def _device_mesh(m, rgb=True):
-    return {"vertices": _t(m["vertices"]), "faces": _t(m["faces"]), "rgb8": _t(m["rgb8"]) if rgb and m["rgb8"] is not None else None,
-            "counts": m["counts"]}
 
 
 def _same_as_host(got, want, cell, origin):
@@ -46,17 +35,11 @@ def _same_as_host(got, want, cell, origin):
         assert np.array_equal(got["rgb8"].cpu().numpy(), want["rgb8"])
 
 
-def _same_device_mesh(a, b):
-    assert a["counts"] == b["counts"]
-    assert torch.equal(a["vertices"].view(torch.int32), b["vertices"].view(torch.int32)) and torch.equal(a["faces"], b["faces"])
-    assert (a["rgb8"] is None) == (b["rgb8"] is None) and (a["rgb8"] is None or torch.equal(a["rgb8"], b["rgb8"]))
-
-
 @pytest.mark.parametrize("name", CASE_NAMES)
 def test_simplify_equals_the_restatement_bit_for_bit(name):
     m, cell, origin = cases()[name]
     for rgb in (True, False):
-        dm = _device_mesh(m, rgb)
+        dm = device_mesh(m, rgb)
         for dedupe in (True, False):
             print(f"{name} rgb {rgb} dedupe {dedupe}: {m['counts']}")
             got = mesh.simplify(dm, cell, origin=origin, dedupe=dedupe)
@@ -70,9 +53,9 @@ def test_simplify_equals_the_restatement_bit_for_bit(name):
 def test_permuted_inputs_give_identical_vertex_bytes(name):
     base = name.rsplit(" / ", 1)[0]
     m, cell, origin = cases()[base]
-    want = mesh.simplify(_device_mesh(m), cell, origin=origin)
+    want = mesh.simplify(device_mesh(m), cell, origin=origin)
     for other in (name, base + " / faces permuted"):
-        got = mesh.simplify(_device_mesh(cases()[other][0]), cell, origin=origin)
+        got = mesh.simplify(device_mesh(cases()[other][0]), cell, origin=origin)
         assert got["counts"] == want["counts"] and got["simplify"] == want["simplify"]
         assert torch.equal(got["vertices"].view(torch.int32), want["vertices"].view(torch.int32))
         assert torch.equal(got["rgb8"], want["rgb8"])
@@ -83,7 +66,7 @@ def test_permuted_inputs_give_identical_vertex_bytes(name):
 def test_two_runs_are_equal_and_a_side_stream_gives_the_same():
     for name in ("strip", "blobs shifted / 2 steps / origin 0.1 / vertices permuted"):
         m, cell, origin = cases()[name]
-        dm = _device_mesh(m)
+        dm = device_mesh(m)
         runs = [mesh.simplify(dm, cell, origin=origin) for _ in range(2)]
         side = torch.cuda.Stream(DEV)
         side.wait_stream(torch.cuda.current_stream(DEV))
@@ -92,7 +75,7 @@ def test_two_runs_are_equal_and_a_side_stream_gives_the_same():
         side.synchronize()
         assert 0 < runs[0]["counts"][1] < m["counts"][1]
         for r in runs[1:]:
-            _same_device_mesh(r, runs[0])
+            same_device_mesh(r, runs[0])
             assert r["simplify"] == runs[0]["simplify"]
 
 
@@ -105,8 +88,8 @@ def test_bad_vertices_raise_and_the_next_call_is_right():
             v = m["vertices"].copy()
             v[row, col] = bad
             with pytest.raises(ValueError, match="not finite or lies 2\\^30 cells"):
-                mesh.simplify(dict(_device_mesh(m), vertices=_t(v)), cell, origin=origin)
-    _same_as_host(mesh.simplify(_device_mesh(m), cell, origin=origin), expected_simplified(name), cell, origin)
+                mesh.simplify(dict(device_mesh(m), vertices=to_dev(v)), cell, origin=origin)
+    _same_as_host(mesh.simplify(device_mesh(m), cell, origin=origin), expected_simplified(name), cell, origin)
 
 
 def test_bad_face_indices_raise_and_the_next_call_is_right():
@@ -119,20 +102,14 @@ def test_bad_face_indices_raise_and_the_next_call_is_right():
                 faces = m["faces"].copy()
                 faces[row, col] = bad
                 with pytest.raises(ValueError, match=f"outside \\[0, {nv}\\)"):
-                    mesh.simplify(dict(_device_mesh(m), faces=_t(faces)), cell, origin=origin, dedupe=dedupe)
-    _same_as_host(mesh.simplify(_device_mesh(m), cell, origin=origin), expected_simplified(name), cell, origin)
+                    mesh.simplify(dict(device_mesh(m), faces=to_dev(faces)), cell, origin=origin, dedupe=dedupe)
+    _same_as_host(mesh.simplify(device_mesh(m), cell, origin=origin), expected_simplified(name), cell, origin)
 
 
 def test_a_box_above_max_bytes_raises_before_any_further_launch(monkeypatch):
     m, cell, origin = cases()["sparse box"]
-    dm = _device_mesh(m)
-    seen = []
-    real = _native.launch
-
-    def recording(name, *a, **k):
-        seen.append(name)
-        return real(name, *a, **k)
-    monkeypatch.setattr(_native, "launch", recording)
+    dm = device_mesh(m)
+    seen = record_launches(monkeypatch)
     need = _native.lib().lrf_mesh_simplify_workspace_bytes(9000, 3000, 128 * 128 * 80)
     with pytest.raises(ValueError, match="128 x 128 x 80") as e:
         mesh.simplify(dm, cell, origin=origin, max_bytes=need - 1)
@@ -152,7 +129,7 @@ def test_an_empty_mesh_and_a_mesh_without_faces():
     assert got["counts"] == (0, 0) and tuple(got["vertices"].shape) == (0, 3) and tuple(got["faces"].shape) == (0, 3)
     assert got["note"] == "kept" and got["simplify"]["occupied"] == 0
     m = cases()["blobs / 2 steps / origin 0"][0]
-    got = mesh.simplify(dict(_device_mesh(m), faces=torch.empty(0, 3, dtype=torch.int32, device=DEV)), 2 * H_ANALYTIC)
+    got = mesh.simplify(dict(device_mesh(m), faces=torch.empty(0, 3, dtype=torch.int32, device=DEV)), 2 * H_ANALYTIC)
     assert got["counts"] == (0, 0) and tuple(got["vertices"].shape) == (0, 3) and tuple(got["rgb8"].shape) == (0, 3)
     assert got["simplify"]["occupied"] == expected_simplified("blobs / 2 steps / origin 0")["counts"][2]
 
@@ -160,31 +137,16 @@ def test_an_empty_mesh_and_a_mesh_without_faces():
 ORIGIN = (0.1, -0.2, 0.3)
 
 
-@functools.lru_cache(maxsize=None)
-def _blob_volumes():
-    fld = blobs_field()
-    rng = np.random.default_rng(12)
-    rgb = rng.uniform(0.0, 1.0, fld.shape + (3,)).astype(np.float32)
-    dense = mesh.TsdfVolume(ORIGIN, H_ANALYTIC, (24, 24, 24), 3 * H_ANALYTIC, DEV)
-    dense.tsdf.copy_(_t(fld)); dense.weight.fill_(1.0); dense.rgb.copy_(_t(rgb))
-    sparse = mesh.SparseTsdfVolume(ORIGIN, H_ANALYTIC, (3, 3, 3), 3 * H_ANALYTIC, DEV, colours=False)
-    sparse.marks.fill_(1)
-    assert sparse.allocate() == 27
-    sparse.tsdf.copy_(_t(np.ascontiguousarray(fld.reshape(3, 8, 3, 8, 3, 8).transpose(0, 2, 4, 1, 3, 5).reshape(27, 8, 8, 8))))
-    sparse.weight.fill_(1.0)
-    return dense, sparse
-
-
 @pytest.mark.parametrize("which", ("dense", "sparse"))
 def test_extract_option_equals_simplify_of_extract(which):
-    vol = _blob_volumes()[which == "sparse"]
+    vol = blob_volumes(ORIGIN)[which == "sparse"]
     plain = vol.extract()
     assert set(plain) == {"vertices", "faces", "rgb8", "counts"} and plain["counts"] == (2902, 5780)
     assert set(vol.extract(simplify_cell=None)) == set(plain)           # the default: exactly today's dict
     for c in (2 * H_ANALYTIC, 3.5 * H_ANALYTIC):
         got = vol.extract(simplify_cell=c)
         want = mesh.simplify(plain, c, origin=vol.origin)
-        _same_device_mesh(got, want)
+        same_device_mesh(got, want)
         assert got["simplify"] == want["simplify"] and got["simplify"]["origin"] == ORIGIN
         assert 0 < got["counts"][1] < plain["counts"][1]
         other = mesh.simplify(plain, c)                                 # another anchor, another mesh
@@ -194,7 +156,7 @@ def test_extract_option_equals_simplify_of_extract(which):
         filtered = mesh.filter_components(plain, 601)
         want = mesh.simplify(filtered, c, origin=vol.origin)
         assert filtered["counts"][1] == 4200
-        _same_device_mesh(got, want)
+        same_device_mesh(got, want)
         assert got["simplify"] == want["simplify"] and got["components"]["kept"] == 1
         wrong = mesh.filter_components(mesh.simplify(plain, c, origin=vol.origin), 601)
         assert wrong["counts"] != got["counts"]                         # simplifying first judges other components
@@ -220,6 +182,6 @@ def test_scene_mesh_option_writes_the_same_ply_twice(tmp_path):
         files.append(path.read_bytes())
     want = mesh.simplify(plain, 3 * voxel, origin=plain["volume"].origin)
     print(f"scene_mesh: {plain['counts']} -> {got['counts']}, {got['simplify']}")
-    _same_device_mesh(got, want)
+    same_device_mesh(got, want)
     assert got["simplify"] == want["simplify"] and "volume" in got
     assert files[0] == files[1] and len(files[0]) > 200 and 0 < got["counts"][1] < plain["counts"][1]

@@ -11,28 +11,18 @@ import torch
 from localrf_amd import NativeError, _native, mesh, novel_views, pointcloud
 from localrf_amd.mesh import smooth, topology, vertex_normals  # noqa: F401  (what every test here is about)
 from mesh_cases import H_ANALYTIC
-from mesh_clean_cases import blobs_field, fan
+from mesh_clean_cases import fan
 from mesh_smooth_cases import (CASE_NAMES, cases, expected_normals, expected_smooth, expected_topology, smooth_arguments)
+from mesh_util import DEV, bits, blob_volumes, device_mesh, same_device_mesh, to_dev
 from novel_views_cases import scene
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 COUNTS = ("boundary_edges", "nonmanifold_edges", "degenerate_faces")
 
 
-def _t(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
 @functools.lru_cache(maxsize=None)
-def _device_mesh(name):
-    m = cases()[name]
-    return {"vertices": _t(m["vertices"]), "faces": _t(m["faces"]), "rgb8": None if m["rgb8"] is None else _t(m["rgb8"]),
-            "counts": (int(m["vertices"].shape[0]), int(m["faces"].shape[0])), "note": "kept"}
-
-
-def _bits(t):
-    return t.detach().cpu().numpy().view(np.uint32)
+def _case_mesh(name):
+    return device_mesh(cases()[name], note="kept")
 
 
 def _ordered(a):
@@ -57,7 +47,7 @@ def _debug_normals(dm):
 
 @pytest.mark.parametrize("name", CASE_NAMES)
 def test_topology_equals_the_restatement(name):
-    dm, want = _device_mesh(name), expected_topology(name)
+    dm, want = _case_mesh(name), expected_topology(name)
     got = mesh.topology(dm)
     print(f"{name}: {dm['counts']} {[got[k] for k in COUNTS]} closed {got['closed']}")
     assert set(got) == set(COUNTS) | {"closed", "boundary_vertices"}
@@ -71,7 +61,7 @@ def test_topology_equals_the_restatement(name):
 
 @pytest.mark.parametrize("name", CASE_NAMES)
 def test_vertex_normals_equal_the_restatement(name):
-    dm, want = _device_mesh(name), expected_normals(name)
+    dm, want = _case_mesh(name), expected_normals(name)
     S, E, debug_n, words = _debug_normals(dm)
     assert E == want["E"] and S.dtype == np.int64 and np.array_equal(S, want["S"])       # the integers: bit for bit
     got = mesh.vertex_normals(dm)
@@ -79,7 +69,7 @@ def test_vertex_normals_equal_the_restatement(name):
     assert n.dtype is torch.float32 and tuple(n.shape) == (dm["counts"][0], 3)
     assert got["normal_info"] == {"zero_normals": want["zero_normals"], "degenerate_faces": want["degenerate_faces"]}
     assert words[4] == want["zero_normals"] and words[1] == want["degenerate_faces"] and words[0] == 0
-    assert np.array_equal(_bits(n), debug_n.view(np.uint32))                              # both entry points, the same bytes
+    assert np.array_equal(bits(n), debug_n.view(np.uint32))                              # both entry points, the same bytes
     steps = np.abs(_ordered(n.cpu().numpy()) - _ordered(want["normals"]))
     # one final rounding to fp32 of an fp64 quotient that may differ from numpy's in its last place: at most one step
     print(f"{name}: E {E}, components that differ from numpy at all: {int((steps > 0).sum())} of {steps.size}")
@@ -89,8 +79,8 @@ def test_vertex_normals_equal_the_restatement(name):
 
 @pytest.mark.parametrize("name", CASE_NAMES)
 def test_smooth_equals_the_restatement_bit_for_bit(name):
-    dm = _device_mesh(name)
-    before = _bits(dm["vertices"]).copy()
+    dm = _case_mesh(name)
+    before = bits(dm["vertices"]).copy()
     for it, lam, mu, boundary in smooth_arguments(name):
         want_v, want_info = expected_smooth(name, it, lam, mu, boundary)
         got = mesh.smooth(dm, it, lam, mu, boundary)
@@ -98,21 +88,21 @@ def test_smooth_equals_the_restatement_bit_for_bit(name):
         assert info == dict(want_info, iterations=it, lam=lam, mu=mu, boundary=boundary), (it, lam, mu, boundary)
         assert all(type(info[k]) is int for k in COUNTS + ("pinned", "iterations"))
         assert got["vertices"].dtype is torch.float32 and tuple(got["vertices"].shape) == tuple(dm["vertices"].shape)
-        assert np.array_equal(_bits(got["vertices"]), want_v.view(np.uint32)), (it, lam, mu, boundary)
+        assert np.array_equal(bits(got["vertices"]), want_v.view(np.uint32)), (it, lam, mu, boundary)
         assert got["faces"] is dm["faces"] and got["rgb8"] is dm["rgb8"] and got["note"] == "kept"
         assert got["vertices"].data_ptr() != dm["vertices"].data_ptr()
-    assert np.array_equal(_bits(dm["vertices"]), before)                                  # the input is left alone
+    assert np.array_equal(bits(dm["vertices"]), before)                                  # the input is left alone
     print(f"{name}: {dm['counts']} {len(smooth_arguments(name))} argument sets, pinned {info['pinned']}")
 
 
 def test_two_runs_are_equal_and_a_side_stream_gives_the_same():
     for name in ("blobs tie", "strip / vertices permuted", "fan 1025", "sphere noisy"):
-        dm = _device_mesh(name)
+        dm = _case_mesh(name)
 
         def run():
             t, n, s = mesh.topology(dm), mesh.vertex_normals(dm), mesh.smooth(dm, 3)
-            return (t["boundary_vertices"].cpu().numpy().tobytes(), tuple(t[k] for k in COUNTS), _bits(n["normals"]).tobytes(),
-                    tuple(sorted(n["normal_info"].items())), _bits(s["vertices"]).tobytes(), tuple(sorted(s["smooth"].items())))
+            return (t["boundary_vertices"].cpu().numpy().tobytes(), tuple(t[k] for k in COUNTS), bits(n["normals"]).tobytes(),
+                    tuple(sorted(n["normal_info"].items())), bits(s["vertices"]).tobytes(), tuple(sorted(s["smooth"].items())))
         runs = [run(), run()]
         side = torch.cuda.Stream(DEV)
         side.wait_stream(torch.cuda.current_stream(DEV))
@@ -124,23 +114,23 @@ def test_two_runs_are_equal_and_a_side_stream_gives_the_same():
 
 def _all_right(name="blobs tie"):
     """The next valid call of each kind is right."""
-    dm = _device_mesh(name)
+    dm = _case_mesh(name)
     t, n, s = mesh.topology(dm), mesh.vertex_normals(dm), mesh.smooth(dm, 3)
     assert {k: t[k] for k in COUNTS} == {k: expected_topology(name)[k] for k in COUNTS}
     assert t["boundary_vertices"].cpu().numpy().tobytes() == expected_topology(name)["boundary_vertices"].tobytes()
     assert np.abs(_ordered(n["normals"].cpu().numpy()) - _ordered(expected_normals(name)["normals"])).max() <= 1
-    assert np.array_equal(_bits(s["vertices"]), expected_smooth(name, 3, 0.5, -0.53, "fixed")[0].view(np.uint32))
+    assert np.array_equal(bits(s["vertices"]), expected_smooth(name, 3, 0.5, -0.53, "fixed")[0].view(np.uint32))
 
 
 def test_bad_face_indices_raise_and_the_next_call_is_right():
     m = cases()["blobs tie"]
     nv, nf = m["vertices"].shape[0], m["faces"].shape[0]
-    dm = _device_mesh("blobs tie")
+    dm = _case_mesh("blobs tie")
     for bad in (nv, -1, (1 << 31) - 1, -(1 << 31)):
         for row, col in ((0, 0), (nf // 2, 1), (nf - 1, 2)):
             faces = m["faces"].copy()
             faces[row, col] = bad
-            broken = dict(dm, faces=_t(faces))
+            broken = dict(dm, faces=to_dev(faces))
             for fn in (mesh.topology, mesh.vertex_normals, mesh.smooth):
                 with pytest.raises(ValueError, match=f"outside \\[0, {nv}\\)"):
                     fn(broken)
@@ -150,12 +140,12 @@ def test_bad_face_indices_raise_and_the_next_call_is_right():
 def test_vertices_that_are_not_finite_raise_and_the_next_call_is_right():
     m = cases()["blobs tie"]
     nv = m["vertices"].shape[0]
-    dm = _device_mesh("blobs tie")
+    dm = _case_mesh("blobs tie")
     for bad in (np.nan, np.inf, -np.inf):
         for row, col in ((0, 0), (nv // 2, 1), (nv - 1, 2)):
             v = m["vertices"].copy()
             v[row, col] = bad
-            broken = dict(dm, vertices=_t(v))
+            broken = dict(dm, vertices=to_dev(v))
             for fn in (mesh.vertex_normals, mesh.smooth):
                 with pytest.raises(ValueError, match="not finite"):
                     fn(broken)
@@ -169,13 +159,13 @@ def test_cpu_tensors_raise_native_error():
         with pytest.raises(NativeError):
             fn(cpu)
         with pytest.raises(NativeError):
-            fn(dict(_device_mesh("tetrahedron"), faces=cpu["faces"]))
+            fn(dict(_case_mesh("tetrahedron"), faces=cpu["faces"]))
 
 
 def test_a_row_of_2_to_the_20_raises_and_one_entry_fewer_does_not():
     for nv, ok in (((1 << 20) + 1, True), ((1 << 20) + 2, False)):      # the hub of a fan holds nv - 2 faces
         m = fan(nv)
-        dm = {"vertices": _t(m["vertices"]), "faces": _t(m["faces"]), "rgb8": None}
+        dm = {"vertices": to_dev(m["vertices"]), "faces": to_dev(m["faces"]), "rgb8": None}
         if ok:
             t = mesh.topology(dm)
             assert (t["boundary_edges"], t["nonmanifold_edges"], t["degenerate_faces"]) == (nv, 0, 0) and bool(t["boundary_vertices"].all())
@@ -189,7 +179,7 @@ def test_a_row_of_2_to_the_20_raises_and_one_entry_fewer_does_not():
 
 
 def test_an_iteration_that_leaves_the_fixed_point_range_raises():
-    dm = _device_mesh("sphere noisy")
+    dm = _case_mesh("sphere noisy")
     with pytest.raises(ValueError, match="diverged"):                   # lam = 1, mu = -1 triples the sharpest mode every iteration
         mesh.smooth(dm, 300, 1.0, -1.0, "free")
     _all_right("sphere noisy")
@@ -204,45 +194,20 @@ def test_an_empty_mesh_and_a_mesh_without_faces():
     assert tuple(n["normals"].shape) == (0, 3) and n["note"] == "kept" and n["normal_info"]["zero_normals"] == 0
     s = mesh.smooth(empty, 3)
     assert tuple(s["vertices"].shape) == (0, 3) and s["smooth"]["pinned"] == 0 and s["note"] == "kept"
-    dm = dict(_device_mesh("blobs"), faces=torch.empty(0, 3, dtype=torch.int32, device=DEV))
+    dm = dict(_case_mesh("blobs"), faces=torch.empty(0, 3, dtype=torch.int32, device=DEV))
     nv = dm["vertices"].shape[0]
     assert mesh.topology(dm)["closed"] is True
     n = mesh.vertex_normals(dm)
     assert n["normal_info"]["zero_normals"] == nv and not bool(n["normals"].any())
-    assert np.array_equal(_bits(mesh.smooth(dm, 3)["vertices"]), _bits(dm["vertices"]))
+    assert np.array_equal(bits(mesh.smooth(dm, 3)["vertices"]), bits(dm["vertices"]))
 
 
 ORIGIN = (0.1, -0.2, 0.3)
 
 
-@functools.lru_cache(maxsize=None)
-def _blob_volumes():
-    fld = blobs_field()
-    rng = np.random.default_rng(12)
-    rgb = rng.uniform(0.0, 1.0, fld.shape + (3,)).astype(np.float32)
-    dense = mesh.TsdfVolume(ORIGIN, H_ANALYTIC, (24, 24, 24), 3 * H_ANALYTIC, DEV)
-    dense.tsdf.copy_(_t(fld)); dense.weight.fill_(1.0); dense.rgb.copy_(_t(rgb))
-    sparse = mesh.SparseTsdfVolume(ORIGIN, H_ANALYTIC, (3, 3, 3), 3 * H_ANALYTIC, DEV, colours=False)
-    sparse.marks.fill_(1)
-    assert sparse.allocate() == 27
-    sparse.tsdf.copy_(_t(np.ascontiguousarray(fld.reshape(3, 8, 3, 8, 3, 8).transpose(0, 2, 4, 1, 3, 5).reshape(27, 8, 8, 8))))
-    sparse.weight.fill_(1.0)
-    return dense, sparse
-
-
-def _same_device_mesh(a, b):
-    assert a["counts"] == b["counts"]
-    assert torch.equal(a["vertices"].view(torch.int32), b["vertices"].view(torch.int32)) and torch.equal(a["faces"], b["faces"])
-    assert (a["rgb8"] is None) == (b["rgb8"] is None) and (a["rgb8"] is None or torch.equal(a["rgb8"], b["rgb8"]))
-    assert ("normals" in a) == ("normals" in b)
-    if "normals" in a:
-        assert torch.equal(a["normals"].view(torch.int32), b["normals"].view(torch.int32)) and a["normal_info"] == b["normal_info"]
-    assert a.get("smooth") == b.get("smooth")
-
-
 @pytest.mark.parametrize("which", ("dense", "sparse"))
 def test_extract_options_equal_the_chain_of_calls(which):
-    vol = _blob_volumes()[which == "sparse"]
+    vol = blob_volumes(ORIGIN)[which == "sparse"]
     plain = vol.extract()
     assert set(plain) == {"vertices", "faces", "rgb8", "counts"} and plain["counts"] == (2902, 5780)
     assert set(vol.extract(smooth_iterations=0, normals=False)) == set(plain)           # the defaults: exactly today's dict
@@ -255,15 +220,15 @@ def test_extract_options_equal_the_chain_of_calls(which):
             want = mesh.simplify(want, cell, origin=vol.origin) if cell is not None else want
             moved = mesh.smooth(want, 3)
             want = mesh.vertex_normals(moved)
-            _same_device_mesh(got, want)
+            same_device_mesh(got, want)
             assert got["smooth"]["iterations"] == 3 and got["counts"][1] > 0 and set(got) == set(want)
             if cell is None and not filt:                                               # the normals of the smoothed positions
                 assert not torch.equal(got["normals"], mesh.vertex_normals(plain)["normals"])
     only = vol.extract(normals=True)
-    _same_device_mesh(only, mesh.vertex_normals(plain))
+    same_device_mesh(only, mesh.vertex_normals(plain))
     assert "smooth" not in only and torch.equal(only["vertices"], plain["vertices"])
     only = vol.extract(smooth_iterations=3)
-    _same_device_mesh(only, mesh.smooth(plain, 3))
+    same_device_mesh(only, mesh.smooth(plain, 3))
     assert "normals" not in only
 
 
@@ -287,6 +252,6 @@ def test_scene_mesh_options_write_the_same_ply_twice(tmp_path):
     assert set(plain) == {"vertices", "faces", "rgb8", "counts", "volume"}
     want = mesh.vertex_normals(mesh.smooth(plain, 3))
     print(f"scene_mesh: {got['counts']}, {got['smooth']}, {got['normal_info']}")
-    _same_device_mesh(got, want)
+    same_device_mesh(got, want)
     assert "volume" in got and files[0] == files[1] and len(files[0]) > 200 and got["counts"][1] > 0
     assert b"property float nx" in files[0][:400]

@@ -12,14 +12,10 @@ from localrf_amd import NativeError, mesh, mesh_raster, novel_views, pointcloud
 from localrf_amd.mesh_raster import rasterize
 from localrf_amd.mesh_texture import INFO_KEYS, TextureBaker, sample_texture, scene_texture
 from mesh_texture_cases import CASE_NAMES, cases, expected, inputs
+from mesh_util import DEV, device_mesh, to_dev
 from novel_views_cases import scene
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-
-
-def _t(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
 
 
 @functools.lru_cache(maxsize=None)
@@ -27,8 +23,7 @@ def _device_case(name):
     c = cases()[name]
     m = c["mesh"]
     frames, depth = inputs(name)
-    dm = {"vertices": _t(m["vertices"]), "faces": _t(m["faces"]), "rgb8": None if m["rgb8"] is None else _t(m["rgb8"])}
-    return dm, _t(frames), _t(depth), _t(c["c2w"])
+    return device_mesh(m), to_dev(frames), to_dev(depth), to_dev(c["c2w"])
 
 
 def _baker(name, **over):

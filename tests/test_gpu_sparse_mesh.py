@@ -7,19 +7,15 @@ import numpy as np
 import pytest
 import torch
 
-from localrf_amd import _native, mesh, novel_views
+from localrf_amd import mesh, novel_views
 from mesh_cases import H_ANALYTIC, closed_manifold_euler, sphere_field
+from mesh_util import DEV, record_launches, same_mesh, to_dev
 from novel_views_cases import scene
 from sparse_mesh_cases import (assign_host, dims_of, extract_blocks_host, face_keys, integrate_blocks_host, lattice_for, new_sparse,
                                random_frames, spread_lattice, touch_host, trajectory)
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 BIG = {(5, 4, 6): lattice_for((5, 4, 6), 0.06, (0.1, 0.0, -3.2)), (10, 8, 10): lattice_for((10, 8, 10), 0.04, (0.1, 0.0, -3.0))}
-
-
-def _t(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
 
 
 def _lat(blocks):
@@ -51,12 +47,12 @@ def _args(case, colours, i0=0, i1=None):
 
 
 def _touch(vol, a, rng):
-    vol.touch(_t(a["depth"]), _t(a["c2w"]), float(a["f"]), (float(a["cx"]), float(a["cy"])), depth_range=rng)
+    vol.touch(to_dev(a["depth"]), to_dev(a["c2w"]), float(a["f"]), (float(a["cx"]), float(a["cy"])), depth_range=rng)
 
 
 def _integrate(vol, a, rng):
-    vol.integrate(_t(a["depth"]), _t(a["c2w"]), float(a["f"]), (float(a["cx"]), float(a["cy"])),
-                  rgb=None if a["rgb8"] is None else _t(a["rgb8"]), depth_range=rng)
+    vol.integrate(to_dev(a["depth"]), to_dev(a["c2w"]), float(a["f"]), (float(a["cx"]), float(a["cy"])),
+                  rgb=None if a["rgb8"] is None else to_dev(a["rgb8"]), depth_range=rng)
 
 
 def _fuse_device(blocks, case, rng, colours):
@@ -82,19 +78,6 @@ def _same_state(vol, sv, pools=True):
             assert tuple(got.shape) == sv[k].shape and np.array_equal(got.cpu().numpy().view(np.uint32), sv[k].view(np.uint32)), k
 
 
-def _same_mesh(got, want):
-    assert got["counts"] == want["counts"], (got["counts"], want["counts"])
-    nv, nf = want["counts"]
-    assert tuple(got["vertices"].shape) == (nv, 3) and tuple(got["faces"].shape) == (nf, 3)
-    assert got["vertices"].dtype is torch.float32 and got["faces"].dtype is torch.int32
-    assert np.array_equal(got["vertices"].cpu().numpy().view(np.uint32), want["vertices"].view(np.uint32))
-    assert np.array_equal(got["faces"].cpu().numpy(), want["faces"])
-    if want["rgb8"] is None:
-        assert got["rgb8"] is None
-    else:
-        assert got["rgb8"].dtype is torch.uint8 and np.array_equal(got["rgb8"].cpu().numpy(), want["rgb8"])
-
-
 def _keys(m):
     return face_keys({"vertices": m["vertices"].cpu().numpy(), "faces": m["faces"].cpu().numpy()})
 
@@ -103,8 +86,8 @@ def _dense_device(blocks, case, rng, colours, i0=0, i1=None):
     origin, voxel, trunc = _lat(blocks)
     ref = mesh.TsdfVolume(origin, voxel, dims_of(blocks), trunc, DEV, colours=colours)
     a = _args(case, colours, i0, i1)
-    ref.integrate(_t(a["depth"]), _t(a["c2w"]), float(a["f"]), (float(a["cx"]), float(a["cy"])),
-                  rgb=None if a["rgb8"] is None else _t(a["rgb8"]), depth_range=rng)
+    ref.integrate(to_dev(a["depth"]), to_dev(a["c2w"]), float(a["f"]), (float(a["cx"]), float(a["cy"])),
+                  rgb=None if a["rgb8"] is None else to_dev(a["rgb8"]), depth_range=rng)
     return ref
 
 
@@ -143,7 +126,7 @@ def test_every_stage_equals_the_restatement_bit_for_bit(blocks):
         dense = _keys(ref.extract())
         for kw in (dict(),) if blocks == (10, 8, 10) else (dict(), dict(level=0.1, min_weight=2.0)):
             got, want = vol.extract(**kw), extract_blocks_host(sv, **kw)
-            _same_mesh(got, want)
+            same_mesh(got, want)
             if not kw:
                 assert _keys(got) <= dense
                 faces += want["counts"][1]
@@ -157,13 +140,7 @@ def test_every_stage_equals_the_restatement_bit_for_bit(blocks):
 def test_a_depth_range_that_excludes_everything_stores_nothing(monkeypatch):
     blocks, case = (3, 2, 2), trajectory(True)
     origin, voxel, trunc = _lat(blocks)
-    launched = []
-    real = _native.launch
-
-    def record(name, *a, **k):
-        launched.append(name)
-        return real(name, *a, **k)
-    monkeypatch.setattr(_native, "launch", record)
+    launched = record_launches(monkeypatch)
     vol = mesh.SparseTsdfVolume(origin, voxel, blocks, trunc, DEV)
     a = _args(case, True)
     _touch(vol, a, (100.0, 200.0))
@@ -188,13 +165,13 @@ def test_the_analytic_sphere_equals_the_dense_mesh():
     vol = mesh.SparseTsdfVolume(o, H_ANALYTIC, blocks, 3 * H_ANALYTIC, DEV, colours=False)
     vol.marks.fill_(1)
     assert vol.allocate() == 27
-    vol.tsdf.copy_(_t(sv["tsdf"]))
+    vol.tsdf.copy_(to_dev(sv["tsdf"]))
     vol.weight.fill_(1.0)
-    assert torch.equal(vol.to_dense()[0], _t(fld))
+    assert torch.equal(vol.to_dense()[0], to_dev(fld))
     got = vol.extract()
-    _same_mesh(got, extract_blocks_host(sv))
+    same_mesh(got, extract_blocks_host(sv))
     assert closed_manifold_euler({"vertices": got["vertices"].cpu().numpy(), "faces": got["faces"].cpu().numpy()}) == 2
-    assert _keys(got) == _keys(mesh.extract_mesh(_t(fld), o, H_ANALYTIC, 0.0))
+    assert _keys(got) == _keys(mesh.extract_mesh(to_dev(fld), o, H_ANALYTIC, 0.0))
     # a plane through every block, seen by every frame: the sparse mesh of the trajectory's clean depth equals the dense one
     vol = _fuse_device((5, 4, 6), trajectory(True), (0.0, np.inf), True)
     assert _keys(vol.extract()) == _keys(_dense_device((5, 4, 6), trajectory(True), (0.0, np.inf), True).extract())
@@ -237,7 +214,7 @@ def test_incremental_use():
         early[8 * bz:8 * bz + 8, 8 * by:8 * by + 8, 8 * bx:8 * bx + 8] = True
     _pools_equal_dense(b, _dense_device(blocks, case, rng, True), stored=early)             # the first blocks saw every frame
     _pools_equal_dense(b, _dense_device(blocks, case, rng, True, k, None), stored=mask & ~early)   # the appended ones frames k..V
-    _same_mesh(b.extract(), extract_blocks_host(sv))
+    same_mesh(b.extract(), extract_blocks_host(sv))
 
 
 def test_two_runs_are_equal_and_a_side_stream_gives_the_same():

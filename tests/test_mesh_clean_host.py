@@ -14,6 +14,7 @@ from localrf_amd import NativeError, mesh
 from mesh_cases import closed_manifold_euler
 from mesh_clean_cases import (BLOB_FACES, MESH_NAMES, all_meshes, base_meshes, components_host, expected, fan, filter_host,
                               labels_bfs, labels_host, labels_host_arrays, threshold_host)
+from mesh_util import DenseStub, cpu_mesh, forbid_native, forbid_render
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMBOLS = ("lrf_mesh_components_init", "lrf_mesh_components_round", "lrf_mesh_components_count",
@@ -97,24 +98,9 @@ def test_thresholds_0_and_1_on_stray_vertices():
         assert out[k].tobytes() == clean[k].tobytes(), k
 
 
-def _cpu_mesh(rgb=True):
-    return {"vertices": torch.zeros(4, 3), "faces": torch.tensor([[0, 1, 2], [1, 2, 3]], dtype=torch.int32),
-            "rgb8": torch.zeros(4, 3, dtype=torch.uint8) if rgb else None, "counts": (4, 2)}
-
-
-class _Vol(mesh.TsdfVolume):
-    def __init__(self):
-        self.origin, self.voxel, self.dims, self.trunc = (0.0, 0.0, 0.0), 0.1, (3, 3, 3), 0.3
-        self.tsdf, self.weight, self.rgb = torch.ones(3, 3, 3), torch.zeros(3, 3, 3), None
-
-
 def test_python_refusals_before_any_native_call(monkeypatch):
-    def forbidden(*a, **k):
-        raise AssertionError("a native call was reached")
-    from localrf_amd import _native
-    for name in ("launch", "call", "workspace"):
-        monkeypatch.setattr(_native, name, forbidden)
-    faces = _cpu_mesh()["faces"]
+    forbid_native(monkeypatch)
+    faces = cpu_mesh()["faces"]
     with pytest.raises(TypeError, match="faces"):
         mesh.components(faces.numpy(), 4)
     for f, nv, match in ((faces.long(), 4, "int32"), (faces[:, :2], 4, "int32"), (faces.reshape(-1), 4, "int32"),
@@ -131,40 +117,36 @@ def test_python_refusals_before_any_native_call(monkeypatch):
         mesh.filter_components([torch.zeros(4, 3), faces])
     for key, bad in (("vertices", np.zeros((4, 3), np.float32)), ("faces", faces.numpy()), ("rgb8", np.zeros((4, 3), np.uint8))):
         with pytest.raises(TypeError, match=key):
-            mesh.filter_components(dict(_cpu_mesh(), **{key: bad}))
+            mesh.filter_components(dict(cpu_mesh(), **{key: bad}))
     for key, bad, match in (("vertices", torch.zeros(4, 3, dtype=torch.float64), "vertices"), ("vertices", torch.zeros(4, 2), "vertices"),
                             ("faces", faces.long(), "faces"), ("faces", faces.t().contiguous(), "faces"),
                             ("rgb8", torch.zeros(4, 3), "rgb8"), ("rgb8", torch.zeros(3, 3, dtype=torch.uint8), "rgb8")):
         with pytest.raises(ValueError, match=match):
-            mesh.filter_components(dict(_cpu_mesh(), **{key: bad}))
+            mesh.filter_components(dict(cpu_mesh(), **{key: bad}))
     for kw, match in ((dict(min_faces=-1), "min_faces"), (dict(min_faces=1.5), "min_faces"), (dict(min_faces=math.nan), "min_faces"),
                       (dict(min_faces=None), "min_faces"), (dict(min_fraction=-0.1), "min_fraction"),
                       (dict(min_fraction=1.01), "min_fraction"), (dict(min_fraction=math.nan), "min_fraction"),
                       (dict(max_rounds=0), "max_rounds")):
         with pytest.raises(ValueError, match=match):
-            mesh.filter_components(_cpu_mesh(), **kw)
+            mesh.filter_components(cpu_mesh(), **kw)
     for rgb in (True, False):
         with pytest.raises(NativeError):
-            mesh.filter_components(_cpu_mesh(rgb), min_faces=1)
+            mesh.filter_components(cpu_mesh(rgb), min_faces=1)
     # the extract options are checked with the other arguments, before the extraction
     for kw, match in ((dict(min_component_faces=-1), "min_component_faces"), (dict(min_component_fraction=2.0), "min_component_fraction"),
                       (dict(min_component_fraction=math.nan), "min_component_fraction")):
         with pytest.raises(ValueError, match=match):
-            _Vol().extract(**kw)
+            DenseStub(colours=False).extract(**kw)
     with pytest.raises(TypeError):
-        _Vol().extract(0.0, 1.0, None, None, 5)                         # keyword-only
+        DenseStub(colours=False).extract(0.0, 1.0, None, None, 5)                         # keyword-only
     assert "min_component_faces" in mesh._MESH_KEYS and "min_component_fraction" in mesh._MESH_KEYS
 
 
 def test_scene_mesh_checks_the_component_options_before_it_renders(monkeypatch):
-    from localrf_amd import novel_views
     from novel_views_cases import scene
     lt, g = scene("cpu")
     W, H = int(g["W"]), int(g["H"])
-
-    def forbidden(*a, **k):
-        raise AssertionError("a render was reached before the refusal")
-    monkeypatch.setattr(novel_views, "render_poses", forbidden)
+    forbid_render(monkeypatch)
     box = ((-1.0, -1.0, -1.0), (1.0, 1.0, 1.0))
     for kw, match in ((dict(min_component_faces=-2), "min_component_faces"), (dict(min_component_fraction=1.5), "min_component_fraction")):
         with pytest.raises(ValueError, match=match):

@@ -25,6 +25,7 @@ from mesh_distance_cases import (CASE_NAMES, CLAMP, QUERY_SIZES, SAMPLE_CASES, S
                                  grid_host, grid_search_host, mean_edge, pair_host, sample_host, slabs, summary_host, summary_inputs,
                                  used_faces)
 from mesh_clean_cases import permute_faces
+from mesh_util import cpu_mesh, forbid_native
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMBOLS = ("lrf_mesh_index_bounds", "lrf_mesh_index_workspace_bytes", "lrf_mesh_index_build", "lrf_mesh_closest", "lrf_mesh_sample_count",
@@ -215,43 +216,35 @@ def test_the_sums_cannot_overflow():
     assert s["sum"] == 10 * per_entry_1 and s["sum_sq"] == 10 * per_entry_2
 
 
-def _cpu_mesh():
-    return {"vertices": torch.zeros(4, 3), "faces": torch.tensor([[0, 1, 2], [1, 2, 3]], dtype=torch.int32), "rgb8": None, "counts": (4, 2)}
-
-
 def test_python_refusals_before_any_native_call(monkeypatch):
-    def forbidden(*a, **k):
-        raise AssertionError("a native call was reached")
-    from localrf_amd import _native
-    for name in ("launch", "call", "workspace", "lib"):
-        monkeypatch.setattr(_native, name, forbidden)
+    forbid_native(monkeypatch)
     with pytest.raises(TypeError, match="mesh"):
         MeshIndex([torch.zeros(4, 3)])
-    for key, bad in (("vertices", torch.zeros(4, 3, dtype=torch.float64)), ("vertices", torch.zeros(4, 2)), ("faces", _cpu_mesh()["faces"].long())):
+    for key, bad in (("vertices", torch.zeros(4, 3, dtype=torch.float64)), ("vertices", torch.zeros(4, 2)), ("faces", cpu_mesh(rgb=False)["faces"].long())):
         with pytest.raises(ValueError, match=key):
-            MeshIndex(dict(_cpu_mesh(), **{key: bad}))
+            MeshIndex(dict(cpu_mesh(rgb=False), **{key: bad}))
         with pytest.raises(ValueError, match=key):
-            sample_surface(dict(_cpu_mesh(), **{key: bad}), 0.1)
+            sample_surface(dict(cpu_mesh(rgb=False), **{key: bad}), 0.1)
         with pytest.raises(ValueError, match=key):
-            mesh_distance.mesh_distance(_cpu_mesh(), dict(_cpu_mesh(), **{key: bad}), 0.1)
+            mesh_distance.mesh_distance(cpu_mesh(rgb=False), dict(cpu_mesh(rgb=False), **{key: bad}), 0.1)
     for bad in (0, -1.0, math.nan, math.inf, True, "a"):
         with pytest.raises(ValueError, match="cell"):
-            MeshIndex(_cpu_mesh(), cell=bad)
+            MeshIndex(cpu_mesh(rgb=False), cell=bad)
         with pytest.raises(ValueError, match="spacing"):
-            sample_surface(_cpu_mesh(), bad)
+            sample_surface(cpu_mesh(rgb=False), bad)
         with pytest.raises(ValueError, match="spacing"):
-            mesh_distance.mesh_distance(_cpu_mesh(), _cpu_mesh(), bad)
+            mesh_distance.mesh_distance(cpu_mesh(rgb=False), cpu_mesh(rgb=False), bad)
         with pytest.raises(ValueError, match="unit"):
             distance_summary(torch.zeros(3), unit=bad)
         with pytest.raises(ValueError, match="threshold"):
             distance_summary(torch.zeros(3), thresholds=(0.1, bad))
         with pytest.raises(ValueError, match="threshold"):
-            cloud_to_mesh(torch.zeros(3, 3), _cpu_mesh(), thresholds=(bad,))
+            cloud_to_mesh(torch.zeros(3, 3), cpu_mesh(rgb=False), thresholds=(bad,))
     for bad in (-1, 1.5, None, True):
         with pytest.raises(ValueError, match="max_bytes"):
-            MeshIndex(_cpu_mesh(), max_bytes=bad)
+            MeshIndex(cpu_mesh(rgb=False), max_bytes=bad)
         with pytest.raises(ValueError, match="max_points"):
-            sample_surface(_cpu_mesh(), 0.1, max_points=bad)
+            sample_surface(cpu_mesh(rgb=False), 0.1, max_points=bad)
     with pytest.raises(ValueError, match="at most 8"):
         distance_summary(torch.zeros(3), thresholds=[0.1] * 9)
     with pytest.raises(ValueError, match="threshold"):
@@ -261,20 +254,20 @@ def test_python_refusals_before_any_native_call(monkeypatch):
     with pytest.raises(ValueError, match="float32"):
         distance_summary(torch.zeros(3, dtype=torch.float64))
     with pytest.raises(TypeError, match="points"):
-        cloud_to_mesh(np.zeros((3, 3), np.float32), _cpu_mesh())
+        cloud_to_mesh(np.zeros((3, 3), np.float32), cpu_mesh(rgb=False))
     for bad in (torch.zeros(3, 2), torch.zeros(3), torch.zeros(3, 3, dtype=torch.float64)):
         with pytest.raises(ValueError, match="points"):
-            cloud_to_mesh(bad, _cpu_mesh())
+            cloud_to_mesh(bad, cpu_mesh(rgb=False))
     for bad in (-0.5, math.nan, True, "far"):
         with pytest.raises(ValueError, match="max_distance"):
-            cloud_to_mesh(torch.zeros(3, 3), _cpu_mesh(), max_distance=bad)
+            cloud_to_mesh(torch.zeros(3, 3), cpu_mesh(rgb=False), max_distance=bad)
         with pytest.raises(ValueError, match="max_distance"):
-            mesh_distance.mesh_distance(_cpu_mesh(), _cpu_mesh(), 0.1, max_distance=bad)
+            mesh_distance.mesh_distance(cpu_mesh(rgb=False), cpu_mesh(rgb=False), 0.1, max_distance=bad)
     with pytest.raises(TypeError, match="mesh_or_index"):
         cloud_to_mesh(torch.zeros(3, 3), None)
-    for call in (lambda: MeshIndex(_cpu_mesh()), lambda: MeshIndex(_cpu_mesh(), cell=0.5), lambda: sample_surface(_cpu_mesh(), 0.1),
-                 lambda: distance_summary(torch.zeros(3), (0.1, 0.2), 2.0), lambda: cloud_to_mesh(torch.zeros(3, 3), _cpu_mesh(), (0.1,), 1.0),
-                 lambda: mesh_distance.mesh_distance(_cpu_mesh(), _cpu_mesh(), 0.1, (0.05,), math.inf)):
+    for call in (lambda: MeshIndex(cpu_mesh(rgb=False)), lambda: MeshIndex(cpu_mesh(rgb=False), cell=0.5), lambda: sample_surface(cpu_mesh(rgb=False), 0.1),
+                 lambda: distance_summary(torch.zeros(3), (0.1, 0.2), 2.0), lambda: cloud_to_mesh(torch.zeros(3, 3), cpu_mesh(rgb=False), (0.1,), 1.0),
+                 lambda: mesh_distance.mesh_distance(cpu_mesh(rgb=False), cpu_mesh(rgb=False), 0.1, (0.05,), math.inf)):
         with pytest.raises(NativeError):                                        # accepted arguments on the CPU: no fallback
             call()
 

@@ -13,14 +13,11 @@ from localrf_amd.mesh import fill_holes, holes  # noqa: F401  (what every test h
 from mesh_fill_cases import (CASE_NAMES, CLOSABLE, E2E_BLOCK, HOLE_KEYS, UNCHANGED, boundary_host, cases, e2e_mesh_host, expected, fill_host,
                              loops_host)
 from mesh_smooth_cases import topology_host
+from mesh_util import DenseStub, bits, cpu_mesh, forbid_native, forbid_render
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMBOLS = ("lrf_mesh_holes_workspace_bytes", "lrf_mesh_holes", "lrf_mesh_fill")
 KERNELS = ("k_hf_zero", "k_hf_edges", "k_hf_next", "k_hf_lead", "k_hf_members", "k_hf_loops", "k_hf_emit", "k_hf_bytes", "k_hf_info")
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 def test_case_names_are_fixed_and_say_what_they_are():
@@ -59,7 +56,7 @@ def test_properties_of_the_restatement(name):
     fill = r["fill"]
     # the input is the output's prefix, bit for bit
     assert r["vertices"].shape == (nv + fill["loops"], 3) and r["faces"].shape == (nf + fill["loop_edges"], 3)
-    assert np.array_equal(_bits(r["vertices"][:nv]), _bits(m["vertices"])) and np.array_equal(r["faces"][:nf], m["faces"])
+    assert np.array_equal(bits(r["vertices"][:nv]), bits(m["vertices"])) and np.array_equal(r["faces"][:nf], m["faces"])
     assert (r["rgb8"] is None) == (m["rgb8"] is None)
     if m["rgb8"] is not None:
         assert r["rgb8"].shape == (nv + fill["loops"], 3) and np.array_equal(r["rgb8"][:nv], m["rgb8"])
@@ -107,7 +104,7 @@ def test_the_set_of_new_vertices_does_not_depend_on_the_order_of_the_faces(name)
     nv = m["vertices"].shape[0]
 
     def new_rows(r):
-        v = _bits(r["vertices"][nv:]).astype(np.int64)
+        v = bits(r["vertices"][nv:]).astype(np.int64)
         rows = np.concatenate([v, r["rgb8"][nv:].astype(np.int64)], 1) if r["rgb8"] is not None else v
         return sorted(map(tuple, rows.tolist()))
     want = expected(name)
@@ -119,7 +116,7 @@ def test_the_set_of_new_vertices_does_not_depend_on_the_order_of_the_faces(name)
         got = fill_host(dict(m, faces=np.ascontiguousarray(f)), max_edges)
         assert got["fill"] == want["fill"] and new_rows(got) == new_rows(want)
         if name == "sphere minus 20":                                       # ... their order does
-            assert not np.array_equal(_bits(got["vertices"]), _bits(want["vertices"]))
+            assert not np.array_equal(bits(got["vertices"]), bits(want["vertices"]))
 
 
 def test_the_punched_volume_leaves_one_simple_loop():
@@ -130,46 +127,32 @@ def test_the_punched_volume_leaves_one_simple_loop():
     assert topology_host(fill_host(m, 64))["closed"] is True
 
 
-def _cpu_mesh():
-    return {"vertices": torch.zeros(4, 3), "faces": torch.tensor([[0, 1, 2], [1, 2, 3]], dtype=torch.int32), "rgb8": None, "counts": (4, 2)}
-
-
-class _Vol(mesh.TsdfVolume):
-    def __init__(self):
-        self.origin, self.voxel, self.dims, self.trunc = (0.0, 0.0, 0.0), 0.1, (3, 3, 3), 0.3
-        self.tsdf, self.weight, self.rgb = torch.ones(3, 3, 3), torch.zeros(3, 3, 3), None
-
-
 def test_python_refusals_before_any_native_call(monkeypatch):
-    def forbidden(*a, **k):
-        raise AssertionError("a native call was reached")
-    from localrf_amd import _native
-    for name in ("launch", "call", "workspace", "lib"):
-        monkeypatch.setattr(_native, name, forbidden)
-    faces = _cpu_mesh()["faces"]
+    forbid_native(monkeypatch)
+    faces = cpu_mesh(rgb=False)["faces"]
     for fn in (mesh.holes, mesh.fill_holes):
         with pytest.raises(TypeError, match="mesh"):
             fn([torch.zeros(4, 3), faces])
         for key, bad in (("vertices", np.zeros((4, 3), np.float32)), ("faces", faces.numpy())):
             with pytest.raises(TypeError, match=key):
-                fn(dict(_cpu_mesh(), **{key: bad}))
+                fn(dict(cpu_mesh(rgb=False), **{key: bad}))
         for key, bad in (("vertices", torch.zeros(4, 3, dtype=torch.float64)), ("vertices", torch.zeros(4, 2)), ("faces", faces.long()),
                          ("faces", faces.t().contiguous()), ("rgb8", torch.zeros(4, 3))):
             with pytest.raises(ValueError, match=key):
-                fn(dict(_cpu_mesh(), **{key: bad}))
+                fn(dict(cpu_mesh(rgb=False), **{key: bad}))
         for bad in (2, 0, -1, 4097, 1.5, None, "ten", True, math.nan):          # 2: what "fan 3" would need to stay open
             with pytest.raises(ValueError, match="max_edges"):
-                fn(_cpu_mesh(), max_edges=bad)
+                fn(cpu_mesh(rgb=False), max_edges=bad)
         with pytest.raises(ValueError, match="vertices"):                      # dtype and shape come before the other arguments
-            fn(dict(_cpu_mesh(), vertices=torch.zeros(4, 2)), max_edges=2)
+            fn(dict(cpu_mesh(rgb=False), vertices=torch.zeros(4, 2)), max_edges=2)
         for ok in (3, 64, 4096):
             with pytest.raises(NativeError):                                    # a valid mesh on the CPU: no fallback
-                fn(_cpu_mesh(), max_edges=ok)
+                fn(cpu_mesh(rgb=False), max_edges=ok)
         with pytest.raises(NativeError):
-            fn(_cpu_mesh())
+            fn(cpu_mesh(rgb=False))
     # the extract option is checked with the other arguments, before the extraction
     sparse = mesh.SparseTsdfVolume.__new__(mesh.SparseTsdfVolume)
-    for vol in (_Vol(), sparse):
+    for vol in (DenseStub(colours=False), sparse):
         for bad in (-1, 1, 2, 4097, 2.5, "three", True, None):
             with pytest.raises(ValueError, match="fill_holes"):
                 vol.extract(fill_holes=bad)
@@ -180,14 +163,10 @@ def test_python_refusals_before_any_native_call(monkeypatch):
 
 
 def test_scene_mesh_checks_the_option_before_it_renders(monkeypatch):
-    from localrf_amd import novel_views
     from novel_views_cases import scene
     lt, g = scene("cpu")
     W, H = int(g["W"]), int(g["H"])
-
-    def forbidden(*a, **k):
-        raise AssertionError("a render was reached before the refusal")
-    monkeypatch.setattr(novel_views, "render_poses", forbidden)
+    forbid_render(monkeypatch)
     box = ((-1.0, -1.0, -1.0), (1.0, 1.0, 1.0))
     for bad in (-1, 2, 4097, 0.5, "three", True):
         with pytest.raises(ValueError, match="fill_holes"):

@@ -13,6 +13,7 @@ import torch
 from localrf_amd import NativeError, mesh, pointcloud
 from mesh_cases import (H_ANALYTIC, N_ANALYTIC, SPHERE_C, SPHERE_R, boundary_edges, closed_manifold_euler, extract_host,
                         integrate_host, new_volume, signed_volume, sphere_field, tet_case, tet_corners, torus_field)
+from mesh_util import DenseStub, forbid_native, forbid_render
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -137,20 +138,8 @@ def _frames():
                 rgb=torch.zeros(2, 4, 5, 3))
 
 
-class _Vol(mesh.TsdfVolume):
-    """A TsdfVolume on the CPU, for the refusals that come before the device check of integrate."""
-    def __init__(self, colours=True):
-        self.origin, self.voxel, self.dims, self.trunc = (0.0, 0.0, 0.0), 0.1, (3, 3, 3), 0.3
-        self.tsdf, self.weight = torch.ones(3, 3, 3), torch.zeros(3, 3, 3)
-        self.rgb = torch.zeros(3, 3, 3, 3) if colours else None
-
-
 def test_python_refusals_before_any_device_work(monkeypatch):
-    def forbidden(*a, **k):
-        raise AssertionError("a native call was reached")
-    from localrf_amd import _native
-    for name in ("launch", "call", "workspace"):
-        monkeypatch.setattr(_native, name, forbidden)
+    forbid_native(monkeypatch)
     V = mesh.TsdfVolume
     for bad, match in ((dict(origin=(0, 0)), "origin"), (dict(origin=(0, math.nan, 0)), "origin"), (dict(voxel=0), "voxel"),
                        (dict(voxel=-1.0), "voxel"), (dict(voxel=math.nan), "voxel"), (dict(dims=(3, 3)), "dims"),
@@ -166,7 +155,7 @@ def test_python_refusals_before_any_device_work(monkeypatch):
     def integrate(vol=None, **over):
         a = _frames()
         a.update(over)
-        return (vol or _Vol()).integrate(a["depth"], a["poses"], a["focal"], a["center"], rgb=a["rgb"],
+        return (vol or DenseStub()).integrate(a["depth"], a["poses"], a["focal"], a["center"], rgb=a["rgb"],
                                          **{k: v for k, v in a.items() if k == "depth_range"})
     for bad, match in ((dict(depth=torch.ones(4, 5)), "depth"), (dict(depth=torch.ones(2, 4, 5).long()), "depth"),
                        (dict(rgb=None), "colours"), (dict(rgb=torch.zeros(2, 4, 5, 2)), "rgb"),
@@ -177,17 +166,17 @@ def test_python_refusals_before_any_device_work(monkeypatch):
         with pytest.raises(ValueError, match=match):
             integrate(**bad)
     with pytest.raises(ValueError, match="colours"):
-        integrate(vol=_Vol(colours=False))
+        integrate(vol=DenseStub(colours=False))
     with pytest.raises(TypeError):
         integrate(depth=np.ones((2, 4, 5), np.float32))
     with pytest.raises(NativeError):                                    # valid arguments, CPU tensors: no fallback
         integrate()
     with pytest.raises(NativeError):
-        integrate(vol=_Vol(colours=False), rgb=None)
+        integrate(vol=DenseStub(colours=False), rgb=None)
     for bad, match in ((dict(level=math.nan), "level"), (dict(min_weight=0), "min_weight"), (dict(min_weight=math.nan), "min_weight"),
                        (dict(max_vertices=-1), "max_vertices"), (dict(max_faces=1.5), "max_faces"), (dict(max_faces=1 << 31), "max_faces")):
         with pytest.raises(ValueError, match=match):
-            _Vol().extract(**bad)
+            DenseStub().extract(**bad)
     vals = torch.zeros(3, 4, 5)
     for args, kw, match in (((torch.zeros(4, 5), (0, 0, 0), 0.1, 0.0), {}, "values"), ((vals.long(), (0, 0, 0), 0.1, 0.0), {}, "values"),
                             ((vals, (0, 0), 0.1, 0.0), {}, "origin"), ((vals, (0, 0, 0), 0.0, 0.0), {}, "voxel"),
@@ -205,14 +194,10 @@ def test_python_refusals_before_any_device_work(monkeypatch):
 
 
 def test_scene_mesh_refusals_on_a_cpu_scene(monkeypatch):
-    from localrf_amd import novel_views
     from novel_views_cases import scene
     lt, g = scene("cpu")
     W, H = int(g["W"]), int(g["H"])
-
-    def forbidden(*a, **k):
-        raise AssertionError("a render was reached before the refusal")
-    monkeypatch.setattr(novel_views, "render_poses", forbidden)
+    forbid_render(monkeypatch)
     box = ((-1.0, -1.0, -1.0), (1.0, 1.0, 1.0))
     need = 21 * 21 * 21 * 20
     with pytest.raises(ValueError, match=f"{need} bytes"):
@@ -238,6 +223,41 @@ def test_scene_mesh_refusals_on_a_cpu_scene(monkeypatch):
         mesh.scene_mesh(lt, W, H, voxel=0.1, bounds=box)
     with pytest.raises(NativeError):
         mesh.scene_mesh(lt, W, H, voxel=0.1)
+
+
+# the options of the post-processing chain in the order in which bad values are reported, one refused value each
+CHAIN_BAD = (("min_component_faces", -1), ("min_component_fraction", 2.0), ("simplify_cell", 0), ("smooth_iterations", -1),
+             ("normals", 1), ("fill_holes", 2))
+
+
+def test_bad_chain_options_are_refused_in_one_order_at_every_entry_point(monkeypatch):
+    """Of two bad options the one that comes first in CHAIN_BAD is named, a bad level wins over all of them, and both extract
+    methods and scene_mesh say the same."""
+    from novel_views_cases import scene
+    forbid_native(monkeypatch)
+    forbid_render(monkeypatch)
+    lt, g = scene("cpu")
+    W, H = int(g["W"]), int(g["H"])
+    box = ((-1.0, -1.0, -1.0), (1.0, 1.0, 1.0))
+    entries = (DenseStub().extract, mesh.SparseTsdfVolume.__new__(mesh.SparseTsdfVolume).extract,
+               lambda **kw: mesh.scene_mesh(lt, W, H, voxel=0.1, bounds=box, **kw))
+
+    def refusals(**kw):
+        said = []
+        for entry in entries:
+            with pytest.raises(ValueError) as e:
+                entry(**kw)
+            said.append(str(e.value))
+        assert said[0] == said[1] == said[2], said
+        return said[0]
+    for i, (first, bad) in enumerate(CHAIN_BAD):
+        assert first in refusals(**{first: bad})
+        assert "level" in refusals(level=math.nan, **{first: bad})
+        for second, worse in CHAIN_BAD[i + 1:]:
+            said = refusals(**{first: bad, second: worse})
+            assert first in said and second not in said, (first, second, said)
+    assert "level" in refusals(level=math.nan, **dict(CHAIN_BAD))
+    assert all(mesh._MESH_KEYS.count(name) == 1 for name, _ in CHAIN_BAD) and len(mesh._MESH_KEYS) == 7 + len(CHAIN_BAD)
 
 
 def _read_ply(raw):

@@ -18,6 +18,7 @@ from localrf_amd.mesh_raster import depth_agreement, rasterize, scene_mesh_agree
 from mesh_raster_cases import (AGREEMENT_SHAPES, AGREEMENT_TOLS, AG_SCALE, BOX_FACE, CASE_NAMES, SMALL_MAX, SPHERE_KIND,
                                SPHERE_NONDEGENERATE, agreement_host, agreement_maps, box_host, cases, expected, moller_trumbore,
                                octa_sphere, to_camera)
+from mesh_util import cpu_mesh, forbid_native, forbid_render
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMBOLS = ("lrf_mesh_rasterize_workspace_bytes", "lrf_mesh_rasterize", "lrf_depth_agreement")
@@ -168,28 +169,20 @@ def test_agreement_restatement_against_plain_numpy(shape):
     assert (np.diff(words[:, 8:8 + len(AGREEMENT_TOLS)], axis=1) >= 0).all()
 
 
-def _cpu_mesh():
-    return {"vertices": torch.zeros(4, 3), "faces": torch.tensor([[0, 1, 2], [1, 2, 3]], dtype=torch.int32), "rgb8": None, "counts": (4, 2)}
-
-
 def test_python_refusals_before_any_native_call(monkeypatch):
-    def forbidden(*a, **k):
-        raise AssertionError("a native call was reached")
-    from localrf_amd import _native
-    for name in ("launch", "call", "workspace", "lib"):
-        monkeypatch.setattr(_native, name, forbidden)
+    forbid_native(monkeypatch)
     poses = torch.eye(4)[None, :3].repeat(2, 1, 1)
     ok = dict(poses=poses, W=8, H=6, focal=5.0, center=(4.0, 3.0))
 
     def ras(mesh=None, **over):
         kw = dict(ok, **over)
-        return rasterize(_cpu_mesh() if mesh is None else mesh, kw.pop("poses"), kw.pop("W"), kw.pop("H"), kw.pop("focal"), kw.pop("center"), **kw)
+        return rasterize(cpu_mesh(rgb=False) if mesh is None else mesh, kw.pop("poses"), kw.pop("W"), kw.pop("H"), kw.pop("focal"), kw.pop("center"), **kw)
     with pytest.raises(TypeError, match="mesh"):
         ras(mesh=[torch.zeros(4, 3)])
     for key, bad in (("vertices", torch.zeros(4, 3, dtype=torch.float64)), ("vertices", torch.zeros(4, 2)),
-                     ("faces", _cpu_mesh()["faces"].long()), ("rgb8", torch.zeros(4, 3))):
+                     ("faces", cpu_mesh(rgb=False)["faces"].long()), ("rgb8", torch.zeros(4, 3))):
         with pytest.raises(ValueError, match=key):
-            ras(mesh=dict(_cpu_mesh(), **{key: bad}))
+            ras(mesh=dict(cpu_mesh(rgb=False), **{key: bad}))
     for bad in (torch.zeros(2, 3, 3), torch.zeros(3, 4), torch.zeros(2, 3, 4, dtype=torch.int32)):
         with pytest.raises(ValueError, match="poses"):
             ras(poses=bad)
@@ -249,17 +242,12 @@ def test_python_refusals_before_any_native_call(monkeypatch):
 
 
 def test_scene_mesh_agreement_checks_before_it_renders(monkeypatch):
-    from localrf_amd import depth_quantiles, novel_views
+    from localrf_amd import depth_quantiles
     from novel_views_cases import scene
     lt, g = scene("cpu")
     W, H = int(g["W"]), int(g["H"])
-
-    def forbidden(*a, **k):
-        raise AssertionError("a render was reached before the refusal")
-    monkeypatch.setattr(novel_views, "render_poses", forbidden)
-    monkeypatch.setattr(depth_quantiles, "fusion_depth", forbidden)
-    monkeypatch.setattr(mesh_raster, "rasterize", forbidden)
-    m = _cpu_mesh()
+    forbid_render(monkeypatch, (depth_quantiles, "fusion_depth"), (mesh_raster, "rasterize"))
+    m = cpu_mesh(rgb=False)
     with pytest.raises(ValueError, match="depth must be"):
         scene_mesh_agreement(lt, m, W, H, depth="mean")
     with pytest.raises(TypeError, match="unknown options"):

@@ -13,6 +13,7 @@ from localrf_amd import NativeError, mesh
 from mesh_cases import H_ANALYTIC
 from mesh_simplify_cases import (CASE_NAMES, canonical, cases, cells_host, expected_simplified, face_keys, simplify_host,
                                  smallest_blob)
+from mesh_util import DenseStub, cpu_mesh, forbid_native, forbid_render
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMBOLS = ("lrf_mesh_simplify_bounds", "lrf_mesh_simplify_workspace_bytes", "lrf_mesh_simplify")
@@ -102,52 +103,37 @@ def test_known_counts():
     assert bad.tolist() == [True, True, True, True, False]
 
 
-def _cpu_mesh(rgb=True):
-    return {"vertices": torch.zeros(4, 3), "faces": torch.tensor([[0, 1, 2], [1, 2, 3]], dtype=torch.int32),
-            "rgb8": torch.zeros(4, 3, dtype=torch.uint8) if rgb else None, "counts": (4, 2)}
-
-
-class _Vol(mesh.TsdfVolume):
-    def __init__(self):
-        self.origin, self.voxel, self.dims, self.trunc = (0.0, 0.0, 0.0), 0.1, (3, 3, 3), 0.3
-        self.tsdf, self.weight, self.rgb = torch.ones(3, 3, 3), torch.zeros(3, 3, 3), None
-
-
 def test_python_refusals_before_any_native_call(monkeypatch):
-    def forbidden(*a, **k):
-        raise AssertionError("a native call was reached")
-    from localrf_amd import _native
-    for name in ("launch", "call", "workspace", "lib"):
-        monkeypatch.setattr(_native, name, forbidden)
-    faces = _cpu_mesh()["faces"]
+    forbid_native(monkeypatch)
+    faces = cpu_mesh()["faces"]
     with pytest.raises(TypeError, match="mesh"):
         mesh.simplify([torch.zeros(4, 3), faces], 1.0)
     for key, bad in (("vertices", np.zeros((4, 3), np.float32)), ("faces", faces.numpy()), ("rgb8", np.zeros((4, 3), np.uint8))):
         with pytest.raises(TypeError, match=key):
-            mesh.simplify(dict(_cpu_mesh(), **{key: bad}), 1.0)
+            mesh.simplify(dict(cpu_mesh(), **{key: bad}), 1.0)
     for key, bad, match in (("vertices", torch.zeros(4, 3, dtype=torch.float64), "vertices"), ("vertices", torch.zeros(4, 2), "vertices"),
                             ("faces", faces.long(), "faces"), ("faces", faces.t().contiguous(), "faces"),
                             ("rgb8", torch.zeros(4, 3), "rgb8"), ("rgb8", torch.zeros(3, 3, dtype=torch.uint8), "rgb8")):
         with pytest.raises(ValueError, match=match):
-            mesh.simplify(dict(_cpu_mesh(), **{key: bad}), 1.0)
+            mesh.simplify(dict(cpu_mesh(), **{key: bad}), 1.0)
     for bad in (0, 0.0, -1.0, math.nan, math.inf, None, "wide", True):
         with pytest.raises(ValueError, match="cell"):
-            mesh.simplify(_cpu_mesh(), bad)
+            mesh.simplify(cpu_mesh(), bad)
     for bad in ((0.0, 0.0), (0.0, 0.0, math.nan), (0.0, math.inf, 0.0), 1.0, None, "abc", (0, 0, 0, 0)):
         with pytest.raises(ValueError, match="origin"):
-            mesh.simplify(_cpu_mesh(), 1.0, origin=bad)
+            mesh.simplify(cpu_mesh(), 1.0, origin=bad)
     for bad in (1, 0, None, "yes"):
         with pytest.raises(ValueError, match="dedupe"):
-            mesh.simplify(_cpu_mesh(), 1.0, dedupe=bad)
+            mesh.simplify(cpu_mesh(), 1.0, dedupe=bad)
     for bad in (-1, 1.5, None, math.nan, True):
         with pytest.raises(ValueError, match="max_bytes"):
-            mesh.simplify(_cpu_mesh(), 1.0, max_bytes=bad)
+            mesh.simplify(cpu_mesh(), 1.0, max_bytes=bad)
     for rgb in (True, False):
         with pytest.raises(NativeError):                                # valid arguments, CPU tensors: no fallback
-            mesh.simplify(_cpu_mesh(rgb), 1.0, origin=(0.5, 0.25, -1.0), dedupe=False, max_bytes=1 << 20)
+            mesh.simplify(cpu_mesh(rgb), 1.0, origin=(0.5, 0.25, -1.0), dedupe=False, max_bytes=1 << 20)
     # the extract option is checked with the other arguments, before the extraction
     sparse = mesh.SparseTsdfVolume.__new__(mesh.SparseTsdfVolume)
-    for vol in (_Vol(), sparse):
+    for vol in (DenseStub(colours=False), sparse):
         for bad in (0, -0.5, math.nan, math.inf, "wide", True):
             with pytest.raises(ValueError, match="simplify_cell"):
                 vol.extract(simplify_cell=bad)
@@ -157,14 +143,10 @@ def test_python_refusals_before_any_native_call(monkeypatch):
 
 
 def test_scene_mesh_checks_simplify_cell_before_it_renders(monkeypatch):
-    from localrf_amd import novel_views
     from novel_views_cases import scene
     lt, g = scene("cpu")
     W, H = int(g["W"]), int(g["H"])
-
-    def forbidden(*a, **k):
-        raise AssertionError("a render was reached before the refusal")
-    monkeypatch.setattr(novel_views, "render_poses", forbidden)
+    forbid_render(monkeypatch)
     box = ((-1.0, -1.0, -1.0), (1.0, 1.0, 1.0))
     for bad in (0, -2.0, math.nan, "wide"):
         with pytest.raises(ValueError, match="simplify_cell"):

@@ -14,16 +14,13 @@ from localrf_amd.mesh import smooth, topology, vertex_normals  # noqa: F401  (wh
 from mesh_cases import SPHERE_C
 from mesh_smooth_cases import (ANALYTIC, BIG_FAN, CASE_NAMES, E_NONE, FAR, ITERATIONS, PARAMS, SHIFT, SMOOTH_FULL, cases,
                                expected_normals, expected_smooth, expected_topology, smooth_arguments, smooth_host)
+from mesh_util import DenseStub, bits, cpu_mesh, forbid_native, forbid_render
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMBOLS = ("lrf_mesh_incidence_workspace_bytes", "lrf_mesh_incidence", "lrf_mesh_topology", "lrf_mesh_vertex_normals",
            "lrf_mesh_smooth_bounds", "lrf_mesh_smooth_workspace_bytes", "lrf_mesh_smooth")
 KERNELS = ("k_sm_zero", "k_sm_count", "k_sm_rows", "k_sm_starts", "k_sm_fill", "k_sm_edges", "k_sm_pinned", "k_sm_exponent",
            "k_sm_normals", "k_sm_bounds", "k_sm_step", "k_sm_copy")
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 def test_case_names_and_arguments_are_fixed():
@@ -96,7 +93,7 @@ def test_smoothing_a_noisy_sphere():
     assert laplace.mean() < before.mean()
     one_point = cases()["one point"]
     for it in ITERATIONS:                                                   # zero extent: the input's bytes
-        assert np.array_equal(_bits(expected_smooth("one point", it, 0.5, -0.53, "free")[0]), _bits(one_point["vertices"]))
+        assert np.array_equal(bits(expected_smooth("one point", it, 0.5, -0.53, "free")[0]), bits(one_point["vertices"]))
 
 
 @pytest.mark.parametrize("name", ("blobs tie", "strip", "two triangles on one edge", "a degenerate face", "fan 65", "blobs strays"))
@@ -110,12 +107,12 @@ def test_fixed_leaves_the_boundary_and_unreferenced_vertices_bit_equal(name):
     for it, lam, mu, b in smooth_arguments(name):
         got, info = expected_smooth(name, it, lam, mu, b)
         stay = ~referenced | (mask if b == "fixed" else False)
-        assert np.array_equal(_bits(got)[stay], _bits(m["vertices"])[stay])
+        assert np.array_equal(bits(got)[stay], bits(m["vertices"])[stay])
         assert info["pinned"] == (int(mask.sum()) if b == "fixed" else 0)
         if it and name == "blobs tie":
-            assert (_bits(got)[~stay] != _bits(m["vertices"])[~stay]).any()
+            assert (bits(got)[~stay] != bits(m["vertices"])[~stay]).any()
             if b == "free":
-                assert (_bits(got)[mask] != _bits(m["vertices"])[mask]).any()
+                assert (bits(got)[mask] != bits(m["vertices"])[mask]).any()
 
 
 @pytest.mark.parametrize("name", ANALYTIC)
@@ -131,65 +128,51 @@ def test_a_vertex_permutation_permutes_the_rows_and_a_face_permutation_changes_n
         t, n = expected_topology(other), expected_normals(other)
         assert {k_: v for k_, v in t.items() if k_ != "boundary_vertices"} == {k_: v for k_, v in t0.items() if k_ != "boundary_vertices"}
         assert np.array_equal(t["boundary_vertices"][rows], t0["boundary_vertices"])
-        assert n["E"] == n0["E"] and np.array_equal(n["S"][rows], n0["S"]) and np.array_equal(_bits(n["normals"])[rows], _bits(n0["normals"]))
+        assert n["E"] == n0["E"] and np.array_equal(n["S"][rows], n0["S"]) and np.array_equal(bits(n["normals"])[rows], bits(n0["normals"]))
         for args in smooth_arguments(other):
             a, b = smooth_host(base, *args), expected_smooth(other, *args)
-            assert np.array_equal(_bits(b[0])[rows], _bits(a["vertices"][args[0]]))
+            assert np.array_equal(bits(b[0])[rows], bits(a["vertices"][args[0]]))
             assert b[1] == {k_: a[k_] for k_ in b[1]}
 
 
-def _cpu_mesh():
-    return {"vertices": torch.zeros(4, 3), "faces": torch.tensor([[0, 1, 2], [1, 2, 3]], dtype=torch.int32), "rgb8": None, "counts": (4, 2)}
-
-
-class _Vol(mesh.TsdfVolume):
-    def __init__(self):
-        self.origin, self.voxel, self.dims, self.trunc = (0.0, 0.0, 0.0), 0.1, (3, 3, 3), 0.3
-        self.tsdf, self.weight, self.rgb = torch.ones(3, 3, 3), torch.zeros(3, 3, 3), None
-
-
 def test_python_refusals_before_any_native_call(monkeypatch):
-    def forbidden(*a, **k):
-        raise AssertionError("a native call was reached")
-    from localrf_amd import _native
-    for name in ("launch", "call", "workspace", "lib"):
-        monkeypatch.setattr(_native, name, forbidden)
-    faces = _cpu_mesh()["faces"]
+    forbid_native(monkeypatch)
+    faces = cpu_mesh(rgb=False)["faces"]
     calls = (mesh.topology, mesh.vertex_normals, mesh.smooth)
     for fn in calls:
         with pytest.raises(TypeError, match="mesh"):
             fn([torch.zeros(4, 3), faces])
         for key, bad in (("vertices", np.zeros((4, 3), np.float32)), ("faces", faces.numpy())):
             with pytest.raises(TypeError, match=key):
-                fn(dict(_cpu_mesh(), **{key: bad}))
+                fn(dict(cpu_mesh(rgb=False), **{key: bad}))
         for key, bad in (("vertices", torch.zeros(4, 3, dtype=torch.float64)), ("vertices", torch.zeros(4, 2)), ("faces", faces.long()),
                          ("faces", faces.t().contiguous()), ("rgb8", torch.zeros(4, 3))):
             with pytest.raises(ValueError, match=key):
-                fn(dict(_cpu_mesh(), **{key: bad}))
+                fn(dict(cpu_mesh(rgb=False), **{key: bad}))
         with pytest.raises(NativeError):                                    # a valid mesh on the CPU: no fallback
-            fn(_cpu_mesh())
+            fn(cpu_mesh(rgb=False))
     for bad in (-1, 1001, 1.5, None, "ten", True, math.nan):
         with pytest.raises(ValueError, match="iterations"):
-            mesh.smooth(_cpu_mesh(), iterations=bad)
+            mesh.smooth(cpu_mesh(rgb=False), iterations=bad)
     for bad in (0, 0.0, -0.5, 1.0001, math.nan, math.inf, None, "half", True):
         with pytest.raises(ValueError, match="lam"):
-            mesh.smooth(_cpu_mesh(), lam=bad)
+            mesh.smooth(cpu_mesh(rgb=False), lam=bad)
     for bad in (0.01, -1.0001, math.nan, -math.inf, None, "half", True):
         with pytest.raises(ValueError, match="mu"):
-            mesh.smooth(_cpu_mesh(), mu=bad)
+            mesh.smooth(cpu_mesh(rgb=False), mu=bad)
     for bad in ("pinned", None, 0, True, "Fixed"):
         with pytest.raises(ValueError, match="boundary"):
-            mesh.smooth(_cpu_mesh(), boundary=bad)
+            mesh.smooth(cpu_mesh(rgb=False), boundary=bad)
     with pytest.raises(ValueError, match="vertices"):                        # dtype and shape come before the other arguments
-        mesh.smooth(dict(_cpu_mesh(), vertices=torch.zeros(4, 2)), iterations=-1)
+        mesh.smooth(dict(cpu_mesh(rgb=False), vertices=torch.zeros(4, 2)), iterations=-1)
     with pytest.raises(ValueError, match="iterations"):                      # ... and those before the device
-        mesh.smooth(_cpu_mesh(), iterations=-1)
+        mesh.smooth(cpu_mesh(rgb=False), iterations=-1)
     for args in (dict(iterations=0), dict(iterations=1000, lam=1.0, mu=-1.0, boundary="free"), dict(lam=1e-9, mu=0.0)):
         with pytest.raises(NativeError):
-            mesh.smooth(_cpu_mesh(), **args)
+            mesh.smooth(cpu_mesh(rgb=False), **args)
     # the extract options are checked with the other arguments, before the extraction
     sparse = mesh.SparseTsdfVolume.__new__(mesh.SparseTsdfVolume)
-    for vol in (_Vol(), sparse):
+    for vol in (DenseStub(colours=False), sparse):
         for bad in (-1, 1001, 2.5, "three", True, None):
             with pytest.raises(ValueError, match="smooth_iterations"):
                 vol.extract(smooth_iterations=bad)
@@ -202,14 +185,10 @@ def test_python_refusals_before_any_native_call(monkeypatch):
 
 
 def test_scene_mesh_checks_the_options_before_it_renders(monkeypatch):
-    from localrf_amd import novel_views
     from novel_views_cases import scene
     lt, g = scene("cpu")
     W, H = int(g["W"]), int(g["H"])
-
-    def forbidden(*a, **k):
-        raise AssertionError("a render was reached before the refusal")
-    monkeypatch.setattr(novel_views, "render_poses", forbidden)
+    forbid_render(monkeypatch)
     box = ((-1.0, -1.0, -1.0), (1.0, 1.0, 1.0))
     for bad in (-1, 1001, 0.5, "three"):
         with pytest.raises(ValueError, match="smooth_iterations"):

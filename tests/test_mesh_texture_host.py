@@ -23,6 +23,7 @@ from localrf_amd.mesh_texture import TextureBaker, atlas_layout, face_uv, sample
 from mesh_raster_cases import SPHERE_C, SPHERE_R, rasterize_host
 from mesh_texture_cases import (CASE_NAMES, G_LEVELS, ROUND_TRIP, WALL_CAMERAS, WALL_Z, bake_case, bake_fp64, cases, expected, inputs,
                                 layout_host, resolve_host, texels_host, uv_host)
+from mesh_util import cpu_mesh, forbid_native, forbid_render
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMBOLS = ("lrf_mesh_texture_state_bytes", "lrf_mesh_texture_bake", "lrf_mesh_texture_resolve")
@@ -247,29 +248,21 @@ def test_write_obj_parses_back(tmp_path):
         write_obj(tmp_path / "bad.obj", mesh, dict(tex, uv=tex["uv"][:-1]))
 
 
-def _cpu_mesh():
-    return {"vertices": torch.zeros(4, 3), "faces": torch.tensor([[0, 1, 2], [1, 2, 3]], dtype=torch.int32), "rgb8": None, "counts": (4, 2)}
-
-
 def test_python_refusals_before_any_native_call(monkeypatch):
-    def forbidden(*a, **k):
-        raise AssertionError("a native call was reached")
-    from localrf_amd import _native
-    for name in ("launch", "call", "workspace", "lib"):
-        monkeypatch.setattr(_native, name, forbidden)
+    forbid_native(monkeypatch)
     with pytest.raises(TypeError, match="mesh"):
         TextureBaker([torch.zeros(4, 3)])
-    for key, bad in (("vertices", torch.zeros(4, 2)), ("faces", _cpu_mesh()["faces"].long()), ("rgb8", torch.zeros(4, 3))):
+    for key, bad in (("vertices", torch.zeros(4, 2)), ("faces", cpu_mesh(rgb=False)["faces"].long()), ("rgb8", torch.zeros(4, 3))):
         with pytest.raises(ValueError, match=key):
-            TextureBaker(dict(_cpu_mesh(), **{key: bad}))
+            TextureBaker(dict(cpu_mesh(rgb=False), **{key: bad}))
     for key, bad in (("patch", 3), ("patch", 65), ("patch", 7.5), ("cols", 0), ("cols", 1.5), ("blend", "max"), ("blend", 1),
                      ("vis_tol", -0.1), ("vis_tol", math.nan), ("vis_tol", "x"), ("min_cos", 1.5), ("min_cos", -0.1),
                      ("min_cos", math.nan), ("two_sided", 1), ("two_sided", None)):
         with pytest.raises(ValueError, match=key):
-            TextureBaker(_cpu_mesh(), **{key: bad})
+            TextureBaker(cpu_mesh(rgb=False), **{key: bad})
     with pytest.raises(TypeError, match="mesh"):                           # the mesh is checked before the layout
         TextureBaker(None, patch=3)
-    baker = TextureBaker(_cpu_mesh(), patch=5, cols=1, blend="best", two_sided=True)
+    baker = TextureBaker(cpu_mesh(rgb=False), patch=5, cols=1, blend="best", two_sided=True)
     assert (baker.rows, baker.cols, baker.Ht, baker.Wt) == (1, 1, 5, 5)
     poses = torch.eye(4)[None, :3].repeat(2, 1, 1)
     ok = dict(rgb=torch.zeros(2, 6, 8, 3, dtype=torch.uint8), poses=poses, focal=5.0, center=(4.0, 3.0))
@@ -320,16 +313,12 @@ def test_python_refusals_before_any_native_call(monkeypatch):
 
 
 def test_scene_texture_checks_before_it_renders(monkeypatch):
-    from localrf_amd import mesh_raster, novel_views
+    from localrf_amd import mesh_raster
     from novel_views_cases import scene
     lt, g = scene("cpu")
     W, H = int(g["W"]), int(g["H"])
-
-    def forbidden(*a, **k):
-        raise AssertionError("a render was reached before the refusal")
-    monkeypatch.setattr(novel_views, "render_poses", forbidden)
-    monkeypatch.setattr(mesh_raster, "rasterize", forbidden)
-    m = _cpu_mesh()
+    forbid_render(monkeypatch, (mesh_raster, "rasterize"))
+    m = cpu_mesh(rgb=False)
     with pytest.raises(TypeError, match="unknown options"):
         scene_texture(lt, m, W, H, voxel=0.1)
     with pytest.raises(TypeError, match="mesh"):

@@ -11,6 +11,7 @@ import torch
 
 from localrf_amd import NativeError, mesh
 from mesh_cases import (H_ANALYTIC, closed_manifold_euler, extract_host, integrate_host, new_volume, sphere_field)
+from mesh_util import SparseStub, forbid_native, forbid_render
 from sparse_mesh_cases import (assign_host, dims_of, extract_blocks_host, face_keys, fuse_host, integrate_blocks_host, lattice_for,
                                new_sparse, random_frames, spread_lattice, to_dense_host, touch_host, trajectory)
 
@@ -115,27 +116,13 @@ def test_assignment_keeps_earlier_indices_and_refuses_past_the_limit():
 
 
 # ------------------------------------------------------------------------------------------------ refusals
-class _Vol(mesh.SparseTsdfVolume):
-    """A SparseTsdfVolume on the CPU, for the refusals that come before the device check."""
-    def __init__(self, colours=True):
-        self.origin, self.voxel, self.blocks, self.dims, self.trunc, self.colours = (0.0, 0.0, 0.0), 0.1, (2, 2, 2), (16, 16, 16), 0.3, colours
-        self.marks, self.table, self.n_blocks = torch.zeros(2, 2, 2, dtype=torch.uint8), torch.full((2, 2, 2), -1, dtype=torch.int32), 0
-        self._coords = torch.zeros(1, 3, dtype=torch.int32)
-        self._tsdf, self._weight = torch.ones(0, 8, 8, 8), torch.zeros(0, 8, 8, 8)
-        self._rgb = torch.zeros(0, 8, 8, 8, 3) if colours else None
-
-
 def _frames():
     return dict(depth=torch.ones(2, 4, 5), poses=torch.eye(4)[None, :3].repeat(2, 1, 1), focal=4.0, center=(2.5, 2.0),
                 rgb=torch.zeros(2, 4, 5, 3))
 
 
 def test_python_refusals_before_any_native_call(monkeypatch):
-    def forbidden(*a, **k):
-        raise AssertionError("a native call was reached")
-    from localrf_amd import _native
-    for name in ("launch", "call", "workspace"):
-        monkeypatch.setattr(_native, name, forbidden)
+    forbid_native(monkeypatch)
     V = mesh.SparseTsdfVolume
     for bad, match in ((dict(origin=(0, 0)), "origin"), (dict(origin=(0, math.nan, 0)), "origin"), (dict(voxel=0), "voxel"),
                        (dict(voxel=math.nan), "voxel"), (dict(blocks=(3, 3)), "blocks"), (dict(blocks=(3, 0, 3)), "blocks"),
@@ -154,7 +141,7 @@ def test_python_refusals_before_any_native_call(monkeypatch):
         kw = {k: v for k, v in a.items() if k == "depth_range"}
         if method == "integrate":
             kw["rgb"] = a["rgb"]
-        return getattr(vol or _Vol(), method)(a["depth"], a["poses"], a["focal"], a["center"], **kw)
+        return getattr(vol or SparseStub(), method)(a["depth"], a["poses"], a["focal"], a["center"], **kw)
     for method in ("touch", "integrate"):
         for bad, match in ((dict(depth=torch.ones(4, 5)), "depth"), (dict(depth=torch.ones(2, 4, 5).long()), "depth"),
                            (dict(poses=torch.zeros(3, 3, 4)), "poses"), (dict(focal=None), "focal"),
@@ -170,28 +157,24 @@ def test_python_refusals_before_any_native_call(monkeypatch):
         with pytest.raises(ValueError, match=match):
             call("integrate", **bad)
     with pytest.raises(ValueError, match="colours"):
-        call("integrate", vol=_Vol(colours=False))
+        call("integrate", vol=SparseStub(colours=False))
     for bad, match in ((dict(level=math.nan), "level"), (dict(min_weight=0), "min_weight"), (dict(min_weight=math.nan), "min_weight"),
                        (dict(max_vertices=-1), "max_vertices"), (dict(max_faces=1.5), "max_faces"), (dict(max_faces=1 << 31), "max_faces")):
         with pytest.raises(ValueError, match=match):
-            _Vol().extract(**bad)
+            SparseStub().extract(**bad)
     with pytest.raises(ValueError, match="max_bytes is 39"):             # marks and table alone take 8 * 5 bytes
-        _Vol().allocate(max_bytes=39)
-    empty = _Vol().extract()                                             # zero blocks: no launch, an empty mesh
+        SparseStub().allocate(max_bytes=39)
+    empty = SparseStub().extract()                                             # zero blocks: no launch, an empty mesh
     assert empty["counts"] == (0, 0) and tuple(empty["vertices"].shape) == (0, 3) and tuple(empty["faces"].shape) == (0, 3)
-    assert tuple(empty["rgb8"].shape) == (0, 3) and _Vol(colours=False).extract()["rgb8"] is None
-    assert _Vol().nbytes == 40 and V.bytes_for((2, 2, 2), 3, True) == 40 + 3 * (12 + 512 * 20) and V.bytes_for((1, 1, 1), 1, False) == 5 + 12 + 4096
+    assert tuple(empty["rgb8"].shape) == (0, 3) and SparseStub(colours=False).extract()["rgb8"] is None
+    assert SparseStub().nbytes == 40 and V.bytes_for((2, 2, 2), 3, True) == 40 + 3 * (12 + 512 * 20) and V.bytes_for((1, 1, 1), 1, False) == 5 + 12 + 4096
 
 
 def test_scene_mesh_sparse_refusals_on_a_cpu_scene(monkeypatch):
-    from localrf_amd import novel_views
     from novel_views_cases import scene
     lt, g = scene("cpu")
     W, H = int(g["W"]), int(g["H"])
-
-    def forbidden(*a, **k):
-        raise AssertionError("a render was reached before the refusal")
-    monkeypatch.setattr(novel_views, "render_poses", forbidden)
+    forbid_render(monkeypatch)
     box = ((-1.0, -1.0, -1.0), (1.0, 1.0, 1.0))
     need = 3 * 3 * 3 * 5                                                 # 21 points per axis: three blocks
     with pytest.raises(ValueError, match=f"{need} bytes"):
