@@ -32,6 +32,13 @@ int     lrf_debug_tile_ranges(const int32_t* ncomp, int32_t R, int32_t G, int32_
  * join[t][l] = join_halves32 (in[t][l] + in[t][l ^ 32]) and sum[t][l] = half_sum32 (the sum of the 32-lane half of lane l, in
  * the butterfly's order), every lane's value. */
 int     lrf_debug_tile_reduce(const float* in, int32_t T, float* join, float* sum, void* stream);
+/* The workgroup reductions every kernel outside the render hot path shares (csrc/lrf_common.h: block_sum, block_sum0, block_min0,
+ * block_max0) on their own: in [B][NT] floats (device), NT in {64, 256, 1024}, one workgroup per row -> sum32[b] the fp32 sum,
+ * sum64[b] the fp64 sum of the same values widened, bits_min[b] / bits_max[b] the unsigned minimum / maximum of their bit
+ * patterns.  every_thread != 0: the flavour that leaves the result in every thread (read from the last one); 0: the thread-0
+ * flavour. */
+int     lrf_debug_block_reduce(const float* in, int32_t B, int32_t NT, int32_t every_thread, float* sum32, double* sum64,
+                               uint32_t* bits_min, uint32_t* bits_max, void* stream);
 void    lrf_debug_set_scene_fuse(int on);         /* lrf_scene_fwd: several fields per march / colour launch (default on); 0 = field by field */
 void    lrf_debug_set_bwd_overlap(int on);        /* lrf_render_bwd: two branches on two streams (default on); 1 + 2 * (n + 1): k_wgrad_w2w3 on the caller's stream (n > 0, default) or on the side stream behind the density scatter (n = 0) */
 void    lrf_debug_set_train_fwd_engine(int bits); /* 8: plane and line gradients by separate scatter kernels; 16: the gradient scatters with fp32 compare-and-swap adds (k_scatter_plane, rounds 2-5) instead of 64-bit fixed point (k_scatter_fix); 256: fixed point for the density tensors only (default: the appearance tensors too where their accumulators fit in LDS, lines up to 479 cells); 1024: no four-channel sweeps (lines of 480 .. 640 cells: the appearance tensors through the compare-and-swap kernel, as before); 512: k_wgrad_w2w3 in its single-buffered 128-row form (rounds 4-5) instead of the double-buffered 64-row one; 32 / 64 / 128: k_train_dgrad3 + k_train_app3 without their row stores / position gradient and X / dz1 products (timing experiments, wrong results) */

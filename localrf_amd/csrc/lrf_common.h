@@ -5,6 +5,7 @@
 #include "lrf_tu.h"          // first: which translation unit this is (renames, see there)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 #include "../../include/lrf.h"
 
 namespace lrf {
@@ -390,10 +391,74 @@ __device__ __forceinline__ void wave_scan_prod(float v, int lane, float& excl, f
   total = __shfl(p, 63, 64);
 }
 
-__device__ __forceinline__ float wave_sum(float v) {
+// ------------------------------------------------------------------ wave and workgroup reductions
+// THE order of every reduction outside the render hot path: per-thread partials, an xor butterfly over the wave's 64 lanes
+// with offsets 32, 16, ... 1, then the waves' results through LDS in wave-index order starting from wave 0's value,
+// ((w0 o w1) o w2) o ...  Nothing depends on scheduling, so the sums are bit-identical from run to run
+// (tests/test_gpu_block_reduce.py pins the order).  A fold that started from +0.0f instead would differ only where every
+// wave's value is -0.0f, that is where every thread's is: never where the threads' values are accumulators that began at
+// +0.0f (+0 + x is never -0), which is what every floating-point caller passes.
+struct OpSum { template <class T> __device__ __forceinline__ T operator()(T a, T b) const { return a + b; } };
+// integers only: fmaxf and max differ on NaN, and no caller reduces a floating-point minimum or maximum
+struct OpMin {
+  template <class T> __device__ __forceinline__ T operator()(T a, T b) const { static_assert(std::is_integral<T>::value, "integers"); return b < a ? b : a; }
+};
+struct OpMax {
+  template <class T> __device__ __forceinline__ T operator()(T a, T b) const { static_assert(std::is_integral<T>::value, "integers"); return a < b ? b : a; }
+};
+
+// the butterfly: every lane of the wave calls, every lane gets the result (float, double, 32- and 64-bit integers)
+template <class T, class Op>
+__device__ __forceinline__ T wave_reduce(T v, Op op) {
 #pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+  for (int d = 32; d >= 1; d >>= 1) v = op(v, __shfl_xor(v, d, 64));
   return v;
 }
+template <class T> __device__ __forceinline__ T wave_sum(T v) { return wave_reduce(v, OpSum()); }
+template <class T> __device__ __forceinline__ T wave_min(T v) { return wave_reduce(v, OpMin()); }
+template <class T> __device__ __forceinline__ T wave_max(T v) { return wave_reduce(v, OpMax()); }
+
+// The fold of NV per-wave values w[i] (lane 0's count) over the NT / 64 waves of the workgroup, every thread calls; red:
+// [NV][NT / 64].  ALL: the results are in every thread, and a trailing barrier leaves red free on return (as block_scan_excl
+// ends).  Otherwise they are valid in thread 0 only and there is one barrier: a caller that writes red again (a second
+// reduction through the same rows) puts a barrier in between.
+template <int NT, bool ALL, int NV, class T, class Op>
+__device__ __forceinline__ void block_fold(T (&w)[NV], T* red, Op op) {
+  static_assert(NT % 64 == 0 && NT <= 1024, "whole waves, one workgroup");
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int i = 0; i < NV; ++i) red[i * (NT / 64) + (threadIdx.x >> 6)] = w[i];
+  }
+  __syncthreads();
+  if (ALL || threadIdx.x == 0) {
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      T s = red[i * (NT / 64)];
+#pragma unroll
+      for (int k = 1; k < NT / 64; ++k) s = op(s, red[i * (NT / 64) + k]);
+      w[i] = s;
+    }
+  }
+  if (ALL) __syncthreads();
+}
+// butterfly, then fold: NV values of every thread at once, or one
+template <int NT, bool ALL, int NV, class T, class Op>
+__device__ __forceinline__ void block_reduce(T (&v)[NV], T* red, Op op) {
+#pragma unroll
+  for (int i = 0; i < NV; ++i) v[i] = wave_reduce(v[i], op);
+  block_fold<NT, ALL>(v, red, op);
+}
+template <int NT, bool ALL, class T, class Op>
+__device__ __forceinline__ T block_reduce(T v, T* red, Op op) {
+  T a[1] = {v};
+  block_reduce<NT, ALL>(a, red, op);
+  return a[0];
+}
+// the named fronts: block_sum leaves the sum in every thread, the ...0 forms in thread 0 only
+template <int NT, class T> __device__ __forceinline__ T block_sum(T v, T* red) { return block_reduce<NT, true>(v, red, OpSum()); }
+template <int NT, class T> __device__ __forceinline__ T block_sum0(T v, T* red) { return block_reduce<NT, false>(v, red, OpSum()); }
+template <int NT, int NV, class T> __device__ __forceinline__ void block_sum0(T (&v)[NV], T* red) { block_reduce<NT, false>(v, red, OpSum()); }
+template <int NT, class T> __device__ __forceinline__ T block_min0(T v, T* red) { return block_reduce<NT, false>(v, red, OpMin()); }
+template <int NT, class T> __device__ __forceinline__ T block_max0(T v, T* red) { return block_reduce<NT, false>(v, red, OpMax()); }
 
 }  // namespace lrf

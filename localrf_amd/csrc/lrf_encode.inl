@@ -46,15 +46,9 @@ __global__ __launch_bounds__(ENC_NT) void k_encode_range(const float* __restrict
     if (u != 0u && !(u & 0x80000000u)) mn = min(mn, u);                    // x > 0: a positive float's bits keep its order
     mx = max(mx, enc_key(u));
   }
-  for (int o = 32; o > 0; o >>= 1) {
-    mn = min(mn, (unsigned)__shfl_xor((int)mn, o));
-    mx = max(mx, (unsigned)__shfl_xor((int)mx, o));
-  }
-  const int w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) { red[0][w] = mn; red[1][w] = mx; }
-  __syncthreads();
+  mn = block_min0<ENC_NT>(mn, red[0]);
+  mx = block_max0<ENC_NT>(mx, red[1]);
   if (threadIdx.x == 0) {
-    for (int k = 1; k < ENC_NT / 64; ++k) { mn = min(mn, red[0][k]); mx = max(mx, red[1][k]); }
     ws[((size_t)v * ENC_RANGE_WG + b) * 2] = mn;
     ws[((size_t)v * ENC_RANGE_WG + b) * 2 + 1] = mx;
   }
@@ -100,10 +94,8 @@ __global__ __launch_bounds__(ENC_NT) void k_encode(EncodeArgs a) {
     const int lane = threadIdx.x & 63;
     for (int f = f0 + (threadIdx.x >> 6); f <= f1; f += ENC_NT / 64) {   // one wave per frame, one partial per lane
       unsigned mn = a.ws[((size_t)f * ENC_RANGE_WG + lane) * 2], mx = a.ws[((size_t)f * ENC_RANGE_WG + lane) * 2 + 1];
-      for (int o = 32; o > 0; o >>= 1) {
-        mn = min(mn, (unsigned)__shfl_xor((int)mn, o));
-        mx = max(mx, (unsigned)__shfl_xor((int)mx, o));
-      }
+      mn = wave_min(mn);
+      mx = wave_max(mx);
       if (lane == 0) {
         const float mi = mn == ENC_NO_POS ? __uint_as_float(0x7FC00000u) : __uint_as_float(mn);
         const float ma = __uint_as_float(enc_unkey(mx));

@@ -96,7 +96,7 @@ __global__ __launch_bounds__(EG_NT) void k_depth_prep(const float* __restrict__ 
   sel[(size_t)V * HW + vp] = inv[vp];
 }
 
-// per (row, chunk of EG_NT * 16 values): fp64 sum of the fp32 |x - t|, fixed order (thread-strided, butterfly, waves in order)
+// per (row, chunk of EG_NT * 16 values): fp64 sum of the fp32 |x - t|, fixed order (thread-strided, then block_sum0)
 __global__ __launch_bounds__(EG_NT) void k_depth_mad(const float* __restrict__ sel, const float* __restrict__ med, double* __restrict__ part,
                                                      int HW, int chunks) {
   __shared__ double red[EG_NT / 64];
@@ -108,14 +108,8 @@ __global__ __launch_bounds__(EG_NT) void k_depth_mad(const float* __restrict__ s
     const int i = (blockIdx.x * 16 + k) * EG_NT + tid;
     if (i < HW) s += (double)fabsf(__fsub_rn(p[i], t));
   }
-  for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
-  if ((tid & 63) == 0) red[tid >> 6] = s;
-  __syncthreads();
-  if (tid == 0) {
-    double q = red[0];
-    for (int w = 1; w < EG_NT / 64; ++w) q += red[w];
-    part[(size_t)r * chunks + blockIdx.x] = q;
-  }
+  const double q = block_sum0<EG_NT>(s, red);
+  if (tid == 0) part[(size_t)r * chunks + blockIdx.x] = q;
 }
 
 // one workgroup per row: the row's partials in order; stats[v] = (t_x, t_y, s_x, s_y)
@@ -125,12 +119,8 @@ __global__ __launch_bounds__(EG_NT) void k_depth_mad_reduce(const double* __rest
   const int r = blockIdx.x, tid = threadIdx.x;
   double s = 0.0;
   for (int c = tid; c < chunks; c += EG_NT) s += part[(size_t)r * chunks + c];
-  for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
-  if ((tid & 63) == 0) red[tid >> 6] = s;
-  __syncthreads();
+  const double q = block_sum0<EG_NT>(s, red);
   if (tid == 0) {
-    double q = red[0];
-    for (int w = 1; w < EG_NT / 64; ++w) q += red[w];
     const int v = r % V, which = r / V;                            // 0: x (rendered), 1: y (dataset)
     stats[v * 4 + which] = med[r];
     stats[v * 4 + 2 + which] = (float)(q / n);

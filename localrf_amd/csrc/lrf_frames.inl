@@ -86,9 +86,9 @@ __device__ inline int reflect101(int i, int n) {             // BORDER_REFLECT_1
 // cv2.Laplacian(grey, cv2.CV_32F) (ksize 1: [[0,1,0],[1,-4,1],[0,1,0]]): integer values; each workgroup writes the exact
 // int64 sums (S1, S2) of its fixed share of the pixels
 __global__ __launch_bounds__(FR_NT) void k_frame_sharpness(const float* __restrict__ rgb, int H, int W, long long* __restrict__ part) {
-  __shared__ long long red[2][FR_NT / 64];
+  __shared__ long long red[2 * (FR_NT / 64)];
   const int tid = threadIdx.x, n_px = H * W;
-  long long s1 = 0, s2 = 0;
+  long long s[2] = {0, 0};                                     // S1, S2
   for (int i = blockIdx.x * FR_NT + tid; i < n_px; i += SH_PARTS * FR_NT) {
     const int y = i / W, x = i - y * W;
     const int c = grey_u8(rgb + 3 * (size_t)i);
@@ -97,19 +97,13 @@ __global__ __launch_bounds__(FR_NT) void k_frame_sharpness(const float* __restri
     const int lf = grey_u8(rgb + 3 * ((size_t)y * W + reflect101(x - 1, W)));
     const int rt = grey_u8(rgb + 3 * ((size_t)y * W + reflect101(x + 1, W)));
     const int lap = up + dn + lf + rt - 4 * c;
-    s1 += lap;
-    s2 += (long long)(lap * lap);
+    s[0] += lap;
+    s[1] += (long long)(lap * lap);
   }
-  for (int off = 32; off > 0; off >>= 1) {
-    s1 += __shfl_xor(s1, off, 64);
-    s2 += __shfl_xor(s2, off, 64);
-  }
-  if ((tid & 63) == 0) { red[0][tid >> 6] = s1; red[1][tid >> 6] = s2; }
-  __syncthreads();
+  block_sum0<FR_NT>(s, red);
   if (tid == 0) {
-    for (int wv = 1; wv < FR_NT / 64; ++wv) { s1 += red[0][wv]; s2 += red[1][wv]; }   // (wave 0's own sums are s1 / s2)
-    part[2 * blockIdx.x] = s1;
-    part[2 * blockIdx.x + 1] = s2;
+    part[2 * blockIdx.x] = s[0];
+    part[2 * blockIdx.x + 1] = s[1];
   }
 }
 
@@ -118,21 +112,15 @@ __global__ __launch_bounds__(FR_NT) void k_frame_sharpness(const float* __restri
 // above 2^53), the division in fp64, one rounding to fp32.  numpy's float32 .var() of the same values agrees to ~1e-7.
 __global__ __launch_bounds__(FR_NT) void k_frame_weight(const long long* __restrict__ part, int n_px, const unsigned char* __restrict__ motion_mask,
                                                          float* __restrict__ weight) {
-  __shared__ long long red[2][FR_NT / 64];
+  __shared__ long long red[2 * (FR_NT / 64)];
   __shared__ float var_s;
   const int tid = threadIdx.x;
-  long long s1 = 0, s2 = 0;
-  for (int k = tid; k < SH_PARTS; k += FR_NT) { s1 += part[2 * k]; s2 += part[2 * k + 1]; }
-  for (int off = 32; off > 0; off >>= 1) {
-    s1 += __shfl_xor(s1, off, 64);
-    s2 += __shfl_xor(s2, off, 64);
-  }
-  if ((tid & 63) == 0) { red[0][tid >> 6] = s1; red[1][tid >> 6] = s2; }
-  __syncthreads();
+  long long s[2] = {0, 0};
+  for (int k = tid; k < SH_PARTS; k += FR_NT) { s[0] += part[2 * k]; s[1] += part[2 * k + 1]; }
+  block_sum0<FR_NT>(s, red);
   if (tid == 0) {
-    for (int wv = 1; wv < FR_NT / 64; ++wv) { s1 += red[0][wv]; s2 += red[1][wv]; }
     const long long N = n_px;
-    const double num = (double)(N * s2 - s1 * s1);
+    const double num = (double)(N * s[1] - s[0] * s[0]);
     var_s = (float)(num / ((double)N * (double)N));
   }
   __syncthreads();

@@ -72,15 +72,6 @@ __device__ __forceinline__ float sorted_quantile(const float* sorted, int n, flo
   const float a = sorted[(int)lo], b = sorted[(int)ceilf(rank)];
   return w < 0.5f ? a + w * (b - a) : b - (b - a) * (1.0f - w);
 }
-__device__ __forceinline__ float block_sum(float v, float* red /* [16] */) {
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  float s = 0.0f;
-  for (int i = 0; i < (int)(blockDim.x >> 6); ++i) s += red[i];
-  return s;
-}
 
 // ------------------------------------------------------------------------------------------- flow loss
 struct Cam2Cam { float R[9], t[3]; };
@@ -174,7 +165,7 @@ __global__ __launch_bounds__(LOSS_NT) void k_flow_loss_fwd(FlowArgs a, float* __
     if (val > thr) { val = 0.0f; arr_out[r] = 0.0f; }
     acc += val;
   }
-  acc = block_sum(acc, red);
+  acc = block_sum<LOSS_NT>(acc, red);
   if (threadIdx.x == 0) vsum[v] = acc;
 }
 
@@ -231,7 +222,7 @@ __global__ __launch_bounds__(LOSS_NT) void k_flow_loss_bwd(FlowArgs a, const flo
     g_dirs[r * 3] = gp[0] * d; g_dirs[r * 3 + 1] = gp[1] * d; g_dirs[r * 3 + 2] = gp[2] * d;
   }
   for (int i = 0; i < 27; ++i) {
-    const float s = block_sum(acc[i], red);
+    const float s = block_sum<LOSS_NT>(acc[i], red);
     if (threadIdx.x == 0) s_tot[i] = s;
   }
   __syncthreads();
@@ -307,7 +298,7 @@ __global__ __launch_bounds__(LOSS_NT) void k_depth_loss_fwd(DepthArgs a, float* 
   const float td = s_st[0];
   float acc = 0.0f;
   for (int j = threadIdx.x; j < n; j += blockDim.x) acc += fabsf(1.0f / fmaxf(dp[j], 1e-6f) - td);
-  const float sd = block_sum(acc, red) / (float)n;
+  const float sd = block_sum<LOSS_NT>(acc, red) / (float)n;
   __syncthreads();
   for (int j = threadIdx.x; j < N; j += blockDim.x) s_key[j] = j < n ? gp[j] : __builtin_inff();
   lds_bitonic_sort<false>(s_key, nullptr, N);
@@ -316,7 +307,7 @@ __global__ __launch_bounds__(LOSS_NT) void k_depth_loss_fwd(DepthArgs a, float* 
   const float tg = s_st[2];
   acc = 0.0f;
   for (int j = threadIdx.x; j < n; j += blockDim.x) acc += fabsf(gp[j] - tg);
-  const float sg = block_sum(acc, red) / (float)n;
+  const float sg = block_sum<LOSS_NT>(acc, red) / (float)n;
   __syncthreads();
   for (int j = threadIdx.x; j < N; j += blockDim.x) {
     float val = __builtin_inff();
@@ -338,7 +329,7 @@ __global__ __launch_bounds__(LOSS_NT) void k_depth_loss_fwd(DepthArgs a, float* 
     if (val > thr) { val = 0.0f; arr_out[r] = 0.0f; }
     acc += val;
   }
-  acc = block_sum(acc, red);
+  acc = block_sum<LOSS_NT>(acc, red);
   if (threadIdx.x == 0) {
     vsum[v] = acc;
     float* st = stats + (size_t)v * 6;
@@ -365,7 +356,7 @@ __global__ __launch_bounds__(LOSS_NT) void k_depth_loss_bwd(DepthArgs a, const f
     const float g = arr_out[(size_t)v * n + j] > 0.0f ? 2.0f * (xn - gn) * gs : 0.0f;
     A += g; B += g * xn; Sg += sgn(x - td);
   }
-  A = block_sum(A, red); B = block_sum(B, red) / sd; Sg = block_sum(Sg, red);
+  A = block_sum<LOSS_NT>(A, red); B = block_sum<LOSS_NT>(B, red) / sd; Sg = block_sum<LOSS_NT>(Sg, red);
   for (int j = threadIdx.x; j < n; j += blockDim.x) {
     const float c = fmaxf(dp[j], 1e-6f);
     const float x = 1.0f / c;

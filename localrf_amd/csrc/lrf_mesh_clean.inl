@@ -145,7 +145,7 @@ __global__ __launch_bounds__(CC_NT) void k_cc_summary(const int* __restrict__ la
   int nf = root ? faces_of[i] : 0;
   wave_count(&summary[0], root);
   wave_count(&summary[1], nf > 0);
-  for (int off = 32; off > 0; off >>= 1) nf = max(nf, __shfl_xor(nf, off, 64));
+  nf = wave_max(nf);
   if ((threadIdx.x & 63) == 0 && nf > 0) atomicMax(&summary[2], (unsigned long long)nf);
 }
 

@@ -206,10 +206,8 @@ __global__ __launch_bounds__(MD_NT) void k_md_bounds(MdMesh m, unsigned long lon
       lo = sm_key(fminf(fminf(x[0][k], x[1][k]), x[2][k]));
       hi = sm_key(fmaxf(fmaxf(x[0][k], x[1][k]), x[2][k]));
     }
-    for (int off = 32; off > 0; off >>= 1) {
-      lo = min(lo, __shfl_xor(lo, off, 64));
-      hi = max(hi, __shfl_xor(hi, off, 64));
-    }
+    lo = wave_min(lo);
+    hi = wave_max(hi);
     if ((threadIdx.x & 63) == 0 && good) { atomicMin(&keys[k], lo); atomicMax(&keys[3 + k], hi); }
   }
 }
@@ -428,14 +426,11 @@ __global__ __launch_bounds__(MD_NT) void k_md_summary(MdSummary g, unsigned long
     for (int t = 0; t < LRF_DISTANCE_MAX_THRESHOLDS; ++t)
       if (t < g.n_tau && d <= g.tau[t]) ++within[t];
   }
+  n_fin = wave_sum(n_fin); n_inf = wave_sum(n_inf); n_nan = wave_sum(n_nan);
+  sum1 = wave_sum(sum1); sum2 = wave_sum(sum2);
+  top = wave_max(top);
 #pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    n_fin += __shfl_xor(n_fin, off, 64); n_inf += __shfl_xor(n_inf, off, 64); n_nan += __shfl_xor(n_nan, off, 64);
-    sum1 += __shfl_xor(sum1, off, 64); sum2 += __shfl_xor(sum2, off, 64);
-    top = max(top, __shfl_xor(top, off, 64));
-#pragma unroll
-    for (int t = 0; t < LRF_DISTANCE_MAX_THRESHOLDS; ++t) within[t] += __shfl_xor(within[t], off, 64);
-  }
+  for (int t = 0; t < LRF_DISTANCE_MAX_THRESHOLDS; ++t) within[t] = wave_sum(within[t]);
   if ((threadIdx.x & 63) == 0) {
     if (n_fin) atomicAdd(&words[0], (unsigned long long)n_fin);
     if (n_inf) atomicAdd(&words[1], (unsigned long long)n_inf);

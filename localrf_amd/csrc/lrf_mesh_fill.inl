@@ -225,11 +225,7 @@ __global__ __launch_bounds__(HF_NT) void k_hf_loops(HfMesh a, const int* __restr
       }
     }
   }
-  int most = L, sum = L;
-  for (int o = 32; o > 0; o >>= 1) {
-    most = max(most, __shfl_xor(most, o, 64));
-    sum += __shfl_xor(sum, o, 64);                                  // at most 64 x 4096
-  }
+  const int most = wave_max(L), sum = wave_sum(L);                  // at most 64 x 4096
   if ((threadIdx.x & 63) == 0 && sum) {
     atomicMax(longest, most);
     atomicAdd(&words[HF_LOOP_EDGES], (unsigned long long)sum);

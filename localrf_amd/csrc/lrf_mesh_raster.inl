@@ -323,13 +323,10 @@ __global__ __launch_bounds__(AG_NT) void k_depth_agreement(AgreeArgs g, unsigned
     else ++n_none;
     if (error_map) error_map[base + p] = rel;
   }
+  n_both = wave_sum(n_both); n_a = wave_sum(n_a); n_b = wave_sum(n_b);
+  n_none = wave_sum(n_none); sum = wave_sum(sum);
 #pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    n_both += __shfl_xor(n_both, off, 64); n_a += __shfl_xor(n_a, off, 64); n_b += __shfl_xor(n_b, off, 64);
-    n_none += __shfl_xor(n_none, off, 64); sum += __shfl_xor(sum, off, 64);
-#pragma unroll
-    for (int t = 0; t < LRF_AGREEMENT_MAX_TOLS; ++t) within[t] += __shfl_xor(within[t], off, 64);
-  }
+  for (int t = 0; t < LRF_AGREEMENT_MAX_TOLS; ++t) within[t] = wave_sum(within[t]);
   if ((threadIdx.x & 63) == 0) {
     unsigned long long* c = counts + (size_t)v * AG_WORDS;
     if (n_both) atomicAdd(&c[0], (unsigned long long)n_both);

@@ -111,12 +111,8 @@ __global__ __launch_bounds__(MS_NT) void k_ms_bounds(const float* __restrict__ v
   int lo[3], hi[3];
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
-    lo[k] = ok ? i[k] : 0x7fffffff;
-    hi[k] = ok ? i[k] : -0x7fffffff - 1;
-    for (int off = 32; off > 0; off >>= 1) {
-      lo[k] = min(lo[k], __shfl_xor(lo[k], off, 64));
-      hi[k] = max(hi[k], __shfl_xor(hi[k], off, 64));
-    }
+    lo[k] = wave_min(ok ? i[k] : 0x7fffffff);
+    hi[k] = wave_max(ok ? i[k] : -0x7fffffff - 1);
   }
   if ((threadIdx.x & 63) == 0 && good) {
 #pragma unroll

@@ -183,8 +183,8 @@ __device__ __forceinline__ void sm_row_sum(const int* __restrict__ row_faces, in
     long long part[3] = {0, 0, 0};
     for (int i = lane; i < nL; i += 64) add(row_faces[bL + i], vL, part);
 #pragma unroll
-    for (int k = 0; k < 3; ++k)
-      for (int off = 32; off > 0; off >>= 1) part[k] += __shfl_xor(part[k], off, 64);
+    for (int k = 0; k < 3; ++k)                                     // wave_sum's order, kept by hand: with the helper k_sm_step zeroes
+      for (int off = 32; off > 0; off >>= 1) part[k] += __shfl_xor(part[k], off, 64);   // part with six more moves per turn
     if (lane == L) { acc[0] = part[0]; acc[1] = part[1]; acc[2] = part[2]; }
   }
 }
@@ -225,7 +225,7 @@ __global__ __launch_bounds__(SM_NT) void k_sm_exponent(const float* __restrict__
       e = max(e, x - 1);
     }
   }
-  for (int off = 32; off > 0; off >>= 1) e = max(e, __shfl_xor(e, off, 64));
+  e = wave_max(e);
   if ((threadIdx.x & 63) == 0 && e != SM_E_NONE) atomicMax(E, e);
 }
 
@@ -294,12 +294,8 @@ __global__ __launch_bounds__(SM_NT) void k_sm_bounds(const float* __restrict__ v
   int lo[3], hi[3];
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
-    lo[k] = ok ? sm_key(x[k]) : 0x7fffffff;
-    hi[k] = ok ? sm_key(x[k]) : -0x7fffffff - 1;
-    for (int off = 32; off > 0; off >>= 1) {
-      lo[k] = min(lo[k], __shfl_xor(lo[k], off, 64));
-      hi[k] = max(hi[k], __shfl_xor(hi[k], off, 64));
-    }
+    lo[k] = wave_min(ok ? sm_key(x[k]) : 0x7fffffff);
+    hi[k] = wave_max(ok ? sm_key(x[k]) : -0x7fffffff - 1);
   }
   if ((threadIdx.x & 63) == 0 && good) {
 #pragma unroll

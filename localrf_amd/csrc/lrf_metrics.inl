@@ -42,7 +42,7 @@ __global__ __launch_bounds__(MT_NT) void k_img_metrics(MetricsArgs a) {
   float* sx = reinterpret_cast<float*>(mt_lds + 5 * MT_RS * EW);     // [EH][EW] window of img0, one channel
   float* sy = sx + EH * EW;                                          // ... of img1
   __shared__ double taps[MT_MAX_FS + 1];
-  __shared__ double red[2][MT_NT / 64];
+  __shared__ double red[2 * (MT_NT / 64)];
 
   const int tid = threadIdx.x, b = blockIdx.y, tile = blockIdx.x;
   const int ty = tile / a.tiles_x, tx = tile - ty * a.tiles_x;
@@ -122,41 +122,25 @@ __global__ __launch_bounds__(MT_NT) void k_img_metrics(MetricsArgs a) {
       }
     }
   }
-  // fixed-order workgroup reduction: butterfly within each wave, then the waves in index order
-  for (int off = 32; off > 0; off >>= 1) {
-    ssim_acc += __shfl_xor(ssim_acc, off, 64);
-    sq_acc += __shfl_xor(sq_acc, off, 64);
-  }
-  if ((tid & 63) == 0) { red[0][tid >> 6] = ssim_acc; red[1][tid >> 6] = sq_acc; }
-  __syncthreads();
-  if (tid == 0) {
-    double s = red[0][0], q = red[1][0];
-    for (int wv = 1; wv < MT_NT / 64; ++wv) { s += red[0][wv]; q += red[1][wv]; }
-    a.part[(size_t)b * a.tiles + tile] = make_double2(s, q);
-  }
+  double acc[2] = {ssim_acc, sq_acc};
+  block_sum0<MT_NT>(acc, red);                                        // the fixed order of lrf_common.h
+  if (tid == 0) a.part[(size_t)b * a.tiles + tile] = make_double2(acc[0], acc[1]);
 }
 
 // one workgroup per frame: thread t sums tiles t, t + MT_NT, ... in order, then the same fixed-order reduction
 __global__ __launch_bounds__(MT_NT) void k_img_metrics_reduce(const double2* __restrict__ part, int tiles, double n_ssim, double n_px,
                                                               double* __restrict__ ssim_mean, double* __restrict__ mse) {
-  __shared__ double red[2][MT_NT / 64];
+  __shared__ double red[2 * (MT_NT / 64)];
   const int tid = threadIdx.x, b = blockIdx.x;
-  double s = 0.0, q = 0.0;
+  double acc[2] = {0.0, 0.0};
   for (int t = tid; t < tiles; t += MT_NT) {
     const double2 p = part[(size_t)b * tiles + t];
-    s += p.x; q += p.y;
+    acc[0] += p.x; acc[1] += p.y;
   }
-  for (int off = 32; off > 0; off >>= 1) {
-    s += __shfl_xor(s, off, 64);
-    q += __shfl_xor(q, off, 64);
-  }
-  if ((tid & 63) == 0) { red[0][tid >> 6] = s; red[1][tid >> 6] = q; }
-  __syncthreads();
+  block_sum0<MT_NT>(acc, red);
   if (tid == 0) {
-    double ss = red[0][0], qq = red[1][0];
-    for (int wv = 1; wv < MT_NT / 64; ++wv) { ss += red[0][wv]; qq += red[1][wv]; }
-    ssim_mean[b] = ss / n_ssim;
-    mse[b] = qq / n_px;
+    ssim_mean[b] = acc[0] / n_ssim;
+    mse[b] = acc[1] / n_px;
   }
 }
 

@@ -138,13 +138,9 @@ __global__ __launch_bounds__(PTS_NT) void k_points_mark(PointsArgs a, unsigned l
     if (lane == 0) bits[word] = m;                                  // every word of the workspace is written
     cnt += (unsigned)__popcll(m);
   }
-  if (lane == 0) red[wv] = cnt;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned s = 0;
-    for (int w = 0; w < PTS_NT / 64; ++w) s += red[w];
-    wg[blockIdx.x] = s;
-  }
+  unsigned s[1] = {cnt};                                            // every lane of a wave holds the wave's count already
+  block_fold<PTS_NT, false>(s, red, OpSum());
+  if (threadIdx.x == 0) wg[blockIdx.x] = s[0];
 }
 
 __global__ __launch_bounds__(PTS_NT) void k_points_write(PointsArgs a, const unsigned long long* __restrict__ bits,

@@ -27,15 +27,6 @@ struct L1Geo {
   long long n;
 };
 
-__device__ __forceinline__ float block_sum_256(float v, float* red) {
-  v = wave_sum(v);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  const float s = red[0] + red[1] + red[2] + red[3];
-  __syncthreads();
-  return s;
-}
-
 // dfeat[i] = d sqrt(max(sig,1e-5)) / d feat[i]; partial[block] = sum of the block's values
 __global__ __launch_bounds__(L1_TPB) void k_l1_fwd(L1Geo G, float shift, int relu, float* __restrict__ dfeat,
                                                    float* __restrict__ partial) {
@@ -63,7 +54,7 @@ __global__ __launch_bounds__(L1_TPB) void k_l1_fwd(L1Geo G, float shift, int rel
     acc += y;
     dfeat[i] = sig >= 1e-5f ? 0.5f / y * dsig : 0.0f;        // clamp(min) passes the gradient where sig >= min
   }
-  const float s = block_sum_256(acc, red);
+  const float s = block_sum<L1_TPB>(acc, red);
   if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
 
@@ -72,7 +63,7 @@ __global__ __launch_bounds__(L1_TPB) void k_l1_mean(const float* __restrict__ pa
   __shared__ float red[4];
   float acc = 0.0f;
   for (int i = threadIdx.x; i < nb; i += L1_TPB) acc += partial[i];
-  const float s = block_sum_256(acc, red);
+  const float s = block_sum<L1_TPB>(acc, red);
   if (threadIdx.x == 0) out[0] = s / (float)n;
 }
 
@@ -295,7 +286,7 @@ __global__ __launch_bounds__(L1_TPB) void k_tv_fwd(TvTable tab, float2* __restri
       if (x > 0) { const float d = v - sg.x[i - 1]; sw += d * d; }
     }
   }
-  const float a = block_sum_256(sh, red), b = block_sum_256(sw, red);
+  const float a = block_sum<L1_TPB>(sh, red), b = block_sum<L1_TPB>(sw, red);
   if (threadIdx.x == 0) partial[blockIdx.x] = make_float2(a, b);
 }
 

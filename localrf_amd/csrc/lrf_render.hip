@@ -1320,6 +1320,40 @@ static hipError_t lds_opt_in() {
 #include "lrf_reg.inl"
 #include "lrf_mask.inl"
 
+namespace lrf {
+// Test hook (lrf_debug_block_reduce): the workgroup reductions of lrf_common.h on a caller's rows, one workgroup per row of NT
+// floats.  ALL: the every-thread flavour, read out of the LAST thread; else the thread-0 flavour.
+template <int NT, bool ALL>
+__global__ __launch_bounds__(NT) void k_block_reduce_dbg(const float* __restrict__ in, float* __restrict__ sum32, double* __restrict__ sum64,
+                                                         unsigned* __restrict__ bits_min, unsigned* __restrict__ bits_max) {
+  __shared__ float red_f[NT / 64];
+  __shared__ double red_d[NT / 64];
+  __shared__ unsigned red_u[2][NT / 64];
+  const float x = in[(size_t)blockIdx.x * NT + threadIdx.x];
+  const unsigned u = __float_as_uint(x);
+  float s; double d; unsigned lo, hi;
+  if (ALL) {
+    s = block_sum<NT>(x, red_f);
+    d = block_sum<NT>((double)x, red_d);
+    lo = block_reduce<NT, true>(u, red_u[0], OpMin());
+    hi = block_reduce<NT, true>(u, red_u[1], OpMax());
+  } else {
+    s = block_sum0<NT>(x, red_f);
+    d = block_sum0<NT>((double)x, red_d);
+    lo = block_min0<NT>(u, red_u[0]);
+    hi = block_max0<NT>(u, red_u[1]);
+  }
+  if (threadIdx.x == (ALL ? NT - 1 : 0)) {
+    sum32[blockIdx.x] = s; sum64[blockIdx.x] = d; bits_min[blockIdx.x] = lo; bits_max[blockIdx.x] = hi;
+  }
+}
+template <int NT>
+static int block_reduce_dbg(int B, bool all, hipStream_t st, const float* in, float* sum32, double* sum64, unsigned* lo, unsigned* hi) {
+  return all ? launch(k_block_reduce_dbg<NT, true>, B, NT, st, in, sum32, sum64, lo, hi)
+             : launch(k_block_reduce_dbg<NT, false>, B, NT, st, in, sum32, sum64, lo, hi);
+}
+}  // namespace lrf
+
 using namespace lrf;
 
 extern "C" {
@@ -1350,6 +1384,18 @@ int lrf_debug_tile_reduce(const float* in, int32_t T, float* join, float* sum, v
   if (!in || !join || !sum) return refuse(who, "null argument");
   if (T <= 0) return refuse(who, "need T > 0");
   return launch(k_tile_reduce_dbg, T, 64, reinterpret_cast<hipStream_t>(stream), in, join, sum);
+}
+int lrf_debug_block_reduce(const float* in, int32_t B, int32_t NT, int32_t every_thread, float* sum32, double* sum64,
+                           uint32_t* bits_min, uint32_t* bits_max, void* stream) {
+  const char* who = "lrf_debug_block_reduce";
+  if (!in || !sum32 || !sum64 || !bits_min || !bits_max) return refuse(who, "null argument");
+  if (B <= 0) return refuse(who, "need B > 0");
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const bool all = every_thread != 0;
+  if (NT == 64) return block_reduce_dbg<64>(B, all, st, in, sum32, sum64, bits_min, bits_max);
+  if (NT == 256) return block_reduce_dbg<256>(B, all, st, in, sum32, sum64, bits_min, bits_max);
+  if (NT == 1024) return block_reduce_dbg<1024>(B, all, st, in, sum32, sum64, bits_min, bits_max);
+  return refuse(who, "NT is 64, 256 or 1024");
 }
 #ifdef LRF_SCATTER_PROF
 int lrf_debug_scatter_prof(unsigned long long* host_out /* [2][2048][12] */) {

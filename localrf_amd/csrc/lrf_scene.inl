@@ -66,27 +66,6 @@ __global__ __launch_bounds__(SCENE_TPB) void k_scene_rays(
   }
 }
 
-// block-wide sum of NV per-thread values; result valid in thread 0.  red: [SCENE_TPB/64][NV]
-template <int NV>
-__device__ __forceinline__ void block_sum(float (&v)[NV], float* red) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-  for (int i = 0; i < NV; ++i) {
-    const float s = wave_sum(v[i]);
-    if (lane == 0) red[wv * NV + i] = s;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      float s = 0.f;
-      for (int w = 0; w < SCENE_TPB / 64; ++w) s += red[w * NV + i];
-      v[i] = s;
-    }
-  }
-  __syncthreads();
-}
-
 // One block per view.  g_c2w [V,3,4]; g_intr [V,3] = per-view partial (d focal, d cx, d cy);
 // g_w2rf [V,n_rf,3] = per-view partial of the origin-shift gradient.
 __global__ __launch_bounds__(SCENE_TPB) void k_scene_rays_bwd(
@@ -108,12 +87,13 @@ __global__ __launch_bounds__(SCENE_TPB) void k_scene_rays_bwd(
       const float* g = g_rays + ((size_t)k * R + (size_t)v * per_view + q) * 6;
       go[0] += g[0]; go[1] += g[1]; go[2] += g[2];
     }
-    block_sum<3>(go, red);
+    block_sum0<SCENE_TPB>(go, red);
     if (threadIdx.x == 0) {
       float* o = g_w2rf + ((size_t)v * n_rf + k) * 3;
       o[0] = go[0]; o[1] = go[1]; o[2] = go[2];
       acc[9] += go[0]; acc[10] += go[1]; acc[11] += go[2];
     }
+    __syncthreads();                   // red is written again: by the next field, then by the sums below
   }
   for (int q = threadIdx.x; q < per_view; q += SCENE_TPB) {
     const size_t r = (size_t)v * per_view + q;
@@ -138,7 +118,7 @@ __global__ __launch_bounds__(SCENE_TPB) void k_scene_rays_bwd(
   }
   float t3[3] = {acc[9], acc[10], acc[11]};      // thread 0 holds dt already reduced
   acc[9] = acc[10] = acc[11] = 0.f;
-  block_sum<15>(acc, red);
+  block_sum0<SCENE_TPB>(acc, red);
   if (threadIdx.x == 0) {
     float* o = g_c2w + (size_t)v * 12;
     o[0] = acc[0]; o[1] = acc[1]; o[2] = acc[2];  o[3] = t3[0];
@@ -214,7 +194,7 @@ __global__ __launch_bounds__(SCENE_TPB) void k_scene_blend_bwd(
     }
   }
   if (g_expo) {
-    block_sum<9>(acc, red);
+    block_sum0<SCENE_TPB>(acc, red);
     if (threadIdx.x == 0)
       for (int i = 0; i < 9; ++i) g_expo[(size_t)v * 9 + i] = acc[i];
   }
