@@ -782,6 +782,27 @@ size_t lrf_mesh_simplify_workspace_bytes(int64_t Nv, int64_t Nf, int64_t cells);
 int lrf_mesh_simplify(const LrfMeshSimplify* m, float* vertices_out, uint8_t* rgb8_out /* nullable */, int32_t* faces_out,
                       int64_t* counts /* device [5] */, void* workspace, void* stream);
 
+/* The same simplification with every emitted cluster's vertex placed where the summed plane quadric of the faces that touch
+ * the cluster is smallest, inside the cluster's closed cell (Lindstrom's out-of-core simplification; rules a-d in
+ * csrc/lrf_mesh_simplify.inl).  Cells, clusters, faces, colours, dedupe and the output order are lrf_mesh_simplify's; only
+ * the positions differ.  int64 sums of coefficients scaled by one power of two per cluster (integer atomicAdd, int32
+ * atomicMax), then fp64 operations each rounded on its own: the same bytes on every run, whatever the order of the input.
+ * regularize in (0, 1] pulls towards the mean of the cluster's vertices with weight regularize * trace: it decides the
+ * position inside a plane and along a crease.  A cluster keeps the mean when it has no contribution, 2^21 or more of them,
+ * or a system that does not solve (trace <= 0, determinant <= 0, a non-finite solution).
+ * counts (device int64 [7]) = the five of lrf_mesh_simplify, then the emitted clusters left at the mean and the emitted
+ * clusters whose solution was clamped to the cell.  Sixteen launches (fifteen without dedupe, six with Nf = 0), no host
+ * synchronisation.  workspace: lrf_mesh_simplify_quadric_workspace_bytes(Nv, Nf, cells) bytes (0 for refused arguments),
+ * 8-byte aligned.  Refused before any launch: everything lrf_mesh_simplify refuses, and a regularize that is not finite or
+ * lies outside (0, 1]. */
+typedef struct LrfMeshSimplifyQuadric {
+  LrfMeshSimplify mesh;
+  double regularize;
+} LrfMeshSimplifyQuadric;
+size_t lrf_mesh_simplify_quadric_workspace_bytes(int64_t Nv, int64_t Nf, int64_t cells);
+int lrf_mesh_simplify_quadric(const LrfMeshSimplifyQuadric* q, float* vertices_out, uint8_t* rgb8_out /* nullable */,
+                              int32_t* faces_out, int64_t* counts /* device [7] */, void* workspace, void* stream);
+
 /* The faces around each vertex of an indexed triangle mesh, and what is built on them: boundary and non-manifold edge counts,
  * area-weighted vertex normals and Taubin lambda|mu smoothing (csrc/lrf_mesh_smooth.inl states the semantics and the kernels).
  * Integer counts, int64 sums of fixed-point values and fp64 operations each rounded on its own: every call leaves the same

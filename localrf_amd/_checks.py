@@ -62,6 +62,13 @@ def check_flag(name, x):
     return bool(x)
 
 
+def check_choice(name, x, choices):
+    """x as one of the strings `choices`."""
+    if not isinstance(x, str) or x not in choices:
+        raise ValueError(f"{name} must be one of {', '.join(repr(c) for c in choices)}, got {x!r}")
+    return x
+
+
 def check_range(depth_range):
     if len(depth_range) != 2:
         raise ValueError(f"depth_range must be (d_min, d_max), got {depth_range!r}")

@@ -149,6 +149,10 @@ class LrfMeshSimplify(C.Structure):
                 ("dedupe", C.c_int32), ("reserved", C.c_int32)]
 
 
+class LrfMeshSimplifyQuadric(C.Structure):
+    _fields_ = [("mesh", LrfMeshSimplify), ("regularize", C.c_double)]
+
+
 class LrfMeshSmooth(C.Structure):
     _fields_ = [("vertices", _f), ("faces", C.c_void_p), ("Nv", C.c_int64), ("Nf", C.c_int64),
                 ("lo", C.c_double * 3), ("lam", C.c_double), ("mu", C.c_double),
@@ -317,6 +321,9 @@ SYMBOLS = {
     "lrf_mesh_simplify_bounds": (C.c_int, [_f, C.c_int64, C.POINTER(C.c_double), C.c_double, C.c_void_p, C.c_void_p]),
     "lrf_mesh_simplify_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64]),
     "lrf_mesh_simplify": (C.c_int, [C.POINTER(LrfMeshSimplify), _f, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "lrf_mesh_simplify_quadric_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64]),
+    "lrf_mesh_simplify_quadric": (C.c_int, [C.POINTER(LrfMeshSimplifyQuadric), _f, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p]),
     "lrf_mesh_incidence_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
     "lrf_mesh_incidence": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "lrf_mesh_topology": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

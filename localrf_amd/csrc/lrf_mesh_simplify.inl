@@ -58,6 +58,41 @@
 //   k_ms_write         a referenced cluster's position and colour to its row; a kept face's three clusters, as rows, to its row
 //   k_ms_finish        flag bit 0: counts[1] = -1 (a bad face index); bit 1: counts[0] = -1 (a vertex outside the box)
 // With Nf = 0 no face kernel runs: zero, mark, count, scan, finish.
+//
+// Quadric placement (lrf_mesh_simplify_quadric): items 1, 2, 3, 5 and 6 as above and item 4's colour; item 4's position becomes
+// the minimum of the cluster's summed plane quadric (Lindstrom, out-of-core simplification), inside the cluster's closed cell.
+// i_c is the integer cell of cluster c; i_v, q_v are item 1's cell and fraction of vertex v.
+//   a. Contributions.  A face contributes once to each DISTINCT cluster among its three corners, whether it survives or not.
+//      In the frame of cluster c, in cell units: u_j = (double)(i_vj - i_c) + (double)q_vj * 2^-32; n = (u_1 - u_0) x (u_2 - u_0)
+//      (each component one product minus another); d = -((n_x u_0x + n_y u_0y) + n_z u_0z); the nine coefficients n_x^2, n_y^2,
+//      n_z^2, n_x n_y, n_x n_z, n_y n_z, -d n_x, -d n_y, -d n_z.  Every operation rounded on its own.  n is not normalised: a face
+//      weighs by its squared area, and there is no square root and no division.  g = max(n_x^2, n_y^2, n_z^2, d^2); a
+//      contribution with g == 0 (a face without area, a repeated index) or g not finite is skipped.
+//   b. One exponent per cluster.  E_c = the maximum of ilogb(g) over the cluster's contributions (int32 atomicMax).  A
+//      contribution adds llrint(ldexp(coef, 40 - E_c)), of magnitude <= 2^41, to nine int64 sums and 1 to the uint32 count m_c
+//      (integer atomicAdd: no order).  The sums are exact for m_c < 2^21; a cluster with m_c >= 2^21 keeps the mean.
+//   c. Solve (the common scale cancels).  A, b = the sums as doubles; mu = item 4's mean fraction ((double)S / (double)n) * 2^-32;
+//      tr = (A00 + A11) + A22, l = regularize * tr, M = A + l I, r = b + l mu.  x = adj(M) r / det(M) by cofactors in this order:
+//        c00 = M11 M22 - M12 M12   c01 = M02 M12 - M01 M22   c02 = M01 M12 - M02 M11
+//        c11 = M00 M22 - M02 M02   c12 = M01 M02 - M00 M12   c22 = M00 M11 - M01 M01
+//        det = (M00 c00 + M01 c01) + M02 c02
+//        x_0 = ((c00 r_0 + c01 r_1) + c02 r_2) / det, x_1 with (c01, c11, c12), x_2 with (c02, c12, c22)
+//      The cluster keeps the mean when m_c == 0, tr <= 0, det <= 0 or an x_k is not finite; else every x_k is clamped to [0, 1].
+//      The regulariser decides the position inside a plane and along a crease.
+//   d. Position: (float)(origin[k] + ((double)i_c[k] + x_k) * cell), item 4's expression with x in place of the mean fraction.
+// The bytes depend on neither the vertex order, the face order nor the scheduling.  No waiting, as above: single atomics whose
+// results nobody reads, never retried; constant trip counts; no scratch.
+// lrf_mesh_simplify_quadric, sixteen launches (fifteen without dedupe, six without faces): k_ms_quadric_zero first (the sums and
+// counts = 0, E = INT_MIN, counts[5], counts[6] = 0), the launches of lrf_mesh_simplify up to k_ms_write, which leaves the
+// mean in every row, then
+//   k_ms_quadric_exponent    one lane per face: rule a's g per distinct cluster, the atomicMax of b.  Corner 0's maximum is
+//                            taken over each run of equal clusters in the wave first (a segmented scan)
+//   k_ms_quadric_accumulate  one lane per face: rule a again, the ten atomicAdds of b per distinct cluster; corner 0's ten
+//                            values are summed over each run of equal clusters in the wave first, as k_ms_accumulate does
+//   k_ms_quadric_place       one lane per cluster: an emitted cluster that solves (c) overwrites its row's position (d); the
+//                            others keep k_ms_write's bytes.  counts[5] += emitted clusters left at the mean, counts[6] +=
+//                            emitted clusters with an x_k outside [0, 1]
+// and k_ms_finish.
 namespace lrf {
 
 constexpr int MS_NT = 256;
@@ -306,14 +341,20 @@ __global__ __launch_bounds__(MS_NT) void k_ms_faces_keep(const int* __restrict__
   wave_count(&counts[4], keyed && !keep);
 }
 
-// item 4's position: every operation is rounded on its own
-__device__ __forceinline__ float ms_position(double origin, double cell, int i, unsigned long long S, unsigned n) {
+// item 4's position from the fraction of the cell, and the mean fraction: every operation is rounded on its own
+__device__ __forceinline__ float ms_position_at(double origin, double cell, int i, double frac) {
 #pragma clang fp contract(off)
-  const double mean = (double)S / (double)n;
-  const double frac = mean * (1.0 / MS_Q_ONE);
   const double t = (double)i + frac;
   const double x = t * cell;
   return (float)(origin + x);
+}
+__device__ __forceinline__ double ms_mean_fraction(unsigned long long S, unsigned n) {
+#pragma clang fp contract(off)
+  const double mean = (double)S / (double)n;
+  return mean * (1.0 / MS_Q_ONE);
+}
+__device__ __forceinline__ float ms_position(double origin, double cell, int i, unsigned long long S, unsigned n) {
+  return ms_position_at(origin, cell, i, ms_mean_fraction(S, n));
 }
 
 // bits, pre, wg: two stacked keep lists of `words` words each (referenced clusters, faces), scanned
@@ -343,6 +384,246 @@ __global__ __launch_bounds__(MS_NT) void k_ms_write(MsGrid g, const unsigned lon
 #pragma unroll
     for (int k = 0; k < 3; ++k) faces_out[3 * row + k] = (int)clusters.rank((long long)tri[3 * i + k]);
   }
+}
+
+// ---------------------------------------------------------------------------------------------- quadric placement (rules a-d)
+constexpr unsigned MS_Q_CAP = 1u << 21;                             // the cap of rule b: below it the nine sums are exact
+constexpr int MS_Q_BITS = 40;                                       // a scaled coefficient has magnitude <= 2^41
+constexpr int MS_Q_NONE = -0x7fffffff - 1;                          // E of a cluster without a contribution
+
+// the corners of face f: clusters, cells, fractions -> false for a face that contributes nowhere (past Nf, an index outside
+// [0, Nv), which is never dereferenced, or a corner without a cluster)
+__device__ __forceinline__ bool ms_quadric_face(const float* __restrict__ vertices, const int* __restrict__ faces, long long f, int Nf,
+                                                int Nv, const MsGrid& g, const int* __restrict__ cluster_of, int* cl, int (*i)[3],
+                                                unsigned long long (*q)[3]) {
+  if (f >= Nf) return false;
+  int at[3];
+#pragma unroll
+  for (int j = 0; j < 3; ++j) at[j] = faces[3 * f + j];
+  if (!(in_range(at[0], Nv) && in_range(at[1], Nv) && in_range(at[2], Nv))) return false;
+  bool ok = true;
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    cl[j] = cluster_of[at[j]];
+    ok = ok && in_range(cl[j], Nv);
+  }
+  if (!ok) return false;
+#pragma unroll
+  for (int j = 0; j < 3; ++j) ok = ms_cell(vertices + 3 * (size_t)at[j], g.origin, g.cell, i[j], q[j]) && ok;
+  return ok;
+}
+
+// corner j speaks for its cluster unless an earlier corner has the same one: once per distinct cluster of the face
+__device__ __forceinline__ bool ms_quadric_speaks(const int* cl, int j) {
+  return j == 0 || (cl[j] != cl[0] && (j == 1 || cl[j] != cl[1]));
+}
+
+// rule a: the nine coefficients of the face's plane in the frame of corner j's cell -> g; every operation rounded on its own
+__device__ __forceinline__ double ms_quadric_coefs(const int (*i)[3], const unsigned long long (*q)[3], int j, double* coef) {
+#pragma clang fp contract(off)
+  double u[3][3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const double frac = (double)q[c][k] * (1.0 / MS_Q_ONE);
+      u[c][k] = (double)(i[c][k] - i[j][k]) + frac;                 // |i| < 2^30: the difference is an int
+    }
+  }
+  double a[3], b[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) { a[k] = u[1][k] - u[0][k]; b[k] = u[2][k] - u[0][k]; }
+  const double y0 = a[1] * b[2], z0 = a[2] * b[1], y1 = a[2] * b[0], z1 = a[0] * b[2], y2 = a[0] * b[1], z2 = a[1] * b[0];
+  const double nx = y0 - z0, ny = y1 - z1, nz = y2 - z2;
+  const double px = nx * u[0][0], py = ny * u[0][1], pz = nz * u[0][2];
+  const double pxy = px + py;
+  const double d = -(pxy + pz);
+  const double md = -d;
+  coef[0] = nx * nx; coef[1] = ny * ny; coef[2] = nz * nz;
+  coef[3] = nx * ny; coef[4] = nx * nz; coef[5] = ny * nz;
+  coef[6] = md * nx; coef[7] = md * ny; coef[8] = md * nz;
+  const double dd = d * d;
+  return fmax(fmax(coef[0], coef[1]), fmax(coef[2], dd));           // all four are finite: |u| < 2^32
+}
+// a contribution counts when g is positive and finite
+__device__ __forceinline__ bool ms_quadric_counts(double g) { return g > 0.0 && g < __builtin_inf(); }
+
+__global__ __launch_bounds__(MS_NT) void k_ms_quadric_zero(long long* __restrict__ Q, unsigned* __restrict__ m, int* __restrict__ E,
+                                                           size_t n_clusters, long long* __restrict__ counts) {
+  const size_t stride = (size_t)gridDim.x * MS_NT;
+  const size_t t0 = (size_t)blockIdx.x * MS_NT + threadIdx.x;
+  for (size_t i = t0; i < 9 * n_clusters; i += stride) Q[i] = 0;
+  for (size_t i = t0; i < n_clusters; i += stride) { m[i] = 0u; E[i] = MS_Q_NONE; }
+  if (t0 < 2) counts[5 + t0] = 0;
+}
+
+// rule b, the exponent: one lane per face, atomicMax of ilogb(g) per distinct cluster.  Corner 0's maxima are taken over the
+// runs of equal clusters in the wave first (a segmented scan, every lane takes part), as k_ms_accumulate sums its runs.
+__global__ __launch_bounds__(MS_NT) void k_ms_quadric_exponent(const float* __restrict__ vertices, const int* __restrict__ faces, int Nf,
+                                                               int Nv, MsGrid g, const int* __restrict__ cluster_of, int* E) {
+  const long long f = (long long)blockIdx.x * MS_NT + threadIdx.x;
+  const int lane = threadIdx.x & 63;
+  int cl[3] = {-1, -1, -1}, i[3][3];
+  unsigned long long q[3][3];
+  int e[3] = {MS_Q_NONE, MS_Q_NONE, MS_Q_NONE};
+  if (ms_quadric_face(vertices, faces, f, Nf, Nv, g, cluster_of, cl, i, q)) {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      if (!ms_quadric_speaks(cl, j)) continue;
+      double coef[9];
+      const double gg = ms_quadric_coefs(i, q, j, coef);
+      if (ms_quadric_counts(gg)) e[j] = ilogb(gg);
+    }
+  } else {
+    cl[0] = -1;
+  }
+#pragma unroll
+  for (int j = 1; j < 3; ++j)
+    if (e[j] != MS_Q_NONE) atomicMax(&E[cl[j]], e[j]);
+  const int key = cl[0];
+  const int key_before = __shfl_up(key, 1, 64), key_after = __shfl_down(key, 1, 64);
+  bool head = lane == 0 || key_before != key;
+  int top = e[0];
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const int tt = __shfl_up(top, off, 64);
+    const int th = __shfl_up((int)head, off, 64);
+    if (lane >= off && !head) {
+      top = tt > top ? tt : top;
+      head = th != 0;
+    }
+  }
+  const bool tail = lane == 63 || key_after != key;
+  if (key >= 0 && tail && top != MS_Q_NONE) atomicMax(&E[key], top);
+}
+
+// rule b, the sums: one lane per face; per distinct cluster nine int64 atomicAdds of llrint(ldexp(coef, 40 - E)) and one of the
+// count.  Corner 0's ten values are summed over the runs of equal clusters in the wave first: integers, so the same sums.
+__global__ __launch_bounds__(MS_NT) void k_ms_quadric_accumulate(const float* __restrict__ vertices, const int* __restrict__ faces,
+                                                                 int Nf, int Nv, MsGrid g, const int* __restrict__ cluster_of,
+                                                                 const int* __restrict__ E, unsigned long long* Q, unsigned* m) {
+  const long long f = (long long)blockIdx.x * MS_NT + threadIdx.x;
+  const int lane = threadIdx.x & 63;
+  int cl[3] = {-1, -1, -1}, i[3][3];
+  unsigned long long q[3][3];
+  unsigned long long s[9] = {0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull};     // corner 0's, two's complement
+  unsigned n = 0u;
+  if (ms_quadric_face(vertices, faces, f, Nf, Nv, g, cluster_of, cl, i, q)) {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      if (!ms_quadric_speaks(cl, j)) continue;
+      double coef[9];
+      const double gg = ms_quadric_coefs(i, q, j, coef);
+      if (!ms_quadric_counts(gg)) continue;
+      const int ec = E[cl[j]];
+      if (ec < ilogb(gg)) continue;                                 // not the E of k_ms_quadric_exponent over these faces
+      const int shift = MS_Q_BITS - ec;
+      if (j == 0) {
+#pragma unroll
+        for (int k = 0; k < 9; ++k) s[k] = (unsigned long long)llrint(ldexp(coef[k], shift));
+        n = 1u;
+      } else {
+#pragma unroll
+        for (int k = 0; k < 9; ++k) atomicAdd(&Q[9 * (size_t)cl[j] + k], (unsigned long long)llrint(ldexp(coef[k], shift)));
+        atomicAdd(&m[cl[j]], 1u);
+      }
+    }
+  } else {
+    cl[0] = -1;
+  }
+  const int key = cl[0];
+  const int key_before = __shfl_up(key, 1, 64), key_after = __shfl_down(key, 1, 64);
+  bool head = lane == 0 || key_before != key;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    unsigned long long ts[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) ts[k] = __shfl_up(s[k], off, 64);
+    const unsigned tn = __shfl_up(n, off, 64);
+    const int th = __shfl_up((int)head, off, 64);
+    if (lane >= off && !head) {
+#pragma unroll
+      for (int k = 0; k < 9; ++k) s[k] += ts[k];
+      n += tn;
+      head = th != 0;
+    }
+  }
+  const bool tail = lane == 63 || key_after != key;
+  if (key < 0 || !tail || n == 0u) return;
+#pragma unroll
+  for (int k = 0; k < 9; ++k) atomicAdd(&Q[9 * (size_t)key + k], s[k]);
+  atomicAdd(&m[key], n);
+}
+
+// rule c in the fixed order: M = A + l I, r = b + l mu, x = adj(M) r / det(M) by cofactors -> false where the mean stands
+__device__ __forceinline__ bool ms_quadric_solve(const long long* __restrict__ Q, const double* mu, double regularize, double* x) {
+#pragma clang fp contract(off)
+  const double A00 = (double)Q[0], A11 = (double)Q[1], A22 = (double)Q[2];
+  const double M01 = (double)Q[3], M02 = (double)Q[4], M12 = (double)Q[5];
+  const double tr = (A00 + A11) + A22;
+  if (!(tr > 0.0)) return false;
+  const double l = regularize * tr;
+  const double M00 = A00 + l, M11 = A11 + l, M22 = A22 + l;
+  double r[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const double lm = l * mu[k];
+    r[k] = (double)Q[6 + k] + lm;
+  }
+  const double p0 = M11 * M22, p1 = M12 * M12, p2 = M02 * M12, p3 = M01 * M22, p4 = M01 * M12, p5 = M02 * M11;
+  const double p6 = M00 * M22, p7 = M02 * M02, p8 = M01 * M02, p9 = M00 * M12, p10 = M00 * M11, p11 = M01 * M01;
+  const double c00 = p0 - p1, c01 = p2 - p3, c02 = p4 - p5, c11 = p6 - p7, c12 = p8 - p9, c22 = p10 - p11;
+  const double d0 = M00 * c00, d1 = M01 * c01, d2 = M02 * c02;
+  const double d01 = d0 + d1;
+  const double det = d01 + d2;
+  if (!(det > 0.0)) return false;
+  const double row[3][3] = {{c00, c01, c02}, {c01, c11, c12}, {c02, c12, c22}};
+  bool ok = true;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const double t0 = row[k][0] * r[0], t1 = row[k][1] * r[1], t2 = row[k][2] * r[2];
+    const double t01 = t0 + t1;
+    const double num = t01 + t2;
+    x[k] = num / det;
+    ok = ok && is_finite(x[k]);
+  }
+  return ok;
+}
+
+// rules c and d, after k_ms_write: one lane per cluster; an emitted cluster whose quadric solves takes the solved position in its
+// row, every other row keeps k_ms_write's mean.  counts[5] += emitted clusters left at the mean, counts[6] += clamped ones.
+// bits, pre, wg: the referenced clusters' keep list, scanned
+__global__ __launch_bounds__(MS_NT) void k_ms_quadric_place(MsGrid g, double regularize, const unsigned long long* __restrict__ S,
+                                                            const unsigned* __restrict__ nC, const int* __restrict__ cell_of,
+                                                            const long long* __restrict__ Q, const unsigned* __restrict__ m,
+                                                            const unsigned long long* __restrict__ bits, const unsigned* __restrict__ pre,
+                                                            const unsigned* __restrict__ wg, long long words,
+                                                            float* __restrict__ vertices_out, unsigned long long* counts) {
+  const long long i = (long long)blockIdx.x * MS_NT + threadIdx.x;
+  const KeepList clusters{bits, pre, wg};
+  const bool live = i < words * 64 && clusters.kept(i);
+  bool solved = false, clamped = false;
+  if (live) {
+    const unsigned mc = m[i];
+    double mu[3], x[3];
+    const unsigned n = nC[4 * i];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) mu[k] = ms_mean_fraction(S[3 * i + k], n);
+    solved = mc > 0u && mc < MS_Q_CAP && ms_quadric_solve(Q + 9 * i, mu, regularize, x);
+    if (solved) {
+      const size_t row = (size_t)(int)clusters.rank(i);
+      const int lin = cell_of[i];
+      const int c[3] = {lin % g.dims[0], (lin / g.dims[0]) % g.dims[1], lin / g.dims[0] / g.dims[1]};
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        clamped = clamped || x[k] < 0.0 || x[k] > 1.0;
+        const double xk = fmin(fmax(x[k], 0.0), 1.0);
+        vertices_out[3 * row + k] = ms_position_at(g.origin[k], g.cell, g.lo[k] + c[k], xk);
+      }
+    }
+  }
+  wave_count(&counts[5], live && !solved);
+  wave_count(&counts[6], clamped);
 }
 
 __global__ __launch_bounds__(64) void k_ms_finish(const int* __restrict__ flag, long long* __restrict__ counts) {
@@ -393,6 +674,83 @@ static MsWs ms_carve(void* workspace, long long Nv, long long Nf, long long cell
   return w;
 }
 
+// the quadric workspace: the layout above as one piece, then per cluster (at most Nv) the nine sums, the count and the exponent
+struct MsQuadricWs { MsWs mean; long long* Q; unsigned* m; int* E; size_t bytes; };
+static MsQuadricWs ms_quadric_carve(void* workspace, long long Nv, long long Nf, long long cells) {
+  Carver c(workspace);
+  MsQuadricWs w;
+  w.mean = ms_carve(workspace, Nv, Nf, cells);
+  c.take<char>(w.mean.bytes);
+  w.Q = c.take<long long>(9 * (size_t)Nv);
+  w.m = c.take<unsigned>((size_t)Nv);
+  w.E = c.take<int>((size_t)Nv);
+  w.bytes = c.bytes();
+  return w;
+}
+
+// the refusals that both entry points share, under the caller's name -> 0 and the cells of the box
+static int ms_check(const char* who, const LrfMeshSimplify* m, const float* vertices_out, const uint8_t* rgb8_out,
+                    const int32_t* faces_out, const int64_t* counts, const void* workspace, long long* cells_out) {
+  if (!mesh_shape(m->Nv, m->Nf)) return refuse(who, "need 1 <= Nv < 2^31 and 0 <= Nf < 2^31");
+  if (!m->vertices || !vertices_out || !counts || !workspace || (m->Nf && (!m->faces || !faces_out))) return refuse(who, "null argument");
+  if (!m->rgb8 != !rgb8_out) return refuse(who, "rgb8 and rgb8_out go together");
+  long long cells = 1;
+  for (int k = 0; k < 3; ++k) {
+    if (m->dims[k] < 1 || cells >= (1ll << 31)) return refuse(who, "need dims >= 1 and 1 <= cells < 2^31");
+    cells *= m->dims[k];
+  }
+  if (cells >= (1ll << 31)) return refuse(who, "need dims >= 1 and 1 <= cells < 2^31");
+  for (int k = 0; k < 3; ++k)
+    if (m->lo[k] <= -(1 << 30) || (long long)m->lo[k] + m->dims[k] > (1 << 30)) return refuse(who, "the box must lie inside (-2^30, 2^30)");
+  if (!(is_finite(m->origin[0]) && is_finite(m->origin[1]) && is_finite(m->origin[2]))) return refuse(who, "origin must hold 3 finite values");
+  if (!(m->cell > 0.0 && is_finite(m->cell))) return refuse(who, "cell must be finite and > 0");
+  if (misaligned(3, m->vertices, m->faces, vertices_out, faces_out)) return refuse(who, "float and int32 arrays must be 4-byte aligned");
+  if (misaligned(7, counts, workspace)) return refuse(who, "counts and workspace must be 8-byte aligned");
+  *cells_out = cells;
+  return 0;
+}
+
+static MsGrid ms_grid(const LrfMeshSimplify* m) {
+  MsGrid g;
+  memset(&g, 0, sizeof(g));
+  for (int k = 0; k < 3; ++k) { g.origin[k] = m->origin[k]; g.lo[k] = m->lo[k]; g.dims[k] = m->dims[k]; }
+  g.cell = m->cell;
+  return g;
+}
+
+// every launch of the mean placement but the last, k_ms_finish
+static int ms_enqueue(const LrfMeshSimplify* m, const MsWs& w, const MsGrid& g, float* vertices_out, uint8_t* rgb8_out,
+                      int32_t* faces_out, int64_t* counts, void* workspace, hipStream_t st) {
+  const int Nv = (int)m->Nv, Nf = (int)m->Nf;
+  long long* cnt = reinterpret_cast<long long*>(counts);
+  unsigned long long* ucnt = reinterpret_cast<unsigned long long*>(counts);
+  const unsigned long long mask = w.cap - 1;
+  const bool dedupe = m->dedupe != 0 && Nf > 0;
+  const size_t n_table = dedupe ? w.cap / 2 : 0;                    // 8-byte words
+  const size_t most = w.n_zero > n_table ? w.n_zero : n_table;
+  const size_t zero_blocks = (most + MS_NT - 1) / MS_NT;
+  const unsigned nbv = blocks_for(Nv, MS_NT), nbf = blocks_for(Nf, MS_NT);
+  LRF_TRY(launch(k_ms_zero, (unsigned)(zero_blocks < MS_ZERO_BLOCKS ? zero_blocks : MS_ZERO_BLOCKS), MS_NT, st,
+                 static_cast<unsigned long long*>(workspace), w.n_zero, reinterpret_cast<unsigned long long*>(w.table), n_table, cnt));
+  LRF_TRY(launch(k_ms_mark, nbv, MS_NT, st, m->vertices, Nv, g, w.cell_bits, w.flag));
+  LRF_TRY(launch(k_ms_count_words, blocks_for((long long)w.words_c, MS_NT), MS_NT, st, w.cell_bits, w.pre_c, w.wg_c, w.words_c));
+  LRF_TRY(launch(k_points_scan, 1, PTS_SCAN_NT, st, w.wg_c, w.words_c / KEEP_GROUP, cnt + 2));
+  if (Nf) {
+    const long long words = (long long)w.words_2;
+    LRF_TRY(launch(k_ms_accumulate, nbv, MS_NT, st, m->vertices, m->rgb8, Nv, g, w.cell_bits, w.pre_c, w.wg_c, w.S, w.nC, w.cell_of,
+                   w.cluster_of));
+    LRF_TRY(launch(k_ms_faces_map, nbf, MS_NT, st, m->faces, Nf, Nv, w.cluster_of, w.tri, w.flag, ucnt));
+    if (dedupe) LRF_TRY(launch(k_ms_faces_insert, nbf, MS_NT, st, w.tri, Nf, w.table, mask));
+    LRF_TRY(launch(k_ms_faces_keep, blocks_for(words * 64, MS_NT), MS_NT, st, w.tri, Nf, Nv, w.table, mask, dedupe ? 1 : 0,
+                   w.bits_2 + words, w.bits_2, ucnt));
+    LRF_TRY(launch(k_ms_count_words, dim3(blocks_for(words, MS_NT), 2), MS_NT, st, w.bits_2, w.pre_2, w.wg_2, words));
+    LRF_TRY(launch(k_points_scan, 2, PTS_SCAN_NT, st, w.wg_2, words / KEEP_GROUP, cnt));
+    LRF_TRY(launch(k_ms_write, dim3(blocks_for(words * 64, MS_NT), 2), MS_NT, st, g, w.S, w.nC, w.cell_of, w.tri, w.bits_2, w.pre_2,
+                   w.wg_2, words, vertices_out, rgb8_out, faces_out));
+  }
+  return 0;
+}
+
 }  // namespace lrf
 
 extern "C" int lrf_mesh_simplify_bounds(const float* vertices, int64_t Nv, const double* origin, double cell, int32_t* out,
@@ -421,58 +779,48 @@ extern "C" size_t lrf_mesh_simplify_workspace_bytes(int64_t Nv, int64_t Nf, int6
 extern "C" int lrf_mesh_simplify(const LrfMeshSimplify* m, float* vertices_out, uint8_t* rgb8_out, int32_t* faces_out,
                                  int64_t* counts, void* workspace, void* stream) {
   using namespace lrf;
-  if (!m) return set_err("lrf_mesh_simplify: null argument");
-  if (!mesh_shape(m->Nv, m->Nf)) return set_err("lrf_mesh_simplify: need 1 <= Nv < 2^31 and 0 <= Nf < 2^31");
-  if (!m->vertices || !vertices_out || !counts || !workspace || (m->Nf && (!m->faces || !faces_out)))
-    return set_err("lrf_mesh_simplify: null argument");
-  if (!m->rgb8 != !rgb8_out) return set_err("lrf_mesh_simplify: rgb8 and rgb8_out go together");
-  long long cells = 1;
-  for (int k = 0; k < 3; ++k) {
-    if (m->dims[k] < 1 || cells >= (1ll << 31)) return set_err("lrf_mesh_simplify: need dims >= 1 and 1 <= cells < 2^31");
-    cells *= m->dims[k];
-  }
-  if (cells >= (1ll << 31)) return set_err("lrf_mesh_simplify: need dims >= 1 and 1 <= cells < 2^31");
-  for (int k = 0; k < 3; ++k)
-    if (m->lo[k] <= -(1 << 30) || (long long)m->lo[k] + m->dims[k] > (1 << 30))
-      return set_err("lrf_mesh_simplify: the box must lie inside (-2^30, 2^30)");
-  if (!(is_finite(m->origin[0]) && is_finite(m->origin[1]) && is_finite(m->origin[2])))
-    return set_err("lrf_mesh_simplify: origin must hold 3 finite values");
-  if (!(m->cell > 0.0 && is_finite(m->cell))) return set_err("lrf_mesh_simplify: cell must be finite and > 0");
-  if (misaligned(3, m->vertices, m->faces, vertices_out, faces_out))
-    return set_err("lrf_mesh_simplify: float and int32 arrays must be 4-byte aligned");
-  if (misaligned(7, counts, workspace)) return set_err("lrf_mesh_simplify: counts and workspace must be 8-byte aligned");
-  const int Nv = (int)m->Nv, Nf = (int)m->Nf;
+  const char* who = "lrf_mesh_simplify";
+  if (!m) return refuse(who, "null argument");
+  long long cells = 0;
+  LRF_TRY(ms_check(who, m, vertices_out, rgb8_out, faces_out, counts, workspace, &cells));
   const MsWs w = ms_carve(workspace, m->Nv, m->Nf, cells);
-  MsGrid g;
-  memset(&g, 0, sizeof(g));
-  for (int k = 0; k < 3; ++k) { g.origin[k] = m->origin[k]; g.lo[k] = m->lo[k]; g.dims[k] = m->dims[k]; }
-  g.cell = m->cell;
-  long long* cnt = reinterpret_cast<long long*>(counts);
-  unsigned long long* ucnt = reinterpret_cast<unsigned long long*>(counts);
-  const unsigned long long mask = w.cap - 1;
-  const bool dedupe = m->dedupe != 0 && Nf > 0;
-  const size_t n_table = dedupe ? w.cap / 2 : 0;                    // 8-byte words
-  const size_t most = w.n_zero > n_table ? w.n_zero : n_table;
-  const size_t zero_blocks = (most + MS_NT - 1) / MS_NT;
-  const unsigned nbv = blocks_for(Nv, MS_NT), nbf = blocks_for(Nf, MS_NT);
+  const MsGrid g = ms_grid(m);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  LRF_TRY(launch(k_ms_zero, (unsigned)(zero_blocks < MS_ZERO_BLOCKS ? zero_blocks : MS_ZERO_BLOCKS), MS_NT, st,
-                 static_cast<unsigned long long*>(workspace), w.n_zero, reinterpret_cast<unsigned long long*>(w.table), n_table, cnt));
-  LRF_TRY(launch(k_ms_mark, nbv, MS_NT, st, m->vertices, Nv, g, w.cell_bits, w.flag));
-  LRF_TRY(launch(k_ms_count_words, blocks_for((long long)w.words_c, MS_NT), MS_NT, st, w.cell_bits, w.pre_c, w.wg_c, w.words_c));
-  LRF_TRY(launch(k_points_scan, 1, PTS_SCAN_NT, st, w.wg_c, w.words_c / KEEP_GROUP, cnt + 2));
+  LRF_TRY(ms_enqueue(m, w, g, vertices_out, rgb8_out, faces_out, counts, workspace, st));
+  return launch(k_ms_finish, 1, 64, st, w.flag, reinterpret_cast<long long*>(counts));
+}
+
+extern "C" size_t lrf_mesh_simplify_quadric_workspace_bytes(int64_t Nv, int64_t Nf, int64_t cells) {
+  using namespace lrf;
+  return ms_shape(Nv, Nf, cells) ? ms_quadric_carve(nullptr, Nv, Nf, cells).bytes : 0;
+}
+
+extern "C" int lrf_mesh_simplify_quadric(const LrfMeshSimplifyQuadric* q, float* vertices_out, uint8_t* rgb8_out, int32_t* faces_out,
+                                         int64_t* counts, void* workspace, void* stream) {
+  using namespace lrf;
+  const char* who = "lrf_mesh_simplify_quadric";
+  if (!q) return refuse(who, "null argument");
+  const LrfMeshSimplify* m = &q->mesh;
+  long long cells = 0;
+  LRF_TRY(ms_check(who, m, vertices_out, rgb8_out, faces_out, counts, workspace, &cells));
+  if (!(q->regularize > 0.0 && q->regularize <= 1.0)) return refuse(who, "regularize must lie in (0, 1]");      // NaN fails
+  const int Nv = (int)m->Nv, Nf = (int)m->Nf;
+  const MsQuadricWs w = ms_quadric_carve(workspace, m->Nv, m->Nf, cells);
+  const MsGrid g = ms_grid(m);
+  long long* cnt = reinterpret_cast<long long*>(counts);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const size_t zero_blocks = (9 * (size_t)Nv + MS_NT - 1) / MS_NT;
+  LRF_TRY(launch(k_ms_quadric_zero, (unsigned)(zero_blocks < MS_ZERO_BLOCKS ? zero_blocks : MS_ZERO_BLOCKS), MS_NT, st, w.Q, w.m, w.E,
+                 (size_t)Nv, cnt));
+  LRF_TRY(ms_enqueue(m, w.mean, g, vertices_out, rgb8_out, faces_out, counts, workspace, st));
   if (Nf) {
-    const long long words = (long long)w.words_2;
-    LRF_TRY(launch(k_ms_accumulate, nbv, MS_NT, st, m->vertices, m->rgb8, Nv, g, w.cell_bits, w.pre_c, w.wg_c, w.S, w.nC, w.cell_of,
-                   w.cluster_of));
-    LRF_TRY(launch(k_ms_faces_map, nbf, MS_NT, st, m->faces, Nf, Nv, w.cluster_of, w.tri, w.flag, ucnt));
-    if (dedupe) LRF_TRY(launch(k_ms_faces_insert, nbf, MS_NT, st, w.tri, Nf, w.table, mask));
-    LRF_TRY(launch(k_ms_faces_keep, blocks_for(words * 64, MS_NT), MS_NT, st, w.tri, Nf, Nv, w.table, mask, dedupe ? 1 : 0,
-                   w.bits_2 + words, w.bits_2, ucnt));
-    LRF_TRY(launch(k_ms_count_words, dim3(blocks_for(words, MS_NT), 2), MS_NT, st, w.bits_2, w.pre_2, w.wg_2, words));
-    LRF_TRY(launch(k_points_scan, 2, PTS_SCAN_NT, st, w.wg_2, words / KEEP_GROUP, cnt));
-    LRF_TRY(launch(k_ms_write, dim3(blocks_for(words * 64, MS_NT), 2), MS_NT, st, g, w.S, w.nC, w.cell_of, w.tri, w.bits_2, w.pre_2,
-                   w.wg_2, words, vertices_out, rgb8_out, faces_out));
+    const long long words = (long long)w.mean.words_2;
+    const unsigned nbf = blocks_for(Nf, MS_NT);
+    LRF_TRY(launch(k_ms_quadric_exponent, nbf, MS_NT, st, m->vertices, m->faces, Nf, Nv, g, w.mean.cluster_of, w.E));
+    LRF_TRY(launch(k_ms_quadric_accumulate, nbf, MS_NT, st, m->vertices, m->faces, Nf, Nv, g, w.mean.cluster_of, w.E,
+                   reinterpret_cast<unsigned long long*>(w.Q), w.m));
+    LRF_TRY(launch(k_ms_quadric_place, blocks_for(words * 64, MS_NT), MS_NT, st, g, q->regularize, w.mean.S, w.mean.nC, w.mean.cell_of,
+                   w.Q, w.m, w.mean.bits_2, w.mean.pre_2, w.mean.wg_2, words, vertices_out, reinterpret_cast<unsigned long long*>(counts)));
   }
-  return launch(k_ms_finish, 1, 64, st, w.flag, cnt);
+  return launch(k_ms_finish, 1, 64, st, w.mean.flag, cnt);
 }
