@@ -999,6 +999,36 @@ int lrf_mesh_sample_emit(const float* vertices, const int32_t* faces, int64_t Nv
 int lrf_distance_summary(const float* distance, int64_t N, const float* thresholds /* host [n_thresholds] */,
                          int32_t n_thresholds, float unit, int64_t* words /* device [16] */, void* stream);
 
+/* Registration around lrf_mesh_closest: a similarity applied to points, the exact moments of corresponding pairs, and the
+ * normal equations of one linearised point-to-plane similarity step (csrc/lrf_align.inl states every rule and the overflow
+ * bounds; the fit itself is the host's: localrf_amd/alignment.py).  Integer sums: the same words on every run and for every
+ * order of the points.
+ * lrf_align_transform: T, HOST, 12 doubles, row-major 3 x 4; out_k = (float)(((T[4k] x + T[4k+1] y) + T[4k+2] z) + T[4k+3]) in
+ * fp64 without contraction.  out may be points.  One launch (none with N = 0).
+ * lrf_align_pairs: a, b [N,3]; keep uint8 [N] (nullable: every pair is kept).  Per coordinate the integer rint((x - c_k) / h).
+ * words (device int64 [24]) = pairs summed, out_of_range (an integer coordinate of magnitude >= 2^20), masked (keep == 0),
+ * nonfinite, sum a [3], sum b [3], sum a_i b_j [9] row-major, sum |a|^2, sum |b|^2, 0, 0, 0.  Two launches (one with N = 0).
+ * lrf_align_plane: points, closest [N,3], face int32 [N] and distance [N] as lrf_mesh_closest wrote them for points against the
+ * mesh; gate: fp32, +inf allowed.  words (device int64 [48]) = points summed, unmatched (no face, a distance not finite),
+ * gated (distance > gate), degenerate (a face without area), out_of_range (a coordinate of (p - c) / u or (q - c) / u beyond
+ * [-1, 1]), 0, sum llrint(r r 2^36), sum llrint(J_k r 2^36) [7], sum llrint(J_k J_l 2^36) for k <= l [28], 0 .. 0, with r the
+ * point-to-plane residual and J = (pt x n, n, pt . n) in units of u.  Two launches (one with N = 0).
+ * Refused before any launch: null or misaligned pointers (float, int32 arrays 4 bytes; T and words 8), N outside [0, 2^20]
+ * (transform: [0, 2^31)), h or u not a positive power of two, c or T not finite, gate < 0 or NaN, Nv outside [1, 2^31), Nf
+ * outside [1, 2^31). */
+typedef struct LrfAlignFrame { double c[3]; double h; } LrfAlignFrame;
+typedef struct LrfAlignPlane {
+  const float* vertices; const int32_t* faces; const float* points; const float* closest; const int32_t* face;
+  const float* distance;
+  int64_t Nv, Nf, N;
+  double c[3]; double u;
+  float gate; int32_t reserved;
+} LrfAlignPlane;
+int lrf_align_transform(const double* T /* host [12] */, const float* points, int64_t N, float* out, void* stream);
+int lrf_align_pairs(const LrfAlignFrame* fr, const float* a, const float* b, const uint8_t* keep /* nullable */, int64_t N,
+                    int64_t* words /* device [24] */, void* stream);
+int lrf_align_plane(const LrfAlignPlane* p, int64_t* words /* device [48] */, void* stream);
+
 /* Depth quantiles of a ray: the distance at which its accumulated weight first reaches q; q = 0.5 is the median depth, which
  * always lies on a surface the ray met (csrc/lrf_quantile.inl states the arithmetic: fp32 without contraction, one fixed
  * summation order per ray).  With C_i the inclusive prefix sum of the weights lrf_render_fwd leaves in weight_out and i* the

@@ -28,6 +28,9 @@ Public surface mirrors the reference's names:
                                     (a texture atlas baked for a mesh from rendered frames, OBJ + PNG export; no reference row)
   mesh_distance.MeshIndex / sample_surface / distance_summary / cloud_to_mesh / mesh_distance
                                     (point-to-mesh distance: surface error, Chamfer, Hausdorff and F-score; no reference row)
+  alignment.fit_pairs / trajectory_error / icp / align_meshes / transform_points / transform_mesh
+                                    (similarity registration of trajectories, clouds and meshes: closed-form fit from exact
+                                    integer moments, point-to-plane ICP, trajectory error after alignment; no reference row)
 The arithmetic of TensorVMSplit.forward and of LocalTensorfs.forward (ray generation, field
 blend, exposure) runs in hand-written HIP kernels for gfx950 (csrc/), reached through the C ABI
 of include/lrf.h.
@@ -48,6 +51,7 @@ from . import mesh  # noqa: F401
 from . import mesh_raster  # noqa: F401
 from . import mesh_texture  # noqa: F401
 from . import mesh_distance  # noqa: F401
+from . import alignment  # noqa: F401
 from .frames import DeviceFrames  # noqa: F401
 
-__all__ = ["TensorVMSplit", "AlphaGridMask", "MLPRender_Fea_late_view", "LocalTensorfs", "rays", "losses", "metrics", "diagnostics", "novel_views", "pointcloud", "normals", "depth_quantiles", "mesh", "mesh_raster", "mesh_texture", "mesh_distance", "NativeError", "FusedAdam", "DeviceFrames"]
+__all__ = ["TensorVMSplit", "AlphaGridMask", "MLPRender_Fea_late_view", "LocalTensorfs", "rays", "losses", "metrics", "diagnostics", "novel_views", "pointcloud", "normals", "depth_quantiles", "mesh", "mesh_raster", "mesh_texture", "mesh_distance", "alignment", "NativeError", "FusedAdam", "DeviceFrames"]

@@ -182,6 +182,16 @@ class LrfMeshIndex(C.Structure):
                 ("lo", C.c_double * 3), ("cell", C.c_double), ("dims", C.c_int32 * 3), ("reserved", C.c_int32)]
 
 
+class LrfAlignFrame(C.Structure):
+    _fields_ = [("c", C.c_double * 3), ("h", C.c_double)]
+
+
+class LrfAlignPlane(C.Structure):
+    _fields_ = [("vertices", _f), ("faces", C.c_void_p), ("points", _f), ("closest", _f), ("face", C.c_void_p), ("distance", _f),
+                ("Nv", C.c_int64), ("Nf", C.c_int64), ("N", C.c_int64), ("c", C.c_double * 3), ("u", C.c_double),
+                ("gate", C.c_float), ("reserved", C.c_int32)]
+
+
 class LrfMeshTexture(C.Structure):
     _fields_ = [("vertices", _f), ("rgb8", C.c_void_p), ("faces", C.c_void_p), ("frames", C.c_void_p), ("mesh_depth", _f),
                 ("cam2world", _f), ("focal", _f), ("center", _f), ("Nv", C.c_int64), ("Nf", C.c_int64),
@@ -352,6 +362,9 @@ SYMBOLS = {
     "lrf_mesh_sample_emit": (C.c_int, [_f, C.c_void_p, C.c_int64, C.c_int64, C.c_double, C.c_void_p, C.c_int64, _f, C.c_void_p,
                                        C.c_void_p]),
     "lrf_distance_summary": (C.c_int, [_f, C.c_int64, C.POINTER(C.c_float), C.c_int32, C.c_float, C.c_void_p, C.c_void_p]),
+    "lrf_align_transform": (C.c_int, [C.POINTER(C.c_double), _f, C.c_int64, _f, C.c_void_p]),
+    "lrf_align_pairs": (C.c_int, [C.POINTER(LrfAlignFrame), _f, _f, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "lrf_align_plane": (C.c_int, [C.POINTER(LrfAlignPlane), C.c_void_p, C.c_void_p]),
     "lrf_mesh_texture_state_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
     "lrf_mesh_texture_bake": (C.c_int, [C.POINTER(LrfMeshTexture), _f, C.c_void_p]),
     "lrf_mesh_texture_resolve": (C.c_int, [C.POINTER(LrfMeshTexture), _f, C.POINTER(C.c_uint8), C.c_void_p, C.c_void_p, C.c_void_p,

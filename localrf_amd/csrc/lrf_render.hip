@@ -1316,6 +1316,7 @@ static hipError_t lds_opt_in() {
 #include "lrf_mesh_raster.inl"
 #include "lrf_mesh_texture.inl"
 #include "lrf_mesh_distance.inl"
+#include "lrf_align.inl"
 #include "lrf_tsdf_blocks.inl"
 #include "lrf_reg.inl"
 #include "lrf_mask.inl"
