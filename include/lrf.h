@@ -1029,6 +1029,63 @@ int lrf_align_pairs(const LrfAlignFrame* fr, const float* a, const float* b, con
                     int64_t* words /* device [24] */, void* stream);
 int lrf_align_plane(const LrfAlignPlane* p, int64_t* words /* device [48] */, void* stream);
 
+/* A point cloud indexed for neighbour queries -- the point-cloud counterpart of the mesh index above -- and a cloud reduced to
+ * one point per cell of a voxel grid (csrc/lrf_cloud.inl states the pair arithmetic, the grid, the walk and its stopping rule,
+ * the k-best slots and the voxel rule).  A cloud point with a coordinate that is not finite is skipped and counted and is never
+ * returned.  Every call leaves the same bytes on every run.
+ * lrf_cloud_index_bounds: out (device int64 [8]) = nonfinite_points, used points, 0, 0, then six int32 -- the order-preserving
+ * keys (lrf_mesh_smooth_bounds') of the used points' per-axis minima and maxima --, 0.  Two launches.
+ * The index: grid, lrf_cloud_index_workspace_bytes(cells) bytes (8 bytes, then a start and an end per cell; 0 when cells is
+ * outside [1, 2^31)), and records, entries x 16 bytes: x, y, z and the point's index as bits, in cell order; entries = the used
+ * points of the bounds pass.  lo, cell, dims: the grid, as in LrfMeshIndex.  lrf_cloud_index_build: five launches (zero, count,
+ * scan, copy, fill); a used point beyond `entries` records is not written.
+ * lrf_cloud_closest: points [N,3] -> distance [N] ((float)sqrt of the fp64 squared distance; +inf without a point within
+ * max_distance; NaN for a query that is not finite), index int32 [N] (the smallest index among equal distances; -1), closest
+ * [N,3] (nullable; the winner's own words; NaN without one).  One launch, no atomics.  The result does not depend on cell.
+ * lrf_cloud_knn: distance, index [N,k], ascending in (squared distance, index); a slot without a neighbour within max_distance
+ * holds +inf, -1; a query that is not finite NaN, -1.  self_first = -1, or query i skips the cloud point self_first + i.  One launch.
+ * lrf_cloud_radius_count: count int32 [N] = the used points with squared distance <= radius radius in fp64 (-1 for a query that
+ * is not finite); self_first as above.  One launch.
+ * lrf_cloud_voxel_bounds: a point's integer cell is floor((x - origin) / cell) per axis (lrf_mesh_simplify's); out (device int64
+ * [8]) = bad points (not finite, or a cell index of magnitude >= 2^30), used points, 0, 0, then six int32: the per-axis minimum
+ * and maximum cell index of the used points, 0.  Two launches.
+ * lrf_cloud_voxel: lo, dims = that box.  points_out [M,3], rgb8_out [M,3] (null iff rgb8 is), count_out int32 [M]: the first
+ * counts[2] rows are written, one per occupied cell in cell order (x fastest): the mean position and rounded mean colour by
+ * lrf_mesh_simplify's integer arithmetic, and the number of points.  cluster_of int32 [M]: each point's row, -1 for a bad point
+ * or one outside the box.  counts (device int64 [8]): word 2 = occupied cells, the others 0.  workspace:
+ * lrf_cloud_voxel_workspace_bytes(M, cells) bytes (0 for a refused shape).  Six launches.
+ * Refused before any launch: null or misaligned pointers (float and int32 arrays 4 bytes; out, counts, workspace and grid 8;
+ * records 16), M outside [1, 2^31), entries outside [0, M], N outside [1, 2^31), k outside [1, 8], radius negative, NaN or
+ * infinite, max_distance negative or NaN, self_first < -1 or self_first + N > M, cell, lo or origin not finite, cell <= 0,
+ * dims < 1 or 2^31 cells or more, a voxel box outside (-2^30, 2^30), rgb8 without rgb8_out or the reverse. */
+#define LRF_CLOUD_MAX_K 8
+typedef struct LrfCloudIndex {
+  const float* points; void* grid; void* records;
+  int64_t M, entries;
+  double lo[3]; double cell;
+  int32_t dims[3]; int32_t reserved;
+} LrfCloudIndex;
+typedef struct LrfCloudVoxel {
+  const float* points; const uint8_t* rgb8 /* nullable */;
+  int64_t M;
+  double origin[3]; double cell;
+  int32_t lo[3]; int32_t dims[3];
+} LrfCloudVoxel;
+int lrf_cloud_index_bounds(const float* points, int64_t M, int64_t* out /* device [8] */, void* stream);
+size_t lrf_cloud_index_workspace_bytes(int64_t cells);
+int lrf_cloud_index_build(const LrfCloudIndex* a, void* stream);
+int lrf_cloud_closest(const LrfCloudIndex* a, const float* points, int64_t N, double max_distance, float* distance, int32_t* index,
+                      float* closest /* nullable */, void* stream);
+int lrf_cloud_knn(const LrfCloudIndex* a, const float* points, int64_t N, int32_t k, double max_distance, int64_t self_first,
+                  float* distance /* [N,k] */, int32_t* index /* [N,k] */, void* stream);
+int lrf_cloud_radius_count(const LrfCloudIndex* a, const float* points, int64_t N, double radius, int64_t self_first,
+                           int32_t* count, void* stream);
+int lrf_cloud_voxel_bounds(const float* points, int64_t M, const double* origin /* host [3] */, double cell,
+                           int64_t* out /* device [8] */, void* stream);
+size_t lrf_cloud_voxel_workspace_bytes(int64_t M, int64_t cells);
+int lrf_cloud_voxel(const LrfCloudVoxel* a, float* points_out, uint8_t* rgb8_out /* nullable */, int32_t* count_out,
+                    int32_t* cluster_of, int64_t* counts /* device [8] */, void* workspace, void* stream);
+
 /* Depth quantiles of a ray: the distance at which its accumulated weight first reaches q; q = 0.5 is the median depth, which
  * always lies on a surface the ray met (csrc/lrf_quantile.inl states the arithmetic: fp32 without contraction, one fixed
  * summation order per ray).  With C_i the inclusive prefix sum of the weights lrf_render_fwd leaves in weight_out and i* the

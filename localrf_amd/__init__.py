@@ -28,6 +28,9 @@ Public surface mirrors the reference's names:
                                     (a texture atlas baked for a mesh from rendered frames, OBJ + PNG export; no reference row)
   mesh_distance.MeshIndex / sample_surface / distance_summary / cloud_to_mesh / mesh_distance
                                     (point-to-mesh distance: surface error, Chamfer, Hausdorff and F-score; no reference row)
+  cloud.CloudIndex / voxel_downsample / nearest_spacing / remove_outliers / cloud_to_cloud / cloud_distance
+                                    (a neighbour index over a point cloud: nearest, k nearest and radius queries, voxel grid,
+                                    outlier removal, cloud-to-cloud Chamfer and F-score against a scan; no reference row)
   alignment.fit_pairs / trajectory_error / icp / align_meshes / transform_points / transform_mesh
                                     (similarity registration of trajectories, clouds and meshes: closed-form fit from exact
                                     integer moments, point-to-plane ICP, trajectory error after alignment; no reference row)
@@ -51,7 +54,8 @@ from . import mesh  # noqa: F401
 from . import mesh_raster  # noqa: F401
 from . import mesh_texture  # noqa: F401
 from . import mesh_distance  # noqa: F401
+from . import cloud  # noqa: F401
 from . import alignment  # noqa: F401
 from .frames import DeviceFrames  # noqa: F401
 
-__all__ = ["TensorVMSplit", "AlphaGridMask", "MLPRender_Fea_late_view", "LocalTensorfs", "rays", "losses", "metrics", "diagnostics", "novel_views", "pointcloud", "normals", "depth_quantiles", "mesh", "mesh_raster", "mesh_texture", "mesh_distance", "alignment", "NativeError", "FusedAdam", "DeviceFrames"]
+__all__ = ["TensorVMSplit", "AlphaGridMask", "MLPRender_Fea_late_view", "LocalTensorfs", "rays", "losses", "metrics", "diagnostics", "novel_views", "pointcloud", "normals", "depth_quantiles", "mesh", "mesh_raster", "mesh_texture", "mesh_distance", "cloud", "alignment", "NativeError", "FusedAdam", "DeviceFrames"]

@@ -182,6 +182,19 @@ class LrfMeshIndex(C.Structure):
                 ("lo", C.c_double * 3), ("cell", C.c_double), ("dims", C.c_int32 * 3), ("reserved", C.c_int32)]
 
 
+LRF_CLOUD_MAX_K = 8
+
+
+class LrfCloudIndex(C.Structure):
+    _fields_ = [("points", _f), ("grid", C.c_void_p), ("records", C.c_void_p), ("M", C.c_int64), ("entries", C.c_int64),
+                ("lo", C.c_double * 3), ("cell", C.c_double), ("dims", C.c_int32 * 3), ("reserved", C.c_int32)]
+
+
+class LrfCloudVoxel(C.Structure):
+    _fields_ = [("points", _f), ("rgb8", C.c_void_p), ("M", C.c_int64), ("origin", C.c_double * 3), ("cell", C.c_double),
+                ("lo", C.c_int32 * 3), ("dims", C.c_int32 * 3)]
+
+
 class LrfAlignFrame(C.Structure):
     _fields_ = [("c", C.c_double * 3), ("h", C.c_double)]
 
@@ -365,6 +378,15 @@ SYMBOLS = {
     "lrf_align_transform": (C.c_int, [C.POINTER(C.c_double), _f, C.c_int64, _f, C.c_void_p]),
     "lrf_align_pairs": (C.c_int, [C.POINTER(LrfAlignFrame), _f, _f, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "lrf_align_plane": (C.c_int, [C.POINTER(LrfAlignPlane), C.c_void_p, C.c_void_p]),
+    "lrf_cloud_index_bounds": (C.c_int, [_f, C.c_int64, C.c_void_p, C.c_void_p]),
+    "lrf_cloud_index_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "lrf_cloud_index_build": (C.c_int, [C.POINTER(LrfCloudIndex), C.c_void_p]),
+    "lrf_cloud_closest": (C.c_int, [C.POINTER(LrfCloudIndex), _f, C.c_int64, C.c_double, _f, C.c_void_p, _f, C.c_void_p]),
+    "lrf_cloud_knn": (C.c_int, [C.POINTER(LrfCloudIndex), _f, C.c_int64, C.c_int32, C.c_double, C.c_int64, _f, C.c_void_p, C.c_void_p]),
+    "lrf_cloud_radius_count": (C.c_int, [C.POINTER(LrfCloudIndex), _f, C.c_int64, C.c_double, C.c_int64, C.c_void_p, C.c_void_p]),
+    "lrf_cloud_voxel_bounds": (C.c_int, [_f, C.c_int64, C.POINTER(C.c_double), C.c_double, C.c_void_p, C.c_void_p]),
+    "lrf_cloud_voxel_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
+    "lrf_cloud_voxel": (C.c_int, [C.POINTER(LrfCloudVoxel), _f, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "lrf_mesh_texture_state_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
     "lrf_mesh_texture_bake": (C.c_int, [C.POINTER(LrfMeshTexture), _f, C.c_void_p]),
     "lrf_mesh_texture_resolve": (C.c_int, [C.POINTER(LrfMeshTexture), _f, C.POINTER(C.c_uint8), C.c_void_p, C.c_void_p, C.c_void_p,

@@ -9,7 +9,8 @@ the two have been registered: a similarity from the trajectories (fit_pairs, tra
   transform_mesh(mesh, T)                        a mesh dict moved: vertices by T, normals by its rotation
   fit_pairs(a, b, keep, scale)                   the least-squares similarity of corresponding pairs, from exact integer moments
   trajectory_error(poses_est, poses_gt, scale)   absolute trajectory error after similarity alignment
-  icp(points, mesh_or_index, ...)                point-to-plane (or point-to-point) ICP against a mesh
+  icp(points, mesh_or_index, ...)                point-to-plane (or point-to-point) ICP against a mesh, or point-to-point
+                                                 ICP against a cloud (a cloud.CloudIndex)
   align_meshes(a, b, spacing, ...)               sample_surface + icp + transform_mesh
 
 A transform is a numpy float64 [4,4] matrix T whose upper-left block is s R with det R = +1, applied as p' = s R p + t.  The
@@ -25,6 +26,7 @@ import torch
 from . import _native as N
 from ._native import NativeError  # noqa: F401
 from ._checks import check_choice, check_flag, check_int, check_interval, check_mesh, check_positive, mesh_on_device
+from .cloud import CloudIndex
 from .mesh_distance import MeshIndex, _as_index, _check_max_distance, _check_points, sample_surface
 
 PAIRS_PER_CALL = 1 << 20                       # lrf_align_pairs and lrf_align_plane: no word can overflow below this
@@ -411,11 +413,22 @@ def icp(points, mesh_or_index, init=None, scale=True, metric="plane", iterations
     exceeds 1e12 (a plane as the target, a direction the cloud can slide along); else reason="iterations".
     Returns T, iterations (steps applied), converged, reason, rms and count (of the last accumulation: the point-to-plane or
     point-to-point residual before its step, in world units) and history: per iteration rms, count, step and the points left
-    out.  One read-back before the loop when max_distance is infinite, one per iteration."""
+    out.  One read-back before the loop when max_distance is infinite, one per iteration.
+
+    The target may also be a cloud.CloudIndex -- a laser scan, another run's scene_point_cloud -- with metric="point": the loop
+    is the same and the closest point is the nearest point of the cloud.  A cloud has no planes: metric="plane" with a
+    CloudIndex raises ValueError."""
     def checks():
         _check_points(points)
         _check_icp_options(init, scale, metric, iterations, max_distance, tol)
-    index = _as_index(mesh_or_index, 1 << 30, checks)
+    if isinstance(mesh_or_index, CloudIndex):
+        checks()
+        if metric == "plane":
+            raise ValueError('a cloud has no planes: metric="plane" needs a mesh or a MeshIndex as the target; '
+                             'pass metric="point" to align against a CloudIndex')
+        index = mesh_or_index
+    else:
+        index = _as_index(mesh_or_index, 1 << 30, checks)
     T = np.eye(4) if init is None else _matrix(init)
     max_distance, tol = _check_max_distance(max_distance), float(tol)
     N.require_gpu(points, "points", "the alignment")

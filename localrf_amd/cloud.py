@@ -1,0 +1,392 @@
+"""Point clouds on the GPU: a neighbour index over a cloud -- the point-cloud counterpart of mesh_distance.MeshIndex -- and what
+follows from it: the nearest point, the k nearest, the points within a radius, a cloud's own spacing, outlier removal, a voxel
+grid, and the cloud-to-cloud figures of the reconstruction benchmarks, whose references are laser scans
+(csrc/lrf_cloud.inl through lrf_cloud_index_*, lrf_cloud_closest, lrf_cloud_knn, lrf_cloud_radius_count and lrf_cloud_voxel*;
+the summary is mesh_distance's lrf_distance_summary).
+
+  CloudIndex(points, cell=None)                    a uniform grid over the points, built once
+  CloudIndex.closest(points, max_distance)         distance, index and the nearest point per query point
+  CloudIndex.knn(points, k, max_distance)          the k nearest, ascending, k <= 8
+  CloudIndex.radius_count(points, radius)          the cloud's points within radius of each query point
+  voxel_downsample(points, cell, origin, rgb8)     one point per occupied cell: mean position, mean colour, count
+  nearest_spacing(points_or_index)                 mean and exact median nearest-neighbour distance: the unit of every threshold
+  remove_outliers(points, radius, min_neighbours)  the points with enough neighbours, in input order
+  cloud_to_cloud(points, cloud_or_index, ...)      closest + distance_summary: cloud_to_mesh's twin
+  cloud_distance(a, b, thresholds, voxel=...)      both directions: Chamfer, Hausdorff, precision / recall / F-score
+
+The benchmarks' protocol: voxel_downsample both clouds (cloud_distance's voxel), align them (alignment.icp takes a CloudIndex
+as its target, metric="point"), nearest-neighbour distances in both directions, precision, recall and F-score at a threshold.
+A cloud is [M,3] fp32 on the device.  Exact minima with an index tie-break, integer counts and sums: the same bytes and the same
+integers on every run, whatever the cell.  Every function checks its arguments on the host before its first launch.  CPU
+tensors raise NativeError: there is no torch fallback.
+"""
+import ctypes as C
+import math
+
+import torch
+
+from . import _native as N
+from . import diagnostics
+from ._native import NativeError  # noqa: F401
+from ._checks import INT32 as _INT32
+from ._checks import check_bytes, check_flag, check_int, check_origin, check_positive, float_of_key
+from .mesh_distance import (_check_max_distance, _check_points, _check_thresholds, _check_unit, _ratio, _summary, _summary_words,
+                            distance_summary, grid_dims)
+
+MAX_K = N.LRF_CLOUD_MAX_K
+_POINTS_PER_CALL = 1 << 30
+
+
+def default_point_cell(lo, hi, used, max_bytes=1 << 30):
+    """The cell edge CloudIndex takes for cell=None, a function of the box (lo, hi: three floats each), the number of used
+    points and max_bytes alone: the longest box edge times 2 / sqrt(used) -- a surface cloud then holds about four points per
+    occupied cell -- doubled until the grid has fewer than 2^31 cells and its start and end words (8 bytes a cell) take at most
+    half of max_bytes; 1.0 for a box without extent."""
+    longest = max(h - l for l, h in zip(lo, hi))
+    if not longest > 0 or used < 1:
+        return 1.0
+    cell = longest * 2.0 / math.sqrt(used)
+    while True:
+        cells = math.prod(grid_dims(lo, hi, cell))
+        if cells <= _INT32 and (8 * cells <= max_bytes // 2 or cells == 1):
+            return cell
+        cell *= 2.0
+
+
+def _check_radius(radius):
+    try:
+        ok = not isinstance(radius, bool) and math.isfinite(float(radius)) and float(radius) >= 0
+    except (TypeError, ValueError, OverflowError):
+        ok = False
+    if not ok:
+        raise ValueError(f"radius must be a finite number >= 0, got {radius!r}")
+    return float(radius)
+
+
+def _check_colours(name, t, n, dtype, what):
+    if t is None:
+        return
+    if not torch.is_tensor(t):
+        raise TypeError(f"{name} must be a torch tensor or None")
+    if t.dtype is not dtype or tuple(t.shape) != (n, 3):
+        raise ValueError(f"{name} must be {(n, 3)} {what} or None, got {t.dtype} {tuple(t.shape)}")
+
+
+class CloudIndex:
+    """A uniform grid over the points of a cloud ([M,3] fp32 on the device), built once and held (csrc/lrf_cloud.inl states
+    every rule).  A point with a coordinate that is not finite is skipped and counted, and no query returns it; duplicates stay.
+    cell=None takes default_point_cell(box, used points, max_bytes).  One read-back: the bounds pass (the box of the used points
+    and the two counts), which fixes the number of records.  ValueError, naming the cell box and asking for a larger cell, for a
+    cell box of 2^31 cells or more or an index of more than max_bytes.
+    .info: cell, box (lo, hi), dims, points (used) and nonfinite_points as Python values; .nbytes: the index's own device memory
+    (the grid words and one 16-byte record -- x, y, z, index -- per used point, in cell order); .counts: (M,).  The index holds
+    the cloud's tensor, not a copy: a cloud changed in place needs a new index.  No result depends on the cell."""
+
+    def __init__(self, points, cell=None, max_bytes=1 << 30):
+        M = _check_points(points)
+        if cell is not None:
+            check_positive("cell", cell)
+        max_bytes = check_bytes(max_bytes)
+        if M > _INT32:
+            raise ValueError(f"points holds {M} rows; a cloud index takes M < 2^31")
+        N.require_gpu(points, "points", "the cloud index")
+        dev = points.device
+        pts = points.detach().contiguous()
+        self.points, self.device, self.counts = pts, dev, (M,)
+        self._grid = self._records = self._args = None
+        self.info = {"cell": None if cell is None else float(cell), "box": None, "dims": (0, 0, 0), "points": 0, "nonfinite_points": 0}
+        if M == 0:
+            return
+        out = torch.empty(8, dtype=torch.int64, device=dev)
+        N.launch("lrf_cloud_index_bounds", dev, pts.data_ptr(), M, out.data_ptr(), guard=True)
+        host = out.cpu()                                            # the read-back
+        counts, keys = host[:4].tolist(), host[4:7].view(torch.int32).tolist()
+        used = int(counts[1])
+        self.info.update(points=used, nonfinite_points=int(counts[0]))
+        if used == 0:
+            return
+        lo, hi = tuple(float_of_key(k) for k in keys[:3]), tuple(float_of_key(k) for k in keys[3:6])
+        cell = default_point_cell(lo, hi, used, max_bytes) if cell is None else float(cell)
+        dims = grid_dims(lo, hi, cell)
+        cells = dims[0] * dims[1] * dims[2]
+        box = f"the cell box {dims[0]} x {dims[1]} x {dims[2]} of cell {cell} over {lo} .. {hi}"
+        if cells > _INT32:
+            raise ValueError(f"{box} holds {cells} cells; an index takes fewer than 2^31: a larger cell is needed")
+        need = int(N.lib().lrf_cloud_index_workspace_bytes(cells))
+        if need == 0:
+            raise NativeError(f"lrf_cloud_index: refused shape {(cells,)}")
+        if need + 16 * used > max_bytes:
+            raise ValueError(f"{box} takes an index of {need + 16 * used} bytes; max_bytes is {max_bytes}: a larger cell is needed")
+        grid = torch.empty(need, dtype=torch.uint8, device=dev)
+        records = torch.empty(used, 4, dtype=torch.float32, device=dev)
+        a = N.LrfCloudIndex()
+        a.points, a.grid, a.records, a.M, a.entries, a.cell = pts.data_ptr(), grid.data_ptr(), records.data_ptr(), M, used, cell
+        for k in range(3):
+            a.lo[k], a.dims[k] = lo[k], dims[k]
+        N.launch("lrf_cloud_index_build", dev, C.byref(a), guard=True)
+        self._grid, self._records, self._args = grid, records, a
+        self.info.update(cell=cell, box=(lo, hi), dims=dims)
+
+    @property
+    def nbytes(self):
+        return 0 if self._grid is None else self._grid.numel() + 16 * self._records.shape[0]
+
+    def _queries(self, points, exclude_self):
+        n = _check_points(points)
+        exclude_self = check_flag("exclude_self", exclude_self)
+        if exclude_self and n != self.counts[0]:
+            raise ValueError(f"exclude_self pairs query i with cloud point i: {n} queries for a cloud of {self.counts[0]} points")
+        return n, exclude_self
+
+    def _on_device(self, points):
+        N.require_gpu(points, "points", "the cloud queries")
+        if points.device != self.device:
+            raise ValueError(f"points live on {points.device}, the index on {self.device}")
+        return points.detach().contiguous()
+
+    def closest(self, points, max_distance=math.inf, closest=False):
+        """points [N,3] fp32 on the index's device -> {"distance": [N] fp32, "index": [N] int32[, "closest": [N,3] fp32]} on the
+        device, no read-back.  distance is the distance to the nearest used point of the cloud, index that point's row (the
+        smallest among equally near points) and closest its own coordinates.  Without a point within max_distance (or without
+        any): +inf, -1, NaN.  For a query with a coordinate that is not finite: NaN, -1, NaN.  The result is a function of the
+        cloud, the query and max_distance alone: it does not depend on cell, on how the queries are batched or on the stream.
+        A query at distance D walks about (2 D / cell)^3 cells, empty or not: give clouds with far outliers a max_distance."""
+        n = _check_points(points)
+        max_distance = _check_max_distance(max_distance)
+        closest = check_flag("closest", closest)
+        pts, dev = self._on_device(points), self.device
+        out = {"distance": torch.empty(n, dtype=torch.float32, device=dev), "index": torch.empty(n, dtype=torch.int32, device=dev)}
+        if closest:
+            out["closest"] = torch.empty(n, 3, dtype=torch.float32, device=dev)
+        if self._grid is None:                                      # no used point: nothing is near
+            finite = torch.isfinite(pts).all(1)
+            out["distance"].copy_(torch.where(finite, math.inf, math.nan))
+            out["index"].fill_(-1)
+            if closest:
+                out["closest"].fill_(math.nan)
+            return out
+        for i0 in range(0, n, _POINTS_PER_CALL):
+            i1 = min(n, i0 + _POINTS_PER_CALL)
+            N.launch("lrf_cloud_closest", dev, C.byref(self._args), pts[i0:].data_ptr(), i1 - i0, max_distance,
+                     out["distance"][i0:].data_ptr(), out["index"][i0:].data_ptr(),
+                     out["closest"][i0:].data_ptr() if closest else None, guard=True)
+        return out
+
+    def knn(self, points, k, max_distance=math.inf, exclude_self=False):
+        """The k nearest used points of the cloud per query point, k in 1..8: {"distance": [N,k] fp32, "index": [N,k] int32},
+        ascending in (distance, index); slots without a neighbour within max_distance hold +inf, -1, a query that is not finite
+        NaN, -1.  exclude_self=True needs N == M and skips cloud point i for query i; a duplicate of it elsewhere still counts,
+        at distance 0.  The walk stops on the k-th best: a query whose k-th neighbour lies at distance D walks about
+        (2 D / cell)^3 cells, empty or not, so give clouds with far outliers a max_distance.  No read-back."""
+        n, exclude_self = self._queries(points, exclude_self)
+        k = check_int("k", k, 1, MAX_K)
+        max_distance = _check_max_distance(max_distance)
+        pts, dev = self._on_device(points), self.device
+        out = {"distance": torch.empty(n, k, dtype=torch.float32, device=dev), "index": torch.empty(n, k, dtype=torch.int32, device=dev)}
+        if self._grid is None:
+            finite = torch.isfinite(pts).all(1, keepdim=True)
+            out["distance"].copy_(torch.where(finite, math.inf, math.nan).expand(n, k))
+            out["index"].fill_(-1)
+            return out
+        for i0 in range(0, n, _POINTS_PER_CALL):
+            i1 = min(n, i0 + _POINTS_PER_CALL)
+            N.launch("lrf_cloud_knn", dev, C.byref(self._args), pts[i0:].data_ptr(), i1 - i0, k, max_distance, i0 if exclude_self else -1,
+                     out["distance"][i0:].data_ptr(), out["index"][i0:].data_ptr(), guard=True)
+        return out
+
+    def radius_count(self, points, radius, exclude_self=False):
+        """int32 [N] on the device: the used points of the cloud within radius of each query point, the boundary included
+        (squared distance <= radius^2 in fp64); -1 for a query that is not finite.  radius is finite and >= 0; exclude_self as in
+        knn.  A query walks about (2 radius / cell)^3 cells, empty or not.  No read-back."""
+        n, exclude_self = self._queries(points, exclude_self)
+        radius = _check_radius(radius)
+        pts, dev = self._on_device(points), self.device
+        out = torch.empty(n, dtype=torch.int32, device=dev)
+        if self._grid is None:
+            out.copy_(torch.where(torch.isfinite(pts).all(1), 0, -1))
+            return out
+        for i0 in range(0, n, _POINTS_PER_CALL):
+            i1 = min(n, i0 + _POINTS_PER_CALL)
+            N.launch("lrf_cloud_radius_count", dev, C.byref(self._args), pts[i0:].data_ptr(), i1 - i0, radius, i0 if exclude_self else -1,
+                     out[i0:].data_ptr(), guard=True)
+        return out
+
+
+def voxel_downsample(points, cell, origin=(0.0, 0.0, 0.0), rgb8=None, max_bytes=1 << 30):
+    """The cloud ([M,3] fp32, rgb8 [M,3] uint8 or None) reduced to one point per occupied cell of the grid of edge `cell`
+    anchored at `origin`: the mean position and the rounded mean colour of the cell's points, by mesh.simplify's integer
+    arithmetic (csrc/lrf_mesh_simplify.inl items 1-4).  Every occupied cell is emitted, in cell order (x fastest) -- simplify
+    emits only what a face holds, so a mesh without faces gives it nothing.  A point that is not finite or lies 2^30 cells or
+    more from origin is skipped and counted.  Returns {"points": [C,3], "rgb8": [C,3] (with rgb8), "count": int32 [C] (points per
+    cluster), "cluster_of": int32 [M] (-1 for a bad point), "counts": (C,), "info": cell, origin, box (lo, dims), points (used),
+    bad_points}.  The bytes of points, rgb8 and count do not depend on the order of the input.  Two read-backs: the bounds pass
+    (a cell box of 2^31 cells or more, or a workspace above max_bytes, raises ValueError before anything is summed), then the
+    number of clusters; the outputs are allocated at M rows and sliced."""
+    M = _check_points(points)
+    cell = check_positive("cell", cell)
+    origin = check_origin(origin)
+    _check_colours("rgb8", rgb8, M, torch.uint8, "uint8")
+    max_bytes = check_bytes(max_bytes)
+    if M > _INT32:
+        raise ValueError(f"points holds {M} rows; a voxel grid takes M < 2^31")
+    N.require_gpu(points, "points", "the voxel grid")
+    dev = points.device
+    if rgb8 is not None:
+        N.require_gpu(rgb8, "rgb8", "the voxel grid")
+        if rgb8.device != dev:
+            raise ValueError("points and rgb8 must live on the same device")
+    pts = points.detach().contiguous()
+    col = None if rgb8 is None else rgb8.contiguous()
+    info = {"cell": cell, "origin": origin, "box": {"lo": (0, 0, 0), "dims": (0, 0, 0)}, "points": 0, "bad_points": 0}
+    out = {"points": pts[:0], "count": torch.empty(0, dtype=torch.int32, device=dev),
+           "cluster_of": torch.full((M,), -1, dtype=torch.int32, device=dev), "counts": (0,), "info": info}
+    if col is not None:
+        out["rgb8"] = col[:0]
+    if M == 0:
+        return out
+    o3 = (C.c_double * 3)(*origin)
+    words = torch.empty(8, dtype=torch.int64, device=dev)
+    N.launch("lrf_cloud_voxel_bounds", dev, pts.data_ptr(), M, o3, cell, words.data_ptr(), guard=True)
+    host = words.cpu()                                              # read-back one
+    bad, used = (int(x) for x in host[:2].tolist())
+    info.update(points=used, bad_points=bad)
+    if used == 0:
+        return out
+    ends = host[4:7].view(torch.int32).tolist()
+    lo, dims = tuple(ends[:3]), tuple(h - l + 1 for l, h in zip(ends[:3], ends[3:6]))
+    cells = dims[0] * dims[1] * dims[2]
+    box = f"the cell box {dims[0]} x {dims[1]} x {dims[2]} from {lo}"
+    if cells > _INT32:
+        raise ValueError(f"{box} holds {cells} cells; a voxel grid takes fewer than 2^31: a larger cell is needed")
+    need = int(N.lib().lrf_cloud_voxel_workspace_bytes(M, cells))
+    if need == 0:
+        raise NativeError(f"lrf_cloud_voxel: refused shape {(M, cells)}")
+    if need > max_bytes:
+        raise ValueError(f"{box} takes a workspace of {need} bytes; max_bytes is {max_bytes}: a larger cell is needed")
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    po, no = torch.empty_like(pts), torch.empty(M, dtype=torch.int32, device=dev)
+    co = None if col is None else torch.empty_like(col)
+    counts = torch.empty(8, dtype=torch.int64, device=dev)
+    a = N.LrfCloudVoxel()
+    a.points, a.rgb8, a.M, a.cell = pts.data_ptr(), None if col is None else col.data_ptr(), M, cell
+    for k in range(3):
+        a.origin[k], a.lo[k], a.dims[k] = origin[k], lo[k], dims[k]
+    N.launch("lrf_cloud_voxel", dev, C.byref(a), po.data_ptr(), None if co is None else co.data_ptr(), no.data_ptr(),
+             out["cluster_of"].data_ptr(), counts.data_ptr(), ws.data_ptr(), guard=True)
+    n = int(counts[2].item())                                       # read-back two (it also orders ws's release)
+    info.update(box={"lo": lo, "dims": dims})
+    out.update(points=po[:n], count=no[:n], counts=(n,))
+    if co is not None:
+        out["rgb8"] = co[:n]
+    return out
+
+
+def _as_cloud_index(cloud_or_index, max_bytes, name="cloud_or_index"):
+    if isinstance(cloud_or_index, CloudIndex):
+        return cloud_or_index
+    if not torch.is_tensor(cloud_or_index):
+        raise TypeError(f"{name} must be a [M, 3] float32 tensor or a CloudIndex")
+    return CloudIndex(cloud_or_index, max_bytes=max_bytes)
+
+
+def nearest_spacing(points_or_index, max_bytes=1 << 30):
+    """A cloud's own spacing: the distance of every used point to its nearest other point (knn with k = 1 and exclude_self on
+    the cloud itself; a duplicate is a neighbour at distance 0).  Returns {"mean": distance_summary's mean over the finite
+    distances in units of the median, "median": diagnostics.median of them (exact, the lower median), "count": the finite
+    distances}; NaN, NaN, 0 for a cloud with fewer than two used points.  Every threshold of this module is best chosen in
+    these units."""
+    check_bytes(max_bytes)
+    index = _as_cloud_index(points_or_index, max_bytes, "points_or_index")
+    d = index.knn(index.points, 1, exclude_self=True)["distance"].reshape(-1)
+    d = d[torch.isfinite(d)]
+    if d.numel() == 0:
+        return {"mean": math.nan, "median": math.nan, "count": 0}
+    median = float(diagnostics.median(d))
+    unit = median if math.isfinite(median) and median > 0 else 1.0
+    s = distance_summary(d, (), _check_unit(unit))
+    return {"mean": s["mean"], "median": median, "count": s["finite"]}
+
+
+def remove_outliers(points, radius, min_neighbours, rgb8=None, normals=None, index=None):
+    """Floater removal: keeps point i iff at least min_neighbours other points of the cloud lie within radius of it
+    (radius_count with exclude_self; the boundary counts).  A point that is not finite goes.  Survivors stay in input order.
+    index: a CloudIndex of these very points, which is then not built again.  Returns {"points", "rgb8" and "normals" where
+    given, "keep": bool [M], "counts": (kept,)}.  One read-back: the number kept."""
+    M = _check_points(points)
+    radius = _check_radius(radius)
+    min_neighbours = check_int("min_neighbours", min_neighbours, 0, _INT32, "an integer in [0, 2^31)")
+    _check_colours("rgb8", rgb8, M, torch.uint8, "uint8")
+    _check_colours("normals", normals, M, torch.float32, "float32")
+    if index is not None:
+        if not isinstance(index, CloudIndex):
+            raise TypeError("index must be a CloudIndex or None")
+        if index.counts != (M,):
+            raise ValueError(f"index was built over {index.counts[0]} points, points holds {M}")
+    N.require_gpu(points, "points", "the outlier removal")
+    for name, t in (("rgb8", rgb8), ("normals", normals)):
+        if t is not None:
+            N.require_gpu(t, name, "the outlier removal")
+            if t.device != points.device:
+                raise ValueError(f"points and {name} must live on the same device")
+    index = CloudIndex(points) if index is None else index
+    keep = index.radius_count(points, radius, exclude_self=True) >= max(min_neighbours, 0)
+    out = {"points": points.detach()[keep], "keep": keep}
+    if rgb8 is not None:
+        out["rgb8"] = rgb8[keep]
+    if normals is not None:
+        out["normals"] = normals.detach()[keep]
+    out["counts"] = (int(out["points"].shape[0]),)
+    return out
+
+
+def cloud_to_cloud(points, cloud_or_index, thresholds=(), max_distance=math.inf, unit=None, max_bytes=1 << 30):
+    """The distances of a point cloud [N,3] fp32 to another cloud (or to a CloudIndex built from it, which is not built again):
+    CloudIndex.closest and distance_summary; mesh_distance.cloud_to_mesh's twin.  unit defaults to max_distance when that is
+    finite and > 0, else 1.0.  Returns distance_summary's dict plus "distance" and "index" on the device.  With a
+    reconstruction's cloud and a reference scan, mean is the accuracy; the other way round, the completeness."""
+    _check_points(points)
+    taus, max_distance = _check_thresholds(thresholds), _check_max_distance(max_distance)
+    if unit is not None:
+        _check_unit(unit)
+    check_bytes(max_bytes)
+    index = _as_cloud_index(cloud_or_index, max_bytes)
+    if unit is None:
+        unit = max_distance if math.isfinite(max_distance) and max_distance > 0 else 1.0
+    unit = _check_unit(unit)
+    near = index.closest(points, max_distance)
+    out = _summary(_summary_words(near["distance"], taus, unit).tolist(), taus, unit)
+    out.update(distance=near["distance"], index=near["index"])
+    return out
+
+
+def cloud_distance(a, b, thresholds=(), max_distance=math.inf, voxel=None, max_bytes=1 << 30):
+    """Two clouds compared point to point: a queried against b, and b against a.  With voxel (a cell edge) both first go through
+    voxel_downsample(cloud, voxel), the benchmarks' protocol, which takes the density of either cloud out of the figures.
+    Returns mesh_distance.mesh_distance's dict: a_to_b and b_to_a (distance_summary's dicts, unit as in cloud_to_cloud);
+    chamfer, the sum of the two means; hausdorff, the larger of the two maxima over the finite entries; per threshold precision
+    (the share of a's finite-or-beyond points within it of b), recall (b's within it of a) and fscore = 2 p r / (p + r), formed
+    on the host from the integer counts, NaN where undefined; thresholds; and samples = (points of a, points of b) that were
+    queried.  With a the reconstruction and b the reference scan these are the figures of the reconstruction benchmarks.  The
+    same integers on every run, and with voxel for every order of the points of either cloud."""
+    _check_points(a)
+    _check_points(b)
+    taus, max_distance = _check_thresholds(thresholds), _check_max_distance(max_distance)
+    if voxel is not None:
+        check_positive("voxel", voxel)
+    check_bytes(max_bytes)
+    if voxel is not None:
+        a, b = (voxel_downsample(x, voxel, max_bytes=max_bytes)["points"] for x in (a, b))
+    sides = {}
+    for name, src, dst in (("a_to_b", a, b), ("b_to_a", b, a)):
+        r = cloud_to_cloud(src, dst, taus, max_distance, None, max_bytes)
+        del r["distance"], r["index"]
+        sides[name] = r
+    ab, ba = sides["a_to_b"], sides["b_to_a"]
+    n_a, n_b = ab["finite"] + ab["beyond"], ba["finite"] + ba["beyond"]
+    maxima = [s["max"] for s in (ab, ba) if s["finite"]]
+    precision = tuple(_ratio(w, n_a) for w in ab["within"])
+    recall = tuple(_ratio(w, n_b) for w in ba["within"])
+    fscore = tuple(2 * p * r / (p + r) if p + r > 0 else math.nan for p, r in zip(precision, recall))
+    return {"a_to_b": ab, "b_to_a": ba, "chamfer": ab["mean"] + ba["mean"], "hausdorff": max(maxima) if maxima else math.nan,
+            "precision": precision, "recall": recall, "fscore": fscore, "thresholds": tuple(taus),
+            "samples": (ab["finite"] + ab["beyond"] + ab["nan"], ba["finite"] + ba["beyond"] + ba["nan"])}

@@ -1317,6 +1317,7 @@ static hipError_t lds_opt_in() {
 #include "lrf_mesh_texture.inl"
 #include "lrf_mesh_distance.inl"
 #include "lrf_align.inl"
+#include "lrf_cloud.inl"
 #include "lrf_tsdf_blocks.inl"
 #include "lrf_reg.inl"
 #include "lrf_mask.inl"
