@@ -1013,9 +1013,14 @@ int lrf_distance_summary(const float* distance, int64_t N, const float* threshol
  * gated (distance > gate), degenerate (a face without area), out_of_range (a coordinate of (p - c) / u or (q - c) / u beyond
  * [-1, 1]), 0, sum llrint(r r 2^36), sum llrint(J_k r 2^36) [7], sum llrint(J_k J_l 2^36) for k <= l [28], 0 .. 0, with r the
  * point-to-plane residual and J = (pt x n, n, pt . n) in units of u.  Two launches (one with N = 0).
+ * lrf_align_plane_cloud: the same step against a cloud: closest, index int32 [N] and distance as lrf_cloud_closest wrote them
+ * for points against the cloud, normals [M,3] fp32 one per cloud point (lrf_cloud_normals'; any length > 0 -- the kernel
+ * normalises in fp64).  The plane of a point is the one through its closest point with the normal stored for index.  The same
+ * 48 words in the same layout; unmatched: an index outside [0, M) or a distance not finite; degenerate: a normal with a word
+ * that is not finite, or of length 0.  Two launches (one with N = 0).
  * Refused before any launch: null or misaligned pointers (float, int32 arrays 4 bytes; T and words 8), N outside [0, 2^20]
  * (transform: [0, 2^31)), h or u not a positive power of two, c or T not finite, gate < 0 or NaN, Nv outside [1, 2^31), Nf
- * outside [1, 2^31). */
+ * outside [1, 2^31), M outside [1, 2^31). */
 typedef struct LrfAlignFrame { double c[3]; double h; } LrfAlignFrame;
 typedef struct LrfAlignPlane {
   const float* vertices; const int32_t* faces; const float* points; const float* closest; const int32_t* face;
@@ -1028,6 +1033,13 @@ int lrf_align_transform(const double* T /* host [12] */, const float* points, in
 int lrf_align_pairs(const LrfAlignFrame* fr, const float* a, const float* b, const uint8_t* keep /* nullable */, int64_t N,
                     int64_t* words /* device [24] */, void* stream);
 int lrf_align_plane(const LrfAlignPlane* p, int64_t* words /* device [48] */, void* stream);
+typedef struct LrfAlignPlaneCloud {
+  const float* points; const float* closest; const int32_t* index; const float* distance; const float* normals;
+  int64_t N, M;
+  double c[3]; double u;
+  float gate; int32_t reserved;
+} LrfAlignPlaneCloud;
+int lrf_align_plane_cloud(const LrfAlignPlaneCloud* p, int64_t* words /* device [48] */, void* stream);
 
 /* A point cloud indexed for neighbour queries -- the point-cloud counterpart of the mesh index above -- and a cloud reduced to
  * one point per cell of a voxel grid (csrc/lrf_cloud.inl states the pair arithmetic, the grid, the walk and its stopping rule,
@@ -1046,6 +1058,18 @@ int lrf_align_plane(const LrfAlignPlane* p, int64_t* words /* device [48] */, vo
  * holds +inf, -1; a query that is not finite NaN, -1.  self_first = -1, or query i skips the cloud point self_first + i.  One launch.
  * lrf_cloud_radius_count: count int32 [N] = the used points with squared distance <= radius radius in fp64 (-1 for a query that
  * is not finite); self_first as above.  One launch.
+ * lrf_cloud_normals: per query point the normal of the cloud around it: the eigenvector to the smallest eigenvalue of the
+ * covariance of the used points within radius (squared distance <= radius radius, the boundary and the query's own twin
+ * included), from integer sums on a lattice of step h -- the host passes the smallest power of two with radius / h <= 2^15 --
+ * and a fixed number of cyclic Jacobi sweeps in fp64 (csrc/lrf_cloud.inl item 9 writes out every operation).  normal [N,3],
+ * eigenvalues [N,3] (ascending, in squared world units) and count int32 [N] (the neighbours).  viewpoints (nullable): one
+ * viewpoint (stride 0) or one per query (stride 3); the normal is turned towards it; without one, or where it lies in the
+ * normal's plane, the component of largest magnitude is made positive.  Fewer than min_neighbours neighbours, or coincident
+ * ones: normal (0, 0, 0), the true count.  A query that is not finite: NaN, NaN, -1.  points == NULL: the queries are the
+ * cloud's own points, N == M, walked in the order of the index's records and written to the rows of the points (two launches:
+ * the rows of points that are not finite, then the records); the same bytes as points = the cloud's.  Otherwise one launch;
+ * none with N = 0.  Refused: N outside [0, 2^31), radius not finite or <= 0, h not that power of two, min_neighbours < 3, a
+ * stride other than 0 or 3, points == NULL with N != M.
  * lrf_cloud_voxel_bounds: a point's integer cell is floor((x - origin) / cell) per axis (lrf_mesh_simplify's); out (device int64
  * [8]) = bad points (not finite, or a cell index of magnitude >= 2^30), used points, 0, 0, then six int32: the per-axis minimum
  * and maximum cell index of the used points, 0.  Two launches.
@@ -1080,6 +1104,10 @@ int lrf_cloud_knn(const LrfCloudIndex* a, const float* points, int64_t N, int32_
                   float* distance /* [N,k] */, int32_t* index /* [N,k] */, void* stream);
 int lrf_cloud_radius_count(const LrfCloudIndex* a, const float* points, int64_t N, double radius, int64_t self_first,
                            int32_t* count, void* stream);
+int lrf_cloud_normals(const LrfCloudIndex* a, const float* points /* null: the cloud's own, record order */, int64_t N, double radius,
+                      double h, int32_t min_neighbours, const float* viewpoints /* nullable */,
+                      int64_t viewpoint_stride /* 0: one for all, 3: per query */, float* normal, float* eigenvalues, int32_t* count,
+                      void* stream);
 int lrf_cloud_voxel_bounds(const float* points, int64_t M, const double* origin /* host [3] */, double cell,
                            int64_t* out /* device [8] */, void* stream);
 size_t lrf_cloud_voxel_workspace_bytes(int64_t M, int64_t cells);

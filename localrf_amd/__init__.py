@@ -31,6 +31,9 @@ Public surface mirrors the reference's names:
   cloud.CloudIndex / voxel_downsample / nearest_spacing / remove_outliers / cloud_to_cloud / cloud_distance
                                     (a neighbour index over a point cloud: nearest, k nearest and radius queries, voxel grid,
                                     outlier removal, cloud-to-cloud Chamfer and F-score against a scan; no reference row)
+  cloud.estimate_normals / CloudIndex.normals
+                                    (normals, eigenvalues and surface variation of a bare point cloud by PCA over radius
+                                    neighbourhoods; point-to-plane alignment.icp against a scan takes them; no reference row)
   alignment.fit_pairs / trajectory_error / icp / align_meshes / transform_points / transform_mesh
                                     (similarity registration of trajectories, clouds and meshes: closed-form fit from exact
                                     integer moments, point-to-plane ICP, trajectory error after alignment; no reference row)

@@ -205,6 +205,12 @@ class LrfAlignPlane(C.Structure):
                 ("gate", C.c_float), ("reserved", C.c_int32)]
 
 
+class LrfAlignPlaneCloud(C.Structure):
+    _fields_ = [("points", _f), ("closest", _f), ("index", C.c_void_p), ("distance", _f), ("normals", _f),
+                ("N", C.c_int64), ("M", C.c_int64), ("c", C.c_double * 3), ("u", C.c_double),
+                ("gate", C.c_float), ("reserved", C.c_int32)]
+
+
 class LrfMeshTexture(C.Structure):
     _fields_ = [("vertices", _f), ("rgb8", C.c_void_p), ("faces", C.c_void_p), ("frames", C.c_void_p), ("mesh_depth", _f),
                 ("cam2world", _f), ("focal", _f), ("center", _f), ("Nv", C.c_int64), ("Nf", C.c_int64),
@@ -378,12 +384,15 @@ SYMBOLS = {
     "lrf_align_transform": (C.c_int, [C.POINTER(C.c_double), _f, C.c_int64, _f, C.c_void_p]),
     "lrf_align_pairs": (C.c_int, [C.POINTER(LrfAlignFrame), _f, _f, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "lrf_align_plane": (C.c_int, [C.POINTER(LrfAlignPlane), C.c_void_p, C.c_void_p]),
+    "lrf_align_plane_cloud": (C.c_int, [C.POINTER(LrfAlignPlaneCloud), C.c_void_p, C.c_void_p]),
     "lrf_cloud_index_bounds": (C.c_int, [_f, C.c_int64, C.c_void_p, C.c_void_p]),
     "lrf_cloud_index_workspace_bytes": (C.c_size_t, [C.c_int64]),
     "lrf_cloud_index_build": (C.c_int, [C.POINTER(LrfCloudIndex), C.c_void_p]),
     "lrf_cloud_closest": (C.c_int, [C.POINTER(LrfCloudIndex), _f, C.c_int64, C.c_double, _f, C.c_void_p, _f, C.c_void_p]),
     "lrf_cloud_knn": (C.c_int, [C.POINTER(LrfCloudIndex), _f, C.c_int64, C.c_int32, C.c_double, C.c_int64, _f, C.c_void_p, C.c_void_p]),
     "lrf_cloud_radius_count": (C.c_int, [C.POINTER(LrfCloudIndex), _f, C.c_int64, C.c_double, C.c_int64, C.c_void_p, C.c_void_p]),
+    "lrf_cloud_normals": (C.c_int, [C.POINTER(LrfCloudIndex), _f, C.c_int64, C.c_double, C.c_double, C.c_int32, _f, C.c_int64, _f, _f,
+                                    C.c_void_p, C.c_void_p]),
     "lrf_cloud_voxel_bounds": (C.c_int, [_f, C.c_int64, C.POINTER(C.c_double), C.c_double, C.c_void_p, C.c_void_p]),
     "lrf_cloud_voxel_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
     "lrf_cloud_voxel": (C.c_int, [C.POINTER(LrfCloudVoxel), _f, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -1,5 +1,6 @@
 """Registration on the GPU: the similarity that brings a point cloud, a trajectory or a mesh from its own gauge into another's
-(csrc/lrf_align.inl through lrf_align_transform, lrf_align_pairs and lrf_align_plane, over mesh_distance.MeshIndex.closest).
+(csrc/lrf_align.inl through lrf_align_transform, lrf_align_pairs, lrf_align_plane and lrf_align_plane_cloud, over
+mesh_distance.MeshIndex.closest and cloud.CloudIndex.closest).
 A localrf scene lives in a gauge of its own -- poses are self-calibrated; origin, orientation and scale are arbitrary -- so
 mesh_distance's figures against a reference scan, another pipeline's mesh or a second training run mean something only after
 the two have been registered: a similarity from the trajectories (fit_pairs, trajectory_error), then ICP (icp, align_meshes).
@@ -9,8 +10,8 @@ the two have been registered: a similarity from the trajectories (fit_pairs, tra
   transform_mesh(mesh, T)                        a mesh dict moved: vertices by T, normals by its rotation
   fit_pairs(a, b, keep, scale)                   the least-squares similarity of corresponding pairs, from exact integer moments
   trajectory_error(poses_est, poses_gt, scale)   absolute trajectory error after similarity alignment
-  icp(points, mesh_or_index, ...)                point-to-plane (or point-to-point) ICP against a mesh, or point-to-point
-                                                 ICP against a cloud (a cloud.CloudIndex)
+  icp(points, mesh_or_index, ...)                point-to-plane (or point-to-point) ICP against a mesh, or against a cloud (a
+                                                 cloud.CloudIndex; point-to-plane with the cloud's normals as target_normals)
   align_meshes(a, b, spacing, ...)               sample_surface + icp + transform_mesh
 
 A transform is a numpy float64 [4,4] matrix T whose upper-left block is s R with det R = +1, applied as p' = s R p + t.  The
@@ -273,6 +274,23 @@ def _plane_words(index, pts, near, c, u, gate):
     return words
 
 
+def _plane_cloud_words(index, normals, pts, near, c, u, gate):
+    """_plane_words against a CloudIndex: the plane of a point is the one through its closest cloud point with that point's normal."""
+    n = pts.shape[0]
+    p = N.LrfAlignPlaneCloud()
+    p.normals, p.M = normals.data_ptr(), index.counts[0]
+    p.u, p.gate = u, gate
+    for k in range(3):
+        p.c[k] = c[k]
+    words = torch.empty(max(1, -(-n // PAIRS_PER_CALL)), 48, dtype=torch.int64, device=pts.device)
+    for j, i0 in enumerate(range(0, max(n, 1), PAIRS_PER_CALL)):
+        p.N = min(n, i0 + PAIRS_PER_CALL) - i0
+        p.points, p.closest = pts[i0:].data_ptr(), near["closest"][i0:].data_ptr()
+        p.index, p.distance = near["index"][i0:].data_ptr(), near["distance"][i0:].data_ptr()
+        N.launch("lrf_align_plane_cloud", pts.device, C.byref(p), words[j].data_ptr(), guard=True)
+    return words
+
+
 def _add_words(host):
     """int64 [chunks, W] read back -> W Python integers: exact for any number of chunks."""
     return [sum(col) for col in zip(*host.tolist())]
@@ -354,10 +372,11 @@ def _check_icp_options(init=None, scale=True, metric="plane", iterations=20, max
     check_interval("tol", tol, 0.0, 1.0, "lie in [0, 1]")
 
 
-def _plane_iteration(index, cur, near, c, u, gate, scale):
+def _plane_iteration(index, cur, near, c, u, gate, scale, normals=None):
     """One accumulation and solve of metric="plane" -> (rms, count, the points left out, the step's transform or None, its size,
-    the next frame centre).  One read-back: the words and the fp64 sum of the closest points in one tensor."""
-    words = _plane_words(index, cur, near, c, u, gate)
+    the next frame centre).  normals: the target_normals of a CloudIndex.  One read-back: the words and the fp64 sum of the
+    closest points in one tensor."""
+    words = _plane_words(index, cur, near, c, u, gate) if normals is None else _plane_cloud_words(index, normals, cur, near, c, u, gate)
     q = near["closest"].double()
     qsum = torch.where(torch.isfinite(q), q, 0.0).sum(0)
     host = torch.cat([words.reshape(-1), qsum.view(torch.int64)]).cpu()                         # the read-back
@@ -390,7 +409,23 @@ def _point_iteration(cur, near, c0, h, u, max_distance, scale):
     return rms, w[0], left, step_T, step
 
 
-def icp(points, mesh_or_index, init=None, scale=True, metric="plane", iterations=20, max_distance=math.inf, tol=1e-7):
+def _check_target_normals(target_normals, target, metric):
+    """target_normals (not None) against icp's target and metric: host checks only."""
+    if not isinstance(target, CloudIndex):
+        raise ValueError("target_normals go with a CloudIndex as the target: a mesh's planes are its faces")
+    if metric != "plane":
+        raise ValueError('target_normals are the planes of metric="plane"; metric="point" takes none')
+    if not torch.is_tensor(target_normals):
+        raise ValueError("target_normals must be a torch tensor or None")
+    m = target.counts[0]
+    if target_normals.dtype is not torch.float32 or tuple(target_normals.shape) != (m, 3):
+        raise ValueError(f"target_normals must be {(m, 3)} float32, one row per point of the CloudIndex, got {target_normals.dtype} "
+                         f"{tuple(target_normals.shape)}")
+    if target_normals.device != target.device:
+        raise ValueError(f"target_normals live on {target_normals.device}, the index on {target.device}")
+
+
+def icp(points, mesh_or_index, init=None, scale=True, metric="plane", iterations=20, max_distance=math.inf, tol=1e-7, target_normals=None):
     """Iterative closest point of a cloud ([N,3] fp32 on the device) against a mesh (or a MeshIndex built from it, which is not
     built again): the similarity T (scale=False: the rigid motion), starting from init, that brings the cloud onto the surface.
 
@@ -415,20 +450,36 @@ def icp(points, mesh_or_index, init=None, scale=True, metric="plane", iterations
     point-to-point residual before its step, in world units) and history: per iteration rms, count, step and the points left
     out.  One read-back before the loop when max_distance is infinite, one per iteration.
 
-    The target may also be a cloud.CloudIndex -- a laser scan, another run's scene_point_cloud -- with metric="point": the loop
-    is the same and the closest point is the nearest point of the cloud.  A cloud has no planes: metric="plane" with a
-    CloudIndex raises ValueError."""
+    The target may also be a cloud.CloudIndex -- a laser scan, another run's scene_point_cloud: the loop is the same and the
+    closest point is the nearest point of the cloud.  A cloud has no planes of its own: metric="plane" with a CloudIndex needs
+    target_normals ([M,3] fp32 on the index's device, one row per point of the cloud; csrc/lrf_align.inl item 4), the plane of a
+    point then being the one through its nearest cloud point with that point's normal; a point whose nearest cloud point has the
+    normal (0, 0, 0) or one that is not finite is left out and counted as degenerate.  Without them it raises ValueError, and
+    metric="point" needs none -- but when the points are not the scan's own sample, the nearest sample lies up to half a spacing
+    off along the surface and point-to-point does not get below that.  The recipe for a scan:
+
+        scan = cloud.CloudIndex(scan_points)
+        normals = cloud.estimate_normals(scan, 3 * cloud.nearest_spacing(scan)["median"])["normals"]
+        T = alignment.icp(points, scan, target_normals=normals, scale=False)["T"]
+
+    target_normals with a mesh as the target, with metric="point", or of another shape, dtype or device raise ValueError."""
     def checks():
         _check_points(points)
         _check_icp_options(init, scale, metric, iterations, max_distance, tol)
     if isinstance(mesh_or_index, CloudIndex):
         checks()
-        if metric == "plane":
+        if target_normals is not None:
+            _check_target_normals(target_normals, mesh_or_index, metric)
+        elif metric == "plane":
             raise ValueError('a cloud has no planes: metric="plane" needs a mesh or a MeshIndex as the target; '
                              'pass metric="point" to align against a CloudIndex')
         index = mesh_or_index
     else:
-        index = _as_index(mesh_or_index, 1 << 30, checks)
+        def mesh_checks():
+            checks()
+            if target_normals is not None:
+                _check_target_normals(target_normals, mesh_or_index, metric)
+        index = _as_index(mesh_or_index, 1 << 30, mesh_checks)
     T = np.eye(4) if init is None else _matrix(init)
     max_distance, tol = _check_max_distance(max_distance), float(tol)
     N.require_gpu(points, "points", "the alignment")
@@ -439,6 +490,7 @@ def icp(points, mesh_or_index, init=None, scale=True, metric="plane", iterations
     if n < MIN_MATCHES or index.info["box"] is None:
         return out
     pts = points.detach().contiguous()
+    normals = None if target_normals is None else target_normals.detach().contiguous()
     cur = torch.empty_like(pts)
     lo, hi = index.info["box"]
     if math.isfinite(max_distance):
@@ -457,7 +509,7 @@ def icp(points, mesh_or_index, init=None, scale=True, metric="plane", iterations
         _transform_into(pts, T, cur)
         near = index.closest(cur, max_distance, closest=True)
         if metric == "plane":
-            rms, count, left, step_T, step, c = _plane_iteration(index, cur, near, c, u, gate, scale)
+            rms, count, left, step_T, step, c = _plane_iteration(index, cur, near, c, u, gate, scale, normals)
         else:
             rms, count, left, step_T, step = _point_iteration(cur, near, c0, h, u, max_distance, scale)
         out.update(rms=rms, count=count)

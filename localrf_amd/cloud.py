@@ -1,13 +1,15 @@
 """Point clouds on the GPU: a neighbour index over a cloud -- the point-cloud counterpart of mesh_distance.MeshIndex -- and what
 follows from it: the nearest point, the k nearest, the points within a radius, a cloud's own spacing, outlier removal, a voxel
 grid, and the cloud-to-cloud figures of the reconstruction benchmarks, whose references are laser scans
-(csrc/lrf_cloud.inl through lrf_cloud_index_*, lrf_cloud_closest, lrf_cloud_knn, lrf_cloud_radius_count and lrf_cloud_voxel*;
-the summary is mesh_distance's lrf_distance_summary).
+(csrc/lrf_cloud.inl through lrf_cloud_index_*, lrf_cloud_closest, lrf_cloud_knn, lrf_cloud_radius_count, lrf_cloud_normals and
+lrf_cloud_voxel*; the summary is mesh_distance's lrf_distance_summary).
 
   CloudIndex(points, cell=None)                    a uniform grid over the points, built once
   CloudIndex.closest(points, max_distance)         distance, index and the nearest point per query point
   CloudIndex.knn(points, k, max_distance)          the k nearest, ascending, k <= 8
   CloudIndex.radius_count(points, radius)          the cloud's points within radius of each query point
+  CloudIndex.normals(points, radius, ...)          the cloud's normal, eigenvalues and neighbour count around each query point
+  estimate_normals(points_or_index, radius, ...)   a cloud's own normals and surface variation: what a bare scan lacks
   voxel_downsample(points, cell, origin, rgb8)     one point per occupied cell: mean position, mean colour, count
   nearest_spacing(points_or_index)                 mean and exact median nearest-neighbour distance: the unit of every threshold
   remove_outliers(points, radius, min_neighbours)  the points with enough neighbours, in input order
@@ -15,7 +17,7 @@ the summary is mesh_distance's lrf_distance_summary).
   cloud_distance(a, b, thresholds, voxel=...)      both directions: Chamfer, Hausdorff, precision / recall / F-score
 
 The benchmarks' protocol: voxel_downsample both clouds (cloud_distance's voxel), align them (alignment.icp takes a CloudIndex
-as its target, metric="point"), nearest-neighbour distances in both directions, precision, recall and F-score at a threshold.
+as its target: metric="point", or metric="plane" with estimate_normals' normals as target_normals), nearest-neighbour distances in both directions, precision, recall and F-score at a threshold.
 A cloud is [M,3] fp32 on the device.  Exact minima with an index tie-break, integer counts and sums: the same bytes and the same
 integers on every run, whatever the cell.  Every function checks its arguments on the host before its first launch.  CPU
 tensors raise NativeError: there is no torch fallback.
@@ -29,11 +31,12 @@ from . import _native as N
 from . import diagnostics
 from ._native import NativeError  # noqa: F401
 from ._checks import INT32 as _INT32
-from ._checks import check_bytes, check_flag, check_int, check_origin, check_positive, float_of_key
+from ._checks import check_bytes, check_choice, check_flag, check_int, check_origin, check_positive, float_of_key
 from .mesh_distance import (_check_max_distance, _check_points, _check_thresholds, _check_unit, _ratio, _summary, _summary_words,
                             distance_summary, grid_dims)
 
 MAX_K = N.LRF_CLOUD_MAX_K
+NORMAL_LATTICE = 1 << 15                       # lrf_cloud_normals: a neighbour's offset is at most this many lattice steps
 _POINTS_PER_CALL = 1 << 30
 
 
@@ -61,6 +64,30 @@ def _check_radius(radius):
     if not ok:
         raise ValueError(f"radius must be a finite number >= 0, got {radius!r}")
     return float(radius)
+
+
+def normal_lattice(radius):
+    """The lattice step of lrf_cloud_normals for a radius (finite, > 0): the smallest power of two h with radius / h <= 2^15.
+    ValueError for a radius so small that h is no longer a float64 (below 2^-1058)."""
+    m, e = math.frexp(radius)                                       # radius = m 2^e, 0.5 <= m < 1
+    h = math.ldexp(1.0, e - 16 if m == 0.5 else e - 15)
+    if not h > 0:
+        raise ValueError(f"radius must be at least 2^-1058, got {radius!r}")
+    return h
+
+
+def _check_viewpoint(viewpoint, n):
+    """None, three finite values or an [n,3] fp32 tensor -> None, a tuple of floats or the tensor."""
+    if viewpoint is None:
+        return None
+    if torch.is_tensor(viewpoint) and viewpoint.dim() == 2:
+        if viewpoint.dtype is not torch.float32 or tuple(viewpoint.shape) != (n, 3):
+            raise ValueError(f"viewpoint must be None, 3 finite values or {(n, 3)} float32, got {viewpoint.dtype} {tuple(viewpoint.shape)}")
+        return viewpoint
+    try:
+        return check_origin(viewpoint)
+    except ValueError:
+        raise ValueError(f"viewpoint must be None, 3 finite values or {(n, 3)} float32, got {viewpoint!r}") from None
 
 
 def _check_colours(name, t, n, dtype, what):
@@ -211,6 +238,55 @@ class CloudIndex:
                      out[i0:].data_ptr(), guard=True)
         return out
 
+    def normals(self, points, radius, min_neighbours=6, viewpoint=None):
+        """points [N,3] fp32 on the index's device -> {"normals": [N,3] fp32, "eigenvalues": [N,3] fp32, "count": int32 [N]} on the
+        device, no read-back: per query point the normal of the cloud around it by principal component analysis.  The
+        neighbourhood is radius_count's -- the used points within radius, the boundary and a point equal to the query included;
+        its covariance is formed from integer sums on a lattice of 2^16 steps across the radius, so the result does not depend on
+        cell, on the order of the cloud's points, on how the queries are batched or on the stream; its eigenvectors come from a
+        fixed number of Jacobi sweeps in fp64 (csrc/lrf_cloud.inl item 9).  normals: the unit eigenvector to the smallest
+        eigenvalue; eigenvalues: all three, ascending, in squared world units; count: the neighbours.  viewpoint: three finite
+        values, or [N,3] fp32 on the index's device, one per query: each normal is turned towards its viewpoint; with None, or
+        where the viewpoint lies exactly in the normal's plane, the component of largest magnitude is made positive.
+        Fewer than min_neighbours (>= 3) neighbours, or neighbours that all coincide: normal (0, 0, 0) and the true count.  A
+        query that is not finite: NaN, NaN, -1.  radius is finite and > 0, best given in units of nearest_spacing."""
+        return self._normals(points, _check_points(points), radius, min_neighbours, viewpoint)
+
+    def _normals(self, points, n, radius, min_neighbours, viewpoint):
+        """normals() for checked points, or with points=None for the cloud's own n = M points walked in record order."""
+        radius = check_positive("radius", radius)
+        h = normal_lattice(radius)
+        min_neighbours = check_int("min_neighbours", min_neighbours, 3, _INT32, "an integer in [3, 2^31)")
+        viewpoint = _check_viewpoint(viewpoint, n)
+        dev = self.device
+        pts = self._on_device(self.points if points is None else points)
+        view, stride = None, 0
+        if torch.is_tensor(viewpoint):
+            N.require_gpu(viewpoint, "viewpoint", "the cloud queries")
+            if viewpoint.device != dev:
+                raise ValueError(f"viewpoint lives on {viewpoint.device}, the index on {dev}")
+            view, stride = viewpoint.detach().contiguous(), 3
+        elif viewpoint is not None:
+            view = torch.tensor(viewpoint, dtype=torch.float32).to(dev)
+        out = {"normals": torch.empty(n, 3, dtype=torch.float32, device=dev), "eigenvalues": torch.empty(n, 3, dtype=torch.float32, device=dev),
+               "count": torch.empty(n, dtype=torch.int32, device=dev)}
+        if self._grid is None:                                      # no used point: no neighbour
+            finite = torch.isfinite(pts).all(1)
+            out["normals"].copy_(torch.where(finite, 0.0, math.nan)[:, None].expand(n, 3))
+            out["eigenvalues"].copy_(out["normals"])
+            out["count"].copy_(torch.where(finite, 0, -1))
+            return out
+        if points is None:
+            N.launch("lrf_cloud_normals", dev, C.byref(self._args), None, n, radius, h, min_neighbours, None if view is None else view.data_ptr(),
+                     stride, out["normals"].data_ptr(), out["eigenvalues"].data_ptr(), out["count"].data_ptr(), guard=True)
+            return out
+        for i0 in range(0, n, _POINTS_PER_CALL):
+            i1 = min(n, i0 + _POINTS_PER_CALL)
+            N.launch("lrf_cloud_normals", dev, C.byref(self._args), pts[i0:].data_ptr(), i1 - i0, radius, h, min_neighbours,
+                     None if view is None else (view[i0:] if stride else view).data_ptr(), stride, out["normals"][i0:].data_ptr(),
+                     out["eigenvalues"][i0:].data_ptr(), out["count"][i0:].data_ptr(), guard=True)
+        return out
+
 
 def voxel_downsample(points, cell, origin=(0.0, 0.0, 0.0), rgb8=None, max_bytes=1 << 30):
     """The cloud ([M,3] fp32, rgb8 [M,3] uint8 or None) reduced to one point per occupied cell of the grid of edge `cell`
@@ -305,6 +381,40 @@ def nearest_spacing(points_or_index, max_bytes=1 << 30):
     unit = median if math.isfinite(median) and median > 0 else 1.0
     s = distance_summary(d, (), _check_unit(unit))
     return {"mean": s["mean"], "median": median, "count": s["finite"]}
+
+
+NORMAL_ORDERS = ("input", "records")
+
+
+def estimate_normals(points_or_index, radius, min_neighbours=6, viewpoint=None, max_bytes=1 << 30, order="records"):
+    """A cloud's own normals: CloudIndex.normals of the cloud ([M,3] fp32 on the device, or a CloudIndex built from it, which is
+    not built again) queried at its own points -> {"normals": [M,3], "eigenvalues": [M,3], "count": int32 [M], "variation": [M]}
+    on the device, no read-back beyond the index's own.  variation is the surface variation l0 / (l0 + l1 + l2) of the ascending
+    eigenvalues (torch, fp32): 0 on a plane, 1 / 3 where the neighbourhood has no direction, and 0 where the sum is 0.
+    radius is best given in units of nearest_spacing: 3 to 4 medians is what the tests use -- at 3 spacings of a unit sphere of
+    4099 points no normal is off by more than a degree.  viewpoint: None, three values, or [M,3] fp32 (the scanner's position per
+    point); without one the signs follow the largest component and are not consistent across a surface.  A point with fewer
+    than min_neighbours neighbours (itself included) has the normal (0, 0, 0), which alignment.icp counts as degenerate; a point
+    that is not finite NaN and count -1.  These are the normals that write_ply(normals=...), remove_outliers(normals=...) and
+    alignment.icp(target_normals=...) take.  order: "records", the default, walks the cloud in the order of the index's records,
+    where the lanes of a wave share cells and cache lines; "input" queries the points as they lie in memory.  The bytes are the
+    same; on a shuffled cloud of a million points "records" measured four times as fast (docs/CLOUD_FIGURES.md)."""
+    if not isinstance(points_or_index, CloudIndex):
+        if not torch.is_tensor(points_or_index):
+            raise TypeError("points_or_index must be a [M, 3] float32 tensor or a CloudIndex")
+        _check_points(points_or_index)
+    m = points_or_index.counts[0] if isinstance(points_or_index, CloudIndex) else int(points_or_index.shape[0])
+    normal_lattice(check_positive("radius", radius))
+    check_int("min_neighbours", min_neighbours, 3, _INT32, "an integer in [3, 2^31)")
+    _check_viewpoint(viewpoint, m)
+    check_bytes(max_bytes)
+    check_choice("order", order, NORMAL_ORDERS)
+    index = _as_cloud_index(points_or_index, max_bytes, "points_or_index")
+    out = index._normals(None if order == "records" else index.points, m, radius, min_neighbours, viewpoint)
+    e = out["eigenvalues"]
+    total = e.sum(1)
+    out["variation"] = torch.where(total == 0, torch.zeros_like(total), e[:, 0] / total)
+    return out
 
 
 def remove_outliers(points, radius, min_neighbours, rgb8=None, normals=None, index=None):

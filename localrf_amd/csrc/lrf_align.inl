@@ -1,8 +1,9 @@
 // lrf_align.inl -- what a registration needs around lrf_mesh_closest: a similarity applied to points, the exact moments of
-// corresponding pairs, and the normal equations of one linearised point-to-plane step (included by lrf_render.hip after
-// lrf_mesh_distance.inl, whose MdMesh, md_face and md_cross it reuses; k_ag_zero is lrf_mesh_raster.inl's, the reductions
-// lrf_common.h's, the host helpers lrf_host.inl's).  The fit itself, a 3 x 3 SVD or a 7 x 7 solve, is the host's
-// (localrf_amd/alignment.py).  The output bytes are a fixed function of the input: integer sums, no float atomics.
+// corresponding pairs, and the normal equations of one linearised point-to-plane step, against a mesh's faces or against the
+// normals stored for a cloud's points (included by lrf_render.hip after lrf_mesh_distance.inl, whose MdMesh, md_face and
+// md_cross it reuses; k_ag_zero is lrf_mesh_raster.inl's, the reductions lrf_common.h's, the host helpers lrf_host.inl's).
+// The fit itself, a 3 x 3 SVD or a 7 x 7 solve, is the host's (localrf_amd/alignment.py).  The output bytes are a fixed
+// function of the input: integer sums, no float atomics.
 //
 // Every function below with contraction off; "fp64" means every operation rounded on its own, in the order written.
 //   1. the transform.  T: 12 doubles, row-major 3 x 4.  With x, y, z the point's fp32 coordinates in fp64 (exact):
@@ -33,12 +34,21 @@
 //      is below 2^40.5, and 2^20 of them sum below 2^60.5, a factor of five under 2^63.  The exponent 36 stays.
 //      A face index is tested before it is used and a corner index inside md_face: nothing outside the arrays is dereferenced,
 //      whatever face holds.
+//   4. item 3 against a cloud: points p_i with lrf_cloud_closest's outputs for them (closest q_i, index j_i, distance d_i) and
+//      normals [M,3] fp32, one per cloud point (lrf_cloud_normals' or any other; a zero row marks a point without one).  Per
+//      point, the first that applies: j_i outside [0, M) or d_i not finite (unmatched); d_i > gate in fp32 (gated); the three
+//      words of normals[j_i] not all finite, or with n their fp64 values nn = (n0 n0 + n1 n1) + n2 n2 == 0 (degenerate);
+//      out_of_range exactly as item 3.  Otherwise m_k = n_k / sqrt(nn) and r, J and the sums exactly as item 3: the same 48
+//      words in the same layout.  k_al_plane_cloud repeats k_al_plane's lines from pt, qt on: shared through a function over s
+//      they cost k_al_plane 32 more registers and 5 % of its time, so k_al_plane stays as it was, line for line.
+//      NO OVERFLOW.  Item 3's argument rests on |pt|, |qt| <= sqrt(3) and |m| <= 1 + 2^-50 alone, and m is again a vector
+//      divided by the root of its own squared length: it carries over word for word.  An index is tested before it is used.
 //
-// Work distribution.  k_al_transform: one lane per point.  k_al_pairs and k_al_plane: a workgroup per AL_NT AL_PX points, lane t
-// on points t, t + AL_NT, ..: consecutive lanes on consecutive points, the sums as long long in registers; block_sum0 over the
-// workgroup, then thread 0 issues one 64-bit integer atomicAdd per non-zero word: at 2^20 points 512 workgroups, about 21 000 adds
-// on 42 addresses (per wave it would be four times that).  Integer adds commute: the words depend on neither scheduling, launch
-// geometry nor the order of the points.  LDS: the helper's [words][waves] only.
+// Work distribution.  k_al_transform: one lane per point.  k_al_pairs, k_al_plane and k_al_plane_cloud: a workgroup per AL_NT AL_PX
+// points, lane t on points t, t + AL_NT, ..: consecutive lanes on consecutive points, the sums as long long in registers;
+// block_sum0 over the workgroup, then thread 0 issues one 64-bit integer atomicAdd per non-zero word: at 2^20 points 512
+// workgroups, about 21 000 adds on 42 addresses (per wave it would be four times that).  Integer adds commute: the words depend
+// on neither scheduling, launch geometry nor the order of the points.  LDS: the helper's [words][waves] only.
 //
 // No waiting: every loop has AL_PX steps; atomics are single instructions that are never retried; no lane, wave or workgroup
 // waits on another beyond block_sum0's one barrier.
@@ -185,6 +195,71 @@ __global__ __launch_bounds__(AL_NT) void k_al_plane(AlPlane g, unsigned long lon
   al_flush(s, words);
 }
 
+struct AlPlaneCloud {
+  const float* points; const float* closest; const int* index; const float* distance; const float* normals;
+  long long N; int M;
+  double c[3]; double u;
+  float gate;
+};
+
+__global__ __launch_bounds__(AL_NT) void k_al_plane_cloud(AlPlaneCloud g, unsigned long long* __restrict__ words) {
+#pragma clang fp contract(off)
+  __shared__ long long red[AL_PLANE_SUMS * (AL_NT / 64)];
+  long long s[AL_PLANE_SUMS];
+#pragma unroll
+  for (int w = 0; w < AL_PLANE_SUMS; ++w) s[w] = 0;
+#pragma unroll 1
+  for (int k = 0; k < AL_PX; ++k) {
+    const long long i = ((long long)blockIdx.x * AL_PX + k) * AL_NT + threadIdx.x;
+    if (i >= g.N) break;
+    const int f = g.index[i];
+    const float d = g.distance[i];
+    if (!in_range(f, g.M) || !((__float_as_uint(d) & 0x7FFFFFFFu) < 0x7F800000u)) { ++s[1]; continue; }
+    if (d > g.gate) { ++s[2]; continue; }
+    double n[3];
+    bool finite = true;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      const float w = g.normals[3ll * f + j];
+      finite = finite && (__float_as_uint(w) & 0x7FFFFFFFu) < 0x7F800000u;
+      n[j] = (double)w;
+    }
+    const double nn = (n[0] * n[0] + n[1] * n[1]) + n[2] * n[2];
+    if (!finite || nn == 0.0) { ++s[3]; continue; }
+    double pt[3], qt[3];
+    bool inside = true;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      pt[j] = ((double)g.points[3 * i + j] - g.c[j]) / g.u;
+      qt[j] = ((double)g.closest[3 * i + j] - g.c[j]) / g.u;
+      inside = inside && fabs(pt[j]) <= 1.0 && fabs(qt[j]) <= 1.0;    // a NaN fails
+    }
+    if (!inside) { ++s[4]; continue; }
+    const double len = sqrt(nn);
+    double J[7], dd[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      J[3 + j] = n[j] / len;
+      dd[j] = pt[j] - qt[j];
+    }
+    const double r = (J[3] * dd[0] + J[4] * dd[1]) + J[5] * dd[2];
+    J[0] = pt[1] * J[5] - pt[2] * J[4];
+    J[1] = pt[2] * J[3] - pt[0] * J[5];
+    J[2] = pt[0] * J[4] - pt[1] * J[3];
+    J[6] = (pt[0] * J[3] + pt[1] * J[4]) + pt[2] * J[5];
+    ++s[0];
+    s[6] += llrint((r * r) * AL_SCALE);
+#pragma unroll
+    for (int a = 0; a < 7; ++a) {
+      s[7 + a] += llrint((J[a] * r) * AL_SCALE);
+#pragma unroll
+      for (int l = a; l < 7; ++l) s[14 + 7 * a - a * (a - 1) / 2 + (l - a)] += llrint((J[a] * J[l]) * AL_SCALE);
+    }
+  }
+  block_sum0<AL_NT>(s, red);
+  al_flush(s, words);
+}
+
 // x > 0, finite and a power of two
 static bool al_power_of_two(double x) {
   int e;
@@ -252,5 +327,30 @@ extern "C" int lrf_align_plane(const LrfAlignPlane* p, int64_t* words, void* str
   unsigned long long* w = reinterpret_cast<unsigned long long*>(words);
   LRF_TRY(launch(k_ag_zero, 1, RS_NT, st, w, (long long)AL_PLANE_WORDS));
   if (p->N) LRF_TRY(launch(k_al_plane, blocks_for(p->N, AL_NT * AL_PX), AL_NT, st, g, w));
+  return 0;
+}
+
+extern "C" int lrf_align_plane_cloud(const LrfAlignPlaneCloud* p, int64_t* words, void* stream) {
+  using namespace lrf;
+  const char* who = "lrf_align_plane_cloud";
+  if (!p || !words) return refuse(who, "null argument");
+  if (p->M < 1 || p->M >= (1ll << 31)) return refuse(who, "need 1 <= M < 2^31");
+  if (p->N < 0 || p->N > AL_MAX_N) return refuse(who, "need 0 <= N <= 2^20");
+  if (!p->normals || (p->N && (!p->points || !p->closest || !p->index || !p->distance))) return refuse(who, "null argument");
+  if (!al_power_of_two(p->u)) return refuse(who, "u must be a positive power of two");
+  if (!is_finite(p->c[0]) || !is_finite(p->c[1]) || !is_finite(p->c[2])) return refuse(who, "c must be finite");
+  if (!(p->gate >= 0.0f)) return refuse(who, "gate must be >= 0 (infinity allowed)");
+  if (misaligned(3, p->points, p->closest, p->index, p->distance, p->normals))
+    return refuse(who, "float and int32 arrays must be 4-byte aligned");
+  if (misaligned(7, words)) return refuse(who, "words must be 8-byte aligned");
+  AlPlaneCloud g;
+  memset(&g, 0, sizeof(g));
+  g.points = p->points; g.closest = p->closest; g.index = p->index; g.distance = p->distance; g.normals = p->normals;
+  g.N = p->N; g.M = (int)p->M; g.u = p->u; g.gate = p->gate;
+  for (int k = 0; k < 3; ++k) g.c[k] = p->c[k];
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  unsigned long long* w = reinterpret_cast<unsigned long long*>(words);
+  LRF_TRY(launch(k_ag_zero, 1, RS_NT, st, w, (long long)AL_PLANE_WORDS));
+  if (p->N) LRF_TRY(launch(k_al_plane_cloud, blocks_for(p->N, AL_NT * AL_PX), AL_NT, st, g, w));
   return 0;
 }

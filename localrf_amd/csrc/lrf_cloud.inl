@@ -1,9 +1,10 @@
 // lrf_cloud.inl -- a point cloud indexed for neighbour queries, and a cloud reduced to one point per cell of a voxel grid: the
-// nearest point, the k nearest, the points within a radius, the voxel grid (included by lrf_render.hip after lrf_align.inl; the
-// grid arithmetic, MdGrid, md_cell, MD_SLACK, md_cells and k_md_bounds_init are lrf_mesh_distance.inl's, sm_key and k_sm_copy
-// lrf_mesh_smooth.inl's, the cell of a point, the cluster scan, the integer sums and the representative lrf_mesh_simplify.inl's,
-// the scan and the wave-leader counts lrf_compact.inl's, the host helpers lrf_host.inl's).  The output bytes are a fixed function
-// of the input: exact minima with an index tie-break, integer counts and sums, no float atomics.
+// nearest point, the k nearest, the points within a radius, the normals, the voxel grid (included by lrf_render.hip after
+// lrf_align.inl, whose al_power_of_two it uses; the grid arithmetic, MdGrid, md_cell, MD_SLACK, md_cells and k_md_bounds_init are
+// lrf_mesh_distance.inl's, sm_key and k_sm_copy lrf_mesh_smooth.inl's, the cell of a point, the cluster scan, the integer sums
+// and the representative lrf_mesh_simplify.inl's, the scan and the wave-leader counts lrf_compact.inl's, the host helpers
+// lrf_host.inl's).  The output bytes are a fixed function of the input: exact minima with an index tie-break, integer counts and
+// sums, no float atomics.
 //
 // Every function below with contraction off; "fp64" means every operation rounded on its own, in the order written.
 //   1. points.  A cloud is points [M,3] fp32.  A point with a coordinate that is not finite is skipped and counted
@@ -46,12 +47,47 @@
 //      ms_position and the rounded mean colour.  A bad point (not finite, or |i| >= 2^30 on an axis) is skipped and counted and
 //      has cluster_of = -1.  EVERY occupied cell is emitted, in cluster order, with the number of its points.  The bytes do
 //      not depend on the order of the points.
+//   9. normals: the eigenvectors of the covariance of a query's neighbourhood, a radius and min_neighbours >= 3 given.
+//      NEIGHBOURHOOD.  The used points with d2 <= radius radius, item 7's test, the boundary included; a point equal to the
+//      query counts; no self_first.  n is their number.
+//      LATTICE.  h, from the host: the smallest power of two with radius / h <= 2^15.  Per neighbour q of the query p:
+//      t_k = (long long)rint(((double)q_k - (double)p_k) / h).  fl(d_k d_k) <= d2 <= fl(radius radius) gives |d_k| <= radius
+//      (1 + 2^-52), so |t_k| <= 2^15.
+//      SUMS, int64 in registers: n, s_k = sum t_k, S_ij = sum t_i t_j for i <= j.
+//      NO OVERFLOW.  |t_i t_j| <= 2^30 and a cloud has fewer than 2^31 points: every sum stays below 2^61.  Integer sums are
+//      why the result cannot depend on the order in which item 3's cursor left the records of a cell.
+//      COVARIANCE, fp64: nd = (double)n, mean_k = (double)s_k / nd, C_ij = (double)S_ij / nd - mean_i mean_j, and trace =
+//      (C_00 + C_11) + C_22.  The conversions are exact while a sum is below 2^53 in magnitude: in every neighbourhood of fewer
+//      than 2^23 points; beyond that they round to nearest, as any restatement's do.
+//      EIGENVECTORS.  A = C, V = the identity, then CL_JACOBI_SWEEPS sweeps of cyclic Jacobi over the pairs (p, q) = (0, 1),
+//      (0, 2), (1, 2), r the remaining index.  A pair with a_pq == 0 is skipped.  Otherwise, every operation as written:
+//        theta = (a_qq - a_pp) / (2 a_pq);  t = (theta < 0 ? -1 : 1) / (|theta| + sqrt(theta theta + 1))
+//        c = 1 / sqrt(t t + 1);  s = t c
+//        a_pp = a_pp - t a_pq;  a_qq = a_qq + t a_pq
+//        (a_rp, a_rq) = (c a_rp - s a_rq, s a_rp + c a_rq), both from the old pair;  a_pq = 0
+//        (v_kp, v_kq) = (c v_kp - s v_kq, s v_kp + c v_kq) for k = 0, 1, 2, both from the old pair
+//      Only + - * / and sqrt: their fp64 results are the same bits on the device and in numpy, which acos, cos or atan2 would
+//      not give.  An infinite theta (a tiny a_pq) gives t = +-0, c = 1, s = +-0 by IEEE rules: no special case.  The sweep
+//      count is a constant: the most any case of tests/cloud_normal_cases.py needs until every off-diagonal entry is 0 or below
+//      2^-52 trace (4), plus 2.  A, V and the pairs are named scalars: nothing is indexed at run time.
+//      OUTPUTS.  The column: that of V at the smallest of a_00, a_11, a_22, the lowest column among equals.  Its sign: with a
+//      viewpoint v (fp32; one for all queries, or one per query), dot = ((v0 - p0) n0 + (v1 - p1) n1) + (v2 - p2) n2 with
+//      v_k - p_k = (double)v_k - (double)p_k; dot < 0 flips, dot > 0 does not; without a viewpoint, or with a dot that is 0
+//      (or NaN: a viewpoint that is not finite), the component of largest magnitude, the lowest index among equals, is made
+//      positive.  normal_k = (float) of the column, flipped or not.  eigenvalues: a_00, a_11, a_22 put in ascending order by
+//      three compare-and-swaps ((0,1), (1,2), (0,1); a swap only on <), each (float)(a (h h)).  count = n.
+//      DEGENERATE.  n < min_neighbours or trace == 0: normal (0, 0, 0), the eigenvalues as computed (0 with n == 0) and the
+//      true count.  A query that is not finite: NaN, NaN, -1.
+//      RECORD ORDER.  Without query points the queries are the cloud's own: lane j takes record j, queries its x, y, z and
+//      writes row index(j); the rows of the points that are not finite are written by k_cl_normals_rest.  The same bytes as
+//      the cloud queried in input order, with the lanes of a wave in the same or neighbouring cells.
 //
 // Work distribution.  k_cl_bounds, k_cl_fill, k_cl_voxel_bounds: one lane per point.  k_cl_fill runs twice: without records it
 // counts (an int32 atomicAdd on the point's one cell), k_points_scan turns the counts into starts, and with the records the
-// cursor starts at a copy of the starts and ends as the cell's end.  k_cl_closest, k_cl_knn<K>, k_cl_radius_count: one lane per
-// query point; no atomics, no LDS, no scratch.  lrf_cloud_voxel: k_ms_zero, k_ms_mark, k_ms_count_words, k_points_scan,
-// k_ms_accumulate as lrf_mesh_simplify runs them, then k_cl_voxel_write, one lane per cluster.
+// cursor starts at a copy of the starts and ends as the cell's end.  k_cl_closest, k_cl_knn<K>, k_cl_radius_count, k_cl_normals:
+// one lane per query point (k_cl_normals<true>: per record); no atomics, no LDS, no scratch.  k_cl_normals_rest: one lane per
+// point.  lrf_cloud_voxel: k_ms_zero, k_ms_mark, k_ms_count_words, k_points_scan, k_ms_accumulate as lrf_mesh_simplify runs them,
+// then k_cl_voxel_write, one lane per cluster.
 //
 // No waiting: every loop is bounded by the grid or by a cell's record count read once; atomics are single instructions that
 // are never retried; no lane, wave or workgroup waits on another.
@@ -157,6 +193,28 @@ struct ClWithin {
   __device__ __forceinline__ double deciding() const { return __longlong_as_double(0x7FF0000000000000ll); }
 };
 
+// item 9's state: the ten integer sums, named so that they stay registers
+struct ClMoments {
+  double r2, h, p0, p1, p2;
+  long long n, s0, s1, s2, s00, s01, s02, s11, s12, s22;
+  __device__ __forceinline__ void init(const float (&p)[3], double r2_, double h_) {
+    r2 = r2_; h = h_;
+    p0 = (double)p[0]; p1 = (double)p[1]; p2 = (double)p[2];
+    n = s0 = s1 = s2 = s00 = s01 = s02 = s11 = s12 = s22 = 0;
+  }
+  __device__ __forceinline__ void visit(double e, int, const float4& r) {
+#pragma clang fp contract(off)
+    if (!(e <= r2)) return;
+    const long long t0 = (long long)rint(((double)r.x - p0) / h), t1 = (long long)rint(((double)r.y - p1) / h);
+    const long long t2 = (long long)rint(((double)r.z - p2) / h);
+    ++n;
+    s0 += t0; s1 += t1; s2 += t2;
+    s00 += t0 * t0; s01 += t0 * t1; s02 += t0 * t2;
+    s11 += t1 * t1; s12 += t1 * t2; s22 += t2 * t2;
+  }
+  __device__ __forceinline__ double deciding() const { return __longlong_as_double(0x7FF0000000000000ll); }
+};
+
 // the records of cell ci against P
 template <class S>
 __device__ __forceinline__ void cl_visit(const ClQuery& q, long long ci, const double (&P)[3], int self, S& s) {
@@ -259,6 +317,123 @@ __global__ __launch_bounds__(CL_NT) void k_cl_radius_count(ClQuery q, int* __res
   count[i] = finite ? s.n : -1;
 }
 
+// ------------------------------------------------------------------------------------------------ item 9
+constexpr int CL_JACOBI_SWEEPS = 6;                                 // tests/cloud_normal_cases.py: no case needs more than 4
+
+struct ClNormals {
+  double h; int min_neighbours; int M;
+  const float* view; long long view_stride;                         // null: no viewpoint; stride 0: one for all, 3: per query
+  float* normal; float* eigenvalues; int* count;
+};
+
+// one rotation of item 9 on the pair (p, q), r the remaining index, every operand a named scalar of the kernel.  A macro, not a
+// function over references: with their addresses taken the columns of V are picked through a selected address, out of scratch
+#define CL_ROTATE(app, aqq, apq, arp, arq, v0p, v0q, v1p, v1q, v2p, v2q)                          \
+  if (apq != 0.0) {                                                                               \
+    const double theta = (aqq - app) / (2.0 * apq);                                               \
+    const double t = (theta < 0.0 ? -1.0 : 1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));      \
+    const double c = 1.0 / sqrt(t * t + 1.0);                                                     \
+    const double s = t * c;                                                                       \
+    app = app - t * apq;                                                                          \
+    aqq = aqq + t * apq;                                                                          \
+    const double x = arp, y = arq;                                                                \
+    arp = c * x - s * y;                                                                          \
+    arq = s * x + c * y;                                                                          \
+    apq = 0.0;                                                                                    \
+    const double x0 = v0p, y0 = v0q, x1 = v1p, y1 = v1q, x2 = v2p, y2 = v2q;                      \
+    v0p = c * x0 - s * y0; v0q = s * x0 + c * y0;                                                 \
+    v1p = c * x1 - s * y1; v1q = s * x1 + c * y1;                                                 \
+    v2p = c * x2 - s * y2; v2q = s * x2 + c * y2;                                                 \
+  }
+
+// RECORDS: lane j takes record j (q.N = the records) and writes the row of the record's index; else query j of q.points
+template <bool RECORDS>
+__global__ __launch_bounds__(CL_NT) void k_cl_normals(ClQuery q, ClNormals g) {
+#pragma clang fp contract(off)
+  const long long j = (long long)blockIdx.x * CL_NT + threadIdx.x;
+  if (j >= q.N) return;
+  float p[3];
+  long long row = j;
+  bool finite;
+  if (RECORDS) {
+    const float4 r = q.records[j];
+    p[0] = r.x; p[1] = r.y; p[2] = r.z;
+    row = __float_as_int(r.w);
+    finite = true;                                                  // only used points have records
+    if (!in_range((int)row, g.M)) return;                           // cannot happen in a built index: no row outside the outputs
+  } else {
+    finite = cl_load(q.points, j, p);
+  }
+  float* normal = g.normal + 3 * row;
+  float* eigen = g.eigenvalues + 3 * row;
+  if (!finite) {
+    const float nan = __uint_as_float(0x7FC00000u);
+    normal[0] = normal[1] = normal[2] = nan;
+    eigen[0] = eigen[1] = eigen[2] = nan;
+    g.count[row] = -1;
+    return;
+  }
+  ClMoments mo;
+  mo.init(p, q.limit * q.limit, g.h);
+  cl_walk(q, p, -1, mo);
+  double e0 = 0.0, e1 = 0.0, e2 = 0.0, c0 = 0.0, c1 = 0.0, c2 = 0.0;
+  bool ok = false;
+  if (mo.n > 0) {
+    const double nd = (double)mo.n;
+    const double m0 = (double)mo.s0 / nd, m1 = (double)mo.s1 / nd, m2 = (double)mo.s2 / nd;
+    double a00 = (double)mo.s00 / nd - m0 * m0, a01 = (double)mo.s01 / nd - m0 * m1, a02 = (double)mo.s02 / nd - m0 * m2;
+    double a11 = (double)mo.s11 / nd - m1 * m1, a12 = (double)mo.s12 / nd - m1 * m2, a22 = (double)mo.s22 / nd - m2 * m2;
+    const double trace = (a00 + a11) + a22;
+    double v00 = 1.0, v01 = 0.0, v02 = 0.0, v10 = 0.0, v11 = 1.0, v12 = 0.0, v20 = 0.0, v21 = 0.0, v22 = 1.0;
+#pragma unroll 1
+    for (int sweep = 0; sweep < CL_JACOBI_SWEEPS; ++sweep) {
+      CL_ROTATE(a00, a11, a01, a02, a12, v00, v01, v10, v11, v20, v21);             // (0, 1), r = 2
+      CL_ROTATE(a00, a22, a02, a01, a12, v00, v02, v10, v12, v20, v22);             // (0, 2), r = 1
+      CL_ROTATE(a11, a22, a12, a01, a02, v01, v02, v11, v12, v21, v22);             // (1, 2), r = 0
+    }
+    double least = a00;
+    c0 = v00; c1 = v10; c2 = v20;
+    if (a11 < least) { least = a11; c0 = v01; c1 = v11; c2 = v21; }
+    if (a22 < least) { least = a22; c0 = v02; c1 = v12; c2 = v22; }
+    e0 = a00; e1 = a11; e2 = a22;
+    if (e1 < e0) { const double x = e0; e0 = e1; e1 = x; }
+    if (e2 < e1) { const double x = e1; e1 = e2; e2 = x; }
+    if (e1 < e0) { const double x = e0; e0 = e1; e1 = x; }
+    double dot = 0.0;
+    if (g.view) {
+      const float* v = g.view + g.view_stride * row;
+      const double d0 = (double)v[0] - (double)p[0], d1 = (double)v[1] - (double)p[1], d2 = (double)v[2] - (double)p[2];
+      dot = (d0 * c0 + d1 * c1) + d2 * c2;
+    }
+    bool flip = dot < 0.0;
+    if (!(dot < 0.0) && !(dot > 0.0)) {
+      double big = c0;
+      if (fabs(c1) > fabs(big)) big = c1;
+      if (fabs(c2) > fabs(big)) big = c2;
+      flip = big < 0.0;
+    }
+    if (flip) { c0 = -c0; c1 = -c1; c2 = -c2; }
+    ok = mo.n >= g.min_neighbours && trace != 0.0;
+  }
+  const double hh = g.h * g.h;
+  normal[0] = ok ? (float)c0 : 0.0f; normal[1] = ok ? (float)c1 : 0.0f; normal[2] = ok ? (float)c2 : 0.0f;
+  eigen[0] = (float)(e0 * hh); eigen[1] = (float)(e1 * hh); eigen[2] = (float)(e2 * hh);
+  g.count[row] = (int)mo.n;
+}
+#undef CL_ROTATE
+
+// the rows k_cl_normals<true> does not reach: the cloud points that are not finite
+__global__ __launch_bounds__(CL_NT) void k_cl_normals_rest(const float* __restrict__ points, long long M, float* __restrict__ normal,
+                                                           float* __restrict__ eigenvalues, int* __restrict__ count) {
+  const long long i = (long long)blockIdx.x * CL_NT + threadIdx.x;
+  float p[3];
+  if (i >= M || cl_load(points, i, p)) return;
+  const float nan = __uint_as_float(0x7FC00000u);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) normal[3 * i + k] = eigenvalues[3 * i + k] = nan;
+  count[i] = -1;
+}
+
 // ------------------------------------------------------------------------------------------------ item 8
 // out: int64 [8] = bad points, used points, 0, 0, then six int32 (lo, hi of the integer cells), 0 (k_md_bounds_init's layout)
 __global__ __launch_bounds__(CL_NT) void k_cl_voxel_bounds(const float* __restrict__ points, long long M, MsGrid g,
@@ -352,18 +527,25 @@ static int cl_index_args(const char* who, const LrfCloudIndex* a, MdGrid& g, lon
   return 0;
 }
 
-// what the three queries share: the index with its records, N and the query points -> q
-static int cl_query_args(const char* who, const LrfCloudIndex* a, const float* points, int64_t N, ClQuery& q) {
+// what every query shares: the index with its records -> q, without its points
+static int cl_query_index(const char* who, const LrfCloudIndex* a, ClQuery& q) {
   memset(&q, 0, sizeof(q));
   long long cells = 0;
   LRF_TRY(cl_index_args(who, a, q.g, cells));
   if (!a->records) return refuse(who, "need the records of a built index");
+  const ClGridWs w = cl_carve(a->grid, cells);
+  q.starts = w.starts; q.ends = w.ends; q.records = static_cast<const float4*>(a->records); q.entries = a->entries;
+  q.self_first = -1;
+  return 0;
+}
+
+// what the three queries of items 5-7 share: the index, N and the query points -> q
+static int cl_query_args(const char* who, const LrfCloudIndex* a, const float* points, int64_t N, ClQuery& q) {
+  LRF_TRY(cl_query_index(who, a, q));
   if (N < 1 || N >= (1ll << 31)) return refuse(who, "need 1 <= N < 2^31");
   if (!points) return refuse(who, "null argument");
   if (misaligned(3, points)) return refuse(who, "float and int32 arrays must be 4-byte aligned");
-  const ClGridWs w = cl_carve(a->grid, cells);
-  q.starts = w.starts; q.ends = w.ends; q.records = static_cast<const float4*>(a->records); q.entries = a->entries;
-  q.points = points; q.N = N; q.self_first = -1;
+  q.points = points; q.N = N;
   return 0;
 }
 
@@ -455,6 +637,42 @@ extern "C" int lrf_cloud_radius_count(const LrfCloudIndex* a, const float* point
   q.limit = radius;
   q.self_first = self_first;
   return launch(k_cl_radius_count, blocks_for(N, CL_NT), CL_NT, reinterpret_cast<hipStream_t>(stream), q, count);
+}
+
+extern "C" int lrf_cloud_normals(const LrfCloudIndex* a, const float* points, int64_t N, double radius, double h, int32_t min_neighbours,
+                                 const float* viewpoints, int64_t viewpoint_stride, float* normal, float* eigenvalues, int32_t* count,
+                                 void* stream) {
+  using namespace lrf;
+  const char* who = "lrf_cloud_normals";
+  ClQuery q;
+  LRF_TRY(cl_query_index(who, a, q));
+  if (N < 0 || N >= (1ll << 31)) return refuse(who, "need 0 <= N < 2^31");
+  if (!(radius > 0.0) || !is_finite(radius)) return refuse(who, "radius must be finite and > 0");
+  if (!al_power_of_two(h)) return refuse(who, "h must be a positive power of two");
+  if (!(radius / h <= 32768.0) || radius / (0.5 * h) <= 32768.0)
+    return refuse(who, "h must be the smallest power of two with radius / h <= 2^15");
+  if (min_neighbours < 3) return refuse(who, "min_neighbours must be >= 3");
+  if (viewpoint_stride != 0 && viewpoint_stride != 3)
+    return refuse(who, "viewpoint_stride must be 0 (one viewpoint) or 3 (one per query)");
+  if (!normal || !eigenvalues || !count) return refuse(who, "null argument");
+  if (misaligned(3, points, viewpoints, normal, eigenvalues, count)) return refuse(who, "float and int32 arrays must be 4-byte aligned");
+  if (!points && N != a->M) return refuse(who, "without points the queries are the cloud's own: need N == M");
+  if (!N) return 0;
+  ClNormals g;
+  memset(&g, 0, sizeof(g));
+  g.h = h; g.min_neighbours = min_neighbours; g.M = (int)(points ? N : a->M);
+  g.view = viewpoints; g.view_stride = viewpoint_stride;
+  g.normal = normal; g.eigenvalues = eigenvalues; g.count = count;
+  q.limit = radius;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (points) {
+    q.points = points; q.N = N;
+    return launch(k_cl_normals<false>, blocks_for(N, CL_NT), CL_NT, st, q, g);
+  }
+  LRF_TRY(launch(k_cl_normals_rest, blocks_for(a->M, CL_NT), CL_NT, st, a->points, (long long)a->M, normal, eigenvalues, count));
+  q.N = a->entries;
+  if (!q.N) return 0;
+  return launch(k_cl_normals<true>, blocks_for(q.N, CL_NT), CL_NT, st, q, g);
 }
 
 extern "C" int lrf_cloud_voxel_bounds(const float* points, int64_t M, const double* origin, double cell, int64_t* out, void* stream) {
