@@ -41,11 +41,26 @@ int     lrf_debug_block_reduce(const float* in, int32_t B, int32_t NT, int32_t e
                                uint32_t* bits_min, uint32_t* bits_max, void* stream);
 void    lrf_debug_set_scene_fuse(int on);         /* lrf_scene_fwd: several fields per march / colour launch (default on); 0 = field by field */
 void    lrf_debug_set_bwd_overlap(int on);        /* lrf_render_bwd: two branches on two streams (default on); 1 + 2 * (n + 1): k_wgrad_w2w3 on the caller's stream (n > 0, default) or on the side stream behind the density scatter (n = 0) */
-void    lrf_debug_set_train_fwd_engine(int bits); /* 8: plane and line gradients by separate scatter kernels; 16: the gradient scatters with fp32 compare-and-swap adds (k_scatter_plane, rounds 2-5) instead of 64-bit fixed point (k_scatter_fix); 256: fixed point for the density tensors only (default: the appearance tensors too where their accumulators fit in LDS, lines up to 479 cells); 1024: no four-channel sweeps (lines of 480 .. 640 cells: the appearance tensors through the compare-and-swap kernel, as before); 512: k_wgrad_w2w3 in its single-buffered 128-row form (rounds 4-5) instead of the double-buffered 64-row one; 32 / 64 / 128: k_train_dgrad3 + k_train_app3 without their row stores / position gradient and X / dz1 products (timing experiments, wrong results) */
+void    lrf_debug_set_train_fwd_engine(int bits); /* 8: plane and line gradients by separate scatter kernels; 16: the gradient scatters with fp32 compare-and-swap adds (k_scatter_plane, rounds 2-5) instead of 64-bit fixed point (k_scatter_fix); 256: fixed point for the density tensors only (default: the appearance tensors too where their accumulators fit in LDS, lines up to 479 cells); 1024: no four-channel sweeps (lines of 480 .. 661 cells: the appearance tensors through the compare-and-swap kernel, as before); 512: k_wgrad_w2w3 in its single-buffered 128-row form (rounds 4-5) instead of the double-buffered 64-row one; 32 / 64 / 128: k_train_dgrad3 + k_train_app3 without their row stores / position gradient and X / dz1 products (timing experiments, wrong results) */
 void    lrf_debug_set_scatter_wgs(int n);         /* lrf_render_bwd: workgroups of the binned plane / line scatter kernels (0 = default, one per CU); either mode -- the tests change the partition with it */
 /* float offset of (row, col) inside the ACT (0) / GRD (1) region of a training workspace (MFMA-fragment order,
- * csrc/lrf_common.h); buffer 2: X-block column of appearance channel col */
+ * csrc/lrf_common.h); buffer 2: X-block column of appearance channel col.  Buffer 1, columns 48 .. 127, is the dX block in
+ * its row-major order (what the compare-and-swap scatter kernels read); buffer 3: the same block in the groups order the
+ * fixed-point appearance scatter asks for (lrf_debug_scatter_plan: appearance engine 0 or 1), col = 24 * plane + channel, 0 .. 71 */
 int64_t lrf_debug_saved_row_offset(int buffer, uint64_t row, int col);
+/* The gradient scatter engines lrf_render_bwd picks for a grid whose longest side is ll_max cells: a pure host function, no
+ * device needed.  deterministic: LRF_FLAG_DETERMINISTIC; engine_bits: as lrf_debug_set_train_fwd_engine takes them (1 = the
+ * defaults), or negative = whatever that switch holds now.  out = {density engine, appearance engine, density channels per
+ * sweep, appearance channels per sweep, dynamic LDS bytes of the density scatter kernel, of the appearance scatter kernel, of
+ * the density line kernel, of the appearance line kernel}; engines: 0 = int64 image (deterministic), 1 = 64-bit fixed point,
+ * 2 = compare-and-swap with the lines fused, 3 = compare-and-swap with the lines apart (the line kernel runs only then).
+ * Returns 0, 1 where lrf_render_bwd refuses the grid (deterministic and ll_max > 640), -1 for bad arguments. */
+int     lrf_debug_scatter_plan(int32_t ll_max, int32_t deterministic, int32_t engine_bits, int64_t out[8]);
+/* Byte offsets, inside a training workspace (any flags: the deterministic mode's image lies behind everything else), of the two
+ * words that hold the largest |contribution| of a backward as float bits: out[0] the density group's (k_bwd_ray), out[1] the
+ * appearance group's (k_train_app3, written only where the appearance scatter runs on fixed point).  k_clear_bins zeroes both
+ * in front of every backward; the fixed-point scatter kernels take their scale from them. */
+void    lrf_debug_workspace_vmax_bwd(int32_t R, int32_t S, const int32_t grid[3], uint64_t out[2]);
 /* k_depth_quantiles alone on caller-supplied weights w [R,S] (device), z [S], rays [R,6]; q: host [K], 1 <= K <= 4, each in
  * (0, 1] -> depth [K,R], index int32 [K,R] (nullable).  The arithmetic of csrc/lrf_quantile.inl without a forward render. */
 int     lrf_depth_quantiles_from_weights(const float* w, const float* z, const float* rays, int32_t R, int32_t S, const float* q,

@@ -1474,7 +1474,7 @@ __device__ __forceinline__ void scatter_fix_body(const DField& f, const BinGeom&
   // three times instead -- 8-channel line accumulators -- fetched every 128-byte line of taps and dX rows three times from
   // beyond L2: 1.57 GB of counter traffic for the two scatter kernels against 0.88 GB with the compare-and-swap kernels.)
   // CH: channels per sweep.  8, or 4 for the appearance tensors of grids whose lines do not fit beside an 8-channel tile (lines of
-  // 480 .. 640 cells: six sweeps per tile, the tile 34.8 KB; the dX block's 8-channel groups are read in halves)
+  // 480 .. 661 cells: six sweeps per tile, the tile 34.8 KB; the dX block's 8-channel groups are read in halves)
   static_assert(C % CH == 0 && (CH == 8 || (APP && CH == 4)) && (APP ? C == LRF_CA : C == LRF_CD), "8 (or 4) channels per sweep");
   constexpr int CELLS = BCELL * BCELL;
   extern __shared__ unsigned long long s_fx[];          // [CH][CELLS] tile (of the sweep), then [C][L_p] line
@@ -1831,7 +1831,12 @@ static hipError_t launch_shade_save(DField d, const float* rays, const float* z,
 }  // namespace lrf
 
 extern "C" void lrf_debug_set_scatter_wgs(int n) { lrf::g_scatter_wgs = n > 0 ? n : 0; }
-extern "C" void lrf_debug_set_train_fwd_engine(int e) { lrf::g_scatter_fused = (e & 8) ? 0 : 1; lrf::g_scatter_fix = (e & 16) ? 0 : ((e & 256) ? 1 : ((e & 1024) ? 7 : 3)); lrf::g_dgrad_dbg = (e >> 5) & 7; lrf::g_wgrad_kt = (e & 512) ? 128 : 64; }
+namespace lrf {
+// the scatter switches inside lrf_debug_set_train_fwd_engine's bits (g_scatter_fused, g_scatter_fix)
+static int engine_bits_fused(int e) { return (e & 8) ? 0 : 1; }
+static int engine_bits_fix(int e) { return (e & 16) ? 0 : ((e & 256) ? 1 : ((e & 1024) ? 7 : 3)); }
+}  // namespace lrf
+extern "C" void lrf_debug_set_train_fwd_engine(int e) { lrf::g_scatter_fused = lrf::engine_bits_fused(e); lrf::g_scatter_fix = lrf::engine_bits_fix(e); lrf::g_dgrad_dbg = (e >> 5) & 7; lrf::g_wgrad_kt = (e & 512) ? 128 : 64; }
 
 namespace lrf {
 // floats per row of weight-gradient operands when the backward runs the generic engine (any non-default network, or
@@ -1871,6 +1876,11 @@ extern "C" void lrf_workspace_layout_bwd(int32_t R, int32_t S, const int32_t gri
   out[8] = off(b.feat);
 }
 
+extern "C" void lrf_debug_workspace_vmax_bwd(int32_t R, int32_t S, const int32_t grid[3], uint64_t out[2]) {
+  const lrf::BwdWorkspace b = lrf::carve_bwd(nullptr, R, S, grid);
+  for (int q = 0; q < 2; ++q) out[q] = (uint64_t)reinterpret_cast<uintptr_t>(b.bins[q].vmax);
+}
+
 extern "C" int lrf_render_fwd_train(const LrfField* f, const float* rays, const float* z, int32_t R, int32_t S,
                                     uint32_t flags, float* rgb, float* depth, void* workspace, void* stream) {
   using namespace lrf;
@@ -1901,10 +1911,56 @@ struct ScatterGroup {
   DetDst det;                // Det: the group's part of the int64 image
   bool fixed_point() const { return eng == ScatterEng::Det || eng == ScatterEng::Fix; }
 };
-static ScatterGroup scatter_group(ScatterEng eng, int ch, size_t lds_fix, size_t lds_plane, size_t lds_line, const BinBufs& bins,
+// The engine choice of both tensor groups: a pure function of the longest line, the deterministic flag and the two scatter
+// switches (lrf_debug_set_train_fwd_engine).  plan_bwd and lrf_debug_scatter_plan (the tests pin every threshold) both read it.
+constexpr int DET_MAX_LINE = 640;          // LRF_FLAG_DETERMINISTIC: the longest line it accepts (the reference ends at 640^3)
+struct ScatterLds { size_t fix, plane, line; };    // fixed-point kernel; compare-and-swap plane kernel (without its lines); k_scatter_line / the fused lines
+struct ScatterChoice {
+  bool refused;                            // deterministic mode and a line longer than DET_MAX_LINE
+  ScatterEng dens, app;
+  int app_ch;                              // Det / Fix: channels per sweep of the appearance scatter, 8 or 4 (the density's: 8)
+  ScatterLds d, a;
+};
+static size_t scatter_group_lds(ScatterEng eng, const ScatterLds& l) {
+  return (eng == ScatterEng::Det || eng == ScatterEng::Fix) ? l.fix : eng == ScatterEng::CasFused ? l.plane + l.line : l.plane;
+}
+static ScatterChoice choose_scatter(size_t ll_max, bool det, int sw_fused, int sw_fix) {
+  ScatterChoice c{};
+  const size_t lds_ap = sizeof(float) * BCELL * BCELL * LRF_CA, lds_al = sizeof(float) * LRF_CA * ll_max;
+  const size_t lds_dp = sizeof(float) * BCELL * BCELL * LRF_CD, lds_dl = sizeof(float) * LRF_CD * ll_max;
+  const bool fit_d = 2 * (lds_dp + lds_dl) <= 158 * 1024;   // 64-bit fixed-point accumulators: twice the bytes (lines up to 1439 cells)
+  // the appearance scatter runs on fixed point too where an 8-channel tile + 24-channel line accumulators of 64-bit cells fit
+  // in LDS (lines up to 479 cells): forward + backward 1.26 -> 1.12 ms at 64^3, 1.36 -> 1.29 at 300^3, on par with the
+  // compare-and-swap kernel at 400^3-460^3 (profiles/r17_fixed_point_scatter.md); above that the compare-and-swap kernel stays
+  const size_t lds_fa = 2 * lds_dp + sizeof(unsigned long long) * LRF_CA * ll_max;
+  // ... and with FOUR channels per sweep (six sweeps, a 34.8 KB tile) where only that leaves room for the lines: 480 .. 661 cells
+  const size_t lds_fa4 = lds_dp + sizeof(unsigned long long) * LRF_CA * ll_max;
+  const bool fit_a8 = fit_d && lds_fa <= 158 * 1024, fit_a4 = fit_d && lds_fa4 <= 158 * 1024;
+  c.app_ch = 8;
+  if (det) {
+    // LRF_FLAG_DETERMINISTIC: always the fixed-point kernels (whatever the debug switches say), up to the reference's longest
+    // line: DET_MAX_LINE = 640 cells.  (The four-channel sweeps would still fit at 641 .. 661 cells; nothing reaches those
+    // lengths, and the refusal says 640.)
+    static_assert(2 * (sizeof(float) * BCELL * BCELL * LRF_CD + sizeof(float) * LRF_CD * DET_MAX_LINE) <= 158 * 1024 &&
+                  sizeof(float) * BCELL * BCELL * LRF_CD + sizeof(unsigned long long) * LRF_CA * DET_MAX_LINE <= 158 * 1024,
+                  "the fixed-point accumulators of a DET_MAX_LINE line fit in LDS");
+    c.refused = ll_max > (size_t)DET_MAX_LINE;
+    c.dens = c.app = ScatterEng::Det;
+    c.app_ch = fit_a8 ? 8 : 4;
+  } else {
+    const bool fix_d = sw_fix && sw_fused && fit_d, fix_a = fix_d && (sw_fix & 2);
+    c.dens = fix_d ? ScatterEng::Fix : (sw_fused && lds_dp + lds_dl <= 64 * 1024) ? ScatterEng::CasFused : ScatterEng::CasSplit;
+    const bool fix_a8 = fix_a && fit_a8, fix_a4 = !fix_a8 && fix_a && !(sw_fix & 4) && fit_a4;
+    c.app = (fix_a8 || fix_a4) ? ScatterEng::Fix : (sw_fused && lds_ap + lds_al <= 158 * 1024) ? ScatterEng::CasFused : ScatterEng::CasSplit;
+    c.app_ch = fix_a4 ? 4 : 8;
+  }
+  c.d = ScatterLds{2 * (lds_dp + lds_dl), lds_dp, lds_dl};
+  c.a = ScatterLds{c.app_ch == 8 ? lds_fa : lds_fa4, lds_ap, lds_al};
+  return c;
+}
+static ScatterGroup scatter_group(ScatterEng eng, int ch, const ScatterLds& l, const BinBufs& bins,
                                   float* const* g_plane, float* const* g_line, const DetDst& det) {
-  ScatterGroup G{eng, ch, 0, lds_line, bins, ScatterDst{}, det};
-  G.lds = G.fixed_point() ? lds_fix : eng == ScatterEng::CasFused ? lds_plane + lds_line : lds_plane;
+  ScatterGroup G{eng, ch, scatter_group_lds(eng, l), l.line, bins, ScatterDst{}, det};
   for (int q = 0; q < 3; ++q) { G.dst.plane[q] = g_plane[q]; G.dst.line[q] = g_line[q]; }
   return G;
 }
@@ -1948,38 +2004,14 @@ static const char* plan_bwd(BwdPlan& P, const LrfField* f, const LrfParams* p, c
   if (P.bg.total > BIN_MAX) return "lrf_render_bwd: grid too large for the tile binning (BIN_MAX)";
   for (int q = 0; q < 3; ++q) if ((size_t)L.ll[q] * LRF_CA * 4 > 150 * 1024) return "lrf_render_bwd: line too long for LDS accumulation";
 
-  const size_t ll_max = (size_t)max(L.ll[0], max(L.ll[1], L.ll[2]));
-  const size_t lds_ap = sizeof(float) * BCELL * BCELL * LRF_CA, lds_al = sizeof(float) * LRF_CA * ll_max;
-  const size_t lds_dp = sizeof(float) * BCELL * BCELL * LRF_CD, lds_dl = sizeof(float) * LRF_CD * ll_max;
-  const bool fit_d = 2 * (lds_dp + lds_dl) <= 158 * 1024;   // 64-bit fixed-point accumulators: twice the bytes
-  // the appearance scatter runs on fixed point too where an 8-channel tile + 24-channel line accumulators of 64-bit cells fit
-  // in LDS (lines up to 479 cells): forward + backward 1.26 -> 1.12 ms at 64^3, 1.36 -> 1.29 at 300^3, on par with the
-  // compare-and-swap kernel at 400^3-460^3 (profiles/r17_fixed_point_scatter.md); above that the compare-and-swap kernel stays
-  const size_t lds_fa = 2 * lds_dp + sizeof(unsigned long long) * LRF_CA * ll_max;
-  // ... and with FOUR channels per sweep (six sweeps, a 34.8 KB tile) where only that leaves room for the lines: 480 .. 640 cells
-  const size_t lds_fa4 = lds_dp + sizeof(unsigned long long) * LRF_CA * ll_max;
-  const bool fit_a8 = fit_d && lds_fa <= 158 * 1024, fit_a4 = fit_d && lds_fa4 <= 158 * 1024;
-  ScatterEng dens, app;
-  int app_ch = 8;
-  if (P.det) {
-    // LRF_FLAG_DETERMINISTIC: always the fixed-point kernels (whatever the debug switches say); lines that leave no room for them
-    // in LDS (density: > 1439 cells, appearance: > 640 cells -- the reference ends at 640^3) are refused
-    if (!fit_a8 && !fit_a4)
-      return "lrf_render_bwd: LRF_FLAG_DETERMINISTIC covers lines up to 640 cells (the fixed-point line accumulators of the "
-             "appearance scatter must fit in LDS)";
-    dens = app = ScatterEng::Det;
-    app_ch = fit_a8 ? 8 : 4;
-  } else {
-    const bool fix_d = g_scatter_fix && g_scatter_fused && fit_d, fix_a = fix_d && (g_scatter_fix & 2);
-    dens = fix_d ? ScatterEng::Fix : (g_scatter_fused && lds_dp + lds_dl <= 64 * 1024) ? ScatterEng::CasFused : ScatterEng::CasSplit;
-    const bool fix_a8 = fix_a && fit_a8, fix_a4 = !fix_a8 && fix_a && !(g_scatter_fix & 4) && fit_a4;
-    app = (fix_a8 || fix_a4) ? ScatterEng::Fix : (g_scatter_fused && lds_ap + lds_al <= 158 * 1024) ? ScatterEng::CasFused : ScatterEng::CasSplit;
-    app_ch = fix_a4 ? 4 : 8;
-  }
+  const ScatterChoice sc = choose_scatter((size_t)max(L.ll[0], max(L.ll[1], L.ll[2])), P.det, g_scatter_fused, g_scatter_fix);
+  if (sc.refused)
+    return "lrf_render_bwd: LRF_FLAG_DETERMINISTIC covers lines up to 640 cells (the fixed-point line accumulators of the "
+           "appearance scatter must fit in LDS)";
 
   P.b = carve_bwd(workspace, R, S, f->grid, P.gen_ld, P.det);
-  P.dens = scatter_group(dens, 8, 2 * (lds_dp + lds_dl), lds_dp, lds_dl, P.b.bins[0], g->density_plane, g->density_line, P.b.det_d);
-  P.app = scatter_group(app, app_ch, app_ch == 8 ? lds_fa : lds_fa4, lds_ap, lds_al, P.b.bins[1], g->app_plane, g->app_line, P.b.det_a);
+  P.dens = scatter_group(sc.dens, 8, sc.d, P.b.bins[0], g->density_plane, g->density_line, P.b.det_d);
+  P.app = scatter_group(sc.app, sc.app_ch, sc.a, P.b.bins[1], g->app_plane, g->app_line, P.b.det_a);
   P.nblk = (int)((P.b.nmax + BIN_CHUNK - 1) / BIN_CHUNK);
   // LRF_FLAG_PLANE_EVENTS (data parallel): one pass per plane, an event behind planes 0 and 1 -- a collective over plane p's
   // gradient (8.6 MB each at 300^3) starts while the later planes are still being scattered; otherwise one pass over all bins
@@ -2157,6 +2189,18 @@ static void bwd_rays_add(const BwdPlan& P, hipStream_t s) {
   hipLaunchKernelGGL(k_rays_add_rpart, dim3((P.R + 255) / 256), dim3(256), 0, s, P.rays, P.R, w.ncomp, P.b.rpart, w.pmax, P.g_rays, P.d.perm);
 }
 }  // namespace lrf
+
+// lrf_render_bwd's engine choice without a device (include/lrf_debug.h)
+extern "C" int lrf_debug_scatter_plan(int32_t ll_max, int32_t deterministic, int32_t engine_bits, int64_t out[8]) {
+  using namespace lrf;
+  if (ll_max < 1 || !out) return -1;
+  const ScatterChoice c = engine_bits < 0 ? choose_scatter((size_t)ll_max, deterministic != 0, g_scatter_fused, g_scatter_fix)
+                                          : choose_scatter((size_t)ll_max, deterministic != 0, engine_bits_fused(engine_bits), engine_bits_fix(engine_bits));
+  out[0] = (int64_t)c.dens; out[1] = (int64_t)c.app; out[2] = 8; out[3] = c.app_ch;
+  out[4] = (int64_t)scatter_group_lds(c.dens, c.d); out[5] = (int64_t)scatter_group_lds(c.app, c.a);
+  out[6] = (int64_t)c.d.line; out[7] = (int64_t)c.a.line;
+  return c.refused ? 1 : 0;
+}
 
 // plan_bwd, then the schedule: which stage, on which stream, behind which event.  A refused call enqueues nothing.
 extern "C" int lrf_render_bwd(const LrfField* f, const LrfParams* p, const float* rays, const float* z,

@@ -1416,6 +1416,11 @@ int64_t lrf_debug_saved_row_offset(int buffer, uint64_t row, int col) {
     if (col >= GRD_DX) return (int64_t)((row >> 4) * (uint64_t)(16 * GRD_LD) + GRD_DX * 16 + (row & 15) * (GRD_LD - GRD_DX) + (col - GRD_DX));   // (the row-major order of the dX block; the other one: lrf_common.h)
     return (int64_t)frag_off((size_t)row, col, GRD_LD);
   }
+  if (buffer == 3) {                       // the dX block in its groups order (grd_dx8): col = 24 p + c
+    if (col < 0 || col >= 3 * LRF_CA) return -1;
+    const int p = col / LRF_CA, c = col % LRF_CA;
+    return (int64_t)((row >> 4) * (uint64_t)(16 * GRD_LD) + GRD_DX * 16 + (((p * 3 + (c >> 3)) * 16 + (int)(row & 15)) << 3) + (c & 7));
+  }
   return -1;
 }
 const char* lrf_last_error(void) { return lrf_error_slot(); }
