@@ -1,14 +1,18 @@
-"""The argument checks that more than one geometry module needs (pointcloud, mesh, mesh_raster, mesh_texture, mesh_distance),
-and the one place where a mesh's tensors are required on a GPU.  A check that a single module uses stays in that module.
+"""The argument checks that more than one geometry module needs (pointcloud, mesh, mesh_raster, mesh_texture, mesh_distance,
+cloud, alignment), the one place each where a mesh's and a point tensor's device is required to be a GPU, and the batcher of
+the launches over points.  A check that a single module uses stays in that module.
 
   check_int, check_positive, check_interval, check_flag    one scalar each; bools, non-numbers and NaN are refused
   check_range, check_origin, check_bytes, check_size       depth_range, three finite values, max_bytes, an image's W and H
   check_mesh, check_faces, mesh_on_device                  the mesh dict of mesh.py: host checks, then the device
+  check_points, points_on_device                           a [N,3] fp32 tensor: host checks, then the device
+  check_max_distance, check_thresholds, check_unit         the arguments of the distance queries and of their summary
+  chunks, POINTS_PER_CALL                                  (first item, count) of each launch over n points
   check_depth, check_frame_poses, check_intrinsics, check_rgb   the frame arguments; dev_f32 and rgb8_frames are their device half
 
 Every check runs on the host and returns the value in the type the caller passes on; a refusal is a ValueError naming the
 argument (TypeError for a value that is not a tensor or a mesh).  Callers keep the order type, then dtype and shape, then
-their other arguments, then the device: mesh_on_device and the require_gpu calls come last.
+their other arguments, then the device: mesh_on_device, points_on_device and the require_gpu calls come last.
 """
 import math
 
@@ -145,6 +149,70 @@ def mesh_on_device(v, f, c, feature):
     if f.device != dev or (c is not None and c.device != dev):
         raise ValueError(("vertices and faces" if c is None else "vertices, faces and rgb8") + " must live on the same device")
     return v.detach().contiguous(), f.detach().contiguous(), None if c is None else c.contiguous(), dev
+
+
+def check_points(points):
+    if not torch.is_tensor(points):
+        raise TypeError("points must be a torch tensor")
+    if points.dtype is not torch.float32 or points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError(f"points must be [N, 3] float32, got {points.dtype} {tuple(points.shape)}")
+    return int(points.shape[0])
+
+
+def points_on_device(t, name, feature, dev=None, wording=None):
+    """The device half of check_points, after the call's other arguments: t on a GPU (NativeError naming it) and, with dev -- an
+    index's device or a first tensor's -- on that one (ValueError(wording): the callers' sentences differ) -> t detached and
+    contiguous.  Also for what goes with the points (a viewpoint per point, normals, a keep mask, uint8 colours, which are
+    not detached)."""
+    N.require_gpu(t, name, feature)
+    if dev is not None and t.device != dev:
+        raise ValueError(wording)
+    return t.contiguous() if t.dtype is torch.uint8 else t.detach().contiguous()
+
+
+def check_max_distance(max_distance):
+    try:
+        ok = not isinstance(max_distance, (bool, np.bool_)) and float(max_distance) >= 0        # NaN fails
+    except (TypeError, ValueError, OverflowError):
+        ok = False
+    if not ok:
+        raise ValueError(f"max_distance must be a number >= 0 or infinity, got {max_distance!r}")
+    return float(max_distance)
+
+
+def check_thresholds(thresholds):
+    try:
+        taus = [float(t) for t in thresholds if not isinstance(t, (bool, np.bool_))]
+        ok = len(taus) == len(thresholds)
+    except (TypeError, ValueError, OverflowError):
+        taus, ok = [], False
+    if not ok:
+        raise ValueError(f"thresholds must be a sequence of numbers, got {thresholds!r}")
+    if len(taus) > N.LRF_DISTANCE_MAX_THRESHOLDS:
+        raise ValueError(f"at most {N.LRF_DISTANCE_MAX_THRESHOLDS} thresholds, got {len(taus)}")
+    if not all(math.isfinite(t) and t > 0 for t in taus):
+        raise ValueError(f"every threshold must be a finite number > 0, got {thresholds!r}")
+    taus = [float(np.float32(t)) for t in taus]                     # the kernel compares in fp32
+    if not all(math.isfinite(t) and t > 0 for t in taus):
+        raise ValueError(f"every threshold must be finite and > 0 as float32, got {thresholds!r}")
+    return taus
+
+
+def check_unit(unit):
+    unit = check_positive("unit", unit)
+    if not (math.isfinite(float(np.float32(unit))) and float(np.float32(unit)) > 0):
+        raise ValueError(f"unit must be finite and > 0 as float32, got {unit!r}")
+    return unit
+
+
+POINTS_PER_CALL = 1 << 30                      # what one launch over points takes; chunks reads it at each call
+
+
+def chunks(n, per_call=None):
+    """(i0, m) per launch over n items taken per_call (None: POINTS_PER_CALL) at a time: m items from item i0.  None for n = 0."""
+    per_call = POINTS_PER_CALL if per_call is None else per_call
+    for i0 in range(0, n, per_call):
+        yield i0, min(per_call, n - i0)
 
 
 def float_of_key(key):

@@ -26,9 +26,10 @@ import torch
 
 from . import _native as N
 from ._native import NativeError  # noqa: F401
-from ._checks import check_choice, check_flag, check_int, check_interval, check_mesh, check_positive, mesh_on_device
+from ._checks import (check_choice, check_flag, check_int, check_interval, check_max_distance, check_mesh, check_points, check_positive,
+                      chunks, mesh_on_device, points_on_device)
 from .cloud import CloudIndex
-from .mesh_distance import MeshIndex, _as_index, _check_max_distance, _check_points, sample_surface
+from .mesh_distance import as_index, check_target, sample_surface
 
 PAIRS_PER_CALL = 1 << 20                       # lrf_align_pairs and lrf_align_plane: no word can overflow below this
 PAIR_RANGE = 1 << 20                           # integer coordinates of fit_pairs stay below this in magnitude
@@ -37,7 +38,6 @@ ROTATION_TOL = 1e-9                            # decompose: max |R^T R - I| of t
 RANK_TOL = 1e-10                               # fit_pairs: second singular value of the covariance against the first
 CONDITION_MAX = 1e12                           # icp: condition number of the normal equations
 MIN_MATCHES = 7
-_POINTS_PER_TRANSFORM = 1 << 30
 
 
 # ------------------------------------------------------------------------------------------------ host helpers
@@ -193,21 +193,18 @@ def plane_update(sol, c, u):
 
 # ------------------------------------------------------------------------------------------------ device halves
 def _transform_into(pts, T, out):
-    n = pts.shape[0]
     t = (C.c_double * 12)(*T[:3].reshape(-1).tolist())
-    for i0 in range(0, n, _POINTS_PER_TRANSFORM):
-        i1 = min(n, i0 + _POINTS_PER_TRANSFORM)
-        N.launch("lrf_align_transform", pts.device, t, pts[i0:].data_ptr(), i1 - i0, out[i0:].data_ptr(), guard=True)
+    for i0, m in chunks(pts.shape[0]):
+        N.launch("lrf_align_transform", pts.device, t, pts[i0:].data_ptr(), m, out[i0:].data_ptr(), guard=True)
     return out
 
 
 def transform_points(points, T):
     """points [N,3] fp32 on the device -> T applied, a new [N,3] fp32 tensor: each coordinate ((T0 x + T1 y) + T2 z) + T3 in
     fp64, rounded once to fp32 (csrc/lrf_align.inl item 1).  No read-back."""
-    _check_points(points)
+    check_points(points)
     M = _matrix(T)
-    N.require_gpu(points, "points", "the alignment")
-    pts = points.detach().contiguous()
+    pts = points_on_device(points, "points", "the alignment")
     return _transform_into(pts, M, torch.empty_like(pts))
 
 
@@ -219,15 +216,14 @@ def transform_mesh(mesh, T):
     _, R, _ = decompose(M)
     normals = mesh.get("normals")
     if normals is not None:
-        _check_points(normals)
+        check_points(normals)
         if normals.shape[0] != Nv:
             raise ValueError(f"normals must be {(Nv, 3)} float32, got {tuple(normals.shape)}")
     v, _, _, dev = mesh_on_device(v, f, None, "the alignment")
     out = dict(mesh)
     out["vertices"] = _transform_into(v, M, torch.empty_like(v))
     if normals is not None:
-        N.require_gpu(normals, "normals", "the alignment")
-        nrm = normals.detach().contiguous()
+        nrm = points_on_device(normals, "normals", "the alignment")
         out["normals"] = _transform_into(nrm, _build(1.0, R, np.zeros(3)), torch.empty_like(nrm))
     return out
 
@@ -243,52 +239,49 @@ def _finite_box(*clouds):
     return tuple(lo_hi[0]), tuple(-h for h in lo_hi[1])
 
 
+def _chunk_words(n, width, dev, launch):
+    """One launch(i0, m, row) per PAIRS_PER_CALL of n > 0 items, which fills row, the data pointer of its `width` words (the
+    entry points zero them themselves) -> int64 [chunks, width] on the device; no read-back."""
+    spans = list(chunks(n, PAIRS_PER_CALL))
+    words = torch.empty(len(spans), width, dtype=torch.int64, device=dev)
+    for j, (i0, m) in enumerate(spans):
+        launch(i0, m, words[j].data_ptr())
+    return words
+
+
 def _pair_words(c, h, a, b, keep):
     """Checked, contiguous device arguments -> int64 [chunks, 24] on the device; no read-back."""
-    n = a.shape[0]
     fr = N.LrfAlignFrame()
     fr.h = h
     for k in range(3):
         fr.c[k] = c[k]
-    words = torch.empty(max(1, -(-n // PAIRS_PER_CALL)), 24, dtype=torch.int64, device=a.device)
-    for j, i0 in enumerate(range(0, max(n, 1), PAIRS_PER_CALL)):
-        m = min(n, i0 + PAIRS_PER_CALL) - i0
-        N.launch("lrf_align_pairs", a.device, C.byref(fr), a[i0:].data_ptr() if m else None, b[i0:].data_ptr() if m else None,
-                 keep[i0:].data_ptr() if keep is not None and m else None, m, words[j].data_ptr(), guard=True)
-    return words
+
+    def launch(i0, m, row):
+        N.launch("lrf_align_pairs", a.device, C.byref(fr), a[i0:].data_ptr(), b[i0:].data_ptr(), None if keep is None else keep[i0:].data_ptr(),
+                 m, row, guard=True)
+    return _chunk_words(a.shape[0], 24, a.device, launch)
 
 
-def _plane_words(index, pts, near, c, u, gate):
-    n = pts.shape[0]
-    p = N.LrfAlignPlane()
-    p.vertices, p.faces, (p.Nv, p.Nf) = index.vertices.data_ptr(), index.faces.data_ptr(), index.counts
+def _plane_words(index, pts, near, c, u, gate, normals=None):
+    """Checked, contiguous device arguments -> int64 [chunks, 48] on the device; no read-back.  Against a MeshIndex the plane of a
+    point is its closest face's (lrf_align_plane); against a CloudIndex, with normals = its target_normals, the one through its
+    closest cloud point with that point's normal (lrf_align_plane_cloud)."""
+    if normals is None:
+        p, symbol, key = N.LrfAlignPlane(), "lrf_align_plane", "face"
+        p.vertices, p.faces, (p.Nv, p.Nf) = index.vertices.data_ptr(), index.faces.data_ptr(), index.counts
+    else:
+        p, symbol, key = N.LrfAlignPlaneCloud(), "lrf_align_plane_cloud", "index"
+        p.normals, p.M = normals.data_ptr(), index.counts[0]
     p.u, p.gate = u, gate
     for k in range(3):
         p.c[k] = c[k]
-    words = torch.empty(max(1, -(-n // PAIRS_PER_CALL)), 48, dtype=torch.int64, device=pts.device)
-    for j, i0 in enumerate(range(0, max(n, 1), PAIRS_PER_CALL)):
-        p.N = min(n, i0 + PAIRS_PER_CALL) - i0
-        p.points, p.closest = pts[i0:].data_ptr(), near["closest"][i0:].data_ptr()
-        p.face, p.distance = near["face"][i0:].data_ptr(), near["distance"][i0:].data_ptr()
-        N.launch("lrf_align_plane", pts.device, C.byref(p), words[j].data_ptr(), guard=True)
-    return words
 
-
-def _plane_cloud_words(index, normals, pts, near, c, u, gate):
-    """_plane_words against a CloudIndex: the plane of a point is the one through its closest cloud point with that point's normal."""
-    n = pts.shape[0]
-    p = N.LrfAlignPlaneCloud()
-    p.normals, p.M = normals.data_ptr(), index.counts[0]
-    p.u, p.gate = u, gate
-    for k in range(3):
-        p.c[k] = c[k]
-    words = torch.empty(max(1, -(-n // PAIRS_PER_CALL)), 48, dtype=torch.int64, device=pts.device)
-    for j, i0 in enumerate(range(0, max(n, 1), PAIRS_PER_CALL)):
-        p.N = min(n, i0 + PAIRS_PER_CALL) - i0
-        p.points, p.closest = pts[i0:].data_ptr(), near["closest"][i0:].data_ptr()
-        p.index, p.distance = near["index"][i0:].data_ptr(), near["distance"][i0:].data_ptr()
-        N.launch("lrf_align_plane_cloud", pts.device, C.byref(p), words[j].data_ptr(), guard=True)
-    return words
+    def launch(i0, m, row):
+        p.N = m
+        p.points, p.closest, p.distance = pts[i0:].data_ptr(), near["closest"][i0:].data_ptr(), near["distance"][i0:].data_ptr()
+        setattr(p, key, near[key][i0:].data_ptr())
+        N.launch(symbol, pts.device, C.byref(p), row, guard=True)
+    return _chunk_words(pts.shape[0], 48, pts.device, launch)
 
 
 def _add_words(host):
@@ -314,21 +307,17 @@ def fit_pairs(a, b, keep=None, scale=True):
     t = mean_b - s R mean_a.  Returns T, scale, rms (the residual after the fit, from the moments, in world units), count, and
     the pairs left out: out_of_range, masked, nonfinite.  ValueError for fewer than 3 kept pairs or a covariance of rank below
     2 (second singular value <= 1e-10 of the first).  Two read-backs: the box, then the words."""
-    n = _check_points(a)
-    if _check_points(b) != n:
+    n = check_points(a)
+    if check_points(b) != n:
         raise ValueError(f"a and b must hold the same number of points, got {n} and {b.shape[0]}")
     _check_keep(keep, n)
     scale = check_flag("scale", scale)
-    N.require_gpu(a, "a", "the alignment")
-    N.require_gpu(b, "b", "the alignment")
-    if keep is not None:
-        N.require_gpu(keep, "keep", "the alignment")
+    a, b = points_on_device(a, "a", "the alignment"), points_on_device(b, "b", "the alignment")
+    keep = None if keep is None else points_on_device(keep, "keep", "the alignment").to(torch.uint8)
     if b.device != a.device or (keep is not None and keep.device != a.device):
         raise ValueError("a, b and keep must live on the same device")
     if n < 3:
         raise ValueError(f"a similarity needs at least 3 kept pairs, got {n}")
-    a, b = a.detach().contiguous(), b.detach().contiguous()
-    keep = None if keep is None else keep.detach().to(torch.uint8).contiguous()
     lo, hi = _finite_box(a, b)                                      # read-back one
     c, h = pair_frame(lo, hi) if all(math.isfinite(x) for x in lo + hi) else ((0.0, 0.0, 0.0), 1.0)
     return solve_pairs(_add_words(_pair_words(c, h, a, b, keep).cpu()), c, h, scale)      # read-back two
@@ -368,7 +357,7 @@ def _check_icp_options(init=None, scale=True, metric="plane", iterations=20, max
     check_flag("scale", scale)
     check_choice("metric", metric, ("plane", "point"))
     check_int("iterations", iterations, 1, 10000)
-    _check_max_distance(max_distance)
+    check_max_distance(max_distance)
     check_interval("tol", tol, 0.0, 1.0, "lie in [0, 1]")
 
 
@@ -376,7 +365,7 @@ def _plane_iteration(index, cur, near, c, u, gate, scale, normals=None):
     """One accumulation and solve of metric="plane" -> (rms, count, the points left out, the step's transform or None, its size,
     the next frame centre).  normals: the target_normals of a CloudIndex.  One read-back: the words and the fp64 sum of the
     closest points in one tensor."""
-    words = _plane_words(index, cur, near, c, u, gate) if normals is None else _plane_cloud_words(index, normals, cur, near, c, u, gate)
+    words = _plane_words(index, cur, near, c, u, gate, normals)
     q = near["closest"].double()
     qsum = torch.where(torch.isfinite(q), q, 0.0).sum(0)
     host = torch.cat([words.reshape(-1), qsum.view(torch.int64)]).cpu()                         # the read-back
@@ -463,33 +452,23 @@ def icp(points, mesh_or_index, init=None, scale=True, metric="plane", iterations
         T = alignment.icp(points, scan, target_normals=normals, scale=False)["T"]
 
     target_normals with a mesh as the target, with metric="point", or of another shape, dtype or device raise ValueError."""
-    def checks():
-        _check_points(points)
-        _check_icp_options(init, scale, metric, iterations, max_distance, tol)
-    if isinstance(mesh_or_index, CloudIndex):
-        checks()
-        if target_normals is not None:
-            _check_target_normals(target_normals, mesh_or_index, metric)
-        elif metric == "plane":
-            raise ValueError('a cloud has no planes: metric="plane" needs a mesh or a MeshIndex as the target; '
-                             'pass metric="point" to align against a CloudIndex')
-        index = mesh_or_index
-    else:
-        def mesh_checks():
-            checks()
-            if target_normals is not None:
-                _check_target_normals(target_normals, mesh_or_index, metric)
-        index = _as_index(mesh_or_index, 1 << 30, mesh_checks)
+    to_cloud = isinstance(mesh_or_index, CloudIndex)
+    if not to_cloud:
+        check_target(mesh_or_index)                                 # the target's type, a mesh dict's tensors
+    check_points(points)
+    _check_icp_options(init, scale, metric, iterations, max_distance, tol)
+    if target_normals is not None:
+        _check_target_normals(target_normals, mesh_or_index, metric)
+    elif to_cloud and metric == "plane":
+        raise ValueError('a cloud has no planes: metric="plane" needs a mesh or a MeshIndex as the target; '
+                         'pass metric="point" to align against a CloudIndex')
+    index = mesh_or_index if to_cloud else as_index(mesh_or_index, 1 << 30)     # a mesh dict: the device, then the index build
     T = np.eye(4) if init is None else _matrix(init)
-    max_distance, tol = _check_max_distance(max_distance), float(tol)
-    N.require_gpu(points, "points", "the alignment")
-    if points.device != index.device:
-        raise ValueError(f"points live on {points.device}, the index on {index.device}")
+    max_distance, tol = check_max_distance(max_distance), float(tol)
+    pts = points_on_device(points, "points", "the alignment", index.device, f"points live on {points.device}, the index on {index.device}")
     out = {"T": T, "iterations": 0, "converged": False, "reason": "degenerate", "rms": math.nan, "count": 0, "history": []}
-    n = points.shape[0]
-    if n < MIN_MATCHES or index.info["box"] is None:
+    if pts.shape[0] < MIN_MATCHES or index.info["box"] is None:
         return out
-    pts = points.detach().contiguous()
     normals = None if target_normals is None else target_normals.detach().contiguous()
     cur = torch.empty_like(pts)
     lo, hi = index.info["box"]
@@ -534,10 +513,7 @@ def align_meshes(a, b, spacing, **icp_options):
         aligned = alignment.align_meshes(mesh, reference, spacing, init=T0, scale=False)["mesh"]
         figures = mesh_distance.mesh_distance(aligned, reference, spacing, thresholds)"""
     check_mesh(a)
-    if not isinstance(b, (dict, MeshIndex)):
-        raise TypeError("b must be a mesh dict or a MeshIndex")
-    if isinstance(b, dict):
-        check_mesh(b)
+    check_target(b, "b")
     check_positive("spacing", spacing)
     unknown = set(icp_options) - {"init", "scale", "metric", "iterations", "max_distance", "tol"}
     if unknown:

@@ -31,13 +31,12 @@ from . import _native as N
 from . import diagnostics
 from ._native import NativeError  # noqa: F401
 from ._checks import INT32 as _INT32
-from ._checks import check_bytes, check_choice, check_flag, check_int, check_origin, check_positive, float_of_key
-from .mesh_distance import (_check_max_distance, _check_points, _check_thresholds, _check_unit, _ratio, _summary, _summary_words,
-                            distance_summary, grid_dims)
+from ._checks import (check_bytes, check_choice, check_flag, check_int, check_max_distance, check_origin, check_points, check_positive,
+                      check_thresholds, check_unit, chunks, points_on_device)
+from .mesh_distance import cell_box, closest_query, decode_bounds, distance_summary, finite_rows, grid_dims, near_summary, two_sided
 
 MAX_K = N.LRF_CLOUD_MAX_K
 NORMAL_LATTICE = 1 << 15                       # lrf_cloud_normals: a neighbour's offset is at most this many lattice steps
-_POINTS_PER_CALL = 1 << 30
 
 
 def default_point_cell(lo, hi, used, max_bytes=1 << 30):
@@ -110,15 +109,14 @@ class CloudIndex:
     the cloud's tensor, not a copy: a cloud changed in place needs a new index.  No result depends on the cell."""
 
     def __init__(self, points, cell=None, max_bytes=1 << 30):
-        M = _check_points(points)
+        M = check_points(points)
         if cell is not None:
             check_positive("cell", cell)
         max_bytes = check_bytes(max_bytes)
         if M > _INT32:
             raise ValueError(f"points holds {M} rows; a cloud index takes M < 2^31")
-        N.require_gpu(points, "points", "the cloud index")
-        dev = points.device
-        pts = points.detach().contiguous()
+        pts = points_on_device(points, "points", "the cloud index")
+        dev = pts.device
         self.points, self.device, self.counts = pts, dev, (M,)
         self._grid = self._records = self._args = None
         self.info = {"cell": None if cell is None else float(cell), "box": None, "dims": (0, 0, 0), "points": 0, "nonfinite_points": 0}
@@ -127,18 +125,13 @@ class CloudIndex:
         out = torch.empty(8, dtype=torch.int64, device=dev)
         N.launch("lrf_cloud_index_bounds", dev, pts.data_ptr(), M, out.data_ptr(), guard=True)
         host = out.cpu()                                            # the read-back
-        counts, keys = host[:4].tolist(), host[4:7].view(torch.int32).tolist()
+        counts, lo, hi = decode_bounds(host)
         used = int(counts[1])
         self.info.update(points=used, nonfinite_points=int(counts[0]))
         if used == 0:
             return
-        lo, hi = tuple(float_of_key(k) for k in keys[:3]), tuple(float_of_key(k) for k in keys[3:6])
         cell = default_point_cell(lo, hi, used, max_bytes) if cell is None else float(cell)
-        dims = grid_dims(lo, hi, cell)
-        cells = dims[0] * dims[1] * dims[2]
-        box = f"the cell box {dims[0]} x {dims[1]} x {dims[2]} of cell {cell} over {lo} .. {hi}"
-        if cells > _INT32:
-            raise ValueError(f"{box} holds {cells} cells; an index takes fewer than 2^31: a larger cell is needed")
+        dims, cells, box = cell_box(lo, hi, cell)
         need = int(N.lib().lrf_cloud_index_workspace_bytes(cells))
         if need == 0:
             raise NativeError(f"lrf_cloud_index: refused shape {(cells,)}")
@@ -159,17 +152,14 @@ class CloudIndex:
         return 0 if self._grid is None else self._grid.numel() + 16 * self._records.shape[0]
 
     def _queries(self, points, exclude_self):
-        n = _check_points(points)
+        n = check_points(points)
         exclude_self = check_flag("exclude_self", exclude_self)
         if exclude_self and n != self.counts[0]:
             raise ValueError(f"exclude_self pairs query i with cloud point i: {n} queries for a cloud of {self.counts[0]} points")
         return n, exclude_self
 
-    def _on_device(self, points):
-        N.require_gpu(points, "points", "the cloud queries")
-        if points.device != self.device:
-            raise ValueError(f"points live on {points.device}, the index on {self.device}")
-        return points.detach().contiguous()
+    def _on_device(self, t, name="points", verb="live"):
+        return points_on_device(t, name, "the cloud queries", self.device, f"{name} {verb} on {t.device}, the index on {self.device}")
 
     def closest(self, points, max_distance=math.inf, closest=False):
         """points [N,3] fp32 on the index's device -> {"distance": [N] fp32, "index": [N] int32[, "closest": [N,3] fp32]} on the
@@ -178,26 +168,8 @@ class CloudIndex:
         any): +inf, -1, NaN.  For a query with a coordinate that is not finite: NaN, -1, NaN.  The result is a function of the
         cloud, the query and max_distance alone: it does not depend on cell, on how the queries are batched or on the stream.
         A query at distance D walks about (2 D / cell)^3 cells, empty or not: give clouds with far outliers a max_distance."""
-        n = _check_points(points)
-        max_distance = _check_max_distance(max_distance)
-        closest = check_flag("closest", closest)
-        pts, dev = self._on_device(points), self.device
-        out = {"distance": torch.empty(n, dtype=torch.float32, device=dev), "index": torch.empty(n, dtype=torch.int32, device=dev)}
-        if closest:
-            out["closest"] = torch.empty(n, 3, dtype=torch.float32, device=dev)
-        if self._grid is None:                                      # no used point: nothing is near
-            finite = torch.isfinite(pts).all(1)
-            out["distance"].copy_(torch.where(finite, math.inf, math.nan))
-            out["index"].fill_(-1)
-            if closest:
-                out["closest"].fill_(math.nan)
-            return out
-        for i0 in range(0, n, _POINTS_PER_CALL):
-            i1 = min(n, i0 + _POINTS_PER_CALL)
-            N.launch("lrf_cloud_closest", dev, C.byref(self._args), pts[i0:].data_ptr(), i1 - i0, max_distance,
-                     out["distance"][i0:].data_ptr(), out["index"][i0:].data_ptr(),
-                     out["closest"][i0:].data_ptr() if closest else None, guard=True)
-        return out
+        return closest_query("lrf_cloud_closest", "index", "the cloud queries", self.device, None if self._grid is None else self._args,
+                             points, max_distance, closest)
 
     def knn(self, points, k, max_distance=math.inf, exclude_self=False):
         """The k nearest used points of the cloud per query point, k in 1..8: {"distance": [N,k] fp32, "index": [N,k] int32},
@@ -207,17 +179,15 @@ class CloudIndex:
         (2 D / cell)^3 cells, empty or not, so give clouds with far outliers a max_distance.  No read-back."""
         n, exclude_self = self._queries(points, exclude_self)
         k = check_int("k", k, 1, MAX_K)
-        max_distance = _check_max_distance(max_distance)
+        max_distance = check_max_distance(max_distance)
         pts, dev = self._on_device(points), self.device
         out = {"distance": torch.empty(n, k, dtype=torch.float32, device=dev), "index": torch.empty(n, k, dtype=torch.int32, device=dev)}
         if self._grid is None:
-            finite = torch.isfinite(pts).all(1, keepdim=True)
-            out["distance"].copy_(torch.where(finite, math.inf, math.nan).expand(n, k))
+            out["distance"].copy_(torch.where(finite_rows(pts)[:, None], math.inf, math.nan).expand(n, k))
             out["index"].fill_(-1)
             return out
-        for i0 in range(0, n, _POINTS_PER_CALL):
-            i1 = min(n, i0 + _POINTS_PER_CALL)
-            N.launch("lrf_cloud_knn", dev, C.byref(self._args), pts[i0:].data_ptr(), i1 - i0, k, max_distance, i0 if exclude_self else -1,
+        for i0, m in chunks(n):
+            N.launch("lrf_cloud_knn", dev, C.byref(self._args), pts[i0:].data_ptr(), m, k, max_distance, i0 if exclude_self else -1,
                      out["distance"][i0:].data_ptr(), out["index"][i0:].data_ptr(), guard=True)
         return out
 
@@ -230,11 +200,10 @@ class CloudIndex:
         pts, dev = self._on_device(points), self.device
         out = torch.empty(n, dtype=torch.int32, device=dev)
         if self._grid is None:
-            out.copy_(torch.where(torch.isfinite(pts).all(1), 0, -1))
+            out.copy_(torch.where(finite_rows(pts), 0, -1))
             return out
-        for i0 in range(0, n, _POINTS_PER_CALL):
-            i1 = min(n, i0 + _POINTS_PER_CALL)
-            N.launch("lrf_cloud_radius_count", dev, C.byref(self._args), pts[i0:].data_ptr(), i1 - i0, radius, i0 if exclude_self else -1,
+        for i0, m in chunks(n):
+            N.launch("lrf_cloud_radius_count", dev, C.byref(self._args), pts[i0:].data_ptr(), m, radius, i0 if exclude_self else -1,
                      out[i0:].data_ptr(), guard=True)
         return out
 
@@ -250,7 +219,7 @@ class CloudIndex:
         where the viewpoint lies exactly in the normal's plane, the component of largest magnitude is made positive.
         Fewer than min_neighbours (>= 3) neighbours, or neighbours that all coincide: normal (0, 0, 0) and the true count.  A
         query that is not finite: NaN, NaN, -1.  radius is finite and > 0, best given in units of nearest_spacing."""
-        return self._normals(points, _check_points(points), radius, min_neighbours, viewpoint)
+        return self._normals(points, check_points(points), radius, min_neighbours, viewpoint)
 
     def _normals(self, points, n, radius, min_neighbours, viewpoint):
         """normals() for checked points, or with points=None for the cloud's own n = M points walked in record order."""
@@ -262,16 +231,13 @@ class CloudIndex:
         pts = self._on_device(self.points if points is None else points)
         view, stride = None, 0
         if torch.is_tensor(viewpoint):
-            N.require_gpu(viewpoint, "viewpoint", "the cloud queries")
-            if viewpoint.device != dev:
-                raise ValueError(f"viewpoint lives on {viewpoint.device}, the index on {dev}")
-            view, stride = viewpoint.detach().contiguous(), 3
+            view, stride = self._on_device(viewpoint, "viewpoint", "lives"), 3
         elif viewpoint is not None:
             view = torch.tensor(viewpoint, dtype=torch.float32).to(dev)
         out = {"normals": torch.empty(n, 3, dtype=torch.float32, device=dev), "eigenvalues": torch.empty(n, 3, dtype=torch.float32, device=dev),
                "count": torch.empty(n, dtype=torch.int32, device=dev)}
         if self._grid is None:                                      # no used point: no neighbour
-            finite = torch.isfinite(pts).all(1)
+            finite = finite_rows(pts)
             out["normals"].copy_(torch.where(finite, 0.0, math.nan)[:, None].expand(n, 3))
             out["eigenvalues"].copy_(out["normals"])
             out["count"].copy_(torch.where(finite, 0, -1))
@@ -280,9 +246,8 @@ class CloudIndex:
             N.launch("lrf_cloud_normals", dev, C.byref(self._args), None, n, radius, h, min_neighbours, None if view is None else view.data_ptr(),
                      stride, out["normals"].data_ptr(), out["eigenvalues"].data_ptr(), out["count"].data_ptr(), guard=True)
             return out
-        for i0 in range(0, n, _POINTS_PER_CALL):
-            i1 = min(n, i0 + _POINTS_PER_CALL)
-            N.launch("lrf_cloud_normals", dev, C.byref(self._args), pts[i0:].data_ptr(), i1 - i0, radius, h, min_neighbours,
+        for i0, m in chunks(n):
+            N.launch("lrf_cloud_normals", dev, C.byref(self._args), pts[i0:].data_ptr(), m, radius, h, min_neighbours,
                      None if view is None else (view[i0:] if stride else view).data_ptr(), stride, out["normals"][i0:].data_ptr(),
                      out["eigenvalues"][i0:].data_ptr(), out["count"][i0:].data_ptr(), guard=True)
         return out
@@ -298,21 +263,16 @@ def voxel_downsample(points, cell, origin=(0.0, 0.0, 0.0), rgb8=None, max_bytes=
     bad_points}.  The bytes of points, rgb8 and count do not depend on the order of the input.  Two read-backs: the bounds pass
     (a cell box of 2^31 cells or more, or a workspace above max_bytes, raises ValueError before anything is summed), then the
     number of clusters; the outputs are allocated at M rows and sliced."""
-    M = _check_points(points)
+    M = check_points(points)
     cell = check_positive("cell", cell)
     origin = check_origin(origin)
     _check_colours("rgb8", rgb8, M, torch.uint8, "uint8")
     max_bytes = check_bytes(max_bytes)
     if M > _INT32:
         raise ValueError(f"points holds {M} rows; a voxel grid takes M < 2^31")
-    N.require_gpu(points, "points", "the voxel grid")
-    dev = points.device
-    if rgb8 is not None:
-        N.require_gpu(rgb8, "rgb8", "the voxel grid")
-        if rgb8.device != dev:
-            raise ValueError("points and rgb8 must live on the same device")
-    pts = points.detach().contiguous()
-    col = None if rgb8 is None else rgb8.contiguous()
+    pts = points_on_device(points, "points", "the voxel grid")
+    dev = pts.device
+    col = None if rgb8 is None else points_on_device(rgb8, "rgb8", "the voxel grid", dev, "points and rgb8 must live on the same device")
     info = {"cell": cell, "origin": origin, "box": {"lo": (0, 0, 0), "dims": (0, 0, 0)}, "points": 0, "bad_points": 0}
     out = {"points": pts[:0], "count": torch.empty(0, dtype=torch.int32, device=dev),
            "cluster_of": torch.full((M,), -1, dtype=torch.int32, device=dev), "counts": (0,), "info": info}
@@ -357,7 +317,8 @@ def voxel_downsample(points, cell, origin=(0.0, 0.0, 0.0), rgb8=None, max_bytes=
     return out
 
 
-def _as_cloud_index(cloud_or_index, max_bytes, name="cloud_or_index"):
+def as_cloud_index(cloud_or_index, max_bytes, name="cloud_or_index"):
+    """The target as a CloudIndex, after the caller's other checks: built here (its checks, the device, launches) unless it is one."""
     if isinstance(cloud_or_index, CloudIndex):
         return cloud_or_index
     if not torch.is_tensor(cloud_or_index):
@@ -372,14 +333,14 @@ def nearest_spacing(points_or_index, max_bytes=1 << 30):
     distances}; NaN, NaN, 0 for a cloud with fewer than two used points.  Every threshold of this module is best chosen in
     these units."""
     check_bytes(max_bytes)
-    index = _as_cloud_index(points_or_index, max_bytes, "points_or_index")
+    index = as_cloud_index(points_or_index, max_bytes, "points_or_index")
     d = index.knn(index.points, 1, exclude_self=True)["distance"].reshape(-1)
     d = d[torch.isfinite(d)]
     if d.numel() == 0:
         return {"mean": math.nan, "median": math.nan, "count": 0}
     median = float(diagnostics.median(d))
     unit = median if math.isfinite(median) and median > 0 else 1.0
-    s = distance_summary(d, (), _check_unit(unit))
+    s = distance_summary(d, (), check_unit(unit))
     return {"mean": s["mean"], "median": median, "count": s["finite"]}
 
 
@@ -402,14 +363,14 @@ def estimate_normals(points_or_index, radius, min_neighbours=6, viewpoint=None, 
     if not isinstance(points_or_index, CloudIndex):
         if not torch.is_tensor(points_or_index):
             raise TypeError("points_or_index must be a [M, 3] float32 tensor or a CloudIndex")
-        _check_points(points_or_index)
+        check_points(points_or_index)
     m = points_or_index.counts[0] if isinstance(points_or_index, CloudIndex) else int(points_or_index.shape[0])
     normal_lattice(check_positive("radius", radius))
     check_int("min_neighbours", min_neighbours, 3, _INT32, "an integer in [3, 2^31)")
     _check_viewpoint(viewpoint, m)
     check_bytes(max_bytes)
     check_choice("order", order, NORMAL_ORDERS)
-    index = _as_cloud_index(points_or_index, max_bytes, "points_or_index")
+    index = as_cloud_index(points_or_index, max_bytes, "points_or_index")
     out = index._normals(None if order == "records" else index.points, m, radius, min_neighbours, viewpoint)
     e = out["eigenvalues"]
     total = e.sum(1)
@@ -422,7 +383,7 @@ def remove_outliers(points, radius, min_neighbours, rgb8=None, normals=None, ind
     (radius_count with exclude_self; the boundary counts).  A point that is not finite goes.  Survivors stay in input order.
     index: a CloudIndex of these very points, which is then not built again.  Returns {"points", "rgb8" and "normals" where
     given, "keep": bool [M], "counts": (kept,)}.  One read-back: the number kept."""
-    M = _check_points(points)
+    M = check_points(points)
     radius = _check_radius(radius)
     min_neighbours = check_int("min_neighbours", min_neighbours, 0, _INT32, "an integer in [0, 2^31)")
     _check_colours("rgb8", rgb8, M, torch.uint8, "uint8")
@@ -432,19 +393,13 @@ def remove_outliers(points, radius, min_neighbours, rgb8=None, normals=None, ind
             raise TypeError("index must be a CloudIndex or None")
         if index.counts != (M,):
             raise ValueError(f"index was built over {index.counts[0]} points, points holds {M}")
-    N.require_gpu(points, "points", "the outlier removal")
-    for name, t in (("rgb8", rgb8), ("normals", normals)):
-        if t is not None:
-            N.require_gpu(t, name, "the outlier removal")
-            if t.device != points.device:
-                raise ValueError(f"points and {name} must live on the same device")
-    index = CloudIndex(points) if index is None else index
-    keep = index.radius_count(points, radius, exclude_self=True) >= max(min_neighbours, 0)
-    out = {"points": points.detach()[keep], "keep": keep}
-    if rgb8 is not None:
-        out["rgb8"] = rgb8[keep]
-    if normals is not None:
-        out["normals"] = normals.detach()[keep]
+    pts = points_on_device(points, "points", "the outlier removal")
+    rows = {name: points_on_device(t, name, "the outlier removal", pts.device, f"points and {name} must live on the same device")
+            for name, t in (("rgb8", rgb8), ("normals", normals)) if t is not None}
+    index = CloudIndex(pts) if index is None else index
+    keep = index.radius_count(pts, radius, exclude_self=True) >= max(min_neighbours, 0)
+    out = {"points": pts[keep], "keep": keep}
+    out.update({name: t[keep] for name, t in rows.items()})
     out["counts"] = (int(out["points"].shape[0]),)
     return out
 
@@ -454,19 +409,12 @@ def cloud_to_cloud(points, cloud_or_index, thresholds=(), max_distance=math.inf,
     CloudIndex.closest and distance_summary; mesh_distance.cloud_to_mesh's twin.  unit defaults to max_distance when that is
     finite and > 0, else 1.0.  Returns distance_summary's dict plus "distance" and "index" on the device.  With a
     reconstruction's cloud and a reference scan, mean is the accuracy; the other way round, the completeness."""
-    _check_points(points)
-    taus, max_distance = _check_thresholds(thresholds), _check_max_distance(max_distance)
+    check_points(points)
+    taus, max_distance = check_thresholds(thresholds), check_max_distance(max_distance)
     if unit is not None:
-        _check_unit(unit)
+        check_unit(unit)
     check_bytes(max_bytes)
-    index = _as_cloud_index(cloud_or_index, max_bytes)
-    if unit is None:
-        unit = max_distance if math.isfinite(max_distance) and max_distance > 0 else 1.0
-    unit = _check_unit(unit)
-    near = index.closest(points, max_distance)
-    out = _summary(_summary_words(near["distance"], taus, unit).tolist(), taus, unit)
-    out.update(distance=near["distance"], index=near["index"])
-    return out
+    return near_summary(as_cloud_index(cloud_or_index, max_bytes), "index", points, taus, max_distance, unit)
 
 
 def cloud_distance(a, b, thresholds=(), max_distance=math.inf, voxel=None, max_bytes=1 << 30):
@@ -478,25 +426,17 @@ def cloud_distance(a, b, thresholds=(), max_distance=math.inf, voxel=None, max_b
     on the host from the integer counts, NaN where undefined; thresholds; and samples = (points of a, points of b) that were
     queried.  With a the reconstruction and b the reference scan these are the figures of the reconstruction benchmarks.  The
     same integers on every run, and with voxel for every order of the points of either cloud."""
-    _check_points(a)
-    _check_points(b)
-    taus, max_distance = _check_thresholds(thresholds), _check_max_distance(max_distance)
+    check_points(a)
+    check_points(b)
+    taus, max_distance = check_thresholds(thresholds), check_max_distance(max_distance)
     if voxel is not None:
         check_positive("voxel", voxel)
     check_bytes(max_bytes)
     if voxel is not None:
         a, b = (voxel_downsample(x, voxel, max_bytes=max_bytes)["points"] for x in (a, b))
-    sides = {}
-    for name, src, dst in (("a_to_b", a, b), ("b_to_a", b, a)):
+
+    def side(src, dst):
         r = cloud_to_cloud(src, dst, taus, max_distance, None, max_bytes)
         del r["distance"], r["index"]
-        sides[name] = r
-    ab, ba = sides["a_to_b"], sides["b_to_a"]
-    n_a, n_b = ab["finite"] + ab["beyond"], ba["finite"] + ba["beyond"]
-    maxima = [s["max"] for s in (ab, ba) if s["finite"]]
-    precision = tuple(_ratio(w, n_a) for w in ab["within"])
-    recall = tuple(_ratio(w, n_b) for w in ba["within"])
-    fscore = tuple(2 * p * r / (p + r) if p + r > 0 else math.nan for p, r in zip(precision, recall))
-    return {"a_to_b": ab, "b_to_a": ba, "chamfer": ab["mean"] + ba["mean"], "hausdorff": max(maxima) if maxima else math.nan,
-            "precision": precision, "recall": recall, "fscore": fscore, "thresholds": tuple(taus),
-            "samples": (ab["finite"] + ab["beyond"] + ab["nan"], ba["finite"] + ba["beyond"] + ba["nan"])}
+        return r
+    return two_sided(side(a, b), side(b, a), taus)

@@ -10,6 +10,8 @@ how a scene_point_cloud and a scene_mesh agree, how a reconstruction scores agai
   distance_summary(distance, thresholds, unit)   integer counts and sums of a distance tensor
   cloud_to_mesh(points, mesh_or_index, ...)      closest + distance_summary
   mesh_distance(a, b, spacing, ...)              both directions: Chamfer, Hausdorff, precision / recall / F-score
+  decode_bounds, cell_box, closest_query, finite_rows, near_summary, two_sided    what cloud.CloudIndex and cloud's figures share
+  check_target, as_index                         a mesh dict or a MeshIndex as the target: host checks, then the build
 
 A module of its own rather than part of mesh.py for the reason mesh_raster.py is one: it consumes meshes, it does not make them.
 A mesh is the dict of mesh.py.  Unsigned distance.  The same bytes and the same integers on every run.  Every function checks
@@ -24,59 +26,16 @@ import torch
 from . import _native as N
 from ._native import NativeError  # noqa: F401
 from ._checks import INT32 as _INT32
-from ._checks import check_bytes, check_flag, check_int, check_mesh, check_positive, float_of_key, mesh_on_device
+from ._checks import (check_bytes, check_flag, check_int, check_max_distance, check_mesh, check_points, check_positive, check_thresholds,
+                      check_unit, chunks, float_of_key, mesh_on_device, points_on_device)
 
 DISTANCE_SCALE = 1 << 24                       # the fixed point of the two sums
 DISTANCE_CLAMP = 8.0                           # a distance enters the sums as min(d / unit, this)
 MAX_FACE_SAMPLES = 1 << 21                     # samples one face may take
-_POINTS_PER_CALL = 1 << 30
-
-
-def _check_max_distance(max_distance):
-    try:
-        ok = not isinstance(max_distance, (bool, np.bool_)) and float(max_distance) >= 0        # NaN fails
-    except (TypeError, ValueError, OverflowError):
-        ok = False
-    if not ok:
-        raise ValueError(f"max_distance must be a number >= 0 or infinity, got {max_distance!r}")
-    return float(max_distance)
-
-
-def _check_thresholds(thresholds):
-    try:
-        taus = [float(t) for t in thresholds if not isinstance(t, (bool, np.bool_))]
-        ok = len(taus) == len(thresholds)
-    except (TypeError, ValueError, OverflowError):
-        taus, ok = [], False
-    if not ok:
-        raise ValueError(f"thresholds must be a sequence of numbers, got {thresholds!r}")
-    if len(taus) > N.LRF_DISTANCE_MAX_THRESHOLDS:
-        raise ValueError(f"at most {N.LRF_DISTANCE_MAX_THRESHOLDS} thresholds, got {len(taus)}")
-    if not all(math.isfinite(t) and t > 0 for t in taus):
-        raise ValueError(f"every threshold must be a finite number > 0, got {thresholds!r}")
-    taus = [float(np.float32(t)) for t in taus]                     # the kernel compares in fp32
-    if not all(math.isfinite(t) and t > 0 for t in taus):
-        raise ValueError(f"every threshold must be finite and > 0 as float32, got {thresholds!r}")
-    return taus
-
-
-def _check_unit(unit):
-    unit = check_positive("unit", unit)
-    if not (math.isfinite(float(np.float32(unit))) and float(np.float32(unit)) > 0):
-        raise ValueError(f"unit must be finite and > 0 as float32, got {unit!r}")
-    return unit
 
 
 def _check_count(max_points):
     return check_int("max_points", max_points, 0, _INT32, "an integer in [0, 2^31)")
-
-
-def _check_points(points):
-    if not torch.is_tensor(points):
-        raise TypeError("points must be a torch tensor")
-    if points.dtype is not torch.float32 or points.dim() != 2 or points.shape[1] != 3:
-        raise ValueError(f"points must be [N, 3] float32, got {points.dtype} {tuple(points.shape)}")
-    return int(points.shape[0])
 
 
 def default_cell(lo, hi, used_faces):
@@ -95,6 +54,50 @@ def default_cell(lo, hi, used_faces):
 def grid_dims(lo, hi, cell):
     """The cells per axis of the box at this cell edge: floor((hi - lo) / cell) + 1 in fp64."""
     return tuple(int(math.floor((h - l) / cell)) + 1 for l, h in zip(lo, hi))
+
+
+def decode_bounds(host):
+    """The 8 int64 words a bounds pass wrote, read back -> (its four counts, lo, hi): the box as Python floats."""
+    counts, keys = host[:4].tolist(), host[4:7].view(torch.int32).tolist()
+    return counts, tuple(float_of_key(k) for k in keys[:3]), tuple(float_of_key(k) for k in keys[3:6])
+
+
+def cell_box(lo, hi, cell):
+    """-> (dims, cells, the words that name the cell box in a refusal); ValueError for a box of 2^31 cells or more."""
+    dims = grid_dims(lo, hi, cell)
+    cells = dims[0] * dims[1] * dims[2]
+    box = f"the cell box {dims[0]} x {dims[1]} x {dims[2]} of cell {cell} over {lo} .. {hi}"
+    if cells > _INT32:
+        raise ValueError(f"{box} holds {cells} cells; an index takes fewer than 2^31: a larger cell is needed")
+    return dims, cells, box
+
+
+def finite_rows(pts):
+    """bool [N] on the device: the rows of pts [N,3] without a coordinate that is not finite."""
+    return torch.isfinite(pts).all(1)
+
+
+def closest_query(symbol, key, feature, dev, args, points, max_distance, closest):
+    """closest() of MeshIndex (lrf_mesh_closest, "face") and of cloud.CloudIndex (lrf_cloud_closest, "index"): the checks, the
+    device, and one launch per chunk.  args: the index's struct, None for an index that holds nothing -- then nothing is near,
+    and nothing is launched."""
+    n = check_points(points)
+    max_distance = check_max_distance(max_distance)
+    closest = check_flag("closest", closest)
+    pts = points_on_device(points, "points", feature, dev, f"points live on {points.device}, the index on {dev}")
+    out = {"distance": torch.empty(n, dtype=torch.float32, device=dev), key: torch.empty(n, dtype=torch.int32, device=dev)}
+    if closest:
+        out["closest"] = torch.empty(n, 3, dtype=torch.float32, device=dev)
+    if args is None:
+        out["distance"].copy_(torch.where(finite_rows(pts), math.inf, math.nan))
+        out[key].fill_(-1)
+        if closest:
+            out["closest"].fill_(math.nan)
+        return out
+    for i0, m in chunks(n):
+        N.launch(symbol, dev, C.byref(args), pts[i0:].data_ptr(), m, max_distance, out["distance"][i0:].data_ptr(), out[key][i0:].data_ptr(),
+                 out["closest"][i0:].data_ptr() if closest else None, guard=True)
+    return out
 
 
 class MeshIndex:
@@ -122,17 +125,12 @@ class MeshIndex:
         out = torch.empty(8, dtype=torch.int64, device=dev)
         N.launch("lrf_mesh_index_bounds", dev, v.data_ptr(), f.data_ptr(), Nv, Nf, out.data_ptr(), guard=True)
         host = out.cpu()                                            # read-back one
-        counts, keys = host[:4].tolist(), host[4:7].view(torch.int32).tolist()
+        counts, lo, hi = decode_bounds(host)
         self.info.update(bad_index_faces=int(counts[0]), nonfinite_faces=int(counts[1]), used_faces=int(counts[2]))
         if counts[2] == 0:
             return
-        lo, hi = tuple(float_of_key(k) for k in keys[:3]), tuple(float_of_key(k) for k in keys[3:6])
         cell = default_cell(lo, hi, int(counts[2])) if cell is None else float(cell)
-        dims = grid_dims(lo, hi, cell)
-        cells = dims[0] * dims[1] * dims[2]
-        box = f"the cell box {dims[0]} x {dims[1]} x {dims[2]} of cell {cell} over {lo} .. {hi}"
-        if cells > _INT32:
-            raise ValueError(f"{box} holds {cells} cells; an index takes fewer than 2^31: a larger cell is needed")
+        dims, cells, box = cell_box(lo, hi, cell)
         need = int(N.lib().lrf_mesh_index_workspace_bytes(cells))
         if need == 0:
             raise NativeError(f"lrf_mesh_index: refused shape {(cells,)}")
@@ -168,30 +166,8 @@ class MeshIndex:
         +inf, -1, NaN.  For a point with a coordinate that is not finite: NaN, -1, NaN.  The result is a function of the mesh,
         the point and max_distance alone: it does not depend on cell, on how the points are batched or on the stream.  A point at
         distance D walks about (2 D / cell)^3 cells, empty or not: give clouds with far outliers a max_distance."""
-        n = _check_points(points)
-        max_distance = _check_max_distance(max_distance)
-        closest = check_flag("closest", closest)
-        N.require_gpu(points, "points", "the mesh distance")
-        dev = self.device
-        if points.device != dev:
-            raise ValueError(f"points live on {points.device}, the index on {dev}")
-        pts = points.detach().contiguous()
-        out = {"distance": torch.empty(n, dtype=torch.float32, device=dev), "face": torch.empty(n, dtype=torch.int32, device=dev)}
-        if closest:
-            out["closest"] = torch.empty(n, 3, dtype=torch.float32, device=dev)
-        if self._grid is None:                                      # no used face: nothing is near
-            finite = torch.isfinite(pts).all(1)
-            out["distance"].copy_(torch.where(finite, math.inf, math.nan))
-            out["face"].fill_(-1)
-            if closest:
-                out["closest"].fill_(math.nan)
-            return out
-        for i0 in range(0, n, _POINTS_PER_CALL):
-            i1 = min(n, i0 + _POINTS_PER_CALL)
-            N.launch("lrf_mesh_closest", dev, C.byref(self._args), pts[i0:].data_ptr(), i1 - i0, max_distance,
-                     out["distance"][i0:].data_ptr(), out["face"][i0:].data_ptr(),
-                     out["closest"][i0:].data_ptr() if closest else None, guard=True)
-        return out
+        return closest_query("lrf_mesh_closest", "face", "the mesh distance", self.device, None if self._grid is None else self._args,
+                             points, max_distance, closest)
 
 
 def sample_surface(mesh, spacing, max_points=1 << 26):
@@ -267,21 +243,35 @@ def distance_summary(distance, thresholds=(), unit=1.0):
     that distances stay below 8 units -- cloud_to_mesh takes max_distance -- or mean and rms saturate.  All integers: the same
     on every run.  One read-back.  diagnostics.quantile takes exact medians and other quantiles of the same tensor."""
     _check_distance(distance)
-    taus = _check_thresholds(thresholds)
-    unit = _check_unit(unit)
+    taus = check_thresholds(thresholds)
+    unit = check_unit(unit)
     N.require_gpu(distance, "distance", "the distance summary")
     return _summary(_summary_words(distance, taus, unit).tolist(), taus, unit)     # the read-back
 
 
-def _as_index(mesh_or_index, max_bytes, checks, name="mesh_or_index"):
-    if isinstance(mesh_or_index, MeshIndex):
-        checks()
-        return mesh_or_index
-    if not isinstance(mesh_or_index, dict):
-        raise TypeError(f"{name} must be a mesh dict or a MeshIndex")
-    check_mesh(mesh_or_index)
-    checks()
-    return MeshIndex(mesh_or_index, max_bytes=max_bytes)
+def check_target(mesh_or_index, name="mesh_or_index"):
+    """The host half of as_index, before the caller's other checks: a MeshIndex passes, a mesh dict goes through check_mesh."""
+    if not isinstance(mesh_or_index, MeshIndex):
+        if not isinstance(mesh_or_index, dict):
+            raise TypeError(f"{name} must be a mesh dict or a MeshIndex")
+        check_mesh(mesh_or_index)
+
+
+def as_index(mesh_or_index, max_bytes):
+    """The checked target as a MeshIndex, after the caller's other checks: built here (device check, launches) unless it is one."""
+    return mesh_or_index if isinstance(mesh_or_index, MeshIndex) else MeshIndex(mesh_or_index, max_bytes=max_bytes)
+
+
+def near_summary(index, key, points, taus, max_distance, unit):
+    """What cloud_to_mesh and cloud.cloud_to_cloud share after their checks: the unit's default, index.closest and
+    distance_summary's dict with "distance" and the index's `key` ("face", "index") carried along."""
+    if unit is None:
+        unit = max_distance if math.isfinite(max_distance) and max_distance > 0 else 1.0
+    unit = check_unit(unit)
+    near = index.closest(points, max_distance)
+    out = _summary(_summary_words(near["distance"], taus, unit).tolist(), taus, unit)
+    out.update({"distance": near["distance"], key: near[key]})
+    return out
 
 
 def cloud_to_mesh(points, mesh_or_index, thresholds=(), max_distance=math.inf, unit=None, max_bytes=1 << 30):
@@ -289,26 +279,30 @@ def cloud_to_mesh(points, mesh_or_index, thresholds=(), max_distance=math.inf, u
     MeshIndex.closest and distance_summary.  unit defaults to max_distance when that is finite and > 0, else 1.0.  Returns
     distance_summary's dict plus "distance" and "face" on the device.  With a reconstruction's cloud and a reference mesh,
     mean is the accuracy; with the reference's cloud and the reconstruction's mesh, the completeness."""
-    def checks():
-        _check_points(points)
-        _check_thresholds(thresholds)
-        _check_max_distance(max_distance)
-        if unit is not None:
-            _check_unit(unit)
-        check_bytes(max_bytes)
-    index = _as_index(mesh_or_index, max_bytes, checks)
-    taus, max_distance = _check_thresholds(thresholds), _check_max_distance(max_distance)
-    if unit is None:
-        unit = max_distance if math.isfinite(max_distance) and max_distance > 0 else 1.0
-    unit = _check_unit(unit)
-    near = index.closest(points, max_distance)
-    out = _summary(_summary_words(near["distance"], taus, unit).tolist(), taus, unit)
-    out.update(distance=near["distance"], face=near["face"])
-    return out
+    check_target(mesh_or_index)
+    check_points(points)
+    taus, max_distance = check_thresholds(thresholds), check_max_distance(max_distance)
+    if unit is not None:
+        check_unit(unit)
+    check_bytes(max_bytes)
+    return near_summary(as_index(mesh_or_index, max_bytes), "face", points, taus, max_distance, unit)
 
 
 def _ratio(a, b):
     return a / b if b else math.nan
+
+
+def two_sided(ab, ba, taus):
+    """The two one-sided summaries (distance_summary's dicts) of a compared with b -> the dict mesh_distance and
+    cloud.cloud_distance return, formed on the host from the integer counts."""
+    n_a, n_b = ab["finite"] + ab["beyond"], ba["finite"] + ba["beyond"]
+    maxima = [s["max"] for s in (ab, ba) if s["finite"]]
+    precision = tuple(_ratio(w, n_a) for w in ab["within"])
+    recall = tuple(_ratio(w, n_b) for w in ba["within"])
+    fscore = tuple(2 * p * r / (p + r) if p + r > 0 else math.nan for p, r in zip(precision, recall))
+    return {"a_to_b": ab, "b_to_a": ba, "chamfer": ab["mean"] + ba["mean"], "hausdorff": max(maxima) if maxima else math.nan,
+            "precision": precision, "recall": recall, "fscore": fscore, "thresholds": tuple(taus),
+            "samples": (ab["finite"] + ab["beyond"] + ab["nan"], ba["finite"] + ba["beyond"] + ba["nan"])}
 
 
 def mesh_distance(a, b, spacing, thresholds=(), max_distance=math.inf, max_bytes=1 << 30, max_points=1 << 26):
@@ -319,28 +313,16 @@ def mesh_distance(a, b, spacing, thresholds=(), max_distance=math.inf, max_bytes
     b), recall (b's within it of a) and fscore = 2 p r / (p + r), formed on the host from the integer counts, NaN where
     undefined; and samples = (M_a, M_b).  With a the reconstruction and b the reference these are the figures of the
     reconstruction benchmarks.  The same integers on every run, and for every order of the faces of either mesh."""
-    def checks():
-        check_positive("spacing", spacing)
-        _check_thresholds(thresholds)
-        _check_max_distance(max_distance)
-        check_bytes(max_bytes)
-        _check_count(max_points)
     check_mesh(a)
     check_mesh(b)
-    checks()
-    taus = _check_thresholds(thresholds)
-    sides = {}
-    for name, src, dst in (("a_to_b", a, b), ("b_to_a", b, a)):
-        s = sample_surface(src, spacing, max_points)
-        r = cloud_to_mesh(s["points"], dst, taus, max_distance, None, max_bytes)
+    check_positive("spacing", spacing)
+    taus = check_thresholds(thresholds)
+    check_max_distance(max_distance)
+    check_bytes(max_bytes)
+    _check_count(max_points)
+
+    def side(src, dst):
+        r = cloud_to_mesh(sample_surface(src, spacing, max_points)["points"], dst, taus, max_distance, None, max_bytes)
         del r["distance"], r["face"]
-        sides[name] = r
-    ab, ba = sides["a_to_b"], sides["b_to_a"]
-    n_a, n_b = ab["finite"] + ab["beyond"], ba["finite"] + ba["beyond"]
-    maxima = [s["max"] for s in (ab, ba) if s["finite"]]
-    precision = tuple(_ratio(w, n_a) for w in ab["within"])
-    recall = tuple(_ratio(w, n_b) for w in ba["within"])
-    fscore = tuple(2 * p * r / (p + r) if p + r > 0 else math.nan for p, r in zip(precision, recall))
-    return {"a_to_b": ab, "b_to_a": ba, "chamfer": ab["mean"] + ba["mean"], "hausdorff": max(maxima) if maxima else math.nan,
-            "precision": precision, "recall": recall, "fscore": fscore, "thresholds": tuple(taus),
-            "samples": (ab["finite"] + ab["beyond"] + ab["nan"], ba["finite"] + ba["beyond"] + ba["nan"])}
+        return r
+    return two_sided(side(a, b), side(b, a), taus)

@@ -76,7 +76,7 @@ def main():
     alignment._transform_into(src, T, cur)
     near = index.closest(cur, reach, closest=True)
     keep = (near["distance"] <= reach).to(torch.uint8)
-    words = alignment._plane_cloud_words(index, normals, cur, near, c, u, reach)
+    words = alignment._plane_words(index, cur, near, c, u, reach, normals)
 
     def back():
         torch.cuda.synchronize()
@@ -88,7 +88,7 @@ def main():
     say(f"icp: source {n} points, max_distance {reach:.6f} (16 spacings)")
     rows = [("transform (lrf_align_transform)", lambda: alignment._transform_into(src, T, cur)),
             ("closest (lrf_cloud_closest, closest=True)", lambda: index.closest(cur, reach, closest=True)),
-            ("accumulate, plane (lrf_align_plane_cloud)", lambda: alignment._plane_cloud_words(index, normals, cur, near, c, u, reach)),
+            ("accumulate, plane (lrf_align_plane_cloud)", lambda: alignment._plane_words(index, cur, near, c, u, reach, normals)),
             ("accumulate, point (lrf_align_pairs)", lambda: alignment._pair_words(c0, h0, cur, near["closest"], keep)),
             ("icp, one iteration, plane (whole call)", lambda: alignment.icp(src, index, iterations=1, max_distance=reach, scale=False, target_normals=normals)),
             ("icp, one iteration, point (whole call)", lambda: alignment.icp(src, index, iterations=1, max_distance=reach, scale=False, metric="point"))]

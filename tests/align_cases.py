@@ -13,7 +13,7 @@ import math
 
 import numpy as np
 
-from mesh_distance_cases import closest_from_pairs, pair_host, used_faces
+from mesh_distance_cases import _cross, _dot, closest_from_pairs, pair_host, used_faces
 from mesh_raster_cases import octa_sphere
 
 F32, F64 = np.float32, np.float64
@@ -156,15 +156,6 @@ def pair_inputs(seed, n, c=(0.25, -0.5, 1.0), h=2.0 ** -18):
 
 
 # ------------------------------------------------------------------------------------------------ item 3
-def _dot(a, b):
-    return (a[..., 0] * b[..., 0] + a[..., 1] * b[..., 1]) + a[..., 2] * b[..., 2]
-
-
-def _cross(a, b):
-    return np.stack([a[..., 1] * b[..., 2] - a[..., 2] * b[..., 1], a[..., 2] * b[..., 0] - a[..., 0] * b[..., 2],
-                     a[..., 0] * b[..., 1] - a[..., 1] * b[..., 0]], -1)
-
-
 def plane_host(mesh, points, closest, face, distance, c, u, gate):
     """-> the 48 words as Python integers."""
     p, q = np.asarray(points, F32).reshape(-1, 3), np.asarray(closest, F32).reshape(-1, 3)

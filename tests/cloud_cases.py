@@ -7,6 +7,7 @@ import math
 
 import numpy as np
 
+from mesh_distance_cases import dims_host
 from mesh_simplify_cases import Q_ONE, cells_host
 
 F32 = np.float32
@@ -92,10 +93,6 @@ def box_host(cloud):
     if not u.shape[0]:
         return None
     return tuple(float(x) + 0.0 for x in u.min(0)), tuple(float(x) + 0.0 for x in u.max(0))
-
-
-def dims_host(lo, hi, cell):
-    return tuple(int(math.floor((h - l) / cell)) + 1 for l, h in zip(lo, hi))
 
 
 def default_point_cell_host(lo, hi, used, max_bytes=1 << 30):

@@ -40,6 +40,17 @@ def bits(a):
     return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
+def same_bits(a, b):
+    """Two device tensors, or two dicts of them, exact: keys, shapes, dtypes, integers, and fp32 as its 32-bit words."""
+    if isinstance(a, dict):
+        assert set(a) == set(b)
+        for k in a:
+            same_bits(a[k], b[k])
+        return
+    assert a.shape == b.shape and a.dtype is b.dtype
+    assert torch.equal(a.view(torch.int32) if a.dtype is torch.float32 else a, b.view(torch.int32) if b.dtype is torch.float32 else b)
+
+
 def same_mesh(got, want):
     """A device mesh against a host expectation: counts, shapes, dtypes, vertices (as uint32), faces and rgb8, all exact."""
     assert got["counts"] == want["counts"], (got["counts"], want["counts"])

@@ -1,13 +1,14 @@
-"""The shared argument checks of the geometry modules (localrf_amd/_checks.py) and the frame batcher of
-pointcloud.SceneFrames, without a GPU: a table of accepted edge values and refused values per validator, the batches of a CPU
-scene with the renderers replaced by recorders, and the order "other arguments, then the device" in one caller per module."""
+"""The shared argument checks of the geometry modules (localrf_amd/_checks.py), the frame batcher of pointcloud.SceneFrames
+and the batcher of the launches over points, without a GPU: a table of accepted edge values and refused values per validator,
+the batches of a CPU scene with the renderers replaced by recorders, the chunks of a launch over points with the launch replaced
+by a recorder, and the order "other arguments, then the device" in one caller per module."""
 import math
 
 import numpy as np
 import pytest
 import torch
 
-from localrf_amd import NativeError, _checks, depth_quantiles, mesh, mesh_distance, mesh_raster, mesh_texture, novel_views
+from localrf_amd import NativeError, _checks, alignment, cloud, depth_quantiles, mesh, mesh_distance, mesh_raster, mesh_texture, novel_views
 from localrf_amd.pointcloud import SceneFrames
 from novel_views_cases import scene
 
@@ -53,6 +54,17 @@ VALIDATORS = (
      (((1, 1), (1, 1)), ((8.0, 6), (8, 6)), ((INT32, 1), (INT32, 1))),
      ((0, 4), (4, 0), (True, 4), (np.True_, 4), (2.5, 4), ("3", 4), (None, 4), (math.nan, 4), (math.inf, 4), (-1, 4), (2 ** 31, 1),
       (1 << 16, 1 << 15), ([4], 4), (Unconvertible(), 4))),
+    ("max_distance", _checks.check_max_distance, "max_distance",       # float() decides: a string that spells a number passes
+     ((0, 0.0), (math.inf, math.inf), (np.float32(0.5), 0.5), (3, 3.0), (1.5, 1.5), ("3", 3.0)),
+     (True, np.True_, math.nan, -1, -1e-300, -math.inf, "far", None, [1.0], Unconvertible())),
+    ("thresholds", _checks.check_thresholds, "threshold",              # returned as float32 values: the kernel compares in fp32
+     (((), []), ([], []), ((0.5, 1), [0.5, 1.0]), ((np.float32(0.5),), [0.5]), ((0.1,) * 8, [float(np.float32(0.1))] * 8),
+      ((1e-45,), [float(np.float32(1e-45))])),
+     ((0.1,) * 9, (True,), (np.True_,), (math.nan,), (math.inf,), (-1,), (0,), ("a",), "ab", 0.5, None, (0.1, None), (1e-50,), (1e39,),
+      (5e-324,), (Unconvertible(),))),
+    ("unit", _checks.check_unit, "unit",
+     ((1, 1.0), (0.5, 0.5), (np.float32(0.5), 0.5), (1e-45, 1e-45), (3e38, 3e38)),
+     (True, np.True_, math.nan, math.inf, -1, 0, "x", None, [1.0], Unconvertible(), 1e-50, 1e39, 5e-324)),
 )
 
 
@@ -120,6 +132,66 @@ def test_mesh_and_frame_checks():
     rgb8 = torch.arange(2 * 4 * 5 * 3, dtype=torch.uint8).view(2, 4, 5, 3)
     assert _checks.rgb8_frames(rgb8, depth) is rgb8                          # uint8 passes through; float would be encoded (HIP)
     assert _checks.float_of_key(0) == 0.0 and _checks.float_of_key(0x3F800000) == 1.0 and _checks.float_of_key(-1) == -0.0
+
+
+def test_points_checks():
+    assert _checks.check_points(torch.zeros(7, 3)) == 7 and _checks.check_points(torch.zeros(0, 3)) == 0
+    assert _checks.check_points(torch.zeros(8, 6)[:, ::2]) == 8              # any strides: points_on_device makes it contiguous
+    with pytest.raises(TypeError, match="points must be a torch tensor"):
+        _checks.check_points(np.zeros((3, 3), np.float32))
+    for bad in (torch.zeros(3, 2), torch.zeros(3), torch.zeros(3, 3, dtype=torch.float64), torch.zeros(3, 3, dtype=torch.int32), torch.zeros(2, 3, 3)):
+        with pytest.raises(ValueError, match=r"points must be \[N, 3\] float32"):
+            _checks.check_points(bad)
+
+
+def test_chunks_cover_every_item_once(monkeypatch):
+    assert _checks.POINTS_PER_CALL == 1 << 30 and list(_checks.chunks(7)) == [(0, 7)]
+    for n in (0, 1, 4, 5, 6, 11):
+        want = [(i0, min(5, n - i0)) for i0 in range(0, n, 5)]
+        assert list(_checks.chunks(n, 5)) == want
+        monkeypatch.setattr(_checks, "POINTS_PER_CALL", 5)                      # read at each call
+        assert list(_checks.chunks(n)) == want
+        monkeypatch.setattr(_checks, "POINTS_PER_CALL", 1 << 30)
+    from localrf_amd import _native
+    seen = []
+    monkeypatch.setattr(_native, "launch", lambda name, dev, *args, guard=False: seen.append((name, dev, args)))
+    monkeypatch.setattr(alignment, "PAIRS_PER_CALL", 5)
+    for n in (1, 4, 5, 6, 11):
+        a, b, keep = torch.zeros(n, 3), torch.ones(n, 3), torch.ones(n, dtype=torch.uint8)
+        del seen[:]
+        words = alignment._pair_words((0.0, 0.0, 0.0), 1.0, a, b, keep)
+        spans = [(i0, min(5, n - i0)) for i0 in range(0, n, 5)]
+        assert tuple(words.shape) == (len(spans), 24) and words.dtype is torch.int64 and len(seen) == len(spans)
+        assert sum(args[4] for _, _, args in seen) == n
+        for j, ((i0, m), (name, dev, args)) in enumerate(zip(spans, seen)):         # one launch per chunk, each into its own row
+            assert name == "lrf_align_pairs" and dev == a.device
+            assert args[1:] == (a[i0:].data_ptr(), b[i0:].data_ptr(), keep[i0:].data_ptr(), m, words[j].data_ptr())
+        del seen[:]
+        assert alignment._pair_words((0.0, 0.0, 0.0), 1.0, a, b, None).shape == (len(spans), 24) and all(args[3] is None for _, _, args in seen)
+        near = {"closest": torch.zeros(n, 3), "distance": torch.zeros(n), "index": torch.zeros(n, dtype=torch.int32), "face": torch.zeros(n, dtype=torch.int32)}
+        mesh_index = _StubMeshIndex()
+        mesh_index.vertices, mesh_index.faces, mesh_index.counts = torch.zeros(4, 3), torch.zeros(2, 3, dtype=torch.int32), (4, 2)
+        for index, normals, symbol, key in ((mesh_index, None, "lrf_align_plane", "face"), (_StubCloudIndex(), torch.zeros(8, 3), "lrf_align_plane_cloud", "index")):
+            del seen[:]
+            words = alignment._plane_words(index, a, near, (0.0, 0.0, 0.0), 2.0, math.inf, normals)
+            assert tuple(words.shape) == (len(spans), 48) and [name for name, _, _ in seen] == [symbol] * len(spans)
+            assert [args[1] for _, _, args in seen] == [words[j].data_ptr() for j in range(len(spans))]
+            p = seen[-1][2][0]._obj                                                # one struct, refilled per chunk: the last chunk's
+            i0, m = spans[-1]
+            assert (p.N, p.points, p.closest, p.distance, getattr(p, key)) == (m, a[i0:].data_ptr(), near["closest"][i0:].data_ptr(),
+                                                                               near["distance"][i0:].data_ptr(), near[key][i0:].data_ptr())
+            assert (p.u, p.gate) == (2.0, math.inf)
+
+
+class _StubMeshIndex(mesh_distance.MeshIndex):
+    """A MeshIndex without a device and without a face: the checks of closest that come before the device check."""
+    def __init__(self):
+        self.device, self.counts, self._grid = torch.device("cpu"), (0, 0), None
+
+
+class _StubCloudIndex(cloud.CloudIndex):
+    def __init__(self, m=8):
+        self.points, self.device, self.counts, self._grid = torch.zeros(m, 3), torch.device("cpu"), (m,), None
 
 
 class _Recorder:
@@ -217,6 +289,19 @@ def test_the_device_comes_after_the_other_arguments():
             call()
     with pytest.raises(NativeError, match="vertices"):
         _checks.mesh_on_device(m["vertices"], m["faces"], None, "the test")
+    pts = torch.zeros(8, 3)
+    for call, bad, name in ((lambda **kw: cloud.CloudIndex(pts, **kw), dict(max_bytes=1.5), "max_bytes"),
+                            (lambda **kw: alignment.transform_points(pts, **{"T": np.eye(4), **kw}), dict(T=np.zeros((3, 3))), "T must be"),
+                            (lambda **kw: _StubMeshIndex().closest(pts, **kw), dict(max_distance=-1.0), "max_distance"),
+                            (lambda **kw: _StubCloudIndex().knn(pts, **{"k": 2, **kw}), dict(k=9), "k must be")):
+        with pytest.raises(ValueError, match=name):
+            call(**bad)
+        with pytest.raises(NativeError, match="points lives on cpu"):
+            call()
+    with pytest.raises(NativeError, match="colours lives on cpu; the test can run only on an AMD GPU"):
+        _checks.points_on_device(torch.zeros(8, 3, dtype=torch.uint8), "colours", "the test")
+    with pytest.raises(TypeError, match="colours"):
+        _checks.points_on_device(None, "colours", "the test")
     lt, g = scene("cpu")
     W, H = float(g["W"]) + 0.5, float(g["H"])                              # SceneFrames takes int(W) first, as render_poses does
     for fn in (mesh_raster.scene_mesh_agreement, mesh_texture.scene_texture):

@@ -8,7 +8,9 @@ test_align_meshes_brings_a_moved_simplified_mesh_back: Chamfer after alignment /
 0.312 (sphere) and 0.601 (torus), bar 1.05: the free scale lets the inscribed simplified mesh grow onto the surface."""
 import ctypes as C
 import functools
+import json
 import math
+import os
 
 import numpy as np
 import pytest
@@ -17,13 +19,15 @@ import torch
 from align_cases import (ICP_BAR, ICP_RUNS, PAIR_SIZES, PERTURBATIONS, TRANSFORM_SIZES, add_words, apply, blob, deviation,
                          move_poses, pair_inputs, pairs_host, parts, plane_host, sim, sim_inverse, source_cloud, trajectory,
                          transform_host, truth, umeyama_host)
-from localrf_amd import NativeError, alignment, mesh_distance
+from localrf_amd import NativeError, _checks, alignment, cloud, mesh_distance
 from localrf_amd import _native as N
 from localrf_amd.mesh import simplify
 from localrf_amd.mesh_distance import MeshIndex
 from mesh_clean_cases import base_meshes
+from cloud_normal_cases import plane_cloud_case, plane_cloud_host
 from mesh_distance_cases import planar
-from mesh_util import DEV, bits, device_mesh, to_dev
+from point_layer_cases import launch_lists
+from mesh_util import DEV, bits, device_mesh, record_launches, same_bits, to_dev
 
 pytestmark = pytest.mark.gpu
 U32 = np.uint32
@@ -229,3 +233,47 @@ def test_transform_mesh_rotates_normals_and_shares_the_faces():
     assert "normals" not in plain
     with pytest.raises(NativeError):
         alignment.transform_points(torch.zeros(3, 3), T_ANY)
+
+
+def test_chunks_give_the_bytes_and_the_words_of_one_call(monkeypatch):
+    """transform_points at 5 points per launch, and the plane words of both targets at 5 points per launch: 11 points are two full
+    chunks and a remainder.  The words of the chunks, added, are the words of one call and the restatement's."""
+    names = record_launches(monkeypatch)
+    p = to_dev((np.random.default_rng(12).standard_normal((11, 3)) * 3).astype(np.float32))
+    whole = alignment.transform_points(p, T_ANY)
+    mesh, source, c, u, max_distance, gate = plane_case()
+    B, normals, source_b, c_b, u_b, max_distance_b, gate_b, _ = plane_cloud_case()
+    runs = []
+    for index, src, nrm, frame in ((MeshIndex(device_mesh(mesh, rgb=False)), source[-11:], None, (c, u, max_distance, gate)),
+                                   (cloud.CloudIndex(to_dev(B)), source_b[-11:], to_dev(normals), (c_b, u_b, max_distance_b, gate_b))):
+        cur = to_dev(src)
+        near = index.closest(cur, frame[2], closest=True)
+        host = {k: v.cpu().numpy() for k, v in near.items()}
+        want = (plane_host(mesh, src, host["closest"], host["face"], host["distance"], frame[0], frame[1], np.float32(frame[3])) if nrm is None else
+                plane_cloud_host(src, host["closest"], host["index"], host["distance"], normals, frame[0], frame[1], np.float32(frame[3])))
+        assert sum(want[:5]) == 11 and want[0] > 0 and want[1] > 0                  # summed and unmatched points among the eleven
+        runs.append((index, cur, near, frame, nrm, want))
+        del names[:]
+        words = alignment._plane_words(index, cur, near, frame[0], frame[1], frame[3], nrm)
+        assert tuple(words.shape) == (1, 48) and len(names) == 1 and alignment._add_words(words.cpu()) == want
+    monkeypatch.setattr(_checks, "POINTS_PER_CALL", 5)
+    monkeypatch.setattr(alignment, "PAIRS_PER_CALL", 5)
+    del names[:]
+    same_bits(alignment.transform_points(p, T_ANY), whole)
+    assert names == ["lrf_align_transform"] * 3
+    for index, cur, near, frame, nrm, want in runs:
+        del names[:]
+        words = alignment._plane_words(index, cur, near, frame[0], frame[1], frame[3], nrm)
+        assert tuple(words.shape) == (3, 48) and names == ["lrf_align_plane" if nrm is None else "lrf_align_plane_cloud"] * 3
+        assert alignment._add_words(words.cpu()) == want and words[2].tolist() != words[0].tolist()
+
+
+def test_the_point_layer_launches_what_it_launched_before_its_helpers_were_shared():
+    """tests/golden/point_layer_launches.json: per public call the (symbol, count) of every launch, recorded from the code before
+    the refactor (tests/golden/make_golden_point_launches.py).  The same launches, in the same order, chunked the same way."""
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "point_layer_launches.json")) as f:
+        want = json.load(f)
+    got = launch_lists()
+    assert set(got) == set(want) and len(want) == 21
+    for call in want:
+        assert got[call] == want[call], call

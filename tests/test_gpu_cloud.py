@@ -5,7 +5,7 @@ import numpy as np
 import pytest
 import torch
 
-from localrf_amd import NativeError, alignment
+from localrf_amd import NativeError, _checks, alignment
 from localrf_amd import _native as N
 from localrf_amd.cloud import (CloudIndex, cloud_distance, cloud_to_cloud, nearest_spacing, remove_outliers, voxel_downsample)
 from localrf_amd.mesh import simplify
@@ -13,7 +13,7 @@ from localrf_amd.mesh_distance import MeshIndex
 from cloud_cases import (CASE_NAMES, KS, box_host, cases, cell_sweep, closest_host, dims_host, expected, icp_case, pairs_host, radius_count_host,
                          random_cloud, sphere, summary_counts_host, surface_with_floaters, voxel_cases, voxel_host)
 from mesh_clean_cases import base_meshes
-from mesh_util import DEV, bits, device_mesh, to_dev
+from mesh_util import DEV, bits, device_mesh, record_launches, same_bits, to_dev
 
 pytestmark = pytest.mark.gpu
 U32 = np.uint32
@@ -293,3 +293,29 @@ def test_refusals_on_the_device():
     assert 8 * math.prod(full.info["dims"]) > 100000 >= 8 * math.prod(small.info["dims"])
     assert small.info["cell"] == 2 * full.info["cell"] and small.nbytes <= 200000
     assert torch.equal(small.closest(pts, 0.5)["index"], full.closest(pts, 0.5)["index"])
+
+
+def test_chunks_give_the_bytes_of_one_call(monkeypatch):
+    """Every query over points at 5 points per launch: 11 queries are two full chunks and a remainder.  exclude_self (the chunk's
+    first query is cloud point i0) and the viewpoint per query (its rows start at i0) are what a wrong offset corrupts."""
+    cloud = random_cloud(11, 80)
+    cloud[4, 1], cloud[9] = np.nan, cloud[2]                                       # one point that is not finite, one duplicate pair
+    pts, view = to_dev(cloud), to_dev(random_cloud(11, 81, 3.0))
+    index = CloudIndex(pts)
+    assert index.info["points"] == 10 and index.info["nonfinite_points"] == 1
+
+    def run():
+        return (index.closest(pts, closest=True), index.knn(pts, 3, exclude_self=True), index.radius_count(pts, 0.75, exclude_self=True),
+                index.normals(pts, 1.5, 3, view), index.normals(pts, 1.5, 3, (0.5, -2.0, 1.0)))
+    names = record_launches(monkeypatch)
+    whole = run()
+    assert names == ["lrf_cloud_closest", "lrf_cloud_knn", "lrf_cloud_radius_count", "lrf_cloud_normals", "lrf_cloud_normals"]
+    assert int(whole[2].max()) >= 2 and int(whole[3]["count"].max()) >= 3 and whole[1]["distance"][9, 0] == 0  # neighbours, and the twin
+    assert not torch.equal(whole[3]["normals"].view(torch.int32), whole[4]["normals"].view(torch.int32))      # the viewpoints matter
+    monkeypatch.setattr(_checks, "POINTS_PER_CALL", 5)
+    del names[:]
+    parts = run()
+    assert names == [n for name in ("lrf_cloud_closest", "lrf_cloud_knn", "lrf_cloud_radius_count", "lrf_cloud_normals", "lrf_cloud_normals")
+                     for n in [name] * 3]
+    for a, b in zip(whole, parts):
+        same_bits(a, b)

@@ -109,7 +109,7 @@ def test_the_same_bytes_for_every_run_stream_split_permutation_and_order():
 
 # ------------------------------------------------------------------------------------------------ lrf_align_plane_cloud
 def plane_cloud_words(index, normals, cur, near, c, u, gate):
-    return alignment._add_words(alignment._plane_cloud_words(index, normals, cur, near, c, u, gate).cpu())
+    return alignment._add_words(alignment._plane_words(index, cur, near, c, u, gate, normals).cpu())
 
 
 def test_plane_cloud_words_equal_the_restatement_for_every_order_and_run():

@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 import torch
 
-from localrf_amd import NativeError, mesh_distance
+from localrf_amd import NativeError, _checks, mesh_distance
 from localrf_amd import _native as N
 from localrf_amd.mesh import simplify
 from localrf_amd.mesh_distance import MeshIndex, cloud_to_mesh, distance_summary, sample_surface
@@ -14,7 +14,7 @@ from mesh_clean_cases import base_meshes
 from mesh_distance_cases import (CASE_NAMES, SAMPLE_CASES, SUMMARY_SIZES, SUMMARY_TAUS, _pairs, box_host, cases, default_cell_host,
                                  dims_host, expected, mesh_distance_host, sample_host, summary_host, summary_inputs)
 from mesh_raster_cases import octa_sphere
-from mesh_util import DEV, bits, device_mesh
+from mesh_util import DEV, bits, device_mesh, record_launches, same_bits
 
 pytestmark = pytest.mark.gpu
 U32 = np.uint32
@@ -219,3 +219,17 @@ def test_refusals():
             index.closest(pts, bad)
     with pytest.raises(ValueError, match="closest"):
         index.closest(pts, closest=1)
+
+
+def test_chunks_give_the_bytes_of_one_call(monkeypatch):
+    c = cases()["octa 512 default cell"]
+    pts = torch.from_numpy(c["points"][:11].copy()).to(DEV)
+    pts[6, 2] = math.nan
+    index = MeshIndex(dev_mesh(c["mesh"]))
+    names = record_launches(monkeypatch)
+    whole = index.closest(pts, closest=True)
+    assert names == ["lrf_mesh_closest"] and int((whole["face"] >= 0).sum()) == 10
+    monkeypatch.setattr(_checks, "POINTS_PER_CALL", 5)
+    del names[:]
+    same_bits(index.closest(pts, closest=True), whole)                              # 5 + 5 + 1 points
+    assert names == ["lrf_mesh_closest"] * 3
