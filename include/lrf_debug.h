@@ -56,6 +56,15 @@ int64_t lrf_debug_saved_row_offset(int buffer, uint64_t row, int col);
  * 2 = compare-and-swap with the lines fused, 3 = compare-and-swap with the lines apart (the line kernel runs only then).
  * Returns 0, 1 where lrf_render_bwd refuses the grid (deterministic and ll_max > 640), -1 for bad arguments. */
 int     lrf_debug_scatter_plan(int32_t ll_max, int32_t deterministic, int32_t engine_bits, int64_t out[8]);
+/* The launch plan of the forward render (csrc/lrf_forward.inl: plan_march, plan_shade3, pipe_chunks) for a field whose three
+ * density lines are ll[0..2] cells long, R rays and S samples: a pure host function, no device needed.  switches: negative =
+ * the process-wide hooks as they are set now; else bit 0 = density lines in LDS where they fit (lrf_debug_set_lds_lines),
+ * bit 1 = tile offsets in LDS where they fit (lrf_debug_set_lds_toff), bits 2.. = lrf_debug_set_march_rays' value (0, 4, 8, 16).
+ * out = {rays per k_march workgroup with the lines in LDS (0: lines from global memory), rays per group sum, z in LDS, k_march's
+ * grid, block, dynamic LDS bytes, k_shade3's offsets in LDS, its dynamic LDS bytes, whether k_scan_tiles_n runs first, chunks of
+ * the two-stream large-batch mode (1: one pass), the dynamic LDS k_march / k_shade3 are opted in for}.  Returns 0, -1 for bad
+ * arguments (null, R <= 0, S outside 2 .. 4096, a line length <= 0, march rays not 0, 4, 8 or 16). */
+int     lrf_debug_forward_plan(const int32_t ll[3], int32_t R, int32_t S, int32_t switches, int64_t out[12]);
 /* Byte offsets, inside a training workspace (any flags: the deterministic mode's image lies behind everything else), of the two
  * words that hold the largest |contribution| of a backward as float bits: out[0] the density group's (k_bwd_ray), out[1] the
  * appearance group's (k_train_app3, written only where the appearance scatter runs on fixed point).  k_clear_bins zeroes both

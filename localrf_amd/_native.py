@@ -242,6 +242,7 @@ SYMBOLS = {
     "lrf_debug_block_reduce": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "lrf_debug_saved_row_offset":(C.c_int64, [C.c_int, C.c_uint64, C.c_int]),
     "lrf_debug_scatter_plan": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
+    "lrf_debug_forward_plan": (C.c_int, [C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
     "lrf_debug_workspace_vmax_bwd": (None, [C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_uint64)]),
     "lrf_debug_set_bwd_overlap": (None, [C.c_int]),
     "lrf_debug_set_train_fwd_engine": (None, [C.c_int]),

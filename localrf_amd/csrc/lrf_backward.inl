@@ -1812,7 +1812,7 @@ static int g_scatter_fix = 3;       // bit 0: density, bit 1: appearance (where 
 static int g_wgrad_kt = 64;          // rows per step of k_wgrad_w2w3 (lrf_debug_set_train_fwd_engine(512 | ...): 128, one workgroup per CU)
 static int g_wgrad_split = 1;       // lrf_debug_set_bwd_overlap(1 + 2 * (n + 1)): n > 0 = k_wgrad_w2w3 on the caller's stream, 0 = on the side stream
 static int g_scatter_wgs = 0;       // lrf_debug_set_scatter_wgs: workgroups of the binned scatter kernels (0: one per CU)
-static hipError_t launch_shade_save(DField d, const float* rays, const float* z, int S, int R, uint32_t flags, const Workspace& w,
+static hipError_t launch_shade_save(DField d, const float* rays, const float* z, int S, int R, uint32_t flags, const Workspace& w, int group_rays,
                                     const BwdWorkspace& b, float* rgb, hipStream_t st) {
   if (!gen_is_default(d.fea_pe, d.view_pe, d.fc) || (flags & LRF_FLAG_MLP_VALU)) {          // generic engine (lrf_generic.inl): same saved state, no mask bits
     const GenCfg gc = gen_cfg(d.fea_pe, d.view_pe, d.fc, !(flags & LRF_FLAG_PE_OFF));
@@ -1824,8 +1824,21 @@ static hipError_t launch_shade_save(DField d, const float* rays, const float* z,
     return hipGetLastError();
   }
   const SaveOut3 sv{b.crgb, b.act, b.relu_bits, b.tileinfo, w.toff};
-  launch_shade3(d, rays, z, R, S, flags, w, b.toff32, rgb, nullptr, &sv, nullptr, st);
+  launch_shade3(d, rays, z, R, S, flags, w, group_rays, b.toff32, rgb, nullptr, &sv, nullptr, st);
   return hipSuccess;
+}
+// The training forward: sort (as asked), k_march with the feature rows, the row-saving colour kernel.  lrf_render_fwd_train runs
+// it, and lrf_render_bwd where it is not handed saved rows.  Sets d.perm and d.rdir; returns through `rays` the rays every later
+// stage reads.
+static int train_forward_rows(DField& d, const float*& rays, const float* z, int R, int S, uint32_t flags, const BwdWorkspace& b,
+                              float* rgb, float* depth, hipStream_t st) {
+  const Workspace& w = b.fw;
+  const MarchPlan m = plan_march(d.ll, R, S);
+  rays = sort_rays_if_asked(d, rays, R, flags, w, st);
+  d.rdir = w.rdir;
+  launch_march(m, d, rays, z, R, S, flags, 0.0f, march_io(w, depth, nullptr, b.feat), st);
+  LRF_HIP(launch_shade_save(d, rays, z, S, R, flags, w, m.group, b, rgb, st));
+  return 0;
 }
 
 }  // namespace lrf
@@ -1890,11 +1903,7 @@ extern "C" int lrf_render_fwd_train(const LrfField* f, const float* rays, const 
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   DField d = make_dfield(f);
   const BwdWorkspace b = carve_bwd(workspace, R, S, f->grid, field_gen_ld(f->fea_pe, f->view_pe, f->feature_c, flags));
-  const Workspace& w = b.fw;
-  rays = sort_rays_if_asked(d, rays, R, flags, w, st);
-  d.rdir = w.rdir;
-  launch_march(d, rays, z, R, S, flags, 0.0f, depth, w.acc, nullptr, w.ncomp, w.gsum, w.cidx, w.cw, b.feat, st);
-  LRF_HIP(launch_shade_save(d, rays, z, S, R, flags, w, b, rgb, st));
+  LRF_TRY(train_forward_rows(d, rays, z, R, S, flags, b, rgb, depth, st));
   LRF_HIP(hipGetLastError());
   return 0;
 }
@@ -2084,10 +2093,7 @@ static void launch_scatter_lines(const BwdPlan& P, const ScatterGroup& G, hipStr
 static int bwd_forward_rows(BwdPlan& P, hipStream_t s) {
   const BwdWorkspace& b = P.b; const Workspace& w = b.fw;
   if (P.flags & LRF_FLAG_ROWS_SAVED) { if (P.sort) { P.d.perm = w.perm; P.rays = w.rays_s; } return 0; }
-  P.rays = sort_rays_if_asked(P.d, P.rays, P.R, P.flags, w, s);
-  launch_march(P.d, P.rays, P.z, P.R, P.S, P.flags, 0.0f, b.depth, w.acc, nullptr, w.ncomp, w.gsum, w.cidx, w.cw, b.feat, s);
-  LRF_HIP(launch_shade_save(P.d, P.rays, P.z, P.S, P.R, P.flags, w, b, b.rgb, s));
-  return 0;
+  return train_forward_rows(P.d, P.rays, P.z, P.R, P.S, P.flags, b, b.rgb, b.depth, s);
 }
 // Both groups' histograms, cursors and maxima, with the caller's zero range; deterministic: once more with the int64 image
 static void bwd_clear(const BwdPlan& P, hipStream_t s) {

@@ -1,10 +1,12 @@
 // lrf_render.hip -- gfx950 (MI355X / CDNA4) forward kernels of the localrf render path and the C ABI declared in
 // include/lrf.h.  One translation unit (this file + the .inl files it includes), built without the SLP vectoriser
 // (lrf_tu.h says why).  In include order: lrf_common.h, lrf_host.inl (the host helpers of every entry point: refuse, launch,
-// misaligned, Carver), lrf_tiles.inl, lrf_shade3.inl (+ lrf_shade3_kernel.inl), lrf_generic.inl, lrf_backward.inl (+ lrf_train32.inl),
-// lrf_scene / adam / losses / metrics / frames / select / evalgeo / encode .inl, lrf_compact.inl and the geometry files
-// (lrf_points, lrf_mesh, lrf_mesh_clean / simplify / smooth / raster / texture / distance, lrf_tsdf_blocks), lrf_reg.inl,
-// lrf_mask.inl, and behind the C ABI of this file lrf_normals.inl and lrf_quantile.inl.
+// misaligned, Carver, TwoStreams), lrf_tiles.inl, lrf_shade3.inl (+ lrf_shade3_kernel.inl), lrf_generic.inl, lrf_forward.inl (the
+// forward's host side: workspace, launch plan and helpers, lrf_render_fwd), lrf_backward.inl (+ lrf_train32.inl), lds_opt_in
+// (behind every kernel it names), lrf_scene / adam / losses / metrics / frames / select / evalgeo / encode .inl, lrf_compact.inl
+// and the geometry files (lrf_points, lrf_mesh, lrf_mesh_clean / simplify / smooth / raster / texture / distance,
+// lrf_tsdf_blocks), lrf_reg.inl, lrf_mask.inl, lrf_normals.inl, lrf_quantile.inl; this file keeps the kernels, the debug
+// setters and the small feature / sampling / pack entry points.
 //
 // Pipeline of lrf_render_fwd (one field, R rays x S samples), two launches, no atomics on floats:
 //   k_march      one wavefront per ray: contracted sampling, density VM gather (channel-last planes, 2 x float4 per tap,
@@ -996,272 +998,31 @@ static DField make_dfield(const LrfField* f) {
   return d;
 }
 
-struct Workspace {
-  int* toff; int* ncomp; float* acc; uint16_t* cidx; float* cw; float* part;
-  int* gsum;               // k_march -> k_shade3: 32-sample tiles of each march workgroup's rays (at most ceil(R / 4) of them)
-  float* rdir;             // k_march -> k_shade3: unit direction and length per ray
-  int* perm; float* rays_s;  // ray sorting: slot -> ray, sorted copy of the rays
-  int pmax; size_t bytes;
-};
-static Workspace carve(void* ws, int R, int S) {     // every piece padded to 256 bytes
-  Workspace w;
-  Carver c(ws);
-  w.pmax = 2 * ((S + ITEM3 - 1) / ITEM3);             // partial slots per ray: enough for 16-sample tiles, 32-sample tiles and the training rows (two 16-row tiles per 32-sample tile)
-  w.toff  = c.take<int>((size_t)R + 1, 256);
-  w.ncomp = c.take<int>(R, 256);
-  w.acc   = c.take<float>(R, 256);
-  w.cidx  = c.take<uint16_t>((size_t)R * S, 256);     // (k_shade3 reads aligned dwords of it: an odd R * S ends 2 bytes short of a dword, inside the padding)
-  w.cw    = c.take<float>((size_t)R * S, 256);
-  w.part  = c.take<float>((size_t)R * w.pmax * 3, 256);
-  w.rdir  = c.take<float>((size_t)R * 4, 256);
-  w.perm  = c.take<int>(R, 256);
-  w.rays_s = c.take<float>((size_t)R * 6, 256);
-  w.gsum  = c.take<int>((R + 3) / 4, 256);
-  w.bytes = c.bytes();
-  return w;
-}
-
-// Test hooks (include/lrf_debug.h): process-wide, not part of the re-entrant ABI.
-static float* g_dump = nullptr;    // lrf_debug_set_dump: device buffer for the s_memtime totals of k_shade3<TIMED>
-static unsigned long long* g_march_dump = nullptr;   // lrf_debug_march_phases: device buffer [R][4] for the phase clocks of k_march_timed
-static int g_no_lds_lines = 0;     // lrf_debug_set_lds_lines(0): k_march reads its lines from global memory
-static int g_pipe_chunk = 16384;    // lrf_debug_set_pipe_chunk: rays per chunk of lrf_render_fwd's large-batch mode (0: one pass over the whole batch, as rounds 1-5)
-static int g_march_rays = 0;       // lrf_debug_set_march_rays: rays per k_march workgroup (4, 8, 16) where that many fit; 0: march_lds_rays' own choice
-static int g_no_lds_toff = 0;      // lrf_debug_set_lds_toff(0): k_shade3 behind k_scan_tiles_n (global tile offsets) at every batch size
-static int g_no_scene_fuse = 0;    // lrf_debug_set_scene_fuse(0): lrf_scene_fwd renders field by field (the tests compare the two forms)
-
-static int device_cus() {                 // of the current device (one process may drive several)
-  static int cache[64] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return 256;
-  int& cus = cache[dev & 63];
-  if (!cus) {
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-    if (cus <= 0) cus = 256;
-  }
-  return cus;
-}
-
-static int g_bwd_overlap = 1;      // lrf_debug_set_bwd_overlap: weight-gradient GEMMs on a side stream, beside the scatter kernels
-struct SideStream { hipStream_t s; hipEvent_t fork, join, app[2], bucket[5]; bool ok, bucket_set; std::mutex mu; };   // bucket[]: lrf_render_bwd_wait
-static SideStream* side_stream() {
-  static SideStream tab[64];
-  static std::mutex init_mu;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return nullptr;
-  SideStream& x = tab[dev & 63];
-  std::lock_guard<std::mutex> lk(init_mu);
-  if (!x.ok) {
-    if (hipStreamCreateWithFlags(&x.s, hipStreamNonBlocking) != hipSuccess) return nullptr;
-    if (hipEventCreateWithFlags(&x.fork, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&x.join, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&x.app[0], hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&x.app[1], hipEventDisableTiming) != hipSuccess) return nullptr;
-    for (int q = 0; q < 5; ++q)
-      if (hipEventCreateWithFlags(&x.bucket[q], hipEventDisableTiming) != hipSuccess) return nullptr;
-    x.bucket_set = false;
-    x.ok = true;
-  }
-  return &x;
-}
-// The caller's stream beside the device's side stream, for one call (lrf_render_bwd, render_fwd_pipelined).  Holds the
-// SideStream's mutex for its lifetime: the side stream and its events are per device, so host threads that enqueue on the same
-// device take turns (enqueueing a backward is ~0.3 ms of host time; the kernels themselves still overlap on the GPU).
-// On one stream -- no SideStream, or (unless `always`) lrf_debug_set_bwd_overlap(0) or a capturing caller's stream -- side() is
-// the caller's stream and fork / join / signal / wait do nothing.  The bucket events of lrf_render_bwd_wait are recorded
-// whenever the device has a SideStream, on one stream and under capture too: that is sx against ss.
-class TwoStreams {
-  hipStream_t st;
-  SideStream* sx;            // the device's, or null
-  SideStream* ss;            // sx when the call runs on two streams, else null
-  std::unique_lock<std::mutex> lock;
- public:
-  explicit TwoStreams(hipStream_t caller, bool always = false) : st(caller), sx(side_stream()), ss(sx) {
-    if (sx) lock = std::unique_lock<std::mutex>(sx->mu);
-    if (ss && !always) {
-      hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-      (void)hipStreamIsCapturing(st, &cap);
-      if (!g_bwd_overlap || cap == hipStreamCaptureStatusActive) ss = nullptr;
-    }
-  }
-  bool overlapping() const { return ss != nullptr; }
-  hipStream_t side() const { return ss ? ss->s : st; }
-  int fork() {               // the side stream continues from here
-    if (ss) { LRF_HIP(hipEventRecord(ss->fork, st)); LRF_HIP(hipStreamWaitEvent(ss->s, ss->fork, 0)); }
-    return 0;
-  }
-  int join() {               // the caller's stream continues behind everything on the side stream
-    if (ss) { LRF_HIP(hipEventRecord(ss->join, ss->s)); LRF_HIP(hipStreamWaitEvent(st, ss->join, 0)); }
-    return 0;
-  }
-  int signal(int i, hipStream_t s) { if (ss) LRF_HIP(hipEventRecord(ss->app[i], s)); return 0; }      // hand-off i (0, 1) is ready behind s ...
-  int wait(int i, hipStream_t s) { if (ss) LRF_HIP(hipStreamWaitEvent(s, ss->app[i], 0)); return 0; } // ... and s goes on behind it
-  int bucket(int i, hipStream_t s) { if (sx) LRF_HIP(hipEventRecord(sx->bucket[i], s)); return 0; }   // lrf_render_bwd_wait(i)'s event
-  void finish() { if (sx) sx->bucket_set = true; }
-};
-// Dynamic LDS above 64 KB has to be opted into, once per device, before the first launch that asks for it: every render-path
-// entry point calls this once its arguments are accepted (defined behind lrf_backward.inl, whose kernels it names too).
-static hipError_t lds_opt_in();
-
-// LRF_FLAG_SORT_RAYS: sort the batch by direction (k_sort_rays) into the workspace; returns the rays the kernels should read
-// and sets d.perm.  Batches beyond the 16-bit index of the sort words are rendered in the caller's order.
-constexpr int LRF_SORT_MAX_R = 32768;
-static bool sorts_rays(int R, uint32_t flags) { return (flags & LRF_FLAG_SORT_RAYS) && R >= 2 && R <= LRF_SORT_MAX_R; }
-static const float* sort_rays_if_asked(DField& d, const float* rays, int R, uint32_t flags, const Workspace& w, hipStream_t st) {
-  d.perm = nullptr;
-  if (!sorts_rays(R, flags)) return rays;
-  int N = 2;
-  while (N < R) N <<= 1;
-  hipLaunchKernelGGL(k_sort_rays, dim3(1), dim3(1024), (size_t)N * 4, st, rays, R, N, w.rays_s, w.perm);
-  d.perm = w.perm;
-  return w.rays_s;
-}
-
-// rays per k_march workgroup with the density lines in LDS (4, 8 or 16), 0 when alpha slices + lines do not fit (grids of
-// about 900^3 and above) or lrf_debug_set_lds_lines(0): k_march<false> then reads the lines from global memory
-static int march_lds_rays(const int32_t ll[3], int S) {
-  if (g_no_lds_lines) return 0;
-  const size_t lds_l = (size_t)(ll[0] + ll[1] + ll[2]) * LRF_CD * sizeof(float);
-  int first = 0;
-  for (int cand = 4; cand <= 16; cand *= 2)
-    if (((size_t)cand * S * sizeof(float) + lds_l) * (16 / cand) <= 156 * 1024) {
-      if (!first) first = cand;
-      if (cand == g_march_rays) return cand;               // (test hook: a larger workgroup than the smallest that fits)
-    }
-  return first;
-}
-// rays per k_march workgroup, with or without the lines in LDS: the unit of Workspace::gsum
-static int march_group_rays(const int32_t ll[3], int S) { const int nw = march_lds_rays(ll, S); return nw ? nw : 4; }
-// whether the schedule's S floats go into LDS too: the choice of march_lds_rays() stands, z joins where the same budget still
-// holds with it (300^3 at S = 512: (8 + 28.8 + 2 KB) x 4 = 155.2 KB; 500^3 at 576 and 640^3 at 738 fit as well); nw = 0 is
-// k_march<false>, four alpha slices (+ z) inside 64 KB; with MARCH_LDS_TAIL behind them the kernel is opted in for 64 KB + 16 B
-static bool march_lds_z(const int32_t ll[3], int S, int nw) {
-  if (!nw) return (size_t)5 * S * sizeof(float) <= 64 * 1024;
-  const size_t lds_l = (size_t)(ll[0] + ll[1] + ll[2]) * LRF_CD * sizeof(float);
-  return ((size_t)(nw + 1) * S * sizeof(float) + lds_l) * (16 / nw) <= 156 * 1024;
-}
-// k_march launch: lines in LDS when the three of them (+ the alpha slices) leave four workgroups per CU.  mf (the fused
-// multi-field form) exists with the lines in LDS only: lrf_scene_fwd does not fuse when march_lds_rays() is 0.
-static void launch_march(const DField& d, const float* rays, const float* z, int R, int S, uint32_t flags, float floater,
-                         float* depth, float* acc, float* w_all, int* ncomp, int* gsum, uint16_t* cidx, float* cw, float* feat,
-                         hipStream_t st, const MultiF* mf = nullptr) {
-  // 4 waves per SIMD either way: 4 / 2 / 1 workgroups of 4 / 8 / 16 rays per CU, whichever keeps
-  // alpha slices + lines within the CU's 160 KB (300^3: 8 + 29 KB x 4; 500^3: 18 + 48 KB x 2; 640^3: 47 + 61 KB x 1)
-  const size_t lds_l = (size_t)(d.ll[0] + d.ll[1] + d.ll[2]) * LRF_CD * sizeof(float);
-  const int nw = march_lds_rays(d.ll, S);
-  const int zlds = march_lds_z(d.ll, S, nw) ? 1 : 0;
-  const size_t lds_z = zlds ? (size_t)S * sizeof(float) : 0;
-  if (g_march_dump && !mf) {                               // test hook: phase clocks -> the dump buffer
-    DField dt = d;
-    dt.dump = reinterpret_cast<float*>(g_march_dump);
-    if (nw) hipLaunchKernelGGL(k_march_timed<true>, dim3((R + nw - 1) / nw), dim3(64 * nw), (size_t)nw * S * sizeof(float) + lds_l + lds_z + MARCH_LDS_TAIL, st,
-                               dt, rays, z, R, S, flags, floater, depth, acc, w_all, ncomp, gsum, cidx, cw, feat, zlds);
-    else    hipLaunchKernelGGL(k_march_timed<false>, dim3((R + 3) / 4), dim3(256), (size_t)4 * S * sizeof(float) + lds_z + MARCH_LDS_TAIL, st,
-                               dt, rays, z, R, S, flags, floater, depth, acc, w_all, ncomp, gsum, cidx, cw, feat, zlds);
-    return;
-  }
-  if (nw) {
-    const size_t lds = (size_t)nw * S * sizeof(float) + lds_l + lds_z + MARCH_LDS_TAIL;
-    if (mf) {                                              // (the caller made sure that Rf is a multiple of 16 >= nw)
-      hipLaunchKernelGGL((k_march<true, true>), dim3((R + nw - 1) / nw), dim3(64 * nw), lds, st,
-                         *mf, rays, z, R, S, flags, floater, depth, acc, w_all, ncomp, gsum, cidx, cw, feat, zlds);
-      return;
-    }
-    hipLaunchKernelGGL(k_march<true>, dim3((R + nw - 1) / nw), dim3(64 * nw), lds, st,
-                       d, rays, z, R, S, flags, floater, depth, acc, w_all, ncomp, gsum, cidx, cw, feat, zlds);
-  } else {
-    hipLaunchKernelGGL(k_march<false>, dim3((R + 3) / 4), dim3(256), (size_t)4 * S * sizeof(float) + lds_z + MARCH_LDS_TAIL, st,
-                       d, rays, z, R, S, flags, floater, depth, acc, w_all, ncomp, gsum, cidx, cw, feat, zlds);
-  }
-}
-
-// k_march's output -> colours: k_shade3 with its tile offsets built in the kernel from k_march's group sums (w.gsum) when they
-// fit in LDS beside the image, behind k_scan_tiles_n otherwise (toff32: R + 1 ints).  sv == nullptr: the eval forward; else the training forward, which
-// also leaves the rows of SaveOut3 (and sv->toff16 must not be toff32).  dump: lrf_debug_set_dump's buffer (eval only).
-static void launch_shade3(DField d, const float* rays, const float* z, int R, int S, uint32_t flags, const Workspace& w,
-                         int* toff32, float* rgb, float* acc_out, const SaveOut3* sv, float* dump, hipStream_t st) {
-  const size_t lds_base = (size_t)W32_ALL_U4 * sizeof(uint4) + (size_t)S * sizeof(float);
-  const size_t lds_toff = (size_t)(R + 1) * sizeof(int) + (size_t)R * sizeof(unsigned short) + 16;
-  const int gsz = march_group_rays(d.ll, S);      // k_march left w.gsum at this many rays per entry
-  // in LDS: R + 1 offsets and R 16-bit counts (absolute ray index; a workgroup fills only its own window) beside image and z,
-  // and no more group sums than one workgroup holds in registers
-  const bool in_lds = !g_no_lds_toff && lds_base + lds_toff + 64 <= 160 * 1024 - 256 && (R + gsz - 1) / gsz <= 512 * TILE_GPT;
-  const dim3 grid(device_cus()), block(512);
-  if (sv) {
-    if (in_lds) {
-      hipLaunchKernelGGL((k_shade3<8, true, false, true>), grid, block, lds_base + lds_toff, st,
-                         d, rays, z, S, w.gsum, R, w.ncomp, w.cidx, w.cw, w.part, w.pmax, flags, w.acc, rgb, acc_out, *sv, gsz);
-    } else {
-      hipLaunchKernelGGL(k_scan_tiles_n<ITEM3>, dim3(1), dim3(1024), 0, st, w.ncomp, R, toff32);
-      hipLaunchKernelGGL((k_shade3<8, false, false, true>), grid, block, lds_base, st,
-                         d, rays, z, S, toff32, R, w.ncomp, w.cidx, w.cw, w.part, w.pmax, flags, w.acc, rgb, acc_out, *sv, gsz);
-    }
-  } else if (in_lds && dump) {                    // test hook: phase timing, s_memtime totals -> the dump buffer
-    d.dump = dump;
-    hipLaunchKernelGGL((k_shade3<8, true, true>), grid, block, lds_base + lds_toff, st,
-                       d, rays, z, S, w.gsum, R, w.ncomp, w.cidx, w.cw, w.part, w.pmax, flags, w.acc, rgb, acc_out, SaveOut3{}, gsz);
-  } else if (in_lds) {
-    hipLaunchKernelGGL((k_shade3<8, true, false>), grid, block, lds_base + lds_toff, st,
-                       d, rays, z, S, w.gsum, R, w.ncomp, w.cidx, w.cw, w.part, w.pmax, flags, w.acc, rgb, acc_out, SaveOut3{}, gsz);
-  } else {
-    hipLaunchKernelGGL(k_scan_tiles_n<ITEM3>, dim3(1), dim3(1024), 0, st, w.ncomp, R, toff32);
-    hipLaunchKernelGGL((k_shade3<8, false, false>), grid, block, lds_base, st,
-                       d, rays, z, S, toff32, R, w.ncomp, w.cidx, w.cw, w.part, w.pmax, flags, w.acc, rgb, acc_out, SaveOut3{}, gsz);
-  }
-}
-
-// Several fields, one launch (see MultiF): global tile offsets over all virtual rays (k_scan_tiles_n), then the colour kernel.
-static void launch_shade3_multi(const MultiF& mf, const float* rays, const float* z, int Rv, int S, uint32_t flags,
-                                const Workspace& w, float* rgb, hipStream_t st) {
-  const size_t lds_base = (size_t)W32_ALL_U4 * sizeof(uint4) + (size_t)S * sizeof(float);
-  hipLaunchKernelGGL(k_scan_tiles_n<ITEM3>, dim3(1), dim3(1024), 0, st, w.ncomp, Rv, w.toff);
-  hipLaunchKernelGGL((k_shade3m<8, false>), dim3(device_cus()), dim3(512), lds_base, st,
-                     mf, rays, z, S, w.toff, Rv, w.ncomp, w.cidx, w.cw, w.part, w.pmax, flags, w.acc, rgb, (float*)nullptr, SaveOut3{}, 0);
-}
-
 }  // namespace lrf
 
 #include "lrf_generic.inl"
-namespace lrf {
-// network configuration of a field: null, or why it cannot be rendered
-static const char* gen_check(const LrfField* f) {
-  const int fc = f->feature_c ? f->feature_c : LRF_FEATC;
-  if (f->fea_pe < 0 || f->fea_pe > GEN_MAX_PE || f->view_pe < 0 || f->view_pe > GEN_MAX_PE || fc < 1 || fc > GEN_MAX_FC)
-    return "localrf: unsupported colour-network configuration (need 0 <= fea_pe, view_pe <= 6 and 1 <= featureC <= 256)";
-  if (!gen_is_default(f->fea_pe, f->view_pe, fc) && (!f->basis || !f->w1 || !f->b1 || !f->w2 || !f->b2 || !f->w3 || !f->b3))
-    return "localrf: a non-default colour-network configuration needs the natural-layout weights in LrfField (basis, w1 .. b3)";
-  return nullptr;
-}
-// the generic colour kernel behind k_march; toff32 != null: the training forward (also leaves colours, feat rows, tile records)
-static hipError_t launch_shade_gen(const DField& d, const GenCfg& gc, const float* rays, const float* z, int R, int S, const Workspace& w,
-                                   const int* toff32, float* crgb, float* act, int4* tileinfo, hipStream_t st) {
-  constexpr int ls = 32;                                      // (the forward's LDS image is at most ~116 KB (fea_pe = view_pe = 6, feature_c = 256), under the 159 KB opt-in)
-  const int nt = gen_block_threads(gc);
-  const size_t lds = (size_t)gen_lds(gc, ls, false).total * 4;
-  const dim3 grid(R * ((w.pmax * 16 + ls - 1) / ls));
-  if (toff32) hipLaunchKernelGGL((k_shade_gen<32, true>), grid, dim3(nt), lds, st, d, gc, rays, z, S, w.ncomp, w.cidx, w.cw, w.part, w.pmax, toff32, crgb, act, tileinfo);
-  else        hipLaunchKernelGGL((k_shade_gen<32, false>), grid, dim3(nt), lds, st, d, gc, rays, z, S, w.ncomp, w.cidx, w.cw, w.part, w.pmax, toff32, crgb, act, tileinfo);
-  return hipGetLastError();
-}
-}  // namespace lrf
+#include "lrf_forward.inl"
 #include "lrf_backward.inl"
 namespace lrf {
+// Every kernel that may ask for more than 64 KB of dynamic LDS, with the most it can ask for.  The forward's rows carry the
+// budgets its plans are held to (lrf_forward.inl): plan_march keeps a k_march<true> workgroup within MARCH_LDS_BUDGET + the tail
+// (static_assert there) and a k_march<false> one within MARCH_LDS_NOLINES; plan_shade3 keeps every form of the colour kernel
+// within SHADE3_LDS_CAP.
 static hipError_t lds_opt_in() {
-  constexpr int L160 = 160 * 1024;
+  constexpr int L160 = 160 * 1024, MARCH = (int)MARCH_LDS_OPT_IN, MARCH_NL = (int)MARCH_LDS_NOLINES, SHADE3 = (int)SHADE3_LDS_CAP;
   static const struct { const void* k; int bytes; } tab[] = {
     {reinterpret_cast<const void*>(&k_sort_rays), LRF_SORT_MAX_R * 4},
-    {reinterpret_cast<const void*>(&k_march<true>), L160},
-    {reinterpret_cast<const void*>(&k_march<true, true>), L160},
-    {reinterpret_cast<const void*>(&k_march_timed<true>), L160},
-    {reinterpret_cast<const void*>(&k_march<false>), 64 * 1024 + MARCH_LDS_TAIL},       // four alpha slices of S = 4096 are 64 KB, + the combine word of gsum
-    {reinterpret_cast<const void*>(&k_march_timed<false>), 64 * 1024 + MARCH_LDS_TAIL},
-    {reinterpret_cast<const void*>(&k_shade3<8, true, false>), L160 - 256},
-    {reinterpret_cast<const void*>(&k_shade3<8, false, false>), L160 - 256},
-    {reinterpret_cast<const void*>(&k_shade3<8, true, true>), L160 - 256},
-    {reinterpret_cast<const void*>(&k_shade3<8, true, false, true>), L160 - 256},
-    {reinterpret_cast<const void*>(&k_shade3<8, false, false, true>), L160 - 256},
-    {reinterpret_cast<const void*>(&k_shade3m<8, false>), L160 - 256},
+    {reinterpret_cast<const void*>(&k_march<true>), MARCH},
+    {reinterpret_cast<const void*>(&k_march<true, true>), MARCH},
+    {reinterpret_cast<const void*>(&k_march_timed<true>), MARCH},
+    {reinterpret_cast<const void*>(&k_march<false>), MARCH_NL},       // four alpha slices of S = 4096 are 64 KB, + the combine word of gsum
+    {reinterpret_cast<const void*>(&k_march_timed<false>), MARCH_NL},
+    {reinterpret_cast<const void*>(&k_shade3<8, true, false>), SHADE3},
+    {reinterpret_cast<const void*>(&k_shade3<8, false, false>), SHADE3},
+    {reinterpret_cast<const void*>(&k_shade3<8, true, true>), SHADE3},
+    {reinterpret_cast<const void*>(&k_shade3<8, true, false, true>), SHADE3},
+    {reinterpret_cast<const void*>(&k_shade3<8, false, false, true>), SHADE3},
+    {reinterpret_cast<const void*>(&k_shade3m<8, false>), SHADE3},
     {reinterpret_cast<const void*>(&k_shade_gen<32, false>), L160 - 1024},
     {reinterpret_cast<const void*>(&k_shade_gen<32, true>), L160 - 1024},
     {reinterpret_cast<const void*>(&k_gen_dgrad<32>), L160 - 1024},
@@ -1321,6 +1082,8 @@ static hipError_t lds_opt_in() {
 #include "lrf_tsdf_blocks.inl"
 #include "lrf_reg.inl"
 #include "lrf_mask.inl"
+#include "lrf_normals.inl"
+#include "lrf_quantile.inl"
 
 namespace lrf {
 // Test hook (lrf_debug_block_reduce): the workgroup reductions of lrf_common.h on a caller's rows, one workgroup per row of NT
@@ -1373,10 +1136,10 @@ int lrf_debug_tile_ranges(const int32_t* ncomp, int32_t R, int32_t G, int32_t nb
   const char* who = "lrf_debug_tile_ranges";
   if (!ncomp || !gsum || !ranges || !toff_out || !nc_out) return refuse(who, "null argument");
   if (R <= 0 || nb <= 0 || (G != 4 && G != 8 && G != 16)) return refuse(who, "need R > 0, nb > 0 and G in {4, 8, 16}");
-  const size_t lds = (size_t)(R + 1) * sizeof(int) + (size_t)R * sizeof(unsigned short) + 16;
+  const size_t lds = shade3_toff_lds(R);
   if (lds > 64 * 1024) return refuse(who, "R too large for 64 KB of LDS");
   const unsigned NG = blocks_for(R, G);
-  if (NG > 512 * TILE_GPT) return refuse(who, "more groups than one workgroup scans");
+  if (NG > SHADE3_MAX_GROUPS) return refuse(who, "more groups than one workgroup scans");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   LRF_TRY(launch(k_group_tiles, blocks_for(NG, 256), 256, st, ncomp, R, G, gsum));
   return launch_lds(k_tile_ranges_dbg, nb, 512, lds, st, gsum, ncomp, R, G, reinterpret_cast<int4*>(ranges), toff_out, nc_out);
@@ -1453,214 +1216,6 @@ int lrf_pack_field(const LrfParams* p, void* cache, void* stream) {
   return launch(k_pack_planes, dim3(blocks_for(wmax, 128), hmax, 19), 128, st, tab, *p, pm, 0);
 }
 
-// Large batches (full-frame evaluation: renderer.py:65-77 renders an image 4096 rays at a time) go through the two kernels
-// in chunks of g_pipe_chunk rays that alternate over the caller's stream and the side stream: a chunk's k_march and the
-// tail of its k_shade3 run beside the other stream's colour kernel (k_shade3 is one persistent workgroup per CU bound by
-// instruction issue at 46 %; k_march is latency / L2 bound).  65536 rays at configs[1]: 2.38 ms in one pass, 2.49 / 2.30 /
-// 2.24 / 2.26 / 2.30 ms in chunks of 4096 / 8192 / 16384 / 24576 / 32768 (scripts/pipe_chunk_probe.py; 262144 rays: 9.55 ->
-// 8.69 ms = 30.2 M rays/s); below two chunks of 16384 one pass is as fast or faster.  Every chunk has a workspace of its own
-// inside the caller's.
-static int pipe_chunks(int R) { return (g_pipe_chunk > 0 && R >= 2 * g_pipe_chunk) ? (R + g_pipe_chunk - 1) / g_pipe_chunk : 1; }
-size_t lrf_workspace_bytes(int32_t R, int32_t S) {
-  const size_t whole = carve(nullptr, R, S).bytes;
-  const int nc = pipe_chunks(R);
-  return nc > 1 ? std::max(whole, (size_t)nc * carve(nullptr, g_pipe_chunk, S).bytes) : whole;
-}
-
-// the colour network the split-bf16 kernels are built for: fea_pe = view_pe = 0, featureC = 128
-static bool default_net(const LrfField* f) { return gen_is_default(f->fea_pe, f->view_pe, f->feature_c ? f->feature_c : LRF_FEATC); }
-// Every refusal of the forward render, before anything is enqueued; null when the batch can be rendered.
-static const char* check_fwd(const LrfField* f, const float* rays, const float* z, const float* rgb, const float* depth,
-                             const void* workspace, int32_t R, int32_t S, uint32_t flags) {
-  if (!f || !f->cache || !rays || !z || !rgb || !depth || !workspace) return "lrf_render_fwd: null argument";
-  if (R <= 0 || S < 2 || S > 4096) return "lrf_render_fwd: need R > 0 and 2 <= S <= 4096";
-  if (flags & ~(LRF_FLAG_ALL & ~(LRF_FLAG_ROWS_SAVED | LRF_FLAG_PLANE_EVENTS))) return "lrf_render_fwd: unknown flag bits (caller built against another ABI version?)";
-  if (const char* bad = gen_check(f)) return bad;
-  if (!default_net(f) && (flags & LRF_FLAG_MLP_F32))
-    return "lrf_render_fwd: the exact-fp32 MFMA engine is built for fea_pe = view_pe = 0, featureC = 128 only";
-  return nullptr;
-}
-// the default engine: k_march -> k_shade3, two launches and no finalize kernel
-static bool fwd_shade3(const LrfField* f, uint32_t flags) { return default_net(f) && !(flags & (LRF_FLAG_MLP_VALU | LRF_FLAG_MLP_F32)); }
-
-// One batch of rays (accepted by check_fwd) through k_march and the colour stage on `st`; ev (optional,
-// lrf_render_fwd_profile): 4 events = start, after k_march, after the colour kernel(s), end.
-static int render_fwd_impl(const LrfField* f, const float* rays, const float* z, int32_t R, int32_t S,
-                           uint32_t flags, float floater_thresh, float* rgb, float* depth,
-                           float* weight_out, float* acc_out, void* workspace, hipStream_t st, hipEvent_t* ev) {
-  DField d = make_dfield(f);
-  const Workspace w = carve(workspace, R, S);
-  if (ev) LRF_HIP(hipEventRecord(ev[0], st));
-  rays = sort_rays_if_asked(d, rays, R, flags, w, st);
-  if (fwd_shade3(f, flags)) {
-    // Default engine: k_march -> k_shade3 (32 samples per wave on v_mfma_f32_32x32x16_bf16, lrf_shade3.inl); the tile
-    // offsets are built inside the colour kernel from k_march's group sums (w.gsum) when they fit in LDS beside the image,
-    // scanned by k_scan_tiles_n otherwise.
-    d.rdir = w.rdir;
-    launch_march(d, rays, z, R, S, flags, floater_thresh, depth, w.acc, weight_out, w.ncomp, w.gsum, w.cidx, w.cw, nullptr, st);
-    if (ev) LRF_HIP(hipEventRecord(ev[1], st));
-    launch_shade3(d, rays, z, R, S, flags, w, w.toff, rgb, acc_out, nullptr, g_dump, st);
-    if (ev) { LRF_HIP(hipEventRecord(ev[2], st)); LRF_HIP(hipEventRecord(ev[3], st)); }
-    LRF_HIP(hipGetLastError());
-    return 0;
-  }
-  // exact-fp32 / plain-loop engines: 16-sample tiles, k_march -> [k_scan_tiles ->] colour kernel -> k_finalize
-  launch_march(d, rays, z, R, S, flags, floater_thresh, depth, w.acc, weight_out, w.ncomp, nullptr /* no group sums: these engines scan the counts */, w.cidx, w.cw, nullptr, st);
-  if (ev) LRF_HIP(hipEventRecord(ev[1], st));
-  if (!default_net(f) || (flags & LRF_FLAG_MLP_VALU)) {
-    const GenCfg gc = gen_cfg(d.fea_pe, d.view_pe, d.fc, !(flags & LRF_FLAG_PE_OFF));
-    LRF_HIP(launch_shade_gen(d, gc, rays, z, R, S, w, nullptr, nullptr, nullptr, nullptr, st));
-  } else {
-    hipLaunchKernelGGL(k_scan_tiles, dim3(1), dim3(1024), 0, st, w.ncomp, R, w.toff);
-    hipLaunchKernelGGL(k_shade, dim3(device_cus()), dim3(1024), 0, st, d, rays, z, S, w.toff, R, w.ncomp, w.cidx, w.cw, w.part, w.pmax);
-  }
-  if (ev) LRF_HIP(hipEventRecord(ev[2], st));
-  hipLaunchKernelGGL(k_finalize, dim3((R + 255) / 256), dim3(256), 0, st, R, w.pmax, flags, w.ncomp, w.acc, w.part, rgb, acc_out, d.perm);
-  if (ev) LRF_HIP(hipEventRecord(ev[3], st));
-  LRF_HIP(hipGetLastError());
-  return 0;
-}
-
-// render_fwd_impl, large batches in chunks over two streams (see lrf_workspace_bytes); 0 or an error code
-static int render_fwd_pipelined(const LrfField* f, const float* rays, const float* z, int32_t R, int32_t S,
-                                uint32_t flags, float floater_thresh, float* rgb, float* depth,
-                                float* weight_out, float* acc_out, void* workspace, hipStream_t st) {
-  const int nc = pipe_chunks(R);
-  if (nc <= 1) return render_fwd_impl(f, rays, z, R, S, flags, floater_thresh, rgb, depth, weight_out, acc_out, workspace, st, nullptr);
-  TwoStreams ts(st, true);
-  if (!ts.overlapping()) return render_fwd_impl(f, rays, z, R, S, flags, floater_thresh, rgb, depth, weight_out, acc_out, workspace, st, nullptr);
-  LRF_TRY(ts.fork());
-  const size_t wb = carve(nullptr, g_pipe_chunk, S).bytes;
-  int rc = 0;
-  for (int c = 0; c < nc && rc == 0; ++c) {
-    const int r0 = c * g_pipe_chunk, rn = std::min(g_pipe_chunk, R - r0);
-    rc = render_fwd_impl(f, rays + (size_t)r0 * 6, z, rn, S, flags, floater_thresh, rgb + (size_t)r0 * 3, depth + r0,
-                         weight_out ? weight_out + (size_t)r0 * S : nullptr, acc_out ? acc_out + r0 : nullptr,
-                         static_cast<char*>(workspace) + (size_t)c * wb, (c & 1) ? ts.side() : st, nullptr);
-  }
-  LRF_TRY(ts.join());                                       // (also after an error: the side stream is joined again)
-  return rc;
-}
-
-int lrf_render_fwd(const LrfField* f, const float* rays, const float* z, int32_t R, int32_t S,
-                   uint32_t flags, float floater_thresh, float* rgb, float* depth,
-                   float* weight_out, float* acc_out, void* workspace, void* stream) {
-  if (const char* bad = check_fwd(f, rays, z, rgb, depth, workspace, R, S, flags)) return set_err(bad);
-  LRF_HIP(lds_opt_in());
-  return render_fwd_pipelined(f, rays, z, R, S, flags, floater_thresh, rgb, depth, weight_out, acc_out, workspace,
-                              reinterpret_cast<hipStream_t>(stream));
-}
-
-// LocalTensorfs.forward without a tape (local_tensorfs.py:397-499) as ONE call: the rays of every active field, the
-// per-field renders chunk by chunk in the reference's order (:440-474: for each chunk, for each field), the blend.  Same
-// launches as lrf_scene_rays + n_rf x lrf_render_fwd + lrf_scene_blend, enqueued from C: the host side of a 4-field scene
-// forward drops from 0.36 ms of Python per call to one ctypes call.  Every argument is checked before the first launch.
-int lrf_scene_fwd(const int64_t* ray_ids, int32_t R, int32_t per_view, const float* cam2world, const float* world2rf,
-                  int32_t n_rf, const float* focal, const float* center, int32_t W, int32_t H, int32_t fov360,
-                  const LrfSceneField* fields, float floater_thresh, int32_t chunk,
-                  const float* blend_w, const float* exposure,
-                  float* rays, float* rgb_f, float* depth_f, float* directions, int64_t* ij,
-                  float* rgbs, float* depth, void* scene_workspace, size_t scene_workspace_bytes, void* stream) {
-  if (!fields || !blend_w || !rays || !rgb_f || !depth_f || !rgbs || !depth) return set_err("lrf_scene_fwd: null argument");
-  if (n_rf <= 0 || n_rf > LRF_SCENE_MAX_FIELDS) return set_err("lrf_scene_fwd: 1 <= n_rf <= LRF_SCENE_MAX_FIELDS");
-  if (R < 0 || per_view <= 0 || R % per_view) return set_err("lrf_scene_fwd: R must be a multiple of per_view");
-  if (chunk <= 0) chunk = R;
-  for (int k = 0; k < n_rf; ++k) {
-    const LrfSceneField& sf = fields[k];
-    if (!sf.field || !sf.z || !sf.workspace) return set_err("lrf_scene_fwd: null field / z / workspace");
-    if (R > 0)                                                 // (each chunk of the field: rays, outputs and R inside these)
-      if (const char* bad = check_fwd(sf.field, rays, sf.z, rgb_f, depth_f, sf.workspace, std::min(chunk, R), sf.S, sf.flags)) return set_err(bad);
-  }
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  // Fused form: groups of up to LRF_MULTI_MAX fields in ONE march and ONE colour launch over their field-major "virtual" rays
-  // (3 launches per group and chunk instead of 2 per field; one prologue, one tail).  Needs: chunks of a multiple of 16 rays
-  // (a march workgroup stays inside one field; a ragged last chunk goes field by field), the default engine, and fields of one shape: same grid, sample count,
-  // flags, thresholds (their schedules z are then the same numbers).  `scene_workspace` (lrf_workspace_bytes(group rays, S))
-  // holds the group's per-ray state.  Same arithmetic per ray (depths bit-identical, colours to an ulp: a second compilation of the colour kernel).
-  bool fuse = scene_workspace && n_rf >= 2 && R > 0 && chunk % 16 == 0 && !g_no_scene_fuse;
-  for (int k = 0; fuse && k < n_rf; ++k) {
-    const LrfSceneField& a = fields[k], &b = fields[0];
-    if (!default_net(a.field)) fuse = false;
-    else if (a.flags & (LRF_FLAG_MLP_VALU | LRF_FLAG_MLP_F32 | LRF_FLAG_SORT_RAYS)) fuse = false;
-    else if (a.S != b.S || a.flags != b.flags || memcmp(a.field->grid, b.field->grid, sizeof(b.field->grid))) fuse = false;
-    else if (a.field->weight_thres != b.field->weight_thres || a.field->term_T != b.field->term_T) fuse = false;
-  }
-  if (fuse && floater_thresh > 0.0f) fuse = false;             // (the floater filter's second pass: per-field path)
-  if (fuse) {                                                  // k_march<MULTI> keeps the density lines in LDS: no such form without them
-    const int32_t* g = fields[0].field->grid;                  // (line p runs along axis VEC[p]: the three lengths are the three grid sizes)
-    const int32_t ll[3] = {g[0], g[1], g[2]};
-    if (!march_lds_rays(ll, fields[0].S)) fuse = false;
-  }
-  // the largest group is the first one of the first chunk (the workspace grows with the rays); a ragged first chunk forms none
-  const int32_t S = fields[0].S, n0 = std::min(chunk, R);
-  if (fuse && n0 % 16 == 0 && lrf_workspace_bytes(std::min(n_rf, LRF_MULTI_MAX) * n0, S) > scene_workspace_bytes)
-    return set_err("lrf_scene_fwd: scene workspace too small");
-  int rc = lrf_scene_rays(ray_ids, R, per_view, cam2world, world2rf, n_rf, focal, center, W, H, fov360, rays, directions, ij, stream);
-  if (rc) return rc;
-  LRF_HIP(lds_opt_in());
-  for (int32_t lo = 0; lo < R; lo += chunk) {                  // chunk by chunk, as the field-by-field form (:440)
-    const int32_t n = R - lo < chunk ? R - lo : chunk;
-    if (!fuse || n % 16) {                                     // field by field (in the fused form: a ragged last chunk)
-      for (int k = 0; k < n_rf; ++k) {
-        const LrfSceneField& sf = fields[k];
-        rc = render_fwd_pipelined(sf.field, rays + ((size_t)k * R + lo) * 6, sf.z, n, sf.S, sf.flags, floater_thresh,   // (chunks of 32768 rays and more: over two streams)
-                                  rgb_f + ((size_t)k * R + lo) * 3, depth_f + (size_t)k * R + lo, nullptr, nullptr, sf.workspace, st);
-        if (rc) return rc;
-      }
-      continue;
-    }
-    for (int k0 = 0; k0 < n_rf; k0 += LRF_MULTI_MAX) {
-      const int nf = n_rf - k0 < LRF_MULTI_MAX ? n_rf - k0 : LRF_MULTI_MAX;
-      const int Rv = nf * n;
-      const Workspace w = carve(scene_workspace, Rv, S);
-      MultiF mf;
-      mf.nf = nf; mf.Rf = n; mf.Rs = R; mf.lo = lo;
-      for (int k = 0; k < nf; ++k) { mf.f[k] = make_dfield(fields[k0 + k].field); mf.f[k].rdir = w.rdir; }
-      for (int k = nf; k < LRF_MULTI_MAX; ++k) mf.f[k] = mf.f[0];
-      const float* rv = rays + (size_t)k0 * R * 6;             // field k of the group: rays [k0 + k][lo + r], outputs likewise (multi_io)
-      launch_march(mf.f[0], rv, fields[k0].z, Rv, S, fields[k0].flags, 0.0f, depth_f + (size_t)k0 * R, w.acc, nullptr,
-                   w.ncomp, nullptr /* k_shade3m reads k_scan_tiles_n's offsets */, w.cidx, w.cw, nullptr, st, &mf);
-      launch_shade3_multi(mf, rv, fields[k0].z, Rv, S, fields[k0].flags, w, rgb_f + (size_t)k0 * R * 3, st);
-    }
-  }
-  LRF_HIP(hipGetLastError());
-  return lrf_scene_blend(rgb_f, depth_f, blend_w, exposure, R, per_view, n_rf, rgbs, depth, nullptr, stream);
-}
-
-int lrf_render_fwd_profile(const LrfField* f, const float* rays, const float* z, int32_t R, int32_t S,
-                           uint32_t flags, float floater_thresh, float* rgb, float* depth,
-                           void* workspace, void* stream, float* ms_out, int32_t* n_shaded_out) {
-  if (!ms_out) return set_err("lrf_render_fwd_profile: null ms_out");
-  if (const char* bad = check_fwd(f, rays, z, rgb, depth, workspace, R, S, flags)) return set_err(bad);
-  LRF_HIP(lds_opt_in());
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  hipEvent_t ev[4];
-  for (int i = 0; i < 4; ++i) LRF_HIP(hipEventCreate(&ev[i]));
-  int rc = render_fwd_impl(f, rays, z, R, S, flags, floater_thresh, rgb, depth, nullptr, nullptr, workspace, st, ev);
-  if (rc == 0) {
-    hipError_t e = hipStreamSynchronize(st);
-    if (e != hipSuccess) rc = set_err("hipStreamSynchronize", e);
-  }
-  if (rc == 0) {
-    for (int i = 0; i < 3; ++i) (void)hipEventElapsedTime(&ms_out[i], ev[i], ev[i + 1]);      // march, colour stage, finalize (0 for the default engine)
-    (void)hipEventElapsedTime(&ms_out[3], ev[0], ev[3]);
-    if (fwd_shade3(f, flags)) { ms_out[2] = 0.0f; (void)hipEventElapsedTime(&ms_out[3], ev[0], ev[2]); }
-    ms_out[4] = ms_out[5] = 0.0f;
-    if (n_shaded_out) {
-      // shaded-sample count of this batch = sum of ncomp (host copy; measurement only)
-      const Workspace w = carve(workspace, R, S);
-      int* h = (int*)malloc((size_t)R * sizeof(int));
-      if (h && hipMemcpy(h, w.ncomp, (size_t)R * sizeof(int), hipMemcpyDeviceToHost) == hipSuccess) {
-        long long tot = 0; for (int i = 0; i < R; ++i) tot += h[i];
-        *n_shaded_out = (int32_t)tot;
-      }
-      free(h);
-    }
-  }
-  for (int i = 0; i < 4; ++i) (void)hipEventDestroy(ev[i]);
-  return rc;
-}
-
 int lrf_density_feature(const LrfField* f, const float* u, int32_t P, float* out, void* stream) {
   if (!f || !f->cache || !u || !out) return refuse("lrf_density_feature", "null argument");
   if (P <= 0) return 0;
@@ -1699,6 +1254,3 @@ int lrf_sample_ray_contracted(const float* rays_o, const float* rays_d, const fl
 }
 
 }  // extern "C"
-
-#include "lrf_normals.inl"
-#include "lrf_quantile.inl"

@@ -260,6 +260,89 @@ extern "C" int lrf_scene_blend_bwd(const float* g_rgbs, const float* g_depth, co
                 g_rgbs, g_depth, pre, blend_w, exposure, R, per_view, n_rf, g_rgb_f, g_depth_f, g_exposure);
 }
 
+namespace lrf {
+// Whether lrf_scene_fwd renders groups of fields in ONE march and ONE colour launch.  Needs: a scene workspace, chunks of a
+// multiple of 16 rays (a march workgroup stays inside one field), the default engine, no floater filter (its second pass goes
+// field by field), fields of one shape -- same grid, sample count, flags, thresholds (their schedules z are then the same
+// numbers) -- and a march plan with the density lines in LDS (m: of fields[0]; k_march<MULTI> has no other form).
+static bool scene_fuses(const LrfSceneField* fields, int n_rf, int R, int chunk, float floater_thresh, bool have_workspace, bool fuse_on,
+                        const MarchPlan& m) {
+  if (!have_workspace || n_rf < 2 || R <= 0 || chunk % 16 != 0 || !fuse_on || floater_thresh > 0.0f || !m.nw) return false;
+  const LrfSceneField& b = fields[0];
+  for (int k = 0; k < n_rf; ++k) {
+    const LrfSceneField& a = fields[k];
+    if (!default_net(a.field) || (a.flags & (LRF_FLAG_MLP_VALU | LRF_FLAG_MLP_F32 | LRF_FLAG_SORT_RAYS))) return false;
+    if (a.S != b.S || a.flags != b.flags || memcmp(a.field->grid, b.field->grid, sizeof(b.field->grid))) return false;
+    if (a.field->weight_thres != b.field->weight_thres || a.field->term_T != b.field->term_T) return false;
+  }
+  return true;
+}
+}  // namespace lrf
+
+// LocalTensorfs.forward without a tape (local_tensorfs.py:397-499) as ONE call: the rays of every active field, the
+// per-field renders chunk by chunk in the reference's order (:440-474: for each chunk, for each field), the blend.  Same
+// launches as lrf_scene_rays + n_rf x lrf_render_fwd + lrf_scene_blend, enqueued from C: the host side of a 4-field scene
+// forward drops from 0.36 ms of Python per call to one ctypes call.  Every argument is checked before the first launch.
+extern "C" int lrf_scene_fwd(const int64_t* ray_ids, int32_t R, int32_t per_view, const float* cam2world, const float* world2rf,
+                             int32_t n_rf, const float* focal, const float* center, int32_t W, int32_t H, int32_t fov360,
+                             const LrfSceneField* fields, float floater_thresh, int32_t chunk,
+                             const float* blend_w, const float* exposure,
+                             float* rays, float* rgb_f, float* depth_f, float* directions, int64_t* ij,
+                             float* rgbs, float* depth, void* scene_workspace, size_t scene_workspace_bytes, void* stream) {
+  using namespace lrf;
+  if (!fields || !blend_w || !rays || !rgb_f || !depth_f || !rgbs || !depth) return set_err("lrf_scene_fwd: null argument");
+  if (n_rf <= 0 || n_rf > LRF_SCENE_MAX_FIELDS) return set_err("lrf_scene_fwd: 1 <= n_rf <= LRF_SCENE_MAX_FIELDS");
+  if (R < 0 || per_view <= 0 || R % per_view) return set_err("lrf_scene_fwd: R must be a multiple of per_view");
+  if (chunk <= 0) chunk = R;
+  for (int k = 0; k < n_rf; ++k) {
+    const LrfSceneField& sf = fields[k];
+    if (!sf.field || !sf.z || !sf.workspace) return set_err("lrf_scene_fwd: null field / z / workspace");
+    if (R > 0)                                                 // (each chunk of the field: rays, outputs and R inside these)
+      if (const char* bad = check_fwd(sf.field, rays, sf.z, rgb_f, depth_f, sf.workspace, std::min(chunk, R), sf.S, sf.flags)) return set_err(bad);
+  }
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  // Fused form: groups of up to LRF_MULTI_MAX fields over their field-major "virtual" rays (3 launches per group and chunk
+  // instead of 2 per field; one prologue, one tail); a ragged last chunk goes field by field.  `scene_workspace`
+  // (lrf_workspace_bytes(group rays, S)) holds the group's per-ray state.  Same arithmetic per ray (depths bit-identical,
+  // colours to an ulp: a second compilation of the colour kernel).
+  const int32_t S = fields[0].S, n0 = std::min(chunk, R);
+  const bool fuse = scene_fuses(fields, n_rf, R, chunk, floater_thresh, scene_workspace != nullptr, !g_no_scene_fuse,
+                                plan_march(fields[0].field->grid /* line p runs along axis VEC[p]: the three line lengths are the three grid sizes */, n0, S));
+  // the largest group is the first one of the first chunk (the workspace grows with the rays); a ragged first chunk forms none
+  if (fuse && n0 % 16 == 0 && lrf_workspace_bytes(std::min(n_rf, LRF_MULTI_MAX) * n0, S) > scene_workspace_bytes)
+    return set_err("lrf_scene_fwd: scene workspace too small");
+  int rc = lrf_scene_rays(ray_ids, R, per_view, cam2world, world2rf, n_rf, focal, center, W, H, fov360, rays, directions, ij, stream);
+  if (rc) return rc;
+  LRF_HIP(lds_opt_in());
+  for (int32_t lo = 0; lo < R; lo += chunk) {                  // chunk by chunk, as the field-by-field form (:440)
+    const int32_t n = R - lo < chunk ? R - lo : chunk;
+    if (!fuse || n % 16) {                                     // field by field (in the fused form: a ragged last chunk)
+      for (int k = 0; k < n_rf; ++k) {
+        const LrfSceneField& sf = fields[k];
+        rc = render_fwd_pipelined(sf.field, rays + ((size_t)k * R + lo) * 6, sf.z, n, sf.S, sf.flags, floater_thresh,   // (chunks of 32768 rays and more: over two streams)
+                                  rgb_f + ((size_t)k * R + lo) * 3, depth_f + (size_t)k * R + lo, nullptr, nullptr, sf.workspace, st);
+        if (rc) return rc;
+      }
+      continue;
+    }
+    for (int k0 = 0; k0 < n_rf; k0 += LRF_MULTI_MAX) {
+      const int nf = n_rf - k0 < LRF_MULTI_MAX ? n_rf - k0 : LRF_MULTI_MAX;
+      const int Rv = nf * n;
+      const Workspace w = carve(scene_workspace, Rv, S);
+      MultiF mf;
+      mf.nf = nf; mf.Rf = n; mf.Rs = R; mf.lo = lo;
+      for (int k = 0; k < nf; ++k) { mf.f[k] = make_dfield(fields[k0 + k].field); mf.f[k].rdir = w.rdir; }
+      for (int k = nf; k < LRF_MULTI_MAX; ++k) mf.f[k] = mf.f[0];
+      const float* rv = rays + (size_t)k0 * R * 6;             // field k of the group: rays [k0 + k][lo + r], outputs likewise (multi_io)
+      launch_march(plan_march(mf.f[0].ll, Rv, S), mf, rv, fields[k0].z, Rv, S, fields[k0].flags, 0.0f,
+                   march_io(w, depth_f + (size_t)k0 * R, nullptr, nullptr, false /* k_shade3m reads k_scan_tiles_n's offsets */), st);
+      launch_shade3_multi(mf, rv, fields[k0].z, Rv, S, fields[k0].flags, w, rgb_f + (size_t)k0 * R * 3, st);
+    }
+  }
+  LRF_HIP(hipGetLastError());
+  return lrf_scene_blend(rgb_f, depth_f, blend_w, exposure, R, per_view, n_rf, rgbs, depth, nullptr, stream);
+}
+
 // ---------------------------------------------------------------------------------------------
 // Pose assembly: LocalTensorfs.get_cam2world (local_tensorfs.py:292-299) + sixD_to_mtx
 // (utils/utils.py:381-388) for up to LRF_POSE_MAX frames per launch.  The per-frame parameters are
