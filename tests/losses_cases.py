@@ -85,6 +85,16 @@ def tolerance(e32, quantity):
     return min(max(4.0 * e32, FLOOR), cap_of(quantity))
 
 
+def _not_stale(table, measured, key, floor=FLOOR):
+    """The recorded and the measured error agree within 2 x.  Below floor / 4 an error does not enter the tolerance
+    (max(4 e32, FLOOR)), and a single float32 result can be exact by chance: both are raised to that before comparing."""
+    assert set(table) == set(measured), key
+    lo = floor / 4
+    for q in table:
+        a, b = max(table[q], lo), max(measured[q], lo)
+        assert a <= 2 * b and b <= 2 * a, (key, q, table[q], measured[q])
+
+
 # ------------------------------------------------------------------------------------------------------- geometric cases
 def _poses(F, gen, rot=0.05, trans=0.2):
     r6 = torch.eye(3)[:, :2][None].repeat(F, 1, 1) + rot * torch.randn(F, 3, 2, generator=gen)

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+from abi_util import FAKE, refused
 from util import FIELD_KW, load_golden, make_field, quiet
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -285,7 +286,7 @@ def test_render_path_refuses_before_any_hip_call():
     import ctypes as C
     from localrf_amd import _native as N
     lib = N.lib()
-    fake = C.c_void_p(0x10000)                                      # non-null, 16-byte aligned; never dereferenced here
+    fake = C.c_void_p(FAKE)
 
     def field(n):
         f = N.LrfField(cache=fake, feature_c=128)
@@ -297,12 +298,9 @@ def test_render_path_refuses_before_any_hip_call():
         return lib.lrf_render_bwd(C.byref(f), C.byref(N.LrfParams()), fake, fake, 64, 64, flags, fake, fake,
                                   C.byref(g), fake, fake, None)
 
-    def last():
-        return lib.lrf_last_error().decode()
-
-    assert bwd(field(64), zero_base=fake, zero_floats=3) != 0 and "zero_floats must name" in last()
-    assert bwd(field(64), zero_base=C.c_void_p(0x10004), zero_floats=4) != 0 and "zero_floats must name" in last()
-    assert bwd(field(700), N.LRF_FLAG_DETERMINISTIC) != 0 and "DETERMINISTIC covers lines up to 640 cells" in last()
+    assert "zero_floats must name" in refused(lib, bwd(field(64), zero_base=fake, zero_floats=3))
+    assert "zero_floats must name" in refused(lib, bwd(field(64), zero_base=C.c_void_p(0x10004), zero_floats=4))
+    assert "DETERMINISTIC covers lines up to 640 cells" in refused(lib, bwd(field(700), N.LRF_FLAG_DETERMINISTIC))
 
     fs = [field(64) for _ in range(2)]
     sf = (N.LrfSceneField * 2)(*[N.LrfSceneField(field=C.pointer(f), z=fake, S=64, flags=0, workspace=fake) for f in fs])
@@ -311,8 +309,8 @@ def test_render_path_refuses_before_any_hip_call():
         return lib.lrf_scene_fwd(fake, 64, 64, fake, fake, 2, fake, fake, 8, 8, 0, sf, 0.0, 64, blend_w, None,
                                  fake, fake, fake, fake, fake, fake, fake, fake, ws_bytes, None)
 
-    assert scene(None, 1 << 40) != 0 and last() == "lrf_scene_fwd: null argument"
-    assert scene(fake, 1) != 0 and last() == "lrf_scene_fwd: scene workspace too small"
+    assert refused(lib, scene(None, 1 << 40)) == "lrf_scene_fwd: null argument"
+    assert refused(lib, scene(fake, 1)) == "lrf_scene_fwd: scene workspace too small"
 
 
 def test_saved_row_layout_is_a_bijection_and_matches_the_test_reader(built_lib):

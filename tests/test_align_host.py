@@ -7,18 +7,17 @@ from the 1500 blob points to 3.8e-8 (bar 1e-6); the plane solve iterated with th
 1.4e-8 within 5 or 6 iterations on the eight blob runs (bar 1e-5, the GPU test's)."""
 import ctypes as C
 import math
-import os
 
 import numpy as np
 import pytest
 import torch
 
+from abi_util import FAKE, declared_exported_bound, filled, refused
 from align_cases import (ICP_BAR, ICP_RUNS, PERTURBATIONS, apply, blob, blob_points, deviation, icp_plane_host, pair_inputs, pairs_host,
                          parts, sim, source_cloud, truth, umeyama_host)
 from localrf_amd import NativeError, alignment
 from mesh_util import cpu_mesh, forbid_native
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMBOLS = ("lrf_align_transform", "lrf_align_pairs", "lrf_align_plane")
 KERNELS = ("k_al_transform", "k_al_pairs", "k_al_plane")
 T_FIT = sim(0.4, 1.07, 0.0, axis=(1.0, 2.0, 3.0), t=(0.3, -0.2, 0.5))
@@ -26,43 +25,29 @@ T_FIT = sim(0.4, 1.07, 0.0, axis=(1.0, 2.0, 3.0), t=(0.3, -0.2, 0.5))
 
 def test_symbols_declared_exported_bound_and_checked(built_lib):
     from localrf_amd import _native as N
-    header = open(os.path.join(ROOT, "include", "lrf.h")).read()
-    for name in SYMBOLS:
-        assert name in N.SYMBOLS and f"{name}(" in header
-        getattr(built_lib, name)
+    header = declared_exported_bound(built_lib, SYMBOLS)
     assert "typedef struct LrfAlignFrame" in header and C.sizeof(N.LrfAlignFrame) == 4 * 8
     assert "typedef struct LrfAlignPlane" in header and C.sizeof(N.LrfAlignPlane) == 6 * 8 + 3 * 8 + 4 * 8 + 2 * 4
     assert built_lib.lrf_abi_version() == 7
     import __graft_entry__ as ge
     import localrf_amd
     assert "lrf_align.inl" in ge.HEADERS and "alignment" in localrf_amd.__all__ and "alignment." in localrf_amd.__doc__
-    fake = 0x10000
 
-    def err(rc, who):
-        assert rc != 0                                                          # every call here must be refused: nothing may launch
-        msg = built_lib.lrf_last_error().decode()
-        assert msg.startswith(who + ": "), msg
-        return msg
-
-    def transform(T=tuple(range(12)), points=fake, n=5, out=fake):
+    def transform(T=tuple(range(12)), points=FAKE, n=5, out=FAKE):
         arr = (C.c_double * 12)(*T) if T is not None else None
-        return err(built_lib.lrf_align_transform(arr, points, n, out, None), "lrf_align_transform")
+        return refused(built_lib, built_lib.lrf_align_transform(arr, points, n, out, None), "lrf_align_transform")
     assert "0 <= N" in transform(n=-1) and "0 <= N" in transform(n=1 << 31)
     for bad in (dict(T=None), dict(points=None), dict(out=None)):
         assert transform(**bad).endswith(": null argument"), bad
-    assert "4-byte aligned" in transform(points=fake + 2) and "4-byte aligned" in transform(out=fake + 1)
+    assert "4-byte aligned" in transform(points=FAKE + 2) and "4-byte aligned" in transform(out=FAKE + 1)
     for bad in (math.nan, math.inf):
         assert "finite" in transform(T=(1.0,) * 11 + (bad,))
 
-    def frame(c=(0.0, 0.0, 0.0), h=0.5):
-        fr = N.LrfAlignFrame()
-        fr.h = h
-        for k in range(3):
-            fr.c[k] = c[k]
-        return fr
+    def frame(**over):
+        return filled(N.LrfAlignFrame, dict(c=(0.0, 0.0, 0.0), h=0.5), **over)
 
-    def pairs(fr=True, a=fake, b=fake, keep=None, n=9, words=fake, **over):
-        return err(built_lib.lrf_align_pairs(C.byref(frame(**over)) if fr else None, a, b, keep, n, words, None), "lrf_align_pairs")
+    def pairs(fr=True, a=FAKE, b=FAKE, keep=None, n=9, words=FAKE, **over):
+        return refused(built_lib, built_lib.lrf_align_pairs(C.byref(frame(**over)) if fr else None, a, b, keep, n, words, None), "lrf_align_pairs")
     for bad in (dict(fr=False), dict(a=None), dict(b=None), dict(words=None)):
         assert pairs(**bad).endswith(": null argument"), bad
     assert "N <= 2^20" in pairs(n=-1) and "N <= 2^20" in pairs(n=(1 << 20) + 1)
@@ -70,19 +55,12 @@ def test_symbols_declared_exported_bound_and_checked(built_lib):
         assert "power of two" in pairs(h=bad), bad
     for bad in ((math.nan, 0.0, 0.0), (0.0, math.inf, 0.0), (0.0, 0.0, -math.inf)):
         assert "c must be finite" in pairs(c=bad), bad
-    assert "4-byte aligned" in pairs(a=fake + 2) and "4-byte aligned" in pairs(b=fake + 1) and "8-byte aligned" in pairs(words=fake + 4)
+    assert "4-byte aligned" in pairs(a=FAKE + 2) and "4-byte aligned" in pairs(b=FAKE + 1) and "8-byte aligned" in pairs(words=FAKE + 4)
 
-    def plane(p=True, words=fake, **over):
-        a = N.LrfAlignPlane()
-        a.vertices, a.faces, a.points, a.closest, a.face, a.distance = (fake,) * 6
-        a.Nv, a.Nf, a.N, a.u, a.gate = 5, 3, 9, 2.0, math.inf
-        for k, v in over.items():
-            if k == "c":
-                for i in range(3):
-                    a.c[i] = v[i]
-            else:
-                setattr(a, k, v)
-        return err(built_lib.lrf_align_plane(C.byref(a) if p else None, words, None), "lrf_align_plane")
+    def plane(p=True, words=FAKE, **over):
+        a = filled(N.LrfAlignPlane, dict(vertices=FAKE, faces=FAKE, points=FAKE, closest=FAKE, face=FAKE, distance=FAKE, Nv=5, Nf=3, N=9,
+                                         u=2.0, gate=math.inf), **over)
+        return refused(built_lib, built_lib.lrf_align_plane(C.byref(a) if p else None, words, None), "lrf_align_plane")
     for bad in (dict(p=False), dict(words=None), dict(vertices=None), dict(faces=None), dict(points=None), dict(closest=None),
                 dict(face=None), dict(distance=None)):
         assert plane(**bad).endswith(": null argument"), bad
@@ -94,10 +72,10 @@ def test_symbols_declared_exported_bound_and_checked(built_lib):
         assert "power of two" in plane(u=bad), bad
     assert "c must be finite" in plane(c=(0.0, math.nan, 0.0)) and "c must be finite" in plane(c=(math.inf, 0.0, 0.0))
     assert "gate" in plane(gate=-1.0) and "gate" in plane(gate=math.nan)
-    for bad in (dict(vertices=fake + 2), dict(faces=fake + 1), dict(points=fake + 2), dict(closest=fake + 1), dict(face=fake + 3),
-                dict(distance=fake + 2)):
+    for bad in (dict(vertices=FAKE + 2), dict(faces=FAKE + 1), dict(points=FAKE + 2), dict(closest=FAKE + 1), dict(face=FAKE + 3),
+                dict(distance=FAKE + 2)):
         assert "4-byte aligned" in plane(**bad), bad
-    assert "8-byte aligned" in plane(words=fake + 4)
+    assert "8-byte aligned" in plane(words=FAKE + 4)
 
 
 def test_python_refusals_before_any_native_call(monkeypatch):
@@ -278,13 +256,5 @@ def test_the_sums_cannot_overflow():
 
 def test_align_kernels_use_no_scratch():
     """The kernels of lrf_align.inl as __graft_entry__.build() compiles them: the metadata only."""
-    import re
-    from test_isa_checks import BUILD_FLAGS, _device_asm
-    asm = _device_asm(BUILD_FLAGS)
-    for name in KERNELS:
-        hits = re.findall(r"\.amdhsa_kernel (_Z\w*?\d+" + name + r"E\w*)", asm)
-        assert len(hits) == 1, (name, hits)
-        meta = asm[asm.index(".amdhsa_kernel " + hits[0]):]
-        meta = meta[:meta.index(".end_amdhsa_kernel")]
-        priv = re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", meta)
-        assert priv and int(priv[1]) == 0, (name, priv and priv[1])
+    from isa_util import assert_no_scratch, device_asm
+    assert_no_scratch(device_asm(), KERNELS, match="exact")

@@ -4,12 +4,12 @@ C ABI), the new symbols and struct sizes, the workspace sizes, icp's new refusal
 import ctypes as C
 import math
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
+from abi_util import FAKE, declared_exported_bound, filled, refused
 from localrf_amd import NativeError, alignment, cloud
 from localrf_amd.cloud import CloudIndex, cloud_distance, cloud_to_cloud, nearest_spacing, remove_outliers, voxel_downsample
 from cloud_cases import (CASE_NAMES, CLOUD_SIZES, NONE, QUERY_SIZES, box_host, cases, cell_sweep, default_point_cell_host, dims_host,
@@ -255,10 +255,7 @@ def test_icp_refuses_planes_on_a_cloud_before_any_launch(monkeypatch):
 
 def test_symbols_declared_exported_bound_and_checked(built_lib):
     from localrf_amd import _native as N
-    header = open(os.path.join(ROOT, "include", "lrf.h")).read()
-    for name in SYMBOLS:
-        assert name in N.SYMBOLS and f"{name}(" in header
-        getattr(built_lib, name)
+    header = declared_exported_bound(built_lib, SYMBOLS)
     assert "typedef struct LrfCloudIndex" in header and C.sizeof(N.LrfCloudIndex) == 3 * 8 + 2 * 8 + 4 * 8 + 4 * 4
     assert "typedef struct LrfCloudVoxel" in header and C.sizeof(N.LrfCloudVoxel) == 2 * 8 + 8 + 4 * 8 + 6 * 4
     assert "#define LRF_CLOUD_MAX_K 8" in header and N.LRF_CLOUD_MAX_K == 8 == cloud.MAX_K
@@ -266,37 +263,21 @@ def test_symbols_declared_exported_bound_and_checked(built_lib):
     assert "lrf_cloud.inl" in ge.HEADERS
     src = open(os.path.join(ROOT, "localrf_amd", "csrc", "lrf_render.hip")).read()
     assert src.index('#include "lrf_align.inl"') < src.index('#include "lrf_cloud.inl"')
-    fake = 0x10000
-
-    def err(rc):
-        assert rc != 0                                                          # every call here must be refused: nothing may launch
-        return built_lib.lrf_last_error().decode()
 
     def index(**over):
-        a = N.LrfCloudIndex()
-        a.points, a.grid, a.records = fake, fake, fake
-        a.M, a.entries, a.cell = 9, 7, 0.5
-        for k in range(3):
-            a.lo[k], a.dims[k] = 0.0, 4
-        for k, v in over.items():
-            if k in ("lo", "dims"):
-                for i in range(3):
-                    getattr(a, k)[i] = v[i]
-            else:
-                setattr(a, k, v)
-        return a
+        return filled(N.LrfCloudIndex, dict(points=FAKE, grid=FAKE, records=FAKE, M=9, entries=7, cell=0.5, lo=(0.0,) * 3, dims=(4,) * 3), **over)
 
     def build(**over):
-        return err(built_lib.lrf_cloud_index_build(C.byref(index(**over)), None))
+        return refused(built_lib, built_lib.lrf_cloud_index_build(C.byref(index(**over)), None))
 
-    def closest(points=fake, n=9, md=math.inf, dist=fake, idx=fake, cl=None, **over):
-        return err(built_lib.lrf_cloud_closest(C.byref(index(**over)), points, n, md, dist, idx, cl, None))
+    def closest(points=FAKE, n=9, md=math.inf, dist=FAKE, idx=FAKE, cl=None, **over):
+        return refused(built_lib, built_lib.lrf_cloud_closest(C.byref(index(**over)), points, n, md, dist, idx, cl, None))
 
-    def knn(points=fake, n=9, k=3, md=math.inf, first=-1, dist=fake, idx=fake, **over):
-        return err(built_lib.lrf_cloud_knn(C.byref(index(**over)), points, n, k, md, first, dist, idx, None))
+    def knn(points=FAKE, n=9, k=3, md=math.inf, first=-1, dist=FAKE, idx=FAKE, **over):
+        return refused(built_lib, built_lib.lrf_cloud_knn(C.byref(index(**over)), points, n, k, md, first, dist, idx, None))
 
-    def count(points=fake, n=9, radius=0.5, first=-1, out=fake, **over):
-        return err(built_lib.lrf_cloud_radius_count(C.byref(index(**over)), points, n, radius, first, out, None))
+    def count(points=FAKE, n=9, radius=0.5, first=-1, out=FAKE, **over):
+        return refused(built_lib, built_lib.lrf_cloud_radius_count(C.byref(index(**over)), points, n, radius, first, out, None))
     for who, call in (("lrf_cloud_index_build", build), ("lrf_cloud_closest", closest), ("lrf_cloud_knn", knn), ("lrf_cloud_radius_count", count)):
         for bad in (dict(M=0), dict(M=1 << 31)):
             assert call(**bad) == who + ": need 1 <= M < 2^31", bad
@@ -308,64 +289,55 @@ def test_symbols_declared_exported_bound_and_checked(built_lib):
             assert "finite cell" in call(**bad), bad
         for bad in (dict(points=None) if call is build else dict(records=None), dict(grid=None)):
             assert call(**bad).startswith(who) and ("null argument" in call(**bad) or "records" in call(**bad)), bad
-        assert "8-byte aligned" in call(grid=fake + 4) and "16-byte aligned" in call(records=fake + 8) and "16-byte aligned" in call(records=fake + 4)
-    assert "4-byte aligned" in build(points=fake + 2) and build(records=None).endswith(": null argument")
-    assert built_lib.lrf_cloud_index_build(None, None) != 0 and built_lib.lrf_cloud_closest(None, fake, 1, 1.0, fake, fake, None, None) != 0
+        assert "8-byte aligned" in call(grid=FAKE + 4) and "16-byte aligned" in call(records=FAKE + 8) and "16-byte aligned" in call(records=FAKE + 4)
+    assert "4-byte aligned" in build(points=FAKE + 2) and build(records=None).endswith(": null argument")
+    assert built_lib.lrf_cloud_index_build(None, None) != 0 and built_lib.lrf_cloud_closest(None, FAKE, 1, 1.0, FAKE, FAKE, None, None) != 0
     for call in (closest, knn, count):
         assert "1 <= N" in call(n=0) and "1 <= N" in call(n=1 << 31)
-        assert call(points=None).endswith(": null argument") and "4-byte aligned" in call(points=fake + 2)
+        assert call(points=None).endswith(": null argument") and "4-byte aligned" in call(points=FAKE + 2)
         assert "records of a built index" in call(records=None)
     for call in (closest, knn):
         assert "max_distance" in call(md=-1.0) and "max_distance" in call(md=math.nan)
         assert call(dist=None).endswith(": null argument") and call(idx=None).endswith(": null argument")
-        assert "4-byte aligned" in call(dist=fake + 1) and "4-byte aligned" in call(idx=fake + 3)
-    assert "4-byte aligned" in closest(cl=fake + 2)
+        assert "4-byte aligned" in call(dist=FAKE + 1) and "4-byte aligned" in call(idx=FAKE + 3)
+    assert "4-byte aligned" in closest(cl=FAKE + 2)
     for bad in (0, 9, -1):
         assert "k must lie in [1, LRF_CLOUD_MAX_K]" in knn(k=bad)
     for bad in (-1.0, math.nan, math.inf):
         assert "radius must be finite and >= 0" in count(radius=bad)
     for call in (knn, count):
         assert "self_first" in call(first=-2) and "self_first" in call(first=1) and "self_first" in call(first=5, n=5)
-    assert count(out=None).endswith(": null argument") and "4-byte aligned" in count(out=fake + 2)
+    assert count(out=None).endswith(": null argument") and "4-byte aligned" in count(out=FAKE + 2)
 
-    def bounds(p=fake, m=5, out=fake):
-        return err(built_lib.lrf_cloud_index_bounds(p, m, out, None))
+    def bounds(p=FAKE, m=5, out=FAKE):
+        return refused(built_lib, built_lib.lrf_cloud_index_bounds(p, m, out, None))
     assert "1 <= M" in bounds(m=0) and "1 <= M" in bounds(m=1 << 31)
     assert bounds(p=None).endswith(": null argument") and bounds(out=None).endswith(": null argument")
-    assert "4-byte aligned" in bounds(p=fake + 2) and "8-byte aligned" in bounds(out=fake + 4)
+    assert "4-byte aligned" in bounds(p=FAKE + 2) and "8-byte aligned" in bounds(out=FAKE + 4)
 
-    def vbounds(p=fake, m=5, origin=(0.0, 0.0, 0.0), cell=0.5, out=fake):
-        return err(built_lib.lrf_cloud_voxel_bounds(p, m, None if origin is None else (C.c_double * 3)(*origin), cell, out, None))
+    def vbounds(p=FAKE, m=5, origin=(0.0, 0.0, 0.0), cell=0.5, out=FAKE):
+        return refused(built_lib, built_lib.lrf_cloud_voxel_bounds(p, m, None if origin is None else (C.c_double * 3)(*origin), cell, out, None))
     assert "1 <= M" in vbounds(m=0) and "1 <= M" in vbounds(m=1 << 31)
     for bad in (dict(p=None), dict(origin=None), dict(out=None)):
         assert vbounds(**bad).endswith(": null argument"), bad
-    assert "origin" in vbounds(origin=(0.0, math.inf, 0.0)) and "4-byte aligned" in vbounds(p=fake + 1) and "8-byte aligned" in vbounds(out=fake + 4)
+    assert "origin" in vbounds(origin=(0.0, math.inf, 0.0)) and "4-byte aligned" in vbounds(p=FAKE + 1) and "8-byte aligned" in vbounds(out=FAKE + 4)
     for bad in (0.0, -1.0, math.nan, math.inf):
         assert "cell must be finite" in vbounds(cell=bad)
 
-    def voxel(po=fake, co=None, no=fake, cl=fake, counts=fake, ws=fake, **over):
-        a = N.LrfCloudVoxel()
-        a.points, a.rgb8, a.M, a.cell = fake, None, 9, 0.5
-        for k in range(3):
-            a.origin[k], a.lo[k], a.dims[k] = 0.0, -2, 4
-        for k, v in over.items():
-            if k in ("lo", "dims", "origin"):
-                for i in range(3):
-                    getattr(a, k)[i] = v[i]
-            else:
-                setattr(a, k, v)
-        return err(built_lib.lrf_cloud_voxel(C.byref(a), po, co, no, cl, counts, ws, None))
+    def voxel(po=FAKE, co=None, no=FAKE, cl=FAKE, counts=FAKE, ws=FAKE, **over):
+        a = filled(N.LrfCloudVoxel, dict(points=FAKE, rgb8=None, M=9, cell=0.5, origin=(0.0,) * 3, lo=(-2,) * 3, dims=(4,) * 3), **over)
+        return refused(built_lib, built_lib.lrf_cloud_voxel(C.byref(a), po, co, no, cl, counts, ws, None))
     assert "1 <= M" in voxel(M=0) and "1 <= M" in voxel(M=1 << 31)
     for bad in (dict(points=None), dict(po=None), dict(no=None), dict(cl=None), dict(counts=None), dict(ws=None)):
         assert voxel(**bad).endswith(": null argument"), bad
-    assert "go together" in voxel(rgb8=fake) and "go together" in voxel(co=fake)
+    assert "go together" in voxel(rgb8=FAKE) and "go together" in voxel(co=FAKE)
     for bad in (dict(dims=(0, 4, 4)), dict(dims=(1 << 11, 1 << 10, 1 << 10))):
         assert "fewer than 2^31 cells" in voxel(**bad), bad
     assert "inside (-2^30, 2^30)" in voxel(lo=(-(1 << 30), 0, 0)) and "inside (-2^30, 2^30)" in voxel(lo=((1 << 30) - 3, 0, 0))
     assert "origin" in voxel(origin=(math.nan, 0.0, 0.0)) and "cell must be finite" in voxel(cell=0.0) and "cell must be finite" in voxel(cell=math.inf)
-    assert "4-byte aligned" in voxel(points=fake + 2) and "4-byte aligned" in voxel(no=fake + 1) and "4-byte aligned" in voxel(cl=fake + 3)
-    assert "8-byte aligned" in voxel(counts=fake + 4) and "8-byte aligned" in voxel(ws=fake + 4)
-    assert built_lib.lrf_cloud_voxel(None, fake, None, fake, fake, fake, fake, None) != 0
+    assert "4-byte aligned" in voxel(points=FAKE + 2) and "4-byte aligned" in voxel(no=FAKE + 1) and "4-byte aligned" in voxel(cl=FAKE + 3)
+    assert "8-byte aligned" in voxel(counts=FAKE + 4) and "8-byte aligned" in voxel(ws=FAKE + 4)
+    assert built_lib.lrf_cloud_voxel(None, FAKE, None, FAKE, FAKE, FAKE, FAKE, None) != 0
 
 
 def test_the_workspace_bytes_refuse_and_follow_the_formula(built_lib):
@@ -385,12 +357,5 @@ def test_the_workspace_bytes_refuse_and_follow_the_formula(built_lib):
 def test_cloud_kernels_use_no_scratch():
     """The kernels of lrf_cloud.inl as __graft_entry__.build() compiles them: the metadata only.  The K slots of k_cl_knn must
     stay registers: a runtime index into them would put them into scratch."""
-    from test_isa_checks import BUILD_FLAGS, _device_asm
-    asm = _device_asm(BUILD_FLAGS)
-    for name in KERNELS:
-        hits = re.findall(r"\.amdhsa_kernel (_Z\w*?\d+" + name + r"\w*)", asm)
-        assert len(hits) == 1, (name, hits)
-        meta = asm[asm.index(".amdhsa_kernel " + hits[0]):]
-        meta = meta[:meta.index(".end_amdhsa_kernel")]
-        priv = re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", meta)
-        assert priv and int(priv[1]) == 0, (name, priv and priv[1])
+    from isa_util import assert_no_scratch, device_asm
+    assert_no_scratch(device_asm(), KERNELS, match="prefix")

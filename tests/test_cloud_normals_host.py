@@ -5,12 +5,12 @@ new kernels' scratch use."""
 import ctypes as C
 import math
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
+from abi_util import FAKE, declared_exported_bound, filled, refused
 from align_cases import deviation, truth
 from cloud_normal_cases import (CASE_NAMES, EPS, SCAN_RUNS, SWEEPS, cases, expected, fibonacci, icp_plane_cloud_host, jacobi_host, lattice_h,
                                 normals_host, plane_cloud_case, plane_cloud_host, scan, scan_normals, scan_source, scan_spacing, sphere_spacing)
@@ -213,36 +213,19 @@ def test_icp_refusals_with_and_without_target_normals(monkeypatch):
 def test_symbols_declared_exported_bound_and_checked(built_lib):
     from localrf_amd import _native as N
     import localrf_amd
-    header = open(os.path.join(ROOT, "include", "lrf.h")).read()
-    for name in SYMBOLS:
-        assert name in N.SYMBOLS and f"{name}(" in header
-        getattr(built_lib, name)
+    header = declared_exported_bound(built_lib, SYMBOLS)
     assert "typedef struct LrfAlignPlaneCloud" in header and C.sizeof(N.LrfAlignPlaneCloud) == 5 * 8 + 2 * 8 + 4 * 8 + 2 * 4
     assert built_lib.lrf_abi_version() == 7
     assert "estimate_normals" in localrf_amd.__doc__ and callable(cloud.estimate_normals) and callable(CloudIndex.normals)
-    fake = 0x10000
-
-    def err(rc, who):
-        assert rc != 0                                                          # every call here must be refused: nothing may launch
-        msg = built_lib.lrf_last_error().decode()
-        assert msg.startswith(who + ": "), msg
-        return msg
 
     def index(**over):
-        a = N.LrfCloudIndex()
-        a.points, a.grid, a.records = fake, fake, fake
-        a.M, a.entries, a.cell = 9, 7, 0.5
-        for k in range(3):
-            a.lo[k], a.dims[k] = 0.0, 4
-        for k, v in over.items():
-            setattr(a, k, v)
-        return a
+        return filled(N.LrfCloudIndex, dict(points=FAKE, grid=FAKE, records=FAKE, M=9, entries=7, cell=0.5, lo=(0.0,) * 3, dims=(4,) * 3), **over)
 
-    def normals(a=True, points=fake, n=9, radius=0.3, h=2.0 ** -16, least=6, view=None, stride=0, normal=fake, eig=fake, count=fake, **over):
-        return err(built_lib.lrf_cloud_normals(C.byref(index(**over)) if a else None, points, n, radius, h, least, view, stride, normal, eig, count, None),
-                   "lrf_cloud_normals")
+    def normals(a=True, points=FAKE, n=9, radius=0.3, h=2.0 ** -16, least=6, view=None, stride=0, normal=FAKE, eig=FAKE, count=FAKE, **over):
+        return refused(built_lib, built_lib.lrf_cloud_normals(C.byref(index(**over)) if a else None, points, n, radius, h, least, view, stride, normal, eig, count, None),
+                       "lrf_cloud_normals")
     assert normals(a=False).endswith(": null argument") and "1 <= M" in normals(M=0) and "entries <= M" in normals(entries=10)
-    assert "records of a built index" in normals(records=None) and "16-byte aligned" in normals(records=fake + 8) and normals(grid=None).endswith(": null argument")
+    assert "records of a built index" in normals(records=None) and "16-byte aligned" in normals(records=FAKE + 8) and normals(grid=None).endswith(": null argument")
     assert "0 <= N < 2^31" in normals(n=-1) and "0 <= N < 2^31" in normals(n=1 << 31)
     for bad in (0.0, -0.3, math.nan, math.inf):
         assert "radius must be finite and > 0" in normals(radius=bad), bad
@@ -254,24 +237,17 @@ def test_symbols_declared_exported_bound_and_checked(built_lib):
     for bad in (2, 0, -1):
         assert "min_neighbours must be >= 3" in normals(least=bad), bad
     for bad in (1, 2, 4, -3, 12):
-        assert "viewpoint_stride must be 0" in normals(view=fake, stride=bad), bad
+        assert "viewpoint_stride must be 0" in normals(view=FAKE, stride=bad), bad
     for bad in (dict(normal=None), dict(eig=None), dict(count=None)):
         assert normals(**bad).endswith(": null argument"), bad
-    for bad in (dict(points=fake + 2), dict(view=fake + 1), dict(normal=fake + 2), dict(eig=fake + 3), dict(count=fake + 1)):
+    for bad in (dict(points=FAKE + 2), dict(view=FAKE + 1), dict(normal=FAKE + 2), dict(eig=FAKE + 3), dict(count=FAKE + 1)):
         assert "4-byte aligned" in normals(**bad), bad
     assert "need N == M" in normals(points=None, n=8) and "need N == M" in normals(points=None, n=0)
 
-    def plane(p=True, words=fake, **over):
-        a = N.LrfAlignPlaneCloud()
-        a.points, a.closest, a.index, a.distance, a.normals = (fake,) * 5
-        a.N, a.M, a.u, a.gate = 9, 5, 2.0, math.inf
-        for k, v in over.items():
-            if k == "c":
-                for i in range(3):
-                    a.c[i] = v[i]
-            else:
-                setattr(a, k, v)
-        return err(built_lib.lrf_align_plane_cloud(C.byref(a) if p else None, words, None), "lrf_align_plane_cloud")
+    def plane(p=True, words=FAKE, **over):
+        a = filled(N.LrfAlignPlaneCloud, dict(points=FAKE, closest=FAKE, index=FAKE, distance=FAKE, normals=FAKE, N=9, M=5, u=2.0, gate=math.inf),
+                   **over)
+        return refused(built_lib, built_lib.lrf_align_plane_cloud(C.byref(a) if p else None, words, None), "lrf_align_plane_cloud")
     for bad in (dict(p=False), dict(words=None), dict(points=None), dict(closest=None), dict(index=None), dict(distance=None), dict(normals=None),
                 dict(normals=None, N=0)):
         assert plane(**bad).endswith(": null argument"), bad
@@ -282,20 +258,13 @@ def test_symbols_declared_exported_bound_and_checked(built_lib):
         assert "power of two" in plane(u=bad), bad
     assert "c must be finite" in plane(c=(0.0, math.nan, 0.0)) and "c must be finite" in plane(c=(math.inf, 0.0, 0.0))
     assert "gate" in plane(gate=-1.0) and "gate" in plane(gate=math.nan)
-    for bad in (dict(points=fake + 2), dict(closest=fake + 1), dict(index=fake + 3), dict(distance=fake + 2), dict(normals=fake + 1)):
+    for bad in (dict(points=FAKE + 2), dict(closest=FAKE + 1), dict(index=FAKE + 3), dict(distance=FAKE + 2), dict(normals=FAKE + 1)):
         assert "4-byte aligned" in plane(**bad), bad
-    assert "8-byte aligned" in plane(words=fake + 4)
+    assert "8-byte aligned" in plane(words=FAKE + 4)
 
 
 def test_the_new_kernels_use_no_scratch():
     """The new kernels, and k_al_plane beside its twin, as __graft_entry__.build() compiles them: the metadata only.  The ten
     sums, A and V of k_cl_normals must stay registers, and so must the 42 sums of k_al_plane_cloud."""
-    from test_isa_checks import BUILD_FLAGS, _device_asm
-    asm = _device_asm(BUILD_FLAGS)
-    for name in KERNELS:
-        hits = re.findall(r"\.amdhsa_kernel (_Z\w*?\d+" + name + r"\w*)", asm)
-        assert len(hits) == 1, (name, hits)
-        meta = asm[asm.index(".amdhsa_kernel " + hits[0]):]
-        meta = meta[:meta.index(".end_amdhsa_kernel")]
-        priv = re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", meta)
-        assert priv and int(priv[1]) == 0, (name, priv and priv[1])
+    from isa_util import assert_no_scratch, device_asm
+    assert_no_scratch(device_asm(), KERNELS, match="prefix")

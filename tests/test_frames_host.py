@@ -12,6 +12,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import frames_cases as fc  # noqa: E402
+from abi_util import filled  # noqa: E402
 from localrf_amd import frames  # noqa: E402
 from localrf_amd import _native as N  # noqa: E402
 
@@ -19,13 +20,8 @@ FAKE = 1 << 40          # a non-null address that is never dereferenced: every c
 
 
 def _window(**over):
-    w = N.LrfFrameWindow()
-    for k in ("rgb", "loss_weight", "invdepth", "fwd_flow", "fwd_mask", "bwd_flow", "bwd_mask", "slot_of", "status"):
-        setattr(w, k, FAKE)
-    w.capacity, w.n_px, w.num_images = 4, 12, 10
-    for k, v in over.items():
-        setattr(w, k, v)
-    return w
+    planes = ("rgb", "loss_weight", "invdepth", "fwd_flow", "fwd_mask", "bwd_flow", "bwd_mask", "slot_of", "status")
+    return filled(N.LrfFrameWindow, dict(dict.fromkeys(planes, FAKE), capacity=4, n_px=12, num_images=10), **over)
 
 
 def test_library_exports_the_frame_store(built_lib):
@@ -219,13 +215,10 @@ def test_device_frames_refuses_bad_readers_and_capacity_before_any_allocation():
 
 def test_frame_store_kernels_use_no_scratch():
     import re
-    from test_isa_checks import BUILD_FLAGS, _device_asm
-    asm = _device_asm(BUILD_FLAGS)
+    from isa_util import device_asm, scratch_bytes
+    asm = device_asm()
     for k in ("k_frames_gather", "k_decode_flow", "k_frame_sharpness", "k_frame_weight"):
         names = [m for m in re.findall(r"^(_Z\w+):", asm, re.M) if k + "E" in m or re.search(k + r"[A-Z]", m)]
         assert names, k
         for name in names:
-            meta = asm[asm.index(".amdhsa_kernel " + name):]
-            meta = meta[:meta.index(".end_amdhsa_kernel")]
-            priv = re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", meta)
-            assert priv and int(priv[1]) == 0, (name, priv and priv[1])
+            assert scratch_bytes(asm, name) == 0, (name, scratch_bytes(asm, name))

@@ -13,36 +13,18 @@ The tile loop is the innermost backward branch that encloses every v_mfma of the
    the only vector-memory operations issued behind it.  (With global tile offsets the walk to the tile's ray, in front of
    H, reads an offset and waits for it: that is the walk's own load, step d of the round-trip work, not taken.)
 """
-import os
 import re
-import subprocess
-import tempfile
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "localrf_amd", "csrc", "lrf_render.hip")
-BUILD_FLAGS = ["-fno-slp-vectorize"]            # = __graft_entry__.build()
+from isa_util import device_asm, kernels
+
 KERNELS = r"k_shade3m?ILi8ELb[01]ELb0ELb[01]EE"  # the four k_shade3 instantiations of the render paths and k_shade3m
 
 
 @pytest.fixture(scope="module")
 def loops():
-    import __graft_entry__ as ge
-    src = open(ge.__file__).read()
-    assert all(f in src for f in BUILD_FLAGS), "this test must compile with the flags of __graft_entry__.build()"
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    with tempfile.TemporaryDirectory() as d:
-        out = os.path.join(d, "k.s")
-        subprocess.check_call([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17"] + BUILD_FLAGS + ["-I", os.path.join(ROOT, "include"),
-                               "-S", "--cuda-device-only", "-o", out, SRC], stderr=subprocess.DEVNULL)
-        asm = open(out).read()
-    found = {}
-    for m in re.finditer(r"^(_Z\w+):[^\n]*\n(.*?)\.end_amdhsa_kernel", asm, re.S | re.M):
-        if re.search(KERNELS, m[1]):
-            found[m[1]] = _tile_loop(m[2])
+    found = {name: _tile_loop(body) for name, body in kernels(device_asm()).items() if re.search(KERNELS, name)}
     assert len(found) == 5, sorted(found)
     return found
 

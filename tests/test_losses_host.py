@@ -6,17 +6,8 @@ import pytest
 import torch
 
 import losses_cases as K
+from losses_cases import _not_stale
 from oracle import vm_render_torch as ot
-
-
-def _not_stale(table, measured, key):
-    """The recorded and the measured error agree within 2 x.  Below FLOOR / 4 an error does not enter the tolerance
-    (max(4 e32, FLOOR)), and a single float32 result can be exact by chance: both are raised to that before comparing."""
-    assert set(table) == set(measured), key
-    lo = K.FLOOR / 4
-    for q in table:
-        a, b = max(table[q], lo), max(measured[q], lo)
-        assert a <= 2 * b and b <= 2 * a, (key, q, table[q], measured[q])
 
 
 @pytest.mark.parametrize("name", K.GEO_CASES)

@@ -4,19 +4,18 @@ vertices at thresholds 0 and 1, argument refusals before any native call (Python
 kernels' scratch use."""
 import ctypes as C
 import math
-import os
 
 import numpy as np
 import pytest
 import torch
 
+from abi_util import FAKE, declared_exported_bound, filled, refused
 from localrf_amd import NativeError, mesh
 from mesh_cases import closed_manifold_euler
 from mesh_clean_cases import (BLOB_FACES, MESH_NAMES, all_meshes, base_meshes, components_host, expected, fan, filter_host,
                               labels_bfs, labels_host, labels_host_arrays, threshold_host)
 from mesh_util import DenseStub, cpu_mesh, forbid_native, forbid_render
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMBOLS = ("lrf_mesh_components_init", "lrf_mesh_components_round", "lrf_mesh_components_count",
            "lrf_mesh_filter_workspace_bytes", "lrf_mesh_filter")
 
@@ -157,51 +156,40 @@ def test_scene_mesh_checks_the_component_options_before_it_renders(monkeypatch):
 
 def test_clean_symbols_declared_exported_bound_and_checked(built_lib):
     from localrf_amd import _native as N
-    header = open(os.path.join(ROOT, "include", "lrf.h")).read()
-    for name in SYMBOLS:
-        assert name in N.SYMBOLS and f"{name}(" in header
-        getattr(built_lib, name)
+    header = declared_exported_bound(built_lib, SYMBOLS)
     assert "typedef struct LrfMeshFilter" in header and C.sizeof(N.LrfMeshFilter) == 5 * 8 + 2 * 8
     assert built_lib.lrf_abi_version() == 7
     ws = built_lib.lrf_mesh_filter_workspace_bytes
     assert ws(0, 0) == 0 and ws(-1, 5) == 0 and ws(5, -1) == 0 and ws(1 << 31, 0) == 0 and ws(5, 1 << 31) == 0
     assert ws(1, 0) == 512 and ws(1024, 1024) == 512 and ws(1025, 3) == 1024 and ws(3, 1025) == 1024
     assert ws((1 << 31) - 1, (1 << 31) - 1) >= 2 * ((1 << 31) // 8 + (1 << 31) // 16)
-    fake = 0x10000
 
-    def err(rc):
-        assert rc != 0                                                  # every call here must be refused: nothing may launch
-        return built_lib.lrf_last_error().decode()
-
-    init = lambda parent=fake, Nv=5: err(built_lib.lrf_mesh_components_init(parent, Nv, None))  # noqa: E731
+    init = lambda parent=FAKE, Nv=5: refused(built_lib, built_lib.lrf_mesh_components_init(parent, Nv, None))  # noqa: E731
     assert "1 <= Nv < 2^31" in init(Nv=0) and "1 <= Nv < 2^31" in init(Nv=1 << 31) and "1 <= Nv < 2^31" in init(Nv=-4)
-    assert init(parent=None) == "lrf_mesh_components_init: null argument" and "4-byte aligned" in init(parent=fake + 2)
+    assert init(parent=None) == "lrf_mesh_components_init: null argument" and "4-byte aligned" in init(parent=FAKE + 2)
 
-    def rnd(parent=fake, faces=fake, Nv=5, Nf=3, changed=fake):
-        return err(built_lib.lrf_mesh_components_round(parent, faces, Nv, Nf, changed, None))
+    def rnd(parent=FAKE, faces=FAKE, Nv=5, Nf=3, changed=FAKE):
+        return refused(built_lib, built_lib.lrf_mesh_components_round(parent, faces, Nv, Nf, changed, None))
     for bad in (dict(Nv=0), dict(Nf=-1), dict(Nv=1 << 31), dict(Nf=1 << 31)):
         assert "need 1 <= Nv < 2^31 and 0 <= Nf < 2^31" in rnd(**bad), bad
     for bad in (dict(parent=None), dict(faces=None), dict(changed=None)):
         assert rnd(**bad) == "lrf_mesh_components_round: null argument", bad
-    for bad in (dict(parent=fake + 1), dict(faces=fake + 2), dict(changed=fake + 3)):
+    for bad in (dict(parent=FAKE + 1), dict(faces=FAKE + 2), dict(changed=FAKE + 3)):
         assert "4-byte aligned" in rnd(**bad), bad
 
-    def count(labels=fake, faces=fake, Nv=5, Nf=3, faces_of=fake, vertices_of=fake, summary=fake):
-        return err(built_lib.lrf_mesh_components_count(labels, faces, Nv, Nf, faces_of, vertices_of, summary, None))
+    def count(labels=FAKE, faces=FAKE, Nv=5, Nf=3, faces_of=FAKE, vertices_of=FAKE, summary=FAKE):
+        return refused(built_lib, built_lib.lrf_mesh_components_count(labels, faces, Nv, Nf, faces_of, vertices_of, summary, None))
     for bad in (dict(Nv=0), dict(Nf=-1), dict(Nv=1 << 31), dict(Nf=1 << 31)):
         assert "need 1 <= Nv < 2^31 and 0 <= Nf < 2^31" in count(**bad), bad
     for bad in (dict(labels=None), dict(faces=None), dict(faces_of=None), dict(vertices_of=None), dict(summary=None)):
         assert count(**bad) == "lrf_mesh_components_count: null argument", bad
-    for bad in (dict(labels=fake + 2), dict(faces=fake + 1), dict(faces_of=fake + 2), dict(vertices_of=fake + 2)):
+    for bad in (dict(labels=FAKE + 2), dict(faces=FAKE + 1), dict(faces_of=FAKE + 2), dict(vertices_of=FAKE + 2)):
         assert "4-byte aligned" in count(**bad), bad
-    assert "8-byte aligned" in count(summary=fake + 4)
+    assert "8-byte aligned" in count(summary=FAKE + 4)
 
-    def flt(threshold=1, vertices_out=fake, rgb8_out=fake, faces_out=fake, counts=fake, wsp=fake, **over):
-        a = N.LrfMeshFilter()
-        a.vertices, a.rgb8, a.faces, a.labels, a.faces_of, a.Nv, a.Nf = fake, fake, fake, fake, fake, 5, 3
-        for k, v in over.items():
-            setattr(a, k, v)
-        return err(built_lib.lrf_mesh_filter(C.byref(a), threshold, vertices_out, rgb8_out, faces_out, counts, wsp, None))
+    def flt(threshold=1, vertices_out=FAKE, rgb8_out=FAKE, faces_out=FAKE, counts=FAKE, wsp=FAKE, **over):
+        a = filled(N.LrfMeshFilter, dict(vertices=FAKE, rgb8=FAKE, faces=FAKE, labels=FAKE, faces_of=FAKE, Nv=5, Nf=3), **over)
+        return refused(built_lib, built_lib.lrf_mesh_filter(C.byref(a), threshold, vertices_out, rgb8_out, faces_out, counts, wsp, None))
     for bad in (dict(Nv=0), dict(Nf=-1), dict(Nv=1 << 31), dict(Nf=1 << 31)):
         assert "need 1 <= Nv < 2^31 and 0 <= Nf < 2^31" in flt(**bad), bad
     for bad in (dict(vertices=None), dict(faces=None), dict(labels=None), dict(faces_of=None), dict(vertices_out=None),
@@ -209,25 +197,16 @@ def test_clean_symbols_declared_exported_bound_and_checked(built_lib):
         assert flt(**bad) == "lrf_mesh_filter: null argument", bad
     assert "go together" in flt(rgb8=None) and "go together" in flt(rgb8_out=None)
     assert "threshold" in flt(threshold=-1)
-    for bad in (dict(vertices=fake + 2), dict(faces=fake + 1), dict(labels=fake + 2), dict(faces_of=fake + 3), dict(vertices_out=fake + 2),
-                dict(faces_out=fake + 2)):
+    for bad in (dict(vertices=FAKE + 2), dict(faces=FAKE + 1), dict(labels=FAKE + 2), dict(faces_of=FAKE + 3), dict(vertices_out=FAKE + 2),
+                dict(faces_out=FAKE + 2)):
         assert "4-byte aligned" in flt(**bad), bad
-    assert "8-byte aligned" in flt(counts=fake + 4) and "8-byte aligned" in flt(wsp=fake + 4)
-    assert built_lib.lrf_mesh_filter(None, 1, fake, fake, fake, fake, fake, None) != 0
+    assert "8-byte aligned" in flt(counts=FAKE + 4) and "8-byte aligned" in flt(wsp=FAKE + 4)
+    assert built_lib.lrf_mesh_filter(None, 1, FAKE, FAKE, FAKE, FAKE, FAKE, None) != 0
 
 
 def test_clean_kernels_use_no_scratch():
     """The kernels of lrf_mesh_clean.inl as __graft_entry__.build() compiles them."""
-    import re
-    from test_isa_checks import BUILD_FLAGS, _body, _device_asm
-    asm = _device_asm(BUILD_FLAGS)
+    from isa_util import assert_no_scratch, device_asm
     names = ("k_cc_init", "k_cc_clear", "k_cc_hook", "k_cc_shorten", "k_cc_zero", "k_cc_count_faces", "k_cc_count_vertices",
              "k_cc_summary", "k_mesh_filter_mark", "k_mesh_filter_write")
-    found = [(n, b) for pat in names for n, b in _body(asm, pat)]
-    assert len(found) == len(names)
-    for name, body in found:
-        meta = asm[asm.index(".amdhsa_kernel " + name):]
-        meta = meta[:meta.index(".end_amdhsa_kernel")]
-        priv = re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", meta)
-        assert priv and int(priv[1]) == 0, (name, priv and priv[1])
-        assert "scratch_" not in body, name
+    assert_no_scratch(device_asm(), names, match="search", total=len(names), body_too=True)

@@ -12,12 +12,12 @@ coordinate difference between the point and the corners, over the fp64 result be
 Each kind's bar is four times its own figure: the bars guard the formulation, not one platform's last bit."""
 import ctypes as C
 import math
-import os
 
 import numpy as np
 import pytest
 import torch
 
+from abi_util import FAKE, declared_exported_bound, filled, refused
 from localrf_amd import NativeError, mesh_distance
 from localrf_amd.mesh_distance import MeshIndex, cloud_to_mesh, distance_summary, sample_surface
 from mesh_distance_cases import (CASE_NAMES, CLAMP, QUERY_SIZES, SAMPLE_CASES, SCALE, SUMMARY_SIZES, SUMMARY_TAUS, TRIANGLE, _pairs,
@@ -27,7 +27,6 @@ from mesh_distance_cases import (CASE_NAMES, CLAMP, QUERY_SIZES, SAMPLE_CASES, S
 from mesh_clean_cases import permute_faces
 from mesh_util import cpu_mesh, forbid_native
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMBOLS = ("lrf_mesh_index_bounds", "lrf_mesh_index_workspace_bytes", "lrf_mesh_index_build", "lrf_mesh_closest", "lrf_mesh_sample_count",
            "lrf_mesh_sample_emit", "lrf_distance_summary")
 KERNELS = ("k_md_bounds_init", "k_md_bounds", "k_md_zero", "k_md_fill", "k_md_closest", "k_md_sample_count", "k_md_sample_emit",
@@ -283,40 +282,22 @@ def test_default_cell_is_a_function_of_box_and_faces():
 
 def test_symbols_declared_exported_bound_and_checked(built_lib):
     from localrf_amd import _native as N
-    header = open(os.path.join(ROOT, "include", "lrf.h")).read()
-    for name in SYMBOLS:
-        assert name in N.SYMBOLS and f"{name}(" in header
-        getattr(built_lib, name)
+    header = declared_exported_bound(built_lib, SYMBOLS)
     assert "typedef struct LrfMeshIndex" in header and C.sizeof(N.LrfMeshIndex) == 4 * 8 + 3 * 8 + 4 * 8 + 4 * 4
     assert "#define LRF_DISTANCE_MAX_THRESHOLDS 8" in header and N.LRF_DISTANCE_MAX_THRESHOLDS == 8
     assert built_lib.lrf_abi_version() == 7
     import __graft_entry__ as ge
     assert "lrf_mesh_distance.inl" in ge.HEADERS
-    fake = 0x10000
-
-    def err(rc):
-        assert rc != 0                                                          # every call here must be refused: nothing may launch
-        return built_lib.lrf_last_error().decode()
 
     def index(**over):
-        a = N.LrfMeshIndex()
-        a.vertices, a.faces, a.grid, a.list = fake, fake, fake, fake
-        a.Nv, a.Nf, a.entries, a.cell = 5, 3, 7, 0.5
-        for k in range(3):
-            a.lo[k], a.dims[k] = 0.0, 4
-        for k, v in over.items():
-            if k in ("lo", "dims"):
-                for i in range(3):
-                    getattr(a, k)[i] = v[i]
-            else:
-                setattr(a, k, v)
-        return a
+        return filled(N.LrfMeshIndex, dict(vertices=FAKE, faces=FAKE, grid=FAKE, list=FAKE, Nv=5, Nf=3, entries=7, cell=0.5, lo=(0.0,) * 3,
+                                           dims=(4,) * 3), **over)
 
-    def build(total=fake, **over):
-        return err(built_lib.lrf_mesh_index_build(C.byref(index(**over)), total, None))
+    def build(total=FAKE, **over):
+        return refused(built_lib, built_lib.lrf_mesh_index_build(C.byref(index(**over)), total, None))
 
-    def closest(points=fake, n=9, md=math.inf, dist=fake, face=fake, cl=None, **over):
-        return err(built_lib.lrf_mesh_closest(C.byref(index(**over)), points, n, md, dist, face, cl, None))
+    def closest(points=FAKE, n=9, md=math.inf, dist=FAKE, face=FAKE, cl=None, **over):
+        return refused(built_lib, built_lib.lrf_mesh_closest(C.byref(index(**over)), points, n, md, dist, face, cl, None))
     for who, call in (("lrf_mesh_index_build", build), ("lrf_mesh_closest", closest)):
         for bad in (dict(Nv=0), dict(Nv=1 << 31), dict(Nf=0), dict(Nf=1 << 31)):
             assert call(**bad).startswith(who + ": need 1 <= Nv"), bad
@@ -326,54 +307,54 @@ def test_symbols_declared_exported_bound_and_checked(built_lib):
             assert "finite cell" in call(**bad), bad
         for bad in (dict(vertices=None), dict(faces=None), dict(grid=None)):
             assert call(**bad).endswith(": null argument"), bad
-        for bad in (dict(vertices=fake + 2), dict(faces=fake + 1), dict(list=fake + 2)):
+        for bad in (dict(vertices=FAKE + 2), dict(faces=FAKE + 1), dict(list=FAKE + 2)):
             assert "4-byte aligned" in call(**bad), bad
-        assert "8-byte aligned" in call(grid=fake + 4)
+        assert "8-byte aligned" in call(grid=FAKE + 4)
     assert "needs total" in build(total=None, list=None)
-    assert "entries" in build(entries=-1) and "entries" in build(entries=1 << 31) and "8-byte aligned" in build(total=fake + 4)
+    assert "entries" in build(entries=-1) and "entries" in build(entries=1 << 31) and "8-byte aligned" in build(total=FAKE + 4)
     assert "entries" in closest(list=None) and "entries" in closest(entries=-1) and "entries" in closest(entries=1 << 31)
     assert "1 <= N" in closest(n=0) and "1 <= N" in closest(n=1 << 31)
     assert "max_distance" in closest(md=-1.0) and "max_distance" in closest(md=math.nan)
     for bad in (dict(points=None), dict(dist=None), dict(face=None)):
         assert closest(**bad).endswith(": null argument"), bad
-    for bad in (dict(points=fake + 2), dict(dist=fake + 1), dict(face=fake + 3), dict(cl=fake + 2)):
+    for bad in (dict(points=FAKE + 2), dict(dist=FAKE + 1), dict(face=FAKE + 3), dict(cl=FAKE + 2)):
         assert "4-byte aligned" in closest(**bad), bad
-    assert built_lib.lrf_mesh_index_build(None, fake, None) != 0 and built_lib.lrf_mesh_closest(None, fake, 1, 1.0, fake, fake, None, None) != 0
+    assert built_lib.lrf_mesh_index_build(None, FAKE, None) != 0 and built_lib.lrf_mesh_closest(None, FAKE, 1, 1.0, FAKE, FAKE, None, None) != 0
 
-    def bounds(v=fake, f=fake, nv=5, nf=3, out=fake):
-        return err(built_lib.lrf_mesh_index_bounds(v, f, nv, nf, out, None))
+    def bounds(v=FAKE, f=FAKE, nv=5, nf=3, out=FAKE):
+        return refused(built_lib, built_lib.lrf_mesh_index_bounds(v, f, nv, nf, out, None))
 
-    def count(v=fake, f=fake, nv=5, nf=3, spacing=0.1, offsets=fake, info=fake):
-        return err(built_lib.lrf_mesh_sample_count(v, f, nv, nf, spacing, offsets, info, None))
+    def count(v=FAKE, f=FAKE, nv=5, nf=3, spacing=0.1, offsets=FAKE, info=FAKE):
+        return refused(built_lib, built_lib.lrf_mesh_sample_count(v, f, nv, nf, spacing, offsets, info, None))
 
-    def emit(v=fake, f=fake, nv=5, nf=3, spacing=0.1, offsets=fake, m=4, pts=fake, face=fake):
-        return err(built_lib.lrf_mesh_sample_emit(v, f, nv, nf, spacing, offsets, m, pts, face, None))
+    def emit(v=FAKE, f=FAKE, nv=5, nf=3, spacing=0.1, offsets=FAKE, m=4, pts=FAKE, face=FAKE):
+        return refused(built_lib, built_lib.lrf_mesh_sample_emit(v, f, nv, nf, spacing, offsets, m, pts, face, None))
     for call in (bounds, count, emit):
         for bad in (dict(nv=0), dict(nv=1 << 31), dict(nf=-1), dict(nf=1 << 31)):
             assert "need 1 <= Nv" in call(**bad), bad
         for bad in (dict(v=None), dict(f=None)):
             assert call(**bad).endswith(": null argument"), bad
-        assert "4-byte aligned" in call(v=fake + 2) and "4-byte aligned" in call(f=fake + 1)
-    assert bounds(out=None).endswith(": null argument") and "8-byte aligned" in bounds(out=fake + 4)
+        assert "4-byte aligned" in call(v=FAKE + 2) and "4-byte aligned" in call(f=FAKE + 1)
+    assert bounds(out=None).endswith(": null argument") and "8-byte aligned" in bounds(out=FAKE + 4)
     for call in (count, emit):
         assert "Nf >= 1" in call(nf=0)
         for bad in (0.0, -1.0, math.nan, math.inf):
             assert "spacing" in call(spacing=bad)
-        assert call(offsets=None).endswith(": null argument") and "4-byte aligned" in call(offsets=fake + 2)
-    assert count(info=None).endswith(": null argument") and "8-byte aligned" in count(info=fake + 4)
+        assert call(offsets=None).endswith(": null argument") and "4-byte aligned" in call(offsets=FAKE + 2)
+    assert count(info=None).endswith(": null argument") and "8-byte aligned" in count(info=FAKE + 4)
     assert "1 <= M" in emit(m=0) and "1 <= M" in emit(m=1 << 31)
-    assert emit(pts=None).endswith(": null argument") and emit(face=None).endswith(": null argument") and "4-byte aligned" in emit(pts=fake + 1)
+    assert emit(pts=None).endswith(": null argument") and emit(face=None).endswith(": null argument") and "4-byte aligned" in emit(pts=FAKE + 1)
 
-    def summary(d=fake, n=9, taus=(0.1, 0.2), k=None, unit=1.0, words=fake):
+    def summary(d=FAKE, n=9, taus=(0.1, 0.2), k=None, unit=1.0, words=FAKE):
         arr = (C.c_float * 9)(*taus) if taus is not None else None
-        return err(built_lib.lrf_distance_summary(d, n, arr, len(taus) if k is None else k, unit, words, None))
+        return refused(built_lib, built_lib.lrf_distance_summary(d, n, arr, len(taus) if k is None else k, unit, words, None))
     assert "0 <= N" in summary(n=-1) and "0 <= N" in summary(n=1 << 31)
     assert "n_thresholds" in summary(k=-1) and "n_thresholds" in summary(k=9)
     for bad in (dict(d=None), dict(words=None), dict(taus=None, k=2)):
         assert summary(**bad).endswith(": null argument"), bad
     for bad in (0.0, -2.0, math.nan, math.inf):
         assert "unit" in summary(unit=bad) and "threshold" in summary(taus=(0.1, bad))
-    assert "4-byte aligned" in summary(d=fake + 2) and "8-byte aligned" in summary(words=fake + 4)
+    assert "4-byte aligned" in summary(d=FAKE + 2) and "8-byte aligned" in summary(words=FAKE + 4)
 
 
 def test_the_grid_bytes_refuse_and_follow_the_formula(built_lib):
@@ -386,13 +367,5 @@ def test_the_grid_bytes_refuse_and_follow_the_formula(built_lib):
 
 def test_distance_kernels_use_no_scratch():
     """The kernels of lrf_mesh_distance.inl as __graft_entry__.build() compiles them: the metadata only."""
-    import re
-    from test_isa_checks import BUILD_FLAGS, _device_asm
-    asm = _device_asm(BUILD_FLAGS)
-    for name in KERNELS:
-        hits = re.findall(r"\.amdhsa_kernel (_Z\w*?\d+" + name + r"E\w*)", asm)
-        assert len(hits) == 1, (name, hits)
-        meta = asm[asm.index(".amdhsa_kernel " + hits[0]):]
-        meta = meta[:meta.index(".end_amdhsa_kernel")]
-        priv = re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", meta)
-        assert priv and int(priv[1]) == 0, (name, priv and priv[1])
+    from isa_util import assert_no_scratch, device_asm
+    assert_no_scratch(device_asm(), KERNELS, match="exact")

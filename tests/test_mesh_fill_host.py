@@ -2,12 +2,12 @@
 refusals before any native call (Python and C ABI), the new symbols, the workspace sizes, and the new kernels' scratch use."""
 import ctypes as C
 import math
-import os
 
 import numpy as np
 import pytest
 import torch
 
+from abi_util import FAKE, declared_exported_bound, filled, refused
 from localrf_amd import NativeError, mesh
 from localrf_amd.mesh import fill_holes, holes  # noqa: F401  (what every test here is about)
 from mesh_fill_cases import (CASE_NAMES, CLOSABLE, E2E_BLOCK, HOLE_KEYS, UNCHANGED, boundary_host, cases, e2e_mesh_host, expected, fill_host,
@@ -15,7 +15,6 @@ from mesh_fill_cases import (CASE_NAMES, CLOSABLE, E2E_BLOCK, HOLE_KEYS, UNCHANG
 from mesh_smooth_cases import topology_host
 from mesh_util import DenseStub, bits, cpu_mesh, forbid_native, forbid_render
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMBOLS = ("lrf_mesh_holes_workspace_bytes", "lrf_mesh_holes", "lrf_mesh_fill")
 KERNELS = ("k_hf_zero", "k_hf_edges", "k_hf_next", "k_hf_lead", "k_hf_members", "k_hf_loops", "k_hf_emit", "k_hf_bytes", "k_hf_info")
 
@@ -178,10 +177,7 @@ def test_scene_mesh_checks_the_option_before_it_renders(monkeypatch):
 def test_fill_symbols_declared_exported_bound_and_checked(built_lib):
     from localrf_amd import _native as N
     import __graft_entry__ as ge
-    header = open(os.path.join(ROOT, "include", "lrf.h")).read()
-    for name in SYMBOLS:
-        assert name in N.SYMBOLS and f"{name}(" in header
-        getattr(built_lib, name)
+    header = declared_exported_bound(built_lib, SYMBOLS)
     assert "lrf_mesh_fill.inl" in ge.HEADERS
     assert "typedef struct LrfMeshHoles" in header and C.sizeof(N.LrfMeshHoles) == 3 * 8 + 2 * 8 + 3 * 8 + 2 * 4
     assert N.SYMBOLS["lrf_mesh_holes"][1] == [C.POINTER(N.LrfMeshHoles), C.c_void_p, C.c_void_p, C.c_void_p]
@@ -190,47 +186,36 @@ def test_fill_symbols_declared_exported_bound_and_checked(built_lib):
     assert ("int lrf_mesh_fill(const LrfMeshHoles* m, float* vertices_out, uint8_t* rgb8_out /* nullable */, int32_t* faces_out, "
             "int64_t cap_v,") in header
     assert built_lib.lrf_abi_version() == 7
-    fake = 0x10000
 
-    def err(rc):
-        assert rc != 0                                                          # every call here must be refused: nothing may launch
-        return built_lib.lrf_last_error().decode()
+    def args(**over):
+        return filled(N.LrfMeshHoles, dict(vertices=FAKE, rgb8=None, faces=FAKE, Nv=5, Nf=3, max_edges=64, s=30, lo=(0.0, 0.0, 0.0)), **over)
 
-    def args(lo=(0.0, 0.0, 0.0), **over):
-        a = N.LrfMeshHoles()
-        a.vertices, a.rgb8, a.faces, a.Nv, a.Nf, a.max_edges, a.s = fake, None, fake, 5, 3, 64, 30
-        for k in range(3):
-            a.lo[k] = lo[k]
-        for k, v in over.items():
-            setattr(a, k, v)
-        return a
+    def holes(info=FAKE, wsp=FAKE, **over):
+        return refused(built_lib, built_lib.lrf_mesh_holes(C.byref(args(**over)), info, wsp, None))
 
-    def holes(info=fake, wsp=fake, **over):
-        return err(built_lib.lrf_mesh_holes(C.byref(args(**over)), info, wsp, None))
-
-    def fill(vertices_out=fake + 0x1000, rgb8_out=None, faces_out=fake + 0x2000, cap_v=6, cap_f=6, info=fake, wsp=fake, **over):
-        return err(built_lib.lrf_mesh_fill(C.byref(args(**over)), vertices_out, rgb8_out, faces_out, cap_v, cap_f, info, wsp, None))
+    def fill(vertices_out=FAKE + 0x1000, rgb8_out=None, faces_out=FAKE + 0x2000, cap_v=6, cap_f=6, info=FAKE, wsp=FAKE, **over):
+        return refused(built_lib, built_lib.lrf_mesh_fill(C.byref(args(**over)), vertices_out, rgb8_out, faces_out, cap_v, cap_f, info, wsp, None))
     for fn, who in ((holes, "lrf_mesh_holes: "), (fill, "lrf_mesh_fill: ")):
         for bad in (dict(Nv=0), dict(Nv=-4), dict(Nv=1 << 31), dict(Nf=-1), dict(Nf=1 << 31), dict(Nf=(1 << 31) // 3 + 1)):
             assert fn(**bad) == who + "need 1 <= Nv < 2^31, 0 <= Nf and 3 Nf < 2^31", bad
         for bad in (dict(faces=None), dict(info=None), dict(wsp=None), dict(vertices=None)):
             assert fn(**bad) == who + "null argument", bad
-        assert "4-byte aligned" in fn(faces=fake + 2) and "4-byte aligned" in fn(vertices=fake + 1)
-        assert "8-byte aligned" in fn(info=fake + 4) and "8-byte aligned" in fn(wsp=fake + 4)
+        assert "4-byte aligned" in fn(faces=FAKE + 2) and "4-byte aligned" in fn(vertices=FAKE + 1)
+        assert "8-byte aligned" in fn(info=FAKE + 4) and "8-byte aligned" in fn(wsp=FAKE + 4)
         for bad in (2, 0, -1, 4097, 1 << 30):
             assert fn(max_edges=bad) == who + "max_edges must lie in [3, 4096]"
         for bad in (257, -257, 1 << 30):
             assert "s must lie in [-256, 256]" in fn(s=bad)
         for bad in ((math.nan, 0.0, 0.0), (0.0, math.inf, 0.0), (0.0, 0.0, -math.inf)):
             assert "lo must hold 3 finite values" in fn(lo=bad)
-    assert built_lib.lrf_mesh_holes(None, fake, fake, None) != 0 and built_lib.lrf_mesh_fill(None, fake, None, fake, 6, 6, fake, fake, None) != 0
+    assert built_lib.lrf_mesh_holes(None, FAKE, FAKE, None) != 0 and built_lib.lrf_mesh_fill(None, FAKE, None, FAKE, 6, 6, FAKE, FAKE, None) != 0
     assert fill(vertices_out=None).endswith(": null argument") and fill(faces_out=None).endswith(": null argument")
-    assert "4-byte aligned" in fill(vertices_out=fake + 0x1002) and "4-byte aligned" in fill(faces_out=fake + 0x2001)
-    assert "go together" in fill(rgb8_out=fake + 0x3000) and "go together" in fill(rgb8=fake + 0x3000)
+    assert "4-byte aligned" in fill(vertices_out=FAKE + 0x1002) and "4-byte aligned" in fill(faces_out=FAKE + 0x2001)
+    assert "go together" in fill(rgb8_out=FAKE + 0x3000) and "go together" in fill(rgb8=FAKE + 0x3000)
     for bad in (dict(cap_v=4), dict(cap_f=2), dict(cap_v=1 << 31), dict(cap_f=1 << 31), dict(cap_v=-1)):
         assert "need Nv <= cap_v < 2^31 and Nf <= cap_f < 2^31" in fill(**bad), bad
-    assert "must not be its input" in fill(vertices_out=fake) and "must not be its input" in fill(faces_out=fake)
-    assert "must not be its input" in fill(rgb8=fake + 0x3000, rgb8_out=fake + 0x3000)
+    assert "must not be its input" in fill(vertices_out=FAKE) and "must not be its input" in fill(faces_out=FAKE)
+    assert "must not be its input" in fill(rgb8=FAKE + 0x3000, rgb8_out=FAKE + 0x3000)
 
 
 def test_workspace_bytes_refuse_are_aligned_and_hold_the_lists(built_lib):
@@ -252,13 +237,5 @@ def test_workspace_bytes_refuse_are_aligned_and_hold_the_lists(built_lib):
 def test_fill_kernels_use_no_scratch():
     """The kernels of lrf_mesh_fill.inl, and k_sm_edges around the loop they share with it, as __graft_entry__.build() compiles
     them: the metadata only."""
-    import re
-    from test_isa_checks import BUILD_FLAGS, _device_asm
-    asm = _device_asm(BUILD_FLAGS)
-    for name in KERNELS + ("k_sm_edges",):
-        hits = re.findall(r"\.amdhsa_kernel (_Z\w*?\d+" + name + r"E\w*)", asm)
-        assert len(hits) == 1, (name, hits)
-        meta = asm[asm.index(".amdhsa_kernel " + hits[0]):]
-        meta = meta[:meta.index(".end_amdhsa_kernel")]
-        priv = re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", meta)
-        assert priv and int(priv[1]) == 0, (name, priv and priv[1])
+    from isa_util import assert_no_scratch, device_asm
+    assert_no_scratch(device_asm(), KERNELS + ("k_sm_edges",), match="exact")

@@ -4,18 +4,17 @@ where weights are missing --, the restated integration on a plane it must recove
 (Python and C ABI), the PLY writer's faces, and the new symbols."""
 import ctypes as C
 import math
-import os
 
 import numpy as np
 import pytest
 import torch
 
+from abi_util import FAKE, declared_exported_bound, filled, refused
 from localrf_amd import NativeError, mesh, pointcloud
 from mesh_cases import (H_ANALYTIC, N_ANALYTIC, SPHERE_C, SPHERE_R, boundary_edges, closed_manifold_euler, extract_host,
                         integrate_host, new_volume, signed_volume, sphere_field, tet_case, tet_corners, torus_field)
 from mesh_util import DenseStub, forbid_native, forbid_render
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
@@ -327,26 +326,17 @@ def test_write_ply_faces_round_trip(tmp_path, sphere):
 
 def test_mesh_symbols_declared_exported_and_checked(built_lib):
     from localrf_amd import _native as N
-    header = open(os.path.join(ROOT, "include", "lrf.h")).read()
-    for name in ("lrf_tsdf_integrate", "lrf_mesh_workspace_bytes", "lrf_mesh_extract"):
-        assert name in N.SYMBOLS and f"{name}(" in header
-        getattr(built_lib, name)
+    header = declared_exported_bound(built_lib, ("lrf_tsdf_integrate", "lrf_mesh_workspace_bytes", "lrf_mesh_extract"))
     assert "typedef struct LrfTsdfVolume" in header and "typedef struct LrfMeshExtract" in header
     assert C.sizeof(N.LrfTsdfVolume) == 3 * 8 + 3 * 4 + 5 * 4 and C.sizeof(N.LrfMeshExtract) == 3 * 8 + 3 * 4 + 6 * 4 + 4    # padded to 8
     assert built_lib.lrf_abi_version() == 7
     ws = built_lib.lrf_mesh_workspace_bytes
     assert ws(0, 4, 5) == 0 and ws(4, -1, 5) == 0 and ws(2048, 2048, 512) == 0 and ws(1 << 16, 1 << 16, 1) == 0
     assert ws(1, 1, 1) == 256 and ws(256, 256, 256) >= 4 * 256 ** 3 + 8 * 256 ** 3 // 256
-    fake = 0x10000
 
-    def integrate(depth=fake, rgb8=fake, c2w=fake, focal=fake, center=fake, V=2, H=4, W=5, d_min=0.0, d_max=math.inf, **over):
-        a = N.LrfTsdfVolume()
-        a.tsdf, a.weight, a.rgb, a.Nx, a.Ny, a.Nz, a.voxel, a.trunc = fake, fake, fake, 3, 4, 5, 0.1, 0.3
-        for k, v in over.items():
-            setattr(a, k, v)
-        rc = built_lib.lrf_tsdf_integrate(C.byref(a), depth, rgb8, c2w, focal, center, V, H, W, d_min, d_max, None)
-        assert rc != 0                                                   # every call here must be refused: nothing may launch
-        return built_lib.lrf_last_error().decode()
+    def integrate(depth=FAKE, rgb8=FAKE, c2w=FAKE, focal=FAKE, center=FAKE, V=2, H=4, W=5, d_min=0.0, d_max=math.inf, **over):
+        a = filled(N.LrfTsdfVolume, dict(tsdf=FAKE, weight=FAKE, rgb=FAKE, Nx=3, Ny=4, Nz=5, voxel=0.1, trunc=0.3), **over)
+        return refused(built_lib, built_lib.lrf_tsdf_integrate(C.byref(a), depth, rgb8, c2w, focal, center, V, H, W, d_min, d_max, None))
     for bad in (dict(Nx=0), dict(Ny=-1), dict(Nz=0), dict(Nx=2048, Ny=2048, Nz=512)):
         assert "need Nx, Ny, Nz >= 1 and Nx Ny Nz < 2^31" in integrate(**bad)
     for bad in (dict(V=0), dict(H=0), dict(W=-1), dict(V=1 << 20, H=1 << 10, W=2)):
@@ -357,17 +347,12 @@ def test_mesh_symbols_declared_exported_and_checked(built_lib):
     assert "voxel" in integrate(voxel=0.0) and "voxel" in integrate(voxel=math.nan)
     assert "trunc" in integrate(trunc=0.0) and "trunc" in integrate(trunc=-1.0) and "trunc" in integrate(trunc=math.nan)
     assert "d_min <= d_max" in integrate(d_min=2.0, d_max=1.0) and "d_min <= d_max" in integrate(d_min=math.nan)
-    assert "4-byte aligned" in integrate(tsdf=fake + 2) and "4-byte aligned" in integrate(depth=fake + 1)
-    assert built_lib.lrf_tsdf_integrate(None, fake, fake, fake, fake, fake, 2, 4, 5, 0.0, 1.0, None) != 0
+    assert "4-byte aligned" in integrate(tsdf=FAKE + 2) and "4-byte aligned" in integrate(depth=FAKE + 1)
+    assert built_lib.lrf_tsdf_integrate(None, FAKE, FAKE, FAKE, FAKE, FAKE, 2, 4, 5, 0.0, 1.0, None) != 0
 
-    def extract(max_v=10, max_f=10, vertices=fake, rgb8_out=fake, faces=fake, counts=fake, wsp=fake, **over):
-        a = N.LrfMeshExtract()
-        a.value, a.weight, a.rgb, a.Nx, a.Ny, a.Nz, a.voxel, a.level, a.min_weight = fake, fake, fake, 3, 4, 5, 0.1, 0.0, 1.0
-        for k, v in over.items():
-            setattr(a, k, v)
-        rc = built_lib.lrf_mesh_extract(C.byref(a), max_v, max_f, vertices, rgb8_out, faces, counts, wsp, None)
-        assert rc != 0
-        return built_lib.lrf_last_error().decode()
+    def extract(max_v=10, max_f=10, vertices=FAKE, rgb8_out=FAKE, faces=FAKE, counts=FAKE, wsp=FAKE, **over):
+        a = filled(N.LrfMeshExtract, dict(value=FAKE, weight=FAKE, rgb=FAKE, Nx=3, Ny=4, Nz=5, voxel=0.1, level=0.0, min_weight=1.0), **over)
+        return refused(built_lib, built_lib.lrf_mesh_extract(C.byref(a), max_v, max_f, vertices, rgb8_out, faces, counts, wsp, None))
     for bad in (dict(Nx=0), dict(Nz=-3), dict(Nx=2048, Ny=2048, Nz=512)):
         assert "need Nx, Ny, Nz >= 1 and Nx Ny Nz < 2^31" in extract(**bad)
     for bad in (dict(value=None), dict(vertices=None), dict(faces=None), dict(counts=None), dict(wsp=None)):
@@ -376,25 +361,17 @@ def test_mesh_symbols_declared_exported_and_checked(built_lib):
     assert "voxel" in extract(voxel=-0.1) and "level" in extract(level=math.nan)
     assert "min_weight" in extract(min_weight=0.0) and "min_weight" in extract(min_weight=math.nan)
     assert "[0, 2^31)" in extract(max_v=-1) and "[0, 2^31)" in extract(max_f=1 << 31)
-    assert "4-byte aligned" in extract(vertices=fake + 2) and "4-byte aligned" in extract(wsp=fake + 1)
-    assert "8-byte aligned" in extract(counts=fake + 4)
-    assert built_lib.lrf_mesh_extract(None, 1, 1, fake, fake, fake, fake, fake, None) != 0
+    assert "4-byte aligned" in extract(vertices=FAKE + 2) and "4-byte aligned" in extract(wsp=FAKE + 1)
+    assert "8-byte aligned" in extract(counts=FAKE + 4)
+    assert built_lib.lrf_mesh_extract(None, 1, 1, FAKE, FAKE, FAKE, FAKE, FAKE, None) != 0
 
 
 def test_mesh_kernels_use_no_scratch_and_keep_the_pose_in_scalar_registers():
     """k_tsdf_integrate, k_mesh_count and k_mesh_emit as __graft_entry__.build() compiles them: no scratch; the frame loop reads
     the camera matrix with scalar loads, divides in full precision and rounds to nearest even."""
     import re
-    from test_isa_checks import BUILD_FLAGS, _body, _device_asm
-    asm = _device_asm(BUILD_FLAGS)
-    found = [(n, b) for pat in (r"k_tsdf_integrate", r"k_mesh_count", r"k_mesh_emit") for n, b in _body(asm, pat)]
-    assert len(found) == 3
-    for name, body in found:
-        meta = asm[asm.index(".amdhsa_kernel " + name):]
-        meta = meta[:meta.index(".end_amdhsa_kernel")]
-        priv = re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", meta)
-        assert priv and int(priv[1]) == 0, (name, priv and priv[1])
-        assert "scratch_" not in body, name
+    from isa_util import assert_no_scratch, device_asm
+    found = assert_no_scratch(device_asm(), (r"k_tsdf_integrate", r"k_mesh_count", r"k_mesh_emit"), match="search", total=3, body_too=True)
     integ = found[0][1]
     assert "v_div_fixup_f32" in integ and "v_rndne_f32" in integ
     assert re.search(r"s_load_dwordx(4|8)", integ)

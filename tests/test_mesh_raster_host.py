@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 import torch
 
+from abi_util import FAKE, declared_exported_bound, filled, refused
 from localrf_amd import NativeError, mesh_raster
 from localrf_amd.mesh_raster import depth_agreement, rasterize, scene_mesh_agreement
 from mesh_raster_cases import (AGREEMENT_SHAPES, AGREEMENT_TOLS, AG_SCALE, BOX_FACE, CASE_NAMES, SMALL_MAX, SPHERE_KIND,
@@ -272,31 +273,20 @@ def test_scene_mesh_agreement_checks_before_it_renders(monkeypatch):
 
 def test_raster_symbols_declared_exported_bound_and_checked(built_lib):
     from localrf_amd import _native as N
-    header = open(os.path.join(ROOT, "include", "lrf.h")).read()
+    header = declared_exported_bound(built_lib, SYMBOLS)
     debug = open(os.path.join(ROOT, "include", "lrf_debug.h")).read()
-    for name in SYMBOLS:
-        assert name in N.SYMBOLS and f"{name}(" in header
-        getattr(built_lib, name)
     assert "lrf_debug_mesh_rasterize(" in debug and "lrf_debug_mesh_rasterize" in N.SYMBOLS
     getattr(built_lib, "lrf_debug_mesh_rasterize")
     assert "typedef struct LrfMeshRaster" in header and C.sizeof(N.LrfMeshRaster) == 6 * 8 + 2 * 8 + 4 * 4 + 2 * 4
     assert "#define LRF_AGREEMENT_MAX_TOLS 8" in header and N.LRF_AGREEMENT_MAX_TOLS == 8
     assert built_lib.lrf_abi_version() == 7
-    fake = 0x10000
 
-    def err(rc):
-        assert rc != 0                                                      # every call here must be refused: nothing may launch
-        return built_lib.lrf_last_error().decode()
-
-    def ras(debug=False, small_max=64, depth=fake, face=fake, rgb8_out=None, weights=fake, crossings=fake, info=fake, wsp=fake, **over):
-        a = N.LrfMeshRaster()
-        a.vertices, a.faces, a.cam2world, a.focal, a.center = fake, fake, fake, fake, fake
-        a.Nv, a.Nf, a.V, a.H, a.W, a.cull, a.d_min, a.d_max = 5, 3, 2, 6, 8, 0, 0.0, math.inf
-        for k, v in over.items():
-            setattr(a, k, v)
+    def ras(debug=False, small_max=64, depth=FAKE, face=FAKE, rgb8_out=None, weights=FAKE, crossings=FAKE, info=FAKE, wsp=FAKE, **over):
+        a = filled(N.LrfMeshRaster, dict(vertices=FAKE, faces=FAKE, cam2world=FAKE, focal=FAKE, center=FAKE, Nv=5, Nf=3, V=2, H=6, W=8, cull=0,
+                                         d_min=0.0, d_max=math.inf), **over)
         if debug:
-            return err(built_lib.lrf_debug_mesh_rasterize(C.byref(a), depth, face, rgb8_out, weights, crossings, info, wsp, small_max, None))
-        return err(built_lib.lrf_mesh_rasterize(C.byref(a), depth, face, rgb8_out, weights, crossings, info, wsp, None))
+            return refused(built_lib, built_lib.lrf_debug_mesh_rasterize(C.byref(a), depth, face, rgb8_out, weights, crossings, info, wsp, small_max, None))
+        return refused(built_lib, built_lib.lrf_mesh_rasterize(C.byref(a), depth, face, rgb8_out, weights, crossings, info, wsp, None))
     for dbg in (False, True):
         who = "lrf_debug_mesh_rasterize" if dbg else "lrf_mesh_rasterize"
         for bad in (dict(V=0), dict(H=0), dict(W=-1), dict(V=1 << 15, H=1 << 8, W=1 << 8), dict(Nv=-1), dict(Nv=1 << 31), dict(Nf=-1),
@@ -306,19 +296,19 @@ def test_raster_symbols_declared_exported_bound_and_checked(built_lib):
             assert ras(dbg, **bad).endswith(": null argument"), bad
         for bad in (dict(depth=None), dict(face=None), dict(info=None), dict(wsp=None)):
             assert ras(dbg, **bad).endswith(": null argument"), bad
-        assert "go together" in ras(dbg, rgb8=fake) and "go together" in ras(dbg, rgb8_out=fake)
+        assert "go together" in ras(dbg, rgb8=FAKE) and "go together" in ras(dbg, rgb8_out=FAKE)
         for bad in (-1, 3):
             assert "cull" in ras(dbg, cull=bad)
         assert "d_min <= d_max" in ras(dbg, d_min=2.0, d_max=1.0) and "d_min <= d_max" in ras(dbg, d_min=math.nan)
-        for bad in (dict(vertices=fake + 2), dict(depth=fake + 1), dict(weights=fake + 2), dict(crossings=fake + 3), dict(focal=fake + 2)):
+        for bad in (dict(vertices=FAKE + 2), dict(depth=FAKE + 1), dict(weights=FAKE + 2), dict(crossings=FAKE + 3), dict(focal=FAKE + 2)):
             assert "4-byte aligned" in ras(dbg, **bad), bad
-        assert "8-byte aligned" in ras(dbg, info=fake + 4) and "8-byte aligned" in ras(dbg, wsp=fake + 4)
+        assert "8-byte aligned" in ras(dbg, info=FAKE + 4) and "8-byte aligned" in ras(dbg, wsp=FAKE + 4)
     assert "small_max" in ras(True, small_max=-1)
-    assert built_lib.lrf_mesh_rasterize(None, fake, fake, None, None, None, fake, fake, None) != 0
+    assert built_lib.lrf_mesh_rasterize(None, FAKE, FAKE, None, None, None, FAKE, FAKE, None) != 0
 
-    def agree(a=fake, b=fake, V=2, H=6, W=8, tols=(0.01, 0.05), n=None, d_min=0.0, d_max=math.inf, counts=fake, emap=None):
+    def agree(a=FAKE, b=FAKE, V=2, H=6, W=8, tols=(0.01, 0.05), n=None, d_min=0.0, d_max=math.inf, counts=FAKE, emap=None):
         arr = (C.c_float * 9)(*tols) if tols is not None else None
-        return err(built_lib.lrf_depth_agreement(a, b, V, H, W, arr, len(tols) if n is None else n, d_min, d_max, counts, emap, None))
+        return refused(built_lib, built_lib.lrf_depth_agreement(a, b, V, H, W, arr, len(tols) if n is None else n, d_min, d_max, counts, emap, None))
     for bad in (dict(V=0), dict(V=65536, H=1, W=1), dict(H=0), dict(W=0), dict(V=1 << 10, H=1 << 11, W=1 << 10)):
         assert "need 1 <= V <= 65535" in agree(**bad), bad
     for bad in (-1, 9):
@@ -328,7 +318,7 @@ def test_raster_symbols_declared_exported_bound_and_checked(built_lib):
     assert "d_min <= d_max" in agree(d_min=1.0, d_max=0.5)
     for bad in ((-0.5,), (0.1, math.nan)):
         assert "tolerance" in agree(tols=bad)
-    assert "4-byte aligned" in agree(a=fake + 2) and "4-byte aligned" in agree(emap=fake + 1) and "8-byte aligned" in agree(counts=fake + 4)
+    assert "4-byte aligned" in agree(a=FAKE + 2) and "4-byte aligned" in agree(emap=FAKE + 1) and "8-byte aligned" in agree(counts=FAKE + 4)
 
 
 def test_workspace_bytes_refuse_and_follow_the_formula(built_lib):
@@ -344,13 +334,5 @@ def test_workspace_bytes_refuse_and_follow_the_formula(built_lib):
 
 def test_raster_kernels_use_no_scratch():
     """The kernels of lrf_mesh_raster.inl as __graft_entry__.build() compiles them: the metadata only."""
-    import re
-    from test_isa_checks import BUILD_FLAGS, _device_asm
-    asm = _device_asm(BUILD_FLAGS)
-    for name in KERNELS:
-        hits = re.findall(r"\.amdhsa_kernel (_Z\w*?\d+" + name + r"E\w*)", asm)
-        assert len(hits) == 1, (name, hits)
-        meta = asm[asm.index(".amdhsa_kernel " + hits[0]):]
-        meta = meta[:meta.index(".end_amdhsa_kernel")]
-        priv = re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", meta)
-        assert priv and int(priv[1]) == 0, (name, priv and priv[1])
+    from isa_util import assert_no_scratch, device_asm
+    assert_no_scratch(device_asm(), KERNELS, match="exact")

@@ -3,19 +3,18 @@
 the workspace size, and the new kernels' scratch use."""
 import ctypes as C
 import math
-import os
 
 import numpy as np
 import pytest
 import torch
 
+from abi_util import FAKE, declared_exported_bound, filled, refused
 from localrf_amd import NativeError, mesh
 from mesh_cases import H_ANALYTIC
 from mesh_simplify_cases import (CASE_NAMES, canonical, cases, cells_host, expected_simplified, face_keys, simplify_host,
                                  smallest_blob)
 from mesh_util import DenseStub, cpu_mesh, forbid_native, forbid_render
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMBOLS = ("lrf_mesh_simplify_bounds", "lrf_mesh_simplify_workspace_bytes", "lrf_mesh_simplify")
 KERNELS = ("k_ms_bounds_init", "k_ms_bounds", "k_ms_zero", "k_ms_mark", "k_ms_count_words", "k_ms_accumulate", "k_ms_faces_map",
            "k_ms_faces_insert", "k_ms_faces_keep", "k_ms_write", "k_ms_finish")
@@ -157,21 +156,13 @@ def test_scene_mesh_checks_simplify_cell_before_it_renders(monkeypatch):
 
 def test_simplify_symbols_declared_exported_bound_and_checked(built_lib):
     from localrf_amd import _native as N
-    header = open(os.path.join(ROOT, "include", "lrf.h")).read()
-    for name in SYMBOLS:
-        assert name in N.SYMBOLS and f"{name}(" in header
-        getattr(built_lib, name)
+    header = declared_exported_bound(built_lib, SYMBOLS)
     assert "typedef struct LrfMeshSimplify" in header and C.sizeof(N.LrfMeshSimplify) == 3 * 8 + 2 * 8 + 4 * 8 + 6 * 4 + 2 * 4
     assert built_lib.lrf_abi_version() == 7
-    fake = 0x10000
     o3 = (C.c_double * 3)(0.0, 0.0, 0.0)
 
-    def err(rc):
-        assert rc != 0                                                  # every call here must be refused: nothing may launch
-        return built_lib.lrf_last_error().decode()
-
-    def bounds(vertices=fake, Nv=5, origin=o3, cell=1.0, out=fake):
-        return err(built_lib.lrf_mesh_simplify_bounds(vertices, Nv, origin, cell, out, None))
+    def bounds(vertices=FAKE, Nv=5, origin=o3, cell=1.0, out=FAKE):
+        return refused(built_lib, built_lib.lrf_mesh_simplify_bounds(vertices, Nv, origin, cell, out, None))
     for bad in (0, -4, 1 << 31):
         assert "1 <= Nv < 2^31" in bounds(Nv=bad)
     for bad in (dict(vertices=None), dict(origin=None), dict(out=None)):
@@ -180,17 +171,12 @@ def test_simplify_symbols_declared_exported_bound_and_checked(built_lib):
         assert "origin" in bounds(origin=(C.c_double * 3)(*bad))
     for bad in (0.0, -1.0, math.nan, math.inf):
         assert "cell must be finite and > 0" in bounds(cell=bad)
-    assert "4-byte aligned" in bounds(vertices=fake + 2) and "4-byte aligned" in bounds(out=fake + 1)
+    assert "4-byte aligned" in bounds(vertices=FAKE + 2) and "4-byte aligned" in bounds(out=FAKE + 1)
 
-    def simp(vertices_out=fake, rgb8_out=fake, faces_out=fake, counts=fake, wsp=fake, origin=(0.0, 0.0, 0.0), dims=(4, 4, 4),
-             lo=(0, 0, 0), **over):
-        a = N.LrfMeshSimplify()
-        a.vertices, a.rgb8, a.faces, a.Nv, a.Nf, a.cell, a.dedupe = fake, fake, fake, 5, 3, 1.0, 1
-        for k in range(3):
-            a.origin[k], a.dims[k], a.lo[k] = origin[k], dims[k], lo[k]
-        for k, v in over.items():
-            setattr(a, k, v)
-        return err(built_lib.lrf_mesh_simplify(C.byref(a), vertices_out, rgb8_out, faces_out, counts, wsp, None))
+    def simp(vertices_out=FAKE, rgb8_out=FAKE, faces_out=FAKE, counts=FAKE, wsp=FAKE, **over):
+        a = filled(N.LrfMeshSimplify, dict(vertices=FAKE, rgb8=FAKE, faces=FAKE, Nv=5, Nf=3, cell=1.0, dedupe=1, origin=(0.0, 0.0, 0.0),
+                                           dims=(4, 4, 4), lo=(0, 0, 0)), **over)
+        return refused(built_lib, built_lib.lrf_mesh_simplify(C.byref(a), vertices_out, rgb8_out, faces_out, counts, wsp, None))
     for bad in (dict(Nv=0), dict(Nf=-1), dict(Nv=1 << 31), dict(Nf=1 << 31)):
         assert "need 1 <= Nv < 2^31 and 0 <= Nf < 2^31" in simp(**bad), bad
     for bad in (dict(vertices=None), dict(faces=None), dict(vertices_out=None), dict(faces_out=None), dict(counts=None), dict(wsp=None)):
@@ -203,10 +189,10 @@ def test_simplify_symbols_declared_exported_bound_and_checked(built_lib):
         assert "origin" in simp(origin=bad)
     for bad in (0.0, -1.0, math.nan, math.inf):
         assert "cell must be finite and > 0" in simp(cell=bad)
-    for bad in (dict(vertices=fake + 2), dict(faces=fake + 1), dict(vertices_out=fake + 2), dict(faces_out=fake + 2)):
+    for bad in (dict(vertices=FAKE + 2), dict(faces=FAKE + 1), dict(vertices_out=FAKE + 2), dict(faces_out=FAKE + 2)):
         assert "4-byte aligned" in simp(**bad), bad
-    assert "8-byte aligned" in simp(counts=fake + 4) and "8-byte aligned" in simp(wsp=fake + 4)
-    assert built_lib.lrf_mesh_simplify(None, fake, fake, fake, fake, fake, None) != 0
+    assert "8-byte aligned" in simp(counts=FAKE + 4) and "8-byte aligned" in simp(wsp=FAKE + 4)
+    assert built_lib.lrf_mesh_simplify(None, FAKE, FAKE, FAKE, FAKE, FAKE, None) != 0
 
 
 def test_workspace_bytes_refuses_and_grows(built_lib):
@@ -230,13 +216,5 @@ def test_workspace_bytes_refuses_and_grows(built_lib):
 
 def test_simplify_kernels_use_no_scratch():
     """The kernels of lrf_mesh_simplify.inl as __graft_entry__.build() compiles them: the metadata only."""
-    import re
-    from test_isa_checks import BUILD_FLAGS, _device_asm
-    asm = _device_asm(BUILD_FLAGS)
-    for name in KERNELS:
-        hits = re.findall(r"\.amdhsa_kernel (_Z\w*?\d+" + name + r"E\w*)", asm)
-        assert len(hits) == 1, (name, hits)
-        meta = asm[asm.index(".amdhsa_kernel " + hits[0]):]
-        meta = meta[:meta.index(".end_amdhsa_kernel")]
-        priv = re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", meta)
-        assert priv and int(priv[1]) == 0, (name, priv and priv[1])
+    from isa_util import assert_no_scratch, device_asm
+    assert_no_scratch(device_asm(), KERNELS, match="exact")

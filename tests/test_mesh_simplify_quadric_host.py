@@ -5,18 +5,17 @@ scratch use."""
 import ctypes as C
 import inspect
 import math
-import os
 
 import numpy as np
 import pytest
 
+from abi_util import FAKE, declared_exported_bound, filled, refused
 from localrf_amd import NativeError, mesh
 from mesh_simplify_cases import expected_simplified, face_keys
 from mesh_simplify_quadric_cases import (ANALYTIC_NAMES, CAP, CAPPED, CASE_NAMES, CUBE_HI, CUBE_LO, PLANE, REGULARIZE, cases,
                                          expected_quadric, signed_volume)
 from mesh_util import cpu_mesh, forbid_native
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMBOLS = ("lrf_mesh_simplify_quadric_workspace_bytes", "lrf_mesh_simplify_quadric")
 KERNELS = ("k_ms_quadric_zero", "k_ms_quadric_exponent", "k_ms_quadric_accumulate", "k_ms_quadric_place")
 # the rows of the issue's table: |signed volume out - signed volume in| must fall; the torus at 9 steps collapses to zero
@@ -149,29 +148,18 @@ def test_python_refusals_before_any_native_call(monkeypatch):
 
 def test_quadric_symbols_declared_exported_bound_and_checked(built_lib):
     from localrf_amd import _native as N
-    header = open(os.path.join(ROOT, "include", "lrf.h")).read()
-    for name in SYMBOLS:
-        assert name in N.SYMBOLS and f"{name}(" in header
-        getattr(built_lib, name)
+    header = declared_exported_bound(built_lib, SYMBOLS)
     assert "typedef struct LrfMeshSimplifyQuadric" in header
     assert C.sizeof(N.LrfMeshSimplifyQuadric) == C.sizeof(N.LrfMeshSimplify) + 8 == 112
     assert N.LrfMeshSimplifyQuadric.mesh.offset == 0 and N.LrfMeshSimplifyQuadric.regularize.offset == 104
     assert built_lib.lrf_abi_version() == 7
-    fake = 0x10000
 
-    def simp(vertices_out=fake, rgb8_out=fake, faces_out=fake, counts=fake, wsp=fake, origin=(0.0, 0.0, 0.0), dims=(4, 4, 4),
-             lo=(0, 0, 0), regularize=REGULARIZE, **over):
+    def simp(vertices_out=FAKE, rgb8_out=FAKE, faces_out=FAKE, counts=FAKE, wsp=FAKE, regularize=REGULARIZE, **over):
         q = N.LrfMeshSimplifyQuadric()
-        a = q.mesh
-        a.vertices, a.rgb8, a.faces, a.Nv, a.Nf, a.cell, a.dedupe = fake, fake, fake, 5, 3, 1.0, 1
         q.regularize = regularize
-        for k in range(3):
-            a.origin[k], a.dims[k], a.lo[k] = origin[k], dims[k], lo[k]
-        for k, v in over.items():
-            setattr(a, k, v)
-        rc = built_lib.lrf_mesh_simplify_quadric(C.byref(q), vertices_out, rgb8_out, faces_out, counts, wsp, None)
-        assert rc != 0                                                  # every call here must be refused: nothing may launch
-        return built_lib.lrf_last_error().decode()
+        q.mesh = filled(N.LrfMeshSimplify, dict(vertices=FAKE, rgb8=FAKE, faces=FAKE, Nv=5, Nf=3, cell=1.0, dedupe=1, origin=(0.0, 0.0, 0.0),
+                                                dims=(4, 4, 4), lo=(0, 0, 0)), **over)
+        return refused(built_lib, built_lib.lrf_mesh_simplify_quadric(C.byref(q), vertices_out, rgb8_out, faces_out, counts, wsp, None))
     for bad in (dict(Nv=0), dict(Nf=-1), dict(Nv=1 << 31), dict(Nf=1 << 31)):
         assert "need 1 <= Nv < 2^31 and 0 <= Nf < 2^31" in simp(**bad), bad
     for bad in (dict(vertices=None), dict(faces=None), dict(vertices_out=None), dict(faces_out=None), dict(counts=None), dict(wsp=None)):
@@ -184,12 +172,12 @@ def test_quadric_symbols_declared_exported_bound_and_checked(built_lib):
         assert "origin" in simp(origin=bad)
     for bad in (0.0, -1.0, math.nan, math.inf):
         assert "cell must be finite and > 0" in simp(cell=bad)
-    for bad in (dict(vertices=fake + 2), dict(faces=fake + 1), dict(vertices_out=fake + 2), dict(faces_out=fake + 2)):
+    for bad in (dict(vertices=FAKE + 2), dict(faces=FAKE + 1), dict(vertices_out=FAKE + 2), dict(faces_out=FAKE + 2)):
         assert "4-byte aligned" in simp(**bad), bad
-    assert "8-byte aligned" in simp(counts=fake + 4) and "8-byte aligned" in simp(wsp=fake + 4)
+    assert "8-byte aligned" in simp(counts=FAKE + 4) and "8-byte aligned" in simp(wsp=FAKE + 4)
     for bad in (0.0, -0.0, -2.0 ** -10, 1.0000000000000002, 2.0, math.nan, math.inf, -math.inf):
         assert simp(regularize=bad) == "lrf_mesh_simplify_quadric: regularize must lie in (0, 1]", bad
-    assert built_lib.lrf_mesh_simplify_quadric(None, fake, fake, fake, fake, fake, None) != 0
+    assert built_lib.lrf_mesh_simplify_quadric(None, FAKE, FAKE, FAKE, FAKE, FAKE, None) != 0
 
 
 def test_workspace_bytes_refuses_and_holds_the_sums(built_lib):
@@ -205,13 +193,5 @@ def test_workspace_bytes_refuses_and_holds_the_sums(built_lib):
 
 def test_quadric_kernels_use_no_scratch():
     """The new kernels as __graft_entry__.build() compiles them: the metadata only."""
-    import re
-    from test_isa_checks import BUILD_FLAGS, _device_asm
-    asm = _device_asm(BUILD_FLAGS)
-    for name in KERNELS:
-        hits = re.findall(r"\.amdhsa_kernel (_Z\w*?\d+" + name + r"E\w*)", asm)
-        assert len(hits) == 1, (name, hits)
-        meta = asm[asm.index(".amdhsa_kernel " + hits[0]):]
-        meta = meta[:meta.index(".end_amdhsa_kernel")]
-        priv = re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", meta)
-        assert priv and int(priv[1]) == 0, (name, priv and priv[1])
+    from isa_util import assert_no_scratch, device_asm
+    assert_no_scratch(device_asm(), KERNELS, match="exact")

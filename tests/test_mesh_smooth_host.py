@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+from abi_util import FAKE, declared_exported_bound, filled, refused
 from localrf_amd import NativeError, mesh
 from localrf_amd.mesh import smooth, topology, vertex_normals  # noqa: F401  (what every test here is about)
 from mesh_cases import SPHERE_C
@@ -202,56 +203,44 @@ def test_scene_mesh_checks_the_options_before_it_renders(monkeypatch):
 
 def test_smooth_symbols_declared_exported_bound_and_checked(built_lib):
     from localrf_amd import _native as N
-    header = open(os.path.join(ROOT, "include", "lrf.h")).read()
+    header = declared_exported_bound(built_lib, SYMBOLS)
     debug = open(os.path.join(ROOT, "include", "lrf_debug.h")).read()
-    for name in SYMBOLS:
-        assert name in N.SYMBOLS and f"{name}(" in header
-        getattr(built_lib, name)
     assert "lrf_debug_mesh_vertex_normals(" in debug and "lrf_debug_mesh_vertex_normals" in N.SYMBOLS
     assert "typedef struct LrfMeshSmooth" in header and C.sizeof(N.LrfMeshSmooth) == 2 * 8 + 2 * 8 + 5 * 8 + 4 * 4
     assert built_lib.lrf_abi_version() == 7
-    fake = 0x10000
-
-    def err(rc):
-        assert rc != 0                                                      # every call here must be refused: nothing may launch
-        return built_lib.lrf_last_error().decode()
     sizes = (dict(Nv=0), dict(Nv=-4), dict(Nv=1 << 31), dict(Nf=-1), dict(Nf=1 << 31), dict(Nf=(1 << 31) // 3 + 1))
 
-    def incidence(faces=fake, Nv=5, Nf=3, info=fake, wsp=fake):
-        return err(built_lib.lrf_mesh_incidence(faces, Nv, Nf, info, wsp, None))
+    def incidence(faces=FAKE, Nv=5, Nf=3, info=FAKE, wsp=FAKE):
+        return refused(built_lib, built_lib.lrf_mesh_incidence(faces, Nv, Nf, info, wsp, None))
 
-    def topology(faces=fake, Nv=5, Nf=3, boundary=fake, info=fake, wsp=fake):
-        return err(built_lib.lrf_mesh_topology(faces, Nv, Nf, boundary, info, wsp, None))
+    def topology(faces=FAKE, Nv=5, Nf=3, boundary=FAKE, info=FAKE, wsp=FAKE):
+        return refused(built_lib, built_lib.lrf_mesh_topology(faces, Nv, Nf, boundary, info, wsp, None))
 
-    def normals(vertices=fake, faces=fake, Nv=5, Nf=3, out=fake, info=fake, wsp=fake):
-        return err(built_lib.lrf_mesh_vertex_normals(vertices, faces, Nv, Nf, out, info, wsp, None))
+    def normals(vertices=FAKE, faces=FAKE, Nv=5, Nf=3, out=FAKE, info=FAKE, wsp=FAKE):
+        return refused(built_lib, built_lib.lrf_mesh_vertex_normals(vertices, faces, Nv, Nf, out, info, wsp, None))
 
-    def debug_normals(vertices=fake, faces=fake, Nv=5, Nf=3, out=fake, S=fake, E=fake, info=fake, wsp=fake):
-        return err(built_lib.lrf_debug_mesh_vertex_normals(vertices, faces, Nv, Nf, out, S, E, info, wsp, None))
+    def debug_normals(vertices=FAKE, faces=FAKE, Nv=5, Nf=3, out=FAKE, S=FAKE, E=FAKE, info=FAKE, wsp=FAKE):
+        return refused(built_lib, built_lib.lrf_debug_mesh_vertex_normals(vertices, faces, Nv, Nf, out, S, E, info, wsp, None))
 
-    def smooth(vertices_out=fake + 0x1000, info=fake, wsp=fake, lo=(0.0, 0.0, 0.0), **over):
-        a = N.LrfMeshSmooth()
-        a.vertices, a.faces, a.Nv, a.Nf, a.lam, a.mu, a.s, a.iterations, a.pin_boundary = fake, fake, 5, 3, 0.5, -0.53, 30, 2, 1
-        for k in range(3):
-            a.lo[k] = lo[k]
-        for k, v in over.items():
-            setattr(a, k, v)
-        return err(built_lib.lrf_mesh_smooth(C.byref(a), vertices_out, info, wsp, None))
+    def smooth(vertices_out=FAKE + 0x1000, info=FAKE, wsp=FAKE, **over):
+        a = filled(N.LrfMeshSmooth, dict(vertices=FAKE, faces=FAKE, Nv=5, Nf=3, lam=0.5, mu=-0.53, s=30, iterations=2, pin_boundary=1,
+                                         lo=(0.0, 0.0, 0.0)), **over)
+        return refused(built_lib, built_lib.lrf_mesh_smooth(C.byref(a), vertices_out, info, wsp, None))
     for fn in (incidence, topology, normals, debug_normals, smooth):
         for bad in sizes:
             assert "need 1 <= Nv < 2^31, 0 <= Nf and 3 Nf < 2^31" in fn(**bad), (fn.__name__, bad)
         for bad in (dict(faces=None), dict(info=None), dict(wsp=None)):
             assert fn(**bad).endswith(": null argument"), (fn.__name__, bad)
-        assert "4-byte aligned" in fn(faces=fake + 2) and "8-byte aligned" in fn(info=fake + 4) and "8-byte aligned" in fn(wsp=fake + 4)
+        assert "4-byte aligned" in fn(faces=FAKE + 2) and "8-byte aligned" in fn(info=FAKE + 4) and "8-byte aligned" in fn(wsp=FAKE + 4)
     assert topology(boundary=None).endswith(": null argument")
     for fn in (normals, debug_normals):
         assert fn(vertices=None).endswith(": null argument") and fn(out=None).endswith(": null argument")
-        assert "4-byte aligned" in fn(vertices=fake + 2) and "4-byte aligned" in fn(out=fake + 1)
+        assert "4-byte aligned" in fn(vertices=FAKE + 2) and "4-byte aligned" in fn(out=FAKE + 1)
     assert debug_normals(S=None).endswith(": null argument") and debug_normals(E=None).endswith(": null argument")
-    assert "8-byte aligned" in debug_normals(S=fake + 4) and "4-byte aligned" in debug_normals(E=fake + 2)
+    assert "8-byte aligned" in debug_normals(S=FAKE + 4) and "4-byte aligned" in debug_normals(E=FAKE + 2)
     assert smooth(vertices=None).endswith(": null argument") and smooth(vertices_out=None).endswith(": null argument")
-    assert "4-byte aligned" in smooth(vertices=fake + 2) and "4-byte aligned" in smooth(vertices_out=fake + 0x1002)
-    assert "must not be the input" in smooth(vertices_out=fake)
+    assert "4-byte aligned" in smooth(vertices=FAKE + 2) and "4-byte aligned" in smooth(vertices_out=FAKE + 0x1002)
+    assert "must not be the input" in smooth(vertices_out=FAKE)
     for bad in (-1, 1001):
         assert "iterations" in smooth(iterations=bad)
     for bad in (0.0, -0.5, 1.5, math.nan, math.inf):
@@ -262,14 +251,14 @@ def test_smooth_symbols_declared_exported_bound_and_checked(built_lib):
         assert "lo must hold 3 finite values" in smooth(lo=bad)
     for bad in (257, -257, 1 << 30):
         assert "s must lie" in smooth(s=bad)
-    assert built_lib.lrf_mesh_smooth(None, fake, fake, fake, None) != 0
+    assert built_lib.lrf_mesh_smooth(None, FAKE, FAKE, FAKE, None) != 0
 
-    def bounds(vertices=fake, Nv=5, out=fake):
-        return err(built_lib.lrf_mesh_smooth_bounds(vertices, Nv, out, None))
+    def bounds(vertices=FAKE, Nv=5, out=FAKE):
+        return refused(built_lib, built_lib.lrf_mesh_smooth_bounds(vertices, Nv, out, None))
     for bad in (0, -4, 1 << 31):
         assert "1 <= Nv < 2^31" in bounds(Nv=bad)
     assert bounds(vertices=None).endswith(": null argument") and bounds(out=None).endswith(": null argument")
-    assert "4-byte aligned" in bounds(vertices=fake + 2) and "4-byte aligned" in bounds(out=fake + 1)
+    assert "4-byte aligned" in bounds(vertices=FAKE + 2) and "4-byte aligned" in bounds(out=FAKE + 1)
 
 
 def test_workspace_bytes_refuse_and_follow_the_formula(built_lib):
@@ -289,13 +278,5 @@ def test_workspace_bytes_refuse_and_follow_the_formula(built_lib):
 
 def test_smooth_kernels_use_no_scratch():
     """The kernels of lrf_mesh_smooth.inl as __graft_entry__.build() compiles them: the metadata only."""
-    import re
-    from test_isa_checks import BUILD_FLAGS, _device_asm
-    asm = _device_asm(BUILD_FLAGS)
-    for name in KERNELS:
-        hits = re.findall(r"\.amdhsa_kernel (_Z\w*?\d+" + name + r"E\w*)", asm)
-        assert len(hits) == 1, (name, hits)
-        meta = asm[asm.index(".amdhsa_kernel " + hits[0]):]
-        meta = meta[:meta.index(".end_amdhsa_kernel")]
-        priv = re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", meta)
-        assert priv and int(priv[1]) == 0, (name, priv and priv[1])
+    from isa_util import assert_no_scratch, device_asm
+    assert_no_scratch(device_asm(), KERNELS, match="exact")

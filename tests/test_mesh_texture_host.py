@@ -11,13 +11,12 @@ cap is 2 %).  The round trip (bar G (s + 1) + 2 levels with G = 10.22 levels per
 these are its figures too."""
 import ctypes as C
 import math
-import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
+from abi_util import FAKE, declared_exported_bound, filled, refused
 from localrf_amd import NativeError
 from localrf_amd.mesh_texture import TextureBaker, atlas_layout, face_uv, sample_texture, scene_texture, write_obj
 from mesh_raster_cases import SPHERE_C, SPHERE_R, rasterize_host
@@ -25,7 +24,6 @@ from mesh_texture_cases import (CASE_NAMES, G_LEVELS, ROUND_TRIP, WALL_CAMERAS, 
                                 layout_host, resolve_host, texels_host, uv_host)
 from mesh_util import cpu_mesh, forbid_native, forbid_render
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMBOLS = ("lrf_mesh_texture_state_bytes", "lrf_mesh_texture_bake", "lrf_mesh_texture_resolve")
 KERNELS = ("k_tx_bake", "k_tx_resolve")
 FP64_LEVELS, FP64_EXCLUDED = 1, 0.02
@@ -342,33 +340,21 @@ def test_scene_texture_checks_before_it_renders(monkeypatch):
 
 def test_texture_symbols_declared_exported_bound_and_checked(built_lib):
     from localrf_amd import _native as N
-    header = open(os.path.join(ROOT, "include", "lrf.h")).read()
-    for name in SYMBOLS:
-        assert name in N.SYMBOLS and f"{name}(" in header
-        getattr(built_lib, name)
+    header = declared_exported_bound(built_lib, SYMBOLS)
     assert "typedef struct LrfMeshTexture" in header and C.sizeof(N.LrfMeshTexture) == 8 * 8 + 2 * 8 + 7 * 4 + 2 * 4 + 4
     assert built_lib.lrf_abi_version() == 7
     assert "mesh_texture" in __import__("localrf_amd").__all__
-    fake = 0x10000
     fill = (C.c_uint8 * 3)(1, 2, 3)
 
-    def err(rc):
-        assert rc != 0                                                      # every call here must be refused: nothing may launch
-        return built_lib.lrf_last_error().decode()
-
     def args(**over):
-        a = N.LrfMeshTexture()
-        a.vertices, a.faces, a.frames, a.mesh_depth, a.cam2world, a.focal, a.center = (fake,) * 7
-        a.Nv, a.Nf, a.patch, a.cols, a.blend, a.two_sided, a.V, a.H, a.W, a.vis_tol, a.min_cos = 5, 3, 8, 2, 0, 0, 2, 6, 8, 0.02, 0.2
-        for k, v in over.items():
-            setattr(a, k, v)
-        return a
+        return filled(N.LrfMeshTexture, dict(vertices=FAKE, faces=FAKE, frames=FAKE, mesh_depth=FAKE, cam2world=FAKE, focal=FAKE, center=FAKE,
+                                             Nv=5, Nf=3, patch=8, cols=2, blend=0, two_sided=0, V=2, H=6, W=8, vis_tol=0.02, min_cos=0.2), **over)
 
-    def bake(state=fake, **over):
-        return err(built_lib.lrf_mesh_texture_bake(C.byref(args(**over)), state, None))
+    def bake(state=FAKE, **over):
+        return refused(built_lib, built_lib.lrf_mesh_texture_bake(C.byref(args(**over)), state, None))
 
-    def resolve(state=fake, fill_=fill, atlas=fake, mask=fake, info=fake, **over):
-        return err(built_lib.lrf_mesh_texture_resolve(C.byref(args(**over)), state, fill_, atlas, mask, info, None))
+    def resolve(state=FAKE, fill_=fill, atlas=FAKE, mask=FAKE, info=FAKE, **over):
+        return refused(built_lib, built_lib.lrf_mesh_texture_resolve(C.byref(args(**over)), state, fill_, atlas, mask, info, None))
     for call, who in ((bake, "lrf_mesh_texture_bake"), (resolve, "lrf_mesh_texture_resolve")):
         for bad in (dict(patch=3), dict(patch=65), dict(Nf=-1), dict(Nv=-1), dict(Nv=1 << 31), dict(Nv=0), dict(Nf=1 << 22, patch=64),
                     dict(Nf=1 << 31)):
@@ -378,9 +364,9 @@ def test_texture_symbols_declared_exported_bound_and_checked(built_lib):
             assert call(**bad).endswith(": null argument"), bad
         for bad in (-1, 2):
             assert "blend" in call(blend=bad)
-        for bad in (dict(vertices=fake + 2), dict(faces=fake + 1)):
+        for bad in (dict(vertices=FAKE + 2), dict(faces=FAKE + 1)):
             assert "4-byte aligned" in call(**bad), bad
-        assert "16-byte aligned" in call(state=fake + 8)
+        assert "16-byte aligned" in call(state=FAKE + 8)
     for bad in (dict(V=0), dict(H=0), dict(W=-1), dict(V=1 << 15, H=1 << 8, W=1 << 8)):
         assert "need V, H, W >= 1" in bake(**bad), bad
     for bad in (dict(frames=None), dict(mesh_depth=None), dict(cam2world=None), dict(focal=None), dict(center=None)):
@@ -391,12 +377,12 @@ def test_texture_symbols_declared_exported_bound_and_checked(built_lib):
         assert "vis_tol" in bake(vis_tol=bad)
     for bad in (-0.1, 1.5, math.nan):
         assert "min_cos" in bake(min_cos=bad)
-    for bad in (dict(mesh_depth=fake + 2), dict(cam2world=fake + 1), dict(focal=fake + 2)):
+    for bad in (dict(mesh_depth=FAKE + 2), dict(cam2world=FAKE + 1), dict(focal=FAKE + 2)):
         assert "4-byte aligned" in bake(**bad), bad
     for bad in (dict(fill_=None), dict(atlas=None), dict(mask=None), dict(info=None)):
         assert resolve(**bad).endswith(": null argument"), bad
-    assert "8-byte aligned" in resolve(info=fake + 4)
-    assert built_lib.lrf_mesh_texture_bake(None, fake, None) != 0 and built_lib.lrf_mesh_texture_resolve(None, fake, fill, fake, fake, fake, None) != 0
+    assert "8-byte aligned" in resolve(info=FAKE + 4)
+    assert built_lib.lrf_mesh_texture_bake(None, FAKE, None) != 0 and built_lib.lrf_mesh_texture_resolve(None, FAKE, fill, FAKE, FAKE, FAKE, None) != 0
     assert built_lib.lrf_mesh_texture_bake(C.byref(args(Nf=0, Nv=0, vertices=None, faces=None)), None, None) == 0   # nothing to launch
 
 
@@ -413,12 +399,5 @@ def test_state_bytes_refuse_and_follow_the_formula(built_lib):
 
 def test_texture_kernels_use_no_scratch():
     """The kernels of lrf_mesh_texture.inl as __graft_entry__.build() compiles them: the metadata only."""
-    from test_isa_checks import BUILD_FLAGS, _device_asm
-    asm = _device_asm(BUILD_FLAGS)
-    for name in KERNELS:
-        hits = re.findall(r"\.amdhsa_kernel (_Z\w*?\d+" + name + r"E\w*)", asm)
-        assert len(hits) == 1, (name, hits)
-        meta = asm[asm.index(".amdhsa_kernel " + hits[0]):]
-        meta = meta[:meta.index(".end_amdhsa_kernel")]
-        priv = re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", meta)
-        assert priv and int(priv[1]) == 0, (name, priv and priv[1])
+    from isa_util import assert_no_scratch, device_asm
+    assert_no_scratch(device_asm(), KERNELS, match="exact")

@@ -1,17 +1,16 @@
 """Normals without a GPU: the fp64 oracle against central differences, the exported symbols and their refusals, PLY files
 with normals, the byte encoding's restatement, and the argument checks that come before any launch."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 import torch
 
+from abi_util import FAKE, declared_exported_bound, refused
 from localrf_amd import NativeError, normals, pointcloud
 from normals_cases import (GRID, encode_normals_host, field, field_dict, flag_x, grad_x, density_of_x, sample_positions,
                            test_rays)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_fp64_oracle_agrees_with_central_differences():
@@ -39,34 +38,28 @@ def test_fp64_oracle_agrees_with_central_differences():
 
 def test_normals_symbols_declared_exported_and_checked(built_lib):
     from localrf_amd import _native as N
-    header = open(os.path.join(ROOT, "include", "lrf.h")).read()
-    for name in ("lrf_density_gradient", "lrf_normals_workspace_bytes", "lrf_render_normals"):
-        assert name in N.SYMBOLS and f"{name}(" in header
-        getattr(built_lib, name)
+    declared_exported_bound(built_lib, ("lrf_density_gradient", "lrf_normals_workspace_bytes", "lrf_render_normals"))
     assert built_lib.lrf_abi_version() == 7
     ws = built_lib.lrf_normals_workspace_bytes
     assert ws(0, 64) == 0 and ws(16, 1) == 0 and ws(16, 4097) == 0
     for R, S in ((1, 2), (200, 88), (4096, 512)):
         assert ws(R, S) >= built_lib.lrf_workspace_bytes(R, S) + 4 * R * S + 20 * R
         assert ws(R, S) <= built_lib.lrf_workspace_bytes(R, S) + 4 * R * S + 20 * R + 5 * 256
-    fake = C.c_void_p(0x10000)
+    fake = C.c_void_p(FAKE)
     fld = N.LrfField()
-    fld.cache = 0x10000
+    fld.cache = FAKE
     fld.grid[:] = list(GRID)
 
-    def refused(fn, *args):
-        assert fn(*args) != 0                                            # every call here must be refused: nothing may launch
-        return built_lib.lrf_last_error().decode()
     dg = built_lib.lrf_density_gradient
-    assert refused(dg, None, fake, 4, fake, None, None) == "lrf_density_gradient: null argument"
-    assert refused(dg, C.byref(fld), None, 4, fake, None, None) == "lrf_density_gradient: null argument"
-    assert refused(dg, C.byref(fld), fake, 4, None, None, None) == "lrf_density_gradient: null argument"
-    assert "0 <= P" in refused(dg, C.byref(fld), fake, -1, fake, None, None)
-    assert "4-byte aligned" in refused(dg, C.byref(fld), fake, 4, C.c_void_p(0x10002), None, None)
+    assert refused(built_lib, dg(None, fake, 4, fake, None, None)) == "lrf_density_gradient: null argument"
+    assert refused(built_lib, dg(C.byref(fld), None, 4, fake, None, None)) == "lrf_density_gradient: null argument"
+    assert refused(built_lib, dg(C.byref(fld), fake, 4, None, None, None)) == "lrf_density_gradient: null argument"
+    assert "0 <= P" in refused(built_lib, dg(C.byref(fld), fake, -1, fake, None, None))
+    assert "4-byte aligned" in refused(built_lib, dg(C.byref(fld), fake, 4, C.c_void_p(0x10002), None, None))
     assert dg(C.byref(fld), fake, 0, fake, None, None) == 0              # no point: no launch
 
     def rn(f=C.byref(fld), rays=fake, z=fake, R=8, S=64, flags=1, bw=None, per_view=1, accumulate=0, out=fake, acc=None, wsp=fake):
-        return refused(built_lib.lrf_render_normals, f, rays, z, R, S, flags, 0.0, bw, per_view, accumulate, out, acc, wsp, None)
+        return refused(built_lib, built_lib.lrf_render_normals(f, rays, z, R, S, flags, 0.0, bw, per_view, accumulate, out, acc, wsp, None))
     for bad in (dict(f=None), dict(rays=None), dict(z=None), dict(out=None), dict(wsp=None)):
         assert rn(**bad) == "lrf_render_normals: null argument", bad
     for bad in (dict(R=0), dict(R=-3), dict(S=1), dict(S=4097)):

@@ -2,17 +2,16 @@
 images (tests/golden/novel_views.npz) and its byte rules, the start / frame-index mapping of renderer.render(test=False)
 on a CPU copy of the golden scene, argument refusals before any device work, and the new C ABI symbols."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 import torch
 
+from abi_util import FAKE, declared_exported_bound, refused
 from localrf_amd import NativeError, novel_views
 from localrf_amd.pose_plan import PosePlan
 from novel_views_cases import depth_idx_frames, depth_idx_host, edge_depths, edge_rgbs, golden, rgb8_host, scene
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_depth_index_restatement_equals_the_reference_images():
@@ -199,42 +198,29 @@ def test_refusals_before_any_device_work():
 
 def test_encode_symbols_declared_exported_and_checked(built_lib):
     from localrf_amd import _native as N
-    header = open(os.path.join(ROOT, "include", "lrf.h")).read()
-    for name in ("lrf_encode_frames", "lrf_encode_frames_workspace_bytes"):
-        assert name in N.SYMBOLS and f"{name}(" in header
-        getattr(built_lib, name)
+    declared_exported_bound(built_lib, ("lrf_encode_frames", "lrf_encode_frames_workspace_bytes"))
     assert built_lib.lrf_abi_version() == 7
     assert built_lib.lrf_encode_frames_workspace_bytes(3) == 3 * 64 * 8
     assert built_lib.lrf_encode_frames_workspace_bytes(0) == 0
-    fake = C.c_void_p(0x10000)
+    fake = C.c_void_p(FAKE)
     fr = (C.c_float * 3)(0.0, 5.0, 5.0)
 
     def enc(rgb=fake, depth=fake, V=2, H=4, W=5, lut=fake, fixed=fr, rgb8=fake, depth8=fake, idx=None, rng=None, ws=None):
-        rc = built_lib.lrf_encode_frames(rgb, depth, V, H, W, lut, fixed, rgb8, depth8, idx, rng, ws, None)
-        return rc, built_lib.lrf_last_error().decode()
-    rc, msg = enc(V=0)
-    assert rc != 0 and msg == "lrf_encode_frames: need V >= 1, H, W > 0 and 3 V H W < 2^31"
-    assert "need V >= 1" in enc(V=0)[1] and "need V >= 1" in enc(H=0)[1] and "need V >= 1" in enc(V=1 << 20, H=1 << 10)[1]
-    assert enc(depth=None)[1] == "lrf_encode_frames: null argument"
-    assert enc(lut=None)[1] == "lrf_encode_frames: null argument"
-    assert enc(rgb8=None)[1] == "lrf_encode_frames: rgb and rgb8 go together"
-    assert enc(fixed=None)[1] == "lrf_encode_frames: the automatic range needs a workspace"
-    assert "16-byte aligned" in enc(rgb=C.c_void_p(0x10004))[1]
-    assert "4-byte aligned" in enc(idx=C.c_void_p(0x10002))[1]
+        return refused(built_lib, built_lib.lrf_encode_frames(rgb, depth, V, H, W, lut, fixed, rgb8, depth8, idx, rng, ws, None))
+    assert enc(V=0) == "lrf_encode_frames: need V >= 1, H, W > 0 and 3 V H W < 2^31"
+    assert "need V >= 1" in enc(V=0) and "need V >= 1" in enc(H=0) and "need V >= 1" in enc(V=1 << 20, H=1 << 10)
+    assert enc(depth=None) == "lrf_encode_frames: null argument"
+    assert enc(lut=None) == "lrf_encode_frames: null argument"
+    assert enc(rgb8=None) == "lrf_encode_frames: rgb and rgb8 go together"
+    assert enc(fixed=None) == "lrf_encode_frames: the automatic range needs a workspace"
+    assert "16-byte aligned" in enc(rgb=C.c_void_p(0x10004))
+    assert "4-byte aligned" in enc(idx=C.c_void_p(0x10002))
 
 
 def test_encode_kernels_use_no_scratch():
     """k_encode (both range modes) and k_encode_range, as __graft_entry__.build() compiles them: no scratch, no spills, and
     the division of the index image is a full-precision one (no v_rcp_f32 without the div_fixup that follows it)."""
-    import re
-    from test_isa_checks import BUILD_FLAGS, _body, _device_asm
-    asm = _device_asm(BUILD_FLAGS)
-    names = [n for pat in (r"k_encodeILb0E", r"k_encodeILb1E", r"k_encode_range") for n, _ in _body(asm, pat)]
-    assert len(names) == 3
-    for name in names:
-        meta = asm[asm.index(".amdhsa_kernel " + name):]
-        meta = meta[:meta.index(".end_amdhsa_kernel")]
-        priv = re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", meta)
-        assert priv and int(priv[1]) == 0, (name, priv and priv[1])
-    for name, body in _body(asm, r"k_encodeILb[01]E"):
+    from isa_util import assert_no_scratch, device_asm, find
+    assert_no_scratch(device_asm(), (r"k_encodeILb0E", r"k_encodeILb1E", r"k_encode_range"), match="search", total=3)
+    for name, body in find(device_asm(), r"k_encodeILb[01]E"):
         assert "v_div_fixup_f32" in body and "scratch_" not in body, name

@@ -3,18 +3,17 @@ points, world points and reprojected pixels (tests/golden/points.npz), the condi
 argument refusals before any device work (Python and C ABI), the PLY writer, and the new symbols."""
 import ctypes as C
 import math
-import os
 
 import numpy as np
 import pytest
 import torch
 
+from abi_util import FAKE, declared_exported_bound, filled, refused
 from localrf_amd import NativeError, pointcloud
 from points_cases import (OFFSETS4, fuse_host, keep_mask, pixel_dirs, random_case, reproject, trajectory_case,
                           trajectory_shares, world_points)
 from util import load_golden
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_restatement_against_the_reference_points_and_pixels():
@@ -185,10 +184,7 @@ def test_write_ply_round_trip(tmp_path):
 
 def test_points_symbols_declared_exported_and_checked(built_lib):
     from localrf_amd import _native as N
-    header = open(os.path.join(ROOT, "include", "lrf.h")).read()
-    for name in ("lrf_points_fuse", "lrf_points_workspace_bytes"):
-        assert name in N.SYMBOLS and f"{name}(" in header
-        getattr(built_lib, name)
+    header = declared_exported_bound(built_lib, ("lrf_points_fuse", "lrf_points_workspace_bytes"))
     assert "#define LRF_POINTS_MAX_NEIGH 8" in header and N.LRF_POINTS_MAX_NEIGH == 8
     assert built_lib.lrf_abi_version() == 7
     ws = built_lib.lrf_points_workspace_bytes
@@ -196,23 +192,12 @@ def test_points_symbols_declared_exported_and_checked(built_lib):
     assert ws(1, 1, 1, 1) == 256                                         # one workgroup: 16 keep words + one count
     assert ws(64, 360, 640, 1) >= 64 * 360 * 640 // 8
     assert ws(64, 360, 640, 2) < ws(64, 360, 640, 1) // 3
-    fake = C.c_void_p(0x10000)
+    fake = C.c_void_p(FAKE)
 
     def fuse(capacity=10, xyz=fake, rgb8_out=fake, src=fake, count=fake, wsp=fake, **over):
-        a = N.LrfPointsFuse()
-        a.depth, a.rgb8, a.cam2world, a.focal, a.center = 0x10000, 0x10000, 0x10000, 0x10000, 0x10000
-        a.V, a.H, a.W, a.fov360, a.stride = 2, 4, 5, 0, 1
-        a.d_min, a.d_max, a.n_neigh, a.rel_tol, a.min_consistent = 0.0, math.inf, 2, 0.02, 1
-        a.neigh[0], a.neigh[1] = -1, 1
-        for k, v in over.items():
-            if k == "neigh":
-                for i, o in enumerate(v):
-                    a.neigh[i] = o
-            else:
-                setattr(a, k, v)
-        rc = built_lib.lrf_points_fuse(C.byref(a), capacity, xyz, rgb8_out, src, count, wsp, None)
-        assert rc != 0                                                   # every call here must be refused: nothing may launch
-        return built_lib.lrf_last_error().decode()
+        a = filled(N.LrfPointsFuse, dict(depth=FAKE, rgb8=FAKE, cam2world=FAKE, focal=FAKE, center=FAKE, V=2, H=4, W=5, fov360=0, stride=1,
+                                         d_min=0.0, d_max=math.inf, n_neigh=2, rel_tol=0.02, min_consistent=1, neigh=(-1, 1)), **over)
+        return refused(built_lib, built_lib.lrf_points_fuse(C.byref(a), capacity, xyz, rgb8_out, src, count, wsp, None))
     assert fuse(V=0) == "lrf_points_fuse: need V, H, W, stride >= 1 and V H W < 2^31"
     for bad in (dict(H=0), dict(W=-1), dict(stride=0), dict(V=1 << 20, H=1 << 10)):
         assert "need V, H, W, stride >= 1" in fuse(**bad)
@@ -230,23 +215,13 @@ def test_points_symbols_declared_exported_and_checked(built_lib):
     assert "min_consistent" in fuse(min_consistent=-1)
     assert "4-byte aligned" in fuse(xyz=C.c_void_p(0x10002)) and "4-byte aligned" in fuse(depth=0x10001)
     assert "8-byte aligned" in fuse(count=C.c_void_p(0x10004)) and "8-byte aligned" in fuse(wsp=C.c_void_p(0x10004))
-    rc = built_lib.lrf_points_fuse(None, 0, fake, fake, fake, fake, fake, None)
-    assert rc != 0 and built_lib.lrf_last_error().decode() == "lrf_points_fuse: null argument"
+    assert refused(built_lib, built_lib.lrf_points_fuse(None, 0, fake, fake, fake, fake, fake, None)) == "lrf_points_fuse: null argument"
 
 
 def test_points_kernels_use_no_scratch():
     """k_points_mark, k_points_scan and k_points_write as __graft_entry__.build() compiles them: no scratch, no spills, the
     divisions of the pixel mapping are full-precision ones, and the kernels multiply and add separately (contraction off)."""
-    import re
-    from test_isa_checks import BUILD_FLAGS, _body, _device_asm
-    asm = _device_asm(BUILD_FLAGS)
-    found = [(n, b) for pat in (r"k_points_mark", r"k_points_scan", r"k_points_write") for n, b in _body(asm, pat)]
-    assert len(found) == 3
-    for name, body in found:
-        meta = asm[asm.index(".amdhsa_kernel " + name):]
-        meta = meta[:meta.index(".end_amdhsa_kernel")]
-        priv = re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", meta)
-        assert priv and int(priv[1]) == 0, (name, priv and priv[1])
-        assert "scratch_" not in body, name
+    from isa_util import assert_no_scratch, device_asm
+    found = assert_no_scratch(device_asm(), (r"k_points_mark", r"k_points_scan", r"k_points_write"), match="search", total=3, body_too=True)
     mark = dict(found)[[n for n, _ in found if "mark" in n][0]]
     assert "v_div_fixup_f32" in mark and "v_rndne_f32" in mark

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+from abi_util import FAKE, declared_exported_bound, refused
 import quantile_cases as Q
 from localrf_amd import NativeError, depth_quantiles, mesh, pointcloud
 
@@ -81,32 +82,27 @@ def test_flagged_share_of_the_field_cases(case):
 
 def test_quantile_symbols_declared_exported_and_checked(built_lib):
     from localrf_amd import _native as N
-    header = open(os.path.join(ROOT, "include", "lrf.h")).read()
+    header = declared_exported_bound(built_lib, ("lrf_quantile_workspace_bytes", "lrf_render_depth_quantiles"))
     debug = open(os.path.join(ROOT, "include", "lrf_debug.h")).read()
-    for name, text in (("lrf_quantile_workspace_bytes", header), ("lrf_render_depth_quantiles", header),
-                       ("lrf_depth_quantiles_from_weights", debug)):
-        assert name in N.SYMBOLS and f"{name}(" in text
-        getattr(built_lib, name)
+    assert "lrf_depth_quantiles_from_weights" in N.SYMBOLS and "lrf_depth_quantiles_from_weights(" in debug
+    getattr(built_lib, "lrf_depth_quantiles_from_weights")
     assert built_lib.lrf_abi_version() == 7 and "#define LRF_ABI_VERSION 7" in header
     ws = built_lib.lrf_quantile_workspace_bytes
     assert ws(0, 64) == 0 and ws(16, 1) == 0 and ws(16, 4097) == 0
     for R, S in ((1, 2), (200, 88), (4096, 512)):
         assert ws(R, S) >= built_lib.lrf_workspace_bytes(R, S) + 4 * R * S + 20 * R
         assert ws(R, S) <= built_lib.lrf_workspace_bytes(R, S) + 4 * R * S + 20 * R + 5 * 256
-    fake = C.c_void_p(0x10000)
+    fake = C.c_void_p(FAKE)
     fld = N.LrfField()
-    fld.cache = 0x10000
+    fld.cache = FAKE
     fld.grid[:] = [20, 24, 28]
     half = (C.c_float * 4)(0.5, 0.25, 0.75, 1.0)
 
-    def refused(fn, *args):
-        assert fn(*args) != 0                                            # every call here must be refused: nothing may launch
-        return built_lib.lrf_last_error().decode()
 
     def dq(f=C.byref(fld), rays=fake, z=fake, R=8, S=64, flags=1, q=half, K=1, bw=None, per_view=1, accumulate=0, depth=fake,
            wsum=None, index=None, acc=None, wsp=fake):
-        return refused(built_lib.lrf_render_depth_quantiles, f, rays, z, R, S, flags, 0.0, q, K, bw, per_view, accumulate, depth,
-                       wsum, index, acc, wsp, None)
+        return refused(built_lib, built_lib.lrf_render_depth_quantiles(f, rays, z, R, S, flags, 0.0, q, K, bw, per_view, accumulate, depth,
+                                                                         wsum, index, acc, wsp, None))
     for bad in (dict(f=None), dict(rays=None), dict(z=None), dict(q=None), dict(depth=None), dict(wsp=None)):
         assert dq(**bad) == "lrf_render_depth_quantiles: null argument", bad
     for bad in (dict(R=0), dict(R=-3), dict(S=1), dict(S=4097)):
@@ -127,7 +123,7 @@ def test_quantile_symbols_declared_exported_and_checked(built_lib):
     assert "256-byte aligned" in dq(wsp=C.c_void_p(0x10010))
 
     def fw(w=fake, z=fake, rays=fake, R=8, S=64, q=half, K=1, depth=fake, index=None):
-        return refused(built_lib.lrf_depth_quantiles_from_weights, w, z, rays, R, S, q, K, depth, index, None)
+        return refused(built_lib, built_lib.lrf_depth_quantiles_from_weights(w, z, rays, R, S, q, K, depth, index, None))
     for bad in (dict(w=None), dict(z=None), dict(rays=None), dict(q=None), dict(depth=None)):
         assert fw(**bad) == "lrf_depth_quantiles_from_weights: null argument", bad
     assert "2 <= S <= 4096" in fw(S=1) and "2 <= S <= 4096" in fw(R=0) and "1 <= K <= 4" in fw(K=5)

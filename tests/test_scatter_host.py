@@ -15,6 +15,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
+from abi_util import FAKE, refused  # noqa: E402
 import scatter_cases as sc                       # noqa: E402
 from oracle import vm_render_torch as ot         # noqa: E402
 
@@ -314,13 +315,13 @@ def test_deterministic_refusal_names_its_first_refused_length(built_lib):
     """LRF_FLAG_DETERMINISTIC accepts every line the reference reaches (640 cells) and refuses 641, with the text that says so.
     Fake device pointers: the refusal comes before any HIP call."""
     from localrf_amd import _native as N
-    fake = C.c_void_p(0x10000)
+    fake = C.c_void_p(FAKE)
 
     def bwd(n):
         f = N.LrfField(cache=fake, feature_c=128)
         f.grid[:] = [n, 17, 19]
         return built_lib.lrf_render_bwd(C.byref(f), C.byref(N.LrfParams()), fake, fake, 64, 64, N.LRF_FLAG_DETERMINISTIC, fake, fake,
                                         C.byref(N.LrfGrads()), fake, fake, None)
-    assert bwd(641) != 0 and "DETERMINISTIC covers lines up to 640 cells" in built_lib.lrf_last_error().decode()
-    assert bwd(2000) != 0 and "line too long" in built_lib.lrf_last_error().decode()
+    assert "DETERMINISTIC covers lines up to 640 cells" in refused(built_lib, bwd(641))
+    assert "line too long" in refused(built_lib, bwd(2000))
     # (640 itself is accepted: test_engine_choice_elsewhere, and on the device tests/test_gpu_scatter.py runs it)

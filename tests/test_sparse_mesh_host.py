@@ -3,19 +3,18 @@
 and a missing block only leaves a hole --, argument refusals before any device work (Python and C ABI), and the new symbols."""
 import ctypes as C
 import math
-import os
 
 import numpy as np
 import pytest
 import torch
 
+from abi_util import FAKE, declared_exported_bound, filled, refused
 from localrf_amd import NativeError, mesh
 from mesh_cases import (H_ANALYTIC, closed_manifold_euler, extract_host, integrate_host, new_volume, sphere_field)
 from mesh_util import SparseStub, forbid_native, forbid_render
 from sparse_mesh_cases import (assign_host, dims_of, extract_blocks_host, face_keys, fuse_host, integrate_blocks_host, lattice_for,
                                new_sparse, random_frames, spread_lattice, to_dense_host, touch_host, trajectory)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("lrf_tsdf_blocks_touch", "lrf_tsdf_blocks_assign_workspace_bytes", "lrf_tsdf_blocks_assign", "lrf_tsdf_blocks_integrate",
        "lrf_mesh_extract_blocks_workspace_bytes", "lrf_mesh_extract_blocks")
 
@@ -198,10 +197,7 @@ def test_scene_mesh_sparse_refusals_on_a_cpu_scene(monkeypatch):
 
 def test_block_symbols_declared_exported_and_checked(built_lib):
     from localrf_amd import _native as N
-    header = open(os.path.join(ROOT, "include", "lrf.h")).read()
-    for name in NEW:
-        assert name in N.SYMBOLS and f"{name}(" in header
-        getattr(built_lib, name)
+    header = declared_exported_bound(built_lib, NEW)
     assert "typedef struct LrfTsdfBlocks" in header
     assert C.sizeof(N.LrfTsdfBlocks) == 6 * 8 + 4 * 4 + 5 * 4 + 4        # padded to 8
     assert C.sizeof(N.LrfTsdfVolume) == 3 * 8 + 3 * 4 + 5 * 4 and C.sizeof(N.LrfMeshExtract) == 3 * 8 + 3 * 4 + 6 * 4 + 4
@@ -211,34 +207,25 @@ def test_block_symbols_declared_exported_and_checked(built_lib):
     assert ws(1, 1, 1) == 256 and ws(256, 256, 256) == 4 * 256 ** 3 // 256
     wm = built_lib.lrf_mesh_extract_blocks_workspace_bytes
     assert wm(-1) == 0 and wm(1 << 22) == 0 and wm(0) == 256 and wm(3) >= 3 * 512 * 4 + 2 * 6 * 4
-    fake = 0x10000
     grid = "need Bx, By, Bz >= 1, 8 B < 2^31 per axis and Bx By Bz < 2^31"
 
     def volume(over):
-        a = N.LrfTsdfBlocks()
-        a.marks, a.table, a.coords, a.tsdf, a.weight, a.rgb = (fake,) * 6
-        a.Bx, a.By, a.Bz, a.n_blocks, a.voxel, a.trunc = 3, 4, 5, 2, 0.1, 0.3
-        for k, v in over.items():
-            setattr(a, k, v)
-        return a
+        return filled(N.LrfTsdfBlocks, dict(marks=FAKE, table=FAKE, coords=FAKE, tsdf=FAKE, weight=FAKE, rgb=FAKE, Bx=3, By=4, Bz=5, n_blocks=2,
+                                            voxel=0.1, trunc=0.3), **over)
 
-    def refused(rc):
-        assert rc != 0                                                   # every call here must be refused: nothing may launch
-        return built_lib.lrf_last_error().decode()
+    def touch(depth=FAKE, c2w=FAKE, focal=FAKE, center=FAKE, V=2, H=4, W=5, d_min=0.0, d_max=math.inf, **over):
+        return refused(built_lib, built_lib.lrf_tsdf_blocks_touch(C.byref(volume(over)), depth, c2w, focal, center, V, H, W, d_min, d_max, None))
 
-    def touch(depth=fake, c2w=fake, focal=fake, center=fake, V=2, H=4, W=5, d_min=0.0, d_max=math.inf, **over):
-        return refused(built_lib.lrf_tsdf_blocks_touch(C.byref(volume(over)), depth, c2w, focal, center, V, H, W, d_min, d_max, None))
+    def integrate(depth=FAKE, rgb8=FAKE, c2w=FAKE, focal=FAKE, center=FAKE, V=2, H=4, W=5, d_min=0.0, d_max=math.inf, **over):
+        return refused(built_lib, built_lib.lrf_tsdf_blocks_integrate(C.byref(volume(over)), depth, rgb8, c2w, focal, center, V, H, W, d_min,
+                                                                        d_max, None))
 
-    def integrate(depth=fake, rgb8=fake, c2w=fake, focal=fake, center=fake, V=2, H=4, W=5, d_min=0.0, d_max=math.inf, **over):
-        return refused(built_lib.lrf_tsdf_blocks_integrate(C.byref(volume(over)), depth, rgb8, c2w, focal, center, V, H, W, d_min,
-                                                           d_max, None))
+    def assign(max_blocks=10, cap=10, count=FAKE, wsp=FAKE, **over):
+        return refused(built_lib, built_lib.lrf_tsdf_blocks_assign(C.byref(volume(over)), max_blocks, cap, count, wsp, None))
 
-    def assign(max_blocks=10, cap=10, count=fake, wsp=fake, **over):
-        return refused(built_lib.lrf_tsdf_blocks_assign(C.byref(volume(over)), max_blocks, cap, count, wsp, None))
-
-    def extract(level=0.0, min_weight=1.0, max_v=10, max_f=10, vertices=fake, rgb8_out=fake, faces=fake, counts=fake, wsp=fake, **over):
-        return refused(built_lib.lrf_mesh_extract_blocks(C.byref(volume(over)), level, min_weight, max_v, max_f, vertices, rgb8_out,
-                                                         faces, counts, wsp, None))
+    def extract(level=0.0, min_weight=1.0, max_v=10, max_f=10, vertices=FAKE, rgb8_out=FAKE, faces=FAKE, counts=FAKE, wsp=FAKE, **over):
+        return refused(built_lib, built_lib.lrf_mesh_extract_blocks(C.byref(volume(over)), level, min_weight, max_v, max_f, vertices, rgb8_out,
+                                                                      faces, counts, wsp, None))
     for fn, name in ((touch, "lrf_tsdf_blocks_touch"), (integrate, "lrf_tsdf_blocks_integrate"), (assign, "lrf_tsdf_blocks_assign"),
                      (extract, "lrf_mesh_extract_blocks")):
         for bad in (dict(Bx=0), dict(By=-1), dict(Bz=0), dict(Bx=2048, By=2048, Bz=512), dict(Bx=1 << 28, By=1, Bz=1)):
@@ -249,52 +236,44 @@ def test_block_symbols_declared_exported_and_checked(built_lib):
             assert fn(**bad) == f"{name}: null argument", bad
         assert "voxel" in fn(voxel=0.0) and "voxel" in fn(voxel=math.nan) and "voxel" in fn(voxel=-1.0)
         assert "trunc" in fn(trunc=0.0) and "trunc" in fn(trunc=-1.0) and "trunc" in fn(trunc=math.nan)
-        assert "4-byte aligned" in fn(table=fake + 2) and "4-byte aligned" in fn(coords=fake + 1)
+        assert "4-byte aligned" in fn(table=FAKE + 2) and "4-byte aligned" in fn(coords=FAKE + 1)
     for fn, name in ((touch, "lrf_tsdf_blocks_touch"), (integrate, "lrf_tsdf_blocks_integrate")):
         for bad in (dict(V=0), dict(H=0), dict(W=-1), dict(V=1 << 20, H=1 << 10, W=2)):
             assert "need V, H, W >= 1 and V H W < 2^31" in fn(**bad)
         for bad in (dict(depth=None), dict(c2w=None), dict(focal=None), dict(center=None)):
             assert fn(**bad) == f"{name}: null argument", bad
         assert "d_min <= d_max" in fn(d_min=2.0, d_max=1.0) and "d_min <= d_max" in fn(d_min=math.nan)
-        assert "4-byte aligned" in fn(depth=fake + 1) and "4-byte aligned" in fn(focal=fake + 2)
+        assert "4-byte aligned" in fn(depth=FAKE + 1) and "4-byte aligned" in fn(focal=FAKE + 2)
     assert touch(marks=None) == "lrf_tsdf_blocks_touch: null argument" and assign(marks=None) == "lrf_tsdf_blocks_assign: null argument"
     for fn, name in ((integrate, "lrf_tsdf_blocks_integrate"), (extract, "lrf_mesh_extract_blocks")):
         for bad in (dict(tsdf=None), dict(weight=None)):
             assert fn(**bad) == f"{name}: null argument", bad
-        assert "4-byte aligned" in fn(tsdf=fake + 2) and "4-byte aligned" in fn(rgb=fake + 1)
+        assert "4-byte aligned" in fn(tsdf=FAKE + 2) and "4-byte aligned" in fn(rgb=FAKE + 1)
     assert "go together" in integrate(rgb=None) and "go together" in integrate(rgb8=None)
     assert "go together" in extract(rgb=None) and "go together" in extract(rgb8_out=None)
     for bad in (dict(count=None), dict(wsp=None)):
         assert assign(**bad) == "lrf_tsdf_blocks_assign: null argument", bad
     assert "max_blocks" in assign(max_blocks=-1) and "max_blocks" in assign(max_blocks=1 << 22)
     assert "[0, 2^31)" in assign(cap=-1) and "[0, 2^31)" in assign(cap=1 << 31)
-    assert "8-byte aligned" in assign(count=fake + 4) and "4-byte aligned" in assign(wsp=fake + 2)
+    assert "8-byte aligned" in assign(count=FAKE + 4) and "4-byte aligned" in assign(wsp=FAKE + 2)
     for bad in (dict(vertices=None), dict(faces=None), dict(counts=None), dict(wsp=None)):
         assert extract(**bad) == "lrf_mesh_extract_blocks: null argument", bad
     assert "level" in extract(level=math.nan) and "min_weight" in extract(min_weight=0.0) and "min_weight" in extract(min_weight=math.nan)
     assert "[0, 2^31)" in extract(max_v=-1) and "[0, 2^31)" in extract(max_f=1 << 31)
-    assert "4-byte aligned" in extract(vertices=fake + 2) and "4-byte aligned" in extract(wsp=fake + 1)
-    assert "8-byte aligned" in extract(counts=fake + 4)
-    assert built_lib.lrf_tsdf_blocks_touch(None, fake, fake, fake, fake, 2, 4, 5, 0.0, 1.0, None) != 0
-    assert built_lib.lrf_tsdf_blocks_assign(None, 1, 1, fake, fake, None) != 0
-    assert built_lib.lrf_tsdf_blocks_integrate(None, fake, fake, fake, fake, fake, 2, 4, 5, 0.0, 1.0, None) != 0
-    assert built_lib.lrf_mesh_extract_blocks(None, 0.0, 1.0, 1, 1, fake, fake, fake, fake, fake, None) != 0
+    assert "4-byte aligned" in extract(vertices=FAKE + 2) and "4-byte aligned" in extract(wsp=FAKE + 1)
+    assert "8-byte aligned" in extract(counts=FAKE + 4)
+    assert built_lib.lrf_tsdf_blocks_touch(None, FAKE, FAKE, FAKE, FAKE, 2, 4, 5, 0.0, 1.0, None) != 0
+    assert built_lib.lrf_tsdf_blocks_assign(None, 1, 1, FAKE, FAKE, None) != 0
+    assert built_lib.lrf_tsdf_blocks_integrate(None, FAKE, FAKE, FAKE, FAKE, FAKE, 2, 4, 5, 0.0, 1.0, None) != 0
+    assert built_lib.lrf_mesh_extract_blocks(None, 0.0, 1.0, 1, 1, FAKE, FAKE, FAKE, FAKE, FAKE, None) != 0
 
 
 def test_block_kernels_use_no_scratch_and_keep_the_pose_in_scalar_registers():
     """The six new kernels as __graft_entry__.build() compiles them: no scratch; the integration's frame loop reads the camera
     matrix with scalar loads."""
     import re
-    from test_isa_checks import BUILD_FLAGS, _body, _device_asm
-    asm = _device_asm(BUILD_FLAGS)
-    found = [(n, b) for pat in (r"k_blocks_touch", r"k_blocks_flag", r"k_blocks_assign", r"k_blocks_fuse", r"k_blocks_count",
-                                r"k_blocks_emit") for n, b in _body(asm, pat)]
-    assert len(found) == 6
-    for name, body in found:
-        meta = asm[asm.index(".amdhsa_kernel " + name):]
-        meta = meta[:meta.index(".end_amdhsa_kernel")]
-        priv = re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", meta)
-        assert priv and int(priv[1]) == 0, (name, priv and priv[1])
-        assert "scratch_" not in body, name
+    from isa_util import assert_no_scratch, device_asm
+    found = assert_no_scratch(device_asm(), (r"k_blocks_touch", r"k_blocks_flag", r"k_blocks_assign", r"k_blocks_fuse", r"k_blocks_count",
+                                             r"k_blocks_emit"), match="search", total=6, body_too=True)
     fuse = found[3][1]
     assert re.search(r"s_load_dwordx(4|8)", fuse)

@@ -8,19 +8,10 @@ import pytest
 import torch
 
 import upkeep_cases as K
+from losses_cases import _not_stale
 from oracle import vm_render_np as onp
 from oracle import vm_render_torch as ot
 from util import field_from_seed, load_golden
-
-
-def _not_stale(table, measured, key):
-    """The recorded and the measured error agree within 2 x.  Below FLOOR / 4 an error does not enter the tolerance
-    (max(4 e32, FLOOR)), and a single float32 result can be exact by chance: both are raised to that before comparing."""
-    assert set(table) == set(measured), key
-    lo = K.FLOOR / 4
-    for q in table:
-        a, b = max(table[q], lo), max(measured[q], lo)
-        assert a <= 2 * b and b <= 2 * a, (key, q, table[q], measured[q])
 
 
 @pytest.mark.parametrize("family,name", [(f, n) for f, (names, _) in K.CHECKS.items() for n in names])
